@@ -276,6 +276,7 @@ class Leg:
         self.cap = 15 * (rl + 2) if all_out else max(65536, rl // 4)
         self.names_buf = C.create_string_buffer(4096)
         self.ms_buf = (C.c_float * 64)()
+        self.last_rec = [None] * self.T                          # the records of each handle's latest tile (views into its score buffer)
 
     def prepare(self, k, host=False):
         R, t = self.Rs[k % self.T], self.tiles[k % self.T]
@@ -294,6 +295,7 @@ class Leg:
         sc = C.c_int64()
         self.lib.dll.uvcgpu_region_last_score_counts(R.h, C.byref(sc), None)
         self.scored = sc.value                                 # records scored (the kept-only form returns fewer)
+        self.last_rec[k % self.T] = rec
         return rec
 
     def kernel_times(self, R, into):
@@ -401,12 +403,34 @@ def score_roofline(ms, npos, n_records, all_out):
             "algorithmic_bytes": needed, "achieved": needed / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": needed / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6     # all files of one dump together, .npy headers included
+NPY_HEADER_BYTES = 4096            # reserved per file: np.save writes a 128-byte header for these 1-D arrays
+
+
+def dump_outputs(out_dir, rec):
+    """The score records of one tile, one DIR/<field>.npy per field: float64 (every field is an integer column, exact below 2**53).  If the
+    files would pass DUMP_MAX_BYTES in all, a fixed seeded sample of the records (the same rows of every field) is written, and its row
+    numbers as _rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(rec["refpos"])
+    per_row = 8 * len(rec)
+    rows = None
+    if n * per_row + NPY_HEADER_BYTES * len(rec) > DUMP_MAX_BYTES:
+        budget = DUMP_MAX_BYTES - NPY_HEADER_BYTES * (len(rec) + 1)     # + 1: _rows.npy
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, budget // (per_row + 8)), replace=False))
+        np.save(os.path.join(out_dir, "_rows.npy"), rows.astype(np.float64))
+    for name, a in rec.items():
+        a = np.asarray(a)
+        assert np.issubdtype(a.dtype, np.integer), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), (a if rows is None else a[rows]).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--repeats", type=int, default=3, help="how many times the timed region of K steps is run; `value` is the median")
+    ap.add_argument("--repeats", type=int, default=1, help="how many times the timed region of K steps is run; `value` is the median (the default 1: --steps K times exactly K steps)")
     ap.add_argument("--tile-kb", type=int, default=1000, help="tile length in kb (chr20 is processed as 1 Mb tiles)")
     ap.add_argument("--tiles", type=int, default=8, help="number of distinct tiles per rank in the stream")
     ap.add_argument("--total-tiles", type=int, default=0, help="STRONG scaling: one job of this many distinct tiles (config 3's shape: a tile list cut into contiguous region shards, "
@@ -420,6 +444,8 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the pcie_inclusive and resident measurements behind the timed region (profiler runs)")
     ap.add_argument("--no-side", action="store_true", help="skip the config-4 and all-out side objects (they need ~1 min of synthetic data generation)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only rehearsal of the launch protocol (no kernels): ranks, barrier, max-over-ranks clock")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records the last timed step returned as DIR/<field>.npy (float64, "
+                                                          "at most 64 MB in all: a seeded sample of the records beyond); with N ranks rank 0's tile only")
     args = ap.parse_args()
     # the validator of the test suite (a sweep over every plane behind each accumulate, ~3 ms per 1 Mb tile) has no place inside a timed step
     if os.environ.pop("UVCGPU_CHECK_PRESENCE", None):
@@ -436,6 +462,8 @@ def main():
     if args.total_tiles > 0 and args.total_tiles < world:
         sys.exit("--total-tiles %d: fewer tiles than ranks (%d): a rank would have nothing to time" % (args.total_tiles, world))
     if args.dry_run:
+        if args.dump_outputs and rank == 0:
+            print("bench.py: --dump-outputs is ignored with --dry-run (no kernels run, nothing is written)", file=sys.stderr)
         clock = shard.Clock(backend="gloo")
         strong_job = None
         if args.total_tiles > 0:   # the strong-scaling cut, as the real run makes it: every tile owned once, every rank owns some
@@ -566,8 +594,9 @@ def main():
 
     run_stream(0, T)              # untimed priming: every handle once (its first set_reads sizes the cached device blocks, its first score page-locks its records buffer)
     run_stream(0, args.warmup)    # the W warmup steps of the contract
-    # the timed region, `--repeats` times (default 3): exactly K steps each, bracketed by barrier + synchronize on both sides, max over ranks;
-    # `value` is the MEDIAN repeat (boxes and runs differ by a few per cent: one 0.2 s region is a sample, not a measurement), all of them are on the line
+    # the timed region, `--repeats` times (default 1, so that --steps K times exactly K steps): K steps each, bracketed by barrier + synchronize
+    # on both sides, max over ranks; `value` is the MEDIAN repeat, all of them are on the line.  By default `value` is therefore one sample:
+    # boxes and runs differ by a few per cent, and a steady figure takes a larger K or --repeats 3
     ktimes = {}
     reps = []
     for rep_ in range(max(1, args.repeats)):
@@ -579,6 +608,9 @@ def main():
         reps.append((clock.max_over_ranks(own_dt), clock.min_over_ranks(own_dt)))
     scored_main = leg.scored
     dt, dt_min = sorted(reps)[len(reps) // 2]
+    if args.dump_outputs and rank == 0:
+        k_last = args.warmup + max(1, args.repeats) * args.steps - 1
+        dump_outputs(args.dump_outputs, leg.last_rec[k_last % T])
     total_positions = (clock.sum_over_ranks(float(region_len) * args.steps) if strong else clock.sum_over_ranks(float(region_len)) * args.steps)
 
     pcie = resident = in_flight4 = None
