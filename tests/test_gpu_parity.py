@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from uvc_amd import synth
-from util import diff_groups, run_region
+from util import diff_groups, presence_violations, run_region
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +35,15 @@ EXACT_FIELDS = ["refpos", "symbol", "refsymbol", "DP", "AD", "bDP", "bAD", "c2DP
                 "cVQAM0", "cVQAM1", "cVQSM0", "cVQSM1", "vAC0", "vAC1", "germ_GT", "germ_emit", "germ_ref", "germ_alt1", "germ_alt2", "out", "NLODV", "FILTER", "keep"]
 PCT_FIELDS = ["cDP1v", "cDP1w", "cDP1x", "cDP2v", "cDP2w", "cDP2x", "CDP1v0", "CDP1v1", "CDP1w0", "CDP1w1", "CDP1x0", "CDP1x1",
               "CDP2v0", "CDP2v1", "CDP2w0", "CDP2w1", "CDP2x0", "CDP2x1"]
+
+
+def set_validator(monkeypatch, validator):
+    """The suite's switch (tests/conftest.py) on -- every accumulate ends in uvcgpu_region_check_presence and a host sync -- or off, the
+    schedule of bench.py and uvc1-mi355x: nothing waits between an accumulate and the next call."""
+    if validator == "on":
+        monkeypatch.setenv("UVCGPU_CHECK_PRESENCE", "1")
+    else:
+        monkeypatch.delenv("UVCGPU_CHECK_PRESENCE", raising=False)
 
 
 def compare_records(ro, rg):
@@ -77,10 +86,12 @@ def test_score_records_match_oracle(name, all_out, oracle_lib, gpu_lib):
     print(name, all_out, len(ro["refpos"]), {k: v for k, v in worst.items() if v})
 
 
+@pytest.mark.parametrize("validator", ["on", "off"])
 @pytest.mark.parametrize("name", ["config2shape_5kb_300x", "umi_duplex_2kb_400x"])
-def test_accumulate_is_repeatable(name, oracle_lib, gpu_lib):
+def test_accumulate_is_repeatable(name, validator, oracle_lib, gpu_lib, monkeypatch):
     """A second accumulate on the same handle (what bench.py times) must reproduce the first: the transient
     bucket planes are not re-zeroed between calls, their consumers (P3b, P5b) have to leave them clean."""
+    set_validator(monkeypatch, validator)
     reads = synth.generate_region(**CASES[name])
     Ro = run_region(oracle_lib, reads)
     Rg = run_region(gpu_lib, reads)
@@ -88,6 +99,8 @@ def test_accumulate_is_repeatable(name, oracle_lib, gpu_lib):
     Rg.accumulate()
     bad = diff_groups(Ro, Rg)
     assert not bad, "\n".join("%s: %d cells differ, e.g. %s" % (g, v[0], v[1]) for g, v in bad.items())
+    if validator == "off":
+        assert presence_violations(Rg) == 0
 
 
 def test_reads_with_many_mismatches_and_indels(oracle_lib, gpu_lib):
@@ -238,10 +251,12 @@ def test_more_than_65535_fragments_on_one_position(oracle_lib, gpu_lib):
     compare_records(Ro.score(), Rg.score())
 
 
-def test_release_state(gpu_lib):
+@pytest.mark.parametrize("validator", ["on", "off"])
+def test_release_state(validator, gpu_lib, monkeypatch):
     """UvcScoreRequest::release_state: the planes are zeroed behind the scoring kernels instead of in front of the next accumulate;
     until then fetch / score refuse, the allele tables stay readable, and the next accumulate gives the same results."""
     from uvc_amd import region
+    set_validator(monkeypatch, validator)
     reads = synth.generate_region(**CASES["config2shape_5kb_300x"])
     R = run_region(gpu_lib, reads)
     planes = {g: R.fetch(g).copy() for g in ("SEG32", "FRAG", "FAM", "VQ", "PREP32")}
@@ -256,13 +271,16 @@ def test_release_state(gpu_lib):
         assert all(np.array_equal(R.fetch(g), planes[g]) for g in planes)
         rec2 = R.score()
         assert all(np.array_equal(rec[k], rec2[k]) for k in rec) and R.indel_alleles() == alleles
+        if validator == "off":
+            assert presence_violations(R) == 0
     # a buffer that is too small: UVCGPU_ENOMEM with the count, and the planes are still there for the second call (region.py retries)
     R.accumulate()
     rec3 = R.score(release_state=True, capacity=8)
     assert all(np.array_equal(rec[k], rec3[k]) for k in rec)
 
 
-def test_reused_handle_same_length_equals_fresh_handles(oracle_lib, gpu_lib):
+@pytest.mark.parametrize("validator", ["on", "off"])
+def test_reused_handle_same_length_equals_fresh_handles(validator, oracle_lib, gpu_lib, monkeypatch):
     """One handle over a run of regions of EQUAL length (what a tile stream does): the zero fill in front of an accumulate then skips the
     (plane family, symbol, block) parts the previous accumulate did not mark (RegionDev::dirty).  Every region's planes must equal the
     oracle's -- a stale cell of the previous region would show -- with and without release_state, and across UMI / InDel-dense / plain reads
@@ -273,6 +291,7 @@ def test_reused_handle_same_length_equals_fresh_handles(oracle_lib, gpu_lib):
              dict(region_len=9000, depth=30, seed=24, err_rate=0.0, indel_every=100000),         # none again
              dict(region_len=9000, depth=50, seed=25, umi=True, indel_every=300)]
     from uvc_amd import region
+    set_validator(monkeypatch, validator)
     R = None
     for k, sp in enumerate(specs):
         reads = synth.generate_region(**sp)
@@ -288,5 +307,7 @@ def test_reused_handle_same_length_equals_fresh_handles(oracle_lib, gpu_lib):
         ro = Ro.score(all_out=True)
         rg = R.score(all_out=True, release_state=(k % 2 == 1))   # every other region hands its planes back with the score call (zeroed on the side stream)
         compare_records(ro, rg)
+        if validator == "off" and k % 2 == 0:
+            assert presence_violations(R) == 0
         Ro.close()
     R.close()

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from uvc_amd import _ffi, region, synth
-from util import run_region
+from util import kept_groups, run_region
 
 REF_SO = os.path.join(_ffi.ROOT, "oracle", "_ref", "libref_vcf.so")
 
@@ -459,28 +459,42 @@ def test_kept_only_records_are_the_groups_the_writer_reads(name, outvar, gpu_lib
     full = R.score()
     kept = R.score(kept_only=True, capacity=64)                  # the caller's buffer only has to hold the kept groups (the mirror grows it on ENOMEM)
     n = len(full["refpos"])
-    is_base = full["symbol"] <= 5
-    head = np.ones(n, bool)
-    head[1:] = (full["refpos"][1:] != full["refpos"][:-1]) | (is_base[1:] != is_base[:-1])
-    gid = np.cumsum(head) - 1
-    written = ((full["keep"] == 1) & (full["out"] == 1)) | (full["germ_emit"] == 1)
-    group_kept = np.zeros(gid.max() + 1, bool)
-    group_kept[gid[written]] = True
-    sel = np.nonzero(group_kept[gid])[0]
+    sel, want = kept_groups(full)
     assert 0 < len(sel) < n and len(kept["refpos"]) == len(sel)
-    new_index = -np.ones(n, np.int64)
-    new_index[sel] = np.arange(len(sel))
     for f in full:
-        want = full[f][sel]
-        if f in ("germ_ref", "germ_alt1", "germ_alt2"):
-            want = np.where(want >= 0, new_index[np.maximum(want, 0)], -1)
-            assert (want[full[f][sel] >= 0] >= 0).all()          # a genotype's records belong to its own group
-        assert np.array_equal(kept[f], want), f
+        assert np.array_equal(kept[f], want[f]), f
     assert R.vcf_records("chr20", kept) == R.vcf_records("chr20", full)
     # all-out: everything is written, nothing to drop but LINK_NN-only groups
     full_a, kept_a = R.score(all_out=True), R.score(all_out=True, kept_only=True)
     assert R.vcf_records("chr20", kept_a) == R.vcf_records("chr20", full_a) and len(kept_a["refpos"]) <= len(full_a["refpos"])
     R.close()
+
+
+@pytest.mark.parametrize("outvar", [None, 63])
+def test_kept_groups_helper_on_oracle_records(outvar, oracle_lib):
+    """util.kept_groups, the expectation of every kept-only test, on the oracle's records: whole groups, exactly those with a written record
+    or a GERMLINE line, in order, and every re-based genotype index names the record the original index named."""
+    reads = synth.generate_region(**HAP_CASES["dense_indels_120x"])
+    p = region.default_params(oracle_lib)
+    if outvar is not None:
+        p.outvar_flag = outvar
+    full = run_region(oracle_lib, reads, params=p).score()
+    sel, kept = kept_groups(full)
+    n = len(full["refpos"])
+    assert 0 < len(sel) < n and (np.diff(sel) > 0).all()
+    key = full["refpos"].astype(np.int64) * 2 + (full["symbol"] > 5)
+    written = ((full["keep"] == 1) & (full["out"] == 1)) | (full["germ_emit"] == 1)
+    assert np.array_equal(sel, np.nonzero(np.isin(key, key[written]))[0])
+    n_links = 0
+    for f in full:
+        if f not in ("germ_ref", "germ_alt1", "germ_alt2"):
+            assert np.array_equal(kept[f], full[f][sel]), f
+            continue
+        has = kept[f] >= 0
+        assert np.array_equal(has, full[f][sel] >= 0), f
+        assert np.array_equal(sel[kept[f][has]], full[f][sel][has]), f
+        n_links += int(has.sum())
+    assert n_links > 0
 
 
 @pytest.mark.gpu

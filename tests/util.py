@@ -1,3 +1,5 @@
+import ctypes as C
+
 import numpy as np
 
 from uvc_amd import _ffi, region, synth
@@ -22,3 +24,40 @@ def diff_groups(Ra, Rb, groups=INT_GROUPS):
             idx = np.argwhere(a != b)
             bad[g] = (len(idx), [(tuple(int(v) for v in i), int(a[tuple(i)]), int(b[tuple(i)])) for i in idx[:8]])
     return bad
+
+
+def kept_groups(full):
+    """What UvcScoreRequest::kept_only returns, made from the records `full` of the same call without it: the (position, symbol type) groups
+    with a written record (keep and out) or a GERMLINE line (germ_emit), whole and in order, with germ_ref / germ_alt1 / germ_alt2 re-based
+    to the record indices of the reduced list.  -> (indices of the kept records in `full`, the expected kept records)."""
+    n = len(full["refpos"])
+    if n == 0:
+        return np.zeros(0, np.int64), {f: v[:0] for f, v in full.items()}
+    is_base = full["symbol"] <= 5
+    head = np.ones(n, bool)
+    head[1:] = (full["refpos"][1:] != full["refpos"][:-1]) | (is_base[1:] != is_base[:-1])
+    gid = np.cumsum(head) - 1
+    written = ((full["keep"] == 1) & (full["out"] == 1)) | (full["germ_emit"] == 1)
+    group_kept = np.zeros(gid.max() + 1, bool)
+    group_kept[gid[written]] = True
+    sel = np.nonzero(group_kept[gid])[0]
+    new_index = -np.ones(n, np.int64)
+    new_index[sel] = np.arange(len(sel))
+    out = {}
+    for f in full:
+        want = full[f][sel]
+        if f in ("germ_ref", "germ_alt1", "germ_alt2"):
+            want = np.where(want >= 0, new_index[np.maximum(want, 0)], -1)
+            assert (want[full[f][sel] >= 0] >= 0).all(), f          # a genotype's records belong to its own group
+        out[f] = want
+    return sel, out
+
+
+def presence_violations(R):
+    """uvcgpu_region_check_presence on the planes the GPU handle R holds (what region.py runs after every accumulate when
+    UVCGPU_CHECK_PRESENCE is set): the number of (position, symbol) cells that contradict the presence statement."""
+    fn = R.lib.dll.uvcgpu_region_check_presence
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]
+    n = C.c_int64(-1)
+    R._check(fn(R.h, C.byref(n)))
+    return int(n.value)

@@ -562,7 +562,9 @@ int uvcgpu_region_read_quals(uvcgpu_region_t *r, uint8_t *dst, int64_t n) {
 struct ZeroPlaneHost { unsigned long long off; int32_t elem; int16_t fam, sym; };
 static int zero_state(uvcgpu_region *r, hipStream_t s) {
     const size_t n_dirty = (size_t)3 * NSYM * (size_t)r->R.ndblk;
-    if (r->dirty_npos == r->npos && !getenv("UVCGPU_FILL_ALL")) {
+    const bool selective = (r->dirty_npos == r->npos && !getenv("UVCGPU_FILL_ALL"));
+    r->dirty_npos = 0;   // from here on the slab and the marks describe no layout until the caller's launch went through and restores it
+    if (selective) {
         if (r->zero_planes_npos != r->npos) {   // the plane table of this layout (once per region length)
             std::vector<ZeroPlaneHost> v;
             const size_t n = (size_t)r->npos;
@@ -599,7 +601,7 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
 static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
     if (!r) return fail(UVCGPU_EINVAL, "null region");
     if (!r->has_reads) return fail(UVCGPU_ENOREADS, "no reads");   // process_batch returns -1, main.cpp:520-523
-    if (r->state_zeroed) HIP_OK(hipStreamWaitEvent(r->stream, r->e_join, 0));   // zeroed behind the last score (release_state)
+    if (r->state_zeroed) { r->dirty_npos = 0; HIP_OK(hipStreamWaitEvent(r->stream, r->e_join, 0)); }   // zeroed behind the last score (release_state)
     else { const int rcz = zero_state(r, r->stream); if (rcz) return rcz; }
     r->state_zeroed = false; r->state_released = false;
     r->buckets_clean = false;
@@ -1107,7 +1109,7 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         else if (rq.release_state && r->side) {   // the scoring kernels are done: zero the planes on the side stream under the D2H of the records
             if (hipEventRecord(r->e_fork, r->stream) == hipSuccess && hipStreamWaitEvent(r->side, r->e_fork, 0) == hipSuccess
                 && zero_state(r, r->side) == 0 && hipEventRecord(r->e_join, r->side) == hipSuccess) {
-                r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes;
+                r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes; r->dirty_npos = r->npos;
             }
         }
         if (!rc && n_out > 0 && (hipMemcpy2DAsync(out->fields, sizeof(int32_t) * out->capacity, src, sizeof(int32_t) * r->score_capacity, sizeof(int32_t) * n_out, UVC_NUM_SCORE_FIELDS, hipMemcpyDeviceToHost, r->stream) != hipSuccess

@@ -1565,7 +1565,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
 __global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, long long ngroups, long long *total_kept, int *err) {
     __shared__ unsigned long long sh_wave[4], sh_prefix;
     __shared__ int sh_tile;
-    const long long n_active = PK_FLAGS(C.offsets[ngroups]);
+    // only the groups that fit the rows (a first kept-only attempt may have more, and is retried): status2 holds min(ngroups, cap) / GS_TILE + 1 tiles
+    const long long n_active = min(PK_FLAGS(C.offsets[ngroups]), (long long)S.cap);
     const int ntiles = (int)((n_active + GS_TILE - 1) / GS_TILE);
     for (;;) {
         if (threadIdx.x == 0) sh_tile = (int)atomicAdd(&S.cnt[CNT_ticket2], 1u);
@@ -1578,7 +1579,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, lon
         for (int i = 0; i < GS_ITEMS; i++) {
             const long long ai = a0 + i;
             long long n = 0;
-            if (ai < n_active && ai < S.cap && GR_(kept, ai)) n = GR_(nrec, ai);   // (a group that did not fit has nrec 0)
+            if (ai < n_active && GR_(kept, ai)) n = GR_(nrec, ai);   // (a group that did not fit has nrec 0)
             v[i] = n; s += (unsigned long long)n;
         }
         unsigned long long total = 0;
@@ -1587,17 +1588,17 @@ __global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, lon
         __syncthreads();
         long long run = (long long)(sh_prefix + excl);
 #pragma unroll
-        for (int i = 0; i < GS_ITEMS; i++) { const long long ai = a0 + i; if (ai < n_active && ai < S.cap) S.keptoff[ai] = (v[i] ? (int32_t)run : -1); run += v[i]; }
+        for (int i = 0; i < GS_ITEMS; i++) { const long long ai = a0 + i; if (ai < n_active) S.keptoff[ai] = (v[i] ? (int32_t)run : -1); run += v[i]; }
         if (tile == ntiles - 1 && threadIdx.x == 0) *total_kept = (long long)(sh_prefix + total);
         __syncthreads();   // sh_tile / sh_prefix / sh_wave are reused by the next tile
     }
 }
 #define KEEP_LANES 8
 __global__ void __launch_bounds__(256) k_keep_copy(ScoreCtx C, Stage S, long long ngroups, int32_t *fields2) {
-    const long long n_active = PK_FLAGS(C.offsets[ngroups]);
+    const long long n_active = min(PK_FLAGS(C.offsets[ngroups]), (long long)S.cap);   // as k_keep_scan
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long ai = t / KEEP_LANES; const int sub = (int)(t % KEEP_LANES);
-    if (ai >= n_active || ai >= S.cap) return;
+    if (ai >= n_active) return;
     const long long q0 = S.keptoff[ai];
     if (q0 < 0) return;
     const long long r0 = GR_(rec0, ai), n = GR_(nrec, ai);
