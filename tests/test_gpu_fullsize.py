@@ -157,7 +157,7 @@ FAM_GROUPS = ("FRAG", "FAM", "FAMINFO32", "DUPLEX", "VQ", "SEG32", "PREP32")
 
 def _umi_tile_planes(gpu_lib, reads, fam_path, monkeypatch):
     if fam_path:
-        monkeypatch.setenv("UVCGPU_FAM_PATH", fam_path)      # read by set_reads: generic = one thread per (unit, position), window = LDS window kernels without the digest
+        monkeypatch.setenv("UVCGPU_FAM_PATH", fam_path)      # read by set_reads: generic = one thread per (unit, position)
     else:
         monkeypatch.delenv("UVCGPU_FAM_PATH", raising=False)
     R = region.Region(gpu_lib, region.default_params(gpu_lib), reads["tid"], reads["beg"], reads["end"], reads["refseq"])
@@ -171,17 +171,16 @@ def _umi_tile_planes(gpu_lib, reads, fam_path, monkeypatch):
     return sums, keep, planes
 
 
-def test_config4_tile_three_forms_of_the_family_kernels_agree(gpu_lib, monkeypatch):
-    """The digest kernels (k_fam_p4d / k_fam_win<5, true> / k_duplex_d, what a deep tile runs by default), the window kernels without the
-    digest and the one-thread-per-(unit, position) kernels are three implementations of P4 / P5 / duplex: at BASELINE config 4's full
+def test_config4_tile_two_forms_of_the_family_kernels_agree(gpu_lib, monkeypatch):
+    """The digest form (k_fam_p4d + k_fam_p4d_rest / k_fam_p5d / k_duplex_d, what a deep tile runs by default) and the generic form (one
+    thread per (unit, position): k_fam_p4 / k_fam_p5 / k_duplex) are two implementations of P4 / P5 / duplex: at BASELINE config 4's full
     tile size they must leave bit-identical planes and identical records.  Plus relations the consensus counters obey by construction."""
     reads = synth.generate_region(seed=4242, region_len=200_000, depth=2000, umi=True)
     assert reads["n_reads"] > 2_000_000 and reads["n_fams"] > 100_000
     base_sums, base_rec, planes = _umi_tile_planes(gpu_lib, reads, None, monkeypatch)
-    for path in ("window", "generic"):
-        sums, rec, _ = _umi_tile_planes(gpu_lib, reads, path, monkeypatch)
-        assert sums == base_sums, path
-        assert all(np.array_equal(rec[k], base_rec[k]) for k in rec), path
+    sums, rec, _ = _umi_tile_planes(gpu_lib, reads, "generic", monkeypatch)
+    assert sums == base_sums
+    assert all(np.array_equal(rec[k], base_rec[k]) for k in rec)
     frag, fam, dup = planes["FRAG"], planes["FAM"], planes["DUPLEX"]
     bdp = frag[:, E["UVC_FRAG_bDP"]]                                          # [strand][symbol][position]
     c12, c1, c2, c3 = (fam[:, E[k]] for k in ("UVC_FAM_cDP12", "UVC_FAM_cDP1", "UVC_FAM_cDP2", "UVC_FAM_cDP3"))

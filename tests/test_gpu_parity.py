@@ -205,6 +205,30 @@ def test_parameter_variants(name, variant, oracle_lib, gpu_lib):
         compare_records(Ro.score(all_out=False), Rg.score(all_out=False))
 
 
+def test_family_of_more_than_16383_fragments_on_the_digest_form(oracle_lib, gpu_lib, monkeypatch, capfd):
+    """The digest of the deep-data family kernels packs the vote counts of a (unit, position) in 14 + 8 bits: a deep duplex-UMI tile plus one
+    molecule whose strand families have more than 16 383 fragments takes the digest form with counts above 14 bits.  Planes bit-exact and
+    records within tolerance against the oracle."""
+    a = synth.generate_region(**CASES["config4shape_1kb_2000x_duplex"])
+    b = synth.generate_region(**dict(CASES["config4shape_1kb_2000x_duplex"], depth=30, fam_mean=17000.0))   # one molecule
+    assert a["refseq"] == b["refseq"]
+    reads = dict(a, n_reads=a["n_reads"] + b["n_reads"], n_fams=a["n_fams"] + b["n_fams"])
+    for k in ("pos", "mpos", "isize", "flag", "mapq", "nm", "l_qseq", "n_cigar", "fam_strand", "bases", "quals", "cigars", "fam_dflag"):
+        reads[k] = np.concatenate([a[k], b[k]])
+    for k, off in (("seq_off", len(a["bases"])), ("cigar_off", len(a["cigars"])), ("frag_id", int(a["frag_id"].max()) + 1), ("fam_id", a["n_fams"])):
+        reads[k] = np.concatenate([a[k], b[k] + off])
+    unit_frags = np.unique(np.stack([reads["fam_id"].astype(np.int64) * 2 + reads["fam_strand"], reads["frag_id"]]), axis=1)[0]
+    assert np.unique(unit_frags, return_counts=True)[1].max() > 16383
+    monkeypatch.setenv("UVCGPU_TIMING", "1")     # set_reads names the family form it chose (stderr)
+    Rg = run_region(gpu_lib, reads)
+    monkeypatch.delenv("UVCGPU_TIMING")
+    assert "family form digest" in capfd.readouterr().err
+    Ro = run_region(oracle_lib, reads)
+    bad = diff_groups(Ro, Rg)
+    assert not bad, "\n".join("%s: %d cells differ, e.g. %s" % (g, vv[0], vv[1]) for g, vv in bad.items())
+    compare_records(Ro.score(all_out=False), Rg.score(all_out=False))
+
+
 def test_score_request_options(oracle_lib, gpu_lib):
     """UvcScoreRequest arms: a sub-range (pos_beg / pos_end), the amplicon minABQ set (main.cpp:524-525), and host-supplied InDel
     alleles (several alleles of one (position, symbol) with their own bDPa / cDP0a / length, main.cpp:853-904)."""

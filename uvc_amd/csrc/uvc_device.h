@@ -19,6 +19,7 @@
 #define MAX_INSERT_SIZE 2000 // common.hpp:64
 #define MAX_STR_N_BASES 100  // common.hpp:63
 #define UVC_MAXEV 8
+#define UVC_DIGEST_MAX_VOTES (1 << 22)   // the family digest packs a vote count in 22 bits: units with fewer fragments (RegionDev::fam_digest)
 
 enum { C_MATCH = 0, C_INS = 1, C_DEL = 2, C_REF_SKIP = 3, C_SOFT_CLIP = 4, C_HARD_CLIP = 5, C_PAD = 6, C_EQUAL = 7, C_DIFF = 8 };
 
@@ -174,13 +175,14 @@ struct RegionDev {
     int32_t *fsum;                  // [2 strands][UVC_FSUM_N][npos]: interval sums of the plain fragments (k_frag_sums), read by k_frag
     FsRec *fss; int32_t n_fs;
     const int32_t *generic_fs; int32_t n_generic_fs; int64_t n_generic_work;
-    const int32_t *generic_sorted; int32_t max_unit_span;   // the generic units ordered by FsRec::beg (window kernels k_fam_win)
+    const int32_t *generic_sorted; int32_t max_unit_span;   // the generic units ordered by FsRec::beg (window kernels k_fam_p4d / k_fam_p5d)
     uint8_t *p5flag;                // [2][npos]: a P5 bucket of this (strand, position) was filled
     uint8_t *dirty; int32_t ndblk;  // [3][NSYM][ndblk]: which (plane family, symbol, block of 4 096 positions) the accumulate wrote outside the part that is zero-filled
                                     // anyway -- family 0: a rare symbol (BASE_NN, every LINK symbol but LINK_M) in the SEG / VQ / BQSUM / FRAG / FAM planes, 1: any symbol in
                                     // FAMINFO32 / 64, 2: any symbol in DUPLEX.  The fill in front of the next accumulate skips what is not marked (uvc_launch_zero_state)
     uint32_t *occ;                  // [npos] bit s: somebody wrote a cell of (s, position) outside the dense-symbol paths (occ_mark); zeroed with the planes, read by the scoring gate
-    uint32_t *fam_digest;           // [n_generic_work][8] or NULL: what P4 leaves per (unit, position) for P5 and the duplex pass (k_fam_win<4> / k_fam_win5d / k_duplex_d)
+    uint32_t *fam_digest;           // [n_generic_work][8]: what P4 leaves per (unit, position) for P5 and the duplex pass (k_fam_p4d / k_fam_p5d / k_duplex_d);
+                                    // set_reads allocates it on deep data, and then the family passes take the digest form; NULL: the generic form
     Contrib *table;
     int32_t *ir_list;               // per InDel read: the positions of its low-quality InDels (k_p2_slow's cursor, main.hpp:1817-1859), [gap_off + 2 * rank .. ) with sentinels
     Item *items; int32_t *item_cnt;     // per complex alignment (indexed like complex_ids)
@@ -189,7 +191,6 @@ struct RegionDev {
     int32_t max_aln_span, max_frag_span;
     int32_t any_amplicon;           // some family carries the amplicon flag (fam_dflag & 0x4)
     int32_t frag32;                 // UVCGPU_FRAG32=1: k_frag with 32-bit buckets although the depth would allow the packed form (tests compare the two)
-    int32_t fam_path;               // 0: the family kernels are chosen from the data; 1 / 2: UVCGPU_FAM_PATH=generic / window (tests compare the three forms)
     int32_t max_frag_depth;         // upper bound of the number of fragments that cover one position
     int32_t *err;                   // device error flag (unsupported CIGAR shapes etc.)
     GapWork gap;                    // InDel allele tables

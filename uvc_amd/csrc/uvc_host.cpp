@@ -400,17 +400,19 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
     R.fss = o.fss; R.n_fs = o.n_fs;
     R.generic_fs = o.generic_fs; R.n_generic_fs = o.n_generic; R.n_generic_work = o.work;
     R.generic_sorted = o.generic_sorted; R.max_unit_span = o.max_unit_span;
+    R.frag32 = (getenv("UVCGPU_FRAG32") != nullptr);
+    // The form of the family passes, decided here once: deep data (more than 8 (unit, position) cells per position) takes the digest form, with
+    // 32 B per cell so that P5 and the duplex pass do not walk the fragments again; shallow data, a digest above 48 GB, a unit with too many
+    // fragments for the digest's vote counts, or UVCGPU_FAM_PATH=generic (the tests' reference form) the generic form.  The two give identical
+    // planes (tests/test_gpu_fullsize.py).
+    const char *fam_path = getenv("UVCGPU_FAM_PATH");
+    const bool generic_forced = (fam_path && !strcmp(fam_path, "generic"));
     R.fam_digest = nullptr;
-    {   // UVCGPU_FAM_PATH=generic | window | (unset: by the data): which form of the family kernels runs -- the three give identical planes (tests/test_gpu_fullsize.py)
-        const char *fp = getenv("UVCGPU_FAM_PATH");
-        R.fam_path = (fp && !strcmp(fp, "generic")) ? 1 : ((fp && !strcmp(fp, "window")) ? 2 : 0);
-        R.frag32 = (getenv("UVCGPU_FRAG32") != nullptr);
-    }
-    if (R.fam_path == 0 && o.work > 8 * r->npos && (size_t)o.work * 32 <= ((size_t)48 << 30) && o.max_unit_frags < 16384) {   // (the digest packs vote counts in 14 bits)
-        // deep data (the window family kernels): 32 B per (unit, position) so that P5 and the duplex pass do not walk the fragments again
+    if (!generic_forced && o.work > 8 * r->npos && (size_t)o.work * 32 <= ((size_t)48 << 30) && o.max_unit_frags < UVC_DIGEST_MAX_VOTES) {
         uint32_t *q = nullptr; if ((rc = dev_alloc(r, (size_t)o.work * 8, &q))) return rc; R.fam_digest = q;
     }
-    if (timing) fprintf(stderr, "[uvcgpu set_reads] %d fragments, %d units, %d generic units, %lld (unit, position) cells, longest unit %d, %lld positions\n", o.n_frags, o.n_fs, o.n_generic, (long long)o.work, o.max_unit_span, (long long)r->npos);
+    if (timing) fprintf(stderr, "[uvcgpu set_reads] %d fragments, %d units, %d generic units, %lld (unit, position) cells, longest unit %d, most fragments in a unit %d, %lld positions, family form %s\n",
+                        o.n_frags, o.n_fs, o.n_generic, (long long)o.work, o.max_unit_span, o.max_unit_frags, (long long)r->npos, R.fam_digest ? "digest" : "generic");
     { Contrib *t; if ((rc = dev_alloc(r, (size_t)std::max<int64_t>(o.table_rows, 1), &t))) return rc; R.table = t; }
     { int32_t *t; if ((rc = dev_alloc(r, (size_t)(o.gap_slots + 2 * (int64_t)o.n_complex + 4), &t))) return rc; R.ir_list = t; }
     { Item *t; if ((rc = dev_alloc(r, (size_t)std::max<int64_t>(o.item_slots, 1), &t))) return rc; R.items = t;

@@ -27,8 +27,10 @@
 //   k_fragstat_*     per fragment   covered / near-mutation position counts, M runs of InDel fragments   main.hpp:2738-2756
 //   k_frag_generic   wave per fragment chunk  P3 at the positions next to InDels / of fragments with > 2 alignments
 //   k_frag           per position   P3 + P3b, and P4/P5 of singleton families                 main.hpp:2620-2830, 2832-3594
-//   k_fam_stat/p4/p5 per (family-strand unit, position): multi-fragment families              main.hpp:2883-3522
-//   k_duplex         per (duplex family, position)                                            main.hpp:3523-3550
+//   k_fam_stat       per generic family-strand unit  medians of read ends, no-strict-bias window main.hpp:2916-2998
+//   k_fam_p4/p5      per (unit, position)  P4 / P5 of multi-fragment families, generic form    main.hpp:2883-3522
+//   k_fam_p4d(_rest)/p5d  per 64-position window  the same on deep data, through a per-cell digest
+//   k_duplex(_d)     per (duplex family, position)  generic form / from the digest             main.hpp:3523-3550
 //   k_p5b            per (position, strand)  bucket -> quality for family consensus           main.hpp:3552-3591
 //   k_gap_keys/alleles/rows  per (family, InDel position)  the allele-keyed counters of the InDel symbols   main.hpp:2710-2717, 3196-3546
 // uvc_launch_accumulate at the end of the file orders them on two streams.
@@ -2476,224 +2478,106 @@ __global__ void __launch_bounds__(64) k_fam_stat(RegionDev R, UvcParams P) {
     R.fss[ui] = u;
 }
 
-// P4 of generic units (main.hpp:2999-3355; consensus FASTQ left out)
-__global__ void __launch_bounds__(256) k_fam_p4(RegionDev R, UvcParams P) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= R.n_generic_work) return;
-    const FsRec u = R.fss[find_unit(R, w)];
-    const int p = u.beg + (int)(w - u.work_off);
-    const int64_t x = p - R.beg;
-    const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
-    const int strand = u.strand;
-    __shared__ int con_s[NSYM][256];
-    const LdsCounts<256> con = { &con_s[0][threadIdx.x] };
-    unit_counts<false>(R, P, u, p, proton, con, con);
-    for (int vi = 0; vi < 2; vi++) {
-        const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-        int cs, cc, ct;
-        fill_consensus(con, cs, cc, ct, st, false, false);
-        if (0 == ct) continue;
-        const bool is_fam_good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
-        mark_sym(R, cs, x);
-        atomicAdd(&FAP(R, strand, UVC_FAM_cDP12, cs, x), 1);
-        if (1 == ct) atomicAdd(&FAP(R, strand, UVC_FAM_cDP21, cs, x), 1);
-        if (!P.inferred_is_vcf_generated) continue;
-        if (is_fam_good) {
-            mark_fi(R, cs, x);
-            atomicAdd(&FAP(R, strand, UVC_FAM_cDP2, cs, x), 1);
-            int rbeg = imin(u.nsb_min, p), rend = imax(u.nsb_max, p);
-            const bool nonconf_middle = (u.l2r_end_median <= (u.r2l_end_median + P.indel_adj_tracklen_dist));
-            if (nonconf_middle && p < u.r2l_end_median) rend = imax(imin(u.l2r_end_median, imin(u.r2l_end_median, rend)), p);
-            if (nonconf_middle && u.l2r_end_median < p) rbeg = imin(imax(u.l2r_end_median, imax(u.r2l_end_median, rbeg)), p);
-            const bool isGap = (UVC_LINK_SYMBOL == st);
-            const int bq = 90, dist = 1024 * 1024;
-            if (((!isGap) && bq >= P.bias_thres_highBQ) || (isGap && dist >= P.bias_thres_highBQ)) {
-                const bool tier2 = (isGap || bq >= P.bias_thres_highBQ);
-                const int l_nb = (int)nnminus(p + 1, rbeg), r_nb = (int)nnminus(rend, p);
-                const int _LPxT = TH(R, UVC_T_aLPxT, x), RPxT = TH(R, UVC_T_aRPxT, x);
-                const int LPxT = (isGap ? _LPxT : imin(_LPxT, RPxT));
-                // indel_len = majority COUNT of one inserted sequence among the unit's fragments (main.hpp:3239-3243): see fam2_ins_len
-                const int indel_len = (is_ins(cs) ? fam2_ins_len(R, P, u, p, con[cs]) : 0);   // (a deletion's count is never read: main.hpp:3245)
-                const bool far = (l_nb + (is_ins(cs) ? (int)nnminus(indel_len, P.microadjust_nobias_pos_indel_maxlen) : 0) >= LPxT) && (r_nb >= RPxT);
-                if (far) {
-                    int LP1 = 0, LP2 = 0, RP1 = 0, RP2 = 0; long long LPL = 0, RPL = 0;
-                    bidir(LP1, LP2, RP1, RP2, LPL, RPL, TH(R, UVC_T_aLP1t, x), TH(R, UVC_T_aLP2t, x), TH(R, UVC_T_aRP1t, x), TH(R, UVC_T_aRP2t, x), l_nb, r_nb, true, 0);
-                    if (LP1) atomicAdd(&FIP(R, UVC_FI_c2LP1, cs, x), LP1);
-                    if (LP2) atomicAdd(&FIP(R, UVC_FI_c2LP2, cs, x), LP2);
-                    if (RP1) atomicAdd(&FIP(R, UVC_FI_c2RP1, cs, x), RP1);
-                    if (RP2) atomicAdd(&FIP(R, UVC_FI_c2RP2, cs, x), RP2);
-                    atomicAdd(&FIP(R, UVC_FI_c2LPL, cs, x), (int)LPL); atomicAdd(&FIP(R, UVC_FI_c2RPL, cs, x), (int)RPL);
-                }
-                if ((int)nnminus(p + 1, u.nsb_min) >= P.bias_thres_strict_c2LRP0) atomicAdd(&FIP(R, UVC_FI_c2LP0, cs, x), 1);
-                if ((int)nnminus(u.nsb_max, p) >= P.bias_thres_strict_c2LRP0) atomicAdd(&FIP(R, UVC_FI_c2RP0, cs, x), 1);
-                const long long baq_last = R.end - 1;
-                const int seg_l_baq = (int)(BAQ1(R, p) - BAQ1(R, lmax((long long)rbeg, nnminus(p, MAX_STR_N_BASES))) + 1);
-                const long long rr = lmin((long long)rend - 1, lmin((long long)p + MAX_STR_N_BASES, baq_last));
-                const int _seg_r_baq = (int)(BAQ1(R, rr) - BAQ1(R, p) + 1);
-                const int seg_r_baq = (isGap ? (int)lmin((long long)_seg_r_baq, BAQ2(R, rr) - BAQ2(R, p) + 7) : _seg_r_baq);
-                const int thres_highBAQ = P.bias_thres_highBAQ + (isGap ? 0 : 3);
-                if (seg_l_baq >= thres_highBAQ && seg_r_baq >= thres_highBAQ) {
-                    int LB1 = 0, LB2 = 0, RB1 = 0, RB2 = 0; long long LBL = 0, RBL = 0;
-                    bidir(LB1, LB2, RB1, RB2, LBL, RBL, P.bias_thres_BAQ1, P.bias_thres_BAQ2, P.bias_thres_BAQ1, P.bias_thres_BAQ2, seg_l_baq, seg_r_baq, tier2, 0);
-                    if (LB1) atomicAdd(&FIP(R, UVC_FI_c2LB1, cs, x), LB1);
-                    if (LB2) atomicAdd(&FIP(R, UVC_FI_c2LB2, cs, x), LB2);
-                    if (RB1) atomicAdd(&FIP(R, UVC_FI_c2RB1, cs, x), RB1);
-                    if (RB2) atomicAdd(&FIP(R, UVC_FI_c2RB2, cs, x), RB2);
-                    add64(&FI64P(R, UVC_FI64_c2LBL, cs, x), LBL); add64(&FI64P(R, UVC_FI64_c2RBL, cs, x), RBL);
-                }
-                atomicAdd(&FIP(R, UVC_FI_c2BQ2, cs, x), 1);
-            }
-        }
-        if (P.fam_thres_dup2add <= ct && (cc * 100 >= ct * P.fam_thres_dup2perc)) atomicAdd(&FAP(R, strand, UVC_FAM_cDP3, cs, x), 1);
-        const int flat = (is_subst(cs) ? P.fam_thres_emperr_all_flat_snv : P.fam_thres_emperr_all_flat_indel);
-        const int perc = (is_subst(cs) ? P.fam_thres_emperr_con_perc_snv : P.fam_thres_emperr_con_perc_indel);
-        if (ct < flat) continue;
-        if (cc * 100 < ct * perc) continue;
-        const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-        int m = 0, M = 0;
-        for (int s = sb; s <= se; s++) if (s != cs) { m += con[s]; M += ct; }
-        mark_sym(R, cs, x);
-        if (m) atomicAdd(&FAP(R, strand, UVC_FAM_cDPm, cs, x), m);
-        atomicAdd(&FAP(R, strand, UVC_FAM_cDPM, cs, x), M);
-    }
-}
-
-// P5 of generic units (main.hpp:3392-3513)
-__global__ void __launch_bounds__(256) k_fam_p5(RegionDev R, UvcParams P) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= R.n_generic_work) return;
-    const FsRec u = R.fss[find_unit(R, w)];
-    const int p = u.beg + (int)(w - u.work_off);
-    const int64_t x = p - R.beg;
-    const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
-    const int strand = u.strand;
-    const bool is_duplex_fam = (0x2 == (u.dflag & 0x2));
-    const bool other_present = (u.other_fs >= 0);
-    const bool will_inc_dscs = is_duplex_fam && other_present;
-    const bool will_inc_sscs = is_duplex_fam && !other_present;
-    __shared__ int con_s[NSYM][256], mmm_s[NSYM][256];
-    const LdsCounts<256> con = { &con_s[0][threadIdx.x] }, mmm = { &mmm_s[0][threadIdx.x] };
-    unit_counts<true>(R, P, u, p, proton, con, mmm);
-    for (int vi = 0; vi < 2; vi++) {
-        const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-        int cs, con_sumBQs, tot_sumBQs;
-        fill_consensus(mmm, cs, con_sumBQs, tot_sumBQs, st, false, false);
-        if (0 == tot_sumBQs) continue;
-        const int con_nfrags = con[cs];
-        int tot_nfrags = 0;
-        const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-        for (int s = sb; s <= se; s++) tot_nfrags += con[s];
-        mark_sym(R, cs, x);
-        atomicAdd(&FAP(R, strand, UVC_FAM_cDP1, cs, x), 1);
-        if (will_inc_sscs && (!will_inc_dscs) && (tot_nfrags >= P.fam_thres_dup1add) && (con_nfrags * 100 >= tot_nfrags * P.fam_thres_dup1perc))
-            atomicAdd(&FAP(R, strand, UVC_FAM_cDPD, cs, x), 1);
-        const int avgBQ = ((0 == tot_nfrags) ? 1 : (con_sumBQs / tot_nfrags));
-        const int majorcount = FAP(R, strand, UVC_FAM_cDPM, cs, x), minorcount = FAP(R, strand, UVC_FAM_cDPm, cs, x);
-        const double prior_weight = 1.0 / (minorcount + 1.0);
-        const double p2p = pow(10.0, (double)(-((float)avgBQ) / 10));   // phred2prob's float cast, main_conversion.hpp:885-888
-        const double prob = (minorcount + prior_weight) / (majorcount + minorcount + prior_weight / p2p);
-        const double realphred = -10 * log(prob) / log(10.0);
-        const int indep_frag_phred = (int)round(((con_nfrags * 2) - tot_nfrags) * realphred);
-        int confam_qual;
-        if (UVC_LINK_SYMBOL == st) confam_qual = imax(1, imin(indep_frag_phred, P.fam_phred_indel_inc_before_barcode_labeling + (int)round(realphred)));
-        else confam_qual = imax(1, imin(indep_frag_phred, (con_sumBQs * 2) - tot_sumBQs));
-        const int max_qual = sscs_phred(P, R.refsym[x], cs) + (!P.tumor_vcf_is_provided ? 0 : 4);
-        const int confam_qual2 = imin(confam_qual, max_qual);
-        if (tot_nfrags >= P.fam_thres_dup1add) {
-            const int pbucket = (max_qual - confam_qual2 + 2) / 4;
-            if (pbucket >= 0 && pbucket < NBUCKETS) { atomicAdd(&BKP(R, strand, cs, pbucket, x), 1); R.p5flag[(size_t)strand * R.npos + x] = 1; }
-        }
-    }
-}
-
-// P4 (PASS 4, main.hpp:2883-3390) and P5 (PASS 5, main.hpp:3392-3513) of the generic units, one block per 64-position window.
-// One thread per (unit, position) with an atomic per increment is bound by the L2 atomic units at depth (deep UMI panels put
-// hundreds of units on a position).  Here the four waves of a block share the units that overlap the window, every lane keeps its
-// position, and the increments of the two dense symbols (reference base, LINK_M) are collected in LDS and written once per position.
+// The increments of the family passes.  FamAcc collects them: a window kernel (a32 set) adds those of its two dense symbols (reference
+// base, LINK_M) in LDS and writes them once per position (fam_flush); without LDS accumulators every increment is a global atomic.
 #define FAMW_SLOTS (2 * UVC_NFAM + UVC_NFAMINFO32)   // [strand][FAM field], then the FamFormatInfoSet i32 fields
 struct FamAcc {
     int (*a32)[FAMW_SLOTS][64]; unsigned long long (*a64)[UVC_NFAMINFO64][64]; int (*bk)[2][NBUCKETS][64];
     const RegionDev *R; int64_t x; int lane, my_ref;
-    DEV int dense(int cs) const { return !a32 ? -1 : (cs == my_ref ? 0 : (cs == UVC_LINK_M ? 1 : -1)); }   // without LDS accumulators (k_fam_p4d_rest) every increment is a global atomic
+    DEV static FamAcc global(const RegionDev &R, int64_t x) { FamAcc A; A.a32 = nullptr; A.a64 = nullptr; A.bk = nullptr; A.R = &R; A.x = x; A.lane = 0; A.my_ref = -1; return A; }
+    DEV int dense(int cs) const { return !a32 ? -1 : (cs == my_ref ? 0 : (cs == UVC_LINK_M ? 1 : -1)); }
     // a window kernel (a32 set) owns its positions: its adds to the planes are L2 atomics of workgroup scope (add_own)
     DEV void gadd(int32_t *p, int v) const { if (a32) add_own(p, v); else atomicAdd(p, v); }
-    DEV void fap(int strand, int f, int cs, int v) const { const int d = dense(cs); if (d >= 0) atomicAdd(&a32[d][strand * UVC_NFAM + f][lane], v); else { mark_sym(*R, cs, x); gadd(&FAP(*R, strand, f, cs, x), v); } }
-    DEV void fi(int f, int cs, int v) const { const int d = dense(cs); if (d >= 0) atomicAdd(&a32[d][2 * UVC_NFAM + f][lane], v); else { occ_mark(*R, cs, x); mark_fi(*R, cs, x); gadd(&FIP(*R, f, cs, x), v); } }
-    DEV void fi64(int f, int cs, long long v) const { const int d = dense(cs); if (d >= 0) atomicAdd(&a64[d][f][lane], (unsigned long long)v); else { occ_mark(*R, cs, x); mark_fi(*R, cs, x); if (a32) add64_own(&FI64P(*R, f, cs, x), v); else add64(&FI64P(*R, f, cs, x), v); } }
+    // the marks of a symbol's cells outside the dense paths (fam_flush marks those), once per (unit, position, symbol) before its increments:
+    // mark for the FAM / bucket planes and the occupancy, fi_mark for the FamFormatInfoSet planes
+    DEV void mark(int cs) const { if (dense(cs) < 0) mark_sym(*R, cs, x); }
+    DEV void fi_mark(int cs) const { if (dense(cs) < 0) mark_fi(*R, cs, x); }
+    DEV void fap(int strand, int f, int cs, int v) const { const int d = dense(cs); if (d >= 0) atomicAdd(&a32[d][strand * UVC_NFAM + f][lane], v); else gadd(&FAP(*R, strand, f, cs, x), v); }
+    DEV void fi(int f, int cs, int v) const { const int d = dense(cs); if (d >= 0) atomicAdd(&a32[d][2 * UVC_NFAM + f][lane], v); else gadd(&FIP(*R, f, cs, x), v); }
+    DEV void fi64(int f, int cs, long long v) const { const int d = dense(cs); if (d >= 0) atomicAdd(&a64[d][f][lane], (unsigned long long)v); else if (a32) add64_own(&FI64P(*R, f, cs, x), v); else add64(&FI64P(*R, f, cs, x), v); }
     DEV void bucket(int strand, int cs, int b) const { const int d = dense(cs); if (d >= 0) atomicAdd(&bk[d][strand][b][lane], 1); else gadd(&BKP(*R, strand, cs, b, x), 1); R->p5flag[(size_t)strand * R->npos + x] = 1; }
 };
 
-// The P4 increments of one (unit, position, symbol type) once the vote consensus (cs = symbol, cc = its votes, ct = all votes) is known
-// (main.hpp:2999-3355); the body of k_fam_win<4> with con[] reduced to what it uses of it.
-// what p4_apply reads of the position alone (thresholds, BAQ prefix sums): loaded once per lane, not once per unit
+// what p4_apply reads of the position alone (thresholds, BAQ prefix sums): a window kernel loads it once per lane, not once per unit
 struct P4Pos { int LPxT, RPxT, LP1t, LP2t, RP1t, RP2t; long long baq1, baq2;
-               const long long *lb1, *lb2; int lb_lo; };   // LB: the two BAQ prefix-sum arrays of [lb_lo, lb_lo + P4_BAQ_WIN) staged in LDS
+               const long long *lb1, *lb2; int lb_lo; };   // k_fam_p4d: the two BAQ prefix-sum arrays of [lb_lo, lb_lo + P4_BAQ_WIN) staged in LDS
 #define P4_BAQ_WIN (64 + 2 * MAX_STR_N_BASES + 2)   // every BAQ index of a window's cells lies within MAX_STR_N_BASES of the window
-template <bool LB = false>
-DEV void p4_apply(const FamAcc &A, const RegionDev &R, const UvcParams &P, const FsRec &u, int p, int64_t x, int st, int cs, int cc, int ct, const P4Pos &Q) {
-    auto baq1_at = [&](long long a) -> long long { if (LB) return Q.lb1[(int)a - Q.lb_lo]; return BAQ1(R, a); };
-    auto baq2_at = [&](long long a) -> long long { if (LB) return Q.lb2[(int)a - Q.lb_lo]; return BAQ2(R, a); };
+DEV P4Pos p4_pos(const RegionDev &R, int p) {
+    const int64_t x = p - R.beg;
+    P4Pos Q;
+    Q.LPxT = TH(R, UVC_T_aLPxT, x); Q.RPxT = TH(R, UVC_T_aRPxT, x); Q.LP1t = TH(R, UVC_T_aLP1t, x); Q.LP2t = TH(R, UVC_T_aLP2t, x); Q.RP1t = TH(R, UVC_T_aRP1t, x); Q.RP2t = TH(R, UVC_T_aRP2t, x);
+    Q.baq1 = BAQ1(R, p); Q.baq2 = BAQ2(R, p);
+    Q.lb1 = nullptr; Q.lb2 = nullptr; Q.lb_lo = 0;
+    return Q;
+}
+
+// The P4 increments of one (unit, position, symbol type) once the vote consensus (cs = symbol, cc = its votes, ct = all votes of the type) is
+// known (main.hpp:2999-3355; consensus FASTQ left out).  Qw: the position's values with the window's BAQ prefix sums in LDS (k_fam_p4d), or
+// NULL: loaded here, for the cells that reach the bias tests only.
+DEV void p4_apply(const FamAcc &A, const RegionDev &R, const UvcParams &P, const FsRec &u, int p, int64_t x, int st, int cs, int cc, int ct, const P4Pos *Qw) {
     const int strand = u.strand;
-    {
-                const bool is_fam_good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
-                A.fap(strand, UVC_FAM_cDP12, cs, 1);
-                if (1 == ct) A.fap(strand, UVC_FAM_cDP21, cs, 1);
-                if (!P.inferred_is_vcf_generated) return;
-                if (is_fam_good) {
-                    A.fap(strand, UVC_FAM_cDP2, cs, 1);
-                    int rbeg = imin(u.nsb_min, p), rend = imax(u.nsb_max, p);
-                    const bool nonconf_middle = (u.l2r_end_median <= (u.r2l_end_median + P.indel_adj_tracklen_dist));
-                    if (nonconf_middle && p < u.r2l_end_median) rend = imax(imin(u.l2r_end_median, imin(u.r2l_end_median, rend)), p);
-                    if (nonconf_middle && u.l2r_end_median < p) rbeg = imin(imax(u.l2r_end_median, imax(u.r2l_end_median, rbeg)), p);
-                    const bool isGap = (UVC_LINK_SYMBOL == st);
-                    const int bq = 90, dist = 1024 * 1024;
-                    if (((!isGap) && bq >= P.bias_thres_highBQ) || (isGap && dist >= P.bias_thres_highBQ)) {
-                        const bool tier2 = (isGap || bq >= P.bias_thres_highBQ);
-                        const int l_nb = (int)nnminus(p + 1, rbeg), r_nb = (int)nnminus(rend, p);
-                        const int _LPxT = Q.LPxT, RPxT = Q.RPxT;
-                        const int LPxT = (isGap ? _LPxT : imin(_LPxT, RPxT));
-                        // indel_len = majority COUNT of one inserted sequence among the unit's fragments (main.hpp:3239-3243): see fam2_ins_len
-                        const int indel_len = (is_ins(cs) ? fam2_ins_len(R, P, u, p, cc) : 0);   // cc = con[cs] of the vote consensus
-                        const bool far = (l_nb + (is_ins(cs) ? (int)nnminus(indel_len, P.microadjust_nobias_pos_indel_maxlen) : 0) >= LPxT) && (r_nb >= RPxT);
-                        if (far) {
-                            int LP1 = 0, LP2 = 0, RP1 = 0, RP2 = 0; long long LPL = 0, RPL = 0;
-                            bidir(LP1, LP2, RP1, RP2, LPL, RPL, Q.LP1t, Q.LP2t, Q.RP1t, Q.RP2t, l_nb, r_nb, true, 0);
-                            if (LP1) A.fi(UVC_FI_c2LP1, cs, LP1);
-                            if (LP2) A.fi(UVC_FI_c2LP2, cs, LP2);
-                            if (RP1) A.fi(UVC_FI_c2RP1, cs, RP1);
-                            if (RP2) A.fi(UVC_FI_c2RP2, cs, RP2);
-                            A.fi(UVC_FI_c2LPL, cs, (int)LPL); A.fi(UVC_FI_c2RPL, cs, (int)RPL);
-                        }
-                        if ((int)nnminus(p + 1, u.nsb_min) >= P.bias_thres_strict_c2LRP0) A.fi(UVC_FI_c2LP0, cs, 1);
-                        if ((int)nnminus(u.nsb_max, p) >= P.bias_thres_strict_c2LRP0) A.fi(UVC_FI_c2RP0, cs, 1);
-                        const long long baq_last = R.end - 1;
-                        const int seg_l_baq = (int)(Q.baq1 - baq1_at(lmax((long long)rbeg, nnminus(p, MAX_STR_N_BASES))) + 1);
-                        const long long rr = lmin((long long)rend - 1, lmin((long long)p + MAX_STR_N_BASES, baq_last));
-                        const int _seg_r_baq = (int)(baq1_at(rr) - Q.baq1 + 1);
-                        const int seg_r_baq = (isGap ? (int)lmin((long long)_seg_r_baq, baq2_at(rr) - Q.baq2 + 7) : _seg_r_baq);
-                        const int thres_highBAQ = P.bias_thres_highBAQ + (isGap ? 0 : 3);
-                        if (seg_l_baq >= thres_highBAQ && seg_r_baq >= thres_highBAQ) {
-                            int LB1 = 0, LB2 = 0, RB1 = 0, RB2 = 0; long long LBL = 0, RBL = 0;
-                            bidir(LB1, LB2, RB1, RB2, LBL, RBL, P.bias_thres_BAQ1, P.bias_thres_BAQ2, P.bias_thres_BAQ1, P.bias_thres_BAQ2, seg_l_baq, seg_r_baq, tier2, 0);
-                            if (LB1) A.fi(UVC_FI_c2LB1, cs, LB1);
-                            if (LB2) A.fi(UVC_FI_c2LB2, cs, LB2);
-                            if (RB1) A.fi(UVC_FI_c2RB1, cs, RB1);
-                            if (RB2) A.fi(UVC_FI_c2RB2, cs, RB2);
-                            A.fi64(UVC_FI64_c2LBL, cs, LBL); A.fi64(UVC_FI64_c2RBL, cs, RBL);
-                        }
-                        A.fi(UVC_FI_c2BQ2, cs, 1);
-                    }
-                }
-                if (P.fam_thres_dup2add <= ct && (cc * 100 >= ct * P.fam_thres_dup2perc)) A.fap(strand, UVC_FAM_cDP3, cs, 1);
-                const int flat = (is_subst(cs) ? P.fam_thres_emperr_all_flat_snv : P.fam_thres_emperr_all_flat_indel);
-                const int perc = (is_subst(cs) ? P.fam_thres_emperr_con_perc_snv : P.fam_thres_emperr_con_perc_indel);
-                if (ct < flat) return;
-                if (cc * 100 < ct * perc) return;
-                const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-                const int m = ct - cc, M = ct * (se - sb);   // sum over the other symbols of the type of (their votes, all votes)
-                if (m) A.fap(strand, UVC_FAM_cDPm, cs, m);
-                A.fap(strand, UVC_FAM_cDPM, cs, M);
+    const bool is_fam_good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
+    A.mark(cs);
+    A.fap(strand, UVC_FAM_cDP12, cs, 1);
+    if (1 == ct) A.fap(strand, UVC_FAM_cDP21, cs, 1);
+    if (!P.inferred_is_vcf_generated) return;
+    if (is_fam_good) {
+        A.fi_mark(cs);
+        A.fap(strand, UVC_FAM_cDP2, cs, 1);
+        int rbeg = imin(u.nsb_min, p), rend = imax(u.nsb_max, p);
+        const bool nonconf_middle = (u.l2r_end_median <= (u.r2l_end_median + P.indel_adj_tracklen_dist));
+        if (nonconf_middle && p < u.r2l_end_median) rend = imax(imin(u.l2r_end_median, imin(u.r2l_end_median, rend)), p);
+        if (nonconf_middle && u.l2r_end_median < p) rbeg = imin(imax(u.l2r_end_median, imax(u.r2l_end_median, rbeg)), p);
+        const bool isGap = (UVC_LINK_SYMBOL == st);
+        const int bq = 90, dist = 1024 * 1024;
+        if (((!isGap) && bq >= P.bias_thres_highBQ) || (isGap && dist >= P.bias_thres_highBQ)) {
+            const bool tier2 = (isGap || bq >= P.bias_thres_highBQ);
+            const P4Pos Q = (Qw ? *Qw : p4_pos(R, p));
+            auto baq1_at = [&](long long a) -> long long { if (Qw) return Q.lb1[(int)a - Q.lb_lo]; return BAQ1(R, a); };
+            auto baq2_at = [&](long long a) -> long long { if (Qw) return Q.lb2[(int)a - Q.lb_lo]; return BAQ2(R, a); };
+            const int l_nb = (int)nnminus(p + 1, rbeg), r_nb = (int)nnminus(rend, p);
+            const int LPxT = (isGap ? Q.LPxT : imin(Q.LPxT, Q.RPxT));
+            // indel_len = majority COUNT of one inserted sequence among the unit's fragments (main.hpp:3239-3243): see fam2_ins_len
+            const int indel_len = (is_ins(cs) ? fam2_ins_len(R, P, u, p, cc) : 0);   // cc = con[cs] of the vote consensus (a deletion's count is never read: main.hpp:3245)
+            const bool far = (l_nb + (is_ins(cs) ? (int)nnminus(indel_len, P.microadjust_nobias_pos_indel_maxlen) : 0) >= LPxT) && (r_nb >= Q.RPxT);
+            if (far) {
+                int LP1 = 0, LP2 = 0, RP1 = 0, RP2 = 0; long long LPL = 0, RPL = 0;
+                bidir(LP1, LP2, RP1, RP2, LPL, RPL, Q.LP1t, Q.LP2t, Q.RP1t, Q.RP2t, l_nb, r_nb, true, 0);
+                if (LP1) A.fi(UVC_FI_c2LP1, cs, LP1);
+                if (LP2) A.fi(UVC_FI_c2LP2, cs, LP2);
+                if (RP1) A.fi(UVC_FI_c2RP1, cs, RP1);
+                if (RP2) A.fi(UVC_FI_c2RP2, cs, RP2);
+                A.fi(UVC_FI_c2LPL, cs, (int)LPL); A.fi(UVC_FI_c2RPL, cs, (int)RPL);
+            }
+            if ((int)nnminus(p + 1, u.nsb_min) >= P.bias_thres_strict_c2LRP0) A.fi(UVC_FI_c2LP0, cs, 1);
+            if ((int)nnminus(u.nsb_max, p) >= P.bias_thres_strict_c2LRP0) A.fi(UVC_FI_c2RP0, cs, 1);
+            const long long baq_last = R.end - 1;
+            const int seg_l_baq = (int)(Q.baq1 - baq1_at(lmax((long long)rbeg, nnminus(p, MAX_STR_N_BASES))) + 1);
+            const long long rr = lmin((long long)rend - 1, lmin((long long)p + MAX_STR_N_BASES, baq_last));
+            const int _seg_r_baq = (int)(baq1_at(rr) - Q.baq1 + 1);
+            const int seg_r_baq = (isGap ? (int)lmin((long long)_seg_r_baq, baq2_at(rr) - Q.baq2 + 7) : _seg_r_baq);
+            const int thres_highBAQ = P.bias_thres_highBAQ + (isGap ? 0 : 3);
+            if (seg_l_baq >= thres_highBAQ && seg_r_baq >= thres_highBAQ) {
+                int LB1 = 0, LB2 = 0, RB1 = 0, RB2 = 0; long long LBL = 0, RBL = 0;
+                bidir(LB1, LB2, RB1, RB2, LBL, RBL, P.bias_thres_BAQ1, P.bias_thres_BAQ2, P.bias_thres_BAQ1, P.bias_thres_BAQ2, seg_l_baq, seg_r_baq, tier2, 0);
+                if (LB1) A.fi(UVC_FI_c2LB1, cs, LB1);
+                if (LB2) A.fi(UVC_FI_c2LB2, cs, LB2);
+                if (RB1) A.fi(UVC_FI_c2RB1, cs, RB1);
+                if (RB2) A.fi(UVC_FI_c2RB2, cs, RB2);
+                A.fi64(UVC_FI64_c2LBL, cs, LBL); A.fi64(UVC_FI64_c2RBL, cs, RBL);
+            }
+            A.fi(UVC_FI_c2BQ2, cs, 1);
+        }
     }
+    if (P.fam_thres_dup2add <= ct && (cc * 100 >= ct * P.fam_thres_dup2perc)) A.fap(strand, UVC_FAM_cDP3, cs, 1);
+    const int flat = (is_subst(cs) ? P.fam_thres_emperr_all_flat_snv : P.fam_thres_emperr_all_flat_indel);
+    const int perc = (is_subst(cs) ? P.fam_thres_emperr_con_perc_snv : P.fam_thres_emperr_con_perc_indel);
+    if (ct < flat) return;
+    if (cc * 100 < ct * perc) return;
+    const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
+    const int m = ct - cc, M = ct * (se - sb);   // sum over the other symbols of the type of (their votes, all votes)
+    if (m) A.fap(strand, UVC_FAM_cDPm, cs, m);
+    A.fap(strand, UVC_FAM_cDPM, cs, M);
 }
 
 // ---- p4_apply for the cells whose consensus symbol is one of the window kernel's two dense symbols (nearly all of them) ----
@@ -2756,36 +2640,158 @@ DEV void p4_apply_dense(const FamAcc &A, int d, const UvcParams &P, const FsRec 
 #undef P4ADD_FI
 }
 
-// DG: P4 leaves a digest per (unit, position) -- the BQ-sum consensus P5 needs and the {1, 1}-threshold vote consensus of the duplex pass --
-// so that the unit's fragments are walked once instead of three times (R.fam_digest, 32 B per cell); P5 then only reads it.
-template <int PASS, bool DG>
-__global__ void __launch_bounds__(256) k_fam_win(RegionDev R, UvcParams P) {
-    __shared__ int con_s[(PASS == 5 && DG) ? 1 : 4][NSYM][(PASS == 5 && DG) ? 1 : 64];
-    __shared__ int mmm_s[((PASS == 5) != DG) ? 4 : 1][NSYM][((PASS == 5) != DG) ? 64 : 1];   // needed by P4 with a digest and by P5 without
-    __shared__ int a32[2][FAMW_SLOTS][64];
-    __shared__ unsigned long long a64[2][UVC_NFAMINFO64][64];
-    __shared__ int bk[PASS == 5 ? 2 : 1][2][NBUCKETS][PASS == 5 ? 64 : 1];
-    __shared__ double p2p_s[PASS == 5 ? 128 : 1];   // phred2prob of every average quality a cell can have: one pow() per value and block, not one per cell
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t x0 = (int64_t)xcd_block() * 64;
-    if (x0 >= R.npos) return;
-    const int w0 = R.beg + (int)x0;
-    // the units whose span can reach this window (sorted by begin)
-    const int lo = win_lo(R, 7, (int)(x0 >> 6)), hi = win_hi(R, 7, (int)(x0 >> 6));
-    if (lo >= hi) return;   // block-uniform
-    for (int i = threadIdx.x; i < 2 * FAMW_SLOTS * 64; i += 256) (&a32[0][0][0])[i] = 0;
-    for (int i = threadIdx.x; i < 2 * UVC_NFAMINFO64 * 64; i += 256) (&a64[0][0][0])[i] = 0ull;
-    if (PASS == 5) for (int i = threadIdx.x; i < 2 * 2 * NBUCKETS * 64; i += 256) (&bk[0][0][0][0])[i] = 0;
-    if (PASS == 5) for (int i = threadIdx.x; i < 128; i += 256) p2p_s[i] = pow(10.0, (double)(-((float)i) / 10));   // the expression of the cell, see below
-    __syncthreads();
-    const int p = w0 + lane;
-    const int64_t x = x0 + lane;
-    const bool valid = x < R.npos;
+// P4 of generic units, the generic form: one thread per (unit, position), every increment a global atomic
+__global__ void __launch_bounds__(256) k_fam_p4(RegionDev R, UvcParams P) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= R.n_generic_work) return;
+    const FsRec u = R.fss[find_unit(R, w)];
+    const int p = u.beg + (int)(w - u.work_off);
+    const int64_t x = p - R.beg;
     const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
-    FamAcc A; A.a32 = a32; A.a64 = a64; A.bk = (int (*)[2][NBUCKETS][64])bk; A.R = &R; A.x = x; A.lane = lane; A.my_ref = (valid ? (int)R.refsym[x] : 0);
-    const LdsCounts<64> con = { &con_s[(PASS == 5 && DG) ? 0 : wv][0][(PASS == 5 && DG) ? 0 : lane] }, mmm = { &mmm_s[((PASS == 5) != DG) ? wv : 0][0][((PASS == 5) != DG) ? lane : 0] };
-    const bool padded_ignored_w = (P.microadjust_padded_deletion_flag & (proton ? 0x2 : 0x1)) != 0;
-    // the unit records of this wave, 64 at a time: one per lane, those that reach the window picked by ballot (see k_fam_p4d)
+    __shared__ int con_s[NSYM][256];
+    const LdsCounts<256> con = { &con_s[0][threadIdx.x] };
+    unit_counts<false>(R, P, u, p, proton, con, con);
+    const FamAcc A = FamAcc::global(R, x);
+    for (int vi = 0; vi < 2; vi++) {
+        const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
+        int cs, cc, ct;
+        fill_consensus(con, cs, cc, ct, st, false, false);
+        if (0 != ct) p4_apply(A, R, P, u, p, x, st, cs, cc, ct, nullptr);
+    }
+}
+
+// The BQ-sum consensus of one symbol type at a (unit, position), with the votes of its symbol and of the whole type: what P5 reads
+struct P5Cons { int cs, con_nfrags, tot_nfrags, con_sumBQs, tot_sumBQs; };
+template <class Arr>
+DEV P5Cons p5_cons(const Arr &con, const Arr &mmm, int st) {
+    P5Cons c;
+    fill_consensus(mmm, c.cs, c.con_sumBQs, c.tot_sumBQs, st, false, false);
+    c.con_nfrags = con[c.cs];
+    c.tot_nfrags = 0;
+    const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
+    for (int s = sb; s <= se; s++) c.tot_nfrags += con[s];
+    return c;
+}
+
+// The empirical family quality of P5 (main.hpp:3472-3488): confam_qual of the consensus c (symbol type st) of a unit on `strand` at x, and the
+// average BQ it starts from.  majorcount / minorcount are complete: P4 ran before.
+// realphred = -10 log10(prob) enters through round(k * realphred) and round(realphred) only.  Given p2p (an LDS table of phred2prob for the
+// average qualities 0..127, see k_fam_p5d), a single-precision evaluation (error of realphred < 1e-5) decides both roundings unless a product
+// lies within its error bound of a half: only then (one wave iteration in ten) the fp64 expression of the reference is evaluated, which a
+// caller without the table always takes.  Two fp64 divisions and a log per cell and symbol type were most of k_fam_p5d.
+DEV int fam_qual(const RegionDev &R, const UvcParams &P, int strand, int64_t x, int st, const P5Cons &c, const double *p2p, int &avgBQ) {
+    avgBQ = ((0 == c.tot_nfrags) ? 1 : (c.con_sumBQs / c.tot_nfrags));
+    const int majorcount = FAP(R, strand, UVC_FAM_cDPM, c.cs, x), minorcount = FAP(R, strand, UVC_FAM_cDPm, c.cs, x);
+    const int kfr = (c.con_nfrags * 2) - c.tot_nfrags;
+    int indep_frag_phred = 0, round_realphred = 0;
+    bool safe = false;
+    if (p2p) {
+        const float wf = __builtin_amdgcn_rcpf((float)minorcount + 1.0f);
+        const float p2pf = ((unsigned)avgBQ < 128u) ? (float)p2p[avgBQ] : 0.0f;
+        const float probf = ((float)minorcount + wf) * __builtin_amdgcn_rcpf((float)majorcount + (float)minorcount + wf * __builtin_amdgcn_rcpf(p2pf));
+        const float rf = -3.0102999566f * __builtin_amdgcn_logf(probf);   // v_log_f32 is log2
+        const float v1 = (float)kfr * rf;
+        const float tol1 = 5.0e-4f + 4.0e-5f * fabsf((float)kfr) + 1.0e-6f * fabsf(v1), tol0 = 5.0e-4f;
+        safe = ((unsigned)avgBQ < 128u) && (majorcount + minorcount < (1 << 22)) && rf > 0.0f && rf < 1000.0f
+               && fabsf(v1 - floorf(v1) - 0.5f) > tol1 && fabsf(rf - floorf(rf) - 0.5f) > tol0;
+        if (safe) { indep_frag_phred = (int)roundf(v1); round_realphred = (int)roundf(rf); }
+    }
+    if (!safe) {
+        const double prior_weight = 1.0 / (minorcount + 1.0);
+        const double p2pd = (p2p && (unsigned)avgBQ < 128u) ? p2p[avgBQ] : pow(10.0, (double)(-((float)avgBQ) / 10));   // phred2prob's float cast, main_conversion.hpp:885-888
+        const double prob = (minorcount + prior_weight) / (majorcount + minorcount + prior_weight / p2pd);
+        const double realphred = -10 * log(prob) / log(10.0);
+        indep_frag_phred = (int)round(kfr * realphred); round_realphred = (int)round(realphred);
+    }
+    if (UVC_LINK_SYMBOL == st) return imax(1, imin(indep_frag_phred, P.fam_phred_indel_inc_before_barcode_labeling + round_realphred));
+    return imax(1, imin(indep_frag_phred, (c.con_sumBQs * 2) - c.tot_sumBQs));
+}
+
+// The P5 increments of one (unit, position, symbol type) (main.hpp:3392-3513): cDP1, cDPD and the quality bucket of the consensus c
+DEV void p5_apply(const FamAcc &A, const RegionDev &R, const UvcParams &P, const FsRec &u, int64_t x, int st, const P5Cons &c, const double *p2p) {
+    if (0 == c.tot_sumBQs) return;
+    const int strand = u.strand;
+    const bool is_duplex_fam = (0x2 == (u.dflag & 0x2));
+    const bool other_present = (u.other_fs >= 0);
+    const bool will_inc_dscs = is_duplex_fam && other_present;
+    const bool will_inc_sscs = is_duplex_fam && !other_present;
+    A.mark(c.cs);
+    A.fap(strand, UVC_FAM_cDP1, c.cs, 1);
+    if (will_inc_sscs && (!will_inc_dscs) && (c.tot_nfrags >= P.fam_thres_dup1add) && (c.con_nfrags * 100 >= c.tot_nfrags * P.fam_thres_dup1perc))
+        A.fap(strand, UVC_FAM_cDPD, c.cs, 1);
+    int avgBQ;
+    const int confam_qual = fam_qual(R, P, strand, x, st, c, p2p, avgBQ);
+    const int max_qual = sscs_phred(P, R.refsym[x], c.cs) + (!P.tumor_vcf_is_provided ? 0 : 4);
+    const int confam_qual2 = imin(confam_qual, max_qual);
+    if (c.tot_nfrags >= P.fam_thres_dup1add) {
+        const int pbucket = (max_qual - confam_qual2 + 2) / 4;
+        if (pbucket >= 0 && pbucket < NBUCKETS) A.bucket(strand, c.cs, pbucket);
+    }
+}
+
+// P5 of generic units, the generic form (main.hpp:3392-3513)
+__global__ void __launch_bounds__(256) k_fam_p5(RegionDev R, UvcParams P) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= R.n_generic_work) return;
+    const FsRec u = R.fss[find_unit(R, w)];
+    const int p = u.beg + (int)(w - u.work_off);
+    const int64_t x = p - R.beg;
+    const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
+    __shared__ int con_s[NSYM][256], mmm_s[NSYM][256];
+    const LdsCounts<256> con = { &con_s[0][threadIdx.x] }, mmm = { &mmm_s[0][threadIdx.x] };
+    unit_counts<true>(R, P, u, p, proton, con, mmm);
+    const FamAcc A = FamAcc::global(R, x);
+    for (int vi = 0; vi < 2; vi++) {
+        const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
+        p5_apply(A, R, P, u, x, st, p5_cons(con, mmm, st), nullptr);
+    }
+}
+
+// ---- the digest form: deep data ----
+// On deep data (many units per position, e.g. UMI panels) the family passes run per 64-position window: the four waves of a block share the
+// units that overlap the window, every lane keeps its position, and the increments of the two dense symbols are collected in LDS (FamAcc).
+// k_fam_p4d (+ k_fam_p4d_rest) walks the fragments of a unit once and leaves a digest per (unit, position) cell -- the BQ-sum consensus P5
+// needs and the {1, 1}-threshold vote consensus of the duplex pass -- which k_fam_p5d and k_duplex_d only read (R.fam_digest, 8 words).
+// Digest words 3 vi .. 3 vi + 2 per symbol type vi (0 = LINK, 1 = BASE): cs | con_nfrags << 4 | tot_nfrags << 18 (the low 14 bits of each
+// count), con_sumBQs, tot_sumBQs; word 6, byte vi: the duplex vote (its symbol | 16 if it votes); word 7, bytes 2 vi and 2 vi + 1: the high 8
+// bits of con_nfrags and tot_nfrags.  A count is at most the unit's fragment count, below UVC_DIGEST_MAX_VOTES (set_reads); P5 reads word 7
+// only for a unit of more than 16 383 fragments.
+DEV int64_t digest_cell(const FsRec &u, int p) { return u.work_off + (int64_t)(p - u.beg); }
+DEV void digest_store(const RegionDev &R, int64_t cell, const P5Cons m[2], const int dcs[2], const int dadj[2]) {
+    uint32_t w[8];
+    w[6] = 0; w[7] = 0;
+    for (int vi = 0; vi < 2; vi++) {
+        w[3 * vi] = (uint32_t)m[vi].cs | (((uint32_t)m[vi].con_nfrags & 16383u) << 4) | ((uint32_t)m[vi].tot_nfrags << 18);
+        w[3 * vi + 1] = (uint32_t)m[vi].con_sumBQs; w[3 * vi + 2] = (uint32_t)m[vi].tot_sumBQs;
+        w[6] |= ((uint32_t)dcs[vi] | ((dadj[vi] >= 1) ? 16u : 0u)) << (8 * vi);
+        w[7] |= (((uint32_t)m[vi].con_nfrags >> 14) | (((uint32_t)m[vi].tot_nfrags >> 14) << 8)) << (16 * vi);
+    }
+    uint4 *dst = (uint4 *)(R.fam_digest + 8 * cell);
+    dst[0] = make_uint4(w[0], w[1], w[2], w[3]); dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+DEV void digest_load(const RegionDev &R, const FsRec &u, int p, P5Cons m[2]) {
+    const uint32_t *src = R.fam_digest + 8 * digest_cell(u, p);
+    const uint4 d0 = *(const uint4 *)src;
+    const uint2 d1 = *(const uint2 *)(src + 4);
+    const uint32_t w7 = (u.frag_end - u.frag_beg > 16383 ? src[7] : 0u);   // (wave-uniform)
+    const uint32_t lo[2] = { d0.x, d0.w };
+    for (int vi = 0; vi < 2; vi++) {
+        const uint32_t hi = w7 >> (16 * vi);
+        m[vi].cs = (int)(lo[vi] & 15u);
+        m[vi].con_nfrags = (int)(((lo[vi] >> 4) & 16383u) | ((hi & 255u) << 14));
+        m[vi].tot_nfrags = (int)((lo[vi] >> 18) | (((hi >> 8) & 255u) << 14));
+    }
+    m[0].con_sumBQs = (int)d0.y; m[0].tot_sumBQs = (int)d0.z; m[1].con_sumBQs = (int)d1.x; m[1].tot_sumBQs = (int)d1.y;
+}
+DEV uint32_t digest_dup_word(const RegionDev &R, int64_t cell) { return R.fam_digest[8 * cell + 6]; }
+DEV bool digest_dup_vote(uint32_t w6, int vi, int &sym) { const uint32_t a = (w6 >> (8 * vi)) & 31u; sym = (int)(a & 15u); return (a & 16u) != 0; }
+
+// Calls f(u) for every unit of this wave's share of a window's units [lo, hi) (window index list 7, by begin; the four waves of a block
+// take every fourth one) that overlaps the window [w0, w0 + 64).  The unit records are read 64 at a time, one per lane; those that reach
+// the window are picked by ballot and their fields broadcast, so a unit that ends in front of the window costs no memory round trip of its
+// own.  u is wave-uniform.
+template <class F>
+DEV void for_window_units(const RegionDev &R, int w0, int lo, int hi, int wv, int lane, F &&f) {
     for (int kb = lo + wv; kb < hi; kb += 4 * 64) {
         int ur[16];
         const int kmine = kb + 4 * lane;
@@ -2797,173 +2803,29 @@ __global__ void __launch_bounds__(256) k_fam_win(RegionDev R, UvcParams P) {
 #pragma unroll
             for (int i = 0; i < 16; i++) ur[i] = 0;
         }
-        unsigned long long todo = __ballot(kmine < hi && ur[3] > w0 && ur[2] < w0 + 64);
-      while (todo) {
-        const int uj = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        FsRec u;
-        u.frag_beg = bcast(ur[0], uj); u.frag_end = bcast(ur[1], uj); u.beg = bcast(ur[2], uj); u.end = bcast(ur[3], uj);
-        u.strand = bcast(ur[4], uj); u.dflag = bcast(ur[5], uj); u.fam = bcast(ur[6], uj); u.generic = bcast(ur[7], uj);
-        u.work_off = (int64_t)(((unsigned long long)(unsigned)bcast(ur[9], uj) << 32) | (unsigned long long)(unsigned)bcast(ur[8], uj));
-        u.l2r_end_median = bcast(ur[10], uj); u.r2l_end_median = bcast(ur[11], uj); u.nsb_min = bcast(ur[12], uj); u.nsb_max = bcast(ur[13], uj);
-        u.other_fs = bcast(ur[14], uj); u.pad_ = 0;
-        if (!(valid && p >= u.beg && p < u.end)) continue;
-        const int strand = u.strand;
-        if (PASS == 4) {
-            if (DG) {
-                // one pass over the unit's fragments serves P4, P5 and the duplex pass: P5 needs the BQ-sum consensus (mmm) and the vote
-                // counts of its symbol, the duplex pass the vote consensus with thresholds {1, 1}; both are left here per (unit, position)
-                unit_counts<true>(R, P, u, p, proton, con, mmm);
-                uint32_t dg[8]; dg[6] = 0; dg[7] = 0;
-                for (int vi = 0; vi < 2; vi++) {
-                    const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-                    int cs, csum, tsum;
-                    fill_consensus(mmm, cs, csum, tsum, st, false, false);
-                    int tot_nfrags = 0;
-                    const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-                    for (int sy = sb; sy <= se; sy++) tot_nfrags += con[sy];
-                    dg[3 * vi] = (uint32_t)cs | ((uint32_t)imin(con[cs], 16383) << 4) | ((uint32_t)imin(tot_nfrags, 16383) << 18);
-                    dg[3 * vi + 1] = (uint32_t)csum; dg[3 * vi + 2] = (uint32_t)tsum;
-                    int ds, dc, dt;
-                    fill_consensus(con, ds, dc, dt, st, false, st == UVC_BASE_SYMBOL && padded_ignored_w);
-                    const int adj = imax(dc * 2, dt) - dt;
-                    dg[6] |= ((uint32_t)ds | ((adj >= 1) ? 16u : 0u)) << (8 * vi);
-                }
-                uint4 *dst = (uint4 *)(R.fam_digest + 8 * (u.work_off + (int64_t)(p - u.beg)));
-                dst[0] = make_uint4(dg[0], dg[1], dg[2], dg[3]); dst[1] = make_uint4(dg[4], dg[5], dg[6], dg[7]);
-            } else unit_counts<false>(R, P, u, p, proton, con, con);
-            for (int vi = 0; vi < 2; vi++) {
-                const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-                int cs, cc, ct;
-                fill_consensus(con, cs, cc, ct, st, false, false);
-                if (0 == ct) continue;
-                const bool is_fam_good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
-                A.fap(strand, UVC_FAM_cDP12, cs, 1);
-                if (1 == ct) A.fap(strand, UVC_FAM_cDP21, cs, 1);
-                if (!P.inferred_is_vcf_generated) continue;
-                if (is_fam_good) {
-                    A.fap(strand, UVC_FAM_cDP2, cs, 1);
-                    int rbeg = imin(u.nsb_min, p), rend = imax(u.nsb_max, p);
-                    const bool nonconf_middle = (u.l2r_end_median <= (u.r2l_end_median + P.indel_adj_tracklen_dist));
-                    if (nonconf_middle && p < u.r2l_end_median) rend = imax(imin(u.l2r_end_median, imin(u.r2l_end_median, rend)), p);
-                    if (nonconf_middle && u.l2r_end_median < p) rbeg = imin(imax(u.l2r_end_median, imax(u.r2l_end_median, rbeg)), p);
-                    const bool isGap = (UVC_LINK_SYMBOL == st);
-                    const int bq = 90, dist = 1024 * 1024;
-                    if (((!isGap) && bq >= P.bias_thres_highBQ) || (isGap && dist >= P.bias_thres_highBQ)) {
-                        const bool tier2 = (isGap || bq >= P.bias_thres_highBQ);
-                        const int l_nb = (int)nnminus(p + 1, rbeg), r_nb = (int)nnminus(rend, p);
-                        const int _LPxT = TH(R, UVC_T_aLPxT, x), RPxT = TH(R, UVC_T_aRPxT, x);
-                        const int LPxT = (isGap ? _LPxT : imin(_LPxT, RPxT));
-                        // indel_len = majority COUNT of one inserted sequence among the unit's fragments (main.hpp:3239-3243): see fam2_ins_len
-                        const int indel_len = (is_ins(cs) ? fam2_ins_len(R, P, u, p, con[cs]) : 0);
-                        const bool far = (l_nb + (is_ins(cs) ? (int)nnminus(indel_len, P.microadjust_nobias_pos_indel_maxlen) : 0) >= LPxT) && (r_nb >= RPxT);
-                        if (far) {
-                            int LP1 = 0, LP2 = 0, RP1 = 0, RP2 = 0; long long LPL = 0, RPL = 0;
-                            bidir(LP1, LP2, RP1, RP2, LPL, RPL, TH(R, UVC_T_aLP1t, x), TH(R, UVC_T_aLP2t, x), TH(R, UVC_T_aRP1t, x), TH(R, UVC_T_aRP2t, x), l_nb, r_nb, true, 0);
-                            if (LP1) A.fi(UVC_FI_c2LP1, cs, LP1);
-                            if (LP2) A.fi(UVC_FI_c2LP2, cs, LP2);
-                            if (RP1) A.fi(UVC_FI_c2RP1, cs, RP1);
-                            if (RP2) A.fi(UVC_FI_c2RP2, cs, RP2);
-                            A.fi(UVC_FI_c2LPL, cs, (int)LPL); A.fi(UVC_FI_c2RPL, cs, (int)RPL);
-                        }
-                        if ((int)nnminus(p + 1, u.nsb_min) >= P.bias_thres_strict_c2LRP0) A.fi(UVC_FI_c2LP0, cs, 1);
-                        if ((int)nnminus(u.nsb_max, p) >= P.bias_thres_strict_c2LRP0) A.fi(UVC_FI_c2RP0, cs, 1);
-                        const long long baq_last = R.end - 1;
-                        const int seg_l_baq = (int)(BAQ1(R, p) - BAQ1(R, lmax((long long)rbeg, nnminus(p, MAX_STR_N_BASES))) + 1);
-                        const long long rr = lmin((long long)rend - 1, lmin((long long)p + MAX_STR_N_BASES, baq_last));
-                        const int _seg_r_baq = (int)(BAQ1(R, rr) - BAQ1(R, p) + 1);
-                        const int seg_r_baq = (isGap ? (int)lmin((long long)_seg_r_baq, BAQ2(R, rr) - BAQ2(R, p) + 7) : _seg_r_baq);
-                        const int thres_highBAQ = P.bias_thres_highBAQ + (isGap ? 0 : 3);
-                        if (seg_l_baq >= thres_highBAQ && seg_r_baq >= thres_highBAQ) {
-                            int LB1 = 0, LB2 = 0, RB1 = 0, RB2 = 0; long long LBL = 0, RBL = 0;
-                            bidir(LB1, LB2, RB1, RB2, LBL, RBL, P.bias_thres_BAQ1, P.bias_thres_BAQ2, P.bias_thres_BAQ1, P.bias_thres_BAQ2, seg_l_baq, seg_r_baq, tier2, 0);
-                            if (LB1) A.fi(UVC_FI_c2LB1, cs, LB1);
-                            if (LB2) A.fi(UVC_FI_c2LB2, cs, LB2);
-                            if (RB1) A.fi(UVC_FI_c2RB1, cs, RB1);
-                            if (RB2) A.fi(UVC_FI_c2RB2, cs, RB2);
-                            A.fi64(UVC_FI64_c2LBL, cs, LBL); A.fi64(UVC_FI64_c2RBL, cs, RBL);
-                        }
-                        A.fi(UVC_FI_c2BQ2, cs, 1);
-                    }
-                }
-                if (P.fam_thres_dup2add <= ct && (cc * 100 >= ct * P.fam_thres_dup2perc)) A.fap(strand, UVC_FAM_cDP3, cs, 1);
-                const int flat = (is_subst(cs) ? P.fam_thres_emperr_all_flat_snv : P.fam_thres_emperr_all_flat_indel);
-                const int perc = (is_subst(cs) ? P.fam_thres_emperr_con_perc_snv : P.fam_thres_emperr_con_perc_indel);
-                if (ct < flat) continue;
-                if (cc * 100 < ct * perc) continue;
-                const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-                int m = 0, M = 0;
-                for (int s = sb; s <= se; s++) if (s != cs) { m += con[s]; M += ct; }
-                if (m) A.fap(strand, UVC_FAM_cDPm, cs, m);
-                A.fap(strand, UVC_FAM_cDPM, cs, M);
-            }
-        } else {
-            const bool is_duplex_fam = (0x2 == (u.dflag & 0x2));
-            const bool other_present = (u.other_fs >= 0);
-            const bool will_inc_dscs = is_duplex_fam && other_present;
-            const bool will_inc_sscs = is_duplex_fam && !other_present;
-            uint4 d0 = make_uint4(0, 0, 0, 0), d1 = make_uint4(0, 0, 0, 0);
-            if (DG) { const uint4 *src = (const uint4 *)(R.fam_digest + 8 * (u.work_off + (int64_t)(p - u.beg))); d0 = src[0]; d1 = src[1]; }
-            else unit_counts<true>(R, P, u, p, proton, con, mmm);
-            for (int vi = 0; vi < 2; vi++) {
-                const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-                int cs, con_sumBQs, tot_sumBQs, con_nfrags, tot_nfrags = 0;
-                if (DG) {
-                    const uint32_t a = (vi == 0 ? d0.x : d0.w);
-                    cs = (int)(a & 15u); con_nfrags = (int)((a >> 4) & 16383u); tot_nfrags = (int)(a >> 18);
-                    con_sumBQs = (int)(vi == 0 ? d0.y : d1.x); tot_sumBQs = (int)(vi == 0 ? d0.z : d1.y);
-                    if (0 == tot_sumBQs) continue;
-                } else {
-                    fill_consensus(mmm, cs, con_sumBQs, tot_sumBQs, st, false, false);
-                    if (0 == tot_sumBQs) continue;
-                    con_nfrags = con[cs];
-                    const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-                    for (int s = sb; s <= se; s++) tot_nfrags += con[s];
-                }
-                A.fap(strand, UVC_FAM_cDP1, cs, 1);
-                if (will_inc_sscs && (!will_inc_dscs) && (tot_nfrags >= P.fam_thres_dup1add) && (con_nfrags * 100 >= tot_nfrags * P.fam_thres_dup1perc))
-                    A.fap(strand, UVC_FAM_cDPD, cs, 1);
-                const int avgBQ = ((0 == tot_nfrags) ? 1 : (con_sumBQs / tot_nfrags));
-                const int majorcount = FAP(R, strand, UVC_FAM_cDPM, cs, x), minorcount = FAP(R, strand, UVC_FAM_cDPm, cs, x);   // complete: P4 ran before
-                // realphred = -10 log10(prob) enters through round(k * realphred) and round(realphred) only.  A single-precision evaluation
-                // (error of realphred < 1e-5) decides both roundings unless a product lies within its error bound of a half: only then (one
-                // wave iteration in ten) the fp64 expression of the reference is evaluated.  Two fp64 divisions and a log per cell and symbol
-                // type were most of this kernel.
-                const int kfr = (con_nfrags * 2) - tot_nfrags;
-                int indep_frag_phred, round_realphred;
-                {
-                    const float wf = __builtin_amdgcn_rcpf((float)minorcount + 1.0f);
-                    const float p2pf = ((unsigned)avgBQ < 128u) ? (float)p2p_s[avgBQ] : 0.0f;
-                    const float probf = ((float)minorcount + wf) * __builtin_amdgcn_rcpf((float)majorcount + (float)minorcount + wf * __builtin_amdgcn_rcpf(p2pf));
-                    const float rf = -3.0102999566f * __builtin_amdgcn_logf(probf);   // v_log_f32 is log2
-                    const float v1 = (float)kfr * rf;
-                    const float tol1 = 5.0e-4f + 4.0e-5f * fabsf((float)kfr) + 1.0e-6f * fabsf(v1), tol0 = 5.0e-4f;
-                    const bool safe = ((unsigned)avgBQ < 128u) && (majorcount + minorcount < (1 << 22)) && rf > 0.0f && rf < 1000.0f
-                                      && fabsf(v1 - floorf(v1) - 0.5f) > tol1 && fabsf(rf - floorf(rf) - 0.5f) > tol0;
-                    if (safe) { indep_frag_phred = (int)roundf(v1); round_realphred = (int)roundf(rf); }
-                    else {
-                        const double prior_weight = 1.0 / (minorcount + 1.0);
-                        const double p2p = ((unsigned)avgBQ < 128u) ? p2p_s[avgBQ] : pow(10.0, (double)(-((float)avgBQ) / 10));   // phred2prob's float cast, main_conversion.hpp:885-888
-                        const double prob = (minorcount + prior_weight) / (majorcount + minorcount + prior_weight / p2p);
-                        const double realphred = -10 * log(prob) / log(10.0);
-                        indep_frag_phred = (int)round(kfr * realphred); round_realphred = (int)round(realphred);
-                    }
-                }
-                int confam_qual;
-                if (UVC_LINK_SYMBOL == st) confam_qual = imax(1, imin(indep_frag_phred, P.fam_phred_indel_inc_before_barcode_labeling + round_realphred));
-                else confam_qual = imax(1, imin(indep_frag_phred, (con_sumBQs * 2) - tot_sumBQs));
-                const int max_qual = sscs_phred(P, R.refsym[x], cs) + (!P.tumor_vcf_is_provided ? 0 : 4);
-                const int confam_qual2 = imin(confam_qual, max_qual);
-                if (tot_nfrags >= P.fam_thres_dup1add) {
-                    const int pbucket = (max_qual - confam_qual2 + 2) / 4;
-                    if (pbucket >= 0 && pbucket < NBUCKETS) A.bucket(strand, cs, pbucket);
-                }
-            }
+        unsigned long long todo = __ballot(kmine < hi && ur[3] > w0 && ur[2] < w0 + 64);   // FsRec::end, FsRec::beg
+        while (todo) {
+            const int uj = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            FsRec u;
+            u.frag_beg = bcast(ur[0], uj); u.frag_end = bcast(ur[1], uj); u.beg = bcast(ur[2], uj); u.end = bcast(ur[3], uj);
+            u.strand = bcast(ur[4], uj); u.dflag = bcast(ur[5], uj); u.fam = bcast(ur[6], uj); u.generic = bcast(ur[7], uj);
+            u.work_off = (int64_t)(((unsigned long long)(unsigned)bcast(ur[9], uj) << 32) | (unsigned long long)(unsigned)bcast(ur[8], uj));
+            u.l2r_end_median = bcast(ur[10], uj); u.r2l_end_median = bcast(ur[11], uj); u.nsb_min = bcast(ur[12], uj); u.nsb_max = bcast(ur[13], uj);
+            u.other_fs = bcast(ur[14], uj); u.pad_ = 0;
+            f(u);
         }
-      }
     }
-    __syncthreads();
-    // one add per non-zero (field, dense symbol, position) of the window
+}
+
+// The LDS accumulators of a window kernel (FamAcc; a64 / bk may be NULL): zeroed before the units, then one add per non-zero (field, dense
+// symbol, position) of the window
+DEV void fam_lds_zero(int (*a32)[FAMW_SLOTS][64], unsigned long long (*a64)[UVC_NFAMINFO64][64], int (*bk)[2][NBUCKETS][64]) {
+    for (int i = threadIdx.x; i < 2 * FAMW_SLOTS * 64; i += 256) (&a32[0][0][0])[i] = 0;
+    if (a64) for (int i = threadIdx.x; i < 2 * UVC_NFAMINFO64 * 64; i += 256) (&a64[0][0][0])[i] = 0ull;
+    if (bk) for (int i = threadIdx.x; i < 2 * 2 * NBUCKETS * 64; i += 256) (&bk[0][0][0][0])[i] = 0;
+}
+DEV void fam_flush(const RegionDev &R, int64_t x0, int (*a32)[FAMW_SLOTS][64], unsigned long long (*a64)[UVC_NFAMINFO64][64], int (*bk)[2][NBUCKETS][64]) {
     for (int i = threadIdx.x; i < 2 * FAMW_SLOTS * 64; i += 256) {
         const int v = (&a32[0][0][0])[i];
         if (!v) continue;
@@ -2973,7 +2835,7 @@ __global__ void __launch_bounds__(256) k_fam_win(RegionDev R, UvcParams P) {
         if (slot < 2 * UVC_NFAM) add_own(&FAP(R, slot / UVC_NFAM, slot % UVC_NFAM, sym, xx), v);
         else { mark_fi(R, sym, xx); add_own(&FIP(R, slot - 2 * UVC_NFAM, sym, xx), v); }
     }
-    for (int i = threadIdx.x; i < 2 * UVC_NFAMINFO64 * 64; i += 256) {
+    if (a64) for (int i = threadIdx.x; i < 2 * UVC_NFAMINFO64 * 64; i += 256) {
         const unsigned long long v = (&a64[0][0][0])[i];
         if (!v) continue;
         const int ln = i & 63, f = (i >> 6) % UVC_NFAMINFO64, d = (i >> 6) / UVC_NFAMINFO64;
@@ -2981,7 +2843,7 @@ __global__ void __launch_bounds__(256) k_fam_win(RegionDev R, UvcParams P) {
         mark_fi(R, (d == 0 ? (int)R.refsym[xx] : UVC_LINK_M), xx);
         add64_own(&FI64P(R, f, (d == 0 ? (int)R.refsym[xx] : UVC_LINK_M), xx), (long long)v);
     }
-    if (PASS == 5) for (int i = threadIdx.x; i < 2 * 2 * NBUCKETS * 64; i += 256) {
+    if (bk) for (int i = threadIdx.x; i < 2 * 2 * NBUCKETS * 64; i += 256) {
         const int v = (&bk[0][0][0][0])[i];
         if (!v) continue;
         const int ln = i & 63, b = (i >> 6) % NBUCKETS, strand = ((i >> 6) / NBUCKETS) % 2, d = (i >> 6) / (2 * NBUCKETS);
@@ -2990,28 +2852,27 @@ __global__ void __launch_bounds__(256) k_fam_win(RegionDev R, UvcParams P) {
     }
 }
 
-// the consensus numbers of a (unit, position) that has a fragment of the general kind: out of line, so that its registers do not count
-// against the occupancy of k_fam_p4d (the call is rare)
+// the consensus numbers of a (unit, position) that has a fragment of the general kind, for k_fam_p4d_rest: per symbol type the vote
+// consensus (vcs, vcc, vct), the BQ-sum consensus (m) and the duplex vote (dcs, dadj)
 DEV void general_unit(const RegionDev &R, const UvcParams &P, const FsRec &u, int p, bool proton, bool padded_ignored,
-                                                int *vcs, int *vcc, int *vct, int *mcs, int *msum, int *mtot, int *mcon, int *dcs, int *dadj) {
+                      int *vcs, int *vcc, int *vct, P5Cons *m, int *dcs, int *dadj) {
     int con_l[NSYM], mmm_l[NSYM];
     unit_counts<true>(R, P, u, p, proton, con_l, mmm_l);
     for (int vi = 0; vi < 2; vi++) {
         const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
         fill_consensus(con_l, vcs[vi], vcc[vi], vct[vi], st, false, false);
-        fill_consensus(mmm_l, mcs[vi], msum[vi], mtot[vi], st, false, false);
-        mcon[vi] = con_l[mcs[vi]];
+        m[vi] = p5_cons(con_l, mmm_l, st);
         int dc, dt;
         fill_consensus(con_l, dcs[vi], dc, dt, st, false, st == UVC_BASE_SYMBOL && padded_ignored);
         dadj[vi] = imax(dc * 2, dt) - dt;
     }
 }
 
-// k_fam_p4d: P4 of the generic units on deep data, writing the digest (see k_fam_win).  Same window structure, but the votes (con) and the
-// BQ sums (mmm) of a (unit, position) live in registers: a fragment of <= 2 simple alignments can only vote for LINK_M and for one of
-// A C G T N, so the updates are a fixed LINK_M add and a select chain over five symbols.  Without the two per-wave LDS count arrays the
-// block needs 17 KiB of LDS instead of 45, and the read-modify-write chains through LDS are gone.  A lane that meets a fragment of the
-// general kind (InDel next to the position, > 2 alignments) redoes its unit through unit_counts<true> on local arrays (rare).
+// k_fam_p4d: P4 of the generic units on deep data, writing the digest.  The votes (con) and the BQ sums (mmm) of a (unit, position) live in
+// registers: a fragment of <= 2 simple alignments can only vote for LINK_M and for one of A C G T N, so the updates are a fixed LINK_M add
+// and a select chain over five symbols.  Without per-wave LDS count arrays the block needs 17 KiB of LDS instead of 45, and the
+// read-modify-write chains through LDS are gone.  A cell under a fragment of the general kind (InDel next to the position, > 2 alignments)
+// is left to k_fam_p4d_rest.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_fam_p4d(RegionDev R, UvcParams P) {
     __shared__ int a32[2][FAMW_SLOTS][64];
     __shared__ unsigned long long a64[2][UVC_NFAMINFO64][64];
@@ -3022,8 +2883,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     const int w0 = R.beg + (int)x0;
     const int lo = win_lo(R, 7, (int)(x0 >> 6)), hi = win_hi(R, 7, (int)(x0 >> 6));
     if (lo >= hi) return;   // block-uniform
-    for (int i = threadIdx.x; i < 2 * FAMW_SLOTS * 64; i += 256) (&a32[0][0][0])[i] = 0;
-    for (int i = threadIdx.x; i < 2 * UVC_NFAMINFO64 * 64; i += 256) (&a64[0][0][0])[i] = 0ull;
+    fam_lds_zero(a32, a64, nullptr);
     // the BAQ prefix sums the position-bias tests of this window can ask for (p4_apply: within MAX_STR_N_BASES of the cell), staged once:
     // six dependent global gathers per (unit, window) otherwise
     const int lb_lo = w0 - MAX_STR_N_BASES - 1;
@@ -3040,32 +2900,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     FamAcc A; A.a32 = a32; A.a64 = a64; A.bk = nullptr; A.R = &R; A.x = x; A.lane = lane; A.my_ref = (valid ? (int)R.refsym[x] : 0);
     const int noindel80 = ((valid && x > 0) ? imin(80, imin(RTRP(R, UVC_RTR_indelphred, x - 1), RTRP(R, UVC_RTR_indelphred, x))) : 80);
     const __amdgpu_buffer_rsrc_t rs = bq_rsrc(R);
-    P4Pos Q = { 0, 0, 0, 0, 0, 0, 0, 0, &baq_s[0][0], &baq_s[1][0], lb_lo };
-    if (valid) { Q.LPxT = TH(R, UVC_T_aLPxT, x); Q.RPxT = TH(R, UVC_T_aRPxT, x); Q.LP1t = TH(R, UVC_T_aLP1t, x); Q.LP2t = TH(R, UVC_T_aLP2t, x); Q.RP1t = TH(R, UVC_T_aRP1t, x); Q.RP2t = TH(R, UVC_T_aRP2t, x);
-                 Q.baq1 = BAQ1(R, p); Q.baq2 = BAQ2(R, p); }
-    // the unit records of this wave, 64 at a time: one per lane, those that reach the window picked by ballot, their fields broadcast --
-    // a unit that ends in front of the window costs no memory round trip of its own
-    for (int kb = lo + wv; kb < hi; kb += 4 * 64) {
-        int ur[16];
-        const int kmine = kb + 4 * lane;
-        if (kmine < hi) {
-            const int4 *q4 = (const int4 *)(R.fss + R.generic_sorted[kmine]);
-#pragma unroll
-            for (int i = 0; i < 4; i++) { const int4 t = q4[i]; ur[4 * i] = t.x; ur[4 * i + 1] = t.y; ur[4 * i + 2] = t.z; ur[4 * i + 3] = t.w; }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; i++) ur[i] = 0;
-        }
-        unsigned long long todo = __ballot(kmine < hi && ur[3] > w0 && ur[2] < w0 + 64);   // FsRec::end, FsRec::beg
-      while (todo) {
-        const int uj = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        FsRec u;
-        u.frag_beg = bcast(ur[0], uj); u.frag_end = bcast(ur[1], uj); u.beg = bcast(ur[2], uj); u.end = bcast(ur[3], uj);
-        u.strand = bcast(ur[4], uj); u.dflag = bcast(ur[5], uj); u.fam = bcast(ur[6], uj); u.generic = bcast(ur[7], uj);
-        u.work_off = (int64_t)(((unsigned long long)(unsigned)bcast(ur[9], uj) << 32) | (unsigned long long)(unsigned)bcast(ur[8], uj));
-        u.l2r_end_median = bcast(ur[10], uj); u.r2l_end_median = bcast(ur[11], uj); u.nsb_min = bcast(ur[12], uj); u.nsb_max = bcast(ur[13], uj);
-        u.other_fs = bcast(ur[14], uj); u.pad_ = 0;
+    P4Pos Q = { 0, 0, 0, 0, 0, 0, 0, 0, nullptr, nullptr, 0 };
+    if (valid) Q = p4_pos(R, p);
+    Q.lb1 = &baq_s[0][0]; Q.lb2 = &baq_s[1][0]; Q.lb_lo = lb_lo;
+    for_window_units(R, w0, lo, hi, wv, lane, [&](const FsRec &u) {
         const bool mine = (valid && p >= u.beg && p < u.end);
         // votes / BQ sums of LINK_M and of A C G T N (registers); the other eight symbols only through the general path
         int cL = 0, mL = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
@@ -3128,65 +2966,37 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
                 }
             }
         }
-        if (!mine) continue;
-        // per symbol type: vote consensus (cs, cc, ct), BQ-sum consensus (ms, msum, mtot) with the votes of its symbol, duplex vote
-        int vcs[2], vcc[2], vct[2], mcs[2], msum[2], mtot[2], mcon[2], dcs[2], dadj[2];
-        if (!general) {
-            // LINK: only LINK_M can be non-zero; an empty type gives the last symbol of the type (fill_consensus starts from it)
-            vcs[0] = (cL > 0 ? UVC_LINK_M : UVC_LINK_NN); vcc[0] = cL; vct[0] = cL;
-            mcs[0] = (mL > 0 ? UVC_LINK_M : UVC_LINK_NN); msum[0] = mL; mtot[0] = mL; mcon[0] = (mL > 0 ? cL : 0);
-            dcs[0] = vcs[0]; dadj[0] = cL;   // imax(2 * cc, ct) - ct with cc == ct
-            // BASE: first maximum in symbol order A C G T N (NN is zero)
-            int bs = UVC_BASE_NN, bc = 0;
-            if (c0 > bc) { bs = 0; bc = c0; } if (c1 > bc) { bs = 1; bc = c1; } if (c2 > bc) { bs = 2; bc = c2; } if (c3 > bc) { bs = 3; bc = c3; } if (c4 > bc) { bs = 4; bc = c4; }
-            vcs[1] = bs; vcc[1] = bc; vct[1] = c0 + c1 + c2 + c3 + c4;
-            int qs = UVC_BASE_NN, qc = 0;
-            if (m0 > qc) { qs = 0; qc = m0; } if (m1 > qc) { qs = 1; qc = m1; } if (m2 > qc) { qs = 2; qc = m2; } if (m3 > qc) { qs = 3; qc = m3; } if (m4 > qc) { qs = 4; qc = m4; }
-            mcs[1] = qs; msum[1] = qc; mtot[1] = m0 + m1 + m2 + m3 + m4;
-            mcon[1] = (qs == 0 ? c0 : qs == 1 ? c1 : qs == 2 ? c2 : qs == 3 ? c3 : qs == 4 ? c4 : 0);
-            // the duplex vote looks at A..T only when padded deletions are ignored (fill_consensus(..., ignore_padded_del)): then the start
-            // symbol is T and N does not take part
-            if (padded_ignored) {
-                int ds = UVC_BASE_T, dc = 0;
-                if (c0 > dc) { ds = 0; dc = c0; } if (c1 > dc) { ds = 1; dc = c1; } if (c2 > dc) { ds = 2; dc = c2; } if (c3 > dc) { ds = 3; dc = c3; }
-                const int dt = c0 + c1 + c2 + c3;
-                dcs[1] = ds; dadj[1] = imax(dc * 2, dt) - dt;
-            } else { dcs[1] = bs; dadj[1] = imax(bc * 2, vct[1]) - vct[1]; }
-        } else continue;   // a cell under a fragment of the general kind: k_fam_p4d_rest writes its digest and its increments
-        uint32_t dg6 = 0;
-        uint32_t dga[2];
-        for (int vi = 0; vi < 2; vi++) {
-            dga[vi] = (uint32_t)mcs[vi] | ((uint32_t)imin(mcon[vi], 16383) << 4) | ((uint32_t)imin(vct[vi], 16383) << 18);
-            dg6 |= ((uint32_t)dcs[vi] | ((dadj[vi] >= 1) ? 16u : 0u)) << (8 * vi);
-        }
-        uint4 *dst = (uint4 *)(R.fam_digest + 8 * (u.work_off + (int64_t)(p - u.beg)));
-        dst[0] = make_uint4(dga[0], (uint32_t)msum[0], (uint32_t)mtot[0], dga[1]); dst[1] = make_uint4((uint32_t)msum[1], (uint32_t)mtot[1], dg6, 0u);
-#ifndef UVC_ABLATE_P4APPLY
+        if (!mine || general) return;   // a cell under a fragment of the general kind: k_fam_p4d_rest writes its digest and its increments
+        // per symbol type: vote consensus (vcs, vcc, vct), BQ-sum consensus (m) with the votes of its symbol and of the type, duplex vote (dcs, dadj)
+        int vcs[2], vcc[2], vct[2], dcs[2], dadj[2];
+        P5Cons m[2];
+        // LINK: only LINK_M can be non-zero; an empty type gives the last symbol of the type (fill_consensus starts from it)
+        vcs[0] = (cL > 0 ? UVC_LINK_M : UVC_LINK_NN); vcc[0] = cL; vct[0] = cL;
+        m[0] = { (mL > 0 ? UVC_LINK_M : UVC_LINK_NN), (mL > 0 ? cL : 0), cL, mL, mL };
+        dcs[0] = vcs[0]; dadj[0] = cL;   // imax(2 * cc, ct) - ct with cc == ct
+        // BASE: first maximum in symbol order A C G T N (NN is zero)
+        int bs = UVC_BASE_NN, bc = 0;
+        if (c0 > bc) { bs = 0; bc = c0; } if (c1 > bc) { bs = 1; bc = c1; } if (c2 > bc) { bs = 2; bc = c2; } if (c3 > bc) { bs = 3; bc = c3; } if (c4 > bc) { bs = 4; bc = c4; }
+        vcs[1] = bs; vcc[1] = bc; vct[1] = c0 + c1 + c2 + c3 + c4;
+        int qs = UVC_BASE_NN, qc = 0;
+        if (m0 > qc) { qs = 0; qc = m0; } if (m1 > qc) { qs = 1; qc = m1; } if (m2 > qc) { qs = 2; qc = m2; } if (m3 > qc) { qs = 3; qc = m3; } if (m4 > qc) { qs = 4; qc = m4; }
+        m[1] = { qs, (qs == 0 ? c0 : qs == 1 ? c1 : qs == 2 ? c2 : qs == 3 ? c3 : qs == 4 ? c4 : 0), vct[1], qc, m0 + m1 + m2 + m3 + m4 };
+        // the duplex vote looks at A..T only when padded deletions are ignored (fill_consensus(..., ignore_padded_del)): then the start
+        // symbol is T and N does not take part
+        if (padded_ignored) {
+            int ds = UVC_BASE_T, dc = 0;
+            if (c0 > dc) { ds = 0; dc = c0; } if (c1 > dc) { ds = 1; dc = c1; } if (c2 > dc) { ds = 2; dc = c2; } if (c3 > dc) { ds = 3; dc = c3; }
+            const int dt = c0 + c1 + c2 + c3;
+            dcs[1] = ds; dadj[1] = imax(dc * 2, dt) - dt;
+        } else { dcs[1] = bs; dadj[1] = imax(bc * 2, vct[1]) - vct[1]; }
+        digest_store(R, digest_cell(u, p), m, dcs, dadj);
         P4Cell W;
         p4_cell(W, R, P, u, p, Q);
-        if (vct[0]) { const int d = A.dense(vcs[0]); if (d >= 0) p4_apply_dense<true>(A, d, P, u, vcc[0], vct[0], Q, W); else p4_apply<true>(A, R, P, u, p, x, UVC_LINK_SYMBOL, vcs[0], vcc[0], vct[0], Q); }
-        if (vct[1]) { const int d = A.dense(vcs[1]); if (d >= 0) p4_apply_dense<false>(A, d, P, u, vcc[1], vct[1], Q, W); else p4_apply<true>(A, R, P, u, p, x, UVC_BASE_SYMBOL, vcs[1], vcc[1], vct[1], Q); }
-#endif
-      }
-    }
+        if (vct[0]) { const int d = A.dense(vcs[0]); if (d >= 0) p4_apply_dense<true>(A, d, P, u, vcc[0], vct[0], Q, W); else p4_apply(A, R, P, u, p, x, UVC_LINK_SYMBOL, vcs[0], vcc[0], vct[0], &Q); }
+        if (vct[1]) { const int d = A.dense(vcs[1]); if (d >= 0) p4_apply_dense<false>(A, d, P, u, vcc[1], vct[1], Q, W); else p4_apply(A, R, P, u, p, x, UVC_BASE_SYMBOL, vcs[1], vcc[1], vct[1], &Q); }
+    });
     __syncthreads();
-    for (int i = threadIdx.x; i < 2 * FAMW_SLOTS * 64; i += 256) {
-        const int v = (&a32[0][0][0])[i];
-        if (!v) continue;
-        const int ln = i & 63, slot = (i >> 6) % FAMW_SLOTS, d = (i >> 6) / FAMW_SLOTS;
-        const int64_t xx = x0 + ln;
-        const int sym = (d == 0 ? (int)R.refsym[xx] : UVC_LINK_M);
-        if (slot < 2 * UVC_NFAM) add_own(&FAP(R, slot / UVC_NFAM, slot % UVC_NFAM, sym, xx), v);
-        else { mark_fi(R, sym, xx); add_own(&FIP(R, slot - 2 * UVC_NFAM, sym, xx), v); }
-    }
-    for (int i = threadIdx.x; i < 2 * UVC_NFAMINFO64 * 64; i += 256) {
-        const unsigned long long v = (&a64[0][0][0])[i];
-        if (!v) continue;
-        const int ln = i & 63, f = (i >> 6) % UVC_NFAMINFO64, d = (i >> 6) / UVC_NFAMINFO64;
-        const int64_t xx = x0 + ln;
-        mark_fi(R, (d == 0 ? (int)R.refsym[xx] : UVC_LINK_M), xx);
-        add64_own(&FI64P(R, f, (d == 0 ? (int)R.refsym[xx] : UVC_LINK_M), xx), (long long)v);
-    }
+    fam_flush(R, x0, a32, a64, nullptr);
 }
 
 // The cells k_fam_p4d leaves out: positions of a unit under a fragment of the general kind (an InDel read, more than two alignments).
@@ -3207,25 +3017,45 @@ __global__ void __launch_bounds__(64) k_fam_p4d_rest(RegionDev R, UvcParams P) {
             general = (p >= ff.v[0] && p < ff.v[1] && (((ff.v[3] & 0x101) != 0) || proton));
         }
         if (!general) continue;
-        int vcs[2], vcc[2], vct[2], mcs[2], msum[2], mtot[2], mcon[2], dcs[2], dadj[2];
-        general_unit(R, P, u, p, proton, padded_ignored, vcs, vcc, vct, mcs, msum, mtot, mcon, dcs, dadj);
-        uint32_t dg6 = 0;
-        uint32_t dga[2];
-        for (int vi = 0; vi < 2; vi++) {
-            dga[vi] = (uint32_t)mcs[vi] | ((uint32_t)imin(mcon[vi], 16383) << 4) | ((uint32_t)imin(vct[vi], 16383) << 18);
-            dg6 |= ((uint32_t)dcs[vi] | ((dadj[vi] >= 1) ? 16u : 0u)) << (8 * vi);
-        }
-        uint4 *dst = (uint4 *)(R.fam_digest + 8 * (u.work_off + (int64_t)(p - u.beg)));
-        dst[0] = make_uint4(dga[0], (uint32_t)msum[0], (uint32_t)mtot[0], dga[1]); dst[1] = make_uint4((uint32_t)msum[1], (uint32_t)mtot[1], dg6, 0u);
-        FamAcc A; A.a32 = nullptr; A.a64 = nullptr; A.bk = nullptr; A.R = &R; A.x = x; A.lane = 0; A.my_ref = -1;
-        P4Pos Q;
-        Q.LPxT = TH(R, UVC_T_aLPxT, x); Q.RPxT = TH(R, UVC_T_aRPxT, x); Q.LP1t = TH(R, UVC_T_aLP1t, x); Q.LP2t = TH(R, UVC_T_aLP2t, x); Q.RP1t = TH(R, UVC_T_aRP1t, x); Q.RP2t = TH(R, UVC_T_aRP2t, x);
-        Q.baq1 = BAQ1(R, p); Q.baq2 = BAQ2(R, p);
+        int vcs[2], vcc[2], vct[2], dcs[2], dadj[2];
+        P5Cons m[2];
+        general_unit(R, P, u, p, proton, padded_ignored, vcs, vcc, vct, m, dcs, dadj);
+        digest_store(R, digest_cell(u, p), m, dcs, dadj);
+        const FamAcc A = FamAcc::global(R, x);
         for (int vi = 0; vi < 2; vi++) {
             if (0 == vct[vi]) continue;
-            p4_apply(A, R, P, u, p, x, (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL), vcs[vi], vcc[vi], vct[vi], Q);
+            p4_apply(A, R, P, u, p, x, (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL), vcs[vi], vcc[vi], vct[vi], nullptr);
         }
     }
+}
+
+// k_fam_p5d: P5 of the generic units on deep data, from the digest k_fam_p4d / k_fam_p4d_rest left
+__global__ void __launch_bounds__(256) k_fam_p5d(RegionDev R, UvcParams P) {
+    __shared__ int a32[2][FAMW_SLOTS][64];
+    __shared__ int bk[2][2][NBUCKETS][64];
+    __shared__ double p2p_s[128];   // phred2prob of every average quality a cell can have: one pow() per value and block, not one per cell
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t x0 = (int64_t)xcd_block() * 64;
+    if (x0 >= R.npos) return;
+    const int w0 = R.beg + (int)x0;
+    const int lo = win_lo(R, 7, (int)(x0 >> 6)), hi = win_hi(R, 7, (int)(x0 >> 6));
+    if (lo >= hi) return;   // block-uniform
+    fam_lds_zero(a32, nullptr, bk);
+    for (int i = threadIdx.x; i < 128; i += 256) p2p_s[i] = pow(10.0, (double)(-((float)i) / 10));   // the fp64 expression of fam_qual
+    __syncthreads();
+    const int p = w0 + lane;
+    const int64_t x = x0 + lane;
+    const bool valid = x < R.npos;
+    FamAcc A; A.a32 = a32; A.a64 = nullptr; A.bk = bk; A.R = &R; A.x = x; A.lane = lane; A.my_ref = (valid ? (int)R.refsym[x] : 0);
+    for_window_units(R, w0, lo, hi, wv, lane, [&](const FsRec &u) {
+        if (!(valid && p >= u.beg && p < u.end)) return;
+        P5Cons m[2];
+        digest_load(R, u, p, m);
+        p5_apply(A, R, P, u, x, UVC_LINK_SYMBOL, m[0], p2p_s);
+        p5_apply(A, R, P, u, x, UVC_BASE_SYMBOL, m[1], p2p_s);
+    });
+    __syncthreads();
+    fam_flush(R, x0, a32, nullptr, bk);
 }
 
 // duplex consensus (main.hpp:3427-3433, 3523-3550): one thread per (strand-0 unit of a duplex family with both strands, position)
@@ -3263,7 +3093,7 @@ __global__ void __launch_bounds__(256) k_duplex(RegionDev R, UvcParams P, const 
     }
 }
 
-// the duplex pass from the digests P4 left (k_fam_win<4, true>): the votes of the two strand units of a duplex family at a position
+// the duplex pass from the digest (k_fam_p4d / k_fam_p4d_rest): the votes of the two strand units of a duplex family at a position
 __global__ void __launch_bounds__(64) k_duplex_d(RegionDev R, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_work) {
     // one wave per duplex family (its strand-0 unit), lanes over the positions of the two units' common span: no search for the family of a
     // (family, position) cell, the two unit records are read once
@@ -3275,14 +3105,12 @@ __global__ void __launch_bounds__(64) k_duplex_d(RegionDev R, const int32_t *dup
     for (int i = (int)threadIdx.x; i < span; i += 64) {
         const int p = pbeg + i;
         const int64_t x = p - R.beg;
-        uint32_t v[2] = { 0, 0 };
-        if (p >= u0.beg && p < u0.end) v[0] = R.fam_digest[8 * (u0.work_off + (int64_t)(p - u0.beg)) + 6];
-        if (p >= u1.beg && p < u1.end) v[1] = R.fam_digest[8 * (u1.work_off + (int64_t)(p - u1.beg)) + 6];
+        const uint32_t w0 = ((p >= u0.beg && p < u0.end) ? digest_dup_word(R, digest_cell(u0, p)) : 0u);
+        const uint32_t w1 = ((p >= u1.beg && p < u1.end) ? digest_dup_word(R, digest_cell(u1, p)) : 0u);
         for (int vi = 0; vi < 2; vi++) {   // fill_consensus over at most two votes: the larger count wins, the smaller symbol on a tie
-            const uint32_t a = (v[0] >> (8 * vi)) & 31u, b = (v[1] >> (8 * vi)) & 31u;
-            const bool va = (a & 16u) != 0, vb = (b & 16u) != 0;
+            int sa, sb;
+            const bool va = digest_dup_vote(w0, vi, sa), vb = digest_dup_vote(w1, vi, sb);
             if (!va && !vb) continue;
-            const int sa = (int)(a & 15u), sb = (int)(b & 15u);
             const int ct = (va ? 1 : 0) + (vb ? 1 : 0);
             const int cs = (va && vb) ? ((sa == sb) ? sa : imin(sa, sb)) : (va ? sa : sb);
             mark_dup(R, cs, x);
@@ -3698,24 +3526,11 @@ __global__ void __launch_bounds__(64) k_hap_units(RegionDev R, UvcParams P, HapW
             unit_counts<true>(R, P, u, p, proton, con, mmm);
             for (int vi = 0; vi < 2; vi++) {
                 const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-                int cs, con_sumBQs, tot_sumBQs;
-                fill_consensus(mmm, cs, con_sumBQs, tot_sumBQs, st, false, false);
-                if (0 == tot_sumBQs) continue;
-                const int con_nfrags = con[cs];
-                int tot_nfrags = 0;
-                const int sb = (st == 0 ? UVC_BASE_A : UVC_LINK_M), se = (st == 0 ? UVC_BASE_NN : UVC_LINK_NN);
-                for (int s2 = sb; s2 <= se; s2++) tot_nfrags += con[s2];
-                // the empirical family quality of P5 (main.hpp:3472-3488), as in k_fam_p5
-                const int avgBQ = ((0 == tot_nfrags) ? 1 : (con_sumBQs / tot_nfrags));
-                const int majorcount = FAP(R, strand, UVC_FAM_cDPM, cs, x), minorcount = FAP(R, strand, UVC_FAM_cDPm, cs, x);
-                const double prior_weight = 1.0 / (minorcount + 1.0);
-                const double p2p = pow(10.0, (double)(-((float)avgBQ) / 10));
-                const double prob = (minorcount + prior_weight) / (majorcount + minorcount + prior_weight / p2p);
-                const double realphred = -10 * log(prob) / log(10.0);
-                const int indep_frag_phred = (int)round(((con_nfrags * 2) - tot_nfrags) * realphred);
-                int confam_qual;
-                if (UVC_LINK_SYMBOL == st) confam_qual = imax(1, imin(indep_frag_phred, P.fam_phred_indel_inc_before_barcode_labeling + (int)round(realphred)));
-                else confam_qual = imax(1, imin(indep_frag_phred, (con_sumBQs * 2) - tot_sumBQs));
+                const P5Cons c = p5_cons(con, mmm, st);
+                if (0 == c.tot_sumBQs) continue;
+                const int cs = c.cs;
+                int avgBQ;
+                const int confam_qual = fam_qual(R, P, strand, x, st, c, nullptr, avgBQ);   // the empirical family quality of P5
                 const bool highBQ = (proton ? (UVC_BASE_SYMBOL == st || imax(confam_qual + 3, avgBQ) >= P.bias_thres_highBQ) : (UVC_LINK_SYMBOL == st || confam_qual >= P.bias_thres_highBQ));
                 if (symbols_mutated(R.refsym[x], cs) && highBQ) {
                     ev1[vi] = true; val[vi] = ((int)x << 4) | cs;
@@ -4007,16 +3822,15 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     }
     if (R->n_generic_fs) {
         if (side) { hipStreamWaitEvent(s, e_stat, 0); hipStreamWaitEvent(s, e_alleles, 0); }   // k_fam_stat's unit records; fam2_ins_len reads what k_gap_alleles left (both ran under k_frag)
-        // shallow data: one thread per (unit, position); deep data (many units per position, e.g. UMI panels): the window kernel, whose
-        // LDS collection removes most of the atomics that bound the per-thread form
-        const bool deep = (R->fam_path == 1 ? false : (R->fam_path == 2 ? true : (R->n_generic_work > 8 * R->npos)));
-        const bool digest = deep && R->fam_digest && P->inferred_is_vcf_generated;   // one walk over the fragments of a unit instead of three
+        // shallow data: the generic form, one thread per (unit, position); deep data (many units per position, e.g. UMI panels): the digest
+        // form, window kernels whose LDS collection removes most of the atomics that bound the per-thread form, and one walk over the
+        // fragments of a unit instead of three.  set_reads chose the form: the digest is allocated for the second.
+        const bool digest = (R->fam_digest != nullptr);
         if (digest) TIMED(prof, "k_fam_p4", { hipLaunchKernelGGL(k_fam_p4d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P);
                                                hipLaunchKernelGGL(k_fam_p4d_rest, dim3(R->n_generic_fs), dim3(64), 0, s, *R, *P); });
-        else if (deep) TIMED(prof, "k_fam_p4", hipLaunchKernelGGL((k_fam_win<4, false>), dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P));
         else TIMED(prof, "k_fam_p4", hipLaunchKernelGGL(k_fam_p4, dim3(nblk(R->n_generic_work, 256)), dim3(256), 0, s, *R, *P));
         if (P->inferred_is_vcf_generated) {
-            if (digest) TIMED(prof, "k_fam_p5", hipLaunchKernelGGL((k_fam_win<5, true>), dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P));
+            if (digest) TIMED(prof, "k_fam_p5", hipLaunchKernelGGL(k_fam_p5d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P));
             else TIMED(prof, "k_fam_p5", hipLaunchKernelGGL(k_fam_p5, dim3(nblk(R->n_generic_work, 256)), dim3(256), 0, s, *R, *P));
             if (n_dup && digest) TIMED(prof, "k_duplex", hipLaunchKernelGGL(k_duplex_d, dim3(n_dup), dim3(64), 0, s, *R, dup_units, n_dup, dup_off, n_dup_work));
             else if (n_dup) TIMED(prof, "k_duplex", hipLaunchKernelGGL(k_duplex, dim3(nblk(n_dup_work, 256)), dim3(256), 0, s, *R, *P, dup_units, n_dup, dup_off, n_dup_work));
