@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- pileup positions scored per second at 300x depth (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
 
 A step = ONE TILE through the whole per-tile hot path, on a stream of DISTINCT synthetic chr20-shaped 300x non-UMI tiles (1 Mb each,
 `--tiles` of them, visited round-robin) whose raw UvcReadSoA columns are resident in HBM when the timed region starts:
@@ -18,15 +18,22 @@ library.  Every rank owns one GPU and its own tiles (different seeds):
 regions shard with no data-path collective, scaling is weak.  value = ranks * tile positions * K / max-over-ranks wall time.
 `--gpus N` without a launcher starts its own N ranks (children are spawned before anything touches a GPU).
 
+A plain run does only what `value` needs: it makes the tiles, primes every handle once, runs the W warm-up and the K timed steps,
+writes --dump-outputs and prints the line.  Everything else is measured behind the timed steps with `--full` only.
+
 Extra objects on the JSON line:
   roofline        dominant kernel of the timed steps: algorithmic bytes per launch / its HIP-event duration on the
                   library's own stream, vs the 8 TB/s HBM peak; `traffic` is REPLAYED from the committed PMC passes (profiles/).
+With --full also:
   cpu_baseline    the CPU oracle (a scalar port of the reference algorithm) on a bounded sample of the same workload shape on the host
                   cores (rank 0, N = 1 only).
   pcie_inclusive  the same stream with the columns starting in (pinned) host memory: uvcgpu_region_set_reads copies them (650 MB per tile)
                   before the device half runs.  Reported beside `value`, never as `value` (inputs resident in HBM is the metric's contract).
   resident        one prepared tile accumulated + scored again and again with nothing overlapped (the round-1 figure): clean per-kernel
                   durations without another tile's kernels beside them.
+  resident_in_flight4  the timed stream again with four tiles in flight on four host threads.
+  config4, all_out, config5  the BASELINE config 4 shape, the all-out series and the config 5 T/N pair on tiles of their own, each with a
+                  cpu_baseline of the same shape (N = 1, default workload only).
 """
 import argparse
 import ctypes as C
@@ -239,12 +246,16 @@ def tumor_keys_of(rec):
 
 
 def _gen_tile(a):
-    from uvc_amd import synth
+    """One synthetic tile in the form its columns are handed over in: BAM's own 4-bit bases and no offset columns (UvcReadSoA::bases4,
+    seq_off = cigar_off = NULL: 530 instead of 712 MB per tile; the library unpacks and scans on the device) unless UVC_BENCH_PLAIN asks for
+    one byte per base + offsets.  Compacted here, in the generator's worker, so that only the compact columns travel back."""
+    from uvc_amd import region, synth
     seed, region_len, depth, beg, umi = a[:5]
     extra = dict(a[5]) if len(a) > 5 else {}
     if os.environ.get("UVC_BENCH_INDEL_EVERY"):   # experiment knob: spacing of the synthetic InDels (0 = none); the default workload does not set it
         extra["indel_every"] = int(os.environ["UVC_BENCH_INDEL_EVERY"])
-    return synth.generate_region(seed=seed, region_len=region_len, depth=depth, beg=beg, umi=umi, **extra)
+    t = synth.generate_region(seed=seed, region_len=region_len, depth=depth, beg=beg, umi=umi, **extra)
+    return t if os.environ.get("UVC_BENCH_PLAIN") else region.compact_form(t)
 
 
 def spawn_ranks(n, argv):
@@ -440,9 +451,11 @@ def main():
     ap.add_argument("--all-out", action="store_true", help="second series of SURVEY 8(d): score every symbol of every position (-A), not only the default-gate candidates")
     ap.add_argument("--all-records", action="store_true", help="D2H of every scored record (the round-1 form) instead of only the record groups the VCF writer reads (UvcScoreRequest::kept_only)")
     ap.add_argument("--serial", action="store_true", help="no pipelining across tiles: preparation, accumulate and score of a tile strictly one after the other")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the pcie_inclusive and resident measurements behind the timed region (profiler runs)")
-    ap.add_argument("--no-side", action="store_true", help="skip the config-4 and all-out side objects (they need ~1 min of synthetic data generation)")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides `value`, behind the timed steps: the CPU baselines, the resident_in_flight4, "
+                                                        "pcie_inclusive and resident legs, and the config4 / all_out / config5 side objects (without it a run does only what `value` needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the resident_in_flight4, pcie_inclusive and resident measurements behind the timed region (profiler runs)")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the config4, all_out and config5 side objects (they need ~1 min of synthetic data generation)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only rehearsal of the launch protocol (no kernels): ranks, barrier, max-over-ranks clock")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records the last timed step returned as DIR/<field>.npy (float64, "
                                                           "at most 64 MB in all: a seeded sample of the records beyond); with N ranks rank 0's tile only")
@@ -489,7 +502,7 @@ def main():
         return
 
     # ---- synthetic tiles (host, before any GPU call so that the generator may fork) ----
-    side = (world == 1) and not (args.no_side or args.no_extras or args.umi or args.all_out or args.tile_kb != 1000 or args.depth != 300)
+    side = args.full and (world == 1) and not (args.no_side or args.no_extras or args.umi or args.all_out or args.tile_kb != 1000 or args.depth != 300)
     t_gen = time.perf_counter()
     # every rank keeps to its own share of the host cores (the generator's workers, the launch thread, the library's pools): N ranks of one node
     # must not oversubscribe each other
@@ -518,39 +531,44 @@ def main():
         specs += [(5000, 200000, args.depth, 1000000, False)]                                   # all-out scoring (-A) tile
         # BASELINE config 5 shape: one tumor (300x) / normal (100x) tile pair over the same reference (same seed: the reference is drawn first), no somatic variants in the normal
         specs += [(6000, region_len, 300, 1000000, False), (6000, region_len, 100, 1000000, False, {"somatic_every": 10 ** 9})]
-    workers = max(1, min(len(specs), 6 if world == 1 else 2, max(1, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2) // max(1, world))))
+    COLS = ("pos", "mpos", "isize", "flag", "mapq", "nm", "l_qseq", "seq_off", "cigar_off", "n_cigar", "frag_id", "fam_id", "fam_strand", "bases", "bases4", "quals", "cigars")
+
+    def init_runtime():
+        import torch
+        # rehearsal of the N-rank path on a one-GPU box: UVC_BENCH_DEVICE puts every rank on one device, UVC_BENCH_CLOCK_BACKEND=gloo keeps the
+        # barrier / max-over-ranks off RCCL (which refuses two ranks on one device); a real run sets neither
+        dev_index = int(os.environ["UVC_BENCH_DEVICE"]) if os.environ.get("UVC_BENCH_DEVICE") else local_rank
+        torch.cuda.set_device(dev_index)
+        clock = shard.Clock(backend=os.environ.get("UVC_BENCH_CLOCK_BACKEND", "nccl"))
+        from uvc_amd import region
+        lib = region.gpu_lib()
+        rc = lib.dll.uvcgpu_init(dev_index)
+        if rc != 0:
+            raise RuntimeError(lib.last_error())
+        lib.dll.uvcgpu_region_last_score_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.dll.uvcgpu_region_set_profiling.argtypes = [C.c_void_p, C.c_int]
+        lib.dll.uvcgpu_region_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int]
+        return torch, dev_index, clock, region, lib
+
+    # one worker per tile up to 8 (the default stream in one round), fewer per rank when N ranks share the node's cores
+    workers = max(1, min(len(specs), 8 if world == 1 else 2, max(1, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2) // max(1, world))))
     if workers > 1:
         from concurrent.futures import ProcessPoolExecutor
         with ProcessPoolExecutor(max_workers=workers) as ex:
-            tiles = list(ex.map(_gen_tile, specs))
+            pending = ex.map(_gen_tile, specs)          # every worker starts here, before anything touches a GPU
+            t_init = time.perf_counter()
+            torch, local_rank, clock, region, lib = init_runtime()    # the HIP runtime and the library start while the workers generate
+            t_init = time.perf_counter() - t_init
+            tiles = list(pending)
     else:
         tiles = [_gen_tile(sp) for sp in specs]
+        t_init = time.perf_counter()
+        torch, local_rank, clock, region, lib = init_runtime()
+        t_init = time.perf_counter() - t_init
     t_gen = time.perf_counter() - t_gen
-
-    # the form the columns are handed over in: BAM's own 4-bit bases and no offset columns (UvcReadSoA::bases4, seq_off = cigar_off = NULL:
-    # 530 instead of 712 MB per tile; the library unpacks and scans on the device) unless UVC_BENCH_PLAIN asks for one byte per base + offsets
-    COLS = ("pos", "mpos", "isize", "flag", "mapq", "nm", "l_qseq", "seq_off", "cigar_off", "n_cigar", "frag_id", "fam_id", "fam_strand", "bases", "bases4", "quals", "cigars")
-    if not os.environ.get("UVC_BENCH_PLAIN"):
-        from uvc_amd import region as _region
-        tiles = [_region.compact_form(t) for t in tiles]
     side_tiles = tiles[n_main:]
     tiles = tiles[:n_main]
-    import torch
-    # rehearsal of the N-rank path on a one-GPU box: UVC_BENCH_DEVICE puts every rank on one device, UVC_BENCH_CLOCK_BACKEND=gloo keeps the
-    # barrier / max-over-ranks off RCCL (which refuses two ranks on one device); a real run sets neither
-    if os.environ.get("UVC_BENCH_DEVICE"):
-        local_rank = int(os.environ["UVC_BENCH_DEVICE"])
-    torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    clock = shard.Clock(backend=os.environ.get("UVC_BENCH_CLOCK_BACKEND", "nccl"))
-    from uvc_amd import region
-    lib = region.gpu_lib()
-    rc = lib.dll.uvcgpu_init(local_rank)
-    if rc != 0:
-        raise RuntimeError(lib.last_error())
-    lib.dll.uvcgpu_region_last_score_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.dll.uvcgpu_region_set_profiling.argtypes = [C.c_void_p, C.c_int]
-    lib.dll.uvcgpu_region_kernel_times.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int]
     params = region.default_params(lib)
 
     # inputs resident in HBM: the columns of every tile + one handle per tile (planes, scratch); the region side arrays are rebuilt from the
@@ -592,7 +610,9 @@ def main():
             return run_in_flight(k0, n_steps, n_thr_value, host=host, ktimes=ktimes)
         return leg.run_stream(k0, n_steps, host=host, ktimes=ktimes, serial=args.serial)
 
+    t_prime = time.perf_counter()
     run_stream(0, T)              # untimed priming: every handle once (its first set_reads sizes the cached device blocks, its first score page-locks its records buffer)
+    t_prime = time.perf_counter() - t_prime
     run_stream(0, args.warmup)    # the W warmup steps of the contract
     # the timed region, `--repeats` times (default 1, so that --steps K times exactly K steps): K steps each, bracketed by barrier + synchronize
     # on both sides, max over ranks; `value` is the MEDIAN repeat, all of them are on the line.  By default `value` is therefore one sample:
@@ -614,7 +634,7 @@ def main():
     total_positions = (clock.sum_over_ranks(float(region_len) * args.steps) if strong else clock.sum_over_ranks(float(region_len)) * args.steps)
 
     pcie = resident = in_flight4 = None
-    if not args.no_extras and not args.serial and T >= 4:
+    if args.full and not args.no_extras and not args.serial and T >= 4:
         # (0) the timed stream again with four tiles in flight on four host threads (inputs resident, same step)
         nf = max(8, min(args.steps, 2 * T))
         run_in_flight(0, 4, 4)
@@ -624,7 +644,7 @@ def main():
         in_flight4 = {"value": clock.sum_over_ranks(float(region_len)) * nf / fdt, "unit": "positions/s", "ms_per_step": 1e3 * fdt / nf, "steps": nf, "tiles_in_flight": 4,
                       "note": "the step of `value` (inputs resident in HBM), the tiles dealt to four host threads as uvc1-mi355x deals them to its workers: the host's launch and read-back "
                               "time of one tile hides under the other tiles' kernels; whole-job aggregate over all ranks, measured behind the timed region"}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (1) the same stream with the columns in pinned host memory: H2D of every column inside the step
         # the columns move into page-locked memory of the library's own (uvcgpu_host_alloc = hipHostMalloc): a numpy array page-locked in place
         # (uvcgpu_pin_host_buffer = hipHostRegister over 4 KiB heap pages) is copied at 29 GB/s on this box, library-owned memory at 57 GB/s
@@ -745,7 +765,7 @@ def main():
                                         "the two tiles in flight overlap differently.  resident.roofline_by_kernel prices both on their undisturbed durations."},
             "kernel_ms": {k: round(v, 4) for k, v in sorted(avg.items(), key=lambda kv: -kv[1])},
             "read_bases_per_s": n_reads_tile * READ_LEN * world * args.steps / dt,
-            "host_prep_s": {"generate": round(t_gen, 2), "columns_to_hbm": round(t_h2d, 3)},
+            "host_prep_s": {"generate": round(t_gen, 2), "runtime_init": round(t_init, 2), "columns_to_hbm": round(t_h2d, 3), "priming": round(t_prime, 2)},
         }
         if score_ms:
             out["roofline_score"] = score_roofline(score_ms, npos_tile, scored_main, args.all_out)
@@ -782,7 +802,7 @@ def main():
                 out["roofline_score"]["undisturbed"] = score_roofline(resident["kernel_ms"]["k_score_all"], npos_tile, scored_main, args.all_out)
                 out["roofline_score"]["note"] = ("kernel_ms = HIP events around the scoring kernels inside the pipelined stream (eleven short launches that queue behind the other tile's kernels: a span, "
                                                  "not a cost); `undisturbed` = the same events with one tile alone on the device (the resident leg)")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = run_cpu_baseline(args.depth)
         print(json.dumps(out))
     if leg.Rs:

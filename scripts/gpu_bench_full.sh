@@ -1,14 +1,15 @@
 #!/bin/bash
-# GPU-box helper: the default bench.py run (every leg) with the key numbers of the line on stdout.
+# GPU-box helper: the default bench.py run with every leg (--full) and the key numbers of the line on stdout; results under $OUT.
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 t0=$(date +%s)
-timeout -k 10 900 python bench.py "$@" > gpurun_out/bench_full.json 2> gpurun_out/bench_full.err || { tail -20 gpurun_out/bench_full.err; exit 3; }
+timeout -k 10 900 python bench.py --full "$@" > $OUT/bench_full.json 2> $OUT/bench_full.err || { tail -20 $OUT/bench_full.err; exit 3; }
 echo "wall $(( $(date +%s) - t0 )) s"
-python3 - <<'PY'
-import json
-j = json.load(open("gpurun_out/bench_full.json"))
+python3 - $OUT/bench_full.json <<'PY'
+import json, sys
+j = json.load(open(sys.argv[1]))
 print("value %.4e ms/step %.3f repeats %s" % (j["value"], j["ms_per_step"], j["repeats"]["ms_per_step"]))
 print("roofline", j["roofline"]["kernel"], round(j["roofline"]["frac"], 4), "|", (j["roofline"]["traffic_source"] or "")[:70])
 rs = j.get("roofline_score")

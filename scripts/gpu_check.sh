@@ -1,16 +1,18 @@
 #!/bin/bash
-# GPU-box helper: full -m gpu test suite, then the default bench (optionally without the CPU baseline).
+# GPU-box helper: full -m gpu test suite, then the default bench with every leg (--full; BENCH_ARGS=--no-cpu-baseline leaves the CPU baseline
+# out); results under $OUT.
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/gpu_tests.log 2>&1
+timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1
 rc=$?
-tail -15 gpurun_out/gpu_tests.log
+tail -15 $OUT/gpu_tests.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 900 python bench.py $BENCH_ARGS > gpurun_out/bench_latest.json 2> gpurun_out/bench_latest.err || { tail -20 gpurun_out/bench_latest.err; exit 3; }
-python - <<'PY'
-import json
-j = json.load(open("gpurun_out/bench_latest.json"))
+timeout -k 10 900 python bench.py --full $BENCH_ARGS > $OUT/bench_latest.json 2> $OUT/bench_latest.err || { tail -20 $OUT/bench_latest.err; exit 3; }
+python - $OUT/bench_latest.json <<'PY'
+import json, sys
+j = json.load(open(sys.argv[1]))
 print("value %.3e pos/s  ms/step %.2f  roofline %s frac %.4f" % (j["value"], j["ms_per_step"], j["roofline"]["kernel"], j["roofline"]["frac"]))
 print(j["kernel_ms"])
 print(j.get("cpu_baseline"))

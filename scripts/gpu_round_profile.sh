@@ -2,7 +2,7 @@
 # GPU-box helper: everything the round's profiles/ directory is made from.
 #   1. rocprofv3 --kernel-trace --stats of the default bench command (summary csv)
 #   2. two PMC passes (FETCH_SIZE, WRITE_SIZE; they do not fit one pass) -> per-kernel HBM-side traffic
-#   3. the default bench.py run with the CPU baseline
+#   3. the default bench.py run with every leg (--full), the CPU baseline among them
 cd "${GRAFT_REPO_ROOT:-.}"
 TAG=${1:-r01}
 OUT=gpurun_out/$TAG
@@ -35,7 +35,7 @@ json.dump(res, open(out + "/traffic.json", "w"), indent=1, sort_keys=True)
 res.pop("_workload"); res.pop("_source_hash")
 for k, v in sorted(res.items(), key=lambda kv: -kv[1]["traffic_bytes_per_launch"])[:12]: print(k, {a: round(b) for a, b in v.items()})
 PY
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 13; }
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 13; }
 cat $OUT/bench.json
 timeout -k 10 900 python3 bench.py --serial --no-cpu-baseline --no-extras > $OUT/bench_serial.json 2>> $OUT/bench.err || exit 14
 rm -rf $OUT/trace $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_SQ_INSTS_VALU

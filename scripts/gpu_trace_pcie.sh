@@ -1,16 +1,18 @@
 #!/bin/bash
 # GPU-box helper: kernel + memory-copy trace of the bench's pcie_inclusive leg (H2D copies against kernels): how busy the copy engine and
-# the compute units are over the leg's steady state.
+# the compute units are over the leg's steady state (--full: the leg runs behind the timed steps); results under $OUT/trace_pcie.
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out/trace_pcie
-rm -rf gpurun_out/trace_pcie/run
+D=${OUT:-bench_out}/trace_pcie
+mkdir -p $D
+rm -rf $D/run
 export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/trace_pcie/run -- python3 bench.py --steps 2 --warmup 0 --tiles 6 --no-cpu-baseline "$@" > gpurun_out/trace_pcie/bench.json 2> gpurun_out/trace_pcie/err.txt
-python3 - <<'PY'
-import csv, glob, json
-j = json.load(open("gpurun_out/trace_pcie/bench.json")); p = j["pcie_inclusive"]; print("pcie_inclusive", p["ms_per_step"], "ms/step over", p["steps"], "steps; value", j["ms_per_step"])
-mc = glob.glob("gpurun_out/trace_pcie/run/**/*memory_copy_trace.csv", recursive=True)[0]
-kt = glob.glob("gpurun_out/trace_pcie/run/**/*kernel_trace.csv", recursive=True)[0]
+timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $D/run -- python3 bench.py --full --steps 2 --warmup 0 --tiles 6 --no-cpu-baseline "$@" > $D/bench.json 2> $D/err.txt
+python3 - $D <<'PY'
+import csv, glob, json, sys
+d = sys.argv[1]
+j = json.load(open(d + "/bench.json")); p = j["pcie_inclusive"]; print("pcie_inclusive", p["ms_per_step"], "ms/step over", p["steps"], "steps; value", j["ms_per_step"])
+mc = glob.glob(d + "/run/**/*memory_copy_trace.csv", recursive=True)[0]
+kt = glob.glob(d + "/run/**/*kernel_trace.csv", recursive=True)[0]
 cp = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Direction"]) for r in csv.DictReader(open(mc))]
 ks = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(kt))]
 big = sorted(c for c in cp if c[1] - c[0] > 2000000 and "HOST_TO_DEVICE" in c[2])   # the quality / base columns
