@@ -15,6 +15,22 @@ def run_region(lib, reads, params=None, platform=1):
     return R
 
 
+def amplicon_stack():
+    """A 70 000-read amplicon stack: every read covers positions 152..209 of a 400 bp region, more than 65 535 fragments on one position."""
+    rng = np.random.default_rng(8)
+    n, L, ref_len, beg = 70000, 60, 400, 7_000_000
+    ref = rng.integers(0, 4, ref_len)
+    start = 150 + rng.integers(0, 3, n)
+    bases = ref[start[:, None] + np.arange(L)[None, :]]
+    err = rng.random((n, L)) < 0.004
+    bases = np.where(err, rng.integers(0, 4, (n, L)), bases).astype(np.uint8)
+    return dict(n_reads=n, pos=(beg + start).astype(np.int32), mpos=np.full(n, -1, np.int32), isize=np.zeros(n, np.int32), flag=np.where(np.arange(n) % 2, 16, 0).astype(np.uint16),
+                mapq=np.full(n, 60, np.uint8), nm=np.full(n, -1, np.int32), l_qseq=np.full(n, L, np.int32), seq_off=(np.arange(n, dtype=np.int64) * L), cigar_off=np.arange(n, dtype=np.int64),
+                n_cigar=np.ones(n, np.int32), frag_id=np.arange(n, dtype=np.int32), fam_id=np.arange(n, dtype=np.int32), fam_strand=(np.arange(n) % 2).astype(np.uint8), n_fams=n,
+                fam_dflag=np.zeros(n, np.uint8), bases=bases.reshape(-1), quals=rng.choice([20, 30, 37], n * L).astype(np.uint8), cigars=np.full(n, (L << 4) | 0, np.uint32),
+                tid=1, beg=beg, end=beg + ref_len, refseq="".join("ACGT"[b] for b in ref))
+
+
 def diff_groups(Ra, Rb, groups=INT_GROUPS):
     """Returns {group: (n_mismatching_cells, first few mismatches)} for groups that differ."""
     bad = {}

@@ -3728,6 +3728,25 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     const char *sp_env = getenv("UVCGPU_SPLIT");
     const long long per_window = (long long)R->n_fast2 * (R->max_p2_span + 64) / (R->npos > 0 ? R->npos : 1);
     const bool split_windows = sp_env ? (atoi(sp_env) != 0) : (R->nwin < 4 * 1024 && per_window >= 1024);
+    const bool proton = (UVC_PLATFORM_IONTORRENT == P->inferred_sequencing_platform);
+    // P2: no IonTorrent values, no amplicon-flagged family, no primer length, median read length at or above
+    // microadjust_median_readlen_thres: the specialisation without those arms
+    const bool p2_plain = !proton && !R->any_amplicon && !(P->primerlen > 0 && !(0x2 & P->primer_flag)) && (P->central_readlen >= P->microadjust_median_readlen_thres);
+    // P3: no IonTorrent values, no SSCS table cap, no padded deletions
+    const bool frag_plain = P->inferred_is_vcf_generated && !proton && !(0x1 & P->fam_flag) && !(P->microadjust_padded_deletion_flag & 0x1);
+    const bool h16 = (R->max_frag_depth < 65536) && !R->frag32;   // two 16-bit bucket counters per LDS word
+    const bool digest = (R->fam_digest != nullptr);              // set_reads chose the form of the family passes
+    const int n_gen = proton ? R->n_frags : R->n_sweep;          // fragments of k_frag_generic: all of them on IonTorrent, else the sweep list
+    if (getenv("UVCGPU_TIMING")) {   // the form each pass takes, "none" where it is not launched (tests/test_gpu_kernel_forms.py parses this line)
+        const bool vcf = P->inferred_is_vcf_generated, fam = (R->n_generic_fs > 0);
+        fprintf(stderr, "[uvcgpu accumulate] forms prep=%s p2=%s%s frag=%s,%s,%s family=%s duplex=%s frag_generic=%s\n",
+                !vcf ? "none" : split_windows ? "split" : "wave",
+                !vcf ? "none" : split_windows ? "split" : "wave", !vcf ? "" : p2_plain ? ",plain" : ",generic",
+                h16 ? "h16" : "b32", (split_windows && h16) ? "split" : "wave", frag_plain ? "plain" : "generic",
+                !fam ? "none" : digest ? "digest" : "generic",
+                !(fam && vcf && n_dup) ? "none" : digest ? "digest" : "generic",
+                !n_gen ? "none" : proton ? "all" : "sweep");
+    }
     if (prof) prof->n = 0;
     hipStream_t s2 = (side ? side : s);
     hipStream_t s3 = ((side && side3) ? side3 : s2);   // the two CIGAR walks of the InDel reads are independent, one wave per 64 reads and long: a stream each
@@ -3763,10 +3782,7 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     // ---- main stream: the base symbols first, so that the queued mismatches (rare symbols, atomics: disjoint from the planes the
     // LINK_M pass stores to) are applied on a side stream while the LINK_M pass runs
     if (P->inferred_is_vcf_generated) {
-        // no IonTorrent values, no amplicon-flagged family, no primer length, median read length at or above microadjust_median_readlen_thres:
-        // the specialisation without those arms
-        const bool plain = (UVC_PLATFORM_IONTORRENT != P->inferred_sequencing_platform) && !R->any_amplicon && !(P->primerlen > 0 && !(0x2 & P->primer_flag))
-                           && (P->central_readlen >= P->microadjust_median_readlen_thres);
+        const bool plain = p2_plain;
         if (split_windows && plain) TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast_split<false, true, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
         else if (split_windows) TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast_split<false, true, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
         else if (plain) TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast<false, true, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
@@ -3806,13 +3822,10 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     if (side) { hipEventRecord(e_stat, s3); hipEventRecord(e_fork2, s2); }
     if (P->inferred_is_vcf_generated && R->n_complex) TIMED(prof, "k_p2_items", hipLaunchKernelGGL(k_p2_items, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
     {
-        const bool proton = (UVC_PLATFORM_IONTORRENT == P->inferred_sequencing_platform);
-        const int n_gen = proton ? R->n_frags : R->n_sweep;
         if (n_gen) TIMED(prof, "k_frag_generic", hipLaunchKernelGGL(k_frag_generic, dim3(imin_h(n_gen, 1 << 20), imin_h((R->max_frag_span + 63) / 64, 16)), dim3(64), 0, s, *R, *P, proton ? (const int32_t *)nullptr : R->sweep_frags, n_gen));
     }
     {
-        const bool plain = P->inferred_is_vcf_generated && (UVC_PLATFORM_IONTORRENT != P->inferred_sequencing_platform) && !(0x1 & P->fam_flag) && !(P->microadjust_padded_deletion_flag & 0x1);
-        const bool h16 = (R->max_frag_depth < 65536) && !R->frag32;
+        const bool plain = frag_plain;
         if (split_windows && h16 && plain) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16_split<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
         else if (split_windows && h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16_split<false>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
         else if (plain && h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16<true>, dim3(nwin), dim3(256), 0, s, *R, *P));
@@ -3825,7 +3838,6 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
         // shallow data: the generic form, one thread per (unit, position); deep data (many units per position, e.g. UMI panels): the digest
         // form, window kernels whose LDS collection removes most of the atomics that bound the per-thread form, and one walk over the
         // fragments of a unit instead of three.  set_reads chose the form: the digest is allocated for the second.
-        const bool digest = (R->fam_digest != nullptr);
         if (digest) TIMED(prof, "k_fam_p4", { hipLaunchKernelGGL(k_fam_p4d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P);
                                                hipLaunchKernelGGL(k_fam_p4d_rest, dim3(R->n_generic_fs), dim3(64), 0, s, *R, *P); });
         else TIMED(prof, "k_fam_p4", hipLaunchKernelGGL(k_fam_p4, dim3(nblk(R->n_generic_work, 256)), dim3(256), 0, s, *R, *P));
