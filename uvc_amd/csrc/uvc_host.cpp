@@ -934,7 +934,9 @@ static int hap_tables(uvcgpu_region_t *r) {
     struct Tmp { std::vector<void *> p; hipStream_t s; ~Tmp() { (void)hipStreamSynchronize(s); for (void *q : p) hipFree(q); } } tmp; tmp.s = r->stream;
     auto get = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr; tmp.p.push_back(q); return q; };
     for (int units = 0; units < 2; units++) {
-        if (!units && !r->P.inferred_is_vcf_generated) continue;   // P3 belongs to updateByAlns3UsingBQ (main.hpp:3691)
+        // the fragment links come from P3 (updateByAlns3UsingBQ, main.hpp:3691), the family links from P5, which updateByAlns3UsingFQ runs
+        // only for a VCF run as well (main.hpp:3371-3521): a FASTQ-only run has no links
+        if (!r->P.inferred_is_vcf_generated) continue;
         const size_t n = (size_t)(units ? R.n_fs : R.n_frags);
         if (n == 0) continue;
         HapWork H; memset(&H, 0, sizeof(H));

@@ -1302,9 +1302,12 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
 // ------------------------------------------------------------------------------------------------
 #define FLD(fld, rec) fields[(size_t)(fld) * capacity + (rec)]
 #define SYM_END UVC_NUM_SYMBOLS
+// double -> int32 as the reference's x86 build converts (cvttsd2si): NaN and values out of range give INT32_MIN, where a plain device
+// conversion gives 0 / saturates.  A germ_hetero_FA outside (0, 1) makes hetLODQ's logarithms NaN.
+DEV int i32_as_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : (int)0x80000000; }
 DEV int het_lodq(double a1, double a2, double expfrac, double powlaw_exponent) {   // hetLODQ, main.hpp:5457-5462
-    const int binomLODQ = (int)binom_llr(expfrac, a1, a2);
-    const int powerLODQ = (int)round(10.0 / log(10.0) * powlaw_exponent * dmax(logit2((a1 + 0.5) * 0.5 / expfrac, (a2 + 0.5) * 0.5 / (1.0 - expfrac)), 0.0));
+    const int binomLODQ = i32_as_x86(binom_llr(expfrac, a1, a2));
+    const int powerLODQ = i32_as_x86(round(10.0 / log(10.0) * powlaw_exponent * dmax(logit2((a1 + 0.5) * 0.5 / expfrac, (a2 + 0.5) * 0.5 / (1.0 - expfrac)), 0.0)));
     return imin(binomLODQ, powerLODQ);
 }
 DEV int indel_n_units(int s) {   // SYMBOL_TO_INDEL_N_UNITS, main.hpp:271-279
