@@ -79,6 +79,37 @@ void uvcgpu_params_default(UvcParams *p);
  * and sets inferred_sequencing_platform / central_readlen / inferred_maxMQ, which the reference
  * infers from the first 5000 BAM records (CmdLineArgs.cpp:50-92). */
 void uvcgpu_params_apply_platform(UvcParams *p, int32_t platform, int32_t central_readlen, int32_t max_mapq);
+/* The whole platform step of the reference for a requested --sequencing-platform (CmdLineArgs.cpp:37-134), on top of whatever values the
+ * caller has set already (the deltas are added to them):
+ *   UVC_PLATFORM_AUTO        = uvcgpu_params_apply_platform(p, inferred, central_readlen, max_mapq)
+ *   UVC_PLATFORM_OTHER       records `inferred`, central_readlen (where 0) and max_mapq like AUTO, and applies no deltas
+ *   UVC_PLATFORM_ILLUMINA / UVC_PLATFORM_IONTORRENT  taken as given: that platform's deltas; `inferred`, `central_readlen` and
+ *                            `max_mapq` are not read (the reference does not look at the file then)
+ * `inferred` (ILLUMINA or IONTORRENT), `central_readlen` and `max_mapq` are what the caller found in the first alignments.
+ * UVCGPU_EINVAL for a requested platform outside 0..3. */
+int uvcgpu_params_apply_platform_ex(UvcParams *p, int32_t sequencing_platform, int32_t inferred, int32_t central_readlen, int32_t max_mapq);
+/* The value refusals of uvcgpu_region_create (which calls this): struct_size, repeat sizes, indel_BQ_max and bias_thres_interfering_indel
+ * (UVCGPU_EINVAL / UVCGPU_EUNSUPPORTED with the same messages).  0 = a region handle accepts *p. */
+int uvcgpu_params_check(const UvcParams *p);
+
+/* ---------------------------------------------------------------- parameter names ---------- */
+/* One table of every row of include/uvc_params.def (UvcParams, in .def order) followed by every row of include/uvc_group_params.def
+ * (UvcGroupParams), generated from the two X-macro files.  A row's name is its field name; uvcgpu_param_set also takes the option form
+ * of the reference's command line (REPLACE_UNDERSCORE_WITH_HYPHEN, CmdLineArgs.cpp:20: every '_' a '-', case kept). */
+enum { UVC_PARAM_INT = 0, UVC_PARAM_DOUBLE = 1 };                 /* kind */
+enum { UVC_PARAM_OF_PARAMS = 0, UVC_PARAM_OF_GROUP = 1 };         /* owning struct */
+struct UvcGroupParams;
+int32_t uvcgpu_param_count(void);
+/* Row i (0 <= i < uvcgpu_param_count()): name, kind, owning struct, default (uvcgpu_params_default / uvcgpu_group_params_default) and
+ * whether uvcgpu_param_set may set it (0 for the derived rows: inferred_*, tumor_vcf_*).  NULL outputs are skipped.  UVCGPU_EINVAL for i
+ * out of range. */
+int uvcgpu_param_info(int32_t i, const char **name, int32_t *kind, int32_t *owner, double *dflt, int32_t *settable);
+/* The value of row i in *p (owner UVC_PARAM_OF_PARAMS) or *g (UVC_PARAM_OF_GROUP), as a double (exact for every int32). */
+int uvcgpu_param_get(const UvcParams *p, const struct UvcGroupParams *g, int32_t i, double *value);
+/* Sets the row called `name` (field or option form) from the text `value`, parsed strictly: the whole string; an int row takes a decimal
+ * int32 or true / false (1 / 0), a double row a finite number.  `p` or `g` may be NULL when the row is not theirs.  UVCGPU_EINVAL for an
+ * unknown or derived name or a bad value, nothing changed; uvcgpu_last_error() names the row. */
+int uvcgpu_param_set(UvcParams *p, struct UvcGroupParams *g, const char *name, const char *value);
 
 /* ---------------------------------------------------------------- reads (alns3) ------------ */
 /* SoA image of `alns3` = vector<pair<array<vector<vector<bam1_t*>>,2>, MolecularBarcode>>

@@ -1,7 +1,7 @@
 // uvc1-mi355x -- BAM + FASTA -> block-gzipped VCF: the host chain of the reference's uvc1 (main.cpp:1196-1603, process_batch :458-1193)
 // in C++ on the three C ABIs of this repository (uvcio.h readers / writer, uvcgroup.h family assignment, uvcgpu.h hot path + record text).
-// The frequently used options keep the reference's names (CmdLineArgs.cpp:188-262): inputBAM -f -o -s --targets -R -t -A -q --outvar-flag
-// --tumor-vcf --tn-is-paired --bed-out-fname --bed-in-fname.
+// Every option of the reference's command line (CmdLineArgs.cpp:188-1000) is accepted under its name, as `--opt value` or `--opt=value`:
+// the hot-path parameters by the library's name table (uvcgpu_param_set), the rest by the class table OPTS below (--help lists all).
 //
 // Region shards.  The reference fans its regions out over threads with `schedule(dynamic, 1)` and writes the chunk outputs in
 // order (main.cpp:1478-1551); uvcTN.sh:92-101 adds one process per chromosome and `bcftools concat -n`.  Here:
@@ -20,7 +20,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -38,59 +40,238 @@ const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-
 struct Opts {
     std::string bam, fasta, out, sample = "-", targets, bed, tumor_vcf, bed_out, bed_in, umi_struct;
     std::vector<int> devices;
-    int threads = 0, outvar_flag = -1, repeat = 1, shard = 0, n_shards = 1, tn_is_paired = 0, tumor_format = 1;
+    int threads = 0, repeat = 1, shard = 0, n_shards = 1, tumor_format = 1;
+    int sequencing_platform = UVC_PLATFORM_AUTO, assay_type = 0;   // --sequencing-platform (0 AUTO, 1 ILLUMINA, 2 IONTORRENT, 3 OTHER), --assay-type (0 inferred per tile, 1 CAPTURE, 2 AMPLICON)
     int64_t tile = 0;            // 0 = no fixed tiles: the regions are the reference's own cuts (uvcio_plan_regions = SamIter::iternext); --tile N overrides
     int64_t mem_per_thread = 1536;   // --mem-per-thread (MB), CmdLineArgs.hpp:33: enters the reference's region cuts
-    bool all_out = false, timing = false, no_header = false, device_inflate = false;
-    double vqual = -1e9;
+    bool timing = false, no_header = false, device_inflate = false, print_params = false;
+    UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
+    UvcGroupParams G;
 };
 [[noreturn]] void die(const std::string &m) { fprintf(stderr, "uvc1-mi355x: %s\n", m.c_str()); exit(2); }
-void usage() {
-    fprintf(stderr, "usage: uvc1-mi355x inputBAM -f ref.fa -o out.vcf.gz [-s sample] [--targets chr[:beg-end] | -R regions.bed] [-t threads] [-A] [-q vqual]\n"
-                    "                   [--outvar-flag bits] [--tile bp (default: the reference's region cuts)] [--mem-per-thread MB] [--devices 0,1,..] [--shard i/n] [--no-header] [--timing] [--device-inflate]\n"
-                    "                   [--tn-is-paired 0|1] [--tumor-vcf tumor.vcf.gz] [--is-tumor-format-retrieved 0|1] [--bed-out-fname f] [--bed-in-fname f]\n"
-                    "       uvc1-mi355x --concat out.vcf.gz shard0.vcf.gz shard1.vcf.gz ...\n");
+const char *const ONLY_PRINT_VCF_HEADER = "/only-print-vcf-header/";   // OPT_ONLY_PRINT_VCF_HEADER, common.hpp:58
+
+// Every option of the reference's command line (CmdLineArgs.cpp:188-1000) falls into one class:
+//   PARAM / GROUP  a row of include/uvc_params.def / uvc_group_params.def, named in option form (--fam-thres-highBQ-snv): set through
+//                  uvcgpu_param_set.  These rows come from the library's name table (uvcgpu_param_info), so a new .def row is an option
+//                  with no edit here; the derived rows (inferred_*, tumor_vcf_*) are not options.
+//   CLI            files, regions, threads and this program's own switches
+//   MODE           switches that are not a plain row, or whose row needs wiring: see main / call_tile
+//   INERT          the reference parses it and its value changes nothing the reference writes (logging, a stderr warning, no live
+//                  reader): accepted, no effect
+//   UNSUPPORTED    what this program does not produce: refused (exit 2) off its default, accepted at it
+// The table below holds every option that is not a PARAM / GROUP row; a name here wins over a .def row of the same name.
+enum OptClass { O_CLI, O_MODE, O_INERT, O_UNSUPPORTED, O_PARAM, O_GROUP };
+const char *const CLASS_NAME[] = { "CLI", "MODE", "INERT", "UNSUPPORTED", "PARAM", "GROUP" };
+struct OptRow { const char *names; OptClass cls; bool flag; const char *dflt; const char *what; };
+const OptRow OPTS[] = {
+    { "-f,--fasta", O_CLI, false, "", "reference FASTA (with .fai)" },
+    { "-o,--output", O_CLI, false, "", "block-gzipped VCF to write" },
+    { "-s,--sample", O_CLI, false, "-", "sample name" },
+    { "--targets", O_CLI, false, "", "chr or chr:beg-end (1-based, inclusive)" },
+    { "-R,--regions-file", O_CLI, false, "", "BED file of the regions to call" },
+    { "-t,--threads", O_CLI, false, "0", "tiles in flight (0: half the usable cores, 1..8 per device)" },
+    { "-A,--all-out", O_CLI, true, "", "every allele of every position (should_output_all = 1)" },
+    { "-q,--vqual", O_CLI, false, "15", "minimum variant quality (the vqual row)" },
+    { "--outvar-flag", O_CLI, false, "62", "output-variant bits (the outvar_flag row)" },
+    { "--tumor-vcf", O_CLI, false, "", "the tumor pass's VCF: this BAM is the normal sample of a T/N pair" },
+    { "--tn-is-paired", O_CLI, false, "0", "the tn_is_paired row" },
+    { "--is-tumor-format-retrieved", O_CLI, false, "1", "carry the tumor's FORMAT column into the normal pass's records" },
+    { "--bed-in-fname", O_CLI, false, "", "BED file of regions (overrides -R)" },
+    { "--bed-out-fname", O_CLI, false, "", "write the region table here" },
+    { "--mem-per-thread", O_CLI, false, "1536", "MB per thread in the reference's region cuts" },
+    { "--tile", O_CLI, false, "0", "fixed tiles of this many bp instead of the reference's region cuts" },
+    { "--devices,--device", O_CLI, false, "", "comma-separated HIP device ids (default: all visible)" },
+    { "--shard", O_CLI, false, "0/1", "i/n: this process takes the i-th of n runs of tiles" },
+    { "--no-header", O_CLI, true, "", "no VCF header" },
+    { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr" },
+    { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
+    { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
+    { "--print-params", O_CLI, true, "", "print the resolved parameters as name=value lines in .def order and exit (no device)" },
+    { "-h,--help", O_CLI, true, "", "this text" },
+    { "-v,--version", O_CLI, true, "", "the version" },
+    { "--assay-type", O_MODE, false, "0", "0 inferred per region, 1 CAPTURE, 2 AMPLICON (main.cpp:511)" },
+    { "--sequencing-platform", O_MODE, false, "0", "0 AUTO, 1 ILLUMINA, 2 IONTORRENT (taken as given), 3 OTHER (inferred, no platform deltas)" },
+    { "--molecule-tag", O_MODE, false, "0", "0 AUTO, 1 NONE, 2 BARCODING, 3 DUPLEX: read-name UMIs" },
+    { "--disable-duplex", O_MODE, false, "0", "0 or 1 (1: a duplex UMI counts as a plain one)" },
+    { "--pair-end-merge", O_MODE, false, "0", "0 YES, 1 NO" },
+    { "--all-germline-out", O_MODE, true, "", "every allele of germline variants (should_output_all_germline = 1)" },
+    { "--central-readlen", O_MODE, false, "0", "read length of the assay (0: inferred)" },
+    // INERT: parsed by the reference, no effect on what it writes (each grepped in the reference)
+    { "--always-log", O_INERT, false, "0", "logging only (grouping.cpp:947, main.cpp:477)" },
+    { "--bias-orientation-counter-avg-end-len", O_INERT, false, "20", "no statement reads it" },
+    { "--bias-thres-aLPxT-perc", O_INERT, false, "160", "no statement reads it" },
+    { "--bias-thres-aXM1T-add", O_INERT, false, "30", "its use is commented out (main.hpp:1883)" },
+    { "--microadjust-fam-lowfreq-invFA", O_INERT, false, "1000", "its uses are commented out (main.hpp:4996-4999)" },
+    { "--microadjust-ref-MQ-dec-max", O_INERT, false, "15", "no statement reads it" },
+    { "--debug-warn-min-read-end-ins-cigar-oplen", O_INERT, false, "16", "a warning on stderr only (main.hpp:2015)" },
+    // not options of the reference as built (COMPILATION_ENABLE_XMGOT is 0, common.hpp:4; main.hpp:1259-1267) or commented out there
+    // (CmdLineArgs.cpp:418-425, grouping.cpp:837-845): accepted for command lines written for builds that have them
+    { "--bias-thres-PFXM1T-add", O_INERT, false, "130", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFXM2T-add", O_INERT, false, "20", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFGO1T-add", O_INERT, false, "125", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFGO2T-add", O_INERT, false, "15", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFXM1T-perc", O_INERT, false, "50", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFXM2T-perc", O_INERT, false, "70", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFGO1T-perc", O_INERT, false, "50", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFGO2T-perc", O_INERT, false, "70", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFXM1NT-perc", O_INERT, false, "70", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--bias-thres-PFGO1NT-perc", O_INERT, false, "70", "compiled out (COMPILATION_ENABLE_XMGOT 0)" },
+    { "--dedup-amplicon-count-to-surrcount-ratio", O_INERT, false, "16", "commented out (grouping.cpp:837-845)" },
+    { "--dedup-amplicon-count-to-surrcount-ratio-twosided", O_INERT, false, "4", "commented out (grouping.cpp:837-845)" },
+    // UNSUPPORTED
+    { "--fam-consensus-out-fastq", O_UNSUPPORTED, false, "", "the consensus FASTQ of UMI families is not written" },
+    { "--fam-consensus-out-fastq-thres-dup1add", O_UNSUPPORTED, false, "1", "the consensus FASTQ of UMI families is not written" },
+    { "--should-add-note", O_UNSUPPORTED, false, "0", "the FORMAT/note field is not written" },
+    { "--debug-note-flag", O_UNSUPPORTED, false, "0", "the debug notes of the records (INFO/RBAQ, main.hpp:6229) are not written" },
+    { "--debug-tid", O_UNSUPPORTED, false, "-1", "the per-locus debug dump is not written" },
+    { "--debug-pos", O_UNSUPPORTED, false, "-1", "the per-locus debug dump is not written" },
+    { "--bed-in-avg-sequencing-DP", O_UNSUPPORTED, false, "-1", "the regions are not planned from BED read counts" },
+    { "--bed-in-avg-sequencing-DP-n-from-t", O_UNSUPPORTED, false, "0", "the regions are not planned from BED read counts" },
+};
+
+const OptRow *find_opt(const std::string &name) {
+    for (const OptRow &r : OPTS) {
+        const std::string ns = r.names; size_t at = 0;
+        while (at <= ns.size()) { size_t c = ns.find(',', at); if (c == std::string::npos) c = ns.size(); if (ns.compare(at, c - at, name) == 0 && c - at == name.size()) return &r; at = c + 1; }
+    }
+    return nullptr;
 }
+// the settable .def row whose option form is `--name`, else -1
+int32_t find_param(const std::string &opt) {
+    if (opt.size() < 3 || opt.compare(0, 2, "--") != 0) return -1;
+    const std::string field = opt.substr(2);
+    for (int32_t i = 0, n = uvcgpu_param_count(); i < n; i++) {
+        const char *nm; int32_t settable;
+        uvcgpu_param_info(i, &nm, nullptr, nullptr, nullptr, &settable);
+        std::string f = nm; std::replace(f.begin(), f.end(), '_', '-');
+        if (settable && f == field) return i;
+    }
+    return -1;
+}
+std::string option_name(const char *field) { std::string f = std::string("--") + field; std::replace(f.begin(), f.end(), '_', '-'); return f; }
+std::string fmt_value(int32_t kind, double v) { char b[64]; if (kind == UVC_PARAM_INT) snprintf(b, sizeof(b), "%d", (int)v); else snprintf(b, sizeof(b), "%.17g", v); return b; }
+bool number(const std::string &s, double *v) {   // a whole decimal number, or true / false
+    if (s == "true" || s == "false") { *v = (s == "true"); return true; }
+    if (s.empty() || isspace((unsigned char)s[0])) return false;
+    char *e = nullptr; *v = strtod(s.c_str(), &e); return *e == 0 && std::isfinite(*v);
+}
+
+void help() {
+    printf("usage: uvc1-mi355x inputBAM -f ref.fa -o out.vcf.gz [options]\n"
+           "       uvc1-mi355x /only-print-vcf-header/ [options]     the VCF header of the resolved parameters on stdout\n"
+           "       uvc1-mi355x inputBAM --print-params [options]     the resolved parameters as name=value lines\n"
+           "       uvc1-mi355x --concat out.vcf.gz shard0.vcf.gz shard1.vcf.gz ...\n"
+           "Every option takes `--opt value` or `--opt=value`.  User values come first, then the platform step of --sequencing-platform\n"
+           "adds its deltas on top of them (CmdLineArgs.cpp:37-134).  [CLASS]: PARAM / GROUP = a parameter of the hot path / of the family\n"
+           "pass; INERT = accepted, no effect (the reference reads no such value); UNSUPPORTED = refused unless at its default.\n");
+    for (const OptRow &r : OPTS) printf("  %s [%s] default=%s  %s\n", r.names, CLASS_NAME[r.cls], r.flag ? "off" : (*r.dflt ? r.dflt : "\"\""), r.what);
+    for (int32_t i = 0, n = uvcgpu_param_count(); i < n; i++) {
+        const char *nm; int32_t kind, owner, settable; double d;
+        uvcgpu_param_info(i, &nm, &kind, &owner, &d, &settable);
+        const std::string opt = option_name(nm);
+        if (!settable || find_opt(opt)) continue;
+        printf("  %s [%s] default=%s  %s\n", opt.c_str(), owner == UVC_PARAM_OF_GROUP ? "GROUP" : "PARAM", fmt_value(kind, d).c_str(), kind == UVC_PARAM_INT ? "int" : "double");
+    }
+}
+
 Opts parse(int argc, char **argv) {
     Opts o;
+    uvcgpu_params_default(&o.P);
+    uvcgpu_group_params_default(&o.G);
+    auto set_row = [&](const char *row, const std::string &opt, const std::string &v) {
+        if (uvcgpu_param_set(&o.P, &o.G, row, v.c_str())) die(opt + ": " + uvcgpu_last_error());
+    };
+    auto enum_value = [&](const std::string &opt, const std::string &v, int hi) {
+        double x; if (!number(v, &x) || x < 0 || x > hi || x != (int)x) die(opt + ": '" + v + "' is not one of 0.." + std::to_string(hi));   // range first: the cast needs it
+        return (int)x;
+    };
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
-        auto val = [&]() -> std::string { if (i + 1 >= argc) die("missing value of " + a); return argv[++i]; };
-        if (a == "-f" || a == "--fasta") o.fasta = val();
-        else if (a == "-o" || a == "--output") o.out = val();
-        else if (a == "-s" || a == "--sample") o.sample = val();
-        else if (a == "--targets") o.targets = val();
-        else if (a == "-R" || a == "--regions-file") o.bed = val();
-        else if (a == "-t" || a == "--threads") o.threads = std::max(1, atoi(val().c_str()));
-        else if (a == "-A" || a == "--all-out") o.all_out = true;
-        else if (a == "-q" || a == "--vqual") o.vqual = atof(val().c_str());
-        else if (a == "--outvar-flag") o.outvar_flag = atoi(val().c_str());
-        else if (a == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
-        else if (a == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
-        else if (a == "--device" || a == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
+        if (a.empty() || a[0] != '-') {
+            if (o.bam.empty()) o.bam = a; else die("more than one inputBAM");
+            continue;
+        }
+        std::string name = a, inline_value; bool has_value = false;
+        if (a.compare(0, 2, "--") == 0 && a.find('=') != std::string::npos) { name = a.substr(0, a.find('=')); inline_value = a.substr(a.find('=') + 1); has_value = true; }
+        const OptRow *row = find_opt(name);
+        const int32_t prow = row ? -1 : find_param(name);
+        if (!row && prow < 0) die("unknown option " + a + " (uvc1-mi355x --help lists every option)");
+        if (row && row->flag && has_value) die(name + " takes no value");
+        auto val = [&]() -> std::string { if (has_value) return inline_value; if (i + 1 >= argc) die("missing value of " + name); return argv[++i]; };
+        if (!row) {   // PARAM / GROUP
+            const char *field; uvcgpu_param_info(prow, &field, nullptr, nullptr, nullptr, nullptr);
+            set_row(field, name, val());
+            continue;
+        }
+        const std::string n0 = std::string(row->names).substr(0, std::string(row->names).find(','));   // the first name of the row
+        if (row->cls == O_INERT) { const std::string v = val(); double x; if (!number(v, &x)) die(name + ": '" + v + "' is not a number"); continue; }
+        if (row->cls == O_UNSUPPORTED) {
+            const std::string v = val(); double x, d;
+            const bool at_default = (v == row->dflt) || (!*row->dflt && v == ".") || (number(v, &x) && number(row->dflt, &d) && x == d);
+            if (!at_default) die(name + " " + v + " is not supported: " + row->what);
+            continue;
+        }
+        if (n0 == "-f") o.fasta = val();
+        else if (n0 == "-o") o.out = val();
+        else if (n0 == "-s") o.sample = val();
+        else if (n0 == "--targets") o.targets = val();
+        else if (n0 == "-R") o.bed = val();
+        else if (n0 == "-t") o.threads = std::max(1, atoi(val().c_str()));
+        else if (n0 == "-A") set_row("should_output_all", name, "1");
+        else if (n0 == "-q") set_row("vqual", name, val());
+        else if (n0 == "--outvar-flag") set_row("outvar_flag", name, val());
+        else if (n0 == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
+        else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
+        else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
             const std::string v = val(); size_t at = 0;
             while (at <= v.size()) { size_t c = v.find(',', at); if (c == std::string::npos) c = v.size(); if (c > at) o.devices.push_back(atoi(v.substr(at, c - at).c_str())); at = c + 1; }
             if (o.devices.empty()) die("--devices needs at least one id");
         }
-        else if (a == "--shard") { const std::string v = val(); if (sscanf(v.c_str(), "%d/%d", &o.shard, &o.n_shards) != 2 || o.n_shards < 1 || o.shard < 0 || o.shard >= o.n_shards) die("--shard takes i/n with 0 <= i < n"); }
-        else if (a == "--no-header") o.no_header = true;
-        else if (a == "--timing") o.timing = true;
-        else if (a == "--device-inflate") o.device_inflate = true;   // the BGZF blocks of the BAM inflated by the GPU (uvcgpu_bgzf_inflate) instead of the host cores
-        else if (a == "--tumor-vcf") o.tumor_vcf = val();
-        else if (a == "--tn-is-paired") o.tn_is_paired = atoi(val().c_str());
-        else if (a == "--is-tumor-format-retrieved") o.tumor_format = atoi(val().c_str());
-        else if (a == "--bed-out-fname") o.bed_out = val();
-        else if (a == "--bed-in-fname") o.bed_in = val();
-        else if (a == "--repeat") o.repeat = std::max(1, atoi(val().c_str()));   // benchmark aid: the tile list n times (steady state on a small file)
-        else if (a == "-h" || a == "--help") { usage(); exit(0); }
-        else if (!a.empty() && a[0] == '-') die("unknown option " + a + " (the hot-path parameters keep the reference's defaults)");
-        else if (o.bam.empty()) o.bam = a;
-        else die("more than one inputBAM");
+        else if (n0 == "--shard") { const std::string v = val(); if (sscanf(v.c_str(), "%d/%d", &o.shard, &o.n_shards) != 2 || o.n_shards < 1 || o.shard < 0 || o.shard >= o.n_shards) die("--shard takes i/n with 0 <= i < n"); }
+        else if (n0 == "--no-header") o.no_header = true;
+        else if (n0 == "--timing") o.timing = true;
+        else if (n0 == "--device-inflate") o.device_inflate = true;   // the BGZF blocks of the BAM inflated by the GPU (uvcgpu_bgzf_inflate) instead of the host cores
+        else if (n0 == "--tumor-vcf") o.tumor_vcf = val();
+        else if (n0 == "--tn-is-paired") set_row("tn_is_paired", name, val());
+        else if (n0 == "--is-tumor-format-retrieved") o.tumor_format = atoi(val().c_str());
+        else if (n0 == "--bed-out-fname") o.bed_out = val();
+        else if (n0 == "--bed-in-fname") o.bed_in = val();
+        else if (n0 == "--repeat") o.repeat = std::max(1, atoi(val().c_str()));   // benchmark aid: the tile list n times (steady state on a small file)
+        else if (n0 == "--print-params") o.print_params = true;
+        else if (n0 == "-h") { help(); exit(0); }
+        else if (n0 == "-v") { printf("uvc1-mi355x (%s)\n", uvcgpu_version()); exit(0); }
+        // MODE
+        else if (n0 == "--assay-type") o.assay_type = enum_value(name, val(), 2);
+        else if (n0 == "--sequencing-platform") o.sequencing_platform = enum_value(name, val(), 3);
+        // the enum values of common.hpp:124-146 only: the reference merges for every pair_end_merge but NO (grouping.cpp:627), the family
+        // pass for YES alone (uvc_group.hip), so a value outside them would not mean the same here
+        else if (n0 == "--molecule-tag") set_row("molecule_tag", name, std::to_string(enum_value(name, val(), 3)));   // read-name digest + UvcGroupParams (call_tile)
+        else if (n0 == "--disable-duplex") set_row("disable_duplex", name, std::to_string(enum_value(name, val(), 1)));
+        else if (n0 == "--pair-end-merge") set_row("pair_end_merge", name, std::to_string(enum_value(name, val(), 1)));
+        else if (n0 == "--all-germline-out") set_row("should_output_all_germline", name, "1");
+        else if (n0 == "--central-readlen") set_row("central_readlen", name, val());  // 0 = inferred by the platform step
+        else die("option without a handler: " + name);
     }
-    if (o.bam.empty() || o.fasta.empty() || o.out.empty()) { usage(); exit(2); }
+    if (o.bam.empty() || (!o.print_params && o.bam != ONLY_PRINT_VCF_HEADER && (o.fasta.empty() || o.out.empty()))) {
+        fprintf(stderr, "usage: uvc1-mi355x inputBAM -f ref.fa -o out.vcf.gz [options] (--help lists them)\n");
+        exit(2);
+    }
+    if (const int rc = uvcgpu_params_check(&o.P)) die(std::string(uvcgpu_last_error()) + " (code " + std::to_string(rc) + ")");   // before any file or device
+    if (!o.tumor_vcf.empty()) o.P.tumor_vcf_is_provided = 1;   // IS_PROVIDED(vcf_tumor_fname), common.hpp:56
     if (const char *us = getenv("ONE_STEP_UMI_STRUCT")) o.umi_struct = us;   // the reference takes the in-read UMI pattern from the environment (main.cpp:1224-1225)
     return o;
+}
+
+// --print-params: every row of both tables, in .def order
+void print_params(const Opts &o) {
+    for (int32_t i = 0, n = uvcgpu_param_count(); i < n; i++) {
+        const char *nm; int32_t kind; double v;
+        uvcgpu_param_info(i, &nm, &kind, nullptr, nullptr, nullptr);
+        uvcgpu_param_get(&o.P, &o.G, i, &v);
+        printf("%s=%s\n", nm, fmt_value(kind, v).c_str());
+    }
 }
 
 // A tile of a run of adjacent tiles.  The reference scores zerobased_pos rpos_beg .. rpos_end inclusive without the BASE sub-position of
@@ -121,9 +302,9 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     const int64_t n = b.n_alns;
     if (n == 0) return false;
     w.h31.resize(n); w.h17.resize(n); w.u31.resize(n); w.u17.resize(n); w.kind.resize(n);
-    uvcgpu_qname_digest_batch(b.qnames, b.qname_off, n, 0, 0, w.h31.data(), w.h17.data(), w.u31.data(), w.u17.data(), w.kind.data());
+    uvcgpu_qname_digest_batch(b.qnames, b.qname_off, n, o.G.molecule_tag, o.G.disable_duplex, w.h31.data(), w.h17.data(), w.u31.data(), w.u17.data(), w.kind.data());
     if (!o.umi_struct.empty() && uvcgpu_umi_in_read_batch(o.umi_struct.c_str(), b.bases, b.seq_off, b.l_qseq, b.flag, n, w.kind.data(), nullptr)) die(uvcgpu_last_error());   // grouping.cpp:787-792
-    UvcGroupParams gp; uvcgpu_group_params_default(&gp);
+    UvcGroupParams gp = o.G;
     gp.fetch_tbeg = (int32_t)t.beg; gp.fetch_tend = (int32_t)t.end; gp.inferred_sequencing_platform = P.inferred_sequencing_platform;
     UvcGroupInput gi; memset(&gi, 0, sizeof(gi));
     gi.n_alns = n; gi.tid = b.tid; gi.pos = b.pos; gi.endpos = b.endpos; gi.mtid = b.mtid; gi.mpos = b.mpos; gi.isize = b.isize; gi.flag = b.flag; gi.mapq = b.mapq;
@@ -164,7 +345,8 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     w.t_reads += now() - t0; t0 = now();
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
-    rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = o.all_out; rq.is_amplicon = (go.n_amplicon * 2 > k);
+    rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
+    rq.is_amplicon = (o.assay_type == 0 ? (go.n_amplicon * 2 > k) : (o.assay_type == 2));   // inferred_assay_type, main.cpp:510-511
     rq.base_at_pos_beg = (t.continues && first == t.beg && t.beg > ext_beg) ? 1 : 0; rq.region_beg = (int32_t)t.run_beg;
     if (tvcf) {   // normal sample of a T/N pair: the tumor records of this region (tkis_beg .. tkis_end, main.cpp:532-533)
         const UvcTumorKey *keys = nullptr; const char *const *cols = nullptr, *const *ras = nullptr; int64_t nk = 0;
@@ -172,7 +354,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
         rq.tumor_keys = keys; rq.n_tumor_keys = nk; rq.tumor_sample_columns = (o.tumor_format ? cols : nullptr); rq.tumor_ref_alt = ras;
     }
     rq.kept_only = 1;   // only the record groups that are written travel to the host
-    int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), uvcgpu_region_score_size(w.reg, &rq) / (o.all_out ? 1 : 64));
+    int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), uvcgpu_region_score_size(w.reg, &rq) / (rq.all_out ? 1 : 64));
     UvcScoreOut so;
     for (;;) {
         w.fields.resize((size_t)UVC_NUM_SCORE_FIELDS * (size_t)cap);
@@ -208,18 +390,45 @@ int main(int argc, char **argv) {
         return 0;
     }
     Opts o = parse(argc, argv);
+    UvcParams &P = o.P;
+    std::string cmd; for (int i = 0; i < argc; i++) { cmd += argv[i]; cmd += "  "; }   // ##variantCallerCommand (main.hpp:5870-5874)
+    auto header = [&](const char *tsample, const char *const *cnames, const int64_t *lens, int32_t nref) {
+        // ##fileDate / ##reference / ##variantCallerCommand as generate_vcf_header prints them (main.hpp:5788-5794, 5870-5874)
+        char date[80]; { time_t raw; time(&raw); strftime(date, sizeof(date), "%F %T", localtime(&raw)); }
+        int64_t len = 0;
+        uvcgpu_vcf_header_ex(&P, o.sample.c_str(), tsample, cnames, lens, nref, date, o.fasta.c_str(), cmd.c_str(), nullptr, 0, &len);
+        std::string h((size_t)len, '\0');
+        if (uvcgpu_vcf_header_ex(&P, o.sample.c_str(), tsample, cnames, lens, nref, date, o.fasta.c_str(), cmd.c_str(), &h[0], len, &len)) die(uvcgpu_last_error());
+        return h;
+    };
+    // the platform step without a look at the file: a given ILLUMINA / IONTORRENT needs none, and the header mode has no file
+    // (main.cpp:1229-1240 prints the header there before any platform step; here a given platform's deltas are in it)
+    const bool platform_given = (o.sequencing_platform == UVC_PLATFORM_ILLUMINA || o.sequencing_platform == UVC_PLATFORM_IONTORRENT);
+    if (platform_given) uvcgpu_params_apply_platform_ex(&P, o.sequencing_platform, 0, 0, 0);
+    if (o.bam == ONLY_PRINT_VCF_HEADER) {
+        if (!platform_given) P.inferred_sequencing_platform = o.sequencing_platform;
+        const std::string h = header(nullptr, nullptr, nullptr, 0);
+        fwrite(h.data(), 1, h.size(), stdout);
+        return 0;
+    }
+    if (o.print_params && platform_given) { print_params(o); return 0; }
     // Each region handle has three streams and a worker's copies should run under another worker's kernels: with the runtime's default of four
     // hardware queues the streams of different handles share queues, and a kernel then waits behind another handle's 10 ms copy (bench.py's
     // pcie_inclusive leg: 16.0 ms per tile with 4 queues, 13.5 with 16).  Read by the HIP runtime when it starts; an explicit setting wins.
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if (o.devices.empty()) { const int nd = uvcgpu_device_count(); if (nd <= 0) die("no HIP device: uvc1-mi355x has no CPU path"); for (int d = 0; d < nd; d++) o.devices.push_back(d); }
+    // --print-params plans the region cuts with the same -t default as the run (the AUTO / OTHER inference reads the first region): the device
+    // count comes from the runtime's enumeration, no device is initialised; none visible = one
+    if (o.devices.empty()) {
+        const int nd = uvcgpu_device_count();
+        if (nd <= 0 && !o.print_params) die("no HIP device: uvc1-mi355x has no CPU path");
+        for (int d = 0; d < std::max(nd, 1); d++) o.devices.push_back(d);
+    }
     // tiles in flight: the host stages of a tile (inflate above all) cost ~1.3 core-seconds per 1 Mb x 300x, the device ~10 ms: as many workers
     // as half the cores this process may use keep the cores busy (measured on a 16-core quota: 4 -> 6.7, 8 -> 8-11, 12-16 -> 8-9.6 M positions/s),
     // never more than 8 per device (a region handle holds ~7 GB of planes) and at least one per device
     if (o.threads <= 0) { const int nd = (int)o.devices.size(); o.threads = std::max(nd, std::min(8 * nd, uvc_effective_cpus() / 2)); }
     // the readers of all tiles in flight share one pool of inflate / decode threads inside libuvcio (as many as this process has cores:
     // quota- and affinity-aware, uvc_cpus.h); UVCIO_THREADS overrides
-    if (uvcgpu_init(o.devices[0])) die(uvcgpu_last_error());
     uvcio_bam_t *bam0 = nullptr;
     if (uvcio_bam_open(&bam0, o.bam.c_str())) die(uvcio_last_error());
     if (!uvcio_bam_has_index(bam0)) fprintf(stderr, "uvc1-mi355x: no .bai next to %s, every tile scans the file\n", o.bam.c_str());
@@ -307,14 +516,9 @@ int main(int argc, char **argv) {
     const size_t tiles_per_pass = tiles.size();
     for (int rep = 1; rep < o.repeat; rep++) for (size_t q = 0; q < tiles_per_pass; q++) tiles.push_back(tiles[q]);
 
-    // parameters: the reference's defaults; platform and read length inferred from the first alignments that are seen (CmdLineArgs.cpp:34-111
-    // reads the first 5000 records of the file; here: of the first tile that has any)
-    UvcParams P; uvcgpu_params_default(&P);
-    if (o.vqual > -1e8) P.vqual = o.vqual;
-    if (o.outvar_flag >= 0) P.outvar_flag = o.outvar_flag;
-    P.should_output_all = o.all_out;
-    P.tn_is_paired = o.tn_is_paired;
-    {
+    // parameters: the reference's defaults and the user's values (parse); AUTO / OTHER infer platform and read length from the first
+    // alignments that are seen (CmdLineArgs.cpp:34-111 reads the first 5000 records of the file; here: of the first tile that has any)
+    if (!platform_given) {
         int platform = UVC_PLATFORM_ILLUMINA, readlen = 150, maxmq = 0; bool seen = false;
         for (size_t ti = 0; ti < tiles.size() && !seen; ti++) {
             UvcBamBatch b;
@@ -332,9 +536,11 @@ int main(int argc, char **argv) {
             const bool fix = ((int64_t)ql[ql.size() / 2] * 100 > (int64_t)ql.back() * 95);
             if (!(pe > 0 || 4 * (q30f - q20f) < q30p || (2 * (q30f - q20f) < q30p && fix))) platform = UVC_PLATFORM_IONTORRENT;
         }
-        uvcgpu_params_apply_platform(&P, platform, readlen, maxmq);
+        uvcgpu_params_apply_platform_ex(&P, o.sequencing_platform, platform, readlen, maxmq);
     }
     uvcio_bam_close(bam0);
+    if (o.print_params) { print_params(o); return 0; }
+    if (uvcgpu_init(o.devices[0])) die(uvcgpu_last_error());
     // UVC1_PINNED=1: the workers' base / quality columns live in page-locked memory of the GPU library from here on, so that set_reads copies
     // them by DMA.  Off by default: on the boxes measured the files -> VCF rate did not move with it (scripts/bench_cli.py; the chain is not
     // bound by that copy) and it locks ~ 800 MB of host memory per worker.
@@ -352,7 +558,6 @@ int main(int argc, char **argv) {
     uvcio_tumor_vcf_t *tvcf = nullptr;
     if (!o.tumor_vcf.empty()) {
         if (uvcio_tumor_vcf_open(&tvcf, o.tumor_vcf.c_str(), cnames.data(), nref, o.tumor_format)) die(uvcio_last_error());
-        P.tumor_vcf_is_provided = 1;
         fprintf(stderr, "uvc1-mi355x: %lld tumor records from %s\n", (long long)uvcio_tumor_vcf_n_records(tvcf), o.tumor_vcf.c_str());
     }
 
@@ -360,14 +565,7 @@ int main(int argc, char **argv) {
     uvcio_bgzf_writer_t *zw = nullptr;
     if (uvcio_bgzf_write_open(&zw, o.out.c_str(), 6)) die(uvcio_last_error());
     if (!o.no_header) {
-        int64_t len = 0;
-        const char *tsample = (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr;
-        // ##fileDate / ##reference / ##variantCallerCommand as generate_vcf_header prints them (main.hpp:5788-5794, 5870-5874)
-        char date[80]; { time_t raw; time(&raw); strftime(date, sizeof(date), "%F %T", localtime(&raw)); }
-        std::string cmd; for (int i = 0; i < argc; i++) { cmd += argv[i]; cmd += "  "; }
-        uvcgpu_vcf_header_ex(&P, o.sample.c_str(), tsample, cnames.data(), lens.data(), nref, date, o.fasta.c_str(), cmd.c_str(), nullptr, 0, &len);
-        std::string h((size_t)len, '\0');
-        if (uvcgpu_vcf_header_ex(&P, o.sample.c_str(), tsample, cnames.data(), lens.data(), nref, date, o.fasta.c_str(), cmd.c_str(), &h[0], len, &len)) die(uvcgpu_last_error());
+        const std::string h = header((tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, cnames.data(), lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
     }
     const double t_start = now();

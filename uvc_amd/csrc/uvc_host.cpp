@@ -202,10 +202,7 @@ void uvcgpu_params_default(UvcParams *p) {
 #undef UVC_PD
 }
 
-void uvcgpu_params_apply_platform(UvcParams *p, int32_t platform, int32_t central_readlen, int32_t max_mapq) {   // CmdLineArgs.cpp:13-15, 50-134
-    p->inferred_sequencing_platform = platform;
-    if (0 == p->central_readlen) p->central_readlen = central_readlen;
-    p->inferred_maxMQ = std::max(p->inferred_maxMQ, max_mapq);
+static void platform_deltas(UvcParams *p, int32_t platform) {   // CmdLineArgs.cpp:13-15, 113-134
     auto dec = [](int32_t &a, int32_t b) { a = a - std::min(a, b); };
     if (platform == UVC_PLATFORM_IONTORRENT) {
         p->bq_phred_added_misma += 8;
@@ -213,6 +210,30 @@ void uvcgpu_params_apply_platform(UvcParams *p, int32_t platform, int32_t centra
     } else if (platform == UVC_PLATFORM_ILLUMINA) {
         p->syserr_minABQ_pcr_snv += 200; p->syserr_minABQ_pcr_indel += 100; p->syserr_minABQ_cap_snv += 200; p->syserr_minABQ_cap_indel += 100;
     }
+}
+
+void uvcgpu_params_apply_platform(UvcParams *p, int32_t platform, int32_t central_readlen, int32_t max_mapq) {   // CmdLineArgs.cpp:13-15, 50-134
+    p->inferred_sequencing_platform = platform;
+    if (0 == p->central_readlen) p->central_readlen = central_readlen;
+    p->inferred_maxMQ = std::max(p->inferred_maxMQ, max_mapq);
+    platform_deltas(p, platform);
+}
+
+// selfUpdateByPlatform (CmdLineArgs.cpp:37-134): AUTO and OTHER infer from the file, OTHER keeps the deltas off; ILLUMINA and IONTORRENT
+// are taken as given and the file is not read (central_readlen and inferred_maxMQ keep the caller's values)
+int uvcgpu_params_apply_platform_ex(UvcParams *p, int32_t sequencing_platform, int32_t inferred, int32_t central_readlen, int32_t max_mapq) {
+    if (!p || sequencing_platform < UVC_PLATFORM_AUTO || sequencing_platform > UVC_PLATFORM_OTHER) return fail(UVCGPU_EINVAL, "sequencing platform outside 0..3");
+    if (sequencing_platform == UVC_PLATFORM_ILLUMINA || sequencing_platform == UVC_PLATFORM_IONTORRENT) {
+        p->inferred_sequencing_platform = sequencing_platform;
+        platform_deltas(p, sequencing_platform);
+    } else if (sequencing_platform == UVC_PLATFORM_AUTO) {
+        uvcgpu_params_apply_platform(p, inferred, central_readlen, max_mapq);
+    } else {
+        p->inferred_sequencing_platform = inferred;
+        if (0 == p->central_readlen) p->central_readlen = central_readlen;
+        p->inferred_maxMQ = std::max(p->inferred_maxMQ, max_mapq);
+    }
+    return 0;
 }
 
 // (Re)binds a handle to a region: side arrays of the reference (C10) and the plane layout.  Device buffers are kept when they are large
@@ -287,13 +308,7 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
 
 static int uvcgpu_region_create_impl(uvcgpu_region_t **out, const UvcParams *params, int32_t tid, int32_t beg, int32_t end, const char *refseq) {
     if (!out || !params || !refseq || end <= beg) return fail(UVCGPU_EINVAL, "bad argument");
-    if (params->struct_size != (int32_t)sizeof(UvcParams)) return fail(UVCGPU_EINVAL, "UvcParams::struct_size mismatch");
-    if (params->indel_str_repeatsize_max < 1 || params->indel_vntr_repeatsize_max < params->indel_str_repeatsize_max) return fail(UVCGPU_EINVAL, "bad repeat-size parameters");
-    if (params->indel_vntr_repeatsize_max > 255 || params->indel_BQ_max < 1 || params->indel_BQ_max > 32767) return fail(UVCGPU_EUNSUPPORTED, "indel_vntr_repeatsize_max > 255 or indel_BQ_max outside 1..32767");
-    // dist_to_interfering_indel is 10000 where a read has no low-quality InDel (main.hpp:1897) and a difference of GENOME coordinates next to
-    // the sentinels of its InDel list otherwise: a threshold above 10000 compares with those.  The kernels carry the distance in 16 bits with
-    // "10000 or more" as one value, which is exact for every threshold up to 10000 (the default is 5) and wrong beyond: refused, not approximated.
-    if (params->bias_thres_interfering_indel > 10000) return fail(UVCGPU_EUNSUPPORTED, "bias_thres_interfering_indel above 10000");
+    if (const int rc = uvcgpu_params_check(params)) return rc;   // uvc_params.cpp: the value refusals, also for callers that check before they open anything
     uvcgpu_region *r = new uvcgpu_region();
     memset(&r->prof, 0, sizeof(r->prof));
     memset(&r->R, 0, sizeof(r->R));

@@ -24,7 +24,7 @@ FILTERS = ["Q10", "Q20", "Q30", "Q40", "Q50", "Q60", "PASS"]
 
 
 def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None, molecule_tag=0, disable_duplex=0, correct_bq=True, all_out=False, keep_handle=False, reuse=None, vcf=False,
-                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None):
+                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0):
     """Scores [beg, end) of `chrom`.  Returns None when no read passes the filters (process_batch returns -1, main.cpp:520-523), else a
     dict: records (field -> int32 array), alleles (InDel allele rows), score range, region handle (if keep_handle).
     Tiles of one stretch: the reference scores zerobased_pos rpos_beg .. rpos_end inclusive and skips the BASE sub-position of the first
@@ -34,7 +34,8 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     tiles writes the records of one uncut region.  `region_beg`: begin of the BED line / contig range the run belongs to (incluBegPosition
     of main.cpp:655-656, default `beg`).  `tumor_vcf`: normal sample of a T/N pair -- the tumor pass's VCF as `uvc_amd.io.TumorVcf` (its records
     of this region become UvcScoreRequest::tumor_keys; `params.tumor_vcf_is_provided` must be set).  `umi_struct`: the in-read UMI pattern
-    (the reference's environment variable ONE_STEP_UMI_STRUCT).
+    (the reference's environment variable ONE_STEP_UMI_STRUCT).  `assay_type`: 0 infers is_amplicon per region from the family pass, 1 (CAPTURE)
+    and 2 (AMPLICON) override it (--assay-type, main.cpp:510-511).
     `reuse`: a dict the caller keeps between calls; the region handle lives in it and is reset for every new region instead of being
     created and destroyed (its device buffers survive while the regions do not grow)."""
     import os, time
@@ -83,7 +84,7 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     if correct_bq:
         R.correct_bq()
     R.accumulate()
-    is_amplicon = (g["n_amplicon"] * 2 > g["n_kept"])                                  # !is_by_capture, main.cpp:507-508
+    is_amplicon = (g["n_amplicon"] * 2 > g["n_kept"]) if assay_type == 0 else (assay_type == 2)   # !is_by_capture / inferred_assay_type, main.cpp:507-511
     last_excl = min(end, bam_end + 1) if has_next else min(rpos_end + 1, ext_end)      # zerobased_pos `end` belongs to the tile behind, if there is one
     skw = dict(pos_beg=rpos_beg, pos_end=last_excl, base_at_pos_beg=bool(continues and rpos_beg == beg and beg > ext_beg), region_beg=(beg if region_beg is None else region_beg))
     score_range = (skw["pos_beg"], skw["pos_end"])
@@ -113,7 +114,7 @@ def contig_tiles(beg, end, tile):
     return [dict(beg=b, end=min(b + tile, end), continues=(b != beg), has_next=(b + tile < end), region_beg=beg) for b in range(beg, end, tile)]
 
 
-def call_contig(lib, bam, fasta, chrom, beg=0, end=None, tile=1_000_000, workers=1, device=None, only=None, **kw):
+def call_contig(lib, bam, fasta, chrom, beg=0, end=None, tile=1_000_000, workers=1, device=None, only=None, assay_type=0, **kw):
     """Tiles [beg, end) of a contig (default: all of it) and yields the result of every tile that has reads, in order.  The reference cuts
     its regions by read and position counts (SamIter, grouping.cpp:28-67, 157-314) and scores the shared end point of two adjacent
     regions in both; here fixed tiles of the size the state slab is laid out for are used and every zerobased_pos has one owner
@@ -150,7 +151,7 @@ def call_contig(lib, bam, fasta, chrom, beg=0, end=None, tile=1_000_000, workers
             local.reuse = {}                                   # one region handle per worker, reset from tile to tile
             if device is not None and lib.prefix == "uvcgpu_" and lib.dll.uvcgpu_init(int(device)) != 0:   # hipSetDevice is per thread
                 raise RuntimeError(lib.last_error())
-        return call_region(lib, hb, hf, chrom, t["beg"], t["end"], reuse=local.reuse, continues=t["continues"], has_next=t["has_next"], region_beg=t["region_beg"], **kw)
+        return call_region(lib, hb, hf, chrom, t["beg"], t["end"], reuse=local.reuse, continues=t["continues"], has_next=t["has_next"], region_beg=t["region_beg"], assay_type=assay_type, **kw)
     if workers <= 1:
         for b in starts:
             res = one(b)
@@ -188,7 +189,7 @@ def write_tsv(res, fh, kept_only=True, header=True):
             rec["cVQ1"][i], rec["cVQ2"][i], rec["TLODQ"][i], rec["NLODQ"][i], rec["germ_GT"][i], rec["germ_GQ"][i]))
 
 
-def write_vcf(lib, bam, fasta, chrom, beg, end, path, sample="SAMPLE", params=None, tumor_vcf=None, **kw):
+def write_vcf(lib, bam, fasta, chrom, beg, end, path, sample="SAMPLE", params=None, tumor_vcf=None, assay_type=0, **kw):
     """BAM + FASTA -> VCF: the header (uvcgpu_vcf_header) and the record lines of every tile, through the BGZF writer when `path` ends in
     .gz (what the reference does with bgzf_write, main.cpp:1196-1215, 1571-1583), else as plain text ("-" = stdout).  Returns the number
     of record lines."""
@@ -201,7 +202,7 @@ def write_vcf(lib, bam, fasta, chrom, beg, end, path, sample="SAMPLE", params=No
     n = 0
     try:
         sink.write(header)
-        for res in call_contig(lib, bam, fasta, chrom, beg, end, vcf=True, params=params, **kw):
+        for res in call_contig(lib, bam, fasta, chrom, beg, end, vcf=True, params=params, assay_type=assay_type, **kw):
             sink.write(res["vcf"]); n += res["vcf"].count("\n")
     finally:
         if sink is not sys.stdout:

@@ -66,6 +66,47 @@ def apply_platform(p, platform, central_readlen, max_mapq):
         p.syserr_minABQ_cap_indel += 100
 
 
+def _param_fn(name, restype, argtypes):
+    f = getattr(gpu_lib().dll, "uvcgpu_" + name)
+    f.restype, f.argtypes = restype, argtypes
+    return f
+
+
+def param_table():
+    """Every row of include/uvc_params.def, then of include/uvc_group_params.def (uvcgpu_param_info): list of dicts name, kind ("int" /
+    "double"), owner ("params" / "group"), default, settable (False for the derived rows inferred_*, tumor_vcf_*)."""
+    info = _param_fn("param_info", C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)])
+    rows = []
+    for i in range(_param_fn("param_count", C.c_int32, [])()):
+        name, kind, owner, dflt, settable = C.c_char_p(), C.c_int32(), C.c_int32(), C.c_double(), C.c_int32()
+        if info(i, C.byref(name), C.byref(kind), C.byref(owner), C.byref(dflt), C.byref(settable)) != 0:
+            raise UvcError(_ffi.ENUMS["UVCGPU_EINVAL"], gpu_lib().last_error())
+        rows.append(dict(name=name.value.decode(), kind=("int" if kind.value == _ffi.ENUMS["UVC_PARAM_INT"] else "double"),
+                         owner=("group" if owner.value == _ffi.ENUMS["UVC_PARAM_OF_GROUP"] else "params"),
+                         default=(int(dflt.value) if kind.value == _ffi.ENUMS["UVC_PARAM_INT"] else dflt.value), settable=bool(settable.value)))
+    return rows
+
+
+def set_param(params, group_params, name, value):
+    """uvcgpu_param_set: the row `name` (field or option form) of `params` (a _ffi.UvcParams) or `group_params` (a group.UvcGroupParams; either
+    may be None when the row is not its) from `value` (a number, a bool or its text), parsed as the command line parses it.  Raises UvcError."""
+    if isinstance(value, bool):
+        value = int(value)
+    text = repr(float(value)) if isinstance(value, float) else str(value)
+    f = _param_fn("param_set", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p])
+    rc = f(C.addressof(params) if params is not None else None, C.addressof(group_params) if group_params is not None else None, name.encode(), text.encode())
+    if rc != 0:
+        raise UvcError(rc, gpu_lib().last_error())
+
+
+def apply_platform_ex(params, sequencing_platform, inferred, central_readlen, max_mapq):
+    """uvcgpu_params_apply_platform_ex: the platform step of a requested --sequencing-platform (0 AUTO, 1 ILLUMINA, 2 IONTORRENT, 3 OTHER)."""
+    f = _param_fn("params_apply_platform_ex", C.c_int, [C.POINTER(_ffi.UvcParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32])
+    rc = f(C.byref(params), sequencing_platform, inferred, central_readlen, max_mapq)
+    if rc != 0:
+        raise UvcError(rc, gpu_lib().last_error())
+
+
 _READ_FIELDS = [("pos", np.int32), ("mpos", np.int32), ("isize", np.int32), ("flag", np.uint16), ("mapq", np.uint8), ("nm", np.int32),
                 ("l_qseq", np.int32), ("seq_off", np.int64), ("cigar_off", np.int64), ("n_cigar", np.int32),
                 ("frag_id", np.int32), ("fam_id", np.int32), ("fam_strand", np.uint8)]
