@@ -366,6 +366,8 @@ typedef struct uvcgpu_region uvcgpu_region_t;
 int uvcgpu_init(int device_id);
 /* Number of HIP devices visible to the process (0 when there is none); the region-shard dispatchers spread their workers over them. */
 int uvcgpu_device_count(void);
+/* hipMemGetInfo of the device the calling thread is bound to (uvcgpu_init): free and total bytes of device memory. */
+int uvcgpu_device_memory(int64_t *free_bytes, int64_t *total_bytes);
 const char *uvcgpu_last_error(void);
 const char *uvcgpu_version(void);
 

@@ -92,10 +92,20 @@ int uvcio_plan_regions(const int32_t *tid, const int32_t *pos, const int32_t *en
  * `contig_names` maps CHROM to tid (the BAM header's order). */
 typedef struct uvcio_tumor_vcf uvcio_tumor_vcf_t;
 int uvcio_tumor_vcf_open(uvcio_tumor_vcf_t **out, const char *path, const char *const *contig_names, int32_t n_contigs, int32_t is_tumor_format_retrieved);
+/* The same records without a file: the tumor pass hands its record lines over in memory (uvc1-mi355x --normal-bam).  The handle starts
+ * empty; uvcio_tumor_vcf_add_lines parses record lines with the parser of uvcio_tumor_vcf_open (header lines are skipped, `sample_name`
+ * is what uvcio_tumor_vcf_sample_name returns).  Lines of any number of tiles, in any order; records of one key keep the order in which
+ * they were added, so after adds in genome order (tile by tile, the order a tumor VCF holds them in) fetch and n_records return what
+ * uvcio_tumor_vcf_open returns on a file of the same lines.  Adds and fetches may come from several threads at once. */
+int uvcio_tumor_vcf_create(uvcio_tumor_vcf_t **out, const char *sample_name, const char *const *contig_names, int32_t n_contigs,
+                           int32_t is_tumor_format_retrieved);
+int uvcio_tumor_vcf_add_lines(uvcio_tumor_vcf_t *v, const char *text, int64_t len);
 const char *uvcio_tumor_vcf_sample_name(const uvcio_tumor_vcf_t *v);   /* last column of the #CHROM line ("" if there is none) */
 int64_t uvcio_tumor_vcf_n_records(const uvcio_tumor_vcf_t *v);
 /* The records of `tid` with pos_beg <= symbolpos <= pos_end, sorted by (symbolpos, symbol) -- tkis_beg .. tkis_end of main.cpp:532-533 --
- * as UvcScoreRequest::tumor_keys / tumor_sample_columns / tumor_ref_alt take them.  The arrays belong to the handle (valid until it is closed). */
+ * as UvcScoreRequest::tumor_keys / tumor_sample_columns / tumor_ref_alt take them.  The arrays belong to the handle.  A handle of
+ * uvcio_tumor_vcf_open: valid until it is closed.  A handle of uvcio_tumor_vcf_create: a copy in storage the handle keeps for the calling
+ * thread, valid until that thread's next fetch on the handle or its close; other threads' adds and fetches leave it alone. */
 int uvcio_tumor_vcf_fetch(const uvcio_tumor_vcf_t *v, int32_t tid, int32_t pos_beg, int32_t pos_end, const UvcTumorKey **keys, const char *const **sample_columns,
                           const char *const **ref_alts, int64_t *n);
 void uvcio_tumor_vcf_close(uvcio_tumor_vcf_t *v);

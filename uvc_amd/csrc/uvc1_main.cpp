@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -87,6 +88,10 @@ const OptRow OPTS[] = {
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
+    { "--normal-bam", O_CLI, false, "", "T/N pair in one run (uvcTN.sh): the normal sample's BAM; inputBAM is the tumor's, -o the normal VCF" },
+    { "--tumor-output", O_CLI, false, "", "with --normal-bam: the tumor VCF" },
+    { "--tumor-params", O_CLI, true, "", "with --normal-bam: the options after it go to the tumor side only" },
+    { "--normal-params", O_CLI, true, "", "with --normal-bam: the options after it go to the normal side only" },
     { "--print-params", O_CLI, true, "", "print the resolved parameters as name=value lines in .def order and exit (no device)" },
     { "-h,--help", O_CLI, true, "", "this text" },
     { "-v,--version", O_CLI, true, "", "the version" },
@@ -161,6 +166,8 @@ void help() {
     printf("usage: uvc1-mi355x inputBAM -f ref.fa -o out.vcf.gz [options]\n"
            "       uvc1-mi355x /only-print-vcf-header/ [options]     the VCF header of the resolved parameters on stdout\n"
            "       uvc1-mi355x inputBAM --print-params [options]     the resolved parameters as name=value lines\n"
+           "       uvc1-mi355x TUMOR.bam --normal-bam NORMAL.bam -f ref.fa -o normal.vcf.gz --tumor-output tumor.vcf.gz -s TUM,NOR [options]\n"
+           "                   [--tumor-params OPT..] [--normal-params OPT..]     a tumor/normal pair in one run (uvcTN.sh)\n"
            "       uvc1-mi355x --concat out.vcf.gz shard0.vcf.gz shard1.vcf.gz ...\n"
            "Every option takes `--opt value` or `--opt=value`.  User values come first, then the platform step of --sequencing-platform\n"
            "adds its deltas on top of them (CmdLineArgs.cpp:37-134).  [CLASS]: PARAM / GROUP = a parameter of the hot path / of the family\n"
@@ -240,6 +247,7 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--bed-in-fname") o.bed_in = val();
         else if (n0 == "--repeat") o.repeat = std::max(1, atoi(val().c_str()));   // benchmark aid: the tile list n times (steady state on a small file)
         else if (n0 == "--print-params") o.print_params = true;
+        else if (n0 == "--normal-bam" || n0 == "--tumor-output" || n0 == "--tumor-params" || n0 == "--normal-params") die(name + " belongs to pair mode (split_pair)");
         else if (n0 == "-h") { help(); exit(0); }
         else if (n0 == "-v") { printf("uvc1-mi355x (%s)\n", uvcgpu_version()); exit(0); }
         // MODE
@@ -265,12 +273,12 @@ Opts parse(int argc, char **argv) {
 }
 
 // --print-params: every row of both tables, in .def order
-void print_params(const Opts &o) {
+void print_params(const Opts &o, const char *prefix = "") {
     for (int32_t i = 0, n = uvcgpu_param_count(); i < n; i++) {
         const char *nm; int32_t kind; double v;
         uvcgpu_param_info(i, &nm, &kind, nullptr, nullptr, nullptr);
         uvcgpu_param_get(&o.P, &o.G, i, &v);
-        printf("%s=%s\n", nm, fmt_value(kind, v).c_str());
+        printf("%s%s=%s\n", prefix, nm, fmt_value(kind, v).c_str());
     }
 }
 
@@ -293,7 +301,9 @@ struct Worker {
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // process_batch for one tile; appends the record lines to `lines`; false = nothing to call there.  *n_kept_reads: reads that passed the filters.
-bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads) {
+// `tumor_ready` (pair mode): called with the tumor records' range before they are fetched; returns once the store holds all of them
+bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads,
+               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr) {
     double t0 = now();
     *n_kept_reads = 0;
     UvcBamBatch b;
@@ -350,6 +360,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     rq.base_at_pos_beg = (t.continues && first == t.beg && t.beg > ext_beg) ? 1 : 0; rq.region_beg = (int32_t)t.run_beg;
     if (tvcf) {   // normal sample of a T/N pair: the tumor records of this region (tkis_beg .. tkis_end, main.cpp:532-533)
         const UvcTumorKey *keys = nullptr; const char *const *cols = nullptr, *const *ras = nullptr; int64_t nk = 0;
+        if (tumor_ready) (*tumor_ready)(t.tid, ext_beg, ext_end);
         if (uvcio_tumor_vcf_fetch(tvcf, t.tid, (int32_t)ext_beg, (int32_t)ext_end, &keys, &cols, &ras, &nk)) die(uvcio_last_error());
         rq.tumor_keys = keys; rq.n_tumor_keys = nk; rq.tumor_sample_columns = (o.tumor_format ? cols : nullptr); rq.tumor_ref_alt = ras;
     }
@@ -381,43 +392,31 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     w.t_text += now() - t0;
     return true;
 }
-}   // namespace
+struct Geometry {   // the contigs of a BAM header
+    std::vector<std::string> names; std::vector<int64_t> lens; std::vector<const char *> cnames;
+    int32_t tid_of(const std::string &chrom) const { for (int32_t i = 0; i < (int32_t)names.size(); i++) if (names[(size_t)i] == chrom) return i; return -1; }
+};
+uvcio_bam_t *open_bam(const std::string &path, Geometry &g) {
+    uvcio_bam_t *bam0 = nullptr;
+    if (uvcio_bam_open(&bam0, path.c_str())) die(uvcio_last_error());
+    if (!uvcio_bam_has_index(bam0)) fprintf(stderr, "uvc1-mi355x: no .bai next to %s, every tile scans the file\n", path.c_str());
+    const int32_t nref = uvcio_bam_n_refs(bam0);
+    for (int32_t i = 0; i < nref; i++) { g.names.push_back(uvcio_bam_ref_name(bam0, i)); g.lens.push_back(uvcio_bam_ref_len(bam0, i)); }
+    for (auto &s : g.names) g.cnames.push_back(s.c_str());
+    return bam0;
+}
 
-int main(int argc, char **argv) {
-    if (argc >= 3 && !strcmp(argv[1], "--concat")) {   // bcftools concat -n (uvcTN.sh:100)
-        std::vector<const char *> in; for (int i = 3; i < argc; i++) in.push_back(argv[i]);
-        if (uvcio_bgzf_concat(argv[2], in.data(), (int32_t)in.size())) die(uvcio_last_error());
-        return 0;
-    }
-    Opts o = parse(argc, argv);
-    UvcParams &P = o.P;
-    std::string cmd; for (int i = 0; i < argc; i++) { cmd += argv[i]; cmd += "  "; }   // ##variantCallerCommand (main.hpp:5870-5874)
-    auto header = [&](const char *tsample, const char *const *cnames, const int64_t *lens, int32_t nref) {
-        // ##fileDate / ##reference / ##variantCallerCommand as generate_vcf_header prints them (main.hpp:5788-5794, 5870-5874)
-        char date[80]; { time_t raw; time(&raw); strftime(date, sizeof(date), "%F %T", localtime(&raw)); }
-        int64_t len = 0;
-        uvcgpu_vcf_header_ex(&P, o.sample.c_str(), tsample, cnames, lens, nref, date, o.fasta.c_str(), cmd.c_str(), nullptr, 0, &len);
-        std::string h((size_t)len, '\0');
-        if (uvcgpu_vcf_header_ex(&P, o.sample.c_str(), tsample, cnames, lens, nref, date, o.fasta.c_str(), cmd.c_str(), &h[0], len, &len)) die(uvcgpu_last_error());
-        return h;
-    };
-    // the platform step without a look at the file: a given ILLUMINA / IONTORRENT needs none, and the header mode has no file
-    // (main.cpp:1229-1240 prints the header there before any platform step; here a given platform's deltas are in it)
+// the platform step without a look at the file: a given ILLUMINA / IONTORRENT needs none, and the header mode has no file
+// (main.cpp:1229-1240 prints the header there before any platform step; here a given platform's deltas are in it)
+bool apply_given_platform(Opts &o) {
     const bool platform_given = (o.sequencing_platform == UVC_PLATFORM_ILLUMINA || o.sequencing_platform == UVC_PLATFORM_IONTORRENT);
-    if (platform_given) uvcgpu_params_apply_platform_ex(&P, o.sequencing_platform, 0, 0, 0);
-    if (o.bam == ONLY_PRINT_VCF_HEADER) {
-        if (!platform_given) P.inferred_sequencing_platform = o.sequencing_platform;
-        const std::string h = header(nullptr, nullptr, nullptr, 0);
-        fwrite(h.data(), 1, h.size(), stdout);
-        return 0;
-    }
-    if (o.print_params && platform_given) { print_params(o); return 0; }
-    // Each region handle has three streams and a worker's copies should run under another worker's kernels: with the runtime's default of four
-    // hardware queues the streams of different handles share queues, and a kernel then waits behind another handle's 10 ms copy (bench.py's
-    // pcie_inclusive leg: 16.0 ms per tile with 4 queues, 13.5 with 16).  Read by the HIP runtime when it starts; an explicit setting wins.
-    setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    // --print-params plans the region cuts with the same -t default as the run (the AUTO / OTHER inference reads the first region): the device
-    // count comes from the runtime's enumeration, no device is initialised; none visible = one
+    if (platform_given) uvcgpu_params_apply_platform_ex(&o.P, o.sequencing_platform, 0, 0, 0);
+    return platform_given;
+}
+
+// --print-params plans the region cuts with the same -t default as the run (the AUTO / OTHER inference reads the first region): the device
+// count comes from the runtime's enumeration, no device is initialised; none visible = one
+void default_devices_and_threads(Opts &o) {
     if (o.devices.empty()) {
         const int nd = uvcgpu_device_count();
         if (nd <= 0 && !o.print_params) die("no HIP device: uvc1-mi355x has no CPU path");
@@ -427,16 +426,16 @@ int main(int argc, char **argv) {
     // as half the cores this process may use keep the cores busy (measured on a 16-core quota: 4 -> 6.7, 8 -> 8-11, 12-16 -> 8-9.6 M positions/s),
     // never more than 8 per device (a region handle holds ~7 GB of planes) and at least one per device
     if (o.threads <= 0) { const int nd = (int)o.devices.size(); o.threads = std::max(nd, std::min(8 * nd, uvc_effective_cpus() / 2)); }
-    // the readers of all tiles in flight share one pool of inflate / decode threads inside libuvcio (as many as this process has cores:
-    // quota- and affinity-aware, uvc_cpus.h); UVCIO_THREADS overrides
-    uvcio_bam_t *bam0 = nullptr;
-    if (uvcio_bam_open(&bam0, o.bam.c_str())) die(uvcio_last_error());
-    if (!uvcio_bam_has_index(bam0)) fprintf(stderr, "uvc1-mi355x: no .bai next to %s, every tile scans the file\n", o.bam.c_str());
-    const int32_t nref = uvcio_bam_n_refs(bam0);
-    std::vector<std::string> names; std::vector<int64_t> lens; std::vector<const char *> cnames;
-    for (int32_t i = 0; i < nref; i++) { names.push_back(uvcio_bam_ref_name(bam0, i)); lens.push_back(uvcio_bam_ref_len(bam0, i)); }
-    for (auto &s : names) cnames.push_back(s.c_str());
-    // the tiles: --bed-in-fname / -R regions, --targets "chr" or "chr:beg-end" (1-based inclusive as in samtools), else every contig
+}
+
+// ownership of the shared end points: a tile whose predecessor ends where it begins continues that one's run
+void link_runs(std::vector<Tile> &tiles) {
+    for (size_t q = 1; q < tiles.size(); q++) if (tiles[q].tid == tiles[q - 1].tid && tiles[q].beg == tiles[q - 1].end) { tiles[q].continues = true; tiles[q - 1].has_next = true; tiles[q].run_beg = tiles[q - 1].run_beg; }
+}
+
+// the tiles: --bed-in-fname / -R regions, --targets "chr" or "chr:beg-end" (1-based inclusive as in samtools), else every contig
+std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G) {
+    const std::vector<std::string> &names = G.names; const std::vector<int64_t> &lens = G.lens; const int32_t nref = (int32_t)names.size();
     std::vector<Tile> tiles;
     const std::string bed_path = (!o.bed_in.empty() ? o.bed_in : o.bed);
     // Without --tile and without a BED file the regions are the ones the reference itself would hand to process_batch: one pass over the
@@ -496,51 +495,65 @@ int main(int argc, char **argv) {
         take_cuts();
         uvcio_planner_close(planner); planner = nullptr;
         fprintf(stderr, "uvc1-mi355x: %zu regions from the reference's cuts over %lld alignments (planning pass %.2f s)\n", tiles.size(), (long long)n_planned, now() - tp);
-        std::vector<int32_t>().swap(pl_tid); std::vector<int32_t>().swap(pl_pos); std::vector<int32_t>().swap(pl_end); std::vector<uint16_t>().swap(pl_flag);
     }
-    // ownership of the shared end points: a tile whose predecessor ends where it begins continues that one's run (fixed tiles only: the
-    // reference's own regions each write both end points, main.cpp:608, 643)
-    if (!ref_cuts)
-    for (size_t q = 1; q < tiles.size(); q++) if (tiles[q].tid == tiles[q - 1].tid && tiles[q].beg == tiles[q - 1].end) { tiles[q].continues = true; tiles[q - 1].has_next = true; tiles[q].run_beg = tiles[q - 1].run_beg; }
-    // --shard i/n: the i-th of n contiguous runs of the list, balanced by index bytes + positions
-    if (o.n_shards > 1) {
-        std::vector<int64_t> cost(tiles.size()); std::vector<int32_t> shard_of(tiles.size());
-        for (size_t q = 0; q < tiles.size(); q++) cost[q] = uvcio_bam_region_bytes(bam0, tiles[q].tid, tiles[q].beg, tiles[q].end) + (tiles[q].end - tiles[q].beg) / 8 + 1;
-        if (uvcio_plan_shards(cost.data(), (int64_t)cost.size(), o.n_shards, shard_of.data())) die(uvcio_last_error());
-        std::vector<Tile> mine;
-        for (size_t q = 0; q < tiles.size(); q++) if (shard_of[q] == o.shard) mine.push_back(tiles[q]);
-        fprintf(stderr, "uvc1-mi355x: shard %d of %d takes %zu of %zu tiles\n", o.shard, o.n_shards, mine.size(), tiles.size());
-        tiles.swap(mine);
-        if (o.shard > 0) o.no_header = true;
-    }
-    const size_t tiles_per_pass = tiles.size();
-    for (int rep = 1; rep < o.repeat; rep++) for (size_t q = 0; q < tiles_per_pass; q++) tiles.push_back(tiles[q]);
+    // fixed tiles only: the reference's own regions each write both end points (main.cpp:608, 643)
+    if (!ref_cuts) link_runs(tiles);
+    return tiles;
+}
 
-    // parameters: the reference's defaults and the user's values (parse); AUTO / OTHER infer platform and read length from the first
-    // alignments that are seen (CmdLineArgs.cpp:34-111 reads the first 5000 records of the file; here: of the first tile that has any)
-    if (!platform_given) {
-        int platform = UVC_PLATFORM_ILLUMINA, readlen = 150, maxmq = 0; bool seen = false;
-        for (size_t ti = 0; ti < tiles.size() && !seen; ti++) {
-            UvcBamBatch b;
-            if (uvcio_bam_fetch(bam0, tiles[ti].tid, tiles[ti].beg, tiles[ti].end, &b)) die(uvcio_last_error());
-            if (b.n_alns == 0) continue;
-            seen = true;
-            const int64_t m = std::min<int64_t>(b.n_alns, 5000);
-            std::vector<int32_t> ql{ 150 }; uint64_t pe = 0, q20f = 0, q30f = 0, q30p = 0;
-            for (int64_t i = 0; i < m; i++) {
-                maxmq = std::max<int>(maxmq, b.mapq[i]); pe += (b.flag[i] & 1); ql.push_back(b.l_qseq[i]);
-                for (int32_t q = 0; q < b.l_qseq[i]; q++) { const uint8_t bq = b.quals[b.seq_off[i] + q]; if (bq < 30) q30f++; else q30p++; if (bq < 20) q20f++; }
-            }
-            std::sort(ql.begin(), ql.end());
-            readlen = ql[ql.size() / 2];
-            const bool fix = ((int64_t)ql[ql.size() / 2] * 100 > (int64_t)ql.back() * 95);
-            if (!(pe > 0 || 4 * (q30f - q20f) < q30p || (2 * (q30f - q20f) < q30p && fix))) platform = UVC_PLATFORM_IONTORRENT;
+// --shard i/n: the i-th of n contiguous runs of the list, balanced by index bytes + positions
+std::vector<int32_t> plan_shard_of(const Opts &o, uvcio_bam_t *bam0, const std::vector<Tile> &tiles) {
+    std::vector<int64_t> cost(tiles.size()); std::vector<int32_t> shard_of(tiles.size());
+    for (size_t q = 0; q < tiles.size(); q++) cost[q] = uvcio_bam_region_bytes(bam0, tiles[q].tid, tiles[q].beg, tiles[q].end) + (tiles[q].end - tiles[q].beg) / 8 + 1;
+    if (uvcio_plan_shards(cost.data(), (int64_t)cost.size(), o.n_shards, shard_of.data())) die(uvcio_last_error());
+    return shard_of;
+}
+
+// parameters: the reference's defaults and the user's values (parse); AUTO / OTHER infer platform and read length from the first
+// alignments that are seen (CmdLineArgs.cpp:34-111 reads the first 5000 records of the file; here: of the first tile that has any)
+void infer_platform(Opts &o, uvcio_bam_t *bam0, const std::vector<Tile> &tiles) {
+    int platform = UVC_PLATFORM_ILLUMINA, readlen = 150, maxmq = 0; bool seen = false;
+    for (size_t ti = 0; ti < tiles.size() && !seen; ti++) {
+        UvcBamBatch b;
+        if (uvcio_bam_fetch(bam0, tiles[ti].tid, tiles[ti].beg, tiles[ti].end, &b)) die(uvcio_last_error());
+        if (b.n_alns == 0) continue;
+        seen = true;
+        const int64_t m = std::min<int64_t>(b.n_alns, 5000);
+        std::vector<int32_t> ql{ 150 }; uint64_t pe = 0, q20f = 0, q30f = 0, q30p = 0;
+        for (int64_t i = 0; i < m; i++) {
+            maxmq = std::max<int>(maxmq, b.mapq[i]); pe += (b.flag[i] & 1); ql.push_back(b.l_qseq[i]);
+            for (int32_t q = 0; q < b.l_qseq[i]; q++) { const uint8_t bq = b.quals[b.seq_off[i] + q]; if (bq < 30) q30f++; else q30p++; if (bq < 20) q20f++; }
         }
-        uvcgpu_params_apply_platform_ex(&P, o.sequencing_platform, platform, readlen, maxmq);
+        std::sort(ql.begin(), ql.end());
+        readlen = ql[ql.size() / 2];
+        const bool fix = ((int64_t)ql[ql.size() / 2] * 100 > (int64_t)ql.back() * 95);
+        if (!(pe > 0 || 4 * (q30f - q20f) < q30p || (2 * (q30f - q20f) < q30p && fix))) platform = UVC_PLATFORM_IONTORRENT;
     }
-    uvcio_bam_close(bam0);
-    if (o.print_params) { print_params(o); return 0; }
-    if (uvcgpu_init(o.devices[0])) die(uvcgpu_last_error());
+    uvcgpu_params_apply_platform_ex(&o.P, o.sequencing_platform, platform, readlen, maxmq);
+}
+
+// ##fileDate / ##reference / ##variantCallerCommand as generate_vcf_header prints them (main.hpp:5788-5794, 5870-5874)
+std::string vcf_header(const Opts &o, const std::string &cmd, const char *tsample, const char *const *cnames, const int64_t *lens, int32_t nref) {
+    char date[80]; { time_t raw; time(&raw); strftime(date, sizeof(date), "%F %T", localtime(&raw)); }
+    int64_t len = 0;
+    uvcgpu_vcf_header_ex(&o.P, o.sample.c_str(), tsample, cnames, lens, nref, date, o.fasta.c_str(), cmd.c_str(), nullptr, 0, &len);
+    std::string h((size_t)len, '\0');
+    if (uvcgpu_vcf_header_ex(&o.P, o.sample.c_str(), tsample, cnames, lens, nref, date, o.fasta.c_str(), cmd.c_str(), &h[0], len, &len)) die(uvcgpu_last_error());
+    return h;
+}
+
+// the region table of main.cpp:1415-1436 (--bed-out-fname): the shard manifest of the normal pass of a T/N pair
+void write_region_table(const Opts &o, const std::vector<const Tile *> &tiles, const std::vector<int64_t> &tile_reads) {
+    FILE *fo = fopen(o.bed_out.c_str(), "w");
+    if (!fo) die("cannot create " + o.bed_out);
+    for (size_t ti = 0; ti < tiles.size(); ti++)
+        fprintf(fo, "%s\t%lld\t%lld\tBedLineFlag\t%d\tNumberOfReadsInThisInterval\t%lld\tNumberOfRefBasesInThisInterval\t%lld\tTier1regionIndex\t0\tTier2regionIndex\t%d\tTier3regionIndex\t%zu\n",
+                tiles[ti]->chrom.c_str(), (long long)tiles[ti]->beg, (long long)tiles[ti]->end, tiles[ti]->continues ? 4 : 16, (long long)tile_reads[ti], (long long)(tiles[ti]->end - tiles[ti]->beg), o.shard, ti);
+    fclose(fo);
+}
+
+// The side-effect switches of the readers (process-wide, after uvcgpu_init of the first device).
+void reader_switches(const Opts &o) {
     // UVC1_PINNED=1: the workers' base / quality columns live in page-locked memory of the GPU library from here on, so that set_reads copies
     // them by DMA.  Off by default: on the boxes measured the files -> VCF rate did not move with it (scripts/bench_cli.py; the chain is not
     // bound by that copy) and it locks ~ 800 MB of host memory per worker.
@@ -554,10 +567,323 @@ int main(int argc, char **argv) {
     }
     if (getenv("UVC1_PINNED"))
         uvcio_set_column_allocator([](size_t n) -> void * { void *q = nullptr; return uvcgpu_host_alloc(&q, (int64_t)n) == 0 ? q : nullptr; }, [](void *q) { (void)uvcgpu_host_free(q); });
+}
+
+// ---- pair mode (--normal-bam): uvcTN.sh:27-50, 120-127 in one process ----
+// The command line split as uvcTN.sh splits it: options before the first --tumor-params / --normal-params go to both sides, after one of
+// them to that side only, until the other.  Side lists take PARAM / GROUP / MODE / INERT options; a CLI option there is refused.
+struct PairArgs { bool pair = false, side_lists = false; std::string normal_bam, tumor_out; std::vector<std::string> shared, side[2]; };
+PairArgs split_pair(int argc, char **argv) {
+    PairArgs a; int sec = -1;   // -1 both sides, 0 tumor, 1 normal
+    for (int i = 1; i < argc; i++) {
+        const std::string t = argv[i];
+        std::vector<std::string> &dst = (sec < 0 ? a.shared : a.side[sec]);
+        if (t.empty() || t[0] != '-') {
+            if (sec >= 0) die("'" + t + "' after " + (sec ? "--normal-params" : "--tumor-params") + ": a side list takes options only");
+            dst.push_back(t); continue;
+        }
+        std::string name = t, val; bool inl = false;
+        if (t.compare(0, 2, "--") == 0 && t.find('=') != std::string::npos) { name = t.substr(0, t.find('=')); val = t.substr(t.find('=') + 1); inl = true; }
+        if (name == "--tumor-params" || name == "--normal-params") {
+            if (inl) die(name + " takes no value");
+            sec = (name == "--tumor-params" ? 0 : 1); a.side_lists = true; continue;
+        }
+        const OptRow *row = find_opt(name);
+        if (row && row->cls == O_CLI && sec >= 0) die(name + " is a [CLI] option: it goes before --tumor-params / --normal-params (both sides)");
+        if (name == "--normal-bam" || name == "--tumor-output") {
+            if (!inl) { if (i + 1 >= argc) die("missing value of " + name); val = argv[++i]; }
+            if (name == "--normal-bam") { a.normal_bam = val; a.pair = true; } else a.tumor_out = val;
+            continue;
+        }
+        const bool takes_value = row ? !row->flag : (find_param(name) >= 0);   // an unknown option is refused by parse
+        dst.push_back(t);
+        if (takes_value && !inl && i + 1 < argc) dst.push_back(argv[++i]);
+    }
+    if (!a.pair) {
+        if (a.side_lists) die("--tumor-params / --normal-params need --normal-bam");
+        if (!a.tumor_out.empty()) die("--tumor-output needs --normal-bam");
+        return a;
+    }
+    if (a.normal_bam.empty()) die("--normal-bam needs a path");
+    for (size_t i = 0; i < a.shared.size(); i++) {
+        const std::string &t = a.shared[i];
+        const std::string name = t.substr(0, t.compare(0, 2, "--") == 0 ? t.find('=') : std::string::npos);
+        if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
+        if (name == "--repeat") die("--repeat cannot go with --normal-bam");
+        if (t == ONLY_PRINT_VCF_HEADER) die(std::string(ONLY_PRINT_VCF_HEADER) + " cannot go with --normal-bam");
+        const OptRow *row = (t[0] == '-' ? find_opt(name) : nullptr);
+        if (t[0] == '-' && t.find('=') == std::string::npos && ((row && !row->flag) || (!row && find_param(name) >= 0))) i++;   // skip the value
+    }
+    if (a.tumor_out.empty()) die("--normal-bam needs --tumor-output (the tumor VCF)");
+    return a;
+}
+Opts parse_side(const char *prog, const PairArgs &a, int side) {
+    std::vector<std::string> v{ prog, "--tn-is-paired", "1" };   // uvcTN.sh passes it in front of the side's own options: a later value wins
+    v.insert(v.end(), a.shared.begin(), a.shared.end());
+    v.insert(v.end(), a.side[side].begin(), a.side[side].end());
+    std::vector<char *> av; for (auto &x : v) av.push_back(&x[0]);
+    return parse((int)av.size(), av.data());
+}
+
+// One process runs both passes of uvcTN.sh: the tumor tiles first in the work order, their record lines written in order to the tumor VCF
+// and added in the same order to an in-memory store (uvcio_tumor_vcf_create), the normal tiles behind them.  A normal tile's tiles are
+// those the normal pass of the two-pass flow reads back from the tumor's region table; it starts its tumor fetch once every tumor tile that
+// reaches into its fetch range has been added.  With --shard i/n the process also runs the tumor tiles of other shards that its normal
+// tiles' fetch ranges reach (the halo) and writes nothing of them.
+int run_pair(Opts &ot, Opts &on, const std::string &cmd) {
+    Opts *side[2] = { &ot, &on };
+    const bool given_t = apply_given_platform(ot), given_n = apply_given_platform(on);
+    if (ot.print_params && given_t && given_n) { print_params(ot, "tumor."); print_params(on, "normal."); return 0; }
+    setenv("GPU_MAX_HW_QUEUES", "16", 0);   // as in the single-sample run (main)
+    default_devices_and_threads(ot);
+    on.devices = ot.devices; on.threads = ot.threads;
+    Geometry gt, gn;
+    uvcio_bam_t *tb0 = open_bam(ot.bam, gt), *nb0 = open_bam(on.bam, gn);
+    // the tumor pass's tiles, all of them (every shard needs the whole list: ownership and the halo are properties of it)
+    const std::vector<Tile> T = plan_tiles(ot, tb0, gt);
+    // the normal pass's tiles: the tumor's region table read back as BED lines (--bed-in-fname), each line cut into --tile tiles (1 Mb
+    // without), linked into runs where lines abut -- not the tumor's own tiles, whose reference cuts carry no `continues`
+    if (on.tile <= 0) on.tile = 1000000;
+    std::vector<int32_t> t2n(gt.names.size(), -1);
+    for (size_t i = 0; i < gt.names.size(); i++) t2n[i] = gn.tid_of(gt.names[i]);
+    std::vector<Tile> N; std::vector<size_t> n_src;
+    for (size_t g = 0; g < T.size(); g++) {
+        const int32_t tid = t2n[(size_t)T[g].tid];
+        if (tid < 0) die("the normal BAM's header has no contig " + T[g].chrom);
+        const int64_t e = std::min<int64_t>(T[g].end, gn.lens[(size_t)tid]);
+        for (int64_t b = std::max<int64_t>(0, T[g].beg); b < e; b += on.tile) { N.push_back(Tile{ tid, gn.names[(size_t)tid], b, std::min(b + on.tile, e), false, false, b }); n_src.push_back(g); }
+    }
+    link_runs(N);
+    // shards: a normal tile goes with the tumor tile it came from, so the shards' normal outputs concatenate to the one-process output
+    std::vector<char> t_own(T.size(), 1), t_run, n_own(N.size(), 1);
+    if (ot.n_shards > 1) {
+        const std::vector<int32_t> shard_of = plan_shard_of(ot, tb0, T);
+        for (size_t g = 0; g < T.size(); g++) t_own[g] = (shard_of[g] == ot.shard);
+        for (size_t j = 0; j < N.size(); j++) n_own[j] = t_own[n_src[j]];
+        if (ot.shard > 0) ot.no_header = on.no_header = true;
+    }
+    t_run = t_own;
+    if (ot.n_shards > 1) {
+        // the halo: a normal tile fetches its tumor records over [ext_beg, ext_end] (call_tile), its reads' extent plus MAX_STR_N_BASES.  Its
+        // reads are those of [beg - MAX_INSERT_SIZE, end + MAX_INSERT_SIZE); the reads that cross the two outer ends of a contig's own tiles
+        // bound every such range, so one query at each end gives the tumor tiles the shard needs
+        std::map<int32_t, std::pair<int64_t, int64_t>> span;
+        for (size_t j = 0; j < N.size(); j++) if (n_own[j]) {
+            auto it = span.find(N[j].tid);
+            if (it == span.end()) span[N[j].tid] = { N[j].beg, N[j].end };
+            else { it->second.first = std::min(it->second.first, N[j].beg); it->second.second = std::max(it->second.second, N[j].end); }
+        }
+        for (auto &sp : span) {
+            const int32_t tid = sp.first;
+            const int64_t L = std::max<int64_t>(0, sp.second.first - MAX_INSERT_SIZE), R = sp.second.second + MAX_INSERT_SIZE;
+            int64_t lo = L, hi = R;
+            UvcBamBatch b;
+            if (uvcio_bam_fetch(nb0, tid, L, L + 1, &b)) die(uvcio_last_error());
+            for (int64_t i = 0; i < b.n_alns; i++) lo = std::min<int64_t>(lo, b.pos[i]);
+            if (uvcio_bam_fetch(nb0, tid, R - 1, R, &b)) die(uvcio_last_error());
+            for (int64_t i = 0; i < b.n_alns; i++) hi = std::max<int64_t>(hi, b.endpos[i]);
+            lo -= MAX_STR_N_BASES; hi += MAX_STR_N_BASES;
+            for (size_t g = 0; g < T.size(); g++) if (t2n[(size_t)T[g].tid] == tid && T[g].beg - 1 <= hi && T[g].end + 1 >= lo) t_run[g] = 1;   // a tile's records lie in [beg, end]
+        }
+    }
+    std::vector<size_t> tj, nj;   // the jobs of this process: tumor tiles (own + halo), normal tiles (own), each in list order
+    std::vector<const Tile *> t_mine, n_mine;
+    for (size_t g = 0; g < T.size(); g++) { if (t_run[g]) tj.push_back(g); if (t_own[g]) t_mine.push_back(&T[g]); }
+    for (size_t j = 0; j < N.size(); j++) if (n_own[j]) { nj.push_back(j); n_mine.push_back(&N[j]); }
+    if (ot.n_shards > 1)
+        fprintf(stderr, "uvc1-mi355x: shard %d of %d takes %zu of %zu tiles (tumor; %zu more as the halo of its normal tiles) and %zu of %zu normal tiles\n",
+                ot.shard, ot.n_shards, t_mine.size(), T.size(), tj.size() - t_mine.size(), n_mine.size(), N.size());
+    // each side's parameters from its own BAM (the two-pass flow's inference, per command line)
+    auto own_tiles = [](const std::vector<const Tile *> &v) { std::vector<Tile> o; for (const Tile *t : v) o.push_back(*t); return o; };
+    if (!given_t) infer_platform(ot, tb0, own_tiles(t_mine));
+    if (!given_n) infer_platform(on, nb0, own_tiles(n_mine));
+    uvcio_bam_close(tb0); uvcio_bam_close(nb0);
+    if (ot.print_params) { print_params(ot, "tumor."); print_params(on, "normal."); return 0; }
+
+    // the dependencies: for each normal tid, every tumor tile on it as [beg - 1, end + 1] (where its records lie) with its job index (-1: not run here)
+    struct Dep { int64_t lo, hi; int64_t job; };
+    std::vector<std::vector<Dep>> deps(gn.names.size()); std::vector<int64_t> dep_span(gn.names.size(), 0);
+    { std::vector<int64_t> job_of(T.size(), -1); for (size_t k = 0; k < tj.size(); k++) job_of[tj[k]] = (int64_t)k;
+      for (size_t g = 0; g < T.size(); g++) { const int32_t tid = t2n[(size_t)T[g].tid]; deps[(size_t)tid].push_back(Dep{ T[g].beg - 1, T[g].end + 1, job_of[g] }); dep_span[(size_t)tid] = std::max(dep_span[(size_t)tid], T[g].end - T[g].beg + 2); }
+      for (auto &v : deps) std::sort(v.begin(), v.end(), [](const Dep &a, const Dep &b) { return a.lo < b.lo; }); }
+
+    if (uvcgpu_init(ot.devices[0])) die(uvcgpu_last_error());
+    reader_switches(ot);
+    // --timing: the device memory this process holds at its peak, from hipMemGetInfo before the handles and after every tile
+    std::map<int, int64_t> mem_base, mem_low;
+    if (ot.timing) {
+        for (int d : ot.devices) if (!mem_base.count(d)) { int64_t fr = 0; if (uvcgpu_init(d) || uvcgpu_device_memory(&fr, nullptr)) die(uvcgpu_last_error()); mem_base[d] = mem_low[d] = fr; }
+        if (uvcgpu_init(ot.devices[0])) die(uvcgpu_last_error());
+    }
+    uvcio_tumor_vcf_t *store = nullptr;
+    if (uvcio_tumor_vcf_create(&store, ot.sample.c_str(), gn.cnames.data(), (int32_t)gn.names.size(), on.tumor_format)) die(uvcio_last_error());
+    uvcio_bgzf_writer_t *zw[2] = { nullptr, nullptr };
+    for (int s = 0; s < 2; s++) if (uvcio_bgzf_write_open(&zw[s], side[s]->out.c_str(), 6)) die(uvcio_last_error());
+    if (!ot.no_header) {
+        const std::string ht = vcf_header(ot, cmd, nullptr, gt.cnames.data(), gt.lens.data(), (int32_t)gt.names.size());
+        const std::string hn = vcf_header(on, cmd, on.tumor_format ? ot.sample.c_str() : nullptr, gn.cnames.data(), gn.lens.data(), (int32_t)gn.names.size());
+        if (uvcio_bgzf_write(zw[0], ht.data(), (int64_t)ht.size()) || uvcio_bgzf_write(zw[1], hn.data(), (int64_t)hn.size())) die(uvcio_last_error());
+    }
+    const double t_start = now();
+    const std::vector<size_t> *jobs[2] = { &tj, &nj };
+    const std::vector<Tile> *tl[2] = { &T, &N };
+    const Geometry *geo[2] = { &gt, &gn };
+    std::vector<std::string> done[2] = { std::vector<std::string>(tj.size()), std::vector<std::string>(nj.size()) };
+    std::vector<char> ready[2] = { std::vector<char>(tj.size(), 0), std::vector<char>(nj.size(), 0) };
+    std::vector<int64_t> tile_reads(tj.size(), 0);
+    std::mutex mu; std::condition_variable cv; std::atomic<size_t> next{ 0 };
+    size_t written[2] = { 0, 0 };   // jobs each writer has taken (guarded by mu)
+    size_t t_added = 0;             // tumor jobs whose lines are in the store (guarded by mu): always a prefix of tj
+    const size_t n_jobs = tj.size() + nj.size();
+    const int nthreads = (int)std::min<size_t>((size_t)ot.threads, std::max<size_t>(n_jobs, 1));
+    const size_t max_ahead = (size_t)4 * (size_t)nthreads;
+    // a normal tile's tumor records over [a, b] of `tid` are complete once every tumor tile that reaches into the range is in the store
+    const std::function<void(int32_t, int64_t, int64_t)> tumor_ready = [&](int32_t tid, int64_t a, int64_t b) {
+        const std::vector<Dep> &v = deps[(size_t)tid];
+        int64_t need = -1;
+        for (size_t q = (size_t)(std::upper_bound(v.begin(), v.end(), b, [](int64_t x, const Dep &d) { return x < d.lo; }) - v.begin()); q-- > 0;) {
+            if (v[q].lo + dep_span[(size_t)tid] < a) break;
+            if (v[q].hi < a) continue;
+            if (v[q].job < 0) die("a normal tile reaches tumor tiles outside the shard's halo (internal error)");
+            need = std::max(need, v[q].job);
+        }
+        std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return (int64_t)t_added > need; });
+    };
+    std::vector<Worker> workers[2] = { std::vector<Worker>((size_t)nthreads), std::vector<Worker>((size_t)nthreads) };
+    std::vector<std::thread> th;
+    for (int wi = 0; wi < nthreads; wi++) th.emplace_back([&, wi]() {
+        const int dev = ot.devices[(size_t)wi % ot.devices.size()];
+        if (uvcgpu_init(dev)) die(uvcgpu_last_error());   // binds this host thread to its device
+        for (int s = 0; s < 2; s++) if (uvcio_bam_open(&workers[s][(size_t)wi].bam, side[s]->bam.c_str()) || uvcio_fasta_open(&workers[s][(size_t)wi].fa, side[s]->fasta.c_str())) die(uvcio_last_error());
+        for (;;) {
+            const size_t q = next.fetch_add(1);
+            if (q >= n_jobs) break;
+            const int s = (q < tj.size() ? 0 : 1); const size_t k = (s ? q - tj.size() : q);
+            { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return k < written[s] + max_ahead; }); }   // bounded run-ahead of each writer
+            Worker &w = workers[s][(size_t)wi];
+            const Tile &t = (*tl[s])[(*jobs[s])[k]];
+            std::string lines; int64_t nk = 0;
+            call_tile(w, *side[s], side[s]->P, t, geo[s]->lens[(size_t)t.tid], s ? store : nullptr, lines, &nk, s ? &tumor_ready : nullptr);
+            w.n_tiles++;
+            int64_t fr = -1;
+            if (ot.timing && uvcgpu_device_memory(&fr, nullptr)) die(uvcgpu_last_error());
+            { std::lock_guard<std::mutex> g(mu); done[s][k].swap(lines); ready[s][k] = 1; if (!s) tile_reads[k] = nk; if (fr >= 0) mem_low[dev] = std::min(mem_low[dev], fr); }
+            cv.notify_all();
+        }
+        for (int s = 0; s < 2; s++) { Worker &w = workers[s][(size_t)wi]; if (w.reg) uvcgpu_region_destroy(w.reg); uvcio_bam_close(w.bam); uvcio_fasta_close(w.fa); }
+    });
+    // two writers, each in the order of its list: the tumor one also feeds the store, in that same order (records of one key then keep
+    // the order a tumor VCF holds them in)
+    int64_t n_lines[2] = { 0, 0 }, n_pos[2] = { 0, 0 };
+    auto writer = [&](int s) {
+        for (size_t k = 0; k < jobs[s]->size(); k++) {
+            std::string lines;
+            { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ready[s][k] != 0; }); lines.swap(done[s][k]); written[s] = k + 1; }
+            cv.notify_all();
+            const size_t ti = (*jobs[s])[k];
+            if (s == 1 || t_own[ti]) {
+                n_lines[s] += std::count(lines.begin(), lines.end(), '\n'); n_pos[s] += (*tl[s])[ti].end - (*tl[s])[ti].beg;
+                if (!lines.empty() && uvcio_bgzf_write(zw[s], lines.data(), (int64_t)lines.size())) die(uvcio_last_error());
+            }
+            if (s == 0) {
+                if (!lines.empty() && uvcio_tumor_vcf_add_lines(store, lines.data(), (int64_t)lines.size())) die(uvcio_last_error());
+                { std::lock_guard<std::mutex> g(mu); t_added = k + 1; }
+                cv.notify_all();
+            }
+        }
+    };
+    std::thread tumor_writer(writer, 0);
+    writer(1);
+    tumor_writer.join();
+    for (auto &t : th) t.join();
+    for (int s = 0; s < 2; s++) if (uvcio_bgzf_write_close(zw[s])) die(uvcio_last_error());
+    const int64_t n_tumor_records = uvcio_tumor_vcf_n_records(store);
+    uvcio_tumor_vcf_close(store);
+    if (!ot.bed_out.empty()) {
+        std::vector<int64_t> reads_mine;
+        for (size_t k = 0; k < tj.size(); k++) if (t_own[tj[k]]) reads_mine.push_back(tile_reads[k]);
+        write_region_table(ot, t_mine, reads_mine);
+    }
+    const double dt = now() - t_start;
+    for (int s = 0; s < 2; s++)
+        fprintf(stderr, "uvc1-mi355x: %s: %lld record lines from %zu tiles (%lld positions)\n", s ? "normal" : "tumor", (long long)n_lines[s], s ? n_mine.size() : t_mine.size(), (long long)n_pos[s]);
+    fprintf(stderr, "uvc1-mi355x: %lld tumor records handed to the normal tiles in memory; both passes in %.2f s, %d tiles in flight on %zu device(s)\n",
+            (long long)n_tumor_records, dt, nthreads, ot.devices.size());
+    if (ot.timing) {
+        for (int s = 0; s < 2; s++) {
+            double f = 0, g = 0, r = 0, x2 = 0, k = 0, x = 0;
+            for (auto &w : workers[s]) { f += w.t_fetch; g += w.t_group; r += w.t_region; x2 += w.t_reads; k += w.t_gpu; x += w.t_text; }
+            fprintf(stderr, "  %s thread-seconds: fetch %.2f, digest+group %.2f, reference+region %.2f, set_reads %.2f, bq+accumulate+score %.2f, record text %.2f\n", s ? "normal" : "tumor", f, g, r, x2, k, x);
+        }
+        for (size_t wi = 0; wi < (size_t)nthreads; wi++) fprintf(stderr, "  worker %zu on device %d: %lld tumor tiles, %lld normal tiles\n", wi, ot.devices[wi % ot.devices.size()], (long long)workers[0][wi].n_tiles, (long long)workers[1][wi].n_tiles);
+        std::string m;
+        for (auto &b : mem_base) { char buf[160]; snprintf(buf, sizeof(buf), "%sdevice %d %.2f GB", m.empty() ? "" : ", ", b.first, (b.second - mem_low[b.first]) / 1e9); m += buf; }
+        fprintf(stderr, "  device memory at the peak (hipMemGetInfo, %d tiles in flight, a tumor and a normal region handle each): %s\n", nthreads, m.c_str());
+    }
+    return 0;
+}
+}   // namespace
+
+int main(int argc, char **argv) {
+    if (argc >= 3 && !strcmp(argv[1], "--concat")) {   // bcftools concat -n (uvcTN.sh:100)
+        std::vector<const char *> in; for (int i = 3; i < argc; i++) in.push_back(argv[i]);
+        if (uvcio_bgzf_concat(argv[2], in.data(), (int32_t)in.size())) die(uvcio_last_error());
+        return 0;
+    }
+    std::string cmd; for (int i = 0; i < argc; i++) { cmd += argv[i]; cmd += "  "; }   // ##variantCallerCommand (main.hpp:5870-5874)
+    const PairArgs pa = split_pair(argc, argv);
+    if (pa.pair) {
+        Opts ot = parse_side(argv[0], pa, 0), on = parse_side(argv[0], pa, 1);
+        ot.out = pa.tumor_out;
+        if (ot.out == on.out) die("--tumor-output is the same file as -o");
+        on.bam = pa.normal_bam;
+        on.P.tumor_vcf_is_provided = 1;   // the normal pass of uvcTN.sh has --tumor-vcf
+        on.bed_out.clear();               // the region table is the tumor pass's
+        const size_t c = ot.sample.find(',');   // -s TUM,NOR; one name N gives N_T and N_N (uvcTN.sh:71-80)
+        if (c != std::string::npos) { on.sample = ot.sample.substr(c + 1); ot.sample = ot.sample.substr(0, c); }
+        else { on.sample = ot.sample + "_N"; ot.sample += "_T"; }
+        return run_pair(ot, on, cmd);
+    }
+    Opts o = parse(argc, argv);
+    UvcParams &P = o.P;
+    const bool platform_given = apply_given_platform(o);
+    if (o.bam == ONLY_PRINT_VCF_HEADER) {
+        if (!platform_given) P.inferred_sequencing_platform = o.sequencing_platform;
+        const std::string h = vcf_header(o, cmd, nullptr, nullptr, nullptr, 0);
+        fwrite(h.data(), 1, h.size(), stdout);
+        return 0;
+    }
+    if (o.print_params && platform_given) { print_params(o); return 0; }
+    // Each region handle has three streams and a worker's copies should run under another worker's kernels: with the runtime's default of four
+    // hardware queues the streams of different handles share queues, and a kernel then waits behind another handle's 10 ms copy (bench.py's
+    // pcie_inclusive leg: 16.0 ms per tile with 4 queues, 13.5 with 16).  Read by the HIP runtime when it starts; an explicit setting wins.
+    setenv("GPU_MAX_HW_QUEUES", "16", 0);
+    default_devices_and_threads(o);
+    // the readers of all tiles in flight share one pool of inflate / decode threads inside libuvcio (as many as this process has cores:
+    // quota- and affinity-aware, uvc_cpus.h); UVCIO_THREADS overrides
+    Geometry G;
+    uvcio_bam_t *bam0 = open_bam(o.bam, G);
+    const int32_t nref = (int32_t)G.names.size();
+    std::vector<Tile> tiles = plan_tiles(o, bam0, G);
+    if (o.n_shards > 1) {
+        const std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
+        std::vector<Tile> mine;
+        for (size_t q = 0; q < tiles.size(); q++) if (shard_of[q] == o.shard) mine.push_back(tiles[q]);
+        fprintf(stderr, "uvc1-mi355x: shard %d of %d takes %zu of %zu tiles\n", o.shard, o.n_shards, mine.size(), tiles.size());
+        tiles.swap(mine);
+        if (o.shard > 0) o.no_header = true;
+    }
+    const size_t tiles_per_pass = tiles.size();
+    for (int rep = 1; rep < o.repeat; rep++) for (size_t q = 0; q < tiles_per_pass; q++) tiles.push_back(tiles[q]);
+    if (!platform_given) infer_platform(o, bam0, tiles);
+    uvcio_bam_close(bam0);
+    if (o.print_params) { print_params(o); return 0; }
+    if (uvcgpu_init(o.devices[0])) die(uvcgpu_last_error());
+    reader_switches(o);
     // T/N: the tumor pass's records (rescue_variants_from_vcf, main.cpp:183-398)
     uvcio_tumor_vcf_t *tvcf = nullptr;
     if (!o.tumor_vcf.empty()) {
-        if (uvcio_tumor_vcf_open(&tvcf, o.tumor_vcf.c_str(), cnames.data(), nref, o.tumor_format)) die(uvcio_last_error());
+        if (uvcio_tumor_vcf_open(&tvcf, o.tumor_vcf.c_str(), G.cnames.data(), nref, o.tumor_format)) die(uvcio_last_error());
         fprintf(stderr, "uvc1-mi355x: %lld tumor records from %s\n", (long long)uvcio_tumor_vcf_n_records(tvcf), o.tumor_vcf.c_str());
     }
 
@@ -565,7 +891,7 @@ int main(int argc, char **argv) {
     uvcio_bgzf_writer_t *zw = nullptr;
     if (uvcio_bgzf_write_open(&zw, o.out.c_str(), 6)) die(uvcio_last_error());
     if (!o.no_header) {
-        const std::string h = header((tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, cnames.data(), lens.data(), nref);
+        const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
     }
     const double t_start = now();
@@ -587,7 +913,7 @@ int main(int argc, char **argv) {
             // 4 * threads in front of it, so a slow early tile cannot make the rest of the genome pile up in memory
             { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ti < written + max_ahead; }); }
             std::string lines; int64_t nk = 0;
-            call_tile(w, o, P, tiles[ti], lens[(size_t)tiles[ti].tid], tvcf, lines, &nk);
+            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, &nk);
             w.n_tiles++;
             { std::lock_guard<std::mutex> g(mu); done[ti].swap(lines); ready[ti] = 1; tile_reads[ti] = nk; }
             cv.notify_all();
@@ -607,13 +933,9 @@ int main(int argc, char **argv) {
     for (auto &t : th) t.join();
     if (uvcio_bgzf_write_close(zw)) die(uvcio_last_error());
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
-    if (!o.bed_out.empty()) {   // the region table of main.cpp:1415-1436 (--bed-out-fname): the shard manifest of the normal pass of a T/N pair
-        FILE *fo = fopen(o.bed_out.c_str(), "w");
-        if (!fo) die("cannot create " + o.bed_out);
-        for (size_t ti = 0; ti < tiles_per_pass; ti++)
-            fprintf(fo, "%s\t%lld\t%lld\tBedLineFlag\t%d\tNumberOfReadsInThisInterval\t%lld\tNumberOfRefBasesInThisInterval\t%lld\tTier1regionIndex\t0\tTier2regionIndex\t%d\tTier3regionIndex\t%zu\n",
-                    tiles[ti].chrom.c_str(), (long long)tiles[ti].beg, (long long)tiles[ti].end, tiles[ti].continues ? 4 : 16, (long long)tile_reads[ti], (long long)(tiles[ti].end - tiles[ti].beg), o.shard, ti);
-        fclose(fo);
+    if (!o.bed_out.empty()) {
+        std::vector<const Tile *> pass; for (size_t ti = 0; ti < tiles_per_pass; ti++) pass.push_back(&tiles[ti]);
+        write_region_table(o, pass, tile_reads);
     }
     const double dt = now() - t_start;
     fprintf(stderr, "uvc1-mi355x: %lld record lines from %zu tiles (%lld positions) in %.2f s = %.2f M positions/s, %d tiles in flight on %zu device(s)\n",

@@ -190,6 +190,14 @@ int uvcgpu_init(int device_id) {
     return 0;
 }
 
+int uvcgpu_device_memory(int64_t *free_bytes, int64_t *total_bytes) {
+    size_t fr = 0, tot = 0;
+    HIP_OK(hipMemGetInfo(&fr, &tot));
+    if (free_bytes) *free_bytes = (int64_t)fr;
+    if (total_bytes) *total_bytes = (int64_t)tot;
+    return 0;
+}
+
 int uvcgpu_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; } return n; }
 
 void uvcgpu_params_default(UvcParams *p) {

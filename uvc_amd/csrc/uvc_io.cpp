@@ -9,6 +9,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <climits>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -905,8 +907,12 @@ extern "C" int uvcio_read_text_file(const char *path, char **out, int64_t *len) 
 }
 
 // ---- the tumor VCF of a T/N pair: rescue_variants_from_vcf (main.cpp:183-398) on plain text ----
+namespace {
+struct TumorRec { int32_t tid; UvcTumorKey k; std::string col, ra; int64_t ord; };
+}
 struct uvcio_tumor_vcf {
     std::string sample;
+    // a file-backed handle (uvcio_tumor_vcf_open): sorted once, never changed; fetch returns pointers into these vectors
     std::vector<int32_t> tid;                   // per record, parallel to keys
     std::vector<UvcTumorKey> keys;              // sorted by (tid, refpos, symbol); records of one key keep their file order
     std::vector<std::string> cols_text;         // sample column of each record
@@ -914,6 +920,16 @@ struct uvcio_tumor_vcf {
     std::vector<std::string> ra_text;           // "REF\tALT" of each record (TumorKeyInfo::ref_alt)
     std::vector<const char *> ras;
     std::vector<int64_t> tid_first;             // [n_contigs + 1] first record of each tid
+    // an in-memory store (uvcio_tumor_vcf_create): per tid, the records ordered by (refpos, symbol, add order); map nodes never move, so the
+    // strings a fetch points at stay put while other threads add
+    bool is_store = false;
+    int32_t is_tumor_format_retrieved = 1;
+    std::map<std::string, int32_t> tid_of;
+    std::vector<std::map<std::tuple<int32_t, int32_t, int64_t>, TumorRec>> by_tid;
+    int64_t n_added = 0;
+    struct FetchBuf { std::vector<UvcTumorKey> keys; std::vector<const char *> cols, ras; };
+    std::map<std::thread::id, FetchBuf> fetch_buf;   // what the last fetch of each thread returned
+    mutable std::mutex mu;
 };
 namespace {
 // the comma-separated integers of one FORMAT value ("." = missing -> none)
@@ -928,17 +944,10 @@ int parse_ints(const char *p, const char *e, int32_t *out, int cap) {
     }
     return n;
 }
-}
-extern "C" int uvcio_tumor_vcf_open(uvcio_tumor_vcf_t **out, const char *path, const char *const *contig_names, int32_t n_contigs, int32_t is_tumor_format_retrieved) {
-    if (!out || !path || n_contigs < 0 || (n_contigs > 0 && !contig_names)) return fail(UVCGPU_EINVAL, "bad argument");
-    char *text = nullptr; int64_t len = 0;
-    int rc = uvcio_read_text_file(path, &text, &len);
-    if (rc) return rc;
-    std::map<std::string, int32_t> tid_of;
-    for (int32_t i = 0; i < n_contigs; i++) tid_of[contig_names[i]] = i;
-    uvcio_tumor_vcf *v = new uvcio_tumor_vcf();
-    struct Rec { int32_t tid; UvcTumorKey k; std::string col, ra; int64_t ord; };
-    std::vector<Rec> recs;
+// The record lines of `text` -> recs (ord = their index), in text order.  Header lines are skipped; `sample` (if not null)
+// takes the last column of the #CHROM line.  Returns the error text ("" = none).
+std::string parse_tumor_lines(const char *text, int64_t len, const std::map<std::string, int32_t> &tid_of, int32_t is_tumor_format_retrieved,
+                              std::string *sample, std::vector<TumorRec> &recs) {
     std::string err;
     const char *p = text, *end = text + len;
     int64_t lineno = 0;
@@ -949,7 +958,7 @@ extern "C" int uvcio_tumor_vcf_open(uvcio_tumor_vcf_t **out, const char *path, c
         if (le > line && le[-1] == '\r') le--;
         if (le == line) continue;
         if (line[0] == '#') {
-            if (le - line > 6 && !strncmp(line, "#CHROM", 6)) { const char *t = le; int tabs = 0; for (const char *q = line; q < le; q++) if (*q == '\t') tabs++; while (t > line && t[-1] != '\t') t--; v->sample = (tabs >= 9 ? std::string(t, le) : std::string()); }
+            if (sample && le - line > 6 && !strncmp(line, "#CHROM", 6)) { const char *t = le; int tabs = 0; for (const char *q = line; q < le; q++) if (*q == '\t') tabs++; while (t > line && t[-1] != '\t') t--; *sample = (tabs >= 9 ? std::string(t, le) : std::string()); }
             continue;
         }
         const char *f[11]; int nf = 0; f[nf++] = line;
@@ -978,7 +987,7 @@ extern "C" int uvcio_tumor_vcf_open(uvcio_tumor_vcf_t **out, const char *path, c
         };
         int32_t a2[4];
         if (get("VTI", a2, 4) != 2) continue;   // valsize <= 0 -> continue (main.cpp:275)
-        Rec r; memset(&r.k, 0, sizeof(r.k));
+        TumorRec r; memset(&r.k, 0, sizeof(r.k));
         r.tid = ti->second; r.ord = (int64_t)recs.size(); r.col = smp; r.ra = ref + "\t" + alt;
         const int symbol = a2[1];
         const long pos0 = strtol(fld(1).c_str(), nullptr, 10) - 1;   // line->pos
@@ -1002,25 +1011,81 @@ extern "C" int uvcio_tumor_vcf_open(uvcio_tumor_vcf_t **out, const char *path, c
         for (size_t k = 0; k < keys.size(); k++) if ((keys[k].second - keys[k].first) == 5 && !memcmp(keys[k].first, "_C2XP", 5)) r.k.tier2 = 1;   // enable_tier2_consensus_format_tags, main.cpp:386-388
         recs.push_back(std::move(r));
     }
+    return err;
+}
+}
+extern "C" int uvcio_tumor_vcf_open(uvcio_tumor_vcf_t **out, const char *path, const char *const *contig_names, int32_t n_contigs, int32_t is_tumor_format_retrieved) {
+    if (!out || !path || n_contigs < 0 || (n_contigs > 0 && !contig_names)) return fail(UVCGPU_EINVAL, "bad argument");
+    char *text = nullptr; int64_t len = 0;
+    int rc = uvcio_read_text_file(path, &text, &len);
+    if (rc) return rc;
+    std::map<std::string, int32_t> tid_of;
+    for (int32_t i = 0; i < n_contigs; i++) tid_of[contig_names[i]] = i;
+    uvcio_tumor_vcf *v = new uvcio_tumor_vcf();
+    std::vector<TumorRec> recs;
+    const std::string err = parse_tumor_lines(text, len, tid_of, is_tumor_format_retrieved, &v->sample, recs);
     free(text);
     if (!err.empty()) { delete v; return fail(UVCGPU_EINVAL, err); }
-    std::stable_sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) {
+    std::stable_sort(recs.begin(), recs.end(), [](const TumorRec &a, const TumorRec &b) {
         if (a.tid != b.tid) return a.tid < b.tid;
         if (a.k.refpos != b.k.refpos) return a.k.refpos < b.k.refpos;
         return a.k.symbol < b.k.symbol; });
     v->tid_first.assign((size_t)n_contigs + 1, 0);
-    for (const Rec &r : recs) { v->tid.push_back(r.tid); v->keys.push_back(r.k); v->cols_text.push_back(r.col); v->ra_text.push_back(r.ra); v->tid_first[(size_t)r.tid + 1]++; }
+    for (const TumorRec &r : recs) { v->tid.push_back(r.tid); v->keys.push_back(r.k); v->cols_text.push_back(r.col); v->ra_text.push_back(r.ra); v->tid_first[(size_t)r.tid + 1]++; }
     for (int32_t i = 0; i < n_contigs; i++) v->tid_first[(size_t)i + 1] += v->tid_first[(size_t)i];
     for (const std::string &s : v->cols_text) v->cols.push_back(s.c_str());
     for (const std::string &s : v->ra_text) v->ras.push_back(s.c_str());
     *out = v;
     return 0;
 }
+extern "C" int uvcio_tumor_vcf_create(uvcio_tumor_vcf_t **out, const char *sample_name, const char *const *contig_names, int32_t n_contigs, int32_t is_tumor_format_retrieved) {
+    if (!out || n_contigs < 0 || (n_contigs > 0 && !contig_names)) return fail(UVCGPU_EINVAL, "bad argument");
+    uvcio_tumor_vcf *v = new uvcio_tumor_vcf();
+    v->is_store = true; v->is_tumor_format_retrieved = is_tumor_format_retrieved;
+    v->sample = sample_name ? sample_name : "";
+    for (int32_t i = 0; i < n_contigs; i++) v->tid_of[contig_names[i]] = i;
+    v->by_tid.resize((size_t)n_contigs);
+    *out = v;
+    return 0;
+}
+extern "C" int uvcio_tumor_vcf_add_lines(uvcio_tumor_vcf_t *v, const char *text, int64_t len) {
+    if (!v || !v->is_store || len < 0 || (len > 0 && !text)) return fail(UVCGPU_EINVAL, "bad argument");
+    std::vector<TumorRec> recs;   // parsed outside the lock; `ord` is assigned under it
+    const std::string err = parse_tumor_lines(text, len, v->tid_of, v->is_tumor_format_retrieved, nullptr, recs);
+    if (!err.empty()) return fail(UVCGPU_EINVAL, err);
+    std::lock_guard<std::mutex> g(v->mu);
+    const int64_t base = v->n_added;
+    for (TumorRec &r : recs) {
+        r.ord += base;
+        v->by_tid[(size_t)r.tid].emplace(std::make_tuple(r.k.refpos, r.k.symbol, r.ord), std::move(r));
+    }
+    v->n_added += (int64_t)recs.size();
+    return 0;
+}
 extern "C" const char *uvcio_tumor_vcf_sample_name(const uvcio_tumor_vcf_t *v) { return v ? v->sample.c_str() : ""; }
-extern "C" int64_t uvcio_tumor_vcf_n_records(const uvcio_tumor_vcf_t *v) { return v ? (int64_t)v->keys.size() : 0; }
+extern "C" int64_t uvcio_tumor_vcf_n_records(const uvcio_tumor_vcf_t *v) {
+    if (!v) return 0;
+    if (!v->is_store) return (int64_t)v->keys.size();
+    std::lock_guard<std::mutex> g(v->mu);
+    return v->n_added;
+}
 extern "C" int uvcio_tumor_vcf_fetch(const uvcio_tumor_vcf_t *v, int32_t tid, int32_t pos_beg, int32_t pos_end, const UvcTumorKey **keys, const char *const **cols, const char *const **ref_alts, int64_t *n) {
     if (!v || !n) return fail(UVCGPU_EINVAL, "bad argument");
     *n = 0; if (keys) *keys = nullptr; if (cols) *cols = nullptr; if (ref_alts) *ref_alts = nullptr;
+    if (v->is_store) {   // a copy into this thread's buffers of the handle: the maps may grow under other threads
+        uvcio_tumor_vcf *w = const_cast<uvcio_tumor_vcf *>(v);
+        std::lock_guard<std::mutex> g(w->mu);
+        if (tid < 0 || (size_t)tid >= w->by_tid.size()) return 0;
+        uvcio_tumor_vcf::FetchBuf &fb = w->fetch_buf[std::this_thread::get_id()];
+        fb.keys.clear(); fb.cols.clear(); fb.ras.clear();
+        const auto &m = w->by_tid[(size_t)tid];
+        for (auto it = m.lower_bound(std::make_tuple(pos_beg, INT32_MIN, INT64_MIN)); it != m.end() && std::get<0>(it->first) <= pos_end; ++it) {
+            fb.keys.push_back(it->second.k); fb.cols.push_back(it->second.col.c_str()); fb.ras.push_back(it->second.ra.c_str());
+        }
+        *n = (int64_t)fb.keys.size();
+        if (*n > 0) { if (keys) *keys = fb.keys.data(); if (cols) *cols = fb.cols.data(); if (ref_alts) *ref_alts = fb.ras.data(); }
+        return 0;
+    }
     if (tid < 0 || (size_t)tid + 1 >= v->tid_first.size()) return 0;
     const int64_t lo0 = v->tid_first[(size_t)tid], hi0 = v->tid_first[(size_t)tid + 1];
     const auto b = v->keys.begin();

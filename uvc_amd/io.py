@@ -48,6 +48,8 @@ def dll():
         d.uvcio_plan_shards.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         d.uvcio_bgzf_concat.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32]
         d.uvcio_tumor_vcf_open.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+        d.uvcio_tumor_vcf_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+        d.uvcio_tumor_vcf_add_lines.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         d.uvcio_tumor_vcf_sample_name.restype, d.uvcio_tumor_vcf_sample_name.argtypes = C.c_char_p, [C.c_void_p]
         d.uvcio_tumor_vcf_n_records.restype, d.uvcio_tumor_vcf_n_records.argtypes = C.c_int64, [C.c_void_p]
         d.uvcio_tumor_vcf_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
@@ -228,6 +230,23 @@ class TumorVcf:
         self.sample = dll().uvcio_tumor_vcf_sample_name(self.h).decode()
         self.n_records = dll().uvcio_tumor_vcf_n_records(self.h)
 
+    @classmethod
+    def create(cls, sample, contig_names, is_tumor_format_retrieved=True):
+        """An empty in-memory store (uvcio_tumor_vcf_create): the tumor pass's record lines go in by add_lines, without a file."""
+        self = cls.__new__(cls)
+        self.h = C.c_void_p()
+        names = (C.c_char_p * max(1, len(contig_names)))(*[n.encode() for n in contig_names])
+        _check(dll().uvcio_tumor_vcf_create(C.byref(self.h), sample.encode(), names, len(contig_names), int(is_tumor_format_retrieved)))
+        self.sample = dll().uvcio_tumor_vcf_sample_name(self.h).decode()
+        self.n_records = 0
+        return self
+
+    def add_lines(self, text):
+        """Record lines of any number of tiles (str or bytes); records of one key keep the order of their adds."""
+        b = text.encode() if isinstance(text, str) else bytes(text)
+        _check(dll().uvcio_tumor_vcf_add_lines(self.h, b, len(b)))
+        self.n_records = dll().uvcio_tumor_vcf_n_records(self.h)
+
     def fetch(self, tid, pos_beg, pos_end):
         """-> (ctypes array of UvcTumorKey or None, list of sample-column strings): the records with pos_beg <= symbolpos <= pos_end;
         `last_ref_alt` holds their "REF\tALT" strings."""
@@ -236,7 +255,7 @@ class TumorVcf:
         self.last_ref_alt = []
         if n.value == 0:
             return None, []
-        arr = (_ffi.UvcTumorKey * n.value).from_address(keys.value)
+        arr = (_ffi.UvcTumorKey * n.value).from_buffer_copy((_ffi.UvcTumorKey * n.value).from_address(keys.value))   # a store reuses its buffers at the next fetch
         texts = [s.decode() for s in (C.c_char_p * n.value).from_address(cols.value)]
         self.last_ref_alt = [s.decode() for s in (C.c_char_p * n.value).from_address(ras.value)]   # "REF\tALT" of the same records
         return arr, texts

@@ -210,6 +210,34 @@ def write_vcf(lib, bam, fasta, chrom, beg, end, path, sample="SAMPLE", params=No
     return n
 
 
+def write_vcf_pair(lib, tumor_bam, normal_bam, fasta, chrom, beg, end, tumor_path, normal_path, tumor_sample="TUMOR", normal_sample="NORMAL",
+                   tumor_params=None, normal_params=None, **kw):
+    """A tumor/normal pair with the tumor records handed over in memory (what `uvc1-mi355x TUMOR.bam --normal-bam NORMAL.bam` does; uvcTN.sh
+    runs it as two processes through a tumor VCF file): the tumor tiles of [beg, end) write `tumor_path`, their record lines go tile by tile
+    into a `uvc_amd.io.TumorVcf.create` store, and the normal tiles of the same span read their tumor records from it and write `normal_path`.
+    Both sides run with tn_is_paired = 1 (uvcTN.sh:120-127).  Returns (tumor record lines, normal record lines)."""
+    pt = tumor_params if tumor_params is not None else region.default_params(lib)
+    pn = normal_params if normal_params is not None else region.default_params(lib)
+    pt.tn_is_paired = pn.tn_is_paired = 1
+    pn.tumor_vcf_is_provided = 1
+    bn = normal_bam if not isinstance(normal_bam, str) else uio.Bam(normal_bam)
+    store = uio.TumorVcf.create(tumor_sample, [name for name, _ in bn.refs])
+    bt = tumor_bam if not isinstance(tumor_bam, str) else uio.Bam(tumor_bam)
+    sink = uio.BgzfWriter(tumor_path)
+    n_t = 0
+    try:
+        sink.write(region.vcf_header(lib, pt, tumor_sample, [(name, ln) for name, ln in bt.refs]))
+        for res in call_contig(lib, tumor_bam, fasta, chrom, beg, end, vcf=True, params=pt, **kw):
+            sink.write(res["vcf"]); store.add_lines(res["vcf"]); n_t += res["vcf"].count("\n")
+    finally:
+        sink.close()
+    try:
+        n_n = write_vcf(lib, normal_bam, fasta, chrom, beg, end, normal_path, sample=normal_sample, params=pn, tumor_vcf=store, **kw)
+    finally:
+        store.close()
+    return n_t, n_n
+
+
 def main(argv):
     args, vcf_path, sample = [], None, "SAMPLE"
     it = iter(argv[1:])
