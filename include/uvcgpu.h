@@ -350,6 +350,14 @@ typedef struct UvcScoreRequest {
     const char *const *tumor_ref_alt;          /* [n_tumor_keys] or NULL: "REF\tALT" of each tumor record (TumorKeyInfo::ref_alt, main.cpp:380).  Record writer
                                  * only: the InDel string of a rescued InDel record is the tumor's (main.cpp:867-880); without it such a record
                                  * is written with its symbolic allele */
+    int64_t n_force_sites;      /* force-output sites: zerobased_pos values, sorted ascending (repeats allowed); 0 / NULL = none.  A site selects
+                                 * both (zerobased_pos, symbol type) groups of its position -- the BASE group of refpos site - 1 and the LINK group
+                                 * of refpos site, whose records all print VCF POS = site -- and those are scored and written exactly as with
+                                 * all_out = 1; every other group exactly as without it.  The two groups of a position go together because the
+                                 * records of one read the other's gate (vAC0 / vAC1, and a GERMLINE line of either lets the REF record out).
+                                 * Sites outside [pos_beg, pos_end) select nothing.  Not with tumor_vcf_is_provided (the rescue set is the gate
+                                 * of a normal sample).  The planes, the MGVCF block and ADDITIONAL_INDEL_CANDIDATE lines do not depend on it */
+    const int32_t *force_sites;
 } UvcScoreRequest;
 
 typedef struct UvcScoreOut {
@@ -397,7 +405,7 @@ int uvcgpu_region_correct_bq(uvcgpu_region_t *r);
 int uvcgpu_region_read_quals(uvcgpu_region_t *r, uint8_t *dst, int64_t n);
 /* Replaces updateByRegion3Aln (main.hpp:3665-3742): passes P1..P5b. Asynchronous on the handle's stream. */
 int uvcgpu_region_accumulate(uvcgpu_region_t *r);
-/* Upper bound of records a request can produce (2 symbol types x <= 8 symbols x positions). */
+/* Upper bound of records a request can produce (2 symbol types x <= 8 symbols x positions, + 16 per force-output site). */
 int64_t uvcgpu_region_score_size(const uvcgpu_region_t *r, const UvcScoreRequest *req);
 /* Replaces the BcfFormat_symbol* call group.  Synchronous: returns after D2H of the records. */
 int uvcgpu_region_score(uvcgpu_region_t *r, const UvcScoreRequest *req, UvcScoreOut *out);

@@ -110,6 +110,19 @@ int uvcio_tumor_vcf_fetch(const uvcio_tumor_vcf_t *v, int32_t tid, int32_t pos_b
                           const char *const **ref_alts, int64_t *n);
 void uvcio_tumor_vcf_close(uvcio_tumor_vcf_t *v);
 
+/* Force-output sites (uvc1-mi355x --force-sites, UvcScoreRequest::force_sites) read from a BED or a VCF, plain or (block-)gzipped.
+ * A file whose first line starts with ##fileformat or #CHROM is a VCF: of each record only CHROM and POS are read, and POS p is the site
+ * p.  Anything else is a BED file (lines starting with #, track or browser are skipped): every base x of an interval [start, end) is the
+ * site x + 1.  A site is a zerobased_pos: the VCF POS of the records it selects (BASE records of refpos POS - 1, LINK records of refpos
+ * POS).  Contig names map through contig_names (the BAM header); an unknown contig or a malformed line fails with UVCGPU_EINVAL and a
+ * message that names the file and the line.  The sites are sorted and de-duplicated per contig. */
+typedef struct uvcio_sites uvcio_sites_t;
+int uvcio_sites_open(uvcio_sites_t **out, const char *path, const char *const *contig_names, int32_t n_contigs);
+int64_t uvcio_sites_count(const uvcio_sites_t *s);
+/* The sites of `tid` with pos_beg <= site < pos_end, ascending: a pointer into the handle (valid until it is closed) and the count. */
+int uvcio_sites_fetch(const uvcio_sites_t *s, int32_t tid, int64_t pos_beg, int64_t pos_end, const int32_t **sites, int64_t *n);
+void uvcio_sites_close(uvcio_sites_t *s);
+
 /* CRC-32 (the zlib / BGZF footer polynomial) as the reader and the writer compute it: carry-less multiplication on CPUs that have it. */
 /* Where the two large columns of a batch (UvcBamBatch::bases, ::quals) live: NULL, NULL = the C heap.  A caller that hands the batch to
  * uvcgpu_region_set_reads passes page-locked memory of the GPU library here (wrappers of uvcgpu_host_alloc / uvcgpu_host_free), so that the

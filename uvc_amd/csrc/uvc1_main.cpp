@@ -39,7 +39,7 @@ namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
 struct Opts {
-    std::string bam, fasta, out, sample = "-", targets, bed, tumor_vcf, bed_out, bed_in, umi_struct;
+    std::string bam, fasta, out, sample = "-", targets, bed, tumor_vcf, bed_out, bed_in, umi_struct, force_sites;
     std::vector<int> devices;
     int threads = 0, repeat = 1, shard = 0, n_shards = 1, tumor_format = 1;
     int sequencing_platform = UVC_PLATFORM_AUTO, assay_type = 0;   // --sequencing-platform (0 AUTO, 1 ILLUMINA, 2 IONTORRENT, 3 OTHER), --assay-type (0 inferred per tile, 1 CAPTURE, 2 AMPLICON)
@@ -48,6 +48,7 @@ struct Opts {
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
+    const uvcio_sites_t *sites = nullptr;   // --force-sites, read once the BAM header is known (main)
 };
 [[noreturn]] void die(const std::string &m) { fprintf(stderr, "uvc1-mi355x: %s\n", m.c_str()); exit(2); }
 const char *const ONLY_PRINT_VCF_HEADER = "/only-print-vcf-header/";   // OPT_ONLY_PRINT_VCF_HEADER, common.hpp:58
@@ -73,6 +74,7 @@ const OptRow OPTS[] = {
     { "-R,--regions-file", O_CLI, false, "", "BED file of the regions to call" },
     { "-t,--threads", O_CLI, false, "0", "tiles in flight (0: half the usable cores, 1..8 per device)" },
     { "-A,--all-out", O_CLI, true, "", "every allele of every position (should_output_all = 1)" },
+    { "--force-sites", O_CLI, false, "", "BED or VCF(.gz) of sites: at each listed POS every allele record as -A writes it, the default gate elsewhere" },
     { "-q,--vqual", O_CLI, false, "15", "minimum variant quality (the vqual row)" },
     { "--outvar-flag", O_CLI, false, "62", "output-variant bits (the outvar_flag row)" },
     { "--tumor-vcf", O_CLI, false, "", "the tumor pass's VCF: this BAM is the normal sample of a T/N pair" },
@@ -226,6 +228,7 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "-R") o.bed = val();
         else if (n0 == "-t") o.threads = std::max(1, atoi(val().c_str()));
         else if (n0 == "-A") set_row("should_output_all", name, "1");
+        else if (n0 == "--force-sites") { o.force_sites = val(); if (o.force_sites.empty()) die("--force-sites needs a path"); }
         else if (n0 == "-q") set_row("vqual", name, val());
         else if (n0 == "--outvar-flag") set_row("outvar_flag", name, val());
         else if (n0 == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
@@ -265,6 +268,10 @@ Opts parse(int argc, char **argv) {
     if (o.bam.empty() || (!o.print_params && o.bam != ONLY_PRINT_VCF_HEADER && (o.fasta.empty() || o.out.empty()))) {
         fprintf(stderr, "usage: uvc1-mi355x inputBAM -f ref.fa -o out.vcf.gz [options] (--help lists them)\n");
         exit(2);
+    }
+    if (!o.force_sites.empty()) {   // before any file or device
+        if (!o.tumor_vcf.empty()) die("--force-sites cannot go with --tumor-vcf: the normal sample's gate is the tumor's rescue set");
+        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--force-sites cannot go with ") + ONLY_PRINT_VCF_HEADER + ": there are no records to force");
     }
     if (const int rc = uvcgpu_params_check(&o.P)) die(std::string(uvcgpu_last_error()) + " (code " + std::to_string(rc) + ")");   // before any file or device
     if (!o.tumor_vcf.empty()) o.P.tumor_vcf_is_provided = 1;   // IS_PROVIDED(vcf_tumor_fname), common.hpp:56
@@ -364,8 +371,9 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
         if (uvcio_tumor_vcf_fetch(tvcf, t.tid, (int32_t)ext_beg, (int32_t)ext_end, &keys, &cols, &ras, &nk)) die(uvcio_last_error());
         rq.tumor_keys = keys; rq.n_tumor_keys = nk; rq.tumor_sample_columns = (o.tumor_format ? cols : nullptr); rq.tumor_ref_alt = ras;
     }
+    if (o.sites && uvcio_sites_fetch(o.sites, t.tid, first, last_excl, &rq.force_sites, &rq.n_force_sites)) die(uvcio_last_error());   // the sites this tile owns
     rq.kept_only = 1;   // only the record groups that are written travel to the host
-    int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), uvcgpu_region_score_size(w.reg, &rq) / (rq.all_out ? 1 : 64));
+    int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), uvcgpu_region_score_size(w.reg, &rq) / (rq.all_out ? 1 : 64) + 16 * rq.n_force_sites);
     UvcScoreOut so;
     for (;;) {
         w.fields.resize((size_t)UVC_NUM_SCORE_FIELDS * (size_t)cap);
@@ -610,6 +618,7 @@ PairArgs split_pair(int argc, char **argv) {
         const std::string name = t.substr(0, t.compare(0, 2, "--") == 0 ? t.find('=') : std::string::npos);
         if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
+        if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (t == ONLY_PRINT_VCF_HEADER) die(std::string(ONLY_PRINT_VCF_HEADER) + " cannot go with --normal-bam");
         const OptRow *row = (t[0] == '-' ? find_opt(name) : nullptr);
         if (t[0] == '-' && t.find('=') == std::string::npos && ((row && !row->flag) || (!row && find_param(name) >= 0))) i++;   // skip the value
@@ -878,6 +887,12 @@ int main(int argc, char **argv) {
     if (!platform_given) infer_platform(o, bam0, tiles);
     uvcio_bam_close(bam0);
     if (o.print_params) { print_params(o); return 0; }
+    uvcio_sites_t *sites = nullptr;
+    if (!o.force_sites.empty()) {
+        if (uvcio_sites_open(&sites, o.force_sites.c_str(), G.cnames.data(), nref)) die("--force-sites: " + std::string(uvcio_last_error()));
+        fprintf(stderr, "uvc1-mi355x: %lld force-output sites from %s\n", (long long)uvcio_sites_count(sites), o.force_sites.c_str());
+        o.sites = sites;
+    }
     if (uvcgpu_init(o.devices[0])) die(uvcgpu_last_error());
     reader_switches(o);
     // T/N: the tumor pass's records (rescue_variants_from_vcf, main.cpp:183-398)
@@ -933,6 +948,7 @@ int main(int argc, char **argv) {
     for (auto &t : th) t.join();
     if (uvcio_bgzf_write_close(zw)) die(uvcio_last_error());
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
+    if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {
         std::vector<const Tile *> pass; for (size_t ti = 0; ti < tiles_per_pass; ti++) pass.push_back(&tiles[ti]);
         write_region_table(o, pass, tile_reads);

@@ -34,7 +34,7 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
                                       const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work, hipStream_t s, UvcProf *prof,
                                       hipStream_t side, hipEvent_t e_fork, hipEvent_t e_join, hipEvent_t e_fork2, hipStream_t side3, hipEvent_t e_join3, hipEvent_t e_stat, hipEvent_t e_alleles);
 extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity, char *scratch, int32_t *d_fields_kept, hipStream_t s);
+                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity, char *scratch, int32_t *d_fields_kept, const int32_t *d_force_sites, hipStream_t s);
 extern "C" size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity);
 extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity);
 extern "C" void uvc_launch_zero_state(char *slab, const void *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s);
@@ -1015,7 +1015,7 @@ static int uvcgpu_region_hap_links_impl(uvcgpu_region_t *r, UvcHapLink *links, i
 int64_t uvcgpu_region_score_size(const uvcgpu_region_t *r, const UvcScoreRequest *req) {
     if (!r) return -1;
     const int64_t np = (req && req->pos_beg >= 0) ? (req->pos_end - req->pos_beg) : r->npos;
-    return NSYM * (np + 1) + (req ? req->n_indel_alleles + req->n_tumor_keys : 0) + (int64_t)r->gap_alleles.size();
+    return NSYM * (np + 1) + (req ? req->n_indel_alleles + req->n_tumor_keys + 16 * std::max<int64_t>(req->n_force_sites, 0) : 0) + (int64_t)r->gap_alleles.size();
 }
 
 // Small host arrays of a score call go to the device through the handle's own page-locked staging buffer: an asynchronous copy straight from
@@ -1047,16 +1047,17 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
     if (rq.pos_beg < r->beg + (rq.base_at_pos_beg ? 1 : 0) || rq.pos_end > r->end - 1 || rq.pos_end < rq.pos_beg) return fail(UVCGPU_EINVAL, "score range outside the region");
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
-    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr;
+    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr;
     std::vector<UvcIndelAllele> merged; std::vector<int32_t> merged_row;
     // the temporaries go back to the caching allocator, which hands them to other handles at once: on every return path the stream is
     // drained first (async copies from `merged` / the caller's keys, kernels that read the blocks), then they are freed
-    struct Temps { uvcgpu_region *r; UvcIndelAllele *&a; int32_t *&b; UvcTumorKey *&c;
-                   ~Temps() { if (a || b || c) (void)hipStreamSynchronize(r->stream); if (a) hipFree(a); if (b) hipFree(b); if (c) hipFree(c); } } temps = { r, d_al, d_al_row, d_tk };
+    struct Temps { uvcgpu_region *r; UvcIndelAllele *&a; int32_t *&b; UvcTumorKey *&c; int32_t *&d;
+                   ~Temps() { if (a || b || c || d) (void)hipStreamSynchronize(r->stream); if (a) hipFree(a); if (b) hipFree(b); if (c) hipFree(c); if (d) hipFree(d); } } temps = { r, d_al, d_al_row, d_tk, d_fs };
     const UvcIndelAllele *use_al = r->d_gap_alleles; const int32_t *use_row = r->d_gap_allele_row; int64_t n_al = (int64_t)r->gap_alleles.size();
     // one staging layout per call (an earlier call's copies are complete: score synchronises before it returns)
     size_t stage_at = 0;
-    const size_t stage_total = (sizeof(UvcIndelAllele) + sizeof(int32_t)) * (size_t)(r->gap_alleles.size() + (size_t)std::max<int64_t>(rq.n_indel_alleles, 0)) + sizeof(UvcTumorKey) * (size_t)std::max<int64_t>(rq.n_tumor_keys, 0) + 256;
+    const size_t stage_total = (sizeof(UvcIndelAllele) + sizeof(int32_t)) * (size_t)(r->gap_alleles.size() + (size_t)std::max<int64_t>(rq.n_indel_alleles, 0)) + sizeof(UvcTumorKey) * (size_t)std::max<int64_t>(rq.n_tumor_keys, 0)
+                              + sizeof(int32_t) * (size_t)std::max<int64_t>(rq.n_force_sites, 0) + 256;
     if (rq.n_indel_alleles > 0) {
         auto less = [](const UvcIndelAllele &a, const UvcIndelAllele &b) { return a.refpos < b.refpos || (a.refpos == b.refpos && a.symbol < b.symbol); };
         for (int64_t q = 1; q < rq.n_indel_alleles; q++) if (less(rq.indel_alleles[q], rq.indel_alleles[q - 1])) return fail(UVCGPU_EINVAL, "indel_alleles must be sorted by (refpos, symbol)");
@@ -1082,6 +1083,13 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         }
         HIP_OK(hipMalloc((void **)&d_tk, sizeof(UvcTumorKey) * rq.n_tumor_keys));
         { int rc1 = stage_upload(r, d_tk, rq.tumor_keys, sizeof(UvcTumorKey) * (size_t)rq.n_tumor_keys, stage_at, stage_total); if (rc1) return rc1; }
+    }
+    if (rq.n_force_sites < 0 || (rq.n_force_sites > 0 && !rq.force_sites)) return fail(UVCGPU_EINVAL, "force_sites: bad count or NULL array");
+    if (rq.n_force_sites > 0) {   // force-output sites: sorted zerobased_pos values, uploaded like the tumor keys (k_force_mask makes the bit mask)
+        if (r->P.tumor_vcf_is_provided) return fail(UVCGPU_EINVAL, "force_sites cannot go with tumor_vcf_is_provided (the normal sample's gate is the rescue set)");
+        for (int64_t q = 1; q < rq.n_force_sites; q++) if (rq.force_sites[q] < rq.force_sites[q - 1]) return fail(UVCGPU_EINVAL, "force_sites must be sorted ascending");
+        HIP_OK(hipMalloc((void **)&d_fs, sizeof(int32_t) * (size_t)rq.n_force_sites));
+        { int rc1 = stage_upload(r, d_fs, rq.force_sites, sizeof(int32_t) * (size_t)rq.n_force_sites, stage_at, stage_total); if (rc1) return rc1; }
     }
     const bool kept_only = (rq.kept_only != 0);
     // device capacity: the caller's in the plain form; with kept_only the caller's buffer only has to hold the kept groups, the device
@@ -1117,7 +1125,8 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         int pi = -1;   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
         if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = "k_score_all"; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); }
         rc = uvc_launch_score(&r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, r->d_score_fields, r->score_capacity, r->d_score_scratch,
-                              kept_only ? r->d_score_kept : nullptr, r->stream);
+                              kept_only ? r->d_score_kept : nullptr, d_fs, r->stream);
+        if (rc) rc = fail(rc, "score: the force-output mask could not be cleared");
         if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream);
         if (!rc && hipGetLastError() != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score kernel launch failed");
         if (!rc) rc = uvcgpu_region_sync(r);

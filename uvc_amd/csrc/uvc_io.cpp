@@ -1096,3 +1096,90 @@ extern "C" int uvcio_tumor_vcf_fetch(const uvcio_tumor_vcf_t *v, int32_t tid, in
     return 0;
 }
 extern "C" void uvcio_tumor_vcf_close(uvcio_tumor_vcf_t *v) { delete v; }
+
+// ---- force-output sites (uvc1-mi355x --force-sites): a BED or a VCF reduced to (tid, zerobased_pos) ----
+struct uvcio_sites {
+    std::vector<int32_t> pos;         // zerobased_pos values, sorted and unique within a contig
+    std::vector<int64_t> tid_first;   // [n_contigs + 1] first site of each tid
+};
+namespace {
+bool parse_nonneg(const std::string &t, int64_t &v) {
+    if (t.empty() || t.size() > 18) return false;
+    v = 0;
+    for (char c : t) { if (c < '0' || c > '9') return false; v = v * 10 + (c - '0'); }
+    return true;
+}
+std::string sites_parse(const char *text, int64_t len, const std::string &path, const std::map<std::string, int32_t> &tid_of, std::vector<std::pair<int32_t, int32_t>> &out) {
+    // VCF: the first line is ##fileformat=VCF... or #CHROM (what every VCF writer puts first); anything else is read as BED
+    const bool vcf = (len >= 12 && !strncmp(text, "##fileformat", 12)) || (len >= 6 && !strncmp(text, "#CHROM", 6));
+    const int64_t max_sites = (int64_t)1 << 30;
+    int64_t lineno = 0, n_expanded = 0;
+    for (int64_t at = 0; at < len;) {
+        const char *nl = (const char *)memchr(text + at, '\n', (size_t)(len - at));
+        const int64_t e = nl ? nl - text : len;
+        std::string line(text + at, (size_t)(e - at));
+        at = e + 1; lineno++;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        if (!vcf && (!line.compare(0, 5, "track") || !line.compare(0, 7, "browser"))) continue;
+        std::vector<std::string> f;
+        for (size_t p = 0; p <= line.size() && f.size() < 3;) {   // VCF: tab-separated; BED: tabs or blanks
+            size_t q = p;
+            while (q < line.size() && line[q] != '\t' && (vcf || line[q] != ' ')) q++;
+            if (q > p || vcf) f.push_back(line.substr(p, q - p));
+            p = q + 1;
+            while (!vcf && p < line.size() && line[p] == ' ') p++;
+        }
+        const std::string where = path + " line " + std::to_string(lineno) + ": ";
+        if (f.size() < (vcf ? 2u : 3u)) return where + (vcf ? "a VCF record needs CHROM and POS" : "a BED line needs chrom, start and end");
+        const auto it = tid_of.find(f[0]);
+        if (it == tid_of.end()) return where + "contig '" + f[0] + "' is not in the BAM header";
+        if (vcf) {
+            int64_t p = 0;
+            if (!parse_nonneg(f[1], p) || p < 1 || p > INT32_MAX - 1) return where + "POS '" + f[1] + "' is not a positive integer";
+            out.emplace_back(it->second, (int32_t)p);                  // VCF POS p = the records of zerobased_pos p
+            n_expanded++;
+        } else {
+            int64_t b = 0, en = 0;
+            if (!parse_nonneg(f[1], b) || !parse_nonneg(f[2], en) || b > en || en > INT32_MAX - 1) return where + "start '" + f[1] + "' and end '" + f[2] + "' are not 0 <= start <= end";
+            n_expanded += en - b;
+            if (n_expanded > max_sites) return where + "more than 2^30 sites in all";
+            for (int64_t x = b; x < en; x++) out.emplace_back(it->second, (int32_t)(x + 1));   // base x (0-based) = VCF POS x + 1
+        }
+    }
+    return std::string();
+}
+}
+extern "C" int uvcio_sites_open(uvcio_sites_t **out, const char *path, const char *const *contig_names, int32_t n_contigs) {
+    if (!out || !path || n_contigs < 0 || (n_contigs > 0 && !contig_names)) return fail(UVCGPU_EINVAL, "bad argument");
+    *out = nullptr;
+    char *text = nullptr; int64_t len = 0;
+    int rc = uvcio_read_text_file(path, &text, &len);
+    if (rc) return rc;
+    std::map<std::string, int32_t> tid_of;
+    for (int32_t i = 0; i < n_contigs; i++) tid_of[contig_names[i]] = i;
+    std::vector<std::pair<int32_t, int32_t>> s;
+    const std::string err = sites_parse(text, len, path, tid_of, s);
+    free(text);
+    if (!err.empty()) return fail(UVCGPU_EINVAL, err);
+    std::sort(s.begin(), s.end());
+    s.erase(std::unique(s.begin(), s.end()), s.end());
+    uvcio_sites *v = new uvcio_sites();
+    v->tid_first.assign((size_t)n_contigs + 1, 0);
+    for (const auto &p : s) { v->pos.push_back(p.second); v->tid_first[(size_t)p.first + 1]++; }
+    for (int32_t i = 0; i < n_contigs; i++) v->tid_first[(size_t)i + 1] += v->tid_first[(size_t)i];
+    *out = v;
+    return 0;
+}
+extern "C" int64_t uvcio_sites_count(const uvcio_sites_t *v) { return v ? (int64_t)v->pos.size() : 0; }
+extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t pos_beg, int64_t pos_end, const int32_t **sites, int64_t *n) {
+    if (!v || !sites || !n) return fail(UVCGPU_EINVAL, "bad argument");
+    *sites = nullptr; *n = 0;
+    if (tid < 0 || (size_t)tid + 1 >= v->tid_first.size() || pos_end <= pos_beg) return 0;
+    const int32_t *b = v->pos.data() + v->tid_first[(size_t)tid], *e = v->pos.data() + v->tid_first[(size_t)tid + 1];
+    const int32_t *lo = std::lower_bound(b, e, (int64_t)std::max<int64_t>(pos_beg, INT32_MIN), [](int32_t a, int64_t k) { return (int64_t)a < k; });
+    const int32_t *hi = std::lower_bound(lo, e, (int64_t)std::min<int64_t>(pos_end, (int64_t)INT32_MAX + 1), [](int32_t a, int64_t k) { return (int64_t)a < k; });
+    *sites = lo; *n = hi - lo;
+    return 0;
+}
+extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }

@@ -116,9 +116,18 @@ struct ScoreCtx {
     const int32_t *allele_rows;                           // parallel: row of uvcgpu_region_indel_alleles that carries the allele's string, or -1
     const UvcTumorKey *tkeys; long long n_tkeys;          // sorted by (refpos, symbol); only read when tumor_vcf_is_provided
     int32_t *fields; long long capacity;
+    const unsigned *force_mask;   // UvcScoreRequest::force_sites as one bit per zerobased_pos of [pos_beg, pos_end) (k_force_mask), or NULL
     long long *offsets;   // exclusive prefix of per-group packed (flag << 32 | allele count), [2 * (pos_end - pos_beg) + 1]
     int *active;          // groups with at least one allele, ascending
 };
+// the gate of group g is the all-out one: -A, or a force-output site at its zerobased_pos (both symbol types of the position: their records
+// read each other's gate through vAC0 / vAC1 and germ_emit).  Without sites the mask pointer is NULL for every lane: one uniform compare.
+DEV bool group_all_out(const ScoreCtx &C, long long g) {
+    if (C.all_out) return true;
+    if (C.force_mask == nullptr) return false;
+    const unsigned i = (unsigned)(g >> 1);
+    return ((C.force_mask[i >> 5] >> (i & 31u)) & 1u) != 0;
+}
 #define PK_COUNT(v) ((long long)((v) & 0xFFFFFFFFLL))
 #define PK_FLAGS(v) ((long long)((v) >> 32))
 
@@ -541,7 +550,8 @@ DEV int gate_count(const RegionDev &R, const UvcParams &P, const ScoreCtx &C, lo
     const int64_t x = refpos - R.beg;
     const int refsymbol = group_refsymbol(R, zpos, st), nsym = st_count(st);
     int bd[8], totBDP = 0;
-    if (C.all_out || P.tumor_vcf_is_provided) {   // the gate does not look at the depths
+    const bool all_out = group_all_out(C, g);
+    if (all_out || P.tumor_vcf_is_provided) {   // the gate does not look at the depths
 #pragma unroll
         for (int k = 0; k < 8; k++) bd[k] = 0;
     } else {
@@ -557,7 +567,7 @@ DEV int gate_count(const RegionDev &R, const UvcParams &P, const ScoreCtx &C, lo
     for (int k = 0; k < 8; k++) {
         if (k >= nsym) break;
         const int s = st_symbol(st, k);
-        if (gate_b(P, s, refsymbol, bd[k], totBDP, C.all_out, pos_rescued)) { long long first; int src; n += allele_source(C, P.tumor_vcf_is_provided, refpos, s, first, src); }
+        if (gate_b(P, s, refsymbol, bd[k], totBDP, all_out, pos_rescued)) { long long first; int src; n += allele_source(C, P.tumor_vcf_is_provided, refpos, s, first, src); }
     }
     return n;
 }
@@ -626,6 +636,7 @@ __global__ void __launch_bounds__(128) k_enum(RegionDev R, UvcParams P, ScoreCtx
     unsigned mask = type_mask(R, st, x, refsymbol);
     int bd[8], cd[8];
     const int totBDP = masked_bdepths(R, st, x, mask, bd);
+    const bool all_out = group_all_out(C, g);
     // deduplicated depth of the marked symbols (main.cpp:806-812)
 #pragma unroll
     for (int k = 0; k < 8; k++) cd[k] = 0;
@@ -670,7 +681,7 @@ __global__ void __launch_bounds__(128) k_enum(RegionDev R, UvcParams P, ScoreCtx
     for (int k = 0; k < 8; k++) {
         if (k >= nsym) break;
         const int s = st_symbol(st, k);
-        if (!gate_b(P, s, refsymbol, bd[k], totBDP, C.all_out, true /* an active group of a normal sample is a rescued position */)) continue;
+        if (!gate_b(P, s, refsymbol, bd[k], totBDP, all_out, true /* an active group of a normal sample is a rescued position */)) continue;
         long long first; int src;
         const int m = allele_source(C, P.tumor_vcf_is_provided, refpos, s, first, src);
         indel_rec = indel_rec || is_ins(s) || is_del(s);
@@ -1470,7 +1481,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int vAC0 = (st == UVC_BASE_SYMBOL ? vA_own : vA_oth), vAC1 = (st == UVC_BASE_SYMBOL ? vA_oth : vA_own);
     const bool germ_any = (GR_(gemit, gi) != 0) || (gj >= 0 && GR_(gemit, gj) != 0);
     const int ref_bDP = GR_(refbdp, gi);
-    const bool should_output_ref_allele = (C.all_out || germ_any);
+    const bool should_output_ref_allele = (group_all_out(C, g) || germ_any);
     OUT(UVC_O_vAC0, vAC0); OUT(UVC_O_vAC1, vAC1);
     const int tki = FLD(UVC_O_tkey, rec);
     const bool will_generate_out = (!tprov ? ((P.outvar_flag & 0x4) != 0) : (tki >= 0 && (P.outvar_flag & 0x2)));
@@ -1616,9 +1627,22 @@ __global__ void __launch_bounds__(256) k_keep_copy(ScoreCtx C, Stage S, long lon
     }
 }
 
+// ---- UvcScoreRequest::force_sites: one bit per zerobased_pos of the scored range, read by group_all_out ----
+// One lane per site (O(sites), a few hundred in a typical list); a site outside [pos_beg, pos_end) sets nothing.  Sorted sites put the lanes
+// of a wave on neighbouring words; repeats and neighbours meet in the same word, hence the atomic OR.
+__global__ void __launch_bounds__(256) k_force_mask(const int32_t *sites, long long n, int pos_beg, int pos_end, unsigned *mask) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int z = sites[i];
+    if (z < pos_beg || z >= pos_end) return;
+    const unsigned b = (unsigned)(z - pos_beg);
+    atomicOr(&mask[b >> 5], 1u << (b & 31u));
+}
+static size_t force_mask_words(int64_t npos_scored) { return (size_t)((npos_scored > 0 ? npos_scored : 0) + 31) / 32; }
+
 // scratch layout of one score call.  The head [record counts (2 x int64)] [counters] [tile states of the two scans] is zeroed in front of every call.
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-struct ScratchLayout { size_t zero_bytes, cnt, status1, status2, offsets, active, grp, tot, rh, al, al64, mid, d4, keptoff, total; };
+struct ScratchLayout { size_t zero_bytes, cnt, status1, status2, offsets, active, grp, tot, rh, al, al64, mid, d4, keptoff, force_mask, total; };
 static ScratchLayout scratch_layout(int64_t npos_scored, int64_t cap) {
     const size_t ngroups = (size_t)(2 * npos_scored), c = (size_t)(cap > 0 ? cap : 1);
     const size_t ntiles1 = (ngroups + GATE_TILE - 1) / GATE_TILE + 1, ntiles2 = (std::min(ngroups, c) + GS_TILE - 1) / GS_TILE + 1;
@@ -1637,6 +1661,7 @@ static ScratchLayout scratch_layout(int64_t npos_scored, int64_t cap) {
     L.mid = o; o = align16(o + (size_t)NMID * c * 8);
     L.d4 = o; o = align16(o + (size_t)NDP4 * 2 * c * 8);
     L.keptoff = o; o = align16(o + c * 4);
+    L.force_mask = o; o = align16(o + force_mask_words(npos_scored) * 4);   // zeroed and filled only by a call with force-output sites
     L.total = o;
     return L;
 }
@@ -1647,7 +1672,8 @@ extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capa
 // records) are its first two int64.
 extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
                                 const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity,
-                                char *scratch /* uvc_score_scratch_bytes */, int32_t *d_fields_kept /* kept_only: a second [fields][capacity] array */, hipStream_t s) {
+                                char *scratch /* uvc_score_scratch_bytes */, int32_t *d_fields_kept /* kept_only: a second [fields][capacity] array */,
+                                const int32_t *d_force_sites /* device copy of UvcScoreRequest::force_sites, or NULL */, hipStream_t s) {
     ScoreCtx C;
     C.pos_beg = req->pos_beg; C.pos_end = req->pos_end; C.all_out = (req->all_out || P->should_output_all) ? 1 : 0; C.is_amplicon = req->is_amplicon; C.base_at_beg = req->base_at_pos_beg ? 1 : 0;
     C.alleles = d_alleles; C.allele_rows = d_allele_rows; C.n_alleles = n_alleles; C.gap_rows = d_gap_rows; C.gap_seq = d_gap_seq; C.tkeys = d_tkeys; C.n_tkeys = (d_tkeys ? req->n_tumor_keys : 0); C.fields = d_fields; C.capacity = capacity;
@@ -1660,6 +1686,13 @@ extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const Uv
     C.offsets = (long long *)(scratch + L.offsets); C.active = (int *)(scratch + L.active);
     S.grp = (int32_t *)(scratch + L.grp); S.tot = (long long *)(scratch + L.tot); S.rh = (int32_t *)(scratch + L.rh); S.al = (int32_t *)(scratch + L.al); S.al64 = (long long *)(scratch + L.al64);
     S.mid = (double *)(scratch + L.mid); S.d4 = (double *)(scratch + L.d4); S.keptoff = (int32_t *)(scratch + L.keptoff); S.cap = capacity;
+    C.force_mask = nullptr;
+    if (d_force_sites && req->n_force_sites > 0 && !C.all_out) {   // (under -A every group is selected already)
+        unsigned *mask = (unsigned *)(scratch + L.force_mask);
+        if (hipMemsetAsync(mask, 0, force_mask_words(npos_scored) * 4, s) != hipSuccess) return UVCGPU_EDEVICE;
+        hipLaunchKernelGGL(k_force_mask, dim3((unsigned)((req->n_force_sites + 255) / 256)), dim3(256), 0, s, d_force_sites, (long long)req->n_force_sites, C.pos_beg, C.pos_end, mask);
+        C.force_mask = mask;
+    }
     const unsigned ntiles = (unsigned)((ngroups + GATE_TILE - 1) / GATE_TILE);
     hipLaunchKernelGGL(k_gate_scan, dim3(ntiles), dim3(GS_BLOCK), 0, s, *R, *P, C, S, d_count);
     // every kernel below works on a list whose length lives on the device: grids cover what the rows can hold, the threads beyond the length leave

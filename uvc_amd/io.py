@@ -54,6 +54,10 @@ def dll():
         d.uvcio_tumor_vcf_n_records.restype, d.uvcio_tumor_vcf_n_records.argtypes = C.c_int64, [C.c_void_p]
         d.uvcio_tumor_vcf_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
         d.uvcio_tumor_vcf_close.argtypes = [C.c_void_p]
+        d.uvcio_sites_open.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.POINTER(C.c_char_p), C.c_int32]
+        d.uvcio_sites_count.restype, d.uvcio_sites_count.argtypes = C.c_int64, [C.c_void_p]
+        d.uvcio_sites_fetch.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        d.uvcio_sites_close.argtypes = [C.c_void_p]
         _dll = d
     return _dll
 
@@ -218,6 +222,36 @@ def plan_regions_stream(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per
     finally:
         d.uvcio_planner_close(h)
     return cuts
+
+
+class Sites:
+    """Force-output sites from a BED or a VCF(.gz) (uvcio_sites_*, what uvc1-mi355x --force-sites reads): per contig the sorted, unique
+    zerobased_pos values, each the VCF POS of the records it selects.  `contig_names`: the BAM header's, in tid order."""
+
+    def __init__(self, path, contig_names):
+        self.h = C.c_void_p()
+        names = (C.c_char_p * max(1, len(contig_names)))(*[n.encode() for n in contig_names])
+        _check(dll().uvcio_sites_open(C.byref(self.h), path.encode(), names, len(contig_names)))
+        self.n_sites = dll().uvcio_sites_count(self.h)
+
+    def fetch(self, tid, pos_beg=0, pos_end=2**31):
+        """-> int32 array: the sites of `tid` with pos_beg <= site < pos_end, ascending."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        _check(dll().uvcio_sites_fetch(self.h, tid, pos_beg, pos_end, C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.int32)
+        return np.ctypeslib.as_array((C.c_int32 * n.value).from_address(p.value)).copy()
+
+    def close(self):
+        if self.h:
+            dll().uvcio_sites_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class TumorVcf:

@@ -24,7 +24,7 @@ FILTERS = ["Q10", "Q20", "Q30", "Q40", "Q50", "Q60", "PASS"]
 
 
 def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None, molecule_tag=0, disable_duplex=0, correct_bq=True, all_out=False, keep_handle=False, reuse=None, vcf=False,
-                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0):
+                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0, force_sites=None):
     """Scores [beg, end) of `chrom`.  Returns None when no read passes the filters (process_batch returns -1, main.cpp:520-523), else a
     dict: records (field -> int32 array), alleles (InDel allele rows), score range, region handle (if keep_handle).
     Tiles of one stretch: the reference scores zerobased_pos rpos_beg .. rpos_end inclusive and skips the BASE sub-position of the first
@@ -36,6 +36,9 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     of this region become UvcScoreRequest::tumor_keys; `params.tumor_vcf_is_provided` must be set).  `umi_struct`: the in-read UMI pattern
     (the reference's environment variable ONE_STEP_UMI_STRUCT).  `assay_type`: 0 infers is_amplicon per region from the family pass, 1 (CAPTURE)
     and 2 (AMPLICON) override it (--assay-type, main.cpp:510-511).
+    `force_sites`: force-output sites (uvc1-mi355x --force-sites) -- a `uvc_amd.io.Sites`, or zerobased_pos values on `chrom` (= the VCF POS
+    of the records they select): at those positions every allele record as `all_out` writes it, the default gate elsewhere.  The sites this
+    tile owns (its score range) go into UvcScoreRequest::force_sites.
     `reuse`: a dict the caller keeps between calls; the region handle lives in it and is reset for every new region instead of being
     created and destroyed (its device buffers survive while the regions do not grow)."""
     import os, time
@@ -94,7 +97,16 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     if tumor_vcf is not None:                                                          # the tumor records inside this region (tkis_beg .. tkis_end, main.cpp:532-533)
         tk, tcols = tumor_vcf.fetch(tid, ext_beg, ext_end)
         tras = tumor_vcf.last_ref_alt
-    rec = R.score(all_out=all_out, is_amplicon=bool(is_amplicon), tumor_keys=tk, **skw)
+    fs = None
+    if force_sites is not None:
+        if tumor_vcf is not None:
+            raise ValueError("force_sites cannot go with tumor_vcf: the normal sample's gate is the tumor's rescue set")
+        if isinstance(force_sites, uio.Sites):
+            fs = force_sites.fetch(tid, skw["pos_beg"], skw["pos_end"])
+        else:
+            fs = np.asarray(force_sites, dtype=np.int64)
+            fs = fs[(fs >= skw["pos_beg"]) & (fs < skw["pos_end"])]
+    rec = R.score(all_out=all_out, is_amplicon=bool(is_amplicon), tumor_keys=tk, force_sites=fs, **skw)
     lap("bq+accumulate+score")
     out = dict(records=rec, alleles=R.indel_alleles(), rpos=(rpos_beg, rpos_end), ext=(ext_beg, ext_end), n_reads=int(g["n_kept"]), n_fams=int(g["n_fams"]), chrom=chrom, refseq=refseq, score_range=score_range)
     if vcf:

@@ -323,8 +323,9 @@ class Region:
 
     @staticmethod
     def make_request(all_out=False, pos_beg=-1, pos_end=-1, is_amplicon=False, indel_alleles=None, tumor_keys=None, release_state=False, base_at_pos_beg=False, region_beg=0,
-                     tumor_sample_columns=None, tumor_ref_alt=None, kept_only=False):
-        """UvcScoreRequest + the ctypes arrays it points into (keep both alive for the call)."""
+                     tumor_sample_columns=None, tumor_ref_alt=None, kept_only=False, force_sites=None):
+        """UvcScoreRequest + the ctypes arrays it points into (keep both alive for the call).  `force_sites`: zerobased_pos values (= the VCF
+        POS of the records they select) whose (position, symbol type) groups are scored as with all_out; sorted and de-duplicated here."""
         req = _ffi.UvcScoreRequest()
         req.pos_beg, req.pos_end, req.all_out, req.is_amplicon = pos_beg, pos_end, int(all_out), int(is_amplicon)
         req.release_state = int(release_state)   # the planes may be zeroed for the next accumulate as soon as the scoring kernels are done
@@ -348,7 +349,11 @@ class Region:
             assert len(tumor_ref_alt) == len(tk)
             ras = (C.c_char_p * len(tk))(*[c.encode() if isinstance(c, str) else c for c in tumor_ref_alt])
             req.tumor_ref_alt = C.cast(ras, C.c_void_p)
-        return req, (arr, tk, cols, ras)
+        fs = None
+        if force_sites is not None and len(force_sites):
+            fs = np.ascontiguousarray(np.unique(np.asarray(force_sites, dtype=np.int64)).astype(np.int32))
+            req.n_force_sites, req.force_sites = len(fs), fs.ctypes.data
+        return req, (arr, tk, cols, ras, fs)
 
     def hap_links(self):
         """hap_bq / hap_fq / hap_f2q of updateByRegion3Aln (uvcgpu_region_hap_links): three lists of (mutations, (fwd, rev), (other fwd, other rev))
@@ -371,11 +376,12 @@ class Region:
         return out
 
     def score(self, all_out=False, pos_beg=-1, pos_end=-1, is_amplicon=False, indel_alleles=None, capacity=None, copy=True, tumor_keys=None, release_state=False, base_at_pos_beg=False, region_beg=0,
-              kept_only=False):
-        req, _keep = self.make_request(all_out, pos_beg, pos_end, is_amplicon, indel_alleles, tumor_keys, release_state, base_at_pos_beg, region_beg, kept_only=kept_only)
+              kept_only=False, force_sites=None):
+        req, _keep = self.make_request(all_out, pos_beg, pos_end, is_amplicon, indel_alleles, tumor_keys, release_state, base_at_pos_beg, region_beg, kept_only=kept_only,
+                                       force_sites=force_sites)
         if capacity is None:
             npos = (pos_end - pos_beg) if pos_beg >= 0 else self.npos
-            capacity = 14 * (npos + 1) if all_out else max(4096, 4 * (npos + 1))
+            capacity = 14 * (npos + 1) if all_out else max(4096, 4 * (npos + 1)) + 16 * int(req.n_force_sites)
         capacity = max(capacity, getattr(self, "_score_cap", 0))   # a handle that needed a larger buffer once asks for it at once the next time
         while True:
             buf = getattr(self, "_score_buf", None)   # reused across calls: the library fills n_records columns of every row
