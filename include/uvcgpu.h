@@ -409,6 +409,22 @@ int uvcgpu_region_accumulate(uvcgpu_region_t *r);
 int64_t uvcgpu_region_score_size(const uvcgpu_region_t *r, const UvcScoreRequest *req);
 /* Replaces the BcfFormat_symbol* call group.  Synchronous: returns after D2H of the records. */
 int uvcgpu_region_score(uvcgpu_region_t *r, const UvcScoreRequest *req, UvcScoreOut *out);
+/* ---- many ranges of one accumulated region in one call (a BED panel whose lines were merged into one region) ----
+ * The records of a ranges call are the records of uvcgpu_region_score called once per range on the same accumulated handle -- the same
+ * `req` with that range's four values put in -- concatenated in range order: every field identical (the planes and the arithmetic are the
+ * same), germ_ref / germ_alt1 / germ_alt2 re-based to the returned array as kept_only does.  One gate, one set of launches, one D2H.
+ *   req->pos_beg must be -1, req->base_at_pos_beg and req->region_beg 0 (the ranges carry them); req = NULL is the default request.
+ *   Ranges are sorted and disjoint (ranges[i + 1].pos_beg >= ranges[i].pos_end) and each obeys the bounds rule of uvcgpu_region_score;
+ *   anything else is UVCGPU_EINVAL with a message that names the range, before any launch.  n_ranges >= 1.
+ * all_out, kept_only, release_state, the caller's InDel alleles, tumor keys and force_sites work as the contract above defines them. */
+typedef struct UvcScoreRange {
+    int32_t pos_beg, pos_end;     /* zerobased_pos, half open, as UvcScoreRequest::pos_beg / pos_end */
+    int32_t base_at_pos_beg;      /* as UvcScoreRequest::base_at_pos_beg, for this range */
+    int32_t region_beg;           /* as UvcScoreRequest::region_beg, for this range */
+} UvcScoreRange;
+/* Upper bound of the records of a ranges call (as uvcgpu_region_score_size, over the ranges' total length); -1 for a NULL argument. */
+int64_t uvcgpu_region_score_ranges_size(const uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges);
+int uvcgpu_region_score_ranges(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out);
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);
@@ -468,6 +484,11 @@ int uvcgpu_vcf_header_ex(const UvcParams *params, const char *sample_name, const
  * records of their position. */
 int uvcgpu_region_vcf_records(uvcgpu_region_t *r, const char *contig_name, const UvcScoreOut *scored, const UvcScoreRequest *req,
                               char *dst, int64_t capacity, int64_t *len);
+/* The text of a ranges call: `scored` is what uvcgpu_region_score_ranges filled for (req, ranges); the result is the concatenation of the
+ * texts uvcgpu_region_vcf_records gives for the single-range calls, MGVCF block and ADDITIONAL_INDEL_CANDIDATE lines included (a block looks
+ * up to 1001 positions past its range's end into the region).  The block statistics of all ranges come in one device round trip. */
+int uvcgpu_region_vcf_records_ranges(uvcgpu_region_t *r, const char *contig_name, const UvcScoreOut *scored, const UvcScoreRequest *req,
+                                     const UvcScoreRange *ranges, int64_t n_ranges, char *dst, int64_t capacity, int64_t *len);
 /* Optional: page-lock a caller buffer that is handed to the library again and again (the records buffer of uvcgpu_region_score, read
  * arrays of uvcgpu_region_set_reads): copies then run at PCIe speed.  Unpin before freeing the buffer. */
 int uvcgpu_pin_host_buffer(void *p, int64_t bytes);

@@ -152,6 +152,18 @@ int64_t uvcio_bam_region_bytes(const uvcio_bam_t *b, int32_t tid, int64_t beg, i
  * non-decreasing in i, so that the outputs of the shards, concatenated in shard order, are in tile order (uvcTN.sh:92-101 does the
  * same per chromosome with bcftools concat).  A tile goes to the shard that holds the midpoint of its cost interval. */
 int uvcio_plan_shards(const int64_t *cost, int64_t n, int32_t n_shards, int32_t *shard_of);
+/* ---- BED lines merged into device regions (uvc1-mi355x --merge-regions) ----
+ * From BED lines (tid, beg, end: 0-based, half open) in file order, the batches of consecutive lines that become one device region.  A line
+ * joins the open batch when it is on the same contig, begins at or after the previous line's end plus one (the score ranges of two lines
+ * include both of their end points and must stay disjoint), begins within merge_distance of the previous line's end, and keeps the batch's
+ * span (its first line's begin to this line's end) within max_span; otherwise it opens a new batch.  A line longer than max_span is cut
+ * into pieces of max_span, as --tile cuts it, and every piece is a batch of its own which no line joins.  Lines with end <= beg give
+ * nothing.  Unsorted or overlapping files therefore still work: they merely merge less.  merge_distance 0 merges nothing.
+ * One UvcBedPiece per line (or per piece of a cut line), in file order; `batch` counts up from 0.  *n_pieces = the number of pieces;
+ * UVCGPU_ENOMEM when capacity is smaller (call with capacity 0 for the size). */
+typedef struct UvcBedPiece { int64_t line, batch, beg, end; } UvcBedPiece;
+int uvcio_plan_bed_batches(const int32_t *tid, const int64_t *beg, const int64_t *end, int64_t n_lines, int64_t merge_distance, int64_t max_span,
+                           UvcBedPiece *out, int64_t capacity, int64_t *n_pieces);
 /* bcftools concat -n (uvcTN.sh:100): the BGZF files one after the other, the 28-byte end-of-file marker of all but the last dropped. */
 int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in);
 /* The whole text of a (block-)gzipped or plain file (the tumor VCF of a T/N pair); *buf is malloc'ed, the caller frees it. */

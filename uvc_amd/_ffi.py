@@ -71,6 +71,10 @@ class UvcScoreRequest(C.Structure):
                 ("tumor_sample_columns", C.c_void_p), ("tumor_ref_alt", C.c_void_p), ("n_force_sites", C.c_int64), ("force_sites", C.c_void_p)]
 
 
+class UvcScoreRange(C.Structure):
+    _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("base_at_pos_beg", C.c_int32), ("region_beg", C.c_int32)]
+
+
 class UvcScoreOut(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n_records", C.c_int64), ("fields", C.c_void_p)]
 

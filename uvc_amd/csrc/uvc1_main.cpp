@@ -45,6 +45,7 @@ struct Opts {
     int sequencing_platform = UVC_PLATFORM_AUTO, assay_type = 0;   // --sequencing-platform (0 AUTO, 1 ILLUMINA, 2 IONTORRENT, 3 OTHER), --assay-type (0 inferred per tile, 1 CAPTURE, 2 AMPLICON)
     int64_t tile = 0;            // 0 = no fixed tiles: the regions are the reference's own cuts (uvcio_plan_regions = SamIter::iternext); --tile N overrides
     int64_t mem_per_thread = 1536;   // --mem-per-thread (MB), CmdLineArgs.hpp:33: enters the reference's region cuts
+    int64_t merge = 0;           // --merge-regions N: BED lines at most N bp apart become ranges of one device region (0 = one region per line)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -84,6 +85,7 @@ const OptRow OPTS[] = {
     { "--bed-out-fname", O_CLI, false, "", "write the region table here" },
     { "--mem-per-thread", O_CLI, false, "1536", "MB per thread in the reference's region cuts" },
     { "--tile", O_CLI, false, "0", "fixed tiles of this many bp instead of the reference's region cuts" },
+    { "--merge-regions", O_CLI, false, "0", "with -R / --bed-in-fname: BED lines at most this many bp apart are called as ranges of one region of at most --tile bp (0: one region per line); a merged region starts its repeat track and BAQ sums at the batch's begin and sees the reads of the gaps, as a --tile region does" },
     { "--devices,--device", O_CLI, false, "", "comma-separated HIP device ids (default: all visible)" },
     { "--shard", O_CLI, false, "0/1", "i/n: this process takes the i-th of n runs of tiles" },
     { "--no-header", O_CLI, true, "", "no VCF header" },
@@ -232,6 +234,7 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "-q") set_row("vqual", name, val());
         else if (n0 == "--outvar-flag") set_row("outvar_flag", name, val());
         else if (n0 == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
+        else if (n0 == "--merge-regions") { const std::string v = val(); double x; if (!number(v, &x) || x < 0 || x != (double)(int64_t)x || x > 2e9) die("--merge-regions takes a distance in bp (0 = off), not '" + v + "'"); o.merge = (int64_t)x; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -273,6 +276,10 @@ Opts parse(int argc, char **argv) {
         if (!o.tumor_vcf.empty()) die("--force-sites cannot go with --tumor-vcf: the normal sample's gate is the tumor's rescue set");
         if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--force-sites cannot go with ") + ONLY_PRINT_VCF_HEADER + ": there are no records to force");
     }
+    if (o.merge > 0) {   // before any file or device
+        if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
+        if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
+    }
     if (const int rc = uvcgpu_params_check(&o.P)) die(std::string(uvcgpu_last_error()) + " (code " + std::to_string(rc) + ")");   // before any file or device
     if (!o.tumor_vcf.empty()) o.P.tumor_vcf_is_provided = 1;   // IS_PROVIDED(vcf_tumor_fname), common.hpp:56
     if (const char *us = getenv("ONE_STEP_UMI_STRUCT")) o.umi_struct = us;   // the reference takes the in-read UMI pattern from the environment (main.cpp:1224-1225)
@@ -309,10 +316,16 @@ double now() { return std::chrono::duration<double>(std::chrono::steady_clock::n
 
 // process_batch for one tile; appends the record lines to `lines`; false = nothing to call there.  *n_kept_reads: reads that passed the filters.
 // `tumor_ready` (pair mode): called with the tumor records' range before they are fetched; returns once the store holds all of them
-bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads,
-               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr) {
+// --merge-regions: `t0_` is the first of `n_merged` consecutive tiles of one batch (BED lines, sorted and at least one base apart).  The batch
+// is one region over [first line's begin, last line's end): one fetch, reset, set_reads and accumulate; every line becomes the score range
+// its own tile would have asked for; one uvcgpu_region_score_ranges, one uvcgpu_region_vcf_records_ranges.  n_kept_reads then has n_merged
+// entries: the kept alignments that overlap each line.  n_merged = 0: the plain call of one tile.
+bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads,
+               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr, size_t n_merged = 0) {
     double t0 = now();
-    *n_kept_reads = 0;
+    for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) n_kept_reads[q] = 0;
+    Tile t = t0_;
+    if (n_merged > 0) { t.end = (&t0_)[n_merged - 1].end; t.continues = t.has_next = false; }   // the batch's span
     UvcBamBatch b;
     if (uvcio_bam_fetch(w.bam, t.tid, std::max<int64_t>(0, t.beg - MAX_INSERT_SIZE), t.end + MAX_INSERT_SIZE, &b)) die(uvcio_last_error());
     w.t_fetch += now() - t0; t0 = now();
@@ -333,7 +346,13 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     if (uvcgpu_group_families(&gp, &gi, &go)) die(uvcgpu_last_error());
     w.t_group += now() - t0; t0 = now();
     const int64_t k = go.n_kept;
-    *n_kept_reads = k;
+    if (n_merged == 0) *n_kept_reads = k;
+    else for (int64_t i = 0; i < k; i++) {   // the lines a kept alignment overlaps (sorted, disjoint: the first line that ends behind its begin, and on)
+        const int64_t rb = b.pos[w.order[(size_t)i]], re = b.endpos[w.order[(size_t)i]];
+        size_t lo = 0, hi = n_merged;
+        while (lo < hi) { const size_t mid = (lo + hi) / 2; if ((&t0_)[mid].end <= rb) lo = mid + 1; else hi = mid; }
+        for (; lo < n_merged && (&t0_)[lo].beg < re; lo++) n_kept_reads[lo]++;
+    }
     if (k == 0) return false;
     // region bounds and reference, main.cpp:523-552
     const int64_t bam_beg = go.extended_inclu_beg_pos, bam_end = go.extended_exclu_end_pos;
@@ -341,7 +360,15 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     const int64_t ext_beg = std::max<int64_t>(0, std::min(t.beg, bam_beg) - MAX_STR_N_BASES), ext_end = std::min(tlen, std::max(t.end, bam_end) + MAX_STR_N_BASES);
     const int64_t first = rpos_beg;
     const int64_t last_excl = t.has_next ? std::min(t.end, bam_end + 1) : std::min(rpos_end + 1, ext_end);   // zerobased_pos t.end belongs to the next tile
-    if (last_excl <= first) return false;
+    // the ranges of a batch: per line what the lines above compute for a tile, with the batch's reads and extent
+    std::vector<UvcScoreRange> ranges;
+    for (size_t q = 0; q < n_merged; q++) {
+        const Tile &l = (&t0_)[q];
+        const int64_t l_first = std::max(l.beg, bam_beg);
+        const int64_t l_excl = l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end);
+        if (l_excl > l_first) ranges.push_back(UvcScoreRange{ (int32_t)l_first, (int32_t)l_excl, (l.continues && l_first == l.beg && l.beg > ext_beg) ? 1 : 0, (int32_t)l.run_beg });
+    }
+    if (n_merged > 0 ? ranges.empty() : last_excl <= first) return false;
     w.ref.resize((size_t)(ext_end - ext_beg));
     if (uvcio_fasta_fetch(w.fa, t.chrom.c_str(), ext_beg, ext_end, &w.ref[0])) die(uvcio_last_error());
     int rc = w.reg ? uvcgpu_region_reset(w.reg, t.tid, (int32_t)ext_beg, (int32_t)ext_end, w.ref.c_str())
@@ -365,6 +392,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
     rq.is_amplicon = (o.assay_type == 0 ? (go.n_amplicon * 2 > k) : (o.assay_type == 2));   // inferred_assay_type, main.cpp:510-511
     rq.base_at_pos_beg = (t.continues && first == t.beg && t.beg > ext_beg) ? 1 : 0; rq.region_beg = (int32_t)t.run_beg;
+    if (n_merged > 0) { rq.pos_beg = -1; rq.pos_end = -1; rq.base_at_pos_beg = 0; rq.region_beg = 0; }   // the ranges carry them
     if (tvcf) {   // normal sample of a T/N pair: the tumor records of this region (tkis_beg .. tkis_end, main.cpp:532-533)
         const UvcTumorKey *keys = nullptr; const char *const *cols = nullptr, *const *ras = nullptr; int64_t nk = 0;
         if (tumor_ready) (*tumor_ready)(t.tid, ext_beg, ext_end);
@@ -373,12 +401,14 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     }
     if (o.sites && uvcio_sites_fetch(o.sites, t.tid, first, last_excl, &rq.force_sites, &rq.n_force_sites)) die(uvcio_last_error());   // the sites this tile owns
     rq.kept_only = 1;   // only the record groups that are written travel to the host
-    int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), uvcgpu_region_score_size(w.reg, &rq) / (rq.all_out ? 1 : 64) + 16 * rq.n_force_sites);
+    const int64_t n_ranges = (int64_t)ranges.size();
+    const int64_t upper = n_merged > 0 ? uvcgpu_region_score_ranges_size(w.reg, &rq, ranges.data(), n_ranges) : uvcgpu_region_score_size(w.reg, &rq);
+    int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), upper / (rq.all_out ? 1 : 64) + 16 * rq.n_force_sites);
     UvcScoreOut so;
     for (;;) {
         w.fields.resize((size_t)UVC_NUM_SCORE_FIELDS * (size_t)cap);
         so.capacity = cap; so.n_records = 0; so.fields = w.fields.data();
-        rc = uvcgpu_region_score(w.reg, &rq, &so);
+        rc = n_merged > 0 ? uvcgpu_region_score_ranges(w.reg, &rq, ranges.data(), n_ranges, &so) : uvcgpu_region_score(w.reg, &rq, &so);
         if (rc == UVCGPU_ENOMEM && so.n_records > cap) { cap = so.n_records + so.n_records / 4; continue; }
         if (rc) die(uvcgpu_last_error());
         break;
@@ -390,7 +420,8 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t, int6
     int64_t len = 0, room = std::max<int64_t>(1 << 16, w.text_cap);
     for (;;) {
         lines.resize(at + (size_t)room);
-        rc = uvcgpu_region_vcf_records(w.reg, t.chrom.c_str(), &so, &rq, &lines[at], room, &len);
+        rc = n_merged > 0 ? uvcgpu_region_vcf_records_ranges(w.reg, t.chrom.c_str(), &so, &rq, ranges.data(), n_ranges, &lines[at], room, &len)
+                          : uvcgpu_region_vcf_records(w.reg, t.chrom.c_str(), &so, &rq, &lines[at], room, &len);
         if (rc == UVCGPU_ENOMEM && len > room) { room = len + len / 4; continue; }
         if (rc) die(uvcgpu_last_error());
         break;
@@ -442,7 +473,9 @@ void link_runs(std::vector<Tile> &tiles) {
 }
 
 // the tiles: --bed-in-fname / -R regions, --targets "chr" or "chr:beg-end" (1-based inclusive as in samtools), else every contig
-std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G) {
+// `batch_of` (--merge-regions): the batch of every tile, from uvcio_plan_bed_batches over the BED lines; consecutive tiles of one batch
+// are called as the ranges of one device region
+std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr) {
     const std::vector<std::string> &names = G.names; const std::vector<int64_t> &lens = G.lens; const int32_t nref = (int32_t)names.size();
     std::vector<Tile> tiles;
     const std::string bed_path = (!o.bed_in.empty() ? o.bed_in : o.bed);
@@ -476,6 +509,7 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G) {
         FILE *fb = fopen(bed_path.c_str(), "r");
         if (!fb) die("cannot open " + bed_path);
         char line[4096], chrom[1024]; long long b = 0, e = 0;
+        std::vector<int32_t> l_tid; std::vector<int64_t> l_beg, l_end;   // the lines as `add` sees them
         while (fgets(line, sizeof(line), fb)) {
             if (line[0] == '#' || !strncmp(line, "track", 5) || !strncmp(line, "browser", 7)) continue;
             if (sscanf(line, "%1023s %lld %lld", chrom, &b, &e) != 3) continue;
@@ -483,8 +517,19 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G) {
             for (int32_t i = 0; i < nref; i++) if (names[(size_t)i] == chrom) tid = i;
             if (tid < 0) die(std::string("the BED file names a contig that is not in the BAM header: ") + chrom);
             add(tid, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]));
+            l_tid.push_back(tid); l_beg.push_back(std::max<long long>(0, b)); l_end.push_back(std::min<long long>(e, lens[(size_t)tid]));
         }
         fclose(fb);
+        if (batch_of && o.merge > 0) {   // one piece per tile: the planner cuts an over-long line exactly as `add` does
+            std::vector<UvcBedPiece> pieces(tiles.size() + 1); int64_t np = 0;
+            if (uvcio_plan_bed_batches(l_tid.data(), l_beg.data(), l_end.data(), (int64_t)l_tid.size(), o.merge, o.tile, pieces.data(), (int64_t)pieces.size(), &np)) die(uvcio_last_error());
+            if (np != (int64_t)tiles.size()) die("--merge-regions: the batch planner and the tile list disagree (internal error)");
+            batch_of->resize(tiles.size());
+            for (size_t q = 0; q < tiles.size(); q++) {
+                if (pieces[q].beg != tiles[q].beg || pieces[q].end != tiles[q].end) die("--merge-regions: the batch planner and the tile list disagree (internal error)");
+                (*batch_of)[q] = pieces[q].batch;
+            }
+        }
     } else if (!o.targets.empty()) {
         std::string chrom = o.targets; int64_t beg = 0, end = -1;
         const size_t c = o.targets.rfind(':');
@@ -619,6 +664,8 @@ PairArgs split_pair(int argc, char **argv) {
         if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
+        if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
+            die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
         if (t == ONLY_PRINT_VCF_HEADER) die(std::string(ONLY_PRINT_VCF_HEADER) + " cannot go with --normal-bam");
         const OptRow *row = (t[0] == '-' ? find_opt(name) : nullptr);
         if (t[0] == '-' && t.find('=') == std::string::npos && ((row && !row->flag) || (!row && find_param(name) >= 0))) i++;   // skip the value
@@ -873,17 +920,35 @@ int main(int argc, char **argv) {
     Geometry G;
     uvcio_bam_t *bam0 = open_bam(o.bam, G);
     const int32_t nref = (int32_t)G.names.size();
-    std::vector<Tile> tiles = plan_tiles(o, bam0, G);
+    std::vector<int64_t> batch_of;   // --merge-regions: the batch of every tile (else empty: every tile is its own job)
+    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of);
     if (o.n_shards > 1) {
-        const std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
-        std::vector<Tile> mine;
-        for (size_t q = 0; q < tiles.size(); q++) if (shard_of[q] == o.shard) mine.push_back(tiles[q]);
+        std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
+        if (!batch_of.empty()) {   // balanced over batches: a batch is one region and goes to one shard, at the sum of its tiles' costs
+            std::vector<int64_t> cost; std::vector<int32_t> of_batch;
+            for (size_t q = 0; q < tiles.size(); q++) {
+                const int64_t c = uvcio_bam_region_bytes(bam0, tiles[q].tid, tiles[q].beg, tiles[q].end) + (tiles[q].end - tiles[q].beg) / 8 + 1;
+                if (q > 0 && batch_of[q] == batch_of[q - 1]) cost.back() += c; else cost.push_back(c);
+            }
+            of_batch.resize(cost.size());
+            if (uvcio_plan_shards(cost.data(), (int64_t)cost.size(), o.n_shards, of_batch.data())) die(uvcio_last_error());
+            for (size_t q = 0, bi = 0; q < tiles.size(); q++) { if (q > 0 && batch_of[q] != batch_of[q - 1]) bi++; shard_of[q] = of_batch[bi]; }
+        }
+        std::vector<Tile> mine; std::vector<int64_t> mine_batch;
+        for (size_t q = 0; q < tiles.size(); q++) if (shard_of[q] == o.shard) { mine.push_back(tiles[q]); if (!batch_of.empty()) mine_batch.push_back(batch_of[q]); }
         fprintf(stderr, "uvc1-mi355x: shard %d of %d takes %zu of %zu tiles\n", o.shard, o.n_shards, mine.size(), tiles.size());
-        tiles.swap(mine);
+        tiles.swap(mine); batch_of.swap(mine_batch);
         if (o.shard > 0) o.no_header = true;
     }
     const size_t tiles_per_pass = tiles.size();
-    for (int rep = 1; rep < o.repeat; rep++) for (size_t q = 0; q < tiles_per_pass; q++) tiles.push_back(tiles[q]);
+    for (int rep = 1; rep < o.repeat; rep++) for (size_t q = 0; q < tiles_per_pass; q++) { tiles.push_back(tiles[q]); if (!batch_of.empty()) batch_of.push_back(batch_of[q] + (int64_t)rep * ((int64_t)tiles_per_pass + 1)); }
+    // a job = what one call_tile takes: a tile, or with --merge-regions the consecutive tiles of one batch
+    std::vector<std::pair<size_t, size_t>> jobs;   // first tile, number of tiles
+    for (size_t q = 0; q < tiles.size(); q++) {
+        if (!batch_of.empty() && q > 0 && batch_of[q] == batch_of[q - 1]) jobs.back().second++; else jobs.emplace_back(q, 1);
+    }
+    const bool merging = !batch_of.empty();
+    if (merging) fprintf(stderr, "uvc1-mi355x: --merge-regions %lld: %zu BED lines in %zu regions\n", (long long)o.merge, tiles_per_pass, jobs.size() / (size_t)o.repeat);
     if (!platform_given) infer_platform(o, bam0, tiles);
     uvcio_bam_close(bam0);
     if (o.print_params) { print_params(o); return 0; }
@@ -910,10 +975,10 @@ int main(int argc, char **argv) {
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
     }
     const double t_start = now();
-    std::vector<std::string> done(tiles.size()); std::vector<char> ready(tiles.size(), 0); std::vector<int64_t> tile_reads(tiles.size(), 0);
+    std::vector<std::string> done(jobs.size()); std::vector<char> ready(jobs.size(), 0); std::vector<int64_t> tile_reads(tiles.size(), 0);
     std::mutex mu; std::condition_variable cv; std::atomic<size_t> next{ 0 };
     size_t written = 0;   // tiles the writer has taken (guarded by mu)
-    const int nthreads = (int)std::min<size_t>((size_t)o.threads, std::max<size_t>(tiles.size(), 1));
+    const int nthreads = (int)std::min<size_t>((size_t)o.threads, std::max<size_t>(jobs.size(), 1));
     const size_t max_ahead = (size_t)4 * (size_t)nthreads;
     std::vector<Worker> workers((size_t)nthreads);
     std::vector<std::thread> th;
@@ -922,27 +987,29 @@ int main(int argc, char **argv) {
         if (uvcgpu_init(o.devices[(size_t)wi % o.devices.size()])) die(uvcgpu_last_error());   // binds this host thread to its device
         if (uvcio_bam_open(&w.bam, o.bam.c_str()) || uvcio_fasta_open(&w.fa, o.fasta.c_str())) die(uvcio_last_error());
         for (;;) {
-            const size_t ti = next.fetch_add(1);
-            if (ti >= tiles.size()) break;
+            const size_t ji = next.fetch_add(1);
+            if (ji >= jobs.size()) break;
+            const size_t ti = jobs[ji].first, nt = jobs[ji].second;
             // bounded run-ahead: finished tiles wait in `done` for the in-order writer; a worker does not start a tile more than
             // 4 * threads in front of it, so a slow early tile cannot make the rest of the genome pile up in memory
-            { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ti < written + max_ahead; }); }
-            std::string lines; int64_t nk = 0;
-            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, &nk);
+            { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ji < written + max_ahead; }); }
+            std::string lines; std::vector<int64_t> nk(nt, 0);
+            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0);
             w.n_tiles++;
-            { std::lock_guard<std::mutex> g(mu); done[ti].swap(lines); ready[ti] = 1; tile_reads[ti] = nk; }
+            { std::lock_guard<std::mutex> g(mu); done[ji].swap(lines); ready[ji] = 1; for (size_t q = 0; q < nt; q++) tile_reads[ti + q] = nk[q]; }
             cv.notify_all();
         }
         if (w.reg) uvcgpu_region_destroy(w.reg);
         uvcio_bam_close(w.bam); uvcio_fasta_close(w.fa);
     });
     int64_t n_lines = 0, n_pos = 0; double t_first_pass = 0; int64_t pos_first_pass = 0;
-    for (size_t ti = 0; ti < tiles.size(); ti++) {
-        if (ti == tiles_per_pass) { t_first_pass = now() - t_start; pos_first_pass = n_pos; }
+    for (size_t ji = 0; ji < jobs.size(); ji++) {
+        if (jobs[ji].first == tiles_per_pass) { t_first_pass = now() - t_start; pos_first_pass = n_pos; }
         std::string lines;
-        { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ready[ti] != 0; }); lines.swap(done[ti]); written = ti + 1; }
+        { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ready[ji] != 0; }); lines.swap(done[ji]); written = ji + 1; }
         cv.notify_all();
-        n_lines += std::count(lines.begin(), lines.end(), '\n'); n_pos += tiles[ti].end - tiles[ti].beg;
+        n_lines += std::count(lines.begin(), lines.end(), '\n');
+        for (size_t q = 0; q < jobs[ji].second; q++) n_pos += tiles[jobs[ji].first + q].end - tiles[jobs[ji].first + q].beg;
         if (!lines.empty() && uvcio_bgzf_write(zw, lines.data(), (int64_t)lines.size())) die(uvcio_last_error());
     }
     for (auto &t : th) t.join();

@@ -34,13 +34,15 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
                                       const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work, hipStream_t s, UvcProf *prof,
                                       hipStream_t side, hipEvent_t e_fork, hipEvent_t e_join, hipEvent_t e_fork2, hipStream_t side3, hipEvent_t e_join3, hipEvent_t e_stat, hipEvent_t e_alleles);
 extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity, char *scratch, int32_t *d_fields_kept, const int32_t *d_force_sites, hipStream_t s);
+                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity, char *scratch, int32_t *d_fields_kept, const int32_t *d_force_sites,
+                                const void *d_ranges, int64_t n_ranges, int64_t n_compact, hipStream_t s);
 extern "C" size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity);
 extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity);
 extern "C" void uvc_launch_zero_state(char *slab, const void *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s);
 extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
 extern "C" void uvc_launch_check_presence(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
 extern "C" void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s);
+extern "C" void uvc_launch_block_stats_windows(const RegionDev *R, const UvcParams *P, const long long *d_win, int n_win, int64_t n, int32_t *d_out, hipStream_t s);
 extern "C" size_t uvc_gap_sort_tmp_bytes(size_t n);
 extern "C" void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
 extern "C" void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
@@ -776,6 +778,34 @@ int uvcgpu_region_block_stats_(uvcgpu_region_t *r, int32_t refpos_beg, int32_t r
     if (e != hipSuccess) return fail(UVCGPU_EDEVICE, hipGetErrorString(e));
     return 0;
 }
+// The same for n_win disjoint windows [win[2k], win[2k + 1]) of refpos in one round trip: one upload of the window table, one launch, one D2H.
+// dst receives the windows' rows back to back.
+int uvcgpu_region_block_stats_windows_(uvcgpu_region_t *r, const int32_t *win, int64_t n_win, int32_t *dst) {
+    if (!r || !win || !dst || n_win < 0 || n_win > INT32_MAX) return fail(UVCGPU_EINVAL, "bad argument");
+    if (!r->accumulated) return fail(UVCGPU_ESTATE, "fetch before accumulate");
+    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    std::vector<long long> tab((size_t)(2 * n_win));
+    int64_t n = 0;
+    for (int64_t k = 0; k < n_win; k++) {
+        if (win[2 * k + 1] <= win[2 * k]) return fail(UVCGPU_EINVAL, "block statistics: empty window");
+        tab[(size_t)(2 * k)] = (long long)win[2 * k] - r->beg; tab[(size_t)(2 * k + 1)] = n; n += (int64_t)win[2 * k + 1] - win[2 * k];
+    }
+    if (n == 0) return 0;
+    int rc = uvcgpu_region_sync(r);
+    if (rc) return rc;
+    long long *d_tab = nullptr; int32_t *d = nullptr;
+    if (hipMalloc((void **)&d_tab, sizeof(long long) * tab.size()) != hipSuccess || hipMalloc((void **)&d, sizeof(int32_t) * 10 * (size_t)n) != hipSuccess) {
+        if (d_tab) hipFree(d_tab);
+        return fail(UVCGPU_ENOMEM, "hipMalloc(block stats) failed");
+    }
+    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) { uvc_launch_block_stats_windows(&r->R, &r->P, d_tab, (int)n_win, n, d, r->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, d, sizeof(int32_t) * 10 * (size_t)n, hipMemcpyDeviceToHost, r->stream);
+    const hipError_t e2 = hipStreamSynchronize(r->stream);   // also when a step failed: `tab` and the two blocks are in use until the stream is idle
+    hipFree(d); hipFree(d_tab);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(UVCGPU_EDEVICE, hipGetErrorString(e != hipSuccess ? e : e2));
+    return 0;
+}
 // Page-locks a caller buffer (the records buffer of uvcgpu_region_score, the read arrays of uvcgpu_region_set_reads) so that copies to
 // and from it run at PCIe speed instead of through the runtime's staging buffers.  Optional; the buffer must be unpinned before it is freed.
 int uvcgpu_pin_host_buffer(void *p, int64_t bytes) {
@@ -1017,6 +1047,12 @@ int64_t uvcgpu_region_score_size(const uvcgpu_region_t *r, const UvcScoreRequest
     const int64_t np = (req && req->pos_beg >= 0) ? (req->pos_end - req->pos_beg) : r->npos;
     return NSYM * (np + 1) + (req ? req->n_indel_alleles + req->n_tumor_keys + 16 * std::max<int64_t>(req->n_force_sites, 0) : 0) + (int64_t)r->gap_alleles.size();
 }
+int64_t uvcgpu_region_score_ranges_size(const uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges) {
+    if (!r || !ranges || n_ranges < 0) return -1;
+    int64_t np = 0;
+    for (int64_t k = 0; k < n_ranges; k++) np += std::max<int64_t>((int64_t)ranges[k].pos_end - ranges[k].pos_beg, 0);
+    return NSYM * (np + 1) + (req ? req->n_indel_alleles + req->n_tumor_keys + 16 * std::max<int64_t>(req->n_force_sites, 0) : 0) + (int64_t)r->gap_alleles.size();
+}
 
 // Small host arrays of a score call go to the device through the handle's own page-locked staging buffer: an asynchronous copy straight from
 // the caller's pageable memory lets the runtime map those heap pages for the GPU (read-only, as a copy source), and heap pages come back to the
@@ -1035,29 +1071,50 @@ static int stage_upload(uvcgpu_region_t *r, void *dst, const void *src, size_t b
     return 0;
 }
 
-static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, UvcScoreOut *out) {
+// `ranges` (uvcgpu_region_score_ranges) or NULL (uvcgpu_region_score): everything but the group axis is the same call
+struct ScoreRangeDev { int32_t beg, end, first, flags; };   // UvcScoreRangeDev of uvc_kernels_score.hip
+static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
     if (!r || !out || !out->fields) return fail(UVCGPU_EINVAL, "bad argument");
     if (!r->accumulated) return fail(UVCGPU_ESTATE, "score before accumulate");
     if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq)); rq.pos_beg = -1;
     if (req) rq = *req;
-    if (rq.pos_beg < 0) { rq.pos_beg = r->beg + 1; rq.pos_end = r->end - 1; }
-    // zerobased_pos == region begin is legal (a contig that starts inside the region: main.cpp:617-619 guards its "base in front" with BASE_NN);
-    // with base_at_pos_beg the BASE sub-position of pos_beg reads refpos pos_beg - 1, which must be inside the region
-    if (rq.pos_beg < r->beg + (rq.base_at_pos_beg ? 1 : 0) || rq.pos_end > r->end - 1 || rq.pos_end < rq.pos_beg) return fail(UVCGPU_EINVAL, "score range outside the region");
+    std::vector<ScoreRangeDev> rtab;   // ranges call: the device table; npos_scored = the compact length
+    int64_t npos_scored = 0;
+    if (ranges) {
+        if (n_ranges < 1 || n_ranges > INT32_MAX) return fail(UVCGPU_EINVAL, "score_ranges: n_ranges must be at least 1");
+        if (rq.pos_beg != -1 || rq.base_at_pos_beg != 0 || rq.region_beg != 0) return fail(UVCGPU_EINVAL, "score_ranges: the request's pos_beg must be -1, its base_at_pos_beg and region_beg 0 (the ranges carry them)");
+        rtab.resize((size_t)n_ranges);
+        for (int64_t k = 0; k < n_ranges; k++) {
+            const UvcScoreRange &q = ranges[k];
+            if (q.pos_beg < r->beg + (q.base_at_pos_beg ? 1 : 0) || q.pos_end > r->end - 1 || q.pos_end < q.pos_beg)   // the bounds rule of the plain call, below
+                return fail(UVCGPU_EINVAL, "score_ranges: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ") is outside the region");
+            if (k > 0 && q.pos_beg < ranges[k - 1].pos_end)
+                return fail(UVCGPU_EINVAL, "score_ranges: range " + std::to_string(k) + " begins at " + std::to_string(q.pos_beg) + ", in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
+            rtab[(size_t)k] = ScoreRangeDev{ q.pos_beg, q.pos_end, (int32_t)npos_scored, q.base_at_pos_beg ? 1 : 0 };
+            npos_scored += (int64_t)q.pos_end - q.pos_beg;
+        }
+        rq.pos_beg = ranges[0].pos_beg; rq.pos_end = ranges[n_ranges - 1].pos_end;   // (the kernels take the table; these only keep the request well-formed)
+    } else {
+        if (rq.pos_beg < 0) { rq.pos_beg = r->beg + 1; rq.pos_end = r->end - 1; }
+        // zerobased_pos == region begin is legal (a contig that starts inside the region: main.cpp:617-619 guards its "base in front" with BASE_NN);
+        // with base_at_pos_beg the BASE sub-position of pos_beg reads refpos pos_beg - 1, which must be inside the region
+        if (rq.pos_beg < r->beg + (rq.base_at_pos_beg ? 1 : 0) || rq.pos_end > r->end - 1 || rq.pos_end < rq.pos_beg) return fail(UVCGPU_EINVAL, "score range outside the region");
+        npos_scored = (int64_t)rq.pos_end - rq.pos_beg;
+    }
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
-    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr;
+    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; ScoreRangeDev *d_rg = nullptr;
     std::vector<UvcIndelAllele> merged; std::vector<int32_t> merged_row;
     // the temporaries go back to the caching allocator, which hands them to other handles at once: on every return path the stream is
     // drained first (async copies from `merged` / the caller's keys, kernels that read the blocks), then they are freed
-    struct Temps { uvcgpu_region *r; UvcIndelAllele *&a; int32_t *&b; UvcTumorKey *&c; int32_t *&d;
-                   ~Temps() { if (a || b || c || d) (void)hipStreamSynchronize(r->stream); if (a) hipFree(a); if (b) hipFree(b); if (c) hipFree(c); if (d) hipFree(d); } } temps = { r, d_al, d_al_row, d_tk, d_fs };
+    struct Temps { uvcgpu_region *r; UvcIndelAllele *&a; int32_t *&b; UvcTumorKey *&c; int32_t *&d; ScoreRangeDev *&e;
+                   ~Temps() { if (a || b || c || d || e) (void)hipStreamSynchronize(r->stream); if (a) hipFree(a); if (b) hipFree(b); if (c) hipFree(c); if (d) hipFree(d); if (e) hipFree(e); } } temps = { r, d_al, d_al_row, d_tk, d_fs, d_rg };
     const UvcIndelAllele *use_al = r->d_gap_alleles; const int32_t *use_row = r->d_gap_allele_row; int64_t n_al = (int64_t)r->gap_alleles.size();
     // one staging layout per call (an earlier call's copies are complete: score synchronises before it returns)
     size_t stage_at = 0;
     const size_t stage_total = (sizeof(UvcIndelAllele) + sizeof(int32_t)) * (size_t)(r->gap_alleles.size() + (size_t)std::max<int64_t>(rq.n_indel_alleles, 0)) + sizeof(UvcTumorKey) * (size_t)std::max<int64_t>(rq.n_tumor_keys, 0)
-                              + sizeof(int32_t) * (size_t)std::max<int64_t>(rq.n_force_sites, 0) + 256;
+                              + sizeof(int32_t) * (size_t)std::max<int64_t>(rq.n_force_sites, 0) + sizeof(ScoreRangeDev) * rtab.size() + 320;
     if (rq.n_indel_alleles > 0) {
         auto less = [](const UvcIndelAllele &a, const UvcIndelAllele &b) { return a.refpos < b.refpos || (a.refpos == b.refpos && a.symbol < b.symbol); };
         for (int64_t q = 1; q < rq.n_indel_alleles; q++) if (less(rq.indel_alleles[q], rq.indel_alleles[q - 1])) return fail(UVCGPU_EINVAL, "indel_alleles must be sorted by (refpos, symbol)");
@@ -1091,11 +1148,15 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         HIP_OK(hipMalloc((void **)&d_fs, sizeof(int32_t) * (size_t)rq.n_force_sites));
         { int rc1 = stage_upload(r, d_fs, rq.force_sites, sizeof(int32_t) * (size_t)rq.n_force_sites, stage_at, stage_total); if (rc1) return rc1; }
     }
+    if (!rtab.empty()) {   // the ranges, through the staging buffer like the keys and the sites (k_range_map makes the position table)
+        HIP_OK(hipMalloc((void **)&d_rg, sizeof(ScoreRangeDev) * rtab.size()));
+        { int rc1 = stage_upload(r, d_rg, rtab.data(), sizeof(ScoreRangeDev) * rtab.size(), stage_at, stage_total); if (rc1) return rc1; }
+    }
     const bool kept_only = (rq.kept_only != 0);
     // device capacity: the caller's in the plain form; with kept_only the caller's buffer only has to hold the kept groups, the device
     // array every record -- start from a guess and grow once if the count says so
     int64_t cap = std::max<int64_t>(out->capacity, 1);
-    if (kept_only) cap = std::max<int64_t>(std::max<int64_t>(cap, r->score_capacity), (int64_t)(rq.pos_end - rq.pos_beg) / 8 + 4096);
+    if (kept_only) cap = std::max<int64_t>(std::max<int64_t>(cap, r->score_capacity), npos_scored / 8 + 4096);
     int rc = 0;
     int64_t cnt[2] = { 0, 0 };
     for (int attempt = 0; attempt < 2 && !rc; attempt++) {
@@ -1112,7 +1173,7 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
             r->score_kept_capacity = r->score_capacity;
         }
         {   // the staged rows of the scoring kernels are sized by the record capacity
-            const size_t need = uvc_score_scratch_bytes(rq.pos_end - rq.pos_beg, r->score_capacity);
+            const size_t need = uvc_score_scratch_bytes(npos_scored, r->score_capacity);
             if (need > r->score_scratch_bytes) {
                 if (r->d_score_scratch) hipFree(r->d_score_scratch);
                 r->d_score_scratch = nullptr; r->score_scratch_bytes = 0;
@@ -1121,11 +1182,11 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
             }
             r->d_score_count = (int64_t *)r->d_score_scratch;   // the record counts head the scratch (zeroed with the scan states)
         }
-        HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(rq.pos_end - rq.pos_beg, r->score_capacity), r->stream));
+        HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos_scored, r->score_capacity), r->stream));
         int pi = -1;   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
         if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = "k_score_all"; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); }
         rc = uvc_launch_score(&r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, r->d_score_fields, r->score_capacity, r->d_score_scratch,
-                              kept_only ? r->d_score_kept : nullptr, d_fs, r->stream);
+                              kept_only ? r->d_score_kept : nullptr, d_fs, d_rg, (int64_t)rtab.size(), npos_scored, r->stream);
         if (rc) rc = fail(rc, "score: the force-output mask could not be cleared");
         if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream);
         if (!rc && hipGetLastError() != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score kernel launch failed");
@@ -1165,7 +1226,10 @@ int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t g, void *dst, int64_t dst_by
 int uvcgpu_region_fetch_columns(uvcgpu_region_t *r, const int32_t *refpos, int64_t n, int64_t *dst) { return guarded("uvcgpu_region_fetch_columns", [&] { return uvcgpu_region_fetch_columns_impl(r, refpos, n, dst); }); }
 int uvcgpu_region_indel_alleles(uvcgpu_region_t *r, UvcGapRow *rows, int64_t row_capacity, int64_t *n_rows, uint8_t *seq, int64_t seq_capacity, int64_t *seq_bytes) { return guarded("uvcgpu_region_indel_alleles", [&] { return uvcgpu_region_indel_alleles_impl(r, rows, row_capacity, n_rows, seq, seq_capacity, seq_bytes); }); }
 int uvcgpu_region_hap_links(uvcgpu_region_t *r, UvcHapLink *links, int64_t link_capacity, int64_t *n_links, int32_t *muts, int64_t mut_capacity, int64_t *n_mut_ints) { return guarded("uvcgpu_region_hap_links", [&] { return uvcgpu_region_hap_links_impl(r, links, link_capacity, n_links, muts, mut_capacity, n_mut_ints); }); }
-int uvcgpu_region_score(uvcgpu_region_t *r, const UvcScoreRequest *req, UvcScoreOut *out) { return guarded("uvcgpu_region_score", [&] { return uvcgpu_region_score_impl(r, req, out); }); }
+int uvcgpu_region_score(uvcgpu_region_t *r, const UvcScoreRequest *req, UvcScoreOut *out) { return guarded("uvcgpu_region_score", [&] { return uvcgpu_region_score_impl(r, req, nullptr, 0, out); }); }
+int uvcgpu_region_score_ranges(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
+    return guarded("uvcgpu_region_score_ranges", [&] { return ranges ? uvcgpu_region_score_impl(r, req, ranges, n_ranges, out) : fail(UVCGPU_EINVAL, "score_ranges: ranges is NULL"); });
+}
 
 void uvcgpu_region_destroy(uvcgpu_region_t *r) {
     if (!r) return;

@@ -865,6 +865,30 @@ extern "C" int uvcio_plan_shards(const int64_t *cost, int64_t n, int32_t n_shard
     }
     return 0;
 }
+// BED lines in file order -> the batches of consecutive lines that become one device region (uvc1-mi355x --merge-regions), see uvcio.h
+extern "C" int uvcio_plan_bed_batches(const int32_t *tid, const int64_t *beg, const int64_t *end, int64_t n_lines, int64_t merge_distance, int64_t max_span,
+                                      UvcBedPiece *out, int64_t capacity, int64_t *n_pieces) {
+    if (n_lines < 0 || (n_lines > 0 && (!tid || !beg || !end)) || merge_distance < 0 || max_span < 1 || !n_pieces || capacity < 0 || (capacity > 0 && !out))
+        return fail(UVCGPU_EINVAL, "plan_bed_batches: bad argument");
+    int64_t n = 0, batch = -1, batch_beg = 0, prev_end = 0; int32_t batch_tid = -1;
+    bool open = false;   // the last batch may take another line (it is not a piece of a cut line)
+    auto put = [&](int64_t line, int64_t b, int64_t e) { if (n < capacity) out[n] = UvcBedPiece{ line, batch, b, e }; n++; };
+    for (int64_t i = 0; i < n_lines; i++) {
+        if (beg[i] < 0 || tid[i] < 0) return fail(UVCGPU_EINVAL, "plan_bed_batches: line " + std::to_string(i) + " has a negative begin or contig");
+        if (end[i] <= beg[i]) continue;   // nothing to call
+        if (end[i] - beg[i] > max_span) {   // cut into tiles as without merging; every piece is a batch of its own
+            for (int64_t b = beg[i]; b < end[i]; b += max_span) { batch++; put(i, b, std::min(b + max_span, end[i])); }
+            open = false;
+            continue;
+        }
+        const bool joins = open && tid[i] == batch_tid && beg[i] >= prev_end + 1 && beg[i] - prev_end <= merge_distance && end[i] - batch_beg <= max_span;
+        if (!joins) { batch++; batch_tid = tid[i]; batch_beg = beg[i]; open = true; }
+        put(i, beg[i], end[i]);
+        prev_end = end[i];
+    }
+    *n_pieces = n;
+    return n > capacity ? fail(UVCGPU_ENOMEM, "plan_bed_batches: capacity too small") : 0;
+}
 extern "C" int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in) {
     if (!out_path || n_in < 0 || (n_in > 0 && !in_paths)) return fail(UVCGPU_EINVAL, "bad argument");
     static const uint8_t eof_marker[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };

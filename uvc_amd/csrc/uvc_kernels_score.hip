@@ -109,6 +109,9 @@ DEV RtrLite load_rtr(const RegionDev &R, int idx) { RtrLite r; r.tracklen = RTRP
 #define OUT(fld, v) ROW_(int32_t, fields, fld, capacity, rec) = (v)
 
 // ------------------------------------------------------------------------------------------------
+// one range of uvcgpu_region_score_ranges on the device: [beg, end) in zerobased_pos, first = the compact position of beg (exclusive prefix
+// of the lengths), flags bit 0 = base_at_pos_beg
+struct UvcScoreRangeDev { int beg, end, first, flags; };
 struct ScoreCtx {
     int pos_beg, pos_end, all_out, is_amplicon, base_at_beg;
     const UvcIndelAllele *alleles; long long n_alleles;   // sorted by (refpos, symbol): the region's own InDel alleles, or the caller's where it listed any
@@ -119,7 +122,19 @@ struct ScoreCtx {
     const unsigned *force_mask;   // UvcScoreRequest::force_sites as one bit per zerobased_pos of [pos_beg, pos_end) (k_force_mask), or NULL
     long long *offsets;   // exclusive prefix of per-group packed (flag << 32 | allele count), [2 * (pos_end - pos_beg) + 1]
     int *active;          // groups with at least one allele, ascending
+    // uvcgpu_region_score_ranges: the group axis is the COMPACT axis, the ranges laid end to end.  pos_beg = 0 and pos_end = the compact length
+    // (so every ngroups bound below holds as it stands); zpos_tab[compact position] = its zerobased_pos z, stored as ~z (negative) on the
+    // first position of a range without base_at_pos_beg (k_range_map).  NULL = one range, today's arithmetic: one uniform compare per group.
+    const int *zpos_tab;
+    const UvcScoreRangeDev *ranges; int n_ranges;   // the table itself (k_range_map, k_force_mask): begin, end and the exclusive prefix of the lengths
 };
+// zerobased_pos of group g, and whether its BASE sub-position is left out (main.cpp:643)
+DEV int group_zpos(const ScoreCtx &C, long long g, bool &no_base) {
+    if (C.zpos_tab == nullptr) { const int z = C.pos_beg + (int)(g >> 1); no_base = (z == C.pos_beg && !C.base_at_beg); return z; }
+    const int v = C.zpos_tab[g >> 1];
+    no_base = (v < 0);
+    return no_base ? ~v : v;
+}
 // the gate of group g is the all-out one: -A, or a force-output site at its zerobased_pos (both symbol types of the position: their records
 // read each other's gate through vAC0 / vAC1 and germ_emit).  Without sites the mask pointer is NULL for every lane: one uniform compare.
 DEV bool group_all_out(const ScoreCtx &C, long long g) {
@@ -544,8 +559,9 @@ DEV int masked_bdepths(const RegionDev &R, int st, int64_t x, unsigned mask, int
     return tot;
 }
 DEV int gate_count(const RegionDev &R, const UvcParams &P, const ScoreCtx &C, long long g) {
-    const int zpos = C.pos_beg + (int)(g >> 1), st = (int)(g & 1);
-    if (zpos == C.pos_beg && st == UVC_BASE_SYMBOL && !C.base_at_beg) return 0;   // main.cpp:643
+    bool no_base;
+    const int zpos = group_zpos(C, g, no_base), st = (int)(g & 1);
+    if (no_base && st == UVC_BASE_SYMBOL) return 0;   // main.cpp:643
     const int refpos = (st == UVC_BASE_SYMBOL ? zpos - 1 : zpos);
     const int64_t x = refpos - R.beg;
     const int refsymbol = group_refsymbol(R, zpos, st), nsym = st_count(st);
@@ -628,7 +644,8 @@ __global__ void __launch_bounds__(128) k_enum(RegionDev R, UvcParams P, ScoreCtx
     const long long g = C.active[gi];
     const long long rec0 = PK_COUNT(C.offsets[g]), nrec = PK_COUNT(C.offsets[g + 1]) - rec0;
     if (nrec <= 0 || rec0 + nrec > C.capacity || rec0 + nrec > S.cap) { GR_(nrec, gi) = 0; return; }   // does not fit: the host sees the count and comes back
-    const int zpos = C.pos_beg + (int)(g >> 1), st = (int)(g & 1);
+    bool no_base_;
+    const int zpos = group_zpos(C, g, no_base_), st = (int)(g & 1);
     const int refpos = (st == UVC_BASE_SYMBOL ? zpos - 1 : zpos);
     const int64_t x = refpos - R.beg;
     const int refidx = zpos - R.beg, refsize = (int)R.npos - 1;
@@ -1630,19 +1647,45 @@ __global__ void __launch_bounds__(256) k_keep_copy(ScoreCtx C, Stage S, long lon
 // ---- UvcScoreRequest::force_sites: one bit per zerobased_pos of the scored range, read by group_all_out ----
 // One lane per site (O(sites), a few hundred in a typical list); a site outside [pos_beg, pos_end) sets nothing.  Sorted sites put the lanes
 // of a wave on neighbouring words; repeats and neighbours meet in the same word, hence the atomic OR.
-__global__ void __launch_bounds__(256) k_force_mask(const int32_t *sites, long long n, int pos_beg, int pos_end, unsigned *mask) {
+// With ranges the bit index is the compact position: the range that holds the site (the last one whose begin is <= the site), if any does.
+__global__ void __launch_bounds__(256) k_force_mask(const int32_t *sites, long long n, int pos_beg, int pos_end, const UvcScoreRangeDev *ranges, int n_ranges, unsigned *mask) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int z = sites[i];
-    if (z < pos_beg || z >= pos_end) return;
-    const unsigned b = (unsigned)(z - pos_beg);
+    unsigned b;
+    if (ranges == nullptr) {
+        if (z < pos_beg || z >= pos_end) return;
+        b = (unsigned)(z - pos_beg);
+    } else {
+        int lo = 0, hi = n_ranges;   // first range whose begin is > z
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (ranges[mid].beg <= z) lo = mid + 1; else hi = mid; }
+        if (lo == 0) return;
+        const UvcScoreRangeDev q = ranges[lo - 1];
+        if (z >= q.end) return;
+        b = (unsigned)(q.first + (z - q.beg));
+    }
     atomicOr(&mask[b >> 5], 1u << (b & 31u));
+}
+// ---- uvcgpu_region_score_ranges: compact position -> zerobased_pos ----
+// One lane per compact position, a binary search in the ranges' exclusive prefix (the last range whose first compact position is <= the
+// lane's; empty ranges share a prefix value with their successor and are passed over by taking the LAST such range).  The table is a few
+// KB and stays in L2; neighbouring lanes walk the same path, so the loads of a wave coalesce to one or two lines per step; the store is
+// one coalesced dword per lane.  No cross-workgroup state (the alternative, a scatter of range heads and a scan, needs the chained scan's
+// tickets and look-back for the same result).
+__global__ void __launch_bounds__(256) k_range_map(const UvcScoreRangeDev *ranges, int n_ranges, int n_compact, int *zpos_tab) {
+    const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= n_compact) return;
+    int lo = 0, hi = n_ranges;   // first range whose first compact position is > c
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ranges[mid].first <= c) lo = mid + 1; else hi = mid; }
+    const UvcScoreRangeDev q = ranges[lo - 1];   // lo >= 1: ranges[0].first == 0 <= c
+    const int z = q.beg + (c - q.first);
+    zpos_tab[c] = ((c == q.first && !(q.flags & 1)) ? ~z : z);
 }
 static size_t force_mask_words(int64_t npos_scored) { return (size_t)((npos_scored > 0 ? npos_scored : 0) + 31) / 32; }
 
 // scratch layout of one score call.  The head [record counts (2 x int64)] [counters] [tile states of the two scans] is zeroed in front of every call.
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-struct ScratchLayout { size_t zero_bytes, cnt, status1, status2, offsets, active, grp, tot, rh, al, al64, mid, d4, keptoff, force_mask, total; };
+struct ScratchLayout { size_t zero_bytes, cnt, status1, status2, offsets, active, grp, tot, rh, al, al64, mid, d4, keptoff, force_mask, zpos_tab, total; };
 static ScratchLayout scratch_layout(int64_t npos_scored, int64_t cap) {
     const size_t ngroups = (size_t)(2 * npos_scored), c = (size_t)(cap > 0 ? cap : 1);
     const size_t ntiles1 = (ngroups + GATE_TILE - 1) / GATE_TILE + 1, ntiles2 = (std::min(ngroups, c) + GS_TILE - 1) / GS_TILE + 1;
@@ -1662,6 +1705,7 @@ static ScratchLayout scratch_layout(int64_t npos_scored, int64_t cap) {
     L.d4 = o; o = align16(o + (size_t)NDP4 * 2 * c * 8);
     L.keptoff = o; o = align16(o + c * 4);
     L.force_mask = o; o = align16(o + force_mask_words(npos_scored) * 4);   // zeroed and filled only by a call with force-output sites
+    L.zpos_tab = o; o = align16(o + (size_t)(npos_scored > 0 ? npos_scored : 0) * 4);   // written only by a ranges call (k_range_map)
     L.total = o;
     return L;
 }
@@ -1673,9 +1717,13 @@ extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capa
 extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
                                 const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity,
                                 char *scratch /* uvc_score_scratch_bytes */, int32_t *d_fields_kept /* kept_only: a second [fields][capacity] array */,
-                                const int32_t *d_force_sites /* device copy of UvcScoreRequest::force_sites, or NULL */, hipStream_t s) {
+                                const int32_t *d_force_sites /* device copy of UvcScoreRequest::force_sites, or NULL */,
+                                const void *d_ranges /* uvcgpu_region_score_ranges: device table of UvcScoreRangeDev, or NULL */, int64_t n_ranges, int64_t n_compact, hipStream_t s) {
     ScoreCtx C;
-    C.pos_beg = req->pos_beg; C.pos_end = req->pos_end; C.all_out = (req->all_out || P->should_output_all) ? 1 : 0; C.is_amplicon = req->is_amplicon; C.base_at_beg = req->base_at_pos_beg ? 1 : 0;
+    C.pos_beg = req->pos_beg; C.pos_end = req->pos_end;
+    if (d_ranges) { C.pos_beg = 0; C.pos_end = (int)n_compact; }   // the compact axis; scratch is sized by it (npos_scored below)
+    C.zpos_tab = nullptr; C.ranges = (const UvcScoreRangeDev *)d_ranges; C.n_ranges = (int)n_ranges;
+    C.all_out = (req->all_out || P->should_output_all) ? 1 : 0; C.is_amplicon = req->is_amplicon; C.base_at_beg = req->base_at_pos_beg ? 1 : 0;
     C.alleles = d_alleles; C.allele_rows = d_allele_rows; C.n_alleles = n_alleles; C.gap_rows = d_gap_rows; C.gap_seq = d_gap_seq; C.tkeys = d_tkeys; C.n_tkeys = (d_tkeys ? req->n_tumor_keys : 0); C.fields = d_fields; C.capacity = capacity;
     const long long npos_scored = C.pos_end - C.pos_beg, ngroups = 2LL * npos_scored;
     if (ngroups <= 0) return 0;
@@ -1686,11 +1734,16 @@ extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const Uv
     C.offsets = (long long *)(scratch + L.offsets); C.active = (int *)(scratch + L.active);
     S.grp = (int32_t *)(scratch + L.grp); S.tot = (long long *)(scratch + L.tot); S.rh = (int32_t *)(scratch + L.rh); S.al = (int32_t *)(scratch + L.al); S.al64 = (long long *)(scratch + L.al64);
     S.mid = (double *)(scratch + L.mid); S.d4 = (double *)(scratch + L.d4); S.keptoff = (int32_t *)(scratch + L.keptoff); S.cap = capacity;
+    if (d_ranges) {
+        int *tab = (int *)(scratch + L.zpos_tab);
+        hipLaunchKernelGGL(k_range_map, dim3((unsigned)((npos_scored + 255) / 256)), dim3(256), 0, s, C.ranges, C.n_ranges, (int)npos_scored, tab);
+        C.zpos_tab = tab;
+    }
     C.force_mask = nullptr;
     if (d_force_sites && req->n_force_sites > 0 && !C.all_out) {   // (under -A every group is selected already)
         unsigned *mask = (unsigned *)(scratch + L.force_mask);
         if (hipMemsetAsync(mask, 0, force_mask_words(npos_scored) * 4, s) != hipSuccess) return UVCGPU_EDEVICE;
-        hipLaunchKernelGGL(k_force_mask, dim3((unsigned)((req->n_force_sites + 255) / 256)), dim3(256), 0, s, d_force_sites, (long long)req->n_force_sites, C.pos_beg, C.pos_end, mask);
+        hipLaunchKernelGGL(k_force_mask, dim3((unsigned)((req->n_force_sites + 255) / 256)), dim3(256), 0, s, d_force_sites, (long long)req->n_force_sites, C.pos_beg, C.pos_end, C.ranges, C.n_ranges, mask);
         C.force_mask = mask;
     }
     const unsigned ntiles = (unsigned)((ngroups + GATE_TILE - 1) / GATE_TILE);
@@ -1734,11 +1787,7 @@ extern "C" void uvc_launch_check_presence(const RegionDev *R, unsigned long long
 // ---- position-level numbers of the VCF writer: the MGVCF block lines (main.cpp:655-735) and ADDITIONAL_INDEL_CANDIDATE (main.cpp:759-799) ----
 // Per position 10 ints: for LINK then BASE (SYMBOL_TYPES_IN_VCF_ORDER) the total fragment depth, the de-duplicated depth, the BQ-filtered
 // de-duplicated depth and the homozygous-reference quality; then segprep_a_dp and segprep_a_near_long_clip_dp.
-__global__ void __launch_bounds__(256) k_block_stats(RegionDev R, UvcParams P, long long x0, long long n, int *out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t x = x0 + i;
-    int *o = out + i * 10;
+DEV void block_stats_at(const RegionDev &R, const UvcParams &P, int64_t x, int *o) {
     if (x < 0 || x >= R.npos) { for (int q = 0; q < 10; q++) o[q] = 0; return; }
     for (int t = 0; t < 2; t++) {
         const int st = (t == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
@@ -1757,6 +1806,24 @@ __global__ void __launch_bounds__(256) k_block_stats(RegionDev R, UvcParams P, l
         o[t * 4 + 3] = P.germ_phred_hetero_snp + (int)round(dmax(rb, rp) - (double)(int)round(dmax(nb, np)));
     }
     o[8] = P32(R, UVC_P_a_dp, x); o[9] = P32(R, UVC_P_a_near_long_clip_dp, x);
+}
+__global__ void __launch_bounds__(256) k_block_stats(RegionDev R, UvcParams P, long long x0, long long n, int *out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    block_stats_at(R, P, x0 + i, out + i * 10);
+}
+// The same over several disjoint windows in one launch (the record writer of a ranges call: the union of the ranges' windows): row i of
+// `out` is the i-th position of the windows laid end to end; win[2 * k] = plane index of window k's first position, win[2 * k + 1] = the
+// row of that position (exclusive prefix of the window lengths).  One lane per row, the window by a search in the prefix, as k_range_map.
+__global__ void __launch_bounds__(256) k_block_stats_windows(RegionDev R, UvcParams P, const long long *win, int n_win, long long n, int *out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int lo = 0, hi = n_win;   // first window whose first row is > i
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (win[2 * mid + 1] <= i) lo = mid + 1; else hi = mid; }
+    block_stats_at(R, P, win[2 * (lo - 1)] + (i - win[2 * (lo - 1) + 1]), out + i * 10);
+}
+extern "C" void uvc_launch_block_stats_windows(const RegionDev *R, const UvcParams *P, const long long *d_win, int n_win, int64_t n, int32_t *d_out, hipStream_t s) {
+    if (n > 0 && n_win > 0) hipLaunchKernelGGL(k_block_stats_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *R, *P, d_win, n_win, (long long)n, d_out);
 }
 extern "C" void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_block_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *R, *P, (long long)x0, (long long)n, d_out);

@@ -21,6 +21,7 @@ extern "C" const UvcParams *uvcgpu_region_params(const uvcgpu_region_t *r);
 extern "C" const std::vector<UvcHapLinkHost> *uvcgpu_region_hap_(uvcgpu_region_t *r);   // the three link vectors (uvc_host.cpp), NULL on error
 extern "C" int uvcgpu_fail_(int code, const char *msg);
 extern "C" int uvcgpu_region_block_stats_(uvcgpu_region_t *r, int32_t refpos_beg, int32_t refpos_end, int32_t *dst);   // 10 ints per position, k_block_stats
+extern "C" int uvcgpu_region_block_stats_windows_(uvcgpu_region_t *r, const int32_t *win, int64_t n_win, int32_t *dst);   // the same for disjoint windows [win[2k], win[2k + 1]), one round trip
 
 namespace {
 const int NSYM = 14;
@@ -480,12 +481,17 @@ extern "C" int uvcgpu_vcf_header(const UvcParams *P, const char *sample, const c
     return uvcgpu_vcf_header_ex(P, sample, tumor_sample, names, lens, n_contigs, nullptr, nullptr, nullptr, dst, cap, len);
 }
 
-extern "C" int uvcgpu_region_vcf_records(uvcgpu_region_t *r, const char *tname, const UvcScoreOut *scored, const UvcScoreRequest *req,
-                                         char *dst, int64_t cap, int64_t *len) {
+// `ranges` = NULL: the range of `req` (uvcgpu_region_vcf_records).  Else the ranges of a uvcgpu_region_score_ranges call: the record and GERMLINE
+// lines come from the records alone, the position-level lines are written range by range, and since the ranges are sorted and disjoint the
+// merge by zerobased_pos at the end yields the single-range texts one after another.
+static int vcf_records_impl(uvcgpu_region_t *r, const char *tname, const UvcScoreOut *scored, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges,
+                            char *dst, int64_t cap, int64_t *len) {
     if (!r || !tname || !len || !scored || (scored->n_records > 0 && !scored->fields) || scored->n_records > scored->capacity) return uvcgpu_fail_(UVCGPU_EINVAL, "bad argument");
-    int32_t pos_beg = (req ? req->pos_beg : -1), pos_end = (req ? req->pos_end : -1);
-    const bool base_at_beg = (req && req->base_at_pos_beg && pos_beg >= 0);
-    const int32_t region_beg = (req ? req->region_beg : 0);
+    if (ranges) {
+        if (n_ranges < 1) return uvcgpu_fail_(UVCGPU_EINVAL, "vcf_records_ranges: n_ranges must be at least 1");
+        for (int64_t k = 0; k < n_ranges; k++) if (ranges[k].pos_beg < 0 || ranges[k].pos_end < ranges[k].pos_beg || (k > 0 && ranges[k].pos_beg < ranges[k - 1].pos_end))
+            return uvcgpu_fail_(UVCGPU_EINVAL, ("vcf_records_ranges: range " + std::to_string(k) + " is malformed or not behind its predecessor (ranges must be sorted and disjoint)").c_str());
+    }
     const UvcTumorKey *tkeys = (req ? req->tumor_keys : nullptr); const int64_t n_tkeys = (req ? req->n_tumor_keys : 0);
     const char *const *tcols = (req && tkeys ? req->tumor_sample_columns : nullptr);
     const char *const *tref_alt = (req && tkeys ? req->tumor_ref_alt : nullptr);
@@ -791,16 +797,43 @@ extern "C" int uvcgpu_region_vcf_records(uvcgpu_region_t *r, const char *tname, 
     timer.lap("record + GERMLINE lines");
 // ---- the position-level lines, in front of the records of their zerobased_pos (main.cpp:607-799) ----
     {
-        if (pos_beg < 0) { pos_beg = beg + 1; pos_end = end; }   // the default range of uvcgpu_region_score
         const bool want_block = (P.outvar_flag & 0x8) != 0, want_cand = (P.outvar_flag & 0x10) != 0;
-        std::vector<std::pair<int32_t, std::string>> pos_lines;
-        if ((want_block || want_cand) && pos_end > pos_beg + (base_at_beg ? 0 : 1)) {
-            const int32_t state_end = end + 1;                                   // getUnifiedExcluEndPosition (main.cpp:569)
-            const int32_t s_beg = pos_beg - 1, s_end = std::min<int64_t>((int64_t)pos_end - 1 + 1001, state_end);
-            std::vector<int32_t> st((size_t)10 * (size_t)std::max(0, s_end - s_beg));
-            if (s_end > s_beg) { const int rc = uvcgpu_region_block_stats_(r, s_beg, s_end, st.data()); if (rc) return rc; }
+        const int32_t state_end = end + 1;                                   // getUnifiedExcluEndPosition (main.cpp:569)
+        // the ranges whose position-level lines are written, and the window of block statistics each reads: [pos_beg - 1, pos_end + 1000)
+        struct LineRange { int32_t pos_beg, pos_end, region_beg; bool base_at_beg; int32_t s_beg, s_end; size_t row; };
+        std::vector<LineRange> todo;
+        auto add_range = [&](int32_t pos_beg, int32_t pos_end, bool base_at_beg, int32_t region_beg) {
+            if (!((want_block || want_cand) && pos_end > pos_beg + (base_at_beg ? 0 : 1))) return;
+            const int32_t s_beg = pos_beg - 1, s_end = (int32_t)std::min<int64_t>((int64_t)pos_end - 1 + 1001, state_end);
+            todo.push_back(LineRange{ pos_beg, pos_end, region_beg, base_at_beg, s_beg, std::max(s_end, s_beg), 0 });
+        };
+        if (ranges) for (int64_t k = 0; k < n_ranges; k++) add_range(ranges[k].pos_beg, ranges[k].pos_end, ranges[k].base_at_pos_beg != 0, ranges[k].region_beg);
+        else {
+            int32_t pos_beg = (req ? req->pos_beg : -1), pos_end = (req ? req->pos_end : -1);
+            const bool base_at_beg = (req && req->base_at_pos_beg && pos_beg >= 0);
+            if (pos_beg < 0) { pos_beg = beg + 1; pos_end = end; }   // the default range of uvcgpu_region_score
+            add_range(pos_beg, pos_end, base_at_beg, req ? req->region_beg : 0);
+        }
+        // one device round trip for all of them: the union of the windows (sorted by begin already; neighbours that overlap or touch merge),
+        // every range then reads its rows inside the union window that holds it
+        std::vector<int32_t> st, win;
+        {
+            size_t rows = 0;
+            for (LineRange &q : todo) {
+                if (q.s_end <= q.s_beg) continue;
+                if (!win.empty() && q.s_beg <= win.back()) { q.row = rows - (size_t)(win.back() - q.s_beg); if (q.s_end > win.back()) { rows += (size_t)(q.s_end - win.back()); win.back() = q.s_end; } }
+                else { q.row = rows; win.push_back(q.s_beg); win.push_back(q.s_end); rows += (size_t)(q.s_end - q.s_beg); }
+            }
+            st.resize((size_t)10 * rows);
+            if (win.size() == 2) { const int rc = uvcgpu_region_block_stats_(r, win[0], win[1], st.data()); if (rc) return rc; }
+            else if (!win.empty()) { const int rc = uvcgpu_region_block_stats_windows_(r, win.data(), (int64_t)(win.size() / 2), st.data()); if (rc) return rc; }
             timer.lap("block statistics (kernel + D2H)");
-            auto S = [&](int32_t refpos, int q) { return st[(size_t)10 * (size_t)(refpos - s_beg) + (size_t)q]; };
+        }
+        std::vector<std::pair<int32_t, std::string>> pos_lines;
+        for (const LineRange &lr : todo) {
+            const int32_t pos_beg = lr.pos_beg, pos_end = lr.pos_end, region_beg = lr.region_beg, s_beg = lr.s_beg; const bool base_at_beg = lr.base_at_beg;
+            const int32_t *strow = st.data() + (size_t)10 * lr.row;
+            auto S = [&](int32_t refpos, int q) { return strow[(size_t)10 * (size_t)(refpos - s_beg) + (size_t)q]; };
             auto refchar = [&](int64_t off) { return (off >= 0 && off < (int64_t)ref.size()) ? ref[(size_t)off] : 'N'; };
             auto code_of = [](char c) { switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case 'I': case 'i': return 6; case '-': case '_': return 9; default: return 4; } };
             // normal sample with the tumor's FORMAT carried over: the tumor's own line of this position, if it has exactly one
@@ -900,4 +933,13 @@ extern "C" int uvcgpu_region_vcf_records(uvcgpu_region_t *r, const char *tname, 
     if (!dst || cap < (int64_t)out.size()) return uvcgpu_fail_(UVCGPU_ENOMEM, "destination too small");
     memcpy(dst, out.data(), out.size());
     return 0;
+}
+extern "C" int uvcgpu_region_vcf_records(uvcgpu_region_t *r, const char *tname, const UvcScoreOut *scored, const UvcScoreRequest *req,
+                                         char *dst, int64_t cap, int64_t *len) {
+    return vcf_records_impl(r, tname, scored, req, nullptr, 0, dst, cap, len);
+}
+extern "C" int uvcgpu_region_vcf_records_ranges(uvcgpu_region_t *r, const char *tname, const UvcScoreOut *scored, const UvcScoreRequest *req,
+                                                const UvcScoreRange *ranges, int64_t n_ranges, char *dst, int64_t cap, int64_t *len) {
+    if (!ranges) return uvcgpu_fail_(UVCGPU_EINVAL, "vcf_records_ranges: ranges is NULL");
+    return vcf_records_impl(r, tname, scored, req, ranges, n_ranges, dst, cap, len);
 }

@@ -192,6 +192,25 @@ def plan_regions(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per_thread
     return [dict(tid=c.tid, beg=c.beg, end=c.end, flag=c.flag, batch=c.batch, n_reads=c.n_reads) for c in out[:n.value]]
 
 
+class UvcBedPiece(C.Structure):
+    _fields_ = [("line", C.c_int64), ("batch", C.c_int64), ("beg", C.c_int64), ("end", C.c_int64)]
+
+
+def plan_bed_batches(tid, beg, end, merge_distance, max_span=1000000):
+    """uvcio_plan_bed_batches: BED lines (tid, beg, end) in file order -> one dict (line, batch, tid, beg, end) per line, or per piece of a
+    line longer than max_span; consecutive pieces with one `batch` value become one device region (uvc1-mi355x --merge-regions)."""
+    d = dll()
+    d.uvcio_plan_bed_batches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    a = [np.ascontiguousarray(tid, dtype=np.int32), np.ascontiguousarray(beg, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)]
+    n = C.c_int64(0)
+    rc = d.uvcio_plan_bed_batches(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, len(a[0]), int(merge_distance), int(max_span), None, 0, C.byref(n))
+    if rc not in (0, -6):
+        _check(rc)
+    out = (UvcBedPiece * max(1, n.value))()
+    _check(d.uvcio_plan_bed_batches(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, len(a[0]), int(merge_distance), int(max_span), out, n.value, C.byref(n)))
+    return [dict(line=int(p.line), batch=int(p.batch), tid=int(a[0][p.line]), beg=int(p.beg), end=int(p.end)) for p in out[:n.value]]
+
+
 def plan_regions_stream(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per_thread_mb=1536, piece=1000):
     """The same cuts through the streaming form (uvcio_planner_*): the columns are fed `piece` alignments at a time, cuts are taken as they appear."""
     d = dll()

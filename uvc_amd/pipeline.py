@@ -24,7 +24,7 @@ FILTERS = ["Q10", "Q20", "Q30", "Q40", "Q50", "Q60", "PASS"]
 
 
 def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None, molecule_tag=0, disable_duplex=0, correct_bq=True, all_out=False, keep_handle=False, reuse=None, vcf=False,
-                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0, force_sites=None):
+                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0, force_sites=None, pieces=None, single_ranges=False):
     """Scores [beg, end) of `chrom`.  Returns None when no read passes the filters (process_batch returns -1, main.cpp:520-523), else a
     dict: records (field -> int32 array), alleles (InDel allele rows), score range, region handle (if keep_handle).
     Tiles of one stretch: the reference scores zerobased_pos rpos_beg .. rpos_end inclusive and skips the BASE sub-position of the first
@@ -39,6 +39,10 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     `force_sites`: force-output sites (uvc1-mi355x --force-sites) -- a `uvc_amd.io.Sites`, or zerobased_pos values on `chrom` (= the VCF POS
     of the records they select): at those positions every allele record as `all_out` writes it, the default gate elsewhere.  The sites this
     tile owns (its score range) go into UvcScoreRequest::force_sites.
+    `pieces`: a batch of BED lines merged into this one region (uvc1-mi355x --merge-regions; `beg` / `end` = the batch's span) as dicts beg,
+    end, continues, has_next, region_beg: every piece becomes the score range its own tile would have asked for, and all of them are scored
+    in one `Region.score_ranges` call with kept_only (`single_ranges`: one `Region.score` call per piece instead -- the same records by
+    contract).  Returns records, ranges and, with `vcf`, the text; not with tumor_vcf or force_sites.
     `reuse`: a dict the caller keeps between calls; the region handle lives in it and is reset for every new region instead of being
     created and destroyed (its device buffers survive while the regions do not grow)."""
     import os, time
@@ -88,6 +92,32 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
         R.correct_bq()
     R.accumulate()
     is_amplicon = (g["n_amplicon"] * 2 > g["n_kept"]) if assay_type == 0 else (assay_type == 2)   # !is_by_capture / inferred_assay_type, main.cpp:507-511
+    if pieces is not None:
+        if tumor_vcf is not None or force_sites is not None:
+            raise ValueError("merged BED lines go neither with tumor_vcf nor with force_sites")
+        ranges = []
+        for q in pieces:                                                                 # what call_region(q) computes below, with this batch's reads
+            first = max(q["beg"], bam_beg)
+            q_excl = min(q["end"], bam_end + 1) if q["has_next"] else min(min(q["end"], bam_end) + 1, ext_end)
+            if q_excl > first:
+                ranges.append((first, q_excl, int(bool(q["continues"] and first == q["beg"] and q["beg"] > ext_beg)), q["region_beg"]))
+        if not ranges:
+            return None
+        if single_ranges:
+            parts = [R.score(all_out=all_out, is_amplicon=bool(is_amplicon), pos_beg=a, pos_end=b, base_at_pos_beg=bool(c), region_beg=d, kept_only=True) for a, b, c, d in ranges]
+            rec = parts
+            text = "".join(R.vcf_records(chrom, r, pos_beg=a, pos_end=b, base_at_pos_beg=bool(c), region_beg=d) for r, (a, b, c, d) in zip(parts, ranges)) if vcf else None
+        else:
+            rec = R.score_ranges(ranges, all_out=all_out, is_amplicon=bool(is_amplicon), kept_only=True)
+            text = R.vcf_records_ranges(chrom, rec, ranges) if vcf else None
+        out = dict(records=rec, ranges=ranges, ext=(ext_beg, ext_end), n_reads=int(g["n_kept"]), n_fams=int(g["n_fams"]), chrom=chrom)
+        if vcf:
+            out["vcf"] = text
+        if keep_handle:
+            out["region"] = R
+        elif reuse is None:
+            R.close()
+        return out
     last_excl = min(end, bam_end + 1) if has_next else min(rpos_end + 1, ext_end)      # zerobased_pos `end` belongs to the tile behind, if there is one
     skw = dict(pos_beg=rpos_beg, pos_end=last_excl, base_at_pos_beg=bool(continues and rpos_beg == beg and beg > ext_beg), region_beg=(beg if region_beg is None else region_beg))
     score_range = (skw["pos_beg"], skw["pos_end"])
@@ -174,6 +204,30 @@ def call_contig(lib, bam, fasta, chrom, beg=0, end=None, tile=1_000_000, workers
         for res in ex.map(one, starts):
             if res is not None:
                 yield res
+
+
+def call_bed_batches(lib, bam, fasta, pieces, single_ranges=False, **kw):
+    """The record text of `uvc1-mi355x -R panel.bed --merge-regions N` (no header): `pieces` = uvc_amd.io.plan_bed_batches of the BED lines;
+    the consecutive pieces of one batch are called as one region (call_region with `pieces`).  Pieces that abut on a contig are linked into
+    runs as the command line links its tiles: every zerobased_pos has one owner."""
+    b = bam if not isinstance(bam, str) else uio.Bam(bam)
+    f = fasta if not isinstance(fasta, str) else uio.Fasta(fasta)
+    ps = [dict(p, continues=False, has_next=False, region_beg=p["beg"]) for p in pieces]
+    for q, p in zip(ps[1:], ps):
+        if q["tid"] == p["tid"] and q["beg"] == p["end"]:
+            q["continues"], p["has_next"], q["region_beg"] = True, True, p["region_beg"]
+    text, reuse, at = [], {}, 0
+    while at < len(ps):
+        n = 1
+        while at + n < len(ps) and ps[at + n]["batch"] == ps[at]["batch"]:
+            n += 1
+        res = call_region(lib, b, f, b.refs[ps[at]["tid"]][0], ps[at]["beg"], ps[at + n - 1]["end"], reuse=reuse, vcf=True, pieces=ps[at:at + n], single_ranges=single_ranges, **kw)
+        if res is not None:
+            text.append(res["vcf"])
+        at += n
+    if reuse.get("region") is not None:
+        reuse["region"].close()
+    return "".join(text)
 
 
 def write_tsv(res, fh, kept_only=True, header=True):

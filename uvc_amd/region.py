@@ -397,6 +397,60 @@ class Region:
             # copy=False returns views into the handle's reusable buffer (valid until the next score() call)
             return {name: (buf[i, :out.n_records].copy() if copy else buf[i, :out.n_records]) for i, name in enumerate(_ffi.SCORE_FIELDS)}
 
+    @staticmethod
+    def make_ranges(ranges):
+        """UvcScoreRange array from (pos_beg, pos_end[, base_at_pos_beg[, region_beg]]) tuples."""
+        rows = [tuple(int(v) for v in q) + (0,) * (4 - len(q)) for q in ranges]
+        return (_ffi.UvcScoreRange * max(len(rows), 1))(*[_ffi.UvcScoreRange(*q) for q in rows]), len(rows)
+
+    def _ranges_fn(self, name, restype, argtypes):
+        """The ranges entry points exist in the HIP library only: bound on first use."""
+        fn = getattr(self.lib.dll, self.lib.prefix + name, None)
+        if fn is None:
+            raise UvcError(_ffi.ENUMS["UVCGPU_EUNSUPPORTED"], "%s has no %s%s" % (self.lib.path, self.lib.prefix, name))
+        fn.restype, fn.argtypes = restype, argtypes
+        return fn
+
+    def score_ranges(self, ranges, all_out=False, is_amplicon=False, indel_alleles=None, capacity=None, copy=True, tumor_keys=None, release_state=False, kept_only=False, force_sites=None):
+        """uvcgpu_region_score_ranges: the records of score() called once per range -- (pos_beg, pos_end[, base_at_pos_beg[, region_beg]]),
+        sorted and disjoint -- on this accumulated handle, concatenated in range order, from one gate, one set of launches and one D2H."""
+        fn = self._ranges_fn("region_score_ranges", C.c_int, [C.c_void_p, C.POINTER(_ffi.UvcScoreRequest), C.c_void_p, C.c_int64, C.POINTER(_ffi.UvcScoreOut)])
+        req, _keep = self.make_request(all_out, -1, -1, is_amplicon, indel_alleles, tumor_keys, release_state, kept_only=kept_only, force_sites=force_sites)
+        arr, n = self.make_ranges(ranges)
+        if capacity is None:
+            npos = sum(max(0, int(q[1]) - int(q[0])) for q in ranges)
+            capacity = 14 * (npos + 1) if all_out else max(4096, 4 * (npos + 1)) + 16 * int(req.n_force_sites)
+        capacity = max(capacity, getattr(self, "_score_cap", 0))
+        while True:
+            buf = getattr(self, "_score_buf", None)
+            if buf is None or buf.shape[1] != capacity:
+                self._free_score_buf()
+                buf = self._score_buf = self._alloc_score_buf(capacity)
+            out = _ffi.UvcScoreOut(capacity, 0, buf.ctypes.data)
+            rc = fn(self.h, C.byref(req), arr, n, C.byref(out))
+            if rc == -6 and out.n_records > capacity:
+                capacity = self._score_cap = int(out.n_records) + int(out.n_records) // 8
+                continue
+            self._check(rc)
+            return {name: (buf[i, :out.n_records].copy() if copy else buf[i, :out.n_records]) for i, name in enumerate(_ffi.SCORE_FIELDS)}
+
+    def vcf_records_ranges(self, contig_name, records, ranges, tumor_keys=None, tumor_sample_columns=None, tumor_ref_alt=None):
+        """uvcgpu_region_vcf_records_ranges: the text of the records score_ranges(ranges) returned = the single-range texts one after another."""
+        fn = self._ranges_fn("region_vcf_records_ranges", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(_ffi.UvcScoreOut), C.POINTER(_ffi.UvcScoreRequest), C.c_void_p, C.c_int64,
+                                                                    C.c_void_p, C.c_int64, C.POINTER(C.c_int64)])
+        n = len(records["refpos"])
+        buf = np.ascontiguousarray(np.stack([np.asarray(records[name], dtype=np.int32) for name in _ffi.SCORE_FIELDS])) if n else np.zeros((_ffi.NUM_SCORE_FIELDS, 1), dtype=np.int32)
+        so = _ffi.UvcScoreOut(max(n, 1), n, buf.ctypes.data)
+        req, _keep = self.make_request(tumor_keys=tumor_keys, tumor_sample_columns=tumor_sample_columns, tumor_ref_alt=tumor_ref_alt)
+        arr, nr = self.make_ranges(ranges)
+        ln = C.c_int64(0)
+        rc = fn(self.h, contig_name.encode(), C.byref(so), C.byref(req), arr, nr, None, 0, C.byref(ln))
+        if rc not in (0, -6):
+            self._check(rc)
+        dst = C.create_string_buffer(max(1, ln.value))
+        self._check(fn(self.h, contig_name.encode(), C.byref(so), C.byref(req), arr, nr, dst, ln.value, C.byref(ln)))
+        return dst.raw[:ln.value].decode()
+
     def fetch_columns(self, refpos):
         """Every plane value of the given positions (uvcgpu_region_fetch_columns): int64 [len(refpos), n_columns]; `column_base(group)`
         gives the first column of a plane group, the planes of a group follow in the order of `fetch(group)`."""
