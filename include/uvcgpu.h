@@ -51,7 +51,8 @@ enum {
                                   (2^29 positions, 2^31 read bases, 2^27 InDel ops per region; bias_thres_interfering_indel above 10000) */
     UVCGPU_EDEVICE = -4,       /* HIP runtime failure / no gfx950 device */
     UVCGPU_ESTATE = -5,        /* call order violated (e.g. score before accumulate) */
-    UVCGPU_ENOMEM = -6
+    UVCGPU_ENOMEM = -6,
+    UVCGPU_STREAM_END = 1      /* uvcgpu_score_stream_next: every chunk has been returned (not an error) */
 };
 
 /* ---------------------------------------------------------------- parameters (C15) --------- */
@@ -425,6 +426,45 @@ typedef struct UvcScoreRange {
 /* Upper bound of the records of a ranges call (as uvcgpu_region_score_size, over the ranges' total length); -1 for a NULL argument. */
 int64_t uvcgpu_region_score_ranges_size(const uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges);
 int uvcgpu_region_score_ranges(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out);
+/* ---- a score in bounded memory: the records of one request, chunk by chunk ----
+ * uvcgpu_region_score sizes its device rows, its records array and the caller's buffer by the records of the whole request (14 per
+ * position under all_out).  A stream runs the gate once over the whole request, cuts the record list into chunks of at most
+ * `chunk_records` records on the device, and runs the per-record kernels chunk by chunk over two row sets sized by chunk_records; chunk
+ * k + 1 is computed and copied while the caller works on chunk k.
+ *     uvcgpu_region_score_stream_begin(r, &req, ranges, n_ranges, chunk_records, &s);
+ *     while ((rc = uvcgpu_score_stream_next(s, &chunk, covered, &n_covered)) == 0)
+ *         uvcgpu_region_vcf_records_ranges(r, contig, &chunk, &req_text, covered, n_covered, dst, cap, &len);   // or anything else with the chunk
+ *     uvcgpu_score_stream_end(s);                                             // rc == UVCGPU_STREAM_END: all chunks were returned
+ *   Request: exactly that of uvcgpu_region_score (ranges = NULL, n_ranges = 0) or of uvcgpu_region_score_ranges; all_out, kept_only, the
+ *     caller's InDel alleles, tumor keys and force_sites mean what they mean there.  The request's arrays are copied by begin.
+ *   Chunks: a chunk is a run of whole zerobased_pos values (both symbol types of a position stay together); chunks come in order, are
+ *     disjoint and together cover the request.  The records of a chunk are the records of uvcgpu_region_score_ranges on the ranges reported
+ *     in `covered` (at most max(n_ranges, 1) entries: the caller's array must hold that many): the request's ranges cut to the chunk, with
+ *     base_at_pos_beg = 1 where a piece continues the previous chunk inside a range, region_beg carried over.  Every field is the one call's;
+ *     germ_ref / germ_alt1 / germ_alt2 are relative to the chunk, as they are to a kept_only result.  The texts of the chunks (covered and
+ *     chunk handed to uvcgpu_region_vcf_records_ranges, with a request whose pos_beg is -1) concatenate to the one call's text.
+ *   Size: every chunk has at most chunk_records records -- all records of its groups, with kept_only counted before the kept groups are
+ *     picked.  There is no minimum.  When one position alone has more, begin returns UVCGPU_ENOMEM, the message names the position and
+ *     the count, and no stream is opened.
+ *   `chunk` is a view: fields points into the stream's own page-locked buffer ([UVC_NUM_SCORE_FIELDS][capacity = chunk_records]) and stays
+ *     valid until the following next / end on the stream.  next returns UVCGPU_STREAM_END behind the last chunk.
+ *   release_state: the planes are released behind the last chunk's kernels -- as soon as that chunk is queued, which is during the next call
+ *     that returns the chunk before it (or begin, with one or two chunks); a stream that is ended earlier keeps them.
+ *   While a stream is open, score, score_ranges, accumulate, reset, set_reads and a second begin on the handle return UVCGPU_ESTATE;
+ *     end is legal at any point, also mid-way; afterwards the handle scores as before.  uvcgpu_region_destroy ends an open stream.
+ *   Memory: uvcgpu_score_stream_bytes_per_record() = device + page-locked host bytes that one unit of chunk_records costs, both row sets
+ *     and both host buffers counted.  uvcgpu_score_stream_footprint(r) = the bytes the handle holds for scoring right now (position-sized
+ *     scratch, staged request arrays, row sets, records arrays, page-locked buffers).  With a stream open
+ *         footprint <= chunk_records * bytes_per_record + 96 * (positions of the region) + staged request arrays * 3 / 2 + 256 KiB.
+ *     begin frees the record-sized buffers of earlier one-call scores; the row sets and host buffers are kept across streams with the same
+ *     chunk_records -- nothing is allocated per chunk. */
+typedef struct uvcgpu_score_stream uvcgpu_score_stream_t;
+int uvcgpu_region_score_stream_begin(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges,
+                                     int64_t chunk_records, uvcgpu_score_stream_t **out);
+int uvcgpu_score_stream_next(uvcgpu_score_stream_t *s, UvcScoreOut *chunk, UvcScoreRange *covered, int64_t *n_covered);
+int uvcgpu_score_stream_end(uvcgpu_score_stream_t *s);
+int64_t uvcgpu_score_stream_bytes_per_record(void);
+int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r);
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);

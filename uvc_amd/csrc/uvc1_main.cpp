@@ -46,6 +46,7 @@ struct Opts {
     int64_t tile = 0;            // 0 = no fixed tiles: the regions are the reference's own cuts (uvcio_plan_regions = SamIter::iternext); --tile N overrides
     int64_t mem_per_thread = 1536;   // --mem-per-thread (MB), CmdLineArgs.hpp:33: enters the reference's region cuts
     int64_t merge = 0;           // --merge-regions N: BED lines at most N bp apart become ranges of one device region (0 = one region per line)
+    int64_t score_mem_mb = 0;    // --score-mem-mb N: score every tile as a stream of chunks whose row sets and record buffers fit N MiB per worker (0 = one call per tile)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -89,7 +90,8 @@ const OptRow OPTS[] = {
     { "--devices,--device", O_CLI, false, "", "comma-separated HIP device ids (default: all visible)" },
     { "--shard", O_CLI, false, "0/1", "i/n: this process takes the i-th of n runs of tiles" },
     { "--no-header", O_CLI, true, "", "no VCF header" },
-    { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr" },
+    { "--score-mem-mb", O_CLI, false, "0", "score every tile in chunks whose device rows and page-locked record buffers take at most this many MiB per worker (-t), chunk k + 1 computed and copied while chunk k is written; 0: one score call per tile, sized by all its records (14 per position under -A).  The output does not depend on it" },
+    { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
     { "--normal-bam", O_CLI, false, "", "T/N pair in one run (uvcTN.sh): the normal sample's BAM; inputBAM is the tumor's, -o the normal VCF" },
@@ -235,6 +237,7 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--outvar-flag") set_row("outvar_flag", name, val());
         else if (n0 == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
         else if (n0 == "--merge-regions") { const std::string v = val(); double x; if (!number(v, &x) || x < 0 || x != (double)(int64_t)x || x > 2e9) die("--merge-regions takes a distance in bp (0 = off), not '" + v + "'"); o.merge = (int64_t)x; }
+        else if (n0 == "--score-mem-mb") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1e9) die("--score-mem-mb takes a size in MiB (0 = off), not '" + v + "'"); o.score_mem_mb = (int64_t)x; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -311,6 +314,8 @@ struct Worker {
     std::vector<int32_t> fields; std::string ref;
     double t_fetch = 0, t_group = 0, t_region = 0, t_reads = 0, t_gpu = 0, t_text = 0;
     int64_t n_tiles = 0, score_cap = 0, text_cap = 0;   // what the last tiles needed: the next call asks for it at once
+    int64_t n_chunks = 0, n_streamed = 0;               // --score-mem-mb: chunks in all, tiles scored as streams
+    std::vector<UvcScoreRange> covered;
 };
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -402,6 +407,36 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (o.sites && uvcio_sites_fetch(o.sites, t.tid, first, last_excl, &rq.force_sites, &rq.n_force_sites)) die(uvcio_last_error());   // the sites this tile owns
     rq.kept_only = 1;   // only the record groups that are written travel to the host
     const int64_t n_ranges = (int64_t)ranges.size();
+    if (o.score_mem_mb > 0) {   // the same records and the same text, chunk by chunk: the stream's chunk is scored while the one before it is written
+        const int64_t chunk_records = std::max<int64_t>(1, (o.score_mem_mb << 20) / uvcgpu_score_stream_bytes_per_record());
+        uvcgpu_score_stream_t *ss = nullptr;
+        if (uvcgpu_region_score_stream_begin(w.reg, &rq, n_merged > 0 ? ranges.data() : nullptr, n_merged > 0 ? n_ranges : 0, chunk_records, &ss)) die(std::string(uvcgpu_last_error()) + " (raise --score-mem-mb)");
+        UvcScoreRequest rt = rq; rt.pos_beg = -1; rt.pos_end = -1; rt.base_at_pos_beg = 0; rt.region_beg = 0;   // the text of a chunk: the covered ranges carry them
+        w.covered.resize((size_t)std::max<int64_t>(n_ranges, 1));
+        UvcScoreOut chunk; int64_t n_cov = 0;
+        double t_wait = now();
+        while ((rc = uvcgpu_score_stream_next(ss, &chunk, w.covered.data(), &n_cov)) == 0) {
+            w.t_gpu += now() - t_wait; t0 = now();
+            const size_t at = lines.size();
+            int64_t len = 0, room = std::max<int64_t>(1 << 16, w.text_cap);
+            for (;;) {
+                lines.resize(at + (size_t)room);
+                rc = uvcgpu_region_vcf_records_ranges(w.reg, t.chrom.c_str(), &chunk, &rt, w.covered.data(), n_cov, &lines[at], room, &len);
+                if (rc == UVCGPU_ENOMEM && len > room) { room = len + len / 4; continue; }
+                if (rc) die(uvcgpu_last_error());
+                break;
+            }
+            lines.resize(at + (size_t)len);
+            w.text_cap = std::max<int64_t>(w.text_cap, len + len / 4);
+            w.n_chunks++;
+            w.t_text += now() - t0; t_wait = now();
+        }
+        if (rc != UVCGPU_STREAM_END) die(uvcgpu_last_error());
+        if (uvcgpu_score_stream_end(ss)) die(uvcgpu_last_error());
+        w.t_gpu += now() - t_wait;
+        w.n_streamed++;
+        return true;
+    }
     const int64_t upper = n_merged > 0 ? uvcgpu_region_score_ranges_size(w.reg, &rq, ranges.data(), n_ranges) : uvcgpu_region_score_size(w.reg, &rq);
     int64_t cap = std::max<int64_t>(std::max<int64_t>(4096, w.score_cap), upper / (rq.all_out ? 1 : 64) + 16 * rq.n_force_sites);
     UvcScoreOut so;
@@ -872,6 +907,10 @@ int run_pair(Opts &ot, Opts &on, const std::string &cmd) {
             fprintf(stderr, "  %s thread-seconds: fetch %.2f, digest+group %.2f, reference+region %.2f, set_reads %.2f, bq+accumulate+score %.2f, record text %.2f\n", s ? "normal" : "tumor", f, g, r, x2, k, x);
         }
         for (size_t wi = 0; wi < (size_t)nthreads; wi++) fprintf(stderr, "  worker %zu on device %d: %lld tumor tiles, %lld normal tiles\n", wi, ot.devices[wi % ot.devices.size()], (long long)workers[0][wi].n_tiles, (long long)workers[1][wi].n_tiles);
+        if (ot.score_mem_mb > 0) for (int s = 0; s < 2; s++) {
+            int64_t nc = 0, ns = 0; for (auto &w : workers[s]) { nc += w.n_chunks; ns += w.n_streamed; }
+            fprintf(stderr, "  --score-mem-mb %lld, %s: %lld chunks in %lld scored tiles = %.2f chunks per tile\n", (long long)ot.score_mem_mb, s ? "normal" : "tumor", (long long)nc, (long long)ns, ns ? (double)nc / (double)ns : 0.0);
+        }
         std::string m;
         for (auto &b : mem_base) { char buf[160]; snprintf(buf, sizeof(buf), "%sdevice %d %.2f GB", m.empty() ? "" : ", ", b.first, (b.second - mem_low[b.first]) / 1e9); m += buf; }
         fprintf(stderr, "  device memory at the peak (hipMemGetInfo, %d tiles in flight, a tumor and a normal region handle each): %s\n", nthreads, m.c_str());
@@ -1029,6 +1068,11 @@ int main(int argc, char **argv) {
         for (auto &w : workers) { f += w.t_fetch; g += w.t_group; r += w.t_region; s += w.t_reads; k += w.t_gpu; x += w.t_text; }
         fprintf(stderr, "  thread-seconds: fetch %.2f, digest+group %.2f, reference+region %.2f, set_reads %.2f, bq+accumulate+score %.2f, record text %.2f\n", f, g, r, s, k, x);
         for (size_t wi = 0; wi < workers.size(); wi++) fprintf(stderr, "  worker %zu on device %d: %lld tiles\n", wi, o.devices[wi % o.devices.size()], (long long)workers[wi].n_tiles);
+        if (o.score_mem_mb > 0) {
+            int64_t nc = 0, ns = 0; for (auto &w : workers) { nc += w.n_chunks; ns += w.n_streamed; }
+            fprintf(stderr, "  --score-mem-mb %lld: %lld records per chunk, %lld chunks in %lld scored tiles = %.2f chunks per tile\n", (long long)o.score_mem_mb,
+                    (long long)std::max<int64_t>(1, (o.score_mem_mb << 20) / uvcgpu_score_stream_bytes_per_record()), (long long)nc, (long long)ns, ns ? (double)nc / (double)ns : 0.0);
+        }
     }
     return 0;
 }

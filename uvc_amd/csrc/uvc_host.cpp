@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <thread>
@@ -37,6 +38,19 @@ extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const Uv
                                 const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity, char *scratch, int32_t *d_fields_kept, const int32_t *d_force_sites,
                                 const void *d_ranges, int64_t n_ranges, int64_t n_compact, hipStream_t s);
 extern "C" size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity);
+// the streamed form (uvcgpu_region_score_stream_*): one gate pass + the chunk cut, then the per-record kernels per chunk into a row set
+extern "C" int uvc_launch_score_gate(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
+                                     const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
+                                     const void *d_ranges, int64_t n_ranges, int64_t n_compact, int64_t chunk_records, int64_t tab_cap, hipStream_t s);
+extern "C" int uvc_launch_score_chunk(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
+                                      const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
+                                      const void *d_ranges, int64_t n_ranges, int64_t n_compact, char *set, int64_t chunk_records, int with_kept,
+                                      int64_t win_g, int64_t win_n, int64_t win_groups, int64_t win_records, hipStream_t s);
+extern "C" size_t uvc_score_set_bytes(int64_t chunk_records, int64_t ngroups, int with_kept);
+extern "C" size_t uvc_score_set_bytes_per_record(void);
+extern "C" int32_t *uvc_score_set_fields(char *set, int64_t chunk_records, int64_t ngroups, int kept);
+extern "C" size_t uvc_score_stream_pos_bytes(int64_t npos_scored, int64_t tab_cap);
+extern "C" size_t uvc_score_stream_table_offset(int64_t npos_scored);
 extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity);
 extern "C" void uvc_launch_zero_state(char *slab, const void *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s);
 extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
@@ -74,6 +88,7 @@ template <class F> static int guarded(const char *what, F &&f) {
 extern "C" int uvcgpu_set_error(int code, const char *msg) { return fail(code, msg ? msg : ""); }   // for the other translation units of the library
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(UVCGPU_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 
+struct uvcgpu_score_stream;
 struct uvcgpu_region {
     UvcParams P;
     int32_t tid, beg, end;     // state covers [beg, end): end = caller's end + 1 (main.cpp:569)
@@ -110,6 +125,7 @@ struct uvcgpu_region {
     int32_t *d_score_fields = nullptr; int64_t score_capacity = 0; int64_t *d_score_count = nullptr;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     int32_t *d_score_kept = nullptr; int64_t score_kept_capacity = 0;   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields
+    uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
     std::vector<UvcGapRow> gap_rows; std::vector<uint8_t> gap_seq;
@@ -121,6 +137,8 @@ struct uvcgpu_region {
     std::vector<UvcHapLinkHost> hap[3];
 };
 
+static bool stream_open_(const uvcgpu_region *r);   // a streamed score is open on the handle: accumulate, reset, set_reads and the one-call scores wait for its end
+static void stream_destroy(uvcgpu_region *r);
 static size_t group_bytes(const uvcgpu_region *r, int g) {
     const size_t n = (size_t)r->npos;
     switch (g) {
@@ -340,6 +358,7 @@ static int uvcgpu_region_create_impl(uvcgpu_region_t **out, const UvcParams *par
 // events and -- when the new region is not longer than the longest one the handle has seen -- the device buffers are kept.
 static int uvcgpu_region_reset_impl(uvcgpu_region_t *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) {
     if (!r || !refseq || end <= beg) return fail(UVCGPU_EINVAL, "bad argument");
+    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "reset while a score stream is open");
     HIP_OK(hipStreamSynchronize(r->stream));
     if (r->side) HIP_OK(hipStreamSynchronize(r->side));
     if (r->side3) HIP_OK(hipStreamSynchronize(r->side3));
@@ -501,6 +520,7 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
 // Host columns: they are copied to the device as they are (no host pass over the reads), then prepared there.
 static int uvcgpu_region_set_reads_impl(uvcgpu_region_t *r, const UvcReadSoA *in) {
     if (!r || !in) return fail(UVCGPU_EINVAL, "bad reads");
+    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "set_reads while a score stream is open");
     if (in->struct_size != (int32_t)sizeof(UvcReadSoA)) return fail(UVCGPU_EINVAL, "UvcReadSoA::struct_size mismatch (set it to sizeof(UvcReadSoA))");
     if (in->n_reads < 0 || in->n_fams < 0) return fail(UVCGPU_EINVAL, "bad reads");
     const bool timing = (getenv("UVCGPU_TIMING") != nullptr);   // stderr breakdown of the ingest, for tuning
@@ -548,6 +568,7 @@ static int uvcgpu_region_set_reads_impl(uvcgpu_region_t *r, const UvcReadSoA *in
 // read bases / quals / cigars in place -- and uvcgpu_region_correct_bq edits `quals` in place, as the reference edits its bam1_t.
 static int uvcgpu_region_set_reads_device_impl(uvcgpu_region_t *r, const UvcReadSoA *in) {
     if (!r || !in) return fail(UVCGPU_EINVAL, "bad reads");
+    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "set_reads while a score stream is open");
     if (in->struct_size != (int32_t)sizeof(UvcReadSoA)) return fail(UVCGPU_EINVAL, "UvcReadSoA::struct_size mismatch (set it to sizeof(UvcReadSoA))");
     if (in->n_reads < 0 || in->n_fams < 0 || in->n_bases < 0 || in->n_cigar_ops < 0) return fail(UVCGPU_EINVAL, "bad reads");
     const bool timing = (getenv("UVCGPU_TIMING") != nullptr);
@@ -627,6 +648,7 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
 
 static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
     if (!r) return fail(UVCGPU_EINVAL, "null region");
+    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "accumulate while a score stream is open");
     if (!r->has_reads) return fail(UVCGPU_ENOREADS, "no reads");   // process_batch returns -1, main.cpp:520-523
     if (r->state_zeroed) { r->dirty_npos = 0; HIP_OK(hipStreamWaitEvent(r->stream, r->e_join, 0)); }   // zeroed behind the last score (release_state)
     else { const int rcz = zero_state(r, r->stream); if (rcz) return rcz; }
@@ -1073,14 +1095,31 @@ static int stage_upload(uvcgpu_region_t *r, void *dst, const void *src, size_t b
 
 // `ranges` (uvcgpu_region_score_ranges) or NULL (uvcgpu_region_score): everything but the group axis is the same call
 struct ScoreRangeDev { int32_t beg, end, first, flags; };   // UvcScoreRangeDev of uvc_kernels_score.hip
-static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
-    if (!r || !out || !out->fields) return fail(UVCGPU_EINVAL, "bad argument");
+// What a score request becomes before any scoring kernel runs -- the checked request, the ranges' device table, the caller's alleles merged
+// with the region's, tumor keys, force-output sites, all uploaded through the staging buffer -- for the one call and for a stream alike.
+// The temporaries go back to the caching allocator, which hands them to other handles at once: the destructor drains the stream first
+// (async copies, kernels that read the blocks), then frees them.
+struct ScorePrep {
+    uvcgpu_region *r = nullptr;
+    UvcScoreRequest rq; std::vector<ScoreRangeDev> rtab; int64_t npos_scored = 0;
+    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; ScoreRangeDev *d_rg = nullptr;
+    const UvcIndelAllele *use_al = nullptr; const int32_t *use_row = nullptr; int64_t n_al = 0;
+    ~ScorePrep() {
+        if (!r) return;
+        if (d_al || d_al_row || d_tk || d_fs || d_rg) { (void)hipStreamSynchronize(r->stream); if (r->side) (void)hipStreamSynchronize(r->side); }
+        if (d_al) hipFree(d_al); if (d_al_row) hipFree(d_al_row); if (d_tk) hipFree(d_tk); if (d_fs) hipFree(d_fs); if (d_rg) hipFree(d_rg);
+    }
+};
+static bool stream_is_open(const uvcgpu_region *r);
+static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, ScorePrep &p) {
     if (!r->accumulated) return fail(UVCGPU_ESTATE, "score before accumulate");
     if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
-    UvcScoreRequest rq; memset(&rq, 0, sizeof(rq)); rq.pos_beg = -1;
+    if (stream_is_open(r)) return fail(UVCGPU_ESTATE, "a score stream is open on this handle (uvcgpu_score_stream_end closes it)");
+    p.r = r;
+    UvcScoreRequest &rq = p.rq; memset(&rq, 0, sizeof(rq)); rq.pos_beg = -1;
     if (req) rq = *req;
-    std::vector<ScoreRangeDev> rtab;   // ranges call: the device table; npos_scored = the compact length
-    int64_t npos_scored = 0;
+    std::vector<ScoreRangeDev> &rtab = p.rtab;   // ranges call: the device table; npos_scored = the compact length
+    int64_t &npos_scored = p.npos_scored;
     if (ranges) {
         if (n_ranges < 1 || n_ranges > INT32_MAX) return fail(UVCGPU_EINVAL, "score_ranges: n_ranges must be at least 1");
         if (rq.pos_beg != -1 || rq.base_at_pos_beg != 0 || rq.region_beg != 0) return fail(UVCGPU_EINVAL, "score_ranges: the request's pos_beg must be -1, its base_at_pos_beg and region_beg 0 (the ranges carry them)");
@@ -1104,13 +1143,10 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
     }
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
-    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; ScoreRangeDev *d_rg = nullptr;
+    UvcIndelAllele *&d_al = p.d_al; int32_t *&d_al_row = p.d_al_row; UvcTumorKey *&d_tk = p.d_tk; int32_t *&d_fs = p.d_fs; ScoreRangeDev *&d_rg = p.d_rg;
     std::vector<UvcIndelAllele> merged; std::vector<int32_t> merged_row;
-    // the temporaries go back to the caching allocator, which hands them to other handles at once: on every return path the stream is
-    // drained first (async copies from `merged` / the caller's keys, kernels that read the blocks), then they are freed
-    struct Temps { uvcgpu_region *r; UvcIndelAllele *&a; int32_t *&b; UvcTumorKey *&c; int32_t *&d; ScoreRangeDev *&e;
-                   ~Temps() { if (a || b || c || d || e) (void)hipStreamSynchronize(r->stream); if (a) hipFree(a); if (b) hipFree(b); if (c) hipFree(c); if (d) hipFree(d); if (e) hipFree(e); } } temps = { r, d_al, d_al_row, d_tk, d_fs, d_rg };
-    const UvcIndelAllele *use_al = r->d_gap_alleles; const int32_t *use_row = r->d_gap_allele_row; int64_t n_al = (int64_t)r->gap_alleles.size();
+    const UvcIndelAllele *&use_al = p.use_al; const int32_t *&use_row = p.use_row; int64_t &n_al = p.n_al;
+    use_al = r->d_gap_alleles; use_row = r->d_gap_allele_row; n_al = (int64_t)r->gap_alleles.size();
     // one staging layout per call (an earlier call's copies are complete: score synchronises before it returns)
     size_t stage_at = 0;
     const size_t stage_total = (sizeof(UvcIndelAllele) + sizeof(int32_t)) * (size_t)(r->gap_alleles.size() + (size_t)std::max<int64_t>(rq.n_indel_alleles, 0)) + sizeof(UvcTumorKey) * (size_t)std::max<int64_t>(rq.n_tumor_keys, 0)
@@ -1152,6 +1188,15 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         HIP_OK(hipMalloc((void **)&d_rg, sizeof(ScoreRangeDev) * rtab.size()));
         { int rc1 = stage_upload(r, d_rg, rtab.data(), sizeof(ScoreRangeDev) * rtab.size(), stage_at, stage_total); if (rc1) return rc1; }
     }
+    return 0;
+}
+static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
+    if (!r || !out || !out->fields) return fail(UVCGPU_EINVAL, "bad argument");
+    ScorePrep prep;   // (its destructor frees the temporaries on every return path)
+    { const int rc0 = score_prepare(r, req, ranges, n_ranges, prep); if (rc0) return rc0; }
+    const UvcScoreRequest &rq = prep.rq; const std::vector<ScoreRangeDev> &rtab = prep.rtab; const int64_t npos_scored = prep.npos_scored;
+    const UvcIndelAllele *use_al = prep.use_al; const int32_t *use_row = prep.use_row; const int64_t n_al = prep.n_al;
+    UvcTumorKey *d_tk = prep.d_tk; int32_t *d_fs = prep.d_fs; ScoreRangeDev *d_rg = prep.d_rg;
     const bool kept_only = (rq.kept_only != 0);
     // device capacity: the caller's in the plain form; with kept_only the caller's buffer only has to hold the kept groups, the device
     // array every record -- start from a guess and grow once if the count says so
@@ -1213,7 +1258,212 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
                              || hipStreamSynchronize(r->stream) != hipSuccess))
             rc = fail(UVCGPU_EDEVICE, "hipMemcpy2D(records)");
     }
-    return rc;   // ~Temps frees the temporaries
+    return rc;   // ~ScorePrep frees the temporaries
+}
+
+// ---- streamed score (uvcgpu_region_score_stream_begin / uvcgpu_score_stream_next / uvcgpu_score_stream_end) ----
+// One gate pass over the whole request and the cut (k_chunk_cut) on the handle's stream, the small chunk table read back once; then the
+// per-record kernels chunk by chunk into one of TWO row sets, each with a page-locked host buffer of its own.  Chunk k's kernels run on the
+// handle's stream, its D2H on the side stream behind an event; `next` for chunk j queues chunk j + 1 (whose set and host buffer the caller
+// gave back with this very call: it held chunk j - 1) and then waits for chunk j's copy alone.  So chunk j + 1 is computed and copied while
+// the caller formats chunk j.  Two streams, four events, no graph; no allocation per chunk.
+struct ScoreSet { char *d = nullptr; size_t d_bytes = 0; char *h = nullptr; size_t h_bytes = 0; hipEvent_t e_k = nullptr, e_c = nullptr; };
+struct uvcgpu_score_stream {
+    uvcgpu_region *r = nullptr; bool open = false;
+    int64_t chunk_records = 0; ScoreSet set[2];          // kept across streams with the same chunk_records
+    ScorePrep *prep = nullptr;                           // the open stream's request and its device temporaries
+    std::vector<UvcScoreRange> ranges; bool plain = true;   // the request's ranges (a plain request: its one range)
+    std::vector<int64_t> tab;                            // [n_chunks][4]: first group, group count, first record, record count
+    int64_t n_chunks = 0, launched = 0, returned = 0, ngroups = 0; int with_kept = 0; bool release_queued = false;
+};
+static bool stream_is_open(const uvcgpu_region *r) { return r && r->ss && r->ss->open; }
+static bool stream_open_(const uvcgpu_region *r) { return stream_is_open(r); }
+#define UVC_STREAM_HOST_TAIL 64   /* behind the records of a page-locked buffer: the chunk's kept count and the kernels' error word */
+static void stream_free_sets(uvcgpu_score_stream *s) {
+    for (ScoreSet &q : s->set) {
+        if (q.d) hipFree(q.d);
+        if (q.h) (void)hipHostFree(q.h);
+        q.d = nullptr; q.h = nullptr; q.d_bytes = q.h_bytes = 0;
+    }
+    s->chunk_records = 0;
+}
+static void stream_destroy(uvcgpu_region *r) {
+    uvcgpu_score_stream *s = r->ss;
+    if (!s) return;
+    delete s->prep; s->prep = nullptr;
+    stream_free_sets(s);
+    for (ScoreSet &q : s->set) { if (q.e_k) hipEventDestroy(q.e_k); if (q.e_c) hipEventDestroy(q.e_c); }
+    delete s; r->ss = nullptr;
+}
+// chunk k: kernels on the handle's stream, then counts + records to the set's host buffer on the side stream
+static int stream_launch_chunk(uvcgpu_score_stream *s, int64_t k) {
+    uvcgpu_region *r = s->r; const ScorePrep &p = *s->prep; ScoreSet &q = s->set[k & 1];
+    const int64_t *t = &s->tab[(size_t)k * 4];
+    const int64_t c = s->chunk_records, nr = t[3];
+    const int64_t win_groups = std::min<int64_t>(std::min<int64_t>(t[1], nr), c);   // active groups of the window: at most its groups, at most its records
+    int rc = uvc_launch_score_chunk(&r->R, &r->P, &p.rq, p.use_al, p.use_row, p.n_al, r->d_gap_rows, r->d_gap_seq, p.d_tk, r->d_score_scratch, p.d_fs, p.d_rg, (int64_t)p.rtab.size(), p.npos_scored,
+                                    q.d, c, s->with_kept, t[0], t[1], win_groups, nr, r->stream);
+    if (rc) return fail(rc, "score stream: chunk launch refused");
+    if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "score stream: kernel launch failed");
+    hipStream_t cs = r->side ? r->side : r->stream;
+    HIP_OK(hipEventRecord(q.e_k, r->stream));
+    if (r->side) HIP_OK(hipStreamWaitEvent(cs, q.e_k, 0));
+    char *tail = q.h + sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)c;
+    HIP_OK(hipMemcpyAsync(tail, q.d, 16, hipMemcpyDeviceToHost, cs));            // the set's record counts: [1] = kept records
+    HIP_OK(hipMemcpyAsync(tail + 16, r->R.err, 4, hipMemcpyDeviceToHost, cs));
+    // (kept_only: the kept count is on the device; the copy takes the columns of all the chunk's records, of which the kept ones are a prefix --
+    //  under -A nearly all of them, at the default gate a few hundred KB more than needed, and nothing waits for a count)
+    if (nr > 0) HIP_OK(hipMemcpy2DAsync(q.h, sizeof(int32_t) * (size_t)c, uvc_score_set_fields(q.d, c, s->ngroups, p.rq.kept_only ? 1 : 0), sizeof(int32_t) * (size_t)c, sizeof(int32_t) * (size_t)nr, UVC_NUM_SCORE_FIELDS, hipMemcpyDeviceToHost, cs));
+    if (k == s->n_chunks - 1 && p.rq.release_state && r->side) {   // behind the last chunk's kernels (and its copy): zero the planes for the next accumulate
+        if (zero_state(r, r->side) == 0 && hipEventRecord(r->e_join, r->side) == hipSuccess) {
+            r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes; r->dirty_npos = r->npos; s->release_queued = true;
+        }
+    }
+    HIP_OK(hipEventRecord(q.e_c, cs));
+    s->launched = k + 1;
+    return 0;
+}
+static int stream_close(uvcgpu_score_stream *s) {
+    uvcgpu_region *r = s->r;
+    int rc = 0;
+    if (hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score stream: hipStreamSynchronize");
+    if (r->side && hipStreamSynchronize(r->side) != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score stream: hipStreamSynchronize(side)");
+    delete s->prep; s->prep = nullptr;
+    s->open = false; s->tab.clear(); s->ranges.clear();
+    return rc;
+}
+static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, int64_t chunk_records, uvcgpu_score_stream_t **out) {
+    if (!r || !out) return fail(UVCGPU_EINVAL, "bad argument");
+    *out = nullptr;
+    if (chunk_records < 1 || chunk_records > INT32_MAX) return fail(UVCGPU_EINVAL, "score stream: chunk_records must be at least 1");
+    if (!ranges && n_ranges != 0) return fail(UVCGPU_EINVAL, "score stream: ranges is NULL but n_ranges is not 0");
+    std::unique_ptr<ScorePrep> prep(new ScorePrep());
+    { const int rc0 = score_prepare(r, req, ranges, n_ranges, *prep); if (rc0) return rc0; }
+    if (!r->ss) {
+        r->ss = new uvcgpu_score_stream(); r->ss->r = r;
+        for (ScoreSet &q : r->ss->set) if (hipEventCreateWithFlags(&q.e_k, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&q.e_c, hipEventDisableTiming) != hipSuccess) { stream_destroy(r); return fail(UVCGPU_EDEVICE, "hipEventCreate"); }
+    }
+    uvcgpu_score_stream *s = r->ss;
+    const UvcScoreRequest &rq = prep->rq;
+    const int64_t npos = prep->npos_scored, ngroups = 2 * npos;
+    // a greedy cut leaves no two neighbouring chunks that would fit one: at most 2 * records / chunk_records + 1 chunks, and one per position
+    const int64_t upper = NSYM * (npos + 1) + rq.n_indel_alleles + rq.n_tumor_keys + 16 * std::max<int64_t>(rq.n_force_sites, 0) + (int64_t)r->gap_alleles.size();
+    const int64_t tab_cap = std::max<int64_t>(1, std::min<int64_t>(npos, 2 * upper / chunk_records + 2));
+    // the record-sized buffers of the one-call path go (a later plain call allocates what it needs again); the position-sized scratch is kept
+    // when it fits and is not a plain call's record-sized one
+    HIP_OK(hipStreamSynchronize(r->stream));
+    if (r->d_score_fields) { hipFree(r->d_score_fields); r->d_score_fields = nullptr; r->score_capacity = 0; }
+    if (r->d_score_kept) { hipFree(r->d_score_kept); r->d_score_kept = nullptr; r->score_kept_capacity = 0; }
+    const size_t pos_need = uvc_score_stream_pos_bytes(npos, tab_cap);
+    if (r->score_scratch_bytes < pos_need || r->score_scratch_bytes > pos_need + pos_need / 4 + 65536) {
+        if (r->d_score_scratch) hipFree(r->d_score_scratch);
+        r->d_score_scratch = nullptr; r->score_scratch_bytes = 0; r->d_score_count = nullptr;
+        if (hipMalloc((void **)&r->d_score_scratch, pos_need) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, "score stream: hipMalloc of the position-sized scratch (" + std::to_string(pos_need) + " bytes)"); }
+        r->score_scratch_bytes = pos_need;
+    }
+    r->d_score_count = (int64_t *)r->d_score_scratch;
+    const int with_kept = rq.kept_only ? 1 : 0;
+    const size_t set_need = uvc_score_set_bytes(chunk_records, ngroups, with_kept), host_need = sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)chunk_records + UVC_STREAM_HOST_TAIL;
+    if (s->chunk_records != chunk_records) stream_free_sets(s);
+    for (ScoreSet &q : s->set) {
+        if (q.d_bytes < set_need) {
+            if (q.d) hipFree(q.d);
+            q.d = nullptr; q.d_bytes = 0;
+            if (hipMalloc((void **)&q.d, set_need) != hipSuccess) { (void)hipGetLastError(); stream_free_sets(s); return fail(UVCGPU_ENOMEM, "score stream: hipMalloc of a row set (" + std::to_string(set_need) + " bytes for chunk_records = " + std::to_string(chunk_records) + ")"); }
+            q.d_bytes = set_need;
+        }
+        if (q.h_bytes < host_need) {
+            if (q.h) (void)hipHostFree(q.h);
+            q.h = nullptr; q.h_bytes = 0;
+            if (hipHostMalloc((void **)&q.h, host_need, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); stream_free_sets(s); return fail(UVCGPU_ENOMEM, "score stream: hipHostMalloc of a records buffer (" + std::to_string(host_need) + " bytes)"); }
+            q.h_bytes = host_need;
+        }
+    }
+    s->chunk_records = chunk_records; s->with_kept = with_kept; s->ngroups = ngroups;
+    s->n_chunks = 0; s->launched = 0; s->returned = 0; s->release_queued = false; s->tab.clear();
+    s->plain = (ranges == nullptr); s->ranges.clear();
+    if (ranges) s->ranges.assign(ranges, ranges + n_ranges);
+    else s->ranges.push_back(UvcScoreRange{ rq.pos_beg, rq.pos_end, rq.base_at_pos_beg ? 1 : 0, rq.region_beg });
+    if (npos > 0) {
+        HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos, 1), r->stream));
+        int rc = uvc_launch_score_gate(&r->R, &r->P, &rq, prep->use_al, prep->use_row, prep->n_al, r->d_gap_rows, r->d_gap_seq, prep->d_tk, r->d_score_scratch, prep->d_fs, prep->d_rg, (int64_t)prep->rtab.size(), npos,
+                                       chunk_records, tab_cap, r->stream);
+        if (rc) return fail(rc, "score stream: the force-output mask could not be cleared");
+        if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "score stream: kernel launch failed");
+        { const int rcs = uvcgpu_region_sync(r); if (rcs) return rcs; }
+        const char *d_tab = r->d_score_scratch + uvc_score_stream_table_offset(npos);
+        int64_t hdr[4] = { 0, 0, 0, 0 };
+        if (hipMemcpyAsync(hdr, d_tab, 32, hipMemcpyDeviceToHost, r->stream) != hipSuccess || hipStreamSynchronize(r->stream) != hipSuccess) return fail(UVCGPU_EDEVICE, "score stream: hipMemcpy(chunk count)");
+        if (hdr[0] == -1) {   // one position alone is more than a chunk: name it (compact position -> zerobased_pos)
+            int64_t z = hdr[1], at = 0;
+            for (const UvcScoreRange &g : s->ranges) { const int64_t len = std::max<int64_t>((int64_t)g.pos_end - g.pos_beg, 0); if (hdr[1] < at + len) { z = g.pos_beg + (hdr[1] - at); break; } at += len; }
+            return fail(UVCGPU_ENOMEM, "score stream: zerobased_pos " + std::to_string(z) + " alone has " + std::to_string(hdr[2]) + " records, more than chunk_records = " + std::to_string(chunk_records));
+        }
+        if (hdr[0] < 0 || hdr[0] > tab_cap) return fail(UVCGPU_EDEVICE, "score stream: the chunk table overflowed");
+        s->n_chunks = hdr[0];
+        s->tab.resize((size_t)s->n_chunks * 4);
+        if (s->n_chunks > 0 && (hipMemcpyAsync(s->tab.data(), d_tab + 32, 32 * (size_t)s->n_chunks, hipMemcpyDeviceToHost, r->stream) != hipSuccess || hipStreamSynchronize(r->stream) != hipSuccess)) return fail(UVCGPU_EDEVICE, "score stream: hipMemcpy(chunk table)");
+    }
+    s->prep = prep.release(); s->open = true;
+    r->last_scored = 0; r->last_returned = 0;
+    for (int64_t k = 0; k < std::min<int64_t>(2, s->n_chunks); k++) { const int rc = stream_launch_chunk(s, k); if (rc) { const std::string msg = g_err; stream_close(s); return fail(rc, msg); } }
+    *out = s;
+    return 0;
+}
+static int uvcgpu_score_stream_next_impl(uvcgpu_score_stream_t *s, UvcScoreOut *chunk, UvcScoreRange *covered, int64_t *n_covered) {
+    if (!s || !chunk) return fail(UVCGPU_EINVAL, "bad argument");
+    if (!s->open) return fail(UVCGPU_ESTATE, "score stream: not open");
+    uvcgpu_region *r = s->r;
+    if (n_covered) *n_covered = 0;
+    chunk->capacity = s->chunk_records; chunk->n_records = 0; chunk->fields = (int32_t *)s->set[0].h;
+    const int64_t j = s->returned;
+    if (j >= s->n_chunks) return UVCGPU_STREAM_END;
+    // this call gives back the buffers of chunk j - 1: chunk j + 1 takes them
+    if (j + 1 < s->n_chunks && s->launched == j + 1) { const int rc = stream_launch_chunk(s, j + 1); if (rc) return rc; }
+    ScoreSet &q = s->set[j & 1];
+    HIP_OK(hipEventSynchronize(q.e_c));
+    const int64_t c = s->chunk_records, *t = &s->tab[(size_t)j * 4];
+    const char *tail = q.h + sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)c;
+    int64_t cnt[2]; int32_t e = 0;
+    memcpy(cnt, tail, 16); memcpy(&e, tail + 16, 4);
+    if (e) return fail(e, "a scoring kernel flagged an error");
+    const int64_t n_out = (s->prep->rq.kept_only ? cnt[1] : t[3]);
+    if (n_out < 0 || n_out > t[3]) return fail(UVCGPU_EDEVICE, "score stream: the kept count of a chunk is out of range");
+    chunk->fields = (int32_t *)q.h; chunk->n_records = n_out;
+    r->last_scored += t[3]; r->last_returned += n_out;
+    // the ranges this chunk covers: the request's ranges cut to the chunk's compact positions; a piece that begins inside a range continues it
+    const int64_t c0 = t[0] / 2, c1 = c0 + t[1] / 2;
+    int64_t at = 0, nc = 0;
+    for (const UvcScoreRange &g : s->ranges) {
+        const int64_t len = std::max<int64_t>((int64_t)g.pos_end - g.pos_beg, 0), lo = std::max(c0, at), hi = std::min(c1, at + len);
+        if (hi > lo) {
+            if (covered) covered[nc] = UvcScoreRange{ (int32_t)(g.pos_beg + (lo - at)), (int32_t)(g.pos_beg + (hi - at)), (lo > at) ? 1 : g.base_at_pos_beg, g.region_beg };
+            nc++;
+        }
+        at += len;
+    }
+    if (n_covered) *n_covered = nc;
+    s->returned = j + 1;
+    return 0;
+}
+static int uvcgpu_score_stream_end_impl(uvcgpu_score_stream_t *s) {
+    if (!s) return fail(UVCGPU_EINVAL, "null stream");
+    if (!s->open) return fail(UVCGPU_ESTATE, "score stream: not open");
+    return stream_close(s);
+}
+int uvcgpu_region_score_stream_begin(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, int64_t chunk_records, uvcgpu_score_stream_t **out) {
+    return guarded("uvcgpu_region_score_stream_begin", [&] { return uvcgpu_region_score_stream_begin_impl(r, req, ranges, n_ranges, chunk_records, out); });
+}
+int uvcgpu_score_stream_next(uvcgpu_score_stream_t *s, UvcScoreOut *chunk, UvcScoreRange *covered, int64_t *n_covered) { return guarded("uvcgpu_score_stream_next", [&] { return uvcgpu_score_stream_next_impl(s, chunk, covered, n_covered); }); }
+int uvcgpu_score_stream_end(uvcgpu_score_stream_t *s) { return guarded("uvcgpu_score_stream_end", [&] { return uvcgpu_score_stream_end_impl(s); }); }
+int64_t uvcgpu_score_stream_bytes_per_record(void) { return 2 * ((int64_t)uvc_score_set_bytes_per_record() + (int64_t)sizeof(int32_t) * UVC_NUM_SCORE_FIELDS); }
+int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
+    if (!r) return -1;
+    int64_t b = (int64_t)r->score_scratch_bytes + (int64_t)r->h_stage_cap;
+    if (r->d_score_fields) b += (int64_t)sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * r->score_capacity;
+    if (r->d_score_kept) b += (int64_t)sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * r->score_kept_capacity;
+    if (r->ss) for (const ScoreSet &q : r->ss->set) b += (int64_t)q.d_bytes + (int64_t)q.h_bytes;
+    return b;
 }
 
 int uvcgpu_region_create(uvcgpu_region_t **out, const UvcParams *params, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_create", [&] { return uvcgpu_region_create_impl(out, params, tid, beg, end, refseq); }); }
@@ -1234,6 +1484,7 @@ int uvcgpu_region_score_ranges(uvcgpu_region_t *r, const UvcScoreRequest *req, c
 void uvcgpu_region_destroy(uvcgpu_region_t *r) {
     if (!r) return;
     quiesce(r);
+    stream_destroy(r);   // an open score stream ends here: its temporaries, row sets and page-locked buffers (the streams are still there)
     free_reads(r);
     if (r->d_refsym) hipFree(r->d_refsym);
     if (r->d_rtr) hipFree(r->d_rtr);

@@ -145,6 +145,10 @@ DEV bool group_all_out(const ScoreCtx &C, long long g) {
 }
 #define PK_COUNT(v) ((long long)((v) & 0xFFFFFFFFLL))
 #define PK_FLAGS(v) ((long long)((v) >> 32))
+// the window of the launch (Stage::win_g / win_n): first active group, number of active groups, first record
+#define WIN_PROLOGUE \
+    const long long win_lo_ = C.offsets[S.win_g], win_hi_ = C.offsets[S.win_g + S.win_n]; \
+    const long long a_base = PK_FLAGS(win_lo_), n_active = PK_FLAGS(win_hi_) - a_base, r_base = PK_COUNT(win_lo_); (void)r_base;
 
 DEV long long allele_lower_bound(const ScoreCtx &C, int refpos, int symbol) {
     long long lo = 0, hi = C.n_alleles;
@@ -297,12 +301,17 @@ struct Stage {
     long long *al64;     // [NAL64][cap]
     double *mid;         // [NMID][cap]
     double *d4;          // [NDP4][2][cap]
-    long long cap;       // records (and therefore active groups) the rows can hold
+    long long cap;       // records the rows can hold
+    long long gcap;      // active groups the group rows (grp, tot, keptoff) can hold: cap in the one-call layout, min(groups, cap) in the streamed one
+    // the chunk window of a streamed score: groups [win_g, win_g + win_n) of the request, cut on a position boundary (k_chunk_cut).  Rows and
+    // record indices are relative to the window's first active group and first record.  The one-call path passes (0, all groups): the
+    // window's bases are then offsets[0] = 0 and the length is the whole list -- uniform scalar loads, no per-lane work
+    long long win_g, win_n;
     unsigned int *cnt;   // [NCNT] counters, zeroed in front of every call: records of the groups that fit, tickets of the two chained scans
     unsigned long long *status1, *status2;   // tile states of the two chained scans (zeroed with the counters)
     int32_t *keptoff;    // [cap] kept_only: first record of an active group in the kept array, or -1
 };
-#define GR_(f, gi_) ROW_(int32_t, S.grp, GR_##f, S.cap, gi_)
+#define GR_(f, gi_) ROW_(int32_t, S.grp, GR_##f, S.gcap, gi_)
 #define RH_(f, r_) ROW_(int32_t, S.rh, RH_##f, S.cap, r_)
 #define MID_(f, r_) ROW_(double, S.mid, MID_##f, S.cap, r_)
 #define D4_(t, k, r_) ROW_(double, S.d4, (t) * 2 + (k), S.cap, r_)
@@ -323,7 +332,7 @@ DEV long long stage_cell(const RegionDev &R, int grp, int plane, int s, int64_t 
     }
 }
 // staged-row accessors: the names of the old per-thread structs (Tot T, Al f) as loads at the point of use; `gi` / `rec` are the thread's group / record
-#define TT_(n) ROW_(long long, S.tot, TOT_##n, S.cap, gi)
+#define TT_(n) ROW_(long long, S.tot, TOT_##n, S.gcap, gi)
 #define AL_(n) ROW_(int32_t, S.al, AL_##n, S.cap, rec)
 #define AL64_(n) ROW_(long long, S.al64, AL_##n - NAL32, S.cap, rec)
 #define T_APDP0 TT_(APDP0)
@@ -637,12 +646,11 @@ __global__ void __launch_bounds__(GS_BLOCK) k_gate_scan(RegionDev R, UvcParams P
 
 // One thread per active group: the group's scalars, the symbols that have anything at this position (type_mask), one header per record.
 __global__ void __launch_bounds__(128) k_enum(RegionDev R, UvcParams P, ScoreCtx C, Stage S) {
-    const long long ngroups = 2LL * (C.pos_end - C.pos_beg);
-    const long long n_active = PK_FLAGS(C.offsets[ngroups]);
+    WIN_PROLOGUE
     const long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= n_active || gi >= S.cap) return;
-    const long long g = C.active[gi];
-    const long long rec0 = PK_COUNT(C.offsets[g]), nrec = PK_COUNT(C.offsets[g + 1]) - rec0;
+    if (gi >= n_active || gi >= S.gcap) return;
+    const long long g = C.active[a_base + gi];
+    const long long rec0 = PK_COUNT(C.offsets[g]) - r_base, nrec = PK_COUNT(C.offsets[g + 1]) - r_base - rec0;
     if (nrec <= 0 || rec0 + nrec > C.capacity || rec0 + nrec > S.cap) { GR_(nrec, gi) = 0; return; }   // does not fit: the host sees the count and comes back
     bool no_base_;
     const int zpos = group_zpos(C, g, no_base_), st = (int)(g & 1);
@@ -732,10 +740,9 @@ __global__ void __launch_bounds__(128) k_enum(RegionDev R, UvcParams P, ScoreCtx
 // are independent (a symbol outside the mask re-reads the first one's cell, same line, instead of branching around a load).
 #define GATHER_PLANES 4
 __global__ void __launch_bounds__(256) k_gather(RegionDev R, ScoreCtx C, Stage S) {
-    const long long ngroups = 2LL * (C.pos_end - C.pos_beg);
-    const long long n_active = PK_FLAGS(C.offsets[ngroups]);
+    WIN_PROLOGUE
     const long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= n_active || gi >= S.cap) return;
+    if (gi >= n_active || gi >= S.gcap) return;
     const int nrec = GR_(nrec, gi);
     if (nrec == 0) return;
     const int64_t x = GR_(x, gi);
@@ -763,13 +770,13 @@ __global__ void __launch_bounds__(256) k_gather(RegionDev R, ScoreCtx C, Stage S
         const int u = (int)blockIdx.y * GATHER_PLANES + q;
         if (u >= NGATHER) break;
         const GatherDesc d = c_gather.d[u];
-        if (d.grp <= SG_PREP64) { ROW_(long long, S.tot, d.tot, S.cap, gi) = c[q][0]; continue; }
+        if (d.grp <= SG_PREP64) { ROW_(long long, S.tot, d.tot, S.gcap, gi) = c[q][0]; continue; }
         if (d.tot >= 0) {
             long long v = 0;
 #pragma unroll
             for (int k = 0; k < 8; k++) v += (((mask >> k) & 1u) ? c[q][k] : 0LL);
             if (d.trunc) v = (long long)(int)v;   // an int32 FORMAT field truncates the int64 sum on assignment (bcf_formats_generator1.cpp:220-245)
-            ROW_(long long, S.tot, d.tot, S.cap, gi) = v;
+            ROW_(long long, S.tot, d.tot, S.gcap, gi) = v;
         }
         for (int j = 0; j < nrec; j++) {
             const int k = st_index(st, RH_(symbol, rec0 + j));
@@ -1373,10 +1380,9 @@ DEV void normv_quals2(int out[4], double tAD, double tDP, int tVQ, int tnVQcap, 
 }
 
 __global__ void __launch_bounds__(128) k_call_group(UvcParams P, ScoreCtx C, Stage S) {
-    const long long ngroups = 2LL * (C.pos_end - C.pos_beg);
-    const long long n_active = PK_FLAGS(C.offsets[ngroups]);
+    WIN_PROLOGUE
     const long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gi >= n_active || gi >= S.cap) return;
+    if (gi >= n_active || gi >= S.gcap) return;
     const long long nrec_ = GR_(nrec, gi);
     GR_(vAC, gi) = 0; GR_(gemit, gi) = 0; GR_(kept, gi) = 0;
     if (nrec_ == 0) return;
@@ -1486,13 +1492,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const bool tprov = (P.tumor_vcf_is_provided != 0);
     const int st = GR_(st, gi);
     // the other symbol type's group of this zerobased_pos, if it is active: BASE (even group index) sits right in front of LINK in the list
-    const long long g = C.active[gi];
+    // (a chunk window holds both groups of a position: the neighbour is inside it)
+    WIN_PROLOGUE
+    const long long g = C.active[a_base + gi];
     long long gj = -1;
     {
-        const long long ngroups = 2LL * (C.pos_end - C.pos_beg);
-        const long long n_active = PK_FLAGS(C.offsets[ngroups]);
-        if (st == UVC_BASE_SYMBOL) { if (gi + 1 < n_active && gi + 1 < S.cap && C.active[gi + 1] == g + 1) gj = gi + 1; }
-        else if (gi > 0 && C.active[gi - 1] == g - 1) gj = gi - 1;
+        if (st == UVC_BASE_SYMBOL) { if (gi + 1 < n_active && gi + 1 < S.gcap && C.active[a_base + gi + 1] == g + 1) gj = gi + 1; }
+        else if (gi > 0 && C.active[a_base + gi - 1] == g - 1) gj = gi - 1;
     }
     const int vA_own = GR_(vAC, gi), vA_oth = (gj >= 0 ? GR_(vAC, gj) : 0);
     const int vAC0 = (st == UVC_BASE_SYMBOL ? vA_own : vA_oth), vAC1 = (st == UVC_BASE_SYMBOL ? vA_oth : vA_own);
@@ -1593,12 +1599,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
 // record writer reads the REF record and the genotype's records of such a group and nothing of the others.  Kept groups keep their order;
 // germ_ref / germ_alt1 / germ_alt2 (record indices inside the group) move with it.  One chained scan over the ACTIVE groups (a few ten
 // thousand at the default gate), blocks take tiles of the list by ticket.
-__global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, long long ngroups, long long *total_kept, int *err) {
+__global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, long long *total_kept, int *err) {
     __shared__ unsigned long long sh_wave[4], sh_prefix;
     __shared__ int sh_tile;
     // only the groups that fit the rows (a first kept-only attempt may have more, and is retried): status2 holds min(ngroups, cap) / GS_TILE + 1 tiles
-    const long long n_active = min(PK_FLAGS(C.offsets[ngroups]), (long long)S.cap);
-    const int ntiles = (int)((n_active + GS_TILE - 1) / GS_TILE);
+    WIN_PROLOGUE
+    const long long n_fit = min(n_active, S.gcap);
+    const int ntiles = (int)((n_fit + GS_TILE - 1) / GS_TILE);
     for (;;) {
         if (threadIdx.x == 0) sh_tile = (int)atomicAdd(&S.cnt[CNT_ticket2], 1u);
         __syncthreads();
@@ -1610,7 +1617,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, lon
         for (int i = 0; i < GS_ITEMS; i++) {
             const long long ai = a0 + i;
             long long n = 0;
-            if (ai < n_active && GR_(kept, ai)) n = GR_(nrec, ai);   // (a group that did not fit has nrec 0)
+            if (ai < n_fit && GR_(kept, ai)) n = GR_(nrec, ai);   // (a group that did not fit has nrec 0)
             v[i] = n; s += (unsigned long long)n;
         }
         unsigned long long total = 0;
@@ -1619,17 +1626,18 @@ __global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, lon
         __syncthreads();
         long long run = (long long)(sh_prefix + excl);
 #pragma unroll
-        for (int i = 0; i < GS_ITEMS; i++) { const long long ai = a0 + i; if (ai < n_active) S.keptoff[ai] = (v[i] ? (int32_t)run : -1); run += v[i]; }
+        for (int i = 0; i < GS_ITEMS; i++) { const long long ai = a0 + i; if (ai < n_fit) S.keptoff[ai] = (v[i] ? (int32_t)run : -1); run += v[i]; }
         if (tile == ntiles - 1 && threadIdx.x == 0) *total_kept = (long long)(sh_prefix + total);
         __syncthreads();   // sh_tile / sh_prefix / sh_wave are reused by the next tile
     }
 }
 #define KEEP_LANES 8
-__global__ void __launch_bounds__(256) k_keep_copy(ScoreCtx C, Stage S, long long ngroups, int32_t *fields2) {
-    const long long n_active = min(PK_FLAGS(C.offsets[ngroups]), (long long)S.cap);   // as k_keep_scan
+__global__ void __launch_bounds__(256) k_keep_copy(ScoreCtx C, Stage S, int32_t *fields2) {
+    WIN_PROLOGUE
+    const long long n_fit = min(n_active, S.gcap);   // as k_keep_scan
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long ai = t / KEEP_LANES; const int sub = (int)(t % KEEP_LANES);
-    if (ai >= n_active) return;
+    if (ai >= n_fit) return;
     const long long q0 = S.keptoff[ai];
     if (q0 < 0) return;
     const long long r0 = GR_(rec0, ai), n = GR_(nrec, ai);
@@ -1712,34 +1720,112 @@ static ScratchLayout scratch_layout(int64_t npos_scored, int64_t cap) {
 extern "C" size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity) { return scratch_layout(npos_scored, capacity).total; }
 extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity) { return scratch_layout(npos_scored, capacity).zero_bytes; }
 
-// The caller zeroes the first uvc_score_scratch_zero_bytes of `scratch` on the stream in front of this; the record counts (all records, kept
-// records) are its first two int64.
-extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity,
-                                char *scratch /* uvc_score_scratch_bytes */, int32_t *d_fields_kept /* kept_only: a second [fields][capacity] array */,
-                                const int32_t *d_force_sites /* device copy of UvcScoreRequest::force_sites, or NULL */,
-                                const void *d_ranges /* uvcgpu_region_score_ranges: device table of UvcScoreRangeDev, or NULL */, int64_t n_ranges, int64_t n_compact, hipStream_t s) {
-    ScoreCtx C;
+// ---- streamed score: the chunk table ----
+// One entry per chunk: first group (even: a position boundary), group count, first record, record count.  The cut is GREEDY: a chunk
+// takes positions until the next one would not fit chunk_records, so every chunk is as full as whole positions allow (fewest launches,
+// fewest D2H) and any two neighbours together hold more than chunk_records (which bounds the table: 2 * records / chunk_records + 1).
+// Greedy cuts depend on each other, so ONE WAVE walks them: per chunk the 64 lanes first probe the next 64 position boundaries of the
+// record prefix (offsets[2 * p], already on the device behind k_gate_scan), and when all fit, narrow [lo, hi) 65-fold per step -- a chunk
+// of 10^5 positions costs 3 steps of one coalesced-or-strided load each, a few microseconds against the milliseconds of its kernels.
+// hdr[0] = number of chunks, or -1: position hdr[1] (compact) alone needs hdr[2] records, or -2: the table is too small (cannot happen).
+struct UvcChunkDev { long long g0, ng, r0, nr; };
+__global__ void __launch_bounds__(64) k_chunk_cut(const long long *offsets, long long npos, long long chunk_records, long long *hdr, UvcChunkDev *tab, long long tab_cap) {
+    const int lane = (int)threadIdx.x;
+    long long p0 = 0, n = 0;
+    while (p0 < npos) {
+        const long long w0 = offsets[2 * p0], s0 = PK_COUNT(w0);
+        long long q = p0 + 1 + lane;
+        bool ok = (q <= npos) && (PK_COUNT(offsets[2 * (q <= npos ? q : npos)]) - s0 <= chunk_records);   // the prefix never falls: the lanes that fit are a run from lane 0
+        int c = __popcll(__ballot(ok));
+        if (c == 0) { if (lane == 0) { hdr[0] = -1; hdr[1] = p0; hdr[2] = PK_COUNT(offsets[2 * (p0 + 1)]) - s0; } return; }
+        long long p1 = p0 + c;
+        if (c == 64) {
+            long long lo = p0 + 64, hi = npos + 1;   // lo fits, hi does not (npos + 1: behind the end)
+            while (hi - lo > 1) {
+                const long long span = hi - lo;
+                if (span <= 65) {
+                    q = lo + 1 + lane;
+                    ok = (q < hi) && (PK_COUNT(offsets[2 * (q < hi ? q : lo)]) - s0 <= chunk_records);
+                    c = __popcll(__ballot(ok));
+                    lo += c; hi = lo + 1;
+                } else {
+                    q = lo + ((long long)(lane + 1) * span) / 65;   // lo < q < hi, ascending with the lane
+                    ok = (PK_COUNT(offsets[2 * q]) - s0 <= chunk_records);
+                    c = __popcll(__ballot(ok));
+                    const long long nlo = (c > 0 ? lo + ((long long)c * span) / 65 : lo), nhi = (c < 64 ? lo + ((long long)(c + 1) * span) / 65 : hi);
+                    lo = nlo; hi = nhi;
+                }
+            }
+            p1 = lo;
+        }
+        if (n >= tab_cap) { if (lane == 0) { hdr[0] = -2; hdr[1] = p0; hdr[2] = n; } return; }
+        if (lane == 0) { const long long w1 = offsets[2 * p1]; tab[n] = UvcChunkDev{ 2 * p0, 2 * (p1 - p0), s0, PK_COUNT(w1) - s0 }; }
+        n++; p0 = p1;
+    }
+    if (lane == 0) { hdr[0] = n; hdr[1] = -1; hdr[2] = 0; }
+}
+
+// Row set of one chunk of a streamed score (two per stream): [record counts 2 x int64][counters][tile states of the keep scan] -- zeroed in
+// front of every chunk -- then the rows, the records and (kept_only) their compacted copy.  c = chunk_records, gc = min(groups of the
+// request, c): a chunk cannot have more active groups than records, nor than the request has groups.
+struct SetLayout { size_t zero_bytes, cnt, status2, grp, tot, rh, al, al64, mid, d4, keptoff, fields, kept, total; };
+static SetLayout set_layout(int64_t c_, int64_t gc_, int with_kept) {
+    const size_t c = (size_t)(c_ > 0 ? c_ : 1), gc = (size_t)(gc_ > 0 ? (gc_ < c_ ? gc_ : c_) : 1);
+    SetLayout L; size_t o = 16;
+    L.cnt = o; o += NCNT * 4;
+    L.status2 = o; o += ((gc + GS_TILE - 1) / GS_TILE + 1) * 8;
+    o = align16(o); L.zero_bytes = o;
+    L.grp = o; o = align16(o + (size_t)NGR * gc * 4);
+    L.tot = o; o = align16(o + (size_t)NTOT * gc * 8);
+    L.rh = o; o = align16(o + (size_t)NRH * c * 4);
+    L.al = o; o = align16(o + (size_t)NAL32 * c * 4);
+    L.al64 = o; o = align16(o + (size_t)NAL64 * c * 8);
+    L.mid = o; o = align16(o + (size_t)NMID * c * 8);
+    L.d4 = o; o = align16(o + (size_t)NDP4 * 2 * c * 8);
+    L.keptoff = o; o = align16(o + gc * 4);
+    L.fields = o; o = align16(o + (size_t)UVC_NUM_SCORE_FIELDS * c * 4);
+    L.kept = o; if (with_kept) o = align16(o + (size_t)UVC_NUM_SCORE_FIELDS * c * 4);
+    L.total = o;
+    return L;
+}
+extern "C" size_t uvc_score_set_bytes(int64_t chunk_records, int64_t ngroups, int with_kept) { return set_layout(chunk_records, ngroups, with_kept).total; }
+// device bytes of one row set per unit of chunk_records, at most (group rows as long as record rows, kept copy included; + 1 for the tile states)
+extern "C" size_t uvc_score_set_bytes_per_record(void) {
+    return (size_t)NGR * 4 + (size_t)NTOT * 8 + (size_t)NRH * 4 + (size_t)NAL32 * 4 + (size_t)NAL64 * 8 + (size_t)NMID * 8 + (size_t)NDP4 * 16 + 4 + (size_t)UVC_NUM_SCORE_FIELDS * 8 + 1;
+}
+extern "C" int32_t *uvc_score_set_fields(char *set, int64_t chunk_records, int64_t ngroups, int kept) { const SetLayout L = set_layout(chunk_records, ngroups, 1); return (int32_t *)(set + (kept ? L.kept : L.fields)); }
+// position-sized scratch of a stream: the one-call layout with one-record rows (counters, gate scan states, offsets, active list, force mask,
+// position table), then the cut's header (4 x int64) and the chunk table
+extern "C" size_t uvc_score_stream_pos_bytes(int64_t npos_scored, int64_t tab_cap) { return align16(scratch_layout(npos_scored, 1).total) + 32 + sizeof(UvcChunkDev) * (size_t)(tab_cap > 0 ? tab_cap : 1); }
+extern "C" size_t uvc_score_stream_table_offset(int64_t npos_scored) { return align16(scratch_layout(npos_scored, 1).total); }
+
+// what every launch of one score request shares: the context, and the position-sized part of the scratch
+struct ScoreSetup { ScoreCtx C; Stage S; long long npos_scored, ngroups; };
+static ScoreSetup score_setup(const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
+                              const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const ScratchLayout &L,
+                              const void *d_ranges, int64_t n_ranges, int64_t n_compact) {
+    ScoreSetup U; ScoreCtx &C = U.C; Stage &S = U.S;
+    S = Stage{};
     C.pos_beg = req->pos_beg; C.pos_end = req->pos_end;
     if (d_ranges) { C.pos_beg = 0; C.pos_end = (int)n_compact; }   // the compact axis; scratch is sized by it (npos_scored below)
     C.zpos_tab = nullptr; C.ranges = (const UvcScoreRangeDev *)d_ranges; C.n_ranges = (int)n_ranges;
     C.all_out = (req->all_out || P->should_output_all) ? 1 : 0; C.is_amplicon = req->is_amplicon; C.base_at_beg = req->base_at_pos_beg ? 1 : 0;
-    C.alleles = d_alleles; C.allele_rows = d_allele_rows; C.n_alleles = n_alleles; C.gap_rows = d_gap_rows; C.gap_seq = d_gap_seq; C.tkeys = d_tkeys; C.n_tkeys = (d_tkeys ? req->n_tumor_keys : 0); C.fields = d_fields; C.capacity = capacity;
-    const long long npos_scored = C.pos_end - C.pos_beg, ngroups = 2LL * npos_scored;
-    if (ngroups <= 0) return 0;
-    const ScratchLayout L = scratch_layout(npos_scored, capacity);
-    long long *d_count = (long long *)scratch;
-    Stage S;
+    C.alleles = d_alleles; C.allele_rows = d_allele_rows; C.n_alleles = n_alleles; C.gap_rows = d_gap_rows; C.gap_seq = d_gap_seq; C.tkeys = d_tkeys; C.n_tkeys = (d_tkeys ? req->n_tumor_keys : 0);
+    C.fields = nullptr; C.capacity = 0; C.force_mask = nullptr;
+    U.npos_scored = C.pos_end - C.pos_beg; U.ngroups = 2LL * U.npos_scored;
     S.cnt = (unsigned int *)(scratch + L.cnt); S.status1 = (unsigned long long *)(scratch + L.status1); S.status2 = (unsigned long long *)(scratch + L.status2);
     C.offsets = (long long *)(scratch + L.offsets); C.active = (int *)(scratch + L.active);
-    S.grp = (int32_t *)(scratch + L.grp); S.tot = (long long *)(scratch + L.tot); S.rh = (int32_t *)(scratch + L.rh); S.al = (int32_t *)(scratch + L.al); S.al64 = (long long *)(scratch + L.al64);
-    S.mid = (double *)(scratch + L.mid); S.d4 = (double *)(scratch + L.d4); S.keptoff = (int32_t *)(scratch + L.keptoff); S.cap = capacity;
-    if (d_ranges) {
+    S.win_g = 0; S.win_n = U.ngroups;
+    return U;
+}
+// k_range_map, k_force_mask, k_gate_scan over the whole request: offsets, the active list, the total (d_count[0])
+static int launch_gate(ScoreSetup &U, const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, char *scratch, const ScratchLayout &L, const int32_t *d_force_sites, long long *d_count, hipStream_t s) {
+    ScoreCtx &C = U.C; const long long npos_scored = U.npos_scored, ngroups = U.ngroups;
+    if (C.ranges) {
         int *tab = (int *)(scratch + L.zpos_tab);
         hipLaunchKernelGGL(k_range_map, dim3((unsigned)((npos_scored + 255) / 256)), dim3(256), 0, s, C.ranges, C.n_ranges, (int)npos_scored, tab);
         C.zpos_tab = tab;
     }
-    C.force_mask = nullptr;
     if (d_force_sites && req->n_force_sites > 0 && !C.all_out) {   // (under -A every group is selected already)
         unsigned *mask = (unsigned *)(scratch + L.force_mask);
         if (hipMemsetAsync(mask, 0, force_mask_words(npos_scored) * 4, s) != hipSuccess) return UVCGPU_EDEVICE;
@@ -1747,9 +1833,12 @@ extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const Uv
         C.force_mask = mask;
     }
     const unsigned ntiles = (unsigned)((ngroups + GATE_TILE - 1) / GATE_TILE);
-    hipLaunchKernelGGL(k_gate_scan, dim3(ntiles), dim3(GS_BLOCK), 0, s, *R, *P, C, S, d_count);
-    // every kernel below works on a list whose length lives on the device: grids cover what the rows can hold, the threads beyond the length leave
-    const long long max_groups = (ngroups < capacity ? ngroups : capacity), max_recs = capacity;
+    hipLaunchKernelGGL(k_gate_scan, dim3(ntiles), dim3(GS_BLOCK), 0, s, *R, *P, C, U.S, d_count);
+    return 0;
+}
+// the per-record kernels over the window of S (the whole list, or one chunk): grids cover what the rows can hold, the threads beyond the
+// length -- which lives on the device -- leave
+static void launch_records(const RegionDev *R, const UvcParams *P, const ScoreCtx &C, const Stage &S, long long max_groups, long long max_recs, int32_t *d_fields_kept, long long *d_count, hipStream_t s) {
     hipLaunchKernelGGL(k_enum, dim3((unsigned)((max_groups + 127) / 128)), dim3(128), 0, s, *R, *P, C, S);
     hipLaunchKernelGGL(k_gather, dim3((unsigned)((max_groups + 255) / 256), (NGATHER + GATHER_PLANES - 1) / GATHER_PLANES), dim3(256), 0, s, *R, C, S);
     hipLaunchKernelGGL(k_dpv_pre, dim3((unsigned)((max_recs + 127) / 128)), dim3(128), 0, s, *P, C, S);
@@ -1758,11 +1847,72 @@ extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const Uv
     hipLaunchKernelGGL(k_qual, dim3((unsigned)((max_recs + 127) / 128)), dim3(128), 0, s, *P, C, S);
     hipLaunchKernelGGL(k_call_group, dim3((unsigned)((max_groups + 127) / 128)), dim3(128), 0, s, *P, C, S);
     hipLaunchKernelGGL(k_call_rec, dim3((unsigned)((max_recs + 127) / 128)), dim3(128), 0, s, *P, C, S);
-    if (req->kept_only && d_fields_kept) {
+    if (d_fields_kept) {
         const long long tiles2 = (max_groups + GS_TILE - 1) / GS_TILE;
-        hipLaunchKernelGGL(k_keep_scan, dim3((unsigned)(tiles2 < 1024 ? (tiles2 > 0 ? tiles2 : 1) : 1024)), dim3(GS_BLOCK), 0, s, C, S, ngroups, d_count + 1, R->err);
-        hipLaunchKernelGGL(k_keep_copy, dim3((unsigned)((max_groups * KEEP_LANES + 255) / 256)), dim3(256), 0, s, C, S, ngroups, d_fields_kept);
+        hipLaunchKernelGGL(k_keep_scan, dim3((unsigned)(tiles2 < 1024 ? (tiles2 > 0 ? tiles2 : 1) : 1024)), dim3(GS_BLOCK), 0, s, C, S, d_count + 1, R->err);
+        hipLaunchKernelGGL(k_keep_copy, dim3((unsigned)((max_groups * KEEP_LANES + 255) / 256)), dim3(256), 0, s, C, S, d_fields_kept);
     }
+}
+
+// The caller zeroes the first uvc_score_scratch_zero_bytes of `scratch` on the stream in front of this; the record counts (all records, kept
+// records) are its first two int64.
+extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
+                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity,
+                                char *scratch /* uvc_score_scratch_bytes */, int32_t *d_fields_kept /* kept_only: a second [fields][capacity] array */,
+                                const int32_t *d_force_sites /* device copy of UvcScoreRequest::force_sites, or NULL */,
+                                const void *d_ranges /* uvcgpu_region_score_ranges: device table of UvcScoreRangeDev, or NULL */, int64_t n_ranges, int64_t n_compact, hipStream_t s) {
+    const long long npos0 = (d_ranges ? (long long)n_compact : (long long)req->pos_end - req->pos_beg);
+    if (npos0 <= 0) return 0;
+    const ScratchLayout L = scratch_layout(npos0, capacity);
+    ScoreSetup U = score_setup(P, req, d_alleles, d_allele_rows, n_alleles, d_gap_rows, d_gap_seq, d_tkeys, scratch, L, d_ranges, n_ranges, n_compact);
+    ScoreCtx &C = U.C; Stage &S = U.S;
+    C.fields = d_fields; C.capacity = capacity;
+    long long *d_count = (long long *)scratch;
+    S.grp = (int32_t *)(scratch + L.grp); S.tot = (long long *)(scratch + L.tot); S.rh = (int32_t *)(scratch + L.rh); S.al = (int32_t *)(scratch + L.al); S.al64 = (long long *)(scratch + L.al64);
+    S.mid = (double *)(scratch + L.mid); S.d4 = (double *)(scratch + L.d4); S.keptoff = (int32_t *)(scratch + L.keptoff); S.cap = capacity; S.gcap = capacity;
+    if (const int rc = launch_gate(U, R, P, req, scratch, L, d_force_sites, d_count, s)) return rc;
+    const long long max_groups = (U.ngroups < capacity ? U.ngroups : capacity);
+    launch_records(R, P, C, S, max_groups, capacity, (req->kept_only && d_fields_kept) ? d_fields_kept : nullptr, d_count, s);
+    return 0;
+}
+
+// ---- the streamed form: one gate pass and the cut, then the per-record kernels chunk by chunk ----
+// `scratch` = uvc_score_stream_pos_bytes, its head (uvc_score_scratch_zero_bytes(npos, 1)) zeroed by the caller in front of this.
+extern "C" int uvc_launch_score_gate(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
+                                     const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
+                                     const void *d_ranges, int64_t n_ranges, int64_t n_compact, int64_t chunk_records, int64_t tab_cap, hipStream_t s) {
+    const long long npos0 = (d_ranges ? (long long)n_compact : (long long)req->pos_end - req->pos_beg);
+    if (npos0 <= 0) return 0;
+    const ScratchLayout L = scratch_layout(npos0, 1);
+    ScoreSetup U = score_setup(P, req, d_alleles, d_allele_rows, n_alleles, d_gap_rows, d_gap_seq, d_tkeys, scratch, L, d_ranges, n_ranges, n_compact);
+    if (const int rc = launch_gate(U, R, P, req, scratch, L, d_force_sites, (long long *)scratch, s)) return rc;
+    char *t = scratch + align16(L.total);
+    hipLaunchKernelGGL(k_chunk_cut, dim3(1), dim3(64), 0, s, U.C.offsets, npos0, (long long)chunk_records, (long long *)t, (UvcChunkDev *)(t + 32), (long long)tab_cap);
+    return 0;
+}
+// one chunk: groups [win_g, win_g + win_n) of the request into the row set `set` (uvc_score_set_bytes; its head is zeroed here)
+extern "C" int uvc_launch_score_chunk(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
+                                      const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
+                                      const void *d_ranges, int64_t n_ranges, int64_t n_compact, char *set, int64_t chunk_records, int with_kept,
+                                      int64_t win_g, int64_t win_n, int64_t win_groups /* active groups of the window */, int64_t win_records, hipStream_t s) {
+    const long long npos0 = (d_ranges ? (long long)n_compact : (long long)req->pos_end - req->pos_beg);
+    if (npos0 <= 0) return 0;
+    const ScratchLayout L = scratch_layout(npos0, 1);
+    ScoreSetup U = score_setup(P, req, d_alleles, d_allele_rows, n_alleles, d_gap_rows, d_gap_seq, d_tkeys, scratch, L, d_ranges, n_ranges, n_compact);
+    ScoreCtx &C = U.C; Stage &S = U.S;
+    if (C.ranges) C.zpos_tab = (const int *)(scratch + L.zpos_tab);
+    if (d_force_sites && req->n_force_sites > 0 && !C.all_out) C.force_mask = (const unsigned *)(scratch + L.force_mask);
+    const SetLayout Q = set_layout(chunk_records, U.ngroups, with_kept);
+    if (win_records > chunk_records || win_groups > (long long)std::min<long long>(U.ngroups, chunk_records)) return UVCGPU_EINVAL;   // (the cut never makes such a window)
+    if (hipMemsetAsync(set, 0, Q.zero_bytes, s) != hipSuccess) return UVCGPU_EDEVICE;
+    S.cnt = (unsigned int *)(set + Q.cnt); S.status2 = (unsigned long long *)(set + Q.status2);
+    S.grp = (int32_t *)(set + Q.grp); S.tot = (long long *)(set + Q.tot); S.rh = (int32_t *)(set + Q.rh); S.al = (int32_t *)(set + Q.al); S.al64 = (long long *)(set + Q.al64);
+    S.mid = (double *)(set + Q.mid); S.d4 = (double *)(set + Q.d4); S.keptoff = (int32_t *)(set + Q.keptoff);
+    S.cap = chunk_records; S.gcap = std::min<long long>(std::max<long long>(U.ngroups, 1), chunk_records);
+    S.win_g = win_g; S.win_n = win_n;
+    C.fields = (int32_t *)(set + Q.fields); C.capacity = chunk_records;
+    // grids by the window's own counts (the host has the table): a last, short chunk launches what it needs
+    launch_records(R, P, C, S, std::max<long long>(win_groups, 1), std::max<long long>(win_records, 1), (req->kept_only && with_kept) ? (int32_t *)(set + Q.kept) : nullptr, (long long *)set, s);
     return 0;
 }
 

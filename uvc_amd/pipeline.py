@@ -24,7 +24,7 @@ FILTERS = ["Q10", "Q20", "Q30", "Q40", "Q50", "Q60", "PASS"]
 
 
 def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None, molecule_tag=0, disable_duplex=0, correct_bq=True, all_out=False, keep_handle=False, reuse=None, vcf=False,
-                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0, force_sites=None, pieces=None, single_ranges=False):
+                continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0, force_sites=None, pieces=None, single_ranges=False, score_mem_mb=0):
     """Scores [beg, end) of `chrom`.  Returns None when no read passes the filters (process_batch returns -1, main.cpp:520-523), else a
     dict: records (field -> int32 array), alleles (InDel allele rows), score range, region handle (if keep_handle).
     Tiles of one stretch: the reference scores zerobased_pos rpos_beg .. rpos_end inclusive and skips the BASE sub-position of the first
@@ -43,6 +43,8 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     end, continues, has_next, region_beg: every piece becomes the score range its own tile would have asked for, and all of them are scored
     in one `Region.score_ranges` call with kept_only (`single_ranges`: one `Region.score` call per piece instead -- the same records by
     contract).  Returns records, ranges and, with `vcf`, the text; not with tumor_vcf or force_sites.
+    `score_mem_mb` (uvc1-mi355x --score-mem-mb): > 0 scores the request as a stream of chunks (`Region.score_stream`) whose row sets and
+    page-locked buffers fit that many MiB; the records (joined here) and the text are those of the one call.
     `reuse`: a dict the caller keeps between calls; the region handle lives in it and is reset for every new region instead of being
     created and destroyed (its device buffers survive while the regions do not grow)."""
     import os, time
@@ -107,6 +109,8 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
             parts = [R.score(all_out=all_out, is_amplicon=bool(is_amplicon), pos_beg=a, pos_end=b, base_at_pos_beg=bool(c), region_beg=d, kept_only=True) for a, b, c, d in ranges]
             rec = parts
             text = "".join(R.vcf_records(chrom, r, pos_beg=a, pos_end=b, base_at_pos_beg=bool(c), region_beg=d) for r, (a, b, c, d) in zip(parts, ranges)) if vcf else None
+        elif score_mem_mb > 0:
+            rec, text = _score_streamed(R, chrom, score_mem_mb, vcf, ranges=ranges, all_out=all_out, is_amplicon=bool(is_amplicon), kept_only=True)
         else:
             rec = R.score_ranges(ranges, all_out=all_out, is_amplicon=bool(is_amplicon), kept_only=True)
             text = R.vcf_records_ranges(chrom, rec, ranges) if vcf else None
@@ -136,10 +140,16 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
         else:
             fs = np.asarray(force_sites, dtype=np.int64)
             fs = fs[(fs >= skw["pos_beg"]) & (fs < skw["pos_end"])]
-    rec = R.score(all_out=all_out, is_amplicon=bool(is_amplicon), tumor_keys=tk, force_sites=fs, **skw)
+    text = None
+    if score_mem_mb > 0:
+        rec, text = _score_streamed(R, chrom, score_mem_mb, vcf, text_kw=dict(tumor_keys=tk, tumor_sample_columns=tcols, tumor_ref_alt=tras), all_out=all_out, is_amplicon=bool(is_amplicon), tumor_keys=tk, force_sites=fs, **skw)
+    else:
+        rec = R.score(all_out=all_out, is_amplicon=bool(is_amplicon), tumor_keys=tk, force_sites=fs, **skw)
     lap("bq+accumulate+score")
     out = dict(records=rec, alleles=R.indel_alleles(), rpos=(rpos_beg, rpos_end), ext=(ext_beg, ext_end), n_reads=int(g["n_kept"]), n_fams=int(g["n_fams"]), chrom=chrom, refseq=refseq, score_range=score_range)
-    if vcf:
+    if vcf and text is not None:
+        out["vcf"] = text
+    elif vcf:
         out["vcf"] = R.vcf_records(chrom, rec, tumor_keys=tk, tumor_sample_columns=tcols, tumor_ref_alt=tras, **skw)          # the record lines of append_vcf_record (uvcgpu_region_vcf_records), before the handle moves on
     if keep_handle:
         out["region"] = R
@@ -149,6 +159,23 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
     if timing:
         sys.stderr.write("[pipeline] " + ", ".join("%s %.1f ms" % (b[0], 1e3 * (b[1] - a[1])) for a, b in zip(laps, laps[1:])) + "\n")
     return out
+
+
+def _score_streamed(R, chrom, score_mem_mb, vcf, ranges=None, text_kw=None, **score_kw):
+    """The records and, with `vcf`, the text of one score request through Region.score_stream: chunk by chunk, the text of a chunk written
+    while the next one is scored and copied.  -> (records joined as one call returns them, text or None)."""
+    chunk_records = max(1, (int(score_mem_mb) << 20) // R.score_stream_bytes_per_record())
+    parts, text, off = [], [], 0
+    for rec, covered in R.score_stream(chunk_records, ranges=ranges, **score_kw):
+        if vcf:
+            text.append(R.vcf_records_ranges(chrom, rec, covered, **(text_kw or {})))
+        for f in ("germ_ref", "germ_alt1", "germ_alt2"):                                # chunk-relative record indices -> indices of the joined list
+            rec[f] = np.where(rec[f] >= 0, rec[f] + off, rec[f])
+        off += len(rec["refpos"])
+        parts.append(rec)
+    if not parts:
+        parts = [{name: np.zeros(0, np.int32) for name in _ffi.SCORE_FIELDS}]
+    return {f: np.concatenate([q[f] for q in parts]) for f in parts[0]}, ("".join(text) if vcf else None)
 
 
 def contig_tiles(beg, end, tile):

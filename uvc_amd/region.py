@@ -434,6 +434,43 @@ class Region:
             self._check(rc)
             return {name: (buf[i, :out.n_records].copy() if copy else buf[i, :out.n_records]) for i, name in enumerate(_ffi.SCORE_FIELDS)}
 
+    def score_stream(self, chunk_records, ranges=None, copy=True, all_out=False, pos_beg=-1, pos_end=-1, is_amplicon=False, indel_alleles=None, tumor_keys=None, release_state=False,
+                     base_at_pos_beg=False, region_beg=0, kept_only=False, force_sites=None):
+        """The records of score(...) -- or, with `ranges`, of score_ranges(ranges, ...) -- in bounded memory (uvcgpu_region_score_stream_begin /
+        uvcgpu_score_stream_next / uvcgpu_score_stream_end): a generator of (records, covered_ranges), one pair per chunk of at most
+        `chunk_records` records.  A chunk is a run of whole positions; its records are those of score_ranges(covered_ranges) and
+        vcf_records_ranges(contig, records, covered_ranges) is its text; the chunks' records and texts concatenate to the one call's (germ_ref /
+        germ_alt1 / germ_alt2 count from the chunk's first record).  copy=False yields views into the stream's page-locked buffer, valid until
+        the generator is advanced.  Closing the generator early ends the stream."""
+        begin = self._ranges_fn("region_score_stream_begin", C.c_int, [C.c_void_p, C.POINTER(_ffi.UvcScoreRequest), C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)])
+        nxt = self._ranges_fn("score_stream_next", C.c_int, [C.c_void_p, C.POINTER(_ffi.UvcScoreOut), C.c_void_p, C.POINTER(C.c_int64)])
+        end = self._ranges_fn("score_stream_end", C.c_int, [C.c_void_p])
+        if ranges is not None:
+            pos_beg, pos_end, base_at_pos_beg, region_beg = -1, -1, False, 0
+        req, _keep = self.make_request(all_out, pos_beg, pos_end, is_amplicon, indel_alleles, tumor_keys, release_state, base_at_pos_beg, region_beg, kept_only=kept_only, force_sites=force_sites)
+        arr, n = self.make_ranges(ranges) if ranges is not None else (None, 0)
+        h = C.c_void_p()
+        self._check(begin(self.h, C.byref(req), arr, n, int(chunk_records), C.byref(h)))
+        try:
+            covered = (_ffi.UvcScoreRange * max(n, 1))()
+            while True:
+                out, nc = _ffi.UvcScoreOut(), C.c_int64(0)
+                rc = nxt(h, C.byref(out), covered, C.byref(nc))
+                if rc == _ffi.ENUMS["UVCGPU_STREAM_END"]:
+                    break
+                self._check(rc)
+                buf = np.ctypeslib.as_array((C.c_int32 * (_ffi.NUM_SCORE_FIELDS * out.capacity)).from_address(out.fields)).reshape(_ffi.NUM_SCORE_FIELDS, out.capacity)
+                rec = {name: (buf[i, :out.n_records].copy() if copy else buf[i, :out.n_records]) for i, name in enumerate(_ffi.SCORE_FIELDS)}
+                yield rec, [(q.pos_beg, q.pos_end, q.base_at_pos_beg, q.region_beg) for q in covered[:nc.value]]
+        finally:
+            end(h)
+
+    def score_stream_bytes_per_record(self):
+        return self._ranges_fn("score_stream_bytes_per_record", C.c_int64, [])()
+
+    def score_stream_footprint(self):
+        return self._ranges_fn("score_stream_footprint", C.c_int64, [C.c_void_p])(self.h)
+
     def vcf_records_ranges(self, contig_name, records, ranges, tumor_keys=None, tumor_sample_columns=None, tumor_ref_alt=None):
         """uvcgpu_region_vcf_records_ranges: the text of the records score_ranges(ranges) returned = the single-range texts one after another."""
         fn = self._ranges_fn("region_vcf_records_ranges", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(_ffi.UvcScoreOut), C.POINTER(_ffi.UvcScoreRequest), C.c_void_p, C.c_int64,
