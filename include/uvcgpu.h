@@ -465,6 +465,25 @@ int uvcgpu_score_stream_next(uvcgpu_score_stream_t *s, UvcScoreOut *chunk, UvcSc
 int uvcgpu_score_stream_end(uvcgpu_score_stream_t *s);
 int64_t uvcgpu_score_stream_bytes_per_record(void);
 int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r);
+/* ---- depth statistics of ranges of the accumulated region (the per-target coverage report) ----
+ * The measures (rows of include/uvc_coverage.def, in this order): per position the raw segment depth, the fragment depth, the de-duplicated
+ * family depth, the BQ-filtered family depth, the families large enough for a single-strand consensus, the duplex families -- each of the
+ * BASE symbol type, summed over both strands and the six BASE symbols where the plane has them. */
+enum UvcCoverageMeasure { UVC_COV_aDP = 0, UVC_COV_bDP, UVC_COV_cDP1, UVC_COV_cDP12, UVC_COV_cDP2, UVC_COV_dDP1, UVC_NCOV };
+enum { UVC_COV_SUM = 0, UVC_COV_MIN = 1, UVC_COV_MAX = 2, UVC_COV_GE = 3 /* .. + 7 */, UVC_COV_MAX_THRESHOLDS = 8, UVC_COV_ROW = 11 /* 3 + 8 */ };
+typedef struct UvcCoverageRange { int32_t pos_beg, pos_end; } UvcCoverageRange;   /* zero-based, half open, inside the region [beg, end + 1) */
+/* One row of UVC_NCOV x UVC_COV_ROW int64 per range: for every measure the sum, the minimum and the maximum of its per-position values over
+ * the range and, for threshold k, the number of positions whose value is >= thresholds[k]; the slots of unused thresholds are 0.  The
+ * planes are reduced on the device (one pass, every needed cell read once); nothing per position travels to the host.
+ *   Legal after uvcgpu_region_accumulate and before the planes are released (a score with release_state comes after it); called before
+ *   accumulate, after such a score or while a score stream is open it returns UVCGPU_EINVAL with a message and computes nothing.
+ *   UVCGPU_EINVAL before any launch, the message naming the range: a range that is empty, outside the region, or begins in front of its
+ *   predecessor's end (ranges are sorted and disjoint; neighbours may share an end point); n_ranges < 1; n_thresholds outside 0..8; a
+ *   negative threshold or one that is not larger than the one before it.  `out` is written only by a call that returns 0. */
+int uvcgpu_region_coverage(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges,
+                           const int32_t *thresholds, int32_t n_thresholds /* 0..8, ascending */,
+                           int64_t *out /* [n_ranges][UVC_NCOV][UVC_COV_ROW] */);
+const char *uvcgpu_coverage_measure_name(int32_t id);   /* "aDP" .. "dDP1"; NULL for an id outside 0..UVC_NCOV - 1 */
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);

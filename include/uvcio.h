@@ -164,6 +164,21 @@ int uvcio_plan_shards(const int64_t *cost, int64_t n, int32_t n_shards, int32_t 
 typedef struct UvcBedPiece { int64_t line, batch, beg, end; } UvcBedPiece;
 int uvcio_plan_bed_batches(const int32_t *tid, const int64_t *beg, const int64_t *end, int64_t n_lines, int64_t merge_distance, int64_t max_span,
                            UvcBedPiece *out, int64_t capacity, int64_t *n_pieces);
+/* ---- the per-target coverage report (uvc1-mi355x --coverage-out) ----
+ * A table of targets (BED lines or fixed windows) and, per target, the merged statistics of the pieces that tiles report for it.  A row
+ * of statistics is what uvcgpu_region_coverage returns for one range: n_measures x 11 int64, per measure sum, min, max and 8 threshold
+ * counts (only the first n_thresholds are kept).  Pieces of one target are disjoint stretches of it; they merge by sum +, min, max,
+ * counts +, in any order and from any thread (add_piece locks).  Positions of a target that no piece covers count as depth 0: they pull
+ * the minimum to 0 and count for a threshold of 0.  A target without any piece is a row of zeros.
+ * write: "#chrom beg end name len" and, per measure, <measure>_sum _min _max _ge<T>..., tab-separated, one line per target in the order of
+ * add_target, integers only; a path that ends in .gz is written block-gzipped (uvcio_bgzf_write_*). */
+typedef struct uvcio_coverage uvcio_coverage_t;
+int uvcio_coverage_open(uvcio_coverage_t **out, const char *const *measure_names, int32_t n_measures, const int32_t *thresholds, int32_t n_thresholds /* 0..8 */);
+/* beg / end: as printed (the BED line's own numbers); len: the positions of the target inside its contig.  Returns the target's index, or a negative code. */
+int64_t uvcio_coverage_add_target(uvcio_coverage_t *c, const char *chrom, int64_t beg, int64_t end, const char *name /* NULL = "." */, int64_t len);
+int uvcio_coverage_add_piece(uvcio_coverage_t *c, int64_t target, int64_t piece_len, const int64_t *row /* [n_measures][11] */);
+int uvcio_coverage_write(const uvcio_coverage_t *c, const char *path);
+void uvcio_coverage_close(uvcio_coverage_t *c);
 /* bcftools concat -n (uvcTN.sh:100): the BGZF files one after the other, the 28-byte end-of-file marker of all but the last dropped. */
 int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in);
 /* The whole text of a (block-)gzipped or plain file (the tumor VCF of a T/N pair); *buf is malloc'ed, the caller frees it. */

@@ -75,6 +75,10 @@ class UvcScoreRange(C.Structure):
     _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("base_at_pos_beg", C.c_int32), ("region_beg", C.c_int32)]
 
 
+class UvcCoverageRange(C.Structure):
+    _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32)]
+
+
 class UvcScoreOut(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n_records", C.c_int64), ("fields", C.c_void_p)]
 
@@ -123,6 +127,9 @@ FIELD_GROUPS = {
 }
 SCORE_FIELDS = [k[len("UVC_O_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_O_")), key=lambda kv: kv[1])]
 NUM_SCORE_FIELDS = ENUMS["UVC_NUM_SCORE_FIELDS"]
+# the depth measures of uvcgpu_region_coverage in id order (UvcCoverageMeasure; the rows of include/uvc_coverage.def)
+COVERAGE_MEASURES = [k[len("UVC_COV_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_COV_") and k[len("UVC_COV_"):] not in ("SUM", "MIN", "MAX", "GE", "MAX_THRESHOLDS", "ROW")), key=lambda kv: kv[1])]
+assert len(COVERAGE_MEASURES) == ENUMS["UVC_NCOV"]
 
 
 class Lib:

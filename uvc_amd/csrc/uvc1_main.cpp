@@ -47,6 +47,10 @@ struct Opts {
     int64_t mem_per_thread = 1536;   // --mem-per-thread (MB), CmdLineArgs.hpp:33: enters the reference's region cuts
     int64_t merge = 0;           // --merge-regions N: BED lines at most N bp apart become ranges of one device region (0 = one region per line)
     int64_t score_mem_mb = 0;    // --score-mem-mb N: score every tile as a stream of chunks whose row sets and record buffers fit N MiB per worker (0 = one call per tile)
+    std::string coverage_out;    // --coverage-out PATH: the per-target depth report; empty = none
+    std::vector<int32_t> coverage_thr{ 1, 20, 100, 500 }; bool coverage_thr_given = false;   // --coverage-thresholds
+    int64_t coverage_window = 0; // --coverage-window N: the targets are windows of N bp (0: the BED lines)
+    uvcio_coverage_t *cov = nullptr;   // the report's store, filled by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -91,6 +95,9 @@ const OptRow OPTS[] = {
     { "--shard", O_CLI, false, "0/1", "i/n: this process takes the i-th of n runs of tiles" },
     { "--no-header", O_CLI, true, "", "no VCF header" },
     { "--score-mem-mb", O_CLI, false, "0", "score every tile in chunks whose device rows and page-locked record buffers take at most this many MiB per worker (-t), chunk k + 1 computed and copied while chunk k is written; 0: one score call per tile, sized by all its records (14 per position under -A).  The output does not depend on it" },
+    { "--coverage-out", O_CLI, false, "", "write the per-target coverage report here (tab-separated; block-gzipped when the name ends in .gz): per BED line, or per --coverage-window, sum / min / max and positions at or above each threshold of six depths the caller itself works with (aDP raw segments, bDP fragments, cDP1 families, cDP12 BQ-filtered families, cDP2 single-strand-consensus families, dDP1 duplex families), reduced on the device from the planes of each tile.  The VCF does not depend on it" },
+    { "--coverage-thresholds", O_CLI, false, "1,20,100,500", "with --coverage-out: at most 8 ascending depths; the report counts the positions at or above each" },
+    { "--coverage-window", O_CLI, false, "0", "with --coverage-out and no BED file: the targets are windows of this many bp, aligned to multiples of it on each contig and clipped to the called span" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -238,6 +245,20 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
         else if (n0 == "--merge-regions") { const std::string v = val(); double x; if (!number(v, &x) || x < 0 || x != (double)(int64_t)x || x > 2e9) die("--merge-regions takes a distance in bp (0 = off), not '" + v + "'"); o.merge = (int64_t)x; }
         else if (n0 == "--score-mem-mb") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1e9) die("--score-mem-mb takes a size in MiB (0 = off), not '" + v + "'"); o.score_mem_mb = (int64_t)x; }
+        else if (n0 == "--coverage-out") { o.coverage_out = val(); if (o.coverage_out.empty()) die("--coverage-out needs a path"); }
+        else if (n0 == "--coverage-thresholds") {   // a,b,c: whole decimal numbers, ascending, at most 8
+            const std::string v = val(); o.coverage_thr.clear(); o.coverage_thr_given = true;
+            for (size_t at = 0; at <= v.size();) {
+                size_t c = v.find(',', at); if (c == std::string::npos) c = v.size();
+                const std::string item = v.substr(at, c - at); double x;
+                if (item == "true" || item == "false" || !number(item, &x) || x < 0 || x != (double)(int64_t)x || x > 2e9) die("--coverage-thresholds takes up to 8 ascending depths such as 1,20,100,500, not '" + v + "' ('" + item + "' is not a depth)");
+                if (!o.coverage_thr.empty() && (int32_t)x <= o.coverage_thr.back()) die("--coverage-thresholds must ascend: '" + v + "' has " + item + " behind " + std::to_string(o.coverage_thr.back()));
+                o.coverage_thr.push_back((int32_t)x);
+                if (o.coverage_thr.size() > (size_t)UVC_COV_MAX_THRESHOLDS) die("--coverage-thresholds takes at most " + std::to_string((int)UVC_COV_MAX_THRESHOLDS) + " depths, not '" + v + "'");
+                at = c + 1;
+            }
+        }
+        else if (n0 == "--coverage-window") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--coverage-window takes a window length in bp, not '" + v + "'"); o.coverage_window = (int64_t)x; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -279,6 +300,17 @@ Opts parse(int argc, char **argv) {
         if (!o.tumor_vcf.empty()) die("--force-sites cannot go with --tumor-vcf: the normal sample's gate is the tumor's rescue set");
         if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--force-sites cannot go with ") + ONLY_PRINT_VCF_HEADER + ": there are no records to force");
     }
+    if (o.coverage_out.empty()) {   // before any file or device
+        if (o.coverage_thr_given) die("--coverage-thresholds needs --coverage-out: it only shapes that report");
+        if (o.coverage_window > 0) die("--coverage-window needs --coverage-out: it only shapes that report");
+    } else {
+        const bool has_bed = (!o.bed.empty() || !o.bed_in.empty());
+        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--coverage-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
+        if (o.n_shards > 1) die("--coverage-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": a target can straddle shards, and --concat joins VCFs only");
+        if (o.repeat != 1) die("--coverage-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
+        if (has_bed && o.coverage_window > 0) die("--coverage-window cannot go with -R / --bed-in-fname: with a BED file the targets of --coverage-out are its lines");
+        if (!has_bed && o.coverage_window <= 0) die("--coverage-out needs --coverage-window N without -R / --bed-in-fname: there are no BED lines to report on");
+    }
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -303,7 +335,8 @@ void print_params(const Opts &o, const char *prefix = "") {
 // the first (main.cpp:608, 643): adjacent regions both write the LINK records of their shared end point.  Here a tile owns the positions
 // [beg, end): `continues` (a tile ends where this one begins) = it scores `beg` completely, `has_next` = it leaves `end` to the next one.
 // `run_beg` = begin of the run (incluBegPosition of the BED line the run came from, main.cpp:655-656).
-struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; };
+// `target` (--coverage-out with a BED file): the report row of the BED line the tile was cut from.
+struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; };
 
 // one worker: its own handles, one region handle for all of its tiles
 struct Worker {
@@ -316,7 +349,33 @@ struct Worker {
     int64_t n_tiles = 0, score_cap = 0, text_cap = 0;   // what the last tiles needed: the next call asks for it at once
     int64_t n_chunks = 0, n_streamed = 0;               // --score-mem-mb: chunks in all, tiles scored as streams
     std::vector<UvcScoreRange> covered;
+    std::vector<UvcCoverageRange> cov_ranges; std::vector<int64_t> cov_targets, cov_rows;   // --coverage-out: the pieces of one tile
 };
+
+// --coverage-out: the pieces of targets that one accumulated tile owns, reduced by one uvcgpu_region_coverage and merged into the report.
+// `own`: the stretches the tile owns (ascending, disjoint); `target_of` >= 0: all of a stretch belongs to that row (a BED line); else the
+// rows are windows of o.coverage_window bp and a stretch is cut at their multiples.
+struct CovSpan { int64_t first = -1, origin = 0; };   // window mode, per contig: the row of the called span's first window, the span's begin
+void coverage_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of, const CovSpan *span) {
+    w.cov_ranges.clear(); w.cov_targets.clear();
+    const int64_t N = o.coverage_window;
+    for (size_t q = 0; q < own.size(); q++) {
+        int64_t b = own[q].first; const int64_t e = own[q].second;
+        if (e <= b) continue;
+        if (target_of[q] >= 0) { w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.cov_targets.push_back(target_of[q]); continue; }
+        if (!span || span->first < 0) die("--coverage-out: a tile outside the planned windows (internal error)");
+        while (b < e) {
+            const int64_t stop = std::min(e, (b / N + 1) * N);
+            w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)stop }); w.cov_targets.push_back(span->first + (b / N - span->origin / N));
+            b = stop;
+        }
+    }
+    if (w.cov_ranges.empty()) return;
+    w.cov_rows.resize(w.cov_ranges.size() * (size_t)UVC_NCOV * UVC_COV_ROW);
+    if (uvcgpu_region_coverage(w.reg, w.cov_ranges.data(), (int64_t)w.cov_ranges.size(), o.coverage_thr.data(), (int32_t)o.coverage_thr.size(), w.cov_rows.data())) die(uvcgpu_last_error());
+    for (size_t q = 0; q < w.cov_ranges.size(); q++)
+        if (uvcio_coverage_add_piece(o.cov, w.cov_targets[q], (int64_t)w.cov_ranges[q].pos_end - w.cov_ranges[q].pos_beg, &w.cov_rows[q * (size_t)UVC_NCOV * UVC_COV_ROW])) die(uvcio_last_error());
+}
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // process_batch for one tile; appends the record lines to `lines`; false = nothing to call there.  *n_kept_reads: reads that passed the filters.
@@ -326,7 +385,7 @@ double now() { return std::chrono::duration<double>(std::chrono::steady_clock::n
 // its own tile would have asked for; one uvcgpu_region_score_ranges, one uvcgpu_region_vcf_records_ranges.  n_kept_reads then has n_merged
 // entries: the kept alignments that overlap each line.  n_merged = 0: the plain call of one tile.
 bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads,
-               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr, size_t n_merged = 0) {
+               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr, size_t n_merged = 0, const CovSpan *cov_span = nullptr) {
     double t0 = now();
     for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) n_kept_reads[q] = 0;
     Tile t = t0_;
@@ -393,6 +452,18 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (uvcgpu_region_set_reads(w.reg, &rs)) die(uvcgpu_last_error());
     w.t_reads += now() - t0; t0 = now();
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
+    if (o.cov) {   // --coverage-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
+                   // point t.end itself, which lies outside every target the tile was cut from (and which two regions of the reference's cuts share)
+        std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of;
+        if (n_merged == 0) { own.emplace_back(first, std::min(last_excl, t.end)); target_of.push_back(t.target); }
+        else for (size_t q = 0; q < n_merged; q++) {
+            const Tile &l = (&t0_)[q];
+            const int64_t l_first = std::max(l.beg, bam_beg);
+            const int64_t l_excl = l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end);
+            own.emplace_back(l_first, std::min(l_excl, l.end)); target_of.push_back(l.target);
+        }
+        coverage_of_tile(w, o, own, target_of, cov_span);
+    }
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
     rq.is_amplicon = (o.assay_type == 0 ? (go.n_amplicon * 2 > k) : (o.assay_type == 2));   // inferred_assay_type, main.cpp:510-511
@@ -510,7 +581,9 @@ void link_runs(std::vector<Tile> &tiles) {
 // the tiles: --bed-in-fname / -R regions, --targets "chr" or "chr:beg-end" (1-based inclusive as in samtools), else every contig
 // `batch_of` (--merge-regions): the batch of every tile, from uvcio_plan_bed_batches over the BED lines; consecutive tiles of one batch
 // are called as the ranges of one device region
-std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr) {
+// --coverage-out: the report's rows are added here in target order -- the BED lines in file order (every tile carries its line's row), or
+// the windows of every called span (cov_spans: per contig the row of the span's first window)
+std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr, std::vector<CovSpan> *cov_spans = nullptr) {
     const std::vector<std::string> &names = G.names; const std::vector<int64_t> &lens = G.lens; const int32_t nref = (int32_t)names.size();
     std::vector<Tile> tiles;
     const std::string bed_path = (!o.bed_in.empty() ? o.bed_in : o.bed);
@@ -527,8 +600,21 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     if (ref_cuts && uvcio_planner_open(&planner, lens.data(), nref, (o.threads > 0 ? o.threads : 8) /* the reference's -t default (CmdLineArgs.hpp:34): enters only where a batch of regions ends */, o.mem_per_thread)) die(uvcio_last_error());
     std::vector<int32_t> pl_tid, pl_pos, pl_end; std::vector<uint16_t> pl_flag;   // one window's columns
     auto take_cuts = [&]() { UvcRegionCut c[256]; int64_t k; while ((k = uvcio_planner_take(planner, c, 256)) > 0) for (int64_t q = 0; q < k; q++) tiles.push_back(Tile{ c[q].tid, names[(size_t)c[q].tid], c[q].beg, c[q].end, false, false, c[q].beg }); };
+    int64_t cov_target = -1;   // the report row of the BED line being added
     auto add = [&](int32_t tid, int64_t beg, int64_t end) {
-        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b }); return; }
+        if (o.cov && cov_spans && o.coverage_window > 0 && end > beg) {   // the windows of this span: aligned to multiples of N, clipped to it
+            const int64_t N = o.coverage_window;
+            CovSpan &sp = (*cov_spans)[(size_t)tid];
+            if (sp.first >= 0) die("--coverage-window: a contig is called twice (internal error)");
+            sp.origin = beg;
+            for (int64_t k = beg / N; k * N < end; k++) {
+                const int64_t wb = std::max(k * N, beg), we = std::min((k + 1) * N, end);
+                const int64_t row = uvcio_coverage_add_target(o.cov, names[(size_t)tid].c_str(), wb, we, nullptr, we - wb);
+                if (row < 0) die(uvcio_last_error());
+                if (sp.first < 0) sp.first = row;
+            }
+        }
+        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target }); return; }
         const int64_t W = 4000000;   // the planning pass reads the span window by window; an alignment is taken by the window it starts in (the first window also takes those that reach into it)
         for (int64_t wb = beg; wb < end; wb += W) {
             UvcBamBatch b;
@@ -543,14 +629,24 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     if (!bed_path.empty()) {   // one region per BED line (0-based, half-open), cut into tiles; overrides --targets as in the reference
         FILE *fb = fopen(bed_path.c_str(), "r");
         if (!fb) die("cannot open " + bed_path);
-        char line[4096], chrom[1024]; long long b = 0, e = 0;
+        char line[4096], chrom[1024], bname[1024]; long long b = 0, e = 0;
         std::vector<int32_t> l_tid; std::vector<int64_t> l_beg, l_end;   // the lines as `add` sees them
         while (fgets(line, sizeof(line), fb)) {
             if (line[0] == '#' || !strncmp(line, "track", 5) || !strncmp(line, "browser", 7)) continue;
-            if (sscanf(line, "%1023s %lld %lld", chrom, &b, &e) != 3) continue;
+            int n_col = sscanf(line, "%1023s %lld %lld %1023s", chrom, &b, &e, bname);
+            if (n_col < 3) continue;
+            if (strchr(line, '\t')) {   // a tab-separated file: column 4 is everything up to the next tab, blanks included
+                const char *p = line; for (int c = 0; c < 3 && p; c++) { p = strchr(p, '\t'); if (p) p++; }
+                const size_t len = p ? std::min<size_t>(strcspn(p, "\t\r\n"), sizeof(bname) - 1) : 0;
+                if (len > 0) { memcpy(bname, p, len); bname[len] = 0; n_col = 4; } else n_col = 3;
+            }
             int32_t tid = -1;
             for (int32_t i = 0; i < nref; i++) if (names[(size_t)i] == chrom) tid = i;
             if (tid < 0) die(std::string("the BED file names a contig that is not in the BAM header: ") + chrom);
+            if (o.cov) {   // one report row per BED line: its own numbers, column 4 as the name, the positions inside the contig as the length
+                cov_target = uvcio_coverage_add_target(o.cov, chrom, b, e, n_col >= 4 ? bname : nullptr, std::max<long long>(0, std::min<long long>(e, lens[(size_t)tid]) - std::max<long long>(0, b)));
+                if (cov_target < 0) die(uvcio_last_error());
+            }
             add(tid, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]));
             l_tid.push_back(tid); l_beg.push_back(std::max<long long>(0, b)); l_end.push_back(std::min<long long>(e, lens[(size_t)tid]));
         }
@@ -698,6 +794,7 @@ PairArgs split_pair(int argc, char **argv) {
         const std::string name = t.substr(0, t.compare(0, 2, "--") == 0 ? t.find('=') : std::string::npos);
         if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
+        if (name == "--coverage-out" || name == "--coverage-thresholds" || name == "--coverage-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no coverage report");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
             die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
@@ -960,7 +1057,12 @@ int main(int argc, char **argv) {
     uvcio_bam_t *bam0 = open_bam(o.bam, G);
     const int32_t nref = (int32_t)G.names.size();
     std::vector<int64_t> batch_of;   // --merge-regions: the batch of every tile (else empty: every tile is its own job)
-    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of);
+    std::vector<CovSpan> cov_spans((size_t)nref);
+    if (!o.coverage_out.empty() && !o.print_params) {
+        const char *mnames[UVC_NCOV]; for (int32_t m = 0; m < UVC_NCOV; m++) mnames[m] = uvcgpu_coverage_measure_name(m);
+        if (uvcio_coverage_open(&o.cov, mnames, UVC_NCOV, o.coverage_thr.data(), (int32_t)o.coverage_thr.size())) die(uvcio_last_error());
+    }
+    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans);
     if (o.n_shards > 1) {
         std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
         if (!batch_of.empty()) {   // balanced over batches: a batch is one region and goes to one shard, at the sum of its tiles' costs
@@ -1009,6 +1111,11 @@ int main(int argc, char **argv) {
     // output: header, then the lines of every tile in tile order
     uvcio_bgzf_writer_t *zw = nullptr;
     if (uvcio_bgzf_write_open(&zw, o.out.c_str(), 6)) die(uvcio_last_error());
+    if (o.cov) {   // a path that cannot be written fails here, not behind the last tile
+        FILE *probe = fopen(o.coverage_out.c_str(), "wb");
+        if (!probe) die("--coverage-out: cannot create " + o.coverage_out);
+        fclose(probe);
+    }
     if (!o.no_header) {
         const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
@@ -1033,7 +1140,7 @@ int main(int argc, char **argv) {
             // 4 * threads in front of it, so a slow early tile cannot make the rest of the genome pile up in memory
             { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ji < written + max_ahead; }); }
             std::string lines; std::vector<int64_t> nk(nt, 0);
-            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0);
+            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0, &cov_spans[(size_t)tiles[ti].tid]);
             w.n_tiles++;
             { std::lock_guard<std::mutex> g(mu); done[ji].swap(lines); ready[ji] = 1; for (size_t q = 0; q < nt; q++) tile_reads[ti + q] = nk[q]; }
             cv.notify_all();
@@ -1053,6 +1160,10 @@ int main(int argc, char **argv) {
     }
     for (auto &t : th) t.join();
     if (uvcio_bgzf_write_close(zw)) die(uvcio_last_error());
+    if (o.cov) {   // every tile has reported: the rows in target order, whichever worker finished first
+        if (uvcio_coverage_write(o.cov, o.coverage_out.c_str())) die("--coverage-out: " + std::string(uvcio_last_error()));
+        uvcio_coverage_close(o.cov);
+    }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

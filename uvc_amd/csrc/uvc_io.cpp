@@ -1207,3 +1207,82 @@ extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t po
     return 0;
 }
 extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }
+
+// ---------------------------------------------------------------- the per-target coverage report ----
+struct uvcio_coverage {
+    std::vector<std::string> measures; std::vector<int32_t> thr;
+    struct Target { std::string chrom, name; int64_t beg, end, len, covered; };
+    std::vector<Target> targets;
+    std::vector<int64_t> rows;   // [target][measure][3 + n_thr]: sum, min, max, counts
+    std::mutex mu;
+    size_t width() const { return measures.size() * (3 + thr.size()); }
+};
+extern "C" int uvcio_coverage_open(uvcio_coverage_t **out, const char *const *measure_names, int32_t n_measures, const int32_t *thresholds, int32_t n_thresholds) {
+    if (!out || !measure_names || n_measures < 1 || n_thresholds < 0 || n_thresholds > 8 || (n_thresholds > 0 && !thresholds)) return fail(UVCGPU_EINVAL, "coverage report: bad argument");
+    uvcio_coverage *c = new uvcio_coverage;
+    for (int32_t m = 0; m < n_measures; m++) c->measures.push_back(measure_names[m] ? measure_names[m] : "");
+    c->thr.assign(thresholds, thresholds + n_thresholds);
+    *out = c;
+    return 0;
+}
+extern "C" int64_t uvcio_coverage_add_target(uvcio_coverage_t *c, const char *chrom, int64_t beg, int64_t end, const char *name, int64_t len) {
+    if (!c || !chrom || len < 0) return fail(UVCGPU_EINVAL, "coverage report: bad target");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->targets.push_back(uvcio_coverage::Target{ chrom, (name && *name) ? name : ".", beg, end, len, 0 });
+    c->rows.resize(c->targets.size() * c->width(), 0);
+    return (int64_t)c->targets.size() - 1;
+}
+extern "C" int uvcio_coverage_add_piece(uvcio_coverage_t *c, int64_t target, int64_t piece_len, const int64_t *row) {
+    if (!c || !row || piece_len < 1) return fail(UVCGPU_EINVAL, "coverage report: bad piece");
+    std::lock_guard<std::mutex> g(c->mu);
+    if (target < 0 || target >= (int64_t)c->targets.size()) return fail(UVCGPU_EINVAL, "coverage report: piece of target " + std::to_string(target) + ", which does not exist");
+    uvcio_coverage::Target &t = c->targets[(size_t)target];
+    if (t.covered + piece_len > t.len) return fail(UVCGPU_EINVAL, "coverage report: the pieces of target " + std::to_string(target) + " are longer than the target (pieces must be disjoint)");
+    const size_t nt = c->thr.size(), w = 3 + nt;
+    int64_t *dst = &c->rows[(size_t)target * c->width()];
+    for (size_t m = 0; m < c->measures.size(); m++) {
+        const int64_t *src = row + m * 11;
+        dst[m * w + 0] += src[0];
+        dst[m * w + 1] = (t.covered == 0 ? src[1] : std::min(dst[m * w + 1], src[1]));
+        dst[m * w + 2] = (t.covered == 0 ? src[2] : std::max(dst[m * w + 2], src[2]));
+        for (size_t k = 0; k < nt; k++) dst[m * w + 3 + k] += src[3 + k];
+    }
+    t.covered += piece_len;
+    return 0;
+}
+extern "C" int uvcio_coverage_write(const uvcio_coverage_t *c, const char *path) {
+    if (!c || !path || !*path) return fail(UVCGPU_EINVAL, "coverage report: bad argument");
+    std::string text = "#chrom\tbeg\tend\tname\tlen";
+    for (const std::string &m : c->measures) {
+        text += "\t" + m + "_sum\t" + m + "_min\t" + m + "_max";
+        for (int32_t t : c->thr) text += "\t" + m + "_ge" + std::to_string(t);
+    }
+    text += "\n";
+    const size_t nt = c->thr.size(), w = 3 + nt;
+    for (size_t q = 0; q < c->targets.size(); q++) {
+        const uvcio_coverage::Target &t = c->targets[q];
+        text += t.chrom + "\t" + std::to_string(t.beg) + "\t" + std::to_string(t.end) + "\t" + t.name + "\t" + std::to_string(t.len);
+        const int64_t *row = &c->rows[q * c->width()];
+        const int64_t bare = t.len - t.covered;   // positions no tile reported: depth 0
+        for (size_t m = 0; m < c->measures.size(); m++) {
+            text += "\t" + std::to_string(row[m * w]) + "\t" + std::to_string(bare > 0 ? std::min<int64_t>(row[m * w + 1], 0) : row[m * w + 1]) + "\t" + std::to_string(row[m * w + 2]);
+            for (size_t k = 0; k < nt; k++) text += "\t" + std::to_string(row[m * w + 3 + k] + (c->thr[k] <= 0 ? bare : 0));
+        }
+        text += "\n";
+    }
+    const std::string p = path;
+    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
+        uvcio_bgzf_writer_t *zw = nullptr;
+        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
+        const int rc2 = uvcio_bgzf_write_close(zw);
+        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+        return 0;
+    }
+    FILE *fo = fopen(path, "wb");
+    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
+    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+    return 0;
+}
+extern "C" void uvcio_coverage_close(uvcio_coverage_t *c) { delete c; }

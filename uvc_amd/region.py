@@ -23,6 +23,8 @@ class UvcError(RuntimeError):
         self.code = code
 
 
+COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
+
 _gpu_lib = None
 
 
@@ -464,6 +466,20 @@ class Region:
                 yield rec, [(q.pos_beg, q.pos_end, q.base_at_pos_beg, q.region_beg) for q in covered[:nc.value]]
         finally:
             end(h)
+
+    def coverage(self, ranges, thresholds=()):
+        """uvcgpu_region_coverage: depth statistics of `ranges` -- (pos_beg, pos_end) pairs, zero-based, half open, sorted and disjoint, inside
+        the region -- reduced on the device from the accumulated planes.  int64 [n_ranges, UVC_NCOV, 3 + n_thresholds]: per measure of
+        COVERAGE_MEASURES the sum, the minimum and the maximum of its per-position depth over the range, then the number of positions at or
+        above each of `thresholds` (at most 8, ascending).  After accumulate() and before anything that releases the planes."""
+        fn = self._ranges_fn("region_coverage", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p])
+        rows = [(int(q[0]), int(q[1])) for q in ranges]
+        arr = (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows])
+        thr = np.ascontiguousarray(thresholds, dtype=np.int32).reshape(-1)
+        ncov, row = _ffi.ENUMS["UVC_NCOV"], _ffi.ENUMS["UVC_COV_ROW"]
+        out = np.zeros((max(len(rows), 1), ncov, row), dtype=np.int64)
+        self._check(fn(self.h, arr, len(rows), thr.ctypes.data if len(thr) else None, len(thr), out.ctypes.data))
+        return out[:len(rows), :, :_ffi.ENUMS["UVC_COV_GE"] + len(thr)].copy()
 
     def score_stream_bytes_per_record(self):
         return self._ranges_fn("score_stream_bytes_per_record", C.c_int64, [])()
