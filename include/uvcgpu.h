@@ -484,6 +484,33 @@ int uvcgpu_region_coverage(uvcgpu_region_t *r, const UvcCoverageRange *ranges, i
                            const int32_t *thresholds, int32_t n_thresholds /* 0..8, ascending */,
                            int64_t *out /* [n_ranges][UVC_NCOV][UVC_COV_ROW] */);
 const char *uvcgpu_coverage_measure_name(int32_t id);   /* "aDP" .. "dDP1"; NULL for an id outside 0..UVC_NCOV - 1 */
+/* ---- background error profile of ranges of the accumulated region (uvc1-mi355x --error-profile-out) ----
+ * How often a non-reference base or an InDel symbol appears at positions that are not variant, per evidence level (rows of
+ * include/uvc_errprofile.def, in this order: fragments, UMI families, BQ-filtered families, consensus-sized families, duplex families), split by
+ * the reference trinucleotide.  c_L(s, p) is the level's cell of symbol s at position p, summed over both strands where the plane has them.
+ *   Context of p: l, m, r = the handle's reference symbols at p - 1, p, p + 1; a position the handle holds no reference base for (in front of
+ *   beg, at or behind end) counts as N.  Unless all three are A/C/G/T the position has no context: it adds 1 to no_context and nothing else.
+ *   Otherwise ctx = 16 l + 4 m + r and, per level and for each of the two kinds
+ *     BASE: symbols A C G T, reference symbol m;      LINK: symbols LINK_M D3P D2 D1 I3P I2 I1, reference symbol LINK_M
+ *   with d = the sum of c_L over the kind's symbols and a = the largest c_L of a non-reference one: d < min_depth counts <kind>_low_depth; else
+ *   a * 1000 > max_alt_permille * d counts <kind>_high_alt (the position looks variant); else <kind>_counted, and c_L(s, p) is added to the bin
+ *   [ctx][s] of every symbol of the kind, the reference symbol included (the denominator's reference part).
+ * A level's row: 256 BASE bins [ctx][4], 448 LINK bins [ctx][7], the 8 counters of UvcErrCounter (no_context is per position, the same in
+ * every row).  Rows of disjoint position sets add. */
+enum UvcErrLevel { UVC_ERRLEVEL_bDP = 0, UVC_ERRLEVEL_cDP1, UVC_ERRLEVEL_cDP12, UVC_ERRLEVEL_cDP2, UVC_ERRLEVEL_dDP1, UVC_NERRLEVEL };
+enum { UVC_ERR_NCTX = 64, UVC_ERR_NBASE = 4, UVC_ERR_NLINK = 7, UVC_ERR_BASE_BINS = 0, UVC_ERR_LINK_BINS = 256 /* 64 * 4 */,
+       UVC_ERR_COUNTERS = 704 /* 256 + 64 * 7 */, UVC_ERR_ROW = 712 /* + 8 */ };
+enum UvcErrCounter { UVC_ERRC_BASE_counted = 0, UVC_ERRC_BASE_low_depth, UVC_ERRC_BASE_high_alt, UVC_ERRC_LINK_counted, UVC_ERRC_LINK_low_depth,
+                     UVC_ERRC_LINK_high_alt, UVC_ERRC_no_context, UVC_ERRC_reserved /* 0 */, UVC_NERRC };
+typedef struct UvcErrorProfileRequest { int32_t min_depth; int32_t max_alt_permille; } UvcErrorProfileRequest;
+/* One profile of UVC_NERRLEVEL x UVC_ERR_ROW int64 per call, summed over all positions of all ranges; integers only, the same bits from call
+ * to call.  The planes are reduced on the device in one pass (396 B per position); nothing per position travels to the host.
+ *   Ranges and the legality window are those of uvcgpu_region_coverage (zero-based, half open, sorted, disjoint, inside [beg, end + 1); after
+ *   accumulate, before the planes are released, no score stream open), with the same refusals.  min_depth < 1 or max_alt_permille outside
+ *   0..1000 is UVCGPU_EINVAL before any launch.  `out` is written only by a call that returns 0. */
+int uvcgpu_region_error_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges,
+                                const UvcErrorProfileRequest *req, int64_t *out /* [UVC_NERRLEVEL][UVC_ERR_ROW] */);
+const char *uvcgpu_error_level_name(int32_t id);   /* "bDP" .. "dDP1"; NULL for an id outside 0..UVC_NERRLEVEL - 1 */
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);

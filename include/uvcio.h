@@ -179,6 +179,20 @@ int64_t uvcio_coverage_add_target(uvcio_coverage_t *c, const char *chrom, int64_
 int uvcio_coverage_add_piece(uvcio_coverage_t *c, int64_t target, int64_t piece_len, const int64_t *row /* [n_measures][11] */);
 int uvcio_coverage_write(const uvcio_coverage_t *c, const char *path);
 void uvcio_coverage_close(uvcio_coverage_t *c);
+/* ---- the background error profile (uvc1-mi355x --error-profile-out) ----
+ * The sum of the profiles that tiles report (uvcgpu_region_error_profile: n_levels x 712 int64 -- per level 256 BASE bins [ctx][A C G T], 448
+ * LINK bins [ctx][M D3P D2 D1 I3P I2 I1], 8 counters).  Profiles of disjoint position sets add; add locks, so pieces come in any order and
+ * from any thread.
+ * write: "##error_profile_min_depth=<n>" and "##error_profile_max_alt_permille=<n>", "#level\tcounter\tcount" and one line per level and
+ * counter (BASE_counted BASE_low_depth BASE_high_alt LINK_counted LINK_low_depth LINK_high_alt no_context), then
+ * "#level\tkind\tcontext\tsymbol\tcount\tref_count" and one line per bin of a (level, kind, context) that is not empty, in level, kind (BASE,
+ * LINK), context (AAA AAC .. TTT) and symbol order; ref_count is the reference symbol's bin of the same level, kind and context (the
+ * context's middle base; M).  Integers only; a path that ends in .gz is written block-gzipped (uvcio_bgzf_write_*). */
+typedef struct uvcio_errprofile uvcio_errprofile_t;
+int uvcio_errprofile_open(uvcio_errprofile_t **out, const char *const *level_names, int32_t n_levels, int32_t min_depth, int32_t max_alt_permille);
+int uvcio_errprofile_add(uvcio_errprofile_t *e, const int64_t *profile /* [n_levels][712] */);
+int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *path);
+void uvcio_errprofile_close(uvcio_errprofile_t *e);
 /* bcftools concat -n (uvcTN.sh:100): the BGZF files one after the other, the 28-byte end-of-file marker of all but the last dropped. */
 int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in);
 /* The whole text of a (block-)gzipped or plain file (the tumor VCF of a T/N pair); *buf is malloc'ed, the caller frees it. */

@@ -79,6 +79,10 @@ class UvcCoverageRange(C.Structure):
     _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32)]
 
 
+class UvcErrorProfileRequest(C.Structure):
+    _fields_ = [("min_depth", C.c_int32), ("max_alt_permille", C.c_int32)]
+
+
 class UvcScoreOut(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n_records", C.c_int64), ("fields", C.c_void_p)]
 
@@ -130,6 +134,9 @@ NUM_SCORE_FIELDS = ENUMS["UVC_NUM_SCORE_FIELDS"]
 # the depth measures of uvcgpu_region_coverage in id order (UvcCoverageMeasure; the rows of include/uvc_coverage.def)
 COVERAGE_MEASURES = [k[len("UVC_COV_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_COV_") and k[len("UVC_COV_"):] not in ("SUM", "MIN", "MAX", "GE", "MAX_THRESHOLDS", "ROW")), key=lambda kv: kv[1])]
 assert len(COVERAGE_MEASURES) == ENUMS["UVC_NCOV"]
+# the evidence levels of uvcgpu_region_error_profile in id order (UvcErrLevel; the rows of include/uvc_errprofile.def)
+ERROR_LEVELS = [k[len("UVC_ERRLEVEL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_ERRLEVEL_")), key=lambda kv: kv[1])]
+assert len(ERROR_LEVELS) == ENUMS["UVC_NERRLEVEL"]
 
 
 class Lib:

@@ -51,6 +51,9 @@ struct Opts {
     std::vector<int32_t> coverage_thr{ 1, 20, 100, 500 }; bool coverage_thr_given = false;   // --coverage-thresholds
     int64_t coverage_window = 0; // --coverage-window N: the targets are windows of N bp (0: the BED lines)
     uvcio_coverage_t *cov = nullptr;   // the report's store, filled by the workers (main)
+    std::string errprof_out;     // --error-profile-out PATH: the background error profile; empty = none
+    UvcErrorProfileRequest errprof_req{ 20, 50 }; bool errprof_gate_given = false;   // --error-profile-min-depth, --error-profile-max-alt-permille
+    uvcio_errprofile_t *errprof = nullptr;   // the run's table, summed over the tiles by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -98,6 +101,9 @@ const OptRow OPTS[] = {
     { "--coverage-out", O_CLI, false, "", "write the per-target coverage report here (tab-separated; block-gzipped when the name ends in .gz): per BED line, or per --coverage-window, sum / min / max and positions at or above each threshold of six depths the caller itself works with (aDP raw segments, bDP fragments, cDP1 families, cDP12 BQ-filtered families, cDP2 single-strand-consensus families, dDP1 duplex families), reduced on the device from the planes of each tile.  The VCF does not depend on it" },
     { "--coverage-thresholds", O_CLI, false, "1,20,100,500", "with --coverage-out: at most 8 ascending depths; the report counts the positions at or above each" },
     { "--coverage-window", O_CLI, false, "0", "with --coverage-out and no BED file: the targets are windows of this many bp, aligned to multiples of it on each contig and clipped to the called span" },
+    { "--error-profile-out", O_CLI, false, "", "write the background error profile here (tab-separated; block-gzipped when the name ends in .gz): how often each base and each InDel symbol is seen at positions that do not look variant, per reference trinucleotide and per evidence level (bDP fragments, cDP1 families, cDP12 BQ-filtered families, cDP2 single-strand-consensus families, dDP1 duplex families), reduced on the device from the planes of each tile over the positions the tile owns.  The VCF does not depend on it" },
+    { "--error-profile-min-depth", O_CLI, false, "20", "with --error-profile-out: a position enters a level's bins only where the level's depth is at least this (1 or more)" },
+    { "--error-profile-max-alt-permille", O_CLI, false, "50", "with --error-profile-out: a position whose largest non-reference count is above this many thousandths of the level's depth counts as variant and stays out of the bins (0..1000)" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -259,6 +265,9 @@ Opts parse(int argc, char **argv) {
             }
         }
         else if (n0 == "--coverage-window") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--coverage-window takes a window length in bp, not '" + v + "'"); o.coverage_window = (int64_t)x; }
+        else if (n0 == "--error-profile-out") { o.errprof_out = val(); if (o.errprof_out.empty()) die("--error-profile-out needs a path"); }
+        else if (n0 == "--error-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--error-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.errprof_req.min_depth = (int32_t)x; o.errprof_gate_given = true; }
+        else if (n0 == "--error-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--error-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.errprof_req.max_alt_permille = (int32_t)x; o.errprof_gate_given = true; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -311,6 +320,13 @@ Opts parse(int argc, char **argv) {
         if (has_bed && o.coverage_window > 0) die("--coverage-window cannot go with -R / --bed-in-fname: with a BED file the targets of --coverage-out are its lines");
         if (!has_bed && o.coverage_window <= 0) die("--coverage-out needs --coverage-window N without -R / --bed-in-fname: there are no BED lines to report on");
     }
+    if (o.errprof_out.empty()) {   // before any file or device
+        if (o.errprof_gate_given) die("--error-profile-min-depth and --error-profile-max-alt-permille need --error-profile-out: they only gate that report");
+    } else {
+        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--error-profile-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
+        if (o.n_shards > 1) die("--error-profile-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": every shard would write a part of the table, and --concat joins VCFs only");
+        if (o.repeat != 1) die("--error-profile-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
+    }
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -350,6 +366,7 @@ struct Worker {
     int64_t n_chunks = 0, n_streamed = 0;               // --score-mem-mb: chunks in all, tiles scored as streams
     std::vector<UvcScoreRange> covered;
     std::vector<UvcCoverageRange> cov_ranges; std::vector<int64_t> cov_targets, cov_rows;   // --coverage-out: the pieces of one tile
+    std::vector<UvcCoverageRange> err_ranges;   // --error-profile-out: the stretches one tile owns
 };
 
 // --coverage-out: the pieces of targets that one accumulated tile owns, reduced by one uvcgpu_region_coverage and merged into the report.
@@ -375,6 +392,16 @@ void coverage_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int6
     if (uvcgpu_region_coverage(w.reg, w.cov_ranges.data(), (int64_t)w.cov_ranges.size(), o.coverage_thr.data(), (int32_t)o.coverage_thr.size(), w.cov_rows.data())) die(uvcgpu_last_error());
     for (size_t q = 0; q < w.cov_ranges.size(); q++)
         if (uvcio_coverage_add_piece(o.cov, w.cov_targets[q], (int64_t)w.cov_ranges[q].pos_end - w.cov_ranges[q].pos_beg, &w.cov_rows[q * (size_t)UVC_NCOV * UVC_COV_ROW])) die(uvcio_last_error());
+}
+// --error-profile-out: the profile of the stretches one accumulated tile owns -- the list coverage_of_tile reports on -- by one
+// uvcgpu_region_error_profile, added to the run's table.
+void errprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own) {
+    w.err_ranges.clear();
+    for (const auto &q : own) if (q.second > q.first) w.err_ranges.push_back(UvcCoverageRange{ (int32_t)q.first, (int32_t)q.second });
+    if (w.err_ranges.empty()) return;
+    int64_t prof[UVC_NERRLEVEL * UVC_ERR_ROW];
+    if (uvcgpu_region_error_profile(w.reg, w.err_ranges.data(), (int64_t)w.err_ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
+    if (uvcio_errprofile_add(o.errprof, prof)) die(uvcio_last_error());
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -452,7 +479,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (uvcgpu_region_set_reads(w.reg, &rs)) die(uvcgpu_last_error());
     w.t_reads += now() - t0; t0 = now();
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
-    if (o.cov) {   // --coverage-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
+    if (o.cov || o.errprof) {   // --coverage-out, --error-profile-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
                    // point t.end itself, which lies outside every target the tile was cut from (and which two regions of the reference's cuts share)
         std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of;
         if (n_merged == 0) { own.emplace_back(first, std::min(last_excl, t.end)); target_of.push_back(t.target); }
@@ -462,7 +489,8 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
             const int64_t l_excl = l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end);
             own.emplace_back(l_first, std::min(l_excl, l.end)); target_of.push_back(l.target);
         }
-        coverage_of_tile(w, o, own, target_of, cov_span);
+        if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
+        if (o.errprof) errprofile_of_tile(w, o, own);
     }
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
@@ -795,6 +823,7 @@ PairArgs split_pair(int argc, char **argv) {
         if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
         if (name == "--coverage-out" || name == "--coverage-thresholds" || name == "--coverage-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no coverage report");
+        if (name == "--error-profile-out" || name == "--error-profile-min-depth" || name == "--error-profile-max-alt-permille") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no error profile");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
             die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
@@ -1062,6 +1091,10 @@ int main(int argc, char **argv) {
         const char *mnames[UVC_NCOV]; for (int32_t m = 0; m < UVC_NCOV; m++) mnames[m] = uvcgpu_coverage_measure_name(m);
         if (uvcio_coverage_open(&o.cov, mnames, UVC_NCOV, o.coverage_thr.data(), (int32_t)o.coverage_thr.size())) die(uvcio_last_error());
     }
+    if (!o.errprof_out.empty() && !o.print_params) {
+        const char *lnames[UVC_NERRLEVEL]; for (int32_t l = 0; l < UVC_NERRLEVEL; l++) lnames[l] = uvcgpu_error_level_name(l);
+        if (uvcio_errprofile_open(&o.errprof, lnames, UVC_NERRLEVEL, o.errprof_req.min_depth, o.errprof_req.max_alt_permille)) die(uvcio_last_error());
+    }
     std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans);
     if (o.n_shards > 1) {
         std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
@@ -1116,6 +1149,11 @@ int main(int argc, char **argv) {
         if (!probe) die("--coverage-out: cannot create " + o.coverage_out);
         fclose(probe);
     }
+    if (o.errprof) {
+        FILE *probe = fopen(o.errprof_out.c_str(), "wb");
+        if (!probe) die("--error-profile-out: cannot create " + o.errprof_out);
+        fclose(probe);
+    }
     if (!o.no_header) {
         const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
@@ -1163,6 +1201,10 @@ int main(int argc, char **argv) {
     if (o.cov) {   // every tile has reported: the rows in target order, whichever worker finished first
         if (uvcio_coverage_write(o.cov, o.coverage_out.c_str())) die("--coverage-out: " + std::string(uvcio_last_error()));
         uvcio_coverage_close(o.cov);
+    }
+    if (o.errprof) {   // every tile has reported: sums do not depend on the order
+        if (uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())) die("--error-profile-out: " + std::string(uvcio_last_error()));
+        uvcio_errprofile_close(o.errprof);
     }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);

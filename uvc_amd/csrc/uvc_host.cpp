@@ -60,6 +60,9 @@ extern "C" void uvc_launch_block_stats_windows(const RegionDev *R, const UvcPara
 extern "C" void uvc_launch_coverage(const RegionDev *R, const void *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s);
 extern "C" const char *uvc_coverage_name(int id);
 extern "C" int64_t uvc_coverage_scratch_rows(int n_ranges, int64_t n_total);
+extern "C" void uvc_launch_errprofile(const RegionDev *R, const void *d_tab, int n_ranges, int64_t n_total, int min_depth, int max_alt_permille, long long *d_out, long long *d_scratch, hipStream_t s);
+extern "C" const char *uvc_errprofile_level_name(int id);
+extern "C" int64_t uvc_errprofile_scratch_cells(void);
 extern "C" size_t uvc_gap_sort_tmp_bytes(size_t n);
 extern "C" void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
 extern "C" void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
@@ -128,7 +131,7 @@ struct uvcgpu_region {
     int32_t *d_score_fields = nullptr; int64_t score_capacity = 0; int64_t *d_score_count = nullptr;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     int32_t *d_score_kept = nullptr; int64_t score_kept_capacity = 0;   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields
-    char *d_cov = nullptr; size_t d_cov_bytes = 0; int64_t *h_cov = nullptr; size_t h_cov_bytes = 0;   // uvcgpu_region_coverage: range table + rows on the device, page-locked rows (grown on demand)
+    char *d_cov = nullptr; size_t d_cov_bytes = 0; int64_t *h_cov = nullptr; size_t h_cov_bytes = 0;   // uvcgpu_region_coverage and uvcgpu_region_error_profile: range table + rows on the device, page-locked rows (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1471,7 +1474,25 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
 }
 
 // ---- depth statistics of ranges (uvc_coverage.hip) ----
-struct CovRangeHost { int32_t x0, first; };   // CovRangeDev of uvc_coverage.hip
+struct CovRangeHost { int32_t x0, first; };   // CovRangeDev of uvc_coverage.hip, ErrRangeDev of uvc_errprofile.hip
+// the device and the page-locked buffer that uvcgpu_region_coverage and uvcgpu_region_error_profile share (both synchronise before they return), grown on demand
+static int cov_buffers(uvcgpu_region_t *r, size_t dev_bytes, size_t out_bytes, const char *what) {
+    if (dev_bytes > r->d_cov_bytes) {
+        if (r->d_cov) { (void)hipStreamSynchronize(r->stream); hipFree(r->d_cov); }
+        r->d_cov = nullptr; r->d_cov_bytes = 0;
+        const size_t want = dev_bytes + dev_bytes / 2;
+        if (hipMalloc((void **)&r->d_cov, want) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipMalloc(") + what + ") failed"); }
+        r->d_cov_bytes = want;
+    }
+    if (out_bytes > r->h_cov_bytes) {
+        if (r->h_cov) { (void)hipStreamSynchronize(r->stream); (void)hipHostFree(r->h_cov); }
+        r->h_cov = nullptr; r->h_cov_bytes = 0;
+        const size_t want = out_bytes + out_bytes / 2;
+        if (hipHostMalloc((void **)&r->h_cov, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipHostMalloc(") + what + ") failed"); }
+        r->h_cov_bytes = want;
+    }
+    return 0;
+}
 static int uvcgpu_region_coverage_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const int32_t *thresholds, int32_t n_thresholds, int64_t *out) {
     if (!r) return fail(UVCGPU_EINVAL, "coverage: null region");
     if (!r->accumulated) return fail(UVCGPU_EINVAL, "coverage before accumulate: there are no planes to reduce");
@@ -1500,20 +1521,7 @@ static int uvcgpu_region_coverage_impl(uvcgpu_region_t *r, const UvcCoverageRang
     const size_t tab_bytes = (sizeof(CovRangeHost) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)n_ranges;
     const int64_t scratch_rows = uvc_coverage_scratch_rows((int)n_ranges, n_total);   // the shard copies of few long ranges (0: the waves merge into the result rows)
     const size_t dev_bytes = tab_bytes + out_bytes + sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)scratch_rows;   // [table] [result rows] [scratch rows]
-    if (dev_bytes > r->d_cov_bytes) {
-        if (r->d_cov) { (void)hipStreamSynchronize(r->stream); hipFree(r->d_cov); }
-        r->d_cov = nullptr; r->d_cov_bytes = 0;
-        const size_t want = dev_bytes + dev_bytes / 2;
-        if (hipMalloc((void **)&r->d_cov, want) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, "hipMalloc(coverage rows) failed"); }
-        r->d_cov_bytes = want;
-    }
-    if (out_bytes > r->h_cov_bytes) {
-        if (r->h_cov) { (void)hipStreamSynchronize(r->stream); (void)hipHostFree(r->h_cov); }
-        r->h_cov = nullptr; r->h_cov_bytes = 0;
-        const size_t want = out_bytes + out_bytes / 2;
-        if (hipHostMalloc((void **)&r->h_cov, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, "hipHostMalloc(coverage rows) failed"); }
-        r->h_cov_bytes = want;
-    }
+    { int rc1 = cov_buffers(r, dev_bytes, out_bytes, "coverage rows"); if (rc1) return rc1; }
     // the table through the handle's staging buffer (stage_upload: never an asynchronous copy from the caller's or the heap's pages); an earlier
     // call's copy out of it is complete, every user of the buffer synchronises before it returns
     size_t at = 0;
@@ -1530,6 +1538,47 @@ int uvcgpu_region_coverage(uvcgpu_region_t *r, const UvcCoverageRange *ranges, i
     return guarded("uvcgpu_region_coverage", [&] { return uvcgpu_region_coverage_impl(r, ranges, n_ranges, thresholds, n_thresholds, out); });
 }
 const char *uvcgpu_coverage_measure_name(int32_t id) { return uvc_coverage_name(id); }
+
+// ---- background error profile of ranges (uvc_errprofile.hip) ----
+static int uvcgpu_region_error_profile_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcErrorProfileRequest *req, int64_t *out) {
+    if (!r) return fail(UVCGPU_EINVAL, "error_profile: null region");
+    if (!r->accumulated) return fail(UVCGPU_EINVAL, "error_profile before accumulate: there are no planes to reduce");
+    if (r->state_released) return fail(UVCGPU_EINVAL, "error_profile after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
+    if (stream_is_open(r)) return fail(UVCGPU_EINVAL, "error_profile while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    if (!ranges || !req || !out) return fail(UVCGPU_EINVAL, "error_profile: ranges, req and out must not be NULL");
+    if (req->min_depth < 1) return fail(UVCGPU_EINVAL, "error_profile: min_depth " + std::to_string(req->min_depth) + " must be at least 1");
+    if (req->max_alt_permille < 0 || req->max_alt_permille > 1000) return fail(UVCGPU_EINVAL, "error_profile: max_alt_permille " + std::to_string(req->max_alt_permille) + " is outside 0..1000");
+    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "error_profile: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
+    if (n_ranges > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "error_profile: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
+    std::vector<CovRangeHost> tab((size_t)n_ranges + 1);
+    int64_t n_total = 0;
+    for (int64_t k = 0; k < n_ranges; k++) {
+        const UvcCoverageRange &q = ranges[k];
+        const std::string name = "error_profile: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
+        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
+        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
+        tab[(size_t)k] = CovRangeHost{ q.pos_beg - r->beg, (int32_t)n_total };
+        n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
+    }
+    tab[(size_t)n_ranges] = CovRangeHost{ 0, (int32_t)n_total };
+    const size_t tab_bytes = (sizeof(CovRangeHost) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NERRLEVEL * UVC_ERR_ROW;
+    const size_t dev_bytes = tab_bytes + out_bytes + sizeof(int64_t) * (size_t)uvc_errprofile_scratch_cells();   // [table] [profile] [shard copies]
+    { int rc1 = cov_buffers(r, dev_bytes, out_bytes, "error profile"); if (rc1) return rc1; }
+    size_t at = 0;   // the table through the handle's staging buffer, as coverage sends its own
+    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(CovRangeHost) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
+    long long *d_prof = (long long *)(r->d_cov + tab_bytes);
+    uvc_launch_errprofile(&r->R, r->d_cov, (int)n_ranges, n_total, req->min_depth, req->max_alt_permille, d_prof, (long long *)(r->d_cov + tab_bytes + out_bytes), r->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(r->h_cov, d_prof, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
+    memcpy(out, r->h_cov, out_bytes);
+    return 0;
+}
+int uvcgpu_region_error_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcErrorProfileRequest *req, int64_t *out) {
+    return guarded("uvcgpu_region_error_profile", [&] { return uvcgpu_region_error_profile_impl(r, ranges, n_ranges, req, out); });
+}
+const char *uvcgpu_error_level_name(int32_t id) { return uvc_errprofile_level_name(id); }
 
 int uvcgpu_region_create(uvcgpu_region_t **out, const UvcParams *params, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_create", [&] { return uvcgpu_region_create_impl(out, params, tid, beg, end, refseq); }); }
 int uvcgpu_region_reset(uvcgpu_region_t *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_reset", [&] { return uvcgpu_region_reset_impl(r, tid, beg, end, refseq); }); }

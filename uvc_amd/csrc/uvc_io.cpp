@@ -1286,3 +1286,66 @@ extern "C" int uvcio_coverage_write(const uvcio_coverage_t *c, const char *path)
     return 0;
 }
 extern "C" void uvcio_coverage_close(uvcio_coverage_t *c) { delete c; }
+
+// ---------------------------------------------------------------- the background error profile ----
+// the row layout is that of uvcgpu_region_error_profile (UVC_ERR_*, UvcErrCounter of uvcgpu.h); the reserved counter is not written
+enum { EP_NCOUNTERS = UVC_ERRC_no_context + 1 };
+struct uvcio_errprofile {
+    std::vector<std::string> levels; int32_t min_depth, max_alt_permille;
+    std::vector<int64_t> sum;   // [level][UVC_ERR_ROW]
+    std::mutex mu;
+};
+extern "C" int uvcio_errprofile_open(uvcio_errprofile_t **out, const char *const *level_names, int32_t n_levels, int32_t min_depth, int32_t max_alt_permille) {
+    if (!out || !level_names || n_levels < 1) return fail(UVCGPU_EINVAL, "error profile: bad argument");
+    uvcio_errprofile *e = new uvcio_errprofile;
+    for (int32_t l = 0; l < n_levels; l++) e->levels.push_back(level_names[l] ? level_names[l] : "");
+    e->min_depth = min_depth; e->max_alt_permille = max_alt_permille;
+    e->sum.assign((size_t)n_levels * UVC_ERR_ROW, 0);
+    *out = e;
+    return 0;
+}
+extern "C" int uvcio_errprofile_add(uvcio_errprofile_t *e, const int64_t *profile) {
+    if (!e || !profile) return fail(UVCGPU_EINVAL, "error profile: bad argument");
+    std::lock_guard<std::mutex> g(e->mu);
+    for (size_t i = 0; i < e->sum.size(); i++) e->sum[i] += profile[i];
+    return 0;
+}
+extern "C" int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *path) {
+    if (!e || !path || !*path) return fail(UVCGPU_EINVAL, "error profile: bad argument");
+    static const char *const COUNTERS[EP_NCOUNTERS] = { "BASE_counted", "BASE_low_depth", "BASE_high_alt", "LINK_counted", "LINK_low_depth", "LINK_high_alt", "no_context" };
+    static const char *const BASE_SYM[UVC_ERR_NBASE] = { "A", "C", "G", "T" };
+    static const char *const LINK_SYM[UVC_ERR_NLINK] = { "M", "D3P", "D2", "D1", "I3P", "I2", "I1" };
+    std::string text = "##error_profile_min_depth=" + std::to_string(e->min_depth) + "\n##error_profile_max_alt_permille=" + std::to_string(e->max_alt_permille) + "\n#level\tcounter\tcount\n";
+    for (size_t l = 0; l < e->levels.size(); l++)
+        for (int k = 0; k < EP_NCOUNTERS; k++) text += e->levels[l] + "\t" + COUNTERS[k] + "\t" + std::to_string(e->sum[l * UVC_ERR_ROW + UVC_ERR_COUNTERS + k]) + "\n";
+    text += "#level\tkind\tcontext\tsymbol\tcount\tref_count\n";
+    for (size_t l = 0; l < e->levels.size(); l++)
+        for (int kind = 0; kind < 2; kind++) {
+            const int n = (kind == 0 ? UVC_ERR_NBASE : UVC_ERR_NLINK);
+            const int64_t *bins = &e->sum[l * UVC_ERR_ROW + (kind == 0 ? 0 : UVC_ERR_LINK_BINS)];
+            for (int ctx = 0; ctx < UVC_ERR_NCTX; ctx++) {
+                const int64_t *b = bins + ctx * n;
+                bool any = false;
+                for (int j = 0; j < n; j++) any = any || b[j] != 0;
+                if (!any) continue;
+                const int ref = (kind == 0 ? (ctx >> 2) & 3 : 0);
+                const std::string head = e->levels[l] + (kind == 0 ? "\tBASE\t" : "\tLINK\t") + BASE_SYM[ctx >> 4] + BASE_SYM[(ctx >> 2) & 3] + BASE_SYM[ctx & 3] + "\t";
+                for (int j = 0; j < n; j++) text += head + (kind == 0 ? BASE_SYM[j] : LINK_SYM[j]) + "\t" + std::to_string(b[j]) + "\t" + std::to_string(b[ref]) + "\n";
+            }
+        }
+    const std::string p = path;
+    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
+        uvcio_bgzf_writer_t *zw = nullptr;
+        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
+        const int rc2 = uvcio_bgzf_write_close(zw);
+        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+        return 0;
+    }
+    FILE *fo = fopen(path, "wb");
+    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
+    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+    return 0;
+}
+extern "C" void uvcio_errprofile_close(uvcio_errprofile_t *e) { delete e; }

@@ -24,6 +24,7 @@ class UvcError(RuntimeError):
 
 
 COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
+ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
 
 _gpu_lib = None
 
@@ -480,6 +481,20 @@ class Region:
         out = np.zeros((max(len(rows), 1), ncov, row), dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), thr.ctypes.data if len(thr) else None, len(thr), out.ctypes.data))
         return out[:len(rows), :, :_ffi.ENUMS["UVC_COV_GE"] + len(thr)].copy()
+
+    def error_profile(self, ranges, min_depth=20, max_alt_permille=50):
+        """uvcgpu_region_error_profile: the background error profile of `ranges` (as Region.coverage takes them), reduced on the device from the
+        accumulated planes.  int64 [UVC_NERRLEVEL, UVC_ERR_ROW]: per level of ERROR_LEVELS 256 BASE bins [ctx][A C G T], 448 LINK bins
+        [ctx][M D3P D2 D1 I3P I2 I1] and 8 counters (UvcErrCounter), ctx = 16 l + 4 m + r of the reference symbols around the position; a
+        position enters a level's bins where the level's depth is >= min_depth and its largest non-reference count is at most max_alt_permille
+        thousandths of it (uvcgpu.h has the rules).  After accumulate() and before anything that releases the planes."""
+        fn = self._ranges_fn("region_error_profile", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+        rows = [(int(q[0]), int(q[1])) for q in ranges]
+        arr = (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows])
+        req = _ffi.UvcErrorProfileRequest(int(min_depth), int(max_alt_permille))
+        out = np.zeros((_ffi.ENUMS["UVC_NERRLEVEL"], _ffi.ENUMS["UVC_ERR_ROW"]), dtype=np.int64)
+        self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data))
+        return out
 
     def score_stream_bytes_per_record(self):
         return self._ranges_fn("score_stream_bytes_per_record", C.c_int64, [])()
