@@ -11,27 +11,27 @@ import re
 
 from test_gpu_parity import CASES, VARIANTS
 
-# Every form the dispatcher can name, with the lines of uvc_amd/csrc/uvc_kernels_acc.hip that launch it.  frag_generic=sweep is left out: whether the
+# Every form the dispatcher can name, with the kernels of uvc_amd/csrc/uvc_kernels_acc.hip it launches.  frag_generic=sweep is left out: whether the
 # sweep list is used depends on the fragments, not on the switches (test_gpu_fuzz.py::test_fragment_longer_than_the_sweep_window covers it).
 FORMS = [
-    "prep=wave",               # 3765 k_prep_fast<false>
-    "prep=split",              # 3764 k_prep_fast<true>
-    "p2=wave,plain",           # 3788 / 3794 k_p2_fast<., ., true>
-    "p2=wave,generic",         # 3789 / 3795 k_p2_fast<., ., false>
-    "p2=split,plain",          # 3786 / 3792 k_p2_fast_split<., ., true>
-    "p2=split,generic",        # 3787 / 3793 k_p2_fast_split<., ., false>
-    "frag=h16,split,plain",    # 3829 k_frag16_split<true>
-    "frag=h16,split,generic",  # 3830 k_frag16_split<false>
-    "frag=h16,wave,plain",     # 3831 k_frag16<true>
-    "frag=h16,wave,generic",   # 3833 k_frag16<false>
-    "frag=b32,wave,plain",     # 3832 k_frag<true>
-    "frag=b32,wave,generic",   # 3834 k_frag<false>
-    "family=generic",          # 3843 / 3846 k_fam_p4 / k_fam_p5
-    "family=digest",           # 3841-3842 / 3845 k_fam_p4d + k_fam_p4d_rest / k_fam_p5d
-    "duplex=generic",          # 3848 k_duplex
-    "duplex=digest",           # 3847 k_duplex_d
-    "frag_generic=all",        # 3825 k_frag_generic over every fragment (IonTorrent)
-    "fastq_only",              # 3759 / 3784: no P1 / P2 (prep=none p2=none), k_frag without the P3 arms
+    "prep=wave",               # k_prep_fast<false>
+    "prep=split",              # k_prep_fast<true>
+    "p2=wave,plain",           # k_p2_fast<., ., true>
+    "p2=wave,generic",         # k_p2_fast<., ., false>
+    "p2=split,plain",          # k_p2_fast_split<., ., true>
+    "p2=split,generic",        # k_p2_fast_split<., ., false>
+    "frag=h16,split,plain",    # k_frag16_split<true>
+    "frag=h16,split,generic",  # k_frag16_split<false>
+    "frag=h16,wave,plain",     # k_frag16<true>
+    "frag=h16,wave,generic",   # k_frag16<false>
+    "frag=b32,wave,plain",     # k_frag<true>
+    "frag=b32,wave,generic",   # k_frag<false>
+    "family=generic",          # k_fam_p4 / k_fam_p5
+    "family=digest",           # k_fam_p4d + k_fam_p4d_rest / k_fam_p5d
+    "duplex=generic",          # k_duplex
+    "duplex=digest",           # k_duplex_d
+    "frag_generic=all",        # k_frag_generic over every fragment (IonTorrent)
+    "fastq_only",              # no k_prep_* / k_thres / k_p2_* (prep=none p2=none), k_frag without the P3 arms
 ]
 
 IONTORRENT = 2   # UVC_PLATFORM_IONTORRENT (include/uvcgpu.h)
@@ -49,7 +49,7 @@ def _edited(name):
 #           partner, so no family pass runs -- a single-fragment unit is folded in by k_frag while the singleton thresholds allow it);
 #   duplex: the tile has duplex families (fam_dflag 0x2 with both strands);
 #   h16:    fewer than 65 536 fragments cover every position;
-#   split:  the form UVCGPU_SPLIT unset gives (uvc_kernels_acc.hip:3730), for the cells that do not force it.
+#   split:  the form UVCGPU_SPLIT unset gives (acc_forms of uvc_kernels_acc.hip), for the cells that do not force it.
 TILES = {
     "nodedup_3kb_60x": dict(gen=_edited("nodedup_3kb_60x"), amplicon=False, family="none", duplex=False, h16=True),
     "umi_duplex_2kb_400x": dict(gen=_edited("umi_duplex_2kb_400x"), amplicon=False, family="digest", duplex=True, h16=True),
@@ -88,13 +88,13 @@ def expected_forms(p, facts, split, frag32=False, fam_generic=False):
     vcf = bool(p.inferred_is_vcf_generated)
     proton = (p.inferred_sequencing_platform == IONTORRENT)
     sp = (split != "0") if split is not None else facts.get("split")
-    # uvc_kernels_acc.hip:3734: P2 without the IonTorrent / amplicon / primer / short-read arms
+    # AccForms::p2_plain: P2 without the IonTorrent / amplicon / primer / short-read arms
     p2_plain = (not proton and not facts.get("amplicon", False) and not (p.primerlen > 0 and not (p.primer_flag & 0x2))
                 and p.central_readlen >= p.microadjust_median_readlen_thres)
-    # uvc_kernels_acc.hip:3736: P3 without the IonTorrent / SSCS-table / padded-deletion arms (and not on a FASTQ-only run)
+    # AccForms::frag_plain: P3 without the IonTorrent / SSCS-table / padded-deletion arms (and not on a FASTQ-only run)
     frag_plain = vcf and not proton and not (p.fam_flag & 0x1) and not (p.microadjust_padded_deletion_flag & 0x1)
-    h16 = facts["h16"] and not frag32                                                   # 3737
-    fam = facts["family"] if (facts["family"] == "none" or not fam_generic) else "generic"   # uvc_host.cpp:408-413
+    h16 = facts["h16"] and not frag32                                                   # AccForms::h16
+    fam = facts["family"] if (facts["family"] == "none" or not fam_generic) else "generic"   # the family form set_reads chooses (uvc_host.cpp)
     sh = "split" if sp else "wave"
     return dict(prep=sh if vcf else "none",
                 p2=("%s,%s" % (sh, "plain" if p2_plain else "generic")) if vcf else "none",

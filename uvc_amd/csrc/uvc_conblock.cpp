@@ -5,6 +5,7 @@
 // one flat event list that is sorted once by (family, strand, type, position, fragment): a fragment's block is the run of its events
 // (per base the maximum quality per base symbol), a family's block is the fold of its fragments' runs.  No per-object maps.
 #include "uvcconsensus.h"
+#include "uvc_host.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -12,8 +13,6 @@
 #include <new>
 #include <string>
 #include <vector>
-
-extern "C" int uvcgpu_set_error(int code, const char *msg);   // uvc_host.cpp
 
 namespace {
 struct Event {

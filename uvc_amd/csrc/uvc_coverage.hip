@@ -7,7 +7,7 @@
 // keeps sum / min / max / counts in registers.  While all lanes of a wave stay in one range nothing crosses lanes; a wave reduces (butterfly
 // over the 64 lanes) and merges into the range's row only when the range changes or its positions end.  The merge is one 64-bit vector atomic
 // per (wave, range segment, statistic), issued by one lane each.  The arithmetic is integer: the order of the merges does not show.
-#include "uvc_device.h"
+#include "uvc_launch.h"
 
 #include <algorithm>
 #include <limits.h>
@@ -57,7 +57,6 @@ DEV int cov_DUPLEX(const RegionDev &R, int plane, int64_t x) {
     return v;
 }
 
-struct CovRangeDev { int x0, first; };   // plane index of the range's first position; its first compact position.  Entry n_ranges: { 0, n_total }
 struct CovThr { int t[UVC_COV_MAX_THRESHOLDS]; };   // unused slots hold INT_MAX
 // A lane's statistics of one range.  The threshold counts are packed two to a register (threshold k in the low half, k + 4 in the high half):
 // a lane counts at most COV_MAX_STEPS positions and a wave 64 times that, far below 2^16.
@@ -147,7 +146,7 @@ __global__ void __launch_bounds__(256) k_coverage_fold(const long long *parts, i
 // One wave takes `steps` consecutive groups of 64 compact positions.  Its registers hold the statistics of one range at a time (`cur`); the
 // positions of a step are taken range by range in ascending order, and a change of range sends what was kept to that range's row.  One
 // more round behind the last step sends the rest, so the merge exists once in the code.
-__global__ void __launch_bounds__(256) k_coverage(RegionDev R, const CovRangeDev *tab, int n_ranges, int n_total, int steps, int shards, CovThr T, long long *out) {
+__global__ void __launch_bounds__(256) k_coverage(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, int steps, int shards, CovThr T, long long *out) {
     const int lane = (int)(threadIdx.x & 63);
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long base = wave * 64 * steps;
@@ -213,7 +212,7 @@ extern "C" int64_t uvc_coverage_scratch_rows(int n_ranges, int64_t n_total) {
 }
 // d_tab: n_ranges + 1 entries of { plane index of the first position, first compact position }, the last one { 0, n_total }; d_out: n_ranges rows;
 // d_scratch: the scratch_rows = uvc_coverage_scratch_rows(n_ranges, n_total) rows the caller allocated (a call with fewer launches nothing)
-extern "C" void uvc_launch_coverage(const RegionDev *R, const void *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s) {
+extern "C" void uvc_launch_coverage(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s) {
     if (n_ranges <= 0 || n_total <= 0 || scratch_rows < uvc_coverage_scratch_rows(n_ranges, n_total)) return;
     int steps, shards; long long n_waves;
     cov_geometry(n_ranges, n_total, steps, n_waves, shards);
@@ -222,6 +221,6 @@ extern "C" void uvc_launch_coverage(const RegionDev *R, const void *d_tab, int n
     hipLaunchKernelGGL(k_coverage_init, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, s, d_parts, n_cells);
     CovThr T;
     for (int k = 0; k < UVC_COV_MAX_THRESHOLDS; k++) T.t[k] = (k < n_thr ? thr[k] : INT_MAX);
-    hipLaunchKernelGGL(k_coverage, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, s, *R, (const CovRangeDev *)d_tab, n_ranges, (int)n_total, steps, shards, T, d_parts);
+    hipLaunchKernelGGL(k_coverage, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, s, *R, d_tab, n_ranges, (int)n_total, steps, shards, T, d_parts);
     if (shards > 1) hipLaunchKernelGGL(k_coverage_fold, dim3((unsigned)((n_final + 255) / 256)), dim3(256), 0, s, d_parts, shards, d_out, n_final);
 }

@@ -13,7 +13,7 @@
 // a question for the measurements of DESIGN.md 4j, not settled here.
 // At the end a block adds its non-zero words to the result with 64-bit vector atomics.  Integer arithmetic only: the order of the adds does
 // not show, the result is the same bits from call to call.
-#include "uvc_device.h"
+#include "uvc_launch.h"
 
 #include <algorithm>
 
@@ -47,8 +47,6 @@ DEV int err_sym(int j) { return j < UVC_ERR_NBASE ? j : UVC_LINK_M + (j - UVC_ER
 DEV long long err_FRAG(const RegionDev &R, int plane, int s, int64_t x) { return (long long)FRP(R, 0, plane, s, x) + FRP(R, 1, plane, s, x); }
 DEV long long err_FAM(const RegionDev &R, int plane, int s, int64_t x) { return (long long)FAP(R, 0, plane, s, x) + FAP(R, 1, plane, s, x); }
 DEV long long err_DUPLEX(const RegionDev &R, int plane, int s, int64_t x) { return (long long)DUP(R, plane, s, x); }
-
-struct ErrRangeDev { int x0, first; };   // plane index of the range's first position; its first compact position.  Entry n_ranges: { 0, n_total }
 
 DEV void lds_add(unsigned long long *p, unsigned long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 // a wave-uniform counter: the lanes with `on` are counted by a ballot, the wave's first lane adds the count
@@ -92,7 +90,7 @@ __global__ void __launch_bounds__(256) k_errprofile_fold(const unsigned long lon
     out[i] = v;
 }
 
-__global__ void __launch_bounds__(256) k_errprofile(RegionDev R, const ErrRangeDev *tab, int n_ranges, int n_total, int steps, int shards, int min_depth, int permille, unsigned long long *out) {
+__global__ void __launch_bounds__(256) k_errprofile(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, int steps, int shards, int min_depth, int permille, unsigned long long *out) {
     __shared__ unsigned long long prof[ERR_CELLS];
     const int tid = (int)threadIdx.x, lane = tid & 63;
     for (int j = tid; j < ERR_CELLS; j += 256) prof[j] = 0;
@@ -161,13 +159,13 @@ extern "C" const char *uvc_errprofile_level_name(int id) { return (id >= 0 && id
 extern "C" int64_t uvc_errprofile_scratch_cells(void) { return (int64_t)ERR_MAX_SHARDS * ERR_CELLS; }
 // d_tab: n_ranges + 1 entries of { plane index of the first position, first compact position }, the last one { 0, n_total }; d_out: one profile;
 // d_scratch: uvc_errprofile_scratch_cells() words
-extern "C" void uvc_launch_errprofile(const RegionDev *R, const void *d_tab, int n_ranges, int64_t n_total, int min_depth, int max_alt_permille, long long *d_out, long long *d_scratch, hipStream_t s) {
+extern "C" void uvc_launch_errprofile(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, int min_depth, int max_alt_permille, long long *d_out, long long *d_scratch, hipStream_t s) {
     if (n_ranges <= 0 || n_total <= 0) return;
     int steps, shards; long long n_blocks;
     err_geometry(n_total, steps, n_blocks, shards);
     unsigned long long *d_parts = (unsigned long long *)(shards > 1 ? d_scratch : d_out);
     const int n_cells = ERR_CELLS * shards;
     hipLaunchKernelGGL(k_errprofile_init, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, s, d_parts, n_cells);
-    hipLaunchKernelGGL(k_errprofile, dim3((unsigned)n_blocks), dim3(256), 0, s, *R, (const ErrRangeDev *)d_tab, n_ranges, (int)n_total, steps, shards, min_depth, max_alt_permille, d_parts);
+    hipLaunchKernelGGL(k_errprofile, dim3((unsigned)n_blocks), dim3(256), 0, s, *R, d_tab, n_ranges, (int)n_total, steps, shards, min_depth, max_alt_permille, d_parts);
     if (shards > 1) hipLaunchKernelGGL(k_errprofile_fold, dim3((unsigned)((ERR_CELLS + 255) / 256)), dim3(256), 0, s, d_parts, shards, (unsigned long long *)d_out);
 }

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <stdint.h>
-#include "uvcgpu.h"
+#include "uvc_launch.h"
 
 extern "C" size_t uvc_gap_sort_tmp_bytes(size_t n) {
     size_t bytes = 0;

@@ -19,6 +19,7 @@
 #include "uvcgpu.h"
 #include "uvcgroup.h"
 #include "uvc_alloc.h"
+#include "uvc_host.h"
 #define hipMalloc(p, n) uvc_dev_malloc((void **)(p), (n))
 #define hipFree(p) uvc_dev_free((void *)(p))
 
@@ -27,8 +28,6 @@
 #define G_OUTER 10               // ARRPOS_OUTER_RANGE
 #define G_INNER 3                // ARRPOS_INNER_RANGE
 typedef unsigned long long u64;
-
-extern "C" int uvcgpu_set_error(int code, const char *msg);   // uvc_host.cpp
 
 struct GCols { const int32_t *tid, *pos, *endpos, *mtid, *mpos, *isize; const uint16_t *flag; const uint8_t *mapq; const u64 *q31, *q17, *u31, *u17; const uint8_t *umi_kind; };
 struct GWork {

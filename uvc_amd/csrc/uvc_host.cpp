@@ -1,7 +1,8 @@
 // uvc_host.cpp -- C ABI of libuvcgpu.so (include/uvcgpu.h): region handles, host-side packing of the
 // alns3-equivalent SoA into device records, kernel sequencing on the handle's HIP stream.
 // There is no CPU compute fallback in this library: every entry point that computes launches HIP kernels.
-#include "uvc_device.h"
+#include "uvc_launch.h"
+#include "uvc_host.h"
 #include "uvc_alloc.h"
 #include "uvc_prep.h"
 #include "uvc_rtr.h"
@@ -20,60 +21,6 @@
 // device memory through the caching allocator (uvc_alloc.h): freed blocks are reused without the device-wide synchronisation of hipFree
 #define hipMalloc(p, n) uvc_dev_malloc((void **)(p), (n))
 #define hipFree(p) uvc_dev_free((void *)(p))
-
-struct RawReads {
-    const int32_t *pos, *endpos, *mpos, *isize, *nm, *l_qseq, *n_cigar, *frag, *fs, *dflag, *kind, *fast_rank;
-    const uint16_t *flag; const uint8_t *mapq;
-    const int64_t *seq_off, *cigar_off, *table_off, *item_off, *gap_off;
-};
-extern "C" void uvc_launch_correct_bq(const RegionDev *R, int bq_max, int bq_inc, hipStream_t s);
-extern "C" void uvc_launch_pack_bq(const uint8_t *bases, const uint8_t *quals, uint16_t *bq, int64_t n, int32_t *bad, hipStream_t s);
-extern "C" void uvc_launch_build_p2list(const RegionDev *R, const int32_t *fast_rank, const int32_t *aln, const int32_t *cbeg, const int32_t *cend, const int32_t *qb, hipStream_t s);
-extern "C" void uvc_launch_prelude(const RegionDev *R, const RawReads *W, const UvcParams *P, hipStream_t s);
-struct UvcProf { int on; int n; const char *name[32]; hipEvent_t ev[32][2]; };
-extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred,
-                                      const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work, hipStream_t s, UvcProf *prof,
-                                      hipStream_t side, hipEvent_t e_fork, hipEvent_t e_join, hipEvent_t e_fork2, hipStream_t side3, hipEvent_t e_join3, hipEvent_t e_stat, hipEvent_t e_alleles);
-extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity, char *scratch, int32_t *d_fields_kept, const int32_t *d_force_sites,
-                                const void *d_ranges, int64_t n_ranges, int64_t n_compact, hipStream_t s);
-extern "C" size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity);
-// the streamed form (uvcgpu_region_score_stream_*): one gate pass + the chunk cut, then the per-record kernels per chunk into a row set
-extern "C" int uvc_launch_score_gate(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                     const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
-                                     const void *d_ranges, int64_t n_ranges, int64_t n_compact, int64_t chunk_records, int64_t tab_cap, hipStream_t s);
-extern "C" int uvc_launch_score_chunk(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                      const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
-                                      const void *d_ranges, int64_t n_ranges, int64_t n_compact, char *set, int64_t chunk_records, int with_kept,
-                                      int64_t win_g, int64_t win_n, int64_t win_groups, int64_t win_records, hipStream_t s);
-extern "C" size_t uvc_score_set_bytes(int64_t chunk_records, int64_t ngroups, int with_kept);
-extern "C" size_t uvc_score_set_bytes_per_record(void);
-extern "C" int32_t *uvc_score_set_fields(char *set, int64_t chunk_records, int64_t ngroups, int kept);
-extern "C" size_t uvc_score_stream_pos_bytes(int64_t npos_scored, int64_t tab_cap);
-extern "C" size_t uvc_score_stream_table_offset(int64_t npos_scored);
-extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity);
-extern "C" void uvc_launch_zero_state(char *slab, const void *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s);
-extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
-extern "C" void uvc_launch_check_presence(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
-extern "C" void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s);
-extern "C" void uvc_launch_block_stats_windows(const RegionDev *R, const UvcParams *P, const long long *d_win, int n_win, int64_t n, int32_t *d_out, hipStream_t s);
-extern "C" void uvc_launch_coverage(const RegionDev *R, const void *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s);
-extern "C" const char *uvc_coverage_name(int id);
-extern "C" int64_t uvc_coverage_scratch_rows(int n_ranges, int64_t n_total);
-extern "C" void uvc_launch_errprofile(const RegionDev *R, const void *d_tab, int n_ranges, int64_t n_total, int min_depth, int max_alt_permille, long long *d_out, long long *d_scratch, hipStream_t s);
-extern "C" const char *uvc_errprofile_level_name(int id);
-extern "C" int64_t uvc_errprofile_scratch_cells(void);
-extern "C" size_t uvc_gap_sort_tmp_bytes(size_t n);
-extern "C" void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
-extern "C" void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
-extern "C" void uvc_launch_gather_columns(const char *const *base, const int32_t *first_col, const int32_t *elem, int64_t npos, const int32_t *d_xs, int64_t n, long long *d_out, hipStream_t s);
-extern "C" int uvc_sort_by_pos_cls(const int32_t *d_pos, const int32_t *d_cls, int32_t beg, int pos_bits, int cls_bits, int64_t n, uint32_t *work, void *tmp, size_t tmp_bytes, hipStream_t s);
-extern "C" size_t uvc_sort32_tmp_bytes(size_t n);
-extern "C" size_t uvc_prep_compact_tmp_bytes(int64_t n);
-extern "C" int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, int64_t n, int64_t n_bases, const uint8_t *bases4, int64_t n_b4, const uint8_t *quals, int64_t *seq_off_out, const int64_t *seq_off_in,
-                                int64_t *cigar_off_out, int64_t *b4_off, uint8_t *bases_out, uint16_t *bq_out, int32_t *bad, void *tmp, size_t tmp_bytes, hipStream_t s);
-extern "C" void uvc_launch_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3, hipStream_t s);
-extern "C" void uvc_launch_rank_from_sorted(const uint32_t *perm, int64_t n, int64_t n_first, int32_t *out_ids, int32_t *rank, hipStream_t s);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -117,7 +64,7 @@ struct uvcgpu_region {
     bool has_reads = false, accumulated = false;
     size_t p5flag_off = 0, occ_off = 0;
     // zero fill without what the last accumulate left untouched (RegionDev::dirty, uvc_launch_zero_state)
-    uint8_t *d_dirty = nullptr; void *d_zero_planes = nullptr; int n_zero_planes = 0; int64_t zero_planes_npos = 0;
+    uint8_t *d_dirty = nullptr; ZeroPlane *d_zero_planes = nullptr; int n_zero_planes = 0; int64_t zero_planes_npos = 0;
     int64_t dirty_npos = 0;      // the region length under which the slab's contents and the marks were written; 0: unknown, fill everything
     bool state_released = false, state_zeroed = false;   // UvcScoreRequest::release_state: planes given up / already zeroed on the side stream (e_join marks the end)
     int64_t last_scored = 0, last_returned = 0;   // record counts of the last score call (uvcgpu_region_last_score_counts)
@@ -614,14 +561,13 @@ int uvcgpu_region_read_quals(uvcgpu_region_t *r, uint8_t *dst, int64_t n) {
 // Zero fill of the plane slab (everything in front of the bucket planes, and the bucket planes too unless P3b / P5b left them clean) on
 // stream `s`.  When the slab's contents were written under the present layout, only what every accumulate writes and what the last one marked
 // (RegionDev::dirty) is filled; otherwise (first use, the handle was rebound to a region of another length) the whole slab.
-struct ZeroPlaneHost { unsigned long long off; int32_t elem; int16_t fam, sym; };
 static int zero_state(uvcgpu_region *r, hipStream_t s) {
     const size_t n_dirty = (size_t)3 * NSYM * (size_t)r->R.ndblk;
     const bool selective = (r->dirty_npos == r->npos && !getenv("UVCGPU_FILL_ALL"));
     r->dirty_npos = 0;   // from here on the slab and the marks describe no layout until the caller's launch went through and restores it
     if (selective) {
         if (r->zero_planes_npos != r->npos) {   // the plane table of this layout (once per region length)
-            std::vector<ZeroPlaneHost> v;
+            std::vector<ZeroPlane> v;
             const size_t n = (size_t)r->npos;
             auto sym_planes = [&](int g, int nplanes, int elem, int fam) {
                 for (int pl = 0; pl < nplanes; pl++) for (int sy = 0; sy < NSYM; sy++) {
@@ -639,8 +585,8 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
             v.push_back({ (unsigned long long)r->p5flag_off, 1, -1, 0 }); v.push_back({ (unsigned long long)(r->p5flag_off + n), 1, -1, 0 });
             v.push_back({ (unsigned long long)r->occ_off, 4, -1, 0 });
             if (r->d_zero_planes) { quiesce(r); hipFree(r->d_zero_planes); r->d_zero_planes = nullptr; }
-            HIP_OK(hipMalloc(&r->d_zero_planes, v.size() * sizeof(ZeroPlaneHost)));
-            HIP_OK(hipMemcpy(r->d_zero_planes, v.data(), v.size() * sizeof(ZeroPlaneHost), hipMemcpyHostToDevice));
+            HIP_OK(hipMalloc(&r->d_zero_planes, v.size() * sizeof(ZeroPlane)));
+            HIP_OK(hipMemcpy(r->d_zero_planes, v.data(), v.size() * sizeof(ZeroPlane), hipMemcpyHostToDevice));
             r->n_zero_planes = (int)v.size(); r->zero_planes_npos = r->npos;
         }
         uvc_launch_zero_state(r->d_state, r->d_zero_planes, r->n_zero_planes, r->d_dirty, r->R.ndblk, r->npos, s);
@@ -670,7 +616,8 @@ static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
         // rows were set to 0xFF in set_reads and k_p2_slow<false> is idempotent under MAX, so no reset is needed
     }
     const int half = (int)std::round((10.0 / std::log(10.0)) * std::log(r->P.indel_del_to_ins_err_ratio)) / 2;   // main.hpp:1244
-    uvc_launch_accumulate(&r->R, &r->P, half, r->d_dup_units, r->n_dup, r->d_dup_off, r->n_dup_work, r->stream, &r->prof, r->side, r->e_fork, r->e_join, r->e_fork2, r->side3, r->e_join3, r->e_stat, r->e_alleles);
+    const UvcAccStreams st = { r->stream, r->side, r->side3, r->e_fork, r->e_join, r->e_fork2, r->e_join3, r->e_stat, r->e_alleles };
+    uvc_launch_accumulate(&r->R, &r->P, half, r->d_dup_units, r->n_dup, r->d_dup_off, r->n_dup_work, &st, &r->prof);
     HIP_OK(hipGetLastError());
     r->buckets_clean = (r->P.inferred_is_vcf_generated != 0);   // k_frag (P3b) and k_p5b cleared every bucket they consumed
     r->dirty_npos = r->npos;   // the slab and the marks now describe this layout
@@ -879,7 +826,6 @@ const int32_t *uvcgpu_region_repeat_tracks(const uvcgpu_region_t *cr, int64_t *n
     return r->h_rtr.data();
 }
 const UvcParams *uvcgpu_region_params(const uvcgpu_region_t *r) { return &r->P; }
-int uvcgpu_fail_(int code, const char *msg) { return fail(code, msg); }
 
 // ---- InDel allele tables: the host half of fill_by_indel_info / indel_get_majority (instcode.hpp, main.hpp:5350-5455) ----
 // The device reduces the allele-keyed counters to one GapRow per (position, symbol, allele) (k_gap_rows); what is left is per InDel
@@ -1101,16 +1047,15 @@ static int stage_upload(uvcgpu_region_t *r, void *dst, const void *src, size_t b
 }
 
 // `ranges` (uvcgpu_region_score_ranges) or NULL (uvcgpu_region_score): everything but the group axis is the same call
-struct ScoreRangeDev { int32_t beg, end, first, flags; };   // UvcScoreRangeDev of uvc_kernels_score.hip
 // What a score request becomes before any scoring kernel runs -- the checked request, the ranges' device table, the caller's alleles merged
 // with the region's, tumor keys, force-output sites, all uploaded through the staging buffer -- for the one call and for a stream alike.
 // The temporaries go back to the caching allocator, which hands them to other handles at once: the destructor drains the stream first
 // (async copies, kernels that read the blocks), then frees them.
 struct ScorePrep {
     uvcgpu_region *r = nullptr;
-    UvcScoreRequest rq; std::vector<ScoreRangeDev> rtab; int64_t npos_scored = 0;
-    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; ScoreRangeDev *d_rg = nullptr;
-    const UvcIndelAllele *use_al = nullptr; const int32_t *use_row = nullptr; int64_t n_al = 0;
+    UvcScoreRequest rq; std::vector<UvcScoreRangeDev> rtab; int64_t npos_scored = 0;
+    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; UvcScoreRangeDev *d_rg = nullptr;
+    UvcScoreIn in = {};   // what the score launchers take: views of the above and of the handle (scratch: set where the scratch is allocated)
     ~ScorePrep() {
         if (!r) return;
         if (d_al || d_al_row || d_tk || d_fs || d_rg) { (void)hipStreamSynchronize(r->stream); if (r->side) (void)hipStreamSynchronize(r->side); }
@@ -1125,7 +1070,7 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
     p.r = r;
     UvcScoreRequest &rq = p.rq; memset(&rq, 0, sizeof(rq)); rq.pos_beg = -1;
     if (req) rq = *req;
-    std::vector<ScoreRangeDev> &rtab = p.rtab;   // ranges call: the device table; npos_scored = the compact length
+    std::vector<UvcScoreRangeDev> &rtab = p.rtab;   // ranges call: the device table; npos_scored = the compact length
     int64_t &npos_scored = p.npos_scored;
     if (ranges) {
         if (n_ranges < 1 || n_ranges > INT32_MAX) return fail(UVCGPU_EINVAL, "score_ranges: n_ranges must be at least 1");
@@ -1137,7 +1082,7 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
                 return fail(UVCGPU_EINVAL, "score_ranges: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ") is outside the region");
             if (k > 0 && q.pos_beg < ranges[k - 1].pos_end)
                 return fail(UVCGPU_EINVAL, "score_ranges: range " + std::to_string(k) + " begins at " + std::to_string(q.pos_beg) + ", in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-            rtab[(size_t)k] = ScoreRangeDev{ q.pos_beg, q.pos_end, (int32_t)npos_scored, q.base_at_pos_beg ? 1 : 0 };
+            rtab[(size_t)k] = UvcScoreRangeDev{ q.pos_beg, q.pos_end, (int32_t)npos_scored, q.base_at_pos_beg ? 1 : 0 };
             npos_scored += (int64_t)q.pos_end - q.pos_beg;
         }
         rq.pos_beg = ranges[0].pos_beg; rq.pos_end = ranges[n_ranges - 1].pos_end;   // (the kernels take the table; these only keep the request well-formed)
@@ -1150,14 +1095,13 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
     }
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
-    UvcIndelAllele *&d_al = p.d_al; int32_t *&d_al_row = p.d_al_row; UvcTumorKey *&d_tk = p.d_tk; int32_t *&d_fs = p.d_fs; ScoreRangeDev *&d_rg = p.d_rg;
+    UvcIndelAllele *&d_al = p.d_al; int32_t *&d_al_row = p.d_al_row; UvcTumorKey *&d_tk = p.d_tk; int32_t *&d_fs = p.d_fs; UvcScoreRangeDev *&d_rg = p.d_rg;
     std::vector<UvcIndelAllele> merged; std::vector<int32_t> merged_row;
-    const UvcIndelAllele *&use_al = p.use_al; const int32_t *&use_row = p.use_row; int64_t &n_al = p.n_al;
-    use_al = r->d_gap_alleles; use_row = r->d_gap_allele_row; n_al = (int64_t)r->gap_alleles.size();
+    const UvcIndelAllele *use_al = r->d_gap_alleles; const int32_t *use_row = r->d_gap_allele_row; int64_t n_al = (int64_t)r->gap_alleles.size();
     // one staging layout per call (an earlier call's copies are complete: score synchronises before it returns)
     size_t stage_at = 0;
     const size_t stage_total = (sizeof(UvcIndelAllele) + sizeof(int32_t)) * (size_t)(r->gap_alleles.size() + (size_t)std::max<int64_t>(rq.n_indel_alleles, 0)) + sizeof(UvcTumorKey) * (size_t)std::max<int64_t>(rq.n_tumor_keys, 0)
-                              + sizeof(int32_t) * (size_t)std::max<int64_t>(rq.n_force_sites, 0) + sizeof(ScoreRangeDev) * rtab.size() + 320;
+                              + sizeof(int32_t) * (size_t)std::max<int64_t>(rq.n_force_sites, 0) + sizeof(UvcScoreRangeDev) * rtab.size() + 320;
     if (rq.n_indel_alleles > 0) {
         auto less = [](const UvcIndelAllele &a, const UvcIndelAllele &b) { return a.refpos < b.refpos || (a.refpos == b.refpos && a.symbol < b.symbol); };
         for (int64_t q = 1; q < rq.n_indel_alleles; q++) if (less(rq.indel_alleles[q], rq.indel_alleles[q - 1])) return fail(UVCGPU_EINVAL, "indel_alleles must be sorted by (refpos, symbol)");
@@ -1192,18 +1136,17 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
         { int rc1 = stage_upload(r, d_fs, rq.force_sites, sizeof(int32_t) * (size_t)rq.n_force_sites, stage_at, stage_total); if (rc1) return rc1; }
     }
     if (!rtab.empty()) {   // the ranges, through the staging buffer like the keys and the sites (k_range_map makes the position table)
-        HIP_OK(hipMalloc((void **)&d_rg, sizeof(ScoreRangeDev) * rtab.size()));
-        { int rc1 = stage_upload(r, d_rg, rtab.data(), sizeof(ScoreRangeDev) * rtab.size(), stage_at, stage_total); if (rc1) return rc1; }
+        HIP_OK(hipMalloc((void **)&d_rg, sizeof(UvcScoreRangeDev) * rtab.size()));
+        { int rc1 = stage_upload(r, d_rg, rtab.data(), sizeof(UvcScoreRangeDev) * rtab.size(), stage_at, stage_total); if (rc1) return rc1; }
     }
+    p.in = UvcScoreIn{ &r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, nullptr, d_fs, d_rg, (int64_t)rtab.size(), npos_scored };
     return 0;
 }
 static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
     if (!r || !out || !out->fields) return fail(UVCGPU_EINVAL, "bad argument");
     ScorePrep prep;   // (its destructor frees the temporaries on every return path)
     { const int rc0 = score_prepare(r, req, ranges, n_ranges, prep); if (rc0) return rc0; }
-    const UvcScoreRequest &rq = prep.rq; const std::vector<ScoreRangeDev> &rtab = prep.rtab; const int64_t npos_scored = prep.npos_scored;
-    const UvcIndelAllele *use_al = prep.use_al; const int32_t *use_row = prep.use_row; const int64_t n_al = prep.n_al;
-    UvcTumorKey *d_tk = prep.d_tk; int32_t *d_fs = prep.d_fs; ScoreRangeDev *d_rg = prep.d_rg;
+    const UvcScoreRequest &rq = prep.rq; const int64_t npos_scored = prep.npos_scored;
     const bool kept_only = (rq.kept_only != 0);
     // device capacity: the caller's in the plain form; with kept_only the caller's buffer only has to hold the kept groups, the device
     // array every record -- start from a guess and grow once if the count says so
@@ -1237,8 +1180,8 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos_scored, r->score_capacity), r->stream));
         int pi = -1;   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
         if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = "k_score_all"; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); }
-        rc = uvc_launch_score(&r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, r->d_score_fields, r->score_capacity, r->d_score_scratch,
-                              kept_only ? r->d_score_kept : nullptr, d_fs, d_rg, (int64_t)rtab.size(), npos_scored, r->stream);
+        prep.in.scratch = r->d_score_scratch;
+        rc = uvc_launch_score(&prep.in, r->d_score_fields, r->score_capacity, kept_only ? r->d_score_kept : nullptr, r->stream);
         if (rc) rc = fail(rc, "score: the force-output mask could not be cleared");
         if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream);
         if (!rc && hipGetLastError() != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score kernel launch failed");
@@ -1308,8 +1251,7 @@ static int stream_launch_chunk(uvcgpu_score_stream *s, int64_t k) {
     const int64_t *t = &s->tab[(size_t)k * 4];
     const int64_t c = s->chunk_records, nr = t[3];
     const int64_t win_groups = std::min<int64_t>(std::min<int64_t>(t[1], nr), c);   // active groups of the window: at most its groups, at most its records
-    int rc = uvc_launch_score_chunk(&r->R, &r->P, &p.rq, p.use_al, p.use_row, p.n_al, r->d_gap_rows, r->d_gap_seq, p.d_tk, r->d_score_scratch, p.d_fs, p.d_rg, (int64_t)p.rtab.size(), p.npos_scored,
-                                    q.d, c, s->with_kept, t[0], t[1], win_groups, nr, r->stream);
+    int rc = uvc_launch_score_chunk(&p.in, q.d, c, s->with_kept, t[0], t[1], win_groups, nr, r->stream);
     if (rc) return fail(rc, "score stream: chunk launch refused");
     if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "score stream: kernel launch failed");
     hipStream_t cs = r->side ? r->side : r->stream;
@@ -1369,6 +1311,7 @@ static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcSc
         r->score_scratch_bytes = pos_need;
     }
     r->d_score_count = (int64_t *)r->d_score_scratch;
+    prep->in.scratch = r->d_score_scratch;   // (the chunks of the stream use it too)
     const int with_kept = rq.kept_only ? 1 : 0;
     const size_t set_need = uvc_score_set_bytes(chunk_records, ngroups, with_kept), host_need = sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)chunk_records + UVC_STREAM_HOST_TAIL;
     if (s->chunk_records != chunk_records) stream_free_sets(s);
@@ -1393,8 +1336,7 @@ static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcSc
     else s->ranges.push_back(UvcScoreRange{ rq.pos_beg, rq.pos_end, rq.base_at_pos_beg ? 1 : 0, rq.region_beg });
     if (npos > 0) {
         HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos, 1), r->stream));
-        int rc = uvc_launch_score_gate(&r->R, &r->P, &rq, prep->use_al, prep->use_row, prep->n_al, r->d_gap_rows, r->d_gap_seq, prep->d_tk, r->d_score_scratch, prep->d_fs, prep->d_rg, (int64_t)prep->rtab.size(), npos,
-                                       chunk_records, tab_cap, r->stream);
+        int rc = uvc_launch_score_gate(&prep->in, chunk_records, tab_cap, r->stream);
         if (rc) return fail(rc, "score stream: the force-output mask could not be cleared");
         if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "score stream: kernel launch failed");
         { const int rcs = uvcgpu_region_sync(r); if (rcs) return rcs; }
@@ -1474,7 +1416,6 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
 }
 
 // ---- depth statistics of ranges (uvc_coverage.hip) ----
-struct CovRangeHost { int32_t x0, first; };   // CovRangeDev of uvc_coverage.hip, ErrRangeDev of uvc_errprofile.hip
 // the device and the page-locked buffer that uvcgpu_region_coverage and uvcgpu_region_error_profile share (both synchronise before they return), grown on demand
 static int cov_buffers(uvcgpu_region_t *r, size_t dev_bytes, size_t out_bytes, const char *what) {
     if (dev_bytes > r->d_cov_bytes) {
@@ -1506,7 +1447,7 @@ static int uvcgpu_region_coverage_impl(uvcgpu_region_t *r, const UvcCoverageRang
         if (thresholds[k] < 0) return fail(UVCGPU_EINVAL, "coverage: threshold " + std::to_string(k) + " is negative (" + std::to_string(thresholds[k]) + ")");
         if (k > 0 && thresholds[k] <= thresholds[k - 1]) return fail(UVCGPU_EINVAL, "coverage: threshold " + std::to_string(k) + " (" + std::to_string(thresholds[k]) + ") is not larger than the one before it (" + std::to_string(thresholds[k - 1]) + "): thresholds ascend");
     }
-    std::vector<CovRangeHost> tab((size_t)n_ranges + 1);
+    std::vector<UvcRangeRow> tab((size_t)n_ranges + 1);
     int64_t n_total = 0;
     for (int64_t k = 0; k < n_ranges; k++) {
         const UvcCoverageRange &q = ranges[k];
@@ -1514,20 +1455,20 @@ static int uvcgpu_region_coverage_impl(uvcgpu_region_t *r, const UvcCoverageRang
         if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
         if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
         if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-        tab[(size_t)k] = CovRangeHost{ q.pos_beg - r->beg, (int32_t)n_total };
+        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
         n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
     }
-    tab[(size_t)n_ranges] = CovRangeHost{ 0, (int32_t)n_total };
-    const size_t tab_bytes = (sizeof(CovRangeHost) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)n_ranges;
+    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
+    const size_t tab_bytes = (sizeof(UvcRangeRow) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)n_ranges;
     const int64_t scratch_rows = uvc_coverage_scratch_rows((int)n_ranges, n_total);   // the shard copies of few long ranges (0: the waves merge into the result rows)
     const size_t dev_bytes = tab_bytes + out_bytes + sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)scratch_rows;   // [table] [result rows] [scratch rows]
     { int rc1 = cov_buffers(r, dev_bytes, out_bytes, "coverage rows"); if (rc1) return rc1; }
     // the table through the handle's staging buffer (stage_upload: never an asynchronous copy from the caller's or the heap's pages); an earlier
     // call's copy out of it is complete, every user of the buffer synchronises before it returns
     size_t at = 0;
-    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(CovRangeHost) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
+    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(UvcRangeRow) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
     long long *d_rows = (long long *)(r->d_cov + tab_bytes);
-    uvc_launch_coverage(&r->R, r->d_cov, (int)n_ranges, n_total, thresholds, n_thresholds, d_rows, (long long *)(r->d_cov + tab_bytes + out_bytes), scratch_rows, r->stream);
+    uvc_launch_coverage(&r->R, (const UvcRangeRow *)r->d_cov, (int)n_ranges, n_total, thresholds, n_thresholds, d_rows, (long long *)(r->d_cov + tab_bytes + out_bytes), scratch_rows, r->stream);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(r->h_cov, d_rows, out_bytes, hipMemcpyDeviceToHost, r->stream));
     { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
@@ -1550,7 +1491,7 @@ static int uvcgpu_region_error_profile_impl(uvcgpu_region_t *r, const UvcCoverag
     if (req->max_alt_permille < 0 || req->max_alt_permille > 1000) return fail(UVCGPU_EINVAL, "error_profile: max_alt_permille " + std::to_string(req->max_alt_permille) + " is outside 0..1000");
     if (n_ranges < 1) return fail(UVCGPU_EINVAL, "error_profile: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
     if (n_ranges > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "error_profile: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
-    std::vector<CovRangeHost> tab((size_t)n_ranges + 1);
+    std::vector<UvcRangeRow> tab((size_t)n_ranges + 1);
     int64_t n_total = 0;
     for (int64_t k = 0; k < n_ranges; k++) {
         const UvcCoverageRange &q = ranges[k];
@@ -1558,17 +1499,17 @@ static int uvcgpu_region_error_profile_impl(uvcgpu_region_t *r, const UvcCoverag
         if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
         if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
         if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-        tab[(size_t)k] = CovRangeHost{ q.pos_beg - r->beg, (int32_t)n_total };
+        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
         n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
     }
-    tab[(size_t)n_ranges] = CovRangeHost{ 0, (int32_t)n_total };
-    const size_t tab_bytes = (sizeof(CovRangeHost) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NERRLEVEL * UVC_ERR_ROW;
+    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
+    const size_t tab_bytes = (sizeof(UvcRangeRow) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NERRLEVEL * UVC_ERR_ROW;
     const size_t dev_bytes = tab_bytes + out_bytes + sizeof(int64_t) * (size_t)uvc_errprofile_scratch_cells();   // [table] [profile] [shard copies]
     { int rc1 = cov_buffers(r, dev_bytes, out_bytes, "error profile"); if (rc1) return rc1; }
     size_t at = 0;   // the table through the handle's staging buffer, as coverage sends its own
-    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(CovRangeHost) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
+    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(UvcRangeRow) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
     long long *d_prof = (long long *)(r->d_cov + tab_bytes);
-    uvc_launch_errprofile(&r->R, r->d_cov, (int)n_ranges, n_total, req->min_depth, req->max_alt_permille, d_prof, (long long *)(r->d_cov + tab_bytes + out_bytes), r->stream);
+    uvc_launch_errprofile(&r->R, (const UvcRangeRow *)r->d_cov, (int)n_ranges, n_total, req->min_depth, req->max_alt_permille, d_prof, (long long *)(r->d_cov + tab_bytes + out_bytes), r->stream);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(r->h_cov, d_prof, out_bytes, hipMemcpyDeviceToHost, r->stream));
     { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }

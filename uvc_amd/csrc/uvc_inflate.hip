@@ -20,9 +20,8 @@
 #include <vector>
 #include "uvcgpu.h"
 #include "uvc_alloc.h"
+#include "uvc_host.h"
 #include "uvc_inflate_core.h"
-
-extern "C" int uvcgpu_set_error(int code, const char *msg);   // uvc_host.cpp
 
 #define DEV_INLINE __device__ __forceinline__
 struct BgzfBlockDev { unsigned long long in_off, out_off; uint32_t in_len, out_len; };

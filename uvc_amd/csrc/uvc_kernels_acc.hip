@@ -34,7 +34,7 @@
 //   k_p5b            per (position, strand)  bucket -> quality for family consensus           main.hpp:3552-3591
 //   k_gap_keys/alleles/rows  per (family, InDel position)  the allele-keyed counters of the InDel symbols   main.hpp:2710-2717, 3196-3546
 // uvc_launch_accumulate at the end of the file orders them on two streams.
-#include "uvc_device.h"
+#include "uvc_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // small helpers
@@ -364,11 +364,6 @@ DEV void primer_window(const UvcParams &P, const AlnRec &a, int &ibeg, int &iend
 // ------------------------------------------------------------------------------------------------
 // k_aln_prelude: one thread per alignment (main.hpp:1795-1885 prelude of updateByAln)
 // ------------------------------------------------------------------------------------------------
-struct RawReads {   // the caller's columns as they are (uvcgpu_region_set_reads) + what uvc_prep.hip derives per read
-    const int32_t *pos, *endpos, *mpos, *isize, *nm, *l_qseq, *n_cigar, *frag, *fs, *dflag, *kind, *fast_rank;
-    const uint16_t *flag; const uint8_t *mapq;
-    const int64_t *seq_off, *cigar_off, *table_off, *item_off, *gap_off;
-};
 
 // does the read have an InDel next to low base qualities (main.hpp:1817-1859)?  Then dist_to_interfering_indel varies along the
 // read and its M runs cannot take the simple path of k_p2_fast.
@@ -3555,13 +3550,10 @@ extern "C" void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, co
     else hipLaunchKernelGGL(k_hap_frags, dim3((unsigned)n_cand), dim3(64), 0, s, *R, *P, *H, n_cand);
 }
 
-extern "C" int uvc_gap_sort(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout, const unsigned long long *vin, unsigned long long *vout,
-                            size_t n, int end_bit, hipStream_t s);
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 static inline int imin_h(int a, int b) { return a < b ? a : b; }
 
-// optional per-kernel HIP-event timing on the handle's own stream (bench.py roofline leg)
-struct UvcProf { int on; int n; const char *name[32]; hipEvent_t ev[32][2]; };
+// optional per-kernel HIP-event timing on the handle's own stream (UvcProf, bench.py roofline leg)
 #define TIMED(prof, kname, ...) do { \
         UvcProf *p_ = (prof); int i_ = -1; \
         if (p_ && p_->on && p_->n < 32) { i_ = p_->n++; p_->name[i_] = kname; if (!p_->ev[i_][0]) { hipEventCreate(&p_->ev[i_][0]); hipEventCreate(&p_->ev[i_][1]); } hipEventRecord(p_->ev[i_][0], s); } \
@@ -3675,7 +3667,6 @@ extern "C" void uvc_launch_prelude(const RegionDev *R, const RawReads *W, const 
 // Zero fill of the plane slab in front of an accumulate, without the parts the last accumulate did not write (RegionDev::dirty): a block
 // per (plane, block of 4 096 positions).  A 1 Mb tile's slab is 5.6 KB per position; what every tile writes (the per-position planes, the
 // planes of A C G T N and LINK_M) is 2.5 KB of it, the rest a few per cent.
-struct ZeroPlane { unsigned long long off; int32_t elem; int16_t fam, sym; };   // fam < 0: always filled
 __global__ void __launch_bounds__(256) k_zero_state(char *slab, const ZeroPlane *planes, const uint8_t *dirty, int ndblk, int64_t npos) {
     const ZeroPlane zp = planes[blockIdx.x];
     const int b = (int)blockIdx.y;
@@ -3689,9 +3680,9 @@ __global__ void __launch_bounds__(256) k_zero_state(char *slab, const ZeroPlane 
     for (uint4 *q = (uint4 *)a0 + threadIdx.x; q < (uint4 *)a1; q += 256) *q = z;
     for (char *q = a1 + threadIdx.x; q < p1; q += 256) *q = 0;
 }
-extern "C" void uvc_launch_zero_state(char *slab, const void *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s) {
+extern "C" void uvc_launch_zero_state(char *slab, const ZeroPlane *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s) {
     if (n_planes <= 0 || ndblk <= 0) return;
-    hipLaunchKernelGGL(k_zero_state, dim3((unsigned)n_planes, (unsigned)ndblk), dim3(256), 0, s, slab, (const ZeroPlane *)planes, dirty, ndblk, npos);
+    hipLaunchKernelGGL(k_zero_state, dim3((unsigned)n_planes, (unsigned)ndblk), dim3(256), 0, s, slab, planes, dirty, ndblk, npos);
 }
 // uvcgpu_region_check_presence, second half: a (family, symbol, block) that is not marked holds only zeros
 __global__ void __launch_bounds__(256) k_check_dirty(RegionDev R, unsigned long long *n_bad) {
@@ -3718,35 +3709,57 @@ extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d
     hipLaunchKernelGGL(k_check_dirty, dim3((unsigned)((R->npos + 255) / 256), NSYM), dim3(256), 0, s, *R, d_n_bad);
 }
 
-extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred,
-                                      const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work, hipStream_t s, UvcProf *prof,
-                                      hipStream_t side, hipEvent_t e_fork, hipEvent_t e_join, hipEvent_t e_fork2, hipStream_t side3, hipEvent_t e_join3, hipEvent_t e_stat, hipEvent_t e_alleles) {
-    const unsigned nwin = nblk(R->npos, 256);   // 4 waves x 64 positions per block
+// The form each pass of the accumulate takes: decided once from the tile's shape, the parameters and the families' flags, then printed
+// (UVCGPU_TIMING) and launched from the same flags.
+struct AccForms { bool vcf, proton, split_windows, p2_plain, frag_plain, h16, fam, digest, duplex; int n_gen; };
+static AccForms acc_forms(const RegionDev *R, const UvcParams *P, int n_dup) {
+    AccForms F;
+    F.vcf = (P->inferred_is_vcf_generated != 0);
+    F.proton = (UVC_PLATFORM_IONTORRENT == P->inferred_sequencing_platform);
     // fewer windows than four per SIMD, and many reads on each (at least sixteen chunks of 64: at 300x a wave of the split form would get fewer
     // than two and pay its prologue for them -- twice as slow on the 1 Mb tile): a block per window in the kernels that can share a window's
     // reads among its waves (UVCGPU_SPLIT=0 / 1 forces)
     const char *sp_env = getenv("UVCGPU_SPLIT");
     const long long per_window = (long long)R->n_fast2 * (R->max_p2_span + 64) / (R->npos > 0 ? R->npos : 1);
-    const bool split_windows = sp_env ? (atoi(sp_env) != 0) : (R->nwin < 4 * 1024 && per_window >= 1024);
-    const bool proton = (UVC_PLATFORM_IONTORRENT == P->inferred_sequencing_platform);
+    F.split_windows = sp_env ? (atoi(sp_env) != 0) : (R->nwin < 4 * 1024 && per_window >= 1024);
     // P2: no IonTorrent values, no amplicon-flagged family, no primer length, median read length at or above
     // microadjust_median_readlen_thres: the specialisation without those arms
-    const bool p2_plain = !proton && !R->any_amplicon && !(P->primerlen > 0 && !(0x2 & P->primer_flag)) && (P->central_readlen >= P->microadjust_median_readlen_thres);
+    F.p2_plain = !F.proton && !R->any_amplicon && !(P->primerlen > 0 && !(0x2 & P->primer_flag)) && (P->central_readlen >= P->microadjust_median_readlen_thres);
     // P3: no IonTorrent values, no SSCS table cap, no padded deletions
-    const bool frag_plain = P->inferred_is_vcf_generated && !proton && !(0x1 & P->fam_flag) && !(P->microadjust_padded_deletion_flag & 0x1);
-    const bool h16 = (R->max_frag_depth < 65536) && !R->frag32;   // two 16-bit bucket counters per LDS word
-    const bool digest = (R->fam_digest != nullptr);              // set_reads chose the form of the family passes
-    const int n_gen = proton ? R->n_frags : R->n_sweep;          // fragments of k_frag_generic: all of them on IonTorrent, else the sweep list
-    if (getenv("UVCGPU_TIMING")) {   // the form each pass takes, "none" where it is not launched (tests/test_gpu_kernel_forms.py parses this line)
-        const bool vcf = P->inferred_is_vcf_generated, fam = (R->n_generic_fs > 0);
-        fprintf(stderr, "[uvcgpu accumulate] forms prep=%s p2=%s%s frag=%s,%s,%s family=%s duplex=%s frag_generic=%s\n",
-                !vcf ? "none" : split_windows ? "split" : "wave",
-                !vcf ? "none" : split_windows ? "split" : "wave", !vcf ? "" : p2_plain ? ",plain" : ",generic",
-                h16 ? "h16" : "b32", (split_windows && h16) ? "split" : "wave", frag_plain ? "plain" : "generic",
-                !fam ? "none" : digest ? "digest" : "generic",
-                !(fam && vcf && n_dup) ? "none" : digest ? "digest" : "generic",
-                !n_gen ? "none" : proton ? "all" : "sweep");
-    }
+    F.frag_plain = F.vcf && !F.proton && !(0x1 & P->fam_flag) && !(P->microadjust_padded_deletion_flag & 0x1);
+    F.h16 = (R->max_frag_depth < 65536) && !R->frag32;   // two 16-bit bucket counters per LDS word
+    F.fam = (R->n_generic_fs > 0);
+    F.digest = (R->fam_digest != nullptr);              // set_reads chose the form of the family passes
+    F.duplex = F.fam && F.vcf && n_dup;
+    F.n_gen = F.proton ? R->n_frags : R->n_sweep;          // fragments of k_frag_generic: all of them on IonTorrent, else the sweep list
+    return F;
+}
+// "none" where a pass is not launched (tests/test_gpu_kernel_forms.py parses this line)
+static void print_forms(const AccForms &F) {
+    fprintf(stderr, "[uvcgpu accumulate] forms prep=%s p2=%s%s frag=%s,%s,%s family=%s duplex=%s frag_generic=%s\n",
+            !F.vcf ? "none" : F.split_windows ? "split" : "wave",
+            !F.vcf ? "none" : F.split_windows ? "split" : "wave", !F.vcf ? "" : F.p2_plain ? ",plain" : ",generic",
+            F.h16 ? "h16" : "b32", (F.split_windows && F.h16) ? "split" : "wave", F.frag_plain ? "plain" : "generic",
+            !F.fam ? "none" : F.digest ? "digest" : "generic",
+            !F.duplex ? "none" : F.digest ? "digest" : "generic",
+            !F.n_gen ? "none" : F.proton ? "all" : "sweep");
+}
+// one pass of k_p2_fast over the P2 work list: LINK_M (DO_L) or the base symbols (DO_B), in the form F names
+template <bool DO_L, bool DO_B>
+static void launch_p2_fast(const char *kname, const AccForms &F, const RegionDev *R, const UvcParams *P, unsigned nwin, UvcProf *prof, hipStream_t s) {
+    if (F.split_windows && F.p2_plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
+    else if (F.split_windows) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
+    else if (F.p2_plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
+    else TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, false>), dim3(nwin), dim3(256), 0, s, *R, *P));
+}
+
+extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
+                                      const UvcAccStreams *st, UvcProf *prof) {
+    const hipStream_t s = st->s, side = st->side, side3 = st->side3;
+    const hipEvent_t e_fork = st->e_fork, e_join = st->e_join, e_fork2 = st->e_fork2, e_join3 = st->e_join3, e_stat = st->e_stat, e_alleles = st->e_alleles;
+    const unsigned nwin = nblk(R->npos, 256);   // 4 waves x 64 positions per block
+    const AccForms F = acc_forms(R, P, n_dup);
+    if (getenv("UVCGPU_TIMING")) print_forms(F);
     if (prof) prof->n = 0;
     hipStream_t s2 = (side ? side : s);
     hipStream_t s3 = ((side && side3) ? side3 : s2);   // the two CIGAR walks of the InDel reads are independent, one wave per 64 reads and long: a stream each
@@ -3761,7 +3774,7 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
         if (side && R->n_complex) { hipEventRecord(e_fork, s); hipStreamWaitEvent(s2, e_fork, 0); }
         if (R->n_complex) TIMED2(prof, "k_prep_slow", hipLaunchKernelGGL(k_prep_slow, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
         if (side && R->n_complex) hipEventRecord(e_join, s2);
-        if (split_windows) TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
+        if (F.split_windows) TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
         else TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<false>, dim3(nwin), dim3(256), 0, s, *R, *P));
         if (side && R->n_complex) hipStreamWaitEvent(s, e_join, 0);
     }
@@ -3782,17 +3795,10 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     // ---- main stream: the base symbols first, so that the queued mismatches (rare symbols, atomics: disjoint from the planes the
     // LINK_M pass stores to) are applied on a side stream while the LINK_M pass runs
     if (P->inferred_is_vcf_generated) {
-        const bool plain = p2_plain;
-        if (split_windows && plain) TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast_split<false, true, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (split_windows) TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast_split<false, true, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (plain) TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast<false, true, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
-        else TIMED(prof, "k_p2_fast_base", hipLaunchKernelGGL((k_p2_fast<false, true, false>), dim3(nwin), dim3(256), 0, s, *R, *P));
+        launch_p2_fast<false, true>("k_p2_fast_base", F, R, P, nwin, prof, s);
         if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s3, e_fork2, 0); }
         TIMED3(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
-        if (split_windows && plain) TIMED(prof, "k_p2_fast_link", hipLaunchKernelGGL((k_p2_fast_split<true, false, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (split_windows) TIMED(prof, "k_p2_fast_link", hipLaunchKernelGGL((k_p2_fast_split<true, false, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (plain) TIMED(prof, "k_p2_fast_link", hipLaunchKernelGGL((k_p2_fast<true, false, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
-        else TIMED(prof, "k_p2_fast_link", hipLaunchKernelGGL((k_p2_fast<true, false, false>), dim3(nwin), dim3(256), 0, s, *R, *P));
+        launch_p2_fast<true, false>("k_p2_fast_link", F, R, P, nwin, prof, s);
     }
     if (side) {
         hipEventRecord(e_join, s2); hipStreamWaitEvent(s, e_join, 0);
@@ -3822,15 +3828,15 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     if (side) { hipEventRecord(e_stat, s3); hipEventRecord(e_fork2, s2); }
     if (P->inferred_is_vcf_generated && R->n_complex) TIMED(prof, "k_p2_items", hipLaunchKernelGGL(k_p2_items, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
     {
-        if (n_gen) TIMED(prof, "k_frag_generic", hipLaunchKernelGGL(k_frag_generic, dim3(imin_h(n_gen, 1 << 20), imin_h((R->max_frag_span + 63) / 64, 16)), dim3(64), 0, s, *R, *P, proton ? (const int32_t *)nullptr : R->sweep_frags, n_gen));
+        if (F.n_gen) TIMED(prof, "k_frag_generic", hipLaunchKernelGGL(k_frag_generic, dim3(imin_h(F.n_gen, 1 << 20), imin_h((R->max_frag_span + 63) / 64, 16)), dim3(64), 0, s, *R, *P, F.proton ? (const int32_t *)nullptr : R->sweep_frags, F.n_gen));
     }
     {
-        const bool plain = frag_plain;
-        if (split_windows && h16 && plain) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16_split<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (split_windows && h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16_split<false>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (plain && h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16<true>, dim3(nwin), dim3(256), 0, s, *R, *P));
+        const bool plain = F.frag_plain;
+        if (F.split_windows && F.h16 && plain) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16_split<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
+        else if (F.split_windows && F.h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16_split<false>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
+        else if (plain && F.h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16<true>, dim3(nwin), dim3(256), 0, s, *R, *P));
         else if (plain) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag<true>, dim3(nwin), dim3(256), 0, s, *R, *P));
-        else if (h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16<false>, dim3(nwin), dim3(256), 0, s, *R, *P));
+        else if (F.h16) TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag16<false>, dim3(nwin), dim3(256), 0, s, *R, *P));
         else TIMED(prof, "k_frag", hipLaunchKernelGGL(k_frag<false>, dim3(nwin), dim3(256), 0, s, *R, *P));
     }
     if (R->n_generic_fs) {
@@ -3838,14 +3844,14 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
         // shallow data: the generic form, one thread per (unit, position); deep data (many units per position, e.g. UMI panels): the digest
         // form, window kernels whose LDS collection removes most of the atomics that bound the per-thread form, and one walk over the
         // fragments of a unit instead of three.  set_reads chose the form: the digest is allocated for the second.
-        if (digest) TIMED(prof, "k_fam_p4", { hipLaunchKernelGGL(k_fam_p4d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P);
+        if (F.digest) TIMED(prof, "k_fam_p4", { hipLaunchKernelGGL(k_fam_p4d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P);
                                                hipLaunchKernelGGL(k_fam_p4d_rest, dim3(R->n_generic_fs), dim3(64), 0, s, *R, *P); });
         else TIMED(prof, "k_fam_p4", hipLaunchKernelGGL(k_fam_p4, dim3(nblk(R->n_generic_work, 256)), dim3(256), 0, s, *R, *P));
         if (P->inferred_is_vcf_generated) {
-            if (digest) TIMED(prof, "k_fam_p5", hipLaunchKernelGGL(k_fam_p5d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P));
+            if (F.digest) TIMED(prof, "k_fam_p5", hipLaunchKernelGGL(k_fam_p5d, dim3(nblk(R->npos, 64)), dim3(256), 0, s, *R, *P));
             else TIMED(prof, "k_fam_p5", hipLaunchKernelGGL(k_fam_p5, dim3(nblk(R->n_generic_work, 256)), dim3(256), 0, s, *R, *P));
-            if (n_dup && digest) TIMED(prof, "k_duplex", hipLaunchKernelGGL(k_duplex_d, dim3(n_dup), dim3(64), 0, s, *R, dup_units, n_dup, dup_off, n_dup_work));
-            else if (n_dup) TIMED(prof, "k_duplex", hipLaunchKernelGGL(k_duplex, dim3(nblk(n_dup_work, 256)), dim3(256), 0, s, *R, *P, dup_units, n_dup, dup_off, n_dup_work));
+            if (F.duplex && F.digest) TIMED(prof, "k_duplex", hipLaunchKernelGGL(k_duplex_d, dim3(n_dup), dim3(64), 0, s, *R, dup_units, n_dup, dup_off, n_dup_work));
+            else if (F.duplex) TIMED(prof, "k_duplex", hipLaunchKernelGGL(k_duplex, dim3(nblk(n_dup_work, 256)), dim3(256), 0, s, *R, *P, dup_units, n_dup, dup_off, n_dup_work));
         }
     }
     if (P->inferred_is_vcf_generated) TIMED(prof, "k_p5b", hipLaunchKernelGGL(k_p5b, dim3(nblk(R->npos * 2, 256)), dim3(256), 0, s, *R, *P));

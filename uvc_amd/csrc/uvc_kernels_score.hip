@@ -8,7 +8,7 @@
 //   BcfFormat_symbol_calc_qual main.hpp:4908   -> k_qual
 // Tumor-only, and with UvcTumorKey records in the request the normal sample of a T/N pair (SURVEY next-row N2).
 #include <algorithm>
-#include "uvc_device.h"
+#include "uvc_launch.h"
 
 #define DBL_EPS 2.220446049250313e-16
 #define FLT_EPS 1.1920928955078125e-07
@@ -109,9 +109,6 @@ DEV RtrLite load_rtr(const RegionDev &R, int idx) { RtrLite r; r.tracklen = RTRP
 #define OUT(fld, v) ROW_(int32_t, fields, fld, capacity, rec) = (v)
 
 // ------------------------------------------------------------------------------------------------
-// one range of uvcgpu_region_score_ranges on the device: [beg, end) in zerobased_pos, first = the compact position of beg (exclusive prefix
-// of the lengths), flags bit 0 = base_at_pos_beg
-struct UvcScoreRangeDev { int beg, end, first, flags; };
 struct ScoreCtx {
     int pos_beg, pos_end, all_out, is_amplicon, base_at_beg;
     const UvcIndelAllele *alleles; long long n_alleles;   // sorted by (refpos, symbol): the region's own InDel alleles, or the caller's where it listed any
@@ -1801,16 +1798,15 @@ extern "C" size_t uvc_score_stream_table_offset(int64_t npos_scored) { return al
 
 // what every launch of one score request shares: the context, and the position-sized part of the scratch
 struct ScoreSetup { ScoreCtx C; Stage S; long long npos_scored, ngroups; };
-static ScoreSetup score_setup(const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                              const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const ScratchLayout &L,
-                              const void *d_ranges, int64_t n_ranges, int64_t n_compact) {
+static ScoreSetup score_setup(const UvcScoreIn *in, const ScratchLayout &L) {
+    const UvcParams *P = in->P; const UvcScoreRequest *req = in->req; char *scratch = in->scratch;
     ScoreSetup U; ScoreCtx &C = U.C; Stage &S = U.S;
     S = Stage{};
     C.pos_beg = req->pos_beg; C.pos_end = req->pos_end;
-    if (d_ranges) { C.pos_beg = 0; C.pos_end = (int)n_compact; }   // the compact axis; scratch is sized by it (npos_scored below)
-    C.zpos_tab = nullptr; C.ranges = (const UvcScoreRangeDev *)d_ranges; C.n_ranges = (int)n_ranges;
+    if (in->ranges) { C.pos_beg = 0; C.pos_end = (int)in->n_compact; }   // the compact axis; scratch is sized by it (npos_scored below)
+    C.zpos_tab = nullptr; C.ranges = in->ranges; C.n_ranges = (int)in->n_ranges;
     C.all_out = (req->all_out || P->should_output_all) ? 1 : 0; C.is_amplicon = req->is_amplicon; C.base_at_beg = req->base_at_pos_beg ? 1 : 0;
-    C.alleles = d_alleles; C.allele_rows = d_allele_rows; C.n_alleles = n_alleles; C.gap_rows = d_gap_rows; C.gap_seq = d_gap_seq; C.tkeys = d_tkeys; C.n_tkeys = (d_tkeys ? req->n_tumor_keys : 0);
+    C.alleles = in->alleles; C.allele_rows = in->allele_rows; C.n_alleles = in->n_alleles; C.gap_rows = in->gap_rows; C.gap_seq = in->gap_seq; C.tkeys = in->tkeys; C.n_tkeys = (in->tkeys ? req->n_tumor_keys : 0);
     C.fields = nullptr; C.capacity = 0; C.force_mask = nullptr;
     U.npos_scored = C.pos_end - C.pos_beg; U.ngroups = 2LL * U.npos_scored;
     S.cnt = (unsigned int *)(scratch + L.cnt); S.status1 = (unsigned long long *)(scratch + L.status1); S.status2 = (unsigned long long *)(scratch + L.status2);
@@ -1819,7 +1815,8 @@ static ScoreSetup score_setup(const UvcParams *P, const UvcScoreRequest *req, co
     return U;
 }
 // k_range_map, k_force_mask, k_gate_scan over the whole request: offsets, the active list, the total (d_count[0])
-static int launch_gate(ScoreSetup &U, const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, char *scratch, const ScratchLayout &L, const int32_t *d_force_sites, long long *d_count, hipStream_t s) {
+static int launch_gate(ScoreSetup &U, const UvcScoreIn *in, const ScratchLayout &L, long long *d_count, hipStream_t s) {
+    const RegionDev *R = in->R; const UvcParams *P = in->P; const UvcScoreRequest *req = in->req; char *scratch = in->scratch; const int32_t *d_force_sites = in->force_sites;
     ScoreCtx &C = U.C; const long long npos_scored = U.npos_scored, ngroups = U.ngroups;
     if (C.ranges) {
         int *tab = (int *)(scratch + L.zpos_tab);
@@ -1854,23 +1851,21 @@ static void launch_records(const RegionDev *R, const UvcParams *P, const ScoreCt
     }
 }
 
-// The caller zeroes the first uvc_score_scratch_zero_bytes of `scratch` on the stream in front of this; the record counts (all records, kept
-// records) are its first two int64.
-extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, int32_t *d_fields, int64_t capacity,
-                                char *scratch /* uvc_score_scratch_bytes */, int32_t *d_fields_kept /* kept_only: a second [fields][capacity] array */,
-                                const int32_t *d_force_sites /* device copy of UvcScoreRequest::force_sites, or NULL */,
-                                const void *d_ranges /* uvcgpu_region_score_ranges: device table of UvcScoreRangeDev, or NULL */, int64_t n_ranges, int64_t n_compact, hipStream_t s) {
-    const long long npos0 = (d_ranges ? (long long)n_compact : (long long)req->pos_end - req->pos_beg);
+// the length of the axis a request is scored on: the compact axis of its ranges, or its one range
+static long long score_npos(const UvcScoreIn *in) { return in->ranges ? (long long)in->n_compact : (long long)in->req->pos_end - in->req->pos_beg; }
+
+extern "C" int uvc_launch_score(const UvcScoreIn *in, int32_t *d_fields, int64_t capacity, int32_t *d_fields_kept, hipStream_t s) {
+    const RegionDev *R = in->R; const UvcParams *P = in->P; const UvcScoreRequest *req = in->req; char *scratch = in->scratch;
+    const long long npos0 = score_npos(in);
     if (npos0 <= 0) return 0;
     const ScratchLayout L = scratch_layout(npos0, capacity);
-    ScoreSetup U = score_setup(P, req, d_alleles, d_allele_rows, n_alleles, d_gap_rows, d_gap_seq, d_tkeys, scratch, L, d_ranges, n_ranges, n_compact);
+    ScoreSetup U = score_setup(in, L);
     ScoreCtx &C = U.C; Stage &S = U.S;
     C.fields = d_fields; C.capacity = capacity;
     long long *d_count = (long long *)scratch;
     S.grp = (int32_t *)(scratch + L.grp); S.tot = (long long *)(scratch + L.tot); S.rh = (int32_t *)(scratch + L.rh); S.al = (int32_t *)(scratch + L.al); S.al64 = (long long *)(scratch + L.al64);
     S.mid = (double *)(scratch + L.mid); S.d4 = (double *)(scratch + L.d4); S.keptoff = (int32_t *)(scratch + L.keptoff); S.cap = capacity; S.gcap = capacity;
-    if (const int rc = launch_gate(U, R, P, req, scratch, L, d_force_sites, d_count, s)) return rc;
+    if (const int rc = launch_gate(U, in, L, d_count, s)) return rc;
     const long long max_groups = (U.ngroups < capacity ? U.ngroups : capacity);
     launch_records(R, P, C, S, max_groups, capacity, (req->kept_only && d_fields_kept) ? d_fields_kept : nullptr, d_count, s);
     return 0;
@@ -1878,30 +1873,28 @@ extern "C" int uvc_launch_score(const RegionDev *R, const UvcParams *P, const Uv
 
 // ---- the streamed form: one gate pass and the cut, then the per-record kernels chunk by chunk ----
 // `scratch` = uvc_score_stream_pos_bytes, its head (uvc_score_scratch_zero_bytes(npos, 1)) zeroed by the caller in front of this.
-extern "C" int uvc_launch_score_gate(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                     const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
-                                     const void *d_ranges, int64_t n_ranges, int64_t n_compact, int64_t chunk_records, int64_t tab_cap, hipStream_t s) {
-    const long long npos0 = (d_ranges ? (long long)n_compact : (long long)req->pos_end - req->pos_beg);
+extern "C" int uvc_launch_score_gate(const UvcScoreIn *in, int64_t chunk_records, int64_t tab_cap, hipStream_t s) {
+    char *scratch = in->scratch;
+    const long long npos0 = score_npos(in);
     if (npos0 <= 0) return 0;
     const ScratchLayout L = scratch_layout(npos0, 1);
-    ScoreSetup U = score_setup(P, req, d_alleles, d_allele_rows, n_alleles, d_gap_rows, d_gap_seq, d_tkeys, scratch, L, d_ranges, n_ranges, n_compact);
-    if (const int rc = launch_gate(U, R, P, req, scratch, L, d_force_sites, (long long *)scratch, s)) return rc;
+    ScoreSetup U = score_setup(in, L);
+    if (const int rc = launch_gate(U, in, L, (long long *)scratch, s)) return rc;
     char *t = scratch + align16(L.total);
     hipLaunchKernelGGL(k_chunk_cut, dim3(1), dim3(64), 0, s, U.C.offsets, npos0, (long long)chunk_records, (long long *)t, (UvcChunkDev *)(t + 32), (long long)tab_cap);
     return 0;
 }
 // one chunk: groups [win_g, win_g + win_n) of the request into the row set `set` (uvc_score_set_bytes; its head is zeroed here)
-extern "C" int uvc_launch_score_chunk(const RegionDev *R, const UvcParams *P, const UvcScoreRequest *req, const UvcIndelAllele *d_alleles, const int32_t *d_allele_rows, int64_t n_alleles,
-                                      const UvcGapRow *d_gap_rows, const uint8_t *d_gap_seq, const UvcTumorKey *d_tkeys, char *scratch, const int32_t *d_force_sites,
-                                      const void *d_ranges, int64_t n_ranges, int64_t n_compact, char *set, int64_t chunk_records, int with_kept,
+extern "C" int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t chunk_records, int with_kept,
                                       int64_t win_g, int64_t win_n, int64_t win_groups /* active groups of the window */, int64_t win_records, hipStream_t s) {
-    const long long npos0 = (d_ranges ? (long long)n_compact : (long long)req->pos_end - req->pos_beg);
+    const RegionDev *R = in->R; const UvcParams *P = in->P; const UvcScoreRequest *req = in->req; char *scratch = in->scratch;
+    const long long npos0 = score_npos(in);
     if (npos0 <= 0) return 0;
     const ScratchLayout L = scratch_layout(npos0, 1);
-    ScoreSetup U = score_setup(P, req, d_alleles, d_allele_rows, n_alleles, d_gap_rows, d_gap_seq, d_tkeys, scratch, L, d_ranges, n_ranges, n_compact);
+    ScoreSetup U = score_setup(in, L);
     ScoreCtx &C = U.C; Stage &S = U.S;
     if (C.ranges) C.zpos_tab = (const int *)(scratch + L.zpos_tab);
-    if (d_force_sites && req->n_force_sites > 0 && !C.all_out) C.force_mask = (const unsigned *)(scratch + L.force_mask);
+    if (in->force_sites && req->n_force_sites > 0 && !C.all_out) C.force_mask = (const unsigned *)(scratch + L.force_mask);
     const SetLayout Q = set_layout(chunk_records, U.ngroups, with_kept);
     if (win_records > chunk_records || win_groups > (long long)std::min<long long>(U.ngroups, chunk_records)) return UVCGPU_EINVAL;   // (the cut never makes such a window)
     if (hipMemsetAsync(set, 0, Q.zero_bytes, s) != hipSuccess) return UVCGPU_EDEVICE;

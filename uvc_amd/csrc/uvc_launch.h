@@ -1,0 +1,92 @@
+// uvc_launch.h -- the host-kernel boundary inside libuvcgpu.so: every launcher and helper that one HIP translation unit defines and another
+// calls, and the structs that cross with them (by value into a kernel, or as a table the host fills and a kernel reads).  Each file that
+// defines or calls one of these includes this header, so the compiler checks every definition against the one declaration.
+#ifndef UVC_LAUNCH_H
+#define UVC_LAUNCH_H
+#include "uvc_device.h"
+
+// the caller's columns as they are (uvcgpu_region_set_reads) + what uvc_prep.hip derives per read; by value into k_aln_bm / k_aln_prelude
+struct RawReads {
+    const int32_t *pos, *endpos, *mpos, *isize, *nm, *l_qseq, *n_cigar, *frag, *fs, *dflag, *kind, *fast_rank;
+    const uint16_t *flag; const uint8_t *mapq;
+    const int64_t *seq_off, *cigar_off, *table_off, *item_off, *gap_off;
+};
+static_assert(sizeof(RawReads) == 19 * sizeof(void *), "RawReads is 19 device pointers");
+// optional per-kernel HIP-event timing on the handle's own stream (bench.py roofline leg)
+struct UvcProf { int on; int n; const char *name[32]; hipEvent_t ev[32][2]; };
+// one plane of the slab for k_zero_state; fam < 0: always filled, else the (plane family, sym) of RegionDev::dirty that says whether to
+struct ZeroPlane { unsigned long long off; int32_t elem; int16_t fam, sym; };
+static_assert(sizeof(ZeroPlane) == 16, "the host uploads the plane table as 16-byte rows");
+// one range of uvcgpu_region_score_ranges on the device: [beg, end) in zerobased_pos, first = the compact position of beg (exclusive prefix
+// of the lengths), flags bit 0 = base_at_pos_beg
+struct UvcScoreRangeDev { int beg, end, first, flags; };
+static_assert(sizeof(UvcScoreRangeDev) == 16, "the host uploads the range table as 16-byte rows");
+// one range of uvcgpu_region_coverage / uvcgpu_region_error_profile: plane index of the range's first position; its first compact position.
+// Entry n_ranges of a table: { 0, n_total }
+struct UvcRangeRow { int x0, first; };
+static_assert(sizeof(UvcRangeRow) == 8, "the host uploads the range table as 8-byte rows");
+
+// What the three score launchers share (host-side aggregate; ScorePrep of uvc_host.cpp owns one).  ranges: the device table of
+// uvcgpu_region_score_ranges or NULL; n_compact: the length of the compact axis the ranges make.  force_sites: device copy of
+// UvcScoreRequest::force_sites or NULL.  scratch: uvc_score_scratch_bytes (one call) / uvc_score_stream_pos_bytes (stream).
+struct UvcScoreIn {
+    const RegionDev *R; const UvcParams *P; const UvcScoreRequest *req;
+    const UvcIndelAllele *alleles; const int32_t *allele_rows; int64_t n_alleles;
+    const UvcGapRow *gap_rows; const uint8_t *gap_seq; const UvcTumorKey *tkeys;
+    char *scratch; const int32_t *force_sites;
+    const UvcScoreRangeDev *ranges; int64_t n_ranges, n_compact;
+};
+// The streams and events of one accumulate (host-side aggregate): the handle's stream, the two side streams (NULL: everything on `s`) and
+// the events of the forks and joins between them (see uvc_launch_accumulate).
+struct UvcAccStreams { hipStream_t s, side, side3; hipEvent_t e_fork, e_join, e_fork2, e_join3, e_stat, e_alleles; };
+
+extern "C" {
+// ---- uvc_kernels_acc.hip ----
+void uvc_launch_correct_bq(const RegionDev *R, int bq_max, int bq_inc, hipStream_t s);
+void uvc_launch_pack_bq(const uint8_t *bases, const uint8_t *quals, uint16_t *bq, int64_t n, int32_t *bad, hipStream_t s);
+void uvc_launch_build_p2list(const RegionDev *R, const int32_t *fast_rank, const int32_t *aln, const int32_t *cbeg, const int32_t *cend, const int32_t *qb, hipStream_t s);
+void uvc_launch_prelude(const RegionDev *R, const RawReads *W, const UvcParams *P, hipStream_t s);
+void uvc_launch_zero_state(char *slab, const ZeroPlane *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s);
+void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
+void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
+                           const UvcAccStreams *st, UvcProf *prof);
+void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
+void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
+// ---- uvc_kernels_score.hip ----
+// The caller zeroes the first uvc_score_scratch_zero_bytes of in->scratch on the stream in front of uvc_launch_score / uvc_launch_score_gate;
+// the record counts (all records, kept records) are its first two int64.  d_fields_kept (kept_only): a second [fields][capacity] array.
+int uvc_launch_score(const UvcScoreIn *in, int32_t *d_fields, int64_t capacity, int32_t *d_fields_kept, hipStream_t s);
+size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity);
+size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity);
+// the streamed form (uvcgpu_region_score_stream_*): one gate pass + the chunk cut, then the per-record kernels per chunk into a row set
+int uvc_launch_score_gate(const UvcScoreIn *in, int64_t chunk_records, int64_t tab_cap, hipStream_t s);
+int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t chunk_records, int with_kept, int64_t win_g, int64_t win_n, int64_t win_groups, int64_t win_records, hipStream_t s);
+size_t uvc_score_set_bytes(int64_t chunk_records, int64_t ngroups, int with_kept);
+size_t uvc_score_set_bytes_per_record(void);
+int32_t *uvc_score_set_fields(char *set, int64_t chunk_records, int64_t ngroups, int kept);
+size_t uvc_score_stream_pos_bytes(int64_t npos_scored, int64_t tab_cap);
+size_t uvc_score_stream_table_offset(int64_t npos_scored);
+void uvc_launch_check_presence(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
+void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s);
+void uvc_launch_block_stats_windows(const RegionDev *R, const UvcParams *P, const long long *d_win, int n_win, int64_t n, int32_t *d_out, hipStream_t s);
+// ---- uvc_coverage.hip, uvc_errprofile.hip: d_tab = n_ranges + 1 rows ----
+void uvc_launch_coverage(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s);
+const char *uvc_coverage_name(int id);
+int64_t uvc_coverage_scratch_rows(int n_ranges, int64_t n_total);
+void uvc_launch_errprofile(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, int min_depth, int max_alt_permille, long long *d_out, long long *d_scratch, hipStream_t s);
+const char *uvc_errprofile_level_name(int id);
+int64_t uvc_errprofile_scratch_cells(void);
+// ---- uvc_gap.hip: the rocPRIM sorts and the small gathers ----
+size_t uvc_gap_sort_tmp_bytes(size_t n);
+int uvc_gap_sort(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout, const unsigned long long *vin, unsigned long long *vout, size_t n, int end_bit, hipStream_t s);
+size_t uvc_sort32_tmp_bytes(size_t n);
+int uvc_sort_by_pos_cls(const int32_t *d_pos, const int32_t *d_cls, int32_t beg, int pos_bits, int cls_bits, int64_t n, uint32_t *work /* [4 n] */, void *tmp, size_t tmp_bytes, hipStream_t s);
+void uvc_launch_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3, hipStream_t s);
+void uvc_launch_rank_from_sorted(const uint32_t *perm, int64_t n, int64_t n_first, int32_t *out_ids, int32_t *rank, hipStream_t s);
+void uvc_launch_gather_columns(const char *const *base, const int32_t *first_col, const int32_t *elem, int64_t npos, const int32_t *d_xs, int64_t n, long long *d_out, hipStream_t s);
+// ---- uvc_prep.hip (uvc_prep_reads itself: uvc_prep.h) ----
+size_t uvc_prep_compact_tmp_bytes(int64_t n);
+int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, int64_t n, int64_t n_bases, const uint8_t *bases4, int64_t n_b4, const uint8_t *quals, int64_t *seq_off_out, const int64_t *seq_off_in,
+                     int64_t *cigar_off_out, int64_t *b4_off, uint8_t *bases_out, uint16_t *bq_out, int32_t *bad, void *tmp, size_t tmp_bytes, hipStream_t s);
+}
+#endif

@@ -2,6 +2,7 @@
 // (uvcgpu_param_count / _info / _get / _set), and the value refusals of a region handle (uvcgpu_params_check).  Host code only.
 #include "uvcgpu.h"
 #include "uvcgroup.h"
+#include "uvc_host.h"
 
 #include <cerrno>
 #include <cmath>
@@ -9,8 +10,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-
-extern "C" int uvcgpu_set_error(int code, const char *msg);   // uvc_host.cpp
 
 namespace {
 struct Row { const char *name; int32_t kind, owner; size_t off; double dflt; };

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "uvc_prep.h"
+#include "uvc_launch.h"
 
 namespace {
 #define PDEV __device__ __forceinline__
@@ -527,8 +528,6 @@ extern "C" int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, i
 }
 
 static inline int pos_bits_of(int64_t npos) { int b = 1; while (((int64_t)1 << b) < npos + 1) b++; return b; }
-extern "C" int uvc_sort_by_pos_cls(const int32_t *d_pos, const int32_t *d_cls, int32_t beg, int pos_bits, int cls_bits, int64_t n, uint32_t *work, void *tmp, size_t tmp_bytes, hipStream_t s);
-extern "C" size_t uvc_sort32_tmp_bytes(size_t n);
 
 #define PREP_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(errmsg, (size_t)errcap, "%s: %s", #call, hipGetErrorString(e_)); return UVCGPU_EDEVICE; } } while (0)
 

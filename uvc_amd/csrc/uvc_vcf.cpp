@@ -3,7 +3,7 @@
 // the score records (uvcgpu_region_score), the plane columns of the positions that are written (uvcgpu_region_fetch_columns, one small
 // gather kernel) and the InDel allele rows (uvcgpu_region_indel_alleles).  O(emitted records); nothing here is on the hot path.
 #include "uvcgpu.h"
-#include "uvc_hap.h"
+#include "uvc_host.h"
 
 #include <algorithm>
 #include <chrono>
@@ -14,14 +14,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-
-extern "C" const char *uvcgpu_region_refseq(const uvcgpu_region_t *r, int32_t *beg, int32_t *end);   // uvc_host.cpp
-extern "C" const int32_t *uvcgpu_region_repeat_tracks(const uvcgpu_region_t *r, int64_t *npos);    // host copy, [UVC_NRTR][npos]
-extern "C" const UvcParams *uvcgpu_region_params(const uvcgpu_region_t *r);
-extern "C" const std::vector<UvcHapLinkHost> *uvcgpu_region_hap_(uvcgpu_region_t *r);   // the three link vectors (uvc_host.cpp), NULL on error
-extern "C" int uvcgpu_fail_(int code, const char *msg);
-extern "C" int uvcgpu_region_block_stats_(uvcgpu_region_t *r, int32_t refpos_beg, int32_t refpos_end, int32_t *dst);   // 10 ints per position, k_block_stats
-extern "C" int uvcgpu_region_block_stats_windows_(uvcgpu_region_t *r, const int32_t *win, int64_t n_win, int32_t *dst);   // the same for disjoint windows [win[2k], win[2k + 1]), one round trip
 
 namespace {
 const int NSYM = 14;
@@ -406,7 +398,7 @@ extern "C" const char *uvcgpu_vcf_format_keys(int32_t with_tier2) { return g_key
 #include "uvc_vcf_header_lines.inc"
 extern "C" int uvcgpu_vcf_header_ex(const UvcParams *P, const char *sample, const char *tumor_sample, const char *const *names, const int64_t *lens, int32_t n_contigs,
                                     const char *file_date, const char *reference_fname, const char *command_line, char *dst, int64_t cap, int64_t *len) {
-    if (!P || !len || (n_contigs > 0 && (!names || !lens))) return uvcgpu_fail_(UVCGPU_EINVAL, "bad argument");
+    if (!P || !len || (n_contigs > 0 && (!names || !lens))) return uvcgpu_set_error(UVCGPU_EINVAL, "bad argument");
     std::string h = "##fileformat=VCFv4.2\n";
     if (file_date) h += std::string("##fileDate=") + file_date + "\n";
     if (reference_fname) h += std::string("##reference=") + reference_fname + "\n";
@@ -473,7 +465,7 @@ extern "C" int uvcgpu_vcf_header_ex(const UvcParams *P, const char *sample, cons
     h += std::string("##variantCallerInferredParameters=(inferred_sequencing_platform=") + plat + ",central_readlen=" + std::to_string(P->central_readlen) + ")\n";
     h += std::string("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t") + (sample ? sample : "SAMPLE") + ((tumor_sample && *tumor_sample) ? std::string("\t") + tumor_sample : std::string()) + "\n";
     *len = (int64_t)h.size();
-    if (!dst || cap < (int64_t)h.size()) return uvcgpu_fail_(UVCGPU_ENOMEM, "destination too small");
+    if (!dst || cap < (int64_t)h.size()) return uvcgpu_set_error(UVCGPU_ENOMEM, "destination too small");
     memcpy(dst, h.data(), h.size());
     return 0;
 }
@@ -486,11 +478,11 @@ extern "C" int uvcgpu_vcf_header(const UvcParams *P, const char *sample, const c
 // merge by zerobased_pos at the end yields the single-range texts one after another.
 static int vcf_records_impl(uvcgpu_region_t *r, const char *tname, const UvcScoreOut *scored, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges,
                             char *dst, int64_t cap, int64_t *len) {
-    if (!r || !tname || !len || !scored || (scored->n_records > 0 && !scored->fields) || scored->n_records > scored->capacity) return uvcgpu_fail_(UVCGPU_EINVAL, "bad argument");
+    if (!r || !tname || !len || !scored || (scored->n_records > 0 && !scored->fields) || scored->n_records > scored->capacity) return uvcgpu_set_error(UVCGPU_EINVAL, "bad argument");
     if (ranges) {
-        if (n_ranges < 1) return uvcgpu_fail_(UVCGPU_EINVAL, "vcf_records_ranges: n_ranges must be at least 1");
+        if (n_ranges < 1) return uvcgpu_set_error(UVCGPU_EINVAL, "vcf_records_ranges: n_ranges must be at least 1");
         for (int64_t k = 0; k < n_ranges; k++) if (ranges[k].pos_beg < 0 || ranges[k].pos_end < ranges[k].pos_beg || (k > 0 && ranges[k].pos_beg < ranges[k - 1].pos_end))
-            return uvcgpu_fail_(UVCGPU_EINVAL, ("vcf_records_ranges: range " + std::to_string(k) + " is malformed or not behind its predecessor (ranges must be sorted and disjoint)").c_str());
+            return uvcgpu_set_error(UVCGPU_EINVAL, ("vcf_records_ranges: range " + std::to_string(k) + " is malformed or not behind its predecessor (ranges must be sorted and disjoint)").c_str());
     }
     const UvcTumorKey *tkeys = (req ? req->tumor_keys : nullptr); const int64_t n_tkeys = (req ? req->n_tumor_keys : 0);
     const char *const *tcols = (req && tkeys ? req->tumor_sample_columns : nullptr);
@@ -503,7 +495,7 @@ static int vcf_records_impl(uvcgpu_region_t *r, const char *tname, const UvcScor
     const std::string ref(refp, (size_t)(end - beg));
     int64_t npos = 0;
     const int32_t *rtr = uvcgpu_region_repeat_tracks(r, &npos);
-    if (!rtr) return uvcgpu_fail_(UVCGPU_EDEVICE, "vcf_records: the repeat tracks could not be fetched from the device");
+    if (!rtr) return uvcgpu_set_error(UVCGPU_EDEVICE, "vcf_records: the repeat tracks could not be fetched from the device");
     auto F = [&](int64_t i, int f) { return recs[(int64_t)f * stride + i]; };
     // the InDel string a rescued record of the normal sample takes from its tumor record: REF / ALT without their common head (main.cpp:867-880)
     auto rescued_text = [&](int64_t i) -> std::string {
@@ -524,7 +516,7 @@ static int vcf_records_impl(uvcgpu_region_t *r, const char *tname, const UvcScor
         while (j > 0 && F(j - 1, UVC_O_refpos) == F(i, UVC_O_refpos)) j--;
         for (; j < n && F(j, UVC_O_refpos) == F(i, UVC_O_refpos); j++)
             if ((is_base(F(j, UVC_O_symbol)) ? UVC_BASE_SYMBOL : UVC_LINK_SYMBOL) == st && F(j, UVC_O_symbol) == F(i, UVC_O_refsymbol)) { found = j; break; }
-        if (found < 0) return uvcgpu_fail_(UVCGPU_EINVAL, "a kept record has no REF record at its position (pass all records of the score call)");
+        if (found < 0) return uvcgpu_set_error(UVCGPU_EINVAL, "a kept record has no REF record at its position (pass all records of the score call)");
         kept.push_back(i); refrec.push_back(found);
     }
     std::vector<std::pair<int32_t, std::string>> rec_lines;   // (zerobased_pos of the iteration that writes it, line)
@@ -930,7 +922,7 @@ static int vcf_records_impl(uvcgpu_region_t *r, const char *tname, const UvcScor
         }
     }
     *len = (int64_t)out.size();
-    if (!dst || cap < (int64_t)out.size()) return uvcgpu_fail_(UVCGPU_ENOMEM, "destination too small");
+    if (!dst || cap < (int64_t)out.size()) return uvcgpu_set_error(UVCGPU_ENOMEM, "destination too small");
     memcpy(dst, out.data(), out.size());
     return 0;
 }
@@ -940,6 +932,6 @@ extern "C" int uvcgpu_region_vcf_records(uvcgpu_region_t *r, const char *tname, 
 }
 extern "C" int uvcgpu_region_vcf_records_ranges(uvcgpu_region_t *r, const char *tname, const UvcScoreOut *scored, const UvcScoreRequest *req,
                                                 const UvcScoreRange *ranges, int64_t n_ranges, char *dst, int64_t cap, int64_t *len) {
-    if (!ranges) return uvcgpu_fail_(UVCGPU_EINVAL, "vcf_records_ranges: ranges is NULL");
+    if (!ranges) return uvcgpu_set_error(UVCGPU_EINVAL, "vcf_records_ranges: ranges is NULL");
     return vcf_records_impl(r, tname, scored, req, ranges, n_ranges, dst, cap, len);
 }
