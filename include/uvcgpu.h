@@ -511,6 +511,37 @@ typedef struct UvcErrorProfileRequest { int32_t min_depth; int32_t max_alt_permi
 int uvcgpu_region_error_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges,
                                 const UvcErrorProfileRequest *req, int64_t *out /* [UVC_NERRLEVEL][UVC_ERR_ROW] */);
 const char *uvcgpu_error_level_name(int32_t id);   /* "bDP" .. "dDP1"; NULL for an id outside 0..UVC_NERRLEVEL - 1 */
+/* ---- UMI family statistics of ranges, from the family units of the region's reads (uvc1-mi355x --family-stats-out) ----
+ * A family is one fam_id of the reads the handle holds (UvcReadSoA), as uvcgpu_group_families formed it and as the family passes of
+ * accumulate consume it.  Family f has a_f / b_f = the fragments (distinct frag_id) of its strand-0 / strand-1 unit (a missing unit: 0),
+ * n_f = its alignments, lo_f = its smallest pos, hi_f = its largest reference end (pos + the reference length of the CIGAR, exclusive; both
+ * unclamped, from the alignments) and dflag_f = fam_dflag[f].  f overlaps range i iff lo_f < pos_end_i and hi_f > pos_beg_i.
+ * One row of UVC_FAMSTAT_ROW int64 per range (sections: include/uvc_famstats.def), two blocks:
+ *   TARGET (words 0..3: families, fragments = sum of a + b, alignments = sum of n, families with a >= 1 and b >= 1) over every family that
+ *     overlaps the range -- with UVC_FAMRANGE_CONTINUES only over those with lo_f >= pos_beg: the range is a later piece of the target its
+ *     predecessor belongs to, which counted the others.  A family may count in several targets.
+ *   FIRST (words 4..): over every family that overlaps the range and has prev_end <= lo_f: the same four counters, the families with dflag
+ *     bit 0 (UMI), bit 1 (duplex tag), bit 2 (amplicon), a reserved 0, size[64] (bin k - 1: a + b == k; the last: a + b >= 64) and
+ *     strands[17][17] (bin [min(a, 16)][min(b, 16)]).  With prev_end = the end of the previous range of a run of sorted, disjoint ranges
+ *     every family that overlaps any range is counted exactly once in the run.
+ * A family is seen as the region it was grouped in sees it: next to a tile cut it may lack fragments that the fetch of the neighbouring
+ * tile holds, so sums over tiles depend on the cuts. */
+enum UvcFamStat { UVC_FAMSTAT_target_families = 0, UVC_FAMSTAT_target_fragments, UVC_FAMSTAT_target_alignments, UVC_FAMSTAT_target_families_both_strands,
+                  UVC_FAMSTAT_families, UVC_FAMSTAT_fragments, UVC_FAMSTAT_alignments, UVC_FAMSTAT_families_both_strands,
+                  UVC_FAMSTAT_families_umi, UVC_FAMSTAT_families_duplex_tag, UVC_FAMSTAT_families_amplicon, UVC_FAMSTAT_reserved,
+                  UVC_FAMSTAT_size, UVC_FAMSTAT_strands, UVC_NFAMSTAT };
+enum { UVC_FAMSTAT_TARGET = 0, UVC_FAMSTAT_FIRST = 4, UVC_FAMSTAT_SIZE = 12, UVC_FAMSTAT_NSIZE = 64, UVC_FAMSTAT_STRANDS = 76 /* 12 + 64 */,
+       UVC_FAMSTAT_STRAND_CAP = 16, UVC_FAMSTAT_ROW = 365 /* 76 + 17 * 17 */, UVC_FAMRANGE_CONTINUES = 1 };
+typedef struct UvcFamilyRange { int32_t pos_beg, pos_end, prev_end, flags; } UvcFamilyRange;   /* zero-based, half open; flags: UVC_FAMRANGE_CONTINUES */
+/* Reduced on the device from the unit records of set_reads (two passes over the alignments and the units); integers only, the same bits
+ * from call to call.  Legal after uvcgpu_region_set_reads / _set_reads_device of the current region (zero reads: rows of zeros), with or
+ * without accumulate, after any score -- a releasing one too: it gives up the planes, not the reads -- and while a score stream is open.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason (a range by its index): called before set_reads or after a reset;
+ *   NULL ranges or out; n_ranges < 1; a range that is empty or reversed, outside the region [beg, end + 1), or begins in front of its
+ *   predecessor's end; prev_end > pos_beg; prev_end smaller than the predecessor's prev_end or pos_end; a flag bit other than
+ *   UVC_FAMRANGE_CONTINUES.  `out` is written only by a call that returns 0. */
+int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out /* [n_ranges][UVC_FAMSTAT_ROW] */);
+const char *uvcgpu_family_stat_name(int32_t id);   /* "target_families" .. "strands"; NULL for an id outside 0..UVC_NFAMSTAT - 1 */
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);

@@ -193,6 +193,23 @@ int uvcio_errprofile_open(uvcio_errprofile_t **out, const char *const *level_nam
 int uvcio_errprofile_add(uvcio_errprofile_t *e, const int64_t *profile /* [n_levels][712] */);
 int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *path);
 void uvcio_errprofile_close(uvcio_errprofile_t *e);
+/* ---- the UMI family report (uvc1-mi355x --family-stats-out) ----
+ * What tiles report with uvcgpu_region_family_stats (rows of 365 int64: the TARGET block of 4 counters, the FIRST block of 8 counters,
+ * size[64] and strands[17][17]), kept per target and per run.  Targets are added in report order before the pieces; add_piece adds the
+ * TARGET block of a row to its target and the FIRST block to the run's sum, under a lock: pieces come in any order and from any thread.
+ * write: two "##" lines; "#summary" and name<TAB>value lines -- families fragments alignments families_both_strands families_umi
+ * families_duplex_tag families_amplicon of the FIRST sum, duplication_permille = 1000 (fragments - families) / fragments,
+ * mean_family_size_x1000 = 1000 fragments / families, both_strands_permille = 1000 families_both_strands / families (integer division,
+ * 0 for an empty denominator); "#family_size\tfamilies" and 64 lines (1 .. 63, 64+); "#strand0_size\tstrand1_size\tfamilies" and the
+ * non-empty bins (sizes capped as 16+); "#chrom\tbeg\tend\tname\tfamilies\tfragments\talignments\tfamilies_both_strands\t
+ * mean_family_size_x1000\tboth_strands_permille" and one line per target in the order they were added, zeros for a target without
+ * pieces.  Integers only; a path that ends in .gz is written block-gzipped (uvcio_bgzf_write_*). */
+typedef struct uvcio_famstats uvcio_famstats_t;
+int uvcio_famstats_open(uvcio_famstats_t **out);
+int64_t uvcio_famstats_add_target(uvcio_famstats_t *f, const char *chrom, int64_t beg, int64_t end, const char *name /* NULL or empty: "." */);   /* -> its index, < 0 on error */
+int uvcio_famstats_add_piece(uvcio_famstats_t *f, int64_t target, const int64_t *row /* [365] */);
+int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path);
+void uvcio_famstats_close(uvcio_famstats_t *f);
 /* bcftools concat -n (uvcTN.sh:100): the BGZF files one after the other, the 28-byte end-of-file marker of all but the last dropped. */
 int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in);
 /* The whole text of a (block-)gzipped or plain file (the tumor VCF of a T/N pair); *buf is malloc'ed, the caller frees it. */

@@ -83,6 +83,10 @@ class UvcErrorProfileRequest(C.Structure):
     _fields_ = [("min_depth", C.c_int32), ("max_alt_permille", C.c_int32)]
 
 
+class UvcFamilyRange(C.Structure):
+    _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("prev_end", C.c_int32), ("flags", C.c_int32)]
+
+
 class UvcScoreOut(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n_records", C.c_int64), ("fields", C.c_void_p)]
 
@@ -137,6 +141,20 @@ assert len(COVERAGE_MEASURES) == ENUMS["UVC_NCOV"]
 # the evidence levels of uvcgpu_region_error_profile in id order (UvcErrLevel; the rows of include/uvc_errprofile.def)
 ERROR_LEVELS = [k[len("UVC_ERRLEVEL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_ERRLEVEL_")), key=lambda kv: kv[1])]
 assert len(ERROR_LEVELS) == ENUMS["UVC_NERRLEVEL"]
+
+
+def _read_famstats_def():
+    """The sections of a row of uvcgpu_region_family_stats: (name, first word, words) per row of include/uvc_famstats.def."""
+    with open(os.path.join(ROOT, "include", "uvc_famstats.def")) as fh:
+        rows = [re.match(r"UVC_FAMSTAT\((\w+),\s*(\d+),\s*(\d+)\)\s*$", line) for line in fh]
+    return [(m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
+
+
+# the sections of a family-statistics row in id order (UvcFamStat): the table of include/uvc_famstats.def, checked against the header's enums
+FAMSTAT_SECTIONS = _read_famstats_def()
+FAMILY_STATS = [n for n, _, _ in FAMSTAT_SECTIONS]
+assert [ENUMS["UVC_FAMSTAT_" + n] for n in FAMILY_STATS] == list(range(ENUMS["UVC_NFAMSTAT"]))
+assert sum(w for _, _, w in FAMSTAT_SECTIONS) == ENUMS["UVC_FAMSTAT_ROW"] and all(f == sum(w for _, _, w in FAMSTAT_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMSTAT_SECTIONS))
 
 
 class Lib:

@@ -54,6 +54,9 @@ struct Opts {
     std::string errprof_out;     // --error-profile-out PATH: the background error profile; empty = none
     UvcErrorProfileRequest errprof_req{ 20, 50 }; bool errprof_gate_given = false;   // --error-profile-min-depth, --error-profile-max-alt-permille
     uvcio_errprofile_t *errprof = nullptr;   // the run's table, summed over the tiles by the workers (main)
+    std::string famstats_out;    // --family-stats-out PATH: the UMI family report; empty = none
+    int64_t famstats_window = 0; // --family-stats-window N: the targets are windows of N bp (0: the BED lines)
+    uvcio_famstats_t *fam = nullptr;   // the report's store, filled by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -104,6 +107,8 @@ const OptRow OPTS[] = {
     { "--error-profile-out", O_CLI, false, "", "write the background error profile here (tab-separated; block-gzipped when the name ends in .gz): how often each base and each InDel symbol is seen at positions that do not look variant, per reference trinucleotide and per evidence level (bDP fragments, cDP1 families, cDP12 BQ-filtered families, cDP2 single-strand-consensus families, dDP1 duplex families), reduced on the device from the planes of each tile over the positions the tile owns.  The VCF does not depend on it" },
     { "--error-profile-min-depth", O_CLI, false, "20", "with --error-profile-out: a position enters a level's bins only where the level's depth is at least this (1 or more)" },
     { "--error-profile-max-alt-permille", O_CLI, false, "50", "with --error-profile-out: a position whose largest non-reference count is above this many thousandths of the level's depth counts as variant and stays out of the bins (0..1000)" },
+    { "--family-stats-out", O_CLI, false, "", "write the UMI family report here (tab-separated; block-gzipped when the name ends in .gz): over all targets the number of read families, fragments and alignments, the families seen on both strands, with a UMI, a duplex tag or the amplicon flag, the duplication rate, the family-size histogram (1 .. 64+) and the strand0 x strand1 size histogram (0 .. 16+), then per BED line, or per --family-stats-window, the families that overlap it -- the families exactly as this caller groups and consumes them, reduced on the device from each tile's family units.  The VCF does not depend on it" },
+    { "--family-stats-window", O_CLI, false, "0", "with --family-stats-out and no BED file: the targets are windows of this many bp, aligned to multiples of it on each contig and clipped to the called span" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -268,6 +273,8 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--error-profile-out") { o.errprof_out = val(); if (o.errprof_out.empty()) die("--error-profile-out needs a path"); }
         else if (n0 == "--error-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--error-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.errprof_req.min_depth = (int32_t)x; o.errprof_gate_given = true; }
         else if (n0 == "--error-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--error-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.errprof_req.max_alt_permille = (int32_t)x; o.errprof_gate_given = true; }
+        else if (n0 == "--family-stats-out") { o.famstats_out = val(); if (o.famstats_out.empty()) die("--family-stats-out needs a path"); }
+        else if (n0 == "--family-stats-window") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--family-stats-window takes a window length in bp, not '" + v + "'"); o.famstats_window = (int64_t)x; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -327,6 +334,16 @@ Opts parse(int argc, char **argv) {
         if (o.n_shards > 1) die("--error-profile-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": every shard would write a part of the table, and --concat joins VCFs only");
         if (o.repeat != 1) die("--error-profile-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
     }
+    if (o.famstats_out.empty()) {   // before any file or device
+        if (o.famstats_window > 0) die("--family-stats-window needs --family-stats-out: it only shapes that report");
+    } else {
+        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--family-stats-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
+        if (o.n_shards > 1) die("--family-stats-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": a target can straddle shards, and --concat joins VCFs only");
+        if (o.repeat != 1) die("--family-stats-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
+        const bool has_bed = (!o.bed.empty() || !o.bed_in.empty());
+        if (has_bed && o.famstats_window > 0) die("--family-stats-window cannot go with -R / --bed-in-fname: with a BED file the targets of --family-stats-out are its lines");
+        if (!has_bed && o.famstats_window <= 0) die("--family-stats-out needs --family-stats-window N without -R / --bed-in-fname: there are no BED lines to report on");
+    }
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -352,7 +369,8 @@ void print_params(const Opts &o, const char *prefix = "") {
 // [beg, end): `continues` (a tile ends where this one begins) = it scores `beg` completely, `has_next` = it leaves `end` to the next one.
 // `run_beg` = begin of the run (incluBegPosition of the BED line the run came from, main.cpp:655-656).
 // `target` (--coverage-out with a BED file): the report row of the BED line the tile was cut from.
-struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; };
+// `fam_target` (--family-stats-out with a BED file): the same for the family report.
+struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; int64_t fam_target = -1; };
 
 // one worker: its own handles, one region handle for all of its tiles
 struct Worker {
@@ -367,6 +385,7 @@ struct Worker {
     std::vector<UvcScoreRange> covered;
     std::vector<UvcCoverageRange> cov_ranges; std::vector<int64_t> cov_targets, cov_rows;   // --coverage-out: the pieces of one tile
     std::vector<UvcCoverageRange> err_ranges;   // --error-profile-out: the stretches one tile owns
+    std::vector<UvcFamilyRange> fam_ranges; std::vector<int64_t> fam_targets, fam_rows;   // --family-stats-out: the pieces of one tile
 };
 
 // --coverage-out: the pieces of targets that one accumulated tile owns, reduced by one uvcgpu_region_coverage and merged into the report.
@@ -403,6 +422,26 @@ void errprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
     if (uvcgpu_region_error_profile(w.reg, w.err_ranges.data(), (int64_t)w.err_ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
     if (uvcio_errprofile_add(o.errprof, prof)) die(uvcio_last_error());
 }
+// --family-stats-out: the pieces of targets that the tiles own, planned before any worker starts (plan_family_pieces), so that the report
+// does not depend on which worker takes which tile.  A piece is a tile's [beg, end), cut at the window borders in window mode: the planned
+// stretch, not the stretch the reads of the tile happen to reach -- families are counted by overlap, and where there are no reads there are
+// no families.  prev_end: the largest end of the pieces planned before it on the contig, at most its own begin (sorted, disjoint targets:
+// the end of the piece before); flags: UVC_FAMRANGE_CONTINUES where the piece before belongs to the same target.
+struct FamPiece { int64_t beg, end, prev_end; int32_t flags; int64_t target; };
+// One uvcgpu_region_family_stats over the pieces of a tile (of the `n_tiles` tiles of a merged batch), after set_reads: the rows go to the report.
+void family_stats_of_tile(Worker &w, const Opts &o, const std::vector<FamPiece> *pieces, size_t n_tiles, int64_t ext_end) {
+    w.fam_ranges.clear(); w.fam_targets.clear();
+    for (size_t q = 0; q < n_tiles; q++)
+        for (const FamPiece &p : pieces[q]) {
+            const int64_t e = std::min(p.end, ext_end + 1);   // (the region holds [ext_beg, ext_end]; a tile lies inside it)
+            if (e > p.beg) { w.fam_ranges.push_back(UvcFamilyRange{ (int32_t)p.beg, (int32_t)e, (int32_t)p.prev_end, p.flags }); w.fam_targets.push_back(p.target); }
+        }
+    if (w.fam_ranges.empty()) return;
+    w.fam_rows.resize(w.fam_ranges.size() * (size_t)UVC_FAMSTAT_ROW);
+    if (uvcgpu_region_family_stats(w.reg, w.fam_ranges.data(), (int64_t)w.fam_ranges.size(), w.fam_rows.data())) die(uvcgpu_last_error());
+    for (size_t q = 0; q < w.fam_ranges.size(); q++)
+        if (uvcio_famstats_add_piece(o.fam, w.fam_targets[q], &w.fam_rows[q * (size_t)UVC_FAMSTAT_ROW])) die(uvcio_last_error());
+}
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // process_batch for one tile; appends the record lines to `lines`; false = nothing to call there.  *n_kept_reads: reads that passed the filters.
@@ -412,7 +451,8 @@ double now() { return std::chrono::duration<double>(std::chrono::steady_clock::n
 // its own tile would have asked for; one uvcgpu_region_score_ranges, one uvcgpu_region_vcf_records_ranges.  n_kept_reads then has n_merged
 // entries: the kept alignments that overlap each line.  n_merged = 0: the plain call of one tile.
 bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads,
-               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr, size_t n_merged = 0, const CovSpan *cov_span = nullptr) {
+               const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr, size_t n_merged = 0, const CovSpan *cov_span = nullptr,
+               const std::vector<FamPiece> *fam_pieces = nullptr) {
     double t0 = now();
     for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) n_kept_reads[q] = 0;
     Tile t = t0_;
@@ -478,6 +518,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     rs.n_fams = go.n_fams; rs.fam_dflag = w.dflag.data();
     if (uvcgpu_region_set_reads(w.reg, &rs)) die(uvcgpu_last_error());
     w.t_reads += now() - t0; t0 = now();
+    if (o.fam && fam_pieces) family_stats_of_tile(w, o, fam_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --family-stats-out: the units of set_reads, before anything else
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
     if (o.cov || o.errprof) {   // --coverage-out, --error-profile-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
                    // point t.end itself, which lies outside every target the tile was cut from (and which two regions of the reference's cuts share)
@@ -611,7 +652,8 @@ void link_runs(std::vector<Tile> &tiles) {
 // are called as the ranges of one device region
 // --coverage-out: the report's rows are added here in target order -- the BED lines in file order (every tile carries its line's row), or
 // the windows of every called span (cov_spans: per contig the row of the span's first window)
-std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr, std::vector<CovSpan> *cov_spans = nullptr) {
+// --family-stats-out: its rows are added the same way (fam_spans, Tile::fam_target)
+std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr, std::vector<CovSpan> *cov_spans = nullptr, std::vector<CovSpan> *fam_spans = nullptr) {
     const std::vector<std::string> &names = G.names; const std::vector<int64_t> &lens = G.lens; const int32_t nref = (int32_t)names.size();
     std::vector<Tile> tiles;
     const std::string bed_path = (!o.bed_in.empty() ? o.bed_in : o.bed);
@@ -628,7 +670,7 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     if (ref_cuts && uvcio_planner_open(&planner, lens.data(), nref, (o.threads > 0 ? o.threads : 8) /* the reference's -t default (CmdLineArgs.hpp:34): enters only where a batch of regions ends */, o.mem_per_thread)) die(uvcio_last_error());
     std::vector<int32_t> pl_tid, pl_pos, pl_end; std::vector<uint16_t> pl_flag;   // one window's columns
     auto take_cuts = [&]() { UvcRegionCut c[256]; int64_t k; while ((k = uvcio_planner_take(planner, c, 256)) > 0) for (int64_t q = 0; q < k; q++) tiles.push_back(Tile{ c[q].tid, names[(size_t)c[q].tid], c[q].beg, c[q].end, false, false, c[q].beg }); };
-    int64_t cov_target = -1;   // the report row of the BED line being added
+    int64_t cov_target = -1, fam_target = -1;   // the report rows of the BED line being added
     auto add = [&](int32_t tid, int64_t beg, int64_t end) {
         if (o.cov && cov_spans && o.coverage_window > 0 && end > beg) {   // the windows of this span: aligned to multiples of N, clipped to it
             const int64_t N = o.coverage_window;
@@ -642,7 +684,18 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
                 if (sp.first < 0) sp.first = row;
             }
         }
-        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target }); return; }
+        if (o.fam && fam_spans && o.famstats_window > 0 && end > beg) {   // the same windows for the family report
+            const int64_t N = o.famstats_window;
+            CovSpan &sp = (*fam_spans)[(size_t)tid];
+            if (sp.first >= 0) die("--family-stats-window: a contig is called twice (internal error)");
+            sp.origin = beg;
+            for (int64_t k = beg / N; k * N < end; k++) {
+                const int64_t row = uvcio_famstats_add_target(o.fam, names[(size_t)tid].c_str(), std::max(k * N, beg), std::min((k + 1) * N, end), nullptr);
+                if (row < 0) die(uvcio_last_error());
+                if (sp.first < 0) sp.first = row;
+            }
+        }
+        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target, fam_target }); return; }
         const int64_t W = 4000000;   // the planning pass reads the span window by window; an alignment is taken by the window it starts in (the first window also takes those that reach into it)
         for (int64_t wb = beg; wb < end; wb += W) {
             UvcBamBatch b;
@@ -674,6 +727,10 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
             if (o.cov) {   // one report row per BED line: its own numbers, column 4 as the name, the positions inside the contig as the length
                 cov_target = uvcio_coverage_add_target(o.cov, chrom, b, e, n_col >= 4 ? bname : nullptr, std::max<long long>(0, std::min<long long>(e, lens[(size_t)tid]) - std::max<long long>(0, b)));
                 if (cov_target < 0) die(uvcio_last_error());
+            }
+            if (o.fam) {   // one report row per BED line, its own numbers and column 4 as the name
+                fam_target = uvcio_famstats_add_target(o.fam, chrom, b, e, n_col >= 4 ? bname : nullptr);
+                if (fam_target < 0) die(uvcio_last_error());
             }
             add(tid, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]));
             l_tid.push_back(tid); l_beg.push_back(std::max<long long>(0, b)); l_end.push_back(std::min<long long>(e, lens[(size_t)tid]));
@@ -785,6 +842,28 @@ void reader_switches(const Opts &o) {
 // The command line split as uvcTN.sh splits it: options before the first --tumor-params / --normal-params go to both sides, after one of
 // them to that side only, until the other.  Side lists take PARAM / GROUP / MODE / INERT options; a CLI option there is refused.
 struct PairArgs { bool pair = false, side_lists = false; std::string normal_bam, tumor_out; std::vector<std::string> shared, side[2]; };
+// --family-stats-out: the pieces of every tile (see FamPiece), in plan order
+std::vector<std::vector<FamPiece>> plan_family_pieces(const Opts &o, const std::vector<Tile> &tiles, const std::vector<CovSpan> &spans, int32_t nref) {
+    std::vector<std::vector<FamPiece>> plan(tiles.size());
+    std::vector<int64_t> reach((size_t)nref, 0);   // per contig: the largest end of the pieces planned so far
+    int64_t last_target = -1;
+    const int64_t N = o.famstats_window;
+    for (size_t q = 0; q < tiles.size(); q++) {
+        const Tile &t = tiles[q];
+        for (int64_t b = t.beg; b < t.end;) {
+            int64_t stop = t.end, target = t.fam_target;
+            if (target < 0) {   // window mode
+                const CovSpan &sp = spans[(size_t)t.tid];
+                if (N <= 0 || sp.first < 0 || b < sp.origin) die("--family-stats-out: a tile outside the planned windows (internal error)");
+                stop = std::min(t.end, (b / N + 1) * N); target = sp.first + (b / N - sp.origin / N);
+            }
+            plan[q].push_back(FamPiece{ b, stop, std::min(b, reach[(size_t)t.tid]), target == last_target ? UVC_FAMRANGE_CONTINUES : 0, target });
+            reach[(size_t)t.tid] = std::max(reach[(size_t)t.tid], stop); last_target = target; b = stop;
+        }
+    }
+    return plan;
+}
+
 PairArgs split_pair(int argc, char **argv) {
     PairArgs a; int sec = -1;   // -1 both sides, 0 tumor, 1 normal
     for (int i = 1; i < argc; i++) {
@@ -824,6 +903,7 @@ PairArgs split_pair(int argc, char **argv) {
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
         if (name == "--coverage-out" || name == "--coverage-thresholds" || name == "--coverage-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no coverage report");
         if (name == "--error-profile-out" || name == "--error-profile-min-depth" || name == "--error-profile-max-alt-permille") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no error profile");
+        if (name == "--family-stats-out" || name == "--family-stats-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no family report");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
             die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
@@ -1095,7 +1175,11 @@ int main(int argc, char **argv) {
         const char *lnames[UVC_NERRLEVEL]; for (int32_t l = 0; l < UVC_NERRLEVEL; l++) lnames[l] = uvcgpu_error_level_name(l);
         if (uvcio_errprofile_open(&o.errprof, lnames, UVC_NERRLEVEL, o.errprof_req.min_depth, o.errprof_req.max_alt_permille)) die(uvcio_last_error());
     }
-    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans);
+    std::vector<CovSpan> fam_spans((size_t)nref);
+    if (!o.famstats_out.empty() && !o.print_params && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
+    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans);
+    std::vector<std::vector<FamPiece>> fam_plan;
+    if (o.fam) fam_plan = plan_family_pieces(o, tiles, fam_spans, nref);
     if (o.n_shards > 1) {
         std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
         if (!batch_of.empty()) {   // balanced over batches: a batch is one region and goes to one shard, at the sum of its tiles' costs
@@ -1149,6 +1233,11 @@ int main(int argc, char **argv) {
         if (!probe) die("--coverage-out: cannot create " + o.coverage_out);
         fclose(probe);
     }
+    if (o.fam) {
+        FILE *probe = fopen(o.famstats_out.c_str(), "wb");
+        if (!probe) die("--family-stats-out: cannot create " + o.famstats_out);
+        fclose(probe);
+    }
     if (o.errprof) {
         FILE *probe = fopen(o.errprof_out.c_str(), "wb");
         if (!probe) die("--error-profile-out: cannot create " + o.errprof_out);
@@ -1178,7 +1267,7 @@ int main(int argc, char **argv) {
             // 4 * threads in front of it, so a slow early tile cannot make the rest of the genome pile up in memory
             { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ji < written + max_ahead; }); }
             std::string lines; std::vector<int64_t> nk(nt, 0);
-            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0, &cov_spans[(size_t)tiles[ti].tid]);
+            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0, &cov_spans[(size_t)tiles[ti].tid], o.fam ? &fam_plan[ti] : nullptr);
             w.n_tiles++;
             { std::lock_guard<std::mutex> g(mu); done[ji].swap(lines); ready[ji] = 1; for (size_t q = 0; q < nt; q++) tile_reads[ti + q] = nk[q]; }
             cv.notify_all();
@@ -1201,6 +1290,10 @@ int main(int argc, char **argv) {
     if (o.cov) {   // every tile has reported: the rows in target order, whichever worker finished first
         if (uvcio_coverage_write(o.cov, o.coverage_out.c_str())) die("--coverage-out: " + std::string(uvcio_last_error()));
         uvcio_coverage_close(o.cov);
+    }
+    if (o.fam) {   // every tile has reported: the rows in target order, sums do not depend on the order
+        if (uvcio_famstats_write(o.fam, o.famstats_out.c_str())) die("--family-stats-out: " + std::string(uvcio_last_error()));
+        uvcio_famstats_close(o.fam);
     }
     if (o.errprof) {   // every tile has reported: sums do not depend on the order
         if (uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())) die("--error-profile-out: " + std::string(uvcio_last_error()));

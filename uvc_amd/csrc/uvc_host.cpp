@@ -62,6 +62,7 @@ struct uvcgpu_region {
     int32_t *d_dup_units = nullptr; int64_t *d_dup_off = nullptr; int n_dup = 0; int64_t n_dup_work = 0;
     size_t off[UVC_NUM_FIELD_GROUPS + 1];
     bool has_reads = false, accumulated = false;
+    bool reads_given = false;    // set_reads went through for the present region, with or without reads (uvcgpu_region_family_stats)
     size_t p5flag_off = 0, occ_off = 0;
     // zero fill without what the last accumulate left untouched (RegionDev::dirty, uvc_launch_zero_state)
     uint8_t *d_dirty = nullptr; ZeroPlane *d_zero_planes = nullptr; int n_zero_planes = 0; int64_t zero_planes_npos = 0;
@@ -146,7 +147,7 @@ template <class T> int upload_raw(uvcgpu_region *r, const T *src, size_t count, 
 }
 // (the cache hands freed blocks to other handles at once: nothing of this handle may still be running on them)
 void quiesce(uvcgpu_region *r) { if (r->stream) (void)hipStreamSynchronize(r->stream); if (r->side) (void)hipStreamSynchronize(r->side); if (r->side3) (void)hipStreamSynchronize(r->side3); }
-void free_reads(uvcgpu_region *r) { if (!r->owned.empty()) quiesce(r); for (void *p : r->owned) hipFree(p); r->owned.clear(); r->has_reads = false; r->accumulated = false; }
+void free_reads(uvcgpu_region *r) { if (!r->owned.empty()) quiesce(r); for (void *p : r->owned) hipFree(p); r->owned.clear(); r->has_reads = false; r->reads_given = false; r->accumulated = false; }
 }  // namespace
 
 extern "C" {
@@ -467,7 +468,7 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
     }
     lap("P2 list sort + build");
     r->n_bases = d->n_bases;
-    r->has_reads = true;
+    r->has_reads = true; r->reads_given = true;
     return 0;
 }
 
@@ -482,7 +483,7 @@ static int uvcgpu_region_set_reads_impl(uvcgpu_region_t *r, const UvcReadSoA *in
     free_reads(r);
     struct SyncOnExit { hipStream_t s, s2; ~SyncOnExit() { hipStreamSynchronize(s); if (s2) hipStreamSynchronize(s2); } } sync_on_exit = { r->stream, r->side };   // no copy may outlive the caller's arrays, on any return path
     const int64_t n = in->n_reads;
-    if (n == 0) return 0;
+    if (n == 0) { r->reads_given = true; return 0; }
     if (n > INT32_MAX / 2) return fail(UVCGPU_EUNSUPPORTED, "more than 2^30 reads in one region");
     if (in->n_bases < 0 || in->n_cigar_ops < 0) return fail(UVCGPU_EINVAL, "bad reads");
     UvcReadSoA d = *in;
@@ -527,7 +528,7 @@ static int uvcgpu_region_set_reads_device_impl(uvcgpu_region_t *r, const UvcRead
     if (in->n_reads < 0 || in->n_fams < 0 || in->n_bases < 0 || in->n_cigar_ops < 0) return fail(UVCGPU_EINVAL, "bad reads");
     const bool timing = (getenv("UVCGPU_TIMING") != nullptr);
     free_reads(r);
-    if (in->n_reads == 0) return 0;
+    if (in->n_reads == 0) { r->reads_given = true; return 0; }
     if (in->n_reads > INT32_MAX / 2) return fail(UVCGPU_EUNSUPPORTED, "more than 2^30 reads in one region");
     return set_reads_on_device(r, in, timing, std::chrono::steady_clock::now());
 }
@@ -1520,6 +1521,49 @@ int uvcgpu_region_error_profile(uvcgpu_region_t *r, const UvcCoverageRange *rang
     return guarded("uvcgpu_region_error_profile", [&] { return uvcgpu_region_error_profile_impl(r, ranges, n_ranges, req, out); });
 }
 const char *uvcgpu_error_level_name(int32_t id) { return uvc_errprofile_level_name(id); }
+
+// ---- family statistics of ranges (uvc_famstats.hip) ----
+// The unit records, the fragments and the per-alignment columns belong to the reads of the handle (uvcgpu_region::owned): only set_reads, reset
+// and destroy free them, and the first two are refused while a score stream is open.  A score with release_state gives up the planes and
+// nothing else.  So the call is legal from set_reads on, whatever was scored since.  It shares the buffers of the coverage call.
+static int uvcgpu_region_family_stats_impl(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out) {
+    if (!r) return fail(UVCGPU_EINVAL, "family_stats: null region");
+    if (!r->reads_given) return fail(UVCGPU_EINVAL, "family_stats before set_reads: the region has no family units yet (uvcgpu_region_set_reads or _set_reads_device of this region comes first)");
+    if (!ranges || !out) return fail(UVCGPU_EINVAL, "family_stats: ranges and out must not be NULL");
+    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "family_stats: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
+    if (n_ranges > (INT32_MAX >> 10)) return fail(UVCGPU_EINVAL, "family_stats: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 10) + ")");
+    for (int64_t k = 0; k < n_ranges; k++) {
+        const UvcFamilyRange &q = ranges[k];
+        const std::string name = "family_stats: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
+        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
+        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
+        if (q.prev_end > q.pos_beg) return fail(UVCGPU_EINVAL, name + " has prev_end " + std::to_string(q.prev_end) + " behind its begin (prev_end is the end of an earlier range)");
+        if (k > 0 && q.prev_end < ranges[k - 1].prev_end) return fail(UVCGPU_EINVAL, name + " has prev_end " + std::to_string(q.prev_end) + " below the prev_end " + std::to_string(ranges[k - 1].prev_end) + " of range " + std::to_string(k - 1) + " (prev_end must not decrease)");
+        if (k > 0 && q.prev_end < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " has prev_end " + std::to_string(q.prev_end) + " below the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + ": that range's families would be counted twice");
+        if (q.flags & ~(int32_t)UVC_FAMRANGE_CONTINUES) return fail(UVCGPU_EINVAL, name + " has unknown flag bits (flags " + std::to_string(q.flags) + "; only UVC_FAMRANGE_CONTINUES = 1 is defined)");
+    }
+    const size_t out_bytes = sizeof(int64_t) * UVC_FAMSTAT_ROW * (size_t)n_ranges;
+    if (!r->has_reads) { memset(out, 0, out_bytes); return 0; }   // set_reads with zero reads: no family, nothing to launch
+    const size_t tab_bytes = (sizeof(UvcFamilyRange) * (size_t)n_ranges + 63) & ~(size_t)63, span_bytes = (sizeof(UvcUnitSpan) * (size_t)std::max(r->R.n_fs, 1) + 63) & ~(size_t)63;
+    { int rc1 = cov_buffers(r, tab_bytes + out_bytes + span_bytes, out_bytes, "family statistics"); if (rc1) return rc1; }   // [ranges] [rows] [unit spans]
+    size_t at = 0;   // the ranges through the handle's staging buffer, as coverage sends its table
+    { int rc1 = stage_upload(r, r->d_cov, ranges, sizeof(UvcFamilyRange) * (size_t)n_ranges, at, tab_bytes); if (rc1) return rc1; }
+    long long *d_rows = (long long *)(r->d_cov + tab_bytes);
+    int pi = -1;   // with profiling on, the three kernels as one more entry of uvcgpu_region_kernel_times (accumulate starts the list anew)
+    if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = "k_famstats"; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); }
+    uvc_launch_famstats(&r->R, r->W.pos, r->W.endpos, r->W.fs, (UvcUnitSpan *)(r->d_cov + tab_bytes + out_bytes), (const UvcFamilyRange *)r->d_cov, (int)n_ranges, d_rows, r->stream);
+    if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(r->h_cov, d_rows, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipStreamSynchronize(r->stream));
+    memcpy(out, r->h_cov, out_bytes);
+    return 0;
+}
+int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out) {
+    return guarded("uvcgpu_region_family_stats", [&] { return uvcgpu_region_family_stats_impl(r, ranges, n_ranges, out); });
+}
+const char *uvcgpu_family_stat_name(int32_t id) { return uvc_famstats_name(id); }
 
 int uvcgpu_region_create(uvcgpu_region_t **out, const UvcParams *params, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_create", [&] { return uvcgpu_region_create_impl(out, params, tid, beg, end, refseq); }); }
 int uvcgpu_region_reset(uvcgpu_region_t *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_reset", [&] { return uvcgpu_region_reset_impl(r, tid, beg, end, refseq); }); }

@@ -1349,3 +1349,70 @@ extern "C" int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *p
     return 0;
 }
 extern "C" void uvcio_errprofile_close(uvcio_errprofile_t *e) { delete e; }
+
+// ---------------------------------------------------------------- the UMI family report ----
+// the row layout is that of uvcgpu_region_family_stats (UVC_FAMSTAT_* of uvcgpu.h, include/uvc_famstats.def); the reserved word is not written
+struct uvcio_famstats {
+    struct Target { std::string chrom, name; int64_t beg, end; int64_t c[4]; };
+    std::vector<Target> targets;
+    int64_t first[UVC_FAMSTAT_ROW];   // the FIRST blocks of all pieces, summed (words below UVC_FAMSTAT_FIRST stay 0)
+    std::mutex mu;
+};
+extern "C" int uvcio_famstats_open(uvcio_famstats_t **out) {
+    if (!out) return fail(UVCGPU_EINVAL, "family report: bad argument");
+    uvcio_famstats *f = new uvcio_famstats;
+    memset(f->first, 0, sizeof(f->first));
+    *out = f;
+    return 0;
+}
+extern "C" int64_t uvcio_famstats_add_target(uvcio_famstats_t *f, const char *chrom, int64_t beg, int64_t end, const char *name) {
+    if (!f || !chrom) return fail(UVCGPU_EINVAL, "family report: bad target");
+    std::lock_guard<std::mutex> g(f->mu);
+    f->targets.push_back(uvcio_famstats::Target{ chrom, (name && *name) ? name : ".", beg, end, { 0, 0, 0, 0 } });
+    return (int64_t)f->targets.size() - 1;
+}
+extern "C" int uvcio_famstats_add_piece(uvcio_famstats_t *f, int64_t target, const int64_t *row) {
+    if (!f || !row) return fail(UVCGPU_EINVAL, "family report: bad piece");
+    std::lock_guard<std::mutex> g(f->mu);
+    if (target < 0 || target >= (int64_t)f->targets.size()) return fail(UVCGPU_EINVAL, "family report: piece of target " + std::to_string(target) + ", which does not exist");
+    for (int k = 0; k < 4; k++) f->targets[(size_t)target].c[k] += row[UVC_FAMSTAT_TARGET + k];
+    for (int k = UVC_FAMSTAT_FIRST; k < UVC_FAMSTAT_ROW; k++) f->first[k] += row[k];
+    return 0;
+}
+static int64_t fs_ratio(int64_t num, int64_t den) { return den ? 1000 * num / den : 0; }
+extern "C" int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path) {
+    if (!f || !path || !*path) return fail(UVCGPU_EINVAL, "family report: bad argument");
+    static const char *const NAMES[7] = { "families", "fragments", "alignments", "families_both_strands", "families_umi", "families_duplex_tag", "families_amplicon" };
+    const int64_t *c = f->first + UVC_FAMSTAT_FIRST;
+    std::string text = "##family_stats=1\n##summary and histograms: every family that overlaps a target, counted once; target lines: every family that overlaps the target\n#summary\n";
+    for (int k = 0; k < 7; k++) text += std::string(NAMES[k]) + "\t" + std::to_string(c[k]) + "\n";
+    text += "duplication_permille\t" + std::to_string(fs_ratio(c[1] - c[0], c[1])) + "\nmean_family_size_x1000\t" + std::to_string(fs_ratio(c[1], c[0])) + "\nboth_strands_permille\t" + std::to_string(fs_ratio(c[3], c[0])) + "\n";
+    text += "#family_size\tfamilies\n";
+    for (int k = 0; k < UVC_FAMSTAT_NSIZE; k++) text += std::to_string(k + 1) + (k + 1 == UVC_FAMSTAT_NSIZE ? "+" : "") + "\t" + std::to_string(f->first[UVC_FAMSTAT_SIZE + k]) + "\n";
+    text += "#strand0_size\tstrand1_size\tfamilies\n";
+    auto label = [](int v) { return std::to_string(v) + (v == UVC_FAMSTAT_STRAND_CAP ? "+" : ""); };
+    for (int a = 0; a <= UVC_FAMSTAT_STRAND_CAP; a++)
+        for (int b = 0; b <= UVC_FAMSTAT_STRAND_CAP; b++) {
+            const int64_t v = f->first[UVC_FAMSTAT_STRANDS + a * (UVC_FAMSTAT_STRAND_CAP + 1) + b];
+            if (v) text += label(a) + "\t" + label(b) + "\t" + std::to_string(v) + "\n";
+        }
+    text += "#chrom\tbeg\tend\tname\tfamilies\tfragments\talignments\tfamilies_both_strands\tmean_family_size_x1000\tboth_strands_permille\n";
+    for (const uvcio_famstats::Target &t : f->targets)
+        text += t.chrom + "\t" + std::to_string(t.beg) + "\t" + std::to_string(t.end) + "\t" + t.name + "\t" + std::to_string(t.c[0]) + "\t" + std::to_string(t.c[1]) + "\t" + std::to_string(t.c[2]) + "\t"
+                + std::to_string(t.c[3]) + "\t" + std::to_string(fs_ratio(t.c[1], t.c[0])) + "\t" + std::to_string(fs_ratio(t.c[3], t.c[0])) + "\n";
+    const std::string p = path;
+    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
+        uvcio_bgzf_writer_t *zw = nullptr;
+        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
+        const int rc2 = uvcio_bgzf_write_close(zw);
+        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+        return 0;
+    }
+    FILE *fo = fopen(path, "wb");
+    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
+    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+    return 0;
+}
+extern "C" void uvcio_famstats_close(uvcio_famstats_t *f) { delete f; }

@@ -25,6 +25,9 @@ static_assert(sizeof(UvcScoreRangeDev) == 16, "the host uploads the range table 
 // Entry n_ranges of a table: { 0, n_total }
 struct UvcRangeRow { int x0, first; };
 static_assert(sizeof(UvcRangeRow) == 8, "the host uploads the range table as 8-byte rows");
+// uvcgpu_region_family_stats: smallest pos and largest reference end of the alignments of one family-strand unit (scratch the host sizes)
+struct UvcUnitSpan { int lo, hi; };
+static_assert(sizeof(UvcUnitSpan) == 8, "the host sizes the span scratch as 8-byte rows");
 
 // What the three score launchers share (host-side aggregate; ScorePrep of uvc_host.cpp owns one).  ranges: the device table of
 // uvcgpu_region_score_ranges or NULL; n_compact: the length of the compact axis the ranges make.  force_sites: device copy of
@@ -76,6 +79,10 @@ int64_t uvc_coverage_scratch_rows(int n_ranges, int64_t n_total);
 void uvc_launch_errprofile(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, int min_depth, int max_alt_permille, long long *d_out, long long *d_scratch, hipStream_t s);
 const char *uvc_errprofile_level_name(int id);
 int64_t uvc_errprofile_scratch_cells(void);
+// ---- uvc_famstats.hip: pos / endpos / fs_of = the per-alignment columns of RawReads; d_span: n_fs rows of scratch; d_ranges: the caller's
+// n_ranges rows; d_rows: n_ranges rows of UVC_FAMSTAT_ROW words ----
+void uvc_launch_famstats(const RegionDev *R, const int32_t *pos, const int32_t *endpos, const int32_t *fs_of, UvcUnitSpan *d_span, const UvcFamilyRange *d_ranges, int n_ranges, long long *d_rows, hipStream_t s);
+const char *uvc_famstats_name(int id);
 // ---- uvc_gap.hip: the rocPRIM sorts and the small gathers ----
 size_t uvc_gap_sort_tmp_bytes(size_t n);
 int uvc_gap_sort(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout, const unsigned long long *vin, unsigned long long *vout, size_t n, int end_bit, hipStream_t s);

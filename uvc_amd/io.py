@@ -176,6 +176,48 @@ class BgzfWriter:
         self.close()
 
 
+class FamilyStats:
+    """uvcio_famstats_*: the store behind uvc1-mi355x --family-stats-out.  Targets are added in report order; a piece is one row of
+    Region.family_stats (its TARGET block goes to the target, its FIRST block to the run's sum; any thread, any order); write() makes the text."""
+
+    def __init__(self):
+        d = dll()
+        d.uvcio_famstats_open.restype, d.uvcio_famstats_open.argtypes = C.c_int, [C.POINTER(C.c_void_p)]
+        d.uvcio_famstats_add_target.restype, d.uvcio_famstats_add_target.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
+        d.uvcio_famstats_add_piece.restype, d.uvcio_famstats_add_piece.argtypes = C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]
+        d.uvcio_famstats_write.restype, d.uvcio_famstats_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
+        d.uvcio_famstats_close.restype, d.uvcio_famstats_close.argtypes = None, [C.c_void_p]
+        self.h = C.c_void_p()
+        _check(d.uvcio_famstats_open(C.byref(self.h)))
+
+    def add_target(self, chrom, beg, end, name=None):
+        t = dll().uvcio_famstats_add_target(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
+        if t < 0:
+            _check(int(t))
+        return int(t)
+
+    def add_piece(self, target, row):
+        import numpy as np
+        row = np.ascontiguousarray(row, dtype=np.int64)
+        if row.shape != (365,):
+            raise ValueError("a piece is one row of Region.family_stats (365 values)")
+        _check(dll().uvcio_famstats_add_piece(self.h, int(target), row.ctypes.data))
+
+    def write(self, path):
+        _check(dll().uvcio_famstats_write(self.h, str(path).encode()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            dll().uvcio_famstats_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def plan_regions(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per_thread_mb=1536):
     """SamIter::iternext without a BED file (grouping.cpp:225-312) over alignment columns in file order: the blocks the reference hands
     to process_batch, as dicts (tid, beg, end, flag, batch, n_reads)."""

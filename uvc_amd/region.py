@@ -24,6 +24,7 @@ class UvcError(RuntimeError):
 
 
 COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
+FAMILY_STATS = _ffi.FAMILY_STATS             # the sections of a row of Region.family_stats, in row order (include/uvc_famstats.def)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
 
 _gpu_lib = None
@@ -494,6 +495,21 @@ class Region:
         req = _ffi.UvcErrorProfileRequest(int(min_depth), int(max_alt_permille))
         out = np.zeros((_ffi.ENUMS["UVC_NERRLEVEL"], _ffi.ENUMS["UVC_ERR_ROW"]), dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data))
+        return out
+
+    def family_stats(self, ranges):
+        """uvcgpu_region_family_stats: family-size statistics of `ranges` -- rows of (pos_beg, pos_end[, prev_end[, flags]]), zero-based, half
+        open, sorted and disjoint, inside the region; prev_end (default: pos_beg) <= pos_beg, not decreasing and not below the end of the range
+        before; flags bit 0 = the range continues the target of the range before -- reduced on the device from the family units of the
+        region's reads.  int64 [n_ranges, UVC_FAMSTAT_ROW]: the TARGET block (families, fragments, alignments, families on both strands, of the
+        families that overlap the range) and the FIRST block (the same, three flag counters, a reserved word, size[64], strands[17][17], of
+        the families that overlap it and begin at or behind prev_end); FAMILY_STATS names the sections, uvcgpu.h has the rules.  After
+        set_reads() / set_reads_device(); accumulate and scores neither are needed nor get in the way."""
+        fn = self._ranges_fn("region_family_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        rows = [(int(q[0]), int(q[1]), int(q[2]) if len(q) > 2 else int(q[0]), int(q[3]) if len(q) > 3 else 0) for q in ranges]
+        arr = (_ffi.UvcFamilyRange * max(len(rows), 1))(*[_ffi.UvcFamilyRange(*q) for q in rows])
+        out = np.zeros((len(rows), _ffi.ENUMS["UVC_FAMSTAT_ROW"]), dtype=np.int64)
+        self._check(fn(self.h, arr, len(rows), out.ctypes.data))
         return out
 
     def score_stream_bytes_per_record(self):
