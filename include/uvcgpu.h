@@ -542,6 +542,28 @@ typedef struct UvcFamilyRange { int32_t pos_beg, pos_end, prev_end, flags; } Uvc
  *   UVC_FAMRANGE_CONTINUES.  `out` is written only by a call that returns 0. */
 int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out /* [n_ranges][UVC_FAMSTAT_ROW] */);
 const char *uvcgpu_family_stat_name(int32_t id);   /* "target_families" .. "strands"; NULL for an id outside 0..UVC_NFAMSTAT - 1 */
+/* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
+ * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
+ * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when
+ * m_0(p) == 0 (the bits and their order: include/uvc_callable.def); a criterion of 0 is not tested, and an untested measure is not read.
+ * p is callable iff its mask is 0.  A run is a maximal stretch of consecutive positions of ONE range with equal masks: runs never cross
+ * a range border, even where two ranges touch and the masks on both sides are equal. */
+enum UvcCallableBit { UVC_CALL_LOW_aDP = 0, UVC_CALL_LOW_bDP, UVC_CALL_LOW_cDP1, UVC_CALL_LOW_cDP12, UVC_CALL_LOW_cDP2, UVC_CALL_LOW_dDP1,
+                      UVC_CALL_EXCESS_aDP, UVC_CALL_NO_COVERAGE, UVC_NCALLBIT };
+typedef struct UvcCallableRequest { int32_t min_depth[UVC_NCOV]; int32_t max_aDP; } UvcCallableRequest;   /* 0 = not tested */
+typedef struct UvcCallableRun { int32_t range, pos_beg, pos_end, mask; } UvcCallableRun;   /* range: index into `ranges`; zero-based, half open */
+/* The runs of every range, sorted by (range, pos_beg); the runs of a range tile it exactly.  Classified, counted and compacted on the
+ * device (integers only: the same bytes from call to call); nothing per position travels to the host, only 16 bytes per run.
+ *   Sizes first, as for uvcgpu_region_indel_alleles: *n_runs always receives the number of runs; when run_capacity is smaller the call
+ *   returns UVCGPU_ENOMEM and writes nothing to `runs`; a second call with enough room returns the data.
+ *   Ranges and the window in which the call is legal: as for uvcgpu_region_coverage (sorted, disjoint, inside [beg, end + 1); after
+ *   accumulate, before the planes are released, while no score stream is open).  UVCGPU_EINVAL before any launch, with a message that names
+ *   the reason (a range by its index): every refusal of uvcgpu_region_coverage; a negative min_depth[k] or max_aDP; a NULL req or n_runs;
+ *   run_capacity < 0; a NULL runs with run_capacity > 0.  A refused call writes neither *n_runs nor runs.  An all-zero request is legal:
+ *   only UVC_CALL_NO_COVERAGE can then be set. */
+int uvcgpu_region_callable(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcCallableRequest *req,
+                           UvcCallableRun *runs, int64_t run_capacity, int64_t *n_runs);
+const char *uvcgpu_callable_bit_name(int32_t bit);   /* "LOW_aDP" .. "NO_COVERAGE"; NULL for a bit outside 0..UVC_NCALLBIT - 1 */
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);

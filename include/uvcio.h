@@ -210,6 +210,26 @@ int64_t uvcio_famstats_add_target(uvcio_famstats_t *f, const char *chrom, int64_
 int uvcio_famstats_add_piece(uvcio_famstats_t *f, int64_t target, const int64_t *row /* [365] */);
 int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path);
 void uvcio_famstats_close(uvcio_famstats_t *f);
+/* ---- the callable-region BED (uvc1-mi355x --callable-out) ----
+ * The targets in report order and, per target, the runs that tiles report for its pieces with uvcgpu_region_callable.  add_runs takes the
+ * runs of one call as they came back and the target of each of the call's ranges, under a lock: pieces come in any order and from any
+ * thread; a run outside its target is refused.  write, in target order: sorts a target's runs by position, FILLS every position of the
+ * target that no piece reported with the mask of depth 0 (NO_COVERAGE and every tested LOW_* bit -- the rule by which the coverage report
+ * counts such positions as depth 0) and JOINS neighbouring runs of equal mask inside the target, never across targets: the text does not
+ * depend on how tiles cut a target.  Overlapping pieces fail the write.
+ * Text: "##callable_regions=1", "#min_depth<TAB>aDP=N,...", "#max_aDP<TAB>N", "#chrom beg end class target"; one BED line per run, class =
+ * CALLABLE or the names of the set bits joined by commas in bit order, target = the name given or "."; then "#summary<TAB>positions<TAB>N",
+ * "#summary<TAB>CALLABLE<TAB>N" and one "#summary<TAB>bit<TAB>N" per bit.  Tab-separated integers; a path that ends in .gz is written
+ * block-gzipped (uvcio_bgzf_write_*).  The store holds 16 bytes per run until close. */
+typedef struct uvcio_callable uvcio_callable_t;
+int uvcio_callable_open(uvcio_callable_t **out, const char *const *measure_names, int32_t n_measures, const int32_t *min_depth /* [n_measures] */, int32_t max_aDP,
+                        const char *const *bit_names, int32_t n_bits /* n_measures + 2: LOW_* per measure, EXCESS_aDP, NO_COVERAGE */);
+/* [beg, end): the positions of the target inside its contig (end <= beg: a target without positions, no line).  Returns the target's index, or a negative code. */
+int64_t uvcio_callable_add_target(uvcio_callable_t *c, const char *chrom, int64_t beg, int64_t end, const char *name /* NULL or empty: "." */);
+int uvcio_callable_add_runs(uvcio_callable_t *c, const int64_t *target_of_range, int64_t n_ranges, const UvcCallableRun *runs, int64_t n_runs);
+int64_t uvcio_callable_n_runs(const uvcio_callable_t *c);   /* the runs held so far */
+int uvcio_callable_write(const uvcio_callable_t *c, const char *path);
+void uvcio_callable_close(uvcio_callable_t *c);
 /* bcftools concat -n (uvcTN.sh:100): the BGZF files one after the other, the 28-byte end-of-file marker of all but the last dropped. */
 int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in);
 /* The whole text of a (block-)gzipped or plain file (the tumor VCF of a T/N pair); *buf is malloc'ed, the caller frees it. */

@@ -87,6 +87,14 @@ class UvcFamilyRange(C.Structure):
     _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("prev_end", C.c_int32), ("flags", C.c_int32)]
 
 
+class UvcCallableRequest(C.Structure):
+    _fields_ = [("min_depth", C.c_int32 * 6), ("max_aDP", C.c_int32)]
+
+
+class UvcCallableRun(C.Structure):
+    _fields_ = [("range", C.c_int32), ("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("mask", C.c_int32)]
+
+
 class UvcScoreOut(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n_records", C.c_int64), ("fields", C.c_void_p)]
 
@@ -155,6 +163,19 @@ FAMSTAT_SECTIONS = _read_famstats_def()
 FAMILY_STATS = [n for n, _, _ in FAMSTAT_SECTIONS]
 assert [ENUMS["UVC_FAMSTAT_" + n] for n in FAMILY_STATS] == list(range(ENUMS["UVC_NFAMSTAT"]))
 assert sum(w for _, _, w in FAMSTAT_SECTIONS) == ENUMS["UVC_FAMSTAT_ROW"] and all(f == sum(w for _, _, w in FAMSTAT_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMSTAT_SECTIONS))
+
+
+def _read_callable_def():
+    """The bits of a mask of uvcgpu_region_callable in bit order: the rows of include/uvc_callable.def."""
+    with open(os.path.join(ROOT, "include", "uvc_callable.def")) as fh:
+        rows = [re.match(r"UVC_CALLBIT\((\w+)\)\s*$", line) for line in fh]
+    return [m.group(1) for m in rows if m]
+
+
+# the bits of a callability mask (UvcCallableBit): the table of include/uvc_callable.def, checked against the header's enums and the measures
+CALLABLE_BITS = _read_callable_def()
+assert [ENUMS["UVC_CALL_" + n] for n in CALLABLE_BITS] == list(range(ENUMS["UVC_NCALLBIT"]))
+assert CALLABLE_BITS[:len(COVERAGE_MEASURES)] == ["LOW_" + m for m in COVERAGE_MEASURES] and C.sizeof(UvcCallableRequest) == 4 * (ENUMS["UVC_NCOV"] + 1)
 
 
 class Lib:

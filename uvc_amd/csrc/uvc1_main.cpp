@@ -57,6 +57,11 @@ struct Opts {
     std::string famstats_out;    // --family-stats-out PATH: the UMI family report; empty = none
     int64_t famstats_window = 0; // --family-stats-window N: the targets are windows of N bp (0: the BED lines)
     uvcio_famstats_t *fam = nullptr;   // the report's store, filled by the workers (main)
+    std::string callable_out;    // --callable-out PATH: the callable-region BED; empty = none
+    UvcCallableRequest call_req = [] { UvcCallableRequest q{}; q.min_depth[UVC_COV_cDP12] = 20; return q; }(); bool call_req_given = false;   // --callable-min-depth, --callable-max-aDP
+    uvcio_callable_t *callable = nullptr;   // the BED's store, filled by the workers (main)
+    std::vector<int64_t> call_contig_target;   // without a BED file: per contig the store's target of its called span (-1: not called)
+    std::vector<std::pair<int64_t, int64_t>> call_target_span;   // per target of the store its [beg, end): a tile's stretch is clipped to it
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -109,6 +114,9 @@ const OptRow OPTS[] = {
     { "--error-profile-max-alt-permille", O_CLI, false, "50", "with --error-profile-out: a position whose largest non-reference count is above this many thousandths of the level's depth counts as variant and stays out of the bins (0..1000)" },
     { "--family-stats-out", O_CLI, false, "", "write the UMI family report here (tab-separated; block-gzipped when the name ends in .gz): over all targets the number of read families, fragments and alignments, the families seen on both strands, with a UMI, a duplex tag or the amplicon flag, the duplication rate, the family-size histogram (1 .. 64+) and the strand0 x strand1 size histogram (0 .. 16+), then per BED line, or per --family-stats-window, the families that overlap it -- the families exactly as this caller groups and consumes them, reduced on the device from each tile's family units.  The VCF does not depend on it" },
     { "--family-stats-window", O_CLI, false, "0", "with --family-stats-out and no BED file: the targets are windows of this many bp, aligned to multiples of it on each contig and clipped to the called span" },
+    { "--callable-out", O_CLI, false, "", "write the callable regions here as BED lines contig, beg, end, class, target (tab-separated; block-gzipped when the name ends in .gz): every target -- BED line, or called contig span without a BED file -- cut into stretches of equal class, CALLABLE or the criteria the stretch fails (LOW_<depth>, EXCESS_aDP, NO_COVERAGE), classified on the device from the planes of each tile over the six depths of --coverage-out; #summary lines count the positions per class.  The VCF does not depend on it" },
+    { "--callable-min-depth", O_CLI, false, "cDP12=20", "with --callable-out: NAME=N[,NAME=N...], the smallest depth a callable position has of each named depth (aDP bDP cDP1 cDP12 cDP2 dDP1; 0 or unnamed: not tested)" },
+    { "--callable-max-aDP", O_CLI, false, "0", "with --callable-out: the largest raw depth aDP a callable position has (0: not tested)" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -275,6 +283,26 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--error-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--error-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.errprof_req.max_alt_permille = (int32_t)x; o.errprof_gate_given = true; }
         else if (n0 == "--family-stats-out") { o.famstats_out = val(); if (o.famstats_out.empty()) die("--family-stats-out needs a path"); }
         else if (n0 == "--family-stats-window") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--family-stats-window takes a window length in bp, not '" + v + "'"); o.famstats_window = (int64_t)x; }
+        else if (n0 == "--callable-out") { o.callable_out = val(); if (o.callable_out.empty()) die("--callable-out needs a path"); }
+        else if (n0 == "--callable-min-depth") {   // NAME=N,...: the names of uvcgpu_coverage_measure_name, each at most once, whole numbers >= 0
+            const std::string v = val(); o.call_req_given = true;
+            bool seen[UVC_NCOV] = {};
+            for (int32_t m = 0; m < UVC_NCOV; m++) o.call_req.min_depth[m] = 0;
+            for (size_t at = 0; at <= v.size();) {
+                size_t c = v.find(',', at); if (c == std::string::npos) c = v.size();
+                const std::string item = v.substr(at, c - at); const size_t eq = item.find('=');
+                const std::string name = item.substr(0, eq), num = (eq == std::string::npos ? "" : item.substr(eq + 1));
+                int32_t m = -1;
+                for (int32_t q = 0; q < UVC_NCOV; q++) if (name == uvcgpu_coverage_measure_name(q)) m = q;
+                double x;
+                if (m < 0) die("--callable-min-depth takes NAME=N[,NAME=N...] with the names aDP bDP cDP1 cDP12 cDP2 dDP1, not '" + v + "' ('" + name + "' is not a depth)");
+                if (num == "true" || num == "false" || num.find_first_not_of("0123456789") != std::string::npos || !number(num, &x) || x > 2e9) die("--callable-min-depth takes NAME=N[,NAME=N...], not '" + v + "' ('" + num + "' is not a whole number >= 0)");
+                if (seen[m]) die("--callable-min-depth names " + name + " twice in '" + v + "'");
+                seen[m] = true; o.call_req.min_depth[m] = (int32_t)x;
+                at = c + 1;
+            }
+        }
+        else if (n0 == "--callable-max-aDP") { const std::string v = val(); double x; if (v.find_first_not_of("0123456789") != std::string::npos || !number(v, &x) || x > 2e9) die("--callable-max-aDP takes a depth (0 = off), not '" + v + "'"); o.call_req.max_aDP = (int32_t)x; o.call_req_given = true; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -344,6 +372,13 @@ Opts parse(int argc, char **argv) {
         if (has_bed && o.famstats_window > 0) die("--family-stats-window cannot go with -R / --bed-in-fname: with a BED file the targets of --family-stats-out are its lines");
         if (!has_bed && o.famstats_window <= 0) die("--family-stats-out needs --family-stats-window N without -R / --bed-in-fname: there are no BED lines to report on");
     }
+    if (o.callable_out.empty()) {   // before any file or device
+        if (o.call_req_given) die("--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file");
+    } else {
+        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--callable-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
+        if (o.n_shards > 1) die("--callable-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": a target can straddle shards, and --concat joins VCFs only");
+        if (o.repeat != 1) die("--callable-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would report its runs that many times");
+    }
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -370,7 +405,8 @@ void print_params(const Opts &o, const char *prefix = "") {
 // `run_beg` = begin of the run (incluBegPosition of the BED line the run came from, main.cpp:655-656).
 // `target` (--coverage-out with a BED file): the report row of the BED line the tile was cut from.
 // `fam_target` (--family-stats-out with a BED file): the same for the family report.
-struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; int64_t fam_target = -1; };
+// `call_target` (--callable-out): the store's target the tile was cut from; -1 (the reference's own cuts): the called span of its contig.
+struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; int64_t fam_target = -1; int64_t call_target = -1; };
 
 // one worker: its own handles, one region handle for all of its tiles
 struct Worker {
@@ -386,6 +422,7 @@ struct Worker {
     std::vector<UvcCoverageRange> cov_ranges; std::vector<int64_t> cov_targets, cov_rows;   // --coverage-out: the pieces of one tile
     std::vector<UvcCoverageRange> err_ranges;   // --error-profile-out: the stretches one tile owns
     std::vector<UvcFamilyRange> fam_ranges; std::vector<int64_t> fam_targets, fam_rows;   // --family-stats-out: the pieces of one tile
+    std::vector<UvcCoverageRange> call_ranges; std::vector<int64_t> call_targets; std::vector<UvcCallableRun> call_runs;   // --callable-out: the pieces of one tile, their runs
 };
 
 // --coverage-out: the pieces of targets that one accumulated tile owns, reduced by one uvcgpu_region_coverage and merged into the report.
@@ -421,6 +458,27 @@ void errprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
     int64_t prof[UVC_NERRLEVEL * UVC_ERR_ROW];
     if (uvcgpu_region_error_profile(w.reg, w.err_ranges.data(), (int64_t)w.err_ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
     if (uvcio_errprofile_add(o.errprof, prof)) die(uvcio_last_error());
+}
+// --callable-out: the runs of the stretches one accumulated tile owns -- the list coverage_of_tile reports on -- by one
+// uvcgpu_region_callable (sizes first: the buffer of the last tiles, grown where a tile has more runs), handed to the store with each
+// stretch's target.  Joining across tiles is the store's.
+void callable_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of) {
+    w.call_ranges.clear(); w.call_targets.clear();
+    for (size_t q = 0; q < own.size(); q++) {   // a region of the reference's own cuts begins and ends with its reads, which may reach over the called span: the target's part of it
+        if (target_of[q] < 0) die("--callable-out: a tile without a target (internal error)");
+        const std::pair<int64_t, int64_t> &span = o.call_target_span[(size_t)target_of[q]];
+        const int64_t b = std::max(own[q].first, span.first), e = std::min(own[q].second, span.second);
+        if (e > b) { w.call_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.call_targets.push_back(target_of[q]); }
+    }
+    if (w.call_ranges.empty()) return;
+    int64_t n = 0;
+    int rc = uvcgpu_region_callable(w.reg, w.call_ranges.data(), (int64_t)w.call_ranges.size(), &o.call_req, w.call_runs.data(), (int64_t)w.call_runs.size(), &n);
+    if (rc == UVCGPU_ENOMEM && n > (int64_t)w.call_runs.size()) {
+        w.call_runs.resize((size_t)n);
+        rc = uvcgpu_region_callable(w.reg, w.call_ranges.data(), (int64_t)w.call_ranges.size(), &o.call_req, w.call_runs.data(), (int64_t)w.call_runs.size(), &n);
+    }
+    if (rc) die(uvcgpu_last_error());
+    if (uvcio_callable_add_runs(o.callable, w.call_targets.data(), (int64_t)w.call_targets.size(), w.call_runs.data(), n)) die(uvcio_last_error());
 }
 // --family-stats-out: the pieces of targets that the tiles own, planned before any worker starts (plan_family_pieces), so that the report
 // does not depend on which worker takes which tile.  A piece is a tile's [beg, end), cut at the window borders in window mode: the planned
@@ -520,18 +578,20 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     w.t_reads += now() - t0; t0 = now();
     if (o.fam && fam_pieces) family_stats_of_tile(w, o, fam_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --family-stats-out: the units of set_reads, before anything else
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
-    if (o.cov || o.errprof) {   // --coverage-out, --error-profile-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
+    if (o.cov || o.errprof || o.callable) {   // --coverage-out, --error-profile-out, --callable-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
                    // point t.end itself, which lies outside every target the tile was cut from (and which two regions of the reference's cuts share)
-        std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of;
-        if (n_merged == 0) { own.emplace_back(first, std::min(last_excl, t.end)); target_of.push_back(t.target); }
+        std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
+        auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !o.callable ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
+        if (n_merged == 0) { own.emplace_back(first, std::min(last_excl, t.end)); target_of.push_back(t.target); call_target_of.push_back(call_target(t)); }
         else for (size_t q = 0; q < n_merged; q++) {
             const Tile &l = (&t0_)[q];
             const int64_t l_first = std::max(l.beg, bam_beg);
             const int64_t l_excl = l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end);
-            own.emplace_back(l_first, std::min(l_excl, l.end)); target_of.push_back(l.target);
+            own.emplace_back(l_first, std::min(l_excl, l.end)); target_of.push_back(l.target); call_target_of.push_back(call_target(l));
         }
         if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
         if (o.errprof) errprofile_of_tile(w, o, own);
+        if (o.callable) callable_of_tile(w, o, own, call_target_of);
     }
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
@@ -670,7 +730,8 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     if (ref_cuts && uvcio_planner_open(&planner, lens.data(), nref, (o.threads > 0 ? o.threads : 8) /* the reference's -t default (CmdLineArgs.hpp:34): enters only where a batch of regions ends */, o.mem_per_thread)) die(uvcio_last_error());
     std::vector<int32_t> pl_tid, pl_pos, pl_end; std::vector<uint16_t> pl_flag;   // one window's columns
     auto take_cuts = [&]() { UvcRegionCut c[256]; int64_t k; while ((k = uvcio_planner_take(planner, c, 256)) > 0) for (int64_t q = 0; q < k; q++) tiles.push_back(Tile{ c[q].tid, names[(size_t)c[q].tid], c[q].beg, c[q].end, false, false, c[q].beg }); };
-    int64_t cov_target = -1, fam_target = -1;   // the report rows of the BED line being added
+    int64_t cov_target = -1, fam_target = -1, call_target = -1;   // the report rows of the BED line being added
+    if (o.callable) o.call_contig_target.assign((size_t)nref, -1);
     auto add = [&](int32_t tid, int64_t beg, int64_t end) {
         if (o.cov && cov_spans && o.coverage_window > 0 && end > beg) {   // the windows of this span: aligned to multiples of N, clipped to it
             const int64_t N = o.coverage_window;
@@ -695,7 +756,13 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
                 if (sp.first < 0) sp.first = row;
             }
         }
-        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target, fam_target }); return; }
+        if (o.callable && bed_path.empty()) {   // --callable-out without a BED file: the called span of the contig is one target
+            if (o.call_contig_target[(size_t)tid] >= 0) die("--callable-out: a contig is called twice (internal error)");
+            call_target = o.call_contig_target[(size_t)tid] = uvcio_callable_add_target(o.callable, names[(size_t)tid].c_str(), beg, end, nullptr);
+            if (call_target < 0) die(uvcio_last_error());
+            o.call_target_span.emplace_back(beg, std::max(beg, end));
+        }
+        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target, fam_target, call_target }); return; }
         const int64_t W = 4000000;   // the planning pass reads the span window by window; an alignment is taken by the window it starts in (the first window also takes those that reach into it)
         for (int64_t wb = beg; wb < end; wb += W) {
             UvcBamBatch b;
@@ -731,6 +798,11 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
             if (o.fam) {   // one report row per BED line, its own numbers and column 4 as the name
                 fam_target = uvcio_famstats_add_target(o.fam, chrom, b, e, n_col >= 4 ? bname : nullptr);
                 if (fam_target < 0) die(uvcio_last_error());
+            }
+            if (o.callable) {   // one target per BED line: its positions inside the contig, column 4 as the name
+                call_target = uvcio_callable_add_target(o.callable, chrom, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]), n_col >= 4 ? bname : nullptr);
+                if (call_target < 0) die(uvcio_last_error());
+                o.call_target_span.emplace_back(std::max<long long>(0, b), std::max<long long>(std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid])));
             }
             add(tid, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]));
             l_tid.push_back(tid); l_beg.push_back(std::max<long long>(0, b)); l_end.push_back(std::min<long long>(e, lens[(size_t)tid]));
@@ -903,6 +975,7 @@ PairArgs split_pair(int argc, char **argv) {
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
         if (name == "--coverage-out" || name == "--coverage-thresholds" || name == "--coverage-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no coverage report");
         if (name == "--error-profile-out" || name == "--error-profile-min-depth" || name == "--error-profile-max-alt-permille") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no error profile");
+        if (name == "--callable-out" || name == "--callable-min-depth" || name == "--callable-max-aDP") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no callable regions");
         if (name == "--family-stats-out" || name == "--family-stats-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no family report");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
@@ -1175,6 +1248,12 @@ int main(int argc, char **argv) {
         const char *lnames[UVC_NERRLEVEL]; for (int32_t l = 0; l < UVC_NERRLEVEL; l++) lnames[l] = uvcgpu_error_level_name(l);
         if (uvcio_errprofile_open(&o.errprof, lnames, UVC_NERRLEVEL, o.errprof_req.min_depth, o.errprof_req.max_alt_permille)) die(uvcio_last_error());
     }
+    if (!o.callable_out.empty() && !o.print_params) {
+        const char *mnames[UVC_NCOV], *bnames[UVC_NCALLBIT];
+        for (int32_t m = 0; m < UVC_NCOV; m++) mnames[m] = uvcgpu_coverage_measure_name(m);
+        for (int32_t b = 0; b < UVC_NCALLBIT; b++) bnames[b] = uvcgpu_callable_bit_name(b);
+        if (uvcio_callable_open(&o.callable, mnames, UVC_NCOV, o.call_req.min_depth, o.call_req.max_aDP, bnames, UVC_NCALLBIT)) die(uvcio_last_error());
+    }
     std::vector<CovSpan> fam_spans((size_t)nref);
     if (!o.famstats_out.empty() && !o.print_params && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
     std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans);
@@ -1238,6 +1317,11 @@ int main(int argc, char **argv) {
         if (!probe) die("--family-stats-out: cannot create " + o.famstats_out);
         fclose(probe);
     }
+    if (o.callable) {
+        FILE *probe = fopen(o.callable_out.c_str(), "wb");
+        if (!probe) die("--callable-out: cannot create " + o.callable_out);
+        fclose(probe);
+    }
     if (o.errprof) {
         FILE *probe = fopen(o.errprof_out.c_str(), "wb");
         if (!probe) die("--error-profile-out: cannot create " + o.errprof_out);
@@ -1294,6 +1378,11 @@ int main(int argc, char **argv) {
     if (o.fam) {   // every tile has reported: the rows in target order, sums do not depend on the order
         if (uvcio_famstats_write(o.fam, o.famstats_out.c_str())) die("--family-stats-out: " + std::string(uvcio_last_error()));
         uvcio_famstats_close(o.fam);
+    }
+    if (o.callable) {   // every tile has reported: sorted, filled and joined per target, in target order
+        if (o.timing) fprintf(stderr, "uvc1-mi355x: --callable-out holds %lld runs\n", (long long)uvcio_callable_n_runs(o.callable));
+        if (uvcio_callable_write(o.callable, o.callable_out.c_str())) die("--callable-out: " + std::string(uvcio_last_error()));
+        uvcio_callable_close(o.callable);
     }
     if (o.errprof) {   // every tile has reported: sums do not depend on the order
         if (uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())) die("--error-profile-out: " + std::string(uvcio_last_error()));

@@ -31,32 +31,6 @@ const char *const COV_NAMES[UVC_NCOV] = {
 #undef UVC_COV
 };
 
-// the value of a measure at plane index x: the plane's cell, summed over both strands / the six BASE symbols where the group has them.
-// 32-bit like block_stats_at: each sum counts a read, fragment or family of the region at most once, and a region holds fewer than 2^31.
-DEV int cov_PREP32(const RegionDev &R, int plane, int64_t x) { return P32(R, plane, x); }
-DEV int cov_FRAG(const RegionDev &R, int plane, int64_t x) {
-    int v = 0;
-#pragma unroll
-    for (int sd = 0; sd < 2; sd++)
-#pragma unroll
-        for (int s = UVC_BASE_A; s <= UVC_BASE_NN; s++) v += FRP(R, sd, plane, s, x);
-    return v;
-}
-DEV int cov_FAM(const RegionDev &R, int plane, int64_t x) {
-    int v = 0;
-#pragma unroll
-    for (int sd = 0; sd < 2; sd++)
-#pragma unroll
-        for (int s = UVC_BASE_A; s <= UVC_BASE_NN; s++) v += FAP(R, sd, plane, s, x);
-    return v;
-}
-DEV int cov_DUPLEX(const RegionDev &R, int plane, int64_t x) {
-    int v = 0;
-#pragma unroll
-    for (int s = UVC_BASE_A; s <= UVC_BASE_NN; s++) v += DUP(R, plane, s, x);
-    return v;
-}
-
 struct CovThr { int t[UVC_COV_MAX_THRESHOLDS]; };   // unused slots hold INT_MAX
 // A lane's statistics of one range.  The threshold counts are packed two to a register (threshold k in the low half, k + 4 in the high half):
 // a lane counts at most COV_MAX_STEPS positions and a wave 64 times that, far below 2^16.

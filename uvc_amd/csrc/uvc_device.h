@@ -232,6 +232,32 @@ DEV int cig_len(uint32_t c) { return (int)(c >> 4); }
 #define BAQ1(R, p) ((R).baq[(p) - (R).beg])
 #define BAQ2(R, p) ((R).baq[(R).npos + (p) - (R).beg])
 
+// the value of a depth measure of include/uvc_coverage.def (UVC_COV(name, group, plane) -> cov_<group>(R, plane, x)) at plane index x: the plane's cell, summed over both strands / the six BASE symbols where the group has them.
+// 32-bit like block_stats_at: each sum counts a read, fragment or family of the region at most once, and a region holds fewer than 2^31.
+DEV int cov_PREP32(const RegionDev &R, int plane, int64_t x) { return P32(R, plane, x); }
+DEV int cov_FRAG(const RegionDev &R, int plane, int64_t x) {
+    int v = 0;
+#pragma unroll
+    for (int sd = 0; sd < 2; sd++)
+#pragma unroll
+        for (int s = UVC_BASE_A; s <= UVC_BASE_NN; s++) v += FRP(R, sd, plane, s, x);
+    return v;
+}
+DEV int cov_FAM(const RegionDev &R, int plane, int64_t x) {
+    int v = 0;
+#pragma unroll
+    for (int sd = 0; sd < 2; sd++)
+#pragma unroll
+        for (int s = UVC_BASE_A; s <= UVC_BASE_NN; s++) v += FAP(R, sd, plane, s, x);
+    return v;
+}
+DEV int cov_DUPLEX(const RegionDev &R, int plane, int64_t x) {
+    int v = 0;
+#pragma unroll
+    for (int s = UVC_BASE_A; s <= UVC_BASE_NN; s++) v += DUP(R, plane, s, x);
+    return v;
+}
+
 // (see RegionDev::dirty)
 #define UVC_DIRTY_SHIFT 12
 DEV bool sym_always_filled(int s) { return s < UVC_BASE_NN || s == UVC_LINK_M; }   // A C G T N (a reference base) and LINK_M: written at nearly every position

@@ -79,7 +79,7 @@ struct uvcgpu_region {
     int32_t *d_score_fields = nullptr; int64_t score_capacity = 0; int64_t *d_score_count = nullptr;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     int32_t *d_score_kept = nullptr; int64_t score_kept_capacity = 0;   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields
-    char *d_cov = nullptr; size_t d_cov_bytes = 0; int64_t *h_cov = nullptr; size_t h_cov_bytes = 0;   // uvcgpu_region_coverage and uvcgpu_region_error_profile: range table + rows on the device, page-locked rows (grown on demand)
+    char *d_cov = nullptr; size_t d_cov_bytes = 0; int64_t *h_cov = nullptr; size_t h_cov_bytes = 0;   // uvcgpu_region_coverage, _error_profile, _family_stats and _callable: range table + rows on the device, page-locked rows (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1564,6 +1564,72 @@ int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges,
     return guarded("uvcgpu_region_family_stats", [&] { return uvcgpu_region_family_stats_impl(r, ranges, n_ranges, out); });
 }
 const char *uvcgpu_family_stat_name(int32_t id) { return uvc_famstats_name(id); }
+
+// ---- callable-region intervals of ranges (uvc_callable.hip) ----
+// Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit
+// and copies 16 bytes per run.  It shares the buffers of the coverage call: [table] [block counts] [mask bytes] [runs, one per position at worst].
+static int uvcgpu_region_callable_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcCallableRequest *req, UvcCallableRun *runs, int64_t run_capacity, int64_t *n_runs) {
+    if (!r) return fail(UVCGPU_EINVAL, "callable: null region");
+    if (!r->accumulated) return fail(UVCGPU_EINVAL, "callable before accumulate: there are no planes to classify");
+    if (r->state_released) return fail(UVCGPU_EINVAL, "callable after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
+    if (stream_is_open(r)) return fail(UVCGPU_EINVAL, "callable while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    if (!ranges || !req || !n_runs) return fail(UVCGPU_EINVAL, "callable: ranges, req and n_runs must not be NULL");
+    if (run_capacity < 0) return fail(UVCGPU_EINVAL, "callable: run_capacity " + std::to_string(run_capacity) + " is negative");
+    if (!runs && run_capacity > 0) return fail(UVCGPU_EINVAL, "callable: runs is NULL with run_capacity " + std::to_string(run_capacity));
+    for (int32_t k = 0; k < UVC_NCOV; k++)
+        if (req->min_depth[k] < 0) return fail(UVCGPU_EINVAL, std::string("callable: min_depth[") + uvc_coverage_name(k) + "] is negative (" + std::to_string(req->min_depth[k]) + ")");
+    if (req->max_aDP < 0) return fail(UVCGPU_EINVAL, "callable: max_aDP is negative (" + std::to_string(req->max_aDP) + ")");
+    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "callable: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
+    if (n_ranges > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "callable: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
+    std::vector<UvcRangeRow> tab((size_t)n_ranges + 1);
+    int64_t n_total = 0;
+    for (int64_t k = 0; k < n_ranges; k++) {
+        const UvcCoverageRange &q = ranges[k];
+        const std::string name = "callable: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
+        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
+        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
+        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
+        n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
+    }
+    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
+    const int64_t n_blocks = uvc_callable_blocks(n_total);
+    const size_t tab_bytes = (sizeof(UvcRangeRow) * tab.size() + 63) & ~(size_t)63, blk_bytes = (sizeof(int32_t) * (size_t)(n_blocks + 1) + 63) & ~(size_t)63;
+    const size_t mask_bytes = ((size_t)n_total + 63) & ~(size_t)63, run_bytes = sizeof(UvcCallableRun) * (size_t)n_total;   // every position can be its own run
+    { int rc1 = cov_buffers(r, tab_bytes + blk_bytes + mask_bytes + run_bytes, 64, "callable runs"); if (rc1) return rc1; }
+    size_t at = 0;   // the table through the handle's staging buffer, as coverage sends its own
+    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(UvcRangeRow) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
+    const UvcRangeRow *d_tab = (const UvcRangeRow *)r->d_cov;
+    int *d_blocks = (int *)(r->d_cov + tab_bytes);
+    unsigned char *d_mask = (unsigned char *)(r->d_cov + tab_bytes + blk_bytes);
+    UvcCallableRun *d_runs = (UvcCallableRun *)(r->d_cov + tab_bytes + blk_bytes + mask_bytes);
+    // with profiling on, two more entries of uvcgpu_region_kernel_times (accumulate starts the list anew): the host reads the count between them
+    auto prof_begin = [&](const char *name) { int pi = -1; if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = name; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); } return pi; };
+    auto prof_end = [&](int pi) { if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream); };
+    int pi = prof_begin("k_callable_count");
+    uvc_launch_callable_count(&r->R, d_tab, (int)n_ranges, n_total, req, d_mask, d_blocks, r->stream);
+    prof_end(pi);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(r->h_cov, d_blocks + n_blocks, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
+    const int64_t n = *(const int32_t *)r->h_cov;
+    *n_runs = n;
+    if (n > run_capacity) return fail(UVCGPU_ENOMEM, "callable: " + std::to_string(n) + " runs, room for " + std::to_string(run_capacity));
+    const size_t out_bytes = sizeof(UvcCallableRun) * (size_t)n;
+    { int rc1 = cov_buffers(r, 0, out_bytes, "callable runs"); if (rc1) return rc1; }
+    pi = prof_begin("k_callable_emit");
+    uvc_launch_callable_emit(&r->R, d_tab, (int)n_ranges, n_total, d_mask, d_blocks, d_runs, r->stream);
+    prof_end(pi);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(r->h_cov, d_runs, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
+    memcpy(runs, r->h_cov, out_bytes);
+    return 0;
+}
+int uvcgpu_region_callable(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcCallableRequest *req, UvcCallableRun *runs, int64_t run_capacity, int64_t *n_runs) {
+    return guarded("uvcgpu_region_callable", [&] { return uvcgpu_region_callable_impl(r, ranges, n_ranges, req, runs, run_capacity, n_runs); });
+}
+const char *uvcgpu_callable_bit_name(int32_t bit) { return uvc_callable_name(bit); }
 
 int uvcgpu_region_create(uvcgpu_region_t **out, const UvcParams *params, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_create", [&] { return uvcgpu_region_create_impl(out, params, tid, beg, end, refseq); }); }
 int uvcgpu_region_reset(uvcgpu_region_t *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_reset", [&] { return uvcgpu_region_reset_impl(r, tid, beg, end, refseq); }); }

@@ -1416,3 +1416,98 @@ extern "C" int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path)
     return 0;
 }
 extern "C" void uvcio_famstats_close(uvcio_famstats_t *f) { delete f; }
+
+// ---------------------------------------------------------------- the callable-region BED ----
+struct uvcio_callable {
+    std::vector<std::string> measures, bits; std::vector<int32_t> min_depth; int32_t max_aDP = 0;
+    struct Target { std::string chrom, name; int64_t beg, end; };
+    struct Run { int32_t target, beg, end, mask; };   // 16 bytes per run, kept to the end: the file is written in target order
+    std::vector<Target> targets; std::vector<Run> runs;
+    std::mutex mu;
+};
+extern "C" int uvcio_callable_open(uvcio_callable_t **out, const char *const *measure_names, int32_t n_measures, const int32_t *min_depth, int32_t max_aDP, const char *const *bit_names, int32_t n_bits) {
+    if (!out || !measure_names || !min_depth || !bit_names || n_measures < 1 || n_measures > 29 || n_bits != n_measures + 2 || max_aDP < 0) return fail(UVCGPU_EINVAL, "callable report: bad argument");
+    uvcio_callable *c = new uvcio_callable;
+    for (int32_t m = 0; m < n_measures; m++) { c->measures.push_back(measure_names[m] ? measure_names[m] : ""); c->min_depth.push_back(min_depth[m]); }
+    for (int32_t b = 0; b < n_bits; b++) c->bits.push_back(bit_names[b] ? bit_names[b] : "");
+    c->max_aDP = max_aDP;
+    *out = c;
+    return 0;
+}
+extern "C" int64_t uvcio_callable_add_target(uvcio_callable_t *c, const char *chrom, int64_t beg, int64_t end, const char *name) {
+    if (!c || !chrom || beg < 0 || end > INT32_MAX) return fail(UVCGPU_EINVAL, "callable report: bad target");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->targets.push_back(uvcio_callable::Target{ chrom, (name && *name) ? name : ".", beg, std::max(beg, end) });
+    return (int64_t)c->targets.size() - 1;
+}
+extern "C" int uvcio_callable_add_runs(uvcio_callable_t *c, const int64_t *target_of_range, int64_t n_ranges, const UvcCallableRun *runs, int64_t n_runs) {
+    if (!c || n_runs < 0 || n_ranges < 0 || (n_runs > 0 && (!runs || !target_of_range))) return fail(UVCGPU_EINVAL, "callable report: bad runs");
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int64_t q = 0; q < n_runs; q++) {   // all of the call's runs or none
+        const UvcCallableRun &r = runs[q];
+        if (r.range < 0 || r.range >= n_ranges) return fail(UVCGPU_EINVAL, "callable report: run " + std::to_string(q) + " names range " + std::to_string(r.range) + " of " + std::to_string(n_ranges));
+        const int64_t t = target_of_range[r.range];
+        if (t < 0 || t >= (int64_t)c->targets.size()) return fail(UVCGPU_EINVAL, "callable report: run of target " + std::to_string(t) + ", which does not exist");
+        if (r.pos_end <= r.pos_beg || r.pos_beg < c->targets[(size_t)t].beg || r.pos_end > c->targets[(size_t)t].end)
+            return fail(UVCGPU_EINVAL, "callable report: run [" + std::to_string(r.pos_beg) + ", " + std::to_string(r.pos_end) + ") is empty or outside target " + std::to_string(t));
+    }
+    for (int64_t q = 0; q < n_runs; q++) c->runs.push_back(uvcio_callable::Run{ (int32_t)target_of_range[runs[q].range], runs[q].pos_beg, runs[q].pos_end, runs[q].mask });
+    return 0;
+}
+extern "C" int64_t uvcio_callable_n_runs(const uvcio_callable_t *c) { return c ? (int64_t)c->runs.size() : 0; }
+extern "C" int uvcio_callable_write(const uvcio_callable_t *c, const char *path) {
+    if (!c || !path || !*path) return fail(UVCGPU_EINVAL, "callable report: bad argument");
+    const size_t nm = c->measures.size(), nb = c->bits.size();
+    std::string text = "##callable_regions=1\n#min_depth\t";
+    int32_t fill = 1 << (nm + 1);   // the mask of depth 0: NO_COVERAGE and every tested LOW bit
+    for (size_t m = 0; m < nm; m++) { text += (m ? "," : "") + c->measures[m] + "=" + std::to_string(c->min_depth[m]); if (c->min_depth[m] > 0) fill |= 1 << m; }
+    text += "\n#max_aDP\t" + std::to_string(c->max_aDP) + "\n#chrom\tbeg\tend\tclass\ttarget\n";
+    std::vector<uvcio_callable::Run> runs = c->runs;
+    std::sort(runs.begin(), runs.end(), [](const uvcio_callable::Run &a, const uvcio_callable::Run &b) { return a.target != b.target ? a.target < b.target : a.beg < b.beg; });
+    int64_t total = 0, callable_ = 0; std::vector<int64_t> per_bit(nb, 0);
+    size_t at = 0;
+    for (size_t t = 0; t < c->targets.size(); t++) {
+        const uvcio_callable::Target &T = c->targets[t];
+        int64_t open_beg = T.beg, open_end = T.beg; int32_t open_mask = 0;   // the line being joined: [open_beg, open_end), empty at first
+        auto flush = [&]() {
+            if (open_end <= open_beg) return;
+            std::string cls;
+            for (size_t b = 0; b < nb; b++) if (open_mask >> b & 1) { cls += (cls.empty() ? "" : ",") + c->bits[b]; per_bit[b] += open_end - open_beg; }
+            if (open_mask == 0) { cls = "CALLABLE"; callable_ += open_end - open_beg; }
+            total += open_end - open_beg;
+            text += T.chrom + "\t" + std::to_string(open_beg) + "\t" + std::to_string(open_end) + "\t" + cls + "\t" + T.name + "\n";
+        };
+        auto put = [&](int64_t a, int64_t b, int32_t mask) {
+            if (b <= a) return;
+            if (open_end > open_beg && mask == open_mask && a == open_end) { open_end = b; return; }
+            flush();
+            open_beg = a; open_end = b; open_mask = mask;
+        };
+        int64_t pos = T.beg;
+        for (; at < runs.size() && runs[at].target == (int32_t)t; at++) {
+            if (runs[at].beg < pos) return fail(UVCGPU_EINVAL, "callable report: the pieces of target " + std::to_string(t) + " overlap at " + std::to_string(runs[at].beg));
+            put(pos, runs[at].beg, fill);
+            put(runs[at].beg, runs[at].end, runs[at].mask);
+            pos = runs[at].end;
+        }
+        put(pos, T.end, fill);
+        flush();
+    }
+    text += "#summary\tpositions\t" + std::to_string(total) + "\n#summary\tCALLABLE\t" + std::to_string(callable_) + "\n";
+    for (size_t b = 0; b < nb; b++) text += "#summary\t" + c->bits[b] + "\t" + std::to_string(per_bit[b]) + "\n";
+    const std::string p = path;
+    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
+        uvcio_bgzf_writer_t *zw = nullptr;
+        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
+        const int rc2 = uvcio_bgzf_write_close(zw);
+        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+        return 0;
+    }
+    FILE *fo = fopen(path, "wb");
+    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
+    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+    return 0;
+}
+extern "C" void uvcio_callable_close(uvcio_callable_t *c) { delete c; }

@@ -83,6 +83,12 @@ int64_t uvc_errprofile_scratch_cells(void);
 // n_ranges rows; d_rows: n_ranges rows of UVC_FAMSTAT_ROW words ----
 void uvc_launch_famstats(const RegionDev *R, const int32_t *pos, const int32_t *endpos, const int32_t *fs_of, UvcUnitSpan *d_span, const UvcFamilyRange *d_ranges, int n_ranges, long long *d_rows, hipStream_t s);
 const char *uvc_famstats_name(int id);
+// ---- uvc_callable.hip: d_tab = n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one the
+// number of runs once the count has run; d_runs: room for that many runs.  The emit follows a count with the same arguments ----
+void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s);
+void uvc_launch_callable_emit(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const unsigned char *d_mask, const int *d_blocks, UvcCallableRun *d_runs, hipStream_t s);
+int64_t uvc_callable_blocks(int64_t n_total);
+const char *uvc_callable_name(int bit);
 // ---- uvc_gap.hip: the rocPRIM sorts and the small gathers ----
 size_t uvc_gap_sort_tmp_bytes(size_t n);
 int uvc_gap_sort(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout, const unsigned long long *vin, unsigned long long *vout, size_t n, int end_bit, hipStream_t s);

@@ -218,6 +218,58 @@ class FamilyStats:
         self.close()
 
 
+class Callable:
+    """uvcio_callable_*: the store behind uvc1-mi355x --callable-out.  Targets are added in report order with their positions inside the
+    contig; add_runs takes the runs of one Region.callable and the target of each of its ranges (any thread, any order); write() sorts,
+    fills what no piece reported with the mask of depth 0, joins equal neighbours inside a target and makes the BED text."""
+
+    def __init__(self, measures, min_depth, max_aDP, bits):
+        d = dll()
+        d.uvcio_callable_open.restype, d.uvcio_callable_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
+        d.uvcio_callable_add_target.restype, d.uvcio_callable_add_target.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
+        d.uvcio_callable_add_runs.restype, d.uvcio_callable_add_runs.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        d.uvcio_callable_n_runs.restype, d.uvcio_callable_n_runs.argtypes = C.c_int64, [C.c_void_p]
+        d.uvcio_callable_write.restype, d.uvcio_callable_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
+        d.uvcio_callable_close.restype, d.uvcio_callable_close.argtypes = None, [C.c_void_p]
+        self.h = C.c_void_p()
+        names = (C.c_char_p * len(measures))(*[m.encode() for m in measures])
+        bnames = (C.c_char_p * len(bits))(*[b.encode() for b in bits])
+        md = (C.c_int32 * len(measures))(*[int(v) for v in min_depth])
+        _check(d.uvcio_callable_open(C.byref(self.h), names, len(measures), md, int(max_aDP), bnames, len(bits)))
+
+    def add_target(self, chrom, beg, end, name=None):
+        t = dll().uvcio_callable_add_target(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
+        if t < 0:
+            _check(int(t))
+        return int(t)
+
+    def add_runs(self, target_of_range, runs):
+        """runs: the structured array of Region.callable (range, pos_beg, pos_end, mask); target_of_range[k]: the target of the call's range k"""
+        import numpy as np
+        runs = np.ascontiguousarray(runs)
+        if runs.dtype.itemsize != 16:
+            raise ValueError("runs are the 16-byte rows of Region.callable")
+        tor = np.ascontiguousarray(target_of_range, dtype=np.int64)
+        _check(dll().uvcio_callable_add_runs(self.h, tor.ctypes.data, len(tor), runs.ctypes.data, len(runs)))
+
+    def n_runs(self):
+        return int(dll().uvcio_callable_n_runs(self.h))
+
+    def write(self, path):
+        _check(dll().uvcio_callable_write(self.h, str(path).encode()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            dll().uvcio_callable_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def plan_regions(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per_thread_mb=1536):
     """SamIter::iternext without a BED file (grouping.cpp:225-312) over alignment columns in file order: the blocks the reference hands
     to process_batch, as dicts (tid, beg, end, flag, batch, n_reads)."""

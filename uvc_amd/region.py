@@ -24,8 +24,10 @@ class UvcError(RuntimeError):
 
 
 COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
+CALLABLE_BITS = _ffi.CALLABLE_BITS           # the bits of a mask of Region.callable, in bit order (include/uvc_callable.def)
 FAMILY_STATS = _ffi.FAMILY_STATS             # the sections of a row of Region.family_stats, in row order (include/uvc_famstats.def)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
+CALLABLE_RUN = np.dtype([("range", np.int32), ("pos_beg", np.int32), ("pos_end", np.int32), ("mask", np.int32)])   # UvcCallableRun
 
 _gpu_lib = None
 
@@ -511,6 +513,26 @@ class Region:
         out = np.zeros((len(rows), _ffi.ENUMS["UVC_FAMSTAT_ROW"]), dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), out.ctypes.data))
         return out
+
+    def callable(self, ranges, min_depth=None, max_aDP=0):
+        """uvcgpu_region_callable: the runs of equal callability masks of `ranges` -- (pos_beg, pos_end) pairs as for coverage().  min_depth:
+        measure name of COVERAGE_MEASURES -> smallest depth (0 or absent: not tested); max_aDP: largest raw depth (0: not tested).  A
+        structured array (range, pos_beg, pos_end, mask; int32), sorted by (range, pos_beg), the runs of a range tiling it; bit k of mask is
+        CALLABLE_BITS[k], mask 0 = callable.  Classified and compacted on the device; asks for the size first, then for the runs."""
+        fn = self._ranges_fn("region_callable", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        rows = [(int(q[0]), int(q[1])) for q in ranges]
+        arr = (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows])
+        req = _ffi.UvcCallableRequest()
+        for name, v in (min_depth or {}).items():
+            req.min_depth[COVERAGE_MEASURES.index(name)] = int(v)
+        req.max_aDP = int(max_aDP)
+        n = C.c_int64(0)
+        rc = fn(self.h, arr, len(rows), C.byref(req), None, 0, C.byref(n))
+        if rc != _ffi.ENUMS["UVCGPU_ENOMEM"]:
+            self._check(rc)
+        out = np.zeros(max(n.value, 1), dtype=CALLABLE_RUN)
+        self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value].copy()
 
     def score_stream_bytes_per_record(self):
         return self._ranges_fn("score_stream_bytes_per_record", C.c_int64, [])()
