@@ -7,7 +7,7 @@ import re
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "uvc_amd", "csrc")
 SOURCES = sorted(glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(CSRC, "*.hip")))
-BOUNDARY_STRUCTS = ("RawReads", "UvcProf", "ZeroPlane", "UvcScoreRangeDev")
+BOUNDARY_STRUCTS = ("RawReads", "UvcProf", "ZeroPlane", "UvcScoreRangeDev", "UvcRangeRow", "UvcUnitSpan", "UvcRangeCursor")
 
 
 def _lines():

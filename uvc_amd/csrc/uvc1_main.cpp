@@ -29,6 +29,7 @@
 #include <cstring>
 #include <ctime>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -194,6 +195,35 @@ bool number(const std::string &s, double *v) {   // a whole decimal number, or t
     char *e = nullptr; *v = strtod(s.c_str(), &e); return *e == 0 && std::isfinite(*v);
 }
 
+// What the report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out) share on the command line.  Each option
+// gives its own words for why; the sentences are these.
+int64_t window_length(const std::string &opt, const std::string &v) {   // --coverage-window, --family-stats-window
+    double x;
+    if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die(opt + " takes a window length in bp, not '" + v + "'");
+    return (int64_t)x;
+}
+// the runs no report can come from: the header-only run, one shard of many, a repeated tile list
+void refuse_report_runs(const Opts &o, const std::string &opt, const char *why_no_shard, const char *why_no_repeat) {
+    if (o.bam == ONLY_PRINT_VCF_HEADER) die(opt + " cannot go with " + ONLY_PRINT_VCF_HEADER + ": no tile is called");
+    if (o.n_shards > 1) die(opt + " cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": " + why_no_shard + ", and --concat joins VCFs only");
+    if (o.repeat != 1) die(opt + " cannot go with --repeat " + std::to_string(o.repeat) + ": " + why_no_repeat);
+}
+// the targets of a report with target lines: the lines of the BED file, or windows of `window` bp (wopt) without one
+void refuse_report_windows(const Opts &o, const std::string &opt, const std::string &wopt, int64_t window) {
+    const bool has_bed = (!o.bed.empty() || !o.bed_in.empty());
+    if (has_bed && window > 0) die(wopt + " cannot go with -R / --bed-in-fname: with a BED file the targets of " + opt + " are its lines");
+    if (!has_bed && window <= 0) die(opt + " needs " + wopt + " N without -R / --bed-in-fname: there are no BED lines to report on");
+}
+// the windows of N bp, aligned to multiples of N, that [beg, end) reaches into, each clipped to it: fn(k, begin, end) of window k
+template <class F> void for_windows(int64_t beg, int64_t end, int64_t N, F fn) {
+    for (int64_t k = beg / N; k * N < end; k++) fn(k, std::max(k * N, beg), std::min((k + 1) * N, end));
+}
+void probe_create(const std::string &opt, const std::string &path) {   // an empty file now: the run's last step writes the report over it
+    FILE *probe = fopen(path.c_str(), "wb");
+    if (!probe) die(opt + ": cannot create " + path);
+    fclose(probe);
+}
+
 void help() {
     printf("usage: uvc1-mi355x inputBAM -f ref.fa -o out.vcf.gz [options]\n"
            "       uvc1-mi355x /only-print-vcf-header/ [options]     the VCF header of the resolved parameters on stdout\n"
@@ -277,12 +307,12 @@ Opts parse(int argc, char **argv) {
                 at = c + 1;
             }
         }
-        else if (n0 == "--coverage-window") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--coverage-window takes a window length in bp, not '" + v + "'"); o.coverage_window = (int64_t)x; }
+        else if (n0 == "--coverage-window") o.coverage_window = window_length(n0, val());
         else if (n0 == "--error-profile-out") { o.errprof_out = val(); if (o.errprof_out.empty()) die("--error-profile-out needs a path"); }
         else if (n0 == "--error-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--error-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.errprof_req.min_depth = (int32_t)x; o.errprof_gate_given = true; }
         else if (n0 == "--error-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--error-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.errprof_req.max_alt_permille = (int32_t)x; o.errprof_gate_given = true; }
         else if (n0 == "--family-stats-out") { o.famstats_out = val(); if (o.famstats_out.empty()) die("--family-stats-out needs a path"); }
-        else if (n0 == "--family-stats-window") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--family-stats-window takes a window length in bp, not '" + v + "'"); o.famstats_window = (int64_t)x; }
+        else if (n0 == "--family-stats-window") o.famstats_window = window_length(n0, val());
         else if (n0 == "--callable-out") { o.callable_out = val(); if (o.callable_out.empty()) die("--callable-out needs a path"); }
         else if (n0 == "--callable-min-depth") {   // NAME=N,...: the names of uvcgpu_coverage_measure_name, each at most once, whole numbers >= 0
             const std::string v = val(); o.call_req_given = true;
@@ -344,41 +374,26 @@ Opts parse(int argc, char **argv) {
         if (!o.tumor_vcf.empty()) die("--force-sites cannot go with --tumor-vcf: the normal sample's gate is the tumor's rescue set");
         if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--force-sites cannot go with ") + ONLY_PRINT_VCF_HEADER + ": there are no records to force");
     }
-    if (o.coverage_out.empty()) {   // before any file or device
+    // the report options, before any file or device
+    if (o.coverage_out.empty()) {
         if (o.coverage_thr_given) die("--coverage-thresholds needs --coverage-out: it only shapes that report");
         if (o.coverage_window > 0) die("--coverage-window needs --coverage-out: it only shapes that report");
     } else {
-        const bool has_bed = (!o.bed.empty() || !o.bed_in.empty());
-        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--coverage-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
-        if (o.n_shards > 1) die("--coverage-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": a target can straddle shards, and --concat joins VCFs only");
-        if (o.repeat != 1) die("--coverage-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
-        if (has_bed && o.coverage_window > 0) die("--coverage-window cannot go with -R / --bed-in-fname: with a BED file the targets of --coverage-out are its lines");
-        if (!has_bed && o.coverage_window <= 0) die("--coverage-out needs --coverage-window N without -R / --bed-in-fname: there are no BED lines to report on");
+        refuse_report_runs(o, "--coverage-out", "a target can straddle shards", "every tile would be counted that many times");
+        refuse_report_windows(o, "--coverage-out", "--coverage-window", o.coverage_window);
     }
-    if (o.errprof_out.empty()) {   // before any file or device
+    if (o.errprof_out.empty()) {
         if (o.errprof_gate_given) die("--error-profile-min-depth and --error-profile-max-alt-permille need --error-profile-out: they only gate that report");
-    } else {
-        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--error-profile-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
-        if (o.n_shards > 1) die("--error-profile-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": every shard would write a part of the table, and --concat joins VCFs only");
-        if (o.repeat != 1) die("--error-profile-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
-    }
-    if (o.famstats_out.empty()) {   // before any file or device
+    } else refuse_report_runs(o, "--error-profile-out", "every shard would write a part of the table", "every tile would be counted that many times");
+    if (o.famstats_out.empty()) {
         if (o.famstats_window > 0) die("--family-stats-window needs --family-stats-out: it only shapes that report");
     } else {
-        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--family-stats-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
-        if (o.n_shards > 1) die("--family-stats-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": a target can straddle shards, and --concat joins VCFs only");
-        if (o.repeat != 1) die("--family-stats-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would be counted that many times");
-        const bool has_bed = (!o.bed.empty() || !o.bed_in.empty());
-        if (has_bed && o.famstats_window > 0) die("--family-stats-window cannot go with -R / --bed-in-fname: with a BED file the targets of --family-stats-out are its lines");
-        if (!has_bed && o.famstats_window <= 0) die("--family-stats-out needs --family-stats-window N without -R / --bed-in-fname: there are no BED lines to report on");
+        refuse_report_runs(o, "--family-stats-out", "a target can straddle shards", "every tile would be counted that many times");
+        refuse_report_windows(o, "--family-stats-out", "--family-stats-window", o.famstats_window);
     }
-    if (o.callable_out.empty()) {   // before any file or device
+    if (o.callable_out.empty()) {
         if (o.call_req_given) die("--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file");
-    } else {
-        if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--callable-out cannot go with ") + ONLY_PRINT_VCF_HEADER + ": no tile is called");
-        if (o.n_shards > 1) die("--callable-out cannot go with --shard " + std::to_string(o.shard) + "/" + std::to_string(o.n_shards) + ": a target can straddle shards, and --concat joins VCFs only");
-        if (o.repeat != 1) die("--callable-out cannot go with --repeat " + std::to_string(o.repeat) + ": every tile would report its runs that many times");
-    }
+    } else refuse_report_runs(o, "--callable-out", "a target can straddle shards", "every tile would report its runs that many times");
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -433,15 +448,11 @@ void coverage_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int6
     w.cov_ranges.clear(); w.cov_targets.clear();
     const int64_t N = o.coverage_window;
     for (size_t q = 0; q < own.size(); q++) {
-        int64_t b = own[q].first; const int64_t e = own[q].second;
+        const int64_t b = own[q].first, e = own[q].second;
         if (e <= b) continue;
         if (target_of[q] >= 0) { w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.cov_targets.push_back(target_of[q]); continue; }
         if (!span || span->first < 0) die("--coverage-out: a tile outside the planned windows (internal error)");
-        while (b < e) {
-            const int64_t stop = std::min(e, (b / N + 1) * N);
-            w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)stop }); w.cov_targets.push_back(span->first + (b / N - span->origin / N));
-            b = stop;
-        }
+        for_windows(b, e, N, [&](int64_t k, int64_t wb, int64_t we) { w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)wb, (int32_t)we }); w.cov_targets.push_back(span->first + (k - span->origin / N)); });
     }
     if (w.cov_ranges.empty()) return;
     w.cov_rows.resize(w.cov_ranges.size() * (size_t)UVC_NCOV * UVC_COV_ROW);
@@ -545,16 +556,15 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (k == 0) return false;
     // region bounds and reference, main.cpp:523-552
     const int64_t bam_beg = go.extended_inclu_beg_pos, bam_end = go.extended_exclu_end_pos;
-    const int64_t rpos_beg = std::max(t.beg, bam_beg), rpos_end = std::min(t.end, bam_end);
     const int64_t ext_beg = std::max<int64_t>(0, std::min(t.beg, bam_beg) - MAX_STR_N_BASES), ext_end = std::min(tlen, std::max(t.end, bam_end) + MAX_STR_N_BASES);
-    const int64_t first = rpos_beg;
-    const int64_t last_excl = t.has_next ? std::min(t.end, bam_end + 1) : std::min(rpos_end + 1, ext_end);   // zerobased_pos t.end belongs to the next tile
+    // what a tile (or a line of a batch) scores of the region: [first, excl); zerobased_pos `end` belongs to the next tile where there is one
+    auto scored = [&](const Tile &l) { return std::make_pair(std::max(l.beg, bam_beg), l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end)); };
+    const int64_t first = scored(t).first, last_excl = scored(t).second;
     // the ranges of a batch: per line what the lines above compute for a tile, with the batch's reads and extent
     std::vector<UvcScoreRange> ranges;
     for (size_t q = 0; q < n_merged; q++) {
         const Tile &l = (&t0_)[q];
-        const int64_t l_first = std::max(l.beg, bam_beg);
-        const int64_t l_excl = l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end);
+        const int64_t l_first = scored(l).first, l_excl = scored(l).second;
         if (l_excl > l_first) ranges.push_back(UvcScoreRange{ (int32_t)l_first, (int32_t)l_excl, (l.continues && l_first == l.beg && l.beg > ext_beg) ? 1 : 0, (int32_t)l.run_beg });
     }
     if (n_merged > 0 ? ranges.empty() : last_excl <= first) return false;
@@ -582,12 +592,9 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
                    // point t.end itself, which lies outside every target the tile was cut from (and which two regions of the reference's cuts share)
         std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
         auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !o.callable ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
-        if (n_merged == 0) { own.emplace_back(first, std::min(last_excl, t.end)); target_of.push_back(t.target); call_target_of.push_back(call_target(t)); }
-        else for (size_t q = 0; q < n_merged; q++) {
+        for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) {   // (n_merged = 0: t0_ alone)
             const Tile &l = (&t0_)[q];
-            const int64_t l_first = std::max(l.beg, bam_beg);
-            const int64_t l_excl = l.has_next ? std::min(l.end, bam_end + 1) : std::min(std::min(l.end, bam_end) + 1, ext_end);
-            own.emplace_back(l_first, std::min(l_excl, l.end)); target_of.push_back(l.target); call_target_of.push_back(call_target(l));
+            own.emplace_back(scored(l).first, std::min(scored(l).second, l.end)); target_of.push_back(l.target); call_target_of.push_back(call_target(l));
         }
         if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
         if (o.errprof) errprofile_of_tile(w, o, own);
@@ -733,29 +740,21 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     int64_t cov_target = -1, fam_target = -1, call_target = -1;   // the report rows of the BED line being added
     if (o.callable) o.call_contig_target.assign((size_t)nref, -1);
     auto add = [&](int32_t tid, int64_t beg, int64_t end) {
-        if (o.cov && cov_spans && o.coverage_window > 0 && end > beg) {   // the windows of this span: aligned to multiples of N, clipped to it
-            const int64_t N = o.coverage_window;
-            CovSpan &sp = (*cov_spans)[(size_t)tid];
-            if (sp.first >= 0) die("--coverage-window: a contig is called twice (internal error)");
+        // window mode of a report: the windows of this span become its targets, in order; the span keeps the row of the first
+        auto window_targets = [&](const char *wopt, int64_t N, CovSpan &sp, auto add_target) {
+            if (sp.first >= 0) die(std::string(wopt) + ": a contig is called twice (internal error)");
             sp.origin = beg;
-            for (int64_t k = beg / N; k * N < end; k++) {
-                const int64_t wb = std::max(k * N, beg), we = std::min((k + 1) * N, end);
-                const int64_t row = uvcio_coverage_add_target(o.cov, names[(size_t)tid].c_str(), wb, we, nullptr, we - wb);
+            for_windows(beg, end, N, [&](int64_t, int64_t wb, int64_t we) {
+                const int64_t row = add_target(wb, we);
                 if (row < 0) die(uvcio_last_error());
                 if (sp.first < 0) sp.first = row;
-            }
-        }
-        if (o.fam && fam_spans && o.famstats_window > 0 && end > beg) {   // the same windows for the family report
-            const int64_t N = o.famstats_window;
-            CovSpan &sp = (*fam_spans)[(size_t)tid];
-            if (sp.first >= 0) die("--family-stats-window: a contig is called twice (internal error)");
-            sp.origin = beg;
-            for (int64_t k = beg / N; k * N < end; k++) {
-                const int64_t row = uvcio_famstats_add_target(o.fam, names[(size_t)tid].c_str(), std::max(k * N, beg), std::min((k + 1) * N, end), nullptr);
-                if (row < 0) die(uvcio_last_error());
-                if (sp.first < 0) sp.first = row;
-            }
-        }
+            });
+        };
+        const char *chrom = names[(size_t)tid].c_str();
+        if (o.cov && cov_spans && o.coverage_window > 0 && end > beg)
+            window_targets("--coverage-window", o.coverage_window, (*cov_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_coverage_add_target(o.cov, chrom, wb, we, nullptr, we - wb); });
+        if (o.fam && fam_spans && o.famstats_window > 0 && end > beg)
+            window_targets("--family-stats-window", o.famstats_window, (*fam_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_famstats_add_target(o.fam, chrom, wb, we, nullptr); });
         if (o.callable && bed_path.empty()) {   // --callable-out without a BED file: the called span of the contig is one target
             if (o.call_contig_target[(size_t)tid] >= 0) die("--callable-out: a contig is called twice (internal error)");
             call_target = o.call_contig_target[(size_t)tid] = uvcio_callable_add_target(o.callable, names[(size_t)tid].c_str(), beg, end, nullptr);
@@ -973,10 +972,13 @@ PairArgs split_pair(int argc, char **argv) {
         const std::string name = t.substr(0, t.compare(0, 2, "--") == 0 ? t.find('=') : std::string::npos);
         if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
-        if (name == "--coverage-out" || name == "--coverage-thresholds" || name == "--coverage-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no coverage report");
-        if (name == "--error-profile-out" || name == "--error-profile-min-depth" || name == "--error-profile-max-alt-permille") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no error profile");
-        if (name == "--callable-out" || name == "--callable-min-depth" || name == "--callable-max-aDP") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no callable regions");
-        if (name == "--family-stats-out" || name == "--family-stats-window") die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no family report");
+        auto no_report = [&](std::initializer_list<const char *> opts, const char *what) {   // the options of a report: pair mode writes none
+            for (const char *opt : opts) if (name == opt) die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no " + what);
+        };
+        no_report({ "--coverage-out", "--coverage-thresholds", "--coverage-window" }, "coverage report");
+        no_report({ "--error-profile-out", "--error-profile-min-depth", "--error-profile-max-alt-permille" }, "error profile");
+        no_report({ "--callable-out", "--callable-min-depth", "--callable-max-aDP" }, "callable regions");
+        no_report({ "--family-stats-out", "--family-stats-window" }, "family report");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
             die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
@@ -1307,26 +1309,11 @@ int main(int argc, char **argv) {
     // output: header, then the lines of every tile in tile order
     uvcio_bgzf_writer_t *zw = nullptr;
     if (uvcio_bgzf_write_open(&zw, o.out.c_str(), 6)) die(uvcio_last_error());
-    if (o.cov) {   // a path that cannot be written fails here, not behind the last tile
-        FILE *probe = fopen(o.coverage_out.c_str(), "wb");
-        if (!probe) die("--coverage-out: cannot create " + o.coverage_out);
-        fclose(probe);
-    }
-    if (o.fam) {
-        FILE *probe = fopen(o.famstats_out.c_str(), "wb");
-        if (!probe) die("--family-stats-out: cannot create " + o.famstats_out);
-        fclose(probe);
-    }
-    if (o.callable) {
-        FILE *probe = fopen(o.callable_out.c_str(), "wb");
-        if (!probe) die("--callable-out: cannot create " + o.callable_out);
-        fclose(probe);
-    }
-    if (o.errprof) {
-        FILE *probe = fopen(o.errprof_out.c_str(), "wb");
-        if (!probe) die("--error-profile-out: cannot create " + o.errprof_out);
-        fclose(probe);
-    }
+    // a report path that cannot be written fails here, not behind the last tile
+    if (o.cov) probe_create("--coverage-out", o.coverage_out);
+    if (o.fam) probe_create("--family-stats-out", o.famstats_out);
+    if (o.callable) probe_create("--callable-out", o.callable_out);
+    if (o.errprof) probe_create("--error-profile-out", o.errprof_out);
     if (!o.no_header) {
         const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
@@ -1371,23 +1358,16 @@ int main(int argc, char **argv) {
     }
     for (auto &t : th) t.join();
     if (uvcio_bgzf_write_close(zw)) die(uvcio_last_error());
-    if (o.cov) {   // every tile has reported: the rows in target order, whichever worker finished first
-        if (uvcio_coverage_write(o.cov, o.coverage_out.c_str())) die("--coverage-out: " + std::string(uvcio_last_error()));
-        uvcio_coverage_close(o.cov);
-    }
-    if (o.fam) {   // every tile has reported: the rows in target order, sums do not depend on the order
-        if (uvcio_famstats_write(o.fam, o.famstats_out.c_str())) die("--family-stats-out: " + std::string(uvcio_last_error()));
-        uvcio_famstats_close(o.fam);
-    }
-    if (o.callable) {   // every tile has reported: sorted, filled and joined per target, in target order
+    // every tile has reported.  The stores write in target order whichever worker finished first (callable: sorted, filled and joined per
+    // target); sums do not depend on the order
+    auto finish = [](const char *opt, int rc) { if (rc) die(std::string(opt) + ": " + uvcio_last_error()); };
+    if (o.cov) { finish("--coverage-out", uvcio_coverage_write(o.cov, o.coverage_out.c_str())); uvcio_coverage_close(o.cov); }
+    if (o.fam) { finish("--family-stats-out", uvcio_famstats_write(o.fam, o.famstats_out.c_str())); uvcio_famstats_close(o.fam); }
+    if (o.callable) {
         if (o.timing) fprintf(stderr, "uvc1-mi355x: --callable-out holds %lld runs\n", (long long)uvcio_callable_n_runs(o.callable));
-        if (uvcio_callable_write(o.callable, o.callable_out.c_str())) die("--callable-out: " + std::string(uvcio_last_error()));
-        uvcio_callable_close(o.callable);
+        finish("--callable-out", uvcio_callable_write(o.callable, o.callable_out.c_str())); uvcio_callable_close(o.callable);
     }
-    if (o.errprof) {   // every tile has reported: sums do not depend on the order
-        if (uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())) die("--error-profile-out: " + std::string(uvcio_last_error()));
-        uvcio_errprofile_close(o.errprof);
-    }
+    if (o.errprof) { finish("--error-profile-out", uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())); uvcio_errprofile_close(o.errprof); }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

@@ -59,20 +59,11 @@ DEV int call_mask(const RegionDev &R, const UvcCallableRequest &q, int64_t x) {
     return mask;
 }
 
-// this lane's range: compact positions [first, next), plane index of the first; kept while the lane's positions stay inside
-struct CallRange { int rid = -1, first = 0, next = 0, x0 = 0; };
-DEV void call_find(CallRange &g, const UvcRangeRow *tab, int n_ranges, long long i) {
-    if (i >= g.first && i < g.next) return;
-    int lo = 0, hi = n_ranges;   // the last range whose first compact position is <= i (ranges are not empty: `first` strictly ascends)
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].first <= i) lo = mid; else hi = mid; }
-    g.rid = lo; g.first = tab[lo].first; g.x0 = tab[lo].x0; g.next = tab[lo + 1].first;
-}
-
 __global__ void __launch_bounds__(256) k_callable_count(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, UvcCallableRequest q, unsigned char *mask_out, int *block_count) {
     __shared__ int wave_heads[4];
     const int lane = (int)(threadIdx.x & 63);
     const long long base = (long long)blockIdx.x * CALL_TILE;
-    CallRange g;
+    UvcRangeCursor g;
     int heads = 0;   // wave-uniform
 #pragma unroll
     for (int c = 0; c < CALL_STEPS; c++) {
@@ -80,7 +71,7 @@ __global__ void __launch_bounds__(256) k_callable_count(RegionDev R, const UvcRa
         const bool act = (i < n_total);
         int m = 0; bool first = false; int64_t x = 0;
         if (act) {
-            call_find(g, tab, n_ranges, i);
+            uvc_range_find(g, tab, n_ranges, i);
             x = (int64_t)g.x0 + (i - g.first);   // (inside [0, npos): the host has checked every range against the region)
             first = (i == g.first);
             m = call_mask(R, q, x);
@@ -122,7 +113,7 @@ __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, i
     __shared__ int wave_heads[4];
     const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
     const long long base = (long long)blockIdx.x * CALL_TILE;
-    CallRange g;
+    UvcRangeCursor g;
     int run_base = block_off[blockIdx.x];   // the heads in front of this step's first position
 #pragma unroll
     for (int c = 0; c < CALL_STEPS; c++) {
@@ -130,7 +121,7 @@ __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, i
         const bool act = (i < n_total);
         int m = 0, pos = 0; bool head = false, tail = false;
         if (act) {
-            call_find(g, tab, n_ranges, i);
+            uvc_range_find(g, tab, n_ranges, i);
             pos = region_beg + g.x0 + (int)(i - g.first);
             m = mask[i];
             head = (i == g.first || mask[i - 1] != m);

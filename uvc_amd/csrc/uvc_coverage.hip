@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(256) k_coverage(RegionDev R, const UvcRangeRow
     const int shard = (int)(wave % shards);   // the copy of every row this wave merges into (row index = range * shards + shard)
     CovAcc acc; acc_clear(acc);
     int cur = -1;                                      // wave-uniform: the range the accumulators belong to, -1 = none
-    int rid = -1, r_first = 0, r_next = 0, r_x0 = 0;   // this lane's range: compact positions [r_first, r_next), plane index of the first
+    UvcRangeCursor g;                                  // this lane's range
     for (int c = 0; ; c++) {
         const bool last = (c >= steps || base + (long long)c * 64 >= n_total);   // wave-uniform
         const long long i = base + (long long)c * 64 + lane;
@@ -137,12 +137,8 @@ __global__ void __launch_bounds__(256) k_coverage(RegionDev R, const UvcRangeRow
 #pragma unroll
         for (int m = 0; m < UVC_NCOV; m++) v[m] = 0;
         if (act) {
-            if (i < r_first || i >= r_next) {   // the last range whose first compact position is <= i (ranges are not empty: `first` strictly ascends)
-                int lo = 0, hi = n_ranges;
-                while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].first <= i) lo = mid; else hi = mid; }
-                rid = lo; r_first = tab[lo].first; r_x0 = tab[lo].x0; r_next = tab[lo + 1].first;
-            }
-            const int64_t x = (int64_t)r_x0 + (i - r_first);
+            uvc_range_find(g, tab, n_ranges, i);
+            const int64_t x = (int64_t)g.x0 + (i - g.first);
             act = (x >= 0 && x < R.npos);   // (the host has checked every range against the region)
             if (act) {
                 int q = 0;
@@ -151,7 +147,7 @@ __global__ void __launch_bounds__(256) k_coverage(RegionDev R, const UvcRangeRow
 #undef UVC_COV
             }
         }
-        const int my = act ? rid : -1;
+        const int my = act ? g.rid : -1;
         unsigned long long todo = last ? 1ull : __ballot(act);
         while (todo) {
             const int seg = last ? -1 : __shfl(my, __ffsll((long long)todo) - 1, 64);

@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(256) k_errprofile(RegionDev R, const UvcRangeR
     for (int j = tid; j < ERR_CELLS; j += 256) prof[j] = 0;
     __syncthreads();
     const long long base = (long long)blockIdx.x * 256 * steps;
-    int r_first = 0, r_next = 0, r_x0 = 0;   // this lane's range: compact positions [r_first, r_next), plane index of the first
+    UvcRangeCursor g;   // this lane's range
     for (int c = 0; c < steps; c++) {
         const long long i0 = base + (long long)c * 256 + (tid & ~63);   // the wave's first compact position of this step: wave-uniform
         if (i0 >= n_total) break;
@@ -104,12 +104,8 @@ __global__ void __launch_bounds__(256) k_errprofile(RegionDev R, const UvcRangeR
         bool act = (i < n_total);
         int64_t x = 0;
         if (act) {
-            if (i < r_first || i >= r_next) {   // the last range whose first compact position is <= i (ranges are not empty: `first` strictly ascends)
-                int lo = 0, hi = n_ranges;
-                while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].first <= i) lo = mid; else hi = mid; }
-                r_first = tab[lo].first; r_x0 = tab[lo].x0; r_next = tab[lo + 1].first;
-            }
-            x = (int64_t)r_x0 + (i - r_first);
+            uvc_range_find(g, tab, n_ranges, i);
+            x = (int64_t)g.x0 + (i - g.first);
             act = (x >= 0 && x < R.npos);   // (the host has checked every range against the region)
         }
         // the context: reference symbols exist for plane indices 0 .. npos - 2 (the region's last position, `end`, has no reference base)

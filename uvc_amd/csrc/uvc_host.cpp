@@ -79,7 +79,7 @@ struct uvcgpu_region {
     int32_t *d_score_fields = nullptr; int64_t score_capacity = 0; int64_t *d_score_count = nullptr;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     int32_t *d_score_kept = nullptr; int64_t score_kept_capacity = 0;   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields
-    char *d_cov = nullptr; size_t d_cov_bytes = 0; int64_t *h_cov = nullptr; size_t h_cov_bytes = 0;   // uvcgpu_region_coverage, _error_profile, _family_stats and _callable: range table + rows on the device, page-locked rows (grown on demand)
+    char *d_report = nullptr; size_t d_report_bytes = 0; char *h_report = nullptr; size_t h_report_bytes = 0;   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1179,12 +1179,11 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
             r->d_score_count = (int64_t *)r->d_score_scratch;   // the record counts head the scratch (zeroed with the scan states)
         }
         HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos_scored, r->score_capacity), r->stream));
-        int pi = -1;   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
-        if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = "k_score_all"; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); }
+        const int pi = uvc_prof_begin(&r->prof, "k_score_all", r->stream);   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
         prep.in.scratch = r->d_score_scratch;
         rc = uvc_launch_score(&prep.in, r->d_score_fields, r->score_capacity, kept_only ? r->d_score_kept : nullptr, r->stream);
         if (rc) rc = fail(rc, "score: the force-output mask could not be cleared");
-        if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
         if (!rc && hipGetLastError() != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score kernel launch failed");
         if (!rc) rc = uvcgpu_region_sync(r);
         // copies on the handle's own stream: a null-stream hipMemcpy would also wait for every other handle's work
@@ -1416,215 +1415,212 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- depth statistics of ranges (uvc_coverage.hip) ----
-// the device and the page-locked buffer that uvcgpu_region_coverage and uvcgpu_region_error_profile share (both synchronise before they return), grown on demand
-static int cov_buffers(uvcgpu_region_t *r, size_t dev_bytes, size_t out_bytes, const char *what) {
-    if (dev_bytes > r->d_cov_bytes) {
-        if (r->d_cov) { (void)hipStreamSynchronize(r->stream); hipFree(r->d_cov); }
-        r->d_cov = nullptr; r->d_cov_bytes = 0;
-        const size_t want = dev_bytes + dev_bytes / 2;
-        if (hipMalloc((void **)&r->d_cov, want) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipMalloc(") + what + ") failed"); }
-        r->d_cov_bytes = want;
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats and _callable ----
+// What the four share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
+// the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
+
+// The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
+// belong to the reads of the handle and are there from set_reads on, whatever was scored since.
+static int report_guard(const uvcgpu_region_t *r, const std::string &call, const char *planes_to) {
+    if (!r) return fail(UVCGPU_EINVAL, call + ": null region");
+    if (!planes_to) return r->reads_given ? 0 : fail(UVCGPU_EINVAL, call + " before set_reads: the region has no family units yet (uvcgpu_region_set_reads or _set_reads_device of this region comes first)");
+    if (!r->accumulated) return fail(UVCGPU_EINVAL, call + " before accumulate: there are no planes to " + planes_to);
+    if (r->state_released) return fail(UVCGPU_EINVAL, call + " after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
+    if (stream_is_open(r)) return fail(UVCGPU_EINVAL, call + " while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    return 0;
+}
+static int range_count(const std::string &call, int64_t n_ranges, int64_t most) {
+    if (n_ranges < 1) return fail(UVCGPU_EINVAL, call + ": n_ranges " + std::to_string(n_ranges) + " must be at least 1");
+    if (n_ranges > most) return fail(UVCGPU_EINVAL, call + ": n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(most) + ")");
+    return 0;
+}
+static std::string range_name(const std::string &call, int64_t k, int32_t pos_beg, int32_t pos_end) {
+    return call + ": range " + std::to_string(k) + " [" + std::to_string(pos_beg) + ", " + std::to_string(pos_end) + ")";
+}
+// The rules of a range list: no range empty, every range inside the region, sorted and disjoint.  last_end: the end of range k - 1 (not read
+// for k = 0).  The text is made for a range that breaks a rule only: a list can have a million ranges.
+static int range_check(const uvcgpu_region_t *r, const std::string &call, int64_t k, int32_t pos_beg, int32_t pos_end, int32_t last_end) {
+    if (pos_end <= pos_beg) return fail(UVCGPU_EINVAL, range_name(call, k, pos_beg, pos_end) + " is empty");
+    if (pos_beg < r->beg || pos_end > r->end) return fail(UVCGPU_EINVAL, range_name(call, k, pos_beg, pos_end) + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+    if (k > 0 && pos_beg < last_end) return fail(UVCGPU_EINVAL, range_name(call, k, pos_beg, pos_end) + " begins in front of the end " + std::to_string(last_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
+    return 0;
+}
+// The list of a plane reader, checked range by range, as the table its kernels search (UvcRangeRow, uvc_launch.h): n_ranges rows and the
+// { 0, n_total } behind them.  The caller has checked n_ranges (range_count, at most INT32_MAX >> 1: compact positions are 32-bit).
+static int range_table(const uvcgpu_region_t *r, const std::string &call, const UvcCoverageRange *ranges, int64_t n_ranges, std::vector<UvcRangeRow> &tab, int64_t &n_total) {
+    tab.resize((size_t)n_ranges + 1);
+    n_total = 0;
+    for (int64_t k = 0; k < n_ranges; k++) {
+        const UvcCoverageRange &q = ranges[k];
+        { int rc1 = range_check(r, call, k, q.pos_beg, q.pos_end, k > 0 ? ranges[k - 1].pos_end : 0); if (rc1) return rc1; }
+        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
+        n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
     }
-    if (out_bytes > r->h_cov_bytes) {
-        if (r->h_cov) { (void)hipStreamSynchronize(r->stream); (void)hipHostFree(r->h_cov); }
-        r->h_cov = nullptr; r->h_cov_bytes = 0;
+    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
+    return 0;
+}
+// The pieces of a call in the device report buffer, each on a 64-byte boundary: take() returns a piece's offset, bytes is the room so far
+struct ReportLayout {
+    size_t bytes = 0;
+    size_t take(size_t n) { const size_t at = bytes; bytes += (n + 63) & ~(size_t)63; return at; }
+};
+// the device and the page-locked buffer that the report calls share (every one synchronises before it returns), grown on demand
+static int report_buffers(uvcgpu_region_t *r, size_t dev_bytes, size_t out_bytes, const char *what) {
+    if (dev_bytes > r->d_report_bytes) {
+        if (r->d_report) { (void)hipStreamSynchronize(r->stream); hipFree(r->d_report); }
+        r->d_report = nullptr; r->d_report_bytes = 0;
+        const size_t want = dev_bytes + dev_bytes / 2;
+        if (hipMalloc((void **)&r->d_report, want) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipMalloc(") + what + ") failed"); }
+        r->d_report_bytes = want;
+    }
+    if (out_bytes > r->h_report_bytes) {
+        if (r->h_report) { (void)hipStreamSynchronize(r->stream); (void)hipHostFree(r->h_report); }
+        r->h_report = nullptr; r->h_report_bytes = 0;
         const size_t want = out_bytes + out_bytes / 2;
-        if (hipHostMalloc((void **)&r->h_cov, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipHostMalloc(") + what + ") failed"); }
-        r->h_cov_bytes = want;
+        if (hipHostMalloc((void **)&r->h_report, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipHostMalloc(") + what + ") failed"); }
+        r->h_report_bytes = want;
     }
     return 0;
 }
+// Room for a call's pieces and its result, and the range list (piece 0 of every layout) on its way: through the handle's staging buffer
+// (stage_upload: never an asynchronous copy from the caller's or the heap's pages); an earlier call's copy out of it is complete, every
+// user of the buffer synchronises before it returns.
+static int report_begin(uvcgpu_region_t *r, const ReportLayout &L, size_t out_bytes, const char *what, const void *list, size_t list_bytes) {
+    { int rc1 = report_buffers(r, L.bytes, out_bytes, what); if (rc1) return rc1; }
+    size_t at = 0;
+    return stage_upload(r, r->d_report, list, list_bytes, at, (list_bytes + 63) & ~(size_t)63);
+}
+// What was launched, to the caller: the launch's status, `bytes` from the device into the page-locked buffer, the wait, the copy out.  The
+// plane readers wait with uvcgpu_region_sync, which also reports a read shape that an accumulate kernel flagged; the family call, legal
+// before any accumulate, waits for the stream alone.
+static int report_result(uvcgpu_region_t *r, const void *d_src, void *dst, size_t bytes, bool planes) {
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(r->h_report, d_src, bytes, hipMemcpyDeviceToHost, r->stream));
+    if (planes) { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
+    else HIP_OK(hipStreamSynchronize(r->stream));
+    memcpy(dst, r->h_report, bytes);
+    return 0;
+}
+
+// ---- depth statistics of ranges (uvc_coverage.hip): [table] [result rows] [scratch rows] ----
 static int uvcgpu_region_coverage_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const int32_t *thresholds, int32_t n_thresholds, int64_t *out) {
-    if (!r) return fail(UVCGPU_EINVAL, "coverage: null region");
-    if (!r->accumulated) return fail(UVCGPU_EINVAL, "coverage before accumulate: there are no planes to reduce");
-    if (r->state_released) return fail(UVCGPU_EINVAL, "coverage after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
-    if (stream_is_open(r)) return fail(UVCGPU_EINVAL, "coverage while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    { int rc1 = report_guard(r, "coverage", "reduce"); if (rc1) return rc1; }
     if (!ranges || !out) return fail(UVCGPU_EINVAL, "coverage: ranges and out must not be NULL");
-    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "coverage: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
-    if (n_ranges > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "coverage: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
+    { int rc1 = range_count("coverage", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
     if (n_thresholds < 0 || n_thresholds > UVC_COV_MAX_THRESHOLDS || (n_thresholds > 0 && !thresholds)) return fail(UVCGPU_EINVAL, "coverage: n_thresholds " + std::to_string(n_thresholds) + " is outside 0.." + std::to_string((int)UVC_COV_MAX_THRESHOLDS));
     for (int32_t k = 0; k < n_thresholds; k++) {
         if (thresholds[k] < 0) return fail(UVCGPU_EINVAL, "coverage: threshold " + std::to_string(k) + " is negative (" + std::to_string(thresholds[k]) + ")");
         if (k > 0 && thresholds[k] <= thresholds[k - 1]) return fail(UVCGPU_EINVAL, "coverage: threshold " + std::to_string(k) + " (" + std::to_string(thresholds[k]) + ") is not larger than the one before it (" + std::to_string(thresholds[k - 1]) + "): thresholds ascend");
     }
-    std::vector<UvcRangeRow> tab((size_t)n_ranges + 1);
-    int64_t n_total = 0;
-    for (int64_t k = 0; k < n_ranges; k++) {
-        const UvcCoverageRange &q = ranges[k];
-        const std::string name = "coverage: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
-        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
-        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
-        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
-        n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
-    }
-    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
-    const size_t tab_bytes = (sizeof(UvcRangeRow) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)n_ranges;
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "coverage", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
     const int64_t scratch_rows = uvc_coverage_scratch_rows((int)n_ranges, n_total);   // the shard copies of few long ranges (0: the waves merge into the result rows)
-    const size_t dev_bytes = tab_bytes + out_bytes + sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW * (size_t)scratch_rows;   // [table] [result rows] [scratch rows]
-    { int rc1 = cov_buffers(r, dev_bytes, out_bytes, "coverage rows"); if (rc1) return rc1; }
-    // the table through the handle's staging buffer (stage_upload: never an asynchronous copy from the caller's or the heap's pages); an earlier
-    // call's copy out of it is complete, every user of the buffer synchronises before it returns
-    size_t at = 0;
-    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(UvcRangeRow) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
-    long long *d_rows = (long long *)(r->d_cov + tab_bytes);
-    uvc_launch_coverage(&r->R, (const UvcRangeRow *)r->d_cov, (int)n_ranges, n_total, thresholds, n_thresholds, d_rows, (long long *)(r->d_cov + tab_bytes + out_bytes), scratch_rows, r->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(r->h_cov, d_rows, out_bytes, hipMemcpyDeviceToHost, r->stream));
-    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
-    memcpy(out, r->h_cov, out_bytes);
-    return 0;
+    const size_t row_bytes = sizeof(int64_t) * UVC_NCOV * UVC_COV_ROW, out_bytes = row_bytes * (size_t)n_ranges;
+    ReportLayout L;
+    const size_t o_tab = L.take(sizeof(UvcRangeRow) * tab.size()), o_rows = L.take(out_bytes), o_scratch = L.take(row_bytes * (size_t)scratch_rows);
+    { int rc1 = report_begin(r, L, out_bytes, "coverage rows", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+    long long *d_rows = (long long *)(r->d_report + o_rows);
+    uvc_launch_coverage(&r->R, (const UvcRangeRow *)(r->d_report + o_tab), (int)n_ranges, n_total, thresholds, n_thresholds, d_rows, (long long *)(r->d_report + o_scratch), scratch_rows, r->stream);
+    return report_result(r, d_rows, out, out_bytes, true);
 }
 int uvcgpu_region_coverage(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const int32_t *thresholds, int32_t n_thresholds, int64_t *out) {
     return guarded("uvcgpu_region_coverage", [&] { return uvcgpu_region_coverage_impl(r, ranges, n_ranges, thresholds, n_thresholds, out); });
 }
 const char *uvcgpu_coverage_measure_name(int32_t id) { return uvc_coverage_name(id); }
 
-// ---- background error profile of ranges (uvc_errprofile.hip) ----
+// ---- background error profile of ranges (uvc_errprofile.hip): [table] [profile] [shard copies] ----
 static int uvcgpu_region_error_profile_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcErrorProfileRequest *req, int64_t *out) {
-    if (!r) return fail(UVCGPU_EINVAL, "error_profile: null region");
-    if (!r->accumulated) return fail(UVCGPU_EINVAL, "error_profile before accumulate: there are no planes to reduce");
-    if (r->state_released) return fail(UVCGPU_EINVAL, "error_profile after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
-    if (stream_is_open(r)) return fail(UVCGPU_EINVAL, "error_profile while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    { int rc1 = report_guard(r, "error_profile", "reduce"); if (rc1) return rc1; }
     if (!ranges || !req || !out) return fail(UVCGPU_EINVAL, "error_profile: ranges, req and out must not be NULL");
     if (req->min_depth < 1) return fail(UVCGPU_EINVAL, "error_profile: min_depth " + std::to_string(req->min_depth) + " must be at least 1");
     if (req->max_alt_permille < 0 || req->max_alt_permille > 1000) return fail(UVCGPU_EINVAL, "error_profile: max_alt_permille " + std::to_string(req->max_alt_permille) + " is outside 0..1000");
-    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "error_profile: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
-    if (n_ranges > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "error_profile: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
-    std::vector<UvcRangeRow> tab((size_t)n_ranges + 1);
-    int64_t n_total = 0;
-    for (int64_t k = 0; k < n_ranges; k++) {
-        const UvcCoverageRange &q = ranges[k];
-        const std::string name = "error_profile: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
-        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
-        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
-        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
-        n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
-    }
-    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
-    const size_t tab_bytes = (sizeof(UvcRangeRow) * tab.size() + 63) & ~(size_t)63, out_bytes = sizeof(int64_t) * UVC_NERRLEVEL * UVC_ERR_ROW;
-    const size_t dev_bytes = tab_bytes + out_bytes + sizeof(int64_t) * (size_t)uvc_errprofile_scratch_cells();   // [table] [profile] [shard copies]
-    { int rc1 = cov_buffers(r, dev_bytes, out_bytes, "error profile"); if (rc1) return rc1; }
-    size_t at = 0;   // the table through the handle's staging buffer, as coverage sends its own
-    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(UvcRangeRow) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
-    long long *d_prof = (long long *)(r->d_cov + tab_bytes);
-    uvc_launch_errprofile(&r->R, (const UvcRangeRow *)r->d_cov, (int)n_ranges, n_total, req->min_depth, req->max_alt_permille, d_prof, (long long *)(r->d_cov + tab_bytes + out_bytes), r->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(r->h_cov, d_prof, out_bytes, hipMemcpyDeviceToHost, r->stream));
-    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
-    memcpy(out, r->h_cov, out_bytes);
-    return 0;
+    { int rc1 = range_count("error_profile", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "error_profile", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
+    const size_t out_bytes = sizeof(int64_t) * UVC_NERRLEVEL * UVC_ERR_ROW;
+    ReportLayout L;
+    const size_t o_tab = L.take(sizeof(UvcRangeRow) * tab.size()), o_prof = L.take(out_bytes), o_scratch = L.take(sizeof(int64_t) * (size_t)uvc_errprofile_scratch_cells());
+    { int rc1 = report_begin(r, L, out_bytes, "error profile", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+    long long *d_prof = (long long *)(r->d_report + o_prof);
+    uvc_launch_errprofile(&r->R, (const UvcRangeRow *)(r->d_report + o_tab), (int)n_ranges, n_total, req->min_depth, req->max_alt_permille, d_prof, (long long *)(r->d_report + o_scratch), r->stream);
+    return report_result(r, d_prof, out, out_bytes, true);
 }
 int uvcgpu_region_error_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcErrorProfileRequest *req, int64_t *out) {
     return guarded("uvcgpu_region_error_profile", [&] { return uvcgpu_region_error_profile_impl(r, ranges, n_ranges, req, out); });
 }
 const char *uvcgpu_error_level_name(int32_t id) { return uvc_errprofile_level_name(id); }
 
-// ---- family statistics of ranges (uvc_famstats.hip) ----
+// ---- family statistics of ranges (uvc_famstats.hip): [ranges] [rows] [unit spans] ----
 // The unit records, the fragments and the per-alignment columns belong to the reads of the handle (uvcgpu_region::owned): only set_reads, reset
 // and destroy free them, and the first two are refused while a score stream is open.  A score with release_state gives up the planes and
-// nothing else.  So the call is legal from set_reads on, whatever was scored since.  It shares the buffers of the coverage call.
+// nothing else.  So the call is legal from set_reads on, whatever was scored since.  Its kernels read the caller's rows as they are, no table.
 static int uvcgpu_region_family_stats_impl(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out) {
-    if (!r) return fail(UVCGPU_EINVAL, "family_stats: null region");
-    if (!r->reads_given) return fail(UVCGPU_EINVAL, "family_stats before set_reads: the region has no family units yet (uvcgpu_region_set_reads or _set_reads_device of this region comes first)");
+    { int rc1 = report_guard(r, "family_stats", nullptr); if (rc1) return rc1; }
     if (!ranges || !out) return fail(UVCGPU_EINVAL, "family_stats: ranges and out must not be NULL");
-    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "family_stats: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
-    if (n_ranges > (INT32_MAX >> 10)) return fail(UVCGPU_EINVAL, "family_stats: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 10) + ")");
+    const std::string call = "family_stats";
+    { int rc1 = range_count(call, n_ranges, INT32_MAX >> 10); if (rc1) return rc1; }
     for (int64_t k = 0; k < n_ranges; k++) {
         const UvcFamilyRange &q = ranges[k];
-        const std::string name = "family_stats: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
-        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
-        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
-        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-        if (q.prev_end > q.pos_beg) return fail(UVCGPU_EINVAL, name + " has prev_end " + std::to_string(q.prev_end) + " behind its begin (prev_end is the end of an earlier range)");
-        if (k > 0 && q.prev_end < ranges[k - 1].prev_end) return fail(UVCGPU_EINVAL, name + " has prev_end " + std::to_string(q.prev_end) + " below the prev_end " + std::to_string(ranges[k - 1].prev_end) + " of range " + std::to_string(k - 1) + " (prev_end must not decrease)");
-        if (k > 0 && q.prev_end < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " has prev_end " + std::to_string(q.prev_end) + " below the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + ": that range's families would be counted twice");
-        if (q.flags & ~(int32_t)UVC_FAMRANGE_CONTINUES) return fail(UVCGPU_EINVAL, name + " has unknown flag bits (flags " + std::to_string(q.flags) + "; only UVC_FAMRANGE_CONTINUES = 1 is defined)");
+        { int rc1 = range_check(r, call, k, q.pos_beg, q.pos_end, k > 0 ? ranges[k - 1].pos_end : 0); if (rc1) return rc1; }
+        auto name = [&] { return range_name(call, k, q.pos_beg, q.pos_end); };
+        if (q.prev_end > q.pos_beg) return fail(UVCGPU_EINVAL, name() + " has prev_end " + std::to_string(q.prev_end) + " behind its begin (prev_end is the end of an earlier range)");
+        if (k > 0 && q.prev_end < ranges[k - 1].prev_end) return fail(UVCGPU_EINVAL, name() + " has prev_end " + std::to_string(q.prev_end) + " below the prev_end " + std::to_string(ranges[k - 1].prev_end) + " of range " + std::to_string(k - 1) + " (prev_end must not decrease)");
+        if (k > 0 && q.prev_end < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name() + " has prev_end " + std::to_string(q.prev_end) + " below the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + ": that range's families would be counted twice");
+        if (q.flags & ~(int32_t)UVC_FAMRANGE_CONTINUES) return fail(UVCGPU_EINVAL, name() + " has unknown flag bits (flags " + std::to_string(q.flags) + "; only UVC_FAMRANGE_CONTINUES = 1 is defined)");
     }
     const size_t out_bytes = sizeof(int64_t) * UVC_FAMSTAT_ROW * (size_t)n_ranges;
     if (!r->has_reads) { memset(out, 0, out_bytes); return 0; }   // set_reads with zero reads: no family, nothing to launch
-    const size_t tab_bytes = (sizeof(UvcFamilyRange) * (size_t)n_ranges + 63) & ~(size_t)63, span_bytes = (sizeof(UvcUnitSpan) * (size_t)std::max(r->R.n_fs, 1) + 63) & ~(size_t)63;
-    { int rc1 = cov_buffers(r, tab_bytes + out_bytes + span_bytes, out_bytes, "family statistics"); if (rc1) return rc1; }   // [ranges] [rows] [unit spans]
-    size_t at = 0;   // the ranges through the handle's staging buffer, as coverage sends its table
-    { int rc1 = stage_upload(r, r->d_cov, ranges, sizeof(UvcFamilyRange) * (size_t)n_ranges, at, tab_bytes); if (rc1) return rc1; }
-    long long *d_rows = (long long *)(r->d_cov + tab_bytes);
-    int pi = -1;   // with profiling on, the three kernels as one more entry of uvcgpu_region_kernel_times (accumulate starts the list anew)
-    if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = "k_famstats"; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); }
-    uvc_launch_famstats(&r->R, r->W.pos, r->W.endpos, r->W.fs, (UvcUnitSpan *)(r->d_cov + tab_bytes + out_bytes), (const UvcFamilyRange *)r->d_cov, (int)n_ranges, d_rows, r->stream);
-    if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(r->h_cov, d_rows, out_bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_OK(hipStreamSynchronize(r->stream));
-    memcpy(out, r->h_cov, out_bytes);
-    return 0;
+    ReportLayout L;
+    const size_t o_ranges = L.take(sizeof(UvcFamilyRange) * (size_t)n_ranges), o_rows = L.take(out_bytes), o_span = L.take(sizeof(UvcUnitSpan) * (size_t)std::max(r->R.n_fs, 1));
+    { int rc1 = report_begin(r, L, out_bytes, "family statistics", ranges, sizeof(UvcFamilyRange) * (size_t)n_ranges); if (rc1) return rc1; }
+    long long *d_rows = (long long *)(r->d_report + o_rows);
+    const int pi = uvc_prof_begin(&r->prof, "k_famstats", r->stream);   // with profiling on, the three kernels as one more entry of uvcgpu_region_kernel_times (accumulate starts the list anew)
+    uvc_launch_famstats(&r->R, r->W.pos, r->W.endpos, r->W.fs, (UvcUnitSpan *)(r->d_report + o_span), (const UvcFamilyRange *)(r->d_report + o_ranges), (int)n_ranges, d_rows, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    return report_result(r, d_rows, out, out_bytes, false);
 }
 int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out) {
     return guarded("uvcgpu_region_family_stats", [&] { return uvcgpu_region_family_stats_impl(r, ranges, n_ranges, out); });
 }
 const char *uvcgpu_family_stat_name(int32_t id) { return uvc_famstats_name(id); }
 
-// ---- callable-region intervals of ranges (uvc_callable.hip) ----
+// ---- callable-region intervals of ranges (uvc_callable.hip): [table] [block counts] [mask bytes] [runs, one per position at worst] ----
 // Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit
-// and copies 16 bytes per run.  It shares the buffers of the coverage call: [table] [block counts] [mask bytes] [runs, one per position at worst].
+// and copies 16 bytes per run.
 static int uvcgpu_region_callable_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcCallableRequest *req, UvcCallableRun *runs, int64_t run_capacity, int64_t *n_runs) {
-    if (!r) return fail(UVCGPU_EINVAL, "callable: null region");
-    if (!r->accumulated) return fail(UVCGPU_EINVAL, "callable before accumulate: there are no planes to classify");
-    if (r->state_released) return fail(UVCGPU_EINVAL, "callable after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
-    if (stream_is_open(r)) return fail(UVCGPU_EINVAL, "callable while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    { int rc1 = report_guard(r, "callable", "classify"); if (rc1) return rc1; }
     if (!ranges || !req || !n_runs) return fail(UVCGPU_EINVAL, "callable: ranges, req and n_runs must not be NULL");
     if (run_capacity < 0) return fail(UVCGPU_EINVAL, "callable: run_capacity " + std::to_string(run_capacity) + " is negative");
     if (!runs && run_capacity > 0) return fail(UVCGPU_EINVAL, "callable: runs is NULL with run_capacity " + std::to_string(run_capacity));
     for (int32_t k = 0; k < UVC_NCOV; k++)
         if (req->min_depth[k] < 0) return fail(UVCGPU_EINVAL, std::string("callable: min_depth[") + uvc_coverage_name(k) + "] is negative (" + std::to_string(req->min_depth[k]) + ")");
     if (req->max_aDP < 0) return fail(UVCGPU_EINVAL, "callable: max_aDP is negative (" + std::to_string(req->max_aDP) + ")");
-    if (n_ranges < 1) return fail(UVCGPU_EINVAL, "callable: n_ranges " + std::to_string(n_ranges) + " must be at least 1");
-    if (n_ranges > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "callable: n_ranges " + std::to_string(n_ranges) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
-    std::vector<UvcRangeRow> tab((size_t)n_ranges + 1);
-    int64_t n_total = 0;
-    for (int64_t k = 0; k < n_ranges; k++) {
-        const UvcCoverageRange &q = ranges[k];
-        const std::string name = "callable: range " + std::to_string(k) + " [" + std::to_string(q.pos_beg) + ", " + std::to_string(q.pos_end) + ")";
-        if (q.pos_end <= q.pos_beg) return fail(UVCGPU_EINVAL, name + " is empty");
-        if (q.pos_beg < r->beg || q.pos_end > r->end) return fail(UVCGPU_EINVAL, name + " is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
-        if (k > 0 && q.pos_beg < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name + " begins in front of the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + " (ranges must be sorted and disjoint)");
-        tab[(size_t)k] = UvcRangeRow{ q.pos_beg - r->beg, (int32_t)n_total };
-        n_total += (int64_t)q.pos_end - q.pos_beg;   // (<= npos: the ranges are disjoint and inside the region)
-    }
-    tab[(size_t)n_ranges] = UvcRangeRow{ 0, (int32_t)n_total };
+    { int rc1 = range_count("callable", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "callable", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
     const int64_t n_blocks = uvc_callable_blocks(n_total);
-    const size_t tab_bytes = (sizeof(UvcRangeRow) * tab.size() + 63) & ~(size_t)63, blk_bytes = (sizeof(int32_t) * (size_t)(n_blocks + 1) + 63) & ~(size_t)63;
-    const size_t mask_bytes = ((size_t)n_total + 63) & ~(size_t)63, run_bytes = sizeof(UvcCallableRun) * (size_t)n_total;   // every position can be its own run
-    { int rc1 = cov_buffers(r, tab_bytes + blk_bytes + mask_bytes + run_bytes, 64, "callable runs"); if (rc1) return rc1; }
-    size_t at = 0;   // the table through the handle's staging buffer, as coverage sends its own
-    { int rc1 = stage_upload(r, r->d_cov, tab.data(), sizeof(UvcRangeRow) * tab.size(), at, tab_bytes); if (rc1) return rc1; }
-    const UvcRangeRow *d_tab = (const UvcRangeRow *)r->d_cov;
-    int *d_blocks = (int *)(r->d_cov + tab_bytes);
-    unsigned char *d_mask = (unsigned char *)(r->d_cov + tab_bytes + blk_bytes);
-    UvcCallableRun *d_runs = (UvcCallableRun *)(r->d_cov + tab_bytes + blk_bytes + mask_bytes);
+    ReportLayout L;
+    const size_t o_tab = L.take(sizeof(UvcRangeRow) * tab.size()), o_blocks = L.take(sizeof(int32_t) * (size_t)(n_blocks + 1)), o_mask = L.take((size_t)n_total);
+    const size_t o_runs = L.take(sizeof(UvcCallableRun) * (size_t)n_total);   // every position can be its own run
+    { int rc1 = report_begin(r, L, 64, "callable runs", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+    const UvcRangeRow *d_tab = (const UvcRangeRow *)(r->d_report + o_tab);
+    int *d_blocks = (int *)(r->d_report + o_blocks);
+    unsigned char *d_mask = (unsigned char *)(r->d_report + o_mask);
+    UvcCallableRun *d_runs = (UvcCallableRun *)(r->d_report + o_runs);
     // with profiling on, two more entries of uvcgpu_region_kernel_times (accumulate starts the list anew): the host reads the count between them
-    auto prof_begin = [&](const char *name) { int pi = -1; if (r->prof.on && r->prof.n < 32) { pi = r->prof.n++; r->prof.name[pi] = name; if (!r->prof.ev[pi][0]) { hipEventCreate(&r->prof.ev[pi][0]); hipEventCreate(&r->prof.ev[pi][1]); } hipEventRecord(r->prof.ev[pi][0], r->stream); } return pi; };
-    auto prof_end = [&](int pi) { if (pi >= 0) hipEventRecord(r->prof.ev[pi][1], r->stream); };
-    int pi = prof_begin("k_callable_count");
+    int pi = uvc_prof_begin(&r->prof, "k_callable_count", r->stream);
     uvc_launch_callable_count(&r->R, d_tab, (int)n_ranges, n_total, req, d_mask, d_blocks, r->stream);
-    prof_end(pi);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(r->h_cov, d_blocks + n_blocks, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
-    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
-    const int64_t n = *(const int32_t *)r->h_cov;
+    uvc_prof_end(&r->prof, pi, r->stream);
+    int32_t n = 0;
+    { int rc1 = report_result(r, d_blocks + n_blocks, &n, sizeof(int32_t), true); if (rc1) return rc1; }
     *n_runs = n;
     if (n > run_capacity) return fail(UVCGPU_ENOMEM, "callable: " + std::to_string(n) + " runs, room for " + std::to_string(run_capacity));
     const size_t out_bytes = sizeof(UvcCallableRun) * (size_t)n;
-    { int rc1 = cov_buffers(r, 0, out_bytes, "callable runs"); if (rc1) return rc1; }
-    pi = prof_begin("k_callable_emit");
+    { int rc1 = report_buffers(r, 0, out_bytes, "callable runs"); if (rc1) return rc1; }
+    pi = uvc_prof_begin(&r->prof, "k_callable_emit", r->stream);
     uvc_launch_callable_emit(&r->R, d_tab, (int)n_ranges, n_total, d_mask, d_blocks, d_runs, r->stream);
-    prof_end(pi);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(r->h_cov, d_runs, out_bytes, hipMemcpyDeviceToHost, r->stream));
-    { int rc1 = uvcgpu_region_sync(r); if (rc1) return rc1; }
-    memcpy(runs, r->h_cov, out_bytes);
-    return 0;
+    uvc_prof_end(&r->prof, pi, r->stream);
+    return report_result(r, d_runs, runs, out_bytes, true);
 }
 int uvcgpu_region_callable(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcCallableRequest *req, UvcCallableRun *runs, int64_t run_capacity, int64_t *n_runs) {
     return guarded("uvcgpu_region_callable", [&] { return uvcgpu_region_callable_impl(r, ranges, n_ranges, req, runs, run_capacity, n_runs); });
@@ -1675,8 +1671,8 @@ void uvcgpu_region_destroy(uvcgpu_region_t *r) {
     if (r->d_score_fields) hipFree(r->d_score_fields);
     if (r->d_score_kept) hipFree(r->d_score_kept);
     if (r->h_stage) (void)hipHostFree(r->h_stage);
-    if (r->d_cov) hipFree(r->d_cov);
-    if (r->h_cov) (void)hipHostFree(r->h_cov);
+    if (r->d_report) hipFree(r->d_report);
+    if (r->h_report) (void)hipHostFree(r->h_report);
     if (r->d_gap_alleles) hipFree(r->d_gap_alleles);
     if (r->d_gap_allele_row) hipFree(r->d_gap_allele_row);
     if (r->d_gap_rows) hipFree(r->d_gap_rows);

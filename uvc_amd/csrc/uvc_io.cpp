@@ -1208,10 +1208,34 @@ extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t po
 }
 extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }
 
+// ---------------------------------------------------------------- the report stores ----
+// What the stores of --coverage-out, --error-profile-out, --family-stats-out and --callable-out share: a store collects what the tiles
+// report under its mutex and writes the whole file at the end.
+// a target as the stores with target lines keep it; a BED line without a name is "."
+struct ReportTarget { std::string chrom, name; int64_t beg, end; };
+static ReportTarget report_target(const char *chrom, const char *name, int64_t beg, int64_t end) { return ReportTarget{ chrom, (name && *name) ? name : ".", beg, end }; }
+// `text` as the file `path`, block-gzipped when the name ends in .gz
+static int write_text(const char *path, const std::string &text) {
+    const std::string p = path;
+    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
+        uvcio_bgzf_writer_t *zw = nullptr;
+        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
+        const int rc2 = uvcio_bgzf_write_close(zw);
+        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+        return 0;
+    }
+    FILE *fo = fopen(path, "wb");
+    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
+    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
+    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
+    return 0;
+}
+
 // ---------------------------------------------------------------- the per-target coverage report ----
 struct uvcio_coverage {
     std::vector<std::string> measures; std::vector<int32_t> thr;
-    struct Target { std::string chrom, name; int64_t beg, end, len, covered; };
+    struct Target : ReportTarget { int64_t len, covered; };
     std::vector<Target> targets;
     std::vector<int64_t> rows;   // [target][measure][3 + n_thr]: sum, min, max, counts
     std::mutex mu;
@@ -1228,7 +1252,7 @@ extern "C" int uvcio_coverage_open(uvcio_coverage_t **out, const char *const *me
 extern "C" int64_t uvcio_coverage_add_target(uvcio_coverage_t *c, const char *chrom, int64_t beg, int64_t end, const char *name, int64_t len) {
     if (!c || !chrom || len < 0) return fail(UVCGPU_EINVAL, "coverage report: bad target");
     std::lock_guard<std::mutex> g(c->mu);
-    c->targets.push_back(uvcio_coverage::Target{ chrom, (name && *name) ? name : ".", beg, end, len, 0 });
+    c->targets.push_back(uvcio_coverage::Target{ report_target(chrom, name, beg, end), len, 0 });
     c->rows.resize(c->targets.size() * c->width(), 0);
     return (int64_t)c->targets.size() - 1;
 }
@@ -1270,20 +1294,7 @@ extern "C" int uvcio_coverage_write(const uvcio_coverage_t *c, const char *path)
         }
         text += "\n";
     }
-    const std::string p = path;
-    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
-        uvcio_bgzf_writer_t *zw = nullptr;
-        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
-        const int rc2 = uvcio_bgzf_write_close(zw);
-        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-        return 0;
-    }
-    FILE *fo = fopen(path, "wb");
-    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
-    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-    return 0;
+    return write_text(path, text);
 }
 extern "C" void uvcio_coverage_close(uvcio_coverage_t *c) { delete c; }
 
@@ -1333,27 +1344,14 @@ extern "C" int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *p
                 for (int j = 0; j < n; j++) text += head + (kind == 0 ? BASE_SYM[j] : LINK_SYM[j]) + "\t" + std::to_string(b[j]) + "\t" + std::to_string(b[ref]) + "\n";
             }
         }
-    const std::string p = path;
-    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
-        uvcio_bgzf_writer_t *zw = nullptr;
-        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
-        const int rc2 = uvcio_bgzf_write_close(zw);
-        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-        return 0;
-    }
-    FILE *fo = fopen(path, "wb");
-    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
-    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-    return 0;
+    return write_text(path, text);
 }
 extern "C" void uvcio_errprofile_close(uvcio_errprofile_t *e) { delete e; }
 
 // ---------------------------------------------------------------- the UMI family report ----
 // the row layout is that of uvcgpu_region_family_stats (UVC_FAMSTAT_* of uvcgpu.h, include/uvc_famstats.def); the reserved word is not written
 struct uvcio_famstats {
-    struct Target { std::string chrom, name; int64_t beg, end; int64_t c[4]; };
+    struct Target : ReportTarget { int64_t c[4]; };
     std::vector<Target> targets;
     int64_t first[UVC_FAMSTAT_ROW];   // the FIRST blocks of all pieces, summed (words below UVC_FAMSTAT_FIRST stay 0)
     std::mutex mu;
@@ -1368,7 +1366,7 @@ extern "C" int uvcio_famstats_open(uvcio_famstats_t **out) {
 extern "C" int64_t uvcio_famstats_add_target(uvcio_famstats_t *f, const char *chrom, int64_t beg, int64_t end, const char *name) {
     if (!f || !chrom) return fail(UVCGPU_EINVAL, "family report: bad target");
     std::lock_guard<std::mutex> g(f->mu);
-    f->targets.push_back(uvcio_famstats::Target{ chrom, (name && *name) ? name : ".", beg, end, { 0, 0, 0, 0 } });
+    f->targets.push_back(uvcio_famstats::Target{ report_target(chrom, name, beg, end), { 0, 0, 0, 0 } });
     return (int64_t)f->targets.size() - 1;
 }
 extern "C" int uvcio_famstats_add_piece(uvcio_famstats_t *f, int64_t target, const int64_t *row) {
@@ -1400,29 +1398,15 @@ extern "C" int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path)
     for (const uvcio_famstats::Target &t : f->targets)
         text += t.chrom + "\t" + std::to_string(t.beg) + "\t" + std::to_string(t.end) + "\t" + t.name + "\t" + std::to_string(t.c[0]) + "\t" + std::to_string(t.c[1]) + "\t" + std::to_string(t.c[2]) + "\t"
                 + std::to_string(t.c[3]) + "\t" + std::to_string(fs_ratio(t.c[1], t.c[0])) + "\t" + std::to_string(fs_ratio(t.c[3], t.c[0])) + "\n";
-    const std::string p = path;
-    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
-        uvcio_bgzf_writer_t *zw = nullptr;
-        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
-        const int rc2 = uvcio_bgzf_write_close(zw);
-        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-        return 0;
-    }
-    FILE *fo = fopen(path, "wb");
-    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
-    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-    return 0;
+    return write_text(path, text);
 }
 extern "C" void uvcio_famstats_close(uvcio_famstats_t *f) { delete f; }
 
 // ---------------------------------------------------------------- the callable-region BED ----
 struct uvcio_callable {
     std::vector<std::string> measures, bits; std::vector<int32_t> min_depth; int32_t max_aDP = 0;
-    struct Target { std::string chrom, name; int64_t beg, end; };
     struct Run { int32_t target, beg, end, mask; };   // 16 bytes per run, kept to the end: the file is written in target order
-    std::vector<Target> targets; std::vector<Run> runs;
+    std::vector<ReportTarget> targets; std::vector<Run> runs;
     std::mutex mu;
 };
 extern "C" int uvcio_callable_open(uvcio_callable_t **out, const char *const *measure_names, int32_t n_measures, const int32_t *min_depth, int32_t max_aDP, const char *const *bit_names, int32_t n_bits) {
@@ -1437,7 +1421,7 @@ extern "C" int uvcio_callable_open(uvcio_callable_t **out, const char *const *me
 extern "C" int64_t uvcio_callable_add_target(uvcio_callable_t *c, const char *chrom, int64_t beg, int64_t end, const char *name) {
     if (!c || !chrom || beg < 0 || end > INT32_MAX) return fail(UVCGPU_EINVAL, "callable report: bad target");
     std::lock_guard<std::mutex> g(c->mu);
-    c->targets.push_back(uvcio_callable::Target{ chrom, (name && *name) ? name : ".", beg, std::max(beg, end) });
+    c->targets.push_back(report_target(chrom, name, beg, std::max(beg, end)));
     return (int64_t)c->targets.size() - 1;
 }
 extern "C" int uvcio_callable_add_runs(uvcio_callable_t *c, const int64_t *target_of_range, int64_t n_ranges, const UvcCallableRun *runs, int64_t n_runs) {
@@ -1467,7 +1451,7 @@ extern "C" int uvcio_callable_write(const uvcio_callable_t *c, const char *path)
     int64_t total = 0, callable_ = 0; std::vector<int64_t> per_bit(nb, 0);
     size_t at = 0;
     for (size_t t = 0; t < c->targets.size(); t++) {
-        const uvcio_callable::Target &T = c->targets[t];
+        const ReportTarget &T = c->targets[t];
         int64_t open_beg = T.beg, open_end = T.beg; int32_t open_mask = 0;   // the line being joined: [open_beg, open_end), empty at first
         auto flush = [&]() {
             if (open_end <= open_beg) return;
@@ -1495,19 +1479,6 @@ extern "C" int uvcio_callable_write(const uvcio_callable_t *c, const char *path)
     }
     text += "#summary\tpositions\t" + std::to_string(total) + "\n#summary\tCALLABLE\t" + std::to_string(callable_) + "\n";
     for (size_t b = 0; b < nb; b++) text += "#summary\t" + c->bits[b] + "\t" + std::to_string(per_bit[b]) + "\n";
-    const std::string p = path;
-    if (p.size() > 3 && p.compare(p.size() - 3, 3, ".gz") == 0) {
-        uvcio_bgzf_writer_t *zw = nullptr;
-        if (uvcio_bgzf_write_open(&zw, path, 6)) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-        const int rc = uvcio_bgzf_write(zw, text.data(), (int64_t)text.size());
-        const int rc2 = uvcio_bgzf_write_close(zw);
-        if (rc || rc2) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-        return 0;
-    }
-    FILE *fo = fopen(path, "wb");
-    if (!fo) return fail(UVCGPU_EINVAL, std::string("cannot create ") + path);
-    const bool ok = (fwrite(text.data(), 1, text.size(), fo) == text.size());
-    if (fclose(fo) != 0 || !ok) return fail(UVCGPU_EINVAL, std::string("cannot write ") + path);
-    return 0;
+    return write_text(path, text);
 }
 extern "C" void uvcio_callable_close(uvcio_callable_t *c) { delete c; }

@@ -3553,12 +3553,11 @@ extern "C" void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, co
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 static inline int imin_h(int a, int b) { return a < b ? a : b; }
 
-// optional per-kernel HIP-event timing on the handle's own stream (UvcProf, bench.py roofline leg)
+// optional per-kernel HIP-event timing on the stream `s` of the place of use (uvc_prof_begin / uvc_prof_end of uvc_launch.h, bench.py roofline leg)
 #define TIMED(prof, kname, ...) do { \
-        UvcProf *p_ = (prof); int i_ = -1; \
-        if (p_ && p_->on && p_->n < 32) { i_ = p_->n++; p_->name[i_] = kname; if (!p_->ev[i_][0]) { hipEventCreate(&p_->ev[i_][0]); hipEventCreate(&p_->ev[i_][1]); } hipEventRecord(p_->ev[i_][0], s); } \
+        UvcProf *p_ = (prof); const int i_ = uvc_prof_begin(p_, kname, s); \
         __VA_ARGS__; \
-        if (i_ >= 0) hipEventRecord(p_->ev[i_][1], s); \
+        uvc_prof_end(p_, i_, s); \
     } while (0)
 
 // apply_bq_err_correction3 (grouping.cpp:459-543): quality increment and cap, tail penalty behind a long soft clip / homopolymer at

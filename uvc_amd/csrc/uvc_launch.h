@@ -12,8 +12,19 @@ struct RawReads {
     const int64_t *seq_off, *cigar_off, *table_off, *item_off, *gap_off;
 };
 static_assert(sizeof(RawReads) == 19 * sizeof(void *), "RawReads is 19 device pointers");
-// optional per-kernel HIP-event timing on the handle's own stream (bench.py roofline leg)
+// optional per-kernel HIP-event timing on the handle's own stream (bench.py roofline leg): the entries of uvcgpu_region_kernel_times
 struct UvcProf { int on; int n; const char *name[32]; hipEvent_t ev[32][2]; };
+// One more entry around what is launched between the two calls on stream s: -1 (and nothing recorded) with profiling off, without a UvcProf
+// or with the 32 entries taken; the events of an entry are created at its first use and live as long as the handle.
+static inline int uvc_prof_begin(UvcProf *p, const char *name, hipStream_t s) {
+    if (!p || !p->on || p->n >= 32) return -1;
+    const int i = p->n++;
+    p->name[i] = name;
+    if (!p->ev[i][0]) { hipEventCreate(&p->ev[i][0]); hipEventCreate(&p->ev[i][1]); }
+    hipEventRecord(p->ev[i][0], s);
+    return i;
+}
+static inline void uvc_prof_end(UvcProf *p, int i, hipStream_t s) { if (i >= 0) hipEventRecord(p->ev[i][1], s); }
 // one plane of the slab for k_zero_state; fam < 0: always filled, else the (plane family, sym) of RegionDev::dirty that says whether to
 struct ZeroPlane { unsigned long long off; int32_t elem; int16_t fam, sym; };
 static_assert(sizeof(ZeroPlane) == 16, "the host uploads the plane table as 16-byte rows");
@@ -21,10 +32,20 @@ static_assert(sizeof(ZeroPlane) == 16, "the host uploads the plane table as 16-b
 // of the lengths), flags bit 0 = base_at_pos_beg
 struct UvcScoreRangeDev { int beg, end, first, flags; };
 static_assert(sizeof(UvcScoreRangeDev) == 16, "the host uploads the range table as 16-byte rows");
-// one range of uvcgpu_region_coverage / uvcgpu_region_error_profile: plane index of the range's first position; its first compact position.
-// Entry n_ranges of a table: { 0, n_total }
+// one range of the plane readers (uvcgpu_region_coverage, _error_profile, _callable): plane index of the range's first position; its first
+// compact position (the exclusive prefix of the lengths).  Entry n_ranges of a table: { 0, n_total }.  The host builds it in one place
+// (range_table of uvc_host.cpp), the kernels look a compact position up through UvcRangeCursor.
 struct UvcRangeRow { int x0, first; };
 static_assert(sizeof(UvcRangeRow) == 8, "the host uploads the range table as 8-byte rows");
+// A lane's range: compact positions [first, next), plane index x0 of the first, kept while the lane's positions stay inside.  uvc_range_find
+// moves it to the last range whose first compact position is <= i (ranges are not empty: `first` strictly ascends), i in [0, n_total).
+struct UvcRangeCursor { int rid = -1, first = 0, next = 0, x0 = 0; };
+DEV void uvc_range_find(UvcRangeCursor &g, const UvcRangeRow *tab, int n_ranges, long long i) {
+    if (i >= g.first && i < g.next) return;
+    int lo = 0, hi = n_ranges;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].first <= i) lo = mid; else hi = mid; }
+    g.rid = lo; g.first = tab[lo].first; g.x0 = tab[lo].x0; g.next = tab[lo + 1].first;
+}
 // uvcgpu_region_family_stats: smallest pos and largest reference end of the alignments of one family-strand unit (scratch the host sizes)
 struct UvcUnitSpan { int lo, hi; };
 static_assert(sizeof(UvcUnitSpan) == 8, "the host sizes the span scratch as 8-byte rows");
@@ -72,7 +93,7 @@ size_t uvc_score_stream_table_offset(int64_t npos_scored);
 void uvc_launch_check_presence(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
 void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s);
 void uvc_launch_block_stats_windows(const RegionDev *R, const UvcParams *P, const long long *d_win, int n_win, int64_t n, int32_t *d_out, hipStream_t s);
-// ---- uvc_coverage.hip, uvc_errprofile.hip: d_tab = n_ranges + 1 rows ----
+// ---- uvc_coverage.hip, uvc_errprofile.hip: d_tab = the n_ranges + 1 rows of UvcRangeRow ----
 void uvc_launch_coverage(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s);
 const char *uvc_coverage_name(int id);
 int64_t uvc_coverage_scratch_rows(int n_ranges, int64_t n_total);

@@ -230,6 +230,13 @@ def vcf_header(lib, params, sample, contigs, tumor_sample=None):
     return dst.raw[:ln.value].decode()
 
 
+def _coverage_ranges(ranges):
+    """(pos_beg, pos_end) pairs as the UvcCoverageRange array of the plane readers (at least one element: an empty list still has an
+    address), and the pairs as ints."""
+    rows = [(int(q[0]), int(q[1])) for q in ranges]
+    return (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows]), rows
+
+
 class Region:
     def __init__(self, lib, params, tid, beg, end, refseq):
         self.lib, self.tid, self.beg, self.end = lib, tid, beg, end
@@ -477,8 +484,7 @@ class Region:
         COVERAGE_MEASURES the sum, the minimum and the maximum of its per-position depth over the range, then the number of positions at or
         above each of `thresholds` (at most 8, ascending).  After accumulate() and before anything that releases the planes."""
         fn = self._ranges_fn("region_coverage", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p])
-        rows = [(int(q[0]), int(q[1])) for q in ranges]
-        arr = (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows])
+        arr, rows = _coverage_ranges(ranges)
         thr = np.ascontiguousarray(thresholds, dtype=np.int32).reshape(-1)
         ncov, row = _ffi.ENUMS["UVC_NCOV"], _ffi.ENUMS["UVC_COV_ROW"]
         out = np.zeros((max(len(rows), 1), ncov, row), dtype=np.int64)
@@ -492,8 +498,7 @@ class Region:
         position enters a level's bins where the level's depth is >= min_depth and its largest non-reference count is at most max_alt_permille
         thousandths of it (uvcgpu.h has the rules).  After accumulate() and before anything that releases the planes."""
         fn = self._ranges_fn("region_error_profile", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
-        rows = [(int(q[0]), int(q[1])) for q in ranges]
-        arr = (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows])
+        arr, rows = _coverage_ranges(ranges)
         req = _ffi.UvcErrorProfileRequest(int(min_depth), int(max_alt_permille))
         out = np.zeros((_ffi.ENUMS["UVC_NERRLEVEL"], _ffi.ENUMS["UVC_ERR_ROW"]), dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data))
@@ -520,8 +525,7 @@ class Region:
         structured array (range, pos_beg, pos_end, mask; int32), sorted by (range, pos_beg), the runs of a range tiling it; bit k of mask is
         CALLABLE_BITS[k], mask 0 = callable.  Classified and compacted on the device; asks for the size first, then for the runs."""
         fn = self._ranges_fn("region_callable", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
-        rows = [(int(q[0]), int(q[1])) for q in ranges]
-        arr = (_ffi.UvcCoverageRange * max(len(rows), 1))(*[_ffi.UvcCoverageRange(*q) for q in rows])
+        arr, rows = _coverage_ranges(ranges)
         req = _ffi.UvcCallableRequest()
         for name, v in (min_depth or {}).items():
             req.min_depth[COVERAGE_MEASURES.index(name)] = int(v)
