@@ -542,6 +542,45 @@ typedef struct UvcFamilyRange { int32_t pos_beg, pos_end, prev_end, flags; } Uvc
  *   UVC_FAMRANGE_CONTINUES.  `out` is written only by a call that returns 0. */
 int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out /* [n_ranges][UVC_FAMSTAT_ROW] */);
 const char *uvcgpu_family_stat_name(int32_t id);   /* "target_families" .. "strands"; NULL for an id outside 0..UVC_NFAMSTAT - 1 */
+/* ---- base-quality and cycle profile of the region's reads (uvc1-mi355x --read-profile-out) ----
+ * One pass over the read bases the handle holds (UvcReadSoA): what the reported qualities are worth, where along the read mismatches,
+ * InDels and clips fall, and which substitutions each read class makes.  All integers.
+ *   An alignment is counted iff mapq >= min_mapq.  Its class c = 2 * ((flag & 0x80) != 0) + ((flag & 0x10) != 0): R1 forward, R1 reverse,
+ *   R2 forward, R2 reverse.  An alignment with l_qseq 0 adds nothing.
+ *   CIGAR walk: query index q from 0, reference coordinate p from pos; M = X consume both, I S the query, D N the reference, H P nothing.
+ *   Cycle of q in a read of l_qseq L: (flag & 0x10) ? L - 1 - q : q (hard clips do not count), bin cb = min(cycle, 255).  Quality bin
+ *   qb = min(quality, 63), the quality being the handle's present one: after uvcgpu_region_correct_bq the corrected one.
+ *   Status of every position p of the region, over ALL counted alignments and independent of the ranges: D(p) = the aligned bases (M = X)
+ *   at p whose read base is A/C/G/T, X(p) = those that differ from the reference symbol; no_ref when the reference symbol is not A/C/G/T
+ *   (the region's last position, which has no reference base, included); else low_depth when D < min_depth; else high_alt when
+ *   X * 1000 > max_alt_permille * D; else clean.
+ *   An aligned base at p inside a range adds to exactly one counter, tested in this order: bases_low_mapq (alignment not counted),
+ *   bases_no_ref, bases_n (read base not A/C/G/T), bases_low_depth, bases_high_alt, else bases_clean together with Q[c][qb][k],
+ *   CYC[c][cb][k] (k = 0 match, 1 mismatch against the reference symbol) and SUB[c][reference base][read base] (forward-strand codes 0..3).
+ *   Unaligned events of counted alignments are gated by an anchor position alone: max(pos, p - 1) for I and S and p for D, p being the
+ *   walk's reference coordinate at the op.  An anchor in no range or outside the region adds nothing; else every inserted base adds
+ *   CYC[c][cb][2] and every soft-clipped base CYC[c][cb][4] at its own cycle, every D op one CYC[c][cb][3] at the cycle of query index
+ *   max(0, q - 1).  N moves p and adds nothing.
+ *   Every position inside a range adds 1 to the positions_* counter of its status.
+ * One row of UVC_READPROF_ROW int64 per call (sections: include/uvc_readprofile.def).  Rows of disjoint position sets add. */
+enum UvcReadProfSection { UVC_READPROF_Q = 0, UVC_READPROF_CYC, UVC_READPROF_SUB, UVC_READPROF_bases_low_mapq, UVC_READPROF_bases_no_ref,
+                          UVC_READPROF_bases_n, UVC_READPROF_bases_low_depth, UVC_READPROF_bases_high_alt, UVC_READPROF_bases_clean,
+                          UVC_READPROF_positions_no_ref, UVC_READPROF_positions_low_depth, UVC_READPROF_positions_high_alt,
+                          UVC_READPROF_positions_clean, UVC_READPROF_reserved, UVC_NREADPROF };
+enum { UVC_READPROF_NCLASS = 4, UVC_READPROF_NQUAL = 64, UVC_READPROF_NCYCLE = 256, UVC_READPROF_NKIND = 5 /* match mismatch ins del clip */,
+       UVC_READPROF_Q_BINS = 0, UVC_READPROF_CYC_BINS = 512 /* 4 * 64 * 2 */, UVC_READPROF_SUB_BINS = 5632 /* + 4 * 256 * 5 */,
+       UVC_READPROF_COUNTERS = 5696 /* + 4 * 4 * 4 */, UVC_READPROF_NCOUNTER = 16, UVC_READPROF_ROW = 5712 /* + 16 */ };
+typedef struct UvcReadProfileRequest { int32_t min_mapq, min_depth, max_alt_permille; } UvcReadProfileRequest;
+/* Reduced on the device in two passes over the read bases; integers only, the same bits from call to call.  Ranges: those of
+ * uvcgpu_region_coverage (zero-based, half open, sorted, disjoint, inside [beg, end + 1)).  Legal where uvcgpu_region_family_stats is:
+ * from uvcgpu_region_set_reads / _set_reads_device of the current region on (zero reads: only the positions_* words are non-zero), with or
+ * without accumulate, after any score and while a score stream is open.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason: called before set_reads or after a reset; NULL ranges, req or
+ *   out; a range list that uvcgpu_region_coverage refuses; min_mapq outside 0..255; min_depth < 1; max_alt_permille outside 0..1000.  `out`
+ *   is written only by a call that returns 0. */
+int uvcgpu_region_read_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcReadProfileRequest *req,
+                               int64_t *out /* [UVC_READPROF_ROW] */);
+const char *uvcgpu_read_class_name(int32_t c);   /* "R1_fwd" "R1_rev" "R2_fwd" "R2_rev"; NULL for a class outside 0..3 */
 /* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
  * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
  * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when

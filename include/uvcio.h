@@ -210,6 +210,19 @@ int64_t uvcio_famstats_add_target(uvcio_famstats_t *f, const char *chrom, int64_
 int uvcio_famstats_add_piece(uvcio_famstats_t *f, int64_t target, const int64_t *row /* [365] */);
 int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path);
 void uvcio_famstats_close(uvcio_famstats_t *f);
+/* ---- the read profile (uvc1-mi355x --read-profile-out) ----
+ * The sum of the rows that tiles report with uvcgpu_region_read_profile (5712 int64: Q[4][64][2], CYC[4][256][5], SUB[4][4][4], 16 counters);
+ * rows of disjoint position sets add, so add() sums under a lock, from any thread in any order.  write(): "##read_profile_min_mapq=",
+ * "##read_profile_min_depth=", "##read_profile_max_alt_permille=" and "##empirical_quality=-10*log10((mismatch+1)/(match+mismatch+2))" (the
+ * quality a bin's counts stand for; left to the reader, the file holds integers only); "#counter\tcount" and the ten counters;
+ * "#class\tquality\tmatch\tmismatch" and one line per (class, quality bin) that is not empty; "#class\tcycle\tmatch\tmismatch\tins\tdel\tclip"
+ * likewise per (class, cycle bin); "#class\tref\tread\tcount" per non-zero substitution bin.  Class, quality and cycle ascend.  A path that
+ * ends in .gz is written block-gzipped (uvcio_bgzf_write_*). */
+typedef struct uvcio_readprofile uvcio_readprofile_t;
+int uvcio_readprofile_open(uvcio_readprofile_t **out, const char *const *class_names /* [4] */, int32_t min_mapq, int32_t min_depth, int32_t max_alt_permille);
+int uvcio_readprofile_add(uvcio_readprofile_t *p, const int64_t *row /* [5712] */);
+int uvcio_readprofile_write(const uvcio_readprofile_t *p, const char *path);
+void uvcio_readprofile_close(uvcio_readprofile_t *p);
 /* ---- the callable-region BED (uvc1-mi355x --callable-out) ----
  * The targets in report order and, per target, the runs that tiles report for its pieces with uvcgpu_region_callable.  add_runs takes the
  * runs of one call as they came back and the target of each of the call's ranges, under a lock: pieces come in any order and from any

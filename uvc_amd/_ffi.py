@@ -83,6 +83,10 @@ class UvcErrorProfileRequest(C.Structure):
     _fields_ = [("min_depth", C.c_int32), ("max_alt_permille", C.c_int32)]
 
 
+class UvcReadProfileRequest(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("min_depth", C.c_int32), ("max_alt_permille", C.c_int32)]
+
+
 class UvcFamilyRange(C.Structure):
     _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("prev_end", C.c_int32), ("flags", C.c_int32)]
 
@@ -163,6 +167,19 @@ FAMSTAT_SECTIONS = _read_famstats_def()
 FAMILY_STATS = [n for n, _, _ in FAMSTAT_SECTIONS]
 assert [ENUMS["UVC_FAMSTAT_" + n] for n in FAMILY_STATS] == list(range(ENUMS["UVC_NFAMSTAT"]))
 assert sum(w for _, _, w in FAMSTAT_SECTIONS) == ENUMS["UVC_FAMSTAT_ROW"] and all(f == sum(w for _, _, w in FAMSTAT_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMSTAT_SECTIONS))
+
+
+def _read_readprofile_def():
+    """The sections of a row of uvcgpu_region_read_profile: (name, first word, words) per row of include/uvc_readprofile.def."""
+    with open(os.path.join(ROOT, "include", "uvc_readprofile.def")) as fh:
+        rows = [re.match(r"UVC_READPROF\((\w+),\s*(\d+),\s*(\d+)\)\s*$", line) for line in fh]
+    return [(m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
+
+
+# the sections of a read-profile row in id order (UvcReadProfSection): the table of include/uvc_readprofile.def, checked against the header's enums
+READPROF_SECTIONS = _read_readprofile_def()
+assert [ENUMS["UVC_READPROF_" + n] for n, _, _ in READPROF_SECTIONS] == list(range(ENUMS["UVC_NREADPROF"]))
+assert sum(w for _, _, w in READPROF_SECTIONS) == ENUMS["UVC_READPROF_ROW"] and all(f == sum(w for _, _, w in READPROF_SECTIONS[:k]) for k, (_, f, _) in enumerate(READPROF_SECTIONS))
 
 
 def _read_callable_def():

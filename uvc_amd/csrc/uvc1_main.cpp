@@ -63,6 +63,9 @@ struct Opts {
     uvcio_callable_t *callable = nullptr;   // the BED's store, filled by the workers (main)
     std::vector<int64_t> call_contig_target;   // without a BED file: per contig the store's target of its called span (-1: not called)
     std::vector<std::pair<int64_t, int64_t>> call_target_span;   // per target of the store its [beg, end): a tile's stretch is clipped to it
+    std::string readprof_out;    // --read-profile-out PATH: the base-quality and cycle profile of the reads; empty = none
+    UvcReadProfileRequest readprof_req{ 0, 20, 50 }; bool readprof_gate_given = false;   // --read-profile-min-mapq, --read-profile-min-depth, --read-profile-max-alt-permille
+    uvcio_readprofile_t *readprof = nullptr;   // the run's row, summed over the tiles by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -118,6 +121,10 @@ const OptRow OPTS[] = {
     { "--callable-out", O_CLI, false, "", "write the callable regions here as BED lines contig, beg, end, class, target (tab-separated; block-gzipped when the name ends in .gz): every target -- BED line, or called contig span without a BED file -- cut into stretches of equal class, CALLABLE or the criteria the stretch fails (LOW_<depth>, EXCESS_aDP, NO_COVERAGE), classified on the device from the planes of each tile over the six depths of --coverage-out; #summary lines count the positions per class.  The VCF does not depend on it" },
     { "--callable-min-depth", O_CLI, false, "cDP12=20", "with --callable-out: NAME=N[,NAME=N...], the smallest depth a callable position has of each named depth (aDP bDP cDP1 cDP12 cDP2 dDP1; 0 or unnamed: not tested)" },
     { "--callable-max-aDP", O_CLI, false, "0", "with --callable-out: the largest raw depth aDP a callable position has (0: not tested)" },
+    { "--read-profile-out", O_CLI, false, "", "write the read profile here (tab-separated; block-gzipped when the name ends in .gz): per read class (R1 / R2, forward / reverse) the matches and mismatches by reported base quality, the matches, mismatches, inserted bases, deletions and soft-clipped bases by sequencing cycle and the substitution matrix, at positions that do not look variant, reduced on the device from the read bases of each tile over the positions the tile owns, with the BAM's own qualities.  The VCF does not depend on it" },
+    { "--read-profile-min-mapq", O_CLI, false, "0", "with --read-profile-out: only alignments of at least this mapping quality are counted (0..255)" },
+    { "--read-profile-min-depth", O_CLI, false, "20", "with --read-profile-out: a base enters the bins only where at least this many counted A/C/G/T bases cover the position (1 or more)" },
+    { "--read-profile-max-alt-permille", O_CLI, false, "50", "with --read-profile-out: a position whose mismatching bases are above this many thousandths of its depth counts as variant and stays out of the bins (0..1000)" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -195,7 +202,7 @@ bool number(const std::string &s, double *v) {   // a whole decimal number, or t
     char *e = nullptr; *v = strtod(s.c_str(), &e); return *e == 0 && std::isfinite(*v);
 }
 
-// What the report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out) share on the command line.  Each option
+// What the report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out) share on the command line.  Each option
 // gives its own words for why; the sentences are these.
 int64_t window_length(const std::string &opt, const std::string &v) {   // --coverage-window, --family-stats-window
     double x;
@@ -333,6 +340,10 @@ Opts parse(int argc, char **argv) {
             }
         }
         else if (n0 == "--callable-max-aDP") { const std::string v = val(); double x; if (v.find_first_not_of("0123456789") != std::string::npos || !number(v, &x) || x > 2e9) die("--callable-max-aDP takes a depth (0 = off), not '" + v + "'"); o.call_req.max_aDP = (int32_t)x; o.call_req_given = true; }
+        else if (n0 == "--read-profile-out") { o.readprof_out = val(); if (o.readprof_out.empty()) die("--read-profile-out needs a path"); }
+        else if (n0 == "--read-profile-min-mapq") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 255) die("--read-profile-min-mapq takes a mapping quality from 0 to 255, not '" + v + "'"); o.readprof_req.min_mapq = (int32_t)x; o.readprof_gate_given = true; }
+        else if (n0 == "--read-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--read-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.readprof_req.min_depth = (int32_t)x; o.readprof_gate_given = true; }
+        else if (n0 == "--read-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--read-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.readprof_req.max_alt_permille = (int32_t)x; o.readprof_gate_given = true; }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -394,6 +405,9 @@ Opts parse(int argc, char **argv) {
     if (o.callable_out.empty()) {
         if (o.call_req_given) die("--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file");
     } else refuse_report_runs(o, "--callable-out", "a target can straddle shards", "every tile would report its runs that many times");
+    if (o.readprof_out.empty()) {
+        if (o.readprof_gate_given) die("--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report");
+    } else refuse_report_runs(o, "--read-profile-out", "every shard would write a part of the profile", "every tile would be counted that many times");
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -437,6 +451,7 @@ struct Worker {
     std::vector<UvcCoverageRange> cov_ranges; std::vector<int64_t> cov_targets, cov_rows;   // --coverage-out: the pieces of one tile
     std::vector<UvcCoverageRange> err_ranges;   // --error-profile-out: the stretches one tile owns
     std::vector<UvcFamilyRange> fam_ranges; std::vector<int64_t> fam_targets, fam_rows;   // --family-stats-out: the pieces of one tile
+    std::vector<UvcCoverageRange> rp_ranges; std::vector<int64_t> rp_row;   // --read-profile-out: the stretches one tile owns, its row
     std::vector<UvcCoverageRange> call_ranges; std::vector<int64_t> call_targets; std::vector<UvcCallableRun> call_runs;   // --callable-out: the pieces of one tile, their runs
 };
 
@@ -469,6 +484,16 @@ void errprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
     int64_t prof[UVC_NERRLEVEL * UVC_ERR_ROW];
     if (uvcgpu_region_error_profile(w.reg, w.err_ranges.data(), (int64_t)w.err_ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
     if (uvcio_errprofile_add(o.errprof, prof)) die(uvcio_last_error());
+}
+// --read-profile-out: the profile of the reads over the stretches one tile owns -- the list coverage_of_tile reports on -- by one
+// uvcgpu_region_read_profile after set_reads, added to the run's row.
+void readprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own) {
+    w.rp_ranges.clear();
+    for (const auto &q : own) if (q.second > q.first) w.rp_ranges.push_back(UvcCoverageRange{ (int32_t)q.first, (int32_t)q.second });
+    if (w.rp_ranges.empty()) return;
+    w.rp_row.resize((size_t)UVC_READPROF_ROW);
+    if (uvcgpu_region_read_profile(w.reg, w.rp_ranges.data(), (int64_t)w.rp_ranges.size(), &o.readprof_req, w.rp_row.data())) die(uvcgpu_last_error());
+    if (uvcio_readprofile_add(o.readprof, w.rp_row.data())) die(uvcio_last_error());
 }
 // --callable-out: the runs of the stretches one accumulated tile owns -- the list coverage_of_tile reports on -- by one
 // uvcgpu_region_callable (sizes first: the buffer of the last tiles, grown where a tile has more runs), handed to the store with each
@@ -587,15 +612,20 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (uvcgpu_region_set_reads(w.reg, &rs)) die(uvcgpu_last_error());
     w.t_reads += now() - t0; t0 = now();
     if (o.fam && fam_pieces) family_stats_of_tile(w, o, fam_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --family-stats-out: the units of set_reads, before anything else
-    if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
-    if (o.cov || o.errprof || o.callable) {   // --coverage-out, --error-profile-out, --callable-out: the positions this tile owns -- the [first, last_excl) that scoring and uvcio_sites_fetch go by, without the end
-                   // point t.end itself, which lies outside every target the tile was cut from (and which two regions of the reference's cuts share)
-        std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
+    // --coverage-out, --error-profile-out, --callable-out, --read-profile-out: the positions this tile owns -- the [first, last_excl) that scoring and
+    // uvcio_sites_fetch go by, without the end point t.end itself, which lies outside every target the tile was cut from (and which two regions of
+    // the reference's cuts share).  The list depends on scored() alone: made here, in front of accumulate, for the report of the reads as well.
+    std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
+    if (o.cov || o.errprof || o.callable || o.readprof) {
         auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !o.callable ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
         for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) {   // (n_merged = 0: t0_ alone)
             const Tile &l = (&t0_)[q];
             own.emplace_back(scored(l).first, std::min(scored(l).second, l.end)); target_of.push_back(l.target); call_target_of.push_back(call_target(l));
         }
+    }
+    if (o.readprof) readprofile_of_tile(w, o, own);   // the BAM's own qualities: in front of the correction
+    if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
+    if (o.cov || o.errprof || o.callable) {
         if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
         if (o.errprof) errprofile_of_tile(w, o, own);
         if (o.callable) callable_of_tile(w, o, own, call_target_of);
@@ -979,6 +1009,7 @@ PairArgs split_pair(int argc, char **argv) {
         no_report({ "--error-profile-out", "--error-profile-min-depth", "--error-profile-max-alt-permille" }, "error profile");
         no_report({ "--callable-out", "--callable-min-depth", "--callable-max-aDP" }, "callable regions");
         no_report({ "--family-stats-out", "--family-stats-window" }, "family report");
+        no_report({ "--read-profile-out", "--read-profile-min-mapq", "--read-profile-min-depth", "--read-profile-max-alt-permille" }, "read profile");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
             die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
@@ -1256,6 +1287,10 @@ int main(int argc, char **argv) {
         for (int32_t b = 0; b < UVC_NCALLBIT; b++) bnames[b] = uvcgpu_callable_bit_name(b);
         if (uvcio_callable_open(&o.callable, mnames, UVC_NCOV, o.call_req.min_depth, o.call_req.max_aDP, bnames, UVC_NCALLBIT)) die(uvcio_last_error());
     }
+    if (!o.readprof_out.empty() && !o.print_params) {
+        const char *cnames[UVC_READPROF_NCLASS]; for (int32_t c = 0; c < UVC_READPROF_NCLASS; c++) cnames[c] = uvcgpu_read_class_name(c);
+        if (uvcio_readprofile_open(&o.readprof, cnames, o.readprof_req.min_mapq, o.readprof_req.min_depth, o.readprof_req.max_alt_permille)) die(uvcio_last_error());
+    }
     std::vector<CovSpan> fam_spans((size_t)nref);
     if (!o.famstats_out.empty() && !o.print_params && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
     std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans);
@@ -1314,6 +1349,7 @@ int main(int argc, char **argv) {
     if (o.fam) probe_create("--family-stats-out", o.famstats_out);
     if (o.callable) probe_create("--callable-out", o.callable_out);
     if (o.errprof) probe_create("--error-profile-out", o.errprof_out);
+    if (o.readprof) probe_create("--read-profile-out", o.readprof_out);
     if (!o.no_header) {
         const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
@@ -1368,6 +1404,7 @@ int main(int argc, char **argv) {
         finish("--callable-out", uvcio_callable_write(o.callable, o.callable_out.c_str())); uvcio_callable_close(o.callable);
     }
     if (o.errprof) { finish("--error-profile-out", uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())); uvcio_errprofile_close(o.errprof); }
+    if (o.readprof) { finish("--read-profile-out", uvcio_readprofile_write(o.readprof, o.readprof_out.c_str())); uvcio_readprofile_close(o.readprof); }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

@@ -79,7 +79,7 @@ struct uvcgpu_region {
     int32_t *d_score_fields = nullptr; int64_t score_capacity = 0; int64_t *d_score_count = nullptr;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     int32_t *d_score_kept = nullptr; int64_t score_kept_capacity = 0;   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields
-    char *d_report = nullptr; size_t d_report_bytes = 0; char *h_report = nullptr; size_t h_report_bytes = 0;   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable): range list + pieces on the device, page-locked result (grown on demand)
+    char *d_report = nullptr; size_t d_report_bytes = 0; char *h_report = nullptr; size_t h_report_bytes = 0;   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1415,15 +1415,15 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats and _callable ----
-// What the four share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable and _read_profile ----
+// What the five share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
 // belong to the reads of the handle and are there from set_reads on, whatever was scored since.
-static int report_guard(const uvcgpu_region_t *r, const std::string &call, const char *planes_to) {
+static int report_guard(const uvcgpu_region_t *r, const std::string &call, const char *planes_to, const char *reads_give = "family units") {
     if (!r) return fail(UVCGPU_EINVAL, call + ": null region");
-    if (!planes_to) return r->reads_given ? 0 : fail(UVCGPU_EINVAL, call + " before set_reads: the region has no family units yet (uvcgpu_region_set_reads or _set_reads_device of this region comes first)");
+    if (!planes_to) return r->reads_given ? 0 : fail(UVCGPU_EINVAL, call + " before set_reads: the region has no " + reads_give + " yet (uvcgpu_region_set_reads or _set_reads_device of this region comes first)");
     if (!r->accumulated) return fail(UVCGPU_EINVAL, call + " before accumulate: there are no planes to " + planes_to);
     if (r->state_released) return fail(UVCGPU_EINVAL, call + " after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
     if (stream_is_open(r)) return fail(UVCGPU_EINVAL, call + " while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
@@ -1583,6 +1583,47 @@ int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges,
     return guarded("uvcgpu_region_family_stats", [&] { return uvcgpu_region_family_stats_impl(r, ranges, n_ranges, out); });
 }
 const char *uvcgpu_family_stat_name(int32_t id) { return uvc_famstats_name(id); }
+
+// ---- base-quality and cycle profile of the reads over ranges (uvc_readprofile.hip): [table] [D, X: 2 x npos int32] [status: npos bytes]
+// [profile copies: the result row and the shard copies] [scratch ints: the chunk prefix of the alignments and the tile sums of the scans] ----
+// The read columns, bases, qualities and CIGARs belong to the reads of the handle as the family units do: the legality is that of
+// uvcgpu_region_family_stats.  Without reads the status stage runs on zero depths and the row holds positions_* alone.
+static int uvcgpu_region_read_profile_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcReadProfileRequest *req, int64_t *out) {
+    { int rc1 = report_guard(r, "read_profile", nullptr, "reads"); if (rc1) return rc1; }
+    if (!ranges || !req || !out) return fail(UVCGPU_EINVAL, "read_profile: ranges, req and out must not be NULL");
+    if (req->min_mapq < 0 || req->min_mapq > 255) return fail(UVCGPU_EINVAL, "read_profile: min_mapq " + std::to_string(req->min_mapq) + " is outside 0..255");
+    if (req->min_depth < 1) return fail(UVCGPU_EINVAL, "read_profile: min_depth " + std::to_string(req->min_depth) + " must be at least 1");
+    if (req->max_alt_permille < 0 || req->max_alt_permille > 1000) return fail(UVCGPU_EINVAL, "read_profile: max_alt_permille " + std::to_string(req->max_alt_permille) + " is outside 0..1000");
+    { int rc1 = range_count("read_profile", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "read_profile", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
+    const int64_t n_alns = r->has_reads ? r->R.n_alns : 0;
+    RegionDev R0 = r->R; if (!r->has_reads) R0.n_alns = 0;   // (the read pointers of an earlier region are gone)
+    const size_t npos = (size_t)r->npos, out_bytes = sizeof(int64_t) * UVC_READPROF_ROW, copies = 1 + (size_t)uvc_readprofile_copies();
+    ReportLayout L;
+    const size_t o_tab = L.take(sizeof(UvcRangeRow) * tab.size()), o_dx = L.take(sizeof(int32_t) * 2 * npos), o_status = L.take(npos), o_prof = L.take(out_bytes * copies);
+    const size_t o_scratch = L.take(sizeof(int32_t) * (size_t)uvc_readprofile_scratch_ints(n_alns, r->npos));
+    { int rc1 = report_begin(r, L, out_bytes, "read profile", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+    int32_t *d_dx = (int32_t *)(r->d_report + o_dx), *d_x = d_dx + npos, *d_scratch = (int32_t *)(r->d_report + o_scratch);
+    uint8_t *d_status = (uint8_t *)(r->d_report + o_status);
+    long long *d_prof = (long long *)(r->d_report + o_prof), *d_parts = d_prof + UVC_READPROF_ROW;
+    HIP_OK(hipMemsetAsync(r->d_report + o_dx, 0, o_scratch - o_dx, r->stream));   // D, X, status, the copies
+    // with profiling on, three more entries of uvcgpu_region_kernel_times (accumulate starts the list anew)
+    int pi = uvc_prof_begin(&r->prof, "k_readprofile_depth", r->stream);
+    uvc_launch_readprofile_depth(&R0, &r->W, r->n_bases, req->min_mapq, d_dx, d_x, d_scratch, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    pi = uvc_prof_begin(&r->prof, "k_readprofile_status", r->stream);
+    uvc_launch_readprofile_status(&R0, (const UvcRangeRow *)(r->d_report + o_tab), (int)n_ranges, req->min_depth, req->max_alt_permille, d_dx, d_x, d_status, d_parts, d_scratch, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    pi = uvc_prof_begin(&r->prof, "k_readprofile_bin", r->stream);
+    uvc_launch_readprofile_bin(&R0, &r->W, r->n_bases, req->min_mapq, d_status, d_parts, d_prof, d_scratch, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    return report_result(r, d_prof, out, out_bytes, false);
+}
+int uvcgpu_region_read_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcReadProfileRequest *req, int64_t *out) {
+    return guarded("uvcgpu_region_read_profile", [&] { return uvcgpu_region_read_profile_impl(r, ranges, n_ranges, req, out); });
+}
+const char *uvcgpu_read_class_name(int32_t c) { return uvc_readprofile_class_name(c); }
 
 // ---- callable-region intervals of ranges (uvc_callable.hip): [table] [block counts] [mask bytes] [runs, one per position at worst] ----
 // Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit

@@ -1209,7 +1209,7 @@ extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t po
 extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }
 
 // ---------------------------------------------------------------- the report stores ----
-// What the stores of --coverage-out, --error-profile-out, --family-stats-out and --callable-out share: a store collects what the tiles
+// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out and --read-profile-out share: a store collects what the tiles
 // report under its mutex and writes the whole file at the end.
 // a target as the stores with target lines keep it; a BED line without a name is "."
 struct ReportTarget { std::string chrom, name; int64_t beg, end; };
@@ -1347,6 +1347,64 @@ extern "C" int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *p
     return write_text(path, text);
 }
 extern "C" void uvcio_errprofile_close(uvcio_errprofile_t *e) { delete e; }
+
+// ---------------------------------------------------------------- the read profile ----
+// the row layout is that of uvcgpu_region_read_profile (UVC_READPROF_* of uvcgpu.h, include/uvc_readprofile.def); the reserved words are not written
+struct uvcio_readprofile {
+    std::string classes[UVC_READPROF_NCLASS]; int32_t min_mapq, min_depth, max_alt_permille;
+    int64_t sum[UVC_READPROF_ROW];
+    std::mutex mu;
+};
+extern "C" int uvcio_readprofile_open(uvcio_readprofile_t **out, const char *const *class_names, int32_t min_mapq, int32_t min_depth, int32_t max_alt_permille) {
+    if (!out || !class_names) return fail(UVCGPU_EINVAL, "read profile: bad argument");
+    uvcio_readprofile *p = new uvcio_readprofile;
+    for (int c = 0; c < UVC_READPROF_NCLASS; c++) p->classes[c] = class_names[c] ? class_names[c] : "";
+    p->min_mapq = min_mapq; p->min_depth = min_depth; p->max_alt_permille = max_alt_permille;
+    memset(p->sum, 0, sizeof(p->sum));
+    *out = p;
+    return 0;
+}
+extern "C" int uvcio_readprofile_add(uvcio_readprofile_t *p, const int64_t *row) {
+    if (!p || !row) return fail(UVCGPU_EINVAL, "read profile: bad argument");
+    std::lock_guard<std::mutex> g(p->mu);
+    for (int i = 0; i < UVC_READPROF_ROW; i++) p->sum[i] += row[i];
+    return 0;
+}
+extern "C" int uvcio_readprofile_write(const uvcio_readprofile_t *p, const char *path) {
+    if (!p || !path || !*path) return fail(UVCGPU_EINVAL, "read profile: bad argument");
+    static const char *const COUNTERS[] = {
+#define UVC_READPROF(name, first, words) #name,
+#include "uvc_readprofile.def"
+#undef UVC_READPROF
+    };
+    static const char *const BASE_SYM[4] = { "A", "C", "G", "T" };
+    std::string text = "##read_profile_min_mapq=" + std::to_string(p->min_mapq) + "\n##read_profile_min_depth=" + std::to_string(p->min_depth) + "\n##read_profile_max_alt_permille=" + std::to_string(p->max_alt_permille)
+                       + "\n##empirical_quality=-10*log10((mismatch+1)/(match+mismatch+2))\n#counter\tcount\n";
+    for (int k = UVC_READPROF_bases_low_mapq; k < UVC_READPROF_reserved; k++) text += std::string(COUNTERS[k]) + "\t" + std::to_string(p->sum[UVC_READPROF_COUNTERS + k - UVC_READPROF_bases_low_mapq]) + "\n";
+    auto lines = [&](const char *head, int first, int bins, int width) {   // one line per (class, bin) with a non-zero word
+        text += head;
+        for (int c = 0; c < UVC_READPROF_NCLASS; c++)
+            for (int b = 0; b < bins; b++) {
+                const int64_t *v = p->sum + first + (c * bins + b) * width;
+                bool any = false;
+                for (int j = 0; j < width; j++) any = any || v[j] != 0;
+                if (!any) continue;
+                text += p->classes[c] + "\t" + std::to_string(b);
+                for (int j = 0; j < width; j++) text += "\t" + std::to_string(v[j]);
+                text += "\n";
+            }
+    };
+    lines("#class\tquality\tmatch\tmismatch\n", UVC_READPROF_Q_BINS, UVC_READPROF_NQUAL, 2);
+    lines("#class\tcycle\tmatch\tmismatch\tins\tdel\tclip\n", UVC_READPROF_CYC_BINS, UVC_READPROF_NCYCLE, UVC_READPROF_NKIND);
+    text += "#class\tref\tread\tcount\n";
+    for (int c = 0; c < UVC_READPROF_NCLASS; c++)
+        for (int k = 0; k < 16; k++) {
+            const int64_t v = p->sum[UVC_READPROF_SUB_BINS + c * 16 + k];
+            if (v) text += p->classes[c] + "\t" + BASE_SYM[k >> 2] + "\t" + BASE_SYM[k & 3] + "\t" + std::to_string(v) + "\n";
+        }
+    return write_text(path, text);
+}
+extern "C" void uvcio_readprofile_close(uvcio_readprofile_t *p) { delete p; }
 
 // ---------------------------------------------------------------- the UMI family report ----
 // the row layout is that of uvcgpu_region_family_stats (UVC_FAMSTAT_* of uvcgpu.h, include/uvc_famstats.def); the reserved word is not written

@@ -104,6 +104,17 @@ int64_t uvc_errprofile_scratch_cells(void);
 // n_ranges rows; d_rows: n_ranges rows of UVC_FAMSTAT_ROW words ----
 void uvc_launch_famstats(const RegionDev *R, const int32_t *pos, const int32_t *endpos, const int32_t *fs_of, UvcUnitSpan *d_span, const UvcFamilyRange *d_ranges, int n_ranges, long long *d_rows, hipStream_t s);
 const char *uvc_famstats_name(int id);
+// ---- uvc_readprofile.hip: three stages, each one entry of uvcgpu_region_kernel_times.  d_dx / d_x: npos ints each (zero at the start: the depth
+// differences, on return of the status stage the depth; the mismatches); d_status: npos bytes; d_parts: uvc_readprofile_copies() rows of
+// UVC_READPROF_ROW words, zero at the start; d_out: one row; d_scratch: uvc_readprofile_scratch_ints(n_alns, npos) ints.  A handle without
+// reads runs the status stage and the fold of the bin stage alone ----
+void uvc_launch_readprofile_depth(const RegionDev *R, const RawReads *W, int64_t n_bases, int min_mapq, int32_t *d_dx, int32_t *d_x, int32_t *d_scratch, hipStream_t s);
+void uvc_launch_readprofile_status(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int min_depth, int max_alt_permille, int32_t *d_dx, const int32_t *d_x, uint8_t *d_status,
+                                   long long *d_parts, int32_t *d_scratch, hipStream_t s);
+void uvc_launch_readprofile_bin(const RegionDev *R, const RawReads *W, int64_t n_bases, int min_mapq, const uint8_t *d_status, long long *d_parts, long long *d_out, const int32_t *d_scratch, hipStream_t s);
+const char *uvc_readprofile_class_name(int c);
+int64_t uvc_readprofile_copies(void);
+int64_t uvc_readprofile_scratch_ints(int64_t n_alns, int64_t npos);
 // ---- uvc_callable.hip: d_tab = n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one the
 // number of runs once the count has run; d_runs: room for that many runs.  The emit follows a count with the same arguments ----
 void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s);

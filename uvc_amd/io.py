@@ -218,6 +218,43 @@ class FamilyStats:
         self.close()
 
 
+class ReadProfile:
+    """uvcio_readprofile_*: the store behind uvc1-mi355x --read-profile-out.  add() sums one row of Region.read_profile (any thread, any
+    order: rows of disjoint position sets add); write() makes the text."""
+
+    def __init__(self, classes, min_mapq=0, min_depth=20, max_alt_permille=50):
+        d = dll()
+        d.uvcio_readprofile_open.restype, d.uvcio_readprofile_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32]
+        d.uvcio_readprofile_add.restype, d.uvcio_readprofile_add.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        d.uvcio_readprofile_write.restype, d.uvcio_readprofile_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
+        d.uvcio_readprofile_close.restype, d.uvcio_readprofile_close.argtypes = None, [C.c_void_p]
+        if len(classes) != 4:
+            raise ValueError("the read classes are four (region.READ_CLASSES)")
+        self.h = C.c_void_p()
+        _check(d.uvcio_readprofile_open(C.byref(self.h), (C.c_char_p * 4)(*[c.encode() for c in classes]), int(min_mapq), int(min_depth), int(max_alt_permille)))
+
+    def add(self, row):
+        import numpy as np
+        row = np.ascontiguousarray(row, dtype=np.int64)
+        if row.shape != (5712,):
+            raise ValueError("a piece is one row of Region.read_profile (5712 values)")
+        _check(dll().uvcio_readprofile_add(self.h, row.ctypes.data))
+
+    def write(self, path):
+        _check(dll().uvcio_readprofile_write(self.h, str(path).encode()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            dll().uvcio_readprofile_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class Callable:
     """uvcio_callable_*: the store behind uvc1-mi355x --callable-out.  Targets are added in report order with their positions inside the
     contig; add_runs takes the runs of one Region.callable and the target of each of its ranges (any thread, any order); write() sorts,

@@ -26,6 +26,7 @@ class UvcError(RuntimeError):
 COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
 CALLABLE_BITS = _ffi.CALLABLE_BITS           # the bits of a mask of Region.callable, in bit order (include/uvc_callable.def)
 FAMILY_STATS = _ffi.FAMILY_STATS             # the sections of a row of Region.family_stats, in row order (include/uvc_famstats.def)
+READ_CLASSES = ["R1_fwd", "R1_rev", "R2_fwd", "R2_rev"]   # the read classes of Region.read_profile, in row order (uvcgpu_read_class_name)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
 CALLABLE_RUN = np.dtype([("range", np.int32), ("pos_beg", np.int32), ("pos_end", np.int32), ("mask", np.int32)])   # UvcCallableRun
 
@@ -517,6 +518,21 @@ class Region:
         arr = (_ffi.UvcFamilyRange * max(len(rows), 1))(*[_ffi.UvcFamilyRange(*q) for q in rows])
         out = np.zeros((len(rows), _ffi.ENUMS["UVC_FAMSTAT_ROW"]), dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), out.ctypes.data))
+        return out
+
+    def read_profile(self, ranges, min_mapq=0, min_depth=20, max_alt_permille=50):
+        """uvcgpu_region_read_profile: the base-quality, cycle and substitution profile of the region's reads over `ranges` (as Region.coverage
+        takes them), reduced on the device from the read bases.  int64 [UVC_READPROF_ROW]: Q[4][64][2] (class of READ_CLASSES, quality bin,
+        match / mismatch), CYC[4][256][5] (class, cycle bin, match / mismatch / ins / del / clip), SUB[4][4][4] (class, reference base, read
+        base) and 16 counters (_ffi.READPROF_SECTIONS names the sections, uvcgpu.h has the rules).  An alignment counts with
+        mapq >= min_mapq; a base enters the bins at a position whose depth of counted A/C/G/T bases is >= min_depth and whose mismatches are
+        at most max_alt_permille thousandths of it.  After set_reads() / set_reads_device(); accumulate and scores neither are needed nor get
+        in the way; after correct_bq() the qualities are the corrected ones."""
+        fn = self._ranges_fn("region_read_profile", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+        arr, rows = _coverage_ranges(ranges)
+        req = _ffi.UvcReadProfileRequest(int(min_mapq), int(min_depth), int(max_alt_permille))
+        out = np.zeros(_ffi.ENUMS["UVC_READPROF_ROW"], dtype=np.int64)
+        self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data))
         return out
 
     def callable(self, ranges, min_depth=None, max_aDP=0):

@@ -42,8 +42,10 @@ def _pack(op, ln):
 
 def generate_region(seed=12345, region_len=10000, depth=30, tid=19, beg=1000000, umi=False,
                     fam_mean=4.0, duplex_frac=0.6, snv_every=1000, somatic_every=10000, indel_every=5000,
-                    err_rate=1e-3, clip_frac=0.01, dedup_by_position=True):
-    """Returns a dict: refseq (str), tid, beg, end and the UvcReadSoA arrays (numpy)."""
+                    err_rate=1e-3, clip_frac=0.01, dedup_by_position=True, variant_inset=500):
+    """Returns a dict: refseq (str), tid, beg, end and the UvcReadSoA arrays (numpy).  Variants are planted from `variant_inset` behind the
+    first read position to as far in front of the last (at least 100: a site is moved up to 199 bp on); a region shorter than twice that
+    gets none unless the inset is lowered."""
     rng = np.random.default_rng(seed)
     n = int(region_len) + 2 * HALO
     ref = make_reference(rng, n)
@@ -66,14 +68,14 @@ def generate_region(seed=12345, region_len=10000, depth=30, tid=19, beg=1000000,
 
     # ---- variants (relative coordinates) ----
     variants = []  # (pos, kind, arg, af)
-    for p in (range(lo + 500, hi - 500, snv_every) if snv_every else ()):
+    for p in (range(lo + variant_inset, hi - variant_inset, snv_every) if snv_every else ()):
         q = p + int(rng.integers(0, 200))
         variants.append((q, "snv", int((ref[q] + 1 + rng.integers(0, 3)) % 4), 0.5))
-    for p in (range(lo + 700, hi - 500, somatic_every) if somatic_every else ()):
+    for p in (range(lo + variant_inset + 200, hi - variant_inset, somatic_every) if somatic_every else ()):
         q = p + int(rng.integers(0, 200))
         variants.append((q, "snv", int((ref[q] + 1 + rng.integers(0, 3)) % 4), float(rng.uniform(0.02, 0.1))))
     k = 0
-    for p in (range(lo + 900, hi - 500, indel_every) if indel_every else ()):
+    for p in (range(lo + variant_inset + 400, hi - variant_inset, indel_every) if indel_every else ()):
         q = p + int(rng.integers(0, 200))
         kind = ("del", "ins")[k % 2]
         ln = (1, 3)[(k // 2) % 2]
