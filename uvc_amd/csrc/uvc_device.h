@@ -50,17 +50,20 @@ struct AlnRec {
     int64_t baq_pos, baq_last, baq2_last;   // baq[pos], baq[rend-1], baq2[rend-1] (region constants, main.hpp:1394-1396)
 };
 
-// 64-byte digest of a simple alignment for the position-centric kernels, stored pos-sorted.  A wave loads 64 consecutive
+// 64-byte digest of a simple alignment (or of one M run of an InDel read) for the position-centric kernels, stored pos-sorted per class.  A wave loads 64 consecutive
 // records (one per lane, coalesced) and broadcasts the fields of record j with v_readlane, so the per-read scalars never
 // cost a dependent memory round trip inside the loop.
 struct FastRec {
     int32_t pos, rend, qb_lo, aln;          // [pos, rend): covered positions (the whole read, or one M run of an InDel read); qb_lo: low word of
                                             // (index of the base at position p) - p; aln: index into alns[]
     int32_t fmd, isize, mpos, xm1500;       // fmd = flag | mapq << 16 | dflag << 24
-    int32_t bmv, xbv, bm4c, clips;          // bmv: a2BM2 increment (<= 100) of base symbols 0..3, one byte each; xbv: that of symbol 4 | a2XM2 increment << 8;
+    int32_t bmv, xbv, bm4c, clips;          // bmv: a2BM2 increment (<= 100) of base symbols 0..3, one byte each; xbv: that of symbol 4 | a2XM2 increment << 8 | FREC_M_RUN;
                                             // bm4c: clip_cnt << 16 | (nogap_penal & 0xFFFF); clips = lclip_oplen | rclip_oplen << 16
     int32_t baq_pos, baq_last, baq2_last, ext;   // ext: (pos - read start) | (read end - rend) << 16, zero for a whole read
 };
+// in FastRec::xbv: the entry is an M run of an InDel read, not a whole simple alignment.  (ext == 0 does not say so: the one M run of 2I58M
+// spans its whole alignment.)  P1 walks the same list as P2 and skips these entries: k_prep_slow has the read.
+#define FREC_M_RUN (1 << 16)
 
 struct FragRec {
     int32_t aln_beg, aln_end;   // alignments are stored fragment-major
@@ -157,10 +160,10 @@ struct RegionDev {
     const uint16_t *bq; uint32_t bq_bytes;   // base | qual << 8 per read base: one bounds-checked buffer load per (alignment, position)
     AlnRec *alns; int32_t n_alns;
     int32_t n_fast;                 // number of simple alignments
-    FastRec *frec;                  // [n_fast] their digests, sorted by pos (FastRec::aln: the index into alns[])
     int32_t p2_off[5];              // frec2 is four pos-sorted sub-lists [p2_off[c], p2_off[c + 1]), c = is-reverse | bam_get_strand << 1
-    FastRec *frec2; int32_t n_fast2; int32_t max_p2_span;   // P2 work list, sorted by (class, pos): simple alignments + the M runs of InDel reads whose
-                                    // InDels are all high-quality (kind 2), which behave like simple alignments in P2 (see k_p2_fast)
+    FastRec *frec2; int32_t n_fast2; int32_t max_p2_span;   // the work list of P1 and P2, sorted by (class, pos): simple alignments + the M runs of InDel reads whose
+                                    // InDels are all high-quality (kind 2), which behave like simple alignments in P2 (see k_p2_fast); P1 skips the M runs (FREC_M_RUN).
+                                    // FastRec::aln: the index into alns[]; max_p2_span: the longest entry
     const int32_t *complex_ids; int32_t n_complex;
     FragRec *frags; int32_t n_frags;
     int32_t *frag_nmut; int32_t *frag_mut;          // mutation events per fragment: count + up to UVC_MAXEV positions
@@ -171,7 +174,7 @@ struct RegionDev {
     int32_t frag_off[3];            // ffast = the strand-0 fragments sorted by beg, then the strand-1 fragments sorted by beg
     FragFast *ffast;                // [n_frags] in (strand, beg)-sorted order
     FragUnit *ffast_u;              // [n_frags] by fragment number (see FragUnit)
-    int32_t *win; int32_t nwin;     // window index [8 lists][lo, hi][nwin = ceil(npos / 64)] (k_win_index)
+    int32_t *win; int32_t nwin;     // window index [8 lists, the first one unused][lo, hi][nwin = ceil(npos / 64)] (k_win_index)
     int32_t *fsum;                  // [2 strands][UVC_FSUM_N][npos]: interval sums of the plain fragments (k_frag_sums), read by k_frag
     FsRec *fss; int32_t n_fs;
     const int32_t *generic_fs; int32_t n_generic_fs; int64_t n_generic_work;
@@ -188,7 +191,7 @@ struct RegionDev {
     Item *items; int32_t *item_cnt;     // per complex alignment (indexed like complex_ids)
     MisItem *mis; int32_t *mis_cnt; int32_t mis_cap;   // mismatch queue of k_p2_fast, sized from the exact count below
     unsigned long long *mis_total;  // number of read bases of simple alignments that differ from the reference (k_aln_prelude)
-    int32_t max_aln_span, max_frag_span;
+    int32_t max_frag_span;
     int32_t any_amplicon;           // some family carries the amplicon flag (fam_dflag & 0x4)
     int32_t frag32;                 // UVCGPU_FRAG32=1: k_frag with 32-bit buckets although the depth would allow the packed form (tests compare the two)
     int32_t max_frag_depth;         // upper bound of the number of fragments that cover one position

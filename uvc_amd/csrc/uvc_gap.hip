@@ -28,12 +28,17 @@ __global__ void __launch_bounds__(256) k_keys_pos_cls(const int32_t *pos, const 
     if (i >= n) return;
     key[i] = ((uint32_t)(pos[i] - beg) | ((uint32_t)cls[i] << shift)); val[i] = (uint32_t)i;
 }
+// The four columns of the work list in sorted order (a0 = the entry's alignment) and, per alignment, the slot of its entry: a simple
+// alignment (kind 0) has exactly one entry, every other alignment gets -1 (RawReads::fast_rank).
 __global__ void __launch_bounds__(256) k_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3,
-                                                 int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3) {
+                                                 int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3, const int32_t *kind, int64_t n_alns, int32_t *slot) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_alns && kind[i] != 0) slot[i] = -1;
     if (i >= n) return;
     const int64_t j = (int64_t)perm[i];
-    o0[i] = a0[j]; o1[i] = a1[j]; o2[i] = a2[j]; o3[i] = a3[j];
+    const int32_t id = a0[j];
+    o0[i] = id; o1[i] = a1[j]; o2[i] = a2[j]; o3[i] = a3[j];
+    if (kind[id] == 0) slot[id] = (int32_t)i;
 }
 // ids sorted by key: out_ids[k] = the k-th id, rank[id] = k for the first n_first ids (the others get -1)
 __global__ void __launch_bounds__(256) k_rank_from_sorted(const uint32_t *perm, int64_t n, int64_t n_first, int32_t *out_ids, int32_t *rank) {
@@ -59,8 +64,10 @@ extern "C" int uvc_sort_by_pos_cls(const int32_t *d_pos, const int32_t *d_cls, i
     hipLaunchKernelGGL(k_keys_pos_cls, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_pos, d_cls, beg, pos_bits, n, key, val);
     return rocprim::radix_sort_pairs(tmp, tmp_bytes, key, key_s, val, val_s, (size_t)n, 0, (unsigned)(pos_bits + cls_bits), s) == hipSuccess ? 0 : -1;
 }
-extern "C" void uvc_launch_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_gather4, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, perm, n, a0, a1, a2, a3, o0, o1, o2, o3);
+extern "C" void uvc_launch_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3,
+                                   const int32_t *kind, int64_t n_alns, int32_t *slot, hipStream_t s) {
+    const int64_t m = std::max(n, n_alns);
+    if (m > 0) hipLaunchKernelGGL(k_gather4, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, perm, n, a0, a1, a2, a3, o0, o1, o2, o3, kind, n_alns, slot);
 }
 extern "C" void uvc_launch_rank_from_sorted(const uint32_t *perm, int64_t n, int64_t n_first, int32_t *out_ids, int32_t *rank, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_rank_from_sorted, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, perm, n, n_first, out_ids, rank);

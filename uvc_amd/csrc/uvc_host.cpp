@@ -374,19 +374,15 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
       uvc_launch_pack_bq(R.bases, R.quals, b, d->n_bases, d_bad, r->stream); }
     { AlnRec *a; if ((rc = dev_alloc(r, (size_t)n, &a))) return rc; R.alns = a; R.n_alns = (int32_t)n; }
     R.n_fast = (int32_t)n_simple;
-    { FastRec *f; if ((rc = dev_alloc(r, (size_t)n_simple, &f))) return rc; R.frec = f; }
     R.complex_ids = o.complex_ids; R.n_complex = o.n_complex;
     R.frags = o.frags; R.n_frags = o.n_frags;
     int pos_bits = 1; while (((int64_t)1 << pos_bits) < r->npos + 1) pos_bits++;   // every sorted position offset is < npos: the radix passes stop there
-    {   // stable device sorts: simple alignments by begin (the others go behind them), fragments by (strand, begin) -- k_frag walks two
-        // beg-sorted sub-lists, one per strand, so that the strand-specific accumulators are fixed registers
-        const size_t nmax = std::max<size_t>(std::max<size_t>((size_t)n, nf), 1);
-        int32_t *d_rank, *d_fsorted, *d_frank; uint32_t *work; uint8_t *tmp;
+    {   // stable device sort of the fragments by (strand, begin) -- k_frag walks two beg-sorted sub-lists, one per strand, so that the
+        // strand-specific accumulators are fixed registers
+        const size_t nmax = std::max<size_t>(nf, 1);
+        int32_t *d_fsorted, *d_frank; uint32_t *work; uint8_t *tmp;
         const size_t tmp_bytes = uvc_sort32_tmp_bytes(nmax);
-        if ((rc = dev_alloc(r, (size_t)n, &d_rank)) || (rc = dev_alloc(r, nf, &d_fsorted)) || (rc = dev_alloc(r, nf, &d_frank)) || (rc = dev_alloc(r, 4 * nmax, &work)) || (rc = dev_alloc(r, tmp_bytes + 16, &tmp))) return rc;
-        if (uvc_sort_by_pos_cls(W.pos, o.is_complex, r->beg, pos_bits, 1, n, work, tmp, tmp_bytes, r->stream) != 0) return fail(UVCGPU_EDEVICE, "device sort of the alignments failed");
-        uvc_launch_rank_from_sorted(work + 3 * n, n, n_simple, nullptr, d_rank, r->stream);
-        W.fast_rank = d_rank;
+        if ((rc = dev_alloc(r, nf, &d_fsorted)) || (rc = dev_alloc(r, nf, &d_frank)) || (rc = dev_alloc(r, 4 * nmax, &work)) || (rc = dev_alloc(r, tmp_bytes + 16, &tmp))) return rc;
         if (uvc_sort_by_pos_cls(o.frag_beg, o.frag_strand, r->beg, pos_bits, 1, (int64_t)nf, work, tmp, tmp_bytes, r->stream) != 0) return fail(UVCGPU_EDEVICE, "device sort of the fragments failed");
         uvc_launch_rank_from_sorted(work + 3 * nf, (int64_t)nf, (int64_t)nf, d_fsorted, d_frank, r->stream);
         R.frag_sorted = d_fsorted; R.frag_rank = d_frank;
@@ -433,26 +429,28 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
     }
     { int32_t *c; if ((rc = dev_alloc(r, (size_t)4, &c, true))) return rc; R.mis_cnt = c; R.mis_total = (unsigned long long *)(c + 2); R.mis = nullptr; R.mis_cap = 0; }
     r->d_dup_units = o.dup_units; r->d_dup_off = o.dup_off; r->n_dup = o.n_dup; r->n_dup_work = o.dup_work;
-    R.max_aln_span = o.max_aln_span; R.max_frag_span = o.max_frag_span;
+    R.max_frag_span = o.max_frag_span;
     R.any_amplicon = o.any_amplicon;
     R.max_frag_depth = o.max_frag_depth;   // k_frag packs two 16-bit bucket counters per LDS word when it is below 65 536
     // table rows are written by k_p2_slow<false>; mark all slots empty (0xFF)
     HIP_OK(hipMemsetAsync(R.table, 0, (size_t)std::max<int64_t>(o.table_rows, 1) * sizeof(Contrib), r->stream));   // no base, no LINK symbol
+    {   // the work list of P1 and P2: stable order by (class, begin) on the device -- begin - region begin < 2^29 and the class takes the two
+        // bits above -- in front of the prelude, which writes the record of a simple alignment straight into the slot of its entry
+        const size_t np2 = (size_t)o.n_p2;
+        for (int c = 0; c <= 4; c++) R.p2_off[c] = o.p2_off[c];
+        uint32_t *work; uint8_t *tmp; int32_t *d_slot;
+        const size_t tmp_bytes = uvc_sort32_tmp_bytes(std::max<size_t>(np2, 1));
+        if ((rc = dev_alloc(r, 4 * np2, &work)) || (rc = dev_alloc(r, tmp_bytes + 16, &tmp)) || (rc = dev_alloc(r, (size_t)n, &d_slot))) return rc;
+        for (int k = 0; k < 4; k++) if ((rc = dev_alloc(r, np2, &r->d_p2[k]))) return rc;
+        if (uvc_sort_by_pos_cls(o.p2_beg, o.p2_cls, r->beg, pos_bits, 2, (int64_t)np2, work, tmp, tmp_bytes, r->stream) != 0) return fail(UVCGPU_EDEVICE, "device sort of the work list failed");
+        uvc_launch_gather4(work + 3 * np2, (int64_t)np2, o.p2_aln, o.p2_beg, o.p2_end, o.p2_qb, r->d_p2[0], r->d_p2[1], r->d_p2[2], r->d_p2[3], W.kind, n, d_slot, r->stream);
+        W.fast_rank = d_slot;
+        { FastRec *f; if ((rc = dev_alloc(r, np2, &f))) return rc; R.frec2 = f; R.n_fast2 = (int32_t)np2; R.max_p2_span = o.max_p2_span; }
+    }
     lap("allocations + orders");
     uvc_launch_prelude(&R, &W, &r->P, r->stream);
     lap("prelude kernel");
-    {   // the P2 work list: stable order by (class, begin) on the device -- begin - region begin < 2^29 and the class takes the two bits above
-        const size_t np2 = (size_t)o.n_p2;
-        for (int c = 0; c <= 4; c++) R.p2_off[c] = o.p2_off[c];
-        uint32_t *work; uint8_t *tmp;
-        const size_t tmp_bytes = uvc_sort32_tmp_bytes(std::max<size_t>(np2, 1));
-        if ((rc = dev_alloc(r, 4 * np2, &work)) || (rc = dev_alloc(r, tmp_bytes + 16, &tmp))) return rc;
-        for (int k = 0; k < 4; k++) if ((rc = dev_alloc(r, np2, &r->d_p2[k]))) return rc;
-        if (uvc_sort_by_pos_cls(o.p2_beg, o.p2_cls, r->beg, pos_bits, 2, (int64_t)np2, work, tmp, tmp_bytes, r->stream) != 0) return fail(UVCGPU_EDEVICE, "device sort of the P2 work list failed");
-        uvc_launch_gather4(work + 3 * np2, (int64_t)np2, o.p2_aln, o.p2_beg, o.p2_end, o.p2_qb, r->d_p2[0], r->d_p2[1], r->d_p2[2], r->d_p2[3], r->stream);
-        { FastRec *f; if ((rc = dev_alloc(r, np2, &f))) return rc; R.frec2 = f; R.n_fast2 = (int32_t)np2; R.max_p2_span = o.max_p2_span; }
-        uvc_launch_build_p2list(&R, W.fast_rank, r->d_p2[0], r->d_p2[1], r->d_p2[2], r->d_p2[3], r->stream);
-    }
+    uvc_launch_build_p2list(&R, W.fast_rank, r->d_p2[0], r->d_p2[1], r->d_p2[2], r->d_p2[3], r->stream);
     HIP_OK(hipGetLastError());
     {   // the queue of mismatching bases (k_p2_fast -> k_p2_mism) is sized from the count the prelude made
         unsigned long long total = 0; int32_t bad4 = 0;
@@ -466,7 +464,7 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
         if ((rc = dev_alloc(r, (size_t)(total + 64), &q))) return rc;
         R.mis = q; R.mis_cap = (int32_t)(total + 64);
     }
-    lap("P2 list sort + build");
+    lap("work list build");
     r->n_bases = d->n_bases;
     r->has_reads = true; r->reads_given = true;
     return 0;

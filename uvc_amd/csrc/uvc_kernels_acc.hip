@@ -14,10 +14,10 @@
 // the code below is written to minimise VALU + SALU instructions per (read, 64 positions).
 //
 //   k_pack_bq        per read base  base | qual << 8
-//   k_aln_prelude    per read       nge/ngo/clips, xm1500, bm1500s, penalties, eligibility   main.hpp:1795-1885
-//   k_build_p2list   per entry      P2 work list (simple reads + M runs of InDel reads), 4 orientation classes
+//   k_aln_prelude    per read       nge/ngo/clips, xm1500, bm1500s, penalties, eligibility; the work-list record of a simple read   main.hpp:1795-1885
+//   k_build_p2list   per entry      the work-list records of the M runs of InDel reads (one list for P1 and P2, 4 orientation classes)
 //   k_correct_bq     per read       apply_bq_err_correction3 (on request)                     grouping.cpp:459-543
-//   k_prep_fast      per position   P1 for simple reads                                       main.hpp:924-1204
+//   k_prep_fast      per position   P1 for simple reads (the work list without the M runs)    main.hpp:924-1204
 //   k_prep_slow      wave per read  P1 for reads with InDels (atomics)
 //   k_thres          per position   P1b, also edits rtr.indelphred                            main.hpp:1206-1299
 //   k_p2_fast<L,B>   per position   P2 + dealwith_segbias, LINK_M / read base instantiations   main.hpp:1360-1595, 1762-2296
@@ -78,8 +78,9 @@ DEV int lower_bound_frec(const FastRec *a, int n, int key) {   // first index wi
 // Window index: for every 64-position window w and every begin-sorted work list, the records a wave of window w walks:
 // [first record with begin >= window begin - longest span + 1, first record with begin >= window end).  A binary search per wave and list is
 // ~20 dependent memory round trips (8 lists' bounds in k_p2_fast: an eighth of a wave's life); the table costs one load each.
-// Lists: 0 = frec (k_prep_fast), 1..4 = the four sub-lists of frec2 (k_p2_fast), 5..6 = the two strands of ffast (k_frag),
-// 7 = the generic family-strand units by begin (the window kernels of the family passes: two loads per search step there).
+// Lists: 1..4 = the four sub-lists of frec2 (k_p2_fast; k_prep_sums and k_prep_fast walk the same four and skip what is not a whole simple
+// alignment), 5..6 = the two strands of ffast (k_frag), 7 = the generic family-strand units by begin (the window kernels of the family
+// passes: two loads per search step there).  Slot 0 of the table is not used.
 #define WIN_LISTS 8
 DEV int win_lo(const RegionDev &R, int list, int w) { return R.win[((size_t)list * 2) * R.nwin + w]; }
 DEV int win_hi(const RegionDev &R, int list, int w) { return R.win[((size_t)list * 2 + 1) * R.nwin + w]; }
@@ -89,8 +90,7 @@ __global__ void __launch_bounds__(256) k_win_index(RegionDev R, int list_beg, in
     if (t >= per_list * (list_end - list_beg)) return;
     const int list = list_beg + (int)(t / per_list), which = (int)((t % per_list) / R.nwin), w = (int)(t % R.nwin);
     const char *base; int stride, lo, hi, span;
-    if (list == 0) { base = (const char *)&R.frec[0].pos; stride = sizeof(FastRec); lo = 0; hi = R.n_fast; span = R.max_aln_span; }
-    else if (list <= 4) { base = (const char *)&R.frec2[0].pos; stride = sizeof(FastRec); lo = R.p2_off[list - 1]; hi = R.p2_off[list]; span = R.max_p2_span; }
+    if (list <= 4) { base = (const char *)&R.frec2[0].pos; stride = sizeof(FastRec); lo = R.p2_off[list - 1]; hi = R.p2_off[list]; span = R.max_p2_span; }
     else if (list <= 6) { base = (const char *)&R.ffast[0].beg; stride = sizeof(FragFast); lo = R.frag_off[list - 5]; hi = R.frag_off[list - 4]; span = R.max_frag_span; }
     else { base = nullptr; stride = 0; lo = 0; hi = R.n_generic_fs; span = R.max_unit_span; }
     const int w0 = R.beg + 64 * w, key = (which == 0 ? w0 - span + 1 : w0 + 64);
@@ -383,38 +383,34 @@ DEV bool has_lowbq_indel(const UvcParams &P, const AlnRec &a, const uint32_t *ci
     return false;
 }
 
-// digest of alignment `a` (index `id`) for the position-centric kernels, covering [cbeg, cend) with query offset qb_lo
-DEV void fill_fastrec(FastRec &f, const AlnRec &a, int id, int cbeg, int cend, int32_t qb_lo) {
+// digest of alignment `a` (index `id`) for the position-centric kernels, covering [cbeg, cend) with query offset qb_lo; m_run: the entry is
+// an M run of an InDel read (FREC_M_RUN: P1 leaves the read to k_prep_slow), not a whole simple alignment
+DEV void fill_fastrec(FastRec &f, const AlnRec &a, int id, int cbeg, int cend, int32_t qb_lo, bool m_run) {
     f.pos = cbeg; f.rend = cend; f.qb_lo = qb_lo; f.aln = id;
     f.fmd = (a.flag & 0xFFFF) | ((a.mapq & 0xFF) << 16) | ((a.dflag & 0xFF) << 24); f.isize = a.isize; f.mpos = a.mpos; f.xm1500 = a.xm1500;
     // per-read constants of dealwith_segbias<false>: the a2XM2 / a2BM2 increments (main.hpp:1521-1522), each <= 100
     int bv[5];
     for (int s2 = 0; s2 < 5; s2++) bv[s2] = (a.bm1500[s2] > 20 ? (100 * (20 * 20) / (a.bm1500[s2] * a.bm1500[s2])) : 100);
     const int xv = (a.xm1500 > 20 ? (100 * (20 * 20) / (a.xm1500 * a.xm1500)) : 100);
-    f.bmv = bv[0] | (bv[1] << 8) | (bv[2] << 16) | (bv[3] << 24); f.xbv = bv[4] | (xv << 8);
+    f.bmv = bv[0] | (bv[1] << 8) | (bv[2] << 16) | (bv[3] << 24); f.xbv = bv[4] | (xv << 8) | (m_run ? FREC_M_RUN : 0);
     f.bm4c = ((a.clip_cnt & 0xF) << 16) | (a.nogap_penal & 0xFFFF);   // nogap_penal is negative when NM < the InDel lengths
     f.clips = (a.lclip_oplen & 0xFFFF) | (a.rclip_oplen << 16);
     f.baq_pos = (int32_t)a.baq_pos; f.baq_last = (int32_t)a.baq_last; f.baq2_last = (int32_t)a.baq2_last;
     f.ext = ((cbeg - a.pos) & 0xFFFF) | ((a.rend - cend) << 16);
 }
 
-// P2 work list: entry j covers [cbeg[j], cend[j]) of alignment aln[j] (sorted by (class, cbeg)).  The entry of a simple alignment is the
-// record k_aln_prelude already made for the P1 list (frec, the same alignment under its rank there): 64 bytes copied instead of the
-// alignment's 200-byte record read again; only the M runs of InDel reads are built from their alignment records.
+// Work list of P1 and P2: entry j covers [cbeg[j], cend[j]) of alignment aln[j] (sorted by (class, cbeg)).  The entry of a simple alignment
+// is the record k_aln_prelude wrote straight into its slot (RawReads::fast_rank); only the M runs of InDel reads are built here, from the
+// alignment records the prelude made.
 __global__ void __launch_bounds__(256) k_build_p2list(RegionDev R, const int32_t *fast_rank, const int32_t *aln, const int32_t *cbeg, const int32_t *cend, const int32_t *qb) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= R.n_fast2) return;
-    const int id = aln[j], rk = fast_rank[id];
-    if (rk >= 0) {
-        const uint4 *src = (const uint4 *)&R.frec[rk]; uint4 *dst = (uint4 *)&R.frec2[j];
-        const uint4 v0 = src[0], v1 = src[1], v2 = src[2], v3 = src[3];
-        dst[0] = v0; dst[1] = v1; dst[2] = v2; dst[3] = v3;
-        return;
-    }
+    const int id = aln[j];
+    if (fast_rank[id] >= 0) return;
     FastRec f;
     const AlnRec &a = R.alns[id];
     // an InDel read that k_aln_prelude found ineligible keeps its slot (the list stays sorted) but covers nothing
-    fill_fastrec(f, a, id, cbeg[j], (a.kind == 1 ? cbeg[j] : cend[j]), qb[j]);
+    fill_fastrec(f, a, id, cbeg[j], (a.kind == 1 ? cbeg[j] : cend[j]), qb[j], true);
     R.frec2[j] = f;
 }
 
@@ -423,7 +419,7 @@ __global__ void __launch_bounds__(256) k_build_p2list(RegionDev R, const int32_t
 // (unaligned loads: the hardware takes them) and a count is a popcount.  The eight lanes of an alignment read 64 consecutive bytes, so a
 // load of the wave touches eight cache lines; with a lane per alignment it touched 64 (8 bytes of each, 150 bytes apart) and the kernel was
 // bound by the L2 -> L1 traffic of lines read sixteen times over (0.39 ms per 2 M reads; a wave per alignment was 0.59 ms, a thread per
-// alignment walking byte by byte 2.0 ms).  The five counts wait in the alignment's own FastRec slot.
+// alignment walking byte by byte 2.0 ms).  The five counts wait in the alignment's own FastRec slot of the work list.
 DEV unsigned long long load8u(const uint8_t *p) { unsigned long long v; __builtin_memcpy(&v, p, 8); return v; }
 __global__ void __launch_bounds__(256) k_aln_bm(RegionDev R, RawReads W) {
     const unsigned long long K7F = 0x7F7F7F7F7F7F7F7FULL, K80 = 0x8080808080808080ULL, K01 = 0x0101010101010101ULL;
@@ -449,7 +445,7 @@ __global__ void __launch_bounds__(256) k_aln_bm(RegionDev R, RawReads W) {
 #pragma unroll
         for (int s2 = 0; s2 < 5; s2++) { cnt[s2] += __shfl_xor(cnt[s2], 1); cnt[s2] += __shfl_xor(cnt[s2], 2); cnt[s2] += __shfl_xor(cnt[s2], 4); }
         if (sub == 0) {
-            int32_t *dst = (int32_t *)&R.frec[rk];
+            int32_t *dst = (int32_t *)&R.frec2[rk];
 #pragma unroll
             for (int s2 = 0; s2 < 5; s2++) dst[s2] = cnt[s2];
         }
@@ -480,7 +476,7 @@ DEV int aln_prelude_one(const RegionDev &R, const RawReads &W, const UvcParams &
     int qpos = 0, rpos = a.pos, lclip_q = 0, m_index = -1;
     const int rk0 = W.fast_rank[id];
     if (rk0 >= 0) {   // simple alignment: k_aln_bm counted its mismatching bases with a whole wave and left them in this read's own FastRec slot
-        const int32_t *pre = (const int32_t *)&R.frec[rk0];
+        const int32_t *pre = (const int32_t *)&R.frec2[rk0];
         for (int s2 = 0; s2 < 5; s2++) bm[s2] = pre[s2];
         for (int i = 0; i < a.n_cigar && m_index < 0; i++) {
             const int op = cig_op(cigar[i]);
@@ -522,8 +518,8 @@ DEV int aln_prelude_one(const RegionDev &R, const RawReads &W, const UvcParams &
     if (rk >= 0 || W.kind[id] == 2) n_mis = bm[0] + bm[1] + bm[2] + bm[3] + bm[4];   // every alignment that can be on the P2 work list: its mismatching bases go through the mismatch queue
     if (rk >= 0) {
         FastRec f;
-        fill_fastrec(f, a, id, a.pos, a.rend, (int32_t)(a.qbase & 0xFFFFFFFFLL));
-        R.frec[rk] = f;
+        fill_fastrec(f, a, id, a.pos, a.rend, (int32_t)(a.qbase & 0xFFFFFFFFLL), false);
+        R.frec2[rk] = f;
     }
     return n_mis;
 }
@@ -629,7 +625,6 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
     for (int i = threadIdx.x; i < 2 * (PSUM_TILE + 1); i += 256) (&d64[0][0])[i] = 0ull;
     __syncthreads();
     const int w_first = (int)blockIdx.x * (PSUM_TILE / 64), w_last = imin(w_first + PSUM_TILE / 64, R.nwin) - 1;
-    const int lo = win_lo(R, 0, w_first), hi = win_hi(R, 0, w_last);
     auto put = [&](int f, int a, int b, int v) {   // += v on [a, b) of plane f, clipped to the tile
         a = imax(a, t0); b = imin(b, t1);
         if (a < b && v != 0) { atomicAdd(&d[f][a - t0], v); atomicAdd(&d[f][b - t0], -v); }
@@ -638,11 +633,14 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
         a = imax(a, t0); b = imin(b, t1);
         if (a < b && v != 0) { atomicAdd(&d64[f][a - t0], (unsigned long long)v); atomicAdd(&d64[f][b - t0], (unsigned long long)(-v)); }
     };
+    for (int cls = 0; cls < 4; cls++) {   // the four class sub-lists of the work list: the sums do not depend on the order of the reads
+    const int lo = win_lo(R, 1 + cls, w_first), hi = win_hi(R, 1 + cls, w_last);
     for (int k = lo + (int)threadIdx.x; k < hi; k += 256) {
-        const int4 *q4 = (const int4 *)(R.frec + k);
+        const int4 *q4 = (const int4 *)(R.frec2 + k);
         const int4 h0 = q4[0], h1 = q4[1];   // pos rend qb_lo aln | fmd isize mpos xm1500
         const int apos = h0.x, rend = h0.y;
         if (rend <= t0 || apos >= t1) continue;
+        if (((const int *)q4)[9] & FREC_M_RUN) continue;   // FastRec::xbv: an M run of an InDel read (k_prep_slow has the read)
         const int dflag = (h1.x >> 24) & 0xFF;
         put(PS_DP, apos, rend, 1); put(PS_PCR, apos, rend, (dflag & 0x4) ? 1 : 0); put(PS_UMI, apos, rend, (dflag & 0x1) ? 1 : 0);
         put(PS_QLEN, apos, rend, rend - apos); put(PS_XM, apos, rend, h1.w);
@@ -659,6 +657,7 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
                 put64(1, apos, brk, MAX_INSERT_SIZE); put(PS_RIA, brk, rend, 1); put64(1, brk, rend, fr);
             }
         }
+    }
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -725,7 +724,6 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
     const int my_baq = valid ? (int)R.baq[x] : 0;
     int ldist = 0, rdist = 0, hbq = 0;
     long long lbaq = 0, rbaq = 0;
-    const int lo = wave_uniform(win_lo(R, 0, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 0, (int)(x0 >> 6)));
     COARSE_T(ct1)
     const __amdgpu_buffer_rsrc_t rs = bq_rsrc(R);
     // Mismatching bases are rare per lane but present in a large share of the iterations of a wave, and their handling (SNV / DNV
@@ -742,9 +740,14 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
         }
         nq = 0;
     };
+    // the four class sub-lists of the work list, one after the other through the same loop body (every counter here is a sum over the covering
+    // reads: their order does not matter)
+#pragma unroll 1
+    for (int cls = 0; cls < 4; cls++) {
+    const int lo = wave_uniform(win_lo(R, 1 + cls, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 1 + cls, (int)(x0 >> 6)));
     for (int k0 = lo + (SPLIT ? 64 * (int)(threadIdx.x >> 6) : 0); k0 < hi; k0 += (SPLIT ? 256 : 64)) {
         Chunk16 c;
-        load_chunk16(R.frec, k0 + lane, hi, c);
+        load_chunk16(R.frec2, k0 + lane, hi, c);
         const int n = imin(64, hi - k0);
         // the base | quality bytes of the chunk's reads are requested four reads ahead (one load per read and lane, HBM / L2 latency each:
         // with one read of look-ahead the wave waited for most of them)
@@ -752,7 +755,7 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
         auto one = [&](int j, int bqn) {
             const int b = bqn & 0xFF, q = (bqn >> 8) & 0xFF;
             const int apos = bcast(c.v[0], j), rend = bcast(c.v[1], j);
-            if (rend <= w0) return;
+            if (rend <= w0 || (bcast(c.v[9], j) & FREC_M_RUN)) return;   // behind the window, or an M run of an InDel read (k_prep_slow has the read)
             const bool cover = (valid && p >= apos && p < rend);
             const wmask mm = BAL(cover && b != my_ref);
             if (mm) {
@@ -783,6 +786,7 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
             if (j + 2 < n) { const int v = r2; if (j + 6 < n) r2 = fetch(j + 6); one(j + 2, v); }
             if (j + 3 < n) { const int v = r3; if (j + 7 < n) r3 = fetch(j + 7); one(j + 3, v); }
         }
+    }
     }
     if (nq > 0) drain();
     COARSE_T(ct2)
@@ -3763,8 +3767,8 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     hipStream_t s2 = (side ? side : s);
     hipStream_t s3 = ((side && side3) ? side3 : s2);   // the two CIGAR walks of the InDel reads are independent, one wave per 64 reads and long: a stream each
     {   // the window index of the alignment lists (the fragment list's follows k_fragstat_fast, which writes it)
-        const int64_t n = 2 * (int64_t)R->nwin * 5;
-        TIMED(prof, "k_win_index", hipLaunchKernelGGL(k_win_index, dim3(nblk(n, 256)), dim3(256), 0, s, *R, 0, 5));
+        const int64_t n = 2 * (int64_t)R->nwin * 4;
+        TIMED(prof, "k_win_index", hipLaunchKernelGGL(k_win_index, dim3(nblk(n, 256)), dim3(256), 0, s, *R, 1, 5));
         if (R->n_generic_fs) hipLaunchKernelGGL(k_win_index, dim3(nblk(2 * (int64_t)R->nwin, 256)), dim3(256), 0, s, *R, 7, 8);
     }
     if (P->inferred_is_vcf_generated && R->n_fast) TIMED(prof, "k_prep_sums", hipLaunchKernelGGL(k_prep_sums, dim3(nblk(R->npos, PSUM_TILE)), dim3(256), 0, s, *R, *P));

@@ -5,7 +5,8 @@
 #define UVC_LAUNCH_H
 #include "uvc_device.h"
 
-// the caller's columns as they are (uvcgpu_region_set_reads) + what uvc_prep.hip derives per read; by value into k_aln_bm / k_aln_prelude
+// the caller's columns as they are (uvcgpu_region_set_reads) + what uvc_prep.hip derives per read; by value into k_aln_bm / k_aln_prelude.
+// fast_rank: the slot of a simple alignment's entry in RegionDev::frec2, -1 for every other alignment (k_gather4)
 struct RawReads {
     const int32_t *pos, *endpos, *mpos, *isize, *nm, *l_qseq, *n_cigar, *frag, *fs, *dflag, *kind, *fast_rank;
     const uint16_t *flag; const uint8_t *mapq;
@@ -126,7 +127,8 @@ size_t uvc_gap_sort_tmp_bytes(size_t n);
 int uvc_gap_sort(void *tmp, size_t tmp_bytes, const unsigned long long *kin, unsigned long long *kout, const unsigned long long *vin, unsigned long long *vout, size_t n, int end_bit, hipStream_t s);
 size_t uvc_sort32_tmp_bytes(size_t n);
 int uvc_sort_by_pos_cls(const int32_t *d_pos, const int32_t *d_cls, int32_t beg, int pos_bits, int cls_bits, int64_t n, uint32_t *work /* [4 n] */, void *tmp, size_t tmp_bytes, hipStream_t s);
-void uvc_launch_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3, hipStream_t s);
+void uvc_launch_gather4(const uint32_t *perm, int64_t n, const int32_t *a0, const int32_t *a1, const int32_t *a2, const int32_t *a3, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *o3,
+                        const int32_t *kind, int64_t n_alns, int32_t *slot, hipStream_t s);
 void uvc_launch_rank_from_sorted(const uint32_t *perm, int64_t n, int64_t n_first, int32_t *out_ids, int32_t *rank, hipStream_t s);
 void uvc_launch_gather_columns(const char *const *base, const int32_t *first_col, const int32_t *elem, int64_t npos, const int32_t *d_xs, int64_t n, long long *d_out, hipStream_t s);
 // ---- uvc_prep.hip (uvc_prep_reads itself: uvc_prep.h) ----

@@ -13,14 +13,14 @@ struct UvcPrepIn {
 };
 // device arrays (owned by the allocator's context) and host-side totals
 struct UvcPrepOut {
-    int32_t *endpos, *kind, *dflag_of, *frag_of, *fs_of, *p2_first, *complex_ids, *is_complex;
+    int32_t *endpos, *kind, *dflag_of, *frag_of, *fs_of, *p2_first, *complex_ids;
     int32_t *frag_beg, *frag_strand;   // FragRec::beg / strand as columns (keys of the fragment order)
     int64_t *table_off, *item_off, *gap_off;
     FragRec *frags; FsRec *fss;
     int32_t *generic_fs, *generic_sorted, *sweep_frags, *dup_units; int64_t *dup_off;
     int32_t *p2_aln, *p2_beg, *p2_end, *p2_qb, *p2_cls;   // P2 work-list entries in read order (the caller sorts them by (class, begin))
     int32_t n_frags, n_fs, n_complex, n_simple, n_generic, n_dup, n_sweep, n_frag_strand0;
-    int32_t max_aln_span, max_frag_span, max_unit_span, max_unit_frags, max_p2_span, max_frag_depth, any_amplicon;
+    int32_t max_frag_span, max_unit_span, max_unit_frags, max_p2_span, max_frag_depth, any_amplicon;
     int32_t p2_off[5];
     int64_t n_p2, table_rows, item_slots, gap_slots, ins_total, work, dup_work;
 };

@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_cols_apply(ScanCols C, const long 
 }
 
 struct Stage1 {   // device counters of the first stage (read back once)
-    int32_t err, max_aln_span, n_frags, n_fs, n_complex, any_amplicon;
+    int32_t err, n_frags, n_fs, n_complex, any_amplicon, pad0_;
     int32_t p2_cls[4]; int32_t max_p2_span, pad_;
     int64_t n_p2, table_rows, item_slots, gap_slots, ins_total;
 };
@@ -126,9 +126,9 @@ struct Stage2 {
 
 // ---- stage 1: what the CIGAR of each read says (nothing here depends on another read except the two "is a new ..." flags) ----
 __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, int32_t rend, int seg_eligible,
-                                                    int32_t *endpos, int32_t *kind, int32_t *dflag_of, int32_t *new_frag, int32_t *new_fs, int32_t *is_complex,
+                                                    int32_t *endpos, int32_t *kind, int32_t *dflag_of, int32_t *new_frag, int32_t *new_fs,
                                                     int32_t *n_p2, int64_t *gaps, int64_t *trows, int64_t *items, int64_t *ins, Stage1 *T, long long *tile_sums, int ntiles) {
-    int w_err = 0, w_span = 0, w_p2span = 0, w_cls[4] = { 0, 0, 0, 0 }, w_amp = 0;   // this lane's contributions to the region-wide counters
+    int w_err = 0, w_p2span = 0, w_cls[4] = { 0, 0, 0, 0 }, w_amp = 0;   // this lane's contributions to the region-wide counters
     long long col[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // this lane's share of the tile's column sums (new_frag, new_fs, is_complex, n_p2, trows, items, ins, gaps)
     // one block per tile of SC_TILE consecutive reads (the tile sums feed the offset scans of k_facts_apply)
     for (int k8 = 0; k8 < SC_ITEMS; k8++) {
@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
             // kind 2 = candidate for the simple path: k_aln_prelude demotes it to 1 when the read has a low-quality InDel
             o_kind = simple ? 0 : (ok ? 2 : 1);
             if (!simple) { o_trows = (e - pos) + 1; o_items = 2 * (int64_t)lq + 2 * del_total + nc + 4; }
-            else { o_gaps = 0; o_ins = 0; w_span = pmax(w_span, e - pos); }
+            else { o_gaps = 0; o_ins = 0; }
             if (o_np2) {
                 const int fl = in.flag[i];
                 const int cls = ((fl & 0x10) ? 1 : 0) | ((((fl & 0x81) == 0x81) ? ((fl & 0x20) != 0) : ((fl & 0x10) != 0)) ? 2 : 0);   // is-reverse | bam_get_strand << 1 (common.hpp:89)
@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
         }
     }
     if (err) { w_err = pmax(w_err, err); o_kind = 1; o_gaps = 0; o_ins = 0; o_np2 = 0; }
-    endpos[i] = o_end; kind[i] = o_kind; n_p2[i] = o_np2; gaps[i] = o_gaps; trows[i] = o_trows; items[i] = o_items; ins[i] = o_ins; is_complex[i] = (o_kind != 0);
+    endpos[i] = o_end; kind[i] = o_kind; n_p2[i] = o_np2; gaps[i] = o_gaps; trows[i] = o_trows; items[i] = o_items; ins[i] = o_ins;
     const bool ok_fam = !bad_fam;
     const int df = ok_fam ? (int)in.fam_dflag[fam] : 0;
     dflag_of[i] = df;
@@ -204,20 +204,19 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
         if (threadIdx.x == 0) { for (int c = 0; c < 8; c++) tile_sums[(size_t)c * ntiles + blockIdx.x] = col[c]; }
     }
     // wave, then block, then one set of atomics per block (the grid is a few thousand blocks)
-    __shared__ int sh[4][8];
-    w_err = wave_max(w_err); w_span = wave_max(w_span); w_p2span = wave_max(w_p2span); w_amp = wave_max(w_amp);
+    __shared__ int sh[4][7];
+    w_err = wave_max(w_err); w_p2span = wave_max(w_p2span); w_amp = wave_max(w_amp);
     for (int c = 0; c < 4; c++) w_cls[c] = wave_sum(w_cls[c]);
     const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[wv][0] = w_err; sh[wv][1] = w_span; sh[wv][2] = w_p2span; sh[wv][3] = w_amp; for (int c = 0; c < 4; c++) sh[wv][4 + c] = w_cls[c]; }
+    if ((threadIdx.x & 63) == 0) { sh[wv][0] = w_err; sh[wv][1] = w_p2span; sh[wv][2] = w_amp; for (int c = 0; c < 4; c++) sh[wv][3 + c] = w_cls[c]; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        int v[8];
-        for (int q = 0; q < 8; q++) { v[q] = sh[0][q]; for (int w = 1; w < 4; w++) v[q] = (q < 4 ? pmax(v[q], sh[w][q]) : v[q] + sh[w][q]); }
+        int v[7];
+        for (int q = 0; q < 7; q++) { v[q] = sh[0][q]; for (int w = 1; w < 4; w++) v[q] = (q < 3 ? pmax(v[q], sh[w][q]) : v[q] + sh[w][q]); }
         if (v[0]) atomicMax(&T->err, v[0]);
-        if (v[1]) atomicMax(&T->max_aln_span, v[1]);
-        if (v[2]) atomicMax(&T->max_p2_span, v[2]);
-        if (v[3]) T->any_amplicon = 1;
-        for (int c = 0; c < 4; c++) if (v[4 + c]) atomicAdd(&T->p2_cls[c], v[4 + c]);
+        if (v[1]) atomicMax(&T->max_p2_span, v[1]);
+        if (v[2]) T->any_amplicon = 1;
+        for (int c = 0; c < 4; c++) if (v[3 + c]) atomicAdd(&T->p2_cls[c], v[3 + c]);
     }
 }
 
@@ -541,10 +540,10 @@ extern "C" int uvc_prep_reads(const UvcPrepIn *inp, const UvcParams *P, int32_t 
 #define ALLOC(ptr, T, count, zero) do { ptr = (T *)A(sizeof(T) * (size_t)(count), zero); if (!ptr) { snprintf(errmsg, (size_t)errcap, "hipMalloc(%s)", #ptr); return UVCGPU_ENOMEM; } } while (0)
     const int seg_eligible = (UVC_PLATFORM_IONTORRENT != P->inferred_sequencing_platform) && rbeg >= 65536 && P->bias_thres_interfering_indel <= 10000;
     // ---- stage 1
-    int32_t *new_frag, *new_fs, *is_complex, *n_p2; int64_t *gaps, *trows, *items, *ins;
+    int32_t *new_frag, *new_fs, *n_p2; int64_t *gaps, *trows, *items, *ins;
     ALLOC(out->endpos, int32_t, n, 0); ALLOC(out->kind, int32_t, n, 0); ALLOC(out->dflag_of, int32_t, n, 0); ALLOC(out->frag_of, int32_t, n, 0); ALLOC(out->fs_of, int32_t, n, 0);
     ALLOC(out->table_off, int64_t, n, 0); ALLOC(out->item_off, int64_t, n, 0); ALLOC(out->gap_off, int64_t, n, 0); ALLOC(out->p2_first, int32_t, n, 0);
-    ALLOC(new_frag, int32_t, n, 0); ALLOC(new_fs, int32_t, n, 0); ALLOC(is_complex, int32_t, n, 0); out->is_complex = is_complex; ALLOC(n_p2, int32_t, n, 0); ALLOC(gaps, int64_t, n, 0);
+    ALLOC(new_frag, int32_t, n, 0); ALLOC(new_fs, int32_t, n, 0); ALLOC(n_p2, int32_t, n, 0); ALLOC(gaps, int64_t, n, 0);
     ALLOC(trows, int64_t, n, 0); ALLOC(items, int64_t, n, 0); ALLOC(ins, int64_t, n, 0);
     Stage1 *dT1; ALLOC(dT1, Stage1, 1, 1);
     Stage2 *dT2; ALLOC(dT2, Stage2, 1, 1);
@@ -556,7 +555,7 @@ extern "C" int uvc_prep_reads(const UvcPrepIn *inp, const UvcParams *P, int32_t 
     long long *tile_sums; ALLOC(tile_sums, long long, (size_t)8 * ntiles + 8, 0);
     long long *col_totals = tile_sums + (size_t)8 * ntiles;
     ALLOC(out->complex_ids, int32_t, n, 0);   // (sized by the reads: the number of InDel reads is only known behind the scan that fills it)
-    hipLaunchKernelGGL(k_read_facts, dim3((unsigned)ntiles), dim3(SC_BLOCK), 0, s, in, rbeg, rend, seg_eligible, out->endpos, out->kind, out->dflag_of, new_frag, new_fs, is_complex, n_p2, gaps, trows, items, ins, dT1, tile_sums, ntiles);
+    hipLaunchKernelGGL(k_read_facts, dim3((unsigned)ntiles), dim3(SC_BLOCK), 0, s, in, rbeg, rend, seg_eligible, out->endpos, out->kind, out->dflag_of, new_frag, new_fs, n_p2, gaps, trows, items, ins, dT1, tile_sums, ntiles);
     hipLaunchKernelGGL(k_tile_tops<8>, dim3(1), dim3(1024), 0, s, tile_sums, ntiles, col_totals);
     hipLaunchKernelGGL(k_facts_apply, dim3((unsigned)ntiles), dim3(SC_BLOCK), 0, s, n, tile_sums, ntiles, col_totals, out->kind, new_frag, new_fs, n_p2, trows, items, gaps,
                        out->frag_of, out->fs_of, out->p2_first, out->table_off, out->item_off, out->gap_off, out->complex_ids, dT1);
@@ -581,7 +580,7 @@ extern "C" int uvc_prep_reads(const UvcPrepIn *inp, const UvcParams *P, int32_t 
         return T1.err == 2 ? UVCGPU_EUNSUPPORTED : UVCGPU_EINVAL;
     }
     out->n_frags = T1.n_frags; out->n_fs = T1.n_fs; out->n_complex = T1.n_complex; out->n_simple = (int32_t)(n - T1.n_complex); out->n_p2 = T1.n_p2; out->table_rows = T1.table_rows;
-    out->item_slots = T1.item_slots; out->gap_slots = T1.gap_slots; out->ins_total = T1.ins_total; out->max_aln_span = std::max(T1.max_aln_span, 1); out->any_amplicon = T1.any_amplicon;
+    out->item_slots = T1.item_slots; out->gap_slots = T1.gap_slots; out->ins_total = T1.ins_total; out->any_amplicon = T1.any_amplicon;
     out->max_p2_span = std::max(T1.max_p2_span, 1);
     out->p2_off[0] = 0; for (int c = 0; c < 4; c++) out->p2_off[c + 1] = out->p2_off[c] + T1.p2_cls[c];
     // ---- stage 2
