@@ -603,6 +603,44 @@ typedef struct UvcCallableRun { int32_t range, pos_beg, pos_end, mask; } UvcCall
 int uvcgpu_region_callable(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcCallableRequest *req,
                            UvcCallableRun *runs, int64_t run_capacity, int64_t *n_runs);
 const char *uvcgpu_callable_bit_name(int32_t bit);   /* "LOW_aDP" .. "NO_COVERAGE"; NULL for a bit outside 0..UVC_NCALLBIT - 1 */
+/* ---- microsatellite length-shift tallies of ranges of the accumulated region (uvc1-mi355x --msi-out) ----
+ * Positions in these rules are region-relative (x = position - beg); the rows carry absolute positions.  RTR_* are the STR planes of
+ * UVC_F_RTR as accumulate leaves them: the microsatellites as the caller itself sees them (indelphred, the BAQ sums, INFO/RU;RC).
+ *   Locus: a position h inside some range is a locus head iff RTR_begpos[h] == h, 1 <= RTR_unitlen[h] <= max_unitlen,
+ *     RTR_tracklen[h] >= min_tracklen and RTR_tracklen[h] / RTR_unitlen[h] >= min_units (integer division).  Its tract is
+ *     [h, h + RTR_tracklen[h]); it belongs to the range that holds h, and its tract may leave that range.  A track whose own head position
+ *     was given to a longer neighbouring track (RTR_begpos[h] != h) is no locus.  Loci come sorted by head, so by (range, position).
+ *   UVC_MSI_EDGE in flags: h == 0 or h + tracklen >= npos - 1 -- the tract holds the first or the last reference base of the region (the
+ *     region's last position npos - 1 has no base of its own), so the region cut may have truncated it.  Its depths and histograms are 0.
+ *   depth[4]: the minimum over the tract of the measures bDP, cDP12, cDP2, dDP1 of uvcgpu_region_coverage (UVC_COV_*), the measures kept
+ *     beside the four allele counters below (the duplex allele counter is kept beside cDPD / dDP2: depth[3] is a measure of the same
+ *     families, not its denominator).  The row holds counts and depths, no ratios.
+ *   Allele rows: every device row (x, symbol, len, inserted bases, cnt[strand * 4 + level]) of the InDel allele tables; a strand
+ *     contributes its four counters only where its fragment counter cnt[strand * 4] is positive, the two strands are summed: the sums of
+ *     the rows of uvcgpu_region_indel_alleles (bAD1, cAD1, c2AD, c2dAD = levels 0..3) over (refpos, symbol, len, sequence).
+ *   A deletion sits on its first deleted base x.  It goes to the locus h = RTR_begpos[x] if h is a reported locus without EDGE: a unit
+ *     shift of -len / unit iff len % unit == 0 and x + len <= h + tracklen, else OTHER.
+ *   An insertion sits on q = x, the position of the base right of the inserted bases (the CIGAR walk's reference coordinate at the I op:
+ *     the position LINK_I* is counted at).  It goes to the locus h = RTR_begpos[q] if that is a reported locus (q lies in its tract);
+ *     failing that, for q > 0, to h = RTR_begpos[q - 1] if that is a reported locus whose tract ends at q (an insertion behind the last
+ *     unit).  Without EDGE: a unit shift of +len / unit iff len % unit == 0 and inserted base i == ref[h + ((q - h + i) mod unit)] for
+ *     every i, else OTHER.  A row that reaches no reported locus adds nothing.
+ *   hist[level][13]: bins 0..5 = shifts -6..-1, bins 6..11 = +1..+6, longer shifts clamped into the -6 / +6 bins, bin 12 = OTHER.
+ * One row of UVC_MSI_ROW int32 per locus (sections: include/uvc_msi.def): range, pos_beg (absolute, zero-based), tracklen, unitlen, flags,
+ * depth[4], hist[4][13], zeros. */
+enum UvcMsiSection { UVC_MSI_range = 0, UVC_MSI_pos_beg, UVC_MSI_tracklen, UVC_MSI_unitlen, UVC_MSI_flags, UVC_MSI_depth, UVC_MSI_hist, UVC_MSI_reserved, UVC_NMSI };
+enum { UVC_MSI_NLEVEL = 4, UVC_MSI_MAXSHIFT = 6, UVC_MSI_NBIN = 13 /* 2 * 6 + OTHER */, UVC_MSI_OTHER = 12, UVC_MSI_DEPTH = 5, UVC_MSI_HIST = 9,
+       UVC_MSI_ROW = 64 /* 9 + 4 * 13 + 3 */, UVC_MSI_EDGE = 1 };
+typedef struct UvcMsiRequest { int32_t min_tracklen, min_units, max_unitlen; } UvcMsiRequest;   /* each at least 1 */
+/* Found, compacted, measured and binned on the device (integers only: the same bytes from call to call); 256 bytes per locus travel home.
+ *   Sizes first, as for uvcgpu_region_callable: *n_loci always receives the number of loci; when locus_capacity is smaller the call returns
+ *   UVCGPU_ENOMEM and writes nothing to `loci`.  Zero loci is legal.
+ *   Ranges and the window in which the call is legal: as for uvcgpu_region_callable.  UVCGPU_EINVAL before any launch, with a message that
+ *   names the reason (a range by its index): every refusal of uvcgpu_region_coverage; a request field below 1; a NULL req or n_loci;
+ *   locus_capacity < 0; a NULL loci with locus_capacity > 0.  A refused call writes neither *n_loci nor loci. */
+int uvcgpu_region_msi(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcMsiRequest *req,
+                      int32_t *loci /* [locus_capacity][UVC_MSI_ROW] */, int64_t locus_capacity, int64_t *n_loci);
+const char *uvcgpu_msi_section_name(int32_t id);   /* "range" .. "reserved"; NULL for an id outside 0..UVC_NMSI - 1 */
 /* Raw state access (the reference reads members directly, main.cpp:682-688, 759-760, 801-816). */
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t field_group);
 int uvcgpu_region_fetch(uvcgpu_region_t *r, int32_t field_group, void *dst, int64_t dst_bytes);

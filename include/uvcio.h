@@ -243,6 +243,23 @@ int uvcio_callable_add_runs(uvcio_callable_t *c, const int64_t *target_of_range,
 int64_t uvcio_callable_n_runs(const uvcio_callable_t *c);   /* the runs held so far */
 int uvcio_callable_write(const uvcio_callable_t *c, const char *path);
 void uvcio_callable_close(uvcio_callable_t *c);
+/* ---- the microsatellite tally (uvc1-mi355x --msi-out) ----
+ * The targets in report order and the loci that tiles report with uvcgpu_region_msi (rows of UVC_MSI_ROW int32, include/uvc_msi.def).  add
+ * takes the rows of one call as they came back, the target of each of the call's ranges and, per locus, the reference bases of its first
+ * unit as text, under a lock: tiles come in any order and from any thread; a locus that begins outside its target is refused.  write, in
+ * target order then position: one line per locus -- chrom, beg, end = beg + tracklen, unit, unitlen, units = tracklen / unitlen, target,
+ * flags ("." or "EDGE"), then per level b, c, c2, d (beside bDP, cDP12, cDP2, dDP1): depth, shifted = the sum of the twelve shift bins,
+ * other, and the bins m6..m1 p1..p6 -- and "#summary<TAB>loci<TAB>N", "#summary<TAB>loci_EDGE<TAB>N" and per level "#summary<TAB>level<TAB>
+ * assessable<TAB>N<TAB>unstable<TAB>M": N = the loci without EDGE whose depth is >= min_depth, M = those of them with 1000 * shifted >=
+ * unstable_permille * depth.  The header says what the file is: a tally for a classifier with a baseline, not an MSI call.  Tab-separated;
+ * a path that ends in .gz is written block-gzipped.  The store holds a row and a unit per locus until close. */
+typedef struct uvcio_msi uvcio_msi_t;
+int uvcio_msi_open(uvcio_msi_t **out, int32_t min_tracklen, int32_t min_units, int32_t max_unitlen, int32_t min_depth, int32_t unstable_permille);
+int64_t uvcio_msi_add_target(uvcio_msi_t *m, const char *chrom, int64_t beg, int64_t end, const char *name /* NULL or empty: "." */);   /* the target's index, or a negative code */
+int uvcio_msi_add(uvcio_msi_t *m, const int64_t *target_of_range, int64_t n_ranges, const int32_t *loci /* [n_loci][UVC_MSI_ROW] */, const char *const *units /* [n_loci] */, int64_t n_loci);
+int64_t uvcio_msi_n_loci(const uvcio_msi_t *m);   /* the loci held so far */
+int uvcio_msi_write(const uvcio_msi_t *m, const char *path);
+void uvcio_msi_close(uvcio_msi_t *m);
 /* bcftools concat -n (uvcTN.sh:100): the BGZF files one after the other, the 28-byte end-of-file marker of all but the last dropped. */
 int uvcio_bgzf_concat(const char *out_path, const char *const *in_paths, int32_t n_in);
 /* The whole text of a (block-)gzipped or plain file (the tumor VCF of a T/N pair); *buf is malloc'ed, the caller frees it. */

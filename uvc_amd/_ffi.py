@@ -99,6 +99,10 @@ class UvcCallableRun(C.Structure):
     _fields_ = [("range", C.c_int32), ("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("mask", C.c_int32)]
 
 
+class UvcMsiRequest(C.Structure):
+    _fields_ = [("min_tracklen", C.c_int32), ("min_units", C.c_int32), ("max_unitlen", C.c_int32)]
+
+
 class UvcScoreOut(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n_records", C.c_int64), ("fields", C.c_void_p)]
 
@@ -193,6 +197,20 @@ def _read_callable_def():
 CALLABLE_BITS = _read_callable_def()
 assert [ENUMS["UVC_CALL_" + n] for n in CALLABLE_BITS] == list(range(ENUMS["UVC_NCALLBIT"]))
 assert CALLABLE_BITS[:len(COVERAGE_MEASURES)] == ["LOW_" + m for m in COVERAGE_MEASURES] and C.sizeof(UvcCallableRequest) == 4 * (ENUMS["UVC_NCOV"] + 1)
+
+
+def _read_msi_def():
+    """The sections of a row of uvcgpu_region_msi: (name, first word, words) per row of include/uvc_msi.def."""
+    with open(os.path.join(ROOT, "include", "uvc_msi.def")) as fh:
+        rows = [re.match(r"UVC_MSI\((\w+),\s*(\d+),\s*(\d+)\)\s*$", line) for line in fh]
+    return [(m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
+
+
+# the sections of a microsatellite row in id order (UvcMsiSection): the table of include/uvc_msi.def, checked against the header's enums
+MSI_SECTIONS = _read_msi_def()
+assert [ENUMS["UVC_MSI_" + n] for n, _, _ in MSI_SECTIONS] == list(range(ENUMS["UVC_NMSI"]))
+assert sum(w for _, _, w in MSI_SECTIONS) == ENUMS["UVC_MSI_ROW"] and all(f == sum(w for _, _, w in MSI_SECTIONS[:k]) for k, (_, f, _) in enumerate(MSI_SECTIONS))
+assert dict((n, (f, w)) for n, f, w in MSI_SECTIONS)["depth"] == (ENUMS["UVC_MSI_DEPTH"], ENUMS["UVC_MSI_NLEVEL"]) and dict((n, (f, w)) for n, f, w in MSI_SECTIONS)["hist"] == (ENUMS["UVC_MSI_HIST"], ENUMS["UVC_MSI_NLEVEL"] * ENUMS["UVC_MSI_NBIN"])
 
 
 class Lib:

@@ -63,6 +63,9 @@ struct Opts {
     uvcio_callable_t *callable = nullptr;   // the BED's store, filled by the workers (main)
     std::vector<int64_t> call_contig_target;   // without a BED file: per contig the store's target of its called span (-1: not called)
     std::vector<std::pair<int64_t, int64_t>> call_target_span;   // per target of the store its [beg, end): a tile's stretch is clipped to it
+    std::string msi_out;         // --msi-out PATH: the microsatellite length-shift tally; empty = none
+    UvcMsiRequest msi_req{ 10, 5, 6 }; int32_t msi_min_depth = 30, msi_unstable_permille = 200; bool msi_sub_given = false;   // --msi-min-tract, --msi-min-units, --msi-max-unit; --msi-min-depth, --msi-unstable-permille
+    uvcio_msi_t *msi = nullptr;   // the tally's store, filled by the workers (main); its targets are those of --callable-out (call_contig_target, call_target_span)
     std::string readprof_out;    // --read-profile-out PATH: the base-quality and cycle profile of the reads; empty = none
     UvcReadProfileRequest readprof_req{ 0, 20, 50 }; bool readprof_gate_given = false;   // --read-profile-min-mapq, --read-profile-min-depth, --read-profile-max-alt-permille
     uvcio_readprofile_t *readprof = nullptr;   // the run's row, summed over the tiles by the workers (main)
@@ -121,6 +124,12 @@ const OptRow OPTS[] = {
     { "--callable-out", O_CLI, false, "", "write the callable regions here as BED lines contig, beg, end, class, target (tab-separated; block-gzipped when the name ends in .gz): every target -- BED line, or called contig span without a BED file -- cut into stretches of equal class, CALLABLE or the criteria the stretch fails (LOW_<depth>, EXCESS_aDP, NO_COVERAGE), classified on the device from the planes of each tile over the six depths of --coverage-out; #summary lines count the positions per class.  The VCF does not depend on it" },
     { "--callable-min-depth", O_CLI, false, "cDP12=20", "with --callable-out: NAME=N[,NAME=N...], the smallest depth a callable position has of each named depth (aDP bDP cDP1 cDP12 cDP2 dDP1; 0 or unnamed: not tested)" },
     { "--callable-max-aDP", O_CLI, false, "0", "with --callable-out: the largest raw depth aDP a callable position has (0: not tested)" },
+    { "--msi-out", O_CLI, false, "", "write the microsatellite length-shift tally here (tab-separated; block-gzipped when the name ends in .gz): one line per microsatellite of the caller's own repeat tracks whose first base lies in a target -- BED line, or called contig span without a BED file -- with, per evidence level (b fragments, c UMI families, c2 consensus families, d duplex families), the smallest depth along the tract and the InDel alleles that shift its length by -6..+6 whole units or otherwise, tallied on the device from the planes and allele rows of each tile; #summary lines count the assessable and the unstable loci per level.  A tally for a classifier with a baseline, not an MSI call.  The VCF does not depend on it" },
+    { "--msi-min-tract", O_CLI, false, "10", "with --msi-out: the shortest tract in bp" },
+    { "--msi-min-units", O_CLI, false, "5", "with --msi-out: the fewest whole repeat units of a tract" },
+    { "--msi-max-unit", O_CLI, false, "6", "with --msi-out: the longest repeat unit in bp" },
+    { "--msi-min-depth", O_CLI, false, "30", "with --msi-out: the smallest depth along the tract at which the #summary lines count a locus as assessable at a level" },
+    { "--msi-unstable-permille", O_CLI, false, "200", "with --msi-out: an assessable locus counts as unstable in the #summary lines when its shifted alleles are at least this many thousandths of its depth" },
     { "--read-profile-out", O_CLI, false, "", "write the read profile here (tab-separated; block-gzipped when the name ends in .gz): per read class (R1 / R2, forward / reverse) the matches and mismatches by reported base quality, the matches, mismatches, inserted bases, deletions and soft-clipped bases by sequencing cycle and the substitution matrix, at positions that do not look variant, reduced on the device from the read bases of each tile over the positions the tile owns, with the BAM's own qualities.  The VCF does not depend on it" },
     { "--read-profile-min-mapq", O_CLI, false, "0", "with --read-profile-out: only alignments of at least this mapping quality are counted (0..255)" },
     { "--read-profile-min-depth", O_CLI, false, "20", "with --read-profile-out: a base enters the bins only where at least this many counted A/C/G/T bases cover the position (1 or more)" },
@@ -202,7 +211,7 @@ bool number(const std::string &s, double *v) {   // a whole decimal number, or t
     char *e = nullptr; *v = strtod(s.c_str(), &e); return *e == 0 && std::isfinite(*v);
 }
 
-// What the report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out) share on the command line.  Each option
+// What the report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out, --msi-out) share on the command line.  Each option
 // gives its own words for why; the sentences are these.
 int64_t window_length(const std::string &opt, const std::string &v) {   // --coverage-window, --family-stats-window
     double x;
@@ -340,6 +349,13 @@ Opts parse(int argc, char **argv) {
             }
         }
         else if (n0 == "--callable-max-aDP") { const std::string v = val(); double x; if (v.find_first_not_of("0123456789") != std::string::npos || !number(v, &x) || x > 2e9) die("--callable-max-aDP takes a depth (0 = off), not '" + v + "'"); o.call_req.max_aDP = (int32_t)x; o.call_req_given = true; }
+        else if (n0 == "--msi-out") { o.msi_out = val(); if (o.msi_out.empty()) die("--msi-out needs a path"); }
+        else if (n0 == "--msi-min-tract" || n0 == "--msi-min-units" || n0 == "--msi-max-unit" || n0 == "--msi-min-depth" || n0 == "--msi-unstable-permille") {
+            const std::string v = val(); double x; const bool permille = (n0 == "--msi-unstable-permille");
+            if (!number(v, &x) || v == "true" || v == "false" || x < (permille ? 0 : 1) || x != (double)(int64_t)x || x > 2e9) die(n0 + (permille ? " takes thousandths of the depth (a whole number >= 0), not '" : " takes a whole number of at least 1, not '") + v + "'");
+            (n0 == "--msi-min-tract" ? o.msi_req.min_tracklen : n0 == "--msi-min-units" ? o.msi_req.min_units : n0 == "--msi-max-unit" ? o.msi_req.max_unitlen : n0 == "--msi-min-depth" ? o.msi_min_depth : o.msi_unstable_permille) = (int32_t)x;
+            o.msi_sub_given = true;
+        }
         else if (n0 == "--read-profile-out") { o.readprof_out = val(); if (o.readprof_out.empty()) die("--read-profile-out needs a path"); }
         else if (n0 == "--read-profile-min-mapq") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 255) die("--read-profile-min-mapq takes a mapping quality from 0 to 255, not '" + v + "'"); o.readprof_req.min_mapq = (int32_t)x; o.readprof_gate_given = true; }
         else if (n0 == "--read-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--read-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.readprof_req.min_depth = (int32_t)x; o.readprof_gate_given = true; }
@@ -405,6 +421,9 @@ Opts parse(int argc, char **argv) {
     if (o.callable_out.empty()) {
         if (o.call_req_given) die("--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file");
     } else refuse_report_runs(o, "--callable-out", "a target can straddle shards", "every tile would report its runs that many times");
+    if (o.msi_out.empty()) {
+        if (o.msi_sub_given) die("--msi-min-tract, --msi-min-units, --msi-max-unit, --msi-min-depth and --msi-unstable-permille need --msi-out: they only shape that file");
+    } else refuse_report_runs(o, "--msi-out", "a target can straddle shards", "every tile would report its loci that many times");
     if (o.readprof_out.empty()) {
         if (o.readprof_gate_given) die("--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report");
     } else refuse_report_runs(o, "--read-profile-out", "every shard would write a part of the profile", "every tile would be counted that many times");
@@ -434,7 +453,7 @@ void print_params(const Opts &o, const char *prefix = "") {
 // `run_beg` = begin of the run (incluBegPosition of the BED line the run came from, main.cpp:655-656).
 // `target` (--coverage-out with a BED file): the report row of the BED line the tile was cut from.
 // `fam_target` (--family-stats-out with a BED file): the same for the family report.
-// `call_target` (--callable-out): the store's target the tile was cut from; -1 (the reference's own cuts): the called span of its contig.
+// `call_target` (--callable-out, --msi-out): the store's target the tile was cut from; -1 (the reference's own cuts): the called span of its contig.
 struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; int64_t fam_target = -1; int64_t call_target = -1; };
 
 // one worker: its own handles, one region handle for all of its tiles
@@ -453,6 +472,7 @@ struct Worker {
     std::vector<UvcFamilyRange> fam_ranges; std::vector<int64_t> fam_targets, fam_rows;   // --family-stats-out: the pieces of one tile
     std::vector<UvcCoverageRange> rp_ranges; std::vector<int64_t> rp_row;   // --read-profile-out: the stretches one tile owns, its row
     std::vector<UvcCoverageRange> call_ranges; std::vector<int64_t> call_targets; std::vector<UvcCallableRun> call_runs;   // --callable-out: the pieces of one tile, their runs
+    std::vector<UvcCoverageRange> msi_ranges; std::vector<int64_t> msi_targets; std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the pieces of one tile, their loci
 };
 
 // --coverage-out: the pieces of targets that one accumulated tile owns, reduced by one uvcgpu_region_coverage and merged into the report.
@@ -515,6 +535,35 @@ void callable_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int6
     }
     if (rc) die(uvcgpu_last_error());
     if (uvcio_callable_add_runs(o.callable, w.call_targets.data(), (int64_t)w.call_targets.size(), w.call_runs.data(), n)) die(uvcio_last_error());
+}
+// --msi-out: the loci whose head lies in the stretches one accumulated tile owns -- the list coverage_of_tile reports on, clipped to the
+// targets as for --callable-out -- by one uvcgpu_region_msi (sizes first: the buffer of the last tiles, grown where a tile has more loci),
+// handed to the store with each stretch's target and each locus's first unit as text.  ref: the reference bases of the region from ref_beg on.
+void msi_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of, const std::string &ref, int64_t ref_beg) {
+    w.msi_ranges.clear(); w.msi_targets.clear();
+    for (size_t q = 0; q < own.size(); q++) {
+        if (target_of[q] < 0) die("--msi-out: a tile without a target (internal error)");
+        const std::pair<int64_t, int64_t> &span = o.call_target_span[(size_t)target_of[q]];
+        const int64_t b = std::max(own[q].first, span.first), e = std::min(own[q].second, span.second);
+        if (e > b) { w.msi_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.msi_targets.push_back(target_of[q]); }
+    }
+    if (w.msi_ranges.empty()) return;
+    int64_t n = 0;
+    int rc = uvcgpu_region_msi(w.reg, w.msi_ranges.data(), (int64_t)w.msi_ranges.size(), &o.msi_req, w.msi_rows.data(), (int64_t)(w.msi_rows.size() / UVC_MSI_ROW), &n);
+    if (rc == UVCGPU_ENOMEM && n > (int64_t)(w.msi_rows.size() / UVC_MSI_ROW)) {
+        w.msi_rows.resize((size_t)n * UVC_MSI_ROW);
+        rc = uvcgpu_region_msi(w.reg, w.msi_ranges.data(), (int64_t)w.msi_ranges.size(), &o.msi_req, w.msi_rows.data(), n, &n);
+    }
+    if (rc) die(uvcgpu_last_error());
+    w.msi_units.resize((size_t)n); w.msi_unit_ptrs.resize((size_t)n);
+    for (int64_t q = 0; q < n; q++) {
+        const int32_t *row = &w.msi_rows[(size_t)q * UVC_MSI_ROW];
+        const int64_t at = (int64_t)row[UVC_MSI_pos_beg] - ref_beg;   // (a tract lies inside the reference bases of its region)
+        w.msi_units[(size_t)q] = (at >= 0 && at + row[UVC_MSI_unitlen] <= (int64_t)ref.size()) ? ref.substr((size_t)at, (size_t)row[UVC_MSI_unitlen]) : std::string(".");
+        for (char &c : w.msi_units[(size_t)q]) c = (char)toupper((unsigned char)c);
+        w.msi_unit_ptrs[(size_t)q] = w.msi_units[(size_t)q].c_str();
+    }
+    if (uvcio_msi_add(o.msi, w.msi_targets.data(), (int64_t)w.msi_targets.size(), w.msi_rows.data(), w.msi_unit_ptrs.data(), n)) die(uvcio_last_error());
 }
 // --family-stats-out: the pieces of targets that the tiles own, planned before any worker starts (plan_family_pieces), so that the report
 // does not depend on which worker takes which tile.  A piece is a tile's [beg, end), cut at the window borders in window mode: the planned
@@ -616,8 +665,8 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     // uvcio_sites_fetch go by, without the end point t.end itself, which lies outside every target the tile was cut from (and which two regions of
     // the reference's cuts share).  The list depends on scored() alone: made here, in front of accumulate, for the report of the reads as well.
     std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
-    if (o.cov || o.errprof || o.callable || o.readprof) {
-        auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !o.callable ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
+    if (o.cov || o.errprof || o.callable || o.readprof || o.msi) {
+        auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !(o.callable || o.msi) ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
         for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) {   // (n_merged = 0: t0_ alone)
             const Tile &l = (&t0_)[q];
             own.emplace_back(scored(l).first, std::min(scored(l).second, l.end)); target_of.push_back(l.target); call_target_of.push_back(call_target(l));
@@ -625,10 +674,11 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     }
     if (o.readprof) readprofile_of_tile(w, o, own);   // the BAM's own qualities: in front of the correction
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
-    if (o.cov || o.errprof || o.callable) {
+    if (o.cov || o.errprof || o.callable || o.msi) {
         if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
         if (o.errprof) errprofile_of_tile(w, o, own);
         if (o.callable) callable_of_tile(w, o, own, call_target_of);
+        if (o.msi) msi_of_tile(w, o, own, call_target_of, w.ref, ext_beg);
     }
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
@@ -768,7 +818,15 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     std::vector<int32_t> pl_tid, pl_pos, pl_end; std::vector<uint16_t> pl_flag;   // one window's columns
     auto take_cuts = [&]() { UvcRegionCut c[256]; int64_t k; while ((k = uvcio_planner_take(planner, c, 256)) > 0) for (int64_t q = 0; q < k; q++) tiles.push_back(Tile{ c[q].tid, names[(size_t)c[q].tid], c[q].beg, c[q].end, false, false, c[q].beg }); };
     int64_t cov_target = -1, fam_target = -1, call_target = -1;   // the report rows of the BED line being added
-    if (o.callable) o.call_contig_target.assign((size_t)nref, -1);
+    if (o.callable || o.msi) o.call_contig_target.assign((size_t)nref, -1);
+    // a target of --callable-out and --msi-out: both stores take the same targets in the same order, so one index names it in both
+    auto add_span_target = [&](const char *chrom, int64_t beg, int64_t end, const char *name) {
+        const int64_t tc = o.callable ? uvcio_callable_add_target(o.callable, chrom, beg, end, name) : -1, tm = o.msi ? uvcio_msi_add_target(o.msi, chrom, beg, end, name) : -1;
+        if ((o.callable && tc < 0) || (o.msi && tm < 0)) die(uvcio_last_error());
+        if (o.callable && o.msi && tc != tm) die("--callable-out and --msi-out disagree on a target's index (internal error)");
+        o.call_target_span.emplace_back(beg, std::max(beg, end));
+        return o.callable ? tc : tm;
+    };
     auto add = [&](int32_t tid, int64_t beg, int64_t end) {
         // window mode of a report: the windows of this span become its targets, in order; the span keeps the row of the first
         auto window_targets = [&](const char *wopt, int64_t N, CovSpan &sp, auto add_target) {
@@ -785,11 +843,9 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
             window_targets("--coverage-window", o.coverage_window, (*cov_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_coverage_add_target(o.cov, chrom, wb, we, nullptr, we - wb); });
         if (o.fam && fam_spans && o.famstats_window > 0 && end > beg)
             window_targets("--family-stats-window", o.famstats_window, (*fam_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_famstats_add_target(o.fam, chrom, wb, we, nullptr); });
-        if (o.callable && bed_path.empty()) {   // --callable-out without a BED file: the called span of the contig is one target
-            if (o.call_contig_target[(size_t)tid] >= 0) die("--callable-out: a contig is called twice (internal error)");
-            call_target = o.call_contig_target[(size_t)tid] = uvcio_callable_add_target(o.callable, names[(size_t)tid].c_str(), beg, end, nullptr);
-            if (call_target < 0) die(uvcio_last_error());
-            o.call_target_span.emplace_back(beg, std::max(beg, end));
+        if ((o.callable || o.msi) && bed_path.empty()) {   // --callable-out, --msi-out without a BED file: the called span of the contig is one target
+            if (o.call_contig_target[(size_t)tid] >= 0) die("--callable-out, --msi-out: a contig is called twice (internal error)");
+            call_target = o.call_contig_target[(size_t)tid] = add_span_target(names[(size_t)tid].c_str(), beg, end, nullptr);
         }
         if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target, fam_target, call_target }); return; }
         const int64_t W = 4000000;   // the planning pass reads the span window by window; an alignment is taken by the window it starts in (the first window also takes those that reach into it)
@@ -828,11 +884,8 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
                 fam_target = uvcio_famstats_add_target(o.fam, chrom, b, e, n_col >= 4 ? bname : nullptr);
                 if (fam_target < 0) die(uvcio_last_error());
             }
-            if (o.callable) {   // one target per BED line: its positions inside the contig, column 4 as the name
-                call_target = uvcio_callable_add_target(o.callable, chrom, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]), n_col >= 4 ? bname : nullptr);
-                if (call_target < 0) die(uvcio_last_error());
-                o.call_target_span.emplace_back(std::max<long long>(0, b), std::max<long long>(std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid])));
-            }
+            if (o.callable || o.msi)   // one target per BED line: its positions inside the contig, column 4 as the name
+                call_target = add_span_target(chrom, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]), n_col >= 4 ? bname : nullptr);
             add(tid, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]));
             l_tid.push_back(tid); l_beg.push_back(std::max<long long>(0, b)); l_end.push_back(std::min<long long>(e, lens[(size_t)tid]));
         }
@@ -1009,6 +1062,7 @@ PairArgs split_pair(int argc, char **argv) {
         no_report({ "--error-profile-out", "--error-profile-min-depth", "--error-profile-max-alt-permille" }, "error profile");
         no_report({ "--callable-out", "--callable-min-depth", "--callable-max-aDP" }, "callable regions");
         no_report({ "--family-stats-out", "--family-stats-window" }, "family report");
+        no_report({ "--msi-out", "--msi-min-tract", "--msi-min-units", "--msi-max-unit", "--msi-min-depth", "--msi-unstable-permille" }, "microsatellite tally");
         no_report({ "--read-profile-out", "--read-profile-min-mapq", "--read-profile-min-depth", "--read-profile-max-alt-permille" }, "read profile");
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
@@ -1287,6 +1341,7 @@ int main(int argc, char **argv) {
         for (int32_t b = 0; b < UVC_NCALLBIT; b++) bnames[b] = uvcgpu_callable_bit_name(b);
         if (uvcio_callable_open(&o.callable, mnames, UVC_NCOV, o.call_req.min_depth, o.call_req.max_aDP, bnames, UVC_NCALLBIT)) die(uvcio_last_error());
     }
+    if (!o.msi_out.empty() && !o.print_params && uvcio_msi_open(&o.msi, o.msi_req.min_tracklen, o.msi_req.min_units, o.msi_req.max_unitlen, o.msi_min_depth, o.msi_unstable_permille)) die(uvcio_last_error());
     if (!o.readprof_out.empty() && !o.print_params) {
         const char *cnames[UVC_READPROF_NCLASS]; for (int32_t c = 0; c < UVC_READPROF_NCLASS; c++) cnames[c] = uvcgpu_read_class_name(c);
         if (uvcio_readprofile_open(&o.readprof, cnames, o.readprof_req.min_mapq, o.readprof_req.min_depth, o.readprof_req.max_alt_permille)) die(uvcio_last_error());
@@ -1348,6 +1403,7 @@ int main(int argc, char **argv) {
     if (o.cov) probe_create("--coverage-out", o.coverage_out);
     if (o.fam) probe_create("--family-stats-out", o.famstats_out);
     if (o.callable) probe_create("--callable-out", o.callable_out);
+    if (o.msi) probe_create("--msi-out", o.msi_out);
     if (o.errprof) probe_create("--error-profile-out", o.errprof_out);
     if (o.readprof) probe_create("--read-profile-out", o.readprof_out);
     if (!o.no_header) {
@@ -1402,6 +1458,10 @@ int main(int argc, char **argv) {
     if (o.callable) {
         if (o.timing) fprintf(stderr, "uvc1-mi355x: --callable-out holds %lld runs\n", (long long)uvcio_callable_n_runs(o.callable));
         finish("--callable-out", uvcio_callable_write(o.callable, o.callable_out.c_str())); uvcio_callable_close(o.callable);
+    }
+    if (o.msi) {
+        if (o.timing) fprintf(stderr, "uvc1-mi355x: --msi-out holds %lld loci\n", (long long)uvcio_msi_n_loci(o.msi));
+        finish("--msi-out", uvcio_msi_write(o.msi, o.msi_out.c_str())); uvcio_msi_close(o.msi);
     }
     if (o.errprof) { finish("--error-profile-out", uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())); uvcio_errprofile_close(o.errprof); }
     if (o.readprof) { finish("--read-profile-out", uvcio_readprofile_write(o.readprof, o.readprof_out.c_str())); uvcio_readprofile_close(o.readprof); }

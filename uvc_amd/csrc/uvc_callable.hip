@@ -144,12 +144,13 @@ __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, i
 
 extern "C" const char *uvc_callable_name(int bit) { return (bit >= 0 && bit < UVC_NCALLBIT) ? CALL_NAMES[bit] : nullptr; }
 extern "C" int64_t uvc_callable_blocks(int64_t n_total) { return (n_total + CALL_TILE - 1) / CALL_TILE; }
+extern "C" void uvc_launch_block_scan(int *d_cnt, int n_blocks, hipStream_t s) { hipLaunchKernelGGL(k_callable_scan, dim3(1), dim3(256), 0, s, d_cnt, n_blocks); }
 // d_tab: n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one receives the number of runs
 extern "C" void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s) {
     if (n_ranges <= 0 || n_total <= 0) return;
     const int n_blocks = (int)uvc_callable_blocks(n_total);
     hipLaunchKernelGGL(k_callable_count, dim3((unsigned)n_blocks), dim3(256), 0, s, *R, d_tab, n_ranges, (int)n_total, *req, d_mask, d_blocks);
-    hipLaunchKernelGGL(k_callable_scan, dim3(1), dim3(256), 0, s, d_blocks, n_blocks);
+    uvc_launch_block_scan(d_blocks, n_blocks, s);
 }
 // after uvc_launch_callable_count with the same arguments; d_runs: room for d_blocks[n_blocks] runs
 extern "C" void uvc_launch_callable_emit(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const unsigned char *d_mask, const int *d_blocks, UvcCallableRun *d_runs, hipStream_t s) {

@@ -1413,8 +1413,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable and _read_profile ----
-// What the five share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile and _msi ----
+// What the six share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1665,6 +1665,59 @@ int uvcgpu_region_callable(uvcgpu_region_t *r, const UvcCoverageRange *ranges, i
     return guarded("uvcgpu_region_callable", [&] { return uvcgpu_region_callable_impl(r, ranges, n_ranges, req, runs, run_capacity, n_runs); });
 }
 const char *uvcgpu_callable_bit_name(int32_t bit) { return uvc_callable_name(bit); }
+
+// ---- microsatellite loci of ranges (uvc_msi.hip): [table] [block counts] [head list, `room` ints] [rows, `room` x UVC_MSI_ROW ints] ----
+// Sizes first, in one pass where the buffer allows: every kernel is launched with the room the device buffer has (at most the caller's),
+// the kernels read the number of loci on the device, and the host reads it (4 bytes) when all have run.  A call whose room was too small
+// for loci the caller has room for lays the buffer out for that number and runs once more; a call without room runs the count alone.
+static int uvcgpu_region_msi_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcMsiRequest *req, int32_t *loci, int64_t locus_capacity, int64_t *n_loci) {
+    { int rc1 = report_guard(r, "msi", "search"); if (rc1) return rc1; }
+    if (!ranges || !req || !n_loci) return fail(UVCGPU_EINVAL, "msi: ranges, req and n_loci must not be NULL");
+    if (locus_capacity < 0) return fail(UVCGPU_EINVAL, "msi: locus_capacity " + std::to_string(locus_capacity) + " is negative");
+    if (!loci && locus_capacity > 0) return fail(UVCGPU_EINVAL, "msi: loci is NULL with locus_capacity " + std::to_string(locus_capacity));
+    if (req->min_tracklen < 1) return fail(UVCGPU_EINVAL, "msi: min_tracklen " + std::to_string(req->min_tracklen) + " must be at least 1");
+    if (req->min_units < 1) return fail(UVCGPU_EINVAL, "msi: min_units " + std::to_string(req->min_units) + " must be at least 1");
+    if (req->max_unitlen < 1) return fail(UVCGPU_EINVAL, "msi: max_unitlen " + std::to_string(req->max_unitlen) + " must be at least 1");
+    { int rc1 = range_count("msi", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "msi", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
+    const int64_t n_blocks = uvc_msi_blocks(n_total);
+    const size_t row_bytes = sizeof(int32_t) * UVC_MSI_ROW;
+    ReportLayout L0;
+    const size_t o_tab = L0.take(sizeof(UvcRangeRow) * tab.size()), o_blocks = L0.take(sizeof(int32_t) * (size_t)(n_blocks + 1));
+    // the loci the buffer as it is has room for behind the fixed pieces (never more than the positions of the call, each of which can be a head)
+    int64_t room = 0;
+    if (locus_capacity > 0 && r->d_report_bytes > L0.bytes + 128) room = std::min({ locus_capacity, n_total, (int64_t)((r->d_report_bytes - L0.bytes - 128) / (row_bytes + sizeof(int32_t))) });
+    // the allele pipeline of the accumulate ran on the side stream: behind it, as gap_tables waits for it (no host wait here)
+    if (r->side) HIP_OK(hipStreamWaitEvent(r->stream, r->e_fork2, 0));
+    int32_t n = 0;
+    int32_t *d_rows = nullptr;
+    for (;;) {
+        ReportLayout L = L0;
+        const size_t o_heads = L.take(sizeof(int32_t) * (size_t)room), o_rows = L.take(row_bytes * (size_t)room);
+        { int rc1 = report_begin(r, L, 64, "msi loci", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+        int *d_blocks = (int *)(r->d_report + o_blocks);
+        d_rows = (int32_t *)(r->d_report + o_rows);
+        if (room) HIP_OK(hipMemsetAsync(d_rows, 0, row_bytes * (size_t)room, r->stream));
+        // with profiling on, one more entry of uvcgpu_region_kernel_times (accumulate starts the list anew); a call that runs twice adds two
+        const int pi = uvc_prof_begin(&r->prof, "k_msi", r->stream);
+        uvc_launch_msi(&r->R, (const UvcRangeRow *)(r->d_report + o_tab), (int)n_ranges, n_total, req, d_blocks, (int32_t *)(r->d_report + o_heads), d_rows, room, r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
+        { int rc1 = report_result(r, d_blocks + n_blocks, &n, sizeof(int32_t), true); if (rc1) return rc1; }
+        if (n <= room || n > locus_capacity) break;
+        room = n;
+    }
+    *n_loci = n;
+    if (n > locus_capacity) return fail(UVCGPU_ENOMEM, "msi: " + std::to_string(n) + " loci, room for " + std::to_string(locus_capacity));
+    if (n == 0) return 0;
+    const size_t out_bytes = row_bytes * (size_t)n;
+    { int rc1 = report_buffers(r, 0, out_bytes, "msi loci"); if (rc1) return rc1; }
+    return report_result(r, d_rows, loci, out_bytes, true);
+}
+int uvcgpu_region_msi(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcMsiRequest *req, int32_t *loci, int64_t locus_capacity, int64_t *n_loci) {
+    return guarded("uvcgpu_region_msi", [&] { return uvcgpu_region_msi_impl(r, ranges, n_ranges, req, loci, locus_capacity, n_loci); });
+}
+const char *uvcgpu_msi_section_name(int32_t id) { return uvc_msi_name(id); }
 
 int uvcgpu_region_create(uvcgpu_region_t **out, const UvcParams *params, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_create", [&] { return uvcgpu_region_create_impl(out, params, tid, beg, end, refseq); }); }
 int uvcgpu_region_reset(uvcgpu_region_t *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) { return guarded("uvcgpu_region_reset", [&] { return uvcgpu_region_reset_impl(r, tid, beg, end, refseq); }); }

@@ -1209,7 +1209,7 @@ extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t po
 extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }
 
 // ---------------------------------------------------------------- the report stores ----
-// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out and --read-profile-out share: a store collects what the tiles
+// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out and --msi-out share: a store collects what the tiles
 // report under its mutex and writes the whole file at the end.
 // a target as the stores with target lines keep it; a BED line without a name is "."
 struct ReportTarget { std::string chrom, name; int64_t beg, end; };
@@ -1540,3 +1540,86 @@ extern "C" int uvcio_callable_write(const uvcio_callable_t *c, const char *path)
     return write_text(path, text);
 }
 extern "C" void uvcio_callable_close(uvcio_callable_t *c) { delete c; }
+
+// ---------------------------------------------------------------- the microsatellite tally ----
+struct uvcio_msi {
+    int32_t min_tracklen = 0, min_units = 0, max_unitlen = 0, min_depth = 0, unstable_permille = 0;
+    struct Locus { int32_t target; std::string unit; int32_t w[UVC_MSI_ROW]; };   // kept to the end: the file is written in target order
+    std::vector<ReportTarget> targets; std::vector<Locus> loci;
+    std::mutex mu;
+};
+static const char *const MSI_LEVELS[UVC_MSI_NLEVEL] = { "b", "c", "c2", "d" };   // beside bDP, cDP12, cDP2, dDP1: fragments, families, consensus families, duplex families
+extern "C" int uvcio_msi_open(uvcio_msi_t **out, int32_t min_tracklen, int32_t min_units, int32_t max_unitlen, int32_t min_depth, int32_t unstable_permille) {
+    if (!out || min_tracklen < 1 || min_units < 1 || max_unitlen < 1 || min_depth < 1 || unstable_permille < 0) return fail(UVCGPU_EINVAL, "msi report: bad argument");
+    uvcio_msi *m = new uvcio_msi;
+    m->min_tracklen = min_tracklen; m->min_units = min_units; m->max_unitlen = max_unitlen; m->min_depth = min_depth; m->unstable_permille = unstable_permille;
+    *out = m;
+    return 0;
+}
+extern "C" int64_t uvcio_msi_add_target(uvcio_msi_t *m, const char *chrom, int64_t beg, int64_t end, const char *name) {
+    if (!m || !chrom || beg < 0 || end > INT32_MAX) return fail(UVCGPU_EINVAL, "msi report: bad target");
+    std::lock_guard<std::mutex> g(m->mu);
+    m->targets.push_back(report_target(chrom, name, beg, std::max(beg, end)));
+    return (int64_t)m->targets.size() - 1;
+}
+extern "C" int uvcio_msi_add(uvcio_msi_t *m, const int64_t *target_of_range, int64_t n_ranges, const int32_t *loci, const char *const *units, int64_t n_loci) {
+    if (!m || n_loci < 0 || n_ranges < 0 || (n_loci > 0 && (!loci || !units || !target_of_range))) return fail(UVCGPU_EINVAL, "msi report: bad loci");
+    std::lock_guard<std::mutex> g(m->mu);
+    for (int64_t q = 0; q < n_loci; q++) {   // all of the call's loci or none
+        const int32_t *w = loci + q * UVC_MSI_ROW;
+        if (w[0] < 0 || w[0] >= n_ranges) return fail(UVCGPU_EINVAL, "msi report: locus " + std::to_string(q) + " names range " + std::to_string(w[0]) + " of " + std::to_string(n_ranges));
+        const int64_t t = target_of_range[w[0]];
+        if (t < 0 || t >= (int64_t)m->targets.size()) return fail(UVCGPU_EINVAL, "msi report: locus of target " + std::to_string(t) + ", which does not exist");
+        if (w[1] < m->targets[(size_t)t].beg || w[1] >= m->targets[(size_t)t].end || w[2] < 1 || w[3] < 1 || !units[q])
+            return fail(UVCGPU_EINVAL, "msi report: locus " + std::to_string(q) + " at " + std::to_string(w[1]) + " begins outside target " + std::to_string(t) + " or has no unit");
+    }
+    for (int64_t q = 0; q < n_loci; q++) {
+        uvcio_msi::Locus l; l.target = (int32_t)target_of_range[loci[q * UVC_MSI_ROW]]; l.unit = units[q];
+        memcpy(l.w, loci + q * UVC_MSI_ROW, sizeof(l.w));
+        m->loci.push_back(l);
+    }
+    return 0;
+}
+extern "C" int64_t uvcio_msi_n_loci(const uvcio_msi_t *m) { return m ? (int64_t)m->loci.size() : 0; }
+extern "C" int uvcio_msi_write(const uvcio_msi_t *m, const char *path) {
+    if (!m || !path || !*path) return fail(UVCGPU_EINVAL, "msi report: bad argument");
+    std::string text = "##msi_loci=1\n"
+        "## A tally for a downstream classifier that has a baseline, NOT an MSI call: per microsatellite of the caller's own repeat tracks the\n"
+        "## smallest depth along the tract and the InDel alleles that change its length by whole units (shifted) or otherwise (other), per\n"
+        "## evidence level: b fragments, c UMI families, c2 consensus families, d duplex families.  A heterozygous germline length allele counts\n"
+        "## as shifted.  EDGE: the tract touches the end of the region it was seen in; nothing was counted.\n";
+    text += "#min_tract\t" + std::to_string(m->min_tracklen) + "\n#min_units\t" + std::to_string(m->min_units) + "\n#max_unit\t" + std::to_string(m->max_unitlen) +
+            "\n#min_depth\t" + std::to_string(m->min_depth) + "\n#unstable_permille\t" + std::to_string(m->unstable_permille) + "\n";
+    text += "#chrom\tbeg\tend\tunit\tunitlen\tunits\ttarget\tflags";
+    for (int l = 0; l < UVC_MSI_NLEVEL; l++) {
+        const std::string L = MSI_LEVELS[l];
+        text += "\t" + L + "_depth\t" + L + "_shifted\t" + L + "_other";
+        for (int b = 0; b < UVC_MSI_OTHER; b++) { const int sh = b < UVC_MSI_MAXSHIFT ? b - UVC_MSI_MAXSHIFT : b - UVC_MSI_MAXSHIFT + 1; text += "\t" + L + (sh < 0 ? "_m" : "_p") + std::to_string(sh < 0 ? -sh : sh); }
+    }
+    text += "\n";
+    std::vector<const uvcio_msi::Locus *> order;
+    for (const uvcio_msi::Locus &l : m->loci) order.push_back(&l);
+    std::sort(order.begin(), order.end(), [](const uvcio_msi::Locus *a, const uvcio_msi::Locus *b) { return a->target != b->target ? a->target < b->target : a->w[1] < b->w[1]; });
+    int64_t n_edge = 0, assessable[UVC_MSI_NLEVEL] = { 0, 0, 0, 0 }, unstable[UVC_MSI_NLEVEL] = { 0, 0, 0, 0 };
+    for (const uvcio_msi::Locus *l : order) {
+        const ReportTarget &T = m->targets[(size_t)l->target];
+        const int32_t *w = l->w;
+        const bool edge = (w[4] & UVC_MSI_EDGE) != 0;
+        n_edge += edge;
+        text += T.chrom + "\t" + std::to_string(w[1]) + "\t" + std::to_string((int64_t)w[1] + w[2]) + "\t" + l->unit + "\t" + std::to_string(w[3]) + "\t" + std::to_string(w[2] / w[3]) + "\t" + T.name + "\t" + (edge ? "EDGE" : ".");
+        for (int lv = 0; lv < UVC_MSI_NLEVEL; lv++) {
+            const int32_t *h = w + UVC_MSI_HIST + lv * UVC_MSI_NBIN;
+            int64_t shifted = 0;
+            for (int b = 0; b < UVC_MSI_OTHER; b++) shifted += h[b];
+            const int64_t depth = w[UVC_MSI_DEPTH + lv];
+            text += "\t" + std::to_string(depth) + "\t" + std::to_string(shifted) + "\t" + std::to_string(h[UVC_MSI_OTHER]);
+            for (int b = 0; b < UVC_MSI_OTHER; b++) text += "\t" + std::to_string(h[b]);
+            if (!edge && depth >= m->min_depth) { assessable[lv]++; if (1000 * shifted >= (int64_t)m->unstable_permille * depth) unstable[lv]++; }
+        }
+        text += "\n";
+    }
+    text += "#summary\tloci\t" + std::to_string(order.size()) + "\n#summary\tloci_EDGE\t" + std::to_string(n_edge) + "\n";
+    for (int lv = 0; lv < UVC_MSI_NLEVEL; lv++) text += std::string("#summary\t") + MSI_LEVELS[lv] + "\tassessable\t" + std::to_string(assessable[lv]) + "\tunstable\t" + std::to_string(unstable[lv]) + "\n";
+    return write_text(path, text);
+}
+extern "C" void uvcio_msi_close(uvcio_msi_t *m) { delete m; }

@@ -307,6 +307,57 @@ class Callable:
         self.close()
 
 
+class Msi:
+    """uvcio_msi_*: the store behind uvc1-mi355x --msi-out.  Targets are added in report order with their positions inside the contig; add
+    takes the rows of one Region.msi, the target of each of its ranges and the first unit of each locus as text (any thread, any order);
+    write() sorts by target then position and makes the tab-separated text with its #summary lines."""
+
+    def __init__(self, min_tracklen=10, min_units=5, max_unitlen=6, min_depth=30, unstable_permille=200):
+        d = dll()
+        d.uvcio_msi_open.restype, d.uvcio_msi_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        d.uvcio_msi_add_target.restype, d.uvcio_msi_add_target.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
+        d.uvcio_msi_add.restype, d.uvcio_msi_add.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_char_p), C.c_int64]
+        d.uvcio_msi_n_loci.restype, d.uvcio_msi_n_loci.argtypes = C.c_int64, [C.c_void_p]
+        d.uvcio_msi_write.restype, d.uvcio_msi_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
+        d.uvcio_msi_close.restype, d.uvcio_msi_close.argtypes = None, [C.c_void_p]
+        self.h = C.c_void_p()
+        _check(d.uvcio_msi_open(C.byref(self.h), int(min_tracklen), int(min_units), int(max_unitlen), int(min_depth), int(unstable_permille)))
+
+    def add_target(self, chrom, beg, end, name=None):
+        t = dll().uvcio_msi_add_target(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
+        if t < 0:
+            _check(int(t))
+        return int(t)
+
+    def add(self, target_of_range, loci, units):
+        """loci: the int32 [n][UVC_MSI_ROW] array of Region.msi; units[k]: the reference bases of the first unit of locus k;
+        target_of_range[k]: the target of the call's range k"""
+        import numpy as np
+        loci = np.ascontiguousarray(loci, dtype=np.int32)
+        if loci.ndim != 2 or len(units) != len(loci):
+            raise ValueError("loci are the rows of Region.msi, one unit text each")
+        tor = np.ascontiguousarray(target_of_range, dtype=np.int64)
+        texts = (C.c_char_p * max(len(units), 1))(*[u.encode() for u in units])
+        _check(dll().uvcio_msi_add(self.h, tor.ctypes.data, len(tor), loci.ctypes.data, texts, len(loci)))
+
+    def n_loci(self):
+        return int(dll().uvcio_msi_n_loci(self.h))
+
+    def write(self, path):
+        _check(dll().uvcio_msi_write(self.h, str(path).encode()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            dll().uvcio_msi_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def plan_regions(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per_thread_mb=1536):
     """SamIter::iternext without a BED file (grouping.cpp:225-312) over alignment columns in file order: the blocks the reference hands
     to process_batch, as dicts (tid, beg, end, flag, batch, n_reads)."""

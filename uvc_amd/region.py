@@ -554,6 +554,25 @@ class Region:
         self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data, n.value, C.byref(n)))
         return out[:n.value].copy()
 
+    def msi(self, ranges, min_tracklen=10, min_units=5, max_unitlen=6):
+        """uvcgpu_region_msi: the microsatellite loci whose head lies in `ranges` -- (pos_beg, pos_end) pairs as for coverage() -- as the STR
+        planes of the region name them: tracts of at least min_tracklen bp and min_units whole units of at most max_unitlen bp.  int32
+        [n_loci, UVC_MSI_ROW], sorted by position: range, pos_beg, tracklen, unitlen, flags (UVC_MSI_EDGE: the tract touches an end of the
+        region; nothing was counted), depth[4] (the smallest bDP, cDP12, cDP2, dDP1 along the tract) and hist[4][13] (per level the InDel
+        alleles that shift the tract by -6..-1, +1..+6 whole units, then OTHER); _ffi.MSI_SECTIONS names the sections, uvcgpu.h has the
+        rules.  Found and tallied on the device; asks for the size first, then for the rows.  After accumulate() and before anything that
+        releases the planes."""
+        fn = self._ranges_fn("region_msi", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        arr, rows = _coverage_ranges(ranges)
+        req = _ffi.UvcMsiRequest(int(min_tracklen), int(min_units), int(max_unitlen))
+        n = C.c_int64(0)
+        rc = fn(self.h, arr, len(rows), C.byref(req), None, 0, C.byref(n))
+        if rc != _ffi.ENUMS["UVCGPU_ENOMEM"]:
+            self._check(rc)
+        out = np.zeros((max(n.value, 1), _ffi.ENUMS["UVC_MSI_ROW"]), dtype=np.int32)
+        self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value].copy()
+
     def score_stream_bytes_per_record(self):
         return self._ranges_fn("score_stream_bytes_per_record", C.c_int64, [])()
 
