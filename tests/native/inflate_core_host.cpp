@@ -5,3 +5,8 @@ extern "C" int inflate_core_host(const uint8_t *in, uint32_t in_len, uint8_t *ou
     static thread_local InflState S;
     return uvc_inflate_block(in, in_len, out, out_len, S);
 }
+// the same body at the table widths of the wave-per-block kernels (10 / 9 bits): their lane-form path, as far as the host can reach it
+extern "C" int inflate_core_host_10_9(const uint8_t *in, uint32_t in_len, uint8_t *out, uint32_t out_len) {
+    static thread_local InflStateT<10, 9> S;
+    return uvc_inflate_block_t<false, 10, 9>(in, in_len, out, out_len, S, 0u);
+}

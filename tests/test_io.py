@@ -329,3 +329,67 @@ def test_fast_inflate_equals_zlib_on_every_block_type():
         out.raw = b"\xAA" * (len(data) + 16)
         f(bytes(comp), len(comp), out, len(data))
         assert out.raw[len(data):] == b"\xAA" * 16
+
+
+def _fast_inflate(comp, isize):
+    """uvcio_inflate_raw_fast on one stream with a 64-byte guard behind the output: (1 decoded / 0 declined, the ISIZE bytes, guard untouched)"""
+    import ctypes
+    f = uio.dll().uvcio_inflate_raw_fast
+    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int64]
+    out = ctypes.create_string_buffer(isize + 64)
+    out.raw = b"\xAB" * (isize + 64)
+    rc = f(comp, len(comp), out, isize)
+    return rc, out.raw[:isize], out.raw[isize:] == b"\xAB" * 64
+
+
+def test_fast_inflate_on_streams_zlibs_compressor_never_writes():
+    """tests/deflate_streams.py: deep codes through the sub-tables, mixed block types at odd bit offsets, empty blocks, matches into earlier
+    blocks, degenerate distance alphabets, every length / distance symbol at both ends of its extra bits.  zlib's inflater is the reference
+    for every stream.  The decoder may decline only a stream whose literal/length alphabet is a single code (the reader then falls back to
+    zlib); everything else it must decode, to the same bytes, without touching what lies behind ISIZE."""
+    import zlib
+    import deflate_streams
+    cases = deflate_streams.catalogue()
+    declined = []
+    for c in cases:
+        d = zlib.decompressobj(-15)
+        assert d.decompress(c.comp) == c.out and d.eof and d.unused_data == b"", c.name
+        rc, got, guard_ok = _fast_inflate(c.comp, len(c.out))
+        assert guard_ok, c.name
+        if rc: assert got == c.out, c.name
+        else: declined.append(c.name)
+    assert all(c.single_ll_code for c in cases if c.name in declined), declined
+    assert declined == ["stored_then_eob_only_dynamic"]                    # a dynamic block of nothing but an end-of-block code: legal, declined, zlib's
+
+
+def test_fast_inflate_declines_structured_invalid_streams():
+    import zlib
+    import deflate_streams
+    for c in deflate_streams.invalid_catalogue():
+        if c.zlib_raises:
+            with pytest.raises(zlib.error):
+                zlib.decompress(c.comp, -15)
+        else: assert len(zlib.decompress(c.comp, -15)) != c.isize, c.name  # a legal stream that misses ISIZE, which zlib is not told
+        rc, _, guard_ok = _fast_inflate(c.comp, c.isize)
+        assert rc == 0, c.name
+        assert guard_ok, c.name
+
+
+def test_fast_inflate_and_bytes_behind_the_final_block():
+    """Pinned: like the decoder core (tests/test_inflate.py) the fast decoder stops at the end of the final block and returns success whatever
+    follows it -- as zlib's inflater does, which reports the rest as unused.  The reader's check of the block's CRC-32 and ISIZE is the
+    judge of the block.  An incomplete literal/length code, which the core accepts, this decoder declines: zlib then refuses the block."""
+    import zlib
+    import deflate_streams
+    s = deflate_streams.Stream().fixed(list(b"trailing") + [(20, 8)], final=True)
+    for tail in (b"\x00", b"\xff" * 3, b"\x00" * 9, b"\x5a" * 40):
+        d = zlib.decompressobj(-15)
+        assert d.decompress(s.getvalue() + tail) == bytes(s.out) and d.eof and d.unused_data == tail
+        rc, got, guard_ok = _fast_inflate(s.getvalue() + tail, len(s.out))
+        assert rc == 1 and got == bytes(s.out) and guard_ok, tail
+    name, incomplete, want = deflate_streams.lenient_catalogue()[0]
+    assert name == "incomplete_literal_code"
+    with pytest.raises(zlib.error):
+        zlib.decompress(incomplete, -15)
+    rc, _, guard_ok = _fast_inflate(incomplete, len(want))
+    assert rc == 0 and guard_ok

@@ -267,7 +267,8 @@ static bool inflate(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_l
     }
 #undef REFILL
 #undef TAKE
-    // every output byte written, no input bit invented, nothing but padding left (a BGZF payload ends with its last block)
+    // every output byte written and no input bit invented.  Whole bytes behind the final block are NOT looked at (zlib's inflate stops there
+    // as well): the caller's CRC-32 and ISIZE check of the output judges the block
     return op == out_end && over <= bc;
 }
 
