@@ -1,11 +1,16 @@
-"""The four report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable) share the rules of a range list and, the three
-plane readers, the lookup of a lane's range on the device.
-  * The same bad lists handed to all four raw entry points give the same return code and, behind the call's name, the same message; the
+"""The six report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi) share the rules of a range
+list and, the plane readers, the lookup of a lane's range on the device.
+  * The same bad lists handed to all six raw entry points give the same return code and, behind the call's name, the same message; the
     handle answers as before afterwards.
   * Range borders inside a wave, on wave borders, on the 256-position step and on the 1 024-position block of the callable kernels, with a
     total that is no multiple of 64: coverage, error profile and callable runs equal the restatements over the oracle's planes, value by value.
+  * The command line with all six reports in one run writes, report by report, the bytes of six runs with one report each.
 Every number is an integer and is compared for equality."""
 import ctypes as C
+import gzip
+import os
+import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -13,7 +18,7 @@ import pytest
 import callable_restatement as cr
 import errprofile_restatement as er
 import famstats_restatement as fr
-from test_gpu_coverage import measures_of, rows_of
+from test_gpu_coverage import EXE, measures_of, panel, rows_of
 from test_gpu_parity import CASES
 from util import run_region
 from uvc_amd import _ffi, region, synth
@@ -24,10 +29,12 @@ E = _ffi.ENUMS
 EINVAL = E["UVCGPU_EINVAL"]
 THR = [1, 3, 5]
 SENTINEL = -123456789
+RP_GATE = (0, 2, 500)   # read_profile: min_mapq, min_depth, max_alt_permille
+MSI_REQ = (4, 2, 6)     # msi: min_tracklen, min_units, max_unitlen (short tracts: 600 random bases have some)
 
 
 def raw_calls(lib, R):
-    """name -> call(ranges, n) -> (rc, message, the output buffers untouched) of the four entry points as the ABI has them"""
+    """name -> call(ranges, n) -> (rc, message, the output buffers untouched) of the six entry points as the ABI has them"""
     def bind(name, argtypes):
         fn = getattr(lib.dll, "uvcgpu_region_" + name)
         fn.restype, fn.argtypes = C.c_int, argtypes
@@ -36,6 +43,8 @@ def raw_calls(lib, R):
     err = bind("error_profile", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
     fam = bind("family_stats", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
     cal = bind("callable", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+    rpf = bind("read_profile", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p])
+    msi = bind("msi", [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
     thr = np.array(THR, np.int32)
 
     def pairs(ranges):
@@ -63,7 +72,17 @@ def raw_calls(lib, R):
         req = _ffi.UvcCallableRequest((C.c_int32 * E["UVC_NCOV"])(0, 0, 0, 3, 0, 0), 0)
         return done(cal(R.h, pairs(ranges), n, C.byref(req), out.ctypes.data, R.npos, n_runs.ctypes.data), out, n_runs)
 
-    return {"coverage": coverage, "error_profile": error_profile, "family_stats": family_stats, "callable": callable_}
+    def read_profile(ranges, n):
+        out = np.full(E["UVC_READPROF_ROW"], SENTINEL, np.int64)
+        req = _ffi.UvcReadProfileRequest(*RP_GATE)
+        return done(rpf(R.h, pairs(ranges), n, C.byref(req), out.ctypes.data), out)
+
+    def msi_(ranges, n):
+        out, n_loci = np.full((R.npos, E["UVC_MSI_ROW"]), SENTINEL, np.int32), np.full(1, SENTINEL, np.int64)
+        req = _ffi.UvcMsiRequest(*MSI_REQ)
+        return done(msi(R.h, pairs(ranges), n, C.byref(req), out.ctypes.data, R.npos, n_loci.ctypes.data), out, n_loci)
+
+    return {"coverage": coverage, "error_profile": error_profile, "family_stats": family_stats, "callable": callable_, "read_profile": read_profile, "msi": msi_}
 
 
 def test_the_four_calls_refuse_the_same_lists_in_the_same_words(oracle_lib, gpu_lib):
@@ -81,7 +100,11 @@ def test_the_four_calls_refuse_the_same_lists_in_the_same_words(oracle_lib, gpu_
 
     def answers():
         return dict(coverage=R.coverage(ok, THR), error_profile=R.error_profile(ok, 2, 500), family_stats=R.family_stats(fam_ok),
-                    callable=R.callable(ok, {"cDP12": 3}))
+                    callable=R.callable(ok, {"cDP12": 3}), read_profile=R.read_profile(ok, *RP_GATE), msi=R.msi(ok, *MSI_REQ))
+
+    # the two newer calls have their restatements in their own tests: here their answers before any refusal are what they answer after one
+    want.update((name, answers()[name]) for name in ("read_profile", "msi"))
+    assert want["read_profile"].any() and len(want["msi"]) > 0 and (want["msi"][:, E["UVC_MSI_range"]] < len(ok)).all()
 
     def assert_right(what):
         got = answers()
@@ -154,3 +177,36 @@ def test_range_borders_on_wave_step_and_block_borders(oracle_lib, gpu_lib):
             assert got.shape == want.shape and np.array_equal(got, want), ("callable", what, min_depth, max_aDP, np.flatnonzero(got != want)[:6] if got.shape == want.shape else (got.shape, want.shape))
             assert sorted(set(got["range"].tolist())) == list(range(len(lst)))   # every range has its runs, under its own index
     Rg.close()
+
+
+# ------------------------------------------------------------------------------------------------ command line: all six reports in one run
+REPORT_OPTS = {"--coverage-out": "--coverage-window", "--error-profile-out": None, "--family-stats-out": "--family-stats-window", "--callable-out": None,
+               "--msi-out": None, "--read-profile-out": None}
+
+
+@pytest.mark.parametrize("case", ["bed_tile_1000", "windows_tile_1700"])
+def test_all_six_reports_in_one_run_equal_six_runs_with_one_each(tmp_path, case):
+    """One worker's range and target lists serve every report of a tile in turn, and --callable-out and --msi-out share their targets: the
+    reports of a run that writes all six are, file by file, the bytes of six runs that write one each, and the seven VCFs are equal.  The
+    panel of test_gpu_coverage: several tiles per target, a target without reads, a target over a contig's end; two workers."""
+    assert os.path.exists(EXE), "build it: make -C uvc_amd/csrc"
+    d = str(tmp_path)
+    bam, fa, bed, _, _ = panel(d)
+    shared = ["-R", bed, "--tile", "1000", "-t", "2"] if case == "bed_tile_1000" else ["--tile", "1700", "-t", "2"]
+    windows = {opt: ([w, "1000"] if w and case == "windows_tile_1700" else []) for opt, w in REPORT_OPTS.items()}
+
+    def run(tag, opts):   # its own child process and time limit; the case ends at the first run that does not exit 0
+        args = [a for opt in opts for a in [opt, os.path.join(d, tag + opt)] + windows[opt]]
+        r = subprocess.run([EXE, bam, "-f", fa, "-o", os.path.join(d, tag + ".vcf.gz"), "-s", "S"] + shared + args, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, (tag, r.returncode, r.stderr[-2000:])
+        vcf = [l for l in gzip.open(os.path.join(d, tag + ".vcf.gz"), "rt").read().splitlines() if not l.startswith(("##fileDate=", "##variantCallerCommand="))]
+        return vcf, {opt: open(os.path.join(d, tag + opt), "rb").read() for opt in opts}
+
+    t0 = time.time()
+    vcf_all, all_six = run("all", list(REPORT_OPTS))
+    assert len(vcf_all) > 100 and all(len(text) > 0 for text in all_six.values())
+    for k, opt in enumerate(REPORT_OPTS):
+        vcf_one, one = run("one%d" % k, [opt])
+        assert one[opt] == all_six[opt], (case, opt)
+        assert vcf_one == vcf_all, (case, opt)
+    print("%s: seven runs in %.1f s" % (case, time.time() - t0))

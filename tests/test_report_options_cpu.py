@@ -1,7 +1,10 @@
-"""The four report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out) refuse the same runs in the same
-sentence: only the option's name and its own words for why differ.  The messages are read from the built uvc1-mi355x; no file is opened and
-no device is needed, every refusal comes first."""
+"""The six report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out, --msi-out, --read-profile-out) refuse
+the same runs in the same sentence: only the option's name and its own words for why differ.  Their whole-number sub-options, and the two
+other whole-number options of the command line, take and refuse the same spellings in one sentence.  The messages are read from the built
+uvc1-mi355x; no file is opened and no device is needed, every refusal comes first."""
+import math
 import os
+import re
 import subprocess
 
 import pytest
@@ -17,6 +20,8 @@ REPORTS = {
     "--error-profile-out": (None, "every shard would write a part of the table", "every tile would be counted that many times", "error profile"),
     "--family-stats-out": ("--family-stats-window", "a target can straddle shards", "every tile would be counted that many times", "family report"),
     "--callable-out": (None, "a target can straddle shards", "every tile would report its runs that many times", "callable regions"),
+    "--msi-out": (None, "a target can straddle shards", "every tile would report its loci that many times", "microsatellite tally"),
+    "--read-profile-out": (None, "every shard would write a part of the profile", "every tile would be counted that many times", "read profile"),
 }
 WINDOWED = [opt for opt, row in REPORTS.items() if row[0]]
 
@@ -61,7 +66,7 @@ def test_the_targets_of_a_windowed_report(tmp_path, opt):
 
 
 def test_the_sentences_are_the_same_for_every_report(tmp_path):
-    """What is left of each refusal once the option's name and its own words are taken out is one text for all four."""
+    """What is left of each refusal once the option's name and its own words are taken out is one text for all six."""
     frames = {}
     for opt, (w, no_shard, no_repeat, writes) in REPORTS.items():
         got = [refusal(["/only-print-vcf-header/"] + with_windows(opt), tmp_path),
@@ -76,6 +81,7 @@ def test_the_sentences_are_the_same_for_every_report(tmp_path):
     first = frames["--coverage-out"]
     assert len(first) == 6 and frames["--family-stats-out"] == first
     assert frames["--error-profile-out"] == first[:4] and frames["--callable-out"] == first[:4]
+    assert frames["--msi-out"] == first[:4] and frames["--read-profile-out"] == first[:4]
 
 
 @pytest.mark.parametrize("opt", list(REPORTS))
@@ -84,3 +90,103 @@ def test_pair_mode_writes_no_report(tmp_path, opt):
     assert refusal(PAIR + [opt, "r.out"], tmp_path) == "%s cannot go with --normal-bam: pair mode has its own tile loop and writes no %s" % (opt, writes)
     if w:
         assert refusal(PAIR + [w + "=100"], tmp_path) == "%s cannot go with --normal-bam: pair mode has its own tile loop and writes no %s" % (w, writes)
+
+
+# ---- every report option and sub-option; the whole-number options ----
+# report -> its sub-options, each with a value it takes (written out here, not read from the program: an option the program's table
+# forgets is then accepted in pair mode, and the test fails)
+SUBS = {
+    "--coverage-out": {"--coverage-thresholds": "1,20", "--coverage-window": "1000"},
+    "--error-profile-out": {"--error-profile-min-depth": "5", "--error-profile-max-alt-permille": "10"},
+    "--family-stats-out": {"--family-stats-window": "1000"},
+    "--callable-out": {"--callable-min-depth": "cDP12=5", "--callable-max-aDP": "7"},
+    "--msi-out": {"--msi-min-tract": "8", "--msi-min-units": "3", "--msi-max-unit": "4", "--msi-min-depth": "9", "--msi-unstable-permille": "100"},
+    "--read-profile-out": {"--read-profile-min-mapq": "1", "--read-profile-min-depth": "5", "--read-profile-max-alt-permille": "10"},
+}
+# report -> the one sentence for its sub-options without it; None: one per sub-option, "<sub> needs <report>: it only shapes that report"
+NEEDS = {
+    "--coverage-out": None,
+    "--error-profile-out": "--error-profile-min-depth and --error-profile-max-alt-permille need --error-profile-out: they only gate that report",
+    "--family-stats-out": None,
+    "--callable-out": "--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file",
+    "--msi-out": "--msi-min-tract, --msi-min-units, --msi-max-unit, --msi-min-depth and --msi-unstable-permille need --msi-out: they only shape that file",
+    "--read-profile-out": "--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report",
+}
+# whole-number option -> (lo, hi, spelling, what it "takes"); the spellings:
+#   strtod       what C's strtod reads to the end of the value with no blank in front, finite; not true / false
+#   digits       [0-9]+ only
+#   strtod+bool  strtod, and true is 1, false is 0
+A_WINDOW, A_DEPTH, PERMILLE, AT_LEAST_1 = "a window length in bp", "a depth of at least 1", "thousandths from 0 to 1000", "a whole number of at least 1"
+NUMBERS = {
+    "--coverage-window": (1, 2e9, "strtod", A_WINDOW), "--family-stats-window": (1, 2e9, "strtod", A_WINDOW),
+    "--error-profile-min-depth": (1, 2e9, "strtod", A_DEPTH), "--read-profile-min-depth": (1, 2e9, "strtod", A_DEPTH),
+    "--error-profile-max-alt-permille": (0, 1000, "strtod", PERMILLE), "--read-profile-max-alt-permille": (0, 1000, "strtod", PERMILLE),
+    "--read-profile-min-mapq": (0, 255, "strtod", "a mapping quality from 0 to 255"),
+    "--msi-min-tract": (1, 2e9, "strtod", AT_LEAST_1), "--msi-min-units": (1, 2e9, "strtod", AT_LEAST_1),
+    "--msi-max-unit": (1, 2e9, "strtod", AT_LEAST_1), "--msi-min-depth": (1, 2e9, "strtod", AT_LEAST_1),
+    "--msi-unstable-permille": (0, 2e9, "strtod", "thousandths of the depth (a whole number >= 0)"),
+    "--score-mem-mb": (0, 1e9, "strtod", "a size in MiB (0 = off)"),
+    "--callable-max-aDP": (0, 2e9, "digits", "a depth (0 = off)"),
+    "--merge-regions": (0, 2e9, "strtod+bool", "a distance in bp (0 = off)"),
+}
+VALUES = ["0", "1", "-1", "2.5", "true", "false", "x", "", "1e3", "0x10", "+5", " 5", "5 ", "3e10", "1000", "1001", "255", "256", "2000000000", "2000000001"]
+PRINT = ["--sequencing-platform", "1", "--print-params"]   # a given platform: exit 0 behind all option checks, no file, no device
+
+
+def c_strtod(v):
+    """The value of v where C's strtod reads all of it and it does not begin with a blank, else None."""
+    if v == "" or v != v.strip() or "_" in v:
+        return None
+    try:
+        x = float.fromhex(v) if v.lstrip("+-")[:2].lower() == "0x" else float(v)
+    except ValueError:
+        return None
+    return x if math.isfinite(x) else None
+
+
+def taken(opt, v):
+    """Whether the table says that `opt` takes the value `v`."""
+    lo, hi, spelling, _ = NUMBERS[opt]
+    if v in ("true", "false"):
+        x = float(v == "true") if spelling == "strtod+bool" else None
+    elif spelling == "digits":
+        x = float(v) if re.fullmatch("[0-9]+", v) else None
+    else:
+        x = c_strtod(v)
+    return x is not None and lo <= x <= hi and x == int(x)
+
+
+def test_the_table_of_spellings():
+    """The expectations below come from the table: what it says of the spellings the issue names."""
+    assert [v for v in VALUES if taken("--msi-min-depth", v)] == ["1", "1e3", "0x10", "+5", "1000", "1001", "255", "256", "2000000000"]
+    assert [v for v in VALUES if taken("--callable-max-aDP", v)] == ["0", "1", "1000", "1001", "255", "256", "2000000000"]
+    assert [v for v in VALUES if taken("--merge-regions", v)] == ["0", "1", "true", "false", "1e3", "0x10", "+5", "1000", "1001", "255", "256", "2000000000"]
+    assert len(NUMBERS) * len(VALUES) == 300
+
+
+@pytest.mark.parametrize("group", list(REPORTS) + ["--score-mem-mb", "--merge-regions"])
+def test_every_report_option_and_whole_number(tmp_path, group):
+    """A report with all of its sub-options, or one of the two other whole-number options: each whole-number option over VALUES as the
+    table has it, then per report a sub-option without the report, an empty path, and every option of it in pair mode."""
+    report = group if group in REPORTS else None
+    window = REPORTS[report][0] if report else None
+    front = BASE + PRINT + ([report, "r.out"] if report else ["-R", "p.bed"] if group == "--merge-regions" else [])
+    for opt in ([o for o in SUBS[report] if o in NUMBERS] if report else [group]):
+        for v in VALUES:
+            args = front + ([window, "1000"] if window and opt != window else []) + [opt + "=" + v]
+            if taken(opt, v):
+                r = subprocess.run([EXE] + args, capture_output=True, text=True, timeout=60, cwd=str(tmp_path))
+                assert (r.returncode, r.stderr) == (0, "") and "vqual=" in r.stdout and os.listdir(tmp_path) == [], (args, r.returncode, r.stderr)
+            else:
+                assert refusal(args, tmp_path) == "%s takes %s, not '%s'" % (opt, NUMBERS[opt][3], v), args
+    if not report:
+        return
+    writes = REPORTS[report][3]
+    assert refusal(BASE + [report, ""], tmp_path) == report + " needs a path"
+    assert refusal(BASE + [report + "="], tmp_path) == report + " needs a path"
+    for opt, value in [(report, "r.out")] + list(SUBS[report].items()):
+        for args in ([opt, value], [opt + "=" + value]):
+            assert refusal(PAIR + args, tmp_path) == "%s cannot go with --normal-bam: pair mode has its own tile loop and writes no %s" % (opt, writes)
+    for sub, value in SUBS[report].items():
+        assert refusal(BASE + [sub, value], tmp_path) == (NEEDS[report] or "%s needs %s: it only shapes that report" % (sub, report))
+        assert refusal(BASE + PRINT + [sub + "=" + value], tmp_path) == (NEEDS[report] or "%s needs %s: it only shapes that report" % (sub, report))

@@ -159,55 +159,32 @@ ERROR_LEVELS = [k[len("UVC_ERRLEVEL_"):] for k, v in sorted(((k, v) for k, v in 
 assert len(ERROR_LEVELS) == ENUMS["UVC_NERRLEVEL"]
 
 
-def _read_famstats_def():
-    """The sections of a row of uvcgpu_region_family_stats: (name, first word, words) per row of include/uvc_famstats.def."""
-    with open(os.path.join(ROOT, "include", "uvc_famstats.def")) as fh:
-        rows = [re.match(r"UVC_FAMSTAT\((\w+),\s*(\d+),\s*(\d+)\)\s*$", line) for line in fh]
-    return [(m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
+def _read_def(file, macro):
+    """The rows `macro(name, first word, words)` of include/<file> as (name, first word, words): the sections of the row of numbers a
+    report call fills.  A table of one column, `macro(name)`, gives its names."""
+    with open(os.path.join(ROOT, "include", file)) as fh:
+        rows = [re.match(macro + r"\((\w+)(?:,\s*(\d+),\s*(\d+))?\)\s*$", line) for line in fh]
+    return [m.group(1) if m.group(2) is None else (m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
 
 
 # the sections of a family-statistics row in id order (UvcFamStat): the table of include/uvc_famstats.def, checked against the header's enums
-FAMSTAT_SECTIONS = _read_famstats_def()
+FAMSTAT_SECTIONS = _read_def("uvc_famstats.def", "UVC_FAMSTAT")
 FAMILY_STATS = [n for n, _, _ in FAMSTAT_SECTIONS]
 assert [ENUMS["UVC_FAMSTAT_" + n] for n in FAMILY_STATS] == list(range(ENUMS["UVC_NFAMSTAT"]))
 assert sum(w for _, _, w in FAMSTAT_SECTIONS) == ENUMS["UVC_FAMSTAT_ROW"] and all(f == sum(w for _, _, w in FAMSTAT_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMSTAT_SECTIONS))
 
-
-def _read_readprofile_def():
-    """The sections of a row of uvcgpu_region_read_profile: (name, first word, words) per row of include/uvc_readprofile.def."""
-    with open(os.path.join(ROOT, "include", "uvc_readprofile.def")) as fh:
-        rows = [re.match(r"UVC_READPROF\((\w+),\s*(\d+),\s*(\d+)\)\s*$", line) for line in fh]
-    return [(m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
-
-
 # the sections of a read-profile row in id order (UvcReadProfSection): the table of include/uvc_readprofile.def, checked against the header's enums
-READPROF_SECTIONS = _read_readprofile_def()
+READPROF_SECTIONS = _read_def("uvc_readprofile.def", "UVC_READPROF")
 assert [ENUMS["UVC_READPROF_" + n] for n, _, _ in READPROF_SECTIONS] == list(range(ENUMS["UVC_NREADPROF"]))
 assert sum(w for _, _, w in READPROF_SECTIONS) == ENUMS["UVC_READPROF_ROW"] and all(f == sum(w for _, _, w in READPROF_SECTIONS[:k]) for k, (_, f, _) in enumerate(READPROF_SECTIONS))
 
-
-def _read_callable_def():
-    """The bits of a mask of uvcgpu_region_callable in bit order: the rows of include/uvc_callable.def."""
-    with open(os.path.join(ROOT, "include", "uvc_callable.def")) as fh:
-        rows = [re.match(r"UVC_CALLBIT\((\w+)\)\s*$", line) for line in fh]
-    return [m.group(1) for m in rows if m]
-
-
-# the bits of a callability mask (UvcCallableBit): the table of include/uvc_callable.def, checked against the header's enums and the measures
-CALLABLE_BITS = _read_callable_def()
+# the bits of a callability mask in bit order (UvcCallableBit): the table of include/uvc_callable.def, checked against the header's enums and the measures
+CALLABLE_BITS = _read_def("uvc_callable.def", "UVC_CALLBIT")
 assert [ENUMS["UVC_CALL_" + n] for n in CALLABLE_BITS] == list(range(ENUMS["UVC_NCALLBIT"]))
 assert CALLABLE_BITS[:len(COVERAGE_MEASURES)] == ["LOW_" + m for m in COVERAGE_MEASURES] and C.sizeof(UvcCallableRequest) == 4 * (ENUMS["UVC_NCOV"] + 1)
 
-
-def _read_msi_def():
-    """The sections of a row of uvcgpu_region_msi: (name, first word, words) per row of include/uvc_msi.def."""
-    with open(os.path.join(ROOT, "include", "uvc_msi.def")) as fh:
-        rows = [re.match(r"UVC_MSI\((\w+),\s*(\d+),\s*(\d+)\)\s*$", line) for line in fh]
-    return [(m.group(1), int(m.group(2)), int(m.group(3))) for m in rows if m]
-
-
 # the sections of a microsatellite row in id order (UvcMsiSection): the table of include/uvc_msi.def, checked against the header's enums
-MSI_SECTIONS = _read_msi_def()
+MSI_SECTIONS = _read_def("uvc_msi.def", "UVC_MSI")
 assert [ENUMS["UVC_MSI_" + n] for n, _, _ in MSI_SECTIONS] == list(range(ENUMS["UVC_NMSI"]))
 assert sum(w for _, _, w in MSI_SECTIONS) == ENUMS["UVC_MSI_ROW"] and all(f == sum(w for _, _, w in MSI_SECTIONS[:k]) for k, (_, f, _) in enumerate(MSI_SECTIONS))
 assert dict((n, (f, w)) for n, f, w in MSI_SECTIONS)["depth"] == (ENUMS["UVC_MSI_DEPTH"], ENUMS["UVC_MSI_NLEVEL"]) and dict((n, (f, w)) for n, f, w in MSI_SECTIONS)["hist"] == (ENUMS["UVC_MSI_HIST"], ENUMS["UVC_MSI_NLEVEL"] * ENUMS["UVC_MSI_NBIN"])

@@ -39,6 +39,42 @@
 namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
+// The reports beside the VCF, in the order their options are checked: of several faults the first in
+// this order is the one reported.
+// A row holds what the command line says of a report in more than one place: parse (the path, "a sub-option was given", the checks behind
+// the loop), split_pair (pair mode writes none) and main (the probe of the path).  A new report is a row here, an Opts store, a
+// *_of_tile and its open / write lines in main.
+enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, N_REPORTS };
+struct ReportRow {
+    const char *out;                 // --X-out PATH
+    const char *subs[6];             // the options that only shape this report: each needs --X-out (the list ends with a null)
+    const char *window;              // the one of them that cuts the targets into windows (refuse_report_windows), or none
+    const char *why_no_shard, *why_no_repeat;   // refuse_report_runs
+    const char *pair_writes_no;      // split_pair: "pair mode ... writes no <this>"
+    const char *needs;               // the sentence for sub-options without --X-out; none: one per sub-option, "<sub> needs <out>: it only shapes that report"
+};
+const ReportRow REPORTS[N_REPORTS] = {
+    { "--coverage-out", { "--coverage-thresholds", "--coverage-window" }, "--coverage-window", "a target can straddle shards", "every tile would be counted that many times", "coverage report", nullptr },
+    { "--error-profile-out", { "--error-profile-min-depth", "--error-profile-max-alt-permille" }, nullptr, "every shard would write a part of the table", "every tile would be counted that many times", "error profile",
+      "--error-profile-min-depth and --error-profile-max-alt-permille need --error-profile-out: they only gate that report" },
+    { "--family-stats-out", { "--family-stats-window" }, "--family-stats-window", "a target can straddle shards", "every tile would be counted that many times", "family report", nullptr },
+    { "--callable-out", { "--callable-min-depth", "--callable-max-aDP" }, nullptr, "a target can straddle shards", "every tile would report its runs that many times", "callable regions",
+      "--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file" },
+    { "--msi-out", { "--msi-min-tract", "--msi-min-units", "--msi-max-unit", "--msi-min-depth", "--msi-unstable-permille" }, nullptr, "a target can straddle shards", "every tile would report its loci that many times", "microsatellite tally",
+      "--msi-min-tract, --msi-min-units, --msi-max-unit, --msi-min-depth and --msi-unstable-permille need --msi-out: they only shape that file" },
+    { "--read-profile-out", { "--read-profile-min-mapq", "--read-profile-min-depth", "--read-profile-max-alt-permille" }, nullptr, "every shard would write a part of the profile", "every tile would be counted that many times", "read profile",
+      "--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report" },
+};
+// the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
+int report_of(const std::string &name, int *sub) {
+    for (int r = 0; r < N_REPORTS; r++) {
+        *sub = -1;
+        if (name == REPORTS[r].out) return r;
+        for (int s = 0; REPORTS[r].subs[s]; s++) if (name == REPORTS[r].subs[s]) { *sub = s; return r; }
+    }
+    return -1;
+}
+
 struct Opts {
     std::string bam, fasta, out, sample = "-", targets, bed, tumor_vcf, bed_out, bed_in, umi_struct, force_sites;
     std::vector<int> devices;
@@ -48,27 +84,22 @@ struct Opts {
     int64_t mem_per_thread = 1536;   // --mem-per-thread (MB), CmdLineArgs.hpp:33: enters the reference's region cuts
     int64_t merge = 0;           // --merge-regions N: BED lines at most N bp apart become ranges of one device region (0 = one region per line)
     int64_t score_mem_mb = 0;    // --score-mem-mb N: score every tile as a stream of chunks whose row sets and record buffers fit N MiB per worker (0 = one call per tile)
-    std::string coverage_out;    // --coverage-out PATH: the per-target depth report; empty = none
-    std::vector<int32_t> coverage_thr{ 1, 20, 100, 500 }; bool coverage_thr_given = false;   // --coverage-thresholds
-    int64_t coverage_window = 0; // --coverage-window N: the targets are windows of N bp (0: the BED lines)
-    uvcio_coverage_t *cov = nullptr;   // the report's store, filled by the workers (main)
-    std::string errprof_out;     // --error-profile-out PATH: the background error profile; empty = none
-    UvcErrorProfileRequest errprof_req{ 20, 50 }; bool errprof_gate_given = false;   // --error-profile-min-depth, --error-profile-max-alt-permille
-    uvcio_errprofile_t *errprof = nullptr;   // the run's table, summed over the tiles by the workers (main)
-    std::string famstats_out;    // --family-stats-out PATH: the UMI family report; empty = none
-    int64_t famstats_window = 0; // --family-stats-window N: the targets are windows of N bp (0: the BED lines)
-    uvcio_famstats_t *fam = nullptr;   // the report's store, filled by the workers (main)
-    std::string callable_out;    // --callable-out PATH: the callable-region BED; empty = none
-    UvcCallableRequest call_req = [] { UvcCallableRequest q{}; q.min_depth[UVC_COV_cDP12] = 20; return q; }(); bool call_req_given = false;   // --callable-min-depth, --callable-max-aDP
-    uvcio_callable_t *callable = nullptr;   // the BED's store, filled by the workers (main)
+    // the reports beside the VCF, one row of REPORTS each: --X-out PATH (empty = none), which of its sub-options were given (bit s: the
+    // row's s-th), and --X-window N where the row has one: the targets are windows of N bp (0: the BED lines)
+    struct Report { std::string path; uint32_t subs_given = 0; int64_t window = 0; } report[N_REPORTS];
+    std::vector<int32_t> coverage_thr{ 1, 20, 100, 500 };   // --coverage-thresholds
+    uvcio_coverage_t *cov = nullptr;   // --coverage-out: the report's store, filled by the workers (main)
+    UvcErrorProfileRequest errprof_req{ 20, 50 };   // --error-profile-min-depth, --error-profile-max-alt-permille
+    uvcio_errprofile_t *errprof = nullptr;   // --error-profile-out: the run's table, summed over the tiles by the workers (main)
+    uvcio_famstats_t *fam = nullptr;   // --family-stats-out: the report's store, filled by the workers (main)
+    UvcCallableRequest call_req = [] { UvcCallableRequest q{}; q.min_depth[UVC_COV_cDP12] = 20; return q; }();   // --callable-min-depth, --callable-max-aDP
+    uvcio_callable_t *callable = nullptr;   // --callable-out: the BED's store, filled by the workers (main)
     std::vector<int64_t> call_contig_target;   // without a BED file: per contig the store's target of its called span (-1: not called)
     std::vector<std::pair<int64_t, int64_t>> call_target_span;   // per target of the store its [beg, end): a tile's stretch is clipped to it
-    std::string msi_out;         // --msi-out PATH: the microsatellite length-shift tally; empty = none
-    UvcMsiRequest msi_req{ 10, 5, 6 }; int32_t msi_min_depth = 30, msi_unstable_permille = 200; bool msi_sub_given = false;   // --msi-min-tract, --msi-min-units, --msi-max-unit; --msi-min-depth, --msi-unstable-permille
-    uvcio_msi_t *msi = nullptr;   // the tally's store, filled by the workers (main); its targets are those of --callable-out (call_contig_target, call_target_span)
-    std::string readprof_out;    // --read-profile-out PATH: the base-quality and cycle profile of the reads; empty = none
-    UvcReadProfileRequest readprof_req{ 0, 20, 50 }; bool readprof_gate_given = false;   // --read-profile-min-mapq, --read-profile-min-depth, --read-profile-max-alt-permille
-    uvcio_readprofile_t *readprof = nullptr;   // the run's row, summed over the tiles by the workers (main)
+    UvcMsiRequest msi_req{ 10, 5, 6 }; int32_t msi_min_depth = 30, msi_unstable_permille = 200;   // --msi-min-tract, --msi-min-units, --msi-max-unit; --msi-min-depth, --msi-unstable-permille
+    uvcio_msi_t *msi = nullptr;   // --msi-out: the tally's store, filled by the workers (main); its targets are those of --callable-out (call_contig_target, call_target_span)
+    UvcReadProfileRequest readprof_req{ 0, 20, 50 };   // --read-profile-min-mapq, --read-profile-min-depth, --read-profile-max-alt-permille
+    uvcio_readprofile_t *readprof = nullptr;   // --read-profile-out: the run's row, summed over the tiles by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -184,10 +215,15 @@ const OptRow OPTS[] = {
     { "--bed-in-avg-sequencing-DP-n-from-t", O_UNSUPPORTED, false, "0", "the regions are not planned from BED read counts" },
 };
 
+// fn(item) for every item of the comma-separated v, the empty ones included ("" is one empty item)
+template <class F> void for_items(const std::string &v, F fn) {
+    for (size_t at = 0; at <= v.size();) { size_t c = v.find(',', at); if (c == std::string::npos) c = v.size(); fn(v.substr(at, c - at)); at = c + 1; }
+}
 const OptRow *find_opt(const std::string &name) {
     for (const OptRow &r : OPTS) {
-        const std::string ns = r.names; size_t at = 0;
-        while (at <= ns.size()) { size_t c = ns.find(',', at); if (c == std::string::npos) c = ns.size(); if (ns.compare(at, c - at, name) == 0 && c - at == name.size()) return &r; at = c + 1; }
+        bool hit = false;
+        for_items(r.names, [&](const std::string &n) { hit |= (n == name); });
+        if (hit) return &r;
     }
     return nullptr;
 }
@@ -211,13 +247,25 @@ bool number(const std::string &s, double *v) {   // a whole decimal number, or t
     char *e = nullptr; *v = strtod(s.c_str(), &e); return *e == 0 && std::isfinite(*v);
 }
 
-// What the report options (--coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out, --msi-out) share on the command line.  Each option
-// gives its own words for why; the sentences are these.
-int64_t window_length(const std::string &opt, const std::string &v) {   // --coverage-window, --family-stats-window
+// A whole number of lo..hi in one of the three spellings the options have grown:
+//   N_STRTOD       what number() takes, without true / false: 1e3, 0x10 and +5 pass; '', ' 5', '5 ' and 2.5 do not
+//   N_DIGITS       [0-9]+ only
+//   N_STRTOD_BOOL  N_STRTOD, and true is 1, false is 0
+enum Spelling { N_STRTOD, N_DIGITS, N_STRTOD_BOOL };
+bool is_whole(const std::string &v, double lo, double hi, Spelling sp, int64_t *n) {
     double x;
-    if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die(opt + " takes a window length in bp, not '" + v + "'");
-    return (int64_t)x;
+    if (sp != N_STRTOD_BOOL && (v == "true" || v == "false")) return false;
+    if (sp == N_DIGITS && v.find_first_not_of("0123456789") != std::string::npos) return false;
+    if (!number(v, &x) || x < lo || x > hi || x != (double)(int64_t)x) return false;   // range first: the cast needs it
+    *n = (int64_t)x; return true;
 }
+int64_t whole_number(const std::string &opt, const std::string &v, double lo, double hi, const char *takes, Spelling sp = N_STRTOD) {
+    int64_t n;
+    if (!is_whole(v, lo, hi, sp, &n)) die(opt + " takes " + takes + ", not '" + v + "'");
+    return n;
+}
+
+// What the report options (the rows of REPORTS) share on the command line.  Each option gives its own words for why; the sentences are these.
 // the runs no report can come from: the header-only run, one shard of many, a repeated tile list
 void refuse_report_runs(const Opts &o, const std::string &opt, const char *why_no_shard, const char *why_no_repeat) {
     if (o.bam == ONLY_PRINT_VCF_HEADER) die(opt + " cannot go with " + ONLY_PRINT_VCF_HEADER + ": no tile is called");
@@ -268,7 +316,7 @@ Opts parse(int argc, char **argv) {
         if (uvcgpu_param_set(&o.P, &o.G, row, v.c_str())) die(opt + ": " + uvcgpu_last_error());
     };
     auto enum_value = [&](const std::string &opt, const std::string &v, int hi) {
-        double x; if (!number(v, &x) || x < 0 || x > hi || x != (int)x) die(opt + ": '" + v + "' is not one of 0.." + std::to_string(hi));   // range first: the cast needs it
+        int64_t x; if (!is_whole(v, 0, hi, N_STRTOD_BOOL, &x)) die(opt + ": '" + v + "' is not one of 0.." + std::to_string(hi));
         return (int)x;
     };
     for (int i = 1; i < argc; i++) {
@@ -297,6 +345,9 @@ Opts parse(int argc, char **argv) {
             if (!at_default) die(name + " " + v + " is not supported: " + row->what);
             continue;
         }
+        int sub; const int rep = report_of(n0, &sub);
+        if (rep >= 0 && sub < 0) { o.report[rep].path = val(); if (o.report[rep].path.empty()) die(n0 + " needs a path"); continue; }
+        if (rep >= 0) o.report[rep].subs_given |= 1u << sub;
         if (n0 == "-f") o.fasta = val();
         else if (n0 == "-o") o.out = val();
         else if (n0 == "-s") o.sample = val();
@@ -308,63 +359,50 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "-q") set_row("vqual", name, val());
         else if (n0 == "--outvar-flag") set_row("outvar_flag", name, val());
         else if (n0 == "--tile") o.tile = std::max<int64_t>(100, atoll(val().c_str()));
-        else if (n0 == "--merge-regions") { const std::string v = val(); double x; if (!number(v, &x) || x < 0 || x != (double)(int64_t)x || x > 2e9) die("--merge-regions takes a distance in bp (0 = off), not '" + v + "'"); o.merge = (int64_t)x; }
-        else if (n0 == "--score-mem-mb") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1e9) die("--score-mem-mb takes a size in MiB (0 = off), not '" + v + "'"); o.score_mem_mb = (int64_t)x; }
-        else if (n0 == "--coverage-out") { o.coverage_out = val(); if (o.coverage_out.empty()) die("--coverage-out needs a path"); }
+        else if (n0 == "--merge-regions") o.merge = whole_number(n0, val(), 0, 2e9, "a distance in bp (0 = off)", N_STRTOD_BOOL);
+        else if (n0 == "--score-mem-mb") o.score_mem_mb = whole_number(n0, val(), 0, 1e9, "a size in MiB (0 = off)");
         else if (n0 == "--coverage-thresholds") {   // a,b,c: whole decimal numbers, ascending, at most 8
-            const std::string v = val(); o.coverage_thr.clear(); o.coverage_thr_given = true;
-            for (size_t at = 0; at <= v.size();) {
-                size_t c = v.find(',', at); if (c == std::string::npos) c = v.size();
-                const std::string item = v.substr(at, c - at); double x;
-                if (item == "true" || item == "false" || !number(item, &x) || x < 0 || x != (double)(int64_t)x || x > 2e9) die("--coverage-thresholds takes up to 8 ascending depths such as 1,20,100,500, not '" + v + "' ('" + item + "' is not a depth)");
+            const std::string v = val(); o.coverage_thr.clear();
+            for_items(v, [&](const std::string &item) {
+                int64_t x;
+                if (!is_whole(item, 0, 2e9, N_STRTOD, &x)) die("--coverage-thresholds takes up to 8 ascending depths such as 1,20,100,500, not '" + v + "' ('" + item + "' is not a depth)");
                 if (!o.coverage_thr.empty() && (int32_t)x <= o.coverage_thr.back()) die("--coverage-thresholds must ascend: '" + v + "' has " + item + " behind " + std::to_string(o.coverage_thr.back()));
                 o.coverage_thr.push_back((int32_t)x);
                 if (o.coverage_thr.size() > (size_t)UVC_COV_MAX_THRESHOLDS) die("--coverage-thresholds takes at most " + std::to_string((int)UVC_COV_MAX_THRESHOLDS) + " depths, not '" + v + "'");
-                at = c + 1;
-            }
+            });
         }
-        else if (n0 == "--coverage-window") o.coverage_window = window_length(n0, val());
-        else if (n0 == "--error-profile-out") { o.errprof_out = val(); if (o.errprof_out.empty()) die("--error-profile-out needs a path"); }
-        else if (n0 == "--error-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--error-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.errprof_req.min_depth = (int32_t)x; o.errprof_gate_given = true; }
-        else if (n0 == "--error-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--error-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.errprof_req.max_alt_permille = (int32_t)x; o.errprof_gate_given = true; }
-        else if (n0 == "--family-stats-out") { o.famstats_out = val(); if (o.famstats_out.empty()) die("--family-stats-out needs a path"); }
-        else if (n0 == "--family-stats-window") o.famstats_window = window_length(n0, val());
-        else if (n0 == "--callable-out") { o.callable_out = val(); if (o.callable_out.empty()) die("--callable-out needs a path"); }
+        else if (n0 == "--coverage-window" || n0 == "--family-stats-window") o.report[rep].window = whole_number(n0, val(), 1, 2e9, "a window length in bp");
+        else if (n0 == "--error-profile-min-depth") o.errprof_req.min_depth = (int32_t)whole_number(n0, val(), 1, 2e9, "a depth of at least 1");
+        else if (n0 == "--error-profile-max-alt-permille") o.errprof_req.max_alt_permille = (int32_t)whole_number(n0, val(), 0, 1000, "thousandths from 0 to 1000");
         else if (n0 == "--callable-min-depth") {   // NAME=N,...: the names of uvcgpu_coverage_measure_name, each at most once, whole numbers >= 0
-            const std::string v = val(); o.call_req_given = true;
+            const std::string v = val();
             bool seen[UVC_NCOV] = {};
             for (int32_t m = 0; m < UVC_NCOV; m++) o.call_req.min_depth[m] = 0;
-            for (size_t at = 0; at <= v.size();) {
-                size_t c = v.find(',', at); if (c == std::string::npos) c = v.size();
-                const std::string item = v.substr(at, c - at); const size_t eq = item.find('=');
+            for_items(v, [&](const std::string &item) {
+                const size_t eq = item.find('=');
                 const std::string name = item.substr(0, eq), num = (eq == std::string::npos ? "" : item.substr(eq + 1));
                 int32_t m = -1;
                 for (int32_t q = 0; q < UVC_NCOV; q++) if (name == uvcgpu_coverage_measure_name(q)) m = q;
-                double x;
+                int64_t x;
                 if (m < 0) die("--callable-min-depth takes NAME=N[,NAME=N...] with the names aDP bDP cDP1 cDP12 cDP2 dDP1, not '" + v + "' ('" + name + "' is not a depth)");
-                if (num == "true" || num == "false" || num.find_first_not_of("0123456789") != std::string::npos || !number(num, &x) || x > 2e9) die("--callable-min-depth takes NAME=N[,NAME=N...], not '" + v + "' ('" + num + "' is not a whole number >= 0)");
+                if (!is_whole(num, 0, 2e9, N_DIGITS, &x)) die("--callable-min-depth takes NAME=N[,NAME=N...], not '" + v + "' ('" + num + "' is not a whole number >= 0)");
                 if (seen[m]) die("--callable-min-depth names " + name + " twice in '" + v + "'");
                 seen[m] = true; o.call_req.min_depth[m] = (int32_t)x;
-                at = c + 1;
-            }
+            });
         }
-        else if (n0 == "--callable-max-aDP") { const std::string v = val(); double x; if (v.find_first_not_of("0123456789") != std::string::npos || !number(v, &x) || x > 2e9) die("--callable-max-aDP takes a depth (0 = off), not '" + v + "'"); o.call_req.max_aDP = (int32_t)x; o.call_req_given = true; }
-        else if (n0 == "--msi-out") { o.msi_out = val(); if (o.msi_out.empty()) die("--msi-out needs a path"); }
-        else if (n0 == "--msi-min-tract" || n0 == "--msi-min-units" || n0 == "--msi-max-unit" || n0 == "--msi-min-depth" || n0 == "--msi-unstable-permille") {
-            const std::string v = val(); double x; const bool permille = (n0 == "--msi-unstable-permille");
-            if (!number(v, &x) || v == "true" || v == "false" || x < (permille ? 0 : 1) || x != (double)(int64_t)x || x > 2e9) die(n0 + (permille ? " takes thousandths of the depth (a whole number >= 0), not '" : " takes a whole number of at least 1, not '") + v + "'");
-            (n0 == "--msi-min-tract" ? o.msi_req.min_tracklen : n0 == "--msi-min-units" ? o.msi_req.min_units : n0 == "--msi-max-unit" ? o.msi_req.max_unitlen : n0 == "--msi-min-depth" ? o.msi_min_depth : o.msi_unstable_permille) = (int32_t)x;
-            o.msi_sub_given = true;
-        }
-        else if (n0 == "--read-profile-out") { o.readprof_out = val(); if (o.readprof_out.empty()) die("--read-profile-out needs a path"); }
-        else if (n0 == "--read-profile-min-mapq") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 255) die("--read-profile-min-mapq takes a mapping quality from 0 to 255, not '" + v + "'"); o.readprof_req.min_mapq = (int32_t)x; o.readprof_gate_given = true; }
-        else if (n0 == "--read-profile-min-depth") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 1 || x != (double)(int64_t)x || x > 2e9) die("--read-profile-min-depth takes a depth of at least 1, not '" + v + "'"); o.readprof_req.min_depth = (int32_t)x; o.readprof_gate_given = true; }
-        else if (n0 == "--read-profile-max-alt-permille") { const std::string v = val(); double x; if (!number(v, &x) || v == "true" || v == "false" || x < 0 || x != (double)(int64_t)x || x > 1000) die("--read-profile-max-alt-permille takes thousandths from 0 to 1000, not '" + v + "'"); o.readprof_req.max_alt_permille = (int32_t)x; o.readprof_gate_given = true; }
+        else if (n0 == "--callable-max-aDP") o.call_req.max_aDP = (int32_t)whole_number(n0, val(), 0, 2e9, "a depth (0 = off)", N_DIGITS);
+        else if (n0 == "--msi-min-tract") o.msi_req.min_tracklen = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--msi-min-units") o.msi_req.min_units = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--msi-max-unit") o.msi_req.max_unitlen = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--msi-min-depth") o.msi_min_depth = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--msi-unstable-permille") o.msi_unstable_permille = (int32_t)whole_number(n0, val(), 0, 2e9, "thousandths of the depth (a whole number >= 0)");
+        else if (n0 == "--read-profile-min-mapq") o.readprof_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
+        else if (n0 == "--read-profile-min-depth") o.readprof_req.min_depth = (int32_t)whole_number(n0, val(), 1, 2e9, "a depth of at least 1");
+        else if (n0 == "--read-profile-max-alt-permille") o.readprof_req.max_alt_permille = (int32_t)whole_number(n0, val(), 0, 1000, "thousandths from 0 to 1000");
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
-            const std::string v = val(); size_t at = 0;
-            while (at <= v.size()) { size_t c = v.find(',', at); if (c == std::string::npos) c = v.size(); if (c > at) o.devices.push_back(atoi(v.substr(at, c - at).c_str())); at = c + 1; }
+            for_items(val(), [&](const std::string &id) { if (!id.empty()) o.devices.push_back(atoi(id.c_str())); });
             if (o.devices.empty()) die("--devices needs at least one id");
         }
         else if (n0 == "--shard") { const std::string v = val(); if (sscanf(v.c_str(), "%d/%d", &o.shard, &o.n_shards) != 2 || o.n_shards < 1 || o.shard < 0 || o.shard >= o.n_shards) die("--shard takes i/n with 0 <= i < n"); }
@@ -402,31 +440,16 @@ Opts parse(int argc, char **argv) {
         if (o.bam == ONLY_PRINT_VCF_HEADER) die(std::string("--force-sites cannot go with ") + ONLY_PRINT_VCF_HEADER + ": there are no records to force");
     }
     // the report options, before any file or device
-    if (o.coverage_out.empty()) {
-        if (o.coverage_thr_given) die("--coverage-thresholds needs --coverage-out: it only shapes that report");
-        if (o.coverage_window > 0) die("--coverage-window needs --coverage-out: it only shapes that report");
-    } else {
-        refuse_report_runs(o, "--coverage-out", "a target can straddle shards", "every tile would be counted that many times");
-        refuse_report_windows(o, "--coverage-out", "--coverage-window", o.coverage_window);
+    for (int r = 0; r < N_REPORTS; r++) {
+        const ReportRow &R = REPORTS[r];
+        if (o.report[r].path.empty()) {
+            if (o.report[r].subs_given && R.needs) die(R.needs);
+            for (int s = 0; R.subs[s]; s++) if ((o.report[r].subs_given >> s) & 1) die(std::string(R.subs[s]) + " needs " + R.out + ": it only shapes that report");
+            continue;
+        }
+        refuse_report_runs(o, R.out, R.why_no_shard, R.why_no_repeat);
+        if (R.window) refuse_report_windows(o, R.out, R.window, o.report[r].window);
     }
-    if (o.errprof_out.empty()) {
-        if (o.errprof_gate_given) die("--error-profile-min-depth and --error-profile-max-alt-permille need --error-profile-out: they only gate that report");
-    } else refuse_report_runs(o, "--error-profile-out", "every shard would write a part of the table", "every tile would be counted that many times");
-    if (o.famstats_out.empty()) {
-        if (o.famstats_window > 0) die("--family-stats-window needs --family-stats-out: it only shapes that report");
-    } else {
-        refuse_report_runs(o, "--family-stats-out", "a target can straddle shards", "every tile would be counted that many times");
-        refuse_report_windows(o, "--family-stats-out", "--family-stats-window", o.famstats_window);
-    }
-    if (o.callable_out.empty()) {
-        if (o.call_req_given) die("--callable-min-depth and --callable-max-aDP need --callable-out: they only set the criteria of that file");
-    } else refuse_report_runs(o, "--callable-out", "a target can straddle shards", "every tile would report its runs that many times");
-    if (o.msi_out.empty()) {
-        if (o.msi_sub_given) die("--msi-min-tract, --msi-min-units, --msi-max-unit, --msi-min-depth and --msi-unstable-permille need --msi-out: they only shape that file");
-    } else refuse_report_runs(o, "--msi-out", "a target can straddle shards", "every tile would report its loci that many times");
-    if (o.readprof_out.empty()) {
-        if (o.readprof_gate_given) die("--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report");
-    } else refuse_report_runs(o, "--read-profile-out", "every shard would write a part of the profile", "every tile would be counted that many times");
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
         if (!o.tumor_vcf.empty()) die("--merge-regions cannot go with --tumor-vcf: the normal pass of a T/N pair is called region by region");
@@ -467,12 +490,13 @@ struct Worker {
     int64_t n_tiles = 0, score_cap = 0, text_cap = 0;   // what the last tiles needed: the next call asks for it at once
     int64_t n_chunks = 0, n_streamed = 0;               // --score-mem-mb: chunks in all, tiles scored as streams
     std::vector<UvcScoreRange> covered;
-    std::vector<UvcCoverageRange> cov_ranges; std::vector<int64_t> cov_targets, cov_rows;   // --coverage-out: the pieces of one tile
-    std::vector<UvcCoverageRange> err_ranges;   // --error-profile-out: the stretches one tile owns
-    std::vector<UvcFamilyRange> fam_ranges; std::vector<int64_t> fam_targets, fam_rows;   // --family-stats-out: the pieces of one tile
-    std::vector<UvcCoverageRange> rp_ranges; std::vector<int64_t> rp_row;   // --read-profile-out: the stretches one tile owns, its row
-    std::vector<UvcCoverageRange> call_ranges; std::vector<int64_t> call_targets; std::vector<UvcCallableRun> call_runs;   // --callable-out: the pieces of one tile, their runs
-    std::vector<UvcCoverageRange> msi_ranges; std::vector<int64_t> msi_targets; std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the pieces of one tile, their loci
+    // the reports: the pieces of one tile and their targets.  One list each for all of them: every *_of_tile clears it, fills it, calls and
+    // hands the result to its store before the next one runs
+    std::vector<UvcCoverageRange> ranges; std::vector<int64_t> targets;
+    std::vector<UvcFamilyRange> fam_ranges;   // --family-stats-out: its pieces carry more than a range
+    std::vector<int64_t> cov_rows, fam_rows, rp_row;   // --coverage-out, --family-stats-out, --read-profile-out: what the device call fills
+    std::vector<UvcCallableRun> call_runs;   // --callable-out: the runs, as many as the last tiles had
+    std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the loci, as many as the last tiles had
 };
 
 // --coverage-out: the pieces of targets that one accumulated tile owns, reduced by one uvcgpu_region_coverage and merged into the report.
@@ -480,81 +504,77 @@ struct Worker {
 // rows are windows of o.coverage_window bp and a stretch is cut at their multiples.
 struct CovSpan { int64_t first = -1, origin = 0; };   // window mode, per contig: the row of the called span's first window, the span's begin
 void coverage_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of, const CovSpan *span) {
-    w.cov_ranges.clear(); w.cov_targets.clear();
-    const int64_t N = o.coverage_window;
+    w.ranges.clear(); w.targets.clear();
+    const int64_t N = o.report[R_COVERAGE].window;
     for (size_t q = 0; q < own.size(); q++) {
         const int64_t b = own[q].first, e = own[q].second;
         if (e <= b) continue;
-        if (target_of[q] >= 0) { w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.cov_targets.push_back(target_of[q]); continue; }
+        if (target_of[q] >= 0) { w.ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.targets.push_back(target_of[q]); continue; }
         if (!span || span->first < 0) die("--coverage-out: a tile outside the planned windows (internal error)");
-        for_windows(b, e, N, [&](int64_t k, int64_t wb, int64_t we) { w.cov_ranges.push_back(UvcCoverageRange{ (int32_t)wb, (int32_t)we }); w.cov_targets.push_back(span->first + (k - span->origin / N)); });
+        for_windows(b, e, N, [&](int64_t k, int64_t wb, int64_t we) { w.ranges.push_back(UvcCoverageRange{ (int32_t)wb, (int32_t)we }); w.targets.push_back(span->first + (k - span->origin / N)); });
     }
-    if (w.cov_ranges.empty()) return;
-    w.cov_rows.resize(w.cov_ranges.size() * (size_t)UVC_NCOV * UVC_COV_ROW);
-    if (uvcgpu_region_coverage(w.reg, w.cov_ranges.data(), (int64_t)w.cov_ranges.size(), o.coverage_thr.data(), (int32_t)o.coverage_thr.size(), w.cov_rows.data())) die(uvcgpu_last_error());
-    for (size_t q = 0; q < w.cov_ranges.size(); q++)
-        if (uvcio_coverage_add_piece(o.cov, w.cov_targets[q], (int64_t)w.cov_ranges[q].pos_end - w.cov_ranges[q].pos_beg, &w.cov_rows[q * (size_t)UVC_NCOV * UVC_COV_ROW])) die(uvcio_last_error());
+    if (w.ranges.empty()) return;
+    w.cov_rows.resize(w.ranges.size() * (size_t)UVC_NCOV * UVC_COV_ROW);
+    if (uvcgpu_region_coverage(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), o.coverage_thr.data(), (int32_t)o.coverage_thr.size(), w.cov_rows.data())) die(uvcgpu_last_error());
+    for (size_t q = 0; q < w.ranges.size(); q++)
+        if (uvcio_coverage_add_piece(o.cov, w.targets[q], (int64_t)w.ranges[q].pos_end - w.ranges[q].pos_beg, &w.cov_rows[q * (size_t)UVC_NCOV * UVC_COV_ROW])) die(uvcio_last_error());
+}
+// w.ranges = the non-empty stretches of `own`; false: there are none
+bool owned_ranges(Worker &w, const std::vector<std::pair<int64_t, int64_t>> &own) {
+    w.ranges.clear();
+    for (const auto &q : own) if (q.second > q.first) w.ranges.push_back(UvcCoverageRange{ (int32_t)q.first, (int32_t)q.second });
+    return !w.ranges.empty();
+}
+// w.ranges, w.targets = the stretches of `own` clipped to the span of their target (of the store of `opt`), with the targets; false: nothing is left
+bool target_ranges(Worker &w, const Opts &o, const char *opt, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of) {
+    w.ranges.clear(); w.targets.clear();
+    for (size_t q = 0; q < own.size(); q++) {   // a region of the reference's own cuts begins and ends with its reads, which may reach over the called span: the target's part of it
+        if (target_of[q] < 0) die(std::string(opt) + ": a tile without a target (internal error)");
+        const std::pair<int64_t, int64_t> &span = o.call_target_span[(size_t)target_of[q]];
+        const int64_t b = std::max(own[q].first, span.first), e = std::min(own[q].second, span.second);
+        if (e > b) { w.ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.targets.push_back(target_of[q]); }
+    }
+    return !w.ranges.empty();
+}
+// sizes first: call(buffer, its capacity in items of `per` elements, &n) with the buffer of the last tiles, grown and called once more
+// where this tile has more items; the number of items
+template <class T, class F> int64_t sizes_first(std::vector<T> &buf, size_t per, F call) {
+    int64_t n = 0;
+    int rc = call(buf.data(), (int64_t)(buf.size() / per), &n);
+    if (rc == UVCGPU_ENOMEM && n > (int64_t)(buf.size() / per)) { buf.resize((size_t)n * per); rc = call(buf.data(), n, &n); }
+    if (rc) die(uvcgpu_last_error());
+    return n;
 }
 // --error-profile-out: the profile of the stretches one accumulated tile owns -- the list coverage_of_tile reports on -- by one
 // uvcgpu_region_error_profile, added to the run's table.
 void errprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own) {
-    w.err_ranges.clear();
-    for (const auto &q : own) if (q.second > q.first) w.err_ranges.push_back(UvcCoverageRange{ (int32_t)q.first, (int32_t)q.second });
-    if (w.err_ranges.empty()) return;
+    if (!owned_ranges(w, own)) return;
     int64_t prof[UVC_NERRLEVEL * UVC_ERR_ROW];
-    if (uvcgpu_region_error_profile(w.reg, w.err_ranges.data(), (int64_t)w.err_ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
+    if (uvcgpu_region_error_profile(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
     if (uvcio_errprofile_add(o.errprof, prof)) die(uvcio_last_error());
 }
 // --read-profile-out: the profile of the reads over the stretches one tile owns -- the list coverage_of_tile reports on -- by one
 // uvcgpu_region_read_profile after set_reads, added to the run's row.
 void readprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own) {
-    w.rp_ranges.clear();
-    for (const auto &q : own) if (q.second > q.first) w.rp_ranges.push_back(UvcCoverageRange{ (int32_t)q.first, (int32_t)q.second });
-    if (w.rp_ranges.empty()) return;
+    if (!owned_ranges(w, own)) return;
     w.rp_row.resize((size_t)UVC_READPROF_ROW);
-    if (uvcgpu_region_read_profile(w.reg, w.rp_ranges.data(), (int64_t)w.rp_ranges.size(), &o.readprof_req, w.rp_row.data())) die(uvcgpu_last_error());
+    if (uvcgpu_region_read_profile(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.readprof_req, w.rp_row.data())) die(uvcgpu_last_error());
     if (uvcio_readprofile_add(o.readprof, w.rp_row.data())) die(uvcio_last_error());
 }
 // --callable-out: the runs of the stretches one accumulated tile owns -- the list coverage_of_tile reports on -- by one
 // uvcgpu_region_callable (sizes first: the buffer of the last tiles, grown where a tile has more runs), handed to the store with each
 // stretch's target.  Joining across tiles is the store's.
 void callable_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of) {
-    w.call_ranges.clear(); w.call_targets.clear();
-    for (size_t q = 0; q < own.size(); q++) {   // a region of the reference's own cuts begins and ends with its reads, which may reach over the called span: the target's part of it
-        if (target_of[q] < 0) die("--callable-out: a tile without a target (internal error)");
-        const std::pair<int64_t, int64_t> &span = o.call_target_span[(size_t)target_of[q]];
-        const int64_t b = std::max(own[q].first, span.first), e = std::min(own[q].second, span.second);
-        if (e > b) { w.call_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.call_targets.push_back(target_of[q]); }
-    }
-    if (w.call_ranges.empty()) return;
-    int64_t n = 0;
-    int rc = uvcgpu_region_callable(w.reg, w.call_ranges.data(), (int64_t)w.call_ranges.size(), &o.call_req, w.call_runs.data(), (int64_t)w.call_runs.size(), &n);
-    if (rc == UVCGPU_ENOMEM && n > (int64_t)w.call_runs.size()) {
-        w.call_runs.resize((size_t)n);
-        rc = uvcgpu_region_callable(w.reg, w.call_ranges.data(), (int64_t)w.call_ranges.size(), &o.call_req, w.call_runs.data(), (int64_t)w.call_runs.size(), &n);
-    }
-    if (rc) die(uvcgpu_last_error());
-    if (uvcio_callable_add_runs(o.callable, w.call_targets.data(), (int64_t)w.call_targets.size(), w.call_runs.data(), n)) die(uvcio_last_error());
+    if (!target_ranges(w, o, "--callable-out", own, target_of)) return;
+    const int64_t n = sizes_first(w.call_runs, 1, [&](UvcCallableRun *runs, int64_t cap, int64_t *n_runs) { return uvcgpu_region_callable(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.call_req, runs, cap, n_runs); });
+    if (uvcio_callable_add_runs(o.callable, w.targets.data(), (int64_t)w.targets.size(), w.call_runs.data(), n)) die(uvcio_last_error());
 }
 // --msi-out: the loci whose head lies in the stretches one accumulated tile owns -- the list coverage_of_tile reports on, clipped to the
 // targets as for --callable-out -- by one uvcgpu_region_msi (sizes first: the buffer of the last tiles, grown where a tile has more loci),
 // handed to the store with each stretch's target and each locus's first unit as text.  ref: the reference bases of the region from ref_beg on.
 void msi_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const std::vector<int64_t> &target_of, const std::string &ref, int64_t ref_beg) {
-    w.msi_ranges.clear(); w.msi_targets.clear();
-    for (size_t q = 0; q < own.size(); q++) {
-        if (target_of[q] < 0) die("--msi-out: a tile without a target (internal error)");
-        const std::pair<int64_t, int64_t> &span = o.call_target_span[(size_t)target_of[q]];
-        const int64_t b = std::max(own[q].first, span.first), e = std::min(own[q].second, span.second);
-        if (e > b) { w.msi_ranges.push_back(UvcCoverageRange{ (int32_t)b, (int32_t)e }); w.msi_targets.push_back(target_of[q]); }
-    }
-    if (w.msi_ranges.empty()) return;
-    int64_t n = 0;
-    int rc = uvcgpu_region_msi(w.reg, w.msi_ranges.data(), (int64_t)w.msi_ranges.size(), &o.msi_req, w.msi_rows.data(), (int64_t)(w.msi_rows.size() / UVC_MSI_ROW), &n);
-    if (rc == UVCGPU_ENOMEM && n > (int64_t)(w.msi_rows.size() / UVC_MSI_ROW)) {
-        w.msi_rows.resize((size_t)n * UVC_MSI_ROW);
-        rc = uvcgpu_region_msi(w.reg, w.msi_ranges.data(), (int64_t)w.msi_ranges.size(), &o.msi_req, w.msi_rows.data(), n, &n);
-    }
-    if (rc) die(uvcgpu_last_error());
+    if (!target_ranges(w, o, "--msi-out", own, target_of)) return;
+    const int64_t n = sizes_first(w.msi_rows, UVC_MSI_ROW, [&](int32_t *rows, int64_t cap, int64_t *n_loci) { return uvcgpu_region_msi(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.msi_req, rows, cap, n_loci); });
     w.msi_units.resize((size_t)n); w.msi_unit_ptrs.resize((size_t)n);
     for (int64_t q = 0; q < n; q++) {
         const int32_t *row = &w.msi_rows[(size_t)q * UVC_MSI_ROW];
@@ -563,7 +583,7 @@ void msi_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, 
         for (char &c : w.msi_units[(size_t)q]) c = (char)toupper((unsigned char)c);
         w.msi_unit_ptrs[(size_t)q] = w.msi_units[(size_t)q].c_str();
     }
-    if (uvcio_msi_add(o.msi, w.msi_targets.data(), (int64_t)w.msi_targets.size(), w.msi_rows.data(), w.msi_unit_ptrs.data(), n)) die(uvcio_last_error());
+    if (uvcio_msi_add(o.msi, w.targets.data(), (int64_t)w.targets.size(), w.msi_rows.data(), w.msi_unit_ptrs.data(), n)) die(uvcio_last_error());
 }
 // --family-stats-out: the pieces of targets that the tiles own, planned before any worker starts (plan_family_pieces), so that the report
 // does not depend on which worker takes which tile.  A piece is a tile's [beg, end), cut at the window borders in window mode: the planned
@@ -573,19 +593,34 @@ void msi_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, 
 struct FamPiece { int64_t beg, end, prev_end; int32_t flags; int64_t target; };
 // One uvcgpu_region_family_stats over the pieces of a tile (of the `n_tiles` tiles of a merged batch), after set_reads: the rows go to the report.
 void family_stats_of_tile(Worker &w, const Opts &o, const std::vector<FamPiece> *pieces, size_t n_tiles, int64_t ext_end) {
-    w.fam_ranges.clear(); w.fam_targets.clear();
+    w.fam_ranges.clear(); w.targets.clear();
     for (size_t q = 0; q < n_tiles; q++)
         for (const FamPiece &p : pieces[q]) {
             const int64_t e = std::min(p.end, ext_end + 1);   // (the region holds [ext_beg, ext_end]; a tile lies inside it)
-            if (e > p.beg) { w.fam_ranges.push_back(UvcFamilyRange{ (int32_t)p.beg, (int32_t)e, (int32_t)p.prev_end, p.flags }); w.fam_targets.push_back(p.target); }
+            if (e > p.beg) { w.fam_ranges.push_back(UvcFamilyRange{ (int32_t)p.beg, (int32_t)e, (int32_t)p.prev_end, p.flags }); w.targets.push_back(p.target); }
         }
     if (w.fam_ranges.empty()) return;
     w.fam_rows.resize(w.fam_ranges.size() * (size_t)UVC_FAMSTAT_ROW);
     if (uvcgpu_region_family_stats(w.reg, w.fam_ranges.data(), (int64_t)w.fam_ranges.size(), w.fam_rows.data())) die(uvcgpu_last_error());
     for (size_t q = 0; q < w.fam_ranges.size(); q++)
-        if (uvcio_famstats_add_piece(o.fam, w.fam_targets[q], &w.fam_rows[q * (size_t)UVC_FAMSTAT_ROW])) die(uvcio_last_error());
+        if (uvcio_famstats_add_piece(o.fam, w.targets[q], &w.fam_rows[q * (size_t)UVC_FAMSTAT_ROW])) die(uvcio_last_error());
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// The record text of one call behind `lines`: write(dst, room, &len) into a buffer as large as the last tiles needed (+ slack); a second
+// call only when the text did not fit
+template <class F> void append_text(Worker &w, std::string &lines, F write) {
+    const size_t at = lines.size();
+    int64_t len = 0, room = std::max<int64_t>(1 << 16, w.text_cap);
+    for (;;) {
+        lines.resize(at + (size_t)room);
+        const int rc = write(&lines[at], room, &len);
+        if (rc == UVCGPU_ENOMEM && len > room) { room = len + len / 4; continue; }
+        if (rc) die(uvcgpu_last_error());
+        break;
+    }
+    lines.resize(at + (size_t)len);
+    w.text_cap = std::max<int64_t>(w.text_cap, len + len / 4);
+}
 
 // process_batch for one tile; appends the record lines to `lines`; false = nothing to call there.  *n_kept_reads: reads that passed the filters.
 // `tumor_ready` (pair mode): called with the tumor records' range before they are fetched; returns once the store holds all of them
@@ -674,12 +709,10 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     }
     if (o.readprof) readprofile_of_tile(w, o, own);   // the BAM's own qualities: in front of the correction
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
-    if (o.cov || o.errprof || o.callable || o.msi) {
-        if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
-        if (o.errprof) errprofile_of_tile(w, o, own);
-        if (o.callable) callable_of_tile(w, o, own, call_target_of);
-        if (o.msi) msi_of_tile(w, o, own, call_target_of, w.ref, ext_beg);
-    }
+    if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
+    if (o.errprof) errprofile_of_tile(w, o, own);
+    if (o.callable) callable_of_tile(w, o, own, call_target_of);
+    if (o.msi) msi_of_tile(w, o, own, call_target_of, w.ref, ext_beg);
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
     rq.is_amplicon = (o.assay_type == 0 ? (go.n_amplicon * 2 > k) : (o.assay_type == 2));   // inferred_assay_type, main.cpp:510-511
@@ -704,17 +737,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
         double t_wait = now();
         while ((rc = uvcgpu_score_stream_next(ss, &chunk, w.covered.data(), &n_cov)) == 0) {
             w.t_gpu += now() - t_wait; t0 = now();
-            const size_t at = lines.size();
-            int64_t len = 0, room = std::max<int64_t>(1 << 16, w.text_cap);
-            for (;;) {
-                lines.resize(at + (size_t)room);
-                rc = uvcgpu_region_vcf_records_ranges(w.reg, t.chrom.c_str(), &chunk, &rt, w.covered.data(), n_cov, &lines[at], room, &len);
-                if (rc == UVCGPU_ENOMEM && len > room) { room = len + len / 4; continue; }
-                if (rc) die(uvcgpu_last_error());
-                break;
-            }
-            lines.resize(at + (size_t)len);
-            w.text_cap = std::max<int64_t>(w.text_cap, len + len / 4);
+            append_text(w, lines, [&](char *dst, int64_t room, int64_t *len) { return uvcgpu_region_vcf_records_ranges(w.reg, t.chrom.c_str(), &chunk, &rt, w.covered.data(), n_cov, dst, room, len); });
             w.n_chunks++;
             w.t_text += now() - t0; t_wait = now();
         }
@@ -737,19 +760,10 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     }
     w.score_cap = cap;
     w.t_gpu += now() - t0; t0 = now();
-    // one call with a buffer as large as the last tile needed (+ slack); a second one only when the text did not fit
-    const size_t at = lines.size();
-    int64_t len = 0, room = std::max<int64_t>(1 << 16, w.text_cap);
-    for (;;) {
-        lines.resize(at + (size_t)room);
-        rc = n_merged > 0 ? uvcgpu_region_vcf_records_ranges(w.reg, t.chrom.c_str(), &so, &rq, ranges.data(), n_ranges, &lines[at], room, &len)
-                          : uvcgpu_region_vcf_records(w.reg, t.chrom.c_str(), &so, &rq, &lines[at], room, &len);
-        if (rc == UVCGPU_ENOMEM && len > room) { room = len + len / 4; continue; }
-        if (rc) die(uvcgpu_last_error());
-        break;
-    }
-    lines.resize(at + (size_t)len);
-    w.text_cap = std::max<int64_t>(w.text_cap, len + len / 4);
+    append_text(w, lines, [&](char *dst, int64_t room, int64_t *len) {
+        return n_merged > 0 ? uvcgpu_region_vcf_records_ranges(w.reg, t.chrom.c_str(), &so, &rq, ranges.data(), n_ranges, dst, room, len)
+                            : uvcgpu_region_vcf_records(w.reg, t.chrom.c_str(), &so, &rq, dst, room, len);
+    });
     w.t_text += now() - t0;
     return true;
 }
@@ -839,10 +853,10 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
             });
         };
         const char *chrom = names[(size_t)tid].c_str();
-        if (o.cov && cov_spans && o.coverage_window > 0 && end > beg)
-            window_targets("--coverage-window", o.coverage_window, (*cov_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_coverage_add_target(o.cov, chrom, wb, we, nullptr, we - wb); });
-        if (o.fam && fam_spans && o.famstats_window > 0 && end > beg)
-            window_targets("--family-stats-window", o.famstats_window, (*fam_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_famstats_add_target(o.fam, chrom, wb, we, nullptr); });
+        if (o.cov && cov_spans && o.report[R_COVERAGE].window > 0 && end > beg)
+            window_targets("--coverage-window", o.report[R_COVERAGE].window, (*cov_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_coverage_add_target(o.cov, chrom, wb, we, nullptr, we - wb); });
+        if (o.fam && fam_spans && o.report[R_FAMSTATS].window > 0 && end > beg)
+            window_targets("--family-stats-window", o.report[R_FAMSTATS].window, (*fam_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_famstats_add_target(o.fam, chrom, wb, we, nullptr); });
         if ((o.callable || o.msi) && bed_path.empty()) {   // --callable-out, --msi-out without a BED file: the called span of the contig is one target
             if (o.call_contig_target[(size_t)tid] >= 0) die("--callable-out, --msi-out: a contig is called twice (internal error)");
             call_target = o.call_contig_target[(size_t)tid] = add_span_target(names[(size_t)tid].c_str(), beg, end, nullptr);
@@ -1001,7 +1015,7 @@ std::vector<std::vector<FamPiece>> plan_family_pieces(const Opts &o, const std::
     std::vector<std::vector<FamPiece>> plan(tiles.size());
     std::vector<int64_t> reach((size_t)nref, 0);   // per contig: the largest end of the pieces planned so far
     int64_t last_target = -1;
-    const int64_t N = o.famstats_window;
+    const int64_t N = o.report[R_FAMSTATS].window;
     for (size_t q = 0; q < tiles.size(); q++) {
         const Tile &t = tiles[q];
         for (int64_t b = t.beg; b < t.end;) {
@@ -1055,15 +1069,8 @@ PairArgs split_pair(int argc, char **argv) {
         const std::string name = t.substr(0, t.compare(0, 2, "--") == 0 ? t.find('=') : std::string::npos);
         if (name == "--tumor-vcf" || name == "--bed-in-fname") die(name + " cannot go with --normal-bam: pair mode hands the tumor records and regions over itself");
         if (name == "--repeat") die("--repeat cannot go with --normal-bam");
-        auto no_report = [&](std::initializer_list<const char *> opts, const char *what) {   // the options of a report: pair mode writes none
-            for (const char *opt : opts) if (name == opt) die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no " + what);
-        };
-        no_report({ "--coverage-out", "--coverage-thresholds", "--coverage-window" }, "coverage report");
-        no_report({ "--error-profile-out", "--error-profile-min-depth", "--error-profile-max-alt-permille" }, "error profile");
-        no_report({ "--callable-out", "--callable-min-depth", "--callable-max-aDP" }, "callable regions");
-        no_report({ "--family-stats-out", "--family-stats-window" }, "family report");
-        no_report({ "--msi-out", "--msi-min-tract", "--msi-min-units", "--msi-max-unit", "--msi-min-depth", "--msi-unstable-permille" }, "microsatellite tally");
-        no_report({ "--read-profile-out", "--read-profile-min-mapq", "--read-profile-min-depth", "--read-profile-max-alt-permille" }, "read profile");
+        int sub; const int rep = report_of(name, &sub);   // the options of a report: pair mode writes none
+        if (rep >= 0) die(name + " cannot go with --normal-bam: pair mode has its own tile loop and writes no " + REPORTS[rep].pair_writes_no);
         if (name == "--force-sites") die("--force-sites cannot go with --normal-bam: the normal pass's gate is the tumor's rescue set");
         if (name == "--merge-regions" && atoll((t.find('=') != std::string::npos ? t.substr(t.find('=') + 1) : (i + 1 < a.shared.size() ? a.shared[i + 1] : std::string("0"))).c_str()) > 0)
             die("--merge-regions cannot go with --normal-bam: pair mode calls both samples region by region");
@@ -1327,27 +1334,17 @@ int main(int argc, char **argv) {
     const int32_t nref = (int32_t)G.names.size();
     std::vector<int64_t> batch_of;   // --merge-regions: the batch of every tile (else empty: every tile is its own job)
     std::vector<CovSpan> cov_spans((size_t)nref);
-    if (!o.coverage_out.empty() && !o.print_params) {
-        const char *mnames[UVC_NCOV]; for (int32_t m = 0; m < UVC_NCOV; m++) mnames[m] = uvcgpu_coverage_measure_name(m);
-        if (uvcio_coverage_open(&o.cov, mnames, UVC_NCOV, o.coverage_thr.data(), (int32_t)o.coverage_thr.size())) die(uvcio_last_error());
-    }
-    if (!o.errprof_out.empty() && !o.print_params) {
-        const char *lnames[UVC_NERRLEVEL]; for (int32_t l = 0; l < UVC_NERRLEVEL; l++) lnames[l] = uvcgpu_error_level_name(l);
-        if (uvcio_errprofile_open(&o.errprof, lnames, UVC_NERRLEVEL, o.errprof_req.min_depth, o.errprof_req.max_alt_permille)) die(uvcio_last_error());
-    }
-    if (!o.callable_out.empty() && !o.print_params) {
-        const char *mnames[UVC_NCOV], *bnames[UVC_NCALLBIT];
-        for (int32_t m = 0; m < UVC_NCOV; m++) mnames[m] = uvcgpu_coverage_measure_name(m);
-        for (int32_t b = 0; b < UVC_NCALLBIT; b++) bnames[b] = uvcgpu_callable_bit_name(b);
-        if (uvcio_callable_open(&o.callable, mnames, UVC_NCOV, o.call_req.min_depth, o.call_req.max_aDP, bnames, UVC_NCALLBIT)) die(uvcio_last_error());
-    }
-    if (!o.msi_out.empty() && !o.print_params && uvcio_msi_open(&o.msi, o.msi_req.min_tracklen, o.msi_req.min_units, o.msi_req.max_unitlen, o.msi_min_depth, o.msi_unstable_permille)) die(uvcio_last_error());
-    if (!o.readprof_out.empty() && !o.print_params) {
-        const char *cnames[UVC_READPROF_NCLASS]; for (int32_t c = 0; c < UVC_READPROF_NCLASS; c++) cnames[c] = uvcgpu_read_class_name(c);
-        if (uvcio_readprofile_open(&o.readprof, cnames, o.readprof_req.min_mapq, o.readprof_req.min_depth, o.readprof_req.max_alt_permille)) die(uvcio_last_error());
-    }
+    // the stores of the reports that are asked for; --print-params plans the tiles without them
+    auto wanted = [&](ReportId r) { return !o.print_params && !o.report[r].path.empty(); };
+    auto names_of = [](const char *(*name_of)(int32_t), int32_t n) { std::vector<const char *> v; for (int32_t i = 0; i < n; i++) v.push_back(name_of(i)); return v; };   // the library's names of a store's columns
+    const std::vector<const char *> mnames = names_of(uvcgpu_coverage_measure_name, UVC_NCOV);   // the depths of --coverage-out and --callable-out
+    if (wanted(R_COVERAGE) && uvcio_coverage_open(&o.cov, mnames.data(), UVC_NCOV, o.coverage_thr.data(), (int32_t)o.coverage_thr.size())) die(uvcio_last_error());
+    if (wanted(R_ERRPROF) && uvcio_errprofile_open(&o.errprof, names_of(uvcgpu_error_level_name, UVC_NERRLEVEL).data(), UVC_NERRLEVEL, o.errprof_req.min_depth, o.errprof_req.max_alt_permille)) die(uvcio_last_error());
+    if (wanted(R_CALLABLE) && uvcio_callable_open(&o.callable, mnames.data(), UVC_NCOV, o.call_req.min_depth, o.call_req.max_aDP, names_of(uvcgpu_callable_bit_name, UVC_NCALLBIT).data(), UVC_NCALLBIT)) die(uvcio_last_error());
+    if (wanted(R_MSI) && uvcio_msi_open(&o.msi, o.msi_req.min_tracklen, o.msi_req.min_units, o.msi_req.max_unitlen, o.msi_min_depth, o.msi_unstable_permille)) die(uvcio_last_error());
+    if (wanted(R_READPROF) && uvcio_readprofile_open(&o.readprof, names_of(uvcgpu_read_class_name, UVC_READPROF_NCLASS).data(), o.readprof_req.min_mapq, o.readprof_req.min_depth, o.readprof_req.max_alt_permille)) die(uvcio_last_error());
     std::vector<CovSpan> fam_spans((size_t)nref);
-    if (!o.famstats_out.empty() && !o.print_params && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
+    if (wanted(R_FAMSTATS) && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
     std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans);
     std::vector<std::vector<FamPiece>> fam_plan;
     if (o.fam) fam_plan = plan_family_pieces(o, tiles, fam_spans, nref);
@@ -1400,12 +1397,7 @@ int main(int argc, char **argv) {
     uvcio_bgzf_writer_t *zw = nullptr;
     if (uvcio_bgzf_write_open(&zw, o.out.c_str(), 6)) die(uvcio_last_error());
     // a report path that cannot be written fails here, not behind the last tile
-    if (o.cov) probe_create("--coverage-out", o.coverage_out);
-    if (o.fam) probe_create("--family-stats-out", o.famstats_out);
-    if (o.callable) probe_create("--callable-out", o.callable_out);
-    if (o.msi) probe_create("--msi-out", o.msi_out);
-    if (o.errprof) probe_create("--error-profile-out", o.errprof_out);
-    if (o.readprof) probe_create("--read-profile-out", o.readprof_out);
+    for (int r = 0; r < N_REPORTS; r++) if (!o.report[r].path.empty()) probe_create(REPORTS[r].out, o.report[r].path);
     if (!o.no_header) {
         const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
@@ -1452,19 +1444,20 @@ int main(int argc, char **argv) {
     if (uvcio_bgzf_write_close(zw)) die(uvcio_last_error());
     // every tile has reported.  The stores write in target order whichever worker finished first (callable: sorted, filled and joined per
     // target); sums do not depend on the order
-    auto finish = [](const char *opt, int rc) { if (rc) die(std::string(opt) + ": " + uvcio_last_error()); };
-    if (o.cov) { finish("--coverage-out", uvcio_coverage_write(o.cov, o.coverage_out.c_str())); uvcio_coverage_close(o.cov); }
-    if (o.fam) { finish("--family-stats-out", uvcio_famstats_write(o.fam, o.famstats_out.c_str())); uvcio_famstats_close(o.fam); }
+    auto path = [&](ReportId r) { return o.report[r].path.c_str(); };
+    auto finish = [](ReportId r, int rc) { if (rc) die(std::string(REPORTS[r].out) + ": " + uvcio_last_error()); };
+    if (o.cov) { finish(R_COVERAGE, uvcio_coverage_write(o.cov, path(R_COVERAGE))); uvcio_coverage_close(o.cov); }
+    if (o.fam) { finish(R_FAMSTATS, uvcio_famstats_write(o.fam, path(R_FAMSTATS))); uvcio_famstats_close(o.fam); }
     if (o.callable) {
         if (o.timing) fprintf(stderr, "uvc1-mi355x: --callable-out holds %lld runs\n", (long long)uvcio_callable_n_runs(o.callable));
-        finish("--callable-out", uvcio_callable_write(o.callable, o.callable_out.c_str())); uvcio_callable_close(o.callable);
+        finish(R_CALLABLE, uvcio_callable_write(o.callable, path(R_CALLABLE))); uvcio_callable_close(o.callable);
     }
     if (o.msi) {
         if (o.timing) fprintf(stderr, "uvc1-mi355x: --msi-out holds %lld loci\n", (long long)uvcio_msi_n_loci(o.msi));
-        finish("--msi-out", uvcio_msi_write(o.msi, o.msi_out.c_str())); uvcio_msi_close(o.msi);
+        finish(R_MSI, uvcio_msi_write(o.msi, path(R_MSI))); uvcio_msi_close(o.msi);
     }
-    if (o.errprof) { finish("--error-profile-out", uvcio_errprofile_write(o.errprof, o.errprof_out.c_str())); uvcio_errprofile_close(o.errprof); }
-    if (o.readprof) { finish("--read-profile-out", uvcio_readprofile_write(o.readprof, o.readprof_out.c_str())); uvcio_readprofile_close(o.readprof); }
+    if (o.errprof) { finish(R_ERRPROF, uvcio_errprofile_write(o.errprof, path(R_ERRPROF))); uvcio_errprofile_close(o.errprof); }
+    if (o.readprof) { finish(R_READPROF, uvcio_readprofile_write(o.readprof, path(R_READPROF))); uvcio_readprofile_close(o.readprof); }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

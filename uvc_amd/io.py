@@ -176,25 +176,54 @@ class BgzfWriter:
         self.close()
 
 
-class FamilyStats:
+class _Store:
+    """What the stores of the reports share: an open handle `h` of the functions uvcio_<name>_*, written by write(), closed by close()
+    or at the end of a `with` block, and add_target where the store has targets.  The constructors open it; what a store takes
+    (add*) is its own."""
+
+    def _bind(self, name):
+        """The library with the shared functions of uvcio_<name>_* declared; the handle is not open yet."""
+        self.name, self.h = name, C.c_void_p()
+        self._f("write").restype, self._f("write").argtypes = C.c_int, [C.c_void_p, C.c_char_p]
+        self._f("close").restype, self._f("close").argtypes = None, [C.c_void_p]
+        return dll()
+
+    def _f(self, what):
+        return getattr(dll(), "uvcio_%s_%s" % (self.name, what))
+
+    def write(self, path):
+        _check(self._f("write")(self.h, str(path).encode()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, C.c_void_p()
+            self._f("close")(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def add_target(self, chrom, beg, end, name=None):
+        """A target, added in report order: its index (FamilyStats, Callable, Msi)."""
+        f = self._f("add_target")
+        f.restype, f.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
+        t = f(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
+        if t < 0:
+            _check(int(t))
+        return int(t)
+
+
+class FamilyStats(_Store):
     """uvcio_famstats_*: the store behind uvc1-mi355x --family-stats-out.  Targets are added in report order; a piece is one row of
     Region.family_stats (its TARGET block goes to the target, its FIRST block to the run's sum; any thread, any order); write() makes the text."""
 
     def __init__(self):
-        d = dll()
+        d = self._bind("famstats")
         d.uvcio_famstats_open.restype, d.uvcio_famstats_open.argtypes = C.c_int, [C.POINTER(C.c_void_p)]
-        d.uvcio_famstats_add_target.restype, d.uvcio_famstats_add_target.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
         d.uvcio_famstats_add_piece.restype, d.uvcio_famstats_add_piece.argtypes = C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]
-        d.uvcio_famstats_write.restype, d.uvcio_famstats_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
-        d.uvcio_famstats_close.restype, d.uvcio_famstats_close.argtypes = None, [C.c_void_p]
-        self.h = C.c_void_p()
         _check(d.uvcio_famstats_open(C.byref(self.h)))
-
-    def add_target(self, chrom, beg, end, name=None):
-        t = dll().uvcio_famstats_add_target(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
-        if t < 0:
-            _check(int(t))
-        return int(t)
 
     def add_piece(self, target, row):
         import numpy as np
@@ -203,34 +232,19 @@ class FamilyStats:
             raise ValueError("a piece is one row of Region.family_stats (365 values)")
         _check(dll().uvcio_famstats_add_piece(self.h, int(target), row.ctypes.data))
 
-    def write(self, path):
-        _check(dll().uvcio_famstats_write(self.h, str(path).encode()))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, C.c_void_p()
-            dll().uvcio_famstats_close(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
-class ReadProfile:
+class ReadProfile(_Store):
     """uvcio_readprofile_*: the store behind uvc1-mi355x --read-profile-out.  add() sums one row of Region.read_profile (any thread, any
     order: rows of disjoint position sets add); write() makes the text."""
+    add_target = None   # one row for the whole run: no targets
 
     def __init__(self, classes, min_mapq=0, min_depth=20, max_alt_permille=50):
-        d = dll()
+        d = self._bind("readprofile")
         d.uvcio_readprofile_open.restype, d.uvcio_readprofile_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32]
         d.uvcio_readprofile_add.restype, d.uvcio_readprofile_add.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
-        d.uvcio_readprofile_write.restype, d.uvcio_readprofile_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
-        d.uvcio_readprofile_close.restype, d.uvcio_readprofile_close.argtypes = None, [C.c_void_p]
         if len(classes) != 4:
             raise ValueError("the read classes are four (region.READ_CLASSES)")
-        self.h = C.c_void_p()
         _check(d.uvcio_readprofile_open(C.byref(self.h), (C.c_char_p * 4)(*[c.encode() for c in classes]), int(min_mapq), int(min_depth), int(max_alt_permille)))
 
     def add(self, row):
@@ -240,45 +254,22 @@ class ReadProfile:
             raise ValueError("a piece is one row of Region.read_profile (5712 values)")
         _check(dll().uvcio_readprofile_add(self.h, row.ctypes.data))
 
-    def write(self, path):
-        _check(dll().uvcio_readprofile_write(self.h, str(path).encode()))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, C.c_void_p()
-            dll().uvcio_readprofile_close(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
-class Callable:
+class Callable(_Store):
     """uvcio_callable_*: the store behind uvc1-mi355x --callable-out.  Targets are added in report order with their positions inside the
     contig; add_runs takes the runs of one Region.callable and the target of each of its ranges (any thread, any order); write() sorts,
     fills what no piece reported with the mask of depth 0, joins equal neighbours inside a target and makes the BED text."""
 
     def __init__(self, measures, min_depth, max_aDP, bits):
-        d = dll()
+        d = self._bind("callable")
         d.uvcio_callable_open.restype, d.uvcio_callable_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32]
-        d.uvcio_callable_add_target.restype, d.uvcio_callable_add_target.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
         d.uvcio_callable_add_runs.restype, d.uvcio_callable_add_runs.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         d.uvcio_callable_n_runs.restype, d.uvcio_callable_n_runs.argtypes = C.c_int64, [C.c_void_p]
-        d.uvcio_callable_write.restype, d.uvcio_callable_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
-        d.uvcio_callable_close.restype, d.uvcio_callable_close.argtypes = None, [C.c_void_p]
-        self.h = C.c_void_p()
         names = (C.c_char_p * len(measures))(*[m.encode() for m in measures])
         bnames = (C.c_char_p * len(bits))(*[b.encode() for b in bits])
         md = (C.c_int32 * len(measures))(*[int(v) for v in min_depth])
         _check(d.uvcio_callable_open(C.byref(self.h), names, len(measures), md, int(max_aDP), bnames, len(bits)))
-
-    def add_target(self, chrom, beg, end, name=None):
-        t = dll().uvcio_callable_add_target(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
-        if t < 0:
-            _check(int(t))
-        return int(t)
 
     def add_runs(self, target_of_range, runs):
         """runs: the structured array of Region.callable (range, pos_beg, pos_end, mask); target_of_range[k]: the target of the call's range k"""
@@ -292,42 +283,19 @@ class Callable:
     def n_runs(self):
         return int(dll().uvcio_callable_n_runs(self.h))
 
-    def write(self, path):
-        _check(dll().uvcio_callable_write(self.h, str(path).encode()))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, C.c_void_p()
-            dll().uvcio_callable_close(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
-class Msi:
+class Msi(_Store):
     """uvcio_msi_*: the store behind uvc1-mi355x --msi-out.  Targets are added in report order with their positions inside the contig; add
     takes the rows of one Region.msi, the target of each of its ranges and the first unit of each locus as text (any thread, any order);
     write() sorts by target then position and makes the tab-separated text with its #summary lines."""
 
     def __init__(self, min_tracklen=10, min_units=5, max_unitlen=6, min_depth=30, unstable_permille=200):
-        d = dll()
+        d = self._bind("msi")
         d.uvcio_msi_open.restype, d.uvcio_msi_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-        d.uvcio_msi_add_target.restype, d.uvcio_msi_add_target.argtypes = C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_char_p]
         d.uvcio_msi_add.restype, d.uvcio_msi_add.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_char_p), C.c_int64]
         d.uvcio_msi_n_loci.restype, d.uvcio_msi_n_loci.argtypes = C.c_int64, [C.c_void_p]
-        d.uvcio_msi_write.restype, d.uvcio_msi_write.argtypes = C.c_int, [C.c_void_p, C.c_char_p]
-        d.uvcio_msi_close.restype, d.uvcio_msi_close.argtypes = None, [C.c_void_p]
-        self.h = C.c_void_p()
         _check(d.uvcio_msi_open(C.byref(self.h), int(min_tracklen), int(min_units), int(max_unitlen), int(min_depth), int(unstable_permille)))
-
-    def add_target(self, chrom, beg, end, name=None):
-        t = dll().uvcio_msi_add_target(self.h, chrom.encode(), int(beg), int(end), name.encode() if name else None)
-        if t < 0:
-            _check(int(t))
-        return int(t)
 
     def add(self, target_of_range, loci, units):
         """loci: the int32 [n][UVC_MSI_ROW] array of Region.msi; units[k]: the reference bases of the first unit of locus k;
@@ -343,19 +311,6 @@ class Msi:
     def n_loci(self):
         return int(dll().uvcio_msi_n_loci(self.h))
 
-    def write(self, path):
-        _check(dll().uvcio_msi_write(self.h, str(path).encode()))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, C.c_void_p()
-            dll().uvcio_msi_close(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def plan_regions(tid, pos, endpos, flag, target_lens, nthreads=1, mem_per_thread_mb=1536):
