@@ -71,7 +71,8 @@ struct FragRec {
     int32_t fs, strand, dflag, normMQ;
     int32_t n_cov, n_near;      // b10xSeqTlen / b10xSeqTNevents, main.hpp:2747-2756 (filled by k_fragstat)
     int32_t singleton;          // 1: the only fragment of its family-strand unit and the fast P4/P5 identities apply
-    int32_t stat_kind;          // 0: n_cov/n_near from mutation events (<= 2 simple alignments, no primer gating); 1: per-fragment sweep
+    int32_t stat_kind;          // 0: n_cov/n_near from mutation events (<= 2 simple alignments, no primer gating); 1: per-fragment sweep;
+                                // 2: the same, and k_frag_generic at every position (a read of the fragment has a base of value 0: k_build_frags)
 };
 
 struct FsRec {                  // family x strand unit (alns2 of main.hpp:2869)

@@ -342,7 +342,7 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
         int rc0;
         int64_t *so = nullptr, *co = nullptr, *b4o = nullptr; uint8_t *ub = nullptr; char *tmp = nullptr;
         const size_t tb = uvc_prep_compact_tmp_bytes(n);
-        if ((rc0 = dev_alloc(r, tb, &tmp)) || (rc0 = dev_alloc(r, 1, &d_bad, true))) return rc0;
+        if ((rc0 = dev_alloc(r, tb, &tmp)) || (rc0 = dev_alloc(r, 2, &d_bad, true))) return rc0;   // [0] malformed input, [1] a quality byte of 0
         if (!d->seq_off && (rc0 = dev_alloc(r, (size_t)n, &so))) return rc0;
         if (!d->cigar_off && (rc0 = dev_alloc(r, (size_t)n, &co))) return rc0;
         if (!d->bases && ((rc0 = dev_alloc(r, (size_t)n, &b4o)) || (rc0 = dev_alloc(r, (size_t)std::max<int64_t>(d->n_bases, 1), &ub)) || (rc0 = dev_alloc(r, (size_t)std::max<int64_t>(d->n_bases, 1), &bq_done)))) return rc0;
@@ -357,6 +357,16 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
     in.n_reads = n; in.n_bases = d->n_bases; in.n_cigar_ops = d->n_cigar_ops; in.n_fams = d->n_fams;
     in.pos = d->pos; in.mpos = d->mpos; in.isize = d->isize; in.nm = d->nm; in.l_qseq = d->l_qseq; in.n_cigar = d->n_cigar; in.frag_id = d->frag_id; in.fam_id = d->fam_id;
     in.flag = d->flag; in.mapq = d->mapq; in.fam_strand = d->fam_strand; in.fam_dflag = d->fam_dflag; in.seq_off = d->seq_off; in.cigar_off = d->cigar_off; in.cigars = d->cigars;
+    // base | quality is packed in front of the preparation: the packing kernels say whether the column has a quality byte of 0 at all
+    // (UvcPrepIn::zero_qual), which decides whether the fragments' qualities are looked at there
+    uint16_t *bq_packed = bq_done;
+    if (!bq_packed) {
+        int rc1;
+        if ((rc1 = dev_alloc(r, (size_t)std::max<int64_t>(d->n_bases, 1), &bq_packed))) return rc1;
+        if (!d_bad && (rc1 = dev_alloc(r, 2, &d_bad, true))) return rc1;
+        uvc_launch_pack_bq(d->bases, d->quals, bq_packed, d->n_bases, d_bad, r->stream);
+    }
+    in.quals = d->quals; in.zero_qual = d_bad + 1;
     UvcPrepOut o; char msg[256];
     int rc = uvc_prep_reads(&in, &r->P, r->beg, r->end, r->npos, prep_alloc, r, r->stream, &o, msg, (int)sizeof(msg));
     if (rc) return fail(rc, msg);
@@ -368,10 +378,7 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
     R.bases = d->bases; R.quals = d->quals; R.cigars = d->cigars;
     R.frag_off[0] = 0; R.frag_off[1] = o.n_frag_strand0; R.frag_off[2] = o.n_frags;
     const int64_t n_simple = o.n_simple; const size_t nf = (size_t)o.n_frags;
-    if (bq_done) { R.bq = bq_done; R.bq_bytes = (uint32_t)(d->n_bases * 2); }   // packed while the 4-bit bases were unpacked
-    else { uint16_t *b = nullptr; if ((rc = dev_alloc(r, (size_t)std::max<int64_t>(d->n_bases, 1), &b))) return rc; R.bq = b; R.bq_bytes = (uint32_t)(d->n_bases * 2);
-      if (!d_bad && (rc = dev_alloc(r, 1, &d_bad, true))) return rc;
-      uvc_launch_pack_bq(R.bases, R.quals, b, d->n_bases, d_bad, r->stream); }
+    R.bq = bq_packed; R.bq_bytes = (uint32_t)(d->n_bases * 2);   // (with bases4: packed while the 4-bit bases were unpacked)
     { AlnRec *a; if ((rc = dev_alloc(r, (size_t)n, &a))) return rc; R.alns = a; R.n_alns = (int32_t)n; }
     R.n_fast = (int32_t)n_simple;
     R.complex_ids = o.complex_ids; R.n_complex = o.n_complex;

@@ -18,6 +18,7 @@
 //   k_build_p2list   per entry      the work-list records of the M runs of InDel reads (one list for P1 and P2, 4 orientation classes)
 //   k_correct_bq     per read       apply_bq_err_correction3 (on request)                     grouping.cpp:459-543
 //   k_prep_fast      per position   P1 for simple reads (the work list without the M runs)    main.hpp:924-1204
+//   k_prep_scan      read / tile    the same by a byte-parallel scan of each read + interval sums (the default where the split form does not run)
 //   k_prep_slow      wave per read  P1 for reads with InDels (atomics)
 //   k_thres          per position   P1b, also edits rtr.indelphred                            main.hpp:1206-1299
 //   k_p2_fast<L,B>   per position   P2 + dealwith_segbias, LINK_M / read base instantiations   main.hpp:1360-1595, 1762-2296
@@ -35,6 +36,8 @@
 //   k_gap_keys/alleles/rows  per (family, InDel position)  the allele-keyed counters of the InDel symbols   main.hpp:2710-2717, 3196-3546
 // uvc_launch_accumulate at the end of the file orders them on two streams.
 #include "uvc_launch.h"
+#include <stdlib.h>
+#include <string.h>
 
 // ------------------------------------------------------------------------------------------------
 // small helpers
@@ -802,6 +805,214 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
     COARSE_T(ct3)
     if (lane == 0 && ((int)(x0 >> 6) % 2999) == 7) printf("coarse prep wave %d lists %llu epilogue %llu\n", (int)(x0 >> 6), ct2 - ct1, ct3 - ct2);
 #endif
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_prep_scan: what k_prep_fast<false> computes, read by read instead of window by window.  The five counters behind the base quality
+// (a_highBQ_dp, a_l_dist_sum, a_r_dist_sum, a_l_BAQ_sum, a_r_BAQ_sum) are sums over the covering simple reads whose base at the position
+// has quality >= bias_thres_highBQ: the sum over ALL covering reads is an interval sum (k_prep_sums), and every low-quality base takes its
+// read's term out again at its own position.  With A the number of covering reads and n the number of low-quality bases at p,
+//   a_highBQ_dp  = A - n
+//   a_l_dist_sum = (p + 1) (A - n) - (S apos - C apos)                mod 2^32, as the plane's wrapping adds
+//   a_r_dist_sum = (S rend - C rend) - p (A - n)
+//   a_l_BAQ_sum  = (A - n) d(p) + (S cL - C cL),  d(p) = baq(p) - baq(t0),  cL = baq(t0) - baq(apos) + 1      (t0: the tile's first position)
+//   a_r_BAQ_sum  = (S cR - C cR) - (A - n) d(p),                            cR = baq(rend - 1) - baq(t0) + 1
+// (S: interval sums over the covering reads, C: sums over the reads that are low at p).  d, cL and cR are wrapping 32-bit differences of
+// the LOW words of the 64-bit BAQ prefix sums; k_prep_fast adds (int)(baq(p) - baq(apos) + 1) = d + cL per read, which holds as integers
+// while neither side overflows 32 bits -- prep_scan_exact() bounds the differences from the parameters and leaves the rest to k_prep_fast.
+// One block per tile of PSCAN_TILE positions takes the work-list entries that reach the tile; eight lanes per entry compare eight bases
+// per lane and step with the reference and test eight qualities, as k_aln_bm does (bytes outside [max(apos, tile begin), min(rend, tile
+// end)) are masked: every base is scanned by the one tile that owns its position).  S and C share five difference arrays in LDS: a read
+// adds +v / -v at the ends of its piece of the tile and -v / +v at p and p + 1 of each of its low-quality bases.  After a block prefix
+// sum every plane gets one coalesced global atomic per position (k_prep_slow adds to the same planes meanwhile).  Mismatching bases wait
+// in an LDS queue and go through snv_dnv_scatter / mut_event a block at a time; the clip events fire in the tile that owns their position.
+// The scan waits on memory (a read's bases and qualities are two or three cache lines each, scattered over the columns): the next
+// entry's record and all words of this one are requested before anything is used (tile sizes and variants: DESIGN.md section 6-r6).
+// ------------------------------------------------------------------------------------------------
+#ifndef PSCAN_TILE
+#define PSCAN_TILE 1024
+#endif
+#define PSCAN_QCAP 512     // LDS queue of (alignment, position) pairs whose base differs from the reference
+#define PSCAN_ROUND 512    // entries between two looks at the queue
+#define PSCAN_WORDS 3      // 8-byte words per lane and trip: 192 bases of an entry (at most 8: a word's flags are every eighth bit of a mask)
+enum { PN_A = 0, PN_APOS, PN_REND, PN_N32 };
+enum { PN_CL = 0, PN_CR, PN_N64 };
+__global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
+    static_assert(PSCAN_TILE % 256 == 0 && PSCAN_TILE % 64 == 0, "a thread owns PSCAN_TILE / 256 consecutive positions in the prefix sums");
+    static_assert(PSCAN_WORDS <= 8, "a word's flags are every eighth bit of a mask");
+    constexpr int PER = PSCAN_TILE / 256;
+    // difference arrays: +v / -v at the ends of a read's piece of the tile, -v / +v around each of its low-quality bases; afterwards the finished counters
+    __shared__ unsigned d32[PN_N32][PSCAN_TILE + 1];
+    __shared__ unsigned long long d64[PN_N64][PSCAN_TILE + 1];
+    __shared__ int2 queue[PSCAN_QCAP];
+    __shared__ int qn;
+    __shared__ unsigned wtot[PN_N32][4];
+    __shared__ unsigned long long wtot64[PN_N64][4];
+    const unsigned long long K7F = 0x7F7F7F7F7F7F7F7FULL, K80 = 0x8080808080808080ULL, K01 = 0x0101010101010101ULL;
+    const int tid = threadIdx.x, sub = tid & 7, grp = tid >> 3;
+    const int tile = xcd_block();   // neighbouring tiles scan the reads across their boundary: one L2 for both
+    const int t0 = R.beg + tile * PSCAN_TILE, t1 = imin(t0 + PSCAN_TILE, R.beg + (int)R.npos);
+    const int w_first = tile * (PSCAN_TILE / 64), w_last = imin(w_first + PSCAN_TILE / 64, R.nwin) - 1;
+    int lo[4], cum[5];
+    cum[0] = 0;
+#pragma unroll
+    for (int cls = 0; cls < 4; cls++) { lo[cls] = win_lo(R, 1 + cls, w_first); cum[cls + 1] = cum[cls] + imax(win_hi(R, 1 + cls, w_last) - lo[cls], 0); }
+    const int total = cum[4];
+    if (total == 0) return;   // (the whole block: nothing reaches the tile)
+    for (int i = tid; i < PN_N32 * (PSCAN_TILE + 1); i += 256) (&d32[0][0])[i] = 0u;
+    for (int i = tid; i < PN_N64 * (PSCAN_TILE + 1); i += 256) (&d64[0][0])[i] = 0ull;
+    if (tid == 0) qn = 0;
+    __syncthreads();
+    const unsigned B0 = (unsigned)R.baq[t0 - R.beg];
+    // quality < thr on eight bytes at once: bit 7 of (q & 0x7F) + add says (q & 0x7F) >= thr (thr <= 128) resp. >= thr - 128
+    const int thr = P.bias_thres_highBQ;
+    const bool thr_hi = (thr > 128);
+    const unsigned long long qadd = K01 * (unsigned)(thr_hi ? imax(0x100 - thr, 0) : 0x80 - imax(thr, 0));
+    auto mismatch = [&](int aln, int p) {
+        const AlnRec &a = R.alns[aln];
+        snv_dnv_scatter(R, R.bases + a.seq_off, (int)(a.qbase + p - a.seq_off), a.l_qseq, a.pos, a.rend, p);
+        mut_event(R, P, a, p, R.refsym[p - R.beg]);
+    };
+    for (int base = 0; base < total; base += PSCAN_ROUND) {
+        const int stop = imin(base + PSCAN_ROUND, total);
+        // the record of the group's next entry is requested before this one's bases are: the group does not wait for the two in turn
+        int4 n0 = make_int4(0, 0, 0, 0), n2 = n0, n3 = n0;
+        const int4 *nq4 = nullptr;
+        auto fetch = [&](int i) {
+            const int cls = (i >= cum[1]) + (i >= cum[2]) + (i >= cum[3]);
+            nq4 = (const int4 *)(R.frec2 + ((cls == 0 ? lo[0] : cls == 1 ? lo[1] - cum[1] : cls == 2 ? lo[2] - cum[2] : lo[3] - cum[3]) + i));
+            n0 = nq4[0]; n2 = nq4[2]; n3 = nq4[3];
+        };
+        if (base + grp < stop) fetch(base + grp);
+        for (int i = base + grp; i < stop; i += 32) {
+            const int4 h0 = n0, h2 = n2, h3 = n3;   // pos rend qb_lo aln | bmv xbv bm4c clips | baq_pos baq_last baq2_last ext
+            const int4 *q4 = nq4;
+            if (i + 32 < stop) fetch(i + 32);
+            const int apos = h0.x, rend = h0.y;
+            if (rend <= t0 || apos >= t1 || apos >= rend) continue;   // (the eight lanes of the entry leave together)
+            if (h2.y & FREC_M_RUN) continue;   // an M run of an InDel read (k_prep_slow has the read)
+            const int s = imax(apos, t0), e = imin(rend, t1);
+            const int cL = (int)(B0 - (unsigned)h3.x + 1u), cR = (int)((unsigned)h3.y - B0 + 1u);
+            // up to PSCAN_WORDS words per lane are requested together, ahead of the LDS atomics
+            const bool whole = (e - s >= 8);
+            for (int pb = s + 8 * sub; pb < e; pb += 64 * PSCAN_WORDS) {
+                unsigned long long bb[PSCAN_WORDS], qq[PSCAN_WORDS], rr[PSCAN_WORDS];
+#pragma unroll
+                for (int w = 0; w < PSCAN_WORDS; w++) {
+                    const int p0 = pb + 64 * w, nb = imin(8, e - p0);
+                    bb[w] = 0; qq[w] = 0; rr[w] = 0;
+                    if (nb <= 0) continue;
+                    const uint8_t *bp = R.bases + (uint32_t)(h0.z + p0), *qp = R.quals + (uint32_t)(h0.z + p0), *rp = R.refsym + (p0 - R.beg);
+                    if (whole) {   // the last e - p0 < 8 bytes come from the word that ends with them: nothing is loaded past the read or the tile
+                        const int back = 8 - nb;
+                        bb[w] = load8u(bp - back) >> (8 * back); qq[w] = load8u(qp - back) >> (8 * back); rr[w] = load8u(rp - back) >> (8 * back);
+                    } else {
+                        for (int j = 0; j < nb; j++) { bb[w] |= (unsigned long long)bp[j] << (8 * j); qq[w] |= (unsigned long long)qp[j] << (8 * j); rr[w] |= (unsigned long long)rp[j] << (8 * j); }
+                    }
+                }
+                // bit 8 j + w: byte j of word w, i.e. position pb + 64 w + j, differs from the reference / has a low quality
+                unsigned long long mism = 0, low = 0;
+#pragma unroll
+                for (int w = 0; w < PSCAN_WORDS; w++) {
+                    const int nb = imin(8, e - (pb + 64 * w));
+                    if (nb <= 0) continue;
+                    const unsigned long long vm = K80 >> (8 * (8 - nb));   // bit 7 of the nb bytes that count
+                    const unsigned long long x = bb[w] ^ rr[w], t = (qq[w] & K7F) + qadd;
+                    mism |= (((((x & K7F) + K7F) | x) & vm) >> 7) << w;
+                    low |= (((thr_hi ? ~(qq[w] & t) : ~(qq[w] | t)) & vm) >> 7) << w;
+                }
+                while (low) {   // the read's terms leave the sums at this one position: -v at p, +v at p + 1
+                    const int bit = __builtin_ctzll(low), xp = pb + 64 * (bit & 7) + (bit >> 3) - t0;
+                    low &= low - 1;
+                    atomicAdd(&d32[PN_A][xp], 0u - 1u); atomicAdd(&d32[PN_A][xp + 1], 1u);
+                    atomicAdd(&d32[PN_APOS][xp], 0u - (unsigned)apos); atomicAdd(&d32[PN_APOS][xp + 1], (unsigned)apos);
+                    atomicAdd(&d32[PN_REND][xp], 0u - (unsigned)rend); atomicAdd(&d32[PN_REND][xp + 1], (unsigned)rend);
+                    atomicAdd(&d64[PN_CL][xp], 0ull - (unsigned long long)(long long)cL); atomicAdd(&d64[PN_CL][xp + 1], (unsigned long long)(long long)cL);
+                    atomicAdd(&d64[PN_CR][xp], 0ull - (unsigned long long)(long long)cR); atomicAdd(&d64[PN_CR][xp + 1], (unsigned long long)(long long)cR);
+                }
+                while (mism) {
+                    const int bit = __builtin_ctzll(mism), p = pb + 64 * (bit & 7) + (bit >> 3);
+                    mism &= mism - 1;
+                    const int slot = atomicAdd(&qn, 1);
+                    if (slot < PSCAN_QCAP) queue[slot] = make_int2(h0.w, p); else mismatch(h0.w, p);   // (a full queue: at once, by this lane)
+                }
+            }
+            // the interval sums, a lane per sum; the clip events
+            if (sub < PN_N32) {
+                const unsigned v = (sub == PN_A ? 1u : sub == PN_APOS ? (unsigned)apos : (unsigned)rend);
+                atomicAdd(&d32[sub][s - t0], v); atomicAdd(&d32[sub][e - t0], 0u - v);
+            } else if (sub < PN_N32 + PN_N64) {
+                const unsigned long long v = (unsigned long long)(long long)(sub == PN_N32 + PN_CL ? cL : cR);
+                atomicAdd(&d64[sub - PN_N32][s - t0], v); atomicAdd(&d64[sub - PN_N32][e - t0], 0ull - v);
+            } else if (sub == 7 && h2.w != 0) {
+                const int lclip = h2.w & 0xFFFF, rclip = (h2.w >> 16) & 0xFFFF;
+                const int pcr_inc = (((q4[1].x >> 24) & 0x4) ? 1 : 0);
+                if (lclip > 0 && apos >= t0) clip_event(R, P, apos, 0, lclip, pcr_inc);
+                if (rclip > 0 && rend <= t1) clip_event(R, P, rend, 1, rclip, pcr_inc);   // any index > 0 gives rpos_delta = -1
+            }
+        }
+        __syncthreads();
+        const int n_queued = imin(qn, PSCAN_QCAP);
+        const bool drain = (n_queued >= 256 || stop == total);   // a base per thread, or the last look
+        if (drain) for (int i = tid; i < n_queued; i += 256) mismatch(queue[i].x, queue[i].y);
+        __syncthreads();
+        if (drain && tid == 0) qn = 0;
+        __syncthreads();
+    }
+    // prefix sums of the five difference arrays at once: PER consecutive positions per thread, the wave's, the block's
+    const int lane = tid & 63, w = tid >> 6;
+    unsigned v32[PN_N32][PER], inc32[PN_N32];
+    unsigned long long v64[PN_N64][PER], inc64[PN_N64];
+#pragma unroll
+    for (int f = 0; f < PN_N32; f++) {
+        unsigned run = 0;
+#pragma unroll
+        for (int i = 0; i < PER; i++) { run += d32[f][tid * PER + i]; v32[f][i] = run; }
+        unsigned inc = run;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+        if (lane == 63) wtot[f][w] = inc;
+        inc32[f] = inc - run;
+    }
+#pragma unroll
+    for (int f = 0; f < PN_N64; f++) {
+        unsigned long long run = 0;
+#pragma unroll
+        for (int i = 0; i < PER; i++) { run += d64[f][tid * PER + i]; v64[f][i] = run; }
+        unsigned long long inc = run;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned long long u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
+        if (lane == 63) wtot64[f][w] = inc;
+        inc64[f] = inc - run;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < PN_N32; f++) for (int i = 0; i < w; i++) inc32[f] += wtot[f][i];
+#pragma unroll
+    for (int f = 0; f < PN_N64; f++) for (int i = 0; i < w; i++) inc64[f] += wtot64[f][i];
+    const int n_here = t1 - t0;
+#pragma unroll
+    for (int i = 0; i < PER; i++) {
+        const int x = tid * PER + i;
+        if (x >= n_here) continue;
+        const unsigned p = (unsigned)(t0 + x);
+        const unsigned hb = inc32[PN_A] + v32[PN_A][i];
+        const unsigned s_apos = inc32[PN_APOS] + v32[PN_APOS][i], s_rend = inc32[PN_REND] + v32[PN_REND][i];
+        const long long s_cl = (long long)(inc64[PN_CL] + v64[PN_CL][i]), s_cr = (long long)(inc64[PN_CR] + v64[PN_CR][i]);
+        const long long hd = (long long)hb * (long long)(int)((unsigned)R.baq[p - (unsigned)R.beg] - B0);
+        d32[PN_A][x] = hb; d32[PN_APOS][x] = (p + 1u) * hb - s_apos; d32[PN_REND][x] = s_rend - p * hb;
+        d64[PN_CL][x] = (unsigned long long)(hd + s_cl); d64[PN_CR][x] = (unsigned long long)(s_cr - hd);
+    }
+    __syncthreads();
+    // (the finished counters went back into LDS so that a wave's atomics cover 64 consecutive positions of a plane)
+    const int64_t xb = (int64_t)tile * PSCAN_TILE;
+    for (int x = tid; x < n_here; x += 256) {
+        const int hb = (int)d32[PN_A][x];
+        if (!hb) continue;   // no high-quality base of a simple read here: every sum is empty
+        atomicAdd(&P32(R, UVC_P_a_highBQ_dp, xb + x), hb);
+        atomicAdd(&P32(R, UVC_P_a_l_dist_sum, xb + x), (int)d32[PN_APOS][x]); atomicAdd(&P32(R, UVC_P_a_r_dist_sum, xb + x), (int)d32[PN_REND][x]);
+        add64(&P64(R, UVC_P_a_l_BAQ_sum, xb + x), (long long)d64[PN_CL][x]); add64(&P64(R, UVC_P_a_r_BAQ_sum, xb + x), (long long)d64[PN_CR][x]);
+    }
 }
 
 // P1 for one alignment whose CIGAR has InDels / unusual clip layouts: one wave per read, lanes stride over the bases of
@@ -1727,7 +1938,7 @@ __global__ void __launch_bounds__(256) k_fragstat_fast(RegionDev R, UvcParams P)
         const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
         const bool amplicon_gated = (((f.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag))) && !(P.tn_is_paired && (0x1 & P.primer_flag)));
         const int n_aln = f.aln_end - f.aln_beg;
-        bool ok = (!proton && !amplicon_gated && n_aln <= 2 && f.end - f.beg < 65536);
+        bool ok = (!proton && !amplicon_gated && n_aln <= 2 && f.end - f.beg < 65536 && f.stat_kind != 2);   // (2: a base of value 0, k_frag would count it)
         int sb, sl;
         if (ok) {
             const AlnRec &x0 = R.alns[f.aln_beg];
@@ -3625,20 +3836,22 @@ extern "C" void uvc_launch_correct_bq(const RegionDev *R, int bq_max, int bq_inc
 // (a base code above 4 is refused here, where the one-byte-per-base column enters: k_aln_bm compares eight bases per load and relies on every
 // byte being below 0x80, the per-symbol tables index with the code)
 __global__ void __launch_bounds__(256) k_pack_bq1(const uint8_t *bases, const uint8_t *quals, uint16_t *bq, int64_t n, int32_t *bad) {
-    int any = 0;
+    int any = 0, zero = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         bq[i] = (uint16_t)(bases[i] | (quals[i] << 8));
-        any |= (bases[i] > 4);
+        any |= (bases[i] > 4); zero |= (quals[i] == 0);
     }
     if (bad && __any(any) && (threadIdx.x & 63) == 0) *bad = 2;
+    if (bad && __any(zero) && (threadIdx.x & 63) == 0) bad[1] = 1;   // a quality byte of 0 (UvcPrepIn::zero_qual)
 }
 // eight read bases per thread: two 8-byte loads, one 16-byte store (a byte per thread ran at 1.7 TB/s of the 1.2 GB it moves)
 __global__ void __launch_bounds__(256) k_pack_bq(const uint8_t *bases, const uint8_t *quals, uint16_t *bq, int64_t n, int32_t *bad) {
     const int64_t n8 = n >> 3;
-    unsigned long long over = 0;   // bits 3..7 of any byte set <=> a code above 7; codes 5..7: bit 2 with bit 0 or 1
+    unsigned long long over = 0, zero = 0;   // bits 3..7 of any byte set <=> a code above 7; codes 5..7: bit 2 with bit 0 or 1
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
         const unsigned long long b = ((const unsigned long long *)bases)[i], q = ((const unsigned long long *)quals)[i];
         over |= (b & 0xF8F8F8F8F8F8F8F8ull) | (b & 0x0404040404040404ull & (((b | (b >> 1)) & 0x0101010101010101ull) << 2));
+        zero |= (q - 0x0101010101010101ull) & ~q & 0x8080808080808080ull;   // bit 7 of a quality byte that is 0
         uint4 o;
         o.x = (uint32_t)((b & 0xFF) | ((q & 0xFF) << 8) | (((b >> 8) & 0xFF) << 16) | (((q >> 8) & 0xFF) << 24));
         o.y = (uint32_t)(((b >> 16) & 0xFF) | (((q >> 16) & 0xFF) << 8) | (((b >> 24) & 0xFF) << 16) | (((q >> 24) & 0xFF) << 24));
@@ -3646,8 +3859,9 @@ __global__ void __launch_bounds__(256) k_pack_bq(const uint8_t *bases, const uin
         o.w = (uint32_t)(((b >> 48) & 0xFF) | (((q >> 48) & 0xFF) << 8) | (((b >> 56) & 0xFF) << 16) | (((q >> 56) & 0xFF) << 24));
         ((uint4 *)bq)[i] = o;
     }
-    if (blockIdx.x == 0) for (int64_t i = (n8 << 3) + threadIdx.x; i < n; i += blockDim.x) { bq[i] = (uint16_t)(bases[i] | (quals[i] << 8)); over |= (bases[i] > 4); }   // the last n % 8
+    if (blockIdx.x == 0) for (int64_t i = (n8 << 3) + threadIdx.x; i < n; i += blockDim.x) { bq[i] = (uint16_t)(bases[i] | (quals[i] << 8)); over |= (bases[i] > 4); zero |= (quals[i] == 0); }   // the last n % 8
     if (bad && __any(over != 0) && (threadIdx.x & 63) == 0) *bad = 2;
+    if (bad && __any(zero != 0) && (threadIdx.x & 63) == 0) bad[1] = 1;   // (UvcPrepIn::zero_qual)
 }
 extern "C" void uvc_launch_pack_bq(const uint8_t *bases, const uint8_t *quals, uint16_t *bq, int64_t n, int32_t *bad, hipStream_t s) {
     if (n <= 0) return;
@@ -3747,6 +3961,24 @@ static void print_forms(const AccForms &F) {
             !F.duplex ? "none" : F.digest ? "digest" : "generic",
             !F.n_gen ? "none" : F.proton ? "all" : "sweep");
 }
+// The P1 pass of the forms that are not split: k_prep_scan, or k_prep_fast<false> with UVCGPU_PREP=window (read on every accumulate, like
+// UVCGPU_SPLIT; tests compare the two).
+static bool prep_scan_wanted() {
+    const char *e = getenv("UVCGPU_PREP");
+    return !(e && !strcmp(e, "window"));
+}
+// k_prep_scan splits (int)(baq(p) - baq(apos) + 1) into two 32-bit differences against the BAQ value at the tile's first position; that is
+// exact while no difference of two BAQ values at most one entry plus one tile apart reaches 2^30.  A position adds at most M / 10 to the
+// prefix sums (k_rtr_tracks: the larger of the two increments, in its int arithmetic), so the bound holds for every read when
+// (longest entry + PSCAN_TILE) * M / 10 + 2 < 2^30; indel_nonSTR_phred_per_base or indel_str_phred_per_region in the millions fail it and
+// keep the window form.  (P is the handle's own parameter block, the one its BAQ prefix sums were made from: uvcgpu_region_accumulate and
+// the region tracks of create / reset both pass &r->P.)
+static bool prep_scan_exact(const RegionDev *R, const UvcParams *P) {
+    const long long m_str = llabs((long long)(int32_t)((uint32_t)P->indel_str_phred_per_region * 10u)) + 1;
+    const long long m_non = llabs((long long)(int32_t)((uint32_t)P->indel_nonSTR_phred_per_base * 10u));
+    const long long m = (m_str > m_non ? m_str : m_non);
+    return ((long long)R->max_p2_span + PSCAN_TILE) * m / 10 + 2 < (1LL << 30);
+}
 // one pass of k_p2_fast over the P2 work list: LINK_M (DO_L) or the base symbols (DO_B), in the form F names
 template <bool DO_L, bool DO_B>
 static void launch_p2_fast(const char *kname, const AccForms &F, const RegionDev *R, const UvcParams *P, unsigned nwin, UvcProf *prof, hipStream_t s) {
@@ -3777,7 +4009,10 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
         if (side && R->n_complex) { hipEventRecord(e_fork, s); hipStreamWaitEvent(s2, e_fork, 0); }
         if (R->n_complex) TIMED2(prof, "k_prep_slow", hipLaunchKernelGGL(k_prep_slow, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
         if (side && R->n_complex) hipEventRecord(e_join, s2);
+        const bool scan = !F.split_windows && prep_scan_wanted() && prep_scan_exact(R, P);
+        if (getenv("UVCGPU_TIMING")) fprintf(stderr, "[uvcgpu accumulate] prep kernel %s\n", F.split_windows ? "k_prep_fast<true>" : scan ? "k_prep_scan" : "k_prep_fast<false>");
         if (F.split_windows) TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
+        else if (scan) TIMED(prof, "k_prep_scan", hipLaunchKernelGGL(k_prep_scan, dim3(nblk(R->npos, PSCAN_TILE)), dim3(256), 0, s, *R, *P));
         else TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<false>, dim3(nwin), dim3(256), 0, s, *R, *P));
         if (side && R->n_complex) hipStreamWaitEvent(s, e_join, 0);
     }

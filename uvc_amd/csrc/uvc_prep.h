@@ -10,6 +10,8 @@ struct UvcPrepIn {
     const uint16_t *flag; const uint8_t *mapq, *fam_strand, *fam_dflag;
     const int64_t *seq_off, *cigar_off;
     const uint32_t *cigars;
+    const uint8_t *quals;        // [n_bases]
+    const int32_t *zero_qual;    // device word: some quality byte of the column is 0 (set by the kernels that pack base | quality); NULL: not known
 };
 // device arrays (owned by the allocator's context) and host-side totals
 struct UvcPrepOut {

@@ -299,7 +299,20 @@ __global__ void __launch_bounds__(256) k_build_frags(UvcPrepIn in, UvcParams P, 
     r.end = pmin(r.end, rend);
     const bool amplicon_gated = (((r.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag))) && !(P.tn_is_paired && (0x1 & P.primer_flag)));
     r.stat_kind = (all_simple && (a1 - a0) <= 2 && !amplicon_gated) ? 0 : 1;
-    sweep_flag[f] = r.stat_kind; frag_beg[f] = r.beg; frag_strand[f] = r.strand;
+    // A base whose value (quality + bq_phred_added_misma; on IonTorrent the smaller of two qualities + the smaller addend) is 0 or less adds
+    // nothing to the fragment's consensus, and a position where nothing adds up is not covered by the fragment (main.hpp:2658-2726).  The closed
+    // forms of k_fragstat_fast / k_frag_sums / k_frag count every aligned position, so a fragment with such a base takes the per-position
+    // kernels (k_fragstat_sweep, k_frag_generic) at every one of its positions: stat_kind 2.  The qualities are only looked at when the column has a byte that low.
+    if (in.quals) {
+        const int zthr = -((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) ? pmin(P.bq_phred_added_misma, P.bq_phred_added_indel) : P.bq_phred_added_misma);
+        if (zthr > 0 || (zthr == 0 && (!in.zero_qual || *in.zero_qual))) {
+            for (int k = a0; k < a1 && r.stat_kind != 2; k++) {
+                const uint8_t *q = in.quals + in.seq_off[k];
+                for (int j = 0; j < in.l_qseq[k]; j++) if ((int)q[j] <= zthr) { r.stat_kind = 2; break; }
+            }
+        }
+    }
+    sweep_flag[f] = (r.stat_kind != 0); frag_beg[f] = r.beg; frag_strand[f] = r.strand;
     frags[f] = r;
     w_span = pmax(w_span, r.end - r.beg); w_s0 += (r.strand == 0);
     }
@@ -470,25 +483,30 @@ __global__ void __launch_bounds__(256) k_pack_bq4_reads(const uint8_t *b4, int64
                 __builtin_memcpy(&w, b4 + bo + (k >> 1), 4); __builtin_memcpy(&q, quals + so + k, 8);
                 unpack8(w, q, bb, o);
                 __builtin_memcpy(bases + so + k, &bb, 8); __builtin_memcpy(bq + so + k, &o, 16);
+                if ((q - 0x0101010101010101ull) & ~q & 0x8080808080808080ull) bad[1] = 1;   // a quality byte of 0 (see UvcPrepIn::zero_qual)
             } else {
                 for (int k2 = k; k2 < lq; k2++) {
                     const unsigned byte = b4[bo + (k2 >> 1)];
                     const unsigned b0 = nt16_int((k2 & 1) ? (byte & 15) : (byte >> 4));
                     bases[so + k2] = (uint8_t)b0; bq[so + k2] = (uint16_t)(b0 | (quals[so + k2] << 8));
+                    if (quals[so + k2] == 0) bad[1] = 1;
                 }
             }
         }
     }
 }
 // Dense form (every read has an even length, so base g is nibble g of the packed column): eight bases per thread, wide loads and stores
-__global__ void __launch_bounds__(256) k_pack_bq4_dense(const uint32_t *b4, const unsigned long long *quals, int64_t n8, unsigned long long *bases, uint4 *bq) {
+__global__ void __launch_bounds__(256) k_pack_bq4_dense(const uint32_t *b4, const unsigned long long *quals, int64_t n8, unsigned long long *bases, uint4 *bq, int32_t *bad) {
+    unsigned long long zero = 0;   // bit 7 of a quality byte that is 0
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t w = b4[i]; const unsigned long long q = quals[i];
         unsigned long long bb; uint4 o;
         unpack8(w, q, bb, o);
         bases[i] = bb;
         bq[i] = o;
+        zero |= (q - 0x0101010101010101ull) & ~q & 0x8080808080808080ull;
     }
+    if (bad && __any(zero != 0) && (threadIdx.x & 63) == 0) bad[1] = 1;   // (see UvcPrepIn::zero_qual)
 }
 // the dense form is only right when no read has an odd length: checked where the lengths are
 __global__ void __launch_bounds__(256) k_any_odd(const int32_t *l_qseq, int64_t n, int32_t *bad) {
@@ -518,7 +536,7 @@ extern "C" int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, i
         if (dense_form) {
             hipLaunchKernelGGL(k_any_odd, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s, l_qseq, n, bad);
             hipLaunchKernelGGL(k_pack_bq4_dense, dim3((unsigned)std::min<int64_t>((n_bases / 8 + 255) / 256 + 1, 16384)), dim3(256), 0, s, (const uint32_t *)bases4, (const unsigned long long *)quals, n_bases / 8,
-                               (unsigned long long *)bases_out, (uint4 *)bq_out);
+                               (unsigned long long *)bases_out, (uint4 *)bq_out, bad);
         } else {
             hipLaunchKernelGGL(k_pack_bq4_reads, dim3((unsigned)std::min<int64_t>((n + 15) / 16, 65536)), dim3(256), 0, s, bases4, n_b4, b4_off, seq_off_out ? seq_off_out : seq_off_in, l_qseq, quals, n, n_bases, bases_out, bq_out, bad);
         }
