@@ -10,6 +10,7 @@ import math
 import numpy as np
 
 from p2_restatement import read_events
+from segbias_restatement import cdiv
 
 NSYM, NUM_BUCKETS, SQR_QUAL_DIV = 14, 16, 32
 BASE_A, BASE_C, BASE_G, BASE_T, BASE_N, BASE_NN, LINK_M, LINK_D3P, LINK_D2, LINK_D1, LINK_I3P, LINK_I2, LINK_I1, LINK_NN = range(14)
@@ -90,7 +91,7 @@ def fragment_pass(reads, P, rtr, indelphred, baq, codes, prep, thres, seg, bqsum
 
     def avgBQ(x, s):
         denom = int(seg["aDPff"][s][x] + seg["aDPfr"][s][x] + seg["aDPrf"][s][x] + seg["aDPrr"][s][x])
-        return int(bqsum[s][x]) // max(1, denom)
+        return cdiv(int(bqsum[s][x]), max(1, denom))     # C division: toward zero, and the sum is negative where bq_phred_added_misma outweighs the qualities
     i = 0
     while i < n:
         j = i

@@ -276,6 +276,28 @@ def test_c_abi_param_set_refuses_and_names_the_row():
     assert chk(C.byref(p)) == einval and lib.last_error() == "UvcParams::struct_size mismatch"
 
 
+def test_params_check_bounds_the_quality_addends():
+    """bq_phred_added_misma / _indel within -256 .. 3840 (the kernels' value tables and 16-bit fields), and no negative addend beside a
+    bias_thres_PFBQ1 / 2 of 0 -- the IonTorrent default -- where the reference divides by zero for a value below 0."""
+    lib = region.gpu_lib()
+    chk = lib.dll.uvcgpu_params_check
+    chk.restype, chk.argtypes = C.c_int, [C.POINTER(_ffi.UvcParams)]
+    unsupported = _ffi.ENUMS["UVCGPU_EUNSUPPORTED"]
+    for plat, ok_negative in ((1, True), (2, False)):
+        for name in ("bq_phred_added_misma", "bq_phred_added_indel"):
+            p = region.default_params(lib, platform=plat)
+            assert chk(C.byref(p)) == 0 and (p.bias_thres_PFBQ1 == 0) == (plat == 2)
+            setattr(p, name, 3840); assert chk(C.byref(p)) == 0
+            setattr(p, name, 3841); assert chk(C.byref(p)) == unsupported and lib.last_error().endswith("above 3840")
+            setattr(p, name, -1); assert (chk(C.byref(p)) == 0) == ok_negative
+            if not ok_negative:
+                assert lib.last_error().endswith("bias_thres_PFBQ1 or bias_thres_PFBQ2 of 0")
+                p.bias_thres_PFBQ1 = 25; assert chk(C.byref(p)) == unsupported          # bias_thres_PFBQ2 is still 0
+                p.bias_thres_PFBQ2 = 30
+            setattr(p, name, -256); assert chk(C.byref(p)) == 0
+            setattr(p, name, -257); assert chk(C.byref(p)) == unsupported and lib.last_error().endswith("below -256")
+
+
 def test_apply_platform_ex_matches_apply_platform():
     """AUTO is uvcgpu_params_apply_platform; the Python restatement region.apply_platform agrees with both"""
     lib = region.gpu_lib()

@@ -14,7 +14,13 @@ pytestmark = pytest.mark.gpu
 M, I, D, N, S, H = 0, 1, 2, 3, 4, 5
 
 
-def weird_region(seed, n_frag=260, ref_len=700, beg=1_000_000, umi=False, lengths=(1, 2, 5, 30, 60, 90, 120, 150)):
+QUALS = (2, 8, 15, 20, 21, 22, 30, 37, 41)
+# every class of quality byte: 0 (a base without value), Illumina's Q2, the printable maximum 93, 0x7F / 0x80 either side of the sign bit of a byte, 0xFF
+WIDE_QUALS = (0, 2, 8, 15, 20, 30, 37, 41, 93, 127, 128, 200, 255)
+
+
+def weird_region(seed, n_frag=260, ref_len=700, beg=1_000_000, umi=False, lengths=(1, 2, 5, 30, 60, 90, 120, 150), quals_from=QUALS):
+    """quals_from: the values the qualities are drawn from (the random stream of the default list is that of the stored chain fixtures)."""
     rng = np.random.default_rng(seed)
     ref = rng.integers(0, 4, ref_len)
     for _ in range(6):                                   # homopolymers / STRs so that the InDel context code is exercised
@@ -89,7 +95,7 @@ def weird_region(seed, n_frag=260, ref_len=700, beg=1_000_000, umi=False, length
             cols["l_qseq"].append(qlen); cols["seq_off"].append(len(bases)); cols["cigar_off"].append(len(cigars)); cols["n_cigar"].append(len(ops))
             cols["frag_id"].append(frag); cols["fam_id"].append(fam); cols["fam_strand"].append(strand)
             bases += [int(b) for b in q]
-            quals += list(rng.choice([2, 8, 15, 20, 21, 22, 30, 37, 41], qlen))
+            quals += list(rng.choice(list(quals_from), qlen))
             cigars += [(l << 4) | o for o, l in ops]
         frag += 1
     dt = dict(pos=np.int32, mpos=np.int32, isize=np.int32, flag=np.uint16, mapq=np.uint8, nm=np.int32, l_qseq=np.int32, seq_off=np.int64, cigar_off=np.int64,

@@ -56,6 +56,22 @@ def test_rows_and_alleles_of_one_insertion_site(oracle_lib):
 
 
 def test_allele_rows_against_the_independent_restatements(oracle_lib):
+    assert allele_rows_check(oracle_lib, ((71, True, 1), (72, False, 1), (73, True, 2))) > 1000
+
+
+def test_allele_rows_on_the_quality_byte_classes(oracle_lib):
+    """Qualities of 0 and of 0x7F .. 0xFF, bq_phred_added_misma = -20, and IonTorrent with bq_phred_added_indel < bq_phred_added_misma < 0
+    (tests/byte_classes.py); each arm has (fragment, position) pairs whose consensus counts
+    add up to 0, counted from the restated walk: 649, 4368 and 1199; the two arms with a negative addend hold 5277 and 2338 aligned bases of a value below 0."""
+    from byte_classes import IONTORRENT_NEGATIVE, NEGATIVE_MISMA
+    from test_gpu_fuzz import QUALS, WIDE_QUALS
+    cells = []
+    assert allele_rows_check(oracle_lib, ((74, True, 1, WIDE_QUALS, None), (75, True, 1, QUALS, NEGATIVE_MISMA), (76, True, 2, QUALS, IONTORRENT_NEGATIVE)), cells) > 1000
+    print("zero-value cells, values below 0:", cells)
+    assert min(c for c, _ in cells) > 0 and [below > 0 for _, below in cells] == [False, True, True], cells
+
+
+def allele_rows_check(oracle_lib, arms, cells=None):
     """Every row fill_by_indel_info reads (fragment, family, cDP2 and duplex support of every allele, per strand) on fuzzed reads: the oracle's
     tables against the allele-keyed maps of the restated fragment and family passes (tests/p3_restatement.py, tests/p45_restatement.py,
     tests/indel_alleles_restatement.py), chained behind the other restatements -- no oracle value enters."""
@@ -66,13 +82,15 @@ def test_allele_rows_against_the_independent_restatements(oracle_lib):
     from p3_restatement import fragment_pass
     from p45_restatement import family_passes
     from indel_alleles_restatement import allele_rows
+    from byte_classes import set_params, zero_value_cells
     from util import run_region
     spec = importlib.util.spec_from_file_location("fz_alleles", os.path.join(os.path.dirname(__file__), "test_gpu_fuzz.py"))
     fz = importlib.util.module_from_spec(spec); spec.loader.exec_module(fz)
     n_rows = 0
-    for seed, umi, platform in ((71, True, 1), (72, False, 1), (73, True, 2)):
-        reads = fz.weird_region(seed, n_frag=150, ref_len=420, umi=umi)
-        P = region.default_params(oracle_lib, platform=platform)
+    for seed, umi, platform, *more in arms:
+        quals_from, values = more if more else (fz.QUALS, None)
+        reads = fz.weird_region(seed, n_frag=150, ref_len=420, umi=umi, quals_from=quals_from)
+        P = set_params(region.default_params(oracle_lib, platform=platform), values)
         R = run_region(oracle_lib, reads, params=P)
         rtr, baq = python_tracks(reads["refseq"], smax=P.indel_str_repeatsize_max, vmax=P.indel_vntr_repeatsize_max, bq_max=P.indel_BQ_max,
                                  slip_rate=P.indel_polymerase_slip_rate, del_to_ins=P.indel_del_to_ins_err_ratio, polymerase_size=P.indel_polymerase_size,
@@ -94,4 +112,6 @@ def test_allele_rows_against_the_independent_restatements(oracle_lib):
         assert got == want, sorted(set(got.items()) ^ set(want.items()))[:6]
         n_rows += len(want)
         R.close()
-    assert n_rows > 1000
+        if cells is not None:
+            cells.append(zero_value_cells(reads, P, rtr, ip, baq[0], codes, prep, thres, proton))
+    return n_rows

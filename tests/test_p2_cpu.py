@@ -15,6 +15,7 @@ from rtr_cases import python_tracks
 from prep_restatement import prep_sets, thres_sets
 from p2_restatement import update_by_aln
 from segbias_restatement import SEG_FIELDS
+from byte_classes import IONTORRENT_NEGATIVE, NEGATIVE_MISMA, set_params, zero_value_cells
 from util import run_region
 
 _spec = importlib.util.spec_from_file_location("fz_p2", os.path.join(os.path.dirname(__file__), "test_gpu_fuzz.py"))
@@ -25,8 +26,21 @@ SEG32 = SEG_FIELDS[:30]; SEG64 = SEG_FIELDS[30:34]; VQ4 = SEG_FIELDS[34:38]
 
 @pytest.mark.parametrize("seed,umi,platform,normal", [(21, False, 1, 0), (22, True, 1, 0), (23, False, 2, 0), (24, False, 1, 1), (25, True, 2, 0), (26, False, 1, 0)])
 def test_updateByAln_against_the_independent_restatements(seed, umi, platform, normal, oracle_lib):
-    reads = fz.weird_region(seed, n_frag=120 + 30 * (seed % 3), ref_len=420 + 30 * seed, umi=umi)
-    P = region.default_params(oracle_lib, platform=platform)
+    check(oracle_lib, seed, umi, platform, normal)
+
+
+@pytest.mark.parametrize("seed,umi,platform,quals_from,values", [(27, True, 1, fz.WIDE_QUALS, None), (28, False, 1, fz.QUALS, NEGATIVE_MISMA), (29, True, 2, fz.QUALS, IONTORRENT_NEGATIVE)])
+def test_updateByAln_on_the_quality_byte_classes(seed, umi, platform, quals_from, values, oracle_lib):
+    """Qualities of 0 and of 0x7F .. 0xFF, bq_phred_added_misma = -20, and IonTorrent with bq_phred_added_indel < bq_phred_added_misma < 0
+    (tests/byte_classes.py).  Each arm has (fragment, position) pairs whose consensus counts add up to 0, counted from the restated walk: 539, 4366 and 1418; the two arms with a negative addend hold 5570 and 2864 aligned bases of a value below 0."""
+    n, below = check(oracle_lib, seed, umi, platform, 0, quals_from, values)
+    print("zero-value cells:", n, "values below 0:", below)
+    assert n > 0 and (below > 0) == (values is not None)     # a negative addend gives values below 0, a quality byte alone never does
+
+
+def check(oracle_lib, seed, umi, platform, normal, quals_from=fz.QUALS, values=None):
+    reads = fz.weird_region(seed, n_frag=120 + 30 * (seed % 3), ref_len=420 + 30 * seed, umi=umi, quals_from=quals_from)
+    P = set_params(region.default_params(oracle_lib, platform=platform), values)
     P.tumor_vcf_is_provided = normal
     R = run_region(oracle_lib, reads, params=P)
     rtr, baq = python_tracks(reads["refseq"], smax=P.indel_str_repeatsize_max, vmax=P.indel_vntr_repeatsize_max, bq_max=P.indel_BQ_max,
@@ -48,3 +62,4 @@ def test_updateByAln_against_the_independent_restatements(seed, umi, platform, n
     assert not bad, bad
     assert obq[7:13].sum() > 0 and obq[5].sum() > 0 and obq[13].sum() > 0          # InDel symbols and both padded-deletion symbols occur
     R.close()
+    return zero_value_cells(reads, P, rtr, ip, baq[0], codes, prep, thres, platform == 2) if values or quals_from is not fz.QUALS else None

@@ -11,6 +11,7 @@ from uvc_amd import region
 from rtr_cases import python_tracks
 from prep_restatement import prep_sets, thres_sets
 from p45_restatement import FAM, FI32, FI64, family_passes
+from byte_classes import IONTORRENT_NEGATIVE, NEGATIVE_MISMA, set_params, zero_value_cells
 from util import run_region
 
 _spec = importlib.util.spec_from_file_location("fz_p45", os.path.join(os.path.dirname(__file__), "test_gpu_fuzz.py"))
@@ -19,8 +20,21 @@ fz = importlib.util.module_from_spec(_spec); _spec.loader.exec_module(fz)
 
 @pytest.mark.parametrize("seed,umi,platform,normal", [(41, True, 1, 0), (42, False, 1, 0), (43, True, 2, 0), (44, True, 1, 1), (45, True, 1, 0)])
 def test_family_passes_against_the_independent_restatements(seed, umi, platform, normal, oracle_lib):
-    reads = fz.weird_region(seed, n_frag=100 + 25 * (seed % 3), ref_len=380 + 30 * (seed % 5), umi=umi)
-    P = region.default_params(oracle_lib, platform=platform)
+    check(oracle_lib, seed, umi, platform, normal)
+
+
+@pytest.mark.parametrize("seed,umi,platform,quals_from,values", [(46, True, 1, fz.WIDE_QUALS, None), (47, True, 1, fz.QUALS, NEGATIVE_MISMA), (48, True, 2, fz.QUALS, IONTORRENT_NEGATIVE)])
+def test_family_passes_on_the_quality_byte_classes(seed, umi, platform, quals_from, values, oracle_lib):
+    """Qualities of 0 and of 0x7F .. 0xFF, bq_phred_added_misma = -20, and IonTorrent with bq_phred_added_indel < bq_phred_added_misma < 0
+    (tests/byte_classes.py).  Each arm has (fragment, position) pairs whose consensus counts add up to 0, counted from the restated walk: 520, 4254 and 904; the two arms with a negative addend hold 5031 and 1621 aligned bases of a value below 0."""
+    n, below = check(oracle_lib, seed, umi, platform, 0, quals_from, values)
+    print("zero-value cells:", n, "values below 0:", below)
+    assert n > 0 and (below > 0) == (values is not None)     # a negative addend gives values below 0, a quality byte alone never does
+
+
+def check(oracle_lib, seed, umi, platform, normal, quals_from=fz.QUALS, values=None):
+    reads = fz.weird_region(seed, n_frag=100 + 25 * (seed % 3), ref_len=380 + 30 * (seed % 5), umi=umi, quals_from=quals_from)
+    P = set_params(region.default_params(oracle_lib, platform=platform), values)
     P.tumor_vcf_is_provided = normal
     R = run_region(oracle_lib, reads, params=P)
     rtr, baq = python_tracks(reads["refseq"], smax=P.indel_str_repeatsize_max, vmax=P.indel_vntr_repeatsize_max, bq_max=P.indel_BQ_max,
@@ -46,3 +60,4 @@ def test_family_passes_against_the_independent_restatements(seed, umi, platform,
     assert not bad, bad
     assert of[:, 0].sum() > 0 and (not umi or (of[:, 2].sum() > 0 and od.sum() > 0 and o32[12].sum() > 0))
     R.close()
+    return zero_value_cells(reads, P, rtr, ip, baq[0], codes, prep, thres, platform == 2) if values or quals_from is not fz.QUALS else None

@@ -12,6 +12,7 @@ import pytest
 from uvc_amd import region
 from rtr_cases import python_tracks
 from prep_restatement import PREP32, PREP64, THRES, prep_sets, thres_sets
+from byte_classes import IONTORRENT_NEGATIVE, NEGATIVE_MISMA, set_params, zero_value_cells
 from util import run_region
 
 _spec = importlib.util.spec_from_file_location("fz_prep", os.path.join(os.path.dirname(__file__), "test_gpu_fuzz.py"))
@@ -20,8 +21,21 @@ fz = importlib.util.module_from_spec(_spec); _spec.loader.exec_module(fz)
 
 @pytest.mark.parametrize("seed,umi,platform,normal", [(11, False, 1, 0), (12, True, 1, 0), (13, False, 2, 0), (14, False, 1, 1), (15, True, 2, 1), (16, False, 1, 0), (17, True, 1, 0), (18, False, 2, 0)])
 def test_prep_and_thresholds_against_the_independent_restatement(seed, umi, platform, normal, oracle_lib):
-    reads = fz.weird_region(seed, n_frag=150 + 40 * (seed % 4), ref_len=500 + 40 * seed, umi=umi)
-    P = region.default_params(oracle_lib, platform=platform)
+    check(oracle_lib, seed, umi, platform, normal)
+
+
+@pytest.mark.parametrize("seed,umi,platform,quals_from,values", [(19, True, 1, fz.WIDE_QUALS, None), (20, False, 1, fz.QUALS, NEGATIVE_MISMA), (22, True, 2, fz.QUALS, IONTORRENT_NEGATIVE)])
+def test_prep_on_the_quality_byte_classes(seed, umi, platform, quals_from, values, oracle_lib):
+    """Qualities of 0 and of 0x7F .. 0xFF, bq_phred_added_misma = -20, and IonTorrent with bq_phred_added_indel < bq_phred_added_misma < 0
+    (tests/byte_classes.py).  Each arm has (fragment, position) pairs whose consensus counts add up to 0, counted from the restated walk: 1173, 3721 and 1690; the two arms with a negative addend hold 4477 and 3258 aligned bases of a value below 0."""
+    n, below = check(oracle_lib, seed, umi, platform, 0, quals_from, values)
+    print("zero-value cells:", n, "values below 0:", below)
+    assert n > 0 and (below > 0) == (values is not None)     # a negative addend gives values below 0, a quality byte alone never does
+
+
+def check(oracle_lib, seed, umi, platform, normal, quals_from=fz.QUALS, values=None):
+    reads = fz.weird_region(seed, n_frag=150 + 40 * (seed % 4), ref_len=500 + 40 * seed, umi=umi, quals_from=quals_from)
+    P = set_params(region.default_params(oracle_lib, platform=platform), values)
     P.tumor_vcf_is_provided = normal                 # the normal sample of a T/N pair takes the ...N... threshold percentages
     R = run_region(oracle_lib, reads, params=P)
     npos = reads["end"] - reads["beg"] + 1
@@ -47,3 +61,4 @@ def test_prep_and_thresholds_against_the_independent_restatement(seed, umi, plat
     assert np.array_equal(R.fetch("RTR")[3].astype(np.int64), ip), np.nonzero(R.fetch("RTR")[3] != ip)[0][:10]
     assert (ip != rtr[3]).any()                      # the edit happened somewhere
     R.close()
+    return zero_value_cells(reads, P, rtr, ip, baq[0], codes[:-1], want, t, platform == 2) if values or quals_from is not fz.QUALS else None

@@ -88,7 +88,7 @@ static_assert(sizeof(FsRec) == 64, "k_fam_p4d fetches a unit record as four 16-b
 
 // One P2 update of an InDel read: "add value `val` of symbol `sym` at position `epos` and run dealwith_segbias with these
 // arguments".  The sequential CIGAR walk (k_p2_slow<true>) only produces items; k_p2_items applies them in parallel.
-struct Item { int32_t epos; uint8_t sym, flags /* bit0 isGap, bits 1..4 cigar op */; uint16_t val; uint16_t dist, indel_len; int32_t pad2; };
+struct Item { int32_t epos; uint8_t sym, flags /* bit0 isGap, bits 1..4 cigar op */; uint16_t pad1_; uint16_t dist, indel_len; int32_t val /* signed: a negative bq_phred_added_* gives values below 0 */; };
 static_assert(sizeof(Item) == 16, "Item");
 
 // A base of a simple alignment that differs from the reference: its P2 update goes to a non-dense symbol, so k_p2_fast

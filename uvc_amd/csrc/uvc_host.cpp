@@ -545,11 +545,28 @@ static int uvcgpu_region_correct_bq_impl(uvcgpu_region_t *r) {
     if (!r->has_reads) return fail(UVCGPU_ENOREADS, "no reads");
     uvc_launch_correct_bq(&r->R, r->P.assay_sequencing_BQ_max, r->P.assay_sequencing_BQ_inc, r->stream);
     uvc_launch_pack_bq(r->R.bases, r->R.quals, (uint16_t *)r->R.bq, r->n_bases, nullptr, r->stream);
+    // A base whose value is 0 or less sends its fragment to the per-position kernels (FragRec::stat_kind 2, k_build_frags).  The penalties keep
+    // a quality at 1 or above, so the correction makes a new quality of 0 only with a negative increment or a cap of 0 or less; where a negative
+    // bq_phred_added_* puts the limit above 0, any lowered quality can cross it.  Then the fragments are looked at again.
+    const int zthr = uvc_prep_zero_value_qual(&r->P);
+    int32_t *d_n_joined = nullptr;   // device word: the fragments that join the sweep list
+    if (zthr > 0 || (zthr == 0 && (r->P.assay_sequencing_BQ_inc < 0 || r->P.assay_sequencing_BQ_max <= 0))) {
+        int rc = dev_alloc(r, 1, &d_n_joined, true);
+        if (rc) return rc;
+        uvc_prep_requalify(r->R.quals, r->W.seq_off, r->W.l_qseq, &r->P, r->R.n_frags, (FragRec *)r->R.frags, (int32_t *)r->R.sweep_frags, r->R.n_sweep, d_n_joined, r->stream);
+    }
     HIP_OK(hipMemsetAsync(r->R.mis_total, 0, sizeof(unsigned long long), r->stream));
     uvc_launch_prelude(&r->R, &r->W, &r->P, r->stream);
     uvc_launch_build_p2list(&r->R, r->W.fast_rank, r->d_p2[0], r->d_p2[1], r->d_p2[2], r->d_p2[3], r->stream);
     HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(r->stream));
+    if (d_n_joined) {
+        // (a blocking copy: it waits for the stream's work, and no copy into this stack slot is left running on any return path)
+        HIP_OK(hipStreamSynchronize(r->stream));
+        int32_t n_joined = 0;
+        HIP_OK(hipMemcpy(&n_joined, d_n_joined, sizeof(n_joined), hipMemcpyDeviceToHost));
+        if (getenv("UVCGPU_TIMING")) fprintf(stderr, "[uvcgpu correct_bq] fragments looked at again: %d joined the sweep list (%d)\n", n_joined, r->R.n_sweep + n_joined);
+        r->R.n_sweep += n_joined;
+    } else HIP_OK(hipStreamSynchronize(r->stream));
     r->accumulated = false;
     return 0;
 }

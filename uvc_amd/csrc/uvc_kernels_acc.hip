@@ -263,6 +263,10 @@ DEV int selm(wmask m, int v) { int r; asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=
 // counters are fixed registers in each instantiation and the loop has no branch on the read's orientation.
 // PLAIN: the region holds no amplicon-flagged family, no primer length is set and the reads are long (is_high_readlen), so the amplicon arms
 // and the microadjust arm are compiled out.
+// The tables of the PFBQ factor hold the values -256 .. 255 (a value is below 0 with a negative bq_phred_added_misma, never below the addend, which
+// uvcgpu_params_check keeps at -256 or above; above 255 the factor is 100 as at 255 while the thresholds stay below 256): one v_med3 and a constant offset.
+#define AMP_LO 256
+#define AMP_AT(bq) (imax(imin((bq), 255), -AMP_LO) + AMP_LO)
 template <bool ISRC, bool STRAND, bool PLAIN>
 DEV void segbias_simple(SegAcc &AL, SegAcc &AB, const UvcParams &P, const SegRead &r, const PosThres &T, int rpos, long long baq_p, long long baq2_p,
                         bool hasL, bool hasB, int bqL, int bqB, int xm_inc, int bm_inc, const int *amp1, const int *amp2) {
@@ -313,7 +317,7 @@ DEV void segbias_simple(SegAcc &AL, SegAcc &AB, const UvcParams &P, const SegRea
     const wmask m_okB = umask(is_normal), m_okL = m_okB | (umask(mate_ok) & m_nonb);
     const int p2 = (is_assay_UMI || !amplicon), nc = (0 == r.clip_cnt);
     auto common = [&](SegAcc &A, int bq) {
-        const int bq2 = (int)(__umul24((unsigned)bq, (unsigned)bq) / SQR_QUAL_DIV);   // bq < 2^12: the 24-bit multiply is exact and full rate
+        const int bq2 = (int)((unsigned)__mul24(bq, bq) / SQR_QUAL_DIV);   // |bq| < 2^12 (below 0 with a negative bq_phred_added_misma; uvcgpu_params_check keeps the addends within -256 .. 3840): the signed 24-bit multiply is exact and full rate
         if (isrc) { A.a1BQr += bq; A.a2BQr += bq2; } else { A.a1BQf += bq; A.a2BQf += bq2; }
         A.bq += bq;
         A.s[UVC_S_aMQs] += r.mapq;
@@ -335,7 +339,7 @@ DEV void segbias_simple(SegAcc &AL, SegAcc &AB, const UvcParams &P, const SegRea
     };
     if (hasB) {
         common(AB, bqB);
-        AB.s[UVC_S_aPF1] += amp1[imin(bqB, 255)]; AB.s[UVC_S_aPF2] += amp2[imin(bqB, 255)];   // "100 * amp / 100" == amp (main.hpp:1472-1519)
+        AB.s[UVC_S_aPF1] += amp1[AMP_AT(bqB)]; AB.s[UVC_S_aPF2] += amp2[AMP_AT(bqB)];   // "100 * amp / 100" == amp (main.hpp:1472-1519)
         AB.s[UVC_S_a2XM2] += xm_inc; AB.s[UVC_S_a2BM2] += bm_inc;
         // the base side enters the bias blocks when bq >= highBQ (tier2 then holds)
         bias(AB, false, BAL(bqB >= P.bias_thres_highBQ), m_farB, m_unaffB, BAL(r_baqB >= P.bias_thres_BAQ1), BAL(r_baqB >= P.bias_thres_BAQ2), r_baqB);
@@ -344,7 +348,7 @@ DEV void segbias_simple(SegAcc &AL, SegAcc &AB, const UvcParams &P, const SegRea
     }
     if (hasL) {
         common(AL, bqL);
-        AL.s[UVC_S_aPF1] += imin(100, amp1[imin(bqL, 255)]); AL.s[UVC_S_aPF2] += imin(100, amp2[imin(bqL, 255)]);
+        AL.s[UVC_S_aPF1] += imin(100, amp1[AMP_AT(bqL)]); AL.s[UVC_S_aPF2] += imin(100, amp2[AMP_AT(bqL)]);
         // the gap side enters when dist_to_interfering_indel (10000) >= bias_thres_interfering_indel
         bias(AL, true, umask(10000 >= P.bias_thres_interfering_indel), m_farL, m_unaffL, BAL(r_baqL >= P.bias_thres_BAQ1), BAL(r_baqL >= P.bias_thres_BAQ2), r_baqL);   // (aP1 inside does not look at `in`)
         if (isrc) { addm(AL.s[UVC_S_aLI1], m_i1lo & m_okL); addm(AL.s[UVC_S_aLI2], m_i2lo & m_okL & m_goodL); addm(AL.s[UVC_S_aLIr], m_goodL); }
@@ -1257,9 +1261,11 @@ template <bool DO_L, bool DO_B, bool PLAIN, bool SPLIT = false>
 DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *amp2, MisItem (*misq)[DO_B ? MISQ_CAP : 1], int (*red)[64] = nullptr) {
     COARSE_T(ct0)
     {
-        const int v = threadIdx.x;
-        amp1[v] = (v < P.bias_thres_PFBQ1 ? 100 * (v * v) / (P.bias_thres_PFBQ1 * P.bias_thres_PFBQ1) : 100);
-        amp2[v] = (v < P.bias_thres_PFBQ2 ? 100 * (v * v) / (P.bias_thres_PFBQ2 * P.bias_thres_PFBQ2) : 100);
+        for (int v = (int)threadIdx.x - AMP_LO; v < 256; v += 256) {   // (a threshold of 0 would divide by zero for a value below it, as the reference does: uvcgpu_params_check refuses a negative addend beside such a threshold, so that entry is never read)
+            const int d1 = P.bias_thres_PFBQ1 * P.bias_thres_PFBQ1, d2 = P.bias_thres_PFBQ2 * P.bias_thres_PFBQ2;
+            amp1[v + AMP_LO] = ((v < P.bias_thres_PFBQ1 && d1) ? 100 * (v * v) / d1 : 100);
+            amp2[v + AMP_LO] = ((v < P.bias_thres_PFBQ2 && d2) ? 100 * (v * v) / d2 : 100);
+        }
     }
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -1457,13 +1463,13 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
 }
 template <bool DO_L, bool DO_B, bool PLAIN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_p2_fast(RegionDev R, UvcParams P) {
-    __shared__ int amp1[256], amp2[256];
+    __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
     __shared__ MisItem misq[DO_B ? 4 : 1][DO_B ? MISQ_CAP : 1];
     p2_fast_body<DO_L, DO_B, PLAIN>(R, P, amp1, amp2, misq);
 }
 template <bool DO_L, bool DO_B, bool PLAIN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_p2_fast_split(RegionDev R, UvcParams P) {
-    __shared__ int amp1[256], amp2[256];
+    __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
     __shared__ MisItem misq[DO_B ? 4 : 1][DO_B ? MISQ_CAP : 1];
     __shared__ __attribute__((aligned(8))) int red[P2_RED_SLOTS][64];
     p2_fast_body<DO_L, DO_B, PLAIN, true>(R, P, amp1, amp2, misq, red);
@@ -1549,8 +1555,8 @@ __global__ void __launch_bounds__(64) k_p2_slow(RegionDev R, UvcParams P) {
     int n_items = 0;
     auto emit = [&](bool gap, int epos, int sym, int v, int bm, int op, int indel_len, int dist) {
         if (BIAS) {   // the bias update itself is applied by k_p2_items, in parallel over the items
-            Item it; it.epos = epos; it.sym = (uint8_t)sym; it.flags = (uint8_t)((gap ? 1 : 0) | (op << 1)); it.val = (uint16_t)imin(imax(v, 0), 65535);
-            it.dist = (uint16_t)imin(imax(dist, 0), 65535); it.indel_len = (uint16_t)imin(indel_len, 65535); it.pad2 = 0;
+            Item it; it.epos = epos; it.sym = (uint8_t)sym; it.flags = (uint8_t)((gap ? 1 : 0) | (op << 1)); it.val = v;
+            it.dist = (uint16_t)imin(imax(dist, 0), 65535); it.indel_len = (uint16_t)imin(indel_len, 65535); it.pad1_ = 0;
             items[n_items++] = it;
         } else if (epos >= a.pos && epos <= a.rend) table_put(R, table + (epos - a.pos), sym, v);
         else atomicExch(R.err, UVCGPU_EDEVICE);   // would leave the read's rows
@@ -2192,13 +2198,15 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
     unsigned long long mq_acgt = 0x0008000800080008ull;
     int mqN = 8, maxq_link = 8, noindel80 = 80;
     if (valid) {
-        mq_acgt = (unsigned long long)imin(maxq_at(UVC_BASE_A), 65535) | ((unsigned long long)imin(maxq_at(UVC_BASE_C), 65535) << 16)
-                | ((unsigned long long)imin(maxq_at(UVC_BASE_G), 65535) << 32) | ((unsigned long long)imin(maxq_at(UVC_BASE_T), 65535) << 48);
+        // (signed: the sum of the values, and with it the average, is below 0 where a negative bq_phred_added_misma outweighs the qualities;
+        // 8 + a quality byte + an addend that uvcgpu_params_check keeps within -256 .. 3840 fits 16 signed bits, so the clamp never acts)
+        auto h16 = [&](int sym) { return (unsigned long long)(unsigned short)imax(imin(maxq_at(sym), 32767), -32768); };
+        mq_acgt = h16(UVC_BASE_A) | (h16(UVC_BASE_C) << 16) | (h16(UVC_BASE_G) << 32) | (h16(UVC_BASE_T) << 48);
         mqN = maxq_at(UVC_BASE_N);
         maxq_link = maxq_at(UVC_LINK_M);
         if (x > 0) noindel80 = imin(80, imin(RTRP(R, UVC_RTR_indelphred, x - 1), RTRP(R, UVC_RTR_indelphred, x)));
     }
-    auto maxq_base = [&](int cs) { return cs >= UVC_BASE_N ? mqN : (int)((mq_acgt >> (16 * cs)) & 0xFFFFull); };   // cs in A..N
+    auto maxq_base = [&](int cs) { return cs >= UVC_BASE_N ? mqN : (int)(short)(mq_acgt >> (16 * cs)); };   // cs in A..N
     const int maxq_ref = maxq_base(my_ref);
     // dense accumulators of the reference symbol: [strand] x {bDP, bTA, bTB, cDP12 (== cDP21), cDP1}, bMQ.  Named structs, selected by
     // a wave-uniform branch on the strand: runtime-indexed local arrays would live in scratch memory (one VMEM round trip per update).
@@ -3867,6 +3875,7 @@ extern "C" void uvc_launch_pack_bq(const uint8_t *bases, const uint8_t *quals, u
     if (n <= 0) return;
     // the wide form needs 8- / 16-byte aligned columns (device allocations are; a caller's sub-array of set_reads_device may not be)
     const bool aligned = !(((uintptr_t)bases | (uintptr_t)quals) & 7) && !((uintptr_t)bq & 15);
+    if (getenv("UVCGPU_TIMING")) fprintf(stderr, "[uvcgpu pack_bq] %s\n", aligned ? "k_pack_bq" : "k_pack_bq1");
     if (aligned) hipLaunchKernelGGL(k_pack_bq, dim3((unsigned)std::min<int64_t>(((n >> 3) + 255) / 256 + 1, 16384)), dim3(256), 0, s, bases, quals, bq, n, bad);
     else hipLaunchKernelGGL(k_pack_bq1, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, s, bases, quals, bq, n, bad);
 }

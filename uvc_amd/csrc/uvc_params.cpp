@@ -115,5 +115,14 @@ extern "C" int uvcgpu_params_check(const UvcParams *params) {
     // the sentinels of its InDel list otherwise: a threshold above 10000 compares with those.  The kernels carry the distance in 16 bits with
     // "10000 or more" as one value, which is exact for every threshold up to 10000 (the default is 5) and wrong beyond: refused, not approximated.
     if (params->bias_thres_interfering_indel > 10000) return uvcgpu_set_error(UVCGPU_EUNSUPPORTED, "bias_thres_interfering_indel above 10000");
+    // A base's value is its quality plus bq_phred_added_misma (on IonTorrent, next to a short gap, plus the smaller of the two addends): below 0
+    // with a negative addend.  The factor tables of k_p2_fast hold the values from -256 on: refused beyond, not approximated.
+    if (params->bq_phred_added_misma < -256 || params->bq_phred_added_indel < -256) return uvcgpu_set_error(UVCGPU_EUNSUPPORTED, "bq_phred_added_misma or bq_phred_added_indel below -256");
+    // Above, a value stays below 2^12 (255 + 3840): k_p2_fast squares it with a 24-bit multiply and k_frag packs "8 + average value" into 16 signed bits.
+    if (params->bq_phred_added_misma > 3840 || params->bq_phred_added_indel > 3840) return uvcgpu_set_error(UVCGPU_EUNSUPPORTED, "bq_phred_added_misma or bq_phred_added_indel above 3840");
+    // dealwith_segbias divides by the square of bias_thres_PFBQ1 / 2 for a value below the threshold (main.hpp:1473-1474): with a threshold of 0
+    // (the IonTorrent default) and a value below 0 the reference ends in a division by zero, so there is nothing to equal.
+    if ((params->bq_phred_added_misma < 0 || params->bq_phred_added_indel < 0) && (params->bias_thres_PFBQ1 == 0 || params->bias_thres_PFBQ2 == 0))
+        return uvcgpu_set_error(UVCGPU_EUNSUPPORTED, "a negative bq_phred_added_misma or bq_phred_added_indel with bias_thres_PFBQ1 or bias_thres_PFBQ2 of 0");
     return 0;
 }

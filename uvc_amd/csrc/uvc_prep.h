@@ -29,4 +29,7 @@ struct UvcPrepOut {
 typedef void *(*UvcPrepAlloc)(void *ctx, size_t bytes, int zero);   // device memory that lives as long as the reads of the handle; NULL on failure
 extern "C" int uvc_prep_reads(const UvcPrepIn *in, const UvcParams *P, int32_t rbeg, int32_t rend, int64_t npos, UvcPrepAlloc alloc, void *ctx, hipStream_t s,
                               UvcPrepOut *out, char *errmsg, int errcap);
+// after uvcgpu_region_correct_bq: FragRec::stat_kind 2 and the sweep list for the fragments that now hold a base without value
+extern "C" int uvc_prep_zero_value_qual(const UvcParams *P);
+extern "C" void uvc_prep_requalify(const uint8_t *quals, const int64_t *seq_off, const int32_t *l_qseq, const UvcParams *P, int32_t n_frags, FragRec *frags, int32_t *sweep_frags, int32_t n_sweep, int32_t *n_joined, hipStream_t s);
 #endif

@@ -7,6 +7,7 @@
 // two small read-backs size the allocations.
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -326,6 +327,26 @@ __global__ void __launch_bounds__(256) k_build_frags(UvcPrepIn in, UvcParams P, 
         if (s0) atomicAdd(&T->n_frag_strand0, s0);
     }
 }
+// uvcgpu_region_correct_bq has rewritten the qualities: a fragment that k_build_frags left to the closed forms (stat_kind 0) or to the M-run
+// form of k_frag (stat_kind 1 with FragFast flag 0x100) may now hold a base whose value is 0 or less.  Such a fragment becomes stat_kind 2, as
+// k_build_frags would have made it, and one that was not on the sweep list joins it at the end (the list's kernels take its entries in any
+// order: one block per entry, integer atomics).  A fragment that lost its last such base keeps stat_kind 2: the per-position kernels are exact for it.
+__global__ void __launch_bounds__(256) k_requalify_frags(const uint8_t *quals, const int64_t *seq_off, const int32_t *l_qseq, int zthr, int32_t n_frags, FragRec *frags,
+                                                         int32_t *sweep_frags, int32_t n_sweep, int32_t *n_joined) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_frags) return;
+    const int kind = frags[f].stat_kind;
+    if (kind == 2) return;
+    const int a0 = frags[f].aln_beg, a1 = frags[f].aln_end;
+    bool low = false;
+    for (int k = a0; k < a1 && !low; k++) {
+        const uint8_t *q = quals + seq_off[k];
+        for (int j = 0; j < l_qseq[k]; j++) if ((int)q[j] <= zthr) { low = true; break; }
+    }
+    if (!low) return;
+    frags[f].stat_kind = 2;
+    if (kind == 0) { const int32_t w = n_sweep + atomicAdd(n_joined, 1); if (w < n_frags) sweep_frags[w] = f; }
+}
 // one thread per family-strand unit: fillTidBegEndFromAlns2 (main.hpp:675-697), the duplex partner, which kernels take it
 __global__ void __launch_bounds__(256) k_build_units(UvcPrepIn in, UvcParams P, int32_t rend, const int32_t *endpos, const int32_t *dflag_of, const int32_t *frag_first, const int32_t *fs_first_frag,
                                                      const int32_t *fam_fs, int32_t n_fs, FsRec *fss, int32_t *generic_flag, int64_t *gen_span, Stage2 *T) {
@@ -533,6 +554,7 @@ extern "C" int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, i
     }
     if (e == hipSuccess && bases4) {
         // reads back to back (offsets derived here) with 2 x bytes == bases can only be all-even lengths: nibble g is base g
+        if (getenv("UVCGPU_TIMING")) fprintf(stderr, "[uvcgpu pack_bq] %s\n", dense_form ? "k_pack_bq4_dense" : "k_pack_bq4_reads");
         if (dense_form) {
             hipLaunchKernelGGL(k_any_odd, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s, l_qseq, n, bad);
             hipLaunchKernelGGL(k_pack_bq4_dense, dim3((unsigned)std::min<int64_t>((n_bases / 8 + 255) / 256 + 1, 16384)), dim3(256), 0, s, (const uint32_t *)bases4, (const unsigned long long *)quals, n_bases / 8,
@@ -542,6 +564,15 @@ extern "C" int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, i
         }
     }
     return (int)e;
+}
+
+// The quality at or below which a base has no value (k_build_frags decides stat_kind 2 by the same number)
+extern "C" int uvc_prep_zero_value_qual(const UvcParams *P) {
+    return -((UVC_PLATFORM_IONTORRENT == P->inferred_sequencing_platform) ? std::min(P->bq_phred_added_misma, P->bq_phred_added_indel) : P->bq_phred_added_misma);
+}
+// n_sweep: the length of sweep_frags (n_frags slots); n_joined: zeroed device word that receives the number of fragments added behind it
+extern "C" void uvc_prep_requalify(const uint8_t *quals, const int64_t *seq_off, const int32_t *l_qseq, const UvcParams *P, int32_t n_frags, FragRec *frags, int32_t *sweep_frags, int32_t n_sweep, int32_t *n_joined, hipStream_t s) {
+    if (n_frags > 0) hipLaunchKernelGGL(k_requalify_frags, dim3(nblk(n_frags, 256)), dim3(256), 0, s, quals, seq_off, l_qseq, uvc_prep_zero_value_qual(P), n_frags, frags, sweep_frags, n_sweep, n_joined);
 }
 
 static inline int pos_bits_of(int64_t npos) { int b = 1; while (((int64_t)1 << b) < npos + 1) b++; return b; }
