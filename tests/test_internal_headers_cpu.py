@@ -1,4 +1,4 @@
-"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h): a source
+"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h): a source
 file that defines a function includes the header that declares it, so the compiler checks the two against each other.  A prototype or a
 boundary struct written out again in a .cpp / .hip file is checked by nobody."""
 import glob

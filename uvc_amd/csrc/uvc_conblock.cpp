@@ -6,6 +6,7 @@
 // (per base the maximum quality per base symbol), a family's block is the fold of its fragments' runs.  No per-object maps.
 #include "uvcconsensus.h"
 #include "uvc_host.h"
+#include "uvc_rules.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -35,8 +36,7 @@ void read_events(const UvcParams &P, const UvcReadSoA &R, int64_t i, int32_t fra
     const int flag = R.flag[i];
     const bool isrc = (flag & 0x10) != 0;
     const uint8_t dflag = (R.fam_dflag ? R.fam_dflag[R.fam_id[i]] : 0);
-    const bool is_assay_amplicon = ((dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag)));
-    const bool normal_filters_primers = (P.tn_is_paired && (0x1 & P.primer_flag));
+    const bool ungated = !amplicon_gated(dflag, P);   // (else the insertions outside the insert's primer-free interval are dropped)
     // the interval between the two primers of the insert (main.hpp:1872-1875)
     const int64_t lo = std::min(R.pos[i], R.mpos[i]);
     const bool single_rc = (isrc && !(flag & 0x1));
@@ -47,7 +47,7 @@ void read_events(const UvcParams &P, const UvcReadSoA &R, int64_t i, int32_t fra
     for (int c = 0; c < n_cigar; c++) {
         const int op = (int)(cig[c] & 0xF); const int32_t len = (int32_t)(cig[c] >> 4);
         if (op == 1 /* I */) {
-            if ((normal_filters_primers || !is_assay_amplicon) || (ibeg <= rpos && rpos < iend))
+            if (ungated || (ibeg <= rpos && rpos < iend))
                 ev.push_back(Event{ R.fam_id[i], (int32_t)R.fam_strand[i], UVC_CONBLOCK_INS, rpos, frag_rank, unit, len, false, R.seq_off[i] + qpos });
         } else if (op == 4 /* S */) {
             const bool first_op = (c == 0);   // "fixed right, variable left": stored from the aligned end outwards

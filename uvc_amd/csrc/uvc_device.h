@@ -10,8 +10,10 @@
 #define UVC_DEVICE_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "uvcgpu.h"
+#include "uvc_rules.h"
 
 #define NSYM UVC_NUM_SYMBOLS
 #define NBUCKETS 16          // NUM_BUCKETS, main_conversion.hpp:920
@@ -64,6 +66,8 @@ struct FastRec {
 // in FastRec::xbv: the entry is an M run of an InDel read, not a whole simple alignment.  (ext == 0 does not say so: the one M run of 2I58M
 // spans its whole alignment.)  P1 walks the same list as P2 and skips these entries: k_prep_slow has the read.
 #define FREC_M_RUN (1 << 16)
+static_assert(sizeof(FastRec) == 64, "the position-centric kernels fetch a work-list record as four 16-byte words per lane");
+#define FR_W(field) ((int)(offsetof(FastRec, field) / 4))   // the dword of a field in a record fetched as words (load_words, the scalar-cache copies of k_p2_fast)
 
 struct FragRec {
     int32_t aln_beg, aln_end;   // alignments are stored fragment-major
@@ -71,9 +75,10 @@ struct FragRec {
     int32_t fs, strand, dflag, normMQ;
     int32_t n_cov, n_near;      // b10xSeqTlen / b10xSeqTNevents, main.hpp:2747-2756 (filled by k_fragstat)
     int32_t singleton;          // 1: the only fragment of its family-strand unit and the fast P4/P5 identities apply
-    int32_t stat_kind;          // 0: n_cov/n_near from mutation events (<= 2 simple alignments, no primer gating); 1: per-fragment sweep;
-                                // 2: the same, and k_frag_generic at every position (a read of the fragment has a base of value 0: k_build_frags)
+    int32_t stat_kind;          // FRAG_STAT_*
 };
+enum { FRAG_STAT_EVENTS = 0, FRAG_STAT_SWEEP = 1,   // n_cov / n_near from mutation events (<= 2 simple alignments, no primer gating); per-fragment sweep;
+       FRAG_STAT_ZERO_VALUE = 2 };   // the same, and k_frag_generic at every position (a read of the fragment has a base of value 0 or less: k_build_frags)
 
 struct FsRec {                  // family x strand unit (alns2 of main.hpp:2869)
     int32_t frag_beg, frag_end;
@@ -100,19 +105,31 @@ struct MisItem { int32_t rank, epos, symval; };
 // plus, per alignment, the "special" positions around its InDel, which k_frag leaves to k_frag_generic.
 // The first 12 dwords of a FragFast record again, indexed by fragment number (the fragments of a family-strand unit are consecutive):
 // k_fam_p4d reaches the records of a unit without the frag_rank indirection.
-struct FragUnit { int32_t v[12]; };
-// What a plain fragment (<= 2 simple alignments, flags & 0x301 == 0) adds to LINK_M and to "some base" at a position does not depend on the
+struct FragUnit { int32_t beg, end, fi, flags, pos0, rend0, pos1, rend1, qb0, qb1, nogap0, nogap1; };
+// What a plain fragment (<= 2 simple alignments, no flag of FF_NOT_IN_SUMS) adds to LINK_M and to "some base" at a position does not depend on the
 // position's bases: a count by micro_nogap_penal class (1..5) for the bucket histogram and sums of per-fragment constants.  k_frag_sums builds
 // them as interval sums (O(1) per fragment and plane), k_frag reads them back per position instead of adding them per (fragment, position).
 enum { UVC_FSUM_LCNT = 0 /* .. 4: LINK_M by class */, UVC_FSUM_LTA = 5, UVC_FSUM_LTB, UVC_FSUM_LSING, UVC_FSUM_LMQ, UVC_FSUM_BDP, UVC_FSUM_BTA, UVC_FSUM_BTB, UVC_FSUM_BMQ, UVC_FSUM_N };
 struct FragFast {
-    int32_t beg, end, fi, flags;        // flags: bit0 generic path only, bit1 strand, bit2 singleton, bits 3..6 number of alignments, bit8 has runs B / special ranges, bit9 a micro_nogap_penal outside 1..5 (k_frag adds its LINK_M per position)
+    int32_t beg, end, fi, flags;        // flags: FF_*
     int32_t pos0, rend0, pos1, rend1;   // run A of alignment 0 / 1: [pos, rend)
     int32_t qb0, qb1, nogap0, nogap1;   // low word of the query offset of run A; micro_nogap_penal of the alignment
     int32_t sq, n_cov, n_near, pad_;    // sq = normMQ^2 / SQR_QUAL_DIV
     int32_t bpos0, brend0, bqb0, sp0;   // run B of alignment 0, its query offset; sp = special range (beg - fragment beg) | length << 16
     int32_t bpos1, brend1, bqb1, sp1;
 };
+enum { FF_GENERIC = 1,            // k_frag_generic takes every position of the fragment
+       FF_STRAND = 2, FF_SINGLETON = 4, FF_NALN_SHIFT = 3, FF_NALN_MASK = 0xF,   // (number of alignments: ff_naln)
+       FF_RUNS_B = 0x100,         // has runs B / special ranges: k_frag takes the M runs, k_frag_generic the positions next to the InDels
+       FF_LINK_PER_POS = 0x200,   // a micro_nogap_penal outside 1..5: k_frag adds its LINK_M per position
+       FF_NOT_REGISTER = FF_GENERIC | FF_RUNS_B,     // any of them: not on the register path of the family kernels (<= 2 simple alignments)
+       FF_FULL = FF_RUNS_B | FF_LINK_PER_POS,        // any of them: k_frag adds the per-fragment constants and LINK_M itself
+       FF_NOT_IN_SUMS = FF_GENERIC | FF_FULL };      // any of them: not in the interval sums of k_frag_sums
+// the dword of a field in a record fetched as words: the struct is the only statement of the layout
+#define FF_W(field) ((int)(offsetof(FragFast, field) / 4))
+static_assert(sizeof(FragFast) == 96, "k_frag fetches a fragment record as six 16-byte words per lane");
+static_assert(sizeof(FragUnit) == 48 && offsetof(FragFast, sq) == sizeof(FragUnit), "FragUnit is the first 12 words of FragFast");
+static_assert(FF_W(flags) == 3 && offsetof(FragUnit, flags) == offsetof(FragFast, flags) && offsetof(FragUnit, nogap1) == offsetof(FragFast, nogap1), "k_frag_sums reads flags as .w of a record's first int4");
 
 // One I / D op of an alignment as the BASE_QUALITY_MAX walk sees it (incIns / incDel, main.hpp:2101-2113, 2216): the allele-keyed
 // counters of the reference (pos2iseq2data / pos2dlen2data) are rebuilt from these by k_gap_alleles.
@@ -202,8 +219,21 @@ struct RegionDev {
 
 #define DEV __device__ __forceinline__
 
-DEV int imin(int a, int b) { return a < b ? a : b; }
-DEV int imax(int a, int b) { return a > b ? a : b; }
+DEV int ff_naln(int flags) { return (flags >> FF_NALN_SHIFT) & FF_NALN_MASK; }
+// One record per lane as 16-byte words, zeros past the end of the list (valid == false: an end of 0 never overlaps a window).  The fields of
+// record j are then broadcast by name: bcast(c[FF_W(field)], j).
+template <int WORDS>
+DEV void load_words(const void *rec, bool valid, int (&c)[WORDS]) {
+    static_assert(WORDS % 4 == 0, "whole 16-byte words");
+    if (valid) {
+        const int4 *q4 = (const int4 *)rec;
+#pragma unroll
+        for (int i = 0; i < WORDS / 4; i++) { const int4 t = q4[i]; c[4 * i] = t.x; c[4 * i + 1] = t.y; c[4 * i + 2] = t.z; c[4 * i + 3] = t.w; }
+    } else {
+#pragma unroll
+        for (int i = 0; i < WORDS; i++) c[i] = 0;
+    }
+}
 DEV int64_t lmin(int64_t a, int64_t b) { return a < b ? a : b; }
 DEV int64_t lmax(int64_t a, int64_t b) { return a > b ? a : b; }
 DEV int64_t nnminus(int64_t a, int64_t b) { return a > b ? a - b : 0; }     // non_neg_minus, common.hpp:195-200
@@ -285,24 +315,6 @@ template <int STRIDE> struct LdsCounts {
     int *p;   // &array[0][threadIdx.x]
     DEV int &operator[](int s) const { return p[s * STRIDE]; }
 };
-
-// GenericSymbol2Count::_fillConsensusCounts<TIsRefCountedOnlyOnce>, main.hpp:374-402
-template <class Arr>
-DEV void fill_consensus(const Arr &c, int &argmax, int &cmax, int &csum, int st, bool ref_once_in_link, bool ignore_padded_del) {
-    const int b = (st == UVC_BASE_SYMBOL ? UVC_BASE_A : UVC_LINK_M);
-    const int e = (st == UVC_BASE_SYMBOL ? (ignore_padded_del ? UVC_BASE_T : UVC_BASE_NN) : UVC_LINK_NN);
-    const bool once = (st == UVC_LINK_SYMBOL && ref_once_in_link);
-    argmax = e; cmax = 0; csum = 0;
-    for (int s = b; s <= e; s++) {
-        const int v = c[s];
-        if (once) {
-            if (cmax < v || (UVC_LINK_M == argmax && (0 < v))) { argmax = s; cmax = v; csum = cmax; }
-        } else {
-            if (cmax < v) { argmax = s; cmax = v; }
-            csum += v;
-        }
-    }
-}
 
 // PhredMutationTable::toPhredErrRate, main.hpp:213-262
 DEV int sscs_phred(const UvcParams &P, int con_symbol, int alt_symbol) {

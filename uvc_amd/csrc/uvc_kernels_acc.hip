@@ -35,6 +35,7 @@
 //   k_p5b            per (position, strand)  bucket -> quality for family consensus           main.hpp:3552-3591
 //   k_gap_keys/alleles/rows  per (family, InDel position)  the allele-keyed counters of the InDel symbols   main.hpp:2710-2717, 3196-3546
 // uvc_launch_accumulate at the end of the file orders them on two streams.
+// The reference rules that several of them share (pair consensus, assay predicates, ...) stand once in uvc_rules.h; record words and flag bits go by the names of uvc_device.h.
 #include "uvc_launch.h"
 #include <stdlib.h>
 #include <string.h>
@@ -61,23 +62,6 @@ DEV int bcast(int v, int j) { return __builtin_amdgcn_readlane(v, j); }   // j m
 // base | qual << 8 of read byte `idx` through a raw buffer descriptor: out-of-range indices (lanes outside the read) return 0
 DEV __amdgpu_buffer_rsrc_t bq_rsrc(const RegionDev &R) { return __builtin_amdgcn_make_buffer_rsrc((void *)R.bq, 0, (int)R.bq_bytes, 0x00020000); }
 DEV int bq_load(__amdgpu_buffer_rsrc_t rs, int idx) { return (int)__builtin_amdgcn_raw_buffer_load_b16(rs, idx << 1, 0, 0); }
-struct Chunk16 { int v[16]; };
-DEV void load_chunk16(const FastRec *base, int kk, int hi, Chunk16 &c) {   // lane <- record kk (zeros past the end: rend = 0 never overlaps)
-    if (kk < hi) {
-        const int4 *q = (const int4 *)(base + kk);
-        const int4 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
-        c.v[0] = a0.x; c.v[1] = a0.y; c.v[2] = a0.z; c.v[3] = a0.w; c.v[4] = a1.x; c.v[5] = a1.y; c.v[6] = a1.z; c.v[7] = a1.w;
-        c.v[8] = a2.x; c.v[9] = a2.y; c.v[10] = a2.z; c.v[11] = a2.w; c.v[12] = a3.x; c.v[13] = a3.y; c.v[14] = a3.z; c.v[15] = a3.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i++) c.v[i] = 0;
-    }
-}
-DEV int lower_bound_frec(const FastRec *a, int n, int key) {   // first index with a[i].pos >= key
-    int lo = 0, hi = n;
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (a[mid].pos < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 // Window index: for every 64-position window w and every begin-sorted work list, the records a wave of window w walks:
 // [first record with begin >= window begin - longest span + 1, first record with begin >= window end).  A binary search per wave and list is
 // ~20 dependent memory round trips (8 lists' bounds in k_p2_fast: an eighth of a wave's life); the table costs one load each.
@@ -100,11 +84,6 @@ __global__ void __launch_bounds__(256) k_win_index(RegionDev R, int list_beg, in
     if (list <= 6) { while (lo < hi) { const int mid = (lo + hi) >> 1; if (*(const int32_t *)(base + (size_t)mid * stride) < key) lo = mid + 1; else hi = mid; } }
     else { while (lo < hi) { const int mid = (lo + hi) >> 1; if (R.fss[R.generic_sorted[mid]].beg < key) lo = mid + 1; else hi = mid; } }
     R.win[((size_t)list * 2 + which) * R.nwin + w] = lo;
-}
-DEV int lower_bound_pos(const AlnRec *a, int n, int key) {   // first index with a[i].pos >= key
-    int lo = 0, hi = n;
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (a[mid].pos < key) lo = mid + 1; else hi = mid; }
-    return lo;
 }
 
 struct SegAcc {   // SegFormatInfoSet (main_conversion.hpp:645-691) + the VQ a1/a2 sums + bqsum of ONE symbol at ONE position
@@ -172,9 +151,9 @@ DEV void bidir(int &LP1, int &LP2, int &RP1, int &RP2, long long &LPL, long long
 template <bool isGap>
 DEV void segbias(SegAcc &A, const UvcParams &P, const SegRead &r, const PosThres &T, int rpos, long long baq_p, long long baq2_p,
                  int bq, int bm1500, int cigar_op, int indel_len, int dist_to_interfering_indel) {
-    const bool is_assay_amplicon = ((r.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag)));
-    const bool normal_filter_primers = (P.tn_is_paired && (0x1 & P.primer_flag));
-    const bool is_assay_UMI = (r.dflag & 0x1);
+    const bool amplicon = is_assay_amplicon(r.dflag, P);
+    const bool normal_filter_primers = normal_filters_primers(P);
+    const bool is_assay_UMI = (r.dflag & UVC_DFLAG_UMI);
     const int seg_l_baq1 = (int)(baq_p - r.baq_pos + 1);
     const int _seg_r_baq = (int)(r.baq_last - baq_p + 1);
     const int seg_r_baq1 = (isGap ? (int)lmin((long long)_seg_r_baq, r.baq2_last - baq2_p + 7) : _seg_r_baq);
@@ -204,8 +183,8 @@ DEV void segbias(SegAcc &A, const UvcParams &P, const SegRead &r, const PosThres
     const int thres_highBAQ = P.bias_thres_highBAQ + (isGap ? 0 : 3);
     const bool is_unaffected_by_edge = (seg_l_baq >= thres_highBAQ && seg_r_baq >= thres_highBAQ);
     const int min_dist2iend = ((r.flag & 0x1) ? imin(frag_l_nbases2, frag_r_nbases2) : (isrc ? seg_r_nbases : seg_l_nbases));
-    if (is_far_from_edge && is_unaffected_by_edge && (min_dist2iend > P.primerlen2 || !is_assay_amplicon)) A.s[UVC_S_aP1] += 1;
-    if (is_assay_UMI || !is_assay_amplicon) A.s[UVC_S_aP2] += 1;
+    if (is_far_from_edge && is_unaffected_by_edge && (min_dist2iend > P.primerlen2 || !amplicon)) A.s[UVC_S_aP1] += 1;
+    if (is_assay_UMI || !amplicon) A.s[UVC_S_aP2] += 1;
 
     int ampfact2 = 100;
     if (bq < P.bias_thres_PFBQ1) ampfact2 = 100 * (bq * bq) / (P.bias_thres_PFBQ1 * P.bias_thres_PFBQ1);
@@ -234,7 +213,7 @@ DEV void segbias(SegAcc &A, const UvcParams &P, const SegRead &r, const PosThres
     const bool mate_ok = ((0 == (r.flag & 0x8)) || (0 == (r.flag & 0x1)));
     const bool is_l_nonbiased = (mate_ok && seg_l_nbases > seg_r_nbases);
     const bool is_r_nonbiased = (mate_ok && seg_l_nbases < seg_r_nbases);
-    const bool pos_good = ((!is_assay_amplicon) || (!normal_filter_primers) || (is_far_from_edge && is_unaffected_by_edge));
+    const bool pos_good = ((!amplicon) || (!normal_filter_primers) || (is_far_from_edge && is_unaffected_by_edge));
     if (isrc) {
         const int d = frag_l_nbases2;
         if ((d >= T.t[UVC_T_aLI1t]) && (d <= T.t[UVC_T_aLI1T] || isGap) && (is_normal || (isGap && is_l_nonbiased))) A.s[UVC_S_aLI1] += 1;
@@ -270,9 +249,9 @@ DEV int selm(wmask m, int v) { int r; asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=
 template <bool ISRC, bool STRAND, bool PLAIN>
 DEV void segbias_simple(SegAcc &AL, SegAcc &AB, const UvcParams &P, const SegRead &r, const PosThres &T, int rpos, long long baq_p, long long baq2_p,
                         bool hasL, bool hasB, int bqL, int bqB, int xm_inc, int bm_inc, const int *amp1, const int *amp2) {
-    const bool amplicon = (PLAIN ? false : ((r.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag))));
-    const bool normal_filter_primers = (P.tn_is_paired && (0x1 & P.primer_flag));
-    const bool is_assay_UMI = (r.dflag & 0x1);
+    const bool amplicon = (PLAIN ? false : is_assay_amplicon(r.dflag, P));
+    const bool normal_filter_primers = normal_filters_primers(P);
+    const bool is_assay_UMI = (r.dflag & UVC_DFLAG_UMI);
     constexpr bool isrc = ISRC, strand = STRAND;
     const bool is_normal = ((r.isize != 0) || (0 == (r.flag & 0x1)));
     const bool mate_ok = ((0 == (r.flag & 0x8)) || (0 == (r.flag & 0x1)));
@@ -588,7 +567,7 @@ DEV int simple_base_value(const UvcParams &P, const AlnRec &a, int p, const uint
 // position p is a high-quality mutation of the fragment and, if so, record it once (by the first mismatching alignment).
 DEV void mut_event(const RegionDev &R, const UvcParams &P, const AlnRec &a, int p, int my_ref) {
     const FragRec &f = R.frags[a.frag];
-    if (f.stat_kind != 0) return;
+    if (f.stat_kind != FRAG_STAT_EVENTS) return;
     const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
     int m[6] = { 0, 0, 0, 0, 0, 0 };
     int first_mis = -1;
@@ -649,7 +628,7 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
         if (rend <= t0 || apos >= t1) continue;
         if (((const int *)q4)[9] & FREC_M_RUN) continue;   // FastRec::xbv: an M run of an InDel read (k_prep_slow has the read)
         const int dflag = (h1.x >> 24) & 0xFF;
-        put(PS_DP, apos, rend, 1); put(PS_PCR, apos, rend, (dflag & 0x4) ? 1 : 0); put(PS_UMI, apos, rend, (dflag & 0x1) ? 1 : 0);
+        put(PS_DP, apos, rend, 1); put(PS_PCR, apos, rend, (dflag & UVC_DFLAG_AMPLICON) ? 1 : 0); put(PS_UMI, apos, rend, (dflag & UVC_DFLAG_UMI) ? 1 : 0);
         put(PS_QLEN, apos, rend, rend - apos); put(PS_XM, apos, rend, h1.w);
         if (h1.y != 0) {
             const int fl = imin(apos, h1.z);
@@ -753,34 +732,34 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
     for (int cls = 0; cls < 4; cls++) {
     const int lo = wave_uniform(win_lo(R, 1 + cls, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 1 + cls, (int)(x0 >> 6)));
     for (int k0 = lo + (SPLIT ? 64 * (int)(threadIdx.x >> 6) : 0); k0 < hi; k0 += (SPLIT ? 256 : 64)) {
-        Chunk16 c;
-        load_chunk16(R.frec2, k0 + lane, hi, c);
+        int c[16];
+        load_words(R.frec2 + (k0 + lane), k0 + lane < hi, c);
         const int n = imin(64, hi - k0);
         // the base | quality bytes of the chunk's reads are requested four reads ahead (one load per read and lane, HBM / L2 latency each:
         // with one read of look-ahead the wave waited for most of them)
-        auto fetch = [&](int j) { return bq_load(rs, bcast(c.v[2], j) + p); };   // low word of qbase + p: exact for lanes inside the read, harmless elsewhere
+        auto fetch = [&](int j) { return bq_load(rs, bcast(c[FR_W(qb_lo)], j) + p); };   // low word of qbase + p: exact for lanes inside the read, harmless elsewhere
         auto one = [&](int j, int bqn) {
-            const int b = bqn & 0xFF, q = (bqn >> 8) & 0xFF;
-            const int apos = bcast(c.v[0], j), rend = bcast(c.v[1], j);
-            if (rend <= w0 || (bcast(c.v[9], j) & FREC_M_RUN)) return;   // behind the window, or an M run of an InDel read (k_prep_slow has the read)
+            const int b = bq_sym(bqn), q = bq_qual(bqn);
+            const int apos = bcast(c[FR_W(pos)], j), rend = bcast(c[FR_W(rend)], j);
+            if (rend <= w0 || (bcast(c[FR_W(xbv)], j) & FREC_M_RUN)) return;   // behind the window, or an M run of an InDel read (k_prep_slow has the read)
             const bool cover = (valid && p >= apos && p < rend);
             const wmask mm = BAL(cover && b != my_ref);
             if (mm) {
                 if (nq > PREPQ_CAP - 64) drain();
-                if (cover && b != my_ref) myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = make_int2(bcast(c.v[3], j), p);   // (FastRec::aln, position)
+                if (cover && b != my_ref) myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = make_int2(bcast(c[FR_W(aln)], j), p);   // (FastRec::aln, position)
                 nq += (int)__builtin_popcountll(mm);
             }
             if (cover) {   // (the counters that do not look at the base: k_prep_sums)
                 if (q >= P.bias_thres_highBQ) {
                     ldist += p - apos + 1; rdist += rend - p;
-                    lbaq += (my_baq - bcast(c.v[12], j) + 1);
-                    rbaq += (bcast(c.v[13], j) - my_baq + 1);
+                    lbaq += (my_baq - bcast(c[FR_W(baq_pos)], j) + 1);
+                    rbaq += (bcast(c[FR_W(baq_last)], j) - my_baq + 1);
                     hbq += 1;
                 }
-                const int clips = bcast(c.v[11], j);
+                const int clips = bcast(c[FR_W(clips)], j);
                 if (clips != 0) {
                     const int lclip = clips & 0xFFFF, rclip = (clips >> 16) & 0xFFFF;
-                    const int pcr_inc = (((bcast(c.v[4], j) >> 24) & 0x4) ? 1 : 0);
+                    const int pcr_inc = (((bcast(c[FR_W(fmd)], j) >> 24) & UVC_DFLAG_AMPLICON) ? 1 : 0);
                     if (p == apos && lclip > 0) clip_event(R, P, apos, 0, lclip, pcr_inc);
                     if (p == rend - 1 && rclip > 0) clip_event(R, P, rend, 1, rclip, pcr_inc);   // any index > 0 gives rpos_delta = -1
                 }
@@ -1044,7 +1023,7 @@ __global__ void __launch_bounds__(64) k_prep_slow(RegionDev R, UvcParams P) {
     const int avg_gaplen = nge / imax(1, ngo);
     const int frag_pos_L = imin(apos, a.mpos), frag_pos_R = frag_pos_L + abs(a.isize);
     const bool isrc = (a.flag & 0x10) != 0;
-    const int pcr_dp_inc = ((a.dflag & 0x4) ? 1 : 0), umi_dp_inc = ((a.dflag & 0x1) ? 1 : 0);
+    const int pcr_dp_inc = ((a.dflag & UVC_DFLAG_AMPLICON) ? 1 : 0), umi_dp_inc = ((a.dflag & UVC_DFLAG_UMI) ? 1 : 0);
     const int atd = P.indel_adj_tracklen_dist;
     const int nrtr = (int)R.npos;
     const int isize = a.isize, l_qseq = a.l_qseq;
@@ -1225,7 +1204,7 @@ DEV int simple_base_value(const UvcParams &P, const AlnRec &a, int p, const uint
             return imin(q, prev_base_phred) + P.bq_phred_added_misma;
         }
     }
-    return q + P.bq_phred_added_misma;
+    return base_value(q, P);
 }
 
 // one queued mismatching base of a simple alignment: dealwith_segbias<false> into a scratch record, flushed with atomics
@@ -1278,7 +1257,7 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     const int64_t x = x0 + lane;
     const bool valid = x < R.npos;
     const bool proton = (PLAIN ? false : (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform));
-    const bool normal_filter_primers = (P.tn_is_paired && (0x1 & P.primer_flag));
+    const bool normal_filter_primers = normal_filters_primers(P);
     const int my_ref = valid ? R.refsym[x] : 0;
     PosThres T;
     long long baq_p = 0, baq2_p = 0;
@@ -1307,30 +1286,30 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     constexpr bool ISRC = decltype(IS)::value, STRAND = decltype(ST)::value;
     const int lo = wave_uniform(win_lo(R, 1 + cls, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 1 + cls, (int)(x0 >> 6)));
     for (int k0 = lo + (SPLIT ? 64 * (int)(threadIdx.x >> 6) : 0); k0 < hi; k0 += (SPLIT ? 256 : 64)) {
-        Chunk16 c;
-        if (DO_B) load_chunk16(R.frec2, k0 + lane, hi, c);   // (the LINK-only pass reads its records through the scalar cache, below)
+        int c[16];
+        if (DO_B) load_words(R.frec2 + (k0 + lane), k0 + lane < hi, c);   // (the LINK-only pass reads its records through the scalar cache, below)
         const int n = imin(64, hi - k0);
         // (the base pass requests the base | quality bytes P2_AHEAD reads ahead: one load per read and lane at HBM / L2 latency)
-        auto fetch = [&](int j) { return bq_load(rs, bcast(c.v[2], j) + p); };   // low word of qbase + p: exact for lanes inside the read, harmless elsewhere
-        auto one = [&](auto K, int bqn) {   // K(i): dword i of the work-list record
-            const int sym = bqn & 0xFF, q = (bqn >> 8) & 0xFF;
-            const int apos = K(0), rend = K(1);
+        auto fetch = [&](int j) { return bq_load(rs, bcast(c[FR_W(qb_lo)], j) + p); };   // low word of qbase + p: exact for lanes inside the read, harmless elsewhere
+        auto one = [&](auto K, int bqn) {   // K(FR_W(field)): a field of the work-list record
+            const int sym = bq_sym(bqn), q = bq_qual(bqn);
+            const int apos = K(FR_W(pos)), rend = K(FR_W(rend));
             if (rend <= w0) return;
-            const int fmd = K(4);
-            const int ext = K(15);
+            const int fmd = K(FR_W(fmd));
+            const int ext = K(FR_W(ext));
             SegRead sr;   // [apos, rend) is what this entry covers; the bias arithmetic uses the ends of the whole alignment
             sr.pos = apos - (ext & 0xFFFF); sr.rend = rend + (int)((unsigned)ext >> 16); sr.flag = fmd & 0xFFFF; sr.mapq = (fmd >> 16) & 0xFF; sr.dflag = (fmd >> 24) & 0xFF;
-            sr.isize = K(5);
-            const int mpos = K(6);
+            sr.isize = K(FR_W(isize));
+            const int mpos = K(FR_W(mpos));
             sr.frag_pos_L = imin(sr.pos, mpos); sr.frag_pos_R = sr.frag_pos_L + abs(sr.isize);
-            sr.xm1500 = K(7);
-            const int bm4c = K(10);
+            sr.xm1500 = K(FR_W(xm1500));
+            const int bm4c = K(FR_W(bm4c));
             sr.clip_cnt = (bm4c >> 16) & 0xF;
             const int nogap = (int)(short)(bm4c & 0xFFFF);
-            sr.baq_pos = K(12); sr.baq_last = K(13); sr.baq2_last = K(14);
-            const bool is_assay_amplicon = (PLAIN ? false : ((sr.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag))));
+            sr.baq_pos = K(FR_W(baq_pos)); sr.baq_last = K(FR_W(baq_last)); sr.baq2_last = K(FR_W(baq2_last));
+            const bool amplicon = (PLAIN ? false : is_assay_amplicon(sr.dflag, P));
             bool gate = true;
-            if (is_assay_amplicon && !normal_filter_primers) {   // primer gating, main.hpp:1872-1875, 1895
+            if (amplicon && !normal_filter_primers) {   // primer gating, main.hpp:1872-1875, 1895
                 constexpr bool isrc = ISRC;
                 const int ibeg = ((sr.isize != 0) ? (sr.frag_pos_L + P.primerlen) : ((isrc && (0x0 == (0x1 & sr.flag))) ? 0 : (sr.pos + P.primerlen)));
                 const int iend = ((sr.isize != 0) ? (int)nnminus(sr.frag_pos_L + abs(sr.isize), P.primerlen) : ((isrc && (0x0 == (0x1 & sr.flag))) ? (int)nnminus(sr.rend, P.primerlen) : INT32_MAX));
@@ -1343,21 +1322,21 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
             int inc = 0, incL = 0;
             if (proton) {   // IonTorrent values need neighbouring qualities and clip lengths: take them from the full record
                 if (cover) {
-                    const AlnRec &a = R.alns[K(3)];
+                    const AlnRec &a = R.alns[K(FR_W(aln))];
                     if (DO_B) inc = simple_base_value(P, a, p, R.quals + a.qbase, true);
                     if (DO_L) incL = (p > apos ? simple_link_value(R, P, a, p, R.quals + a.qbase, true) : 0);
                 }
-            } else { inc = q + P.bq_phred_added_misma; incL = (int)nnminus(noindel80, nogap) + 1; }
+            } else { inc = base_value(q, P); incL = (int)nnminus(noindel80, nogap) + 1; }
             const wmask mm = DO_B ? BAL(cover && !hasB) : 0ull;
             if (DO_B && mm) {   // bases that differ from the reference go to the wave's queue; k_p2_mism applies them
                 if (nq > MISQ_CAP - 64) flush_queue();
-                if (cover && !hasB) { MisItem it; it.rank = K(3); it.epos = p; it.symval = sym | (inc << 8); myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = it; }
+                if (cover && !hasB) { MisItem it; it.rank = K(FR_W(aln)); it.epos = p; it.symval = sym | (inc << 8); myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = it; }
                 nq += (int)__builtin_popcountll(mm);
             }
             // a pass with one side acts on a lane iff that side has something there (one exec-mask level instead of cover, then hasL / hasB inside)
             constexpr bool ONE_SIDE = (DO_B != DO_L);
             if (!ONE_SIDE ? cover : (DO_B ? (cover & hasB) : (cover & hasL))) {
-                const int bmv = K(8), xbv = K(9);
+                const int bmv = K(FR_W(bmv)), xbv = K(FR_W(xbv));
                 const int bm_inc = (sym < 4 ? ((bmv >> (8 * sym)) & 0xFF) : (xbv & 0xFF)), xm_inc = (xbv >> 8) & 0xFF;
                 segbias_simple<ISRC, STRAND, PLAIN>(Alink, Aref, P, sr, T, p, baq_p, baq2_p, ONE_SIDE ? DO_L : hasL, ONE_SIDE ? DO_B : hasB, incL, inc, xm_inc, bm_inc, amp1, amp2);
             }
@@ -1367,16 +1346,16 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
 #if P2_AHEAD == 4
             int r2 = (2 < n ? fetch(2) : 0), r3 = (3 < n ? fetch(3) : 0);
             for (int j = 0; j < n; j += 4) {
-                { const int v = r0; if (j + 4 < n) r0 = fetch(j + 4); one([&](int i) { return bcast(c.v[i], j); }, v); }
-                if (j + 1 < n) { const int v = r1; if (j + 5 < n) r1 = fetch(j + 5); one([&](int i) { return bcast(c.v[i], j + 1); }, v); }
-                if (j + 2 < n) { const int v = r2; if (j + 6 < n) r2 = fetch(j + 6); one([&](int i) { return bcast(c.v[i], j + 2); }, v); }
-                if (j + 3 < n) { const int v = r3; if (j + 7 < n) r3 = fetch(j + 7); one([&](int i) { return bcast(c.v[i], j + 3); }, v); }
+                { const int v = r0; if (j + 4 < n) r0 = fetch(j + 4); one([&](int i) { return bcast(c[i], j); }, v); }
+                if (j + 1 < n) { const int v = r1; if (j + 5 < n) r1 = fetch(j + 5); one([&](int i) { return bcast(c[i], j + 1); }, v); }
+                if (j + 2 < n) { const int v = r2; if (j + 6 < n) r2 = fetch(j + 6); one([&](int i) { return bcast(c[i], j + 2); }, v); }
+                if (j + 3 < n) { const int v = r3; if (j + 7 < n) r3 = fetch(j + 7); one([&](int i) { return bcast(c[i], j + 3); }, v); }
             }
 #else
 #ifdef UVC_P2_BASE_VECREC
             for (int j = 0; j < n; j += 2) {
-                { const int v = r0; if (j + 2 < n) r0 = fetch(j + 2); one([&](int i) { return bcast(c.v[i], j); }, v); }
-                if (j + 1 < n) { const int v = r1; if (j + 3 < n) r1 = fetch(j + 3); one([&](int i) { return bcast(c.v[i], j + 1); }, v); }
+                { const int v = r0; if (j + 2 < n) r0 = fetch(j + 2); one([&](int i) { return bcast(c[i], j); }, v); }
+                if (j + 1 < n) { const int v = r1; if (j + 3 < n) r1 = fetch(j + 3); one([&](int i) { return bcast(c[i], j + 1); }, v); }
             }
 #else
             // the record's fields through the scalar cache as in the LINK pass; the per-lane copy of the chunk stays for the one field the byte
@@ -1546,8 +1525,8 @@ __global__ void __launch_bounds__(64) k_p2_slow(RegionDev R, UvcParams P) {
     const uint8_t *bases = R.bases + a.seq_off, *quals = R.quals + a.seq_off;
     const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
     const int off = R.beg, rend = a.rend, n_cigar = a.n_cigar;
-    const bool is_assay_amplicon = ((a.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag)));
-    const bool normal_filter_primers = (P.tn_is_paired && (0x1 & P.primer_flag));
+    const bool amplicon = is_assay_amplicon(a.dflag, P);
+    const bool normal_filter_primers = normal_filters_primers(P);
     const int addMis = P.bq_phred_added_misma, addInd = P.bq_phred_added_indel;
     Contrib *table = BIAS ? nullptr : (R.table + a.table_off);
     auto Q = [&](int q) -> int { return (int)quals[imin(imax(q, 0), a.l_qseq - 1)]; };
@@ -1603,7 +1582,7 @@ __global__ void __launch_bounds__(64) k_p2_slow(RegionDev R, UvcParams P) {
         if (op == C_MATCH || op == C_EQUAL || op == C_DIFF) {
             if (BIAS && a.kind == 2) { rpos += len; qpos += len; continue; }   // the M runs of this read are on the P2 work list of k_p2_fast
             for (int i2 = 0; i2 < len; i2++) {
-                if ((normal_filter_primers || !is_assay_amplicon) || (ibeg <= rpos && rpos < iend)) {
+                if ((normal_filter_primers || !amplicon) || (ibeg <= rpos && rpos < iend)) {
                     int dist = 10000;
                     if (BIAS && nge > 0) {
                         if (indel_rposs[ir_idx] <= rpos) ir_idx++;
@@ -1638,7 +1617,7 @@ __global__ void __launch_bounds__(64) k_p2_slow(RegionDev R, UvcParams P) {
             }
         } else if (op == C_INS) {
             bool gapped = false;
-            if ((normal_filter_primers || !is_assay_amplicon) || (ibeg <= rpos && rpos < iend)) {
+            if ((normal_filter_primers || !amplicon) || (ibeg <= rpos && rpos < iend)) {
                 const int nbases2end = imin(qpos, a.l_qseq - (qpos + len));
                 int inslen = len;
                 if (nbases2end <= 0) {
@@ -1684,7 +1663,7 @@ __global__ void __launch_bounds__(64) k_p2_slow(RegionDev R, UvcParams P) {
             qpos += len;
         } else if (op == C_DEL) {
             bool gapped = false;
-            if ((normal_filter_primers || !is_assay_amplicon) || (ibeg <= rpos && rpos < iend)) {
+            if ((normal_filter_primers || !amplicon) || (ibeg <= rpos && rpos < iend)) {
                 const int nbases2end = imin(qpos, a.l_qseq - qpos);
                 int dellen = len;
                 if (nbases2end <= 0) {
@@ -1786,8 +1765,7 @@ DEV void aln_contrib_max(const RegionDev &R, const UvcParams &P, const AlnRec &a
     // an InDel read can carry an insertion symbol at rpos == rend (CIGAR ...M I [S]): its table has one row more than the read spans
     if (p < a.pos || p > a.rend || (p == a.rend && a.kind == 0)) return;
     if (a.kind == 0) {
-        const bool is_assay_amplicon = ((a.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag)));
-        if (is_assay_amplicon && !(P.tn_is_paired && (0x1 & P.primer_flag))) {
+        if (amplicon_gated(a.dflag, P)) {
             int ibeg, iend; primer_window(P, a, ibeg, iend);
             if (!(ibeg <= p && p < iend)) return;
         }
@@ -1936,15 +1914,14 @@ __global__ void __launch_bounds__(256) k_fragstat_fast(RegionDev R, UvcParams P)
     FragFast ff;
     memset(&ff, 0, sizeof(ff));
     ff.beg = f.beg; ff.end = f.end; ff.fi = fi;
-    ff.flags = (f.stat_kind ? 1 : 0) | (f.strand << 1) | (f.singleton << 2) | ((f.aln_end - f.aln_beg) << 3);
+    ff.flags = (f.stat_kind != FRAG_STAT_EVENTS ? FF_GENERIC : 0) | (f.strand * FF_STRAND) | (f.singleton * FF_SINGLETON) | ((f.aln_end - f.aln_beg) << FF_NALN_SHIFT);
     ff.sq = (f.normMQ * f.normMQ) / SQR_QUAL_DIV;
-    if (f.stat_kind != 0) {
+    if (f.stat_kind != FRAG_STAT_EVENTS) {
         // fragments with InDel reads: k_frag can still take every position outside the InDels' neighbourhoods when the alignments
         // decompose into <= 2 M runs each (n_cov / n_near arrive from k_fragstat_sweep)
         const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
-        const bool amplicon_gated = (((f.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag))) && !(P.tn_is_paired && (0x1 & P.primer_flag)));
         const int n_aln = f.aln_end - f.aln_beg;
-        bool ok = (!proton && !amplicon_gated && n_aln <= 2 && f.end - f.beg < 65536 && f.stat_kind != 2);   // (2: a base of value 0, k_frag would count it)
+        bool ok = (!proton && !amplicon_gated(f.dflag, P) && n_aln <= 2 && f.end - f.beg < 65536 && f.stat_kind != FRAG_STAT_ZERO_VALUE);   // (a base of value 0: k_frag would count it)
         int sb, sl;
         if (ok) {
             const AlnRec &x0 = R.alns[f.aln_beg];
@@ -1958,7 +1935,7 @@ __global__ void __launch_bounds__(256) k_fragstat_fast(RegionDev R, UvcParams P)
             ff.nogap1 = x1.nogap_penal; ff.sp1 = (sb - f.beg) | (sl << 16);
             if (sb < f.beg) ok = false;
         }
-        if (ok) ff.flags = (ff.flags & ~1) | 0x100;
+        if (ok) ff.flags = (ff.flags & ~FF_GENERIC) | FF_RUNS_B;
         R.ffast[R.frag_rank[fi]] = ff; R.ffast_u[fi] = *(const FragUnit *)&ff; return;
     }
     const int nm = R.frag_nmut[fi];
@@ -1975,7 +1952,7 @@ __global__ void __launch_bounds__(256) k_fragstat_fast(RegionDev R, UvcParams P)
     }
     // k_frag_sums counts LINK_M by micro_nogap_penal class 1..5 (main.hpp:1882-1885 gives min(4, ..) + 1; below 1 only when NM is smaller than
     // the InDel lengths it should contain): anything else keeps the per-position form
-    if (ff.nogap0 < 1 || ff.nogap0 > 5 || (f.aln_end - f.aln_beg == 2 && (ff.nogap1 < 1 || ff.nogap1 > 5))) ff.flags |= 0x200;
+    if (ff.nogap0 < 1 || ff.nogap0 > 5 || (f.aln_end - f.aln_beg == 2 && (ff.nogap1 < 1 || ff.nogap1 > 5))) ff.flags |= FF_LINK_PER_POS;
     const int n_cov = (b1 - a1) + (b2 - a2);
     int n_near = 0;
     if (nm > UVC_MAXEV) {   // too many events for the closed form: the sweep kernel (overflow pass) fills n_cov / n_near of this record
@@ -2015,11 +1992,9 @@ __global__ void __launch_bounds__(256) k_frag_sums(RegionDev R, UvcParams P) {
     const int t0 = R.beg + (int)blockIdx.x * FSUM_TILE, t1 = imin(t0 + FSUM_TILE, R.beg + (int)R.npos);
     for (int i = threadIdx.x; i < UVC_FSUM_N * (FSUM_TILE + 1); i += 256) (&d[0][0])[i] = 0;
     __syncthreads();
-    const int seg_beg = R.frag_off[strand], seg_end = R.frag_off[strand + 1];
     // the fragments that can reach the tile, from the window index (k_win_index, lists 5 / 6): first with beg >= t0 - max_frag_span + 1 ..
     // first with beg >= the end of the tile's last 64-position window; two binary searches over the list by every thread (forty dependent
     // loads in front of the block's work) otherwise
-    (void)seg_beg; (void)seg_end;
     const int lo = win_lo(R, 5 + strand, (int)blockIdx.x * (FSUM_TILE / 64)), hi = win_hi(R, 5 + strand, (t1 - 1 - R.beg) >> 6);
     auto put = [&](int f, int a, int b, int v) {   // += v on [a, b) of plane f, clipped to the tile
         a = imax(a, t0); b = imin(b, t1);
@@ -2027,11 +2002,11 @@ __global__ void __launch_bounds__(256) k_frag_sums(RegionDev R, UvcParams P) {
     };
     for (int k = lo + (int)threadIdx.x; k < hi; k += 256) {
         const int4 *q4 = (const int4 *)(R.ffast + k);
-        const int4 h0 = q4[0];   // beg, end, fi, flags
-        if ((h0.w & 0x301) || h0.y <= t0) continue;
+        const int4 h0 = q4[0]; const int flags = h0.w;   // beg, end, fi, flags (FF_W(flags) == 3: static_assert beside the struct)
+        if ((flags & FF_NOT_IN_SUMS) || h0.y <= t0) continue;
         const int4 h1 = q4[1], h2 = q4[2], h3 = q4[3];   // pos0 rend0 pos1 rend1 | qb0 qb1 nogap0 nogap1 | sq n_cov n_near
-        const bool has2 = (((h0.w >> 3) & 0xF) == 2);
-        const int sing = (h0.w >> 2) & 1, sq = h3.x, n_cov = h3.y, n_near = h3.z;
+        const bool has2 = (ff_naln(flags) == 2);
+        const int sing = ((flags & FF_SINGLETON) ? 1 : 0), sq = h3.x, n_cov = h3.y, n_near = h3.z;
         // k_frag only looks at positions of [beg, end)
         const int a0 = imax(h1.x, h0.x), a1 = imin(h1.y, h0.y), b0 = (has2 ? imax(h1.z, h0.x) : 0), b1 = (has2 ? imin(h1.w, h0.y) : 0);
         {   // base side: the union of [a0, a1) and [b0, b1)
@@ -2100,7 +2075,7 @@ __global__ void __launch_bounds__(64) k_frag_generic(RegionDev R, UvcParams P, c
         const bool singleton = f.singleton;
         const int fsq = (f.normMQ * f.normMQ) / SQR_QUAL_DIV;
         const FragFast &ff = R.ffast[R.frag_rank[fi]];
-        const bool special_only = (ff.flags & 0x100) != 0;   // k_frag takes every other position of this fragment
+        const bool special_only = (ff.flags & FF_RUNS_B) != 0;   // k_frag takes every other position of this fragment
         const int sp0 = ff.sp0, sp1 = ff.sp1;
         const int n0 = (special_only ? (sp0 >> 16) : 0), n1 = (special_only ? (sp1 >> 16) : 0);
         const int p_lo = imax(f.beg, R.beg), p_hi = imin(f.end, R.end);
@@ -2207,7 +2182,6 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
         if (x > 0) noindel80 = imin(80, imin(RTRP(R, UVC_RTR_indelphred, x - 1), RTRP(R, UVC_RTR_indelphred, x)));
     }
     auto maxq_base = [&](int cs) { return cs >= UVC_BASE_N ? mqN : (int)(short)(mq_acgt >> (16 * cs)); };   // cs in A..N
-    const int maxq_ref = maxq_base(my_ref);
     // dense accumulators of the reference symbol: [strand] x {bDP, bTA, bTB, cDP12 (== cDP21), cDP1}, bMQ.  Named structs, selected by
     // a wave-uniform branch on the strand: runtime-indexed local arrays would live in scratch memory (one VMEM round trip per update).
     struct DAcc { int bDP, bTA, bTB, c12, c1; };
@@ -2251,7 +2225,7 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
     };
     // FULL: the fragment is not in k_frag_sums' interval sums, its per-fragment constants are added here.  Otherwise the sums hold them for
     // every position with a base, as if the base were the reference: a rare symbol takes its share back out of the reference's accumulators.
-    // K(i): dword i of the fragment's record.  Returns the event of a rare symbol, or 0.
+    // K(FF_W(field)): a field of the fragment's record.  Returns the event of a rare symbol, or 0.
     auto apply = [&](bool full, DAcc &ar, int cs, int cc, int ct, int cs4, int cc4, int ct4, int max_qual, int strand, auto K, bool singleton, int k) -> unsigned long long {
         const bool is_ref = (cs == my_ref);
         int pb = 31;
@@ -2262,10 +2236,10 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
             const int pbucket = imax(0, max_qual - phredlike);
             if (is_ref) {
                 if (pbucket < NBUCKETS) hist_add(0, pbucket);
-                if (full) { ar.bDP += 1; ar.bTA += K(13); ar.bTB += K(14); bMQ_r += K(12); }
+                if (full) { ar.bDP += 1; ar.bTA += K(FF_W(n_cov)); ar.bTB += K(FF_W(n_near)); bMQ_r += K(FF_W(sq)); }
             } else {
                 pb = imin(pbucket, 31);
-                if (!full) { ar.bDP -= 1; ar.bTA -= K(13); ar.bTB -= K(14); bMQ_r -= K(12); }
+                if (!full) { ar.bDP -= 1; ar.bTA -= K(FF_W(n_cov)); ar.bTB -= K(FF_W(n_near)); bMQ_r -= K(FF_W(sq)); }
             }
         }
         // (conditions as values, increments as adds of 0 / 1: a nest of per-lane ifs is an exec-mask level each -- save, branch, restore -- per record)
@@ -2292,7 +2266,7 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
             const int pbucket = imax(0, maxq_link - phredlike);
             if (pbucket < NBUCKETS) hist_add(1, pbucket);
             const int lr = (SPLIT ? 5 * strand : 0);
-            atomicAdd(&lacc[lr + 0][col], 1); atomicAdd(&lacc[lr + 1][col], K(13)); atomicAdd(&lacc[lr + 2][col], K(14)); atomicAdd(&lacc[lr + 3][col], K(12));
+            atomicAdd(&lacc[lr + 0][col], 1); atomicAdd(&lacc[lr + 1][col], K(FF_W(n_cov))); atomicAdd(&lacc[lr + 2][col], K(FF_W(n_near))); atomicAdd(&lacc[lr + 3][col], K(FF_W(sq)));
         }
         if (singleton) atomicAdd(&lacc[(SPLIT ? 5 * strand : 0) + 4][col], 1);
     };
@@ -2305,55 +2279,48 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
         // one FragFast (24 dwords) per lane, fields of record j broadcast with v_readlane; base/qual bytes of record j+1 are
         // requested before record j is processed
         int c[24];
-        if (k0 + lane < hi) {
-            const int4 *q4 = (const int4 *)(R.ffast + (k0 + lane));
-#pragma unroll
-            for (int i = 0; i < 6; i++) { const int4 t = q4[i]; c[4 * i] = t.x; c[4 * i + 1] = t.y; c[4 * i + 2] = t.z; c[4 * i + 3] = t.w; }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 24; i++) c[i] = 0;
-        }
+        load_words(R.ffast + (k0 + lane), k0 + lane < hi, c);
         const int n = imin(64, hi - k0);
         int bq0n = 0, bq1n = 0;
         int n_fl = 0, n_fend = 0;   // of the record whose bytes are on their way: read once, used by its iteration too
         auto issue = [&](int j) {
-            const int fl = n_fl = bcast(c[3], j);
-            n_fend = bcast(c[1], j);
+            const int fl = n_fl = bcast(c[FF_W(flags)], j);
+            n_fend = bcast(c[FF_W(end)], j);
             // the list holds every fragment that could reach the window (begin within the longest span): four in ten end in front of it,
             // and a fragment of the generic kind is not read here at all -- no bytes for those
-            if (n_fend <= w0 || (fl & 1)) return;
-            int i0 = bcast(c[8], j), i1 = bcast(c[9], j);
-            if (fl & 0x100) {   // the lane's position may lie in run B of either alignment
-                if (p >= bcast(c[16], j) && p < bcast(c[17], j)) i0 = bcast(c[18], j);
-                if (p >= bcast(c[20], j) && p < bcast(c[21], j)) i1 = bcast(c[22], j);
+            if (n_fend <= w0 || (fl & FF_GENERIC)) return;
+            int i0 = bcast(c[FF_W(qb0)], j), i1 = bcast(c[FF_W(qb1)], j);
+            if (fl & FF_RUNS_B) {   // the lane's position may lie in run B of either alignment
+                if (p >= bcast(c[FF_W(bpos0)], j) && p < bcast(c[FF_W(brend0)], j)) i0 = bcast(c[FF_W(bqb0)], j);
+                if (p >= bcast(c[FF_W(bpos1)], j) && p < bcast(c[FF_W(brend1)], j)) i1 = bcast(c[FF_W(bqb1)], j);
             }
             bq0n = bq_load(rs, i0 + p);
-            if (((fl >> 3) & 0xF) == 2) bq1n = bq_load(rs, i1 + p);
+            if (ff_naln(fl) == 2) bq1n = bq_load(rs, i1 + p);
         };
         if (proton) break;   // IonTorrent values need neighbouring qualities: every fragment takes k_frag_generic
         issue(0);
         for (int j = 0; j < n; j++) {
-            const int b0 = bq0n & 0xFF, q0 = (bq0n >> 8) & 0xFF, b1 = bq1n & 0xFF, q1 = (bq1n >> 8) & 0xFF;
+            const int bq0 = bq0n, bq1 = bq1n;
             const int flags = n_fl, fend = n_fend;
             if (j + 1 < n) issue(j + 1);
             if (fend <= w0) continue;
-            const int fbeg = bcast(c[0], j);
-            if (flags & 1) continue;   // done by k_frag_generic
+            const int fbeg = bcast(c[FF_W(beg)], j);
+            if (flags & FF_GENERIC) continue;   // done by k_frag_generic
             // from here on the control flow stays wave-uniform down to the queue bookkeeping (nq is a scalar): per-lane conditions are predicates
             bool cover = (valid && p >= fbeg && p < fend);
-            const bool singleton = (flags >> 2) & 1;
+            const bool singleton = (flags & FF_SINGLETON) != 0;
             auto K = [&](int i) { return bcast(c[i], j); };
-            // consensus of <= 2 alignments in registers, written with selects (BASE_QUALITY_MAX merge, main.hpp:339-349)
-            const int pos0 = bcast(c[4], j), rend0 = bcast(c[5], j), pos1 = bcast(c[6], j), rend1 = bcast(c[7], j);
-            const bool has2 = (((flags >> 3) & 0xF) == 2);
+            // consensus of <= 2 alignments in registers (pair_consensus, link_better_mate)
+            const int pos0 = bcast(c[FF_W(pos0)], j), rend0 = bcast(c[FF_W(rend0)], j), pos1 = bcast(c[FF_W(pos1)], j), rend1 = bcast(c[FF_W(rend1)], j);
+            const bool has2 = (ff_naln(flags) == 2);
             bool in0 = (p >= pos0 && p < rend0), in1 = (has2 && p >= pos1 && p < rend1);
-            const bool full = (flags & 0x300) != 0;   // wave-uniform: not in k_frag_sums
+            const bool full = (flags & FF_FULL) != 0;   // wave-uniform: not in k_frag_sums
             if (full) {
-                const int nogap0 = bcast(c[10], j), nogap1 = bcast(c[11], j);
+                const int nogap0 = bcast(c[FF_W(nogap0)], j), nogap1 = bcast(c[FF_W(nogap1)], j);
                 bool lk0 = (in0 && p > pos0), lk1 = (in1 && p > pos1);   // LINK_M exists from the second base of a run on
-                if (flags & 0x100) {
-                    const int bpos0 = bcast(c[16], j), brend0 = bcast(c[17], j), bpos1 = bcast(c[20], j), brend1 = bcast(c[21], j);
-                    const int sp0 = bcast(c[19], j), sp1 = bcast(c[23], j);
+                if (flags & FF_RUNS_B) {
+                    const int bpos0 = bcast(c[FF_W(bpos0)], j), brend0 = bcast(c[FF_W(brend0)], j), bpos1 = bcast(c[FF_W(bpos1)], j), brend1 = bcast(c[FF_W(brend1)], j);
+                    const int sp0 = bcast(c[FF_W(sp0)], j), sp1 = bcast(c[FF_W(sp1)], j);
                     const bool inb0 = (p >= bpos0 && p < brend0), inb1 = (p >= bpos1 && p < brend1);
                     in0 = in0 || inb0; in1 = in1 || inb1;
                     lk0 = lk0 || (inb0 && p > bpos0); lk1 = lk1 || (inb1 && p > bpos1);
@@ -2361,28 +2328,14 @@ DEV void frag_body(const RegionDev &R, const UvcParams &P, unsigned (*hist)[NBUC
                     const unsigned off = (unsigned)(p - fbeg);
                     if (off - (unsigned)(sp0 & 0xFFFF) < (unsigned)(sp0 >> 16) || off - (unsigned)(sp1 & 0xFFFF) < (unsigned)(sp1 >> 16)) cover = false;
                 }
-                // LINK_M: value of the better mate
-                const int lv0 = (lk0 ? imax(noindel80 - nogap0, 0) + 1 : 0), lv1 = (lk1 ? imax(noindel80 - nogap1, 0) + 1 : 0);
-                const int lv = imax(lv0, lv1);
+                const int lv = link_better_mate(lk0, lk1, noindel80, nogap0, nogap1);
                 if (cover && lv > 0) link_full(lv, strand, K, singleton);
             }
             unsigned long long ev = 0ull;
             if (cover && (in0 || in1)) {
-                const int v0 = q0 + P.bq_phred_added_misma, v1 = q1 + P.bq_phred_added_misma;
-                const int A = (in0 ? v0 : 0), B = (in1 ? v1 : 0);
-                const bool diff = (in0 && in1 && b0 != b1);
-                const bool first = (v0 > v1) || (v0 == v1 && b0 < b1);
-                const int cc = imax(A, B), ct = (diff ? A + B : cc);
-                const int cs = ((in0 && (!diff || first)) ? b0 : b1);
-                int cs4 = cs, cc4 = cc, ct4 = ct;
-                if (padded_ignored) {   // fillConsensusCounts<false, true>: only A..T take part (main.hpp:410)
-                    const int A4 = ((in0 && b0 <= UVC_BASE_T) ? v0 : 0), B4 = ((in1 && b1 <= UVC_BASE_T) ? v1 : 0);
-                    const bool first4 = (A4 > B4) || (A4 == B4 && b0 < b1);
-                    cc4 = imax(A4, B4); ct4 = (diff ? A4 + B4 : cc4);
-                    cs4 = ((A4 == 0 && B4 == 0) ? UVC_BASE_T : (diff ? (first4 ? b0 : b1) : cs));
-                }
-                const int mq = maxq_base(cs);
-                ev = apply(full, ar, cs, cc, ct, cs4, cc4, ct4, mq, strand, K, singleton, k0 + j);
+                const PairCons pc = pair_consensus(in0, in1, bq0, bq1, P, padded_ignored);
+                const int mq = maxq_base(pc.cs);
+                ev = apply(full, ar, pc.cs, pc.cc, pc.ct, pc.cs4, pc.cc4, pc.ct4, mq, strand, K, singleton, k0 + j);
             }
             const wmask mm = BAL(ev != 0ull);
             if (mm) {
@@ -2607,33 +2560,19 @@ DEV void unit_counts(const RegionDev &R, const UvcParams &P, const FsRec &u, int
         const FragFast &ff = R.ffast[R.frag_rank[fi]];
         const int fbeg = ff.beg, fend = ff.end, flags = ff.flags;
         if (p < fbeg || p >= fend) continue;
-        if ((flags & 0x101) == 0 && !proton) {
-            // register path (see k_frag): LINK_M value of the better mate; BASE_QUALITY_MAX merge of the two mates' bases
+        if ((flags & FF_NOT_REGISTER) == 0 && !proton) {
+            // register path (see k_frag): link_better_mate, pair_consensus
             const int pos0 = ff.pos0, rend0 = ff.rend0, pos1 = ff.pos1, rend1 = ff.rend1;
-            const bool has2 = (((flags >> 3) & 0xF) == 2);
+            const bool has2 = (ff_naln(flags) == 2);
             const bool in0 = (p >= pos0 && p < rend0), in1 = (has2 && p >= pos1 && p < rend1);
-            const int lv0 = ((in0 && p > pos0) ? imax(noindel80 - ff.nogap0, 0) + 1 : 0), lv1 = ((in1 && p > pos1) ? imax(noindel80 - ff.nogap1, 0) + 1 : 0);
-            const int lv = imax(lv0, lv1);
+            const int lv = link_better_mate(in0 && p > pos0, in1 && p > pos1, noindel80, ff.nogap0, ff.nogap1);
             if (lv > 0) { con[UVC_LINK_M] += 1; if (HAS_MMM) mmm[UVC_LINK_M] += lv; }   // one symbol: 2*max - tot = lv, threshold 0 (main.hpp:466-520)
             if (in0 || in1) {
                 const int bq0 = (in0 ? bq_load(rs, ff.qb0 + p) : 0), bq1 = (in1 ? bq_load(rs, ff.qb1 + p) : 0);
-                const int b0 = bq0 & 0xFF, b1 = bq1 & 0xFF;
-                const int v0 = ((bq0 >> 8) & 0xFF) + P.bq_phred_added_misma, v1 = ((bq1 >> 8) & 0xFF) + P.bq_phred_added_misma;
-                const int A = (in0 ? v0 : 0), B = (in1 ? v1 : 0);
-                const bool diff = (in0 && in1 && b0 != b1);
-                const bool first = (v0 > v1) || (v0 == v1 && b0 < b1);
-                const int cc = imax(A, B), ct = (diff ? A + B : cc);
-                const int cs = ((in0 && (!diff || first)) ? b0 : b1);
-                int cs4 = cs, cc4 = cc, ct4 = ct;
-                if (padded_ignored) {   // fillConsensusCounts<false, true>: only A..T take part (main.hpp:410)
-                    const int A4 = ((in0 && b0 <= UVC_BASE_T) ? v0 : 0), B4 = ((in1 && b1 <= UVC_BASE_T) ? v1 : 0);
-                    const bool first4 = (A4 > B4) || (A4 == B4 && b0 < b1);
-                    cc4 = imax(A4, B4); ct4 = (diff ? A4 + B4 : cc4);
-                    cs4 = ((A4 == 0 && B4 == 0) ? UVC_BASE_T : (diff ? (first4 ? b0 : b1) : cs));
-                }
-                const int adj = imax(cc4 * 2, ct4) - ct4;
-                if (adj >= P.fam_thres_highBQ_snv && adj > 0) con[cs4] += 1;
-                if (HAS_MMM) { const int adj5 = imax(cc * 2, ct) - ct; if (adj5 > 0) mmm[cs] += adj5; }
+                const PairCons pc = pair_consensus(in0, in1, bq0, bq1, P, padded_ignored);
+                const int adj = imax(pc.cc4 * 2, pc.ct4) - pc.ct4;
+                if (adj >= P.fam_thres_highBQ_snv && adj > 0) con[pc.cs4] += 1;
+                if (HAS_MMM) { const int adj5 = imax(pc.cc * 2, pc.ct) - pc.ct; if (adj5 > 0) mmm[pc.cs] += adj5; }
             }
             continue;
         }
@@ -2674,7 +2613,7 @@ __global__ void __launch_bounds__(64) k_fam_stat(RegionDev R, UvcParams P) {
     int nsb_min = u.end, nsb_max = u.beg;
     const int nfrags = u.frag_end - u.frag_beg;
     // the scan can only succeed for UMI families (or fam_flag & 0x2): is_fam_good needs it (main.hpp:2988-2989)
-    if ((nfrags >= P.fam_thres_dup1add) && (qsum >= nq * P.fam_thres_qseqlen) && ((u.dflag & 0x1) || (P.fam_flag & 0x2))) {
+    if ((nfrags >= P.fam_thres_dup1add) && (qsum >= nq * P.fam_thres_qseqlen) && unit_may_be_good(u.dflag, P)) {
         int con[NSYM];
         for (int dir = 0; dir < 2; dir++) {
             int b = (dir ? (u.end - 1) : u.beg), e = (dir ? (u.beg - 1) : u.end), step = (dir ? -1 : 1);
@@ -2683,7 +2622,7 @@ __global__ void __launch_bounds__(64) k_fam_stat(RegionDev R, UvcParams P) {
                 int cs, cc, ct;
                 fill_consensus(con, cs, cc, ct, UVC_BASE_SYMBOL, false, false);
                 if (0 == ct) continue;
-                const bool good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
+                const bool good = is_fam_good(cc, ct, u.dflag, P);
                 if (good && (UVC_BASE_N != cs) && (UVC_BASE_NN != cs)) { if (dir) nsb_max = p; else nsb_min = p; break; }
             }
         }
@@ -2691,7 +2630,7 @@ __global__ void __launch_bounds__(64) k_fam_stat(RegionDev R, UvcParams P) {
     u.nsb_min = nsb_min; u.nsb_max = nsb_max;
     // k_fam_p4d leaves the (unit, position) cells under a fragment of the general kind (InDel reads, > 2 alignments) to k_fam_p4d_rest
     int has_general = (proton ? 1 : 0);
-    for (int f = u.frag_beg; f < u.frag_end && !has_general; f++) if (R.ffast_u[f].v[3] & 0x101) has_general = 1;
+    for (int f = u.frag_beg; f < u.frag_end && !has_general; f++) if (R.ffast_u[f].flags & FF_NOT_REGISTER) has_general = 1;
     u.pad_ = has_general;
     R.fss[ui] = u;
 }
@@ -2734,12 +2673,12 @@ DEV P4Pos p4_pos(const RegionDev &R, int p) {
 // NULL: loaded here, for the cells that reach the bias tests only.
 DEV void p4_apply(const FamAcc &A, const RegionDev &R, const UvcParams &P, const FsRec &u, int p, int64_t x, int st, int cs, int cc, int ct, const P4Pos *Qw) {
     const int strand = u.strand;
-    const bool is_fam_good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
+    const bool fam_good = is_fam_good(cc, ct, u.dflag, P);
     A.mark(cs);
     A.fap(strand, UVC_FAM_cDP12, cs, 1);
     if (1 == ct) A.fap(strand, UVC_FAM_cDP21, cs, 1);
     if (!P.inferred_is_vcf_generated) return;
-    if (is_fam_good) {
+    if (fam_good) {
         A.fi_mark(cs);
         A.fap(strand, UVC_FAM_cDP2, cs, 1);
         int rbeg = imin(u.nsb_min, p), rend = imax(u.nsb_max, p);
@@ -2805,7 +2744,7 @@ DEV void p4_apply(const FamAcc &A, const RegionDev &R, const UvcParams &P, const
 // position-bias flags -- is computed once for the cell's LINK and BASE consensus (P4Cell) instead of once per symbol type.  Same sums.
 struct P4Cell { int good_unit, l_nb, r_nb, lp1, lp2, rp1, rp2, lp0, rp0, seg_l_baq, seg_r_base, seg_r_gap; };
 DEV void p4_cell(P4Cell &W, const RegionDev &R, const UvcParams &P, const FsRec &u, int p, const P4Pos &Q) {
-    W.good_unit = (((u.dflag & 0x1) || (P.fam_flag & 0x2)) ? 1 : 0);
+    W.good_unit = (unit_may_be_good(u.dflag, P) ? 1 : 0);
     int rbeg = imin(u.nsb_min, p), rend = imax(u.nsb_max, p);
     const bool nonconf_middle = (u.l2r_end_median <= (u.r2l_end_median + P.indel_adj_tracklen_dist));
     if (nonconf_middle && p < u.r2l_end_median) rend = imax(imin(u.l2r_end_median, imin(u.r2l_end_median, rend)), p);
@@ -2929,7 +2868,7 @@ DEV int fam_qual(const RegionDev &R, const UvcParams &P, int strand, int64_t x, 
 DEV void p5_apply(const FamAcc &A, const RegionDev &R, const UvcParams &P, const FsRec &u, int64_t x, int st, const P5Cons &c, const double *p2p) {
     if (0 == c.tot_sumBQs) return;
     const int strand = u.strand;
-    const bool is_duplex_fam = (0x2 == (u.dflag & 0x2));
+    const bool is_duplex_fam = ((u.dflag & UVC_DFLAG_DUPLEX) != 0);
     const bool other_present = (u.other_fs >= 0);
     const bool will_inc_dscs = is_duplex_fam && other_present;
     const bool will_inc_sscs = is_duplex_fam && !other_present;
@@ -3126,55 +3065,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         // votes / BQ sums of LINK_M and of A C G T N (registers); the other eight symbols only through the general path
         int cL = 0, mL = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
         bool general = false;
-        // the fragment records of the unit: one per lane (12 dwords), fields of record j broadcast with v_readlane, the base / quality
+        // the fragment records of the unit: one per lane (FragUnit: the first 12 dwords of FragFast), fields of record j broadcast with v_readlane, the base / quality
         // bytes of record j + 1 requested before record j is evaluated -- three dependent memory round trips per unit instead of three per fragment
         const int nfr = u.frag_end - u.frag_beg;
         for (int f0 = 0; f0 < nfr; f0 += 64) {
             int c[12];
-            if (f0 + lane < nfr) {
-                const int4 *q4 = (const int4 *)(R.ffast_u + u.frag_beg + f0 + lane);
-#pragma unroll
-                for (int i = 0; i < 3; i++) { const int4 t = q4[i]; c[4 * i] = t.x; c[4 * i + 1] = t.y; c[4 * i + 2] = t.z; c[4 * i + 3] = t.w; }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 12; i++) c[i] = 0;
-            }
+            load_words(R.ffast_u + u.frag_beg + f0 + lane, f0 + lane < nfr, c);
             const int n = imin(64, nfr - f0);
             int bq0n = 0, bq1n = 0;
             auto issue = [&](int j) {
-                const int fl = bcast(c[3], j);
-                bq0n = bq_load(rs, bcast(c[8], j) + p);
-                if (((fl >> 3) & 0xF) == 2) bq1n = bq_load(rs, bcast(c[9], j) + p);
+                const int fl = bcast(c[FF_W(flags)], j);
+                bq0n = bq_load(rs, bcast(c[FF_W(qb0)], j) + p);
+                if (ff_naln(fl) == 2) bq1n = bq_load(rs, bcast(c[FF_W(qb1)], j) + p);
             };
             issue(0);
             for (int j = 0; j < n; j++) {
                 const int bq0 = bq0n, bq1 = bq1n;
                 if (j + 1 < n) issue(j + 1);
-                const int fbeg = bcast(c[0], j), fend = bcast(c[1], j), flags = bcast(c[3], j);
+                const int fbeg = bcast(c[FF_W(beg)], j), fend = bcast(c[FF_W(end)], j), flags = bcast(c[FF_W(flags)], j);
                 if (!(mine && p >= fbeg && p < fend)) continue;
-                if ((flags & 0x101) != 0 || proton) { general = true; continue; }
-                const int pos0 = bcast(c[4], j), rend0 = bcast(c[5], j), pos1 = bcast(c[6], j), rend1 = bcast(c[7], j);
-                const int nogap0 = bcast(c[10], j), nogap1 = bcast(c[11], j);
-                const bool has2 = (((flags >> 3) & 0xF) == 2);
+                if ((flags & FF_NOT_REGISTER) != 0 || proton) { general = true; continue; }
+                const int pos0 = bcast(c[FF_W(pos0)], j), rend0 = bcast(c[FF_W(rend0)], j), pos1 = bcast(c[FF_W(pos1)], j), rend1 = bcast(c[FF_W(rend1)], j);
+                const int nogap0 = bcast(c[FF_W(nogap0)], j), nogap1 = bcast(c[FF_W(nogap1)], j);
+                const bool has2 = (ff_naln(flags) == 2);
                 const bool in0 = (p >= pos0 && p < rend0), in1 = (has2 && p >= pos1 && p < rend1);
-                const int lv0 = ((in0 && p > pos0) ? imax(noindel80 - nogap0, 0) + 1 : 0), lv1 = ((in1 && p > pos1) ? imax(noindel80 - nogap1, 0) + 1 : 0);
-                const int lv = imax(lv0, lv1);
+                const int lv = link_better_mate(in0 && p > pos0, in1 && p > pos1, noindel80, nogap0, nogap1);
                 if (lv > 0) { cL += 1; mL += lv; }
                 if (in0 || in1) {
-                    const int b0 = bq0 & 0xFF, b1 = bq1 & 0xFF;
-                    const int v0 = ((bq0 >> 8) & 0xFF) + P.bq_phred_added_misma, v1 = ((bq1 >> 8) & 0xFF) + P.bq_phred_added_misma;
-                    const int Aq = (in0 ? v0 : 0), Bq = (in1 ? v1 : 0);
-                    const bool diff = (in0 && in1 && b0 != b1);
-                    const bool first = (v0 > v1) || (v0 == v1 && b0 < b1);
-                    const int cc = imax(Aq, Bq), ct = (diff ? Aq + Bq : cc);
-                    const int cs = ((in0 && (!diff || first)) ? b0 : b1);
-                    int cs4 = cs, cc4 = cc, ct4 = ct;
-                    if (padded_ignored) {
-                        const int A4 = ((in0 && b0 <= UVC_BASE_T) ? v0 : 0), B4 = ((in1 && b1 <= UVC_BASE_T) ? v1 : 0);
-                        const bool first4 = (A4 > B4) || (A4 == B4 && b0 < b1);
-                        cc4 = imax(A4, B4); ct4 = (diff ? A4 + B4 : cc4);
-                        cs4 = ((A4 == 0 && B4 == 0) ? UVC_BASE_T : (diff ? (first4 ? b0 : b1) : cs));
-                    }
+                    const PairCons pc = pair_consensus(in0, in1, bq0, bq1, P, padded_ignored); const int cs = pc.cs, cc = pc.cc, ct = pc.ct, cs4 = pc.cs4, cc4 = pc.cc4, ct4 = pc.ct4;
                     if (cs > UVC_BASE_N || cs4 > UVC_BASE_N) { general = true; continue; }   // cannot happen for packed base codes 0..4; kept as a guard
                     const int adj = imax(cc4 * 2, ct4) - ct4;
                     const int vote = ((adj >= P.fam_thres_highBQ_snv && adj > 0) ? 1 : 0);
@@ -3232,7 +3150,7 @@ __global__ void __launch_bounds__(64) k_fam_p4d_rest(RegionDev R, UvcParams P) {
         bool general = false;
         for (int f = u.frag_beg; f < u.frag_end && !general; f++) {
             const FragUnit &ff = R.ffast_u[f];
-            general = (p >= ff.v[0] && p < ff.v[1] && (((ff.v[3] & 0x101) != 0) || proton));
+            general = (p >= ff.beg && p < ff.end && (((ff.flags & FF_NOT_REGISTER) != 0) || proton));
         }
         if (!general) continue;
         int vcs[2], vcc[2], vct[2], dcs[2], dadj[2];
@@ -3468,7 +3386,7 @@ DEV void gap_alleles_run(const RegionDev &R, const UvcParams &P, const EV &E, co
     const FsRec u_first = R.fss[fs_first];
     int units[2] = { -1, -1 };
     units[u_first.strand] = fs_first; units[1 - u_first.strand] = u_first.other_fs;
-    const bool is_duplex_fam = (0x2 == (u_first.dflag & 0x2));
+    const bool is_duplex_fam = ((u_first.dflag & UVC_DFLAG_DUPLEX) != 0);
     const bool will_inc_dscs = is_duplex_fam && units[0] >= 0 && units[1] >= 0;
     const bool will_inc_sscs = is_duplex_fam && !will_inc_dscs;
     int con[2][NSYM], mmm[2][NSYM], cnt[NSYM];
@@ -3520,9 +3438,9 @@ DEV void gap_alleles_run(const RegionDev &R, const UvcParams &P, const EV &E, co
             const int e = unit_allele(cs);
             if (e < 0) atomicExch(R.err, UVCGPU_EDEVICE);
             else {
-                const bool is_fam_good = ((P.fam_thres_dup1add <= ct) && (cc * 100 >= ct * P.fam_thres_dup1perc) && ((u.dflag & 0x1) || (P.fam_flag & 0x2)));
+                const bool fam_good = is_fam_good(cc, ct, u.dflag, P);
                 emit(s, 1, cs, e);
-                if (is_fam_good) emit(s, 2, cs, e);
+                if (fam_good) emit(s, 2, cs, e);
             }
         }
         if (will_inc_dscs) {   // updateByFiltering<true, false, false>(con, {1, 1}), main.hpp:3429-3432

@@ -16,12 +16,10 @@
 
 namespace {
 #define PDEV __device__ __forceinline__
-PDEV int pmin(int a, int b) { return a < b ? a : b; }
-PDEV int pmax(int a, int b) { return a > b ? a : b; }
 enum { PC_MATCH = 0, PC_INS = 1, PC_DEL = 2, PC_REF_SKIP = 3, PC_SOFT_CLIP = 4, PC_HARD_CLIP = 5, PC_PAD = 6, PC_EQUAL = 7, PC_DIFF = 8 };
 PDEV bool is_m(int op) { return op == PC_MATCH || op == PC_EQUAL || op == PC_DIFF; }
 // one atomic per wave instead of one per lane: millions of same-address atomics serialise (k_read_facts took 8.6 ms with them, 0.2 without)
-PDEV int wave_max(int v) { for (int d = 32; d > 0; d >>= 1) v = pmax(v, __shfl_xor(v, d)); return v; }
+PDEV int wave_max(int v) { for (int d = 32; d > 0; d >>= 1) v = imax(v, __shfl_xor(v, d)); return v; }
 PDEV int wave_sum(int v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
 
 // ---- several prefix sums over one index in three launches (tile sums inside the producing kernel, one block over the tile sums, one apply
@@ -171,7 +169,7 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
             int32_t rp = pos, np2 = 0, span = 1;
             for (int k = 0; k < nc && ok; k++) {
                 const int op = (int)(cg[k] & 0xF); const int32_t len = (int32_t)(cg[k] >> 4);
-                if (is_m(op)) { if (rp - pos > 65535 || e - (rp + len) > 65535) ok = false; np2++; span = pmax(span, len); rp += len; }
+                if (is_m(op)) { if (rp - pos > 65535 || e - (rp + len) > 65535) ok = false; np2++; span = imax(span, len); rp += len; }
                 else if (op == PC_DEL) rp += len;
                 else if (op == PC_INS || op == PC_SOFT_CLIP || op == PC_HARD_CLIP) {}
                 else ok = false;   // N / P: keep the sequential path
@@ -184,11 +182,11 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
             if (o_np2) {
                 const int fl = in.flag[i];
                 const int cls = ((fl & 0x10) ? 1 : 0) | ((((fl & 0x81) == 0x81) ? ((fl & 0x20) != 0) : ((fl & 0x10) != 0)) ? 2 : 0);   // is-reverse | bam_get_strand << 1 (common.hpp:89)
-                w_cls[0] += (cls == 0) * o_np2; w_cls[1] += (cls == 1) * o_np2; w_cls[2] += (cls == 2) * o_np2; w_cls[3] += (cls == 3) * o_np2; w_p2span = pmax(w_p2span, span);
+                w_cls[0] += (cls == 0) * o_np2; w_cls[1] += (cls == 1) * o_np2; w_cls[2] += (cls == 2) * o_np2; w_cls[3] += (cls == 3) * o_np2; w_p2span = imax(w_p2span, span);
             }
         }
     }
-    if (err) { w_err = pmax(w_err, err); o_kind = 1; o_gaps = 0; o_ins = 0; o_np2 = 0; }
+    if (err) { w_err = imax(w_err, err); o_kind = 1; o_gaps = 0; o_ins = 0; o_np2 = 0; }
     endpos[i] = o_end; kind[i] = o_kind; n_p2[i] = o_np2; gaps[i] = o_gaps; trows[i] = o_trows; items[i] = o_items; ins[i] = o_ins;
     const bool ok_fam = !bad_fam;
     const int df = ok_fam ? (int)in.fam_dflag[fam] : 0;
@@ -213,7 +211,7 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
     __syncthreads();
     if (threadIdx.x == 0) {
         int v[7];
-        for (int q = 0; q < 7; q++) { v[q] = sh[0][q]; for (int w = 1; w < 4; w++) v[q] = (q < 3 ? pmax(v[q], sh[w][q]) : v[q] + sh[w][q]); }
+        for (int q = 0; q < 7; q++) { v[q] = sh[0][q]; for (int w = 1; w < 4; w++) v[q] = (q < 3 ? imax(v[q], sh[w][q]) : v[q] + sh[w][q]); }
         if (v[0]) atomicMax(&T->err, v[0]);
         if (v[1]) atomicMax(&T->max_p2_span, v[1]);
         if (v[2]) T->any_amplicon = 1;
@@ -293,50 +291,49 @@ __global__ void __launch_bounds__(256) k_build_frags(UvcPrepIn in, UvcParams P, 
     r.aln_beg = a0; r.aln_end = a1; r.beg = INT32_MAX; r.end = 0; r.fs = fs_of[a0]; r.strand = in.fam_strand[a0]; r.dflag = dflag_of[a0];
     bool all_simple = true;
     for (int k = a0; k < a1; k++) {
-        r.beg = pmin(r.beg, in.pos[k]); r.end = pmax(r.end, endpos[k]) + 1;
-        r.normMQ = pmax(r.normMQ, (int)in.mapq[k]);
+        r.beg = imin(r.beg, in.pos[k]); r.end = imax(r.end, endpos[k]) + 1;
+        r.normMQ = imax(r.normMQ, (int)in.mapq[k]);
         all_simple = all_simple && (kind[k] == 0);
     }
-    r.end = pmin(r.end, rend);
-    const bool amplicon_gated = (((r.dflag & 0x4) || ((P.primerlen > 0) && !(0x2 & P.primer_flag))) && !(P.tn_is_paired && (0x1 & P.primer_flag)));
-    r.stat_kind = (all_simple && (a1 - a0) <= 2 && !amplicon_gated) ? 0 : 1;
+    r.end = imin(r.end, rend);
+    r.stat_kind = (all_simple && (a1 - a0) <= 2 && !amplicon_gated(r.dflag, P)) ? FRAG_STAT_EVENTS : FRAG_STAT_SWEEP;
     // A base whose value (quality + bq_phred_added_misma; on IonTorrent the smaller of two qualities + the smaller addend) is 0 or less adds
     // nothing to the fragment's consensus, and a position where nothing adds up is not covered by the fragment (main.hpp:2658-2726).  The closed
     // forms of k_fragstat_fast / k_frag_sums / k_frag count every aligned position, so a fragment with such a base takes the per-position
-    // kernels (k_fragstat_sweep, k_frag_generic) at every one of its positions: stat_kind 2.  The qualities are only looked at when the column has a byte that low.
+    // kernels (k_fragstat_sweep, k_frag_generic) at every one of its positions: FRAG_STAT_ZERO_VALUE.  The qualities are only looked at when the column has a byte that low.
     if (in.quals) {
-        const int zthr = -((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) ? pmin(P.bq_phred_added_misma, P.bq_phred_added_indel) : P.bq_phred_added_misma);
+        const int zthr = zero_value_qual(P);
         if (zthr > 0 || (zthr == 0 && (!in.zero_qual || *in.zero_qual))) {
-            for (int k = a0; k < a1 && r.stat_kind != 2; k++) {
+            for (int k = a0; k < a1 && r.stat_kind != FRAG_STAT_ZERO_VALUE; k++) {
                 const uint8_t *q = in.quals + in.seq_off[k];
-                for (int j = 0; j < in.l_qseq[k]; j++) if ((int)q[j] <= zthr) { r.stat_kind = 2; break; }
+                for (int j = 0; j < in.l_qseq[k]; j++) if ((int)q[j] <= zthr) { r.stat_kind = FRAG_STAT_ZERO_VALUE; break; }
             }
         }
     }
-    sweep_flag[f] = (r.stat_kind != 0); frag_beg[f] = r.beg; frag_strand[f] = r.strand;
+    sweep_flag[f] = (r.stat_kind != FRAG_STAT_EVENTS); frag_beg[f] = r.beg; frag_strand[f] = r.strand;
     frags[f] = r;
-    w_span = pmax(w_span, r.end - r.beg); w_s0 += (r.strand == 0);
+    w_span = imax(w_span, r.end - r.beg); w_s0 += (r.strand == 0);
     }
     __shared__ int sh[4][2];
     w_span = wave_max(w_span); w_s0 = wave_sum(w_s0);
     if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6][0] = w_span; sh[threadIdx.x >> 6][1] = w_s0; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int sp = pmax(pmax(sh[0][0], sh[1][0]), pmax(sh[2][0], sh[3][0])), s0 = sh[0][1] + sh[1][1] + sh[2][1] + sh[3][1];
+        const int sp = imax(imax(sh[0][0], sh[1][0]), imax(sh[2][0], sh[3][0])), s0 = sh[0][1] + sh[1][1] + sh[2][1] + sh[3][1];
         if (sp) atomicMax(&T->max_frag_span, sp);
         if (s0) atomicAdd(&T->n_frag_strand0, s0);
     }
 }
-// uvcgpu_region_correct_bq has rewritten the qualities: a fragment that k_build_frags left to the closed forms (stat_kind 0) or to the M-run
-// form of k_frag (stat_kind 1 with FragFast flag 0x100) may now hold a base whose value is 0 or less.  Such a fragment becomes stat_kind 2, as
+// uvcgpu_region_correct_bq has rewritten the qualities: a fragment that k_build_frags left to the closed forms (FRAG_STAT_EVENTS) or to the M-run
+// form of k_frag (FRAG_STAT_SWEEP with FF_RUNS_B) may now hold a base whose value is 0 or less.  Such a fragment becomes FRAG_STAT_ZERO_VALUE, as
 // k_build_frags would have made it, and one that was not on the sweep list joins it at the end (the list's kernels take its entries in any
-// order: one block per entry, integer atomics).  A fragment that lost its last such base keeps stat_kind 2: the per-position kernels are exact for it.
+// order: one block per entry, integer atomics).  A fragment that lost its last such base keeps that kind: the per-position kernels are exact for it.
 __global__ void __launch_bounds__(256) k_requalify_frags(const uint8_t *quals, const int64_t *seq_off, const int32_t *l_qseq, int zthr, int32_t n_frags, FragRec *frags,
                                                          int32_t *sweep_frags, int32_t n_sweep, int32_t *n_joined) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n_frags) return;
     const int kind = frags[f].stat_kind;
-    if (kind == 2) return;
+    if (kind == FRAG_STAT_ZERO_VALUE) return;
     const int a0 = frags[f].aln_beg, a1 = frags[f].aln_end;
     bool low = false;
     for (int k = a0; k < a1 && !low; k++) {
@@ -344,8 +341,8 @@ __global__ void __launch_bounds__(256) k_requalify_frags(const uint8_t *quals, c
         for (int j = 0; j < l_qseq[k]; j++) if ((int)q[j] <= zthr) { low = true; break; }
     }
     if (!low) return;
-    frags[f].stat_kind = 2;
-    if (kind == 0) { const int32_t w = n_sweep + atomicAdd(n_joined, 1); if (w < n_frags) sweep_frags[w] = f; }
+    frags[f].stat_kind = FRAG_STAT_ZERO_VALUE;
+    if (kind == FRAG_STAT_EVENTS) { const int32_t w = n_sweep + atomicAdd(n_joined, 1); if (w < n_frags) sweep_frags[w] = f; }
 }
 // one thread per family-strand unit: fillTidBegEndFromAlns2 (main.hpp:675-697), the duplex partner, which kernels take it
 __global__ void __launch_bounds__(256) k_build_units(UvcPrepIn in, UvcParams P, int32_t rend, const int32_t *endpos, const int32_t *dflag_of, const int32_t *frag_first, const int32_t *fs_first_frag,
@@ -357,11 +354,11 @@ __global__ void __launch_bounds__(256) k_build_units(UvcPrepIn in, UvcParams P, 
     r.frag_beg = fs_first_frag[u]; r.frag_end = fs_first_frag[u + 1];
     const int a0 = frag_first[r.frag_beg], a1 = frag_first[r.frag_end];
     r.beg = INT32_MAX; r.end = 0; r.strand = in.fam_strand[a0]; r.fam = in.fam_id[a0]; r.dflag = dflag_of[a0];
-    for (int k = a0; k < a1; k++) { r.beg = pmin(r.beg, in.pos[k]); r.end = pmax(r.end, endpos[k]) + 1; }
-    r.end = pmin(r.end, rend);
+    for (int k = a0; k < a1; k++) { r.beg = imin(r.beg, in.pos[k]); r.end = imax(r.end, endpos[k]) + 1; }
+    r.end = imin(r.end, rend);
     r.other_fs = fam_fs[r.fam * 2 + (1 - r.strand)];
     const bool singleton_ok = (P.fam_thres_dup1add >= 2 && P.fam_thres_dup2add >= 2 && P.fam_thres_emperr_all_flat_snv >= 2 && P.fam_thres_emperr_all_flat_indel >= 2);
-    const bool duplex = ((r.dflag & 0x2) && r.other_fs >= 0);
+    const bool duplex = ((r.dflag & UVC_DFLAG_DUPLEX) && r.other_fs >= 0);
     r.generic = ((r.frag_end - r.frag_beg) >= 2 || duplex || !singleton_ok) ? 1 : 0;
     r.work_off = 0;
     fss[u] = r;
@@ -378,9 +375,9 @@ __global__ void __launch_bounds__(256) k_units_post(int32_t rend, int32_t n_fs, 
     FsRec &r = fss[u];
     int32_t df = 0; int64_t ds = 0;
     if (r.generic) { r.work_off = work_off[u]; generic_fs[generic_rank[u]] = u; }
-    if ((r.dflag & 0x2) && r.other_fs >= 0 && r.strand == 0) {
+    if ((r.dflag & UVC_DFLAG_DUPLEX) && r.other_fs >= 0 && r.strand == 0) {
         const FsRec &o = fss[r.other_fs];
-        df = 1; ds = (int64_t)(pmax(r.end, pmin(o.end, rend)) - pmin(r.beg, o.beg));
+        df = 1; ds = (int64_t)(imax(r.end, imin(o.end, rend)) - imin(r.beg, o.beg));
     }
     dup_flag[u] = df; dup_span[u] = ds;
 }
@@ -405,8 +402,8 @@ __global__ void k_stage2_totals(int32_t n_fs, int32_t n_frags, const int32_t *ge
 }
 __global__ void __launch_bounds__(256) k_max_i32(const int32_t *v, int64_t n, int32_t *out) {
     int32_t m = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) m = pmax(m, v[i]);
-    for (int d = 32; d > 0; d >>= 1) m = pmax(m, __shfl_xor(m, d));
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) m = imax(m, v[i]);
+    for (int d = 32; d > 0; d >>= 1) m = imax(m, __shfl_xor(m, d));
     if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 // the P2 work-list entries at their places (one thread per alignment; the order by (class, begin) is made afterwards)
@@ -566,10 +563,7 @@ extern "C" int uvc_prep_compact(const int32_t *l_qseq, const int32_t *n_cigar, i
     return (int)e;
 }
 
-// The quality at or below which a base has no value (k_build_frags decides stat_kind 2 by the same number)
-extern "C" int uvc_prep_zero_value_qual(const UvcParams *P) {
-    return -((UVC_PLATFORM_IONTORRENT == P->inferred_sequencing_platform) ? std::min(P->bq_phred_added_misma, P->bq_phred_added_indel) : P->bq_phred_added_misma);
-}
+extern "C" int uvc_prep_zero_value_qual(const UvcParams *P) { return zero_value_qual(*P); }   // (k_build_frags decides FRAG_STAT_ZERO_VALUE by the same number)
 // n_sweep: the length of sweep_frags (n_frags slots); n_joined: zeroed device word that receives the number of fragments added behind it
 extern "C" void uvc_prep_requalify(const uint8_t *quals, const int64_t *seq_off, const int32_t *l_qseq, const UvcParams *P, int32_t n_frags, FragRec *frags, int32_t *sweep_frags, int32_t n_sweep, int32_t *n_joined, hipStream_t s) {
     if (n_frags > 0) hipLaunchKernelGGL(k_requalify_frags, dim3(nblk(n_frags, 256)), dim3(256), 0, s, quals, seq_off, l_qseq, uvc_prep_zero_value_qual(P), n_frags, frags, sweep_frags, n_sweep, n_joined);
