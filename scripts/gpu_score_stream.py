@@ -80,8 +80,9 @@ def main():
     rec_b = 4 * _ffi.NUM_SCORE_FIELDS
     rows = bpr // 2 - 3 * rec_b                                             # device rows of one set per record
     print("# bytes per unit of chunk_records %d (rows %d + records %d + kept copy %d + host buffer %d, twice); chunk_records %d" % (bpr, rows, rec_b, rec_b, rec_b, c))
+    grp_rows = 692                                                          # of `rows`: the rows per group, of which a call holds min(2 x positions, capacity)
     print("# one call for %d records by the layout formulas: %.2f GB on the device (rows with 12.5 %% slack + records), %.2f GB of host buffer; the stream: %.2f GB in all"
-          % (n_rec, n_rec * (rows * 1.125 + rec_b) / 1e9, n_rec * rec_b / 1e9, c * bpr / 1e9))
+          % (n_rec, (((rows - grp_rows) * n_upper + grp_rows * min(2 * npos, n_upper)) * 1.125 + n_upper * rec_b) / 1e9, n_upper * rec_b / 1e9, c * bpr / 1e9))
     for leg, v in ms.items():
         print("# %-14s median %.2f ms  min %.2f  max %.2f  (n = %d)" % (leg, statistics.median(v), min(v), max(v), len(v)))
     for q in R.values():

@@ -1,4 +1,4 @@
-"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h): a source
+"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h, uvc_score_rows.h): a source
 file that defines a function includes the header that declares it, so the compiler checks the two against each other.  A prototype or a
 boundary struct written out again in a .cpp / .hip file is checked by nobody."""
 import glob
@@ -7,7 +7,8 @@ import re
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "uvc_amd", "csrc")
 SOURCES = sorted(glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(CSRC, "*.hip")))
-BOUNDARY_STRUCTS = ("RawReads", "UvcProf", "ZeroPlane", "UvcScoreRangeDev", "UvcRangeRow", "UvcUnitSpan", "UvcRangeCursor")
+BOUNDARY_STRUCTS = ("RawReads", "UvcProf", "ZeroPlane", "UvcScoreRangeDev", "UvcRangeRow", "UvcUnitSpan", "UvcRangeCursor", "UvcChunkDev",
+                    "ScoreRowDesc", "ScoreRows", "ScratchLayout", "SetLayout")
 
 
 def _lines():

@@ -92,7 +92,7 @@ struct uvcgpu_region {
     std::vector<UvcHapLinkHost> hap[3];
 };
 
-static bool stream_open_(const uvcgpu_region *r);   // a streamed score is open on the handle: accumulate, reset, set_reads and the one-call scores wait for its end
+static bool stream_is_open(const uvcgpu_region *r);   // a streamed score is open on the handle: accumulate, reset, set_reads and the one-call scores wait for its end
 static void stream_destroy(uvcgpu_region *r);
 static size_t group_bytes(const uvcgpu_region *r, int g) {
     const size_t n = (size_t)r->npos;
@@ -313,7 +313,7 @@ static int uvcgpu_region_create_impl(uvcgpu_region_t **out, const UvcParams *par
 // events and -- when the new region is not longer than the longest one the handle has seen -- the device buffers are kept.
 static int uvcgpu_region_reset_impl(uvcgpu_region_t *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) {
     if (!r || !refseq || end <= beg) return fail(UVCGPU_EINVAL, "bad argument");
-    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "reset while a score stream is open");
+    if (stream_is_open(r)) return fail(UVCGPU_ESTATE, "reset while a score stream is open");
     HIP_OK(hipStreamSynchronize(r->stream));
     if (r->side) HIP_OK(hipStreamSynchronize(r->side));
     if (r->side3) HIP_OK(hipStreamSynchronize(r->side3));
@@ -480,7 +480,7 @@ static int set_reads_on_device(uvcgpu_region_t *r, const UvcReadSoA *d, bool tim
 // Host columns: they are copied to the device as they are (no host pass over the reads), then prepared there.
 static int uvcgpu_region_set_reads_impl(uvcgpu_region_t *r, const UvcReadSoA *in) {
     if (!r || !in) return fail(UVCGPU_EINVAL, "bad reads");
-    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "set_reads while a score stream is open");
+    if (stream_is_open(r)) return fail(UVCGPU_ESTATE, "set_reads while a score stream is open");
     if (in->struct_size != (int32_t)sizeof(UvcReadSoA)) return fail(UVCGPU_EINVAL, "UvcReadSoA::struct_size mismatch (set it to sizeof(UvcReadSoA))");
     if (in->n_reads < 0 || in->n_fams < 0) return fail(UVCGPU_EINVAL, "bad reads");
     const bool timing = (getenv("UVCGPU_TIMING") != nullptr);   // stderr breakdown of the ingest, for tuning
@@ -528,7 +528,7 @@ static int uvcgpu_region_set_reads_impl(uvcgpu_region_t *r, const UvcReadSoA *in
 // read bases / quals / cigars in place -- and uvcgpu_region_correct_bq edits `quals` in place, as the reference edits its bam1_t.
 static int uvcgpu_region_set_reads_device_impl(uvcgpu_region_t *r, const UvcReadSoA *in) {
     if (!r || !in) return fail(UVCGPU_EINVAL, "bad reads");
-    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "set_reads while a score stream is open");
+    if (stream_is_open(r)) return fail(UVCGPU_ESTATE, "set_reads while a score stream is open");
     if (in->struct_size != (int32_t)sizeof(UvcReadSoA)) return fail(UVCGPU_EINVAL, "UvcReadSoA::struct_size mismatch (set it to sizeof(UvcReadSoA))");
     if (in->n_reads < 0 || in->n_fams < 0 || in->n_bases < 0 || in->n_cigar_ops < 0) return fail(UVCGPU_EINVAL, "bad reads");
     const bool timing = (getenv("UVCGPU_TIMING") != nullptr);
@@ -624,7 +624,7 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
 
 static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
     if (!r) return fail(UVCGPU_EINVAL, "null region");
-    if (stream_open_(r)) return fail(UVCGPU_ESTATE, "accumulate while a score stream is open");
+    if (stream_is_open(r)) return fail(UVCGPU_ESTATE, "accumulate while a score stream is open");
     if (!r->has_reads) return fail(UVCGPU_ENOREADS, "no reads");   // process_batch returns -1, main.cpp:520-523
     if (r->state_zeroed) { r->dirty_npos = 0; HIP_OK(hipStreamWaitEvent(r->stream, r->e_join, 0)); }   // zeroed behind the last score (release_state)
     else { const int rcz = zero_state(r, r->stream); if (rcz) return rcz; }
@@ -1085,7 +1085,6 @@ struct ScorePrep {
         if (d_al) hipFree(d_al); if (d_al_row) hipFree(d_al_row); if (d_tk) hipFree(d_tk); if (d_fs) hipFree(d_fs); if (d_rg) hipFree(d_rg);
     }
 };
-static bool stream_is_open(const uvcgpu_region *r);
 static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, ScorePrep &p) {
     if (!r->accumulated) return fail(UVCGPU_ESTATE, "score before accumulate");
     if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
@@ -1165,6 +1164,31 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
     p.in = UvcScoreIn{ &r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, nullptr, d_fs, d_rg, (int64_t)rtab.size(), npos_scored };
     return 0;
 }
+// One buffer of the score paths, `have` units of `unit` bytes each: device memory, or page-locked host memory with `host`.  It stays when
+// it holds `need` units and, with keep_max, no more than keep_max; else it is released and allocated anew with `slack` units on top.
+// Pointer and size change together (both clear after a failure, which returns `err` with the size in the message).
+extern "C++" template <class T, class N>
+static int fit_buffer(T *&p, N &have, N need, N slack, N keep_max, size_t unit, bool host, int err, const char *what) {
+    if (have >= need && !(keep_max && have > keep_max)) return 0;
+    if (p) { if (host) (void)hipHostFree(p); else (void)hipFree(p); }
+    p = nullptr; have = 0;
+    const size_t bytes = (size_t)(need + slack) * unit;
+    if ((host ? hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) : hipMalloc((void **)&p, bytes)) != hipSuccess) {
+        (void)hipGetLastError(); p = nullptr;
+        return fail(err, std::string(what) + " (" + std::to_string(bytes) + " bytes)");
+    }
+    have = need + slack;
+    return 0;
+}
+static const size_t SCORE_RECORD_BYTES = sizeof(int32_t) * UVC_NUM_SCORE_FIELDS;   // one record of a [fields][capacity] array
+// UvcScoreRequest::release_state: zero the planes on the side stream for the next accumulate, under the copies of the records.  The side
+// stream has to be behind the scoring kernels: the one call orders it here (e_fork); a chunk's caller has done so already (behind e_k).
+static bool queue_release_state(uvcgpu_region *r, bool stream_already_ordered) {
+    if (!stream_already_ordered && (hipEventRecord(r->e_fork, r->stream) != hipSuccess || hipStreamWaitEvent(r->side, r->e_fork, 0) != hipSuccess)) return false;
+    if (zero_state(r, r->side) != 0 || hipEventRecord(r->e_join, r->side) != hipSuccess) return false;
+    r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes; r->dirty_npos = r->npos;
+    return true;
+}
 static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
     if (!r || !out || !out->fields) return fail(UVCGPU_EINVAL, "bad argument");
     ScorePrep prep;   // (its destructor frees the temporaries on every return path)
@@ -1178,28 +1202,14 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
     int rc = 0;
     int64_t cnt[2] = { 0, 0 };
     for (int attempt = 0; attempt < 2 && !rc; attempt++) {
-        if (cap > r->score_capacity) {
-            if (r->d_score_fields) hipFree(r->d_score_fields);
-            r->d_score_fields = nullptr; r->score_capacity = 0;
-            HIP_OK(hipMalloc((void **)&r->d_score_fields, sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * cap));
-            r->score_capacity = cap;
-        }
-        if (kept_only && r->score_kept_capacity != r->score_capacity) {
-            if (r->d_score_kept) hipFree(r->d_score_kept);
-            r->d_score_kept = nullptr; r->score_kept_capacity = 0;
-            HIP_OK(hipMalloc((void **)&r->d_score_kept, sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * r->score_capacity));
-            r->score_kept_capacity = r->score_capacity;
-        }
-        {   // the staged rows of the scoring kernels are sized by the record capacity
-            const size_t need = uvc_score_scratch_bytes(npos_scored, r->score_capacity);
-            if (need > r->score_scratch_bytes) {
-                if (r->d_score_scratch) hipFree(r->d_score_scratch);
-                r->d_score_scratch = nullptr; r->score_scratch_bytes = 0;
-                HIP_OK(hipMalloc((void **)&r->d_score_scratch, need + need / 8));
-                r->score_scratch_bytes = need + need / 8;
-            }
-            r->d_score_count = (int64_t *)r->d_score_scratch;   // the record counts head the scratch (zeroed with the scan states)
-        }
+        const int64_t none = 0;
+        if ((rc = fit_buffer(r->d_score_fields, r->score_capacity, cap, none, none, SCORE_RECORD_BYTES, false, UVCGPU_EDEVICE, "score: hipMalloc of the records"))) break;
+        // the kept copy has the pitch of the records: exactly their capacity
+        if (kept_only && (rc = fit_buffer(r->d_score_kept, r->score_kept_capacity, r->score_capacity, none, r->score_capacity, SCORE_RECORD_BYTES, false, UVCGPU_EDEVICE, "score: hipMalloc of the kept records"))) break;
+        // the staged rows of the scoring kernels are sized by the record capacity (and the groups of the request)
+        const size_t need = uvc_score_scratch_bytes(npos_scored, r->score_capacity);
+        if ((rc = fit_buffer(r->d_score_scratch, r->score_scratch_bytes, need, need / 8, (size_t)0, 1, false, UVCGPU_EDEVICE, "score: hipMalloc of the scratch"))) break;
+        r->d_score_count = (int64_t *)r->d_score_scratch;   // the record counts head the scratch (zeroed with the scan states)
         HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos_scored, r->score_capacity), r->stream));
         const int pi = uvc_prof_begin(&r->prof, "k_score_all", r->stream);   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
         prep.in.scratch = r->d_score_scratch;
@@ -1220,12 +1230,7 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         out->n_records = n_out;
         if (kept_only && cnt[0] > r->score_capacity) rc = fail(UVCGPU_EDEVICE, "score: the record count changed between two passes");
         else if (n_out > out->capacity) rc = fail(UVCGPU_ENOMEM, "score output capacity too small");   // the planes stay: the caller comes back with a larger buffer
-        else if (rq.release_state && r->side) {   // the scoring kernels are done: zero the planes on the side stream under the D2H of the records
-            if (hipEventRecord(r->e_fork, r->stream) == hipSuccess && hipStreamWaitEvent(r->side, r->e_fork, 0) == hipSuccess
-                && zero_state(r, r->side) == 0 && hipEventRecord(r->e_join, r->side) == hipSuccess) {
-                r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes; r->dirty_npos = r->npos;
-            }
-        }
+        else if (rq.release_state && r->side) (void)queue_release_state(r, false);   // the scoring kernels are done: under the D2H of the records
         if (!rc && n_out > 0 && (hipMemcpy2DAsync(out->fields, sizeof(int32_t) * out->capacity, src, sizeof(int32_t) * r->score_capacity, sizeof(int32_t) * n_out, UVC_NUM_SCORE_FIELDS, hipMemcpyDeviceToHost, r->stream) != hipSuccess
                              || hipStreamSynchronize(r->stream) != hipSuccess))
             rc = fail(UVCGPU_EDEVICE, "hipMemcpy2D(records)");
@@ -1245,12 +1250,14 @@ struct uvcgpu_score_stream {
     int64_t chunk_records = 0; ScoreSet set[2];          // kept across streams with the same chunk_records
     ScorePrep *prep = nullptr;                           // the open stream's request and its device temporaries
     std::vector<UvcScoreRange> ranges; bool plain = true;   // the request's ranges (a plain request: its one range)
-    std::vector<int64_t> tab;                            // [n_chunks][4]: first group, group count, first record, record count
+    std::vector<UvcChunkDev> tab;                        // [n_chunks], as k_chunk_cut wrote it
     int64_t n_chunks = 0, launched = 0, returned = 0, ngroups = 0; int with_kept = 0; bool release_queued = false;
 };
 static bool stream_is_open(const uvcgpu_region *r) { return r && r->ss && r->ss->open; }
-static bool stream_open_(const uvcgpu_region *r) { return stream_is_open(r); }
-#define UVC_STREAM_HOST_TAIL 64   /* behind the records of a page-locked buffer: the chunk's kept count and the kernels' error word */
+#define UVC_STREAM_HOST_TAIL 64   /* behind the records of a page-locked buffer: */
+struct StreamTail { int64_t counts[2]; int32_t err; };   // the set's record counts ([1] = kept records) and the kernels' error word
+static_assert(sizeof(StreamTail) <= UVC_STREAM_HOST_TAIL, "the tail of a page-locked records buffer holds a StreamTail");
+static StreamTail *stream_tail(const ScoreSet &q, int64_t chunk_records) { return (StreamTail *)(q.h + SCORE_RECORD_BYTES * (size_t)chunk_records); }
 static void stream_free_sets(uvcgpu_score_stream *s) {
     for (ScoreSet &q : s->set) {
         if (q.d) hipFree(q.d);
@@ -1270,26 +1277,23 @@ static void stream_destroy(uvcgpu_region *r) {
 // chunk k: kernels on the handle's stream, then counts + records to the set's host buffer on the side stream
 static int stream_launch_chunk(uvcgpu_score_stream *s, int64_t k) {
     uvcgpu_region *r = s->r; const ScorePrep &p = *s->prep; ScoreSet &q = s->set[k & 1];
-    const int64_t *t = &s->tab[(size_t)k * 4];
-    const int64_t c = s->chunk_records, nr = t[3];
-    const int64_t win_groups = std::min<int64_t>(std::min<int64_t>(t[1], nr), c);   // active groups of the window: at most its groups, at most its records
-    int rc = uvc_launch_score_chunk(&p.in, q.d, c, s->with_kept, t[0], t[1], win_groups, nr, r->stream);
+    const UvcChunkDev &t = s->tab[(size_t)k];
+    const int64_t c = s->chunk_records, nr = t.nr;
+    const int64_t win_groups = std::min<int64_t>(std::min<int64_t>(t.ng, nr), c);   // active groups of the window: at most its groups, at most its records
+    int rc = uvc_launch_score_chunk(&p.in, q.d, c, s->with_kept, &t, win_groups, r->stream);
     if (rc) return fail(rc, "score stream: chunk launch refused");
     if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "score stream: kernel launch failed");
     hipStream_t cs = r->side ? r->side : r->stream;
     HIP_OK(hipEventRecord(q.e_k, r->stream));
     if (r->side) HIP_OK(hipStreamWaitEvent(cs, q.e_k, 0));
-    char *tail = q.h + sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)c;
-    HIP_OK(hipMemcpyAsync(tail, q.d, 16, hipMemcpyDeviceToHost, cs));            // the set's record counts: [1] = kept records
-    HIP_OK(hipMemcpyAsync(tail + 16, r->R.err, 4, hipMemcpyDeviceToHost, cs));
+    StreamTail *tail = stream_tail(q, c);
+    HIP_OK(hipMemcpyAsync(tail->counts, q.d, sizeof(tail->counts), hipMemcpyDeviceToHost, cs));   // (they head the row set)
+    HIP_OK(hipMemcpyAsync(&tail->err, r->R.err, sizeof(tail->err), hipMemcpyDeviceToHost, cs));
     // (kept_only: the kept count is on the device; the copy takes the columns of all the chunk's records, of which the kept ones are a prefix --
     //  under -A nearly all of them, at the default gate a few hundred KB more than needed, and nothing waits for a count)
     if (nr > 0) HIP_OK(hipMemcpy2DAsync(q.h, sizeof(int32_t) * (size_t)c, uvc_score_set_fields(q.d, c, s->ngroups, p.rq.kept_only ? 1 : 0), sizeof(int32_t) * (size_t)c, sizeof(int32_t) * (size_t)nr, UVC_NUM_SCORE_FIELDS, hipMemcpyDeviceToHost, cs));
-    if (k == s->n_chunks - 1 && p.rq.release_state && r->side) {   // behind the last chunk's kernels (and its copy): zero the planes for the next accumulate
-        if (zero_state(r, r->side) == 0 && hipEventRecord(r->e_join, r->side) == hipSuccess) {
-            r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes; r->dirty_npos = r->npos; s->release_queued = true;
-        }
-    }
+    // behind the last chunk's kernels (and its copy): cs is the side stream, ordered behind e_k above
+    if (k == s->n_chunks - 1 && p.rq.release_state && r->side && queue_release_state(r, true)) s->release_queued = true;
     HIP_OK(hipEventRecord(q.e_c, cs));
     s->launched = k + 1;
     return 0;
@@ -1326,30 +1330,17 @@ static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcSc
     if (r->d_score_fields) { hipFree(r->d_score_fields); r->d_score_fields = nullptr; r->score_capacity = 0; }
     if (r->d_score_kept) { hipFree(r->d_score_kept); r->d_score_kept = nullptr; r->score_kept_capacity = 0; }
     const size_t pos_need = uvc_score_stream_pos_bytes(npos, tab_cap);
-    if (r->score_scratch_bytes < pos_need || r->score_scratch_bytes > pos_need + pos_need / 4 + 65536) {
-        if (r->d_score_scratch) hipFree(r->d_score_scratch);
-        r->d_score_scratch = nullptr; r->score_scratch_bytes = 0; r->d_score_count = nullptr;
-        if (hipMalloc((void **)&r->d_score_scratch, pos_need) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, "score stream: hipMalloc of the position-sized scratch (" + std::to_string(pos_need) + " bytes)"); }
-        r->score_scratch_bytes = pos_need;
-    }
+    r->d_score_count = nullptr;
+    { const int rcb = fit_buffer(r->d_score_scratch, r->score_scratch_bytes, pos_need, (size_t)0, pos_need + pos_need / 4 + 65536, 1, false, UVCGPU_ENOMEM, "score stream: hipMalloc of the position-sized scratch"); if (rcb) return rcb; }
     r->d_score_count = (int64_t *)r->d_score_scratch;
     prep->in.scratch = r->d_score_scratch;   // (the chunks of the stream use it too)
     const int with_kept = rq.kept_only ? 1 : 0;
-    const size_t set_need = uvc_score_set_bytes(chunk_records, ngroups, with_kept), host_need = sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)chunk_records + UVC_STREAM_HOST_TAIL;
+    const size_t set_need = uvc_score_set_bytes(chunk_records, ngroups, with_kept), host_need = SCORE_RECORD_BYTES * (size_t)chunk_records + UVC_STREAM_HOST_TAIL;
     if (s->chunk_records != chunk_records) stream_free_sets(s);
     for (ScoreSet &q : s->set) {
-        if (q.d_bytes < set_need) {
-            if (q.d) hipFree(q.d);
-            q.d = nullptr; q.d_bytes = 0;
-            if (hipMalloc((void **)&q.d, set_need) != hipSuccess) { (void)hipGetLastError(); stream_free_sets(s); return fail(UVCGPU_ENOMEM, "score stream: hipMalloc of a row set (" + std::to_string(set_need) + " bytes for chunk_records = " + std::to_string(chunk_records) + ")"); }
-            q.d_bytes = set_need;
-        }
-        if (q.h_bytes < host_need) {
-            if (q.h) (void)hipHostFree(q.h);
-            q.h = nullptr; q.h_bytes = 0;
-            if (hipHostMalloc((void **)&q.h, host_need, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); stream_free_sets(s); return fail(UVCGPU_ENOMEM, "score stream: hipHostMalloc of a records buffer (" + std::to_string(host_need) + " bytes)"); }
-            q.h_bytes = host_need;
-        }
+        int rcb = fit_buffer(q.d, q.d_bytes, set_need, (size_t)0, (size_t)0, 1, false, UVCGPU_ENOMEM, ("score stream: hipMalloc of a row set for chunk_records = " + std::to_string(chunk_records)).c_str());
+        if (!rcb) rcb = fit_buffer(q.h, q.h_bytes, host_need, (size_t)0, (size_t)0, 1, true, UVCGPU_ENOMEM, "score stream: hipHostMalloc of a records buffer");
+        if (rcb) { stream_free_sets(s); return rcb; }
     }
     s->chunk_records = chunk_records; s->with_kept = with_kept; s->ngroups = ngroups;
     s->n_chunks = 0; s->launched = 0; s->returned = 0; s->release_queued = false; s->tab.clear();
@@ -1372,8 +1363,8 @@ static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcSc
         }
         if (hdr[0] < 0 || hdr[0] > tab_cap) return fail(UVCGPU_EDEVICE, "score stream: the chunk table overflowed");
         s->n_chunks = hdr[0];
-        s->tab.resize((size_t)s->n_chunks * 4);
-        if (s->n_chunks > 0 && (hipMemcpyAsync(s->tab.data(), d_tab + 32, 32 * (size_t)s->n_chunks, hipMemcpyDeviceToHost, r->stream) != hipSuccess || hipStreamSynchronize(r->stream) != hipSuccess)) return fail(UVCGPU_EDEVICE, "score stream: hipMemcpy(chunk table)");
+        s->tab.resize((size_t)s->n_chunks);
+        if (s->n_chunks > 0 && (hipMemcpyAsync(s->tab.data(), d_tab + 32, sizeof(UvcChunkDev) * (size_t)s->n_chunks, hipMemcpyDeviceToHost, r->stream) != hipSuccess || hipStreamSynchronize(r->stream) != hipSuccess)) return fail(UVCGPU_EDEVICE, "score stream: hipMemcpy(chunk table)");
     }
     s->prep = prep.release(); s->open = true;
     r->last_scored = 0; r->last_returned = 0;
@@ -1393,17 +1384,15 @@ static int uvcgpu_score_stream_next_impl(uvcgpu_score_stream_t *s, UvcScoreOut *
     if (j + 1 < s->n_chunks && s->launched == j + 1) { const int rc = stream_launch_chunk(s, j + 1); if (rc) return rc; }
     ScoreSet &q = s->set[j & 1];
     HIP_OK(hipEventSynchronize(q.e_c));
-    const int64_t c = s->chunk_records, *t = &s->tab[(size_t)j * 4];
-    const char *tail = q.h + sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * (size_t)c;
-    int64_t cnt[2]; int32_t e = 0;
-    memcpy(cnt, tail, 16); memcpy(&e, tail + 16, 4);
-    if (e) return fail(e, "a scoring kernel flagged an error");
-    const int64_t n_out = (s->prep->rq.kept_only ? cnt[1] : t[3]);
-    if (n_out < 0 || n_out > t[3]) return fail(UVCGPU_EDEVICE, "score stream: the kept count of a chunk is out of range");
+    const UvcChunkDev &t = s->tab[(size_t)j];
+    const StreamTail tail = *stream_tail(q, s->chunk_records);
+    if (tail.err) return fail(tail.err, "a scoring kernel flagged an error");
+    const int64_t n_out = (s->prep->rq.kept_only ? tail.counts[1] : (int64_t)t.nr);
+    if (n_out < 0 || n_out > t.nr) return fail(UVCGPU_EDEVICE, "score stream: the kept count of a chunk is out of range");
     chunk->fields = (int32_t *)q.h; chunk->n_records = n_out;
-    r->last_scored += t[3]; r->last_returned += n_out;
+    r->last_scored += t.nr; r->last_returned += n_out;
     // the ranges this chunk covers: the request's ranges cut to the chunk's compact positions; a piece that begins inside a range continues it
-    const int64_t c0 = t[0] / 2, c1 = c0 + t[1] / 2;
+    const int64_t c0 = t.g0 / 2, c1 = c0 + t.ng / 2;
     int64_t at = 0, nc = 0;
     for (const UvcScoreRange &g : s->ranges) {
         const int64_t len = std::max<int64_t>((int64_t)g.pos_end - g.pos_beg, 0), lo = std::max(c0, at), hi = std::min(c1, at + len);
@@ -1427,12 +1416,12 @@ int uvcgpu_region_score_stream_begin(uvcgpu_region_t *r, const UvcScoreRequest *
 }
 int uvcgpu_score_stream_next(uvcgpu_score_stream_t *s, UvcScoreOut *chunk, UvcScoreRange *covered, int64_t *n_covered) { return guarded("uvcgpu_score_stream_next", [&] { return uvcgpu_score_stream_next_impl(s, chunk, covered, n_covered); }); }
 int uvcgpu_score_stream_end(uvcgpu_score_stream_t *s) { return guarded("uvcgpu_score_stream_end", [&] { return uvcgpu_score_stream_end_impl(s); }); }
-int64_t uvcgpu_score_stream_bytes_per_record(void) { return 2 * ((int64_t)uvc_score_set_bytes_per_record() + (int64_t)sizeof(int32_t) * UVC_NUM_SCORE_FIELDS); }
+int64_t uvcgpu_score_stream_bytes_per_record(void) { return 2 * ((int64_t)uvc_score_set_bytes_per_record() + (int64_t)SCORE_RECORD_BYTES); }
 int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     if (!r) return -1;
     int64_t b = (int64_t)r->score_scratch_bytes + (int64_t)r->h_stage_cap;
-    if (r->d_score_fields) b += (int64_t)sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * r->score_capacity;
-    if (r->d_score_kept) b += (int64_t)sizeof(int32_t) * UVC_NUM_SCORE_FIELDS * r->score_kept_capacity;
+    if (r->d_score_fields) b += (int64_t)SCORE_RECORD_BYTES * r->score_capacity;
+    if (r->d_score_kept) b += (int64_t)SCORE_RECORD_BYTES * r->score_kept_capacity;
     if (r->ss) for (const ScoreSet &q : r->ss->set) b += (int64_t)q.d_bytes + (int64_t)q.h_bytes;
     return b;
 }

@@ -9,6 +9,7 @@
 // Tumor-only, and with UvcTumorKey records in the request the normal sample of a T/N pair (SURVEY next-row N2).
 #include <algorithm>
 #include "uvc_launch.h"
+#include "uvc_score_rows.h"
 
 #define DBL_EPS 2.220446049250313e-16
 #define FLT_EPS 1.1920928955078125e-07
@@ -199,57 +200,8 @@ DEV int group_refsymbol(const RegionDev &R, int zpos, int st) {   // symboltype_
 //   k_qual        per record: sum_DPv over the group's records + calc_qual
 // The arithmetic kernels read coalesced rows, hold no plane pointers and fit four waves per SIMD.
 // ================================================================================================
-enum { SG_PREP32 = 0, SG_PREP64, SG_SEG32, SG_SEG64, SG_VQ, SG_FRAG, SG_FAM, SG_FI32, SG_FI64, SG_DUP };
 struct StageDesc { unsigned char grp, trunc; unsigned short plane; };
 
-// symbol-type totals (fill_symboltype_fmt, main.hpp:3745-3793): X(name, plane group, plane, the int32 FORMAT field truncates the sum)
-#define TOT_LIST(X) \
-    X(APDP0, SG_PREP32, UVC_P_a_dp, 0) X(APDP1, SG_PREP32, UVC_P_a_near_ins_dp, 0) X(APDP2, SG_PREP32, UVC_P_a_near_del_dp, 0) X(APDP3, SG_PREP32, UVC_P_a_near_RTR_ins_dp, 0) \
-    X(APDP4, SG_PREP32, UVC_P_a_near_RTR_del_dp, 0) X(APDP5, SG_PREP32, UVC_P_a_pcr_dp, 0) X(APDP6, SG_PREP32, UVC_P_a_snv_dp, 0) X(APDP7, SG_PREP32, UVC_P_a_dnv_dp, 0) \
-    X(APDP8, SG_PREP32, UVC_P_a_highBQ_dp, 0) X(APDP9, SG_PREP32, UVC_P_a_near_pcr_clip_dp, 0) X(APDP10, SG_PREP32, UVC_P_a_near_long_clip_dp, 0) X(APDP11, SG_PREP32, UVC_P_a_umi_dp, 0) \
-    X(APXM0, SG_PREP32, UVC_P_a_XM1500, 0) X(APXM1, SG_PREP32, UVC_P_a_GO1500, 0) X(APXM2, SG_PREP32, UVC_P_a_qlen, 0) X(APXM3, SG_PREP32, UVC_P_a_GAPLEN, 0) \
-    X(APXM4, SG_PREP64, UVC_P_a_near_ins_pow2len, 0) X(APXM5, SG_PREP64, UVC_P_a_near_del_pow2len, 0) X(APXM6, SG_PREP32, UVC_P_a_near_ins_inv100len, 0) X(APXM7, SG_PREP32, UVC_P_a_near_del_inv100len, 0) \
-    X(APLRI0, SG_PREP64, UVC_P_a_LI, 0) X(APLRI1, SG_PREP32, UVC_P_a_LIDP, 0) X(APLRI2, SG_PREP64, UVC_P_a_RI, 0) X(APLRI3, SG_PREP32, UVC_P_a_RIDP, 0) \
-    X(A1BQf0, SG_VQ, UVC_VQ_a1BQf, 1) X(A1BQr0, SG_VQ, UVC_VQ_a1BQr, 1) X(AMQs0, SG_SEG32, UVC_S_aMQs, 1) X(AP10, SG_SEG32, UVC_S_aP1, 1) X(AP20, SG_SEG32, UVC_S_aP2, 1) \
-    X(ADPff0, SG_SEG32, UVC_S_aDPff, 1) X(ADPfr0, SG_SEG32, UVC_S_aDPfr, 1) X(ADPrf0, SG_SEG32, UVC_S_aDPrf, 1) X(ADPrr0, SG_SEG32, UVC_S_aDPrr, 1) \
-    X(ALP10, SG_SEG32, UVC_S_aLP1, 1) X(ALP20, SG_SEG32, UVC_S_aLP2, 1) X(ALPL0, SG_SEG32, UVC_S_aLPL, 0) X(ARP20, SG_SEG32, UVC_S_aRP2, 1) X(ARPL0, SG_SEG32, UVC_S_aRPL, 0) \
-    X(ALB20, SG_SEG32, UVC_S_aLB2, 1) X(ALBL0, SG_SEG64, UVC_S64_aLBL, 0) X(ARB20, SG_SEG32, UVC_S_aRB2, 1) X(ARBL0, SG_SEG64, UVC_S64_aRBL, 0) \
-    X(ABQ20, SG_SEG32, UVC_S_aBQ2, 1) X(APF20, SG_SEG32, UVC_S_aPF2, 1) X(ALI20, SG_SEG32, UVC_S_aLI2, 1) X(ARIf0, SG_SEG32, UVC_S_aRIf, 1) X(ARI20, SG_SEG32, UVC_S_aRI2, 1) X(ALIr0, SG_SEG32, UVC_S_aLIr, 1) \
-    X(BDPb0, SG_FRAG, 0 * UVC_NFRAG + UVC_FRAG_bDP, 1) X(BDPb1, SG_FRAG, 1 * UVC_NFRAG + UVC_FRAG_bDP, 1) X(BTAb0, SG_FRAG, 0 * UVC_NFRAG + UVC_FRAG_bTA, 1) X(BTAb1, SG_FRAG, 1 * UVC_NFRAG + UVC_FRAG_bTA, 1) \
-    X(BTBb0, SG_FRAG, 0 * UVC_NFRAG + UVC_FRAG_bTB, 1) X(BTBb1, SG_FRAG, 1 * UVC_NFRAG + UVC_FRAG_bTB, 1) \
-    X(CDP1b0, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP1, 1) X(CDP1b1, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP1, 1) X(CDP12b0, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP12, 1) X(CDP12b1, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP12, 1) \
-    X(CDP2b0, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP2, 1) X(CDP2b1, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP2, 1) X(CDP3b0, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP3, 1) X(CDP3b1, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP3, 1) \
-    X(C2LP20, SG_FI32, UVC_FI_c2LP2, 1) X(C2LPL0, SG_FI32, UVC_FI_c2LPL, 0) X(C2RP20, SG_FI32, UVC_FI_c2RP2, 1) X(C2RPL0, SG_FI32, UVC_FI_c2RPL, 0) \
-    X(C2LB20, SG_FI32, UVC_FI_c2LB2, 1) X(C2LBL0, SG_FI64, UVC_FI64_c2LBL, 0) X(C2RB20, SG_FI32, UVC_FI_c2RB2, 1) X(C2RBL0, SG_FI64, UVC_FI64_c2RBL, 0) \
-    X(C2BQ20, SG_FI32, UVC_FI_c2BQ2, 1) X(C2LP00, SG_FI32, UVC_FI_c2LP0, 1) X(C2RP00, SG_FI32, UVC_FI_c2RP0, 1) X(DDP10, SG_DUP, UVC_DUPLEX_dDP1, 1)
-// one allele's own cells (BcfFormat_symbol_init, main.hpp:4094-4251): X(name, plane group, plane); the 64-bit planes last
-#define AL_LIST(X) \
-    X(a1BQf, SG_VQ, UVC_VQ_a1BQf) X(a1BQr, SG_VQ, UVC_VQ_a1BQr) X(v2BQf, SG_VQ, UVC_VQ_a2BQf) X(v2BQr, SG_VQ, UVC_VQ_a2BQr) X(vbMQ, SG_VQ, UVC_VQ_bMQ) \
-    X(bIAQb, SG_VQ, UVC_VQ_bIAQb) X(bIADb, SG_VQ, UVC_VQ_bIADb) X(cIAQf, SG_VQ, UVC_VQ_cIAQf) X(cIADf, SG_VQ, UVC_VQ_cIADf) X(cIDQf, SG_VQ, UVC_VQ_cIDQf) \
-    X(cIAQr, SG_VQ, UVC_VQ_cIAQr) X(cIADr, SG_VQ, UVC_VQ_cIADr) X(cIDQr, SG_VQ, UVC_VQ_cIDQr) \
-    X(aMQs, SG_SEG32, UVC_S_aMQs) X(aP1, SG_SEG32, UVC_S_aP1) X(aP2, SG_SEG32, UVC_S_aP2) X(aDPff, SG_SEG32, UVC_S_aDPff) X(aDPfr, SG_SEG32, UVC_S_aDPfr) X(aDPrf, SG_SEG32, UVC_S_aDPrf) X(aDPrr, SG_SEG32, UVC_S_aDPrr) \
-    X(aLP1, SG_SEG32, UVC_S_aLP1) X(aLP2, SG_SEG32, UVC_S_aLP2) X(aLPL, SG_SEG32, UVC_S_aLPL) X(aRP1, SG_SEG32, UVC_S_aRP1) X(aRP2, SG_SEG32, UVC_S_aRP2) X(aRPL, SG_SEG32, UVC_S_aRPL) \
-    X(aLB1, SG_SEG32, UVC_S_aLB1) X(aLB2, SG_SEG32, UVC_S_aLB2) X(aRB1, SG_SEG32, UVC_S_aRB1) X(aRB2, SG_SEG32, UVC_S_aRB2) X(a2XM2, SG_SEG32, UVC_S_a2XM2) X(a2BM2, SG_SEG32, UVC_S_a2BM2) X(aBQ2, SG_SEG32, UVC_S_aBQ2) \
-    X(aPF1, SG_SEG32, UVC_S_aPF1) X(aPF2, SG_SEG32, UVC_S_aPF2) X(aLI1, SG_SEG32, UVC_S_aLI1) X(aLI2, SG_SEG32, UVC_S_aLI2) X(aLIr, SG_SEG32, UVC_S_aLIr) X(aRI1, SG_SEG32, UVC_S_aRI1) X(aRI2, SG_SEG32, UVC_S_aRI2) X(aRIf, SG_SEG32, UVC_S_aRIf) \
-    X(aP3, SG_SEG32, UVC_S_aP3) X(aNC, SG_SEG32, UVC_S_aNC) \
-    X(bDPf, SG_FRAG, 0 * UVC_NFRAG + UVC_FRAG_bDP) X(bTAf, SG_FRAG, 0 * UVC_NFRAG + UVC_FRAG_bTA) X(bTBf, SG_FRAG, 0 * UVC_NFRAG + UVC_FRAG_bTB) \
-    X(bDPr, SG_FRAG, 1 * UVC_NFRAG + UVC_FRAG_bDP) X(bTAr, SG_FRAG, 1 * UVC_NFRAG + UVC_FRAG_bTA) X(bTBr, SG_FRAG, 1 * UVC_NFRAG + UVC_FRAG_bTB) \
-    X(cDP1f, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP1) X(cDP12f, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP12) X(cDP2f, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP2) X(cDP3f, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDP3) \
-    X(cDPMf, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDPM) X(cDPmf, SG_FAM, 0 * UVC_NFAM + UVC_FAM_cDPm) \
-    X(cDP1r, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP1) X(cDP12r, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP12) X(cDP2r, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP2) X(cDP3r, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDP3) \
-    X(cDPMr, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDPM) X(cDPmr, SG_FAM, 1 * UVC_NFAM + UVC_FAM_cDPm) \
-    X(c2LP1, SG_FI32, UVC_FI_c2LP1) X(c2LP2, SG_FI32, UVC_FI_c2LP2) X(c2LPL, SG_FI32, UVC_FI_c2LPL) X(c2RP1, SG_FI32, UVC_FI_c2RP1) X(c2RP2, SG_FI32, UVC_FI_c2RP2) X(c2RPL, SG_FI32, UVC_FI_c2RPL) \
-    X(c2LB1, SG_FI32, UVC_FI_c2LB1) X(c2LB2, SG_FI32, UVC_FI_c2LB2) X(c2RB1, SG_FI32, UVC_FI_c2RB1) X(c2RB2, SG_FI32, UVC_FI_c2RB2) X(c2BQ2, SG_FI32, UVC_FI_c2BQ2) X(c2LP0, SG_FI32, UVC_FI_c2LP0) X(c2RP0, SG_FI32, UVC_FI_c2RP0) \
-    X(dDP1, SG_DUP, UVC_DUPLEX_dDP1) X(dDP2, SG_DUP, UVC_DUPLEX_dDP2) \
-    X(aLBL, SG_SEG64, UVC_S64_aLBL) X(aRBL, SG_SEG64, UVC_S64_aRBL) X(aLIT, SG_SEG64, UVC_S64_aLIT) X(aRIT, SG_SEG64, UVC_S64_aRIT) X(c2LBL, SG_FI64, UVC_FI64_c2LBL) X(c2RBL, SG_FI64, UVC_FI64_c2RBL)
-#define NAL64 6
-#define X(n, g, p, t) TOT_##n,
-enum { TOT_LIST(X) NTOT };
-#undef X
-#define X(n, g, p) AL_##n,
-enum { AL_LIST(X) NAL };
-#undef X
-#define NAL32 (NAL - NAL64)
 // One table of the distinct planes the two lists read (every symbol plane of TOT_LIST is also an allele cell): the gather fetches a plane's
 // cells of a group once and serves the group's total and its records' own cells from them.
 struct GatherDesc { unsigned char grp, trunc; unsigned short plane; short tot, al; };
@@ -281,33 +233,32 @@ constexpr GatherTab make_gather_tab() {
     return g;
 }
 __constant__ GatherTab c_gather = make_gather_tab();
-// per active group
-enum { GR_x = 0, GR_zpos, GR_st, GR_refsym, GR_mask, GR_hp, GR_r1t, GR_r1u, GR_r1a, GR_r2t, GR_r2u, GR_r2a, GR_insc, GR_delc, GR_ins1c, GR_del1c, GR_rusize, GR_repnum, GR_rec0, GR_nrec, GR_refbdp, GR_vAC, GR_gemit, GR_kept, NGR };
-// per record
-enum { RH_gi = 0, RH_symbol, RH_src, RH_idx, RH_bdepth, RH_cdepth, NRH };
-// what k_dpv_pre hands to k_dp4 / k_dpv_post
-enum { MID_cbP = 0, MID_cbBQ, MID_dirdiv, MID_aDPFA, MID_cFA2L, MID_cFA2R, MID_dff, MID_pcread, MID_aPprior, MID_aBprior, MID_aIprior, MID_aSBprior, MID_oriall, NMID };
-#define NDP4 14
-enum { CNT_nvalid = 0, CNT_ticket1, CNT_ticket2, CNT_kept, NCNT = 8 };
 
 struct Stage {
-    int32_t *grp;        // [NGR][cap]
-    long long *tot;      // [NTOT][cap]
+    int32_t *grp;        // [NGR][gcap]
+    long long *tot;      // [NTOT][gcap]
     int32_t *rh;         // [NRH][cap]
     int32_t *al;         // [NAL32][cap]
     long long *al64;     // [NAL64][cap]
     double *mid;         // [NMID][cap]
     double *d4;          // [NDP4][2][cap]
     long long cap;       // records the rows can hold
-    long long gcap;      // active groups the group rows (grp, tot, keptoff) can hold: cap in the one-call layout, min(groups, cap) in the streamed one
+    long long gcap;      // active groups the group rows (grp, tot, keptoff) can hold: min(groups of the request, cap)
     // the chunk window of a streamed score: groups [win_g, win_g + win_n) of the request, cut on a position boundary (k_chunk_cut).  Rows and
     // record indices are relative to the window's first active group and first record.  The one-call path passes (0, all groups): the
     // window's bases are then offsets[0] = 0 and the length is the whole list -- uniform scalar loads, no per-lane work
     long long win_g, win_n;
     unsigned int *cnt;   // [NCNT] counters, zeroed in front of every call: records of the groups that fit, tickets of the two chained scans
     unsigned long long *status1, *status2;   // tile states of the two chained scans (zeroed with the counters)
-    int32_t *keptoff;    // [cap] kept_only: first record of an active group in the kept array, or -1
+    int32_t *keptoff;    // [gcap] kept_only: first record of an active group in the kept array, or -1
 };
+// the row pointers and the two pitches of S from a row block laid out at `base` (SCORE_ROW_LIST: every block, by the name of its pointer)
+static void bind_rows(Stage &S, char *base, const ScoreRows &L) {
+#define X(n, T, rows, by_group) S.n = (T *)(base + L.off[SROW_##n]);
+    SCORE_ROW_LIST(X)
+#undef X
+    S.cap = L.c; S.gcap = L.gc;
+}
 #define GR_(f, gi_) ROW_(int32_t, S.grp, GR_##f, S.gcap, gi_)
 #define RH_(f, r_) ROW_(int32_t, S.rh, RH_##f, S.cap, r_)
 #define MID_(f, r_) ROW_(double, S.mid, MID_##f, S.cap, r_)
@@ -328,163 +279,11 @@ DEV long long stage_cell(const RegionDev &R, int grp, int plane, int s, int64_t 
         default: return R.duplex[((size_t)plane * NSYM + s) * np + x];
     }
 }
-// staged-row accessors: the names of the old per-thread structs (Tot T, Al f) as loads at the point of use; `gi` / `rec` are the thread's group / record
-#define TT_(n) ROW_(long long, S.tot, TOT_##n, S.gcap, gi)
-#define AL_(n) ROW_(int32_t, S.al, AL_##n, S.cap, rec)
+// staged-row accessors: a cell by its list name, as a load at the point of use and as a value of the type the lists of uvc_score_rows.h
+// give it (TOT_INT_LIST, AL_WIDE_LIST); `gi` / `rec` are the thread's group / record
+#define TT_(n) ((TotRead<TOT_##n>::type)ROW_(long long, S.tot, TOT_##n, S.gcap, gi))
+#define AL_(n) ((AlRead<AL_##n>::type)ROW_(int32_t, S.al, AL_##n, S.cap, rec))
 #define AL64_(n) ROW_(long long, S.al64, AL_##n - NAL32, S.cap, rec)
-#define T_APDP0 TT_(APDP0)
-#define T_APDP1 TT_(APDP1)
-#define T_APDP2 TT_(APDP2)
-#define T_APDP3 TT_(APDP3)
-#define T_APDP4 TT_(APDP4)
-#define T_APDP5 TT_(APDP5)
-#define T_APDP6 TT_(APDP6)
-#define T_APDP7 TT_(APDP7)
-#define T_APDP8 TT_(APDP8)
-#define T_APDP9 TT_(APDP9)
-#define T_APDP10 TT_(APDP10)
-#define T_APDP11 TT_(APDP11)
-#define T_APXM0 TT_(APXM0)
-#define T_APXM1 TT_(APXM1)
-#define T_APXM2 TT_(APXM2)
-#define T_APXM3 TT_(APXM3)
-#define T_APXM4 TT_(APXM4)
-#define T_APXM5 TT_(APXM5)
-#define T_APXM6 TT_(APXM6)
-#define T_APXM7 TT_(APXM7)
-#define T_APLRI0 TT_(APLRI0)
-#define T_APLRI1 TT_(APLRI1)
-#define T_APLRI2 TT_(APLRI2)
-#define T_APLRI3 TT_(APLRI3)
-#define T_A1BQf0 TT_(A1BQf0)
-#define T_A1BQr0 TT_(A1BQr0)
-#define T_AMQs0 TT_(AMQs0)
-#define T_AP10 TT_(AP10)
-#define T_AP20 TT_(AP20)
-#define T_ADPff0 TT_(ADPff0)
-#define T_ADPfr0 TT_(ADPfr0)
-#define T_ADPrf0 TT_(ADPrf0)
-#define T_ADPrr0 TT_(ADPrr0)
-#define T_ALP10 TT_(ALP10)
-#define T_ALP20 TT_(ALP20)
-#define T_ALPL0 TT_(ALPL0)
-#define T_ARP20 TT_(ARP20)
-#define T_ARPL0 TT_(ARPL0)
-#define T_ALB20 TT_(ALB20)
-#define T_ALBL0 TT_(ALBL0)
-#define T_ARB20 TT_(ARB20)
-#define T_ARBL0 TT_(ARBL0)
-#define T_ABQ20 TT_(ABQ20)
-#define T_APF20 TT_(APF20)
-#define T_ALI20 TT_(ALI20)
-#define T_ARIf0 TT_(ARIf0)
-#define T_ARI20 TT_(ARI20)
-#define T_ALIr0 TT_(ALIr0)
-#define T_C2LP20 TT_(C2LP20)
-#define T_C2LPL0 TT_(C2LPL0)
-#define T_C2RP20 TT_(C2RP20)
-#define T_C2RPL0 TT_(C2RPL0)
-#define T_C2LB20 TT_(C2LB20)
-#define T_C2LBL0 TT_(C2LBL0)
-#define T_C2RB20 TT_(C2RB20)
-#define T_C2RBL0 TT_(C2RBL0)
-#define T_C2BQ20 TT_(C2BQ20)
-#define T_C2LP00 TT_(C2LP00)
-#define T_C2RP00 TT_(C2RP00)
-#define T_BDPb0 ((int)TT_(BDPb0))
-#define T_BDPb1 ((int)TT_(BDPb1))
-#define T_BTAb0 ((int)TT_(BTAb0))
-#define T_BTAb1 ((int)TT_(BTAb1))
-#define T_BTBb0 ((int)TT_(BTBb0))
-#define T_BTBb1 ((int)TT_(BTBb1))
-#define T_CDP1b0 ((int)TT_(CDP1b0))
-#define T_CDP1b1 ((int)TT_(CDP1b1))
-#define T_CDP12b0 ((int)TT_(CDP12b0))
-#define T_CDP12b1 ((int)TT_(CDP12b1))
-#define T_CDP2b0 ((int)TT_(CDP2b0))
-#define T_CDP2b1 ((int)TT_(CDP2b1))
-#define T_CDP3b0 ((int)TT_(CDP3b0))
-#define T_CDP3b1 ((int)TT_(CDP3b1))
-#define T_DDP10 ((int)TT_(DDP10))
-#define f_a1BQf AL_(a1BQf)
-#define f_a1BQr AL_(a1BQr)
-#define f_bIAQb AL_(bIAQb)
-#define f_bIADb AL_(bIADb)
-#define f_cIAQf AL_(cIAQf)
-#define f_cIADf AL_(cIADf)
-#define f_cIDQf AL_(cIDQf)
-#define f_cIAQr AL_(cIAQr)
-#define f_cIADr AL_(cIADr)
-#define f_cIDQr AL_(cIDQr)
-#define f_aMQs AL_(aMQs)
-#define f_aP1 AL_(aP1)
-#define f_aP2 AL_(aP2)
-#define f_aDPff AL_(aDPff)
-#define f_aDPfr AL_(aDPfr)
-#define f_aDPrf AL_(aDPrf)
-#define f_aDPrr AL_(aDPrr)
-#define f_aLP1 AL_(aLP1)
-#define f_aLP2 AL_(aLP2)
-#define f_aRP1 AL_(aRP1)
-#define f_aRP2 AL_(aRP2)
-#define f_aLB1 AL_(aLB1)
-#define f_aLB2 AL_(aLB2)
-#define f_aRB1 AL_(aRB1)
-#define f_aRB2 AL_(aRB2)
-#define f_a2XM2 AL_(a2XM2)
-#define f_a2BM2 AL_(a2BM2)
-#define f_aBQ2 AL_(aBQ2)
-#define f_aPF1 AL_(aPF1)
-#define f_aPF2 AL_(aPF2)
-#define f_aLI1 AL_(aLI1)
-#define f_aLI2 AL_(aLI2)
-#define f_aLIr AL_(aLIr)
-#define f_aRI1 AL_(aRI1)
-#define f_aRI2 AL_(aRI2)
-#define f_aRIf AL_(aRIf)
-#define f_aP3 AL_(aP3)
-#define f_aNC AL_(aNC)
-#define f_bDPf AL_(bDPf)
-#define f_bTAf AL_(bTAf)
-#define f_bTBf AL_(bTBf)
-#define f_bDPr AL_(bDPr)
-#define f_bTAr AL_(bTAr)
-#define f_bTBr AL_(bTBr)
-#define f_cDP1f AL_(cDP1f)
-#define f_cDP12f AL_(cDP12f)
-#define f_cDP2f AL_(cDP2f)
-#define f_cDP3f AL_(cDP3f)
-#define f_cDPMf AL_(cDPMf)
-#define f_cDPmf AL_(cDPmf)
-#define f_cDP1r AL_(cDP1r)
-#define f_cDP12r AL_(cDP12r)
-#define f_cDP2r AL_(cDP2r)
-#define f_cDP3r AL_(cDP3r)
-#define f_cDPMr AL_(cDPMr)
-#define f_cDPmr AL_(cDPmr)
-#define f_c2LP1 AL_(c2LP1)
-#define f_c2LP2 AL_(c2LP2)
-#define f_c2RP1 AL_(c2RP1)
-#define f_c2RP2 AL_(c2RP2)
-#define f_c2LB1 AL_(c2LB1)
-#define f_c2LB2 AL_(c2LB2)
-#define f_c2RB1 AL_(c2RB1)
-#define f_c2RB2 AL_(c2RB2)
-#define f_c2BQ2 AL_(c2BQ2)
-#define f_c2LP0 AL_(c2LP0)
-#define f_c2RP0 AL_(c2RP0)
-#define f_dDP1 AL_(dDP1)
-#define f_dDP2 AL_(dDP2)
-#define f_aLPL ((long long)AL_(aLPL))
-#define f_aRPL ((long long)AL_(aRPL))
-#define f_c2LPL ((long long)AL_(c2LPL))
-#define f_c2RPL ((long long)AL_(c2RPL))
-#define f_aLBL AL64_(aLBL)
-#define f_aRBL AL64_(aRBL)
-#define f_aLIT AL64_(aLIT)
-#define f_aRIT AL64_(aRIT)
-#define f_c2LBL AL64_(c2LBL)
-#define f_c2RBL AL64_(c2RBL)
 // ---- chained scan (one launch): every block takes the next tile by ticket, publishes the tile's sum, and adds up its predecessors'.
 // A tile's state is ONE naturally aligned 8-byte word written by one agent-scope store and polled by agent-scope loads (nothing else is
 // handed between blocks), bits 63..62: 1 = sum of this tile, 2 = sum of all tiles up to and including this one; bits 61..0 the packed sums.
@@ -594,15 +393,6 @@ DEV int gate_count(const RegionDev &R, const UvcParams &P, const ScoreCtx &C, lo
     return n;
 }
 
-#define GS_BLOCK 256
-#define GS_ITEMS 8
-#define GS_TILE (GS_BLOCK * GS_ITEMS)
-// groups per thread of the gate (measured on the 1 Mb tile: 8 -> 58 us, 4 -> 69 us, 2 -> 84 us: more tiles cost more in tickets and look-back
-// than the shorter chains of dependent loads per thread give back)
-#ifndef GATE_ITEMS
-#define GATE_ITEMS 8
-#endif
-#define GATE_TILE (GS_BLOCK * GATE_ITEMS)
 // gate + record slots + active list in one launch.  offsets[g] = packed (number of active groups << 32 | number of records) in front of g.
 __global__ void __launch_bounds__(GS_BLOCK) k_gate_scan(RegionDev R, UvcParams P, ScoreCtx C, Stage S, long long *total_records) {
     __shared__ long long sh_cnt[GATE_TILE + GATE_TILE / 8];   // one pad word per 8: thread t reads 8 consecutive words, 9 apart from its neighbour's
@@ -799,18 +589,18 @@ DEV double rec_tpfa_dpv(const ScoreCtx &C, int src, int idx) { if (src != 2) ret
 #define DPV_COMMON \
     const bool tprov = P.tumor_vcf_is_provided; \
     const double unbias_ratio = (!tprov ? 1.0 : sqrt(2.0)); \
-    const int pcr_dp = (int)T_APDP5, a_dp = (int)T_APDP0, near_pcr_clip = (int)T_APDP9; \
+    const int pcr_dp = (int)TT_(APDP5), a_dp = (int)TT_(APDP0), near_pcr_clip = (int)TT_(APDP9); \
     const bool strong_amp = (pcr_dp * 100 > a_dp * 50), weak_amp = (pcr_dp * 100 > a_dp * 30); \
     const bool is_rescued = (tpfa >= 0);   /* main.hpp:4297-4298 */ \
     const double pfa = (is_rescued ? tpfa : 0.5), c2altpc = 0.025; \
-    const int ADP1 = (int)(T_ADPff0 + T_ADPfr0 + T_ADPrf0 + T_ADPrr0); \
-    const int aDP = (f_aDPff + f_aDPfr + f_aDPrf + f_aDPrr); \
+    const int ADP1 = (int)(TT_(ADPff0) + TT_(ADPfr0) + TT_(ADPrf0) + TT_(ADPrr0)); \
+    const int aDP = (AL_(aDPff) + AL_(aDPfr) + AL_(aDPrf) + AL_(aDPrr)); \
     const int ADP = imax(ADP1, near_pcr_clip); \
-    const int cDP1 = f_cDP1f + f_cDP1r, CDP1 = T_CDP1b0 + T_CDP1b1; \
-    const int sumCDP2 = T_CDP2b0 + T_CDP2b1, sumCDP1 = CDP1; \
+    const int cDP1 = AL_(cDP1f) + AL_(cDP1r), CDP1 = TT_(CDP1b0) + TT_(CDP1b1); \
+    const int sumCDP2 = TT_(CDP2b0) + TT_(CDP2b1), sumCDP1 = CDP1; \
     const bool nmore_amp = (!tprov ? strong_amp : weak_amp), tmore_amp = (!tprov ? weak_amp : strong_amp); \
-    const int normCDP1 = (T_CDP12b0 + T_CDP12b1) + 1, normBDP = (T_BDPb0 + T_BDPb1) + 1; \
-    const int c2DP = f_cDP2f + f_cDP2r;
+    const int normCDP1 = (TT_(CDP12b0) + TT_(CDP12b1)) + 1, normBDP = (TT_(BDPb0) + TT_(BDPb1)) + 1; \
+    const int c2DP = AL_(cDP2f) + AL_(cDP2r);
 
 // BcfFormat_symbol_init's derived values (fill_symbol_VQ_fmts, main.hpp:3820-3887) + BcfFormat_symbol_calc_DPv (main.hpp:4274-4844) up to its contingency tests
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))) k_dpv_pre(UvcParams P, ScoreCtx C, Stage S) {
@@ -838,8 +628,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     int f_bMQ, f_aBQQ, f_aBQ;
     {   // fill_symbol_VQ_fmts
         const int a2BQf = AL_(v2BQf), a2BQr = AL_(v2BQr);
-    const int aDPf = f_aDPff + f_aDPrf, aDPr = f_aDPfr + f_aDPrr;
-    const int ADP = (int)(T_ADPff0 + T_ADPrf0 + T_ADPfr0 + T_ADPrr0);
+    const int aDPf = AL_(aDPff) + AL_(aDPrf), aDPr = AL_(aDPfr) + AL_(aDPrr);
+    const int ADP = (int)(TT_(ADPff0) + TT_(ADPrf0) + TT_(ADPfr0) + TT_(ADPrr0));
     const int rssf = (int)(aDPf * sqrt((double)(((long long)a2BQf * SQR_QUAL_DIV) / imax(1, aDPf))));
     const int rssr = (int)(aDPr * sqrt((double)(((long long)a2BQr * SQR_QUAL_DIV) / imax(1, aDPr))));
     const int rssb = (int)((aDPf + aDPr) * sqrt((double)((a2BQf + a2BQr) * SQR_QUAL_DIV / imax(1, aDPf + aDPr))));
@@ -847,8 +637,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     int minABQa = minABQ - (int)(5 * 10.0 * (t * t));
     const double sbratio = (double)(imax(aDPf, aDPr) * 10 + 10) / (double)(imin(aDPf, aDPr) * 10 + 10);
     minABQa += ibetween((int)(sbratio * sbratio) - P.syserr_BQ_sbratio_q_add, 0, P.syserr_BQ_sbratio_q_max);
-    const int xmratio = (P.syserr_BQ_xmratio_q_max * 10 * (aDPf + aDPr) / imax(1, f_a2XM2));
-    const int bmratio = (P.syserr_BQ_bmratio_q_max * 10 * (aDPf + aDPr) / imax(1, f_a2BM2));
+    const int xmratio = (P.syserr_BQ_xmratio_q_max * 10 * (aDPf + aDPr) / imax(1, AL_(a2XM2)));
+    const int bmratio = (P.syserr_BQ_bmratio_q_max * 10 * (aDPf + aDPr) / imax(1, AL_(a2BM2)));
     minABQa += ibetween(xmratio - P.syserr_BQ_xmratio_q_add, 0, P.syserr_BQ_xmratio_q_max) + ibetween(bmratio - P.syserr_BQ_bmratio_q_add, 0, P.syserr_BQ_bmratio_q_max);
     const int m = P.syserr_BQ_strand_favor_mul;
     const int q_fw = (rssf * m - minABQa * aDPf * m / 10 + rssr - minABQa * aDPr / 10) / m;
@@ -856,13 +646,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int q_2d = rssb - minABQa * (aDPf + aDPr) / 10;
     const int a_rmsBQ = rssb / imax(1, aDPf + aDPr);
         const int bMQraw = AL_(vbMQ);
-    f_bMQ = (int)round(sqrt((double)(((long long)bMQraw * SQR_QUAL_DIV) / imax(f_bDPf + f_bDPr, 1))) + (double)(1.0 - FLT_EPS));
+    f_bMQ = (int)round(sqrt((double)(((long long)bMQraw * SQR_QUAL_DIV) / imax(AL_(bDPf) + AL_(bDPr), 1))) + (double)(1.0 - FLT_EPS));
     f_aBQQ = imax(a_rmsBQ, P.syserr_BQ_prior + imax(q_2d, imax(q_fw, q_rv)));
         f_aBQ = a_rmsBQ;
         FO_(a2BQf) = rssf; FO_(a2BQr) = rssr; FO_(aBQ) = a_rmsBQ; FO_(aBQQ) = f_aBQQ; FO_(bMQ) = f_bMQ;
     }
     FO_(refpos) = refpos; FO_(symbol) = symbol; FO_(refsymbol) = refsymbol;
-    FO_(DP) = T_CDP1b0 + T_CDP1b1; FO_(bDP) = T_BDPb0 + T_BDPb1; FO_(c2DP) = T_CDP2b0 + T_CDP2b1; FO_(c2AD) = f_cDP2f + f_cDP2r;
+    FO_(DP) = TT_(CDP1b0) + TT_(CDP1b1); FO_(bDP) = TT_(BDPb0) + TT_(BDPb1); FO_(c2DP) = TT_(CDP2b0) + TT_(CDP2b1); FO_(c2AD) = AL_(cDP2f) + AL_(cDP2r);
     FO_(bDPa) = bDPa; FO_(cDP0a) = cDP0a; FO_(gapSa) = gap_row; FO_(gapSa_len) = glen; FO_(tkey) = tkey_idx;
     // ---- calc_DPv ----
     DPV_COMMON
@@ -870,38 +660,38 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int allprior = (!tprov ? 0 : 31);
     double cbP = 1e-9, cbBQ = 1e-9, dir_bias_div = 1.0;
     if ((nmore_amp && (0x2 == (0x2 & P.nobias_flag))) || ((!nmore_amp) && (0x1 == (0x1 & P.nobias_flag)))) {
-        const double oddsA_bias = prob2odds((aDP - f_aP1 + 0.5) / (ADP - T_AP10 + 1.0));
-        const double oddsA_nobias = prob2odds((f_aP1 + 0.5) / (T_AP10 + 1.0));
+        const double oddsA_bias = prob2odds((aDP - AL_(aP1) + 0.5) / (ADP - TT_(AP10) + 1.0));
+        const double oddsA_nobias = prob2odds((AL_(aP1) + 0.5) / (TT_(AP10) + 1.0));
         const bool pos_cb = ((oddsA_bias * P.microadjust_counterbias_pos_odds_ratio < oddsA_nobias * (unbias_ratio - DBL_EPS))
-                && (f_aP1 * (unbias_ratio - DBL_EPS) > aDP - f_aP1)
-                && ((ADP - T_AP10) * P.microadjust_counterbias_pos_fold_ratio * (unbias_ratio - DBL_EPS) > T_AP10)
+                && (AL_(aP1) * (unbias_ratio - DBL_EPS) > aDP - AL_(aP1))
+                && ((ADP - TT_(AP10)) * P.microadjust_counterbias_pos_fold_ratio * (unbias_ratio - DBL_EPS) > TT_(AP10))
                 && ((0 == P.primerlen && 0 != P.primerlen2) || !is_subst(symbol)));
-        if (pos_cb) cbP = dmax(cbP, (f_aP1 + 0.5) / (lmax(T_AP10, (long long)near_pcr_clip) + 1.0)); else cbP = dmax(cbP, 2e-9);
+        if (pos_cb) cbP = dmax(cbP, (AL_(aP1) + 0.5) / (lmax(TT_(AP10), (long long)near_pcr_clip) + 1.0)); else cbP = dmax(cbP, 2e-9);
         if (is_subst(symbol)) {
-            const bool f_good = ((T_ADPfr0 + T_ADPrr0) + 150 <= (T_ADPff0 + T_ADPrf0) * 5 * unbias_ratio);
-            const bool r_good = ((T_ADPff0 + T_ADPrf0) + 150 <= (T_ADPfr0 + T_ADPrr0) * 5 * unbias_ratio);
-            const int avg_f_aBQ = (f_a1BQf / imax(1, f_aDPff + f_aDPrf)), avg_r_aBQ = (f_a1BQr / imax(1, f_aDPfr + f_aDPrr));
-            const int avg_f_ABQ = (int)(T_A1BQf0 / lmax(1, T_ADPff0 + T_ADPrf0)), avg_r_ABQ = (int)(T_A1BQr0 / lmax(1, T_ADPfr0 + T_ADPrr0));
-            if ((f_a1BQf >= f_a1BQr) && (f_good && r_good) && (avg_f_aBQ + unbias_qualadd >= avg_r_ABQ + 14) && (avg_r_ABQ <= 14 + unbias_qualadd))
-                cbBQ = dmax(cbBQ, (f_aDPff + f_aDPrf + 0.5) / (T_ADPff0 + T_ADPrf0 + 1.0));
-            if ((f_a1BQr >= f_a1BQf) && (f_good && r_good) && (avg_r_aBQ + unbias_qualadd >= avg_f_ABQ + 14) && (avg_f_ABQ <= 14 + unbias_qualadd))
-                cbBQ = dmax(cbBQ, (f_aDPfr + f_aDPrr + 0.5) / (T_ADPfr0 + T_ADPrr0 + 1.0));
+            const bool f_good = ((TT_(ADPfr0) + TT_(ADPrr0)) + 150 <= (TT_(ADPff0) + TT_(ADPrf0)) * 5 * unbias_ratio);
+            const bool r_good = ((TT_(ADPff0) + TT_(ADPrf0)) + 150 <= (TT_(ADPfr0) + TT_(ADPrr0)) * 5 * unbias_ratio);
+            const int avg_f_aBQ = (AL_(a1BQf) / imax(1, AL_(aDPff) + AL_(aDPrf))), avg_r_aBQ = (AL_(a1BQr) / imax(1, AL_(aDPfr) + AL_(aDPrr)));
+            const int avg_f_ABQ = (int)(TT_(A1BQf0) / lmax(1, TT_(ADPff0) + TT_(ADPrf0))), avg_r_ABQ = (int)(TT_(A1BQr0) / lmax(1, TT_(ADPfr0) + TT_(ADPrr0)));
+            if ((AL_(a1BQf) >= AL_(a1BQr)) && (f_good && r_good) && (avg_f_aBQ + unbias_qualadd >= avg_r_ABQ + 14) && (avg_r_ABQ <= 14 + unbias_qualadd))
+                cbBQ = dmax(cbBQ, (AL_(aDPff) + AL_(aDPrf) + 0.5) / (TT_(ADPff0) + TT_(ADPrf0) + 1.0));
+            if ((AL_(a1BQr) >= AL_(a1BQf)) && (f_good && r_good) && (avg_r_aBQ + unbias_qualadd >= avg_f_ABQ + 14) && (avg_f_ABQ <= 14 + unbias_qualadd))
+                cbBQ = dmax(cbBQ, (AL_(aDPfr) + AL_(aDPrr) + 0.5) / (TT_(ADPfr0) + TT_(ADPrr0) + 1.0));
         } else dir_bias_div = (1.0 + (unsigned)f_gap_len / (unsigned)P.indel_str_repeatsize_max);
     }
-    const long long aDPgap = nnminus(lmax(T_APDP1, T_APDP2), f_aP3);
-    const double aDPFAgap = ((rtr1.tracklen + rtr2.tracklen < P.indel_str_repeatsize_max) ? 1.0 : ((f_aP3 + pfa) / (aDPgap + 1.0)));
+    const long long aDPgap = nnminus(lmax(TT_(APDP1), TT_(APDP2)), AL_(aP3));
+    const double aDPFAgap = ((rtr1.tracklen + rtr2.tracklen < P.indel_str_repeatsize_max) ? 1.0 : ((AL_(aP3) + pfa) / (aDPgap + 1.0)));
     const double aDPFA1 = ((aDP + pfa) / (ADP + 1.0));
-    const double labelFA = (f_aP2 + 1.5 + f_aP2) / (T_AP20 + 2.0 + f_aP2);
-    const double aDPFA = dmin((is_subst(symbol) ? dmin(aDPFA1, dmax(aDPFA1 / 3, aDPFAgap)) : aDPFA1), labelFA * (ADP + 1.0) / (T_AP20 + 0.5) * unbias_ratio);
+    const double labelFA = (AL_(aP2) + 1.5 + AL_(aP2)) / (TT_(AP20) + 2.0 + AL_(aP2));
+    const double aDPFA = dmin((is_subst(symbol) ? dmin(aDPFA1, dmax(aDPFA1 / 3, aDPFAgap)) : aDPFA1), labelFA * (ADP + 1.0) / (TT_(AP20) + 0.5) * unbias_ratio);
     const int aDPplus = (is_subst(symbol) ? 0 : ((aDP + 1) * P.bias_prior_DPadd_perc / 100));
-    const double dp_coef = ((symbol == UVC_LINK_M) ? dmax(P.contam_any_mul_frac, 1.0 - imax(rtr1.tracklen, rtr2.tracklen) / (lmax(1, lmax(T_ALPL0, T_ARPL0)) / dmax(1.0 / 150.0, (double)T_ABQ20))) : 1.0);
+    const double dp_coef = ((symbol == UVC_LINK_M) ? dmax(P.contam_any_mul_frac, 1.0 - imax(rtr1.tracklen, rtr2.tracklen) / (lmax(1, lmax(TT_(ALPL0), TT_(ARPL0))) / dmax(1.0 / 150.0, (double)TT_(ABQ20)))) : 1.0);
     double aPprior = P.bias_priorfreq_pos, aBprior = P.bias_priorfreq_pos;
-    const bool in_indel_read = ((T_APXM1) / 15.0 * P.microadjust_bias_pos_indel_fold * (P.bias_prior_var_DP_mul) > (aDP + aDPplus) * dp_coef);
-    const bool in_indel_len = (lmax(T_APDP1, T_APDP2) * (P.bias_prior_var_DP_mul) > (aDP + aDPplus) * dp_coef);
-    const bool in_indel_rtr = (lmax(T_APDP3, T_APDP4) * (P.bias_prior_var_DP_mul) > (aDP + aDPplus) * dp_coef);
+    const bool in_indel_read = ((TT_(APXM1)) / 15.0 * P.microadjust_bias_pos_indel_fold * (P.bias_prior_var_DP_mul) > (aDP + aDPplus) * dp_coef);
+    const bool in_indel_len = (lmax(TT_(APDP1), TT_(APDP2)) * (P.bias_prior_var_DP_mul) > (aDP + aDPplus) * dp_coef);
+    const bool in_indel_rtr = (lmax(TT_(APDP3), TT_(APDP4)) * (P.bias_prior_var_DP_mul) > (aDP + aDPplus) * dp_coef);
     const bool in_rtr = (imax(rtr1.tracklen, rtr2.tracklen) > round(P.indel_polymerase_size));
-    const bool in_dnv_read = ((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) && (T_APDP7 * 2 > T_APDP6));
-    if (in_indel_read || in_dnv_read || ((is_ins(symbol) || is_del(symbol)) && (T_APXM0 > T_APXM1 * P.microadjust_bias_pos_indel_misma_to_indel_ratio))) {
+    const bool in_dnv_read = ((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) && (TT_(APDP7) * 2 > TT_(APDP6)));
+    if (in_indel_read || in_dnv_read || ((is_ins(symbol) || is_del(symbol)) && (TT_(APXM0) > TT_(APXM1) * P.microadjust_bias_pos_indel_misma_to_indel_ratio))) {
         aPprior -= P.bias_priorfreq_indel_in_read_div; aBprior -= P.bias_priorfreq_indel_in_read_div;
     }
     if (UVC_LINK_M != symbol && UVC_LINK_NN != symbol) {
@@ -922,10 +712,10 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const double dedup_a2c1 = dmin(1.0, (double)imax(cDP1, P.bias_reduction_by_high_sequencingDP_min_n_altDepth) / (double)imax(aDP, 1));
     const double dff = dmax(dedup_A2C1, dedup_a2c1);
     const double pc_read = (in_indel_read ? P.bias_FA_pseudocount_indel_in_read : 0.5);
-    const int f_tier2 = (is_rescued ? (tki_tier2 ? 1 : 0) : (((c2DP >= 2) && (normBDP * P.fam_bias_overseq_perc >= normCDP1 * 100) && (T_APDP11 * 100 > (long long)a_dp * 50)) ? 1 : 0));   // main.hpp:4475
+    const int f_tier2 = (is_rescued ? (tki_tier2 ? 1 : 0) : (((c2DP >= 2) && (normBDP * P.fam_bias_overseq_perc >= normCDP1 * 100) && (TT_(APDP11) * 100 > (long long)a_dp * 50)) ? 1 : 0));   // main.hpp:4475
     FO_(tier2) = f_tier2;
-    const double cFA2L = (f_tier2 ? (((double)(((long long)f_c2LP0 * f_c2LP0) * 2 / lmax(1, (long long)imin(c2DP, f_c2LP0 * 4))) + c2altpc) / (T_C2LP00 + 1.0)) : 1.0);
-    const double cFA2R = (f_tier2 ? (((double)(((long long)f_c2RP0 * f_c2RP0) * 2 / lmax(1, (long long)imin(c2DP, f_c2RP0 * 4))) + c2altpc) / (T_C2RP00 + 1.0)) : 1.0);
+    const double cFA2L = (f_tier2 ? (((double)(((long long)AL_(c2LP0) * AL_(c2LP0)) * 2 / lmax(1, (long long)imin(c2DP, AL_(c2LP0) * 4))) + c2altpc) / (TT_(C2LP00) + 1.0)) : 1.0);
+    const double cFA2R = (f_tier2 ? (((double)(((long long)AL_(c2RP0) * AL_(c2RP0)) * 2 / lmax(1, (long long)imin(c2DP, AL_(c2RP0) * 4))) + c2altpc) / (TT_(C2RP00) + 1.0)) : 1.0);
     const double ori_base = (is_subst(symbol) ? P.bias_priorfreq_orientation_snv_base : P.bias_priorfreq_orientation_indel_base) + allprior;
     const double te = dmax(aDPFA, P.bias_orientation_min_effective_allelefrac);
     const double ori_all = log(te * te) + phred2nat(ori_base);
@@ -942,8 +732,8 @@ __global__ void __launch_bounds__(64 * DP4_WAVES) __attribute__((amdgpu_waves_pe
     if (rec >= (long long)S.cnt[CNT_nvalid]) return;
     const long long gi = RH_(gi, rec);
     int32_t *fields = C.fields; const long long capacity = C.capacity;
-    const int aDP = (f_aDPff + f_aDPfr + f_aDPrf + f_aDPrr);
-    const int ADP = imax((int)(T_ADPff0 + T_ADPfr0 + T_ADPrf0 + T_ADPrr0), (int)T_APDP9);
+    const int aDP = (AL_(aDPff) + AL_(aDPfr) + AL_(aDPrf) + AL_(aDPrr));
+    const int ADP = imax((int)(TT_(ADPff0) + TT_(ADPfr0) + TT_(ADPrf0) + TT_(ADPrr0)), (int)TT_(APDP9));
     const double dff = MID_(dff, rec), pl = P.powlaw_exponent, c2altpc = 0.025;
     {   // (no loop over the wave's two tests -- blockIdx.y picks the half: hoisted per-field addresses of both iterations spilled 106 registers)
         const int t = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + DP4_WAVES * (int)blockIdx.y;
@@ -952,39 +742,39 @@ __global__ void __launch_bounds__(64 * DP4_WAVES) __attribute__((amdgpu_waves_pe
         double a1 = 0, a2 = 0, d1 = 0, d2 = 0, nats = 0, k1 = -1, k2 = -1, pa = 0.5, pd = 1.0;
         switch (t) {
         case 0: case 1: case 2: case 3: {   // position / BAQ bias of the read ends
-            const double aBQ2d = (double)imax(1, f_aBQ2), ABQ2d = (double)lmax(1, T_ABQ20);
+            const double aBQ2d = (double)imax(1, AL_(aBQ2)), ABQ2d = (double)lmax(1, TT_(ABQ20));
             a2 = aDP; d2 = ADP; pa = MID_(pcread, rec);
-            if (t == 0) { a1 = f_aLP1; d1 = T_ALP20 + f_aLP1 - f_aLP2; nats = phred2nat(MID_(aPprior, rec)); k1 = lmax(1, f_aLPL) / aBQ2d; k2 = lmax(1, T_ALPL0) / ABQ2d; }
-            else if (t == 1) { a1 = f_aRP1; d1 = T_ARP20 + f_aRP1 - f_aRP2; nats = phred2nat(MID_(aPprior, rec)); k1 = lmax(1, f_aRPL) / aBQ2d; k2 = lmax(1, T_ARPL0) / ABQ2d; }
-            else if (t == 2) { a1 = f_aLB1; d1 = T_ALB20 + f_aLB1 - f_aLB2; nats = phred2nat(MID_(aBprior, rec)); k1 = lmax(1, f_aLBL) / aBQ2d; k2 = lmax(1, T_ALBL0) / ABQ2d; }
-            else { a1 = f_aRB1; d1 = T_ARB20 + f_aRB1 - f_aRB2; nats = phred2nat(MID_(aBprior, rec)); k1 = lmax(1, f_aRBL) / aBQ2d; k2 = lmax(1, T_ARBL0) / ABQ2d; }
+            if (t == 0) { a1 = AL_(aLP1); d1 = TT_(ALP20) + AL_(aLP1) - AL_(aLP2); nats = phred2nat(MID_(aPprior, rec)); k1 = lmax(1, AL_(aLPL)) / aBQ2d; k2 = lmax(1, TT_(ALPL0)) / ABQ2d; }
+            else if (t == 1) { a1 = AL_(aRP1); d1 = TT_(ARP20) + AL_(aRP1) - AL_(aRP2); nats = phred2nat(MID_(aPprior, rec)); k1 = lmax(1, AL_(aRPL)) / aBQ2d; k2 = lmax(1, TT_(ARPL0)) / ABQ2d; }
+            else if (t == 2) { a1 = AL_(aLB1); d1 = TT_(ALB20) + AL_(aLB1) - AL_(aLB2); nats = phred2nat(MID_(aBprior, rec)); k1 = lmax(1, AL64_(aLBL)) / aBQ2d; k2 = lmax(1, TT_(ALBL0)) / ABQ2d; }
+            else { a1 = AL_(aRB1); d1 = TT_(ARB20) + AL_(aRB1) - AL_(aRB2); nats = phred2nat(MID_(aBprior, rec)); k1 = lmax(1, AL64_(aRBL)) / aBQ2d; k2 = lmax(1, TT_(ARBL0)) / ABQ2d; }
         } break;
         case 4: case 5: case 6: case 7: {   // the same on the tier-2 families
             if (!FO_(tier2)) { skip = true; break; }   // (the results stay 1.0)
-            const int c2DP = f_cDP2f + f_cDP2r, sumCDP2 = T_CDP2b0 + T_CDP2b1;
+            const int c2DP = AL_(cDP2f) + AL_(cDP2r), sumCDP2 = TT_(CDP2b0) + TT_(CDP2b1);
             const double c2Pp = dmax(0.0, MID_(aPprior, rec)), c2Bp = dmax(0.0, MID_(aBprior, rec));
-            const double cb = (double)imax(1, f_c2BQ2), CB = (double)lmax(1, T_C2BQ20);
+            const double cb = (double)imax(1, AL_(c2BQ2)), CB = (double)lmax(1, TT_(C2BQ20));
             noseq = true; a2 = c2DP; d2 = sumCDP2; pa = c2altpc; pd = 1.0;
-            if (t == 4) { a1 = f_c2LP1; d1 = T_C2LP20 + f_c2LP1 - f_c2LP2; nats = phred2nat(c2Pp); k1 = lmax(1, f_c2LPL) / cb; k2 = lmax(1, T_C2LPL0) / CB; }
-            else if (t == 5) { a1 = f_c2RP1; d1 = T_C2RP20 + f_c2RP1 - f_c2RP2; nats = phred2nat(c2Pp); k1 = lmax(1, f_c2RPL) / cb; k2 = lmax(1, T_C2RPL0) / CB; }
-            else if (t == 6) { a1 = f_c2LB1; d1 = T_C2LB20 + f_c2LB1 - f_c2LB2; nats = phred2nat(c2Bp); k1 = lmax(1, f_c2LBL) / cb; k2 = lmax(1, T_C2LBL0) / CB; }
-            else { a1 = f_c2RB1; d1 = T_C2RB20 + f_c2RB1 - f_c2RB2; nats = phred2nat(c2Bp); k1 = lmax(1, f_c2RBL) / cb; k2 = lmax(1, T_C2RBL0) / CB; }
+            if (t == 4) { a1 = AL_(c2LP1); d1 = TT_(C2LP20) + AL_(c2LP1) - AL_(c2LP2); nats = phred2nat(c2Pp); k1 = lmax(1, AL_(c2LPL)) / cb; k2 = lmax(1, TT_(C2LPL0)) / CB; }
+            else if (t == 5) { a1 = AL_(c2RP1); d1 = TT_(C2RP20) + AL_(c2RP1) - AL_(c2RP2); nats = phred2nat(c2Pp); k1 = lmax(1, AL_(c2RPL)) / cb; k2 = lmax(1, TT_(C2RPL0)) / CB; }
+            else if (t == 6) { a1 = AL_(c2LB1); d1 = TT_(C2LB20) + AL_(c2LB1) - AL_(c2LB2); nats = phred2nat(c2Bp); k1 = lmax(1, AL64_(c2LBL)) / cb; k2 = lmax(1, TT_(C2LBL0)) / CB; }
+            else { a1 = AL_(c2RB1); d1 = TT_(C2RB20) + AL_(c2RB1) - AL_(c2RB2); nats = phred2nat(c2Bp); k1 = lmax(1, AL64_(c2RBL)) / cb; k2 = lmax(1, TT_(C2RBL0)) / CB; }
         } break;
         case 8: {
-            const double ALpd = (T_ALI20 + 0.5) / (T_ADPfr0 + T_ADPrr0 - T_ALI20 + 0.5);
-            const double aLpd = (f_aLI1 + ALpd / (1.0 + ALpd)) / (f_aDPfr + f_aDPrr - f_aLI1 + 1.0 / (1.0 + ALpd));
-            a1 = f_aLI1; a2 = (f_aDPfr + f_aDPrr); d1 = (T_ALI20 + f_aLI1 - f_aLI2); d2 = (T_ADPfr0 + T_ADPrr0); nats = phred2nat(MID_(aIprior, rec)); k1 = aLpd; k2 = ALpd; pa = 0.25; pd = 0.5;
+            const double ALpd = (TT_(ALI20) + 0.5) / (TT_(ADPfr0) + TT_(ADPrr0) - TT_(ALI20) + 0.5);
+            const double aLpd = (AL_(aLI1) + ALpd / (1.0 + ALpd)) / (AL_(aDPfr) + AL_(aDPrr) - AL_(aLI1) + 1.0 / (1.0 + ALpd));
+            a1 = AL_(aLI1); a2 = (AL_(aDPfr) + AL_(aDPrr)); d1 = (TT_(ALI20) + AL_(aLI1) - AL_(aLI2)); d2 = (TT_(ADPfr0) + TT_(ADPrr0)); nats = phred2nat(MID_(aIprior, rec)); k1 = aLpd; k2 = ALpd; pa = 0.25; pd = 0.5;
         } break;
         case 9: {
-            const double ARpd = (T_ARI20 + 0.5) / (T_ADPff0 + T_ADPrf0 - T_ARI20 + 0.5);
-            const double aRpd = (f_aRI1 + ARpd / (1.0 + ARpd)) / (f_aDPff + f_aDPrf - f_aRI1 + 1.0 / (1.0 + ARpd));
-            a1 = f_aRI1; a2 = (f_aDPff + f_aDPrf); d1 = (T_ARI20 + f_aRI1 - f_aRI2); d2 = (T_ADPff0 + T_ADPrf0); nats = phred2nat(MID_(aIprior, rec)); k1 = aRpd; k2 = ARpd; pa = 0.25; pd = 0.5;
+            const double ARpd = (TT_(ARI20) + 0.5) / (TT_(ADPff0) + TT_(ADPrf0) - TT_(ARI20) + 0.5);
+            const double aRpd = (AL_(aRI1) + ARpd / (1.0 + ARpd)) / (AL_(aDPff) + AL_(aDPrf) - AL_(aRI1) + 1.0 / (1.0 + ARpd));
+            a1 = AL_(aRI1); a2 = (AL_(aDPff) + AL_(aDPrf)); d1 = (TT_(ARI20) + AL_(aRI1) - AL_(aRI2)); d2 = (TT_(ADPff0) + TT_(ADPrf0)); nats = phred2nat(MID_(aIprior, rec)); k1 = aRpd; k2 = ARpd; pa = 0.25; pd = 0.5;
         } break;
-        case 10: bidir = true; a1 = f_aRIf; a2 = f_aLIr; d1 = T_ARIf0; d2 = T_ALIr0; nats = phred2nat(MID_(aSBprior, rec)); break;
-        case 11: bidir = true; a1 = f_cDP1f; a2 = f_cDP1r; d1 = T_CDP1b0; d2 = T_CDP1b1; nats = MID_(oriall, rec); break;
+        case 10: bidir = true; a1 = AL_(aRIf); a2 = AL_(aLIr); d1 = TT_(ARIf0); d2 = TT_(ALIr0); nats = phred2nat(MID_(aSBprior, rec)); break;
+        case 11: bidir = true; a1 = AL_(cDP1f); a2 = AL_(cDP1r); d1 = TT_(CDP1b0); d2 = TT_(CDP1b1); nats = MID_(oriall, rec); break;
         case 12: if (!P.bias_is_orientation_artifact_mixed_with_sequencing_error) { skip = true; break; }
-                 bidir = true; a1 = f_cDP12f; a2 = f_cDP12r; d1 = T_CDP12b0; d2 = T_CDP12b1; nats = MID_(oriall, rec); break;
-        default: bidir = true; noseq = true; a1 = f_cDP2f; a2 = f_cDP2r; d1 = T_CDP2b0; d2 = T_CDP2b1; nats = MID_(oriall, rec); pa = c2altpc; pd = 1.0; break;
+                 bidir = true; a1 = AL_(cDP12f); a2 = AL_(cDP12r); d1 = TT_(CDP12b0); d2 = TT_(CDP12b1); nats = MID_(oriall, rec); break;
+        default: bidir = true; noseq = true; a1 = AL_(cDP2f); a2 = AL_(cDP2r); d1 = TT_(CDP2b0); d2 = TT_(CDP2b1); nats = MID_(oriall, rec); pa = c2altpc; pd = 1.0; break;
         }
         double r2[2] = { 1.0, 1.0 };
         if (!skip) dp4(r2, bidir, noseq, dff, a1, a2, d1, d2, pl, nats, k1, k2, pa, pd);
@@ -992,17 +782,17 @@ __global__ void __launch_bounds__(64 * DP4_WAVES) __attribute__((amdgpu_waves_pe
     }
 }
 
-#define SHORT_FRAG(wgs_min) ((T_APLRI0 + T_APLRI2) < (T_APLRI1 + T_APLRI3) * (long long)(wgs_min))   // does_fmt_imply_short_frag, main.hpp:169-174
+#define SHORT_FRAG(wgs_min) ((TT_(APLRI0) + TT_(APLRI2)) < (TT_(APLRI1) + TT_(APLRI3)) * (long long)(wgs_min))   // does_fmt_imply_short_frag, main.hpp:169-174
 // BcfFormat_symbol_calc_DPv behind its contingency tests: the bias-reduced allele fractions, their minima, FTS, cDP1v .. cDP2x (main.hpp:4409-4844)
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))) k_dpv_post(UvcParams P, ScoreCtx C, Stage S) {
     REC_PROLOGUE
     const double tpfa = rec_tpfa_dpv(C, RH_(src, rec), RH_(idx, rec));
     DPV_COMMON
     const int f_symbol = symbol, f_gap_len = FO_(gapSa_len), f_bDPa = FO_(bDPa), f_cDP0a = FO_(cDP0a), f_tier2 = FO_(tier2), f_bMQ = FO_(bMQ);
-    int f_AD = f_cDP1f + f_cDP1r, f_bAD = f_bDPf + f_bDPr;
+    int f_AD = AL_(cDP1f) + AL_(cDP1r), f_bAD = AL_(bDPf) + AL_(bDPr);
     int f_bNMQ, f_cDP1v, f_cDP1w, f_cDP1x, f_cDP2v, f_cDP2w, f_cDP2x;
-    const double cFA2 = (f_cDP2f + f_cDP2r + c2altpc) / (sumCDP2 + 1.0);
-    const double cFA3 = (f_cDP3f + f_cDP3r + c2altpc) / ((T_CDP3b0 + T_CDP3b1) + 1.0);
+    const double cFA2 = (AL_(cDP2f) + AL_(cDP2r) + c2altpc) / (sumCDP2 + 1.0);
+    const double cFA3 = (AL_(cDP3f) + AL_(cDP3r) + c2altpc) / ((TT_(CDP3b0) + TT_(CDP3b1)) + 1.0);
     const double cbP = MID_(cbP, rec), cbBQ = MID_(cbBQ, rec), dir_bias_div = MID_(dirdiv, rec), aDPFA = MID_(aDPFA, rec), cFA2L = MID_(cFA2L, rec), cFA2R = MID_(cFA2R, rec);
     double aLPFA = D4_(0, 0, rec), aRPFA = D4_(1, 0, rec), aLBFA = D4_(2, 0, rec), aRBFA = D4_(3, 0, rec);
     double c2LPFA = D4_(4, 0, rec), c2RPFA = D4_(5, 0, rec), c2LBFA = D4_(6, 0, rec), c2RBFA = D4_(7, 0, rec);   // 1.0 without tier 2
@@ -1010,51 +800,51 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     double RO1[2] = { D4_(11, 0, rec), D4_(11, 1, rec) };
     const double RO2[2] = { D4_(13, 0, rec), D4_(13, 1, rec) };
     if (P.bias_is_orientation_artifact_mixed_with_sequencing_error) {
-        if ((T_ADPff0 * 8 >= ADP) && (T_ADPfr0 * 8 >= ADP) && (T_ADPrf0 * 8 >= ADP) && (T_ADPrr0 * 8 >= ADP)) { RO1[0] = D4_(12, 0, rec); RO1[1] = D4_(12, 1, rec); }
+        if ((TT_(ADPff0) * 8 >= ADP) && (TT_(ADPfr0) * 8 >= ADP) && (TT_(ADPrf0) * 8 >= ADP) && (TT_(ADPrr0) * 8 >= ADP)) { RO1[0] = D4_(12, 0, rec); RO1[1] = D4_(12, 1, rec); }
     }
     double aLIFA = LI2[0] * (tmore_amp ? dir_bias_div : dmax(dir_bias_div, aDPFA / LI2[1]));
     double aRIFA = RI2[0] * (tmore_amp ? dir_bias_div : dmax(dir_bias_div, aDPFA / RI2[1]));
-    const double aSIFA = dmax((f_aLI1 + 0.5) / (T_ALI20 + f_aLI1 - f_aLI2 + 1.0), (f_aRI1 + 0.5) / (T_ARI20 + f_aRI1 - f_aRI2 + 1.0));
+    const double aSIFA = dmax((AL_(aLI1) + 0.5) / (TT_(ALI20) + AL_(aLI1) - AL_(aLI2) + 1.0), (AL_(aRI1) + 0.5) / (TT_(ARI20) + AL_(aRI1) - AL_(aRI2) + 1.0));
     const int indel_size = f_gap_len;
     if (is_ins(symbol) || is_del(symbol)) {
-        const double coef = imax(1, f_bDPa) / (double)imax(1, f_bDPf + f_bDPr);
-        const bool major_reg = ((lmax(T_APDP1, T_APDP3) + lmax(T_APDP2, T_APDP4)) * 0.5 * (1.0 + (double)FLT_EPS) < aDP * coef);
+        const double coef = imax(1, f_bDPa) / (double)imax(1, AL_(bDPf) + AL_(bDPr));
+        const bool major_reg = ((lmax(TT_(APDP1), TT_(APDP3)) + lmax(TT_(APDP2), TT_(APDP4))) * 0.5 * (1.0 + (double)FLT_EPS) < aDP * coef);
         if ((imin(indel_size, P.microadjust_nobias_pos_indel_maxlen) * aDPFA * coef >= P.nobias_pos_indel_lenfrac_thres) ||
-            (imax(rtr1.tracklen, rtr2.tracklen) >= P.nobias_pos_indel_str_track_len && major_reg && !(T_APXM0 > T_APXM1 * P.microadjust_nobias_pos_indel_misma_to_indel_ratio))) {
+            (imax(rtr1.tracklen, rtr2.tracklen) >= P.nobias_pos_indel_str_track_len && major_reg && !(TT_(APXM0) > TT_(APXM1) * P.microadjust_nobias_pos_indel_misma_to_indel_ratio))) {
             aLPFA += 2.0; aRPFA += 2.0; aLBFA += 2.0; aRBFA += 2.0;
             if (f_tier2) { c2LPFA += 2.0; c2RPFA += 2.0; c2LBFA += 2.0; c2RBFA += 2.0; }
         }
-        if (f_bMQ >= P.microadjust_nobias_pos_indel_bMQ && f_a2XM2 * 100 >= aDP * 100 * P.microadjust_nobias_pos_indel_perc) { aLIFA += 2.0; aRIFA += 2.0; }
+        if (f_bMQ >= P.microadjust_nobias_pos_indel_bMQ && AL_(a2XM2) * 100 >= aDP * 100 * P.microadjust_nobias_pos_indel_perc) { aLIFA += 2.0; aRIFA += 2.0; }
     } else if (UVC_LINK_M == symbol || UVC_LINK_NN == symbol) {
         const double pc = P.bias_FA_pseudocount_indel_in_read;
-        aLBFA = dmin(aLBFA, (pc + f_aLB1) / (double)(pc * 2 + ADP));
-        aRBFA = dmin(aRBFA, (pc + f_aRB1) / (double)(pc * 2 + ADP));
+        aLBFA = dmin(aLBFA, (pc + AL_(aLB1)) / (double)(pc * 2 + ADP));
+        aRBFA = dmin(aRBFA, (pc + AL_(aRB1)) / (double)(pc * 2 + ADP));
     } else if (refsymbol == symbol) { aLIFA = aRIFA = dmax(aLIFA, aRIFA); }
-    const long long avg_sqr = lmax(T_APXM4 / lmax(1, T_APDP1), T_APXM5 / lmax(1, T_APDP2));
+    const long long avg_sqr = lmax(TT_(APXM4) / lmax(1, TT_(APDP1)), TT_(APXM5) / lmax(1, TT_(APDP2)));
     if ((!is_subst(symbol)) && ((long long)P.microadjust_nobias_pos_indel_maxlen * P.microadjust_nobias_pos_indel_maxlen < avg_sqr)
         && (UVC_LINK_M == symbol || UVC_LINK_NN == symbol || ((long long)(indel_size * 2) * (indel_size * 2) < avg_sqr))) {
         const double pc = P.bias_FA_pseudocount_indel_in_read;
-        const double aLmin = (pc + f_aLP1) / (double)(pc * 2 + T_ALP10), aRmin = (pc + f_aRP1) / (double)(pc * 2 + T_ALP10);   // sic: ALP1 in both (main.hpp:4575-4576)
+        const double aLmin = (pc + AL_(aLP1)) / (double)(pc * 2 + TT_(ALP10)), aRmin = (pc + AL_(aRP1)) / (double)(pc * 2 + TT_(ALP10));   // sic: ALP1 in both (main.hpp:4575-4576)
         aLPFA = dmin(aLPFA, aLmin); aRPFA = dmin(aRPFA, aRmin);
         if (f_tier2) { c2LPFA = dmin(c2LPFA, aLmin); c2RPFA = dmin(c2RPFA, aRmin); }
     }
     if (tprov || (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform)) aLIFA = aRIFA = dmax(aLIFA, aRIFA);
-    const double aPFFA = (f_aPF1 + pfa * 100.0) / (T_APF20 + (f_aPF1 - f_aPF2) + 100.0);
+    const double aPFFA = (AL_(aPF1) + pfa * 100.0) / (TT_(APF20) + (AL_(aPF1) - AL_(aPF2)) + 100.0);
     double aSSFA = SS2[0] * dir_bias_div, cROFA1 = RO1[0] * dir_bias_div, cROFA2 = RO2[0] * dir_bias_div;
     if (is_ins(symbol) || is_del(symbol)) { f_bAD = imin(f_bAD, f_bDPa); f_AD = imin(f_AD, f_cDP0a); }
-    const double bFA = (f_bDPa + pfa) / ((T_BDPb0 + T_BDPb1) + 1.0);
+    const double bFA = (f_bDPa + pfa) / ((TT_(BDPb0) + TT_(BDPb1)) + 1.0);
     const double cFA0 = (f_cDP0a + pfa * (SHORT_FRAG(P.lib_wgs_min_avg_fraglen) ? P.lib_nonwgs_ad_pseudocount : 1.0)) / (sumCDP1 + 1.0);
-    if ((T_ADPfr0 + T_ADPrr0) * P.microadjust_nobias_strand_all_fold < (T_ADPff0 + T_ADPrf0) * unbias_ratio) { aLIFA += 4.0; aSSFA += 4.0; }
-    if ((T_ADPff0 + T_ADPrf0) * P.microadjust_nobias_strand_all_fold < (T_ADPfr0 + T_ADPrr0) * unbias_ratio) { aRIFA += 4.0; aSSFA += 4.0; }
+    if ((TT_(ADPfr0) + TT_(ADPrr0)) * P.microadjust_nobias_strand_all_fold < (TT_(ADPff0) + TT_(ADPrf0)) * unbias_ratio) { aLIFA += 4.0; aSSFA += 4.0; }
+    if ((TT_(ADPff0) + TT_(ADPrf0)) * P.microadjust_nobias_strand_all_fold < (TT_(ADPfr0) + TT_(ADPrr0)) * unbias_ratio) { aRIFA += 4.0; aSSFA += 4.0; }
     const double aLPFA2 = dmax(aDPFA * 0.01, aLPFA), aRPFA2 = dmax(aDPFA * 0.01, aRPFA), aLBFA2 = dmax(aDPFA * 0.01, aLBFA), aRBFA2 = dmax(aDPFA * 0.01, aRBFA);
     const double c2LPFA2 = dmax(cFA2 * 0.01, c2LPFA), c2RPFA2 = dmax(cFA2 * 0.01, c2RPFA), c2LBFA2 = dmax(cFA2 * 0.01, c2LBFA), c2RBFA2 = dmax(cFA2 * 0.01, c2RBFA);
     const double aLIFA2 = dmax(aDPFA * 0.01, aLIFA), aRIFA2 = dmax(aDPFA * 0.01, aRIFA), aSSFA2 = dmax(aDPFA * 0.05, aSSFA);
     cROFA1 = dmax(aDPFA * 1e-4, cROFA1); cROFA2 = dmax(aDPFA * 1e-4, cROFA2);
-    const double fBTA = (double)((T_BTAb0 + T_BTAb1) + 200), fBTB = (double)((T_BTBb0 + T_BTBb1) + 6);
-    const double fbTA = (double)(f_bTAf + f_bTAr + 100), fbTB = (double)(f_bTBf + f_bTBr + 3);
+    const double fBTA = (double)((TT_(BTAb0) + TT_(BTAb1)) + 200), fBTB = (double)((TT_(BTBb0) + TT_(BTBb1)) + 6);
+    const double fbTA = (double)(AL_(bTAf) + AL_(bTAr) + 100), fbTB = (double)(AL_(bTBf) + AL_(bTBr) + 3);
     const long long sl = lmin(
-            lmin(lmax(0, f_aLIT / lmax(1, (long long)(f_aDPfr + f_aDPrr)) - P.microadjust_longfrag_sidelength_min), (long long)P.microadjust_longfrag_sidelength_max),
-            lmin(lmax(0, f_aRIT / lmax(1, (long long)(f_aDPff + f_aDPrf)) - P.microadjust_longfrag_sidelength_min), (long long)P.microadjust_longfrag_sidelength_max));
+            lmin(lmax(0, AL64_(aLIT) / lmax(1, (long long)(AL_(aDPfr) + AL_(aDPrr))) - P.microadjust_longfrag_sidelength_min), (long long)P.microadjust_longfrag_sidelength_max),
+            lmin(lmax(0, AL64_(aRIT) / lmax(1, (long long)(AL_(aDPff) + AL_(aDPrf))) - P.microadjust_longfrag_sidelength_min), (long long)P.microadjust_longfrag_sidelength_max));
     const double sidelen_frac = 1.0 - sl / P.microadjust_longfrag_sidelength_zeroMQpenalty;
     const double _alt_frac = fbTB / fbTA;
     const double alt_frac = (nmore_amp ? (dmax(0.0, _alt_frac - 0.2) * 1.25) : _alt_frac);
@@ -1092,7 +882,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     OUT(UVC_O_FTS, FTS);
     OUT(UVC_O_FTSpct0, (int)pct0); OUT(UVC_O_FTSpct1, (int)pct1); OUT(UVC_O_FTSpct2, (int)pct2); OUT(UVC_O_FTSpct3, (int)pct3); OUT(UVC_O_FTSpct4, (int)pct4);
     const double aNCFA = ((!tprov && SHORT_FRAG(P.lib_wgs_min_avg_fraglen) && (is_ins(symbol) || is_del(symbol)) && indel_size >= P.lib_nonwgs_clip_penal_min_indelsize)
-            ? dmax((f_aNC + 0.5) / (ADP + 1.0), dbetween((f_cDP1f + f_cDP1r) / 300.0, 1.0 / 3.0, 2.0 / 3.0) * aDPFA) : 2.0);
+            ? dmax((AL_(aNC) + 0.5) / (ADP + 1.0), dbetween((AL_(cDP1f) + AL_(cDP1r)) / 300.0, 1.0 / 3.0, 2.0 / 3.0) * aDPFA) : 2.0);
     const double cb_normalgerm = ((!tprov || !SHORT_FRAG(P.lib_wgs_min_avg_fraglen)) ? 1e-9
             : dbetween(aPFFA * aPFFA * (1.0 / P.lib_nonwgs_normal_full_self_rescue_fa), aPFFA * P.lib_nonwgs_normal_min_self_rescue_fa_ratio, aPFFA));
     const double cbFA = dmax(cbP, dmax(cbBQ, cb_normalgerm));
@@ -1102,7 +892,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     if ((is_ins(f_symbol) || is_del(f_symbol)) && is_rescued) {   // main.hpp:4804-4810
         const int isz = f_gap_len;
         const int noinfo = (isz * (is_ins(f_symbol) ? 2 : 1) + imax(isz, imax(rtr1.tracklen, rtr2.anyTR_tracklen)));
-        refbias = (double)(noinfo) / ((double)(lmin(T_ALPL0, T_ARPL0) * 2 + noinfo) / (double)(T_ABQ20 + 0.5));
+        refbias = (double)(noinfo) / ((double)(lmin(TT_(ALPL0), TT_(ARPL0)) * 2 + noinfo) / (double)(TT_(ABQ20) + 0.5));
         refbias = dmin(refbias, P.microadjust_refbias_indel_max);
     }
     f_cDP1v = (int)(norm_fa(dmax(dmin(dmin(t1plus, t1only), aNCFA), cbFA), refbias) * sumCDP1 * 100);
@@ -1147,8 +937,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int f_cDP1v = FO_(cDP1v), f_cDP1w = FO_(cDP1w), f_cDP1x = FO_(cDP1x), f_cDP2v = FO_(cDP2v), f_cDP2w = FO_(cDP2w);
     const bool tprov = P.tumor_vcf_is_provided, is_rescued = tprov;   // the caller passes IS_PROVIDED(vcf_tumor_fname), main.cpp:979
     const int indel_size = f_gap_len;
-    const int sumCDP1 = T_CDP1b0 + T_CDP1b1, sumCDP2 = T_CDP2b0 + T_CDP2b1, sumBDP = T_BDPb0 + T_BDPb1, sumCDP12 = T_CDP12b0 + T_CDP12b1;
-    const double cFA2 = (f_cDP2f + f_cDP2r + 0.5) / (sumCDP2 + 1.0);
+    const int sumCDP1 = TT_(CDP1b0) + TT_(CDP1b1), sumCDP2 = TT_(CDP2b0) + TT_(CDP2b1), sumBDP = TT_(BDPb0) + TT_(BDPb1), sumCDP12 = TT_(CDP12b0) + TT_(CDP12b1);
+    const double cFA2 = (AL_(cDP2f) + AL_(cDP2r) + 0.5) / (sumCDP2 + 1.0);
     const int phrederr = sscs_phred(P, refsymbol, symbol) + (!tprov ? 0 : 4);
     const double umi_cFA = (((double)(f_cDP2v) + 0.5) / ((double)(sumCDP2 * 100 + 1.0)));
     const double umi_cFA_w = (((double)(f_cDP2w) + 0.5) / ((double)(sumCDP2 * 100 + 1.0)));
@@ -1162,36 +952,36 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     inc4tn += (oxid ? P.tn_q_inc_max_sscs_CG_AT : P.tn_q_inc_max_sscs_other);
     const double t2n = (tpfa > 0 ? tpfa : 0) * P.contam_t2n_mul_frac;
     const double contamfrac = P.contam_any_mul_frac + (1.0 - P.contam_any_mul_frac) * t2n;
-    const int aDP = (f_aDPff + f_aDPfr + f_aDPrf + f_aDPrr);
-    const int ADP = (int)(T_ADPff0 + T_ADPrf0 + T_ADPfr0 + T_ADPrr0);
-    const int cDP0 = (f_cDP1f + f_cDP1r), CDP0 = sumCDP1, cDP2 = (f_cDP2f + f_cDP2r), CDP2 = sumCDP2;
-    const int aavgMQ = (int)(f_aMQs / imax(1, aDP));
-    const int diffAaMQs = (int)((T_AMQs0 - f_aMQs) / imax(1, ADP - aDP)) - aavgMQ;
+    const int aDP = (AL_(aDPff) + AL_(aDPfr) + AL_(aDPrf) + AL_(aDPrr));
+    const int ADP = (int)(TT_(ADPff0) + TT_(ADPrf0) + TT_(ADPfr0) + TT_(ADPrr0));
+    const int cDP0 = (AL_(cDP1f) + AL_(cDP1r)), CDP0 = sumCDP1, cDP2 = (AL_(cDP2f) + AL_(cDP2r)), CDP2 = sumCDP2;
+    const int aavgMQ = (int)(AL_(aMQs) / imax(1, aDP));
+    const int diffAaMQs = (int)((TT_(AMQs0) - AL_(aMQs)) / imax(1, ADP - aDP)) - aavgMQ;
     const int noUMI_inc = imin(P.bias_FA_powerlaw_noUMI_phred_inc_snv, aDP / 2);
     const double pl_noUMI = P.powlaw_anyvar_base + (is_subst(symbol) ? noUMI_inc : P.bias_FA_powerlaw_noUMI_phred_inc_indel);
     const int withUMI_inc = imin(P.bias_FA_powerlaw_withUMI_phred_inc_snv - P.bias_FA_powerlaw_noUMI_phred_inc_snv, cDP2 / 2) + noUMI_inc;
     const double pl_withUMI = P.powlaw_anyvar_base + (is_subst(symbol) ? withUMI_inc : P.bias_FA_powerlaw_withUMI_phred_inc_indel);
-    const double prior_weight = 1.0 / (f_cDPmf + f_cDPmr + 1.0);
+    const double prior_weight = 1.0 / (AL_(cDPmf) + AL_(cDPmr) + 1.0);
     const int thres_highBQ = (is_subst(symbol) ? P.fam_thres_highBQ_snv : P.fam_thres_highBQ_indel);
-    const int cMmQ = (int)round(numstates2phred((f_cDPMf + f_cDPmf + f_cDPMr + f_cDPmr + pow(10.0, thres_highBQ / 10.0) * prior_weight) / (f_cDPmf + f_cDPmr + prior_weight)));
-    const int nb1 = f_bIADb * 100 + 1, nb2 = imin(nb1, f_cDP1v + 1);
-    const long long pq1 = 10 * f_bIAQb / imax(1, f_bIADb);
+    const int cMmQ = (int)round(numstates2phred((AL_(cDPMf) + AL_(cDPmf) + AL_(cDPMr) + AL_(cDPmr) + pow(10.0, thres_highBQ / 10.0) * prior_weight) / (AL_(cDPmf) + AL_(cDPmr) + prior_weight)));
+    const int nb1 = AL_(bIADb) * 100 + 1, nb2 = imin(nb1, f_cDP1v + 1);
+    const long long pq1 = 10 * AL_(bIAQb) / imax(1, AL_(bIADb));
     const long long pq2 = pq1 + (long long)round(10 * numstates2phred((double)nb2 / (double)nb1));
     long long duped_binom = ((is_ins(symbol) || is_del(symbol)) ? pq1 : pq2) * nb2 / (10 * 100);
     const long long contam_frag_q = (long long)round(binom_llr(t2n, cDP0, CDP0 - cDP0)) + 9 - 3;
     const int h_snp = imax(0, 2 * P.germ_phred_hetero_snp - P.germ_phred_het3al_snp), h_indel = imax(0, 2 * P.germ_phred_hetero_indel - P.germ_phred_het3al_indel);
     int het3al_inc = (is_subst(symbol) ? h_snp : h_indel);
     if (is_ins(symbol) || is_del(symbol)) het3al_inc = (int)nnminus(h_indel + 1, indel_size);
-    const int normcDP1 = (f_cDP12f + f_cDP12r + 1), normCDP1 = sumCDP12 + 1, normBDP = sumBDP + 1;
+    const int normcDP1 = (AL_(cDP12f) + AL_(cDP12r) + 1), normCDP1 = sumCDP12 + 1, normBDP = sumBDP + 1;
     const int ddiv = (is_rescued ? 2 : 1);
     const long long dec1a = (((P.fam_min_n_copies / ddiv <= normCDP1) || (P.fam_min_n_copies_DPxAD / ddiv <= (long long)normCDP1 * normcDP1)) ? 0 : (inc1 + 3));
     const long long dec1b = (((long long)((P.fam_min_overseq_perc - 100) / ddiv + 100) * normCDP1 <= (long long)100 * normBDP) ? 0 : (inc1 + 3));
     const long long dec1 = lmax(dec1a, dec1b);
     const long long dec2 = nnminus(thres_highBQ, cMmQ);
-    const long long cIADnorm = (long long)(f_cIADf + f_cIADr) * 100 + 1;
+    const long long cIADnorm = (long long)(AL_(cIADf) + AL_(cIADr)) * 100 + 1;
     const long long cIADmin = lmin(cIADnorm, (long long)f_cDP2v + 1);
-    const long long bq_fw = f_cIAQf + ((long long)f_cIAQr * imin(P.fam_phred_dscs_all - f_cIDQf, f_cIDQr)) / imax(f_cIDQr, 1);
-    const long long bq_rv = f_cIAQr + ((long long)f_cIAQf * imin(P.fam_phred_dscs_all - f_cIDQr, f_cIDQf)) / imax(f_cIDQf, 1);
+    const long long bq_fw = AL_(cIAQf) + ((long long)AL_(cIAQr) * imin(P.fam_phred_dscs_all - AL_(cIDQf), AL_(cIDQr))) / imax(AL_(cIDQr), 1);
+    const long long bq_rv = AL_(cIAQr) + ((long long)AL_(cIAQf) * imin(P.fam_phred_dscs_all - AL_(cIDQr), AL_(cIDQf))) / imax(AL_(cIDQf), 1);
     const long long contam_sscs_q = (long long)round(binom_llr(t2n, cDP2, CDP2 - cDP2)) + 9 - 3;
     long long sscs_binom = ((long long)nnminus_d((double)lmax(bq_fw, bq_rv), numstates2phred(cIADnorm / (double)cIADmin) * cIADnorm / 100.0) * cIADmin) / (cIADnorm);
     if (lmax(bq_fw, bq_rv) > P.microadjust_fam_binom_qual_halving_thres && is_subst(symbol))
@@ -1201,8 +991,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     int pl_v = (int)round(P.powlaw_exponent * numstates2phred(bcFA_v) + (pl_noUMI));
     const double bcFA_w = (((double)(f_cDP1w) + 0.5) / (double)(sumCDP1 * 100 + 1.0));
     int pl_w = (int)round(P.powlaw_exponent * numstates2phred(bcFA_w) + (pl_noUMI) + P.tn_q_inc_max);
-    const int ds_pl = (int)round(10 / log(10.0) * dmin(log((f_cDP12f + 0.5) / (T_CDP12b0 + 1.0)), log((f_cDP12r + 0.5) / (T_CDP12b1 + 1.0)))) + (phrederr);
-    const int ds_binom = 3 * imin(f_cDP2f, f_cDP2r);
+    const int ds_pl = (int)round(10 / log(10.0) * dmin(log((AL_(cDP12f) + 0.5) / (TT_(CDP12b0) + 1.0)), log((AL_(cDP12r) + 0.5) / (TT_(CDP12b1) + 1.0)))) + (phrederr);
+    const int ds_binom = 3 * imin(AL_(cDP2f), AL_(cDP2r));
     const long long m5 = lmin(lmin(bq_fw, bq_rv), (long long)imin(ds_pl, imin(ds_binom, 3)));
     const int inc2 = (int)lmax(0, m5) * ((cFA2 > 0.002) ? 1 : 0);
     const int dec3 = (is_rescued ? (-3) : ((cFA2 >= 0.003) ? 0 : 5));
@@ -1210,17 +1000,17 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int base_2tn = (int)(pl_withUMI + inc4tn + inc2 - dec1 - dec2 - dec3);
     int sscs_pl_v = (int)round((P.powlaw_exponent * numstates2phred(umi_cFA) + base_2));
     int sscs_pl_w = (int)round((P.powlaw_exponent * numstates2phred(umi_cFA_w) + base_2tn));
-    const double dFA = (double)(f_dDP2 + 0.5) / (double)(T_DDP10 + 1.0);
-    const double dSNR = (double)(f_dDP2 + 0.5) / (double)(f_dDP1 + 1.0);
+    const double dFA = (double)(AL_(dDP2) + 0.5) / (double)(TT_(DDP10) + 1.0);
+    const double dSNR = (double)(AL_(dDP2) + 0.5) / (double)(AL_(dDP1) + 1.0);
     const double dnormFA = dFA * pow(dSNR, 1.0 / P.powlaw_exponent);
     const long long dscs_est = (long long)round((P.fam_phred_dscs_max + phrederr) / 2.0);
-    const long long dFA_binom = (dscs_est - (long long)round(numstates2phred(1.0 / (dnormFA)))) * (long long)f_dDP2 * cIADmin / cIADnorm;
+    const long long dFA_binom = (dscs_est - (long long)round(numstates2phred(1.0 / (dnormFA)))) * (long long)AL_(dDP2) * cIADmin / cIADnorm;
     const int dFA_pl = (int)(P.powlaw_anyvar_base + (dscs_est - P.fam_phred_pow_dscs_all_origin)
             + (int)round(numstates2phred((dnormFA) * dmin(1.0, (double)((f_cDP1v) + 0.5) / (double)(sumCDP1 * 100 + 1.0)))));
     OUT(UVC_O_cMmQ, cMmQ);
     const double eps = (double)FLT_EPS;
     const bool penal_applied = ((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) && !tprov);
-    const int penal_base = (penal_applied ? ((int)round(P.indel_multiallele_samepos_penal / log(2.0) * log((double)dmax(aDP + eps, (double)lmax(T_APDP1, T_APDP2)) / (double)(aDP + eps)))) : 0);
+    const int penal_base = (penal_applied ? ((int)round(P.indel_multiallele_samepos_penal / log(2.0) * log((double)dmax(aDP + eps, (double)lmax(TT_(APDP1), TT_(APDP2))) / (double)(aDP + eps)))) : 0);
     int penal4multi = 0, penal4multi_g = 0, penal4multi_soma = 0, indel_UMI_penal = 0;
     if (indel_size > 0 && f_cDP0a > 0) {
         const double indel_pq = (double)imin(indel_phred_s(P.indel_polymerase_slip_rate, ru_size, repeatnum), 24) + 2 - (double)10;
@@ -1232,7 +1022,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
         int ic = (is_ins(symbol) ? ins_cdepth : del_cdepth);
         if (UVC_LINK_D1 == symbol) ic += ins1_cdepth;
         if (UVC_LINK_I1 == symbol) ic = (int)(ic + del1_cdepth / P.indel_del_to_ins_err_ratio);
-        const int nearInDelDP = (int)(is_ins(symbol) ? T_APDP1 : T_APDP2);
+        const int nearInDelDP = (int)(is_ins(symbol) ? TT_(APDP1) : TT_(APDP2));
         int penal1 = (int)round(P.indel_multiallele_samepos_penal / log(2.0) * log((double)(ic + eps) / (double)(f_cDP0a + eps)));
         if (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) penal1 = (int)nnminus_d(penal1, P.indel_multiallele_samepos_penal);
         const int penal2 = (int)round(P.indel_multiallele_diffpos_penal / log(2.0) * log((double)(nearInDelDP + eps) / (double)(imax(aDP, nearInDelDP) + eps)));
@@ -1252,7 +1042,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     }
     if (oxid && tprov) sscs_binom = lmax(sscs_binom, (long long)imin(aDP, 3));
     OUT(UVC_O_aAaMQ, diffAaMQs);
-    const int readlenMQcap = (int)((T_APXM2) / lmax(1, T_APDP0) - 17);
+    const int readlenMQcap = (int)((TT_(APXM2)) / lmax(1, TT_(APDP0)) - 17);
     const int diffMQ = imax(0, diffAaMQs);
     const bool extra_accurate = (P.inferred_maxMQ > 60);
     const int MQVQadd = ((symbol == refsymbol) ? 0 : (imin(P.germ_phred_homalt_snp, ADP * 3)));
@@ -1261,9 +1051,9 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int MQVQminus = (MQ_unadj ? 0 : ((int)nnminus((60 - 30), aavgMQ) * 2 / 5)) + ((MQ_unadj || (refsymbol != symbol)) ? 0 : (int)nnminus(imin(15, diffMQ), aavgMQ));
     int diffMQ2 = diffMQ;
     if (f_bMQ < 20 && !tprov) {
-        const double axf = (f_aDPff + f_aDPrf + 0.5), axr = (f_aDPfr + f_aDPrr + 0.5), Axf = (T_ADPff0 + T_ADPrf0 + 1.0), Axr = (T_ADPfr0 + T_ADPrr0 + 1.0);
+        const double axf = (AL_(aDPff) + AL_(aDPrf) + 0.5), axr = (AL_(aDPfr) + AL_(aDPrr) + 0.5), Axf = (TT_(ADPff0) + TT_(ADPrf0) + 1.0), Axr = (TT_(ADPfr0) + TT_(ADPrr0) + 1.0);
         if ((axr / Axr) * 2 < (axf / Axf) || (axf / Axf) * 2 < (axr / Axr)
-            || (f_aLI1 + 0.5) / (T_ALI20 + 1.0) * (2 * (1.0 + DBL_EPS)) < (axr) / (Axr) || (f_aRI1 + 0.5) / (T_ARI20 + 1.0) * (2 * (1.0 + DBL_EPS)) < (axf) / (Axf)) diffMQ2 = imax(diffMQ2, 20 - imin(f_bMQ, 20));
+            || (AL_(aLI1) + 0.5) / (TT_(ALI20) + 1.0) * (2 * (1.0 + DBL_EPS)) < (axr) / (Axr) || (AL_(aRI1) + 0.5) / (TT_(ARI20) + 1.0) * (2 * (1.0 + DBL_EPS)) < (axf) / (Axf)) diffMQ2 = imax(diffMQ2, 20 - imin(f_bMQ, 20));
     }
     const double MQ_base = ((f_bMQ * (P.syserr_MQ_max - P.syserr_MQ_nonref_base) / P.syserr_MQ_max + P.syserr_MQ_nonref_base)) - (int)(diffMQ2) - (int)(f_bNMQ);
     const int sysMQ = (((refsymbol == symbol) && (ADP > aDP * 2)) ? f_bMQ : (int)(MQ_base - (int)(numstates2phred((ADP + 1.0) / (aDP + 0.5)))));
@@ -1271,25 +1061,25 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
     const int rescued_MQ = imin((int)nnminus(readlenMQcap, 60), (nonWGS ? P.lib_nonwgs_normal_max_rescued_MQ : P.lib_wgs_normal_max_rescued_MQ));
     int sysMQVQ1 = imin((imax(sysMQ, P.syserr_MQ_min) + MQVQadd), readlenMQcap);
     const int sysBQVQ = (((UVC_PLATFORM_IONTORRENT != P.inferred_sequencing_platform) && is_subst(symbol)) ? f_aBQQ : 200);
-    const int pcr_dp = (int)T_APDP5;
-    const bool strong_amp = ((pcr_dp * 100) > T_APDP0 * 50), weak_amp = ((pcr_dp * 100) > T_APDP0 * 30);
+    const int pcr_dp = (int)TT_(APDP5);
+    const bool strong_amp = ((pcr_dp * 100) > TT_(APDP0) * 50), weak_amp = ((pcr_dp * 100) > TT_(APDP0) * 30);
     const bool tmore_amp = (!tprov ? weak_amp : strong_amp);
-    if (tmore_amp && (is_ins(symbol) || is_del(symbol)) && (sysMQVQ1 > 70) && (T_APXM1 / lmax(T_APDP0, 1) > 20))
-        sysMQVQ1 = (int)(70 + ((sysMQVQ1 - 70) * 5 / (T_APXM1 / lmax(T_APDP0, 1) - 15)));
+    if (tmore_amp && (is_ins(symbol) || is_del(symbol)) && (sysMQVQ1 > 70) && (TT_(APXM1) / lmax(TT_(APDP0), 1) > 20))
+        sysMQVQ1 = (int)(70 + ((sysMQVQ1 - 70) * 5 / (TT_(APXM1) / lmax(TT_(APDP0), 1) - 15)));
     int penal_add = 0;
     if (!tprov) {
-        const long long delAPDP = lmax(T_APDP2, T_APDP4);
-        const long long snv_dp = T_APDP6;
-        if ((T_APDP0 < 3 * delAPDP) && (T_APDP0 < 3 * snv_dp) && (aDP * 3 < delAPDP) && (aDP * 3 < snv_dp) && is_subst(symbol) && (rtr2.tracklen >= 8 * rtr2.unitlen))
+        const long long delAPDP = lmax(TT_(APDP2), TT_(APDP4));
+        const long long snv_dp = TT_(APDP6);
+        if ((TT_(APDP0) < 3 * delAPDP) && (TT_(APDP0) < 3 * snv_dp) && (aDP * 3 < delAPDP) && (aDP * 3 < snv_dp) && is_subst(symbol) && (rtr2.tracklen >= 8 * rtr2.unitlen))
             penal_add = P.microadjust_germline_mix_with_del_snv_penalty;
         if (tmore_amp && is_del(symbol)) {
-            if (aDP * 4 < T_APDP2) penal_add = imax(penal_add, 5);
+            if (aDP * 4 < TT_(APDP2)) penal_add = imax(penal_add, 5);
             else if (f_cDP0a * 3 < 2 * (del_cdepth)) penal_add = imax(penal_add, 2);
         }
     }
     const int sysMQVQ = imax(0, sysMQVQ1);
     const int penal_base2 = penal_base + penal_add;
-    const long long fx = T_ADPff0 + T_ADPfr0, rx = T_ADPrf0 + T_ADPrr0, xf = T_ADPff0 + T_ADPrf0, xr = T_ADPfr0 + T_ADPrr0;
+    const long long fx = TT_(ADPff0) + TT_(ADPfr0), rx = TT_(ADPrf0) + TT_(ADPrr0), xf = TT_(ADPff0) + TT_(ADPrf0), xr = TT_(ADPfr0) + TT_(ADPrr0);
     const bool frx = (lmax(fx, rx) > P.microadjust_strand_orientation_absence_DP_fold * (lmin(fx, rx) + 1));
     const bool xfr = (lmax(xf, xr) > P.microadjust_strand_orientation_absence_DP_fold * (lmin(xf, xr) + 1));
     const int v_minus = (is_subst(symbol) ? ((frx ? P.microadjust_orientation_absence_snv_penalty : 0) + (xfr ? P.microadjust_strand_absence_snv_penalty : 0)) : (tmore_amp ? P.microadjust_dedup_absence_indel_penalty : 0));
@@ -1554,9 +1344,9 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
         double add1 = 0, add2 = 0;
         int tn_dec_both = 0;
         if (normal) {
-            const long long LI = T_APLRI0 + T_APLRI2, LIDP = T_APLRI1 + T_APLRI3;
+            const long long LI = TT_(APLRI0) + TT_(APLRI2), LIDP = TT_(APLRI1) + TT_(APLRI3);
             if (LI < LIDP * (long long)P.lib_wgs_min_avg_fraglen) { add1 = P.lib_nonwgs_normal_add_mul_ad * nfm_cDP1x / 100.0; add2 = P.lib_nonwgs_normal_add_mul_ad * nfm_cDP2x / 100.0; }
-            if (t_tDP > 500 && FLD(UVC_O_DP, rec) > 500 && is_del(symbol) && T_APDP2 * 3 > T_APDP0) tn_dec_both = imin((int)nnminus(nfm_cVQ1, 31), 9);
+            if (t_tDP > 500 && FLD(UVC_O_DP, rec) > 500 && is_del(symbol) && TT_(APDP2) * 3 > TT_(APDP0)) tn_dec_both = imin((int)nnminus(nfm_cVQ1, 31), 9);
         }
         const int prior_phred = ((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) ? 11 : 3);
         if (P.tn_syserr_norm_devqual >= 0) normv_quals(bq4, (t_cDP1x + 0.5) / 100.0 + 0.0, (t_CDP1x + 1.0) / 100.0 + 0.0, t_cVQ1, t_cPCQ1, (nfm_cDP1x + 0.5) / 100.0 + 0.0 + add1, (nfm_CDP1x + 1.0) / 100.0 + 0.0 + add1,
@@ -1579,7 +1369,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
         { const float base = (float)pow(10.0, 0.1); if (v < 10.0f) v = log1pf(powf(base, v)) / logf(base); }   // calc_non_negative<float>
         o_TLODQ = tlodq; o_NLODQ = nlodq; o_SQ = somaticq; o_QUAL = __float_as_int(v);
         o_FILTER = (v < 10 ? 0 : v < 20 ? 1 : v < 30 ? 2 : v < 40 ? 3 : v < 50 ? 4 : v < 60 ? 5 : 6);
-        const int vad1 = f_aBQ2; const long long vdp1 = T_ABQ20;
+        const int vad1 = AL_(aBQ2); const long long vdp1 = TT_(ABQ20);
         const bool keep_var = ((((double)v >= P.vqual) || ((!tprov) && ((vad1 >= P.vad1 && vdp1 >= P.vdp1 && (vdp1 * P.vfa1) <= vad1) || (t_bDP >= P.vad2 && t_BDP >= P.vdp2 && (t_BDP * P.vfa2) <= t_bDP))))
                                && (symbol != refsymbol || should_output_ref_allele));
         o_keep = (keep_var && t_bDP >= ((symbol == refsymbol) ? P.min_r_ad : P.min_a_ad)) ? 1 : 0;
@@ -1686,34 +1476,6 @@ __global__ void __launch_bounds__(256) k_range_map(const UvcScoreRangeDev *range
     const int z = q.beg + (c - q.first);
     zpos_tab[c] = ((c == q.first && !(q.flags & 1)) ? ~z : z);
 }
-static size_t force_mask_words(int64_t npos_scored) { return (size_t)((npos_scored > 0 ? npos_scored : 0) + 31) / 32; }
-
-// scratch layout of one score call.  The head [record counts (2 x int64)] [counters] [tile states of the two scans] is zeroed in front of every call.
-static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-struct ScratchLayout { size_t zero_bytes, cnt, status1, status2, offsets, active, grp, tot, rh, al, al64, mid, d4, keptoff, force_mask, zpos_tab, total; };
-static ScratchLayout scratch_layout(int64_t npos_scored, int64_t cap) {
-    const size_t ngroups = (size_t)(2 * npos_scored), c = (size_t)(cap > 0 ? cap : 1);
-    const size_t ntiles1 = (ngroups + GATE_TILE - 1) / GATE_TILE + 1, ntiles2 = (std::min(ngroups, c) + GS_TILE - 1) / GS_TILE + 1;
-    ScratchLayout L; size_t o = 16;
-    L.cnt = o; o += NCNT * 4;
-    L.status1 = o; o += ntiles1 * 8;
-    L.status2 = o; o += ntiles2 * 8;
-    o = align16(o); L.zero_bytes = o;
-    L.offsets = o; o = align16(o + (ngroups + 1) * 8);
-    L.active = o; o = align16(o + ngroups * 4);
-    L.grp = o; o = align16(o + (size_t)NGR * c * 4);
-    L.tot = o; o = align16(o + (size_t)NTOT * c * 8);
-    L.rh = o; o = align16(o + (size_t)NRH * c * 4);
-    L.al = o; o = align16(o + (size_t)NAL32 * c * 4);
-    L.al64 = o; o = align16(o + (size_t)NAL64 * c * 8);
-    L.mid = o; o = align16(o + (size_t)NMID * c * 8);
-    L.d4 = o; o = align16(o + (size_t)NDP4 * 2 * c * 8);
-    L.keptoff = o; o = align16(o + c * 4);
-    L.force_mask = o; o = align16(o + force_mask_words(npos_scored) * 4);   // zeroed and filled only by a call with force-output sites
-    L.zpos_tab = o; o = align16(o + (size_t)(npos_scored > 0 ? npos_scored : 0) * 4);   // written only by a ranges call (k_range_map)
-    L.total = o;
-    return L;
-}
 extern "C" size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity) { return scratch_layout(npos_scored, capacity).total; }
 extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity) { return scratch_layout(npos_scored, capacity).zero_bytes; }
 
@@ -1725,7 +1487,6 @@ extern "C" size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capa
 // record prefix (offsets[2 * p], already on the device behind k_gate_scan), and when all fit, narrow [lo, hi) 65-fold per step -- a chunk
 // of 10^5 positions costs 3 steps of one coalesced-or-strided load each, a few microseconds against the milliseconds of its kernels.
 // hdr[0] = number of chunks, or -1: position hdr[1] (compact) alone needs hdr[2] records, or -2: the table is too small (cannot happen).
-struct UvcChunkDev { long long g0, ng, r0, nr; };
 __global__ void __launch_bounds__(64) k_chunk_cut(const long long *offsets, long long npos, long long chunk_records, long long *hdr, UvcChunkDev *tab, long long tab_cap) {
     const int lane = (int)threadIdx.x;
     long long p0 = 0, n = 0;
@@ -1762,39 +1523,13 @@ __global__ void __launch_bounds__(64) k_chunk_cut(const long long *offsets, long
     if (lane == 0) { hdr[0] = n; hdr[1] = -1; hdr[2] = 0; }
 }
 
-// Row set of one chunk of a streamed score (two per stream): [record counts 2 x int64][counters][tile states of the keep scan] -- zeroed in
-// front of every chunk -- then the rows, the records and (kept_only) their compacted copy.  c = chunk_records, gc = min(groups of the
-// request, c): a chunk cannot have more active groups than records, nor than the request has groups.
-struct SetLayout { size_t zero_bytes, cnt, status2, grp, tot, rh, al, al64, mid, d4, keptoff, fields, kept, total; };
-static SetLayout set_layout(int64_t c_, int64_t gc_, int with_kept) {
-    const size_t c = (size_t)(c_ > 0 ? c_ : 1), gc = (size_t)(gc_ > 0 ? (gc_ < c_ ? gc_ : c_) : 1);
-    SetLayout L; size_t o = 16;
-    L.cnt = o; o += NCNT * 4;
-    L.status2 = o; o += ((gc + GS_TILE - 1) / GS_TILE + 1) * 8;
-    o = align16(o); L.zero_bytes = o;
-    L.grp = o; o = align16(o + (size_t)NGR * gc * 4);
-    L.tot = o; o = align16(o + (size_t)NTOT * gc * 8);
-    L.rh = o; o = align16(o + (size_t)NRH * c * 4);
-    L.al = o; o = align16(o + (size_t)NAL32 * c * 4);
-    L.al64 = o; o = align16(o + (size_t)NAL64 * c * 8);
-    L.mid = o; o = align16(o + (size_t)NMID * c * 8);
-    L.d4 = o; o = align16(o + (size_t)NDP4 * 2 * c * 8);
-    L.keptoff = o; o = align16(o + gc * 4);
-    L.fields = o; o = align16(o + (size_t)UVC_NUM_SCORE_FIELDS * c * 4);
-    L.kept = o; if (with_kept) o = align16(o + (size_t)UVC_NUM_SCORE_FIELDS * c * 4);
-    L.total = o;
-    return L;
-}
 extern "C" size_t uvc_score_set_bytes(int64_t chunk_records, int64_t ngroups, int with_kept) { return set_layout(chunk_records, ngroups, with_kept).total; }
-// device bytes of one row set per unit of chunk_records, at most (group rows as long as record rows, kept copy included; + 1 for the tile states)
-extern "C" size_t uvc_score_set_bytes_per_record(void) {
-    return (size_t)NGR * 4 + (size_t)NTOT * 8 + (size_t)NRH * 4 + (size_t)NAL32 * 4 + (size_t)NAL64 * 8 + (size_t)NMID * 8 + (size_t)NDP4 * 16 + 4 + (size_t)UVC_NUM_SCORE_FIELDS * 8 + 1;
-}
+extern "C" size_t uvc_score_set_bytes_per_record(void) { return score_set_bytes_per_record(); }
 extern "C" int32_t *uvc_score_set_fields(char *set, int64_t chunk_records, int64_t ngroups, int kept) { const SetLayout L = set_layout(chunk_records, ngroups, 1); return (int32_t *)(set + (kept ? L.kept : L.fields)); }
 // position-sized scratch of a stream: the one-call layout with one-record rows (counters, gate scan states, offsets, active list, force mask,
 // position table), then the cut's header (4 x int64) and the chunk table
-extern "C" size_t uvc_score_stream_pos_bytes(int64_t npos_scored, int64_t tab_cap) { return align16(scratch_layout(npos_scored, 1).total) + 32 + sizeof(UvcChunkDev) * (size_t)(tab_cap > 0 ? tab_cap : 1); }
-extern "C" size_t uvc_score_stream_table_offset(int64_t npos_scored) { return align16(scratch_layout(npos_scored, 1).total); }
+extern "C" size_t uvc_score_stream_pos_bytes(int64_t npos_scored, int64_t tab_cap) { return scratch_layout(npos_scored, 1).total + 32 + sizeof(UvcChunkDev) * (size_t)(tab_cap > 0 ? tab_cap : 1); }
+extern "C" size_t uvc_score_stream_table_offset(int64_t npos_scored) { return scratch_layout(npos_scored, 1).total; }
 
 // what every launch of one score request shares: the context, and the position-sized part of the scratch
 struct ScoreSetup { ScoreCtx C; Stage S; long long npos_scored, ngroups; };
@@ -1814,6 +1549,8 @@ static ScoreSetup score_setup(const UvcScoreIn *in, const ScratchLayout &L) {
     S.win_g = 0; S.win_n = U.ngroups;
     return U;
 }
+// the request has a force mask: sites were listed and the gate is not the all-out one already (under -A every group is selected)
+static bool has_force_mask(const UvcScoreIn *in, int all_out) { return in->force_sites && in->req->n_force_sites > 0 && !all_out; }
 // k_range_map, k_force_mask, k_gate_scan over the whole request: offsets, the active list, the total (d_count[0])
 static int launch_gate(ScoreSetup &U, const UvcScoreIn *in, const ScratchLayout &L, long long *d_count, hipStream_t s) {
     const RegionDev *R = in->R; const UvcParams *P = in->P; const UvcScoreRequest *req = in->req; char *scratch = in->scratch; const int32_t *d_force_sites = in->force_sites;
@@ -1823,7 +1560,7 @@ static int launch_gate(ScoreSetup &U, const UvcScoreIn *in, const ScratchLayout 
         hipLaunchKernelGGL(k_range_map, dim3((unsigned)((npos_scored + 255) / 256)), dim3(256), 0, s, C.ranges, C.n_ranges, (int)npos_scored, tab);
         C.zpos_tab = tab;
     }
-    if (d_force_sites && req->n_force_sites > 0 && !C.all_out) {   // (under -A every group is selected already)
+    if (has_force_mask(in, C.all_out)) {
         unsigned *mask = (unsigned *)(scratch + L.force_mask);
         if (hipMemsetAsync(mask, 0, force_mask_words(npos_scored) * 4, s) != hipSuccess) return UVCGPU_EDEVICE;
         hipLaunchKernelGGL(k_force_mask, dim3((unsigned)((req->n_force_sites + 255) / 256)), dim3(256), 0, s, d_force_sites, (long long)req->n_force_sites, C.pos_beg, C.pos_end, C.ranges, C.n_ranges, mask);
@@ -1863,11 +1600,9 @@ extern "C" int uvc_launch_score(const UvcScoreIn *in, int32_t *d_fields, int64_t
     ScoreCtx &C = U.C; Stage &S = U.S;
     C.fields = d_fields; C.capacity = capacity;
     long long *d_count = (long long *)scratch;
-    S.grp = (int32_t *)(scratch + L.grp); S.tot = (long long *)(scratch + L.tot); S.rh = (int32_t *)(scratch + L.rh); S.al = (int32_t *)(scratch + L.al); S.al64 = (long long *)(scratch + L.al64);
-    S.mid = (double *)(scratch + L.mid); S.d4 = (double *)(scratch + L.d4); S.keptoff = (int32_t *)(scratch + L.keptoff); S.cap = capacity; S.gcap = capacity;
+    bind_rows(S, scratch, L.rows);   // rows per group: min(groups, capacity), as in a chunk's row set
     if (const int rc = launch_gate(U, in, L, d_count, s)) return rc;
-    const long long max_groups = (U.ngroups < capacity ? U.ngroups : capacity);
-    launch_records(R, P, C, S, max_groups, capacity, (req->kept_only && d_fields_kept) ? d_fields_kept : nullptr, d_count, s);
+    launch_records(R, P, C, S, S.gcap, capacity, (req->kept_only && d_fields_kept) ? d_fields_kept : nullptr, d_count, s);
     return 0;
 }
 
@@ -1880,13 +1615,12 @@ extern "C" int uvc_launch_score_gate(const UvcScoreIn *in, int64_t chunk_records
     const ScratchLayout L = scratch_layout(npos0, 1);
     ScoreSetup U = score_setup(in, L);
     if (const int rc = launch_gate(U, in, L, (long long *)scratch, s)) return rc;
-    char *t = scratch + align16(L.total);
+    char *t = scratch + L.total;
     hipLaunchKernelGGL(k_chunk_cut, dim3(1), dim3(64), 0, s, U.C.offsets, npos0, (long long)chunk_records, (long long *)t, (UvcChunkDev *)(t + 32), (long long)tab_cap);
     return 0;
 }
 // one chunk: groups [win_g, win_g + win_n) of the request into the row set `set` (uvc_score_set_bytes; its head is zeroed here)
-extern "C" int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t chunk_records, int with_kept,
-                                      int64_t win_g, int64_t win_n, int64_t win_groups /* active groups of the window */, int64_t win_records, hipStream_t s) {
+extern "C" int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t chunk_records, int with_kept, const UvcChunkDev *win, int64_t win_groups /* active groups of the window */, hipStream_t s) {
     const RegionDev *R = in->R; const UvcParams *P = in->P; const UvcScoreRequest *req = in->req; char *scratch = in->scratch;
     const long long npos0 = score_npos(in);
     if (npos0 <= 0) return 0;
@@ -1894,18 +1628,16 @@ extern "C" int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t c
     ScoreSetup U = score_setup(in, L);
     ScoreCtx &C = U.C; Stage &S = U.S;
     if (C.ranges) C.zpos_tab = (const int *)(scratch + L.zpos_tab);
-    if (in->force_sites && req->n_force_sites > 0 && !C.all_out) C.force_mask = (const unsigned *)(scratch + L.force_mask);
+    if (has_force_mask(in, C.all_out)) C.force_mask = (const unsigned *)(scratch + L.force_mask);
     const SetLayout Q = set_layout(chunk_records, U.ngroups, with_kept);
-    if (win_records > chunk_records || win_groups > (long long)std::min<long long>(U.ngroups, chunk_records)) return UVCGPU_EINVAL;   // (the cut never makes such a window)
+    if (win->nr > Q.rows.c || win_groups > Q.rows.gc) return UVCGPU_EINVAL;   // (the cut never makes such a window)
     if (hipMemsetAsync(set, 0, Q.zero_bytes, s) != hipSuccess) return UVCGPU_EDEVICE;
     S.cnt = (unsigned int *)(set + Q.cnt); S.status2 = (unsigned long long *)(set + Q.status2);
-    S.grp = (int32_t *)(set + Q.grp); S.tot = (long long *)(set + Q.tot); S.rh = (int32_t *)(set + Q.rh); S.al = (int32_t *)(set + Q.al); S.al64 = (long long *)(set + Q.al64);
-    S.mid = (double *)(set + Q.mid); S.d4 = (double *)(set + Q.d4); S.keptoff = (int32_t *)(set + Q.keptoff);
-    S.cap = chunk_records; S.gcap = std::min<long long>(std::max<long long>(U.ngroups, 1), chunk_records);
-    S.win_g = win_g; S.win_n = win_n;
+    bind_rows(S, set, Q.rows);
+    S.win_g = win->g0; S.win_n = win->ng;
     C.fields = (int32_t *)(set + Q.fields); C.capacity = chunk_records;
     // grids by the window's own counts (the host has the table): a last, short chunk launches what it needs
-    launch_records(R, P, C, S, std::max<long long>(win_groups, 1), std::max<long long>(win_records, 1), (req->kept_only && with_kept) ? (int32_t *)(set + Q.kept) : nullptr, (long long *)set, s);
+    launch_records(R, P, C, S, std::max<long long>(win_groups, 1), std::max<long long>(win->nr, 1), (req->kept_only && with_kept) ? (int32_t *)(set + Q.kept) : nullptr, (long long *)set, s);
     return 0;
 }
 

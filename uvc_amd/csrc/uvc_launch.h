@@ -33,6 +33,10 @@ static_assert(sizeof(ZeroPlane) == 16, "the host uploads the plane table as 16-b
 // of the lengths), flags bit 0 = base_at_pos_beg
 struct UvcScoreRangeDev { int beg, end, first, flags; };
 static_assert(sizeof(UvcScoreRangeDev) == 16, "the host uploads the range table as 16-byte rows");
+// one chunk of a streamed score (k_chunk_cut writes the table, the host reads it back): first group of the request (even: a position
+// boundary), group count, first record, record count
+struct UvcChunkDev { long long g0, ng, r0, nr; };
+static_assert(sizeof(UvcChunkDev) == 32, "the host reads the chunk table back as 32-byte rows");
 // one range of the plane readers (uvcgpu_region_coverage, _error_profile, _callable): plane index of the range's first position; its first
 // compact position (the exclusive prefix of the lengths).  Entry n_ranges of a table: { 0, n_total }.  The host builds it in one place
 // (range_table of uvc_host.cpp), the kernels look a compact position up through UvcRangeCursor.
@@ -78,14 +82,18 @@ void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_rati
 void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
 void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
 // ---- uvc_kernels_score.hip ----
-// The caller zeroes the first uvc_score_scratch_zero_bytes of in->scratch on the stream in front of uvc_launch_score / uvc_launch_score_gate;
-// the record counts (all records, kept records) are its first two int64.  d_fields_kept (kept_only): a second [fields][capacity] array.
+// The staged rows, their layouts and the sizes below come from one table (uvc_score_rows.h).  The caller zeroes the first
+// uvc_score_scratch_zero_bytes of in->scratch on the stream in front of uvc_launch_score / uvc_launch_score_gate; the record counts (all
+// records, kept records) are its first two int64.  d_fields_kept (kept_only): a second [fields][capacity] array.  In both forms the rows
+// per record hold `capacity` / `chunk_records` records and the rows per group min(groups of the request, that many) groups.
 int uvc_launch_score(const UvcScoreIn *in, int32_t *d_fields, int64_t capacity, int32_t *d_fields_kept, hipStream_t s);
 size_t uvc_score_scratch_bytes(int64_t npos_scored, int64_t capacity);
 size_t uvc_score_scratch_zero_bytes(int64_t npos_scored, int64_t capacity);
-// the streamed form (uvcgpu_region_score_stream_*): one gate pass + the chunk cut, then the per-record kernels per chunk into a row set
+// the streamed form (uvcgpu_region_score_stream_*): one gate pass + the chunk cut (the header of 4 x int64 and the UvcChunkDev table at
+// uvc_score_stream_table_offset of the scratch), then the per-record kernels per chunk into a row set: `win` is the chunk's table entry,
+// win_groups a bound of its active groups that sizes the grids (at most its groups, its records and the rows)
 int uvc_launch_score_gate(const UvcScoreIn *in, int64_t chunk_records, int64_t tab_cap, hipStream_t s);
-int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t chunk_records, int with_kept, int64_t win_g, int64_t win_n, int64_t win_groups, int64_t win_records, hipStream_t s);
+int uvc_launch_score_chunk(const UvcScoreIn *in, char *set, int64_t chunk_records, int with_kept, const UvcChunkDev *win, int64_t win_groups, hipStream_t s);
 size_t uvc_score_set_bytes(int64_t chunk_records, int64_t ngroups, int with_kept);
 size_t uvc_score_set_bytes_per_record(void);
 int32_t *uvc_score_set_fields(char *set, int64_t chunk_records, int64_t ngroups, int kept);
