@@ -1,4 +1,4 @@
-"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h, uvc_score_rows.h): a source
+"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h, uvc_score_rows.h, uvc_collectives.h): a source
 file that defines a function includes the header that declares it, so the compiler checks the two against each other.  A prototype or a
 boundary struct written out again in a .cpp / .hip file is checked by nobody."""
 import glob
@@ -28,3 +28,55 @@ def test_boundary_structs_are_defined_in_headers_only():
     pat = re.compile(r"^struct\s+(%s)\b" % "|".join(BOUNDARY_STRUCTS))
     bad = [at for at, line in _lines() if pat.match(line)]
     assert not bad, bad
+
+
+# Loops over shuffle distances (a `for` whose step is `<<= 1` or `>>= 1` around a __shfl_ call) live in uvc_collectives.h.  The three that
+# stay in a source file, one each, with the shuffle they use: the suffix minimum of uvc_rtr.hip and the segmented fold of uvc_famstats.hip are
+# not scans or reductions of the header's kind; the butterfly of uvc_coverage.hip costs k_coverage registers when it goes through the header
+# (the comment on wave_merge has the numbers).
+SHUFFLE_LOOPS_OUTSIDE_THE_HEADER = [("uvc_coverage.hip", "__shfl_xor"), ("uvc_famstats.hip", "__shfl_down"), ("uvc_rtr.hip", "__shfl_down")]
+
+
+def _closing(text, i, open_ch, close_ch):
+    """index just behind the bracket that closes the one at text[i]"""
+    depth = 0
+    for j in range(i, len(text)):
+        depth += (text[j] == open_ch) - (text[j] == close_ch)
+        if depth == 0:
+            return j + 1
+    raise AssertionError("unbalanced %s at %d" % (open_ch, i))
+
+
+def _shuffle_loops(text):
+    """the set of __shfl_ calls in the body of every `for` with a shift step"""
+    text = re.sub(r"//[^\n]*", "", text)
+    found = []
+    for m in re.finditer(r"\bfor\s*\(", text):
+        head_end = _closing(text, m.end() - 1, "(", ")")
+        if not re.search(r"(<<|>>)=\s*1\s*\)$", text[m.end():head_end]):
+            continue
+        body = text[head_end:]
+        while body.lstrip().startswith("#"):   # (#pragma unroll in front of a nested loop)
+            body = body.lstrip().split("\n", 1)[1]
+        start = len(body) - len(body.lstrip())
+        body = body[:_closing(body, start, "{", "}")] if body[start] == "{" else body[:body.index(";") + 1]
+        calls = sorted(set(re.findall(r"__shfl_\w*", body)))
+        if calls:
+            found.append(calls)
+    return found
+
+
+def test_shuffle_loop_finder_sees_both_forms():
+    assert _shuffle_loops("for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);  // x") == [["__shfl_xor"]]
+    assert _shuffle_loops("for (int o = 1; o < 64; o <<= 1) {\n#pragma unroll\n for (int c = 0; c < 2; c++) { t = __shfl_up(v[c], o); } }") == [["__shfl_up"]]
+    assert _shuffle_loops("for (int o = 1; o < 64; o <<= 1) n++;\nx = __shfl_up(m, 1);\nfor (int i = 0; i < 4; i++) y = __shfl(y, i);") == []
+
+
+def test_loops_over_shuffle_distances_live_in_the_collectives_header():
+    found = []
+    for path in SOURCES:
+        with open(path) as f:
+            found += [(os.path.basename(path), call) for calls in _shuffle_loops(f.read()) for call in calls]
+    assert sorted(found) == SHUFFLE_LOOPS_OUTSIDE_THE_HEADER, found
+    with open(os.path.join(CSRC, "uvc_collectives.h")) as f:
+        assert len(_shuffle_loops(f.read())) == 4   # wave_sum, wave_min, wave_max, wave_incl

@@ -9,13 +9,14 @@
 //                     byte per compact position and counts the block's run heads.  A position is a head when it is the first of its range or
 //                     its mask differs from the mask of the position before it; that mask comes from the lane to the left, and a lane 0
 //                     that does not start a range RECOMPUTES the mask of the position before the wave's first (one lane in 64 reads twice).
-//   k_callable_scan   one block: the exclusive prefix of the block counts in place, their total (the number of runs) behind them.
+//   k_block_scan      one block: the exclusive prefix of the block counts in place, their total (the number of runs) behind them.
 //   k_callable_emit   reads the mask bytes (its own, both neighbours'), ranks the heads -- ballot and popcount in a wave, LDS across the four
 //                     waves, a running base across the steps, the scanned count across blocks -- and writes the runs in order: a head
 //                     writes { range, pos_beg, mask } of its run, the last position of a run writes its pos_end.
 // No workgroup waits on another, nothing is atomic, every store is a plain vector store; the bytes are the same from call to call.  The host
 // reads the number of runs between scan and emit, so a call whose caller has too little room launches no emit.
 #include "uvc_launch.h"
+#include "uvc_collectives.h"
 
 namespace {
 enum {
@@ -76,37 +77,32 @@ __global__ void __launch_bounds__(256) k_callable_count(RegionDev R, const UvcRa
             first = (i == g.first);
             m = call_mask(R, q, x);
         }
-        int left = __shfl_up(m, 1, 64);
+        int left = __shfl_up(m, 1, 64);   // (the previous lane's mask: a neighbour fetch, not a scan step)
         if (act && lane == 0 && !first) left = call_mask(R, q, x - 1);   // the position before the wave's first, of the same range
         const bool head = act && (first || left != m);
         if (act) mask_out[i] = (unsigned char)m;
         heads += __popcll(__ballot(head));
     }
-    if (lane == 0) wave_heads[threadIdx.x >> 6] = heads;
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = wave_heads[0] + wave_heads[1] + wave_heads[2] + wave_heads[3];
+    const int block_heads = waves_sum<4>(heads, wave_heads);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = block_heads;
 }
 
-// in place: cnt[b] becomes the number of heads in front of block b, cnt[n_blocks] their total (at most the positions of the call: below 2^31)
-__global__ void __launch_bounds__(256) k_callable_scan(int *cnt, int n_blocks) {
-    __shared__ int wave_sum[4];
-    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
+// The array scan of the reports, one block: in place, a[i] becomes the sum of the elements in front of it, a[n] (one element behind the
+// input) their total.  The callable and the MSI call scan their block counts with it (heads in front of block b, at most the positions of
+// the call: below 2^31), the read profile the tile sums of its depth differences and chunk counts.
+__global__ void __launch_bounds__(1024) k_block_scan(int *a, int n) {
+    __shared__ int sh_wave[16];
     int carry = 0;
-    for (int b0 = 0; b0 < n_blocks; b0 += 256) {
-        const int b = b0 + (int)threadIdx.x;
-        const int v = (b < n_blocks ? cnt[b] : 0);
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
-        if (lane == 63) wave_sum[wv] = incl;
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; w++) before += wave_sum[w];
-        if (b < n_blocks) cnt[b] = carry + before + incl - v;
-        carry += wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-        __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int i = i0 + (int)threadIdx.x;
+        const int v = (i < n ? a[i] : 0);
+        int total;
+        const int excl = block_excl<16>(v, sh_wave, total);
+        if (i < n) a[i] = carry + excl;
+        carry += total;
+        __syncthreads();   // sh_wave is written again in the next round
     }
-    if (threadIdx.x == 0) cnt[n_blocks] = carry;
+    if (threadIdx.x == 0) a[n] = carry;
 }
 
 __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, int n_ranges, int n_total, int region_beg, const unsigned char *mask, const int *block_off, UvcCallableRun *runs) {
@@ -144,7 +140,7 @@ __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, i
 
 extern "C" const char *uvc_callable_name(int bit) { return (bit >= 0 && bit < UVC_NCALLBIT) ? CALL_NAMES[bit] : nullptr; }
 extern "C" int64_t uvc_callable_blocks(int64_t n_total) { return (n_total + CALL_TILE - 1) / CALL_TILE; }
-extern "C" void uvc_launch_block_scan(int *d_cnt, int n_blocks, hipStream_t s) { hipLaunchKernelGGL(k_callable_scan, dim3(1), dim3(256), 0, s, d_cnt, n_blocks); }
+extern "C" void uvc_launch_block_scan(int *d_a, int n, hipStream_t s) { hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, d_a, n); }
 // d_tab: n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one receives the number of runs
 extern "C" void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s) {
     if (n_ranges <= 0 || n_total <= 0) return;

@@ -57,6 +57,9 @@ DEV void acc_add(CovAcc &a, const int (&v)[UVC_NCOV], const CovThr &T) {   // (u
 }
 // The wave's lanes hold partial statistics of one range (neutral values in lanes that have none): butterfly over the 64 lanes, then lane j
 // merges statistic j of the row (66 statistics: two rounds).  A zero is not added; min and max always go out (every range has a position).
+// The butterfly is written out here, all statistics per distance, and not as wave_sum / wave_min / wave_max of uvc_collectives.h per
+// statistic: with those k_coverage takes 167 VGPRs instead of 161 (171 and 177 in two other orders of the calls), at or past the 168 that
+// three waves per SIMD allow (profiles/collectives_registers.txt).
 DEV void wave_merge(CovAcc a, long long rid, long long *out) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {

@@ -63,8 +63,9 @@ __global__ void __launch_bounds__(256) k_famstat_span(const int32_t *pos, const 
     int u = -1, p = INT_MAX, e = INT_MIN;
     if (i < n_alns) { u = fs_of[i]; p = pos[i]; e = endpos[i]; }
     if (u < 0 || u >= n_fs) u = -1;   // (no such unit: set_reads refuses these reads)
-    const int u_prev = __shfl_up(u, 1);
-    // lane l ends up with the run's part in lanes [l, 64): after the step with `off` it holds lanes [l, l + 2 off) of its run
+    const int u_prev = __shfl_up(u, 1);   // (the previous lane's unit: a neighbour fetch, not a scan step)
+    // lane l ends up with the run's part in lanes [l, 64): after the step with `off` it holds lanes [l, l + 2 off) of its run.  (A fold segmented
+    // by the unit, over (min, max) pairs: not a scan or reduction of uvc_collectives.h's kind.)
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const int u2 = __shfl_down(u, off), p2 = __shfl_down(p, off), e2 = __shfl_down(e, off);

@@ -20,6 +20,7 @@
 #include "uvcgroup.h"
 #include "uvc_alloc.h"
 #include "uvc_host.h"
+#include "uvc_collectives.h"
 #define hipMalloc(p, n) uvc_dev_malloc((void **)(p), (n))
 #define hipFree(p) uvc_dev_free((void *)(p))
 
@@ -97,7 +98,7 @@ __global__ void __launch_bounds__(256) k_g_pre(GWork W, GCols C, UvcGroupParams 
 
 // one block per class: border[c][i + 1] = sum_{j <= i} (begc + endc)
 __global__ void __launch_bounds__(1024) k_g_scan(GWork W) {
-    __shared__ long long buf[1024];
+    __shared__ long long sh_wave[16];
     const int c = blockIdx.x, t = threadIdx.x;
     const int32_t *b = W.begc + (size_t)c * W.fetch_size, *e = W.endc + (size_t)c * W.fetch_size;
     long long *out = W.border + (size_t)c * (W.fetch_size + 1);
@@ -105,12 +106,12 @@ __global__ void __launch_bounds__(1024) k_g_scan(GWork W) {
     if (t == 0) out[0] = 0;
     for (int base = 0; base < W.fetch_size; base += 1024) {
         const int i = base + t;
-        long long v = (i < W.fetch_size ? (long long)b[i] + e[i] : 0);
-        buf[t] = v; __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) { long long a = (t >= off ? buf[t - off] : 0); __syncthreads(); buf[t] += a; __syncthreads(); }
-        if (i < W.fetch_size) out[i + 1] = carry + buf[t];
-        carry += buf[1023];
-        __syncthreads();
+        const long long v = (i < W.fetch_size ? (long long)b[i] + e[i] : 0);
+        long long total;
+        const long long excl = block_excl<16>(v, sh_wave, total);
+        if (i < W.fetch_size) out[i + 1] = carry + excl + v;
+        carry += total;
+        __syncthreads();   // sh_wave is written again in the next round
     }
 }
 

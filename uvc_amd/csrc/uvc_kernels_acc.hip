@@ -37,6 +37,7 @@
 // uvc_launch_accumulate at the end of the file orders them on two streams.
 // The reference rules that several of them share (pair consensus, assay predicates, ...) stand once in uvc_rules.h; record words and flag bits go by the names of uvc_device.h.
 #include "uvc_launch.h"
+#include "uvc_collectives.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -429,7 +430,7 @@ __global__ void __launch_bounds__(256) k_aln_bm(RegionDev R, RawReads W) {
 #pragma unroll
                          for (int s2 = 0; s2 < 5; s2++) cnt[s2] += (mm && bs == s2); } }
 #pragma unroll
-        for (int s2 = 0; s2 < 5; s2++) { cnt[s2] += __shfl_xor(cnt[s2], 1); cnt[s2] += __shfl_xor(cnt[s2], 2); cnt[s2] += __shfl_xor(cnt[s2], 4); }
+        for (int s2 = 0; s2 < 5; s2++) cnt[s2] = wave_sum<8>(cnt[s2]);   // over the read's eight lanes
         if (sub == 0) {
             int32_t *dst = (int32_t *)&R.frec2[rk];
 #pragma unroll
@@ -516,11 +517,10 @@ __global__ void __launch_bounds__(256) k_aln_prelude(RegionDev R, RawReads W, Uv
     __shared__ __attribute__((aligned(16))) AlnRec stage[256];
     const int id0 = blockIdx.x * blockDim.x, id = id0 + threadIdx.x;
     __shared__ int mis_s[4];
-    int n_mis = (id < R.n_alns) ? aln_prelude_one(R, W, P, id, stage[threadIdx.x]) : 0;
-    for (int d = 32; d > 0; d >>= 1) n_mis += __shfl_xor(n_mis, d);   // one atomic per block: same-address atomics serialise
-    if ((threadIdx.x & 63) == 0) mis_s[threadIdx.x >> 6] = n_mis;
-    __syncthreads();
-    if (threadIdx.x == 0) { const int t = mis_s[0] + mis_s[1] + mis_s[2] + mis_s[3]; if (t) atomicAdd(R.mis_total, (unsigned long long)t); }
+    const int n_mis = (id < R.n_alns) ? aln_prelude_one(R, W, P, id, stage[threadIdx.x]) : 0;
+    // one atomic per block: same-address atomics serialise.  (The barrier inside also orders the records in `stage` before the copy below.)
+    const int t = waves_sum<4>(wave_sum(n_mis), mis_s);
+    if (threadIdx.x == 0 && t) atomicAdd(R.mis_total, (unsigned long long)t);
     const int nrec = imin(256, R.n_alns - id0);
     if (nrec == 256) {
         const uint4 *src = (const uint4 *)&stage[0]; uint4 *dst = (uint4 *)(R.alns + id0);
@@ -611,14 +611,8 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
     for (int i = threadIdx.x; i < 2 * (PSUM_TILE + 1); i += 256) (&d64[0][0])[i] = 0ull;
     __syncthreads();
     const int w_first = (int)blockIdx.x * (PSUM_TILE / 64), w_last = imin(w_first + PSUM_TILE / 64, R.nwin) - 1;
-    auto put = [&](int f, int a, int b, int v) {   // += v on [a, b) of plane f, clipped to the tile
-        a = imax(a, t0); b = imin(b, t1);
-        if (a < b && v != 0) { atomicAdd(&d[f][a - t0], v); atomicAdd(&d[f][b - t0], -v); }
-    };
-    auto put64 = [&](int f, int a, int b, long long v) {
-        a = imax(a, t0); b = imin(b, t1);
-        if (a < b && v != 0) { atomicAdd(&d64[f][a - t0], (unsigned long long)v); atomicAdd(&d64[f][b - t0], (unsigned long long)(-v)); }
-    };
+    auto put = [&](int f, int a, int b, int v) { if (v != 0) diff_put(d[f], t0, t1, a, b, v); };   // += v on [a, b) of plane f, clipped to the tile
+    auto put64 = [&](int f, int a, int b, long long v) { if (v != 0) diff_put(d64[f], t0, t1, a, b, (unsigned long long)v); };
     for (int cls = 0; cls < 4; cls++) {   // the four class sub-lists of the work list: the sums do not depend on the order of the reads
     const int lo = win_lo(R, 1 + cls, w_first), hi = win_hi(R, 1 + cls, w_last);
     for (int k = lo + (int)threadIdx.x; k < hi; k += 256) {
@@ -646,23 +640,15 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
     }
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int n_here = t1 - t0;
     const int64_t xb = (int64_t)blockIdx.x * PSUM_TILE;
     int liA[4] = {0, 0, 0, 0}, riA[4] = {0, 0, 0, 0};
     const int plane_of[PS_N32] = { UVC_P_a_dp, UVC_P_a_pcr_dp, UVC_P_a_umi_dp, UVC_P_a_qlen, UVC_P_a_XM1500, UVC_P_a_LIDP, UVC_P_a_RIDP, -1, -1 };
-    for (int f = 0; f < PS_N32; f++) {
-        int v[4], run = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { run += d[f][threadIdx.x * 4 + i]; v[i] = run; }
-        int inc = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wtot[w] = inc;
-        __syncthreads();
-        int before = inc - run;
-        for (int i = 0; i < w; i++) before += wtot[i];
-        __syncthreads();
+#pragma unroll 1
+    for (int f = 0; f < PS_N32; f++) {   // (one body for the nine planes)
+        int v[4];
+        const int before = block_excl<4>(diff_run<4>(d[f], v), wtot);
+        __syncthreads();   // wtot is written again in the next round
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int x = threadIdx.x * 4 + i, val = before + v[i];
@@ -671,17 +657,9 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
         }
     }
     for (int f = 0; f < 2; f++) {
-        unsigned long long v[4], run = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { run += d64[f][threadIdx.x * 4 + i]; v[i] = run; }
-        unsigned long long inc = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wtot64[w] = inc;
-        __syncthreads();
-        unsigned long long before = inc - run;
-        for (int i = 0; i < w; i++) before += wtot64[i];
-        __syncthreads();
+        unsigned long long v[4];
+        const unsigned long long before = block_excl<4>(diff_run<4>(d64[f], v), wtot64);
+        __syncthreads();   // wtot64 is written again in the next round
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int x = threadIdx.x * 4 + i;
@@ -923,10 +901,10 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
             // the interval sums, a lane per sum; the clip events
             if (sub < PN_N32) {
                 const unsigned v = (sub == PN_A ? 1u : sub == PN_APOS ? (unsigned)apos : (unsigned)rend);
-                atomicAdd(&d32[sub][s - t0], v); atomicAdd(&d32[sub][e - t0], 0u - v);
+                diff_put_at(d32[sub], s - t0, e - t0, v);   // (s < e are the read's ends clipped to the tile)
             } else if (sub < PN_N32 + PN_N64) {
                 const unsigned long long v = (unsigned long long)(long long)(sub == PN_N32 + PN_CL ? cL : cR);
-                atomicAdd(&d64[sub - PN_N32][s - t0], v); atomicAdd(&d64[sub - PN_N32][e - t0], 0ull - v);
+                diff_put_at(d64[sub - PN_N32], s - t0, e - t0, v);
             } else if (sub == 7 && h2.w != 0) {
                 const int lclip = h2.w & 0xFFFF, rclip = (h2.w >> 16) & 0xFFFF;
                 const int pcr_inc = (((q4[1].x >> 24) & 0x4) ? 1 : 0);
@@ -943,36 +921,17 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
         __syncthreads();
     }
     // prefix sums of the five difference arrays at once: PER consecutive positions per thread, the wave's, the block's
-    const int lane = tid & 63, w = tid >> 6;
     unsigned v32[PN_N32][PER], inc32[PN_N32];
     unsigned long long v64[PN_N64][PER], inc64[PN_N64];
 #pragma unroll
-    for (int f = 0; f < PN_N32; f++) {
-        unsigned run = 0;
+    for (int f = 0; f < PN_N32; f++) inc32[f] = block_scan_begin(diff_run<PER>(d32[f], v32[f]), wtot[f]);
 #pragma unroll
-        for (int i = 0; i < PER; i++) { run += d32[f][tid * PER + i]; v32[f][i] = run; }
-        unsigned inc = run;
+    for (int f = 0; f < PN_N64; f++) inc64[f] = block_scan_begin(diff_run<PER>(d64[f], v64[f]), wtot64[f]);
+    __syncthreads();   // the one barrier of the five scans
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-        if (lane == 63) wtot[f][w] = inc;
-        inc32[f] = inc - run;
-    }
+    for (int f = 0; f < PN_N32; f++) inc32[f] = block_scan_end<4>(inc32[f], wtot[f]);
 #pragma unroll
-    for (int f = 0; f < PN_N64; f++) {
-        unsigned long long run = 0;
-#pragma unroll
-        for (int i = 0; i < PER; i++) { run += d64[f][tid * PER + i]; v64[f][i] = run; }
-        unsigned long long inc = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long u = __shfl_up(inc, o, 64); if (lane >= o) inc += u; }
-        if (lane == 63) wtot64[f][w] = inc;
-        inc64[f] = inc - run;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int f = 0; f < PN_N32; f++) for (int i = 0; i < w; i++) inc32[f] += wtot[f][i];
-#pragma unroll
-    for (int f = 0; f < PN_N64; f++) for (int i = 0; i < w; i++) inc64[f] += wtot64[f][i];
+    for (int f = 0; f < PN_N64; f++) inc64[f] = block_scan_end<4>(inc64[f], wtot64[f]);
     const int n_here = t1 - t0;
 #pragma unroll
     for (int i = 0; i < PER; i++) {
@@ -1996,10 +1955,7 @@ __global__ void __launch_bounds__(256) k_frag_sums(RegionDev R, UvcParams P) {
     // first with beg >= the end of the tile's last 64-position window; two binary searches over the list by every thread (forty dependent
     // loads in front of the block's work) otherwise
     const int lo = win_lo(R, 5 + strand, (int)blockIdx.x * (FSUM_TILE / 64)), hi = win_hi(R, 5 + strand, (t1 - 1 - R.beg) >> 6);
-    auto put = [&](int f, int a, int b, int v) {   // += v on [a, b) of plane f, clipped to the tile
-        a = imax(a, t0); b = imin(b, t1);
-        if (a < b) { atomicAdd(&d[f][a - t0], v); atomicAdd(&d[f][b - t0], -v); }
-    };
+    auto put = [&](int f, int a, int b, int v) { diff_put(d[f], t0, t1, a, b, v); };   // += v on [a, b) of plane f, clipped to the tile
     for (int k = lo + (int)threadIdx.x; k < hi; k += 256) {
         const int4 *q4 = (const int4 *)(R.ffast + k);
         const int4 h0 = q4[0]; const int flags = h0.w;   // beg, end, fi, flags (FF_W(flags) == 3: static_assert beside the struct)
@@ -2032,21 +1988,13 @@ __global__ void __launch_bounds__(256) k_frag_sums(RegionDev R, UvcParams P) {
     }
     __syncthreads();
     // prefix sums: four consecutive positions per thread, the block's 256 partial sums by wave scan + the waves' totals
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int32_t *out = R.fsum + (size_t)strand * UVC_FSUM_N * R.npos + (size_t)blockIdx.x * FSUM_TILE;
     const int n_here = t1 - t0;
-    for (int f = 0; f < UVC_FSUM_N; f++) {
-        int v[4], run = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { run += d[f][threadIdx.x * 4 + i]; v[i] = run; }
-        int inc = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wtot[w] = inc;
-        __syncthreads();
-        int before = inc - run;
-        for (int i = 0; i < w; i++) before += wtot[i];
-        __syncthreads();
+#pragma unroll 1
+    for (int f = 0; f < UVC_FSUM_N; f++) {   // (one body for all planes)
+        int v[4];
+        const int before = block_excl<4>(diff_run<4>(d[f], v), wtot);
+        __syncthreads();   // wtot is written again in the next round
         int32_t *o4 = out + (size_t)f * R.npos + threadIdx.x * 4;
         if (threadIdx.x * 4 + 4 <= n_here && (((uintptr_t)o4) & 15) == 0) *(int4 *)o4 = make_int4(before + v[0], before + v[1], before + v[2], before + v[3]);
         else {

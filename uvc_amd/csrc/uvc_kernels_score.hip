@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "uvc_launch.h"
 #include "uvc_score_rows.h"
+#include "uvc_collectives.h"
 
 #define DBL_EPS 2.220446049250313e-16
 #define FLT_EPS 1.1920928955078125e-07
@@ -286,7 +287,7 @@ DEV long long stage_cell(const RegionDev &R, int grp, int plane, int s, int64_t 
 #define AL64_(n) ROW_(long long, S.al64, AL_##n - NAL32, S.cap, rec)
 // ---- chained scan (one launch): every block takes the next tile by ticket, publishes the tile's sum, and adds up its predecessors'.
 // A tile's state is ONE naturally aligned 8-byte word written by one agent-scope store and polled by agent-scope loads (nothing else is
-// handed between blocks), bits 63..62: 1 = sum of this tile, 2 = sum of all tiles up to and including this one; bits 61..0 the packed sums.
+// handed between blocks; a spin protocol, not a scan of uvc_collectives.h's kind -- only the sum over the lanes is), bits 63..62: 1 = sum of this tile, 2 = sum of all tiles up to and including this one; bits 61..0 the packed sums.
 // Tickets are dealt in order, so the block of tile t - 1 is resident or done whenever tile t looks back: the spin is bounded all the same.
 #define CS_VALUE(w) ((w) & 0x3FFFFFFFFFFFFFFFull)
 DEV unsigned long long cs_load(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -304,10 +305,7 @@ DEV unsigned long long cs_lookback(unsigned long long *status, int tile, unsigne
         const int k = (incl ? __builtin_ctzll(incl) : 64);                              // the nearest tile that already knows its prefix
         const unsigned long long need = (k >= 63 ? ~0ull : ((1ull << (k + 1)) - 1));
         if ((ready & need) == need) {
-            unsigned long long v = (lane <= k ? CS_VALUE(w) : 0ull);
-#pragma unroll
-            for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-            run += v;
+            run += wave_sum(lane <= k ? CS_VALUE(w) : 0ull);
             if (k < 64) break;
             j -= 64;
             continue;
@@ -317,19 +315,6 @@ DEV unsigned long long cs_lookback(unsigned long long *status, int tile, unsigne
     }
     if (lane == 0) cs_store(&status[tile], (2ull << 62) | CS_VALUE(run + aggregate));
     return run;
-}
-// exclusive scan of one value per thread over the block (256 threads), the block's total in `total`
-DEV unsigned long long block_excl_scan256(unsigned long long v, unsigned long long *sh_wave /* [4] */, unsigned long long &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-    if (lane == 63) sh_wave[wv] = inc;
-    __syncthreads();
-    unsigned long long base = 0;
-    for (int q = 0; q < 4; q++) { if (q < wv) base += sh_wave[q]; }
-    total = sh_wave[0] + sh_wave[1] + sh_wave[2] + sh_wave[3];
-    return base + inc - v;
 }
 
 // candidate gate, main.cpp:801-840, on the fragment depth alone (cdepth is an output of the gate, not part of the decision)
@@ -417,7 +402,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_gate_scan(RegionDev R, UvcParams P
 #pragma unroll
       for (int i = 0; i < GATE_ITEMS; i++) { v[i] = sh_cnt[j0 + i + (j0 >> 3)]; s += (unsigned long long)v[i]; } }
     unsigned long long total = 0;
-    const unsigned long long excl = block_excl_scan256(s, sh_wave, total);
+    const unsigned long long excl = block_excl<GS_BLOCK / 64>(s, sh_wave, total);
     if (threadIdx.x < 64) { const unsigned long long p = cs_lookback(S.status1, tile, total, (int)threadIdx.x, R.err); if (threadIdx.x == 0) sh_prefix = p; }
     __syncthreads();
     long long run = (long long)(sh_prefix + excl);
@@ -1408,7 +1393,7 @@ __global__ void __launch_bounds__(GS_BLOCK) k_keep_scan(ScoreCtx C, Stage S, lon
             v[i] = n; s += (unsigned long long)n;
         }
         unsigned long long total = 0;
-        const unsigned long long excl = block_excl_scan256(s, sh_wave, total);
+        const unsigned long long excl = block_excl<GS_BLOCK / 64>(s, sh_wave, total);
         if (threadIdx.x < 64) { const unsigned long long p = cs_lookback(S.status2, tile, total, (int)threadIdx.x, err); if (threadIdx.x == 0) sh_prefix = p; }
         __syncthreads();
         long long run = (long long)(sh_prefix + excl);

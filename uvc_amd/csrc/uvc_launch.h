@@ -130,8 +130,9 @@ void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int
 void uvc_launch_callable_emit(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const unsigned char *d_mask, const int *d_blocks, UvcCallableRun *d_runs, hipStream_t s);
 int64_t uvc_callable_blocks(int64_t n_total);
 const char *uvc_callable_name(int bit);
-// the scan of uvc_launch_callable_count on its own: in place, cnt[b] becomes the sum of cnt[0 .. b), cnt[n_blocks] the total (one block)
-void uvc_launch_block_scan(int *d_cnt, int n_blocks, hipStream_t s);
+// the array scan of the reports (the block counts of uvc_launch_callable_count and of the MSI call, the tile sums of the read profile):
+// in place, a[i] becomes the sum of a[0 .. i), a[n] -- one element behind the input -- the total (one block of 1 024 threads)
+void uvc_launch_block_scan(int *d_a, int n, hipStream_t s);
 // ---- uvc_msi.hip: d_tab = n_ranges + 1 rows; d_blocks: uvc_msi_blocks(n_total) + 1 ints, the last one the number of loci once the kernels
 // have run; d_heads: `room` ints (the region-relative head of each locus, ascending); d_rows: `room` rows of UVC_MSI_ROW ints, zero at the
 // start.  Loci beyond `room` are counted and not written; room 0 runs the count alone ----

@@ -16,6 +16,7 @@
 // The kernels behind the scan read the number of loci from the device and leave what lies beyond `room` alone: the host learns the number
 // after everything has run, and a call whose buffer was too small runs again with a larger one.  Integer arithmetic only; the adds commute.
 #include "uvc_launch.h"
+#include "uvc_collectives.h"
 
 namespace {
 enum {
@@ -64,7 +65,6 @@ DEV bool msi_head(const RegionDev &R, const UvcMsiRequest &q, int64_t x, int &tl
 
 __global__ void __launch_bounds__(256) k_msi_heads(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, UvcMsiRequest q, int *block_count) {
     __shared__ int wave_heads[4];
-    const int lane = (int)(threadIdx.x & 63);
     const long long base = (long long)blockIdx.x * MSI_TILE;
     UvcRangeCursor g;
     int heads = 0;   // wave-uniform
@@ -79,9 +79,8 @@ __global__ void __launch_bounds__(256) k_msi_heads(RegionDev R, const UvcRangeRo
         }
         heads += __popcll(__ballot(head));
     }
-    if (lane == 0) wave_heads[threadIdx.x >> 6] = heads;
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = wave_heads[0] + wave_heads[1] + wave_heads[2] + wave_heads[3];
+    const int block_heads = waves_sum<4>(heads, wave_heads);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = block_heads;
 }
 
 __global__ void __launch_bounds__(256) k_msi_emit(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, UvcMsiRequest q, const int *block_off, int32_t *heads_out, int32_t *rows, int room) {
@@ -116,12 +115,6 @@ __global__ void __launch_bounds__(256) k_msi_emit(RegionDev R, const UvcRangeRow
         locus_base += wave_heads[0] + wave_heads[1] + wave_heads[2] + wave_heads[3];
         __syncthreads();
     }
-}
-
-DEV int wave_min(int v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = imin(v, __shfl_xor(v, d, 64));
-    return v;
 }
 
 // grid-stride over the loci, one wave each; n_loci_dev: the scanned total

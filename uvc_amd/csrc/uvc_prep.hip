@@ -13,70 +13,35 @@
 #include <stdint.h>
 #include "uvc_prep.h"
 #include "uvc_launch.h"
+#include "uvc_collectives.h"
 
 namespace {
 #define PDEV __device__ __forceinline__
 enum { PC_MATCH = 0, PC_INS = 1, PC_DEL = 2, PC_REF_SKIP = 3, PC_SOFT_CLIP = 4, PC_HARD_CLIP = 5, PC_PAD = 6, PC_EQUAL = 7, PC_DIFF = 8 };
 PDEV bool is_m(int op) { return op == PC_MATCH || op == PC_EQUAL || op == PC_DIFF; }
-// one atomic per wave instead of one per lane: millions of same-address atomics serialise (k_read_facts took 8.6 ms with them, 0.2 without)
-PDEV int wave_max(int v) { for (int d = 32; d > 0; d >>= 1) v = imax(v, __shfl_xor(v, d)); return v; }
-PDEV int wave_sum(int v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
+// (wave_max / wave_sum in front of an atomic: one atomic per wave instead of one per lane: millions of same-address atomics serialise --
+// k_read_facts took 8.6 ms with them, 0.2 without)
 
 // ---- several prefix sums over one index in three launches (tile sums inside the producing kernel, one block over the tile sums, one apply
 // pass that writes every offset column) instead of a library scan -- two launches -- per column.  Tile = 2 048 consecutive elements.
 #define SC_BLOCK 256
 #define SC_ITEMS 8
 #define SC_TILE (SC_BLOCK * SC_ITEMS)
-PDEV long long wave_sum64(long long v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-// block-wide sums of NC per-thread values; the result is valid in thread 0
-template <int NC> PDEV void block_sums(long long (&v)[NC], long long (*sh)[NC] /* [4][NC] */) {
-    const int wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NC; c++) v[c] = wave_sum64(v[c]);
-    if ((threadIdx.x & 63) == 0) { for (int c = 0; c < NC; c++) sh[wv][c] = v[c]; }
-    __syncthreads();
-    if (threadIdx.x == 0) { for (int c = 0; c < NC; c++) v[c] = sh[0][c] + sh[1][c] + sh[2][c] + sh[3][c]; }
-}
 // exclusive scan of every column of tile_sums [NC][ntiles] in place, the column totals to totals[NC]; one block of 1 024 threads
 template <int NC> __global__ void __launch_bounds__(1024) k_tile_tops(long long *tile_sums, int ntiles, long long *totals) {
-    __shared__ long long sh[1024];
+    __shared__ long long sh[16];
     for (int c = 0; c < NC; c++) {
         long long carry = 0;
         for (int b0 = 0; b0 < ntiles; b0 += 1024) {
             const int i = b0 + (int)threadIdx.x;
             const long long v = (i < ntiles ? tile_sums[(size_t)c * ntiles + i] : 0);
-            sh[threadIdx.x] = v;
-            __syncthreads();
-            for (int d = 1; d < 1024; d <<= 1) {
-                const long long o = (threadIdx.x >= (unsigned)d ? sh[threadIdx.x - d] : 0);
-                __syncthreads();
-                sh[threadIdx.x] += o;
-                __syncthreads();
-            }
-            if (i < ntiles) tile_sums[(size_t)c * ntiles + i] = carry + sh[threadIdx.x] - v;
-            const long long tot = sh[1023];
-            __syncthreads();
+            long long tot;
+            const long long excl = block_excl<16>(v, sh, tot);
+            if (i < ntiles) tile_sums[(size_t)c * ntiles + i] = carry + excl;
+            __syncthreads();   // sh is written again in the next round
             carry += tot;
         }
         if (threadIdx.x == 0) totals[c] = carry;
-    }
-}
-// exclusive prefix of this thread's NC values over the block's threads (thread order), the tile's prefix added: v[c] becomes the exclusive prefix
-template <int NC> PDEV void block_excl(long long (&v)[NC], const long long *tile_pref /* [NC][ntiles] */, int ntiles, int tile, long long (*shw)[NC] /* [4][NC] */) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    long long inc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        inc[c] = v[c];
-        for (int d = 1; d < 64; d <<= 1) { const long long o = __shfl_up(inc[c], d); if (lane >= d) inc[c] += o; }
-    }
-    if (lane == 63) { for (int c = 0; c < NC; c++) shw[wv][c] = inc[c]; }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        long long base = tile_pref[(size_t)c * ntiles + tile];
-        for (int q = 0; q < 4; q++) if (q < wv) base += shw[q][c];
-        v[c] = base + inc[c] - v[c];
     }
 }
 
@@ -84,25 +49,26 @@ template <int NC> PDEV void block_excl(long long (&v)[NC], const long long *tile
 struct ScanCols { const void *in[3]; void *out[3]; int64_t n[3]; int in64[3], out64[3], inclusive[3]; };
 PDEV long long col_load(const ScanCols &C, int c, int64_t i) { return i < C.n[c] ? (C.in64[c] ? ((const long long *)C.in[c])[i] : (long long)((const int32_t *)C.in[c])[i]) : 0LL; }
 __global__ void __launch_bounds__(SC_BLOCK) k_cols_sums(ScanCols C, long long *tile_sums, int ntiles) {
-    __shared__ long long sh[4][3];
+    __shared__ long long sh[3][4];
     long long v[3] = { 0, 0, 0 };
     for (int k = 0; k < SC_ITEMS; k++) {
         const int64_t i = (int64_t)blockIdx.x * SC_TILE + (int64_t)k * SC_BLOCK + threadIdx.x;
 #pragma unroll
         for (int c = 0; c < 3; c++) v[c] += col_load(C, c, i);
     }
-    block_sums<3>(v, sh);
+    block_sums<4>(v, sh);
     if (threadIdx.x == 0) { for (int c = 0; c < 3; c++) tile_sums[(size_t)c * ntiles + blockIdx.x] = v[c]; }
 }
 __global__ void __launch_bounds__(SC_BLOCK) k_cols_apply(ScanCols C, const long long *tile_pref, int ntiles) {
-    __shared__ long long shw[4][3];
+    __shared__ long long shw[3][4];
     const int64_t i0 = (int64_t)blockIdx.x * SC_TILE + (int64_t)threadIdx.x * SC_ITEMS;
     long long e[3][SC_ITEMS], v[3] = { 0, 0, 0 };
 #pragma unroll
     for (int c = 0; c < 3; c++) { for (int k = 0; k < SC_ITEMS; k++) { e[c][k] = col_load(C, c, i0 + k); v[c] += e[c][k]; } }
-    block_excl<3>(v, tile_pref, ntiles, (int)blockIdx.x, shw);
+    block_excl<4>(v, shw);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
+        v[c] += tile_pref[(size_t)c * ntiles + blockIdx.x];
         for (int k = 0; k < SC_ITEMS; k++) {
             const int64_t i = i0 + k;
             if (i >= C.n[c]) break;
@@ -198,8 +164,8 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
     col[0] += nfr; col[1] += nfs; col[2] += (o_kind != 0); col[3] += o_np2; col[4] += o_trows; col[5] += o_items; col[6] += o_ins; col[7] += o_gaps;
     }
     {
-        __shared__ long long shc[4][8];
-        block_sums<8>(col, shc);
+        __shared__ long long shc[8][4];
+        block_sums<4>(col, shc);
         if (threadIdx.x == 0) { for (int c = 0; c < 8; c++) tile_sums[(size_t)c * ntiles + blockIdx.x] = col[c]; }
     }
     // wave, then block, then one set of atomics per block (the grid is a few thousand blocks)
@@ -223,7 +189,7 @@ __global__ void __launch_bounds__(256) k_read_facts(UvcPrepIn in, int32_t rbeg, 
 __global__ void __launch_bounds__(SC_BLOCK) k_facts_apply(int64_t n, const long long *tile_pref, int ntiles, const long long *totals, const int32_t *kind, const int32_t *new_frag, const int32_t *new_fs,
                                                           const int32_t *n_p2, const int64_t *trows, const int64_t *items, const int64_t *gaps,
                                                           int32_t *frag_of, int32_t *fs_of, int32_t *p2_first, int64_t *table_off, int64_t *item_off, int64_t *gap_off, int32_t *complex_ids, Stage1 *T) {
-    __shared__ long long shw[4][7];
+    __shared__ long long shw[7][4];
     const int64_t i0 = (int64_t)blockIdx.x * SC_TILE + (int64_t)threadIdx.x * SC_ITEMS;   // this thread's SC_ITEMS consecutive reads
     long long v[7] = { 0, 0, 0, 0, 0, 0, 0 };   // new_frag, new_fs, is_complex, n_p2, trows, items, gaps (the sum of the inserted lengths is only needed as a total)
     int e_nf[SC_ITEMS], e_ns[SC_ITEMS], e_k[SC_ITEMS], e_p2[SC_ITEMS]; long long e_tr[SC_ITEMS], e_it[SC_ITEMS], e_gp[SC_ITEMS];
@@ -235,20 +201,9 @@ __global__ void __launch_bounds__(SC_BLOCK) k_facts_apply(int64_t n, const long 
         v[0] += e_nf[k]; v[1] += e_ns[k]; v[2] += (e_k[k] != 0); v[3] += e_p2[k]; v[4] += e_tr[k]; v[5] += e_it[k]; v[6] += e_gp[k];
     }
     // (column 6 of the tile sums is the inserted length: skipped here)
-    {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        long long inc[7];
+    block_excl<4>(v, shw);
 #pragma unroll
-        for (int c = 0; c < 7; c++) { inc[c] = v[c]; for (int d = 1; d < 64; d <<= 1) { const long long o = __shfl_up(inc[c], d); if (lane >= d) inc[c] += o; } }
-        if (lane == 63) { for (int c = 0; c < 7; c++) shw[wv][c] = inc[c]; }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 7; c++) {
-            long long base = tile_pref[(size_t)(c < 6 ? c : 7) * ntiles + blockIdx.x];
-            for (int q = 0; q < 4; q++) if (q < wv) base += shw[q][c];
-            v[c] = base + inc[c] - v[c];
-        }
-    }
+    for (int c = 0; c < 7; c++) v[c] += tile_pref[(size_t)(c < 6 ? c : 7) * ntiles + blockIdx.x];
 #pragma unroll
     for (int k = 0; k < SC_ITEMS; k++) {
         const int64_t i = i0 + k;
@@ -403,7 +358,7 @@ __global__ void k_stage2_totals(int32_t n_fs, int32_t n_frags, const int32_t *ge
 __global__ void __launch_bounds__(256) k_max_i32(const int32_t *v, int64_t n, int32_t *out) {
     int32_t m = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) m = imax(m, v[i]);
-    for (int d = 32; d > 0; d >>= 1) m = imax(m, __shfl_xor(m, d));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 // the P2 work-list entries at their places (one thread per alignment; the order by (class, begin) is made afterwards)
@@ -457,23 +412,25 @@ PDEV void unpack8(uint32_t w, unsigned long long q, unsigned long long &bb, uint
 }
 // the offset columns of the compact input form: exclusive prefix sums of l_qseq, n_cigar and ceil(l_qseq / 2) over the reads, three at once
 __global__ void __launch_bounds__(SC_BLOCK) k_len_sums(const int32_t *l_qseq, const int32_t *n_cigar, int64_t n, long long *tile_sums, int ntiles) {
-    __shared__ long long sh[4][3];
+    __shared__ long long sh[3][4];
     long long v[3] = { 0, 0, 0 };
     for (int k = 0; k < SC_ITEMS; k++) {
         const int64_t i = (int64_t)blockIdx.x * SC_TILE + (int64_t)k * SC_BLOCK + threadIdx.x;
         if (i < n) { const int32_t lq = l_qseq[i]; v[0] += lq; v[1] += n_cigar[i]; v[2] += (lq + 1) >> 1; }
     }
-    block_sums<3>(v, sh);
+    block_sums<4>(v, sh);
     if (threadIdx.x == 0) { for (int c = 0; c < 3; c++) tile_sums[(size_t)c * ntiles + blockIdx.x] = v[c]; }
 }
 __global__ void __launch_bounds__(SC_BLOCK) k_len_apply(const int32_t *l_qseq, const int32_t *n_cigar, int64_t n, const long long *tile_pref, int ntiles, int64_t *seq_off, int64_t *cigar_off, int64_t *b4_off) {
-    __shared__ long long shw[4][3];
+    __shared__ long long shw[3][4];
     const int64_t i0 = (int64_t)blockIdx.x * SC_TILE + (int64_t)threadIdx.x * SC_ITEMS;
     int lq[SC_ITEMS], nc[SC_ITEMS];
     long long v[3] = { 0, 0, 0 };
 #pragma unroll
     for (int k = 0; k < SC_ITEMS; k++) { const int64_t i = i0 + k; lq[k] = (i < n ? l_qseq[i] : 0); nc[k] = (i < n ? n_cigar[i] : 0); v[0] += lq[k]; v[1] += nc[k]; v[2] += (lq[k] + 1) >> 1; }
-    block_excl<3>(v, tile_pref, ntiles, (int)blockIdx.x, shw);
+    block_excl<4>(v, shw);
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] += tile_pref[(size_t)c * ntiles + blockIdx.x];
 #pragma unroll
     for (int k = 0; k < SC_ITEMS; k++) {
         const int64_t i = i0 + k;

@@ -30,6 +30,7 @@
 // At the end a block adds its non-zero words to one of `shards` copies of the row with 64-bit vector atomics; k_rp_fold sums the copies.
 // Integer adds only: their order does not show, two calls return the same bits.
 #include "uvc_launch.h"
+#include "uvc_collectives.h"
 
 #include <algorithm>
 
@@ -89,24 +90,6 @@ DEV void rp_merge_add(unsigned *tab, int key, bool on, int lane) {
         left &= ~same;
     }
 }
-// inclusive scan over the wave
-DEV int rp_wave_incl(int v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(v, off); if (lane >= off) v += u; }
-    return v;
-}
-// exclusive scan of one value per thread over a block of NW waves; the block's sum in `total`
-template <int NW> DEV int rp_block_excl(int v, int *sh_wave /* [NW] */, int &total) {
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int incl = rp_wave_incl(v, lane);
-    __syncthreads();   // (sh_wave of an earlier round has been read)
-    if (lane == 63) sh_wave[wv] = incl;
-    __syncthreads();
-    int before = 0; total = 0;
-#pragma unroll
-    for (int k = 0; k < NW; k++) { const int s = sh_wave[k]; if (k < wv) before += s; total += s; }
-    return before + incl - v;
-}
 
 // what a scan is over: the differences of the depth as they are, or the chunks of the alignments
 DEV int rp_scan_value(const int32_t *in, long long i, long long n, int chunks) {
@@ -116,31 +99,16 @@ DEV int rp_scan_value(const int32_t *in, long long i, long long n, int chunks) {
 }
 __global__ void __launch_bounds__(RP_TILE) k_rp_tile_sums(const int32_t *in, long long n, int chunks, int32_t *tile_sums) {
     __shared__ int sh_wave[RP_TILE / 64];
-    int total;
-    (void)rp_block_excl<RP_TILE / 64>(rp_scan_value(in, (long long)blockIdx.x * RP_TILE + threadIdx.x, n, chunks), sh_wave, total);
+    const int total = waves_sum<RP_TILE / 64>(wave_sum(rp_scan_value(in, (long long)blockIdx.x * RP_TILE + threadIdx.x, n, chunks)), sh_wave);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
 }
-// exclusive scan of the tile sums in place, one block; the sum of all tiles behind them (entry n_tiles)
-__global__ void __launch_bounds__(1024) k_rp_tile_scan(int32_t *tile_sums, int n_tiles) {
-    __shared__ int sh_wave[16];
-    int carry = 0;
-    for (int base = 0; base < n_tiles; base += 1024) {
-        const int i = base + (int)threadIdx.x;
-        const int v = (i < n_tiles ? tile_sums[i] : 0);
-        int total;
-        const int excl = rp_block_excl<16>(v, sh_wave, total);
-        if (i < n_tiles) tile_sums[i] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) tile_sums[n_tiles] = carry;
-}
+// (the exclusive scan of the tile sums in place, their total behind them in entry n_tiles: uvc_launch_block_scan)
 // cpre[a] = the first chunk of alignment a; cpre[n_alns] = the number of chunks
 __global__ void __launch_bounds__(RP_TILE) k_rp_chunks(const int32_t *l_qseq, int n_alns, const int32_t *tile_pref, int32_t *cpre) {
     __shared__ int sh_wave[RP_TILE / 64];
     const long long i = (long long)blockIdx.x * RP_TILE + threadIdx.x;
     const int v = rp_scan_value(l_qseq, i, n_alns, 1);
-    int total;
-    const int excl = rp_block_excl<RP_TILE / 64>(v, sh_wave, total);
+    const int excl = block_excl<RP_TILE / 64>(v, sh_wave);
     if (i < n_alns) cpre[i] = tile_pref[blockIdx.x] + excl;
     if (i == n_alns - 1) cpre[n_alns] = tile_pref[blockIdx.x] + excl + v;
 }
@@ -162,8 +130,7 @@ __global__ void __launch_bounds__(RP_TILE) k_rp_status(RegionDev R, int32_t *dx,
     const long long x = (long long)blockIdx.x * RP_TILE + tid;
     const bool have = (x < R.npos);
     const int d = have ? dx[x] : 0;
-    int total;
-    const int D = tile_pref[blockIdx.x] + rp_block_excl<RP_TILE / 64>(d, sh_wave, total) + d;   // (the syncs inside also order cnt's zeroing)
+    const int D = tile_pref[blockIdx.x] + block_excl<RP_TILE / 64>(d, sh_wave) + d;   // (the sync inside also orders cnt's zeroing)
     int st = -1; bool in = false;
     if (have) {
         dx[x] = D;
@@ -219,7 +186,7 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
                 const uint32_t cg = (j < nc ? R.cigars[co + j] : (uint32_t)C_PAD);
                 const int op = cig_op(cg), len = cig_len(cg);
                 const int ql = rp_op_query(op) ? len : 0, rl = rp_op_ref(op) ? len : 0;
-                const int qi = rp_wave_incl(ql, lane), ri = rp_wave_incl(rl, lane);
+                const int qi = wave_incl(ql), ri = wave_incl(rl);
                 const int qs = qcur + qi - ql, ps = pcur + ri - rl;   // the op's first query index and reference coordinate
                 if (!BIN) {
                     if (rp_op_aligned(op) && len > 0 && qs >= q0 && qs < q0 + 64) {   // the run's ends, clipped to the region
@@ -318,7 +285,7 @@ extern "C" void uvc_launch_readprofile_depth(const RegionDev *R, const RawReads 
     int32_t *cpre = d_scratch, *tsum = d_scratch + n + 1;
     const unsigned nt = (unsigned)rp_tiles(n);
     hipLaunchKernelGGL(k_rp_tile_sums, dim3(nt), dim3(RP_TILE), 0, s, W->l_qseq, (long long)n, 1, tsum);
-    hipLaunchKernelGGL(k_rp_tile_scan, dim3(1), dim3(1024), 0, s, tsum, (int)nt);
+    uvc_launch_block_scan(tsum, (int)nt, s);
     hipLaunchKernelGGL(k_rp_chunks, dim3(nt), dim3(RP_TILE), 0, s, W->l_qseq, n, tsum, cpre);
     const long long most = n_bases / 64 + n;   // no more chunks than this
     const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>(RP_MAX_BLOCKS, (most + 4 * RP_MIN_CHUNKS - 1) / (4 * RP_MIN_CHUNKS)));
@@ -330,7 +297,7 @@ extern "C" void uvc_launch_readprofile_status(const RegionDev *R, const UvcRange
     int32_t *tsum = d_scratch + (R->n_alns > 0 ? R->n_alns : 0) + 1;
     const unsigned nt = (unsigned)rp_tiles(R->npos);
     hipLaunchKernelGGL(k_rp_tile_sums, dim3(nt), dim3(RP_TILE), 0, s, d_dx, (long long)R->npos, 0, tsum);
-    hipLaunchKernelGGL(k_rp_tile_scan, dim3(1), dim3(1024), 0, s, tsum, (int)nt);
+    uvc_launch_block_scan(tsum, (int)nt, s);
     hipLaunchKernelGGL(k_rp_status, dim3(nt), dim3(RP_TILE), 0, s, *R, d_dx, d_x, tsum, d_tab, n_ranges, min_depth, max_alt_permille, d_status, RP_MAX_SHARDS, (unsigned long long *)d_parts);
 }
 extern "C" void uvc_launch_readprofile_bin(const RegionDev *R, const RawReads *W, int64_t n_bases, int min_mapq, const uint8_t *d_status, long long *d_parts, long long *d_out, const int32_t *d_scratch, hipStream_t s) {

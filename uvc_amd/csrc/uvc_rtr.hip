@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "uvc_rtr.h"
+#include "uvc_collectives.h"
 
 namespace {
 #define RDEV __device__ __forceinline__
@@ -54,7 +55,8 @@ RDEV uint8_t base_code(uint8_t c) {   // CHAR_TO_SYMBOL, main_conversion.hpp:473
     switch (c) { case 'A': case 'a': return UVC_BASE_A; case 'C': case 'c': return UVC_BASE_C; case 'G': case 'g': return UVC_BASE_G; case 'T': case 't': return UVC_BASE_T;
                  case 'I': case 'i': return UVC_LINK_M; case '-': case '_': return UVC_LINK_D1; default: return UVC_BASE_N; }
 }
-// reverse (suffix) minimum over the lanes of a wave: inclusive result per lane
+// reverse (suffix) minimum over the lanes of a wave: inclusive result per lane.  (A scan from the high lanes down, and of minima: not one of
+// uvc_collectives.h, whose scans are prefix sums.)
 RDEV int wave_suffix_min(int v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_down(v, d); if (lane + d < 64) v = rmin(v, o); }
@@ -78,7 +80,7 @@ __global__ void __launch_bounds__(256) k_rtr_first(const uint8_t *ref, int n, in
             const int w = t + 256 * j, q = base + w;
             if (q < n && !(q + u < n && sref[w] == sref[w + u])) v = q;   // descending j: the smallest q survives
         }
-        for (int d = 32; d > 0; d >>= 1) v = rmin(v, __shfl_xor(v, d));
+        v = wave_min(v);
         if ((t & 63) == 0) wmin[u][t >> 6] = v;
     }
     __syncthreads();
@@ -138,7 +140,7 @@ __global__ void __launch_bounds__(NT) k_rtr_cand(const uint8_t *ref, int n, int 
             v[j] = run;
         }
         const int incl = wave_suffix_min(run, lane);
-        int excl = __shfl_down(incl, 1); if (lane == 63) excl = INF;
+        int excl = __shfl_down(incl, 1); if (lane == 63) excl = INF;   // (the next lane's value: a neighbour fetch, not a scan step)
         if (lane == 0) wtot[buf][t >> 6] = incl;
 #pragma unroll
         for (int j = 0; j < 3; j++) nm[buf][w0 + j] = rmin(v[j], excl);
@@ -331,21 +333,16 @@ __global__ void __launch_bounds__(NT) k_rtr_tracks(int n, int64_t npos, int bq_m
     }
     // what this block's positions add to the prefix sums (the repeated last entry is not part of any total: k_rtr_baq reads it itself)
     __shared__ long long wtot2[2][NT / 64];
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        long long v = inc[a];
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if ((t & 63) == 0) wtot2[a][t >> 6] = v;
-    }
-    __syncthreads();
-    if (t < 2) { long long v = 0; for (int w = 0; w < NT / 64; w++) v += wtot2[t][w]; btot[(size_t)t * gridDim.x + blockIdx.x] = v; }
+    long long tot[2] = { inc[0], inc[1] };
+    block_sums<NT / 64>(tot, wtot2);
+    if (t == 0) { btot[blockIdx.x] = tot[0]; btot[(size_t)gridDim.x + blockIdx.x] = tot[1]; }
 }
 // region_repeatvec_to_baq_offsetarr, main.cpp:400-429: prefix sums of the increments from the region start, then / 10.  Every block sums the
 // totals of the blocks in front of it itself (k_rtr_tracks left one per block), then scans its own 1024 positions.
 __global__ void __launch_bounds__(NT) k_rtr_baq(int nb_tracks, int64_t npos, const int32_t *incs /* [2][npos] */, const long long *btot /* [2][nb_tracks] */, int64_t *baq) {
     __shared__ long long wsum[2][NT / 64];
     __shared__ long long base_s[2];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, cs = blockIdx.x * TB;
+    const int t = threadIdx.x, cs = blockIdx.x * TB;
     const int np = (int)npos;
     // the blocks in front of this one
     long long pre[2] = { 0, 0 };
@@ -353,30 +350,13 @@ __global__ void __launch_bounds__(NT) k_rtr_baq(int nb_tracks, int64_t npos, con
     long long own[2] = { 0, 0 };
     const int p = cs + t;
     if (p < np) { own[0] = incs[p]; own[1] = incs[npos + p]; }
+    block_sums<NT / 64>(pre, wsum);
+    if (t == 0) { base_s[0] = pre[0]; base_s[1] = pre[1]; }
+    __syncthreads();   // base_s is there, and wsum has been read: block_excl writes it again
+    long long excl[2] = { own[0], own[1] };
+    block_excl<NT / 64>(excl, wsum);
 #pragma unroll
-    for (int a = 0; a < 2; a++) {
-        long long v = pre[a];
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if (lane == 0) wsum[a][wave] = v;
-    }
-    __syncthreads();
-    if (t < 2) { long long v = 0; for (int w = 0; w < NT / 64; w++) v += wsum[t][w]; base_s[t] = v; }
-    __syncthreads();
-    long long incl[2];
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        long long v = own[a];
-        for (int d = 1; d < 64; d <<= 1) { const long long o = __shfl_up(v, d); if (lane >= d) v += o; }
-        incl[a] = v;
-        if (lane == 63) wsum[a][wave] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-        long long v = incl[a] + base_s[a];
-        for (int w = 0; w < wave; w++) v += wsum[a][w];
-        if (p < np) baq[(size_t)a * npos + p] = v / 10;
-    }
+    for (int a = 0; a < 2; a++) { if (p < np) baq[(size_t)a * npos + p] = (excl[a] + own[a] + base_s[a]) / 10; }
 }
 size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
 }   // namespace
