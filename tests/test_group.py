@@ -1,7 +1,8 @@
 """Family assignment (grouping.cpp:608-997, MolecularID.hpp, Hash.hpp).
 CPU: the oracle against an independent pure-Python restatement (dict / set based, written from the reference text).
 GPU: uvcgpu_group_families against the oracle: per-alignment outputs bit-exact, the family / fragment structure equal as a
-partition (the order of families is the one thing the two are allowed to differ in, see include/uvcgroup.h)."""
+partition (the order of families is the one thing the two are allowed to differ in, see include/uvcgroup.h), and inside every family
+as the exact sequence along `order` (structure()).  The inputs at the kernels' edges are in tests/group_cases.py."""
 import numpy as np
 import pytest
 
@@ -105,7 +106,9 @@ def py_prefilter(P, flag, mapq, pos, endpos, mpos, isize_raw):
     return 0, isrc, isr2, tB, tE, isize
 
 
-def py_group(P, c):
+def py_group(P, c, scan_round=0, pow_scale=1.0):
+    """scan_round = 1024 drops the carry of the border sums at every multiple of 1024 (what a scan in rounds of 1024 bins gives when it forgets
+    the rounds before); pow_scale multiplies the power of dedup_center_mult.  Both are there to prove that an input can tell such a fault."""
     n = len(c["pos"])
     size = P.fetch_tend - P.fetch_tbeg + (MARGIN + OUTER) * 2
     begc = np.zeros((4, size), np.int64); endc = np.zeros((4, size), np.int64)
@@ -121,14 +124,19 @@ def py_group(P, c):
         if not (max(r[3], r[4]) + 2 <= P.fetch_tbeg or P.fetch_tend <= min(r[3], r[4])):
             visited.add((int(c["qname_hash31"][i]), int(c["qname_hash17"][i])))
     border = np.concatenate([np.zeros((4, 1), np.int64), np.cumsum(begc + endc, axis=1)], axis=1)
+    if scan_round:
+        first = (np.arange(1, size + 1) - 1) // scan_round * scan_round   # border[i] ends with bin i - 1, whose round starts here
+        border[:, 1:] -= border[:, first]
 
     def centers(cnt):
+        """the walk over hi = lo - 3 .. lo + 3 with its running maximum, for every lo at once"""
         cen = np.zeros(size, np.int64)
-        for lo in range(INNER, size - INNER):
-            cen[lo] = lo; mx = cnt[lo]
-            for hi in range(lo - INNER, lo + INNER + 1):
-                if cnt[hi] > mx and (cnt[hi] + 1) > (cnt[lo] + 1) * P.dedup_center_mult ** abs(lo - hi):
-                    cen[lo] = hi; mx = cnt[hi]
+        lo = np.arange(INNER, size - INNER)
+        cen[lo] = lo; mx = cnt[lo].copy()
+        for off in range(-INNER, INNER + 1):
+            power = float(P.dedup_center_mult) ** abs(off) * pow_scale    # Python's float power is the host's pow()
+            take = (cnt[lo + off] > mx) & ((cnt[lo + off] + 1) > (cnt[lo] + 1) * power)
+            cen[lo[take]] = lo[take] + off; mx[take] = cnt[lo + off][take]
         return cen
     # only the bins that are looked up matter; computing all of them is what the reference does
     b2c = [centers(begc[k]) for k in range(4)]; e2c = [centers(endc[k]) for k in range(4)]
@@ -181,9 +189,40 @@ def canon(res):
     return fams, sorted(tuple(v) for v in frag.values())          # fragments keep file order inside
 
 
+def structure(res):
+    """The strict form of canon(): every family as the exact sequence of (strand, input index) along `order`, every fragment as its index
+    sequence.  Only the order of families among themselves is free (include/uvcgroup.h), so inside a family nothing is sorted here; the
+    strands must not decrease, a fragment must be one run of one family and strand, and its indices must ascend (file order)."""
+    order, fam_id, frag_id, strand = (np.asarray(res[k]).astype(np.int64) for k in ("order", "fam_id", "frag_id", "fam_strand"))
+    assert len(order) == len(fam_id) == len(frag_id) == len(strand) == res["n_kept"]
+    if len(order) == 0:
+        assert res["n_fams"] == 0 and res["n_frags"] == 0
+        return [], []
+    assert fam_id[0] == 0 and frag_id[0] == 0 and set(np.diff(fam_id)) <= {0, 1} and set(np.diff(frag_id)) <= {0, 1}
+    assert fam_id[-1] + 1 == res["n_fams"] and frag_id[-1] + 1 == res["n_frags"] and len(set(order.tolist())) == len(order)
+    same_fam, same_frag = np.diff(fam_id) == 0, np.diff(frag_id) == 0
+    assert (np.diff(strand)[same_fam] >= 0).all(), "strands out of order inside a family"
+    assert same_fam[same_frag].all() and (np.diff(strand)[same_frag] == 0).all(), "a fragment spans two families or strands"
+    assert (np.diff(order)[same_frag] > 0).all(), "a fragment is not in file order"
+    fams, frags = {}, {}
+    for k in range(len(order)):
+        fams.setdefault(int(fam_id[k]), []).append((int(strand[k]), int(order[k])))
+        frags.setdefault(int(frag_id[k]), []).append(int(order[k]))
+    return (sorted((tuple(v), int(res["fam_dflag"][f]), int(res["fam_idflag"][f])) for f, v in fams.items()), sorted(tuple(v) for v in frags.values()))
+
+
+def py_structure(fams):
+    """what structure() must give, from py_group's families: strand, then fragments by their base-17 name hash, then file order"""
+    return (sorted((tuple((s, i) for (s, q17) in sorted(fr) for i in fr[(s, q17)]), key[4], key[5]) for key, fr in fams.items()),
+            sorted(tuple(idx) for fr in fams.values() for idx in fr.values()))
+
+
+SEEDS = dict(plain=311, umi=622, amplicon=933, end2end_nomerge=144)      # fixed: the same reads in every process
+
+
 @pytest.mark.parametrize("case", ["plain", "umi", "amplicon", "end2end_nomerge"])
 def test_oracle_against_python(oracle_lib, case):
-    cols, qnames, tb, te = make_alignments(seed=hash(case) % 1000, umi=(case == "umi"), amplicon=(case == "amplicon"), n_pairs=1400 if case == "amplicon" else 300)
+    cols, qnames, tb, te = make_alignments(seed=SEEDS[case], umi=(case == "umi"), amplicon=(case == "amplicon"), n_pairs=1400 if case == "amplicon" else 300)
     P = group.default_params(oracle_lib, tb, te)
     if case == "end2end_nomerge":
         P.pair_end_merge, P.end2end, P.kept_aln_min_aln_len, P.kept_aln_min_mapqual = 1, 0, 10, 60
@@ -195,6 +234,7 @@ def test_oracle_against_python(oracle_lib, case):
     got, frags = canon(res)
     assert got == exp
     assert frags == sorted(tuple(idx) for fr in fams.values() for idx in fr.values())
+    assert structure(res) == py_structure(fams)
     assert (np.diff(res["fam_id"]) >= 0).all() and (np.diff(res["frag_id"]) >= 0).all()
     if case == "amplicon":
         assert n_amp > 100 and any(k[5] == 0x7 for k in fams)
@@ -218,7 +258,7 @@ def test_gpu_against_oracle(oracle_lib, gpu_lib, case):
     if case == "big":
         cols, qnames, tb, te = make_alignments(seed=77, n_pairs=60_000, length=200_000, umi=True)
     else:
-        cols, qnames, tb, te = make_alignments(seed=hash(case) % 1000, umi=(case == "umi"), amplicon=(case == "amplicon"), n_pairs=1400 if case == "amplicon" else 300)
+        cols, qnames, tb, te = make_alignments(seed=SEEDS[case], umi=(case == "umi"), amplicon=(case == "amplicon"), n_pairs=1400 if case == "amplicon" else 300)
     P = group.default_params(oracle_lib, tb, te)
     if case == "end2end_nomerge":
         P.pair_end_merge, P.end2end, P.kept_aln_min_aln_len, P.kept_aln_min_mapqual = 1, 0, 10, 60
@@ -229,6 +269,7 @@ def test_gpu_against_oracle(oracle_lib, gpu_lib, case):
     for k in ("n_kept", "n_fams", "n_frags", "ext_beg", "ext_end", "n_amplicon", "n_visited_qnames"):
         assert ro[k] == rg[k], (k, ro[k], rg[k])
     assert canon(ro) == canon(rg)
+    assert structure(ro) == structure(rg)
     assert (np.diff(rg["fam_id"]) >= 0).all() and (np.diff(rg["frag_id"]) >= 0).all()
     for s in ["q#ACGT+TTGA", "plain"]:
         assert group.qname_digest(gpu_lib, s) == group.qname_digest(oracle_lib, s)

@@ -10,6 +10,7 @@
 // Read names and UMIs are 2 x 64-bit hashes (uvcgroup.h).  A family key is reduced to two independent 64-bit mixes; two keys are
 // the same family only if both agree.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -115,7 +116,13 @@ __global__ void __launch_bounds__(1024) k_g_scan(GWork W) {
     }
 }
 
-__global__ void __launch_bounds__(256) k_g_center(GWork W, double mult) {
+// pow(dedup_center_mult, d) for d = 0 .. G_INNER, taken on the host: the reference calls the host's pow (grouping.cpp:422-442), and the
+// device pow is not it.  On 3.0 the device's comes out low, (hicnt + 1) == (locnt + 1) * 3^d then reads as "greater", and two families
+// merge.  Nor is the host's the correctly rounded power (glibc's cube is an ulp off for about one multiplier in 1 200), so it is not
+// rebuilt from exact products here either.
+struct GCenterPow { double v[G_INNER + 1]; };
+
+__global__ void __launch_bounds__(256) k_g_center(GWork W, GCenterPow pw) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t per = 4LL * W.fetch_size;
     if (t >= 2 * per) return;
@@ -127,10 +134,11 @@ __global__ void __launch_bounds__(256) k_g_center(GWork W, double mult) {
     if (lo < G_INNER || lo >= W.fetch_size - G_INNER) { cen[lo] = 0; return; }   // untouched bins keep the vector's initial 0
     const int locnt = cnt[lo];
     int center = lo, maxc = locnt;
+#pragma unroll
     for (int hi = lo - G_INNER; hi < lo + G_INNER + 1; hi++) {
         const int hicnt = cnt[hi];
         const int d = (lo > hi ? lo - hi : hi - lo);
-        if ((hicnt > maxc) && ((double)(hicnt + 1) > (double)(locnt + 1) * pow(mult, (double)d))) { center = hi; maxc = hicnt; }
+        if ((hicnt > maxc) && ((double)(hicnt + 1) > (double)(locnt + 1) * pw.v[d])) { center = hi; maxc = hicnt; }
     }
     cen[lo] = center;
 }
@@ -349,7 +357,9 @@ int uvcgpu_group_families(const UvcGroupParams *Pp, const UvcGroupInput *in, Uvc
     hipStream_t s = nullptr;
     if (n) hipLaunchKernelGGL(k_g_pre, dim3(nblk(n)), dim3(256), 0, s, W, C, P);
     hipLaunchKernelGGL(k_g_scan, dim3(4), dim3(1024), 0, s, W);
-    hipLaunchKernelGGL(k_g_center, dim3(nblk(8LL * W.fetch_size)), dim3(256), 0, s, W, P.dedup_center_mult);
+    GCenterPow pw;
+    for (int d = 0; d <= G_INNER; d++) pw.v[d] = pow(P.dedup_center_mult, (double)d);
+    hipLaunchKernelGGL(k_g_center, dim3(nblk(8LL * W.fetch_size)), dim3(256), 0, s, W, pw);
     if (n) hipLaunchKernelGGL(k_g_key, dim3(nblk(n)), dim3(256), 0, s, W, C, P);
     u64 counters[4] = { 0, 0, 0, 0 };
     if (hipMemcpy(counters, W.counters, sizeof(counters), hipMemcpyDeviceToHost) != hipSuccess) return uvcgpu_set_error(UVCGPU_EDEVICE, hipGetErrorString(hipGetLastError()));
