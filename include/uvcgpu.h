@@ -156,7 +156,8 @@ typedef struct UvcReadSoA {
 /* ---------------------------------------------------------------- per-position state (a2) -- */
 /* Plane groups readable with uvcgpu_region_fetch().  Every group is a dense array
  * [n_planes][n_positions] (position fastest), position index = refpos - region begin.
- * "per symbol" groups are [field][symbol][pos]. */
+ * "per symbol" groups are [field][symbol][pos].  The comments below are documentation: the table that the library and the Python mirror
+ * read (element size, fields, strands, per symbol, zero fill) is uvc_field_groups.def. */
 enum UvcField {
     UVC_F_PREP32 = 0,   /* int32 [UVC_NPREP32][npos]          SegFormatPrepSet i32 fields, main_conversion.hpp:541-605 */
     UVC_F_PREP64 = 1,   /* int64 [UVC_NPREP64][npos]          SegFormatPrepSet i64 fields                             */

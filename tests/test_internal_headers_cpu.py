@@ -1,4 +1,4 @@
-"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h, uvc_score_rows.h, uvc_collectives.h): a source
+"""The internal C interface of libuvcgpu.so is declared once, in headers (uvc_amd/csrc/uvc_launch.h, uvc_host.h, uvc_prep.h, uvc_rtr.h, uvc_rules.h, uvc_planes.h, uvc_score_rows.h, uvc_collectives.h): a source
 file that defines a function includes the header that declares it, so the compiler checks the two against each other.  A prototype or a
 boundary struct written out again in a .cpp / .hip file is checked by nobody."""
 import glob
@@ -8,7 +8,7 @@ import re
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "uvc_amd", "csrc")
 SOURCES = sorted(glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(CSRC, "*.hip")))
 BOUNDARY_STRUCTS = ("RawReads", "UvcProf", "ZeroPlane", "UvcScoreRangeDev", "UvcRangeRow", "UvcUnitSpan", "UvcRangeCursor", "UvcChunkDev",
-                    "ScoreRowDesc", "ScoreRows", "ScratchLayout", "SetLayout")
+                    "ScoreRowDesc", "ScoreRows", "ScratchLayout", "SetLayout", "UvcGroup", "SlabLayout")
 
 
 def _lines():
@@ -80,3 +80,35 @@ def test_loops_over_shuffle_distances_live_in_the_collectives_header():
     assert sorted(found) == SHUFFLE_LOOPS_OUTSIDE_THE_HEADER, found
     with open(os.path.join(CSRC, "uvc_collectives.h")) as f:
         assert len(_shuffle_loops(f.read())) == 4   # wave_sum, wave_min, wave_max, wave_incl
+
+
+# The memory of a region handle has two owners in uvc_host.cpp, Buf (a buffer that grows on demand) and Pool (allocations freed together):
+# both wait for the handle's streams before a block goes back.  Outside their definitions the file names no allocation call, and it has no
+# switch over the plane groups (include/uvc_field_groups.def is their table).
+def _code_of_uvc_host():
+    with open(os.path.join(CSRC, "uvc_host.cpp")) as f:
+        text = f.read()
+    text = re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', text)   # string literals (messages name the calls)
+    return re.sub(r"/\*.*?\*/", "", re.sub(r"//[^\n]*", "", text), flags=re.S)
+
+
+def test_allocation_calls_only_inside_the_two_owning_types():
+    text = _code_of_uvc_host()
+    for owner in ("Buf", "Pool"):
+        m = re.search(r"\bstruct %s\s*\{" % owner, text)
+        assert m, owner
+        text = text[:m.start()] + text[_closing(text, m.end() - 1, "{", "}"):]
+    found = re.findall(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree|uvc_dev_malloc|uvc_dev_free)\b", text)
+    assert not found, found
+    assert not re.search(r"#\s*define\s+hip\w+", text)   # (no call under another name)
+
+
+def test_no_switch_over_the_plane_groups_in_uvc_host():
+    text = _code_of_uvc_host()
+    bad = []
+    for m in re.finditer(r"\bswitch\s*\(", text):
+        body_at = text.index("{", _closing(text, m.end() - 1, "(", ")"))
+        if "UVC_F_" in text[body_at:_closing(text, body_at, "{", "}")]:
+            bad.append(text[m.start():body_at])
+    assert not bad, bad
+    assert not re.search(r"\bcase\s+UVC_F_", text)

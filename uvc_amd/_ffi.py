@@ -131,24 +131,23 @@ def _parse_enums():
 ENUMS = _parse_enums()
 NSYM = ENUMS["UVC_NUM_SYMBOLS"]
 
-# field group -> (dtype, planes per position as a shape prefix)
+# field group -> (id, dtype, planes per position as a shape prefix): the rows of include/uvc_field_groups.def in id order, each
+# UVC_GROUP(name, element bytes, fields, strands, per_symbol, fill); an axis of length 1 in front of the symbols is not part of the shape
 import numpy as _np
-FIELD_GROUPS = {
-    "PREP32": (ENUMS["UVC_F_PREP32"], _np.int32, (ENUMS["UVC_NPREP32"],)),
-    "PREP64": (ENUMS["UVC_F_PREP64"], _np.int64, (ENUMS["UVC_NPREP64"],)),
-    "THRES": (ENUMS["UVC_F_THRES"], _np.int32, (ENUMS["UVC_NTHRES"],)),
-    "SEG32": (ENUMS["UVC_F_SEG32"], _np.int32, (ENUMS["UVC_NSEG32"], NSYM)),
-    "SEG64": (ENUMS["UVC_F_SEG64"], _np.int64, (ENUMS["UVC_NSEG64"], NSYM)),
-    "VQ": (ENUMS["UVC_F_VQ"], _np.int32, (ENUMS["UVC_NVQ"], NSYM)),
-    "BQSUM": (ENUMS["UVC_F_BQSUM"], _np.int32, (NSYM,)),
-    "FRAG": (ENUMS["UVC_F_FRAG"], _np.int32, (2, ENUMS["UVC_NFRAG"], NSYM)),
-    "FAM": (ENUMS["UVC_F_FAM"], _np.int32, (2, ENUMS["UVC_NFAM"], NSYM)),
-    "FAMINFO32": (ENUMS["UVC_F_FAMINFO32"], _np.int32, (ENUMS["UVC_NFAMINFO32"], NSYM)),
-    "FAMINFO64": (ENUMS["UVC_F_FAMINFO64"], _np.int64, (ENUMS["UVC_NFAMINFO64"], NSYM)),
-    "DUPLEX": (ENUMS["UVC_F_DUPLEX"], _np.int32, (ENUMS["UVC_NDUPLEX"], NSYM)),
-    "RTR": (ENUMS["UVC_F_RTR"], _np.int32, (ENUMS["UVC_NRTR"],)),
-    "BAQ": (ENUMS["UVC_F_BAQ"], _np.int64, (2,)),
-}
+
+
+def _read_field_groups():
+    groups = {}
+    with open(os.path.join(ROOT, "include", "uvc_field_groups.def")) as fh:
+        for m in filter(None, (re.match(r"UVC_GROUP\((\w+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*\w+\)\s*$", line) for line in fh)):
+            elem, fields, strands, per_symbol = (int(t) for t in m.groups()[1:])
+            shape = ((strands,) if strands > 1 else ()) + ((fields,) if fields > 1 or not per_symbol else ()) + ((NSYM,) if per_symbol else ())
+            groups[m.group(1)] = (ENUMS["UVC_F_" + m.group(1)], {4: _np.int32, 8: _np.int64}[elem], shape)
+    return groups
+
+
+FIELD_GROUPS = _read_field_groups()
+assert [gid for gid, _, _ in FIELD_GROUPS.values()] == list(range(ENUMS["UVC_NUM_FIELD_GROUPS"]))
 SCORE_FIELDS = [k[len("UVC_O_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_O_")), key=lambda kv: kv[1])]
 NUM_SCORE_FIELDS = ENUMS["UVC_NUM_SCORE_FIELDS"]
 # the depth measures of uvcgpu_region_coverage in id order (UvcCoverageMeasure; the rows of include/uvc_coverage.def)

@@ -14,9 +14,8 @@
 #include <stdint.h>
 #include "uvcgpu.h"
 #include "uvc_rules.h"
+#include "uvc_planes.h"   // NSYM, NBUCKETS and the plane groups
 
-#define NSYM UVC_NUM_SYMBOLS
-#define NBUCKETS 16          // NUM_BUCKETS, main_conversion.hpp:920
 #define SQR_QUAL_DIV 32      // main_conversion.hpp:20
 #define MAX_INSERT_SIZE 2000 // common.hpp:64
 #define MAX_STR_N_BASES 100  // common.hpp:63
@@ -294,7 +293,6 @@ DEV int cov_DUPLEX(const RegionDev &R, int plane, int64_t x) {
 
 // (see RegionDev::dirty)
 #define UVC_DIRTY_SHIFT 12
-DEV bool sym_always_filled(int s) { return s < UVC_BASE_NN || s == UVC_LINK_M; }   // A C G T N (a reference base) and LINK_M: written at nearly every position
 // RegionDev::occ: every writer of a cell that does not belong to one of the position's two dense symbols says so here (agent scope: kernels
 // on the side streams mark the same words), so that scoring knows the symbols of a position without reading their planes
 // (a plain look first: the P2 kernels have usually marked the symbol long before the fragment and family kernels come by; a stale look costs an OR)

@@ -10,6 +10,7 @@
 #include "uvc_cpus.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -18,9 +19,6 @@
 #include <string>
 #include <thread>
 #include <vector>
-// device memory through the caching allocator (uvc_alloc.h): freed blocks are reused without the device-wide synchronisation of hipFree
-#define hipMalloc(p, n) uvc_dev_malloc((void **)(p), (n))
-#define hipFree(p) uvc_dev_free((void *)(p))
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -42,30 +40,71 @@ extern "C" int uvcgpu_set_error(int code, const char *msg) { return fail(code, m
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(UVCGPU_EDEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 
 struct uvcgpu_score_stream;
+struct uvcgpu_region;
+// (the cache hands freed blocks to other handles at once: nothing of this handle may still be running on them)
+static void quiesce(const uvcgpu_region *r);   // waits for the handle's streams: main, side and side3
+// The two owners of a handle's memory.  Device memory comes from the caching allocator (uvc_alloc.h: freed blocks are reused without the
+// device-wide synchronisation of hipFree), page-locked memory from the runtime; both wait for the handle's streams before a block goes back.
+// A buffer that is grown on demand: p holds cap units of the size the site's fit() calls name (bytes, elements or records).
+template <class T, bool HOST = false> struct Buf {
+    const uvcgpu_region *r; T *p = nullptr; size_t cap = 0;
+    explicit Buf(const uvcgpu_region *r_) : r(r_) {}
+    Buf(const Buf &) = delete; Buf &operator=(const Buf &) = delete;
+    ~Buf() { release(); }
+    operator T *() const { return p; }
+    static hipError_t raw_alloc(void **q, size_t bytes) { return HOST ? hipHostMalloc(q, bytes, hipHostMallocDefault) : uvc_dev_malloc(q, bytes); }
+    static hipError_t raw_free(void *q) { return HOST ? hipHostFree(q) : uvc_dev_free(q); }
+    void release() { if (p) { quiesce(r); (void)raw_free(p); } p = nullptr; cap = 0; }
+    // It stays when it holds `need` units and, with keep_max, no more than keep_max; else it is released and allocated anew with `slack` units
+    // on top.  Pointer and capacity change together: both are clear after a failure, whose bytes *bytes then names.
+    hipError_t fit(size_t need, size_t slack = 0, size_t keep_max = 0, size_t unit = sizeof(T), size_t *bytes = nullptr) {
+        if (cap >= need && !(keep_max && cap > keep_max)) return hipSuccess;
+        release();
+        const size_t want = (need + slack) * unit;
+        if (bytes) *bytes = want;
+        const hipError_t e = raw_alloc((void **)&p, want);
+        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e; }
+        cap = need + slack;
+        return hipSuccess;
+    }
+};
+// Device allocations that are made one by one and freed together: the read-dependent arrays of a handle, the temporaries of one call.
+struct Pool {
+    const uvcgpu_region *r; std::vector<void *> blocks; hipError_t last = hipSuccess;
+    explicit Pool(const uvcgpu_region *r_) : r(r_) {}
+    Pool(const Pool &) = delete; Pool &operator=(const Pool &) = delete;
+    ~Pool() { clear(); }
+    void *get(size_t bytes) { void *q = nullptr; last = uvc_dev_malloc(&q, bytes); if (last != hipSuccess) return nullptr; blocks.push_back(q); return q; }
+    template <class T> bool get(T **out, size_t count) { *out = (T *)get(count * sizeof(T)); return *out != nullptr; }
+    void clear() { if (!blocks.empty()) quiesce(r); for (void *q : blocks) (void)uvc_dev_free(q); blocks.clear(); }
+};
+
 struct uvcgpu_region {
     UvcParams P;
     int32_t tid, beg, end;     // state covers [beg, end): end = caller's end + 1 (main.cpp:569)
     int64_t npos;
     std::string refstring;
     std::vector<int32_t> h_rtr; bool h_rtr_valid = false;   // host copy of the repeat tracks as built (begpos / tracklen / unitlen planes), fetched when the record writer first asks
-    UvcRtrWork rw; char *d_rtrwork = nullptr; bool thr_ready = false;   // scratch of the side-array kernels (uvc_rtr.hip)
-    char *h_ref = nullptr; size_t h_ref_cap = 0;                        // page-locked staging of the reference characters
+    UvcRtrWork rw; Buf<char> d_rtrwork{this}; bool thr_ready = false;   // scratch of the side-array kernels (uvc_rtr.hip)
+    Buf<char, true> h_ref{this};                                        // page-locked staging of the reference characters
     hipStream_t stream = nullptr;
+    // the streams (the main one first) and the events of a handle: created and destroyed in one loop over these lists
+    std::array<hipStream_t *, 3> streams() { return { { &stream, &side, &side3 } }; }
+    std::array<hipEvent_t *, 6> events() { return { { &e_fork, &e_join, &e_fork2, &e_join3, &e_stat, &e_alleles } }; }
     hipStream_t side = nullptr, side3 = nullptr; hipEvent_t e_fork = nullptr, e_join = nullptr, e_fork2 = nullptr, e_join3 = nullptr, e_stat = nullptr, e_alleles = nullptr;   // fork/join inside accumulate (see uvc_launch_accumulate)
     // device buffers
-    uint8_t *d_refsym = nullptr; int32_t *d_rtr = nullptr, *d_rtr0 = nullptr, *d_fsum = nullptr, *d_win = nullptr; int64_t *d_baq = nullptr;
-    char *d_state = nullptr; size_t state_bytes = 0;
+    Buf<uint8_t> d_refsym{this}; Buf<int32_t> d_rtr{this}, d_rtr0{this}, d_fsum{this}, d_win{this}; Buf<int64_t> d_baq{this};
+    Buf<char> d_state{this}; SlabLayout L = {};   // the plane slab and its layout for npos (uvc_planes.h)
+    Buf<int32_t> d_err{this};     // RegionDev::err
     int64_t npos_cap = 0;         // positions the side arrays and the slab were allocated for (uvcgpu_region_reset reuses them)
-    size_t bucket_off = 0; bool buckets_clean = false;   // the transient bucket planes (tail of the slab) are left zero by P3b / P5b
-    std::vector<void *> owned;   // read-dependent device allocations
+    bool buckets_clean = false;   // the transient bucket planes (tail of the slab) are left zero by P3b / P5b
+    Pool owned{this};             // read-dependent device allocations
     RegionDev R;
     int32_t *d_dup_units = nullptr; int64_t *d_dup_off = nullptr; int n_dup = 0; int64_t n_dup_work = 0;
-    size_t off[UVC_NUM_FIELD_GROUPS + 1];
     bool has_reads = false, accumulated = false;
     bool reads_given = false;    // set_reads went through for the present region, with or without reads (uvcgpu_region_family_stats)
-    size_t p5flag_off = 0, occ_off = 0;
     // zero fill without what the last accumulate left untouched (RegionDev::dirty, uvc_launch_zero_state)
-    uint8_t *d_dirty = nullptr; ZeroPlane *d_zero_planes = nullptr; int n_zero_planes = 0; int64_t zero_planes_npos = 0;
+    Buf<uint8_t> d_dirty{this}; Buf<ZeroPlane> d_zero_planes{this}; int64_t zero_planes_npos = 0;
     int64_t dirty_npos = 0;      // the region length under which the slab's contents and the marks were written; 0: unknown, fill everything
     bool state_released = false, state_zeroed = false;   // UvcScoreRequest::release_state: planes given up / already zeroed on the side stream (e_join marks the end)
     int64_t last_scored = 0, last_returned = 0;   // record counts of the last score call (uvcgpu_region_last_score_counts)
@@ -75,18 +114,17 @@ struct uvcgpu_region {
     int64_t n_bases = 0;
     UvcProf prof;
     // persistent scoring buffers (grown on demand)
-    char *d_score_scratch = nullptr; size_t score_scratch_bytes = 0;
-    int32_t *d_score_fields = nullptr; int64_t score_capacity = 0; int64_t *d_score_count = nullptr;
-    uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
-    int32_t *d_score_kept = nullptr; int64_t score_kept_capacity = 0;   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields
-    char *d_report = nullptr; size_t d_report_bytes = 0; char *h_report = nullptr; size_t h_report_bytes = 0;   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_score_scratch{this};   // (cap: bytes)
+    Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
+    Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
+    Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
     std::vector<UvcGapRow> gap_rows; std::vector<uint8_t> gap_seq;
     std::vector<UvcIndelAllele> gap_alleles; std::vector<int32_t> gap_allele_row;   // what indel_get_majority yields, sorted by (refpos, symbol)
-    UvcIndelAllele *d_gap_alleles = nullptr; int32_t *d_gap_allele_row = nullptr; int64_t gap_alleles_cap = 0;
-    UvcGapRow *d_gap_rows = nullptr; int64_t gap_rows_cap = 0; uint8_t *d_gap_seq = nullptr; int64_t gap_seq_cap = 0;   // device copies for k_call
+    Buf<UvcIndelAllele> d_gap_alleles{this}; Buf<int32_t> d_gap_allele_row{this}; Buf<UvcGapRow> d_gap_rows{this}; Buf<uint8_t> d_gap_seq{this};   // device copies for k_call
     // haplotype links of the last accumulate (built on first use by hap_tables): hap_bq, hap_fq, hap_f2q of updateByRegion3Aln
     bool hap_ready = false;
     std::vector<UvcHapLinkHost> hap[3];
@@ -94,24 +132,11 @@ struct uvcgpu_region {
 
 static bool stream_is_open(const uvcgpu_region *r);   // a streamed score is open on the handle: accumulate, reset, set_reads and the one-call scores wait for its end
 static void stream_destroy(uvcgpu_region *r);
-static size_t group_bytes(const uvcgpu_region *r, int g) {
-    const size_t n = (size_t)r->npos;
-    switch (g) {
-        case UVC_F_PREP32: return 4 * n * UVC_NPREP32;
-        case UVC_F_PREP64: return 8 * n * UVC_NPREP64;
-        case UVC_F_THRES: return 4 * n * UVC_NTHRES;
-        case UVC_F_SEG32: return 4 * n * UVC_NSEG32 * NSYM;
-        case UVC_F_SEG64: return 8 * n * UVC_NSEG64 * NSYM;
-        case UVC_F_VQ: return 4 * n * UVC_NVQ * NSYM;
-        case UVC_F_BQSUM: return 4 * n * NSYM;
-        case UVC_F_FRAG: return 4 * n * 2 * UVC_NFRAG * NSYM;
-        case UVC_F_FAM: return 4 * n * 2 * UVC_NFAM * NSYM;
-        case UVC_F_FAMINFO32: return 4 * n * UVC_NFAMINFO32 * NSYM;
-        case UVC_F_FAMINFO64: return 8 * n * UVC_NFAMINFO64 * NSYM;
-        case UVC_F_DUPLEX: return 4 * n * UVC_NDUPLEX * NSYM;
-        case UVC_F_RTR: return 4 * n * UVC_NRTR;
-        case UVC_F_BAQ: return 8 * n * 2;
-    }
+static void quiesce(const uvcgpu_region *r) { for (hipStream_t s : { r->stream, r->side, r->side3 }) if (s) (void)hipStreamSynchronize(s); }
+// A reader of the accumulated planes: they exist and the last score did not release them.  `call` heads the text (the calls differ in it alone).
+static int planes_guard(const uvcgpu_region *r, const char *call) {
+    if (!r->accumulated) return fail(UVCGPU_ESTATE, std::string(call) + " before accumulate");
+    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
     return 0;
 }
 
@@ -119,35 +144,14 @@ static size_t group_bytes(const uvcgpu_region *r, int g) {
 // refstring2repeatvec (main.hpp:803-874) + region_repeatvec_to_baq_offsetarr (main.cpp:400-429) run on the device (uvc_rtr.hip); the host
 // only stages the reference characters and, once per handle, turns indel_phred (main.hpp:794-801) into its threshold table.
 namespace {
-template <class T> int upload(uvcgpu_region *r, const std::vector<T> &v, T **out, bool owned = true) {
-    *out = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    hipError_t e = hipMalloc((void **)out, bytes);
-    if (e != hipSuccess) return fail(UVCGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if (owned) r->owned.push_back(*out);
-    if (!v.empty()) { e = hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, r->stream); if (e != hipSuccess) return fail(UVCGPU_EDEVICE, hipGetErrorString(e)); }
-    return 0;
-}
 // device allocation without a host image (the prelude kernels write every element); optionally zero-filled on the stream
 template <class T> int dev_alloc(uvcgpu_region *r, size_t count, T **out, bool zero = false) {
-    *out = nullptr;
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = hipMalloc((void **)out, bytes);
-    if (e != hipSuccess) return fail(UVCGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    r->owned.push_back(*out);
-    if (zero && hipMemsetAsync(*out, 0, bytes, r->stream) != hipSuccess) return fail(UVCGPU_EDEVICE, "hipMemsetAsync");
+    const size_t n = std::max<size_t>(count, 1);
+    if (!r->owned.get(out, n)) return fail(UVCGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(r->owned.last));
+    if (zero && hipMemsetAsync(*out, 0, n * sizeof(T), r->stream) != hipSuccess) return fail(UVCGPU_EDEVICE, "hipMemsetAsync");
     return 0;
 }
-// straight from the caller's array (it stays valid until set_reads returns, which synchronises the stream)
-template <class T> int upload_raw(uvcgpu_region *r, const T *src, size_t count, T **out) {
-    int rc = dev_alloc(r, count, out);
-    if (rc) return rc;
-    if (count && hipMemcpyAsync(*out, src, count * sizeof(T), hipMemcpyHostToDevice, r->stream) != hipSuccess) return fail(UVCGPU_EDEVICE, "hipMemcpyAsync(H2D)");
-    return 0;
-}
-// (the cache hands freed blocks to other handles at once: nothing of this handle may still be running on them)
-void quiesce(uvcgpu_region *r) { if (r->stream) (void)hipStreamSynchronize(r->stream); if (r->side) (void)hipStreamSynchronize(r->side); if (r->side3) (void)hipStreamSynchronize(r->side3); }
-void free_reads(uvcgpu_region *r) { if (!r->owned.empty()) quiesce(r); for (void *p : r->owned) hipFree(p); r->owned.clear(); r->has_reads = false; r->reads_given = false; r->accumulated = false; }
+void free_reads(uvcgpu_region *r) { r->owned.clear(); r->has_reads = false; r->reads_given = false; r->accumulated = false; }
 }  // namespace
 
 extern "C" {
@@ -226,30 +230,19 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
     r->refstring.assign(refseq, (size_t)(end - beg));
     r->accumulated = false; r->gap_ready = false; r->hap_ready = false; r->state_released = false;
     r->h_rtr_valid = false;
-    // one slab for all per-position planes (+ the transient bucket planes), 8-byte groups first
-    const int order[] = { UVC_F_PREP64, UVC_F_SEG64, UVC_F_FAMINFO64, UVC_F_PREP32, UVC_F_THRES, UVC_F_SEG32, UVC_F_VQ, UVC_F_BQSUM, UVC_F_FRAG, UVC_F_FAM, UVC_F_FAMINFO32, UVC_F_DUPLEX };
-    size_t o = 0;
-    for (int g : order) { r->off[g] = o; o += group_bytes(r, g); }
-    r->p5flag_off = o; o += ((size_t)2 * r->npos + 255) & ~(size_t)255;   // one byte per (strand, position): a P5 bucket was filled (k_p5b skips the others); zeroed with the planes
-    r->occ_off = o; o += ((size_t)4 * r->npos + 255) & ~(size_t)255;   // RegionDev::occ, zeroed with the planes
-    r->bucket_off = o; o += (size_t)4 * r->npos * 2 * NSYM * NBUCKETS;
-    r->state_bytes = o;
+    r->L = slab_layout(r->npos);   // one slab for all per-position planes (+ the transient bucket planes)
     // planes that the last score zeroed on the side stream (release_state) stay zero under the new layout when it fits into what was zeroed
-    r->state_zeroed = r->state_zeroed && r->npos <= r->npos_cap && r->state_bytes <= r->zeroed_bytes;
+    r->state_zeroed = r->state_zeroed && r->npos <= r->npos_cap && r->L.total <= r->zeroed_bytes;
     r->buckets_clean = r->state_zeroed;
     const int vmax = r->P.indel_vntr_repeatsize_max, smax = r->P.indel_str_repeatsize_max, bqm = r->P.indel_BQ_max;
-    const size_t n_rtr = (size_t)UVC_NRTR * r->npos;
-    if (r->npos > r->npos_cap) {
-        quiesce(r);
-        for (void *p : { (void *)r->d_refsym, (void *)r->d_rtr, (void *)r->d_rtr0, (void *)r->d_fsum, (void *)r->d_win, (void *)r->d_baq, (void *)r->d_state, (void *)r->d_rtrwork, (void *)r->d_dirty }) if (p) hipFree(p);
-        r->d_dirty = nullptr; r->dirty_npos = 0;
-        r->d_refsym = nullptr; r->d_rtr = r->d_rtr0 = r->d_fsum = r->d_win = nullptr; r->d_baq = nullptr; r->d_state = nullptr; r->d_rtrwork = nullptr; r->npos_cap = 0; r->thr_ready = false;
+    const size_t n_rtr = (size_t)UVC_NRTR * r->npos, n = (size_t)r->npos;
+    if (r->npos > r->npos_cap) {   // every buffer to the new length exactly
+        r->npos_cap = 0; r->dirty_npos = 0; r->thr_ready = false;
         size_t scan_tmp = 0;
         const size_t work_bytes = uvc_rtr_work_bytes(r->npos, vmax, smax, bqm, &scan_tmp);
-        if (hipMalloc((void **)&r->d_refsym, (size_t)r->npos + 1) != hipSuccess || hipMalloc((void **)&r->d_rtr, sizeof(int32_t) * n_rtr) != hipSuccess
-            || hipMalloc((void **)&r->d_rtr0, sizeof(int32_t) * n_rtr) != hipSuccess || hipMalloc((void **)&r->d_fsum, sizeof(int32_t) * 2 * UVC_FSUM_N * (size_t)r->npos) != hipSuccess || hipMalloc((void **)&r->d_win, sizeof(int32_t) * 16 * (size_t)((r->npos + 63) / 64)) != hipSuccess || hipMalloc((void **)&r->d_baq, sizeof(int64_t) * 2 * (size_t)r->npos) != hipSuccess
-            || hipMalloc((void **)&r->d_state, r->state_bytes) != hipSuccess || hipMalloc((void **)&r->d_rtrwork, work_bytes) != hipSuccess
-            || hipMalloc((void **)&r->d_dirty, (size_t)3 * NSYM * (size_t)((r->npos >> UVC_DIRTY_SHIFT) + 2)) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(region planes) failed");
+        if (r->d_refsym.fit(n + 1) != hipSuccess || r->d_rtr.fit(n_rtr) != hipSuccess || r->d_rtr0.fit(n_rtr) != hipSuccess || r->d_fsum.fit(2 * UVC_FSUM_N * n) != hipSuccess
+            || r->d_win.fit(16 * (size_t)((r->npos + 63) / 64)) != hipSuccess || r->d_baq.fit(2 * n) != hipSuccess || r->d_state.fit(r->L.total) != hipSuccess || r->d_rtrwork.fit(work_bytes) != hipSuccess
+            || r->d_dirty.fit((size_t)3 * NSYM * (size_t)((r->npos >> UVC_DIRTY_SHIFT) + 2)) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(region planes) failed");
         uvc_rtr_bind(&r->rw, r->d_rtrwork, r->npos, vmax, smax, bqm, scan_tmp);
         r->npos_cap = r->npos;
     }
@@ -261,31 +254,24 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
     }
     // the reference characters travel from page-locked memory of the handle, so that the copy is a stream operation like the kernels behind it
     const size_t n_ref = (size_t)(end - beg);
-    if (n_ref > r->h_ref_cap) {
-        if (r->h_ref) (void)hipHostFree(r->h_ref);
-        r->h_ref = nullptr; r->h_ref_cap = 0;
-        if (hipHostMalloc((void **)&r->h_ref, n_ref, hipHostMallocDefault) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipHostMalloc(reference staging) failed");
-        r->h_ref_cap = n_ref;
-    }
+    if (r->h_ref.fit(n_ref) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipHostMalloc(reference staging) failed");
     memcpy(r->h_ref, refseq, n_ref);
     HIP_OK(hipMemcpyAsync(r->rw.refchar, r->h_ref, n_ref, hipMemcpyHostToDevice, r->stream));
     {
         const int e = uvc_launch_region_tracks(&r->rw, &r->P, r->npos, r->d_refsym, r->d_rtr0, r->d_baq, r->stream);
         if (e) return fail(UVCGPU_EDEVICE, std::string("side-array kernels: ") + hipGetErrorString((hipError_t)e));
     }
-    int32_t *d_err = r->R.err;
     RegionDev &R = r->R;
     memset(&R, 0, sizeof(R));
     R.beg = r->beg; R.end = r->end; R.npos = r->npos; R.refsym = r->d_refsym; R.rtr = r->d_rtr; R.baq = r->d_baq; R.fsum = r->d_fsum; R.win = r->d_win; R.nwin = (int32_t)((r->npos + 63) / 64);
     char *b = r->d_state;
-    R.prep64 = (int64_t *)(b + r->off[UVC_F_PREP64]); R.seg64 = (int64_t *)(b + r->off[UVC_F_SEG64]); R.faminfo64 = (int64_t *)(b + r->off[UVC_F_FAMINFO64]);
-    R.prep32 = (int32_t *)(b + r->off[UVC_F_PREP32]); R.thres = (int32_t *)(b + r->off[UVC_F_THRES]); R.seg32 = (int32_t *)(b + r->off[UVC_F_SEG32]);
-    R.vq = (int32_t *)(b + r->off[UVC_F_VQ]); R.bqsum = (int32_t *)(b + r->off[UVC_F_BQSUM]); R.frag = (int32_t *)(b + r->off[UVC_F_FRAG]);
-    R.fam = (int32_t *)(b + r->off[UVC_F_FAM]); R.faminfo32 = (int32_t *)(b + r->off[UVC_F_FAMINFO32]); R.duplex = (int32_t *)(b + r->off[UVC_F_DUPLEX]);
-    R.bucket = (int32_t *)(b + r->bucket_off); R.p5flag = (uint8_t *)(b + r->p5flag_off); R.occ = (uint32_t *)(b + r->occ_off);
+#define X(g, m) R.m = (decltype(R.m))(b + r->L.off[UVC_F_##g]);
+    UVC_SLAB_MEMBERS(X)
+#undef X
+    R.bucket = (int32_t *)(b + r->L.bucket_off); R.p5flag = (uint8_t *)(b + r->L.p5flag_off); R.occ = (uint32_t *)(b + r->L.occ_off);
     R.dirty = r->d_dirty; R.ndblk = (int32_t)((r->npos + ((int64_t)1 << UVC_DIRTY_SHIFT) - 1) >> UVC_DIRTY_SHIFT);
-    R.err = d_err;
-    HIP_OK(hipMemsetAsync(d_err, 0, 4, r->stream));
+    R.err = r->d_err;
+    HIP_OK(hipMemsetAsync(R.err, 0, 4, r->stream));
     return 0;   // nothing to wait for: the staging memory belongs to the handle and a handle is rebound only when its streams are idle
 }
 
@@ -296,13 +282,16 @@ static int uvcgpu_region_create_impl(uvcgpu_region_t **out, const UvcParams *par
     memset(&r->prof, 0, sizeof(r->prof));
     memset(&r->R, 0, sizeof(r->R));
     r->P = *params;
-    if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) { delete r; return fail(UVCGPU_EDEVICE, "hipStreamCreate failed (no GPU?)"); }
-    // UVCGPU_ONE_STREAM=1 (diagnosis): no side streams, every kernel of a handle runs alone, so that UVCGPU_TIMING shows undisturbed durations
-    if (getenv("UVCGPU_ONE_STREAM")) { /* side stays null: uvc_launch_accumulate and score run everything on the main stream */ }
-    else if (hipStreamCreateWithFlags(&r->side, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&r->side3, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&r->e_join3, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->e_stat, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->e_alleles, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->e_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->e_join, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->e_fork2, hipEventDisableTiming) != hipSuccess) {
-        uvcgpu_region_destroy(r); return fail(UVCGPU_EDEVICE, "hipStreamCreate / hipEventCreate failed");
+    // UVCGPU_ONE_STREAM=1 (diagnosis): the main stream alone, every kernel of a handle runs there (uvc_launch_accumulate and score see no side
+    // stream), so that UVCGPU_TIMING shows undisturbed durations
+    const bool one_stream = (getenv("UVCGPU_ONE_STREAM") != nullptr);
+    for (hipStream_t *s : r->streams()) {
+        const bool main = (s == &r->stream);
+        if (!main && one_stream) break;
+        if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) { uvcgpu_region_destroy(r); return fail(UVCGPU_EDEVICE, main ? "hipStreamCreate failed (no GPU?)" : "hipStreamCreate / hipEventCreate failed"); }
     }
-    if (hipMalloc((void **)&r->R.err, 4) != hipSuccess) { uvcgpu_region_destroy(r); return fail(UVCGPU_ENOMEM, "hipMalloc failed"); }
+    if (!one_stream) for (hipEvent_t *e : r->events()) if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { uvcgpu_region_destroy(r); return fail(UVCGPU_EDEVICE, "hipStreamCreate / hipEventCreate failed"); }
+    if (r->d_err.fit(1) != hipSuccess) { uvcgpu_region_destroy(r); return fail(UVCGPU_ENOMEM, "hipMalloc failed"); }
     const int rc = configure_region(r, tid, beg, end, refseq);
     if (rc) { uvcgpu_region_destroy(r); return rc; }
     *out = r;
@@ -590,33 +579,19 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
     r->dirty_npos = 0;   // from here on the slab and the marks describe no layout until the caller's launch went through and restores it
     if (selective) {
         if (r->zero_planes_npos != r->npos) {   // the plane table of this layout (once per region length)
-            std::vector<ZeroPlane> v;
-            const size_t n = (size_t)r->npos;
-            auto sym_planes = [&](int g, int nplanes, int elem, int fam) {
-                for (int pl = 0; pl < nplanes; pl++) for (int sy = 0; sy < NSYM; sy++) {
-                    const bool always = (fam == 0 && (sy < UVC_BASE_NN || sy == UVC_LINK_M));
-                    v.push_back({ (unsigned long long)(r->off[g] + ((size_t)pl * NSYM + sy) * n * elem), elem, (int16_t)(always ? -1 : fam), (int16_t)sy });
-                }
-            };
-            for (int pl = 0; pl < UVC_NPREP32; pl++) v.push_back({ (unsigned long long)(r->off[UVC_F_PREP32] + (size_t)pl * n * 4), 4, -1, 0 });
-            for (int pl = 0; pl < UVC_NPREP64; pl++) v.push_back({ (unsigned long long)(r->off[UVC_F_PREP64] + (size_t)pl * n * 8), 8, -1, 0 });
-            // (k_thres stores every threshold of every position, but a handle that is rebound to a region of another length relies on an all-zero slab)
-            for (int pl = 0; pl < UVC_NTHRES; pl++) v.push_back({ (unsigned long long)(r->off[UVC_F_THRES] + (size_t)pl * n * 4), 4, -1, 0 });
-            sym_planes(UVC_F_SEG32, UVC_NSEG32, 4, 0); sym_planes(UVC_F_SEG64, UVC_NSEG64, 8, 0); sym_planes(UVC_F_VQ, UVC_NVQ, 4, 0); sym_planes(UVC_F_BQSUM, 1, 4, 0);
-            sym_planes(UVC_F_FRAG, 2 * UVC_NFRAG, 4, 0); sym_planes(UVC_F_FAM, 2 * UVC_NFAM, 4, 0);
-            sym_planes(UVC_F_FAMINFO32, UVC_NFAMINFO32, 4, 1); sym_planes(UVC_F_FAMINFO64, UVC_NFAMINFO64, 8, 1); sym_planes(UVC_F_DUPLEX, UVC_NDUPLEX, 4, 2);
-            v.push_back({ (unsigned long long)r->p5flag_off, 1, -1, 0 }); v.push_back({ (unsigned long long)(r->p5flag_off + n), 1, -1, 0 });
-            v.push_back({ (unsigned long long)r->occ_off, 4, -1, 0 });
-            if (r->d_zero_planes) { quiesce(r); hipFree(r->d_zero_planes); r->d_zero_planes = nullptr; }
-            HIP_OK(hipMalloc(&r->d_zero_planes, v.size() * sizeof(ZeroPlane)));
-            HIP_OK(hipMemcpy(r->d_zero_planes, v.data(), v.size() * sizeof(ZeroPlane), hipMemcpyHostToDevice));
-            r->n_zero_planes = (int)v.size(); r->zero_planes_npos = r->npos;
+            ZeroPlane v[UVC_N_ZERO_PLANES];
+            zero_plane_rows(r->L, r->npos, v);
+            r->zero_planes_npos = 0;
+            const hipError_t e = r->d_zero_planes.fit(UVC_N_ZERO_PLANES);
+            if (e != hipSuccess) return fail(UVCGPU_EDEVICE, std::string("hipMalloc(zero-fill table): ") + hipGetErrorString(e));
+            HIP_OK(hipMemcpy(r->d_zero_planes, v, sizeof(v), hipMemcpyHostToDevice));
+            r->zero_planes_npos = r->npos;
         }
-        uvc_launch_zero_state(r->d_state, r->d_zero_planes, r->n_zero_planes, r->d_dirty, r->R.ndblk, r->npos, s);
+        uvc_launch_zero_state(r->d_state, r->d_zero_planes, UVC_N_ZERO_PLANES, r->d_dirty, r->R.ndblk, r->npos, s);
         if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "zero fill of the planes failed");
-        if (!r->buckets_clean) HIP_OK(hipMemsetAsync(r->d_state + r->bucket_off, 0, r->state_bytes - r->bucket_off, s));
+        if (!r->buckets_clean) HIP_OK(hipMemsetAsync(r->d_state + r->L.bucket_off, 0, r->L.total - r->L.bucket_off, s));
     } else {
-        HIP_OK(hipMemsetAsync(r->d_state, 0, r->buckets_clean ? r->bucket_off : r->state_bytes, s));
+        HIP_OK(hipMemsetAsync(r->d_state, 0, r->buckets_clean ? r->L.bucket_off : r->L.total, s));
     }
     HIP_OK(hipMemsetAsync(r->d_dirty, 0, n_dirty, s));
     return 0;
@@ -650,13 +625,13 @@ static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
 
 int uvcgpu_region_check_presence(uvcgpu_region_t *r, int64_t *n_violations) {
     if (!r || !n_violations) return fail(UVCGPU_EINVAL, "bad argument");
-    if (!r->accumulated || r->state_released) return fail(UVCGPU_ESTATE, "check_presence needs the planes of an accumulate");
+    if (planes_guard(r, "check_presence")) return fail(UVCGPU_ESTATE, "check_presence needs the planes of an accumulate");
+    Pool tmp(r);   // (waits for the streams, then frees, on every return path)
     unsigned long long *d = nullptr, h = 0;
-    HIP_OK(hipMalloc((void **)&d, 8));
+    if (!tmp.get(&d, 1)) return fail(UVCGPU_EDEVICE, std::string("hipMalloc(violation count): ") + hipGetErrorString(tmp.last));
     int rc = 0;
     if (hipMemsetAsync(d, 0, 8, r->stream) != hipSuccess) rc = fail(UVCGPU_EDEVICE, "hipMemsetAsync");
     if (!rc) { uvc_launch_check_presence(&r->R, d, r->stream); uvc_launch_check_dirty(&r->R, d, r->stream); if (hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, r->stream) != hipSuccess || hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(UVCGPU_EDEVICE, "check_presence"); }
-    hipFree(d);
     *n_violations = (int64_t)h;
     return rc;
 }
@@ -697,63 +672,44 @@ int uvcgpu_region_sync(uvcgpu_region_t *r) {
 
 int64_t uvcgpu_region_field_bytes(const uvcgpu_region_t *r, int32_t g) {
     if (!r || g < 0 || g >= UVC_NUM_FIELD_GROUPS) return -1;
-    if (g != UVC_F_RTR && g != UVC_F_BAQ && !r->accumulated) return -1;
-    return (int64_t)group_bytes(r, g);
+    if (uvc_group_in_slab(g) && !r->accumulated) return -1;
+    return (int64_t)uvc_group_bytes(g, r->npos);
 }
 
 static int uvcgpu_region_fetch_impl(uvcgpu_region_t *r, int32_t g, void *dst, int64_t dst_bytes) {
     if (!r || !dst || g < 0 || g >= UVC_NUM_FIELD_GROUPS) return fail(UVCGPU_EINVAL, "bad argument");
-    if (g != UVC_F_RTR && g != UVC_F_BAQ && !r->accumulated) return fail(UVCGPU_ESTATE, "fetch before accumulate");
-    if (g != UVC_F_RTR && g != UVC_F_BAQ && r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
-    if ((int64_t)group_bytes(r, g) != dst_bytes) return fail(UVCGPU_EINVAL, "bad destination size");
+    if (uvc_group_in_slab(g)) { const int rcg = planes_guard(r, "fetch"); if (rcg) return rcg; }
+    if ((int64_t)uvc_group_bytes(g, r->npos) != dst_bytes) return fail(UVCGPU_EINVAL, "bad destination size");
     int rc = uvcgpu_region_sync(r);
     if (rc) return rc;
-    const void *src = (g == UVC_F_RTR) ? (const void *)(r->accumulated ? r->d_rtr : r->d_rtr0) /* P1b's edit of indelphred exists after accumulate only */ : (g == UVC_F_BAQ) ? (const void *)r->d_baq : (const void *)(r->d_state + r->off[g]);
+    const void *src = (g == UVC_F_RTR) ? (const void *)(r->accumulated ? r->d_rtr : r->d_rtr0) /* P1b's edit of indelphred exists after accumulate only */ : (g == UVC_F_BAQ) ? (const void *)r->d_baq : (const void *)(r->d_state + r->L.off[g]);
     HIP_OK(hipMemcpy(dst, src, (size_t)dst_bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
 // ---- columns of chosen positions (the read side of the record writer, uvc_vcf.cpp) ----
-namespace {
-int group_elem(int g) { return (g == UVC_F_PREP64 || g == UVC_F_SEG64 || g == UVC_F_FAMINFO64 || g == UVC_F_BAQ) ? 8 : 4; }
-int group_planes(int g) {
-    switch (g) {
-        case UVC_F_PREP32: return UVC_NPREP32; case UVC_F_PREP64: return UVC_NPREP64; case UVC_F_THRES: return UVC_NTHRES; case UVC_F_SEG32: return UVC_NSEG32 * NSYM;
-        case UVC_F_SEG64: return UVC_NSEG64 * NSYM; case UVC_F_VQ: return UVC_NVQ * NSYM; case UVC_F_BQSUM: return NSYM; case UVC_F_FRAG: return 2 * UVC_NFRAG * NSYM;
-        case UVC_F_FAM: return 2 * UVC_NFAM * NSYM; case UVC_F_FAMINFO32: return UVC_NFAMINFO32 * NSYM; case UVC_F_FAMINFO64: return UVC_NFAMINFO64 * NSYM; case UVC_F_DUPLEX: return UVC_NDUPLEX * NSYM;
-    }
-    return 0;   // RTR / BAQ are not part of a row
-}
-}
-int32_t uvcgpu_region_column_base(int32_t g) {
-    if (g < 0 || g >= UVC_NUM_FIELD_GROUPS || group_planes(g) == 0) return -1;
-    int32_t at = 0;
-    for (int q = 0; q < g; q++) at += group_planes(q);
-    return at;
-}
-int32_t uvcgpu_region_n_columns(void) { int32_t at = 0; for (int q = 0; q < UVC_NUM_FIELD_GROUPS; q++) at += group_planes(q); return at; }
+int32_t uvcgpu_region_column_base(int32_t g) { return (g < 0 || g >= UVC_NUM_FIELD_GROUPS) ? -1 : uvc_group_first_column(g); }
+int32_t uvcgpu_region_n_columns(void) { return UVC_N_COLUMNS; }
 static int uvcgpu_region_fetch_columns_impl(uvcgpu_region_t *r, const int32_t *refpos, int64_t n, int64_t *dst) {
     if (!r || n < 0 || (n > 0 && (!refpos || !dst))) return fail(UVCGPU_EINVAL, "bad argument");
-    if (!r->accumulated) return fail(UVCGPU_ESTATE, "fetch before accumulate");
-    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    { const int rcg = planes_guard(r, "fetch"); if (rcg) return rcg; }
     if (n == 0) return 0;
     int rc = uvcgpu_region_sync(r);
     if (rc) return rc;
-    const int32_t ncol = uvcgpu_region_n_columns();
+    const int32_t ncol = UVC_N_COLUMNS;
     const char *base[UVC_NUM_FIELD_GROUPS]; int32_t first[UVC_NUM_FIELD_GROUPS + 1], elem[UVC_NUM_FIELD_GROUPS];
-    int32_t at = 0;
-    for (int g = 0; g < UVC_NUM_FIELD_GROUPS; g++) { first[g] = at; at += group_planes(g); elem[g] = group_elem(g); base[g] = (group_planes(g) ? r->d_state + r->off[g] : r->d_state); }
-    first[UVC_NUM_FIELD_GROUPS] = at;
+    for (int g = 0; g <= UVC_NUM_FIELD_GROUPS; g++) first[g] = uvc_columns_before(g);
+    for (int g = 0; g < UVC_NUM_FIELD_GROUPS; g++) { elem[g] = uvc_group_elem(g); base[g] = r->d_state + r->L.off[g]; }   // (a group outside the slab has no columns)
     std::vector<int32_t> xs((size_t)n);
     for (int64_t i = 0; i < n; i++) xs[(size_t)i] = refpos[i] - r->beg;   // out of range -> a row of zeros (checked in the kernel)
+    Pool tmp(r);   // (waits for the streams, then frees, on every return path: a launched kernel may still write the blocks when a later step fails)
     int32_t *d_xs = nullptr; long long *d_out = nullptr;
-    if (hipMalloc((void **)&d_xs, sizeof(int32_t) * (size_t)n) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(column positions) failed");
-    if (hipMalloc((void **)&d_out, sizeof(long long) * (size_t)n * ncol) != hipSuccess) { hipFree(d_xs); return fail(UVCGPU_ENOMEM, "hipMalloc(columns) failed"); }
+    if (!tmp.get(&d_xs, (size_t)n)) return fail(UVCGPU_ENOMEM, "hipMalloc(column positions) failed");
+    if (!tmp.get(&d_out, (size_t)n * ncol)) return fail(UVCGPU_ENOMEM, "hipMalloc(columns) failed");
     hipError_t e = hipMemcpyAsync(d_xs, xs.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, r->stream);
     if (e == hipSuccess) { uvc_launch_gather_columns(base, first, elem, r->npos, d_xs, n, d_out, r->stream); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(dst, d_out, sizeof(long long) * (size_t)n * ncol, hipMemcpyDeviceToHost, r->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    hipFree(d_xs); hipFree(d_out);
     if (e != hipSuccess) return fail(UVCGPU_EDEVICE, hipGetErrorString(e));
     return 0;
 }
@@ -761,19 +717,18 @@ static int uvcgpu_region_fetch_columns_impl(uvcgpu_region_t *r, const int32_t *r
 // [refpos_beg, refpos_end), see k_block_stats
 int uvcgpu_region_block_stats_(uvcgpu_region_t *r, int32_t refpos_beg, int32_t refpos_end, int32_t *dst) {
     if (!r || !dst || refpos_end < refpos_beg) return fail(UVCGPU_EINVAL, "bad argument");
-    if (!r->accumulated) return fail(UVCGPU_ESTATE, "fetch before accumulate");
-    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    { const int rcg = planes_guard(r, "fetch"); if (rcg) return rcg; }
     const int64_t n = (int64_t)refpos_end - refpos_beg;
     if (n == 0) return 0;
     int rc = uvcgpu_region_sync(r);
     if (rc) return rc;
+    Pool tmp(r);   // (waits for the streams, then frees, on every return path)
     int32_t *d = nullptr;
-    if (hipMalloc((void **)&d, sizeof(int32_t) * 10 * (size_t)n) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(block stats) failed");
+    if (!tmp.get(&d, 10 * (size_t)n)) return fail(UVCGPU_ENOMEM, "hipMalloc(block stats) failed");
     uvc_launch_block_stats(&r->R, &r->P, (int64_t)refpos_beg - r->beg, n, d, r->stream);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(dst, d, sizeof(int32_t) * 10 * (size_t)n, hipMemcpyDeviceToHost, r->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    hipFree(d);
     if (e != hipSuccess) return fail(UVCGPU_EDEVICE, hipGetErrorString(e));
     return 0;
 }
@@ -781,8 +736,7 @@ int uvcgpu_region_block_stats_(uvcgpu_region_t *r, int32_t refpos_beg, int32_t r
 // dst receives the windows' rows back to back.
 int uvcgpu_region_block_stats_windows_(uvcgpu_region_t *r, const int32_t *win, int64_t n_win, int32_t *dst) {
     if (!r || !win || !dst || n_win < 0 || n_win > INT32_MAX) return fail(UVCGPU_EINVAL, "bad argument");
-    if (!r->accumulated) return fail(UVCGPU_ESTATE, "fetch before accumulate");
-    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    { const int rcg = planes_guard(r, "fetch"); if (rcg) return rcg; }
     std::vector<long long> tab((size_t)(2 * n_win));
     int64_t n = 0;
     for (int64_t k = 0; k < n_win; k++) {
@@ -792,16 +746,13 @@ int uvcgpu_region_block_stats_windows_(uvcgpu_region_t *r, const int32_t *win, i
     if (n == 0) return 0;
     int rc = uvcgpu_region_sync(r);
     if (rc) return rc;
+    Pool tmp(r);   // declared behind `tab`: it waits for the streams before `tab` goes, on every return path, and then frees the two blocks
     long long *d_tab = nullptr; int32_t *d = nullptr;
-    if (hipMalloc((void **)&d_tab, sizeof(long long) * tab.size()) != hipSuccess || hipMalloc((void **)&d, sizeof(int32_t) * 10 * (size_t)n) != hipSuccess) {
-        if (d_tab) hipFree(d_tab);
-        return fail(UVCGPU_ENOMEM, "hipMalloc(block stats) failed");
-    }
+    if (!tmp.get(&d_tab, tab.size()) || !tmp.get(&d, 10 * (size_t)n)) return fail(UVCGPU_ENOMEM, "hipMalloc(block stats) failed");
     hipError_t e = hipMemcpyAsync(d_tab, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, r->stream);
     if (e == hipSuccess) { uvc_launch_block_stats_windows(&r->R, &r->P, d_tab, (int)n_win, n, d, r->stream); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(dst, d, sizeof(int32_t) * 10 * (size_t)n, hipMemcpyDeviceToHost, r->stream);
-    const hipError_t e2 = hipStreamSynchronize(r->stream);   // also when a step failed: `tab` and the two blocks are in use until the stream is idle
-    hipFree(d); hipFree(d_tab);
+    const hipError_t e2 = hipStreamSynchronize(r->stream);
     if (e != hipSuccess || e2 != hipSuccess) return fail(UVCGPU_EDEVICE, hipGetErrorString(e != hipSuccess ? e : e2));
     return 0;
 }
@@ -816,13 +767,13 @@ int uvcgpu_pin_host_buffer(void *p, int64_t bytes) {
 int uvcgpu_host_alloc(void **p, int64_t bytes) {
     if (!p || bytes <= 0) return fail(UVCGPU_EINVAL, "bad argument");
     *p = nullptr;
-    hipError_t e = hipHostMalloc(p, (size_t)bytes, hipHostMallocDefault);
+    hipError_t e = Buf<char, true>::raw_alloc(p, (size_t)bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return fail(UVCGPU_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
     return 0;
 }
 int uvcgpu_host_free(void *p) {
     if (!p) return 0;
-    hipError_t e = hipHostFree(p);
+    hipError_t e = Buf<char, true>::raw_free(p);
     if (e != hipSuccess) { (void)hipGetLastError(); if (getenv("UVCGPU_DEBUG")) fprintf(stderr, "[uvcgpu] hipHostFree: %s\n", hipGetErrorString(e)); return fail(UVCGPU_EDEVICE, std::string("hipHostFree: ") + hipGetErrorString(e)); }
     return 0;
 }
@@ -933,17 +884,10 @@ static int gap_tables(uvcgpu_region_t *r) {
         g0 = g1;
     }
     const int64_t na = (int64_t)r->gap_alleles.size();
-    if (na > r->gap_alleles_cap) {
-        if (r->d_gap_alleles) hipFree(r->d_gap_alleles);
-        if (r->d_gap_allele_row) hipFree(r->d_gap_allele_row);
-        r->d_gap_alleles = nullptr; r->d_gap_allele_row = nullptr; r->gap_alleles_cap = 0;
-        HIP_OK(hipMalloc((void **)&r->d_gap_alleles, sizeof(UvcIndelAllele) * (size_t)(na + 64)));
-        HIP_OK(hipMalloc((void **)&r->d_gap_allele_row, sizeof(int32_t) * (size_t)(na + 64)));
-        r->gap_alleles_cap = na + 64;
-    }
     const int64_t nr = (int64_t)r->gap_rows.size(), ns = (int64_t)r->gap_seq.size();
-    if (nr > r->gap_rows_cap) { if (r->d_gap_rows) hipFree(r->d_gap_rows); r->d_gap_rows = nullptr; r->gap_rows_cap = 0; HIP_OK(hipMalloc((void **)&r->d_gap_rows, sizeof(UvcGapRow) * (size_t)(nr + 64))); r->gap_rows_cap = nr + 64; }
-    if (ns > r->gap_seq_cap) { if (r->d_gap_seq) hipFree(r->d_gap_seq); r->d_gap_seq = nullptr; r->gap_seq_cap = 0; HIP_OK(hipMalloc((void **)&r->d_gap_seq, (size_t)(ns + 64))); r->gap_seq_cap = ns + 64; }
+    // (64 elements of slack each; the alleles and their rows grow together)
+    for (const hipError_t e : { r->d_gap_alleles.fit((size_t)na, 64), r->d_gap_allele_row.fit((size_t)na, 64), r->d_gap_rows.fit((size_t)nr, 64), r->d_gap_seq.fit((size_t)ns, 64) })
+        if (e != hipSuccess) return fail(UVCGPU_EDEVICE, std::string("hipMalloc(InDel allele tables): ") + hipGetErrorString(e));
     if (nr) HIP_OK(hipMemcpyAsync(r->d_gap_rows, r->gap_rows.data(), sizeof(UvcGapRow) * (size_t)nr, hipMemcpyHostToDevice, cs));
     if (ns) HIP_OK(hipMemcpyAsync(r->d_gap_seq, r->gap_seq.data(), (size_t)ns, hipMemcpyHostToDevice, cs));
     if (nr || ns) HIP_OK(hipStreamSynchronize(cs));
@@ -975,15 +919,14 @@ static int uvcgpu_region_indel_alleles_impl(uvcgpu_region_t *r, UvcGapRow *rows,
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static int hap_tables(uvcgpu_region_t *r) {
     if (r->hap_ready) return 0;
-    if (!r->accumulated) return fail(UVCGPU_ESTATE, "haplotype links before accumulate");
-    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    { const int rcg = planes_guard(r, "haplotype links"); if (rcg) return rcg; }
     const RegionDev &R = r->R;
     std::vector<int32_t> events;
     const bool timing = (getenv("UVCGPU_TIMING") != nullptr);
     double t_prev = now_s();
     auto lap = [&](const char *what, long long n) { if (timing) { const double t = now_s(); fprintf(stderr, "[uvcgpu hap_links] %-34s %8.2f ms (%lld)\n", what, 1e3 * (t - t_prev), n); t_prev = t; } };
-    struct Tmp { std::vector<void *> p; hipStream_t s; ~Tmp() { (void)hipStreamSynchronize(s); for (void *q : p) hipFree(q); } } tmp; tmp.s = r->stream;
-    auto get = [&](size_t bytes) -> void * { void *q = nullptr; if (hipMalloc(&q, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr; tmp.p.push_back(q); return q; };
+    Pool tmp(r);   // (waits for the streams, then frees, on every return path)
+    auto get = [&](size_t bytes) { return tmp.get(std::max<size_t>(bytes, 8)); };
     for (int units = 0; units < 2; units++) {
         // the fragment links come from P3 (updateByAlns3UsingBQ, main.hpp:3691), the family links from P5, which updateByAlns3UsingFQ runs
         // only for a VCF run as well (main.hpp:3371-3521): a FASTQ-only run has no links
@@ -1056,13 +999,7 @@ int64_t uvcgpu_region_score_ranges_size(const uvcgpu_region_t *r, const UvcScore
 // the caller's pageable memory lets the runtime map those heap pages for the GPU (read-only, as a copy source), and heap pages come back to the
 // caller in other roles -- as a records buffer the next copy writes to.  `at` advances through the staging buffer within one call.
 static int stage_upload(uvcgpu_region_t *r, void *dst, const void *src, size_t bytes, size_t &at, size_t total) {
-    if (total > r->h_stage_cap) {
-        if (r->h_stage) { (void)hipStreamSynchronize(r->stream); (void)hipHostFree(r->h_stage); }
-        r->h_stage = nullptr; r->h_stage_cap = 0;
-        const size_t want = total + total / 2 + 4096;
-        if (hipHostMalloc((void **)&r->h_stage, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, "hipHostMalloc(staging)"); }
-        r->h_stage_cap = want;
-    }
+    if (r->h_stage.fit(total, total / 2 + 4096) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipHostMalloc(staging)");
     memcpy(r->h_stage + at, src, bytes);
     if (hipMemcpyAsync(dst, r->h_stage + at, bytes, hipMemcpyHostToDevice, r->stream) != hipSuccess) return fail(UVCGPU_EDEVICE, "hipMemcpyAsync(staging)");
     at += (bytes + 63) & ~(size_t)63;
@@ -1072,24 +1009,17 @@ static int stage_upload(uvcgpu_region_t *r, void *dst, const void *src, size_t b
 // `ranges` (uvcgpu_region_score_ranges) or NULL (uvcgpu_region_score): everything but the group axis is the same call
 // What a score request becomes before any scoring kernel runs -- the checked request, the ranges' device table, the caller's alleles merged
 // with the region's, tumor keys, force-output sites, all uploaded through the staging buffer -- for the one call and for a stream alike.
-// The temporaries go back to the caching allocator, which hands them to other handles at once: the destructor drains the stream first
-// (async copies, kernels that read the blocks), then frees them.
+// The temporaries (the merged alleles and their rows, the tumor keys, the force-output sites, the ranges) live in a pool of the call, which
+// drains the handle's streams (async copies, kernels that read the blocks) before it frees them.
 struct ScorePrep {
-    uvcgpu_region *r = nullptr;
     UvcScoreRequest rq; std::vector<UvcScoreRangeDev> rtab; int64_t npos_scored = 0;
-    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; UvcScoreRangeDev *d_rg = nullptr;
+    std::unique_ptr<Pool> tmp;
     UvcScoreIn in = {};   // what the score launchers take: views of the above and of the handle (scratch: set where the scratch is allocated)
-    ~ScorePrep() {
-        if (!r) return;
-        if (d_al || d_al_row || d_tk || d_fs || d_rg) { (void)hipStreamSynchronize(r->stream); if (r->side) (void)hipStreamSynchronize(r->side); }
-        if (d_al) hipFree(d_al); if (d_al_row) hipFree(d_al_row); if (d_tk) hipFree(d_tk); if (d_fs) hipFree(d_fs); if (d_rg) hipFree(d_rg);
-    }
 };
 static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, ScorePrep &p) {
-    if (!r->accumulated) return fail(UVCGPU_ESTATE, "score before accumulate");
-    if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    { const int rcg = planes_guard(r, "score"); if (rcg) return rcg; }
     if (stream_is_open(r)) return fail(UVCGPU_ESTATE, "a score stream is open on this handle (uvcgpu_score_stream_end closes it)");
-    p.r = r;
+    p.tmp.reset(new Pool(r));
     UvcScoreRequest &rq = p.rq; memset(&rq, 0, sizeof(rq)); rq.pos_beg = -1;
     if (req) rq = *req;
     std::vector<UvcScoreRangeDev> &rtab = p.rtab;   // ranges call: the device table; npos_scored = the compact length
@@ -1117,7 +1047,8 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
     }
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
-    UvcIndelAllele *&d_al = p.d_al; int32_t *&d_al_row = p.d_al_row; UvcTumorKey *&d_tk = p.d_tk; int32_t *&d_fs = p.d_fs; UvcScoreRangeDev *&d_rg = p.d_rg;
+    UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; UvcScoreRangeDev *d_rg = nullptr;
+    auto no_room = [&] { return fail(UVCGPU_EDEVICE, std::string("hipMalloc(score request): ") + hipGetErrorString(p.tmp->last)); };
     std::vector<UvcIndelAllele> merged; std::vector<int32_t> merged_row;
     const UvcIndelAllele *use_al = r->d_gap_alleles; const int32_t *use_row = r->d_gap_allele_row; int64_t n_al = (int64_t)r->gap_alleles.size();
     // one staging layout per call (an earlier call's copies are complete: score synchronises before it returns)
@@ -1136,8 +1067,7 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
             while (j < rq.n_indel_alleles && !less(key, rq.indel_alleles[j])) { merged.push_back(rq.indel_alleles[j]); merged_row.push_back(-1); j++; }
         }
         n_al = (int64_t)merged.size();
-        HIP_OK(hipMalloc((void **)&d_al, sizeof(UvcIndelAllele) * (size_t)n_al));
-        HIP_OK(hipMalloc((void **)&d_al_row, sizeof(int32_t) * (size_t)n_al));
+        if (!p.tmp->get(&d_al, (size_t)n_al) || !p.tmp->get(&d_al_row, (size_t)n_al)) return no_room();
         { int rc1 = stage_upload(r, d_al, merged.data(), sizeof(UvcIndelAllele) * (size_t)n_al, stage_at, stage_total); if (rc1) return rc1; }
         { int rc1 = stage_upload(r, d_al_row, merged_row.data(), sizeof(int32_t) * (size_t)n_al, stage_at, stage_total); if (rc1) return rc1; }
         use_al = d_al; use_row = d_al_row;
@@ -1147,38 +1077,28 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
             const UvcTumorKey &a = rq.tumor_keys[q - 1], &b = rq.tumor_keys[q];
             if (a.refpos > b.refpos || (a.refpos == b.refpos && a.symbol > b.symbol)) return fail(UVCGPU_EINVAL, "tumor_keys must be sorted by (refpos, symbol)");
         }
-        HIP_OK(hipMalloc((void **)&d_tk, sizeof(UvcTumorKey) * rq.n_tumor_keys));
+        if (!p.tmp->get(&d_tk, (size_t)rq.n_tumor_keys)) return no_room();
         { int rc1 = stage_upload(r, d_tk, rq.tumor_keys, sizeof(UvcTumorKey) * (size_t)rq.n_tumor_keys, stage_at, stage_total); if (rc1) return rc1; }
     }
     if (rq.n_force_sites < 0 || (rq.n_force_sites > 0 && !rq.force_sites)) return fail(UVCGPU_EINVAL, "force_sites: bad count or NULL array");
     if (rq.n_force_sites > 0) {   // force-output sites: sorted zerobased_pos values, uploaded like the tumor keys (k_force_mask makes the bit mask)
         if (r->P.tumor_vcf_is_provided) return fail(UVCGPU_EINVAL, "force_sites cannot go with tumor_vcf_is_provided (the normal sample's gate is the rescue set)");
         for (int64_t q = 1; q < rq.n_force_sites; q++) if (rq.force_sites[q] < rq.force_sites[q - 1]) return fail(UVCGPU_EINVAL, "force_sites must be sorted ascending");
-        HIP_OK(hipMalloc((void **)&d_fs, sizeof(int32_t) * (size_t)rq.n_force_sites));
+        if (!p.tmp->get(&d_fs, (size_t)rq.n_force_sites)) return no_room();
         { int rc1 = stage_upload(r, d_fs, rq.force_sites, sizeof(int32_t) * (size_t)rq.n_force_sites, stage_at, stage_total); if (rc1) return rc1; }
     }
     if (!rtab.empty()) {   // the ranges, through the staging buffer like the keys and the sites (k_range_map makes the position table)
-        HIP_OK(hipMalloc((void **)&d_rg, sizeof(UvcScoreRangeDev) * rtab.size()));
+        if (!p.tmp->get(&d_rg, rtab.size())) return no_room();
         { int rc1 = stage_upload(r, d_rg, rtab.data(), sizeof(UvcScoreRangeDev) * rtab.size(), stage_at, stage_total); if (rc1) return rc1; }
     }
     p.in = UvcScoreIn{ &r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, nullptr, d_fs, d_rg, (int64_t)rtab.size(), npos_scored };
     return 0;
 }
-// One buffer of the score paths, `have` units of `unit` bytes each: device memory, or page-locked host memory with `host`.  It stays when
-// it holds `need` units and, with keep_max, no more than keep_max; else it is released and allocated anew with `slack` units on top.
-// Pointer and size change together (both clear after a failure, which returns `err` with the size in the message).
-extern "C++" template <class T, class N>
-static int fit_buffer(T *&p, N &have, N need, N slack, N keep_max, size_t unit, bool host, int err, const char *what) {
-    if (have >= need && !(keep_max && have > keep_max)) return 0;
-    if (p) { if (host) (void)hipHostFree(p); else (void)hipFree(p); }
-    p = nullptr; have = 0;
-    const size_t bytes = (size_t)(need + slack) * unit;
-    if ((host ? hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) : hipMalloc((void **)&p, bytes)) != hipSuccess) {
-        (void)hipGetLastError(); p = nullptr;
-        return fail(err, std::string(what) + " (" + std::to_string(bytes) + " bytes)");
-    }
-    have = need + slack;
-    return 0;
+// Buf::fit for the score paths, whose failures name the size: `err` with "what (N bytes)"
+extern "C++" template <class B>
+static int fit_buffer(B &b, size_t need, size_t slack, size_t keep_max, size_t unit, int err, const std::string &what) {
+    size_t bytes = 0;
+    return b.fit(need, slack, keep_max, unit, &bytes) == hipSuccess ? 0 : fail(err, what + " (" + std::to_string(bytes) + " bytes)");
 }
 static const size_t SCORE_RECORD_BYTES = sizeof(int32_t) * UVC_NUM_SCORE_FIELDS;   // one record of a [fields][capacity] array
 // UvcScoreRequest::release_state: zero the planes on the side stream for the next accumulate, under the copies of the records.  The side
@@ -1186,7 +1106,7 @@ static const size_t SCORE_RECORD_BYTES = sizeof(int32_t) * UVC_NUM_SCORE_FIELDS;
 static bool queue_release_state(uvcgpu_region *r, bool stream_already_ordered) {
     if (!stream_already_ordered && (hipEventRecord(r->e_fork, r->stream) != hipSuccess || hipStreamWaitEvent(r->side, r->e_fork, 0) != hipSuccess)) return false;
     if (zero_state(r, r->side) != 0 || hipEventRecord(r->e_join, r->side) != hipSuccess) return false;
-    r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->state_bytes; r->dirty_npos = r->npos;
+    r->state_released = true; r->state_zeroed = true; r->zeroed_bytes = r->L.total; r->dirty_npos = r->npos;
     return true;
 }
 static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *req, const UvcScoreRange *ranges, int64_t n_ranges, UvcScoreOut *out) {
@@ -1198,29 +1118,28 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
     // device capacity: the caller's in the plain form; with kept_only the caller's buffer only has to hold the kept groups, the device
     // array every record -- start from a guess and grow once if the count says so
     int64_t cap = std::max<int64_t>(out->capacity, 1);
-    if (kept_only) cap = std::max<int64_t>(std::max<int64_t>(cap, r->score_capacity), npos_scored / 8 + 4096);
+    if (kept_only) cap = std::max<int64_t>(std::max<int64_t>(cap, (int64_t)r->d_score_fields.cap), npos_scored / 8 + 4096);
     int rc = 0;
     int64_t cnt[2] = { 0, 0 };
     for (int attempt = 0; attempt < 2 && !rc; attempt++) {
-        const int64_t none = 0;
-        if ((rc = fit_buffer(r->d_score_fields, r->score_capacity, cap, none, none, SCORE_RECORD_BYTES, false, UVCGPU_EDEVICE, "score: hipMalloc of the records"))) break;
+        if ((rc = fit_buffer(r->d_score_fields, (size_t)cap, 0, 0, SCORE_RECORD_BYTES, UVCGPU_EDEVICE, "score: hipMalloc of the records"))) break;
         // the kept copy has the pitch of the records: exactly their capacity
-        if (kept_only && (rc = fit_buffer(r->d_score_kept, r->score_kept_capacity, r->score_capacity, none, r->score_capacity, SCORE_RECORD_BYTES, false, UVCGPU_EDEVICE, "score: hipMalloc of the kept records"))) break;
+        if (kept_only && (rc = fit_buffer(r->d_score_kept, r->d_score_fields.cap, 0, r->d_score_fields.cap, SCORE_RECORD_BYTES, UVCGPU_EDEVICE, "score: hipMalloc of the kept records"))) break;
         // the staged rows of the scoring kernels are sized by the record capacity (and the groups of the request)
-        const size_t need = uvc_score_scratch_bytes(npos_scored, r->score_capacity);
-        if ((rc = fit_buffer(r->d_score_scratch, r->score_scratch_bytes, need, need / 8, (size_t)0, 1, false, UVCGPU_EDEVICE, "score: hipMalloc of the scratch"))) break;
-        r->d_score_count = (int64_t *)r->d_score_scratch;   // the record counts head the scratch (zeroed with the scan states)
-        HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos_scored, r->score_capacity), r->stream));
+        const size_t need = uvc_score_scratch_bytes(npos_scored, (int64_t)r->d_score_fields.cap);
+        if ((rc = fit_buffer(r->d_score_scratch, need, need / 8, 0, 1, UVCGPU_EDEVICE, "score: hipMalloc of the scratch"))) break;
+        r->d_score_count = (int64_t *)r->d_score_scratch.p;   // the record counts head the scratch (zeroed with the scan states)
+        HIP_OK(hipMemsetAsync(r->d_score_scratch, 0, uvc_score_scratch_zero_bytes(npos_scored, (int64_t)r->d_score_fields.cap), r->stream));
         const int pi = uvc_prof_begin(&r->prof, "k_score_all", r->stream);   // with profiling on, the scoring kernels (gate + scan + k_score + k_call + the kept-groups copy) as one more entry of uvcgpu_region_kernel_times
         prep.in.scratch = r->d_score_scratch;
-        rc = uvc_launch_score(&prep.in, r->d_score_fields, r->score_capacity, kept_only ? r->d_score_kept : nullptr, r->stream);
+        rc = uvc_launch_score(&prep.in, r->d_score_fields, (int64_t)r->d_score_fields.cap, kept_only ? r->d_score_kept : nullptr, r->stream);
         if (rc) rc = fail(rc, "score: the force-output mask could not be cleared");
         uvc_prof_end(&r->prof, pi, r->stream);
         if (!rc && hipGetLastError() != hipSuccess) rc = fail(UVCGPU_EDEVICE, "score kernel launch failed");
         if (!rc) rc = uvcgpu_region_sync(r);
         // copies on the handle's own stream: a null-stream hipMemcpy would also wait for every other handle's work
         if (!rc && (hipMemcpyAsync(cnt, r->d_score_count, 16, hipMemcpyDeviceToHost, r->stream) != hipSuccess || hipStreamSynchronize(r->stream) != hipSuccess)) rc = fail(UVCGPU_EDEVICE, "hipMemcpy(count)");
-        if (rc || !kept_only || cnt[0] <= r->score_capacity) break;
+        if (rc || !kept_only || cnt[0] <= (int64_t)r->d_score_fields.cap) break;
         cap = cnt[0] + cnt[0] / 8;   // the guess was too small: nothing was written, once more with room for every record
     }
     if (!rc) {
@@ -1228,10 +1147,10 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
         r->last_scored = cnt[0]; r->last_returned = n_out;
         const int32_t *src = (kept_only ? r->d_score_kept : r->d_score_fields);
         out->n_records = n_out;
-        if (kept_only && cnt[0] > r->score_capacity) rc = fail(UVCGPU_EDEVICE, "score: the record count changed between two passes");
+        if (kept_only && cnt[0] > (int64_t)r->d_score_fields.cap) rc = fail(UVCGPU_EDEVICE, "score: the record count changed between two passes");
         else if (n_out > out->capacity) rc = fail(UVCGPU_ENOMEM, "score output capacity too small");   // the planes stay: the caller comes back with a larger buffer
         else if (rq.release_state && r->side) (void)queue_release_state(r, false);   // the scoring kernels are done: under the D2H of the records
-        if (!rc && n_out > 0 && (hipMemcpy2DAsync(out->fields, sizeof(int32_t) * out->capacity, src, sizeof(int32_t) * r->score_capacity, sizeof(int32_t) * n_out, UVC_NUM_SCORE_FIELDS, hipMemcpyDeviceToHost, r->stream) != hipSuccess
+        if (!rc && n_out > 0 && (hipMemcpy2DAsync(out->fields, sizeof(int32_t) * out->capacity, src, sizeof(int32_t) * (int64_t)r->d_score_fields.cap, sizeof(int32_t) * n_out, UVC_NUM_SCORE_FIELDS, hipMemcpyDeviceToHost, r->stream) != hipSuccess
                              || hipStreamSynchronize(r->stream) != hipSuccess))
             rc = fail(UVCGPU_EDEVICE, "hipMemcpy2D(records)");
     }
@@ -1244,14 +1163,15 @@ static int uvcgpu_region_score_impl(uvcgpu_region_t *r, const UvcScoreRequest *r
 // handle's stream, its D2H on the side stream behind an event; `next` for chunk j queues chunk j + 1 (whose set and host buffer the caller
 // gave back with this very call: it held chunk j - 1) and then waits for chunk j's copy alone.  So chunk j + 1 is computed and copied while
 // the caller formats chunk j.  Two streams, four events, no graph; no allocation per chunk.
-struct ScoreSet { char *d = nullptr; size_t d_bytes = 0; char *h = nullptr; size_t h_bytes = 0; hipEvent_t e_k = nullptr, e_c = nullptr; };
+struct ScoreSet { Buf<char> d; Buf<char, true> h; hipEvent_t e_k = nullptr, e_c = nullptr; explicit ScoreSet(const uvcgpu_region *r) : d(r), h(r) {} };   // (cap: bytes)
 struct uvcgpu_score_stream {
-    uvcgpu_region *r = nullptr; bool open = false;
+    uvcgpu_region *r; bool open = false;
     int64_t chunk_records = 0; ScoreSet set[2];          // kept across streams with the same chunk_records
     ScorePrep *prep = nullptr;                           // the open stream's request and its device temporaries
     std::vector<UvcScoreRange> ranges; bool plain = true;   // the request's ranges (a plain request: its one range)
     std::vector<UvcChunkDev> tab;                        // [n_chunks], as k_chunk_cut wrote it
     int64_t n_chunks = 0, launched = 0, returned = 0, ngroups = 0; int with_kept = 0; bool release_queued = false;
+    explicit uvcgpu_score_stream(uvcgpu_region *r_) : r(r_), set{ ScoreSet(r_), ScoreSet(r_) } {}
 };
 static bool stream_is_open(const uvcgpu_region *r) { return r && r->ss && r->ss->open; }
 #define UVC_STREAM_HOST_TAIL 64   /* behind the records of a page-locked buffer: */
@@ -1259,11 +1179,7 @@ struct StreamTail { int64_t counts[2]; int32_t err; };   // the set's record cou
 static_assert(sizeof(StreamTail) <= UVC_STREAM_HOST_TAIL, "the tail of a page-locked records buffer holds a StreamTail");
 static StreamTail *stream_tail(const ScoreSet &q, int64_t chunk_records) { return (StreamTail *)(q.h + SCORE_RECORD_BYTES * (size_t)chunk_records); }
 static void stream_free_sets(uvcgpu_score_stream *s) {
-    for (ScoreSet &q : s->set) {
-        if (q.d) hipFree(q.d);
-        if (q.h) (void)hipHostFree(q.h);
-        q.d = nullptr; q.h = nullptr; q.d_bytes = q.h_bytes = 0;
-    }
+    for (ScoreSet &q : s->set) { q.d.release(); q.h.release(); }
     s->chunk_records = 0;
 }
 static void stream_destroy(uvcgpu_region *r) {
@@ -1315,7 +1231,7 @@ static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcSc
     std::unique_ptr<ScorePrep> prep(new ScorePrep());
     { const int rc0 = score_prepare(r, req, ranges, n_ranges, *prep); if (rc0) return rc0; }
     if (!r->ss) {
-        r->ss = new uvcgpu_score_stream(); r->ss->r = r;
+        r->ss = new uvcgpu_score_stream(r);
         for (ScoreSet &q : r->ss->set) if (hipEventCreateWithFlags(&q.e_k, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&q.e_c, hipEventDisableTiming) != hipSuccess) { stream_destroy(r); return fail(UVCGPU_EDEVICE, "hipEventCreate"); }
     }
     uvcgpu_score_stream *s = r->ss;
@@ -1327,19 +1243,18 @@ static int uvcgpu_region_score_stream_begin_impl(uvcgpu_region_t *r, const UvcSc
     // the record-sized buffers of the one-call path go (a later plain call allocates what it needs again); the position-sized scratch is kept
     // when it fits and is not a plain call's record-sized one
     HIP_OK(hipStreamSynchronize(r->stream));
-    if (r->d_score_fields) { hipFree(r->d_score_fields); r->d_score_fields = nullptr; r->score_capacity = 0; }
-    if (r->d_score_kept) { hipFree(r->d_score_kept); r->d_score_kept = nullptr; r->score_kept_capacity = 0; }
+    r->d_score_fields.release(); r->d_score_kept.release();
     const size_t pos_need = uvc_score_stream_pos_bytes(npos, tab_cap);
     r->d_score_count = nullptr;
-    { const int rcb = fit_buffer(r->d_score_scratch, r->score_scratch_bytes, pos_need, (size_t)0, pos_need + pos_need / 4 + 65536, 1, false, UVCGPU_ENOMEM, "score stream: hipMalloc of the position-sized scratch"); if (rcb) return rcb; }
-    r->d_score_count = (int64_t *)r->d_score_scratch;
+    { const int rcb = fit_buffer(r->d_score_scratch, pos_need, 0, pos_need + pos_need / 4 + 65536, 1, UVCGPU_ENOMEM, "score stream: hipMalloc of the position-sized scratch"); if (rcb) return rcb; }
+    r->d_score_count = (int64_t *)r->d_score_scratch.p;
     prep->in.scratch = r->d_score_scratch;   // (the chunks of the stream use it too)
     const int with_kept = rq.kept_only ? 1 : 0;
     const size_t set_need = uvc_score_set_bytes(chunk_records, ngroups, with_kept), host_need = SCORE_RECORD_BYTES * (size_t)chunk_records + UVC_STREAM_HOST_TAIL;
     if (s->chunk_records != chunk_records) stream_free_sets(s);
     for (ScoreSet &q : s->set) {
-        int rcb = fit_buffer(q.d, q.d_bytes, set_need, (size_t)0, (size_t)0, 1, false, UVCGPU_ENOMEM, ("score stream: hipMalloc of a row set for chunk_records = " + std::to_string(chunk_records)).c_str());
-        if (!rcb) rcb = fit_buffer(q.h, q.h_bytes, host_need, (size_t)0, (size_t)0, 1, true, UVCGPU_ENOMEM, "score stream: hipHostMalloc of a records buffer");
+        int rcb = fit_buffer(q.d, set_need, 0, 0, 1, UVCGPU_ENOMEM, "score stream: hipMalloc of a row set for chunk_records = " + std::to_string(chunk_records));
+        if (!rcb) rcb = fit_buffer(q.h, host_need, 0, 0, 1, UVCGPU_ENOMEM, "score stream: hipHostMalloc of a records buffer");
         if (rcb) { stream_free_sets(s); return rcb; }
     }
     s->chunk_records = chunk_records; s->with_kept = with_kept; s->ngroups = ngroups;
@@ -1377,7 +1292,7 @@ static int uvcgpu_score_stream_next_impl(uvcgpu_score_stream_t *s, UvcScoreOut *
     if (!s->open) return fail(UVCGPU_ESTATE, "score stream: not open");
     uvcgpu_region *r = s->r;
     if (n_covered) *n_covered = 0;
-    chunk->capacity = s->chunk_records; chunk->n_records = 0; chunk->fields = (int32_t *)s->set[0].h;
+    chunk->capacity = s->chunk_records; chunk->n_records = 0; chunk->fields = (int32_t *)s->set[0].h.p;
     const int64_t j = s->returned;
     if (j >= s->n_chunks) return UVCGPU_STREAM_END;
     // this call gives back the buffers of chunk j - 1: chunk j + 1 takes them
@@ -1389,7 +1304,7 @@ static int uvcgpu_score_stream_next_impl(uvcgpu_score_stream_t *s, UvcScoreOut *
     if (tail.err) return fail(tail.err, "a scoring kernel flagged an error");
     const int64_t n_out = (s->prep->rq.kept_only ? tail.counts[1] : (int64_t)t.nr);
     if (n_out < 0 || n_out > t.nr) return fail(UVCGPU_EDEVICE, "score stream: the kept count of a chunk is out of range");
-    chunk->fields = (int32_t *)q.h; chunk->n_records = n_out;
+    chunk->fields = (int32_t *)q.h.p; chunk->n_records = n_out;
     r->last_scored += t.nr; r->last_returned += n_out;
     // the ranges this chunk covers: the request's ranges cut to the chunk's compact positions; a piece that begins inside a range continues it
     const int64_t c0 = t.g0 / 2, c1 = c0 + t.ng / 2;
@@ -1419,10 +1334,10 @@ int uvcgpu_score_stream_end(uvcgpu_score_stream_t *s) { return guarded("uvcgpu_s
 int64_t uvcgpu_score_stream_bytes_per_record(void) { return 2 * ((int64_t)uvc_score_set_bytes_per_record() + (int64_t)SCORE_RECORD_BYTES); }
 int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     if (!r) return -1;
-    int64_t b = (int64_t)r->score_scratch_bytes + (int64_t)r->h_stage_cap;
-    if (r->d_score_fields) b += (int64_t)SCORE_RECORD_BYTES * r->score_capacity;
-    if (r->d_score_kept) b += (int64_t)SCORE_RECORD_BYTES * r->score_kept_capacity;
-    if (r->ss) for (const ScoreSet &q : r->ss->set) b += (int64_t)q.d_bytes + (int64_t)q.h_bytes;
+    int64_t b = (int64_t)r->d_score_scratch.cap + (int64_t)r->h_stage.cap;
+    if (r->d_score_fields) b += (int64_t)SCORE_RECORD_BYTES * (int64_t)r->d_score_fields.cap;
+    if (r->d_score_kept) b += (int64_t)SCORE_RECORD_BYTES * (int64_t)r->d_score_kept.cap;
+    if (r->ss) for (const ScoreSet &q : r->ss->set) b += (int64_t)q.d.cap + (int64_t)q.h.cap;
     return b;
 }
 
@@ -1477,20 +1392,8 @@ struct ReportLayout {
 };
 // the device and the page-locked buffer that the report calls share (every one synchronises before it returns), grown on demand
 static int report_buffers(uvcgpu_region_t *r, size_t dev_bytes, size_t out_bytes, const char *what) {
-    if (dev_bytes > r->d_report_bytes) {
-        if (r->d_report) { (void)hipStreamSynchronize(r->stream); hipFree(r->d_report); }
-        r->d_report = nullptr; r->d_report_bytes = 0;
-        const size_t want = dev_bytes + dev_bytes / 2;
-        if (hipMalloc((void **)&r->d_report, want) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipMalloc(") + what + ") failed"); }
-        r->d_report_bytes = want;
-    }
-    if (out_bytes > r->h_report_bytes) {
-        if (r->h_report) { (void)hipStreamSynchronize(r->stream); (void)hipHostFree(r->h_report); }
-        r->h_report = nullptr; r->h_report_bytes = 0;
-        const size_t want = out_bytes + out_bytes / 2;
-        if (hipHostMalloc((void **)&r->h_report, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(UVCGPU_ENOMEM, std::string("hipHostMalloc(") + what + ") failed"); }
-        r->h_report_bytes = want;
-    }
+    if (r->d_report.fit(dev_bytes, dev_bytes / 2) != hipSuccess) return fail(UVCGPU_ENOMEM, std::string("hipMalloc(") + what + ") failed");
+    if (r->h_report.fit(out_bytes, out_bytes / 2) != hipSuccess) return fail(UVCGPU_ENOMEM, std::string("hipHostMalloc(") + what + ") failed");
     return 0;
 }
 // Room for a call's pieces and its result, and the range list (piece 0 of every layout) on its way: through the handle's staging buffer
@@ -1700,7 +1603,7 @@ static int uvcgpu_region_msi_impl(uvcgpu_region_t *r, const UvcCoverageRange *ra
     const size_t o_tab = L0.take(sizeof(UvcRangeRow) * tab.size()), o_blocks = L0.take(sizeof(int32_t) * (size_t)(n_blocks + 1));
     // the loci the buffer as it is has room for behind the fixed pieces (never more than the positions of the call, each of which can be a head)
     int64_t room = 0;
-    if (locus_capacity > 0 && r->d_report_bytes > L0.bytes + 128) room = std::min({ locus_capacity, n_total, (int64_t)((r->d_report_bytes - L0.bytes - 128) / (row_bytes + sizeof(int32_t))) });
+    if (locus_capacity > 0 && r->d_report.cap > L0.bytes + 128) room = std::min({ locus_capacity, n_total, (int64_t)((r->d_report.cap - L0.bytes - 128) / (row_bytes + sizeof(int32_t))) });
     // the allele pipeline of the accumulate ran on the side stream: behind it, as gap_tables waits for it (no host wait here)
     if (r->side) HIP_OK(hipStreamWaitEvent(r->stream, r->e_fork2, 0));
     int32_t n = 0;
@@ -1751,39 +1654,9 @@ void uvcgpu_region_destroy(uvcgpu_region_t *r) {
     if (!r) return;
     quiesce(r);
     stream_destroy(r);   // an open score stream ends here: its temporaries, row sets and page-locked buffers (the streams are still there)
-    free_reads(r);
-    if (r->d_refsym) hipFree(r->d_refsym);
-    if (r->d_rtr) hipFree(r->d_rtr);
-    if (r->d_rtr0) hipFree(r->d_rtr0);
-    if (r->d_baq) hipFree(r->d_baq);
-    if (r->d_rtrwork) hipFree(r->d_rtrwork);
-    if (r->h_ref) (void)hipHostFree(r->h_ref);
-    if (r->d_fsum) hipFree(r->d_fsum);
-    if (r->d_win) hipFree(r->d_win);
-    if (r->side) hipStreamDestroy(r->side);
-    if (r->side3) hipStreamDestroy(r->side3);
-    if (r->e_join3) hipEventDestroy(r->e_join3);
-    if (r->e_stat) hipEventDestroy(r->e_stat);
-    if (r->e_alleles) hipEventDestroy(r->e_alleles);
-    if (r->e_fork) hipEventDestroy(r->e_fork);
-    if (r->e_join) hipEventDestroy(r->e_join);
-    if (r->e_fork2) hipEventDestroy(r->e_fork2);
-    if (r->d_state) hipFree(r->d_state);
-    if (r->d_dirty) hipFree(r->d_dirty);
-    if (r->d_zero_planes) hipFree(r->d_zero_planes);
-    if (r->R.err) hipFree(r->R.err);
-    if (r->d_score_scratch) hipFree(r->d_score_scratch);
-    if (r->d_score_fields) hipFree(r->d_score_fields);
-    if (r->d_score_kept) hipFree(r->d_score_kept);
-    if (r->h_stage) (void)hipHostFree(r->h_stage);
-    if (r->d_report) hipFree(r->d_report);
-    if (r->h_report) (void)hipHostFree(r->h_report);
-    if (r->d_gap_alleles) hipFree(r->d_gap_alleles);
-    if (r->d_gap_allele_row) hipFree(r->d_gap_allele_row);
-    if (r->d_gap_rows) hipFree(r->d_gap_rows);
-    if (r->d_gap_seq) hipFree(r->d_gap_seq);
-    if (r->stream) hipStreamDestroy(r->stream);
-    delete r;
+    for (hipEvent_t *e : r->events()) if (*e) { hipEventDestroy(*e); *e = nullptr; }
+    for (hipStream_t *s : r->streams()) if (*s) { hipStreamDestroy(*s); *s = nullptr; }
+    delete r;   // the buffers and the pool free what they own (nothing is in flight, and no stream is left to wait for)
     { const hipError_t stale = hipGetLastError(); if (stale != hipSuccess && getenv("UVCGPU_DEBUG")) fprintf(stderr, "[uvcgpu] uvcgpu_region_destroy left HIP error: %s\n", hipGetErrorString(stale)); }
 }
 

@@ -3782,19 +3782,14 @@ __global__ void __launch_bounds__(256) k_check_dirty(RegionDev R, unsigned long 
     const int s = (int)blockIdx.y;
     if (x >= R.npos) return;
     const int b = (int)(x >> UVC_DIRTY_SHIFT);
-    long long core = 0, fi = 0, du = 0;
-    for (int f = 0; f < UVC_NSEG32; f++) core |= S32(R, f, s, x);
-    for (int f = 0; f < UVC_NSEG64; f++) core |= S64(R, f, s, x);
-    for (int f = 0; f < UVC_NVQ; f++) core |= VQP(R, f, s, x);
-    core |= BQS(R, s, x);
-    for (int st = 0; st < 2; st++) { for (int f = 0; f < UVC_NFRAG; f++) core |= FRP(R, st, f, s, x); for (int f = 0; f < UVC_NFAM; f++) core |= FAP(R, st, f, s, x); }
-    for (int f = 0; f < UVC_NFAMINFO32; f++) fi |= FIP(R, f, s, x);
-    for (int f = 0; f < UVC_NFAMINFO64; f++) fi |= FI64P(R, f, s, x);
-    for (int f = 0; f < UVC_NDUPLEX; f++) du |= DUP(R, f, s, x);
+    long long any[UVC_N_DIRTY_FAMILIES] = { 0, 0, 0 };   // the cells of (s, x) in the groups of each plane family, OR-ed
+#define X(g, m) { constexpr int fill = UVC_GROUPS[UVC_F_##g].fill; \
+                  if (fill >= 0) for (int pl = 0; pl < uvc_group_sym_planes(UVC_F_##g); pl++) any[fill >= 0 ? fill : 0] |= R.m[((size_t)pl * NSYM + s) * R.npos + x]; }
+    UVC_SLAB_MEMBERS(X)
+#undef X
     int bad = 0;
-    if (core && !sym_always_filled(s) && !R.dirty[(size_t)s * R.ndblk + b]) bad++;
-    if (fi && !R.dirty[((size_t)NSYM + s) * R.ndblk + b]) bad++;
-    if (du && !R.dirty[((size_t)2 * NSYM + s) * R.ndblk + b]) bad++;
+    for (int fam = 0; fam < UVC_N_DIRTY_FAMILIES; fam++)
+        if (any[fam] && !(fam == UVC_FILL_CORE && sym_always_filled(s)) && !R.dirty[((size_t)fam * NSYM + s) * R.ndblk + b]) bad++;
     if (bad) atomicAdd(n_bad, (unsigned long long)bad);
 }
 extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s) {

@@ -26,9 +26,6 @@ static inline int uvc_prof_begin(UvcProf *p, const char *name, hipStream_t s) {
     return i;
 }
 static inline void uvc_prof_end(UvcProf *p, int i, hipStream_t s) { if (i >= 0) hipEventRecord(p->ev[i][1], s); }
-// one plane of the slab for k_zero_state; fam < 0: always filled, else the (plane family, sym) of RegionDev::dirty that says whether to
-struct ZeroPlane { unsigned long long off; int32_t elem; int16_t fam, sym; };
-static_assert(sizeof(ZeroPlane) == 16, "the host uploads the plane table as 16-byte rows");
 // one range of uvcgpu_region_score_ranges on the device: [beg, end) in zerobased_pos, first = the compact position of beg (exclusive prefix
 // of the lengths), flags bit 0 = base_at_pos_beg
 struct UvcScoreRangeDev { int beg, end, first, flags; };

@@ -22,6 +22,8 @@ UVC_RULE int base_value(int q, const UvcParams &P) { return q + P.bq_phred_added
 // The quality at or below which a base has no value (on IonTorrent the smaller of two qualities + the smaller addend): a fragment with
 // such a base takes the per-position kernels (FRAG_STAT_ZERO_VALUE)
 UVC_RULE int zero_value_qual(const UvcParams &P) { return -((UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform) ? imin(P.bq_phred_added_misma, P.bq_phred_added_indel) : P.bq_phred_added_misma); }
+// ---- RegionDev::dirty: A C G T N (a reference base) and LINK_M are written at nearly every position, so their planes are zero-filled without a look at the marks ----
+UVC_RULE bool sym_always_filled(int s) { return s < UVC_BASE_NN || s == UVC_LINK_M; }
 // ---- assay predicates.  UvcReadSoA::fam_dflag bits (MolecularBarcode::duplexflag, grouping.cpp:931) ----
 enum { UVC_DFLAG_UMI = 0x1, UVC_DFLAG_DUPLEX = 0x2, UVC_DFLAG_AMPLICON = 0x4 };
 UVC_RULE bool normal_filters_primers(const UvcParams &P) { return P.tn_is_paired && (0x1 & P.primer_flag); }
