@@ -70,8 +70,7 @@ i32 indel_len_rusize_phred(i32 indel_len, i32 repeatunit_size) {
 i32 indel_phred(double ampfact, i32 rs, i32 rn) {
     i32 region_size = rs * rn;
     double num_slips = (region_size > 64 ? (double)(region_size - 8) : log1p(exp((double)region_size - (double)8))) * ampfact / ((double)(rs * rs));
-    double p = (1.0 - DBL_EPSILON) / (num_slips + 1.0);
-    return (i32)floor(-10 * log(p) / log(10));
+    return prob2phred((1.0 - DBL_EPSILON) / (num_slips + 1.0));
 }
 
 // infer_max_qual_assuming_independence, main_conversion.hpp:943-974
@@ -108,7 +107,7 @@ i32 oracle_sscs_phred(const UvcParams &P, int con_symbol, int alt_symbol) { retu
 // ------------------------------------------------------------------------------------------------
 // region side arrays (C10)
 // ------------------------------------------------------------------------------------------------
-static int char_to_symbol(char c) {  // CHAR_TO_SYMBOL, main_conversion.hpp:473-488 (base letters only)
+int char_to_symbol(char c) {  // CHAR_TO_SYMBOL, main_conversion.hpp:473-488 (base letters only)
     switch (c) { case 'A': case 'a': return UVC_BASE_A; case 'C': case 'c': return UVC_BASE_C;
                  case 'G': case 'g': return UVC_BASE_G; case 'T': case 't': return UVC_BASE_T;
                  case 'I': case 'i': return UVC_LINK_M; case '-': case '_': return UVC_LINK_D1; default: return UVC_BASE_N; }
@@ -536,7 +535,7 @@ static i32 ref_to_phredvalue(i32 &n_units, i32 &max_rn, i32 &rs_at_max, const St
 }
 
 // proton_cigarlen2phred, main_conversion.hpp:922-941
-static i32 proton_cigarlen2phred(i32 cigarlen) {
+i32 proton_cigarlen2phred(i32 cigarlen) {
     static const i32 t[13] = { 0, 0, 9, 14, 18, 21, 23, 25, 27, 29, 30, 31, 32 };
     return t[min_(cigarlen, 12)];
 }
@@ -1155,9 +1154,9 @@ static int using_fq(State &S, std::string &err) {
                     const i32 majorcount = S.FA(strand, UVC_FAM_cDPM, con_symbol, x);
                     const i32 minorcount = S.FA(strand, UVC_FAM_cDPm, con_symbol, x);
                     const double prior_weight = 1.0 / (minorcount + 1.0);
-                    const double phred2prob_avgBQ = pow(10, -((float)avgBQ) / 10);   // phred2prob: float cast, main_conversion.hpp:885-888
+                    const double phred2prob_avgBQ = phred2prob(avgBQ);
                     const double prob = (minorcount + prior_weight) / (majorcount + minorcount + prior_weight / phred2prob_avgBQ);
-                    const double realphred = -10 * log(prob) / log(10);               // prob2realphred, main_conversion.hpp:895-898
+                    const double realphred = prob2realphred(prob);
                     const i32 indep_frag_phred = (i32)round(((con_nfrags * 2) - tot_nfrags) * realphred);
                     i32 confam_qual;
                     if (UVC_LINK_SYMBOL == st) confam_qual = max_(1, min_(indep_frag_phred, (i32)P.fam_phred_indel_inc_before_barcode_labeling + (i32)round(realphred)));

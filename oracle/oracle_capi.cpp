@@ -3,6 +3,8 @@
 // harness drives the oracle and the HIP library.  Symbols are prefixed uvc_oracle_.
 #include "oracle_common.hpp"
 
+#include <emmintrin.h>
+
 using namespace uvco;
 
 namespace uvco { i32 oracle_sscs_phred(const UvcParams &P, int con_symbol, int alt_symbol);
@@ -290,5 +292,73 @@ void uvc_oracle_infer_max_qual(int32_t *out3, int32_t max_qual, int32_t dec_qual
 int32_t uvc_oracle_indel_phred(double ampfact, int32_t rs, int32_t rn) { return indel_phred(ampfact, rs, rn); }
 int32_t uvc_oracle_indel_len_rusize_phred(int32_t len, int32_t rs) { return indel_len_rusize_phred(len, rs); }
 int32_t uvc_oracle_sscs_phred(const UvcParams *p, int32_t con, int32_t alt) { return oracle_sscs_phred(*p, con, alt); }
+
+// ---- the same primitives over whole grids (tests/test_ref_math_cpu.py, tests/test_gpu_math_probe.py): n rows of `in` (row-major, integers
+// carried as doubles) give n rows of `out`; the widths and argument orders are those of oracle/ref_math_driver.cpp and tests/math_grids.py ----
+#define ROWS(n_in, n_out) for (int64_t i = 0; i < n; i++) { const double *a = in + i * (n_in); double *o = out + i * (n_out); (void)a; (void)o;
+#define END_ROWS }
+void uvc_oracle_math_phred2nat(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = phred2nat(a[0]); END_ROWS }
+void uvc_oracle_math_numstates2phred(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = numstates2phred(a[0]); END_ROWS }
+void uvc_oracle_math_numstates2deciphred(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = numstates2deciphred(a[0]); END_ROWS }
+void uvc_oracle_math_non_neg_minus(int64_t n, const double *in, double *out) { ROWS(2, 1) o[0] = nnminus_d(a[0], a[1]); END_ROWS }
+void uvc_oracle_math_non_neg_minus_i64(int64_t n, const double *in, double *out) { ROWS(2, 1) o[0] = (double)nnminus((i64)a[0], (i64)a[1]); END_ROWS }
+void uvc_oracle_math_prob2odds(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = prob2odds(a[0]); END_ROWS }
+void uvc_oracle_math_odds2prob(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = odds2prob(a[0]); END_ROWS }
+void uvc_oracle_math_logit(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = logit(a[0]); END_ROWS }
+void uvc_oracle_math_logit2(int64_t n, const double *in, double *out) { ROWS(2, 1) o[0] = logit2(a[0], a[1]); END_ROWS }
+void uvc_oracle_math_binom_llr(int64_t n, const double *in, double *out) { ROWS(5, 1) o[0] = calc_binom_10log10_likeratio(a[0], a[1], a[2], a[3] != 0, a[4] != 0); END_ROWS }
+void uvc_oracle_math_dp4(int64_t n, const double *in, double *out) {
+    ROWS(13, 2) dp4_to_pcFA(o, a[0] != 0, a[1] != 0, a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12]); END_ROWS
+}
+void uvc_oracle_math_calc_non_negative_float(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = (double)calc_non_negative_f((float)a[0]); END_ROWS }
+void uvc_oracle_math_phred2prob(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = phred2prob((i32)a[0]); END_ROWS }
+void uvc_oracle_math_prob2phred(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = prob2phred(a[0]); END_ROWS }
+void uvc_oracle_math_prob2realphred(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = prob2realphred(a[0]); END_ROWS }
+void uvc_oracle_math_proton_cigarlen2phred(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = proton_cigarlen2phred((i32)a[0]); END_ROWS }
+void uvc_oracle_math_infer_max_qual(int64_t n, const double *in, double *out) {
+    ROWS(19, 3)
+        i32 distr[NBUCKETS], r[3];
+        for (int k = 0; k < NBUCKETS; k++) distr[k] = (i32)a[k];
+        infer_max_qual_assuming_independence(r[0], r[1], r[2], (i32)a[16], (i32)a[17], distr, (i32)a[18]);
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+    END_ROWS
+}
+void uvc_oracle_math_infer_max_qual_one(int64_t n, const double *in, double *out) {
+    ROWS(5, 3)
+        i32 distr[NBUCKETS], r[3];
+        for (int k = 0; k < NBUCKETS; k++) distr[k] = (k == (int)a[0]) ? (i32)a[1] : 0;
+        infer_max_qual_assuming_independence(r[0], r[1], r[2], (i32)a[2], (i32)a[3], distr, (i32)a[4]);
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
+    END_ROWS
+}
+void uvc_oracle_math_symbols_mutated(int64_t n, const double *in, double *out) { ROWS(2, 1) o[0] = symbols_mutated((int)a[0], (int)a[1]) ? 1 : 0; END_ROWS }
+void uvc_oracle_math_symbol_kind(int64_t n, const double *in, double *out) { ROWS(1, 3) o[0] = is_ins((int)a[0]) ? 1 : 0; o[1] = is_del((int)a[0]) ? 1 : 0; o[2] = is_subst((int)a[0]) ? 1 : 0; END_ROWS }
+void uvc_oracle_math_len_to_symbol(int64_t n, const double *in, double *out) { ROWS(1, 2) o[0] = ins_len_to_symbol((int)a[0]); o[1] = del_len_to_symbol((int)a[0]); END_ROWS }
+// the functions of main.hpp, which has no compiled reference: the oracle is the comparator of the device probe here
+void uvc_oracle_math_indel_len_rusize_phred(int64_t n, const double *in, double *out) { ROWS(2, 1) o[0] = indel_len_rusize_phred((i32)a[0], (i32)a[1]); END_ROWS }
+void uvc_oracle_math_indel_phred(int64_t n, const double *in, double *out) { ROWS(3, 1) o[0] = indel_phred(a[0], (i32)a[1], (i32)a[2]); END_ROWS }
+void uvc_oracle_math_more_STR(int64_t n, const double *in, double *out) { ROWS(5, 1) o[0] = is_indel_context_more_STR((i32)a[0], (i32)a[1], (i32)a[2], (i32)a[3], (i32)a[4]) ? 1 : 0; END_ROWS }
+void uvc_oracle_math_norm_fa(int64_t n, const double *in, double *out) { ROWS(2, 1) o[0] = norm_fa(a[0], a[1]); END_ROWS }
+void uvc_oracle_math_het_lodq(int64_t n, const double *in, double *out) { ROWS(4, 1) o[0] = hetLODQ(a[0], a[1], a[2], a[3]); END_ROWS }
+void uvc_oracle_math_normv_quals(int64_t n, const double *in, double *out) {
+    ROWS(11, 4) i32 r[4]; normv_quals(r, a[0], a[1], (i32)a[2], (i32)a[3], a[4], a[5], (i32)a[6], a[7], (i32)a[8], (i32)a[9], a[10]); for (int k = 0; k < 4; k++) o[k] = r[k]; END_ROWS
+}
+void uvc_oracle_math_normv_quals2(int64_t n, const double *in, double *out) {
+    ROWS(7, 4) i32 r[4]; normv_quals2(r, a[0], a[1], (i32)a[2], (i32)a[3], a[4], a[5], (i32)a[6]); for (int k = 0; k < 4; k++) o[k] = r[k]; END_ROWS
+}
+// con, alt, then fam_phred_sscs_indel_open, _indel_ext, _transition_CG_TA, _transition_AT_GC, _transversion_CG_AT, _transversion_other, tumor_vcf_fname_nonempty
+void uvc_oracle_math_sscs_phred(int64_t n, const double *in, double *out) {
+    ROWS(9, 1)
+        UvcParams p; uvc_oracle_params_default(&p);
+        p.fam_phred_sscs_indel_open = (int)a[2]; p.fam_phred_sscs_indel_ext = (int)a[3]; p.fam_phred_sscs_transition_CG_TA = (int)a[4]; p.fam_phred_sscs_transition_AT_GC = (int)a[5];
+        p.fam_phred_sscs_transversion_CG_AT = (int)a[6]; p.fam_phred_sscs_transversion_other = (int)a[7]; p.tumor_vcf_fname_nonempty = (int)a[8];
+        o[0] = oracle_sscs_phred(p, (int)a[0], (int)a[1]);
+    END_ROWS
+}
+// what (int32)v gives on x86-64 (cvttsd2si: INT32_MIN for NaN and out of range), the conversion every (i32) cast of the oracle compiles to
+void uvc_oracle_math_i32_cast(int64_t n, const double *in, double *out) { ROWS(1, 1) o[0] = (double)_mm_cvttsd_si32(_mm_set_sd(a[0])); END_ROWS }
+void uvc_oracle_math_char_to_symbol(int32_t *out256) { for (int c = 0; c < 256; c++) out256[c] = char_to_symbol((char)c); }
+#undef ROWS
+#undef END_ROWS
 
 }  // extern "C"

@@ -76,6 +76,18 @@ static const int ST_NSYMBOLS[2] = { 6, 8 };
 static inline double phred2nat(double x) { return (log(10.0) / 10.0) * x; }
 static inline double numstates2phred(double x) { return (10.0 / log(10.0)) * log(x); }
 static inline i32 numstates2deciphred(double x) { return (i32)round((100.0 / log(10.0)) * log(x)); }
+// main_conversion.hpp:191-219
+static inline double prob2odds(double p) { return p / (1.0 - p); }
+static inline double odds2prob(double odds) { return odds / (odds + 1.0); }
+static inline double logit(double p) { return log(prob2odds(p)); }
+static inline double logit2(double a, double b) { return logit((a + DBL_EPSILON) / (a + b + 2.0 * DBL_EPSILON)); }
+// main_conversion.hpp:885-898 (phred2prob: the exponent is a float quotient)
+static inline double phred2prob(i32 phredvalue) { return pow(10, -((float)phredvalue) / 10); }
+static inline i32 prob2phred(double probvalue) { return (i32)floor(-10 * log(probvalue) / log(10)); }
+static inline double prob2realphred(double probvalue) { return -10 * log(probvalue) / log(10); }
+// calc_non_negative<float> with its defaults, main_conversion.hpp:163-171 (the one call site, main.hpp:6206, passes a float)
+static inline float calc_non_negative_f(float v) { const float base = (float)pow(10.0, 0.1); return (v < 10.0f) ? (log1pf(powf(base, v)) / logf(base)) : v; }
+static inline double norm_fa(double FA, double refbias) { return (FA + FA * refbias) / (FA + (1.0 - FA) / (1.0 + refbias) + FA * refbias); }   // main.hpp:4253-4256
 
 struct Rtr { i32 begpos = 0, tracklen = 0, unitlen = 0, indelphred = 43, anyTR_begpos = 0, anyTR_tracklen = 0, anyTR_unitlen = 0; };  // common.hpp:150-160
 
@@ -172,6 +184,11 @@ void infer_max_qual_assuming_independence(i32 &maxvqual, i32 &argmaxAD, i32 &arg
 i32 indel_phred(double ampfact, i32 repeatsize_at_max_repeatnum, i32 max_repeatnum);
 i32 indel_len_rusize_phred(i32 indel_len, i32 repeatunit_size);
 bool is_indel_context_more_STR(i32 rulen1, i32 rc1, i32 rulen2, i32 rc2, i32 indel_str_repeatsize_max);
+i32 proton_cigarlen2phred(i32 cigarlen);
+int char_to_symbol(char c);
+i32 hetLODQ(double a1, double a2, double expfrac, double powlaw_exponent);
+void normv_quals(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap, double nAD, double nDP, i32 nVQ, double penal_dimret_coef, i32 prior_phred, i32 tn_dec_by_xm, double powlaw_exponent);
+void normv_quals2(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap, double nAD, double nDP, i32 nVQ);
 void indelpos_to_context(i32 &repeatunit_len, i32 &max_repeatnum, const std::string &refstring, i32 refpos, i32 indel_str_repeatsize_max);
 
 }  // namespace uvco

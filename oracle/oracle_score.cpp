@@ -26,8 +26,6 @@ double calc_binom_10log10_likeratio(double prob, double a, double b, bool bidire
     if (bidirectional || a > A) return 10.0 / log(10.0) * (a * log(a / A) + b * log(b / B));
     return 0.0;
 }
-static inline double prob2odds(double p) { return p / (1.0 - p); }                                  // main_conversion.hpp:191-196
-static inline double logit2(double a, double b) { return log(prob2odds((a + DBL_EPSILON) / (a + b + 2.0 * DBL_EPSILON))); }  // :211-219
 
 // dp4_to_pcFA<TBidirectional, TIsOverseqFracDisabled>, main_conversion.hpp:798-849
 void dp4_to_pcFA(double out[2], bool bidir, bool overseq_disabled, double overseq_frac, double aADpass, double aADfail, double aDPpass, double aDPfail,
@@ -195,7 +193,6 @@ static void symbol_init(Fmt &f, State &S, i32 refpos, int sym, i32 bDPa, i32 cDP
 
 // does_fmt_imply_short_frag, main.hpp:169-174
 static inline bool implies_short_frag(const Fmt &f, i32 wgs_min_avg_fragsize) { return (f.APLRI[0] + f.APLRI[2]) < (f.APLRI[1] + f.APLRI[3]) * (i64)wgs_min_avg_fragsize; }
-static inline double norm_fa(double FA, double refbias) { return (FA + FA * refbias) / (FA + (1.0 - FA) / (1.0 + refbias) + FA * refbias); }   // main.hpp:4253-4256
 
 // ---- test hook: what BcfFormat_symboltype_init / BcfFormat_symbol_init gathered for one record, as named numbers, so that an independent
 // restatement of calc_DPv / calc_qual (tests/score_restatement.py) starts from the same inputs
@@ -839,7 +836,7 @@ static void indel_majority(State &S, i32 refpos, int symbol, std::vector<GapAlle
 // append_vcf_record (main.hpp:6027-6272).  Strings (GT text, REF / ALT, INFO, FORMAT) stay with the caller.
 // ------------------------------------------------------------------------------------------------
 static const int SYM_END = UVC_NUM_SYMBOLS;   // END_ALIGNMENT_SYMBOLS
-static i32 hetLODQ(double a1, double a2, double expfrac, double powlaw_exponent) {   // main.hpp:5457-5462
+i32 hetLODQ(double a1, double a2, double expfrac, double powlaw_exponent) {   // main.hpp:5457-5462
     const i32 binomLODQ = (i32)calc_binom_10log10_likeratio(expfrac, a1, a2);
     const i32 powerLODQ = (i32)round(10.0 / log(10.0) * powlaw_exponent * max_(logit2((a1 + 0.5) * 0.5 / expfrac, (a2 + 0.5) * 0.5 / (1.0 - expfrac)), 0.0));
     return min_(binomLODQ, powerLODQ);
@@ -909,7 +906,7 @@ static void call_germline(const UvcParams &P, int refsymbol, std::vector<Fmt> &f
 }
 
 // calc_binom_powlaw_syserr_normv_quals, main.hpp:5982-6009
-static void normv_quals(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap, double nAD, double nDP, i32 nVQ, double penal_dimret_coef, i32 prior_phred, i32 tn_dec_by_xm, double powlaw_exponent) {
+void normv_quals(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap, double nAD, double nDP, i32 nVQ, double penal_dimret_coef, i32 prior_phred, i32 tn_dec_by_xm, double powlaw_exponent) {
     const i32 binom_b10log10like = (i32)calc_binom_10log10_likeratio((tDP - tAD) / (tDP), nDP - nAD, nAD);
     const double nADplus = nAD * between_(nDP / tDP - 1.0, 0.0, 1.0);
     const double bjpfrac = ((tAD + 0.5) / (tDP + 1.0)) / ((nAD + 0.5 + nADplus) / (nDP + 1.0 + nADplus));
@@ -921,7 +918,7 @@ static void normv_quals(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap
     out[0] = binom_b10log10like; out[1] = powlaw_b10log10like; out[2] = tnVQdec; out[3] = min_(tnVQcap, tVQ + tnVQinc) - tnVQdec;
 }
 // calc_binom_powlaw_syserr_normv_quals2, main.hpp:6011-6025
-static void normv_quals2(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap, double nAD, double nDP, i32 nVQ) {
+void normv_quals2(i32 out[4], double tAD, double tDP, i32 tVQ, i32 tnVQcap, double nAD, double nDP, i32 nVQ) {
     const i32 binom = (i32)calc_binom_10log10_likeratio((tDP - tAD) / (tDP), nDP - nAD, nAD);
     const i32 powlaw = (nAD <= 3 ? binom : (i32)round(binom * 3 / nAD));
     const double m = max_((double)(min_(binom, powlaw) - 3), max_(-3 * nAD, -3.0));   // TVN_MICRO_VQ_DELTA = 3; MAX3 promotes to double
@@ -1003,7 +1000,6 @@ static void call_record(const UvcParams &P, Fmt &fmt, const Fmt &reffmt, const s
     else normv_quals2(cq4, (t_cDP2x + 0.5) / 100.0 + 0.0, (t_CDP2x + 1.0) / 100.0 + 0.0, t_cVQ2, t_cPCQ2, (nfm_cDP2x + 0.0) / 100.0 + 0.5 + add2, (nfm_CDP2x + 0.0) / 100.0 + 1.0 + add2, norm_norm_vq);
     const i32 tlodq1 = max_(bq4[3], cq4[3] + 0);
     const bool is_cytosine_deanim_CT = ((UVC_BASE_C == refsymbol && UVC_BASE_T == symbol) || (UVC_BASE_G == refsymbol && UVC_BASE_A == symbol));
-    auto prob2realphred = [](double p) { return -10 * log(p) / log(10); };
     const double b_min_tlodq = 2 + 3 - prob2realphred((t_bDP + 1e-3) / (t_BDP + 1)) / 10.0;
     const double c2v_min_tlodq = 2 + 5 - prob2realphred((t_cDP2x * 0.01 + 1e-5) / (t_CDP2x * 0.01 + 1) / (is_cytosine_deanim_CT ? 5 : 1)) / 10.0;
     const float lowestVAQ = (float)max_(b_min_tlodq, c2v_min_tlodq);
@@ -1011,7 +1007,7 @@ static void call_record(const UvcParams &P, Fmt &fmt, const Fmt &reffmt, const s
     const i32 nlodq = nlodq1 - tn_dec_both;
     const i32 somaticq = min_(tlodq, nlodq);
     float v = (is_processing_normal ? ((float)somaticq) : max_((float)tlodq, lowestVAQ));
-    { const float base = (float)pow(10.0, 0.1); if (v < 10.0f) v = log1pf(powf(base, v)) / logf(base); }   // calc_non_negative<float>, main_conversion.hpp:163-171
+    v = calc_non_negative_f(v);
     const float vcfqual = v;
     fmt.TLODQ = tlodq; fmt.NLODQ = nlodq; fmt.SomaticQ = somaticq;
     for (int i = 0; i < 4; i++) { fmt.TNBQF[i] = bq4[i]; fmt.TNCQF[i] = cq4[i]; }

@@ -2784,6 +2784,8 @@ DEV P5Cons p5_cons(const Arr &con, const Arr &mmm, int st) {
 // average qualities 0..127, see k_fam_p5d), a single-precision evaluation (error of realphred < 1e-5) decides both roundings unless a product
 // lies within its error bound of a half: only then (one wave iteration in ten) the fp64 expression of the reference is evaluated, which a
 // caller without the table always takes.  Two fp64 divisions and a log per cell and symbol type were most of k_fam_p5d.
+DEV double phred2prob(int phred) { return pow(10.0, (double)(-((float)phred) / 10)); }   // phred2prob's float cast, main_conversion.hpp:885-888
+DEV double phred2prob_tab(const double *p2p, int avgBQ) { return (p2p && (unsigned)avgBQ < 128u) ? p2p[avgBQ] : phred2prob(avgBQ); }
 DEV int fam_qual(const RegionDev &R, const UvcParams &P, int strand, int64_t x, int st, const P5Cons &c, const double *p2p, int &avgBQ) {
     avgBQ = ((0 == c.tot_nfrags) ? 1 : (c.con_sumBQs / c.tot_nfrags));
     const int majorcount = FAP(R, strand, UVC_FAM_cDPM, c.cs, x), minorcount = FAP(R, strand, UVC_FAM_cDPm, c.cs, x);
@@ -2803,7 +2805,7 @@ DEV int fam_qual(const RegionDev &R, const UvcParams &P, int strand, int64_t x, 
     }
     if (!safe) {
         const double prior_weight = 1.0 / (minorcount + 1.0);
-        const double p2pd = (p2p && (unsigned)avgBQ < 128u) ? p2p[avgBQ] : pow(10.0, (double)(-((float)avgBQ) / 10));   // phred2prob's float cast, main_conversion.hpp:885-888
+        const double p2pd = phred2prob_tab(p2p, avgBQ);
         const double prob = (minorcount + prior_weight) / (majorcount + minorcount + prior_weight / p2pd);
         const double realphred = -10 * log(prob) / log(10.0);
         indep_frag_phred = (int)round(kfr * realphred); round_realphred = (int)round(realphred);
@@ -3125,7 +3127,7 @@ __global__ void __launch_bounds__(256) k_fam_p5d(RegionDev R, UvcParams P) {
     const int lo = win_lo(R, 7, (int)(x0 >> 6)), hi = win_hi(R, 7, (int)(x0 >> 6));
     if (lo >= hi) return;   // block-uniform
     fam_lds_zero(a32, nullptr, bk);
-    for (int i = threadIdx.x; i < 128; i += 256) p2p_s[i] = pow(10.0, (double)(-((float)i) / 10));   // the fp64 expression of fam_qual
+    for (int i = threadIdx.x; i < 128; i += 256) p2p_s[i] = phred2prob(i);   // the fp64 expression of fam_qual
     __syncthreads();
     const int p = w0 + lane;
     const int64_t x = x0 + lane;
@@ -3964,4 +3966,23 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     }
     if (P->inferred_is_vcf_generated) TIMED(prof, "k_p5b", hipLaunchKernelGGL(k_p5b, dim3(nblk(R->npos * 2, 256)), dim3(256), 0, s, *R, *P));
     if (side) hipStreamWaitEvent(s, e_fork2, 0);   // the allele tables
+}
+
+// ------------------------------------------------------------------------------------------------
+// The scalar functions of this file on their own, for tests (the second half of uvc_launch_math_probe, uvc_kernels_score.hip): one thread
+// per row, the argument and the result as doubles.  with_table: phred2prob_tab reads the table a block of k_fam_p5d builds.
+__global__ void __launch_bounds__(256) k_math_probe_acc(int op, long long n, const double *in, int n_in, double *out, int n_out) {
+    __shared__ double p2p_s[128];
+    const bool with_table = (op == UVC_PROBE_phred2prob_tab);
+    if (with_table) { for (int i = threadIdx.x; i < 128; i += 256) p2p_s[i] = phred2prob(i); __syncthreads(); }
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int v = (int)in[i * n_in];
+    out[i * n_out] = (op == UVC_PROBE_proton_cigarlen2phred) ? (double)proton_cigarlen2phred(cig_len((uint32_t)v << 4)) :   // (a CIGAR length: 28 bits, as at the call sites)
+                     phred2prob_tab(with_table ? p2p_s : nullptr, v);
+}
+extern "C" int uvc_launch_math_probe_acc(int op, int64_t n, const double *in, int n_in, double *out, int n_out, hipStream_t s) {
+    if (op < UVC_PROBE_proton_cigarlen2phred || op >= UVC_PROBE_END || n < 1 || n > (1LL << 32) || n_in < 1 || n_out < 1 || !in || !out) return -1;
+    hipLaunchKernelGGL(k_math_probe_acc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, (long long)n, in, n_in, out, n_out);
+    return 0;
 }

@@ -21,7 +21,11 @@ DEV double dbetween(double v, double a, double b) { return dmin(dmax(a, v), b); 
 DEV double nnminus_d(double a, double b) { return a > b ? a - b : 0.0; }
 DEV double phred2nat(double x) { return (log(10.0) / 10.0) * x; }                       // common.hpp:81
 DEV double numstates2phred(double x) { return (10.0 / log(10.0)) * log(x); }            // common.hpp:85
-DEV int numstates2deciphred(double x) { return (int)round((100.0 / log(10.0)) * log(x)); }   // common.hpp:87
+// double -> int32 as the reference's x86 build converts (cvttsd2si): NaN and values out of range give INT32_MIN, where a plain device
+// conversion gives 0 / saturates.  A germ_hetero_FA outside (0, 1) makes hetLODQ's logarithms NaN; a bias fraction that dp4 returns as NaN or
+// +inf reaches numstates2deciphred.
+DEV int i32_as_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : (int)0x80000000; }
+DEV int numstates2deciphred(double x) { return i32_as_x86(round((100.0 / log(10.0)) * log(x))); }   // common.hpp:87
 DEV double prob2odds(double p) { return p / (1.0 - p); }
 DEV double logit2(double a, double b) { return log(prob2odds((a + DBL_EPS) / (a + b + 2.0 * DBL_EPS))); }   // main_conversion.hpp:216-219
 
@@ -1109,9 +1113,6 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))
 // ------------------------------------------------------------------------------------------------
 #define FLD(fld, rec) fields[(size_t)(fld) * capacity + (rec)]
 #define SYM_END UVC_NUM_SYMBOLS
-// double -> int32 as the reference's x86 build converts (cvttsd2si): NaN and values out of range give INT32_MIN, where a plain device
-// conversion gives 0 / saturates.  A germ_hetero_FA outside (0, 1) makes hetLODQ's logarithms NaN.
-DEV int i32_as_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : (int)0x80000000; }
 DEV int het_lodq(double a1, double a2, double expfrac, double powlaw_exponent) {   // hetLODQ, main.hpp:5457-5462
     const int binomLODQ = i32_as_x86(binom_llr(expfrac, a1, a2));
     const int powerLODQ = i32_as_x86(round(10.0 / log(10.0) * powlaw_exponent * dmax(logit2((a1 + 0.5) * 0.5 / expfrac, (a2 + 0.5) * 0.5 / (1.0 - expfrac)), 0.0)));
@@ -1687,4 +1688,57 @@ extern "C" void uvc_launch_block_stats_windows(const RegionDev *R, const UvcPara
 }
 extern "C" void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_block_stats, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *R, *P, (long long)x0, (long long)n, d_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The scalar functions of the scoring kernels on their own, for tests (uvc_launch.h: UvcProbeOp): each op calls the DEV function the
+// kernels call.  One thread per row.
+__global__ void __launch_bounds__(256) k_math_probe(int op, long long n, const double *in, int n_in, double *out, int n_out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *a = in + i * n_in;
+    double *o = out + i * n_out;
+    switch (op) {
+    case UVC_PROBE_phred2nat: o[0] = phred2nat(a[0]); break;
+    case UVC_PROBE_numstates2phred: o[0] = numstates2phred(a[0]); break;
+    case UVC_PROBE_numstates2deciphred: o[0] = numstates2deciphred(a[0]); break;
+    case UVC_PROBE_prob2odds: o[0] = prob2odds(a[0]); break;
+    case UVC_PROBE_logit2: o[0] = logit2(a[0], a[1]); break;
+    case UVC_PROBE_binom_llr: o[0] = binom_llr(a[0], a[1], a[2]); break;
+    case UVC_PROBE_dp4: { double r[2]; dp4(r, a[0] != 0, a[1] != 0, a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], a[12]); o[0] = r[0]; o[1] = r[1]; break; }
+    case UVC_PROBE_indel_len_rusize_phred_s: o[0] = indel_len_rusize_phred_s((int)a[0], (int)a[1]); break;
+    case UVC_PROBE_indel_phred_s: o[0] = indel_phred_s(a[0], (int)a[1], (int)a[2]); break;
+    case UVC_PROBE_more_STR_s: o[0] = more_STR_s((int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4]) ? 1 : 0; break;
+    case UVC_PROBE_norm_fa: o[0] = norm_fa(a[0], a[1]); break;
+    case UVC_PROBE_i32_as_x86: o[0] = i32_as_x86(a[0]); break;
+    case UVC_PROBE_het_lodq: o[0] = het_lodq(a[0], a[1], a[2], a[3]); break;
+    case UVC_PROBE_normv_quals: { int r[4]; normv_quals(r, a[0], a[1], (int)a[2], (int)a[3], a[4], a[5], (int)a[6], a[7], (int)a[8], (int)a[9], a[10]); for (int k = 0; k < 4; k++) o[k] = r[k]; break; }
+    case UVC_PROBE_normv_quals2: { int r[4]; normv_quals2(r, a[0], a[1], (int)a[2], (int)a[3], a[4], a[5], (int)a[6]); for (int k = 0; k < 4; k++) o[k] = r[k]; break; }
+    case UVC_PROBE_symbols_mutated: o[0] = symbols_mutated((int)a[0], (int)a[1]) ? 1 : 0; break;
+    case UVC_PROBE_sscs_phred: {
+        UvcParams P = {};
+        P.fam_phred_sscs_indel_open = (int)a[2]; P.fam_phred_sscs_indel_ext = (int)a[3]; P.fam_phred_sscs_transition_CG_TA = (int)a[4]; P.fam_phred_sscs_transition_AT_GC = (int)a[5];
+        P.fam_phred_sscs_transversion_CG_AT = (int)a[6]; P.fam_phred_sscs_transversion_other = (int)a[7]; P.tumor_vcf_fname_nonempty = (int)a[8];
+        o[0] = sscs_phred(P, (int)a[0], (int)a[1]); break;
+    }
+    case UVC_PROBE_infer_max_qual: case UVC_PROBE_infer_max_qual_regs: case UVC_PROBE_infer_max_qual_one: case UVC_PROBE_infer_max_qual_regs_one: {
+        const bool one = (op == UVC_PROBE_infer_max_qual_one || op == UVC_PROBE_infer_max_qual_regs_one), regs = (op == UVC_PROBE_infer_max_qual_regs || op == UVC_PROBE_infer_max_qual_regs_one);
+        int h[NBUCKETS], r[3];
+#pragma unroll
+        for (int k = 0; k < NBUCKETS; k++) h[k] = one ? (k == (int)a[0] ? (int)a[1] : 0) : (int)a[k];
+        const int max_qual = (int)(one ? a[2] : a[16]), dec_qual = (int)(one ? a[3] : a[17]), totDP = (int)(one ? a[4] : (regs ? a[17] : a[18]));
+        if (regs) infer_max_qual_regs(r[0], r[1], r[2], max_qual, totDP, h);
+        else infer_max_qual(r[0], r[1], r[2], max_qual, dec_qual, totDP, [&](int idx) { return h[idx]; });
+        o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; break;
+    }
+    default: break;
+    }
+}
+extern "C" int uvc_launch_math_probe(int op, int64_t n, const double *in, int n_in, double *out, int n_out, hipStream_t s) {
+    static const signed char width[UVC_PROBE_END][2] = { {1, 1}, {1, 1}, {1, 1}, {1, 1}, {2, 1}, {3, 1}, {13, 2}, {2, 1}, {3, 1}, {5, 1}, {2, 1}, {1, 1}, {4, 1}, {11, 4}, {7, 4}, {2, 1}, {9, 1},
+                                                         {19, 3}, {18, 3}, {5, 3}, {5, 3}, {1, 1}, {1, 1}, {1, 1} };
+    if (op < 0 || op >= UVC_PROBE_END || n < 1 || n > (1LL << 32) || n_in < width[op][0] || n_out < width[op][1] || !in || !out) return -1;
+    if (op >= UVC_PROBE_proton_cigarlen2phred) return uvc_launch_math_probe_acc(op, n, in, n_in, out, n_out, s);
+    else hipLaunchKernelGGL(k_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, (long long)n, in, n_in, out, n_out);
+    return 0;
 }

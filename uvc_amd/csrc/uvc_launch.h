@@ -130,6 +130,32 @@ const char *uvc_callable_name(int bit);
 // the array scan of the reports (the block counts of uvc_launch_callable_count and of the MSI call, the tile sums of the read profile):
 // in place, a[i] becomes the sum of a[0 .. i), a[n] -- one element behind the input -- the total (one block of 1 024 threads)
 void uvc_launch_block_scan(int *d_a, int n, hipStream_t s);
+// ---- the scalar DEV functions of the scoring and accumulate kernels on their own, for tests: one thread per row of `in` (n rows of n_in
+// doubles; integer arguments travel as doubles, all below 2^31) writes a row of `out` (n_out doubles; integer results as doubles).  The op
+// fixes how many arguments a row holds and how many results it gives: a call with fewer, an unknown op or n < 1 launches nothing and
+// returns -1.  uvc_launch_math_probe hands the ops of uvc_kernels_acc.hip on to uvc_launch_math_probe_acc, which checks its own three ops the same way ----
+enum UvcProbeOp {
+    UVC_PROBE_phred2nat, UVC_PROBE_numstates2phred, UVC_PROBE_numstates2deciphred, UVC_PROBE_prob2odds, UVC_PROBE_logit2,
+    UVC_PROBE_binom_llr,                 // prob, a, b
+    UVC_PROBE_dp4,                       // bidir, overseq_disabled, then dp4's eleven arguments -> 2
+    UVC_PROBE_indel_len_rusize_phred_s,  // indel_len, repeatunit_size (not 0)
+    UVC_PROBE_indel_phred_s,             // ampfact, rs, rn
+    UVC_PROBE_more_STR_s,                // rulen1, rc1, rulen2, rc2, strmax
+    UVC_PROBE_norm_fa, UVC_PROBE_i32_as_x86,
+    UVC_PROBE_het_lodq,                  // a1, a2, expfrac, powlaw_exponent
+    UVC_PROBE_normv_quals,               // its eleven arguments -> 4
+    UVC_PROBE_normv_quals2,              // its seven arguments -> 4
+    UVC_PROBE_symbols_mutated,           // ref, alt
+    UVC_PROBE_sscs_phred,                // con, alt, fam_phred_sscs_indel_open, _indel_ext, _transition_CG_TA, _transition_AT_GC, _transversion_CG_AT, _transversion_other, tumor_vcf_fname_nonempty
+    UVC_PROBE_infer_max_qual,            // 16 bucket counts, max_qual, dec_qual (> 0), totDP -> maxvqual, argmaxAD, argmaxBQ
+    UVC_PROBE_infer_max_qual_regs,       // 16 bucket counts, max_qual, totDP -> the same three
+    UVC_PROBE_infer_max_qual_one,        // bucket index, its count, max_qual, dec_qual, totDP: a histogram with one bucket filled -> the same three
+    UVC_PROBE_infer_max_qual_regs_one,   // the same row (dec_qual is not read) through infer_max_qual_regs
+    UVC_PROBE_proton_cigarlen2phred, UVC_PROBE_phred2prob, UVC_PROBE_phred2prob_tab,   // (uvc_kernels_acc.hip)
+    UVC_PROBE_END
+};
+int uvc_launch_math_probe(int op, int64_t n, const double *in, int n_in, double *out, int n_out, hipStream_t s);
+int uvc_launch_math_probe_acc(int op, int64_t n, const double *in, int n_in, double *out, int n_out, hipStream_t s);
 // ---- uvc_msi.hip: d_tab = n_ranges + 1 rows; d_blocks: uvc_msi_blocks(n_total) + 1 ints, the last one the number of loci once the kernels
 // have run; d_heads: `room` ints (the region-relative head of each locus, ascending); d_rows: `room` rows of UVC_MSI_ROW ints, zero at the
 // start.  Loci beyond `room` are counted and not written; room 0 runs the count alone ----
