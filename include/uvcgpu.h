@@ -543,6 +543,55 @@ typedef struct UvcFamilyRange { int32_t pos_beg, pos_end, prev_end, flags; } Uvc
  *   UVC_FAMRANGE_CONTINUES.  `out` is written only by a call that returns 0. */
 int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out /* [n_ranges][UVC_FAMSTAT_ROW] */);
 const char *uvcgpu_family_stat_name(int32_t id);   /* "target_families" .. "strands"; NULL for an id outside 0..UVC_NFAMSTAT - 1 */
+/* ---- fragment length and end-motif profile of ranges, from the fragments and family units of the region's reads (uvc1-mi355x
+ * --fragment-profile-out) ----
+ * All values are integers.
+ *   An alignment is counted iff mapq >= min_mapq and (flag & 0x904) == 0 (not unmapped, secondary or supplementary).  Its reference span is
+ *   [pos, rend), rend = pos + the reference length of the CIGAR (a CIGAR that consumes no reference counts one position, as for the family
+ *   statistics); it is forward iff !(flag & 0x10).  Nothing is clamped to the region.
+ *   A fragment g is one distinct (fam_id, fam_strand, frag_id) of the reads the handle holds.  Over its counted alignments nF / nR are the
+ *   numbers of forward / reverse ones, loF / hiF the smallest pos and the largest rend of the forward ones, loR / hiR those of the reverse
+ *   ones; lo_g = min(loF, loR), hi_g = max(hiF, hiR), L_g = hi_g - lo_g.  A fragment without a counted alignment adds nothing anywhere.
+ *   Every other fragment has one kind:
+ *     pair:   nF >= 1, nR >= 1, loF <= loR and hiF <= hiR (the forward end is leftmost, the reverse end rightmost: the span is the template);
+ *     other:  nF >= 1 and nR >= 1 otherwise (everted, or one mate reaching past the other);
+ *     single: one orientation only (the span is not a template length).
+ *   A family f is one fam_id, both strand units joined.  It is sized iff it has at least one pair fragment; its template is
+ *   [tlo_f, thi_f) = the smallest lo_g and the largest hi_g over its pair fragments, TL_f = thi_f - tlo_f.
+ *   Ranges are UvcFamilyRange rows with the rules and refusals of uvcgpu_region_family_stats; overlap, UVC_FAMRANGE_CONTINUES and prev_end
+ *   mean what they mean there, applied to [lo_g, hi_g) for the fragment counters and to [tlo_f, thi_f) for the family counters.
+ * out_ranges: UVC_FRAGPROF_TARGET_ROW int64 per range, the TARGET rule (every overlapping object; with UVC_FAMRANGE_CONTINUES only those
+ *   that begin at or behind pos_beg): pairs, others, singles, len_sum (the sum of L_g over the pairs), short (pairs with
+ *   short_lo <= L_g <= short_hi), long (the same with the long bounds), families (sized families), a reserved 0.
+ * out_profile: one row of UVC_FRAGPROF_ROW int64 per call (sections: include/uvc_fragprofile.def), the FIRST rule (an object counts iff
+ *   there is a range that it overlaps and whose prev_end is at most its begin: once per call however many ranges it spans): the eight
+ *   words above, families_both_strands (sized families with a pair fragment in each strand unit), ends, ends_off_region, ends_no_ref,
+ *   reserved zeros up to 16 words; LEN[1024] (pairs, bin min(L_g, 1023)); FAMLEN[1024] (sized families, bin min(TL_f, 1023)); MOTIF[256].
+ *   End motifs come from the reference, so soft clips and base errors do not enter.  Each pair fragment counted in the profile has two 5'
+ *   ends.  With x = lo_g - beg, y = hi_g - beg and n = the positions of the region that hold a reference base (its last position holds
+ *   none): the left end is usable iff x >= 0 and x + 4 <= n, its symbols are s_k = ref[x + k]; the right end is usable iff y - 4 >= 0 and
+ *   y <= n, its symbols are s_k = 3 - ref[y - 1 - k] (the reverse complement; A C G T are 0..3), k = 0..3.  An end that is not usable adds
+ *   to ends_off_region; a usable end with a symbol above UVC_BASE_T to ends_no_ref; any other end to ends and to
+ *   MOTIF[s_0 * 64 + s_1 * 16 + s_2 * 4 + s_3].
+ * A fragment and a family are seen as the region they were grouped in sees them: next to a tile cut a fragment may lack the mate that the
+ * fetch of the neighbouring tile holds, so sums over tiles depend on the cuts. */
+enum UvcFragProfSection { UVC_FRAGPROF_pairs = 0, UVC_FRAGPROF_others, UVC_FRAGPROF_singles, UVC_FRAGPROF_len_sum, UVC_FRAGPROF_short,
+                          UVC_FRAGPROF_long, UVC_FRAGPROF_families, UVC_FRAGPROF_reserved, UVC_FRAGPROF_families_both_strands,
+                          UVC_FRAGPROF_ends, UVC_FRAGPROF_ends_off_region, UVC_FRAGPROF_ends_no_ref, UVC_FRAGPROF_reserved2,
+                          UVC_FRAGPROF_LEN, UVC_FRAGPROF_FAMLEN, UVC_FRAGPROF_MOTIF, UVC_NFRAGPROF };
+enum { UVC_FRAGPROF_TARGET_ROW = 8, UVC_FRAGPROF_NCOUNTER = 16, UVC_FRAGPROF_NLEN = 1024, UVC_FRAGPROF_NMOTIF = 256,
+       UVC_FRAGPROF_LEN_BINS = 16, UVC_FRAGPROF_FAMLEN_BINS = 1040 /* 16 + 1024 */, UVC_FRAGPROF_MOTIF_BINS = 2064 /* + 1024 */,
+       UVC_FRAGPROF_ROW = 2320 /* + 256 */ };
+typedef struct UvcFragmentProfileRequest { int32_t min_mapq, short_lo, short_hi, long_lo, long_hi; } UvcFragmentProfileRequest;
+/* Reduced on the device from the per-alignment columns, the fragments and the unit records of set_reads; integers only, the same bits from
+ * call to call.  Legal where uvcgpu_region_family_stats is: from uvcgpu_region_set_reads / _set_reads_device of the current region on (zero
+ * reads: zeros), with or without accumulate, after any score and while a score stream is open.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason: what uvcgpu_region_family_stats refuses; NULL req, out_ranges or
+ *   out_profile; min_mapq outside 0..255; a bound below 0; short_lo > short_hi or long_lo > long_hi.  The outputs are written only by a
+ *   call that returns 0. */
+int uvcgpu_region_fragment_profile(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, const UvcFragmentProfileRequest *req,
+                                   int64_t *out_ranges /* [n_ranges][UVC_FRAGPROF_TARGET_ROW] */, int64_t *out_profile /* [UVC_FRAGPROF_ROW] */);
+const char *uvcgpu_fragment_profile_name(int32_t id);   /* "pairs" .. "MOTIF"; NULL for an id outside 0..UVC_NFRAGPROF - 1 */
 /* ---- base-quality and cycle profile of the region's reads (uvc1-mi355x --read-profile-out) ----
  * One pass over the read bases the handle holds (UvcReadSoA): what the reported qualities are worth, where along the read mismatches,
  * InDels and clips fall, and which substitutions each read class makes.  All integers.

@@ -210,6 +210,24 @@ int64_t uvcio_famstats_add_target(uvcio_famstats_t *f, const char *chrom, int64_
 int uvcio_famstats_add_piece(uvcio_famstats_t *f, int64_t target, const int64_t *row /* [365] */);
 int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path);
 void uvcio_famstats_close(uvcio_famstats_t *f);
+/* ---- the fragment length and end-motif profile (uvc1-mi355x --fragment-profile-out) ----
+ * What tiles report with uvcgpu_region_fragment_profile: per piece a TARGET row (8 int64: pairs others singles len_sum short long families,
+ * a reserved 0) and per call the profile row (2320 int64: 16 counters, LEN[1024], FAMLEN[1024], MOTIF[256]; include/uvc_fragprofile.def).
+ * Targets are added in report order before the pieces; add_piece adds a TARGET row to its target and add_profile a profile row to the
+ * run's sum, under a lock: both come in any order and from any thread.
+ * write: "##fragment_profile=1", "##fragment_profile_min_mapq=", "##fragment_profile_short=A-B", "##fragment_profile_long=A-B" and one more
+ * "##" line; "#summary" and name<TAB>value lines -- pairs others singles len_sum short long families families_both_strands ends
+ * ends_off_region ends_no_ref of the profile sum; "#length\tfragments\tfamilies" and 1024 lines (0 .. 1022, 1023+: LEN and FAMLEN);
+ * "#end_motif\tcount" and 256 lines (AAAA .. TTTT); "#chrom\tbeg\tend\tname\tpairs\tothers\tsingles\tlen_sum\tshort\tlong\tfamilies" and one
+ * line per target in the order they were added, zeros for a target without pieces.  Integers only: ratios are the reader's.  A path that
+ * ends in .gz is written block-gzipped (uvcio_bgzf_write_*). */
+typedef struct uvcio_fragprofile uvcio_fragprofile_t;
+int uvcio_fragprofile_open(uvcio_fragprofile_t **out, int32_t min_mapq, int32_t short_lo, int32_t short_hi, int32_t long_lo, int32_t long_hi);
+int64_t uvcio_fragprofile_add_target(uvcio_fragprofile_t *f, const char *chrom, int64_t beg, int64_t end, const char *name /* NULL or empty: "." */);   /* -> its index, < 0 on error */
+int uvcio_fragprofile_add_piece(uvcio_fragprofile_t *f, int64_t target, const int64_t *row /* [8] */);
+int uvcio_fragprofile_add_profile(uvcio_fragprofile_t *f, const int64_t *profile /* [2320] */);
+int uvcio_fragprofile_write(const uvcio_fragprofile_t *f, const char *path);
+void uvcio_fragprofile_close(uvcio_fragprofile_t *f);
 /* ---- the read profile (uvc1-mi355x --read-profile-out) ----
  * The sum of the rows that tiles report with uvcgpu_region_read_profile (5712 int64: Q[4][64][2], CYC[4][256][5], SUB[4][4][4], 16 counters);
  * rows of disjoint position sets add, so add() sums under a lock, from any thread in any order.  write(): "##read_profile_min_mapq=",

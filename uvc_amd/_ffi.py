@@ -91,6 +91,10 @@ class UvcFamilyRange(C.Structure):
     _fields_ = [("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("prev_end", C.c_int32), ("flags", C.c_int32)]
 
 
+class UvcFragmentProfileRequest(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("short_lo", C.c_int32), ("short_hi", C.c_int32), ("long_lo", C.c_int32), ("long_hi", C.c_int32)]
+
+
 class UvcCallableRequest(C.Structure):
     _fields_ = [("min_depth", C.c_int32 * 6), ("max_aDP", C.c_int32)]
 
@@ -171,6 +175,15 @@ FAMSTAT_SECTIONS = _read_def("uvc_famstats.def", "UVC_FAMSTAT")
 FAMILY_STATS = [n for n, _, _ in FAMSTAT_SECTIONS]
 assert [ENUMS["UVC_FAMSTAT_" + n] for n in FAMILY_STATS] == list(range(ENUMS["UVC_NFAMSTAT"]))
 assert sum(w for _, _, w in FAMSTAT_SECTIONS) == ENUMS["UVC_FAMSTAT_ROW"] and all(f == sum(w for _, _, w in FAMSTAT_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMSTAT_SECTIONS))
+
+# the sections of a fragment-profile row in id order (UvcFragProfSection): the table of include/uvc_fragprofile.def, checked against the header's enums
+FRAGPROF_SECTIONS = _read_def("uvc_fragprofile.def", "UVC_FRAGPROF")
+FRAGMENT_PROFILE = [n for n, _, _ in FRAGPROF_SECTIONS]
+assert [ENUMS["UVC_FRAGPROF_" + n] for n in FRAGMENT_PROFILE] == list(range(ENUMS["UVC_NFRAGPROF"]))
+assert sum(w for _, _, w in FRAGPROF_SECTIONS) == ENUMS["UVC_FRAGPROF_ROW"] and all(f == sum(w for _, _, w in FRAGPROF_SECTIONS[:k]) for k, (_, f, _) in enumerate(FRAGPROF_SECTIONS))
+assert [f for _, f, _ in FRAGPROF_SECTIONS[:ENUMS["UVC_FRAGPROF_TARGET_ROW"]]] == list(range(ENUMS["UVC_FRAGPROF_TARGET_ROW"])), "the first eight sections are the words of a TARGET row"
+assert {n: (f, w) for n, f, w in FRAGPROF_SECTIONS}["LEN"] == (ENUMS["UVC_FRAGPROF_LEN_BINS"], ENUMS["UVC_FRAGPROF_NLEN"]) and {n: (f, w) for n, f, w in FRAGPROF_SECTIONS}["FAMLEN"] == (ENUMS["UVC_FRAGPROF_FAMLEN_BINS"], ENUMS["UVC_FRAGPROF_NLEN"])
+assert {n: (f, w) for n, f, w in FRAGPROF_SECTIONS}["MOTIF"] == (ENUMS["UVC_FRAGPROF_MOTIF_BINS"], ENUMS["UVC_FRAGPROF_NMOTIF"]) and ENUMS["UVC_FRAGPROF_LEN_BINS"] == ENUMS["UVC_FRAGPROF_NCOUNTER"]
 
 # the sections of a read-profile row in id order (UvcReadProfSection): the table of include/uvc_readprofile.def, checked against the header's enums
 READPROF_SECTIONS = _read_def("uvc_readprofile.def", "UVC_READPROF")

@@ -39,12 +39,12 @@
 namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
-// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m), in the order their options are checked: of several faults the first in
+// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o), in the order their options are checked: of several faults the first in
 // this order is the one reported.
 // A row holds what the command line says of a report in more than one place: parse (the path, "a sub-option was given", the checks behind
 // the loop), split_pair (pair mode writes none) and main (the probe of the path).  A new report is a row here, an Opts store, a
 // *_of_tile and its open / write lines in main.
-enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, N_REPORTS };
+enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, N_REPORTS };
 struct ReportRow {
     const char *out;                 // --X-out PATH
     const char *subs[6];             // the options that only shape this report: each needs --X-out (the list ends with a null)
@@ -64,6 +64,8 @@ const ReportRow REPORTS[N_REPORTS] = {
       "--msi-min-tract, --msi-min-units, --msi-max-unit, --msi-min-depth and --msi-unstable-permille need --msi-out: they only shape that file" },
     { "--read-profile-out", { "--read-profile-min-mapq", "--read-profile-min-depth", "--read-profile-max-alt-permille" }, nullptr, "every shard would write a part of the profile", "every tile would be counted that many times", "read profile",
       "--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report" },
+    { "--fragment-profile-out", { "--fragment-profile-window", "--fragment-profile-min-mapq", "--fragment-profile-short", "--fragment-profile-long" }, "--fragment-profile-window", "a target can straddle shards",
+      "every tile would be counted that many times", "fragment profile", nullptr },
 };
 // the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
 int report_of(const std::string &name, int *sub) {
@@ -100,6 +102,8 @@ struct Opts {
     uvcio_msi_t *msi = nullptr;   // --msi-out: the tally's store, filled by the workers (main); its targets are those of --callable-out (call_contig_target, call_target_span)
     UvcReadProfileRequest readprof_req{ 0, 20, 50 };   // --read-profile-min-mapq, --read-profile-min-depth, --read-profile-max-alt-permille
     uvcio_readprofile_t *readprof = nullptr;   // --read-profile-out: the run's row, summed over the tiles by the workers (main)
+    UvcFragmentProfileRequest fragprof_req{ 0, 100, 150, 151, 220 };   // --fragment-profile-min-mapq, --fragment-profile-short A-B, --fragment-profile-long A-B
+    uvcio_fragprofile_t *fragprof = nullptr;   // --fragment-profile-out: the report's store, filled by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -165,6 +169,11 @@ const OptRow OPTS[] = {
     { "--read-profile-min-mapq", O_CLI, false, "0", "with --read-profile-out: only alignments of at least this mapping quality are counted (0..255)" },
     { "--read-profile-min-depth", O_CLI, false, "20", "with --read-profile-out: a base enters the bins only where at least this many counted A/C/G/T bases cover the position (1 or more)" },
     { "--read-profile-max-alt-permille", O_CLI, false, "50", "with --read-profile-out: a position whose mismatching bases are above this many thousandths of its depth counts as variant and stays out of the bins (0..1000)" },
+    { "--fragment-profile-out", O_CLI, false, "", "write the fragment length and end-motif profile here (tab-separated; block-gzipped when the name ends in .gz): of the fragments and read families the caller formed, over all targets the FR pairs, other two-orientation and one-orientation fragments, the template lengths of the pairs and of the families in 1024 one-bp bins, the short and long pairs and the 256 four-base reference motifs at the 5' ends of the pairs, each counted once, and per target -- BED line, or --fragment-profile-window -- the same counters; integers only" },
+    { "--fragment-profile-window", O_CLI, false, "0", "with --fragment-profile-out and no BED file: the targets are windows of this many bp, aligned to multiples of it on each contig and clipped to the called span" },
+    { "--fragment-profile-min-mapq", O_CLI, false, "0", "with --fragment-profile-out: only alignments of at least this mapping quality are counted (0..255)" },
+    { "--fragment-profile-short", O_CLI, false, "100-150", "with --fragment-profile-out: A-B, the template lengths in bp (both inclusive) of a short pair" },
+    { "--fragment-profile-long", O_CLI, false, "151-220", "with --fragment-profile-out: A-B, the template lengths in bp (both inclusive) of a long pair" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -371,7 +380,7 @@ Opts parse(int argc, char **argv) {
                 if (o.coverage_thr.size() > (size_t)UVC_COV_MAX_THRESHOLDS) die("--coverage-thresholds takes at most " + std::to_string((int)UVC_COV_MAX_THRESHOLDS) + " depths, not '" + v + "'");
             });
         }
-        else if (n0 == "--coverage-window" || n0 == "--family-stats-window") o.report[rep].window = whole_number(n0, val(), 1, 2e9, "a window length in bp");
+        else if (n0 == "--coverage-window" || n0 == "--family-stats-window" || n0 == "--fragment-profile-window") o.report[rep].window = whole_number(n0, val(), 1, 2e9, "a window length in bp");
         else if (n0 == "--error-profile-min-depth") o.errprof_req.min_depth = (int32_t)whole_number(n0, val(), 1, 2e9, "a depth of at least 1");
         else if (n0 == "--error-profile-max-alt-permille") o.errprof_req.max_alt_permille = (int32_t)whole_number(n0, val(), 0, 1000, "thousandths from 0 to 1000");
         else if (n0 == "--callable-min-depth") {   // NAME=N,...: the names of uvcgpu_coverage_measure_name, each at most once, whole numbers >= 0
@@ -399,6 +408,15 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--read-profile-min-mapq") o.readprof_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
         else if (n0 == "--read-profile-min-depth") o.readprof_req.min_depth = (int32_t)whole_number(n0, val(), 1, 2e9, "a depth of at least 1");
         else if (n0 == "--read-profile-max-alt-permille") o.readprof_req.max_alt_permille = (int32_t)whole_number(n0, val(), 0, 1000, "thousandths from 0 to 1000");
+        else if (n0 == "--fragment-profile-min-mapq") o.fragprof_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
+        else if (n0 == "--fragment-profile-short" || n0 == "--fragment-profile-long") {   // A-B: two whole numbers >= 0, A <= B
+            const std::string v = val();
+            const size_t dash = v.find('-');
+            int64_t a = 0, b = 0;
+            if (dash == std::string::npos || !is_whole(v.substr(0, dash), 0, 2e9, N_DIGITS, &a) || !is_whole(v.substr(dash + 1), 0, 2e9, N_DIGITS, &b)) die(n0 + " takes A-B, two lengths in bp such as 100-150, not '" + v + "'");
+            if (a > b) die(n0 + " takes A-B with A at most B, not '" + v + "'");
+            if (n0 == "--fragment-profile-short") { o.fragprof_req.short_lo = (int32_t)a; o.fragprof_req.short_hi = (int32_t)b; } else { o.fragprof_req.long_lo = (int32_t)a; o.fragprof_req.long_hi = (int32_t)b; }
+        }
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -476,8 +494,9 @@ void print_params(const Opts &o, const char *prefix = "") {
 // `run_beg` = begin of the run (incluBegPosition of the BED line the run came from, main.cpp:655-656).
 // `target` (--coverage-out with a BED file): the report row of the BED line the tile was cut from.
 // `fam_target` (--family-stats-out with a BED file): the same for the family report.
+// `frag_target` (--fragment-profile-out with a BED file): the same for the fragment profile.
 // `call_target` (--callable-out, --msi-out): the store's target the tile was cut from; -1 (the reference's own cuts): the called span of its contig.
-struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; int64_t fam_target = -1; int64_t call_target = -1; };
+struct Tile { int32_t tid; std::string chrom; int64_t beg, end; bool continues, has_next; int64_t run_beg; int64_t target = -1; int64_t fam_target = -1; int64_t call_target = -1; int64_t frag_target = -1; };
 
 // one worker: its own handles, one region handle for all of its tiles
 struct Worker {
@@ -493,8 +512,8 @@ struct Worker {
     // the reports: the pieces of one tile and their targets.  One list each for all of them: every *_of_tile clears it, fills it, calls and
     // hands the result to its store before the next one runs
     std::vector<UvcCoverageRange> ranges; std::vector<int64_t> targets;
-    std::vector<UvcFamilyRange> fam_ranges;   // --family-stats-out: its pieces carry more than a range
-    std::vector<int64_t> cov_rows, fam_rows, rp_row;   // --coverage-out, --family-stats-out, --read-profile-out: what the device call fills
+    std::vector<UvcFamilyRange> fam_ranges;   // --family-stats-out, --fragment-profile-out: their pieces carry more than a range
+    std::vector<int64_t> cov_rows, fam_rows, rp_row, frag_rows;   // --coverage-out, --family-stats-out, --read-profile-out, --fragment-profile-out: what the device call fills
     std::vector<UvcCallableRun> call_runs;   // --callable-out: the runs, as many as the last tiles had
     std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the loci, as many as the last tiles had
 };
@@ -591,19 +610,35 @@ void msi_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, 
 // no families.  prev_end: the largest end of the pieces planned before it on the contig, at most its own begin (sorted, disjoint targets:
 // the end of the piece before); flags: UVC_FAMRANGE_CONTINUES where the piece before belongs to the same target.
 struct FamPiece { int64_t beg, end, prev_end; int32_t flags; int64_t target; };
-// One uvcgpu_region_family_stats over the pieces of a tile (of the `n_tiles` tiles of a merged batch), after set_reads: the rows go to the report.
-void family_stats_of_tile(Worker &w, const Opts &o, const std::vector<FamPiece> *pieces, size_t n_tiles, int64_t ext_end) {
+// w.fam_ranges, w.targets = the pieces of a tile (of the `n_tiles` tiles of a merged batch) inside the region, with their targets; false: there are none
+bool piece_ranges(Worker &w, const std::vector<FamPiece> *pieces, size_t n_tiles, int64_t ext_end) {
     w.fam_ranges.clear(); w.targets.clear();
     for (size_t q = 0; q < n_tiles; q++)
         for (const FamPiece &p : pieces[q]) {
             const int64_t e = std::min(p.end, ext_end + 1);   // (the region holds [ext_beg, ext_end]; a tile lies inside it)
             if (e > p.beg) { w.fam_ranges.push_back(UvcFamilyRange{ (int32_t)p.beg, (int32_t)e, (int32_t)p.prev_end, p.flags }); w.targets.push_back(p.target); }
         }
-    if (w.fam_ranges.empty()) return;
+    return !w.fam_ranges.empty();
+}
+// One uvcgpu_region_family_stats over the pieces of a tile (of the `n_tiles` tiles of a merged batch), after set_reads: the rows go to the report.
+void family_stats_of_tile(Worker &w, const Opts &o, const std::vector<FamPiece> *pieces, size_t n_tiles, int64_t ext_end) {
+    if (!piece_ranges(w, pieces, n_tiles, ext_end)) return;
     w.fam_rows.resize(w.fam_ranges.size() * (size_t)UVC_FAMSTAT_ROW);
     if (uvcgpu_region_family_stats(w.reg, w.fam_ranges.data(), (int64_t)w.fam_ranges.size(), w.fam_rows.data())) die(uvcgpu_last_error());
     for (size_t q = 0; q < w.fam_ranges.size(); q++)
         if (uvcio_famstats_add_piece(o.fam, w.targets[q], &w.fam_rows[q * (size_t)UVC_FAMSTAT_ROW])) die(uvcio_last_error());
+}
+// --fragment-profile-out: one uvcgpu_region_fragment_profile over the pieces of a tile, planned as the family report's are (plan_family_pieces
+// for this report's own targets or windows), after set_reads: the TARGET rows go to their targets, the profile row to the run's sum.
+void fragment_profile_of_tile(Worker &w, const Opts &o, const std::vector<FamPiece> *pieces, size_t n_tiles, int64_t ext_end) {
+    if (!piece_ranges(w, pieces, n_tiles, ext_end)) return;
+    const size_t n = w.fam_ranges.size();
+    w.frag_rows.resize(n * (size_t)UVC_FRAGPROF_TARGET_ROW + (size_t)UVC_FRAGPROF_ROW);
+    int64_t *prof = &w.frag_rows[n * (size_t)UVC_FRAGPROF_TARGET_ROW];
+    if (uvcgpu_region_fragment_profile(w.reg, w.fam_ranges.data(), (int64_t)n, &o.fragprof_req, w.frag_rows.data(), prof)) die(uvcgpu_last_error());
+    for (size_t q = 0; q < n; q++)
+        if (uvcio_fragprofile_add_piece(o.fragprof, w.targets[q], &w.frag_rows[q * (size_t)UVC_FRAGPROF_TARGET_ROW])) die(uvcio_last_error());
+    if (uvcio_fragprofile_add_profile(o.fragprof, prof)) die(uvcio_last_error());
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // The record text of one call behind `lines`: write(dst, room, &len) into a buffer as large as the last tiles needed (+ slack); a second
@@ -630,7 +665,7 @@ template <class F> void append_text(Worker &w, std::string &lines, F write) {
 // entries: the kept alignments that overlap each line.  n_merged = 0: the plain call of one tile.
 bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, int64_t tlen, const uvcio_tumor_vcf_t *tvcf, std::string &lines, int64_t *n_kept_reads,
                const std::function<void(int32_t, int64_t, int64_t)> *tumor_ready = nullptr, size_t n_merged = 0, const CovSpan *cov_span = nullptr,
-               const std::vector<FamPiece> *fam_pieces = nullptr) {
+               const std::vector<FamPiece> *fam_pieces = nullptr, const std::vector<FamPiece> *frag_pieces = nullptr) {
     double t0 = now();
     for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) n_kept_reads[q] = 0;
     Tile t = t0_;
@@ -696,6 +731,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (uvcgpu_region_set_reads(w.reg, &rs)) die(uvcgpu_last_error());
     w.t_reads += now() - t0; t0 = now();
     if (o.fam && fam_pieces) family_stats_of_tile(w, o, fam_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --family-stats-out: the units of set_reads, before anything else
+    if (o.fragprof && frag_pieces) fragment_profile_of_tile(w, o, frag_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --fragment-profile-out: the fragments and units of set_reads
     // --coverage-out, --error-profile-out, --callable-out, --read-profile-out: the positions this tile owns -- the [first, last_excl) that scoring and
     // uvcio_sites_fetch go by, without the end point t.end itself, which lies outside every target the tile was cut from (and which two regions of
     // the reference's cuts share).  The list depends on scored() alone: made here, in front of accumulate, for the report of the reads as well.
@@ -814,7 +850,9 @@ void link_runs(std::vector<Tile> &tiles) {
 // --coverage-out: the report's rows are added here in target order -- the BED lines in file order (every tile carries its line's row), or
 // the windows of every called span (cov_spans: per contig the row of the span's first window)
 // --family-stats-out: its rows are added the same way (fam_spans, Tile::fam_target)
-std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr, std::vector<CovSpan> *cov_spans = nullptr, std::vector<CovSpan> *fam_spans = nullptr) {
+// --fragment-profile-out: and so are its (frag_spans, Tile::frag_target)
+std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std::vector<int64_t> *batch_of = nullptr, std::vector<CovSpan> *cov_spans = nullptr, std::vector<CovSpan> *fam_spans = nullptr,
+                              std::vector<CovSpan> *frag_spans = nullptr) {
     const std::vector<std::string> &names = G.names; const std::vector<int64_t> &lens = G.lens; const int32_t nref = (int32_t)names.size();
     std::vector<Tile> tiles;
     const std::string bed_path = (!o.bed_in.empty() ? o.bed_in : o.bed);
@@ -831,7 +869,7 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
     if (ref_cuts && uvcio_planner_open(&planner, lens.data(), nref, (o.threads > 0 ? o.threads : 8) /* the reference's -t default (CmdLineArgs.hpp:34): enters only where a batch of regions ends */, o.mem_per_thread)) die(uvcio_last_error());
     std::vector<int32_t> pl_tid, pl_pos, pl_end; std::vector<uint16_t> pl_flag;   // one window's columns
     auto take_cuts = [&]() { UvcRegionCut c[256]; int64_t k; while ((k = uvcio_planner_take(planner, c, 256)) > 0) for (int64_t q = 0; q < k; q++) tiles.push_back(Tile{ c[q].tid, names[(size_t)c[q].tid], c[q].beg, c[q].end, false, false, c[q].beg }); };
-    int64_t cov_target = -1, fam_target = -1, call_target = -1;   // the report rows of the BED line being added
+    int64_t cov_target = -1, fam_target = -1, call_target = -1, frag_target = -1;   // the report rows of the BED line being added
     if (o.callable || o.msi) o.call_contig_target.assign((size_t)nref, -1);
     // a target of --callable-out and --msi-out: both stores take the same targets in the same order, so one index names it in both
     auto add_span_target = [&](const char *chrom, int64_t beg, int64_t end, const char *name) {
@@ -857,11 +895,13 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
             window_targets("--coverage-window", o.report[R_COVERAGE].window, (*cov_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_coverage_add_target(o.cov, chrom, wb, we, nullptr, we - wb); });
         if (o.fam && fam_spans && o.report[R_FAMSTATS].window > 0 && end > beg)
             window_targets("--family-stats-window", o.report[R_FAMSTATS].window, (*fam_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_famstats_add_target(o.fam, chrom, wb, we, nullptr); });
+        if (o.fragprof && frag_spans && o.report[R_FRAGPROF].window > 0 && end > beg)
+            window_targets("--fragment-profile-window", o.report[R_FRAGPROF].window, (*frag_spans)[(size_t)tid], [&](int64_t wb, int64_t we) { return uvcio_fragprofile_add_target(o.fragprof, chrom, wb, we, nullptr); });
         if ((o.callable || o.msi) && bed_path.empty()) {   // --callable-out, --msi-out without a BED file: the called span of the contig is one target
             if (o.call_contig_target[(size_t)tid] >= 0) die("--callable-out, --msi-out: a contig is called twice (internal error)");
             call_target = o.call_contig_target[(size_t)tid] = add_span_target(names[(size_t)tid].c_str(), beg, end, nullptr);
         }
-        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target, fam_target, call_target }); return; }
+        if (!ref_cuts) { for (int64_t b = beg; b < end; b += o.tile) tiles.push_back(Tile{ tid, names[(size_t)tid], b, std::min(b + o.tile, end), false, false, b, cov_target, fam_target, call_target, frag_target }); return; }
         const int64_t W = 4000000;   // the planning pass reads the span window by window; an alignment is taken by the window it starts in (the first window also takes those that reach into it)
         for (int64_t wb = beg; wb < end; wb += W) {
             UvcBamBatch b;
@@ -897,6 +937,10 @@ std::vector<Tile> plan_tiles(Opts &o, uvcio_bam_t *bam0, const Geometry &G, std:
             if (o.fam) {   // one report row per BED line, its own numbers and column 4 as the name
                 fam_target = uvcio_famstats_add_target(o.fam, chrom, b, e, n_col >= 4 ? bname : nullptr);
                 if (fam_target < 0) die(uvcio_last_error());
+            }
+            if (o.fragprof) {   // one report row per BED line, its own numbers and column 4 as the name
+                frag_target = uvcio_fragprofile_add_target(o.fragprof, chrom, b, e, n_col >= 4 ? bname : nullptr);
+                if (frag_target < 0) die(uvcio_last_error());
             }
             if (o.callable || o.msi)   // one target per BED line: its positions inside the contig, column 4 as the name
                 call_target = add_span_target(chrom, std::max<long long>(0, b), std::min<long long>(e, lens[(size_t)tid]), n_col >= 4 ? bname : nullptr);
@@ -1010,19 +1054,19 @@ void reader_switches(const Opts &o) {
 // The command line split as uvcTN.sh splits it: options before the first --tumor-params / --normal-params go to both sides, after one of
 // them to that side only, until the other.  Side lists take PARAM / GROUP / MODE / INERT options; a CLI option there is refused.
 struct PairArgs { bool pair = false, side_lists = false; std::string normal_bam, tumor_out; std::vector<std::string> shared, side[2]; };
-// --family-stats-out: the pieces of every tile (see FamPiece), in plan order
-std::vector<std::vector<FamPiece>> plan_family_pieces(const Opts &o, const std::vector<Tile> &tiles, const std::vector<CovSpan> &spans, int32_t nref) {
+// --family-stats-out, --fragment-profile-out (`opt`): the pieces of every tile (see FamPiece), in plan order, for the report's own targets
+// (`target_of` of a tile) or windows of N bp
+std::vector<std::vector<FamPiece>> plan_family_pieces(const char *opt, int64_t N, int64_t Tile::*target_of, const std::vector<Tile> &tiles, const std::vector<CovSpan> &spans, int32_t nref) {
     std::vector<std::vector<FamPiece>> plan(tiles.size());
     std::vector<int64_t> reach((size_t)nref, 0);   // per contig: the largest end of the pieces planned so far
     int64_t last_target = -1;
-    const int64_t N = o.report[R_FAMSTATS].window;
     for (size_t q = 0; q < tiles.size(); q++) {
         const Tile &t = tiles[q];
         for (int64_t b = t.beg; b < t.end;) {
-            int64_t stop = t.end, target = t.fam_target;
+            int64_t stop = t.end, target = t.*target_of;
             if (target < 0) {   // window mode
                 const CovSpan &sp = spans[(size_t)t.tid];
-                if (N <= 0 || sp.first < 0 || b < sp.origin) die("--family-stats-out: a tile outside the planned windows (internal error)");
+                if (N <= 0 || sp.first < 0 || b < sp.origin) die(std::string(opt) + ": a tile outside the planned windows (internal error)");
                 stop = std::min(t.end, (b / N + 1) * N); target = sp.first + (b / N - sp.origin / N);
             }
             plan[q].push_back(FamPiece{ b, stop, std::min(b, reach[(size_t)t.tid]), target == last_target ? UVC_FAMRANGE_CONTINUES : 0, target });
@@ -1345,9 +1389,12 @@ int main(int argc, char **argv) {
     if (wanted(R_READPROF) && uvcio_readprofile_open(&o.readprof, names_of(uvcgpu_read_class_name, UVC_READPROF_NCLASS).data(), o.readprof_req.min_mapq, o.readprof_req.min_depth, o.readprof_req.max_alt_permille)) die(uvcio_last_error());
     std::vector<CovSpan> fam_spans((size_t)nref);
     if (wanted(R_FAMSTATS) && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
-    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans);
-    std::vector<std::vector<FamPiece>> fam_plan;
-    if (o.fam) fam_plan = plan_family_pieces(o, tiles, fam_spans, nref);
+    std::vector<CovSpan> frag_spans((size_t)nref);
+    if (wanted(R_FRAGPROF) && uvcio_fragprofile_open(&o.fragprof, o.fragprof_req.min_mapq, o.fragprof_req.short_lo, o.fragprof_req.short_hi, o.fragprof_req.long_lo, o.fragprof_req.long_hi)) die(uvcio_last_error());
+    std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans, &frag_spans);
+    std::vector<std::vector<FamPiece>> fam_plan, frag_plan;
+    if (o.fam) fam_plan = plan_family_pieces(REPORTS[R_FAMSTATS].out, o.report[R_FAMSTATS].window, &Tile::fam_target, tiles, fam_spans, nref);
+    if (o.fragprof) frag_plan = plan_family_pieces(REPORTS[R_FRAGPROF].out, o.report[R_FRAGPROF].window, &Tile::frag_target, tiles, frag_spans, nref);
     if (o.n_shards > 1) {
         std::vector<int32_t> shard_of = plan_shard_of(o, bam0, tiles);
         if (!batch_of.empty()) {   // balanced over batches: a batch is one region and goes to one shard, at the sum of its tiles' costs
@@ -1422,7 +1469,7 @@ int main(int argc, char **argv) {
             // 4 * threads in front of it, so a slow early tile cannot make the rest of the genome pile up in memory
             { std::unique_lock<std::mutex> g(mu); cv.wait(g, [&] { return ji < written + max_ahead; }); }
             std::string lines; std::vector<int64_t> nk(nt, 0);
-            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0, &cov_spans[(size_t)tiles[ti].tid], o.fam ? &fam_plan[ti] : nullptr);
+            call_tile(w, o, P, tiles[ti], G.lens[(size_t)tiles[ti].tid], tvcf, lines, nk.data(), nullptr, merging ? nt : 0, &cov_spans[(size_t)tiles[ti].tid], o.fam ? &fam_plan[ti] : nullptr, o.fragprof ? &frag_plan[ti] : nullptr);
             w.n_tiles++;
             { std::lock_guard<std::mutex> g(mu); done[ji].swap(lines); ready[ji] = 1; for (size_t q = 0; q < nt; q++) tile_reads[ti + q] = nk[q]; }
             cv.notify_all();
@@ -1458,6 +1505,7 @@ int main(int argc, char **argv) {
     }
     if (o.errprof) { finish(R_ERRPROF, uvcio_errprofile_write(o.errprof, path(R_ERRPROF))); uvcio_errprofile_close(o.errprof); }
     if (o.readprof) { finish(R_READPROF, uvcio_readprofile_write(o.readprof, path(R_READPROF))); uvcio_readprofile_close(o.readprof); }
+    if (o.fragprof) { finish(R_FRAGPROF, uvcio_fragprofile_write(o.fragprof, path(R_FRAGPROF))); uvcio_fragprofile_close(o.fragprof); }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

@@ -118,7 +118,7 @@ struct uvcgpu_region {
     Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
     Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
-    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1341,8 +1341,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile and _msi ----
-// What the six share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi and _fragment_profile ----
+// What the seven share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1468,10 +1468,8 @@ const char *uvcgpu_error_level_name(int32_t id) { return uvc_errprofile_level_na
 // The unit records, the fragments and the per-alignment columns belong to the reads of the handle (uvcgpu_region::owned): only set_reads, reset
 // and destroy free them, and the first two are refused while a score stream is open.  A score with release_state gives up the planes and
 // nothing else.  So the call is legal from set_reads on, whatever was scored since.  Its kernels read the caller's rows as they are, no table.
-static int uvcgpu_region_family_stats_impl(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out) {
-    { int rc1 = report_guard(r, "family_stats", nullptr); if (rc1) return rc1; }
-    if (!ranges || !out) return fail(UVCGPU_EINVAL, "family_stats: ranges and out must not be NULL");
-    const std::string call = "family_stats";
+// The rules of a list of UvcFamilyRange rows (uvcgpu_region_family_stats, _fragment_profile): those of a range list, and prev_end and the flags
+static int family_ranges_check(const uvcgpu_region_t *r, const std::string &call, const UvcFamilyRange *ranges, int64_t n_ranges) {
     { int rc1 = range_count(call, n_ranges, INT32_MAX >> 10); if (rc1) return rc1; }
     for (int64_t k = 0; k < n_ranges; k++) {
         const UvcFamilyRange &q = ranges[k];
@@ -1482,6 +1480,12 @@ static int uvcgpu_region_family_stats_impl(uvcgpu_region_t *r, const UvcFamilyRa
         if (k > 0 && q.prev_end < ranges[k - 1].pos_end) return fail(UVCGPU_EINVAL, name() + " has prev_end " + std::to_string(q.prev_end) + " below the end " + std::to_string(ranges[k - 1].pos_end) + " of range " + std::to_string(k - 1) + ": that range's families would be counted twice");
         if (q.flags & ~(int32_t)UVC_FAMRANGE_CONTINUES) return fail(UVCGPU_EINVAL, name() + " has unknown flag bits (flags " + std::to_string(q.flags) + "; only UVC_FAMRANGE_CONTINUES = 1 is defined)");
     }
+    return 0;
+}
+static int uvcgpu_region_family_stats_impl(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, int64_t *out) {
+    { int rc1 = report_guard(r, "family_stats", nullptr); if (rc1) return rc1; }
+    if (!ranges || !out) return fail(UVCGPU_EINVAL, "family_stats: ranges and out must not be NULL");
+    { int rc1 = family_ranges_check(r, "family_stats", ranges, n_ranges); if (rc1) return rc1; }
     const size_t out_bytes = sizeof(int64_t) * UVC_FAMSTAT_ROW * (size_t)n_ranges;
     if (!r->has_reads) { memset(out, 0, out_bytes); return 0; }   // set_reads with zero reads: no family, nothing to launch
     ReportLayout L;
@@ -1497,6 +1501,42 @@ int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges,
     return guarded("uvcgpu_region_family_stats", [&] { return uvcgpu_region_family_stats_impl(r, ranges, n_ranges, out); });
 }
 const char *uvcgpu_family_stat_name(int32_t id) { return uvc_famstats_name(id); }
+
+// ---- fragment length and end-motif profile of ranges (uvc_fragprofile.hip): [ranges] [TARGET rows, the profile row] [profile copies]
+// [fragment spans] [unit template spans] ----
+// The reads' columns, fragments and units: the legality and the ranges are those of uvcgpu_region_family_stats.
+static int uvcgpu_region_fragment_profile_impl(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, const UvcFragmentProfileRequest *req, int64_t *out_ranges, int64_t *out_profile) {
+    { int rc1 = report_guard(r, "fragment_profile", nullptr, "fragments"); if (rc1) return rc1; }
+    if (!ranges || !req || !out_ranges || !out_profile) return fail(UVCGPU_EINVAL, "fragment_profile: ranges, req, out_ranges and out_profile must not be NULL");
+    if (req->min_mapq < 0 || req->min_mapq > 255) return fail(UVCGPU_EINVAL, "fragment_profile: min_mapq " + std::to_string(req->min_mapq) + " is outside 0..255");
+    if (req->short_lo < 0 || req->short_hi < 0 || req->long_lo < 0 || req->long_hi < 0)
+        return fail(UVCGPU_EINVAL, "fragment_profile: a length bound is negative (short " + std::to_string(req->short_lo) + "-" + std::to_string(req->short_hi) + ", long " + std::to_string(req->long_lo) + "-" + std::to_string(req->long_hi) + ")");
+    if (req->short_lo > req->short_hi) return fail(UVCGPU_EINVAL, "fragment_profile: short_lo " + std::to_string(req->short_lo) + " is above short_hi " + std::to_string(req->short_hi));
+    if (req->long_lo > req->long_hi) return fail(UVCGPU_EINVAL, "fragment_profile: long_lo " + std::to_string(req->long_lo) + " is above long_hi " + std::to_string(req->long_hi));
+    { int rc1 = family_ranges_check(r, "fragment_profile", ranges, n_ranges); if (rc1) return rc1; }
+    const size_t rows_bytes = sizeof(int64_t) * UVC_FRAGPROF_TARGET_ROW * (size_t)n_ranges, prof_bytes = sizeof(int64_t) * UVC_FRAGPROF_ROW, out_bytes = rows_bytes + prof_bytes;
+    if (!r->has_reads) { memset(out_ranges, 0, rows_bytes); memset(out_profile, 0, prof_bytes); return 0; }   // set_reads with zero reads: no fragment, nothing to launch
+    ReportLayout L;
+    const size_t o_ranges = L.take(sizeof(UvcFamilyRange) * (size_t)n_ranges), o_out = L.take(out_bytes), o_parts = L.take(prof_bytes * (size_t)uvc_fragprofile_copies());
+    const size_t o_fspan = L.take(sizeof(UvcFragSpan) * (size_t)std::max(r->R.n_frags, 1)), o_uspan = L.take(sizeof(UvcUnitSpan) * (size_t)std::max(r->R.n_fs, 1));
+    { int rc1 = report_begin(r, L, out_bytes, "fragment profile", ranges, sizeof(UvcFamilyRange) * (size_t)n_ranges); if (rc1) return rc1; }
+    long long *d_out = (long long *)(r->d_report + o_out);
+    const int pi = uvc_prof_begin(&r->prof, "k_fragprofile", r->stream);   // with profiling on, the five kernels as one more entry of uvcgpu_region_kernel_times
+    uvc_launch_fragprofile(&r->R, &r->W, req, (UvcFragSpan *)(r->d_report + o_fspan), (UvcUnitSpan *)(r->d_report + o_uspan), (const UvcFamilyRange *)(r->d_report + o_ranges), (int)n_ranges, d_out,
+                           (long long *)(r->d_report + o_parts), r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    // the rows and the profile come home in one copy and part in the page-locked buffer
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(r->h_report, d_out, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipStreamSynchronize(r->stream));
+    memcpy(out_ranges, r->h_report, rows_bytes);
+    memcpy(out_profile, (const char *)r->h_report + rows_bytes, prof_bytes);
+    return 0;
+}
+int uvcgpu_region_fragment_profile(uvcgpu_region_t *r, const UvcFamilyRange *ranges, int64_t n_ranges, const UvcFragmentProfileRequest *req, int64_t *out_ranges, int64_t *out_profile) {
+    return guarded("uvcgpu_region_fragment_profile", [&] { return uvcgpu_region_fragment_profile_impl(r, ranges, n_ranges, req, out_ranges, out_profile); });
+}
+const char *uvcgpu_fragment_profile_name(int32_t id) { return uvc_fragprofile_name(id); }
 
 // ---- base-quality and cycle profile of the reads over ranges (uvc_readprofile.hip): [table] [D, X: 2 x npos int32] [status: npos bytes]
 // [profile copies: the result row and the shard copies] [scratch ints: the chunk prefix of the alignments and the tile sums of the scans] ----

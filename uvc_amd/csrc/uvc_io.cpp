@@ -1209,7 +1209,7 @@ extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t po
 extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }
 
 // ---------------------------------------------------------------- the report stores ----
-// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out and --msi-out share: a store collects what the tiles
+// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out, --msi-out and --fragment-profile-out share: a store collects what the tiles
 // report under its mutex and writes the whole file at the end.
 // a target as the stores with target lines keep it; a BED line without a name is "."
 struct ReportTarget { std::string chrom, name; int64_t beg, end; };
@@ -1459,6 +1459,76 @@ extern "C" int uvcio_famstats_write(const uvcio_famstats_t *f, const char *path)
     return write_text(path, text);
 }
 extern "C" void uvcio_famstats_close(uvcio_famstats_t *f) { delete f; }
+
+// ---------------------------------------------------------------- the fragment length and end-motif profile ----
+// the layouts are those of uvcgpu_region_fragment_profile (UVC_FRAGPROF_* of uvcgpu.h); the sections and their names: include/uvc_fragprofile.def
+struct FragProfSection { const char *name; int first, words; };
+static const FragProfSection FRAGPROF_SECTIONS[UVC_NFRAGPROF] = {
+#define UVC_FRAGPROF(name, first, words) { #name, first, words },
+#include "uvc_fragprofile.def"
+#undef UVC_FRAGPROF
+};
+struct uvcio_fragprofile {
+    UvcFragmentProfileRequest req;
+    struct Target : ReportTarget { int64_t c[UVC_FRAGPROF_TARGET_ROW]; };
+    std::vector<Target> targets;
+    int64_t prof[UVC_FRAGPROF_ROW];   // the profile rows of all calls, summed
+    std::mutex mu;
+};
+extern "C" int uvcio_fragprofile_open(uvcio_fragprofile_t **out, int32_t min_mapq, int32_t short_lo, int32_t short_hi, int32_t long_lo, int32_t long_hi) {
+    if (!out) return fail(UVCGPU_EINVAL, "fragment profile: bad argument");
+    uvcio_fragprofile *f = new uvcio_fragprofile;
+    f->req = UvcFragmentProfileRequest{ min_mapq, short_lo, short_hi, long_lo, long_hi };
+    memset(f->prof, 0, sizeof(f->prof));
+    *out = f;
+    return 0;
+}
+extern "C" int64_t uvcio_fragprofile_add_target(uvcio_fragprofile_t *f, const char *chrom, int64_t beg, int64_t end, const char *name) {
+    if (!f || !chrom) return fail(UVCGPU_EINVAL, "fragment profile: bad target");
+    std::lock_guard<std::mutex> g(f->mu);
+    f->targets.push_back(uvcio_fragprofile::Target{ report_target(chrom, name, beg, end), {} });
+    return (int64_t)f->targets.size() - 1;
+}
+extern "C" int uvcio_fragprofile_add_piece(uvcio_fragprofile_t *f, int64_t target, const int64_t *row) {
+    if (!f || !row) return fail(UVCGPU_EINVAL, "fragment profile: bad piece");
+    std::lock_guard<std::mutex> g(f->mu);
+    if (target < 0 || target >= (int64_t)f->targets.size()) return fail(UVCGPU_EINVAL, "fragment profile: piece of target " + std::to_string(target) + ", which does not exist");
+    for (int k = 0; k < UVC_FRAGPROF_TARGET_ROW; k++) f->targets[(size_t)target].c[k] += row[k];
+    return 0;
+}
+extern "C" int uvcio_fragprofile_add_profile(uvcio_fragprofile_t *f, const int64_t *profile) {
+    if (!f || !profile) return fail(UVCGPU_EINVAL, "fragment profile: bad profile");
+    std::lock_guard<std::mutex> g(f->mu);
+    for (int k = 0; k < UVC_FRAGPROF_ROW; k++) f->prof[k] += profile[k];
+    return 0;
+}
+extern "C" int uvcio_fragprofile_write(const uvcio_fragprofile_t *f, const char *path) {
+    if (!f || !path || !*path) return fail(UVCGPU_EINVAL, "fragment profile: bad argument");
+    auto range = [](int32_t a, int32_t b) { return std::to_string(a) + "-" + std::to_string(b); };
+    std::string text = "##fragment_profile=1\n##fragment_profile_min_mapq=" + std::to_string(f->req.min_mapq) + "\n##fragment_profile_short=" + range(f->req.short_lo, f->req.short_hi)
+                       + "\n##fragment_profile_long=" + range(f->req.long_lo, f->req.long_hi)
+                       + "\n##summary, lengths and end motifs: every fragment and family that overlaps a target, counted once; target lines: every fragment and family that overlaps the target\n#summary\n";
+    auto is_counter = [](const FragProfSection &s) { return s.words == 1 && s.first < UVC_FRAGPROF_NCOUNTER && strncmp(s.name, "reserved", 8) != 0; };
+    for (const FragProfSection &s : FRAGPROF_SECTIONS) if (is_counter(s)) text += std::string(s.name) + "\t" + std::to_string(f->prof[s.first]) + "\n";
+    text += "#length\tfragments\tfamilies\n";
+    for (int k = 0; k < UVC_FRAGPROF_NLEN; k++)
+        text += std::to_string(k) + (k + 1 == UVC_FRAGPROF_NLEN ? "+" : "") + "\t" + std::to_string(f->prof[UVC_FRAGPROF_LEN_BINS + k]) + "\t" + std::to_string(f->prof[UVC_FRAGPROF_FAMLEN_BINS + k]) + "\n";
+    text += "#end_motif\tcount\n";
+    for (int m = 0; m < UVC_FRAGPROF_NMOTIF; m++) {
+        char motif[5] = { "ACGT"[(m >> 6) & 3], "ACGT"[(m >> 4) & 3], "ACGT"[(m >> 2) & 3], "ACGT"[m & 3], 0 };
+        text += std::string(motif) + "\t" + std::to_string(f->prof[UVC_FRAGPROF_MOTIF_BINS + m]) + "\n";
+    }
+    text += "#chrom\tbeg\tend\tname";
+    for (const FragProfSection &s : FRAGPROF_SECTIONS) if (is_counter(s) && s.first < UVC_FRAGPROF_TARGET_ROW) text += std::string("\t") + s.name;
+    text += "\n";
+    for (const uvcio_fragprofile::Target &t : f->targets) {
+        text += t.chrom + "\t" + std::to_string(t.beg) + "\t" + std::to_string(t.end) + "\t" + t.name;
+        for (const FragProfSection &s : FRAGPROF_SECTIONS) if (is_counter(s) && s.first < UVC_FRAGPROF_TARGET_ROW) text += "\t" + std::to_string(t.c[s.first]);
+        text += "\n";
+    }
+    return write_text(path, text);
+}
+extern "C" void uvcio_fragprofile_close(uvcio_fragprofile_t *f) { delete f; }
 
 // ---------------------------------------------------------------- the callable-region BED ----
 struct uvcio_callable {

@@ -51,6 +51,10 @@ DEV void uvc_range_find(UvcRangeCursor &g, const UvcRangeRow *tab, int n_ranges,
 // uvcgpu_region_family_stats: smallest pos and largest reference end of the alignments of one family-strand unit (scratch the host sizes)
 struct UvcUnitSpan { int lo, hi; };
 static_assert(sizeof(UvcUnitSpan) == 8, "the host sizes the span scratch as 8-byte rows");
+// uvcgpu_region_fragment_profile: smallest pos and largest reference end of the counted forward and of the counted reverse alignments of one
+// fragment (scratch the host sizes; a unit's template span of that call is a UvcUnitSpan)
+struct UvcFragSpan { int loF, hiF, loR, hiR; };
+static_assert(sizeof(UvcFragSpan) == 16, "the host sizes the fragment span scratch as 16-byte rows");
 
 // What the three score launchers share (host-side aggregate; ScorePrep of uvc_host.cpp owns one).  ranges: the device table of
 // uvcgpu_region_score_ranges or NULL; n_compact: the length of the compact axis the ranges make.  force_sites: device copy of
@@ -110,6 +114,13 @@ int64_t uvc_errprofile_scratch_cells(void);
 // n_ranges rows; d_rows: n_ranges rows of UVC_FAMSTAT_ROW words ----
 void uvc_launch_famstats(const RegionDev *R, const int32_t *pos, const int32_t *endpos, const int32_t *fs_of, UvcUnitSpan *d_span, const UvcFamilyRange *d_ranges, int n_ranges, long long *d_rows, hipStream_t s);
 const char *uvc_famstats_name(int id);
+// ---- uvc_fragprofile.hip: W = the per-alignment columns (pos, endpos, frag, flag, mapq are read); d_fspan: n_frags rows and d_uspan: n_fs
+// rows of scratch; d_ranges: the caller's n_ranges rows; d_out: n_ranges rows of UVC_FRAGPROF_TARGET_ROW words and the profile row of
+// UVC_FRAGPROF_ROW words behind them; d_parts: uvc_fragprofile_copies() rows of UVC_FRAGPROF_ROW words ----
+void uvc_launch_fragprofile(const RegionDev *R, const RawReads *W, const UvcFragmentProfileRequest *req, UvcFragSpan *d_fspan, UvcUnitSpan *d_uspan, const UvcFamilyRange *d_ranges, int n_ranges,
+                            long long *d_out, long long *d_parts, hipStream_t s);
+const char *uvc_fragprofile_name(int id);
+int64_t uvc_fragprofile_copies(void);
 // ---- uvc_readprofile.hip: three stages, each one entry of uvcgpu_region_kernel_times.  d_dx / d_x: npos ints each (zero at the start: the depth
 // differences, on return of the status stage the depth; the mismatches); d_status: npos bytes; d_parts: uvc_readprofile_copies() rows of
 // UVC_READPROF_ROW words, zero at the start; d_out: one row; d_scratch: uvc_readprofile_scratch_ints(n_alns, npos) ints.  A handle without

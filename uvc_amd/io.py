@@ -234,6 +234,33 @@ class FamilyStats(_Store):
 
 
 
+class FragmentProfile(_Store):
+    """uvcio_fragprofile_*: the store behind uvc1-mi355x --fragment-profile-out.  Targets are added in report order; add_piece takes one
+    TARGET row of Region.fragment_profile for a target, add_profile sums the profile row of a call (any thread, any order); write() makes
+    the text."""
+
+    def __init__(self, min_mapq=0, short=(100, 150), long=(151, 220)):
+        d = self._bind("fragprofile")
+        d.uvcio_fragprofile_open.restype, d.uvcio_fragprofile_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        d.uvcio_fragprofile_add_piece.restype, d.uvcio_fragprofile_add_piece.argtypes = C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]
+        d.uvcio_fragprofile_add_profile.restype, d.uvcio_fragprofile_add_profile.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        _check(d.uvcio_fragprofile_open(C.byref(self.h), int(min_mapq), int(short[0]), int(short[1]), int(long[0]), int(long[1])))
+
+    def add_piece(self, target, row):
+        import numpy as np
+        row = np.ascontiguousarray(row, dtype=np.int64)
+        if row.shape != (8,):
+            raise ValueError("a piece is one TARGET row of Region.fragment_profile (8 values)")
+        _check(dll().uvcio_fragprofile_add_piece(self.h, int(target), row.ctypes.data))
+
+    def add_profile(self, profile):
+        import numpy as np
+        profile = np.ascontiguousarray(profile, dtype=np.int64)
+        if profile.shape != (2320,):
+            raise ValueError("a profile is the second result of Region.fragment_profile (2320 values)")
+        _check(dll().uvcio_fragprofile_add_profile(self.h, profile.ctypes.data))
+
+
 class ReadProfile(_Store):
     """uvcio_readprofile_*: the store behind uvc1-mi355x --read-profile-out.  add() sums one row of Region.read_profile (any thread, any
     order: rows of disjoint position sets add); write() makes the text."""

@@ -26,6 +26,7 @@ class UvcError(RuntimeError):
 COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
 CALLABLE_BITS = _ffi.CALLABLE_BITS           # the bits of a mask of Region.callable, in bit order (include/uvc_callable.def)
 FAMILY_STATS = _ffi.FAMILY_STATS             # the sections of a row of Region.family_stats, in row order (include/uvc_famstats.def)
+FRAGMENT_PROFILE = _ffi.FRAGMENT_PROFILE     # the sections of the profile row of Region.fragment_profile, in row order (include/uvc_fragprofile.def)
 READ_CLASSES = ["R1_fwd", "R1_rev", "R2_fwd", "R2_rev"]   # the read classes of Region.read_profile, in row order (uvcgpu_read_class_name)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
 CALLABLE_RUN = np.dtype([("range", np.int32), ("pos_beg", np.int32), ("pos_end", np.int32), ("mask", np.int32)])   # UvcCallableRun
@@ -519,6 +520,24 @@ class Region:
         out = np.zeros((len(rows), _ffi.ENUMS["UVC_FAMSTAT_ROW"]), dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), out.ctypes.data))
         return out
+
+    def fragment_profile(self, ranges, min_mapq=0, short=(100, 150), long=(151, 220)):
+        """uvcgpu_region_fragment_profile: template lengths and reference end motifs of the fragments and families of `ranges` (rows as
+        family_stats takes them), reduced on the device from the alignment columns, the fragments and the family units of the region's
+        reads.  -> (rows, profile): rows int64 [n_ranges, UVC_FRAGPROF_TARGET_ROW] (pairs, others, singles, len_sum, short, long, families,
+        a reserved 0, of the objects that overlap the range) and profile int64 [UVC_FRAGPROF_ROW] (the same words, families_both_strands,
+        ends, ends_off_region, ends_no_ref, LEN[1024], FAMLEN[1024], MOTIF[256], of the objects that overlap a range and begin at or behind
+        its prev_end: once per call); FRAGMENT_PROFILE names the sections, uvcgpu.h has the rules.  An alignment counts with
+        mapq >= min_mapq and none of the flags 0x904; `short` / `long` are inclusive bounds of the template length.  Legal where
+        family_stats() is."""
+        fn = self._ranges_fn("region_fragment_profile", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])
+        rows = [(int(q[0]), int(q[1]), int(q[2]) if len(q) > 2 else int(q[0]), int(q[3]) if len(q) > 3 else 0) for q in ranges]
+        arr = (_ffi.UvcFamilyRange * max(len(rows), 1))(*[_ffi.UvcFamilyRange(*q) for q in rows])
+        req = _ffi.UvcFragmentProfileRequest(int(min_mapq), int(short[0]), int(short[1]), int(long[0]), int(long[1]))
+        out = np.zeros((len(rows), _ffi.ENUMS["UVC_FRAGPROF_TARGET_ROW"]), dtype=np.int64)
+        prof = np.zeros(_ffi.ENUMS["UVC_FRAGPROF_ROW"], dtype=np.int64)
+        self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data, prof.ctypes.data))
+        return out, prof
 
     def read_profile(self, ranges, min_mapq=0, min_depth=20, max_alt_permille=50):
         """uvcgpu_region_read_profile: the base-quality, cycle and substitution profile of the region's reads over `ranges` (as Region.coverage
