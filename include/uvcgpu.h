@@ -631,6 +631,54 @@ typedef struct UvcReadProfileRequest { int32_t min_mapq, min_depth, max_alt_perm
 int uvcgpu_region_read_profile(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcReadProfileRequest *req,
                                int64_t *out /* [UVC_READPROF_ROW] */);
 const char *uvcgpu_read_class_name(int32_t c);   /* "R1_fwd" "R1_rev" "R2_fwd" "R2_rev"; NULL for a class outside 0..3 */
+/* ---- the alignments behind listed sites (uvc1-mi355x --site-reads-out) ----
+ * Which alignments of the handle (UvcReadSoA; `read` is an alignment's index in that struct as given) show what at a short list of
+ * positions.  sites[n_sites]: zero-based positions, strictly ascending, every one inside [beg, end + 1).  All integers.
+ *   An alignment is counted iff mapq >= min_mapq and l_qseq > 0; others add nothing anywhere.
+ *   CIGAR walk (that of uvcgpu_region_read_profile): query index q from 0, reference coordinate p from pos; M = X consume both, I S the
+ *   query, D N the reference, H P nothing.
+ *   Observation: a counted alignment has one observation at site s iff an M = X or D op holds s (a site inside an N op or outside the
+ *   aligned span has none).  kind = 0..3 for the read base A C G T at s, 4 for any other base, 5 when s lies inside a D op.  q = the query
+ *   index of that base; for kind 5 max(0, q_at_op - 1), the base in front of the op.  qual = the handle's present quality at q: after
+ *   uvcgpu_region_correct_bq the corrected one.
+ *   Events: an I op of length n at walk coordinate p has anchor p - 1 and adds ins_len += n, ins_q being the query index of the first
+ *   inserted base of the first such op of that anchor; a D op of length n whose first deleted coordinate is p has anchor p - 1 and adds
+ *   del_len += n.  An event attaches to the same alignment's observation at its anchor iff that observation exists: an event whose anchor
+ *   lies in front of pos, inside an N op or is not a listed site is dropped.  Several events of one anchor add their lengths (I P I, 2I3D).
+ *   counts[n_sites][8], over all observations of counted alignments and independent of alt_only: columns 0..5 the observations of each
+ *   kind, column 6 those with ins_len > 0, column 7 those with del_len > 0.
+ *   alt_only = 0: every observation is a row.  alt_only = 1: a row is kept iff kind == 5, ins_len > 0, del_len > 0, or kind <= 3 and the
+ *   reference symbol at the site is A/C/G/T and differs from kind (the region's last position has no reference base).
+ *   Rows ascend by (read, site). */
+typedef struct UvcSiteReadsRequest { int32_t min_mapq; int32_t alt_only; } UvcSiteReadsRequest;
+typedef struct UvcSiteRead {
+    int32_t site;      /* index into `sites` */
+    int32_t read;      /* index of the alignment in the UvcReadSoA */
+    int32_t q;         /* query index of the observation */
+    int32_t obs;       /* kind | qual << 8 */
+    int32_t ins_q;     /* query index of the first inserted base; -1 without an insertion */
+    int32_t ins_len;   /* summed inserted length at this anchor */
+    int32_t del_len;   /* summed deleted length at this anchor */
+    int32_t reserved;  /* 0 */
+} UvcSiteRead;
+enum { UVC_SITEREAD_A = 0, UVC_SITEREAD_C, UVC_SITEREAD_G, UVC_SITEREAD_T, UVC_SITEREAD_N, UVC_SITEREAD_DEL, UVC_SITEREAD_NKIND,
+       UVC_SITEREAD_COL_INS = 6, UVC_SITEREAD_COL_DEL_AFTER = 7, UVC_SITEREAD_NCOL = 8 };
+/* Found, counted and compacted on the device from the read columns, CIGARs and packed base | quality of the handle: the work is split by
+ * (alignment, site) item, the kept rows are ranked by count / scan / write (no atomic decides an order), the counts are integer adds: two
+ * calls return the same bytes.
+ *   Sizes first, as for uvcgpu_region_callable: *n_rows and counts are always written by a call that is not refused; when row_capacity is
+ *   smaller than *n_rows the call returns UVCGPU_ENOMEM and writes nothing to `rows`; a second call with enough room returns the data.
+ *   Legal where uvcgpu_region_family_stats is: from uvcgpu_region_set_reads / _set_reads_device of the current region on, with or without
+ *   accumulate, after any score and while a score stream is open.  Zero reads: zero rows and zero counts.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason (a site by its index): called before set_reads or after a reset;
+ *   NULL sites, req, counts or n_rows; n_sites < 1; a site not strictly above its predecessor; a site outside [beg, end + 1); min_mapq
+ *   outside 0..255; alt_only outside 0..1; row_capacity < 0; NULL rows with row_capacity > 0.
+ *   UVCGPU_EUNSUPPORTED, the one refusal that comes behind a launch (the number is known only on the device): the (alignment, site)
+ *   candidates -- the listed sites inside [pos, endpos) of the counted alignments, summed -- number 2^31 or more; pass the sites in
+ *   several calls.  A refused call, this one included, writes nothing: neither *n_rows nor counts nor rows. */
+int uvcgpu_region_site_reads(uvcgpu_region_t *r, const int32_t *sites, int64_t n_sites, const UvcSiteReadsRequest *req,
+                             int32_t *counts /* [n_sites][8] */, UvcSiteRead *rows, int64_t row_capacity, int64_t *n_rows);
+const char *uvcgpu_site_read_kind_name(int32_t kind);   /* "A" "C" "G" "T" "N" "DEL"; NULL for a kind outside 0..5 */
 /* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
  * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
  * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when

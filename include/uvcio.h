@@ -228,6 +228,30 @@ int uvcio_fragprofile_add_piece(uvcio_fragprofile_t *f, int64_t target, const in
 int uvcio_fragprofile_add_profile(uvcio_fragprofile_t *f, const int64_t *profile /* [2320] */);
 int uvcio_fragprofile_write(const uvcio_fragprofile_t *f, const char *path);
 void uvcio_fragprofile_close(uvcio_fragprofile_t *f);
+/* ---- the reads and families behind listed sites (uvc1-mi355x --site-reads-out) ----
+ * What tiles report with uvcgpu_region_site_reads.  add() takes one call's sites of one contig (zero-based, the `sites` of the call), per
+ * site the reference base (`ref`, n_sites chars; NULL: unknown, written as "."), the counts (NULL: zeros -- a listed site that no tile
+ * reports on) and the rows, with the columns of the call's alignments that the text needs, indexed by UvcSiteRead::read: qname (entries of
+ * alignments without rows may be NULL), flag, mapq, l_qseq, fam_id, fam_strand, frag_id and the bases (one byte per base, 0..3 = ACGT) at
+ * seq_off for the inserted sequences.  It copies what it keeps, under a lock: any thread, any order; the rows of a site come from one call.
+ * write: "##site_reads_min_mapq=", "##site_reads_alt_only=", the three "#S", "#A", "#R" column lines, then per site in (contig id, pos) order
+ *   S contig pos(1-based) ref depth A C G T N DEL INS DEL_after        depth = the six kinds summed; also for a site without observations
+ *   A contig pos allele reads fragments families families_both_strands  one per allele with rows: a kind's name, +<inserted bases> or
+ *     -<deleted length>; a row with an event counts under its event allele(s) and not under its base; fragments and families are the
+ *     distinct (fam_id, fam_strand, frag_id) and fam_id among the allele's rows, families_both_strands those with rows of both fam_strand
+ *     values; kinds first in their order, then the insertions by their bases, then the deletions by length
+ *   R contig pos obs qual cycle class mapq qname flag family strand ins del   one per row, ordered by (family, qname, flag); cycle =
+ *     (flag & 0x10) ? l_qseq - 1 - q : q; class as in the read profile; family = the 1-based rank of the row's family among the families
+ *     with rows at this site, ordered by the smallest (qname, flag) of their rows there (ids of a tile do not show); ins = the inserted
+ *     bases or "."; del = the deleted length or 0.
+ * Integers and names only, tab-separated.  A path that ends in .gz is written block-gzipped. */
+typedef struct uvcio_sitereads uvcio_sitereads_t;
+int uvcio_sitereads_open(uvcio_sitereads_t **out, const char *const *kind_names /* [6] */, const char *const *class_names /* [4] */, int32_t min_mapq, int32_t alt_only);
+int uvcio_sitereads_add(uvcio_sitereads_t *f, int32_t tid, const char *contig, const int32_t *sites, const char *ref, int64_t n_sites, const int32_t *counts /* [n_sites][8] */,
+                        const UvcSiteRead *rows, int64_t n_rows, int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *l_qseq,
+                        const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id, const uint8_t *bases, const int64_t *seq_off);
+int uvcio_sitereads_write(const uvcio_sitereads_t *f, const char *path);
+void uvcio_sitereads_close(uvcio_sitereads_t *f);
 /* ---- the read profile (uvc1-mi355x --read-profile-out) ----
  * The sum of the rows that tiles report with uvcgpu_region_read_profile (5712 int64: Q[4][64][2], CYC[4][256][5], SUB[4][4][4], 16 counters);
  * rows of disjoint position sets add, so add() sums under a lock, from any thread in any order.  write(): "##read_profile_min_mapq=",

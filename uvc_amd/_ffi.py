@@ -99,6 +99,14 @@ class UvcCallableRequest(C.Structure):
     _fields_ = [("min_depth", C.c_int32 * 6), ("max_aDP", C.c_int32)]
 
 
+class UvcSiteReadsRequest(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("alt_only", C.c_int32)]
+
+
+class UvcSiteRead(C.Structure):
+    _fields_ = [("site", C.c_int32), ("read", C.c_int32), ("q", C.c_int32), ("obs", C.c_int32), ("ins_q", C.c_int32), ("ins_len", C.c_int32), ("del_len", C.c_int32), ("reserved", C.c_int32)]
+
+
 class UvcCallableRun(C.Structure):
     _fields_ = [("range", C.c_int32), ("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("mask", C.c_int32)]
 
@@ -194,6 +202,10 @@ assert sum(w for _, _, w in READPROF_SECTIONS) == ENUMS["UVC_READPROF_ROW"] and 
 CALLABLE_BITS = _read_def("uvc_callable.def", "UVC_CALLBIT")
 assert [ENUMS["UVC_CALL_" + n] for n in CALLABLE_BITS] == list(range(ENUMS["UVC_NCALLBIT"]))
 assert CALLABLE_BITS[:len(COVERAGE_MEASURES)] == ["LOW_" + m for m in COVERAGE_MEASURES] and C.sizeof(UvcCallableRequest) == 4 * (ENUMS["UVC_NCOV"] + 1)
+
+# the observation kinds of uvcgpu_region_site_reads in id order (uvcgpu_site_read_kind_name), checked against the header's enums
+SITE_READ_KINDS = ["A", "C", "G", "T", "N", "DEL"]
+assert [ENUMS["UVC_SITEREAD_" + n] for n in SITE_READ_KINDS] == list(range(ENUMS["UVC_SITEREAD_NKIND"])) and C.sizeof(UvcSiteRead) == 4 * ENUMS["UVC_SITEREAD_NCOL"]
 
 # the sections of a microsatellite row in id order (UvcMsiSection): the table of include/uvc_msi.def, checked against the header's enums
 MSI_SECTIONS = _read_def("uvc_msi.def", "UVC_MSI")

@@ -39,12 +39,12 @@
 namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
-// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o), in the order their options are checked: of several faults the first in
+// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o, 4p), in the order their options are checked: of several faults the first in
 // this order is the one reported.
 // A row holds what the command line says of a report in more than one place: parse (the path, "a sub-option was given", the checks behind
 // the loop), split_pair (pair mode writes none) and main (the probe of the path).  A new report is a row here, an Opts store, a
 // *_of_tile and its open / write lines in main.
-enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, N_REPORTS };
+enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, N_REPORTS };
 struct ReportRow {
     const char *out;                 // --X-out PATH
     const char *subs[6];             // the options that only shape this report: each needs --X-out (the list ends with a null)
@@ -66,6 +66,7 @@ const ReportRow REPORTS[N_REPORTS] = {
       "--read-profile-min-mapq, --read-profile-min-depth and --read-profile-max-alt-permille need --read-profile-out: they only gate that report" },
     { "--fragment-profile-out", { "--fragment-profile-window", "--fragment-profile-min-mapq", "--fragment-profile-short", "--fragment-profile-long" }, "--fragment-profile-window", "a target can straddle shards",
       "every tile would be counted that many times", "fragment profile", nullptr },
+    { "--site-reads-out", { "--site-reads-sites", "--site-reads-min-mapq", "--site-reads-alt-only" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its rows that many times", "site reads report", nullptr },
 };
 // the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
 int report_of(const std::string &name, int *sub) {
@@ -104,6 +105,8 @@ struct Opts {
     uvcio_readprofile_t *readprof = nullptr;   // --read-profile-out: the run's row, summed over the tiles by the workers (main)
     UvcFragmentProfileRequest fragprof_req{ 0, 100, 150, 151, 220 };   // --fragment-profile-min-mapq, --fragment-profile-short A-B, --fragment-profile-long A-B
     uvcio_fragprofile_t *fragprof = nullptr;   // --fragment-profile-out: the report's store, filled by the workers (main)
+    std::string sitereads_sites; UvcSiteReadsRequest sitereads_req{ 0, 1 };   // --site-reads-sites, --site-reads-min-mapq, --site-reads-alt-only
+    uvcio_sitereads_t *sitereads = nullptr; uvcio_sites_t *sitereads_list = nullptr;   // --site-reads-out: the report's store, filled by the workers, and the listed sites (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -174,6 +177,10 @@ const OptRow OPTS[] = {
     { "--fragment-profile-min-mapq", O_CLI, false, "0", "with --fragment-profile-out: only alignments of at least this mapping quality are counted (0..255)" },
     { "--fragment-profile-short", O_CLI, false, "100-150", "with --fragment-profile-out: A-B, the template lengths in bp (both inclusive) of a short pair" },
     { "--fragment-profile-long", O_CLI, false, "151-220", "with --fragment-profile-out: A-B, the template lengths in bp (both inclusive) of a long pair" },
+    { "--site-reads-out", O_CLI, false, "", "write the reads and families behind listed sites here (tab-separated; block-gzipped when the name ends in .gz): per site of --site-reads-sites an S line with the depth and the reads showing A C G T N, a deletion, an insertion or a deletion behind the site; per allele an A line with its reads, fragments, UMI families and families seen on both strands; per read an R line with base, corrected quality, cycle, read class, mapping quality, name, flag, family rank and strand -- found on the device among each tile's read bases, with the fragments and families the caller itself formed.  The VCF does not depend on it" },
+    { "--site-reads-sites", O_CLI, false, "", "with --site-reads-out (required): BED or VCF(.gz) of the sites, read as --force-sites reads its file" },
+    { "--site-reads-min-mapq", O_CLI, false, "0", "with --site-reads-out: only alignments of at least this mapping quality are counted (0..255)" },
+    { "--site-reads-alt-only", O_CLI, false, "1", "with --site-reads-out: 1 (or true) writes R and A lines only for reads that differ from the reference at the site -- another base, a deletion, an InDel behind the site; 0 (or false) for every read.  The S lines count every read either way" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -417,6 +424,9 @@ Opts parse(int argc, char **argv) {
             if (a > b) die(n0 + " takes A-B with A at most B, not '" + v + "'");
             if (n0 == "--fragment-profile-short") { o.fragprof_req.short_lo = (int32_t)a; o.fragprof_req.short_hi = (int32_t)b; } else { o.fragprof_req.long_lo = (int32_t)a; o.fragprof_req.long_hi = (int32_t)b; }
         }
+        else if (n0 == "--site-reads-sites") { o.sitereads_sites = val(); if (o.sitereads_sites.empty()) die("--site-reads-sites needs a path"); }
+        else if (n0 == "--site-reads-min-mapq") o.sitereads_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
+        else if (n0 == "--site-reads-alt-only") o.sitereads_req.alt_only = (int32_t)whole_number(n0, val(), 0, 1, "0 or 1 (false or true)", N_STRTOD_BOOL);
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -467,6 +477,7 @@ Opts parse(int argc, char **argv) {
         }
         refuse_report_runs(o, R.out, R.why_no_shard, R.why_no_repeat);
         if (R.window) refuse_report_windows(o, R.out, R.window, o.report[r].window);
+        if (r == R_SITEREADS && o.sitereads_sites.empty()) die("--site-reads-out needs --site-reads-sites FILE: the report is about the sites of that file");
     }
     if (o.merge > 0) {   // before any file or device
         if (o.bed.empty() && o.bed_in.empty()) die("--merge-regions needs a BED file (-R / --bed-in-fname): it merges BED lines");
@@ -515,6 +526,7 @@ struct Worker {
     std::vector<UvcFamilyRange> fam_ranges;   // --family-stats-out, --fragment-profile-out: their pieces carry more than a range
     std::vector<int64_t> cov_rows, fam_rows, rp_row, frag_rows;   // --coverage-out, --family-stats-out, --read-profile-out, --fragment-profile-out: what the device call fills
     std::vector<UvcCallableRun> call_runs;   // --callable-out: the runs, as many as the last tiles had
+    std::vector<int32_t> sr_sites, sr_counts; std::vector<UvcSiteRead> sr_rows; std::vector<const char *> sr_qnames;   // --site-reads-out: the sites a tile owns, their counts and rows, the names of the rows' alignments
     std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the loci, as many as the last tiles had
 };
 
@@ -640,6 +652,26 @@ void fragment_profile_of_tile(Worker &w, const Opts &o, const std::vector<FamPie
         if (uvcio_fragprofile_add_piece(o.fragprof, w.targets[q], &w.frag_rows[q * (size_t)UVC_FRAGPROF_TARGET_ROW])) die(uvcio_last_error());
     if (uvcio_fragprofile_add_profile(o.fragprof, prof)) die(uvcio_last_error());
 }
+// --site-reads-out: the listed sites inside the stretches one tile owns -- the list coverage_of_tile reports on, so every site has one owner
+// however the tiles are cut -- by one uvcgpu_region_site_reads behind correct_bq (sizes first: the buffer of the last tiles, grown where a
+// tile has more rows), handed to the store with the columns of the kept alignments (alns3 order: a row's `read` indexes them) and the names
+// of the batch.  A tile without an owned site makes no call.  A listed site is the VCF POS of uvcio_sites_*: the zero-based position + 1.
+void site_reads_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const Tile &t, const UvcBamBatch &b, int64_t k) {
+    w.sr_sites.clear();
+    for (const auto &q : own) {
+        const int32_t *s = nullptr; int64_t n = 0;
+        if (q.second > q.first && uvcio_sites_fetch(o.sitereads_list, t.tid, q.first + 1, q.second + 1, &s, &n)) die(uvcio_last_error());
+        for (int64_t i = 0; i < n; i++) w.sr_sites.push_back(s[i] - 1);
+    }
+    if (w.sr_sites.empty()) return;
+    const int64_t n_sites = (int64_t)w.sr_sites.size();
+    w.sr_counts.resize((size_t)n_sites * UVC_SITEREAD_NCOL);
+    const int64_t n = sizes_first(w.sr_rows, 1, [&](UvcSiteRead *rows, int64_t cap, int64_t *n_rows) { return uvcgpu_region_site_reads(w.reg, w.sr_sites.data(), n_sites, &o.sitereads_req, w.sr_counts.data(), rows, cap, n_rows); });
+    w.sr_qnames.assign((size_t)k, nullptr);
+    for (int64_t i = 0; i < n; i++) { const int32_t a = w.sr_rows[(size_t)i].read; w.sr_qnames[(size_t)a] = b.qnames + b.qname_off[w.order[(size_t)a]]; }
+    if (uvcio_sitereads_add(o.sitereads, t.tid, t.chrom.c_str(), w.sr_sites.data(), nullptr, n_sites, w.sr_counts.data(), w.sr_rows.data(), n, k, w.sr_qnames.data(), w.flag.data(), w.mapq.data(), w.lq.data(),
+                            w.fam.data(), w.fstrand.data(), w.frag.data(), b.bases, w.soff.data())) die(uvcio_last_error());
+}
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // The record text of one call behind `lines`: write(dst, room, &len) into a buffer as large as the last tiles needed (+ slack); a second
 // call only when the text did not fit
@@ -732,11 +764,11 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     w.t_reads += now() - t0; t0 = now();
     if (o.fam && fam_pieces) family_stats_of_tile(w, o, fam_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --family-stats-out: the units of set_reads, before anything else
     if (o.fragprof && frag_pieces) fragment_profile_of_tile(w, o, frag_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --fragment-profile-out: the fragments and units of set_reads
-    // --coverage-out, --error-profile-out, --callable-out, --read-profile-out: the positions this tile owns -- the [first, last_excl) that scoring and
+    // --coverage-out, --error-profile-out, --callable-out, --read-profile-out, --site-reads-out: the positions this tile owns -- the [first, last_excl) that scoring and
     // uvcio_sites_fetch go by, without the end point t.end itself, which lies outside every target the tile was cut from (and which two regions of
     // the reference's cuts share).  The list depends on scored() alone: made here, in front of accumulate, for the report of the reads as well.
     std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
-    if (o.cov || o.errprof || o.callable || o.readprof || o.msi) {
+    if (o.cov || o.errprof || o.callable || o.readprof || o.msi || o.sitereads) {
         auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !(o.callable || o.msi) ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
         for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) {   // (n_merged = 0: t0_ alone)
             const Tile &l = (&t0_)[q];
@@ -749,6 +781,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (o.errprof) errprofile_of_tile(w, o, own);
     if (o.callable) callable_of_tile(w, o, own, call_target_of);
     if (o.msi) msi_of_tile(w, o, own, call_target_of, w.ref, ext_beg);
+    if (o.sitereads) site_reads_of_tile(w, o, own, t, b, k);   // the corrected qualities: behind correct_bq
     UvcScoreRequest rq; memset(&rq, 0, sizeof(rq));
     rq.pos_beg = (int32_t)first; rq.pos_end = (int32_t)last_excl; rq.all_out = (P.should_output_all != 0);
     rq.is_amplicon = (o.assay_type == 0 ? (go.n_amplicon * 2 > k) : (o.assay_type == 2));   // inferred_assay_type, main.cpp:510-511
@@ -1391,6 +1424,25 @@ int main(int argc, char **argv) {
     if (wanted(R_FAMSTATS) && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
     std::vector<CovSpan> frag_spans((size_t)nref);
     if (wanted(R_FRAGPROF) && uvcio_fragprofile_open(&o.fragprof, o.fragprof_req.min_mapq, o.fragprof_req.short_lo, o.fragprof_req.short_hi, o.fragprof_req.long_lo, o.fragprof_req.long_hi)) die(uvcio_last_error());
+    if (wanted(R_SITEREADS)) {   // the listed sites, each with its reference base: a site that no tile owns keeps its S line of zeros
+        uvcio_sites_t *list = nullptr; uvcio_fasta_t *fa = nullptr;
+        if (uvcio_sites_open(&list, o.sitereads_sites.c_str(), G.cnames.data(), nref)) die("--site-reads-sites: " + std::string(uvcio_last_error()));
+        fprintf(stderr, "uvc1-mi355x: %lld sites from %s\n", (long long)uvcio_sites_count(list), o.sitereads_sites.c_str());
+        if (uvcio_sitereads_open(&o.sitereads, names_of(uvcgpu_site_read_kind_name, UVC_SITEREAD_NKIND).data(), names_of(uvcgpu_read_class_name, UVC_READPROF_NCLASS).data(), o.sitereads_req.min_mapq, o.sitereads_req.alt_only)
+            || uvcio_fasta_open(&fa, o.fasta.c_str())) die(uvcio_last_error());
+        for (int32_t tid = 0; tid < nref; tid++) {
+            const int32_t *s = nullptr; int64_t n = 0;
+            if (uvcio_sites_fetch(list, tid, 0, (int64_t)INT32_MAX + 1, &s, &n)) die(uvcio_last_error());
+            std::vector<int32_t> pos((size_t)n); std::string ref((size_t)n, '.');
+            for (int64_t i = 0; i < n; i++) {
+                pos[(size_t)i] = s[i] - 1;
+                if (s[i] <= G.lens[(size_t)tid] && uvcio_fasta_fetch(fa, G.cnames[(size_t)tid], s[i] - 1, s[i], &ref[(size_t)i])) die(uvcio_last_error());
+            }
+            if (n > 0 && uvcio_sitereads_add(o.sitereads, tid, G.cnames[(size_t)tid], pos.data(), ref.data(), n, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) die(uvcio_last_error());
+        }
+        uvcio_fasta_close(fa);
+        o.sitereads_list = list;
+    }
     std::vector<Tile> tiles = plan_tiles(o, bam0, G, &batch_of, &cov_spans, &fam_spans, &frag_spans);
     std::vector<std::vector<FamPiece>> fam_plan, frag_plan;
     if (o.fam) fam_plan = plan_family_pieces(REPORTS[R_FAMSTATS].out, o.report[R_FAMSTATS].window, &Tile::fam_target, tiles, fam_spans, nref);
@@ -1506,6 +1558,7 @@ int main(int argc, char **argv) {
     if (o.errprof) { finish(R_ERRPROF, uvcio_errprofile_write(o.errprof, path(R_ERRPROF))); uvcio_errprofile_close(o.errprof); }
     if (o.readprof) { finish(R_READPROF, uvcio_readprofile_write(o.readprof, path(R_READPROF))); uvcio_readprofile_close(o.readprof); }
     if (o.fragprof) { finish(R_FRAGPROF, uvcio_fragprofile_write(o.fragprof, path(R_FRAGPROF))); uvcio_fragprofile_close(o.fragprof); }
+    if (o.sitereads) { finish(R_SITEREADS, uvcio_sitereads_write(o.sitereads, path(R_SITEREADS))); uvcio_sitereads_close(o.sitereads); uvcio_sites_close(o.sitereads_list); }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

@@ -118,7 +118,7 @@ struct uvcgpu_region {
     Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
     Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
-    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1341,8 +1341,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi and _fragment_profile ----
-// What the seven share.  Each is synchronous: a checked list of sorted, disjoint ranges goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile and _site_reads ----
+// What the eight share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1578,6 +1578,71 @@ int uvcgpu_region_read_profile(uvcgpu_region_t *r, const UvcCoverageRange *range
     return guarded("uvcgpu_region_read_profile", [&] { return uvcgpu_region_read_profile_impl(r, ranges, n_ranges, req, out); });
 }
 const char *uvcgpu_read_class_name(int32_t c) { return uvc_readprofile_class_name(c); }
+
+// ---- the alignments behind listed sites (uvc_sitereads.hip): [sites] [counts, n_sites x 8 ints] [scratch ints] [rows, `room` of them] ----
+// The read columns, CIGARs and packed base | quality belong to the reads of the handle: the legality is that of uvcgpu_region_family_stats.
+// Sizes first, in one pass where the buffer allows (as uvcgpu_region_msi): the count runs, the host reads the number of items, the number
+// of kept rows and the counts in one wait, and only a call with enough room launches the write and copies 32 bytes per row.  A call whose
+// caller has room the device buffer lacks lays the buffer out for that number of rows and counts once more (the buffer keeps its size).
+static int uvcgpu_region_site_reads_impl(uvcgpu_region_t *r, const int32_t *sites, int64_t n_sites, const UvcSiteReadsRequest *req, int32_t *counts, UvcSiteRead *rows, int64_t row_capacity, int64_t *n_rows) {
+    { int rc1 = report_guard(r, "site_reads", nullptr, "reads"); if (rc1) return rc1; }
+    if (!sites || !req || !counts || !n_rows) return fail(UVCGPU_EINVAL, "site_reads: sites, req, counts and n_rows must not be NULL");
+    if (n_sites < 1) return fail(UVCGPU_EINVAL, "site_reads: n_sites " + std::to_string(n_sites) + " must be at least 1");
+    if (req->min_mapq < 0 || req->min_mapq > 255) return fail(UVCGPU_EINVAL, "site_reads: min_mapq " + std::to_string(req->min_mapq) + " is outside 0..255");
+    if (req->alt_only < 0 || req->alt_only > 1) return fail(UVCGPU_EINVAL, "site_reads: alt_only " + std::to_string(req->alt_only) + " is outside 0..1");
+    if (row_capacity < 0) return fail(UVCGPU_EINVAL, "site_reads: row_capacity " + std::to_string(row_capacity) + " is negative");
+    if (!rows && row_capacity > 0) return fail(UVCGPU_EINVAL, "site_reads: rows is NULL with row_capacity " + std::to_string(row_capacity));
+    for (int64_t k = 0; k < n_sites; k++) {
+        if (sites[k] < r->beg || sites[k] >= r->end) return fail(UVCGPU_EINVAL, "site_reads: site " + std::to_string(k) + " (" + std::to_string(sites[k]) + ") is outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+        if (k > 0 && sites[k] <= sites[k - 1]) return fail(UVCGPU_EINVAL, "site_reads: site " + std::to_string(k) + " (" + std::to_string(sites[k]) + ") is not above site " + std::to_string(k - 1) + " (" + std::to_string(sites[k - 1]) + "): sites ascend strictly");
+    }
+    const size_t counts_bytes = sizeof(int32_t) * UVC_SITEREAD_NCOL * (size_t)n_sites;
+    if (!r->has_reads) { memset(counts, 0, counts_bytes); *n_rows = 0; return 0; }   // set_reads with zero reads: nothing to launch
+    const int64_t n_alns = r->R.n_alns, scratch_ints = uvc_sitereads_scratch_ints(n_alns, n_sites), rows_at = uvc_sitereads_rows_at(n_alns, n_sites);
+    ReportLayout L0;
+    const size_t o_sites = L0.take(sizeof(int32_t) * (size_t)n_sites), o_counts = L0.take(counts_bytes), o_scratch = L0.take(sizeof(int32_t) * (size_t)scratch_ints);
+    const size_t head_bytes = 64;   // the page-locked result: the number of items and of rows, then the counts
+    int64_t room = 0;   // the rows the buffer as it is has room for behind the fixed pieces, never more than the caller's
+    if (row_capacity > 0 && r->d_report.cap > L0.bytes + 128) room = std::min(row_capacity, (int64_t)((r->d_report.cap - L0.bytes - 128) / sizeof(UvcSiteRead)));
+    int32_t n = 0;
+    int32_t *d_scratch = nullptr; const int32_t *d_sites = nullptr; UvcSiteRead *d_rows = nullptr;
+    for (;;) {
+        ReportLayout L = L0;
+        const size_t o_rows = L.take(sizeof(UvcSiteRead) * (size_t)room);
+        { int rc1 = report_begin(r, L, head_bytes + counts_bytes, "site reads", sites, sizeof(int32_t) * (size_t)n_sites); if (rc1) return rc1; }
+        d_sites = (const int32_t *)(r->d_report + o_sites); d_scratch = (int32_t *)(r->d_report + o_scratch); d_rows = (UvcSiteRead *)(r->d_report + o_rows);
+        int32_t *d_counts = (int32_t *)(r->d_report + o_counts);
+        HIP_OK(hipMemsetAsync(d_counts, 0, o_scratch - o_counts + 64, r->stream));   // the counts and the number of items at the head of the scratch
+        // with profiling on, two more entries of uvcgpu_region_kernel_times (accumulate starts the list anew); a call that counts twice adds two
+        const int pi = uvc_prof_begin(&r->prof, "k_sitereads_count", r->stream);
+        uvc_launch_sitereads_count(&r->R, &r->W, d_sites, (int)n_sites, req, d_counts, d_scratch, r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
+        HIP_OK(hipGetLastError());
+        char *h = r->h_report;
+        HIP_OK(hipMemcpyAsync(h, d_scratch, sizeof(int64_t), hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipMemcpyAsync(h + 8, d_scratch + rows_at, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipMemcpyAsync(h + head_bytes, d_counts, counts_bytes, hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipStreamSynchronize(r->stream));
+        int64_t n_items; memcpy(&n_items, h, sizeof n_items); memcpy(&n, h + 8, sizeof n);
+        if (n_items > INT32_MAX) return fail(UVCGPU_EUNSUPPORTED, "site_reads: " + std::to_string(n_items) + " (alignment, site) candidates, more than one call takes (2^31 - 1): pass the sites in several calls");
+        if (n <= room || n > row_capacity) break;
+        room = n;
+    }
+    *n_rows = n;
+    memcpy(counts, (const char *)r->h_report + head_bytes, counts_bytes);
+    if (n > row_capacity) return fail(UVCGPU_ENOMEM, "site_reads: " + std::to_string(n) + " rows, room for " + std::to_string(row_capacity));
+    if (n == 0) return 0;
+    const size_t out_bytes = sizeof(UvcSiteRead) * (size_t)n;
+    { int rc1 = report_buffers(r, 0, out_bytes, "site reads"); if (rc1) return rc1; }
+    const int pi = uvc_prof_begin(&r->prof, "k_sitereads_write", r->stream);
+    uvc_launch_sitereads_write(&r->R, &r->W, d_sites, (int)n_sites, req, d_scratch, d_rows, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    return report_result(r, d_rows, rows, out_bytes, false);
+}
+int uvcgpu_region_site_reads(uvcgpu_region_t *r, const int32_t *sites, int64_t n_sites, const UvcSiteReadsRequest *req, int32_t *counts, UvcSiteRead *rows, int64_t row_capacity, int64_t *n_rows) {
+    return guarded("uvcgpu_region_site_reads", [&] { return uvcgpu_region_site_reads_impl(r, sites, n_sites, req, counts, rows, row_capacity, n_rows); });
+}
+const char *uvcgpu_site_read_kind_name(int32_t kind) { return uvc_sitereads_kind_name(kind); }
 
 // ---- callable-region intervals of ranges (uvc_callable.hip): [table] [block counts] [mask bytes] [runs, one per position at worst] ----
 // Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit

@@ -19,6 +19,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -1209,7 +1210,7 @@ extern "C" int uvcio_sites_fetch(const uvcio_sites_t *v, int32_t tid, int64_t po
 extern "C" void uvcio_sites_close(uvcio_sites_t *v) { delete v; }
 
 // ---------------------------------------------------------------- the report stores ----
-// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out, --msi-out and --fragment-profile-out share: a store collects what the tiles
+// What the stores of --coverage-out, --error-profile-out, --family-stats-out, --callable-out, --read-profile-out, --msi-out, --fragment-profile-out and --site-reads-out share: a store collects what the tiles
 // report under its mutex and writes the whole file at the end.
 // a target as the stores with target lines keep it; a BED line without a name is "."
 struct ReportTarget { std::string chrom, name; int64_t beg, end; };
@@ -1529,6 +1530,117 @@ extern "C" int uvcio_fragprofile_write(const uvcio_fragprofile_t *f, const char 
     return write_text(path, text);
 }
 extern "C" void uvcio_fragprofile_close(uvcio_fragprofile_t *f) { delete f; }
+
+// ---------------------------------------------------------------- the reads and families behind listed sites ----
+// the rows and counts are those of uvcgpu_region_site_reads (UvcSiteRead, UVC_SITEREAD_* of uvcgpu.h).  The family and fragment ids of a row are
+// local to its call: the store keeps them with the call's serial number, compares them for equality alone and writes none of them.
+struct uvcio_sitereads {
+    UvcSiteReadsRequest req;
+    std::string kinds[UVC_SITEREAD_NKIND], classes[4];
+    struct Row { int32_t kind, qual, cycle, cls, mapq, flag, strand, frag, del_len; int64_t fam; std::string qname, ins; };   // fam: call << 32 | the 32 bits of fam_id
+    struct Site { std::string contig; char ref = '.'; int64_t c[UVC_SITEREAD_NCOL] = {}; std::vector<Row> rows; };
+    std::map<std::pair<int32_t, int32_t>, Site> sites;   // by (tid, zero-based position)
+    int64_t n_calls = 0;
+    std::mutex mu;
+};
+extern "C" int uvcio_sitereads_open(uvcio_sitereads_t **out, const char *const *kind_names, const char *const *class_names, int32_t min_mapq, int32_t alt_only) {
+    if (!out || !kind_names || !class_names) return fail(UVCGPU_EINVAL, "site reads: bad argument");
+    uvcio_sitereads *f = new uvcio_sitereads;
+    f->req = UvcSiteReadsRequest{ min_mapq, alt_only };
+    for (int k = 0; k < UVC_SITEREAD_NKIND; k++) f->kinds[k] = kind_names[k] ? kind_names[k] : "";
+    for (int c = 0; c < 4; c++) f->classes[c] = class_names[c] ? class_names[c] : "";
+    *out = f;
+    return 0;
+}
+extern "C" int uvcio_sitereads_add(uvcio_sitereads_t *f, int32_t tid, const char *contig, const int32_t *sites, const char *ref, int64_t n_sites, const int32_t *counts, const UvcSiteRead *rows, int64_t n_rows,
+                                   int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *l_qseq, const int32_t *fam_id, const uint8_t *fam_strand,
+                                   const int32_t *frag_id, const uint8_t *bases, const int64_t *seq_off) {
+    if (!f || !contig || n_sites < 0 || (n_sites > 0 && !sites) || n_rows < 0) return fail(UVCGPU_EINVAL, "site reads: bad argument");
+    if (n_rows > 0 && (!rows || !counts || !qnames || !flag || !mapq || !l_qseq || !fam_id || !fam_strand || !frag_id || !bases || !seq_off)) return fail(UVCGPU_EINVAL, "site reads: rows without the columns of their alignments");
+    // what the rows keep is made outside the lock
+    std::vector<std::pair<int32_t, uvcio_sitereads::Row>> made((size_t)n_rows);
+    for (int64_t k = 0; k < n_rows; k++) {
+        const UvcSiteRead &r = rows[k];
+        if (r.site < 0 || r.site >= n_sites || r.read < 0 || r.read >= n_alns || !qnames[r.read]) return fail(UVCGPU_EINVAL, "site reads: row " + std::to_string(k) + " names site " + std::to_string(r.site) + " and alignment " + std::to_string(r.read) + ", which the call does not hold");
+        const int a = r.read, L = l_qseq[a], fl = flag[a];
+        uvcio_sitereads::Row w;
+        w.kind = r.obs & 0xFF; w.qual = r.obs >> 8; w.cycle = (fl & 0x10) ? L - 1 - r.q : r.q; w.cls = 2 * ((fl & 0x80) != 0) + ((fl & 0x10) != 0);
+        w.mapq = mapq[a]; w.flag = fl; w.fam = (int64_t)(uint32_t)fam_id[a]; w.strand = fam_strand[a]; w.frag = frag_id[a]; w.del_len = r.del_len; w.qname = qnames[a];
+        if (w.kind < 0 || w.kind >= UVC_SITEREAD_NKIND) return fail(UVCGPU_EINVAL, "site reads: row " + std::to_string(k) + " has kind " + std::to_string(w.kind));
+        for (int32_t j = 0; j < r.ins_len && r.ins_q >= 0 && r.ins_q + j < L; j++) { const uint8_t b = bases[seq_off[a] + r.ins_q + j]; w.ins += (b < 4 ? "ACGT"[b] : 'N'); }
+        made[(size_t)k] = std::make_pair(r.site, std::move(w));
+    }
+    std::lock_guard<std::mutex> g(f->mu);
+    for (int64_t s = 0; s < n_sites; s++) {
+        uvcio_sitereads::Site &site = f->sites[std::make_pair(tid, sites[s])];
+        if (site.contig.empty()) site.contig = contig;
+        if (ref && ref[s]) site.ref = (char)toupper((unsigned char)ref[s]);
+        if (counts) for (int c = 0; c < UVC_SITEREAD_NCOL; c++) site.c[c] += counts[s * UVC_SITEREAD_NCOL + c];
+    }
+    const int64_t call = f->n_calls++;
+    for (auto &m : made) { m.second.fam |= call << 32; f->sites[std::make_pair(tid, sites[m.first])].rows.push_back(std::move(m.second)); }
+    return 0;
+}
+extern "C" int uvcio_sitereads_write(const uvcio_sitereads_t *f, const char *path) {
+    if (!f || !path || !*path) return fail(UVCGPU_EINVAL, "site reads: bad argument");
+    typedef uvcio_sitereads::Row Row;
+    std::string text = "##site_reads_min_mapq=" + std::to_string(f->req.min_mapq) + "\n##site_reads_alt_only=" + std::to_string(f->req.alt_only)
+                       + "\n#S\tcontig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tDEL\tINS\tDEL_after\n#A\tcontig\tpos\tallele\treads\tfragments\tfamilies\tfamilies_both_strands\n"
+                         "#R\tcontig\tpos\tobs\tqual\tcycle\tclass\tmapq\tqname\tflag\tfamily\tstrand\tins\tdel\n";
+    for (const auto &kv : f->sites) {   // (the map is ordered by (tid, pos))
+        const uvcio_sitereads::Site &site = kv.second;
+        const std::string at = "\t" + site.contig + "\t" + std::to_string((int64_t)kv.first.second + 1);
+        int64_t depth = 0;
+        for (int c = 0; c < UVC_SITEREAD_NKIND; c++) depth += site.c[c];
+        text += "S" + at + "\t" + site.ref + "\t" + std::to_string(depth);
+        for (int c = 0; c < UVC_SITEREAD_NCOL; c++) text += "\t" + std::to_string(site.c[c]);
+        text += "\n";
+        if (site.rows.empty()) continue;
+        // a family's rank: by the smallest (qname, flag) of its rows at this site (families of two calls that share it share the rank)
+        std::map<int64_t, std::pair<std::string, int32_t>> least;
+        for (const Row &r : site.rows) {
+            const auto key = std::make_pair(r.qname, r.flag);
+            auto it = least.find(r.fam);
+            if (it == least.end()) least[r.fam] = key; else if (key < it->second) it->second = key;
+        }
+        std::vector<std::pair<std::string, int32_t>> keys;
+        for (const auto &l : least) keys.push_back(l.second);
+        std::sort(keys.begin(), keys.end());
+        keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        std::map<int64_t, int64_t> rank;
+        for (const auto &l : least) rank[l.first] = (std::lower_bound(keys.begin(), keys.end(), l.second) - keys.begin()) + 1;
+        // the alleles: the kinds in their order, the insertions by their bases, the deletions by their length; a row with an event counts
+        // under its event alleles and not under its base
+        std::map<std::pair<int, std::string>, std::vector<const Row *>> alleles;
+        auto del_key = [](int32_t n) { std::string s = std::to_string(n); return std::string(12 - std::min<size_t>(12, s.size()), '0') + s; };   // (numeric order)
+        for (const Row &r : site.rows) {
+            if (!r.ins.empty()) alleles[std::make_pair(UVC_SITEREAD_NKIND, r.ins)].push_back(&r);
+            if (r.del_len > 0) alleles[std::make_pair(UVC_SITEREAD_NKIND + 1, del_key(r.del_len))].push_back(&r);
+            if (r.ins.empty() && r.del_len <= 0) alleles[std::make_pair(r.kind, std::string())].push_back(&r);
+        }
+        for (const auto &al : alleles) {
+            const int cls = al.first.first;
+            const std::string name = cls < UVC_SITEREAD_NKIND ? f->kinds[cls] : cls == UVC_SITEREAD_NKIND ? "+" + al.first.second : "-" + std::to_string(al.second[0]->del_len);
+            std::set<std::tuple<int64_t, int32_t, int32_t>> frags;
+            std::map<int64_t, int> strands;   // family -> bit 0 / 1: a row of fam_strand 0 / 1
+            for (const Row *r : al.second) { frags.insert(std::make_tuple(r->fam, r->strand, r->frag)); strands[r->fam] |= 1 << (r->strand & 1); }
+            int64_t both = 0;
+            for (const auto &s : strands) both += (s.second == 3);
+            text += "A" + at + "\t" + name + "\t" + std::to_string(al.second.size()) + "\t" + std::to_string(frags.size()) + "\t" + std::to_string(strands.size()) + "\t" + std::to_string(both) + "\n";
+        }
+        std::vector<const Row *> order;
+        for (const Row &r : site.rows) order.push_back(&r);
+        std::sort(order.begin(), order.end(), [&](const Row *a, const Row *b) {
+            const int64_t ra = rank[a->fam], rb = rank[b->fam];
+            return std::tie(ra, a->qname, a->flag, a->cycle) < std::tie(rb, b->qname, b->flag, b->cycle);
+        });
+        for (const Row *r : order)
+            text += "R" + at + "\t" + f->kinds[r->kind] + "\t" + std::to_string(r->qual) + "\t" + std::to_string(r->cycle) + "\t" + f->classes[r->cls] + "\t" + std::to_string(r->mapq) + "\t" + r->qname + "\t"
+                    + std::to_string(r->flag) + "\t" + std::to_string(rank[r->fam]) + "\t" + std::to_string(r->strand) + "\t" + (r->ins.empty() ? std::string(".") : r->ins) + "\t" + std::to_string(r->del_len) + "\n";
+    }
+    return write_text(path, text);
+}
+extern "C" void uvcio_sitereads_close(uvcio_sitereads_t *f) { delete f; }
 
 // ---------------------------------------------------------------- the callable-region BED ----
 struct uvcio_callable {

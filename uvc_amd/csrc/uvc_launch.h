@@ -132,6 +132,15 @@ void uvc_launch_readprofile_bin(const RegionDev *R, const RawReads *W, int64_t n
 const char *uvc_readprofile_class_name(int c);
 int64_t uvc_readprofile_copies(void);
 int64_t uvc_readprofile_scratch_ints(int64_t n_alns, int64_t npos);
+// ---- uvc_sitereads.hip: two stages, each one entry of uvcgpu_region_kernel_times.  d_sites: the caller's n_sites positions; d_counts:
+// n_sites rows of UVC_SITEREAD_NCOL ints, zero at the start; d_scratch: uvc_sitereads_scratch_ints(n_alns, n_sites) ints, the first two zero
+// at the start: behind the count they hold the 64-bit number of (alignment, site) items, and entry uvc_sitereads_rows_at the number of kept
+// rows.  The write follows a count with the same arguments; d_rows: room for that many rows ----
+void uvc_launch_sitereads_count(const RegionDev *R, const RawReads *W, const int32_t *d_sites, int n_sites, const UvcSiteReadsRequest *req, int32_t *d_counts, int32_t *d_scratch, hipStream_t s);
+void uvc_launch_sitereads_write(const RegionDev *R, const RawReads *W, const int32_t *d_sites, int n_sites, const UvcSiteReadsRequest *req, int32_t *d_scratch, UvcSiteRead *d_rows, hipStream_t s);
+int64_t uvc_sitereads_scratch_ints(int64_t n_alns, int64_t n_sites);
+int64_t uvc_sitereads_rows_at(int64_t n_alns, int64_t n_sites);
+const char *uvc_sitereads_kind_name(int k);
 // ---- uvc_callable.hip: d_tab = n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one the
 // number of runs once the count has run; d_runs: room for that many runs.  The emit follows a count with the same arguments ----
 void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s);

@@ -283,6 +283,51 @@ class ReadProfile(_Store):
 
 
 
+class SiteReads(_Store):
+    """uvcio_sitereads_*: the store behind uvc1-mi355x --site-reads-out.  add() takes the sites (zero-based), counts and rows of one
+    Region.site_reads with the columns of that call's alignments (any thread, any order; the rows of a site come from one call); a call
+    without counts lists sites that nobody reported on.  write() sorts by (contig id, position) and makes the S / A / R lines."""
+    add_target = None   # the sites are the targets
+
+    def __init__(self, kinds, classes, min_mapq=0, alt_only=True):
+        d = self._bind("sitereads")
+        d.uvcio_sitereads_open.restype, d.uvcio_sitereads_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.c_int32]
+        d.uvcio_sitereads_add.restype, d.uvcio_sitereads_add.argtypes = C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                                                  C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if len(kinds) != 6 or len(classes) != 4:
+            raise ValueError("the kinds are six (region.SITE_READ_KINDS), the read classes four (region.READ_CLASSES)")
+        _check(d.uvcio_sitereads_open(C.byref(self.h), (C.c_char_p * 6)(*[k.encode() for k in kinds]), (C.c_char_p * 4)(*[c.encode() for c in classes]), int(min_mapq), int(alt_only)))
+
+    def add(self, tid, contig, sites, ref=None, counts=None, rows=None, reads=None, qnames=None):
+        """sites: the zero-based positions of the call; ref: their reference bases as one string, or None; counts, rows: what
+        Region.site_reads returned, or None for sites without a report; reads: the reads the region was given (flag, mapq, l_qseq,
+        fam_id, fam_strand, frag_id, bases, seq_off); qnames: one name per alignment."""
+        import numpy as np
+        sites = np.ascontiguousarray(sites, dtype=np.int32)
+        if ref is not None and len(ref) != len(sites):
+            raise ValueError("ref holds one base per site")
+        n_rows = 0 if rows is None else len(rows)
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (len(sites), 8):
+                raise ValueError("counts is the second result of Region.site_reads ([n_sites, 8])")
+        if n_rows == 0:
+            _check(dll().uvcio_sitereads_add(self.h, int(tid), contig.encode(), sites.ctypes.data, ref.encode() if ref is not None else None, len(sites), counts.ctypes.data if counts is not None else None,
+                                             None, 0, 0, None, None, None, None, None, None, None, None, None))
+            return
+        rows = np.ascontiguousarray(rows)
+        if rows.dtype.itemsize != 32 or counts is None or reads is None or qnames is None:
+            raise ValueError("rows come with the counts of their call, the reads and their names")
+        n = len(qnames)
+        col = lambda k, t: np.ascontiguousarray(reads[k], dtype=t)                      # noqa: E731
+        fl, mq, lq, fam, st, fr, ba, so = col("flag", np.uint16), col("mapq", np.uint8), col("l_qseq", np.int32), col("fam_id", np.int32), col("fam_strand", np.uint8), col("frag_id", np.int32), col("bases", np.uint8), col("seq_off", np.int64)
+        if min(len(fl), len(mq), len(lq), len(fam), len(st), len(fr), len(so)) < n:
+            raise ValueError("every alignment has a name")
+        names = (C.c_char_p * n)(*[q.encode() if isinstance(q, str) else q for q in qnames])
+        _check(dll().uvcio_sitereads_add(self.h, int(tid), contig.encode(), sites.ctypes.data, ref.encode() if ref is not None else None, len(sites), counts.ctypes.data, rows.ctypes.data, n_rows, n,
+                                         names, fl.ctypes.data, mq.ctypes.data, lq.ctypes.data, fam.ctypes.data, st.ctypes.data, fr.ctypes.data, ba.ctypes.data, so.ctypes.data))
+
+
 class Callable(_Store):
     """uvcio_callable_*: the store behind uvc1-mi355x --callable-out.  Targets are added in report order with their positions inside the
     contig; add_runs takes the runs of one Region.callable and the target of each of its ranges (any thread, any order); write() sorts,

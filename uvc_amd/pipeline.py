@@ -26,7 +26,7 @@ FILTERS = ["Q10", "Q20", "Q30", "Q40", "Q50", "Q60", "PASS"]
 def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None, molecule_tag=0, disable_duplex=0, correct_bq=True, all_out=False, keep_handle=False, reuse=None, vcf=False,
                 continues=False, has_next=False, region_beg=None, tumor_vcf=None, umi_struct=None, assay_type=0, force_sites=None, pieces=None, single_ranges=False, score_mem_mb=0):
     """Scores [beg, end) of `chrom`.  Returns None when no read passes the filters (process_batch returns -1, main.cpp:520-523), else a
-    dict: records (field -> int32 array), alleles (InDel allele rows), score range, region handle (if keep_handle).
+    dict: records (field -> int32 array), alleles (InDel allele rows), score range, region handle with its reads, the fetch's names and the reads' order in the fetch (if keep_handle).
     Tiles of one stretch: the reference scores zerobased_pos rpos_beg .. rpos_end inclusive and skips the BASE sub-position of the first
     (main.cpp:608, 643), so two adjacent regions both write the LINK records of their shared end point.  Here every zerobased_pos has one
     owner: `has_next` (an adjacent tile [end, ..) follows) leaves zerobased_pos `end` to that tile, and `continues` (an adjacent tile
@@ -151,8 +151,8 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
         out["vcf"] = text
     elif vcf:
         out["vcf"] = R.vcf_records(chrom, rec, tumor_keys=tk, tumor_sample_columns=tcols, tumor_ref_alt=tras, **skw)          # the record lines of append_vcf_record (uvcgpu_region_vcf_records), before the handle moves on
-    if keep_handle:
-        out["region"] = R
+    if keep_handle:                                                                    # with the reads the handle was given; alignment i of them is alignment order[i] of the fetch, whose name is qnames[order[i]] (decoded on demand)
+        out["region"], out["reads"], out["qnames"], out["order"] = R, reads, cols["qnames"], o
     elif reuse is None:
         R.close()
     lap("alleles+close")

@@ -29,6 +29,8 @@ FAMILY_STATS = _ffi.FAMILY_STATS             # the sections of a row of Region.f
 FRAGMENT_PROFILE = _ffi.FRAGMENT_PROFILE     # the sections of the profile row of Region.fragment_profile, in row order (include/uvc_fragprofile.def)
 READ_CLASSES = ["R1_fwd", "R1_rev", "R2_fwd", "R2_rev"]   # the read classes of Region.read_profile, in row order (uvcgpu_read_class_name)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
+SITE_READ_KINDS = _ffi.SITE_READ_KINDS       # the observation kinds of Region.site_reads, in id order: A C G T N DEL
+SITE_READ = np.dtype([(n, np.int32) for n, _ in _ffi.UvcSiteRead._fields_])   # UvcSiteRead: site read q obs ins_q ins_len del_len reserved
 CALLABLE_RUN = np.dtype([("range", np.int32), ("pos_beg", np.int32), ("pos_end", np.int32), ("mask", np.int32)])   # UvcCallableRun
 
 _gpu_lib = None
@@ -572,6 +574,30 @@ class Region:
         out = np.zeros(max(n.value, 1), dtype=CALLABLE_RUN)
         self._check(fn(self.h, arr, len(rows), C.byref(req), out.ctypes.data, n.value, C.byref(n)))
         return out[:n.value].copy()
+
+    def site_reads(self, sites, min_mapq=0, alt_only=False):
+        """uvcgpu_region_site_reads: the alignments of the region's reads behind `sites` -- zero-based positions, strictly ascending, inside
+        the region.  -> (rows, counts): rows a structured array of SITE_READ (site: index into `sites`; read: the alignment's index in the
+        reads as given; q: query index; obs: kind | quality << 8, kind of SITE_READ_KINDS; ins_q, ins_len, del_len: the InDels anchored at
+        the site; reserved 0), ascending by (read, site); counts int32 [n_sites, 8]: the observations of each kind, those with an insertion
+        and those with a deletion behind them, over all alignments with mapq >= min_mapq, whatever alt_only says.  alt_only keeps the rows
+        that differ from the reference: a deletion, an InDel anchored at the site, or an A/C/G/T base other than an A/C/G/T reference
+        symbol.  The quality is the handle's present one (after correct_bq() the corrected one); uvcgpu.h has the rules.  Found and
+        compacted on the device; asks for the size first, then for the rows: the count pass runs once for the size and once more with the
+        rows (a third time while the handle's report buffer still has to grow), so a caller who times the call, or who knows a bound of
+        the rows, calls uvcgpu_region_site_reads itself with room (scripts/gpu_sitereads_bench.py does).  Legal where family_stats() is."""
+        fn = self._ranges_fn("region_site_reads", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        arr = np.ascontiguousarray(sites, dtype=np.int32)
+        req = _ffi.UvcSiteReadsRequest(int(min_mapq), int(alt_only))
+        counts = np.zeros((len(arr), _ffi.ENUMS["UVC_SITEREAD_NCOL"]), dtype=np.int32)
+        n = C.c_int64(0)
+        rc = fn(self.h, arr.ctypes.data, len(arr), C.byref(req), counts.ctypes.data, None, 0, C.byref(n))
+        if rc != _ffi.ENUMS["UVCGPU_ENOMEM"]:
+            self._check(rc)
+        out = np.zeros(max(n.value, 1), dtype=SITE_READ)
+        if n.value:
+            self._check(fn(self.h, arr.ctypes.data, len(arr), C.byref(req), counts.ctypes.data, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value].copy(), counts
 
     def msi(self, ranges, min_tracklen=10, min_units=5, max_unitlen=6):
         """uvcgpu_region_msi: the microsatellite loci whose head lies in `ranges` -- (pos_beg, pos_end) pairs as for coverage() -- as the STR
