@@ -1,4 +1,4 @@
-"""uvc_launch_block_scan on its own: the one-block array scan behind the callable, MSI and read-profile reports (uvc_callable.hip).  In place,
+"""uvc_launch_block_scan on its own: the one-block array scan behind the callable, MSI, read-profile and site reports (uvc_report_common.hip).  In place,
 a[i] becomes the sum of a[0 .. i) and a[n], one element behind the input, the total.  The sizes cover a lane, a wave, a block of 1 024
 threads and the carry between rounds; the values are signed (the read profile scans depth differences) and far from overflow.
 The array lives in memory of the HIP runtime the library itself links, as in test_gpu_device_reads.py: torch's own copy of the runtime

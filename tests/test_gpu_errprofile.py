@@ -106,6 +106,27 @@ def test_rows_equal_the_numpy_restatement_over_the_oracles_planes(name, oracle_l
     Rg.close()
 
 
+def test_sharded_profile_equals_the_restatement(oracle_lib, gpu_lib):
+    """From 128 blocks (32 768 compact positions) on the blocks add into copies of the profile and the shared fold (uvc_launch_sum_fold, with
+    the profile's 3 560 words as its run-time row length) sums them: 40 000 positions in one range are 157 blocks and 2 copies."""
+    reads = synth.generate_region(region_len=40000, depth=8, seed=21)
+    Ro = run_region(oracle_lib, reads)
+    cells = er.level_cells(Ro.fetch)
+    Ro.close()
+    Rg = run_region(gpu_lib, reads)
+    beg, npos = Rg.beg, Rg.npos
+    blocks = -(-npos // 256)
+    assert 128 <= blocks < 192 and blocks // 64 == 2, (npos, blocks)   # err_geometry: one step per block, shards = blocks / 64
+    whole = [(beg, beg + npos)]
+    for g in [(1, 1000), (5, 50)]:
+        want = er.Restatement(cells, reads["refseq"], beg, *g).profile(whole)
+        got = Rg.error_profile(whole, *g)
+        assert want[LEVEL["bDP"], er.BASE_BINS:er.LINK_BINS].any() and (g != (1, 1000) or want[LEVEL["bDP"], er.C["BASE_counted"]] > 20000)   # (the oracle's profile is not zeros)
+        bad = np.argwhere(got != want)
+        assert len(bad) == 0, (g, [(tuple(i), int(got[tuple(i)]), int(want[tuple(i)])) for i in bad[:6]])
+    Rg.close()
+
+
 def test_argument_checks(oracle_lib, gpu_lib):
     reads = synth.generate_region(**CASES["tiny_600bp_5x"])
     fn = gpu_lib.dll.uvcgpu_region_error_profile

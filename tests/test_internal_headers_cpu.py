@@ -30,11 +30,11 @@ def test_boundary_structs_are_defined_in_headers_only():
     assert not bad, bad
 
 
-# Loops over shuffle distances (a `for` whose step is `<<= 1` or `>>= 1` around a __shfl_ call) live in uvc_collectives.h.  The three that
-# stay in a source file, one each, with the shuffle they use: the suffix minimum of uvc_rtr.hip and the segmented fold of uvc_famstats.hip are
-# not scans or reductions of the header's kind; the butterfly of uvc_coverage.hip costs k_coverage registers when it goes through the header
-# (the comment on wave_merge has the numbers).
-SHUFFLE_LOOPS_OUTSIDE_THE_HEADER = [("uvc_coverage.hip", "__shfl_xor"), ("uvc_famstats.hip", "__shfl_down"), ("uvc_rtr.hip", "__shfl_down")]
+# Loops over shuffle distances (a `for` whose step is `<<= 1` or `>>= 1` around a __shfl_ call) live in uvc_collectives.h, and the segmented
+# fold of the reports -- not a scan or reduction of that header's kind -- once in uvc_report_dev.h.  The two that stay in a source file, one
+# each, with the shuffle they use: the suffix minimum of uvc_rtr.hip, not of the header's kind either; the butterfly of uvc_coverage.hip costs
+# k_coverage registers when it goes through the header (the comment on wave_merge has the numbers).
+SHUFFLE_LOOPS_OUTSIDE_THE_HEADER = [("uvc_coverage.hip", "__shfl_xor"), ("uvc_rtr.hip", "__shfl_down")]
 
 
 def _closing(text, i, open_ch, close_ch):
@@ -80,6 +80,8 @@ def test_loops_over_shuffle_distances_live_in_the_collectives_header():
     assert sorted(found) == SHUFFLE_LOOPS_OUTSIDE_THE_HEADER, found
     with open(os.path.join(CSRC, "uvc_collectives.h")) as f:
         assert len(_shuffle_loops(f.read())) == 4   # wave_sum, wave_min, wave_max, wave_incl
+    with open(os.path.join(CSRC, "uvc_report_dev.h")) as f:
+        assert _shuffle_loops(f.read()) == [["__shfl_down"]]   # seg_fold_minmax
 
 
 # The memory of a region handle has two owners in uvc_host.cpp, Buf (a buffer that grows on demand) and Pool (allocations freed together):

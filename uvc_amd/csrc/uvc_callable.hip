@@ -9,14 +9,13 @@
 //                     byte per compact position and counts the block's run heads.  A position is a head when it is the first of its range or
 //                     its mask differs from the mask of the position before it; that mask comes from the lane to the left, and a lane 0
 //                     that does not start a range RECOMPUTES the mask of the position before the wave's first (one lane in 64 reads twice).
-//   k_block_scan      one block: the exclusive prefix of the block counts in place, their total (the number of runs) behind them.
+//   (scan)            uvc_launch_block_scan, one block: the exclusive prefix of the block counts in place, their total (the number of runs) behind them.
 //   k_callable_emit   reads the mask bytes (its own, both neighbours'), ranks the heads -- ballot and popcount in a wave, LDS across the four
 //                     waves, a running base across the steps, the scanned count across blocks -- and writes the runs in order: a head
 //                     writes { range, pos_beg, mask } of its run, the last position of a run writes its pos_end.
 // No workgroup waits on another, nothing is atomic, every store is a plain vector store; the bytes are the same from call to call.  The host
 // reads the number of runs between scan and emit, so a call whose caller has too little room launches no emit.
-#include "uvc_launch.h"
-#include "uvc_collectives.h"
+#include "uvc_report_dev.h"
 
 namespace {
 enum {
@@ -87,27 +86,8 @@ __global__ void __launch_bounds__(256) k_callable_count(RegionDev R, const UvcRa
     if (threadIdx.x == 0) block_count[blockIdx.x] = block_heads;
 }
 
-// The array scan of the reports, one block: in place, a[i] becomes the sum of the elements in front of it, a[n] (one element behind the
-// input) their total.  The callable and the MSI call scan their block counts with it (heads in front of block b, at most the positions of
-// the call: below 2^31), the read profile the tile sums of its depth differences and chunk counts.
-__global__ void __launch_bounds__(1024) k_block_scan(int *a, int n) {
-    __shared__ int sh_wave[16];
-    int carry = 0;
-    for (int i0 = 0; i0 < n; i0 += 1024) {
-        const int i = i0 + (int)threadIdx.x;
-        const int v = (i < n ? a[i] : 0);
-        int total;
-        const int excl = block_excl<16>(v, sh_wave, total);
-        if (i < n) a[i] = carry + excl;
-        carry += total;
-        __syncthreads();   // sh_wave is written again in the next round
-    }
-    if (threadIdx.x == 0) a[n] = carry;
-}
-
 __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, int n_ranges, int n_total, int region_beg, const unsigned char *mask, const int *block_off, UvcCallableRun *runs) {
     __shared__ int wave_heads[4];
-    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
     const long long base = (long long)blockIdx.x * CALL_TILE;
     UvcRangeCursor g;
     int run_base = block_off[blockIdx.x];   // the heads in front of this step's first position
@@ -123,24 +103,19 @@ __global__ void __launch_bounds__(256) k_callable_emit(const UvcRangeRow *tab, i
             head = (i == g.first || mask[i - 1] != m);
             tail = (i + 1 == g.next || mask[i + 1] != m);   // (g.next <= n_total: i + 1 is read only inside the range)
         }
-        const unsigned long long heads = __ballot(head);
-        if (lane == 0) wave_heads[wv] = __popcll(heads);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; w++) before += wave_heads[w];
+        int step_heads;
         // the run this position lies in: the heads up to and including it, less one (position 0 of the call is a head, so never below 0)
-        const int idx = run_base + before + __popcll(heads & ((2ull << lane) - 1ull)) - 1;
+        const int idx = run_base + head_rank(head, wave_heads, step_heads) - 1;
         if (head) { runs[idx].range = g.rid; runs[idx].pos_beg = pos; runs[idx].mask = m; }
         if (tail) runs[idx].pos_end = pos + 1;
-        run_base += wave_heads[0] + wave_heads[1] + wave_heads[2] + wave_heads[3];
-        __syncthreads();
+        run_base += step_heads;
+        __syncthreads();   // wave_heads is written again in the next step
     }
 }
 }   // namespace
 
 extern "C" const char *uvc_callable_name(int bit) { return (bit >= 0 && bit < UVC_NCALLBIT) ? CALL_NAMES[bit] : nullptr; }
 extern "C" int64_t uvc_callable_blocks(int64_t n_total) { return (n_total + CALL_TILE - 1) / CALL_TILE; }
-extern "C" void uvc_launch_block_scan(int *d_a, int n, hipStream_t s) { hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, d_a, n); }
 // d_tab: n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one receives the number of runs
 extern "C" void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s) {
     if (n_ranges <= 0 || n_total <= 0) return;

@@ -246,6 +246,10 @@ DEV bool symbols_mutated(int ref, int alt) {      // areSymbolsMutated, main_con
 }
 DEV int cig_op(uint32_t c) { return (int)(c & 0xF); }
 DEV int cig_len(uint32_t c) { return (int)(c >> 4); }
+// the op classes: an aligned op (M, =, X) consumes query and reference alike
+DEV bool cig_aligned(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF; }
+DEV bool cig_query(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF || op == C_INS || op == C_SOFT_CLIP; }
+DEV bool cig_ref(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF || op == C_DEL || op == C_REF_SKIP; }
 
 // plane addressing
 #define P32(R, f, x) ((R).prep32[(size_t)(f) * (R).npos + (x)])

@@ -13,7 +13,7 @@
 // a question for the measurements of DESIGN.md 4j, not settled here.
 // At the end a block adds its non-zero words to the result with 64-bit vector atomics.  Integer arithmetic only: the order of the adds does
 // not show, the result is the same bits from call to call.
-#include "uvc_launch.h"
+#include "uvc_report_dev.h"
 
 #include <algorithm>
 
@@ -48,12 +48,6 @@ DEV long long err_FRAG(const RegionDev &R, int plane, int s, int64_t x) { return
 DEV long long err_FAM(const RegionDev &R, int plane, int s, int64_t x) { return (long long)FAP(R, 0, plane, s, x) + FAP(R, 1, plane, s, x); }
 DEV long long err_DUPLEX(const RegionDev &R, int plane, int s, int64_t x) { return (long long)DUP(R, plane, s, x); }
 
-DEV void lds_add(unsigned long long *p, unsigned long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// a wave-uniform counter: the lanes with `on` are counted by a ballot, the wave's first lane adds the count
-DEV void count_lanes(unsigned long long *p, bool on, int lane) {
-    const unsigned long long m = __ballot(on);
-    if (lane == 0 && m) lds_add(p, (unsigned long long)__popcll(m));
-}
 // One kind of one level at one position: v[0] is the reference symbol's cell when ref == 0 (LINK: LINK_M is slot 0), else ref names the slot
 // (BASE: m).  `ctx` < 0: the position has no context (or the lane has no position) and adds nothing.
 template <int N> DEV void err_kind(const long long (&v)[N], int ref, int ctx, int min_depth, int permille, unsigned long long *bins, unsigned long long *counters, int lane) {
@@ -79,15 +73,6 @@ static_assert(UVC_ERRC_BASE_low_depth == UVC_ERRC_BASE_counted + 1 && UVC_ERRC_B
 __global__ void __launch_bounds__(256) k_errprofile_init(unsigned long long *out, int n_cells) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i < n_cells) out[i] = 0;
-}
-// Many blocks: their flushes meet on the same 3 560 words, and atomics on one word run one after the other (61 ns each).  The
-// blocks then add into `shards` copies of the profile (block index modulo shards) and this kernel folds the copies: one lane per word.
-__global__ void __launch_bounds__(256) k_errprofile_fold(const unsigned long long *parts, int shards, unsigned long long *out) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= ERR_CELLS) return;
-    unsigned long long v = 0;
-    for (int s = 0; s < shards; s++) v += parts[(size_t)s * ERR_CELLS + i];
-    out[i] = v;
 }
 
 __global__ void __launch_bounds__(256) k_errprofile(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, int steps, int shards, int min_depth, int permille, unsigned long long *out) {
@@ -142,7 +127,7 @@ __global__ void __launch_bounds__(256) k_errprofile(RegionDev R, const UvcRangeR
 
 void err_geometry(int64_t n_total, int &steps, long long &n_blocks, int &shards) {
     // a block keeps its profile in LDS over `steps` groups of 256 positions: fewer flushes, as long as 1 024 blocks (four per CU) stay to fill
-    // the machine.  From 128 blocks on the profile is sharded (k_errprofile_fold), at most 16 copies: up to 1 024 blocks (4 M positions at 16
+    // the machine.  From 128 blocks on the profile is sharded (its flushes meet on the same 3 560 words; uvc_launch_sum_fold sums the copies), at most 16 copies: up to 1 024 blocks (4 M positions at 16
     // steps) fewer than 128 flushes meet on one word; beyond that the chain on a word grows with the positions, blocks / 16 flushes
     steps = (int)std::max<int64_t>(1, std::min<int64_t>(ERR_MAX_STEPS, n_total / (256 * 1024)));
     n_blocks = (n_total + 256LL * steps - 1) / (256LL * steps);
@@ -163,5 +148,5 @@ extern "C" void uvc_launch_errprofile(const RegionDev *R, const UvcRangeRow *d_t
     const int n_cells = ERR_CELLS * shards;
     hipLaunchKernelGGL(k_errprofile_init, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, s, d_parts, n_cells);
     hipLaunchKernelGGL(k_errprofile, dim3((unsigned)n_blocks), dim3(256), 0, s, *R, d_tab, n_ranges, (int)n_total, steps, shards, min_depth, max_alt_permille, d_parts);
-    if (shards > 1) hipLaunchKernelGGL(k_errprofile_fold, dim3((unsigned)((ERR_CELLS + 255) / 256)), dim3(256), 0, s, d_parts, shards, (unsigned long long *)d_out);
+    if (shards > 1) uvc_launch_sum_fold(d_scratch, shards, ERR_CELLS, d_out, s);
 }

@@ -6,21 +6,17 @@
 // over the alignments, and a unit holds one alignment or tens of thousands (a non-UMI amplicon pile).  So the work is split by alignment,
 // never by unit: a lane takes one alignment (pos, end and unit index are 4-byte columns: 64 consecutive alignments are one wave
 // instruction each; AlnRec::pos / rend hold the same two numbers 200 bytes apart), the alignments of a unit are consecutive, and a wave reduces each
-// run of equal unit indices among its lanes with a segmented butterfly.  The head lane of a run merges it into the unit's { lo, hi } with
+// run of equal unit indices among its lanes with a segmented butterfly (seg_fold_minmax).  The head lane of a run merges it into the unit's { lo, hi } with
 // one atomicMin and one atomicMax: a unit of 30 000 alignments costs 470 pairs of atomics on its word, a unit of one alignment one pair.
 //
 // Stage two, the rows (k_famstat_bin).  A lane takes one unit; the strand-0 unit of a family -- or its strand-1 unit where there is no
-// other -- joins its partner (FsRec::other_fs) into the family record { a, b, n, lo, hi, dflag }, finds the first range that ends behind lo
-// by binary search on pos_end and walks forward while the family overlaps.  A 365-word row per range does not fit LDS for hundreds of
-// ranges, and one range must not put every lane of the machine on the same 365 global words.  So a block keeps the partial rows of a WINDOW
-// of FS_WIN consecutive ranges in LDS, beginning at the smallest first-candidate range of its families (the units of a tile come roughly in
-// position order, so most adds of a block fall into its window; with at most FS_WIN ranges every add does), and adds everything outside the
-// window straight to the global rows -- adds that then spread over many ranges.  LDS words are 32 bits: a block's families add each
-// counter of a row at most once per family, and a region holds fewer than 2^30 alignments.  At the end a block adds its non-zero words to
-// the int64 rows with 64-bit vector atomics.  Integer adds only: their order does not show, the rows are the same bits from call to call.
-#include "uvc_launch.h"
-
-#include <limits.h>
+// other -- joins its partner (FsRec::other_fs) into the family record { a, b, n, lo, hi, dflag }, finds its first range (first_range) and
+// walks forward while the family overlaps.  A 365-word row per range does not fit LDS for hundreds of ranges, and one range must not put
+// every lane of the machine on the same 365 global words.  So a block keeps a UvcRowWindow of FS_WIN consecutive ranges (the units of a
+// tile come roughly in position order, so most adds of a block fall into its window; with at most FS_WIN ranges every add does).  LDS
+// words are 32 bits: a block's families add each counter of a row at most once per family, and a region holds fewer than 2^30 alignments.
+// Integer adds only: their order does not show, the rows are the same bits from call to call.
+#include "uvc_report_dev.h"
 
 namespace {
 enum {
@@ -33,14 +29,12 @@ static_assert(FSROW_N == UVC_NFAMSTAT, "include/uvc_famstats.def and UvcFamStat 
 #define UVC_FAMSTAT(name, first, words) static_assert((int)FSROW_##name == (int)UVC_FAMSTAT_##name, "uvc_famstats.def order = UvcFamStat order");
 #include "uvc_famstats.def"
 #undef UVC_FAMSTAT
-struct FsSection { const char *name; int first, words; };
-constexpr FsSection FS_SECTIONS[UVC_NFAMSTAT] = {
+constexpr UvcSection FS_SECTIONS[UVC_NFAMSTAT] = {
 #define UVC_FAMSTAT(name, first, words) { #name, first, words },
 #include "uvc_famstats.def"
 #undef UVC_FAMSTAT
 };
-constexpr bool fs_sections_abut(int k) { return k == 0 ? FS_SECTIONS[0].first == 0 : (FS_SECTIONS[k].first == FS_SECTIONS[k - 1].first + FS_SECTIONS[k - 1].words && fs_sections_abut(k - 1)); }
-static_assert(fs_sections_abut(UVC_NFAMSTAT - 1) && FS_SECTIONS[UVC_NFAMSTAT - 1].first + FS_SECTIONS[UVC_NFAMSTAT - 1].words == UVC_FAMSTAT_ROW, "the sections of uvc_famstats.def tile the row");
+static_assert(uvc_sections_tile(FS_SECTIONS, UVC_FAMSTAT_ROW), "the sections of uvc_famstats.def tile the row");
 static_assert(FS_SECTIONS[UVC_FAMSTAT_target_families].first == UVC_FAMSTAT_TARGET && FS_SECTIONS[UVC_FAMSTAT_families].first == UVC_FAMSTAT_FIRST
               && FS_SECTIONS[UVC_FAMSTAT_size].first == UVC_FAMSTAT_SIZE && FS_SECTIONS[UVC_FAMSTAT_size].words == UVC_FAMSTAT_NSIZE
               && FS_SECTIONS[UVC_FAMSTAT_strands].first == UVC_FAMSTAT_STRANDS && FS_SECTIONS[UVC_FAMSTAT_strands].words == (UVC_FAMSTAT_STRAND_CAP + 1) * (UVC_FAMSTAT_STRAND_CAP + 1),
@@ -59,34 +53,19 @@ __global__ void __launch_bounds__(256) k_famstat_init(UvcUnitSpan *span, int n_f
 
 __global__ void __launch_bounds__(256) k_famstat_span(const int32_t *pos, const int32_t *endpos, const int32_t *fs_of, int n_alns, int n_fs, UvcUnitSpan *span) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = (int)(threadIdx.x & 63);
-    int u = -1, p = INT_MAX, e = INT_MIN;
-    if (i < n_alns) { u = fs_of[i]; p = pos[i]; e = endpos[i]; }
+    int u = -1, p[1] = { INT_MAX }, e[1] = { INT_MIN };
+    if (i < n_alns) { u = fs_of[i]; p[0] = pos[i]; e[0] = endpos[i]; }
     if (u < 0 || u >= n_fs) u = -1;   // (no such unit: set_reads refuses these reads)
-    const int u_prev = __shfl_up(u, 1);   // (the previous lane's unit: a neighbour fetch, not a scan step)
-    // lane l ends up with the run's part in lanes [l, 64): after the step with `off` it holds lanes [l, l + 2 off) of its run.  (A fold segmented
-    // by the unit, over (min, max) pairs: not a scan or reduction of uvc_collectives.h's kind.)
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int u2 = __shfl_down(u, off), p2 = __shfl_down(p, off), e2 = __shfl_down(e, off);
-        if (lane + off < 64 && u2 == u) { p = imin(p, p2); e = imax(e, e2); }
-    }
-    if (u >= 0 && (lane == 0 || u_prev != u)) { atomicMin(&span[u].lo, p); atomicMax(&span[u].hi, e); }
+    seg_fold_minmax<1>(u, p, e);   // the run of a unit among the lanes
+    if (seg_head(u) && u >= 0) { atomicMin(&span[u].lo, p[0]); atomicMax(&span[u].hi, e[0]); }
 }
 
 struct FsFamily { int a, b, n, lo, hi, dflag, first; };   // first: the first range that ends behind lo; n_ranges: the lane has no family or no range
 
-DEV void fs_add(unsigned *part, unsigned long long *rows, int i, int w0, int word, unsigned v) {
-    if ((unsigned)(i - w0) < (unsigned)FS_WIN) __hip_atomic_fetch_add(part + (i - w0) * UVC_FAMSTAT_ROW + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else atomicAdd(rows + (size_t)i * UVC_FAMSTAT_ROW + word, (unsigned long long)v);
-}
-
 __global__ void __launch_bounds__(256) k_famstat_bin(RegionDev R, const UvcUnitSpan *span, const UvcFamilyRange *ranges, int n_ranges, unsigned long long *rows) {
-    __shared__ unsigned part[FS_WIN * UVC_FAMSTAT_ROW];
-    __shared__ int win0;
+    __shared__ UvcRowWindow<unsigned, FS_WIN, UVC_FAMSTAT_ROW> win;
     const int tid = (int)threadIdx.x;
-    for (int j = tid; j < FS_WIN * UVC_FAMSTAT_ROW; j += 256) part[j] = 0;
-    if (tid == 0) win0 = INT_MAX;
+    win.begin(tid);
     __syncthreads();
     FsFamily fam[FS_STEPS];
     int first_min = INT_MAX;
@@ -114,47 +93,41 @@ __global__ void __launch_bounds__(256) k_famstat_bin(RegionDev R, const UvcUnitS
         }
         f.a = a; f.b = b; f.lo = s.lo; f.hi = s.hi; f.dflag = me.dflag;
         if (f.hi <= f.lo) continue;   // (a unit without alignments)
-        int lo = 0, hi = n_ranges;   // the first range with pos_end > f.lo
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (ranges[mid].pos_end > f.lo) hi = mid; else lo = mid + 1; }
-        if (lo < n_ranges && ranges[lo].pos_beg < f.hi) { f.first = lo; first_min = imin(first_min, lo); }
+        f.first = first_range(ranges, n_ranges, f.lo, f.hi);
+        if (f.first < n_ranges) first_min = imin(first_min, f.first);
     }
-    if (first_min != INT_MAX) __hip_atomic_fetch_min(&win0, first_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __syncthreads();
-    const int w0 = win0;
+    const int w0 = win.choose(first_min);
     if (w0 == INT_MAX) return;   // (block-uniform) none of the block's families meets a range
 #pragma unroll
     for (int c = 0; c < FS_STEPS; c++) {
         const FsFamily &f = fam[c];
         const int frg = f.a + f.b;
+        const bool both = (f.a >= 1 && f.b >= 1);
         for (int i = f.first; i < n_ranges; i++) {
             const UvcFamilyRange q = ranges[i];
             if (q.pos_beg >= f.hi) break;   // the ranges ascend: no later one overlaps (f.lo < q.pos_end holds from `first` on)
-            const bool both = (f.a >= 1 && f.b >= 1);
+            const auto add = [&](int word, unsigned v) { win.add(w0, rows, i, word, v); };
             if (!(q.flags & UVC_FAMRANGE_CONTINUES) || f.lo >= q.pos_beg) {
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_TARGET + 0, 1u);
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_TARGET + 1, (unsigned)frg);
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_TARGET + 2, (unsigned)f.n);
-                if (both) fs_add(part, rows, i, w0, UVC_FAMSTAT_TARGET + 3, 1u);
+                add(UVC_FAMSTAT_TARGET + 0, 1u);
+                add(UVC_FAMSTAT_TARGET + 1, (unsigned)frg);
+                add(UVC_FAMSTAT_TARGET + 2, (unsigned)f.n);
+                if (both) add(UVC_FAMSTAT_TARGET + 3, 1u);
             }
             if (q.prev_end <= f.lo) {
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 0, 1u);
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 1, (unsigned)frg);
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 2, (unsigned)f.n);
-                if (both) fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 3, 1u);
-                if (f.dflag & 1) fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 4, 1u);
-                if (f.dflag & 2) fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 5, 1u);
-                if (f.dflag & 4) fs_add(part, rows, i, w0, UVC_FAMSTAT_FIRST + 6, 1u);
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_SIZE + imin(frg, UVC_FAMSTAT_NSIZE) - 1, 1u);
-                fs_add(part, rows, i, w0, UVC_FAMSTAT_STRANDS + imin(f.a, UVC_FAMSTAT_STRAND_CAP) * (UVC_FAMSTAT_STRAND_CAP + 1) + imin(f.b, UVC_FAMSTAT_STRAND_CAP), 1u);
+                add(UVC_FAMSTAT_FIRST + 0, 1u);
+                add(UVC_FAMSTAT_FIRST + 1, (unsigned)frg);
+                add(UVC_FAMSTAT_FIRST + 2, (unsigned)f.n);
+                if (both) add(UVC_FAMSTAT_FIRST + 3, 1u);
+                if (f.dflag & 1) add(UVC_FAMSTAT_FIRST + 4, 1u);
+                if (f.dflag & 2) add(UVC_FAMSTAT_FIRST + 5, 1u);
+                if (f.dflag & 4) add(UVC_FAMSTAT_FIRST + 6, 1u);
+                add(UVC_FAMSTAT_SIZE + imin(frg, UVC_FAMSTAT_NSIZE) - 1, 1u);
+                add(UVC_FAMSTAT_STRANDS + imin(f.a, UVC_FAMSTAT_STRAND_CAP) * (UVC_FAMSTAT_STRAND_CAP + 1) + imin(f.b, UVC_FAMSTAT_STRAND_CAP), 1u);
             }
         }
     }
     __syncthreads();
-    for (int j = tid; j < FS_WIN * UVC_FAMSTAT_ROW; j += 256) {
-        const unsigned v = part[j];
-        const int i = w0 + j / UVC_FAMSTAT_ROW;
-        if (v && i < n_ranges) atomicAdd(rows + (size_t)i * UVC_FAMSTAT_ROW + (j % UVC_FAMSTAT_ROW), (unsigned long long)v);
-    }
+    win.flush(tid, w0, n_ranges, rows);
 }
 static_assert(UVC_FAMSTAT_families_umi == UVC_FAMSTAT_families + 4 && UVC_FAMSTAT_families_duplex_tag == UVC_FAMSTAT_families + 5 && UVC_FAMSTAT_families_amplicon == UVC_FAMSTAT_families + 6
               && UVC_FAMSTAT_target_families_both_strands == 3 && UVC_FAMSTAT_families_both_strands == UVC_FAMSTAT_families + 3, "k_famstat_bin's counter order");

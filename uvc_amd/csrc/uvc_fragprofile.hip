@@ -20,12 +20,9 @@
 // (its two ends) to a word.  len_sum is a sum of lengths, not a count, so the block's len_sum and the window's TARGET rows are 64-bit
 // words.  A block adds its non-zero words with 64-bit vector atomics: the profile into one of FP_SHARDS copies that k_fp_fold sums, the
 // window into the result rows.  Integer adds only: their order does not show, the result is the same bits from call to call.
-#include "uvc_launch.h"
-#include "uvc_collectives.h"
-#include "uvc_segfold.h"
+#include "uvc_report_dev.h"
 
 #include <algorithm>
-#include <limits.h>
 
 namespace {
 enum {
@@ -38,14 +35,12 @@ static_assert(FPROW_N == UVC_NFRAGPROF, "include/uvc_fragprofile.def and UvcFrag
 #define UVC_FRAGPROF(name, first, words) static_assert((int)FPROW_##name == (int)UVC_FRAGPROF_##name, "uvc_fragprofile.def order = UvcFragProfSection order");
 #include "uvc_fragprofile.def"
 #undef UVC_FRAGPROF
-struct FpSection { const char *name; int first, words; };
-constexpr FpSection FP_SECTIONS[UVC_NFRAGPROF] = {
+constexpr UvcSection FP_SECTIONS[UVC_NFRAGPROF] = {
 #define UVC_FRAGPROF(name, first, words) { #name, first, words },
 #include "uvc_fragprofile.def"
 #undef UVC_FRAGPROF
 };
-constexpr bool fp_sections_abut(int k) { return k == 0 ? FP_SECTIONS[0].first == 0 : (FP_SECTIONS[k].first == FP_SECTIONS[k - 1].first + FP_SECTIONS[k - 1].words && fp_sections_abut(k - 1)); }
-static_assert(fp_sections_abut(UVC_NFRAGPROF - 1) && FP_SECTIONS[UVC_NFRAGPROF - 1].first + FP_SECTIONS[UVC_NFRAGPROF - 1].words == UVC_FRAGPROF_ROW, "the sections of uvc_fragprofile.def tile the row");
+static_assert(uvc_sections_tile(FP_SECTIONS, UVC_FRAGPROF_ROW), "the sections of uvc_fragprofile.def tile the row");
 static_assert(FP_SECTIONS[UVC_FRAGPROF_LEN].first == UVC_FRAGPROF_LEN_BINS && FP_SECTIONS[UVC_FRAGPROF_LEN].words == UVC_FRAGPROF_NLEN
               && FP_SECTIONS[UVC_FRAGPROF_FAMLEN].first == UVC_FRAGPROF_FAMLEN_BINS && FP_SECTIONS[UVC_FRAGPROF_FAMLEN].words == UVC_FRAGPROF_NLEN
               && FP_SECTIONS[UVC_FRAGPROF_MOTIF].first == UVC_FRAGPROF_MOTIF_BINS && FP_SECTIONS[UVC_FRAGPROF_MOTIF].words == UVC_FRAGPROF_NMOTIF
@@ -86,7 +81,7 @@ __global__ void __launch_bounds__(256) k_fp_span(const int32_t *pos, const int32
         }
     }
     if (g < 0 || g >= n_frags) g = -1;   // (no such fragment: set_reads refuses these reads)
-    seg_fold_minmax<2>(g, lo, hi);   // the run of a fragment among the lanes, as k_famstat_span folds a unit's, over two (min, max) pairs
+    seg_fold_minmax<2>(g, lo, hi);   // the run of a fragment among the lanes, over two (min, max) pairs
     if (seg_head(g) && g >= 0) {
         if (lo[0] != INT_MAX) { atomicMin(&fspan[g].loF, lo[0]); atomicMax(&fspan[g].hiF, hi[0]); }
         if (lo[1] != INT_MAX) { atomicMin(&fspan[g].loR, lo[1]); atomicMax(&fspan[g].hiR, hi[1]); }
@@ -95,56 +90,19 @@ __global__ void __launch_bounds__(256) k_fp_span(const int32_t *pos, const int32
 
 struct FpObj { int lo, hi, first, kind; };   // [lo, hi); first: the first range it overlaps, n_ranges where there is none; kind < 0: the lane has no object
 
-// the first range that ends behind lo, where it begins in front of hi; else n_ranges
-DEV int fp_first_range(const UvcFamilyRange *ranges, int n_ranges, int lo, int hi) {
-    int a = 0, b = n_ranges;
-    while (a < b) { const int mid = (a + b) >> 1; if (ranges[mid].pos_end > lo) b = mid; else a = mid + 1; }
-    return (a < n_ranges && ranges[a].pos_beg < hi) ? a : n_ranges;
-}
-DEV void fp_target_add(unsigned long long *part, unsigned long long *rows, int i, int w0, int word, unsigned long long v) {
-    if ((unsigned)(i - w0) < (unsigned)FP_WIN) __hip_atomic_fetch_add(part + (i - w0) * FP_TROW + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else atomicAdd(rows + (size_t)i * FP_TROW + word, v);
-}
-DEV void fp_lds_add(unsigned *p, unsigned v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// a word every lane of the wave would add 1 to: the lanes with `on` are counted by a ballot, the wave's first lane adds the count
-DEV void fp_count_lanes(unsigned *p, bool on, int lane) {
-    const unsigned long long m = __ballot(on);
-    if (lane == 0 && m) fp_lds_add(p, (unsigned)__popcll(m));
-}
-// tab[key] += 1 for every lane with `on`, equal keys merged first (rp_merge_add of the read profile).  Called by the whole wave.
-DEV void fp_merge_add(unsigned *tab, int key, bool on, int lane) {
-    unsigned long long left = __ballot(on);
-    while (left) {
-        const int lead = __ffsll((long long)left) - 1;
-        const int k = __shfl(key, lead);
-        const unsigned long long same = __ballot(on && key == k);
-        if (lane == lead) fp_lds_add(tab + k, (unsigned)__popcll(same));
-        left &= ~same;
-    }
-}
-// what a block keeps: the profile copy, the TARGET rows of its window, its len_sum and the window's first range
-struct FpBlock { unsigned prof[UVC_FRAGPROF_ROW]; unsigned long long part[FP_WIN * FP_TROW]; unsigned long long len_sum; int win0; };
+// what a block keeps: the profile copy, the TARGET rows of its window and its len_sum
+struct FpBlock { unsigned prof[UVC_FRAGPROF_ROW]; UvcRowWindow<unsigned long long, FP_WIN, FP_TROW> win; unsigned long long len_sum; };
 DEV void fp_block_begin(FpBlock &B, int tid) {
     for (int j = tid; j < UVC_FRAGPROF_ROW; j += 256) B.prof[j] = 0;
-    for (int j = tid; j < FP_WIN * FP_TROW; j += 256) B.part[j] = 0;
-    if (tid == 0) { B.win0 = INT_MAX; B.len_sum = 0; }
+    B.win.begin(tid);
+    if (tid == 0) B.len_sum = 0;
     __syncthreads();
-}
-// the window begins at the smallest first range of the block's objects; INT_MAX (block-uniform): none of them meets a range
-DEV int fp_block_window(FpBlock &B, int first_min) {
-    if (first_min != INT_MAX) __hip_atomic_fetch_min(&B.win0, first_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __syncthreads();
-    return B.win0;
 }
 DEV void fp_block_end(FpBlock &B, int tid, int w0, int n_ranges, unsigned long long *rows, unsigned long long *part_row) {
     __syncthreads();
     for (int j = tid; j < UVC_FRAGPROF_ROW; j += 256) { const unsigned v = B.prof[j]; if (v) atomicAdd(part_row + j, (unsigned long long)v); }
     if (tid == 0 && B.len_sum) atomicAdd(part_row + UVC_FRAGPROF_len_sum, B.len_sum);
-    for (int j = tid; j < FP_WIN * FP_TROW; j += 256) {
-        const unsigned long long v = B.part[j];
-        const int i = w0 + j / FP_TROW;
-        if (v && i < n_ranges) atomicAdd(rows + (size_t)i * FP_TROW + (j % FP_TROW), v);
-    }
+    B.win.flush(tid, w0, n_ranges, rows);
 }
 // one 5' end of a pair in the profile: x = the region offset of its first reference base (left end) or one behind its last (right end)
 DEV void fp_end(const RegionDev &R, long long x, bool right, bool on, unsigned *prof, int lane) {
@@ -159,10 +117,10 @@ DEV void fp_end(const RegionDev &R, long long x, bool right, bool on, unsigned *
             key = key * 4 + ((right ? 3 - s : s) & 3);
         }
     }
-    fp_count_lanes(prof + UVC_FRAGPROF_ends_off_region, on && !usable, lane);
-    fp_count_lanes(prof + UVC_FRAGPROF_ends_no_ref, on && usable && !acgt, lane);
-    fp_count_lanes(prof + UVC_FRAGPROF_ends, on && usable && acgt, lane);
-    fp_merge_add(prof + UVC_FRAGPROF_MOTIF_BINS, key, on && usable && acgt, lane);
+    count_lanes(prof + UVC_FRAGPROF_ends_off_region, on && !usable, lane);
+    count_lanes(prof + UVC_FRAGPROF_ends_no_ref, on && usable && !acgt, lane);
+    count_lanes(prof + UVC_FRAGPROF_ends, on && usable && acgt, lane);
+    merge_add(prof + UVC_FRAGPROF_MOTIF_BINS, key, on && usable && acgt, lane);
 }
 
 __global__ void __launch_bounds__(256) k_fp_frag(RegionDev R, const UvcFragSpan *fspan, UvcUnitSpan *uspan, const UvcFamilyRange *ranges, int n_ranges, UvcFragmentProfileRequest req,
@@ -187,7 +145,7 @@ __global__ void __launch_bounds__(256) k_fp_frag(RegionDev R, const UvcFragSpan 
                 o.lo = imin(s.loF, s.loR); o.hi = imax(s.hiF, s.hiR);
                 o.kind = (fwd && rev) ? ((s.loF <= s.loR && s.hiF <= s.hiR) ? FP_PAIR : FP_OTHER) : FP_SINGLE;
                 if (o.kind == FP_PAIR) { tlo[0] = o.lo; thi[0] = o.hi; }
-                o.first = fp_first_range(ranges, n_ranges, o.lo, o.hi);
+                o.first = first_range(ranges, n_ranges, o.lo, o.hi);
                 if (o.first < n_ranges) first_min = imin(first_min, o.first);
             }
         }
@@ -195,7 +153,7 @@ __global__ void __launch_bounds__(256) k_fp_frag(RegionDev R, const UvcFragSpan 
         seg_fold_minmax<1>(u, tlo, thi);
         if (seg_head(u) && u >= 0 && tlo[0] != INT_MAX) { atomicMin(&uspan[u].lo, tlo[0]); atomicMax(&uspan[u].hi, thi[0]); }
     }
-    const int w0 = fp_block_window(B, first_min);
+    const int w0 = B.win.choose(first_min);
     if (w0 == INT_MAX) return;   // (block-uniform) none of the block's fragments meets a range
 #pragma unroll
     for (int c = 0; c < FP_STEPS; c++) {
@@ -204,15 +162,17 @@ __global__ void __launch_bounds__(256) k_fp_frag(RegionDev R, const UvcFragSpan 
         const bool is_short = (L >= req.short_lo && L <= req.short_hi), is_long = (L >= req.long_lo && L <= req.long_hi);
         bool in_first = false;
         if (o.kind >= 0) {
+            // (k_famstat_bin's walk and k_fp_fam's, each spelled out: through one shared walk with a callback this kernel takes 56 VGPRs for 54 and
+            // k_fp_fam is scheduled differently; profiles/report_kernels_registers.txt)
             for (int i = o.first; i < n_ranges; i++) {
                 const UvcFamilyRange q = ranges[i];
                 if (q.pos_beg >= o.hi) break;   // the ranges ascend: no later one overlaps (o.lo < q.pos_end holds from `first` on)
                 if (!(q.flags & UVC_FAMRANGE_CONTINUES) || o.lo >= q.pos_beg) {
-                    fp_target_add(B.part, rows, i, w0, UVC_FRAGPROF_pairs + o.kind, 1ull);
+                    B.win.add(w0, rows, i, UVC_FRAGPROF_pairs + o.kind, 1ull);
                     if (o.kind == FP_PAIR) {
-                        fp_target_add(B.part, rows, i, w0, UVC_FRAGPROF_len_sum, (unsigned long long)L);
-                        if (is_short) fp_target_add(B.part, rows, i, w0, UVC_FRAGPROF_short, 1ull);
-                        if (is_long) fp_target_add(B.part, rows, i, w0, UVC_FRAGPROF_long, 1ull);
+                        B.win.add(w0, rows, i, UVC_FRAGPROF_len_sum, (unsigned long long)L);
+                        if (is_short) B.win.add(w0, rows, i, UVC_FRAGPROF_short, 1ull);
+                        if (is_long) B.win.add(w0, rows, i, UVC_FRAGPROF_long, 1ull);
                     }
                 }
                 if (q.prev_end <= o.lo) in_first = true;
@@ -220,14 +180,14 @@ __global__ void __launch_bounds__(256) k_fp_frag(RegionDev R, const UvcFragSpan 
         }
         // the profile: the whole wave, so that equal keys merge
         const bool pair = (in_first && o.kind == FP_PAIR);
-        fp_count_lanes(B.prof + UVC_FRAGPROF_pairs, pair, lane);
-        fp_count_lanes(B.prof + UVC_FRAGPROF_others, in_first && o.kind == FP_OTHER, lane);
-        fp_count_lanes(B.prof + UVC_FRAGPROF_singles, in_first && o.kind == FP_SINGLE, lane);
-        fp_count_lanes(B.prof + UVC_FRAGPROF_short, pair && is_short, lane);
-        fp_count_lanes(B.prof + UVC_FRAGPROF_long, pair && is_long, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_pairs, pair, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_others, in_first && o.kind == FP_OTHER, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_singles, in_first && o.kind == FP_SINGLE, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_short, pair && is_short, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_long, pair && is_long, lane);
         const long long wave_len = wave_sum(pair ? L : 0ll);
-        if (lane == 0 && wave_len) __hip_atomic_fetch_add(&B.len_sum, (unsigned long long)wave_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        fp_merge_add(B.prof + UVC_FRAGPROF_LEN_BINS, (int)(L < 0 ? 0 : L < UVC_FRAGPROF_NLEN - 1 ? L : UVC_FRAGPROF_NLEN - 1), pair, lane);
+        if (lane == 0 && wave_len) lds_add(&B.len_sum, (unsigned long long)wave_len);
+        merge_add(B.prof + UVC_FRAGPROF_LEN_BINS, (int)(L < 0 ? 0 : L < UVC_FRAGPROF_NLEN - 1 ? L : UVC_FRAGPROF_NLEN - 1), pair, lane);
         fp_end(R, (long long)o.lo - R.beg, false, pair, B.prof, lane);
         fp_end(R, (long long)o.hi - R.beg, true, pair, B.prof, lane);
     }
@@ -258,10 +218,10 @@ __global__ void __launch_bounds__(256) k_fp_fam(RegionDev R, const UvcUnitSpan *
         }
         if (s.lo == INT_MAX) continue;   // not sized: no pair fragment
         o.lo = s.lo; o.hi = s.hi; o.kind = both ? 1 : 0;
-        o.first = fp_first_range(ranges, n_ranges, o.lo, o.hi);
+        o.first = first_range(ranges, n_ranges, o.lo, o.hi);
         if (o.first < n_ranges) first_min = imin(first_min, o.first);
     }
-    const int w0 = fp_block_window(B, first_min);
+    const int w0 = B.win.choose(first_min);
     if (w0 == INT_MAX) return;   // (block-uniform) none of the block's families meets a range
 #pragma unroll
     for (int c = 0; c < FP_STEPS; c++) {
@@ -272,18 +232,20 @@ __global__ void __launch_bounds__(256) k_fp_fam(RegionDev R, const UvcUnitSpan *
             for (int i = o.first; i < n_ranges; i++) {
                 const UvcFamilyRange q = ranges[i];
                 if (q.pos_beg >= o.hi) break;
-                if (!(q.flags & UVC_FAMRANGE_CONTINUES) || o.lo >= q.pos_beg) fp_target_add(B.part, rows, i, w0, UVC_FRAGPROF_families, 1ull);
+                if (!(q.flags & UVC_FAMRANGE_CONTINUES) || o.lo >= q.pos_beg) B.win.add(w0, rows, i, UVC_FRAGPROF_families, 1ull);
                 if (q.prev_end <= o.lo) in_first = true;
             }
         }
-        fp_count_lanes(B.prof + UVC_FRAGPROF_families, in_first, lane);
-        fp_count_lanes(B.prof + UVC_FRAGPROF_families_both_strands, in_first && o.kind == 1, lane);
-        fp_merge_add(B.prof + UVC_FRAGPROF_FAMLEN_BINS, (int)(TL < 0 ? 0 : TL < UVC_FRAGPROF_NLEN - 1 ? TL : UVC_FRAGPROF_NLEN - 1), in_first, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_families, in_first, lane);
+        count_lanes(B.prof + UVC_FRAGPROF_families_both_strands, in_first && o.kind == 1, lane);
+        merge_add(B.prof + UVC_FRAGPROF_FAMLEN_BINS, (int)(TL < 0 ? 0 : TL < UVC_FRAGPROF_NLEN - 1 ? TL : UVC_FRAGPROF_NLEN - 1), in_first, lane);
     }
     fp_block_end(B, tid, w0, n_ranges, rows, parts + (size_t)(blockIdx.x % FP_SHARDS) * UVC_FRAGPROF_ROW);
 }
 
-// the copies of the row summed into the result: one lane per word
+// The copies of the row summed into the result: one lane per word.  Not uvc_launch_sum_fold: FP_SHARDS is a compile-time count, so the 16
+// loads of a lane are in flight together, and through the shared kernel's loop over a run-time count they wait one for the other -- 3 to
+// 8 us more per call on the 1 Mb x 300x tile (profiles/report_kernels_bench.json).
 __global__ void __launch_bounds__(256) k_fp_fold(const unsigned long long *parts, unsigned long long *out) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= UVC_FRAGPROF_ROW) return;

@@ -69,6 +69,9 @@ struct UvcScoreIn {
 // The streams and events of one accumulate (host-side aggregate): the handle's stream, the two side streams (NULL: everything on `s`) and
 // the events of the forks and joins between them (see uvc_launch_accumulate).
 struct UvcAccStreams { hipStream_t s, side, side3; hipEvent_t e_fork, e_join, e_fork2, e_join3, e_stat, e_alleles; };
+// elements of one tile of the reports' tile scan = threads of a block (uvc_launch_tile_sums)
+#define UVC_SCAN_TILE 256
+static inline int64_t uvc_scan_tiles(int64_t n) { return (n + UVC_SCAN_TILE - 1) / UVC_SCAN_TILE; }
 
 extern "C" {
 // ---- uvc_kernels_acc.hip ----
@@ -103,6 +106,17 @@ size_t uvc_score_stream_table_offset(int64_t npos_scored);
 void uvc_launch_check_presence(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
 void uvc_launch_block_stats(const RegionDev *R, const UvcParams *P, int64_t x0, int64_t n, int32_t *d_out, hipStream_t s);
 void uvc_launch_block_stats_windows(const RegionDev *R, const UvcParams *P, const long long *d_win, int n_win, int64_t n, int32_t *d_out, hipStream_t s);
+// ---- uvc_report_common.hip: the kernels several reports launch ----
+// the array scan (the block counts of the callable and the MSI call, the waves' row counts of the site call, the tile sums below): in
+// place, a[i] becomes the sum of a[0 .. i), a[n] -- one element behind the input -- the total (one block of 1 024 threads)
+void uvc_launch_block_scan(int *d_a, int n, hipStream_t s);
+// the tile scan of n values, d_out[i] = the sum of the values in front of i and d_out[n] their total, in three launches: tile_sums into
+// uvc_scan_tiles(n) + 1 ints, uvc_launch_block_scan over them, tile_prefix (d_out may be d_in).  chunks: 0 scans the values as they are,
+// 1 the 64-element chunks of each length, ceil(v / 64)
+void uvc_launch_tile_sums(const int32_t *d_in, int64_t n, int chunks, int32_t *d_tile_sums, hipStream_t s);
+void uvc_launch_tile_prefix(const int32_t *d_in, int n, int chunks, const int32_t *d_tile_pref, int32_t *d_out, hipStream_t s);
+// d_out[i] = the sum over `shards` copies of a row of `cells` words, laid one behind the other in d_parts
+void uvc_launch_sum_fold(const long long *d_parts, int shards, int cells, long long *d_out, hipStream_t s);
 // ---- uvc_coverage.hip, uvc_errprofile.hip: d_tab = the n_ranges + 1 rows of UvcRangeRow ----
 void uvc_launch_coverage(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const int32_t *thr, int n_thr, long long *d_out, long long *d_scratch, int64_t scratch_rows, hipStream_t s);
 const char *uvc_coverage_name(int id);
@@ -147,9 +161,6 @@ void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int
 void uvc_launch_callable_emit(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const unsigned char *d_mask, const int *d_blocks, UvcCallableRun *d_runs, hipStream_t s);
 int64_t uvc_callable_blocks(int64_t n_total);
 const char *uvc_callable_name(int bit);
-// the array scan of the reports (the block counts of uvc_launch_callable_count and of the MSI call, the tile sums of the read profile):
-// in place, a[i] becomes the sum of a[0 .. i), a[n] -- one element behind the input -- the total (one block of 1 024 threads)
-void uvc_launch_block_scan(int *d_a, int n, hipStream_t s);
 // ---- the scalar DEV functions of the scoring and accumulate kernels on their own, for tests: one thread per row of `in` (n rows of n_in
 // doubles; integer arguments travel as doubles, all below 2^31) writes a row of `out` (n_out doubles; integer results as doubles).  The op
 // fixes how many arguments a row holds and how many results it gives: a call with fewer, an unknown op or n < 1 launches nothing and

@@ -1,7 +1,7 @@
 // uvc_msi.hip -- uvcgpu_region_msi: the microsatellite loci of many ranges of the accumulated region, as the STR planes of UVC_F_RTR name
 // them, with the smallest depths along each tract and a length-shift histogram per evidence level from the device InDel allele rows
 // (the definitions are in uvcgpu.h, the row layout in include/uvc_msi.def).  The number of loci depends on the data: a count,
-// a scan and an ordered compaction as in uvc_callable.hip (whose scan kernel this file launches), then two passes over what was compacted.
+// a scan and an ordered compaction as in uvc_callable.hip, then two passes over what was compacted.
 //   k_msi_heads   lanes walk the ranges laid end to end by compact position, read the three STR planes and count the block's locus heads.
 //   (scan)        uvc_launch_block_scan: the exclusive prefix of the block counts, the number of loci behind them.
 //   k_msi_emit    the same walk; a head ranks itself (ballot and popcount in a wave, LDS across the four waves, a running base across the
@@ -15,8 +15,7 @@
 //                 sees tens of adds, so there is no LDS stage.
 // The kernels behind the scan read the number of loci from the device and leave what lies beyond `room` alone: the host learns the number
 // after everything has run, and a call whose buffer was too small runs again with a larger one.  Integer arithmetic only; the adds commute.
-#include "uvc_launch.h"
-#include "uvc_collectives.h"
+#include "uvc_report_dev.h"
 
 namespace {
 enum {
@@ -29,28 +28,17 @@ static_assert(MSI_N == UVC_NMSI, "include/uvc_msi.def and UvcMsiSection of uvcgp
 #define UVC_MSI(name, first, words) static_assert((int)MSI_##name == (int)UVC_MSI_##name, "uvc_msi.def order = UvcMsiSection order");
 #include "uvc_msi.def"
 #undef UVC_MSI
-constexpr int MSI_FIRST[UVC_NMSI + 1] = {
-#define UVC_MSI(name, first, words) first,
-#include "uvc_msi.def"
-#undef UVC_MSI
-    UVC_MSI_ROW };
-constexpr int MSI_WORDS[UVC_NMSI] = {
-#define UVC_MSI(name, first, words) words,
+constexpr UvcSection MSI_SECTIONS[UVC_NMSI] = {
+#define UVC_MSI(name, first, words) { #name, first, words },
 #include "uvc_msi.def"
 #undef UVC_MSI
 };
-constexpr bool msi_sections_tile_the_row() { for (int k = 0; k < UVC_NMSI; k++) if (MSI_FIRST[k] + MSI_WORDS[k] != MSI_FIRST[k + 1]) return false; return MSI_FIRST[0] == 0; }
-static_assert(msi_sections_tile_the_row(), "the sections of uvc_msi.def follow each other and fill UVC_MSI_ROW words");
-static_assert(MSI_FIRST[MSI_range] == 0 && MSI_FIRST[MSI_pos_beg] == 1 && MSI_FIRST[MSI_tracklen] == 2 && MSI_FIRST[MSI_unitlen] == 3 && MSI_FIRST[MSI_flags] == 4, "the header words k_msi_emit writes");
-static_assert(MSI_FIRST[MSI_depth] == UVC_MSI_DEPTH && MSI_WORDS[MSI_depth] == UVC_MSI_NLEVEL && MSI_FIRST[MSI_hist] == UVC_MSI_HIST && MSI_WORDS[MSI_hist] == UVC_MSI_NLEVEL * UVC_MSI_NBIN, "depth[4] and hist[4][13]");
+static_assert(uvc_sections_tile(MSI_SECTIONS, UVC_MSI_ROW), "the sections of uvc_msi.def follow each other and fill UVC_MSI_ROW words");
+#define MSI_W(section) (MSI_SECTIONS[MSI_##section].first)   // the first word of a section
+static_assert(MSI_W(range) == 0 && MSI_W(pos_beg) == 1 && MSI_W(tracklen) == 2 && MSI_W(unitlen) == 3 && MSI_W(flags) == 4, "the header words k_msi_emit writes");
+static_assert(MSI_W(depth) == UVC_MSI_DEPTH && MSI_SECTIONS[MSI_depth].words == UVC_MSI_NLEVEL && MSI_W(hist) == UVC_MSI_HIST && MSI_SECTIONS[MSI_hist].words == UVC_MSI_NLEVEL * UVC_MSI_NBIN, "depth[4] and hist[4][13]");
 static_assert(UVC_MSI_NBIN == 2 * UVC_MSI_MAXSHIFT + 1 && UVC_MSI_OTHER == 2 * UVC_MSI_MAXSHIFT, "twelve shift bins and OTHER");
 static_assert(sizeof(UvcMsiRequest) == 12, "the request goes into the kernel by value");
-
-const char *const MSI_NAMES[UVC_NMSI] = {
-#define UVC_MSI(name, first, words) #name,
-#include "uvc_msi.def"
-#undef UVC_MSI
-};
 
 #define MSI_STEPS 4
 #define MSI_TILE (256 * MSI_STEPS)   // compact positions of one block, as in uvc_callable.hip
@@ -85,7 +73,6 @@ __global__ void __launch_bounds__(256) k_msi_heads(RegionDev R, const UvcRangeRo
 
 __global__ void __launch_bounds__(256) k_msi_emit(RegionDev R, const UvcRangeRow *tab, int n_ranges, int n_total, UvcMsiRequest q, const int *block_off, int32_t *heads_out, int32_t *rows, int room) {
     __shared__ int wave_heads[4];
-    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
     const long long base = (long long)blockIdx.x * MSI_TILE;
     UvcRangeCursor g;
     int locus_base = block_off[blockIdx.x];   // the heads in front of this step's first position
@@ -98,22 +85,18 @@ __global__ void __launch_bounds__(256) k_msi_emit(RegionDev R, const UvcRangeRow
             x = g.x0 + (int)(i - g.first);
             head = msi_head(R, q, x, tl, ul);
         }
-        const unsigned long long m = __ballot(head);
-        if (lane == 0) wave_heads[wv] = __popcll(m);
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; w++) before += wave_heads[w];
-        const int idx = locus_base + before + __popcll(m & ((1ull << lane) - 1ull));   // the heads in front of this one
+        int step_heads;
+        const int idx = locus_base + head_rank(head, wave_heads, step_heads) - 1;   // (of a head) the heads in front of this one
         if (head && idx < room) {
             heads_out[idx] = x;
             int32_t *row = rows + (size_t)idx * UVC_MSI_ROW;
             // the tract holds the first or the last reference base of the region (position npos - 1 has none): the cut may have truncated it
             const bool edge = (x == 0 || (int64_t)x + tl >= R.npos - 1);
-            row[MSI_FIRST[MSI_range]] = g.rid; row[MSI_FIRST[MSI_pos_beg]] = R.beg + x; row[MSI_FIRST[MSI_tracklen]] = tl; row[MSI_FIRST[MSI_unitlen]] = ul;
-            row[MSI_FIRST[MSI_flags]] = edge ? UVC_MSI_EDGE : 0;
+            row[MSI_W(range)] = g.rid; row[MSI_W(pos_beg)] = R.beg + x; row[MSI_W(tracklen)] = tl; row[MSI_W(unitlen)] = ul;
+            row[MSI_W(flags)] = edge ? UVC_MSI_EDGE : 0;
         }
-        locus_base += wave_heads[0] + wave_heads[1] + wave_heads[2] + wave_heads[3];
-        __syncthreads();
+        locus_base += step_heads;
+        __syncthreads();   // wave_heads is written again in the next step
     }
 }
 
@@ -124,8 +107,8 @@ __global__ void __launch_bounds__(256) k_msi_depth(RegionDev R, const int *n_loc
     const int waves = (int)gridDim.x * 4;
     for (int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); i < n; i += waves) {   // (i is wave-uniform)
         int32_t *row = rows + (size_t)i * UVC_MSI_ROW;
-        if (row[MSI_FIRST[MSI_flags]] & UVC_MSI_EDGE) continue;
-        const int64_t h = row[MSI_FIRST[MSI_pos_beg]] - R.beg, end = lmin(h + row[MSI_FIRST[MSI_tracklen]], R.npos);   // (a track ends at the last reference base at the latest)
+        if (row[MSI_W(flags)] & UVC_MSI_EDGE) continue;
+        const int64_t h = row[MSI_W(pos_beg)] - R.beg, end = lmin(h + row[MSI_W(tracklen)], R.npos);   // (a track ends at the last reference base at the latest)
         int d0 = INT32_MAX, d1 = INT32_MAX, d2 = INT32_MAX, d3 = INT32_MAX;
         for (int64_t x = h + lane; x < end; x += 64) {
             d0 = imin(d0, cov_FRAG(R, UVC_FRAG_bDP, x));
@@ -140,8 +123,7 @@ __global__ void __launch_bounds__(256) k_msi_depth(RegionDev R, const int *n_loc
 
 // the index of head h in the ascending list, -1 when it is not there
 DEV int msi_find(const int32_t *heads, int n, int h) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (heads[mid] < h) lo = mid + 1; else hi = mid; }
+    const int lo = first_ge(heads, n, h);
     return (lo < n && heads[lo] == h) ? lo : -1;
 }
 
@@ -164,12 +146,12 @@ __global__ void __launch_bounds__(256) k_msi_bin(RegionDev R, const int *n_loci_
     if (ins && idx < 0 && g.x > 0) {   // behind the last unit of the locus in front
         h = RTRP(R, UVC_RTR_begpos, g.x - 1);
         idx = msi_find(heads, n, h);
-        if (idx >= 0 && h + rows[(size_t)idx * UVC_MSI_ROW + MSI_FIRST[MSI_tracklen]] != g.x) idx = -1;
+        if (idx >= 0 && h + rows[(size_t)idx * UVC_MSI_ROW + MSI_W(tracklen)] != g.x) idx = -1;
     }
     if (idx < 0) return;
     int32_t *row = rows + (size_t)idx * UVC_MSI_ROW;
-    if (row[MSI_FIRST[MSI_flags]] & UVC_MSI_EDGE) return;
-    const int tl = row[MSI_FIRST[MSI_tracklen]], ul = row[MSI_FIRST[MSI_unitlen]];
+    if (row[MSI_W(flags)] & UVC_MSI_EDGE) return;
+    const int tl = row[MSI_W(tracklen)], ul = row[MSI_W(unitlen)];
     bool unit_shift = (g.len % ul == 0);
     if (del) unit_shift = unit_shift && ((int64_t)g.x + g.len <= (int64_t)h + tl);
     else {
@@ -184,7 +166,7 @@ __global__ void __launch_bounds__(256) k_msi_bin(RegionDev R, const int *n_loci_
 }
 }   // namespace
 
-extern "C" const char *uvc_msi_name(int id) { return (id >= 0 && id < UVC_NMSI) ? MSI_NAMES[id] : nullptr; }
+extern "C" const char *uvc_msi_name(int id) { return (id >= 0 && id < UVC_NMSI) ? MSI_SECTIONS[id].name : nullptr; }
 extern "C" int64_t uvc_msi_blocks(int64_t n_total) { return (n_total + MSI_TILE - 1) / MSI_TILE; }
 extern "C" void uvc_launch_msi(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcMsiRequest *req, int *d_blocks, int32_t *d_heads, int32_t *d_rows, int64_t room, hipStream_t s) {
     if (n_ranges <= 0 || n_total <= 0) return;

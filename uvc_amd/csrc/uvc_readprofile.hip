@@ -3,7 +3,7 @@
 // (RawReads), RegionDev::bases / bq / cigars and the reference symbols.
 //
 // The work is proportional to read bases and is split by read base, never by read: a CHUNK is 64 consecutive query indices of one
-// alignment, a wave takes a run of consecutive chunks (k_rp_chunks: the exclusive prefix of ceil(l_qseq / 64) over the alignments, a
+// alignment, a wave takes a run of consecutive chunks (uvc_launch_tile_prefix: the exclusive prefix of ceil(l_qseq / 64) over the alignments, a
 // three-launch tile scan), finds the alignment of its first chunk by one binary search and moves on from there.  A 150-base read is three
 // chunks, a 15 kb read 235; both load the machine alike.  Everything about the alignment is wave-uniform (scalar loads).
 //
@@ -27,10 +27,9 @@
 //   whole chunk of a long read meets on one word per kind: such a chunk counts each kind by a ballot and one lane adds.
 //   Q, SUB and the counters: a wave of one read meets on a handful of words (an instrument reports 4-8 distinct qualities), so equal
 //   keys are merged in the wave first -- one ballot per distinct key, the first lane of each adds the popcount.
-// At the end a block adds its non-zero words to one of `shards` copies of the row with 64-bit vector atomics; k_rp_fold sums the copies.
+// At the end a block adds its non-zero words to one of `shards` copies of the row with 64-bit vector atomics; uvc_launch_sum_fold sums the copies.
 // Integer adds only: their order does not show, two calls return the same bits.
-#include "uvc_launch.h"
-#include "uvc_collectives.h"
+#include "uvc_report_dev.h"
 
 #include <algorithm>
 
@@ -45,14 +44,12 @@ static_assert(RPROW_N == UVC_NREADPROF, "include/uvc_readprofile.def and UvcRead
 #define UVC_READPROF(name, first, words) static_assert((int)RPROW_##name == (int)UVC_READPROF_##name, "uvc_readprofile.def order = UvcReadProfSection order");
 #include "uvc_readprofile.def"
 #undef UVC_READPROF
-struct RpSection { const char *name; int first, words; };
-constexpr RpSection RP_SECTIONS[UVC_NREADPROF] = {
+constexpr UvcSection RP_SECTIONS[UVC_NREADPROF] = {
 #define UVC_READPROF(name, first, words) { #name, first, words },
 #include "uvc_readprofile.def"
 #undef UVC_READPROF
 };
-constexpr bool rp_sections_abut(int k) { return k == 0 ? RP_SECTIONS[0].first == 0 : (RP_SECTIONS[k].first == RP_SECTIONS[k - 1].first + RP_SECTIONS[k - 1].words && rp_sections_abut(k - 1)); }
-static_assert(rp_sections_abut(UVC_NREADPROF - 1) && RP_SECTIONS[UVC_NREADPROF - 1].first + RP_SECTIONS[UVC_NREADPROF - 1].words == UVC_READPROF_ROW, "the sections of uvc_readprofile.def tile the row");
+static_assert(uvc_sections_tile(RP_SECTIONS, UVC_READPROF_ROW), "the sections of uvc_readprofile.def tile the row");
 static_assert(RP_SECTIONS[UVC_READPROF_Q].first == UVC_READPROF_Q_BINS && RP_SECTIONS[UVC_READPROF_Q].words == UVC_READPROF_NCLASS * UVC_READPROF_NQUAL * 2
               && RP_SECTIONS[UVC_READPROF_CYC].first == UVC_READPROF_CYC_BINS && RP_SECTIONS[UVC_READPROF_CYC].words == UVC_READPROF_NCLASS * UVC_READPROF_NCYCLE * UVC_READPROF_NKIND
               && RP_SECTIONS[UVC_READPROF_SUB].first == UVC_READPROF_SUB_BINS && RP_SECTIONS[UVC_READPROF_SUB].words == UVC_READPROF_NCLASS * 16
@@ -61,7 +58,7 @@ static_assert(RP_SECTIONS[UVC_READPROF_Q].first == UVC_READPROF_Q_BINS && RP_SEC
 
 #define RP_CELLS UVC_READPROF_ROW
 #define RP_MAX_SHARDS 16
-#define RP_TILE 256             // elements of one scan tile = threads of a block
+#define RP_TILE UVC_SCAN_TILE   // k_rp_status takes a tile of the depth scan: threads of a block
 #define RP_MIN_CHUNKS 8         // chunks a wave takes at least (one binary search per wave)
 #define RP_MAX_BLOCKS 1024      // four per CU: a block keeps its copy of the row over all of its chunks
 enum { RP_NO_REF = 0, RP_LOW_DEPTH = 1, RP_HIGH_ALT = 2, RP_CLEAN = 3, RP_IN_RANGE = 4 };   // the status byte
@@ -72,50 +69,9 @@ static_assert(UVC_READPROF_positions_low_depth == UVC_READPROF_positions_no_ref 
 
 const char *const RP_CLASS_NAMES[UVC_READPROF_NCLASS] = { "R1_fwd", "R1_rev", "R2_fwd", "R2_rev" };
 
-DEV void rp_lds_add(unsigned *p, unsigned v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// a word every lane of the wave would add 1 to: the lanes with `on` are counted by a ballot, the wave's first lane adds the count
-DEV void rp_count_lanes(unsigned *p, bool on, int lane) {
-    const unsigned long long m = __ballot(on);
-    if (lane == 0 && m) rp_lds_add(p, (unsigned)__popcll(m));
-}
-// tab[key] += 1 for every lane with `on`, equal keys merged first: one round per distinct key among the lanes, its first lane adds the
-// popcount.  Called by the whole wave.
-DEV void rp_merge_add(unsigned *tab, int key, bool on, int lane) {
-    unsigned long long left = __ballot(on);
-    while (left) {
-        const int lead = __ffsll((long long)left) - 1;
-        const int k = __shfl(key, lead);
-        const unsigned long long same = __ballot(on && key == k);
-        if (lane == lead) rp_lds_add(tab + k, (unsigned)__popcll(same));
-        left &= ~same;
-    }
-}
-
-// what a scan is over: the differences of the depth as they are, or the chunks of the alignments
-DEV int rp_scan_value(const int32_t *in, long long i, long long n, int chunks) {
-    if (i >= n) return 0;
-    const int v = in[i];
-    return chunks ? (v > 0 ? (v + 63) >> 6 : 0) : v;
-}
-__global__ void __launch_bounds__(RP_TILE) k_rp_tile_sums(const int32_t *in, long long n, int chunks, int32_t *tile_sums) {
-    __shared__ int sh_wave[RP_TILE / 64];
-    const int total = waves_sum<RP_TILE / 64>(wave_sum(rp_scan_value(in, (long long)blockIdx.x * RP_TILE + threadIdx.x, n, chunks)), sh_wave);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-// (the exclusive scan of the tile sums in place, their total behind them in entry n_tiles: uvc_launch_block_scan)
-// cpre[a] = the first chunk of alignment a; cpre[n_alns] = the number of chunks
-__global__ void __launch_bounds__(RP_TILE) k_rp_chunks(const int32_t *l_qseq, int n_alns, const int32_t *tile_pref, int32_t *cpre) {
-    __shared__ int sh_wave[RP_TILE / 64];
-    const long long i = (long long)blockIdx.x * RP_TILE + threadIdx.x;
-    const int v = rp_scan_value(l_qseq, i, n_alns, 1);
-    const int excl = block_excl<RP_TILE / 64>(v, sh_wave);
-    if (i < n_alns) cpre[i] = tile_pref[blockIdx.x] + excl;
-    if (i == n_alns - 1) cpre[n_alns] = tile_pref[blockIdx.x] + excl + v;
-}
-
 // is plane index x inside a range of the table (rows { x0, first compact position }, n_ranges + 1 of them)
 DEV bool rp_in_ranges(const UvcRangeRow *tab, int n_ranges, int x) {
-    int lo = 0, hi = n_ranges;   // the last range that begins at or in front of x
+    int lo = 0, hi = n_ranges;   // the last range that begins at or in front of x (last_le over a member of the rows: kept here, k_rp_status' text is the parent's)
     if (tab[0].x0 > x) return false;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].x0 <= x) lo = mid; else hi = mid; }
     return x - tab[lo].x0 < tab[lo + 1].first - tab[lo].first;
@@ -143,14 +99,10 @@ __global__ void __launch_bounds__(RP_TILE) k_rp_status(RegionDev R, int32_t *dx,
         status[x] = (uint8_t)(st | (in ? RP_IN_RANGE : 0));
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) rp_count_lanes(cnt + k, in && st == k, lane);
+    for (int k = 0; k < 4; k++) count_lanes(cnt + k, in && st == k, lane);
     __syncthreads();
     if (tid < 4 && cnt[tid]) atomicAdd(parts + (size_t)(blockIdx.x % (unsigned)shards) * RP_CELLS + RP_WORD(positions_no_ref) + tid, (unsigned long long)cnt[tid]);
 }
-
-DEV bool rp_op_query(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF || op == C_INS || op == C_SOFT_CLIP; }
-DEV bool rp_op_ref(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF || op == C_DEL || op == C_REF_SKIP; }
-DEV bool rp_op_aligned(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF; }
 
 // BIN = false: pass one (dx, X); BIN = true: pass two (status -> parts)
 template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev R, RawReads W, const int32_t *cpre, int min_mapq, int32_t *dx, int32_t *X, const uint8_t *status,
@@ -166,8 +118,7 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
     const int wv = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (tid >> 6));
     const long long c0 = (long long)wv * per, c1 = (c0 + per < total ? c0 + per : total);
     if (c0 < c1) {
-        int a = 0;
-        { int hi = n_alns; while (hi - a > 1) { const int mid = (a + hi) >> 1; if (cpre[mid] <= c0) a = mid; else hi = mid; } }   // the last alignment with cpre <= c0: it holds chunk c0
+        int a = last_le(cpre, 0, n_alns, c0);   // the last alignment with cpre <= c0: it holds chunk c0
         for (long long c = c0; c < c1; c++) {
             while (c >= cpre[a + 1]) a++;   // (c < total = cpre[n_alns]: a + 1 <= n_alns)
             const int mapq = (int)W.mapq[a];
@@ -185,11 +136,11 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
                 const int j = b0 + lane;
                 const uint32_t cg = (j < nc ? R.cigars[co + j] : (uint32_t)C_PAD);
                 const int op = cig_op(cg), len = cig_len(cg);
-                const int ql = rp_op_query(op) ? len : 0, rl = rp_op_ref(op) ? len : 0;
+                const int ql = cig_query(op) ? len : 0, rl = cig_ref(op) ? len : 0;
                 const int qi = wave_incl(ql), ri = wave_incl(rl);
                 const int qs = qcur + qi - ql, ps = pcur + ri - rl;   // the op's first query index and reference coordinate
                 if (!BIN) {
-                    if (rp_op_aligned(op) && len > 0 && qs >= q0 && qs < q0 + 64) {   // the run's ends, clipped to the region
+                    if (cig_aligned(op) && len > 0 && qs >= q0 && qs < q0 + 64) {   // the run's ends, clipped to the region
                         const long long lo = (long long)ps - R.beg > 0 ? (long long)ps - R.beg : 0, hi = (long long)ps + len - R.beg < npos ? (long long)ps + len - R.beg : npos;
                         if (lo < hi) { atomicAdd(dx + lo, 1); if (hi < npos) atomicAdd(dx + hi, -1); }
                     }
@@ -198,7 +149,7 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
                     const long long x = (long long)ps - R.beg;
                     if (qe >= q0 && qe < q0 + 64 && qe < L && x >= 0 && x < npos && (status[x] & RP_IN_RANGE)) {
                         const int cyc = rev ? L - 1 - qe : qe;
-                        rp_lds_add(prof + RP_WORD(CYC) + (cls * UVC_READPROF_NCYCLE + imin(cyc, UVC_READPROF_NCYCLE - 1)) * UVC_READPROF_NKIND + RP_K_DEL, 1u);
+                        lds_add(prof + RP_WORD(CYC) + (cls * UVC_READPROF_NCYCLE + imin(cyc, UVC_READPROF_NCYCLE - 1)) * UVC_READPROF_NKIND + RP_K_DEL, 1u);
                     }
                 }
                 unsigned long long m = __ballot(ql > 0 && qs < q0 + 64 && qs + ql > q0);
@@ -206,7 +157,7 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
                     const int l = __ffsll((long long)m) - 1;
                     m &= m - 1;
                     const int o = __shfl(op, l), s = __shfl(qs, l), n = __shfl(ql, l), pp = __shfl(ps, l);
-                    if (have && q >= s && q - s < n) { my_op = o; my_p = rp_op_aligned(o) ? pp + (q - s) : imax(pos, pp - 1); }
+                    if (have && q >= s && q - s < n) { my_op = o; my_p = cig_aligned(o) ? pp + (q - s) : imax(pos, pp - 1); }
                 }
                 qcur += __shfl(qi, 63); pcur += __shfl(ri, 63);
             }
@@ -214,7 +165,7 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
             const long long x = (long long)my_p - R.beg;
             const bool inb = act && x >= 0 && x < npos;
             if (!BIN) {
-                if (inb && rp_op_aligned(my_op)) {
+                if (inb && cig_aligned(my_op)) {
                     const int base = (int)R.bases[so + q];
                     if (base > UVC_BASE_T) { atomicAdd(dx + x, -1); if (x + 1 < npos) atomicAdd(dx + x + 1, 1); }
                     else { const int ref = (int)R.refsym[x]; if (ref <= UVC_BASE_T && ref != base) atomicAdd(X + x, 1); }
@@ -224,31 +175,31 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
             const int sb = inb ? (int)status[x] : 0;
             const bool inr = (sb & RP_IN_RANGE) != 0;
             const int st = sb & 3;
-            const bool aligned = inr && rp_op_aligned(my_op);
-            if (!counted) { rp_count_lanes(prof + RP_WORD(bases_low_mapq), aligned, lane); continue; }   // (wave-uniform)
+            const bool aligned = inr && cig_aligned(my_op);
+            if (!counted) { count_lanes(prof + RP_WORD(bases_low_mapq), aligned, lane); continue; }   // (wave-uniform)
             const int v = inr ? (int)R.bq[so + q] : 0, base = v & 0xFF, qb = imin(v >> 8, UVC_READPROF_NQUAL - 1);
             const bool no_ref = aligned && st == RP_NO_REF, isn = aligned && !no_ref && base > UVC_BASE_T;
             const bool clean = aligned && !isn && st == RP_CLEAN;
-            rp_count_lanes(prof + RP_WORD(bases_no_ref), no_ref, lane);
-            rp_count_lanes(prof + RP_WORD(bases_n), isn, lane);
-            rp_count_lanes(prof + RP_WORD(bases_low_depth), aligned && !isn && st == RP_LOW_DEPTH, lane);
-            rp_count_lanes(prof + RP_WORD(bases_high_alt), aligned && !isn && st == RP_HIGH_ALT, lane);
-            rp_count_lanes(prof + RP_WORD(bases_clean), clean, lane);
+            count_lanes(prof + RP_WORD(bases_no_ref), no_ref, lane);
+            count_lanes(prof + RP_WORD(bases_n), isn, lane);
+            count_lanes(prof + RP_WORD(bases_low_depth), aligned && !isn && st == RP_LOW_DEPTH, lane);
+            count_lanes(prof + RP_WORD(bases_high_alt), aligned && !isn && st == RP_HIGH_ALT, lane);
+            count_lanes(prof + RP_WORD(bases_clean), clean, lane);
             const int ref = clean ? (int)R.refsym[x] : 0;   // (a clean position has an A/C/G/T reference symbol)
             const int mis = (clean && base != ref) ? 1 : 0;
-            rp_merge_add(prof + RP_WORD(Q) + cls * UVC_READPROF_NQUAL * 2, qb * 2 + mis, clean, lane);
-            rp_merge_add(prof + RP_WORD(SUB) + cls * 16, ref * 4 + (base & 3), clean, lane);
+            merge_add(prof + RP_WORD(Q) + cls * UVC_READPROF_NQUAL * 2, qb * 2 + mis, clean, lane);
+            merge_add(prof + RP_WORD(SUB) + cls * 16, ref * 4 + (base & 3), clean, lane);
             const int kind = clean ? mis : (inr && my_op == C_INS) ? RP_K_INS : (inr && my_op == C_SOFT_CLIP) ? RP_K_CLIP : -1;
             const int cyc = rev ? L - 1 - q : q;
             unsigned *row = prof + RP_WORD(CYC) + cls * UVC_READPROF_NCYCLE * UVC_READPROF_NKIND;
             const int last = (q0 + 63 < L - 1 ? q0 + 63 : L - 1);   // the chunk's last query index
             if ((rev ? L - 1 - last : q0) >= UVC_READPROF_NCYCLE - 1) {   // (wave-uniform) the whole chunk lies in the last cycle bin
                 unsigned *cell = row + (UVC_READPROF_NCYCLE - 1) * UVC_READPROF_NKIND;
-                rp_count_lanes(cell + RP_K_MATCH, kind == RP_K_MATCH, lane);
-                rp_count_lanes(cell + RP_K_MISMATCH, kind == RP_K_MISMATCH, lane);
-                rp_count_lanes(cell + RP_K_INS, kind == RP_K_INS, lane);
-                rp_count_lanes(cell + RP_K_CLIP, kind == RP_K_CLIP, lane);
-            } else if (kind >= 0) rp_lds_add(row + imin(cyc, UVC_READPROF_NCYCLE - 1) * UVC_READPROF_NKIND + kind, 1u);
+                count_lanes(cell + RP_K_MATCH, kind == RP_K_MATCH, lane);
+                count_lanes(cell + RP_K_MISMATCH, kind == RP_K_MISMATCH, lane);
+                count_lanes(cell + RP_K_INS, kind == RP_K_INS, lane);
+                count_lanes(cell + RP_K_CLIP, kind == RP_K_CLIP, lane);
+            } else if (kind >= 0) lds_add(row + imin(cyc, UVC_READPROF_NCYCLE - 1) * UVC_READPROF_NKIND + kind, 1u);
         }
     }
     if (BIN) {
@@ -258,23 +209,13 @@ template <bool BIN> __global__ void __launch_bounds__(256) k_rp_reads(RegionDev 
     }
 }
 
-// the copies of the row summed into the result: one lane per word
-__global__ void __launch_bounds__(256) k_rp_fold(const unsigned long long *parts, int shards, unsigned long long *out) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= RP_CELLS) return;
-    unsigned long long v = 0;
-    for (int s = 0; s < shards; s++) v += parts[(size_t)s * RP_CELLS + i];
-    out[i] = v;
-}
-
-long long rp_tiles(long long n) { return (n + RP_TILE - 1) / RP_TILE; }
 }   // namespace
 
 extern "C" const char *uvc_readprofile_class_name(int c) { return (c >= 0 && c < UVC_READPROF_NCLASS) ? RP_CLASS_NAMES[c] : nullptr; }
 // copies of the row a call adds into (the result itself is one more)
 extern "C" int64_t uvc_readprofile_copies(void) { return RP_MAX_SHARDS; }
 // ints of scratch: the first chunk of every alignment and their number, then the tile sums of the larger of the two scans and their total
-extern "C" int64_t uvc_readprofile_scratch_ints(int64_t n_alns, int64_t npos) { return (n_alns + 1) + rp_tiles(std::max<int64_t>(n_alns, npos)) + 1; }
+extern "C" int64_t uvc_readprofile_scratch_ints(int64_t n_alns, int64_t npos) { return (n_alns + 1) + uvc_scan_tiles(std::max<int64_t>(n_alns, npos)) + 1; }
 
 // The three stages of a call, each one entry of uvcgpu_region_kernel_times.  d_dx / d_x: npos ints each; d_status: npos bytes; d_parts:
 // uvc_readprofile_copies() rows, zero like d_dx / d_x when stage one starts (the caller fills them); d_scratch: uvc_readprofile_scratch_ints.
@@ -283,10 +224,10 @@ extern "C" void uvc_launch_readprofile_depth(const RegionDev *R, const RawReads 
     const int n = R->n_alns;
     if (n <= 0) return;
     int32_t *cpre = d_scratch, *tsum = d_scratch + n + 1;
-    const unsigned nt = (unsigned)rp_tiles(n);
-    hipLaunchKernelGGL(k_rp_tile_sums, dim3(nt), dim3(RP_TILE), 0, s, W->l_qseq, (long long)n, 1, tsum);
-    uvc_launch_block_scan(tsum, (int)nt, s);
-    hipLaunchKernelGGL(k_rp_chunks, dim3(nt), dim3(RP_TILE), 0, s, W->l_qseq, n, tsum, cpre);
+    // cpre[a] = the first chunk of alignment a, cpre[n] = the number of chunks: the tile scan of ceil(l_qseq / 64)
+    uvc_launch_tile_sums(W->l_qseq, n, 1, tsum, s);
+    uvc_launch_block_scan(tsum, (int)uvc_scan_tiles(n), s);
+    uvc_launch_tile_prefix(W->l_qseq, n, 1, tsum, cpre, s);
     const long long most = n_bases / 64 + n;   // no more chunks than this
     const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>(RP_MAX_BLOCKS, (most + 4 * RP_MIN_CHUNKS - 1) / (4 * RP_MIN_CHUNKS)));
     hipLaunchKernelGGL(k_rp_reads<false>, dim3(nb), dim3(256), 0, s, *R, *W, cpre, min_mapq, d_dx, d_x, (const uint8_t *)nullptr, 1, (unsigned long long *)nullptr);
@@ -295,8 +236,8 @@ extern "C" void uvc_launch_readprofile_status(const RegionDev *R, const UvcRange
                                               long long *d_parts, int32_t *d_scratch, hipStream_t s) {
     if (R->npos <= 0 || n_ranges <= 0) return;
     int32_t *tsum = d_scratch + (R->n_alns > 0 ? R->n_alns : 0) + 1;
-    const unsigned nt = (unsigned)rp_tiles(R->npos);
-    hipLaunchKernelGGL(k_rp_tile_sums, dim3(nt), dim3(RP_TILE), 0, s, d_dx, (long long)R->npos, 0, tsum);
+    const unsigned nt = (unsigned)uvc_scan_tiles(R->npos);
+    uvc_launch_tile_sums(d_dx, R->npos, 0, tsum, s);
     uvc_launch_block_scan(tsum, (int)nt, s);
     hipLaunchKernelGGL(k_rp_status, dim3(nt), dim3(RP_TILE), 0, s, *R, d_dx, d_x, tsum, d_tab, n_ranges, min_depth, max_alt_permille, d_status, RP_MAX_SHARDS, (unsigned long long *)d_parts);
 }
@@ -307,5 +248,5 @@ extern "C" void uvc_launch_readprofile_bin(const RegionDev *R, const RawReads *W
         const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>(RP_MAX_BLOCKS, (most + 4 * RP_MIN_CHUNKS - 1) / (4 * RP_MIN_CHUNKS)));
         hipLaunchKernelGGL(k_rp_reads<true>, dim3(nb), dim3(256), 0, s, *R, *W, d_scratch, min_mapq, (int32_t *)nullptr, (int32_t *)nullptr, d_status, RP_MAX_SHARDS, (unsigned long long *)d_parts);
     }
-    hipLaunchKernelGGL(k_rp_fold, dim3((unsigned)((RP_CELLS + 255) / 256)), dim3(256), 0, s, (const unsigned long long *)d_parts, RP_MAX_SHARDS, (unsigned long long *)d_out);
+    uvc_launch_sum_fold(d_parts, RP_MAX_SHARDS, RP_CELLS, d_out, s);
 }

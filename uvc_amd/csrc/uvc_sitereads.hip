@@ -9,7 +9,7 @@
 //                give the first candidate site and the number of candidates, 0 for an alignment that is not counted; the block's sum is
 //                the tile sum of the scan, and one 64-bit add per tile keeps the true total (the 32-bit scan is refused above 2^31 - 1).
 //   (uvc_launch_block_scan over the tile sums)
-//   k_sr_prefix  ipre[a] = the first item of alignment a, ipre[n_alns] = the number of items (the k_rp_tile_sums / k_rp_chunks pattern).
+//   (uvc_launch_tile_prefix, in place: ipre[a] = the first item of alignment a, ipre[n_alns] = the number of items)
 //   k_sr_items<false>  the COUNT pass.  A wave takes a run of consecutive items, whole 64-item steps; two wave-uniform binary searches in
 //                ipre give the alignments of its first and last item, and a lane finds the alignment of its own item between the two.  A
 //                lane walks its alignment's CIGAR to the op that holds the site and looks one step further for the events anchored there.
@@ -21,26 +21,18 @@
 //                the kept rows of the earlier steps and a ballot over the lower lanes -- item order, which is (read, site) order.  A row
 //                leaves as two 16-byte vector stores.
 // Integer adds only, no LDS atomics, no scratch memory; the order of the rows depends on no atomic, two calls return the same bytes.
-#include "uvc_launch.h"
-#include "uvc_collectives.h"
+#include "uvc_report_dev.h"
 
 #include <algorithm>
 
 namespace {
-#define SR_TILE 256             // alignments of one scan tile = threads of a block
+#define SR_TILE UVC_SCAN_TILE   // alignments of one scan tile = threads of a block
 #define SR_LDS_SITES 4096       // a list this long or shorter is searched in LDS (16 KiB)
 #define SR_SPAN_BLOCKS 1024     // k_sr_span's blocks at most: each stages the list once and takes every SR_SPAN_BLOCKS-th tile
 #define SR_MAX_BLOCKS 1024      // k_sr_items' blocks at most, four waves each
 
 const char *const SR_KIND_NAMES[UVC_SITEREAD_NKIND] = { "A", "C", "G", "T", "N", "DEL" };
 static_assert(sizeof(UvcSiteRead) == 32 && UVC_SITEREAD_NCOL == 8, "a row is eight int32, a site has eight counts");
-
-// the first index whose site is >= x (n when there is none)
-DEV int sr_lower_bound(const int32_t *sites, int n, int x) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (sites[mid] < x) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 
 // first[a], cnt[a]: the first candidate site of alignment a and the number of candidates; tile_sums[t]: the candidates of tile t; total:
 // their 64-bit sum over all tiles (zero when the kernel starts)
@@ -56,32 +48,14 @@ template <bool LDS> __global__ void __launch_bounds__(SR_TILE) k_sr_span(RawRead
         const int a = t * SR_TILE + tid;
         int lo = 0, c = 0;
         if (a < n_alns && (int)W.mapq[a] >= min_mapq && W.l_qseq[a] > 0) {
-            lo = sr_lower_bound(list, n_sites, W.pos[a]);
-            c = sr_lower_bound(list, n_sites, W.endpos[a]) - lo;   // (endpos is behind the last reference position of the alignment: c >= 0)
+            lo = first_ge(list, n_sites, W.pos[a]);
+            c = first_ge(list, n_sites, W.endpos[a]) - lo;   // (endpos is behind the last reference position of the alignment: c >= 0)
         }
         if (a < n_alns) { first[a] = lo; cnt[a] = c; }
         const long long sum = waves_sum<SR_TILE / 64>(wave_sum((long long)c), sh_wave);
         if (tid == 0) { tile_sums[t] = (int32_t)sum; if (sum) atomicAdd(total, (unsigned long long)sum); }
         __syncthreads();   // sh_wave is written again in the next round
     }
-}
-// (the exclusive scan of the tile sums in place: uvc_launch_block_scan)
-// in place: cnt[a] becomes the first item of alignment a, entry n_alns the number of items
-__global__ void __launch_bounds__(SR_TILE) k_sr_prefix(int n_alns, const int32_t *tile_pref, int32_t *ipre) {
-    __shared__ int sh_wave[SR_TILE / 64];
-    const int i = (int)blockIdx.x * SR_TILE + (int)threadIdx.x;
-    const int v = (i < n_alns ? ipre[i] : 0);
-    const int excl = block_excl<SR_TILE / 64>(v, sh_wave);
-    if (i < n_alns) ipre[i] = tile_pref[blockIdx.x] + excl;
-    if (i == n_alns - 1) ipre[n_alns] = tile_pref[blockIdx.x] + excl + v;
-}
-
-DEV bool sr_op_query(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF || op == C_INS || op == C_SOFT_CLIP; }
-DEV bool sr_op_ref(int op) { return op == C_MATCH || op == C_EQUAL || op == C_DIFF || op == C_DEL || op == C_REF_SKIP; }
-// the last alignment in [lo, hi) whose first item is <= i: it holds item i (an alignment without items shares its entry with its successor)
-DEV int sr_aln_of(const int32_t *ipre, int lo, int hi, int i) {
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ipre[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
 }
 
 // WRITE = false: counts and wave_rows[wave] = the kept rows of the wave's run; WRITE = true: wave_rows holds the exclusive prefix, the rows
@@ -98,7 +72,8 @@ template <bool WRITE> __global__ void __launch_bounds__(256) k_sr_items(RegionDe
     const long long i0 = (long long)wv * per, i1 = (i0 + per < total ? i0 + per : total);
     int kept = WRITE ? wave_rows[wv] : 0;   // WRITE: the rank of the next kept row
     if (i0 < i1) {
-        const int a_lo = sr_aln_of(ipre, 0, n_alns, (int)i0), a_hi = sr_aln_of(ipre, a_lo, n_alns, (int)(i1 - 1));
+        // the last alignment whose first item is <= i holds item i (an alignment without items shares its entry with its successor)
+        const int a_lo = last_le(ipre, 0, n_alns, (int)i0), a_hi = last_le(ipre, a_lo, n_alns, (int)(i1 - 1));
         // the walk of this lane: the alignment it is in, the op it stands in front of, that op's first query index and reference coordinate
         int cur = -1, j = 0, q = 0, p = 0, nc = 0, L = 0;
         long long so = 0, co = 0;
@@ -108,7 +83,7 @@ template <bool WRITE> __global__ void __launch_bounds__(256) k_sr_items(RegionDe
             bool obs = false, keep = false;
             int a = 0, si = 0, kind = 0, qi = 0, qual = 0, ins_q = -1, ins_len = 0, del_len = 0;
             if (have) {
-                a = sr_aln_of(ipre, a_lo, a_hi + 1, i);
+                a = last_le(ipre, a_lo, a_hi + 1, i);
                 si = first[a] + (i - ipre[a]);
                 const int s = sites[si];
                 if (a != cur) { cur = a; j = 0; q = 0; p = W.pos[a]; nc = W.n_cigar[a]; L = W.l_qseq[a]; so = W.seq_off[a]; co = W.cigar_off[a]; }
@@ -116,9 +91,9 @@ template <bool WRITE> __global__ void __launch_bounds__(256) k_sr_items(RegionDe
                 for (; j < nc; j++) {   // to the op that holds s: s >= p here, the sites of an alignment ascend
                     const uint32_t cg = R.cigars[co + j];
                     op = cig_op(cg); len = cig_len(cg);
-                    const int rl = sr_op_ref(op) ? len : 0;
+                    const int rl = cig_ref(op) ? len : 0;
                     if (s - p < rl) break;
-                    p += rl; q += sr_op_query(op) ? len : 0;
+                    p += rl; q += cig_query(op) ? len : 0;
                 }
                 if (j < nc && op != C_REF_SKIP) {
                     obs = true;
@@ -167,7 +142,6 @@ template <bool WRITE> __global__ void __launch_bounds__(256) k_sr_items(RegionDe
     if (!WRITE && lane == 0) wave_rows[wv] = kept;
 }
 
-int sr_tiles(int64_t n_alns) { return (int)((n_alns + SR_TILE - 1) / SR_TILE); }
 // the blocks of the item passes: no more waves than 64-item steps of the most items the call can have
 int sr_item_blocks(int64_t n_alns, int64_t n_sites) {
     const double most = (double)n_alns * (double)n_sites;
@@ -179,7 +153,7 @@ extern "C" const char *uvc_sitereads_kind_name(int k) { return (k >= 0 && k < UV
 // ints of scratch of a call: [first candidate site per alignment] [first item per alignment, their number] [tile sums, their total]
 // [kept rows per wave, their total]; two more for the 64-bit number of items in front of them all
 extern "C" int64_t uvc_sitereads_scratch_ints(int64_t n_alns, int64_t n_sites) {
-    return 2 + n_alns + (n_alns + 1) + (sr_tiles(n_alns) + 1) + ((int64_t)sr_item_blocks(n_alns, n_sites) * 4 + 1);
+    return 2 + n_alns + (n_alns + 1) + (uvc_scan_tiles(n_alns) + 1) + ((int64_t)sr_item_blocks(n_alns, n_sites) * 4 + 1);
 }
 // where the host reads: the 64-bit number of items (scratch[0..1]) and the number of kept rows
 extern "C" int64_t uvc_sitereads_rows_at(int64_t n_alns, int64_t n_sites) { return uvc_sitereads_scratch_ints(n_alns, n_sites) - 1; }
@@ -188,14 +162,14 @@ extern "C" int64_t uvc_sitereads_rows_at(int64_t n_alns, int64_t n_sites) { retu
 extern "C" void uvc_launch_sitereads_count(const RegionDev *R, const RawReads *W, const int32_t *d_sites, int n_sites, const UvcSiteReadsRequest *req, int32_t *d_counts, int32_t *d_scratch, hipStream_t s) {
     const int n = R->n_alns;
     if (n <= 0 || n_sites <= 0) return;
-    const int nt = sr_tiles(n), nb = sr_item_blocks(n, n_sites);
+    const int nt = (int)uvc_scan_tiles(n), nb = sr_item_blocks(n, n_sites);
     unsigned long long *total = (unsigned long long *)d_scratch;
     int32_t *first = d_scratch + 2, *ipre = first + n, *tsum = ipre + n + 1, *wrows = tsum + nt + 1;
     const unsigned sb = (unsigned)std::min(nt, SR_SPAN_BLOCKS);
     if (n_sites <= SR_LDS_SITES) hipLaunchKernelGGL(k_sr_span<true>, dim3(sb), dim3(SR_TILE), 0, s, *W, n, d_sites, n_sites, req->min_mapq, first, ipre, tsum, total);
     else hipLaunchKernelGGL(k_sr_span<false>, dim3(sb), dim3(SR_TILE), 0, s, *W, n, d_sites, n_sites, req->min_mapq, first, ipre, tsum, total);
     uvc_launch_block_scan(tsum, nt, s);
-    hipLaunchKernelGGL(k_sr_prefix, dim3((unsigned)nt), dim3(SR_TILE), 0, s, n, tsum, ipre);
+    uvc_launch_tile_prefix(ipre, n, 0, tsum, ipre, s);
     hipLaunchKernelGGL(k_sr_items<false>, dim3((unsigned)nb), dim3(256), 0, s, *R, *W, d_sites, first, ipre, req->alt_only, total, d_counts, wrows, (UvcSiteRead *)nullptr);
     uvc_launch_block_scan(wrows, nb * 4, s);
 }
@@ -203,7 +177,7 @@ extern "C" void uvc_launch_sitereads_count(const RegionDev *R, const RawReads *W
 extern "C" void uvc_launch_sitereads_write(const RegionDev *R, const RawReads *W, const int32_t *d_sites, int n_sites, const UvcSiteReadsRequest *req, int32_t *d_scratch, UvcSiteRead *d_rows, hipStream_t s) {
     const int n = R->n_alns;
     if (n <= 0 || n_sites <= 0) return;
-    const int nt = sr_tiles(n), nb = sr_item_blocks(n, n_sites);
+    const int nt = (int)uvc_scan_tiles(n), nb = sr_item_blocks(n, n_sites);
     int32_t *first = d_scratch + 2, *ipre = first + n, *wrows = ipre + n + 1 + nt + 1;   // (the layout of uvc_launch_sitereads_count)
     hipLaunchKernelGGL(k_sr_items<true>, dim3((unsigned)nb), dim3(256), 0, s, *R, *W, d_sites, first, ipre, req->alt_only, (const unsigned long long *)d_scratch, (int32_t *)nullptr, wrows, d_rows);
 }
