@@ -34,7 +34,7 @@
 //   k_duplex(_d)     per (duplex family, position)  generic form / from the digest             main.hpp:3523-3550
 //   k_p5b            per (position, strand)  bucket -> quality for family consensus           main.hpp:3552-3591
 //   k_gap_keys/alleles/rows  per (family, InDel position)  the allele-keyed counters of the InDel symbols   main.hpp:2710-2717, 3196-3546
-// uvc_launch_accumulate at the end of the file orders them on two streams.
+// uvc_launch_accumulate at the end of the file orders them on three streams (the dependency table in front of it).
 // The reference rules that several of them share (pair consensus, assay predicates, ...) stand once in uvc_rules.h; record words and flag bits go by the names of uvc_device.h.
 #include "uvc_launch.h"
 #include "uvc_collectives.h"
@@ -3860,6 +3860,40 @@ static void launch_p2_fast(const char *kname, const AccForms &F, const RegionDev
     else TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, false>), dim3(nwin), dim3(256), 0, s, *R, *P));
 }
 
+// The launches of one accumulate and what orders them (the same table: DESIGN 6-r7).  "reads": what another kernel of the accumulate writes;
+// the reads' columns, the lists of set_reads and the region tracks are complete before the first launch.  Streams: M = the handle's stream,
+// S2 = side, S3 = side3; without side streams everything is on M and the order of the launches below is the order of the rows.  An edge is
+// either stream order or the event named in brackets.
+//  #  launch                          on  reads (writer)                                            writes
+//  1  k_win_index lists 1-4, 7        M   --                                                        window index of the work list / the generic units
+//  2  k_prep_sums                     M   index 1-4 (1)                                             PREP: plain stores into zeroed planes
+//  3  k_prep_slow                     S2  -- ; its atomics must follow the plain stores of 2        PREP (atomics), fragment event lists, clip events
+//                                         [e_fork recorded behind 2]
+//  4  k_prep_scan / k_prep_fast       M   index 1-4 (1); atomics behind the stores of 2             PREP (atomics), fragment event lists, clip events
+//  5  k_thres                         M   PREP (2, 3 [e_join], 4)                                   THRES, RTR.indelphred
+//     -- fork [e_fork]: S2 and S3 behind 5 --
+//  6  k_p2_slow<true>  (walk)         S2  RTR.indelphred, THRES (5)                                 P2 items of the InDel reads
+//  7  k_p2_slow<false> (table)        S3  RTR.indelphred (5)                                        contribution table, gap events
+//  8  k_fragstat_fast                 S3  fragment event lists (3, 4)                               ffast / ffast_u (whole records), n_cov / n_near, overflow list
+//  9  k_win_index lists 5-6           S3  ffast.beg (8)                                             window index of the fragments
+// 10  k_fragstat_sweep, sweep list    S3  table (7); behind the record stores of 8                  n_cov / n_near of frags and ffast
+// 11  k_fragstat_sweep, overflow      S3  overflow list and count (8), table (7)                    n_cov / n_near of frags and ffast
+// 12  k_frag_sums                     S3  ffast with n_cov / n_near (8, 10, 11), index 5-6 (9)      fsum
+// 13  k_p2_fast, base symbols         M   THRES (5), index 1-4 (1)                                  SEG32 / SEG64 / BQSUM / VQ a*BQ* of the reference symbol: plain stores; mismatch queue
+// 14  k_p2_mism                       S2  mismatch queue (13 [e_fork2]); atomics behind the stores of 13   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
+// 15  k_p2_fast, LINK_M               M   THRES, RTR.indelphred (5)                                 the same planes of LINK_M: plain stores (no other writer of LINK_M cells before 18)
+//     -- join: M behind 14 [e_join] and 12 [e_join3]; S2 behind 12 [e_join3] --
+// 16  k_gap_keys .. k_gap_rows_fin    S2  gap events (7 [e_join3])                                  InDel allele tables; fam2_ins_len complete at [e_alleles]
+// 17  k_fam_stat                      S3  table (7), ffast_u (8)                                    unit records (fss) -> [e_stat]
+// 18  k_p2_items                      M   items (6 [e_join]), THRES (5); atomics behind the stores of 13 and 15   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
+// 19  k_frag_generic                  M   SEG32 aDP*, BQSUM (13, 14 [e_join], 15, 18), table (7 [e_join3]), ffast, n_cov / n_near (8, 10, 11 [e_join3])
+//                                                                                                   FRAG, FAM, VQ bMQ (atomics), global buckets
+// 20  k_frag16 / k_frag               M   SEG32 aDP*, BQSUM (as 19), fsum (12 [e_join3]), ffast, index 5-6, global buckets (19)   FRAG, FAM, VQ b*, buckets
+// 21  k_fam_p4* / k_fam_p5* / k_duplex*  M  unit records (17 [e_stat]), fam2_ins_len (16 [e_alleles]), table, ffast_u, index 7 (1)   FAM, family info planes, buckets
+// 22  k_p5b                           M   buckets, p5flag (20, 21)                                  VQ, buckets cleared
+//     -- M behind 16 [e_fork2, recorded again on S2: gap_tables, the MSI call and set_reads wait for this last record] --
+// Rows 19 and 20 read, per position, the aDP* and BQSUM sums that row 18 adds to: k_p2_items cannot run beside the fragment kernels.
+// Row 3 cannot be forked in front of rows 1 and 2: a store of row 2 would overwrite what row 3 has added.
 extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
                                       const UvcAccStreams *st, UvcProf *prof) {
     const hipStream_t s = st->s, side = st->side, side3 = st->side3;
@@ -3877,7 +3911,8 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     }
     if (P->inferred_is_vcf_generated && R->n_fast) TIMED(prof, "k_prep_sums", hipLaunchKernelGGL(k_prep_sums, dim3(nblk(R->npos, PSUM_TILE)), dim3(256), 0, s, *R, *P));
     if (P->inferred_is_vcf_generated) {
-        // P1: the InDel reads (one wave per read) underneath the position-centric pass
+        // P1: the InDel reads (one wave per read) underneath the position-centric pass; behind k_prep_sums, whose plain stores go to planes
+        // that k_prep_slow adds to (row 3 of the table)
         if (side && R->n_complex) { hipEventRecord(e_fork, s); hipStreamWaitEvent(s2, e_fork, 0); }
         if (R->n_complex) TIMED2(prof, "k_prep_slow", hipLaunchKernelGGL(k_prep_slow, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
         if (side && R->n_complex) hipEventRecord(e_join, s2);
@@ -3891,28 +3926,31 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     // P1b is part of updateByAlns3UsingBQ too (main.hpp:3691-3702): on a FASTQ-only run the thresholds stay zero and rtr.indelphred unedited
     if (P->inferred_is_vcf_generated) TIMED(prof, "k_thres", hipLaunchKernelGGL(k_thres, dim3(nblk(R->npos, 256)), dim3(256), 0, s, *R, *P, half_ratio_phred));
     if (side) { hipEventRecord(e_fork, s); hipStreamWaitEvent(s2, e_fork, 0); if (s3 != s2) hipStreamWaitEvent(s3, e_fork, 0); }
-    // ---- side streams.  s2: the walk that produces the P2 items.  s3: the walk that fills the contribution table, then the per-fragment
-    // statistics, the fragment window index and the interval sums (they need P1 / P1b only), then the queued mismatches of the base pass.
+    // ---- the P2 phase (rows 6-15 of the table).  Neither side chain may be longer than the two passes of k_p2_fast on the main stream, and
+    // no more should run beside them than that takes: a side kernel costs the pass it runs beside part of its own time.
+    // s2: the walk that produces the P2 items, then, behind the base pass, its queued mismatches.  s3: the walk that fills the contribution
+    // table, then the per-fragment statistics, the fragment window index and the interval sums (they need P1 / P1b only).
     if (P->inferred_is_vcf_generated && R->n_complex) TIMED2(prof, "k_p2_slow_walk", hipLaunchKernelGGL(k_p2_slow<true>, dim3(nblk(R->n_complex, 64)), dim3(64), 0, s, *R, *P));
     if (R->n_complex) TIMED3(prof, "k_p2_slow_table", hipLaunchKernelGGL(k_p2_slow<false>, dim3(nblk(R->n_complex, 64)), dim3(64), 0, s, *R, *P));
     TIMED3(prof, "k_fragstat_fast", hipLaunchKernelGGL(k_fragstat_fast, dim3(nblk(R->n_frags, 256)), dim3(256), 0, s, *R, *P));
     TIMED3(prof, "k_win_index_frag", hipLaunchKernelGGL(k_win_index, dim3(nblk(2 * (int64_t)R->nwin * 2, 256)), dim3(256), 0, s, *R, 5, 7));
     if (R->n_sweep) TIMED3(prof, "k_fragstat_sweep", hipLaunchKernelGGL(k_fragstat_sweep, dim3(R->n_sweep), dim3(64), 0, s, *R, *P, R->sweep_frags, (const int32_t *)nullptr, R->n_sweep));
-    // fragments whose event list overflowed (device-side list; the grid covers the worst case, surplus threads exit)
+    // fragments whose event list overflowed (device-side list; the grid covers the worst case up to 65 535 blocks, surplus blocks exit and the
+    // blocks stride over a longer list; a smaller fixed grid was measured and moved nothing: DESIGN 6-r7)
     TIMED3(prof, "k_fragstat_overflow", hipLaunchKernelGGL(k_fragstat_sweep, dim3(imin_h(R->n_frags, 65535)), dim3(64), 0, s, *R, *P, (const int32_t *)R->overflow_frags, (const int32_t *)R->n_overflow, 0));
     if (UVC_PLATFORM_IONTORRENT != P->inferred_sequencing_platform)   // (there every fragment takes k_frag_generic)
         TIMED3(prof, "k_frag_sums", hipLaunchKernelGGL(k_frag_sums, dim3(nblk(R->npos, FSUM_TILE), 2), dim3(256), 0, s, *R, *P));
-    // ---- main stream: the base symbols first, so that the queued mismatches (rare symbols, atomics: disjoint from the planes the
+    // main stream: the base symbols first, so that the queued mismatches (rare symbols, atomics: disjoint from the planes the
     // LINK_M pass stores to) are applied on a side stream while the LINK_M pass runs
     if (P->inferred_is_vcf_generated) {
         launch_p2_fast<false, true>("k_p2_fast_base", F, R, P, nwin, prof, s);
-        if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s3, e_fork2, 0); }
-        TIMED3(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
+        if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s2, e_fork2, 0); }
+        TIMED2(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
         launch_p2_fast<true, false>("k_p2_fast_link", F, R, P, nwin, prof, s);
     }
     if (side) {
         hipEventRecord(e_join, s2); hipStreamWaitEvent(s, e_join, 0);
-        if (s3 != s2) { hipEventRecord(e_join3, s3); hipStreamWaitEvent(s, e_join3, 0); hipStreamWaitEvent(s2, e_join3, 0); }   // (the allele tables below read the contribution table)
+        if (s3 != s2) { hipEventRecord(e_join3, s3); hipStreamWaitEvent(s, e_join3, 0); hipStreamWaitEvent(s2, e_join3, 0); }   // (the allele tables below read the gap events of the table walk)
     }
     // InDel allele tables: they read the contribution table (side stream) and the reads only, so the pipeline stays on the side stream
     // underneath the fragment / family kernels; the main stream picks it up at the end
@@ -3933,7 +3971,7 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     }
     if (side && !(P->inferred_is_vcf_generated && G.n_ev > 0)) hipEventRecord(e_alleles, s2);
     // per-unit statistics of the generic family units (medians, first / last consensus position, general-kind flag): they need the contribution
-    // table and the fragment records only: on s3 behind the queued mismatches, beside the allele tables on s2, underneath k_frag
+    // table and the fragment records only: on s3 behind the interval sums, beside the allele tables on s2, underneath k_frag
     if (R->n_generic_fs) TIMED3(prof, "k_fam_stat", hipLaunchKernelGGL(k_fam_stat, dim3(nblk(R->n_generic_fs, 64)), dim3(64), 0, s, *R, *P));
     if (side) { hipEventRecord(e_stat, s3); hipEventRecord(e_fork2, s2); }
     if (P->inferred_is_vcf_generated && R->n_complex) TIMED(prof, "k_p2_items", hipLaunchKernelGGL(k_p2_items, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
