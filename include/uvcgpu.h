@@ -679,6 +679,56 @@ enum { UVC_SITEREAD_A = 0, UVC_SITEREAD_C, UVC_SITEREAD_G, UVC_SITEREAD_T, UVC_S
 int uvcgpu_region_site_reads(uvcgpu_region_t *r, const int32_t *sites, int64_t n_sites, const UvcSiteReadsRequest *req,
                              int32_t *counts /* [n_sites][8] */, UvcSiteRead *rows, int64_t row_capacity, int64_t *n_rows);
 const char *uvcgpu_site_read_kind_name(int32_t kind);   /* "A" "C" "G" "T" "N" "DEL"; NULL for a kind outside 0..5 */
+/* ---- clipped-read breakpoint sites (uvc1-mi355x --clip-sites-out) ----
+ * Where the soft and hard clips of the handle's alignments (UvcReadSoA) pile up inside a list of ranges: the sites are found, not given.
+ * All integers.
+ *   An alignment is counted iff mapq >= min_mapq, (flag & 0x4) == 0 and l_qseq > 0; secondary and supplementary alignments count (split
+ *   reads are the point).  rend = pos + the reference length of the CIGAR.
+ *   CIGAR walk (that of uvcgpu_region_read_profile): reference coordinate p from pos; M = X D N move p.  An aligned op is M, = or X; a CIGAR
+ *   without one adds nothing but the counted alignment.
+ *   LEFT event (side 0): all S and H ops in front of the first aligned op; its boundary p is the walk's coordinate at that op.  RIGHT event
+ *   (side 1): all S and H ops behind the last aligned op; its boundary p is the walk's coordinate behind that op.  S / H ops between aligned
+ *   ops add nothing.  soft_len / hard_len: the summed S / H lengths of the event, len = soft_len + hard_len.  An event exists iff len >= 1
+ *   and qualifies iff len >= min_clip; an alignment has at most one event per side.
+ *   Vote bases: the query bases of the event's S ops in query order, c[0 .. soft_len).  Vote index k counts outward from the junction:
+ *   c[soft_len - 1 - k] for LEFT, c[k] for RIGHT, k < min(soft_len, UVC_CLIPSITE_NCONS).  Codes 0..3 = A C G T, 4 = anything else;
+ *   qualities are not read.
+ *   A qualifying event is in range iff p lies inside one of `ranges` (those of uvcgpu_region_coverage).  Every other qualifying event --
+ *   one whose p - beg falls outside [0, npos) included -- adds to its total alone.
+ *   A site is a (p, side) whose qualifying in-range events number at least min_reads.  Sites come sorted by (p, side).
+ *   spanning(p): the counted alignments with pos < p < rend (aligned on both sides of the junction, D and N included); independent of the
+ *   ranges and of min_clip.
+ * sites: one row of UVC_CLIPSITE_ROW int64 per site (sections: include/uvc_clipsites.def): range (index into `ranges`), pos (absolute p),
+ *   side, reads (its events), reads_fwd (!(flag & 0x10)), reads_supp (flag & 0x800), reads_secondary (flag & 0x100), reads_hard (events
+ *   with hard_len > 0), len_sum, len_max, mapq_sum, spanning, reserved zeros up to word 16, VOTE[32][5] (k, code).
+ * totals[UVC_CLIPSITE_NTOTAL]: counted alignments; qualifying events in range; qualifying events not in range; events with
+ *   1 <= len < min_clip (any p); qualifying events at kept sites; three zeros.
+ * reads (written only with want_reads = 1): one UvcClipRead per qualifying in-range event at a kept site, ascending by (read, side);
+ *   `site` indexes the returned rows, `read` the UvcReadSoA as given.  *n_reads is written either way. */
+enum UvcClipSiteSection { UVC_CLIPSITE_range = 0, UVC_CLIPSITE_pos, UVC_CLIPSITE_side, UVC_CLIPSITE_reads, UVC_CLIPSITE_reads_fwd, UVC_CLIPSITE_reads_supp,
+                          UVC_CLIPSITE_reads_secondary, UVC_CLIPSITE_reads_hard, UVC_CLIPSITE_len_sum, UVC_CLIPSITE_len_max, UVC_CLIPSITE_mapq_sum,
+                          UVC_CLIPSITE_spanning, UVC_CLIPSITE_reserved, UVC_CLIPSITE_VOTE, UVC_NCLIPSITE };
+enum { UVC_CLIPSITE_NTOTAL = 8, UVC_CLIPSITE_NCOUNTER = 16, UVC_CLIPSITE_NCONS = 32, UVC_CLIPSITE_NCODE = 5, UVC_CLIPSITE_VOTE_BINS = 16,
+       UVC_CLIPSITE_ROW = 176 /* 16 + 32 * 5 */, UVC_CLIPSITE_LEFT = 0, UVC_CLIPSITE_RIGHT = 1 };
+enum UvcClipSiteTotal { UVC_CLIPTOTAL_alignments = 0, UVC_CLIPTOTAL_events_in_range, UVC_CLIPTOTAL_events_off_range, UVC_CLIPTOTAL_events_short,
+                        UVC_CLIPTOTAL_events_at_sites };
+typedef struct UvcClipSitesRequest { int32_t min_mapq, min_clip, min_reads, want_reads; } UvcClipSitesRequest;
+typedef struct UvcClipRead { int32_t site, read, soft_len, hard_len; } UvcClipRead;
+/* Found, counted, ranked and filled on the device from the read columns, CIGARs and bases of the handle: two passes over the alignments,
+ * the sites and the event rows ranked by count / scan / write (no atomic decides an order), the row words integer adds: two calls return
+ * the same bytes.
+ *   Sizes first: a call that is not refused always writes totals, *n_sites and *n_reads.  It returns UVCGPU_ENOMEM when site_capacity <
+ *   *n_sites, or when want_reads is set and read_capacity < *n_reads, and then writes nothing to `sites` or `reads`.
+ *   Legal where uvcgpu_region_read_profile is: from uvcgpu_region_set_reads / _set_reads_device of the current region on, with or without
+ *   accumulate, after any score and while a score stream is open.  Zero reads: zero sites.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason: called before set_reads or after a reset; a range list that
+ *   uvcgpu_region_coverage refuses; NULL req, totals, n_sites or n_reads; min_mapq outside 0..255; min_clip < 1; min_reads < 1; want_reads
+ *   outside 0..1; a negative capacity; a NULL array with a positive capacity.  A refused call writes nothing. */
+int uvcgpu_region_clip_sites(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcClipSitesRequest *req,
+                             int64_t *totals /* [UVC_CLIPSITE_NTOTAL] */,
+                             int64_t *sites /* [site_capacity][UVC_CLIPSITE_ROW] */, int64_t site_capacity, int64_t *n_sites,
+                             UvcClipRead *reads, int64_t read_capacity, int64_t *n_reads);
+const char *uvcgpu_clip_site_section_name(int32_t id);   /* "range" .. "VOTE"; NULL for an id outside 0..UVC_NCLIPSITE - 1 */
 /* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
  * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
  * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when

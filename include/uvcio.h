@@ -252,6 +252,30 @@ int uvcio_sitereads_add(uvcio_sitereads_t *f, int32_t tid, const char *contig, c
                         const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id, const uint8_t *bases, const int64_t *seq_off);
 int uvcio_sitereads_write(const uvcio_sitereads_t *f, const char *path);
 void uvcio_sitereads_close(uvcio_sitereads_t *f);
+/* ---- clipped-read breakpoint sites (uvc1-mi355x --clip-sites-out) ----
+ * What tiles report with uvcgpu_region_clip_sites (want_reads = 1).  add() takes one call's site rows of one contig ([n_sites][176], the
+ * `sites` of the call) and its event rows, with the columns of the call's alignments that the text needs, indexed by UvcClipRead::read:
+ * qname (entries of alignments without rows may be NULL), flag, mapq, fam_id, fam_strand and frag_id.  It copies what it keeps, under a
+ * lock: any thread, any order; a site comes from one call (the tile that owns its position).  A site that two calls report -- a position
+ * inside two overlapping targets -- is kept once: the report with the lexicographically larger row from `reads` on, the first of equal ones.
+ * write: "##clip_sites_min_mapq=", "##clip_sites_min_clip=", "##clip_sites_min_reads=", "##clip_sites_reads=", the "#S" and "#R" column
+ * lines, then per site in (contig id, pos, side) order
+ *   S contig pos(1-based) side(L|R) reads fwd supp secondary hard len_sum len_max mapq_sum spanning fragments families
+ *     families_both_strands cons_len cons      fragments and families are the distinct (fam_id, fam_strand, frag_id) and fam_id among the
+ *     site's events, families_both_strands those with events of both fam_strand values (ids are local to a call); cons_len = the vote
+ *     indices k with at least one vote; cons = one letter per such k, the base with the most votes (ties to the smaller code, N for code 4),
+ *     lower-case iff winner * 3 < total * 2, a LEFT site in reference direction (k descending), a RIGHT site with k ascending; "." when
+ *     cons_len is 0
+ *   R contig pos side qname flag mapq soft_len hard_len family_rank strand   with reads = 1 one per event behind the site, ordered by
+ *     (family_rank, qname, flag): the 1-based rank of the event's family among the families of the site, ordered by the smallest (qname,
+ *     flag) of their events there.
+ * Integers and names only, tab-separated.  A path that ends in .gz is written block-gzipped. */
+typedef struct uvcio_clipsites uvcio_clipsites_t;
+int uvcio_clipsites_open(uvcio_clipsites_t **out, int32_t min_mapq, int32_t min_clip, int32_t min_reads, int32_t with_reads);
+int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads,
+                        int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id);
+int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *path);
+void uvcio_clipsites_close(uvcio_clipsites_t *f);
 /* ---- the read profile (uvc1-mi355x --read-profile-out) ----
  * The sum of the rows that tiles report with uvcgpu_region_read_profile (5712 int64: Q[4][64][2], CYC[4][256][5], SUB[4][4][4], 16 counters);
  * rows of disjoint position sets add, so add() sums under a lock, from any thread in any order.  write(): "##read_profile_min_mapq=",

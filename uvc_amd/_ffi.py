@@ -107,6 +107,14 @@ class UvcSiteRead(C.Structure):
     _fields_ = [("site", C.c_int32), ("read", C.c_int32), ("q", C.c_int32), ("obs", C.c_int32), ("ins_q", C.c_int32), ("ins_len", C.c_int32), ("del_len", C.c_int32), ("reserved", C.c_int32)]
 
 
+class UvcClipSitesRequest(C.Structure):
+    _fields_ = [("min_mapq", C.c_int32), ("min_clip", C.c_int32), ("min_reads", C.c_int32), ("want_reads", C.c_int32)]
+
+
+class UvcClipRead(C.Structure):
+    _fields_ = [("site", C.c_int32), ("read", C.c_int32), ("soft_len", C.c_int32), ("hard_len", C.c_int32)]
+
+
 class UvcCallableRun(C.Structure):
     _fields_ = [("range", C.c_int32), ("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("mask", C.c_int32)]
 
@@ -206,6 +214,13 @@ assert CALLABLE_BITS[:len(COVERAGE_MEASURES)] == ["LOW_" + m for m in COVERAGE_M
 # the observation kinds of uvcgpu_region_site_reads in id order (uvcgpu_site_read_kind_name), checked against the header's enums
 SITE_READ_KINDS = ["A", "C", "G", "T", "N", "DEL"]
 assert [ENUMS["UVC_SITEREAD_" + n] for n in SITE_READ_KINDS] == list(range(ENUMS["UVC_SITEREAD_NKIND"])) and C.sizeof(UvcSiteRead) == 4 * ENUMS["UVC_SITEREAD_NCOL"]
+
+# the sections of a clip-site row in id order (UvcClipSiteSection): the table of include/uvc_clipsites.def, checked against the header's enums
+CLIPSITE_SECTIONS = _read_def("uvc_clipsites.def", "UVC_CLIPSITE")
+assert [ENUMS["UVC_CLIPSITE_" + n] for n, _, _ in CLIPSITE_SECTIONS] == list(range(ENUMS["UVC_NCLIPSITE"]))
+assert sum(w for _, _, w in CLIPSITE_SECTIONS) == ENUMS["UVC_CLIPSITE_ROW"] and all(f == sum(w for _, _, w in CLIPSITE_SECTIONS[:k]) for k, (_, f, _) in enumerate(CLIPSITE_SECTIONS))
+assert CLIPSITE_SECTIONS[-1] == ("VOTE", ENUMS["UVC_CLIPSITE_VOTE_BINS"], ENUMS["UVC_CLIPSITE_NCONS"] * ENUMS["UVC_CLIPSITE_NCODE"]) and C.sizeof(UvcClipRead) == 16 and C.sizeof(UvcClipSitesRequest) == 16
+CLIPSITE_TOTALS = [k[len("UVC_CLIPTOTAL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPTOTAL_")), key=lambda kv: kv[1])]
 
 # the sections of a microsatellite row in id order (UvcMsiSection): the table of include/uvc_msi.def, checked against the header's enums
 MSI_SECTIONS = _read_def("uvc_msi.def", "UVC_MSI")

@@ -39,12 +39,12 @@
 namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
-// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o, 4p), in the order their options are checked: of several faults the first in
+// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o, 4p, 4q), in the order their options are checked: of several faults the first in
 // this order is the one reported.
 // A row holds what the command line says of a report in more than one place: parse (the path, "a sub-option was given", the checks behind
 // the loop), split_pair (pair mode writes none) and main (the probe of the path).  A new report is a row here, an Opts store, a
 // *_of_tile and its open / write lines in main.
-enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, N_REPORTS };
+enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, R_CLIPSITES, N_REPORTS };
 struct ReportRow {
     const char *out;                 // --X-out PATH
     const char *subs[6];             // the options that only shape this report: each needs --X-out (the list ends with a null)
@@ -67,6 +67,8 @@ const ReportRow REPORTS[N_REPORTS] = {
     { "--fragment-profile-out", { "--fragment-profile-window", "--fragment-profile-min-mapq", "--fragment-profile-short", "--fragment-profile-long" }, "--fragment-profile-window", "a target can straddle shards",
       "every tile would be counted that many times", "fragment profile", nullptr },
     { "--site-reads-out", { "--site-reads-sites", "--site-reads-min-mapq", "--site-reads-alt-only" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its rows that many times", "site reads report", nullptr },
+    { "--clip-sites-out", { "--clip-sites-min-clip", "--clip-sites-min-reads", "--clip-sites-min-mapq", "--clip-sites-reads" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its sites that many times",
+      "clip sites report", nullptr },
 };
 // the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
 int report_of(const std::string &name, int *sub) {
@@ -107,6 +109,8 @@ struct Opts {
     uvcio_fragprofile_t *fragprof = nullptr;   // --fragment-profile-out: the report's store, filled by the workers (main)
     std::string sitereads_sites; UvcSiteReadsRequest sitereads_req{ 0, 1 };   // --site-reads-sites, --site-reads-min-mapq, --site-reads-alt-only
     uvcio_sitereads_t *sitereads = nullptr; uvcio_sites_t *sitereads_list = nullptr;   // --site-reads-out: the report's store, filled by the workers, and the listed sites (main)
+    UvcClipSitesRequest clipsites_req{ 0, 10, 3, 1 }; int32_t clipsites_reads = 0;   // --clip-sites-min-mapq, --clip-sites-min-clip, --clip-sites-min-reads (the call always asks for the event rows); --clip-sites-reads
+    uvcio_clipsites_t *clipsites = nullptr;   // --clip-sites-out: the report's store, filled by the workers (main)
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -181,6 +185,11 @@ const OptRow OPTS[] = {
     { "--site-reads-sites", O_CLI, false, "", "with --site-reads-out (required): BED or VCF(.gz) of the sites, read as --force-sites reads its file" },
     { "--site-reads-min-mapq", O_CLI, false, "0", "with --site-reads-out: only alignments of at least this mapping quality are counted (0..255)" },
     { "--site-reads-alt-only", O_CLI, false, "1", "with --site-reads-out: 1 (or true) writes R and A lines only for reads that differ from the reference at the site -- another base, a deletion, an InDel behind the site; 0 (or false) for every read.  The S lines count every read either way" },
+    { "--clip-sites-out", O_CLI, false, "", "write the clipped-read breakpoint sites here (tab-separated; block-gzipped when the name ends in .gz): per (position, side) at which the soft or hard clips of enough alignments end an S line with the reads, their strands, supplementary, secondary and hard-clipped ones, the clip lengths, the reads that span the junction aligned, the fragments, UMI families and families seen on both strands behind the clips, and the consensus of the clipped bases counted outward from the junction -- found on the device among each tile's reads over the positions the tile owns, with the fragments and families the caller itself formed.  The VCF does not depend on it" },
+    { "--clip-sites-min-clip", O_CLI, false, "10", "with --clip-sites-out: a clip counts from this many clipped bases on, soft and hard together (1 or more)" },
+    { "--clip-sites-min-reads", O_CLI, false, "3", "with --clip-sites-out: a site is written when the clips of at least this many alignments end there (1 or more)" },
+    { "--clip-sites-min-mapq", O_CLI, false, "0", "with --clip-sites-out: only alignments of at least this mapping quality are counted (0..255)" },
+    { "--clip-sites-reads", O_CLI, false, "0", "with --clip-sites-out: 1 (or true) writes an R line per clipped read behind each S line -- name, flag, mapping quality, soft and hard clip length, family rank and strand; 0 (or false) the S lines alone" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -427,6 +436,10 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--site-reads-sites") { o.sitereads_sites = val(); if (o.sitereads_sites.empty()) die("--site-reads-sites needs a path"); }
         else if (n0 == "--site-reads-min-mapq") o.sitereads_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
         else if (n0 == "--site-reads-alt-only") o.sitereads_req.alt_only = (int32_t)whole_number(n0, val(), 0, 1, "0 or 1 (false or true)", N_STRTOD_BOOL);
+        else if (n0 == "--clip-sites-min-clip") o.clipsites_req.min_clip = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--clip-sites-min-reads") o.clipsites_req.min_reads = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--clip-sites-min-mapq") o.clipsites_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
+        else if (n0 == "--clip-sites-reads") o.clipsites_reads = (int32_t)whole_number(n0, val(), 0, 1, "0 or 1 (false or true)", N_STRTOD_BOOL);
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -527,6 +540,7 @@ struct Worker {
     std::vector<int64_t> cov_rows, fam_rows, rp_row, frag_rows;   // --coverage-out, --family-stats-out, --read-profile-out, --fragment-profile-out: what the device call fills
     std::vector<UvcCallableRun> call_runs;   // --callable-out: the runs, as many as the last tiles had
     std::vector<int32_t> sr_sites, sr_counts; std::vector<UvcSiteRead> sr_rows; std::vector<const char *> sr_qnames;   // --site-reads-out: the sites a tile owns, their counts and rows, the names of the rows' alignments
+    std::vector<int64_t> cs_rows; std::vector<UvcClipRead> cs_reads; std::vector<const char *> cs_qnames;   // --clip-sites-out: the site rows and event rows of a tile, as many as the last tiles had, the names of the events' alignments
     std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the loci, as many as the last tiles had
 };
 
@@ -672,6 +686,24 @@ void site_reads_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
     if (uvcio_sitereads_add(o.sitereads, t.tid, t.chrom.c_str(), w.sr_sites.data(), nullptr, n_sites, w.sr_counts.data(), w.sr_rows.data(), n, k, w.sr_qnames.data(), w.flag.data(), w.mapq.data(), w.lq.data(),
                             w.fam.data(), w.fstrand.data(), w.frag.data(), b.bases, w.soff.data())) die(uvcio_last_error());
 }
+// --clip-sites-out: the clip sites inside the stretches one tile owns -- the list coverage_of_tile reports on, so a site belongs to the tile
+// that owns its position however the tiles are cut -- by one uvcgpu_region_clip_sites after set_reads, always with the event rows (sizes
+// first on both arrays: the buffers of the last tiles, grown where a tile has more), handed to the store with the columns of the kept
+// alignments (alns3 order: an event's `read` indexes them) and the names of the batch.
+void clip_sites_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own, const Tile &t, const UvcBamBatch &b, int64_t k) {
+    if (!owned_ranges(w, own)) return;
+    int64_t totals[UVC_CLIPSITE_NTOTAL], n_reads = 0;
+    const int64_t n_sites = sizes_first(w.cs_rows, UVC_CLIPSITE_ROW, [&](int64_t *rows, int64_t cap, int64_t *n) {
+        int rc = uvcgpu_region_clip_sites(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.clipsites_req, totals, rows, cap, n, w.cs_reads.data(), (int64_t)w.cs_reads.size(), &n_reads);
+        if (rc == UVCGPU_ENOMEM && n_reads > (int64_t)w.cs_reads.size()) w.cs_reads.resize((size_t)n_reads);   // (sizes_first calls once more: with room for both)
+        if (rc == UVCGPU_ENOMEM && *n <= cap) rc = uvcgpu_region_clip_sites(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.clipsites_req, totals, rows, cap, n, w.cs_reads.data(), (int64_t)w.cs_reads.size(), &n_reads);
+        return rc;
+    });
+    if (n_sites == 0) return;
+    w.cs_qnames.assign((size_t)k, nullptr);
+    for (int64_t i = 0; i < n_reads; i++) { const int32_t a = w.cs_reads[(size_t)i].read; w.cs_qnames[(size_t)a] = b.qnames + b.qname_off[w.order[(size_t)a]]; }
+    if (uvcio_clipsites_add(o.clipsites, t.tid, t.chrom.c_str(), w.cs_rows.data(), n_sites, w.cs_reads.data(), n_reads, k, w.cs_qnames.data(), w.flag.data(), w.mapq.data(), w.fam.data(), w.fstrand.data(), w.frag.data())) die(uvcio_last_error());
+}
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // The record text of one call behind `lines`: write(dst, room, &len) into a buffer as large as the last tiles needed (+ slack); a second
 // call only when the text did not fit
@@ -768,7 +800,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     // uvcio_sites_fetch go by, without the end point t.end itself, which lies outside every target the tile was cut from (and which two regions of
     // the reference's cuts share).  The list depends on scored() alone: made here, in front of accumulate, for the report of the reads as well.
     std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
-    if (o.cov || o.errprof || o.callable || o.readprof || o.msi || o.sitereads) {
+    if (o.cov || o.errprof || o.callable || o.readprof || o.msi || o.sitereads || o.clipsites) {
         auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !(o.callable || o.msi) ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
         for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) {   // (n_merged = 0: t0_ alone)
             const Tile &l = (&t0_)[q];
@@ -776,6 +808,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
         }
     }
     if (o.readprof) readprofile_of_tile(w, o, own);   // the BAM's own qualities: in front of the correction
+    if (o.clipsites) clip_sites_of_tile(w, o, own, t, b, k);   // the read columns, CIGARs and bases of set_reads: qualities are not read
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
     if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
     if (o.errprof) errprofile_of_tile(w, o, own);
@@ -1424,6 +1457,7 @@ int main(int argc, char **argv) {
     if (wanted(R_FAMSTATS) && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
     std::vector<CovSpan> frag_spans((size_t)nref);
     if (wanted(R_FRAGPROF) && uvcio_fragprofile_open(&o.fragprof, o.fragprof_req.min_mapq, o.fragprof_req.short_lo, o.fragprof_req.short_hi, o.fragprof_req.long_lo, o.fragprof_req.long_hi)) die(uvcio_last_error());
+    if (wanted(R_CLIPSITES) && uvcio_clipsites_open(&o.clipsites, o.clipsites_req.min_mapq, o.clipsites_req.min_clip, o.clipsites_req.min_reads, o.clipsites_reads)) die(uvcio_last_error());
     if (wanted(R_SITEREADS)) {   // the listed sites, each with its reference base: a site that no tile owns keeps its S line of zeros
         uvcio_sites_t *list = nullptr; uvcio_fasta_t *fa = nullptr;
         if (uvcio_sites_open(&list, o.sitereads_sites.c_str(), G.cnames.data(), nref)) die("--site-reads-sites: " + std::string(uvcio_last_error()));
@@ -1559,6 +1593,7 @@ int main(int argc, char **argv) {
     if (o.readprof) { finish(R_READPROF, uvcio_readprofile_write(o.readprof, path(R_READPROF))); uvcio_readprofile_close(o.readprof); }
     if (o.fragprof) { finish(R_FRAGPROF, uvcio_fragprofile_write(o.fragprof, path(R_FRAGPROF))); uvcio_fragprofile_close(o.fragprof); }
     if (o.sitereads) { finish(R_SITEREADS, uvcio_sitereads_write(o.sitereads, path(R_SITEREADS))); uvcio_sitereads_close(o.sitereads); uvcio_sites_close(o.sitereads_list); }
+    if (o.clipsites) { finish(R_CLIPSITES, uvcio_clipsites_write(o.clipsites, path(R_CLIPSITES))); uvcio_clipsites_close(o.clipsites); }
     if (tvcf) uvcio_tumor_vcf_close(tvcf);
     if (sites) uvcio_sites_close(sites);
     if (!o.bed_out.empty()) {

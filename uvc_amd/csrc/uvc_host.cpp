@@ -118,7 +118,7 @@ struct uvcgpu_region {
     Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
     Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
-    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1341,8 +1341,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile and _site_reads ----
-// What the eight share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads and _clip_sites ----
+// What the nine share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1643,6 +1643,78 @@ int uvcgpu_region_site_reads(uvcgpu_region_t *r, const int32_t *sites, int64_t n
     return guarded("uvcgpu_region_site_reads", [&] { return uvcgpu_region_site_reads_impl(r, sites, n_sites, req, counts, rows, row_capacity, n_rows); });
 }
 const char *uvcgpu_site_read_kind_name(int32_t kind) { return uvc_sitereads_kind_name(kind); }
+
+// ---- clipped-read breakpoint sites of ranges (uvc_clipsites.hip): [table] [totals] [per-position counts: cnt[npos][2], spanning[npos]]
+// [site keys] [rows, `room_sites` of them] [scan scratch ints] [event rows, `room_reads` of them] ----
+// The read columns, CIGARs and bases belong to the reads of the handle: the legality is that of uvcgpu_region_read_profile.
+// Sizes first in one pass: no call has more sites than min(2 positions of its ranges, 2 alignments) or more event rows than 2 alignments,
+// so the room is the caller's capacity capped by those bounds, and a call whose room is too small is one whose capacity is.  The find
+// stage runs, the host reads the totals and the two numbers in one wait, and only a call with enough room launches the fill.
+static int uvcgpu_region_clip_sites_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcClipSitesRequest *req, int64_t *totals, int64_t *sites, int64_t site_capacity,
+                                         int64_t *n_sites, UvcClipRead *reads, int64_t read_capacity, int64_t *n_reads) {
+    { int rc1 = report_guard(r, "clip_sites", nullptr, "reads"); if (rc1) return rc1; }
+    if (!ranges || !req || !totals || !n_sites || !n_reads) return fail(UVCGPU_EINVAL, "clip_sites: ranges, req, totals, n_sites and n_reads must not be NULL");
+    if (req->min_mapq < 0 || req->min_mapq > 255) return fail(UVCGPU_EINVAL, "clip_sites: min_mapq " + std::to_string(req->min_mapq) + " is outside 0..255");
+    if (req->min_clip < 1) return fail(UVCGPU_EINVAL, "clip_sites: min_clip " + std::to_string(req->min_clip) + " must be at least 1");
+    if (req->min_reads < 1) return fail(UVCGPU_EINVAL, "clip_sites: min_reads " + std::to_string(req->min_reads) + " must be at least 1");
+    if (req->want_reads < 0 || req->want_reads > 1) return fail(UVCGPU_EINVAL, "clip_sites: want_reads " + std::to_string(req->want_reads) + " is outside 0..1");
+    if (site_capacity < 0) return fail(UVCGPU_EINVAL, "clip_sites: site_capacity " + std::to_string(site_capacity) + " is negative");
+    if (read_capacity < 0) return fail(UVCGPU_EINVAL, "clip_sites: read_capacity " + std::to_string(read_capacity) + " is negative");
+    if (!sites && site_capacity > 0) return fail(UVCGPU_EINVAL, "clip_sites: sites is NULL with site_capacity " + std::to_string(site_capacity));
+    if (!reads && read_capacity > 0) return fail(UVCGPU_EINVAL, "clip_sites: reads is NULL with read_capacity " + std::to_string(read_capacity));
+    { int rc1 = range_count("clip_sites", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "clip_sites", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
+    const size_t totals_bytes = sizeof(int64_t) * UVC_CLIPSITE_NTOTAL, row_bytes = sizeof(int64_t) * UVC_CLIPSITE_ROW;
+    if (!r->has_reads) { memset(totals, 0, totals_bytes); *n_sites = 0; *n_reads = 0; return 0; }   // set_reads with zero reads: nothing to launch
+    const int64_t n_alns = r->R.n_alns, most_sites = std::min<int64_t>(2 * n_total, 2 * n_alns);
+    const int64_t room_sites = std::min(site_capacity, most_sites), room_reads = req->want_reads ? std::min<int64_t>(read_capacity, 2 * n_alns) : 0;
+    const int64_t sites_at = uvc_clipsites_sites_at(n_alns, r->npos), reads_at = uvc_clipsites_reads_at(n_alns, r->npos);
+    ReportLayout L;
+    const size_t o_tab = L.take(sizeof(UvcRangeRow) * tab.size()), o_totals = L.take(totals_bytes), o_pos = L.take(sizeof(int32_t) * (size_t)uvc_clipsites_pos_ints(r->npos));
+    const size_t o_keys = L.take(sizeof(int32_t) * (size_t)most_sites), o_rows = L.take(row_bytes * (size_t)room_sites);
+    const size_t o_scratch = L.take(sizeof(int32_t) * (size_t)uvc_clipsites_scratch_ints(n_alns, r->npos)), o_reads = L.take(sizeof(UvcClipRead) * (size_t)room_reads);
+    const size_t head_bytes = 128;   // the page-locked head: the totals, the number of sites and of event rows
+    { int rc1 = report_begin(r, L, std::max(head_bytes, row_bytes * (size_t)room_sites + sizeof(UvcClipRead) * (size_t)room_reads), "clip sites", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+    const UvcRangeRow *d_tab = (const UvcRangeRow *)(r->d_report + o_tab);
+    long long *d_totals = (long long *)(r->d_report + o_totals), *d_rows = (long long *)(r->d_report + o_rows);
+    int32_t *d_pos = (int32_t *)(r->d_report + o_pos), *d_keys = (int32_t *)(r->d_report + o_keys), *d_scratch = (int32_t *)(r->d_report + o_scratch);
+    UvcClipRead *d_reads = (UvcClipRead *)(r->d_report + o_reads);
+    HIP_OK(hipMemsetAsync(d_totals, 0, o_keys - o_totals, r->stream));   // the totals and the per-position counts
+    // with profiling on, two more entries of uvcgpu_region_kernel_times (accumulate starts the list anew)
+    int pi = uvc_prof_begin(&r->prof, "k_clipsites_find", r->stream);
+    uvc_launch_clipsites_find(&r->R, &r->W, d_tab, (int)n_ranges, req, d_totals, d_pos, d_keys, most_sites, d_scratch, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    HIP_OK(hipGetLastError());
+    char *h = r->h_report;
+    HIP_OK(hipMemcpyAsync(h, d_totals, totals_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipMemcpyAsync(h + totals_bytes, d_scratch + sites_at, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipMemcpyAsync(h + totals_bytes + 4, d_scratch + reads_at, sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipStreamSynchronize(r->stream));
+    int32_t ns = 0, nr = 0;
+    memcpy(totals, h, totals_bytes); memcpy(&ns, h + totals_bytes, sizeof ns); memcpy(&nr, h + totals_bytes + 4, sizeof nr);
+    *n_sites = ns; *n_reads = nr;
+    if (ns > site_capacity) return fail(UVCGPU_ENOMEM, "clip_sites: " + std::to_string(ns) + " sites, room for " + std::to_string(site_capacity));
+    if (req->want_reads && nr > read_capacity) return fail(UVCGPU_ENOMEM, "clip_sites: " + std::to_string(nr) + " event rows, room for " + std::to_string(read_capacity));
+    if (ns == 0) return 0;
+    const size_t sites_bytes = row_bytes * (size_t)ns, reads_bytes = req->want_reads ? sizeof(UvcClipRead) * (size_t)nr : 0;
+    HIP_OK(hipMemsetAsync(d_rows, 0, sites_bytes, r->stream));
+    pi = uvc_prof_begin(&r->prof, "k_clipsites_fill", r->stream);
+    uvc_launch_clipsites_fill(&r->R, &r->W, d_tab, (int)n_ranges, req, d_pos, d_keys, ns, d_scratch, d_rows, req->want_reads ? d_reads : nullptr, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h, d_rows, sites_bytes, hipMemcpyDeviceToHost, r->stream));
+    if (reads_bytes) HIP_OK(hipMemcpyAsync(h + sites_bytes, d_reads, reads_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipStreamSynchronize(r->stream));
+    memcpy(sites, h, sites_bytes);
+    if (reads_bytes) memcpy(reads, h + sites_bytes, reads_bytes);
+    return 0;
+}
+int uvcgpu_region_clip_sites(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, const UvcClipSitesRequest *req, int64_t *totals, int64_t *sites, int64_t site_capacity, int64_t *n_sites,
+                             UvcClipRead *reads, int64_t read_capacity, int64_t *n_reads) {
+    return guarded("uvcgpu_region_clip_sites", [&] { return uvcgpu_region_clip_sites_impl(r, ranges, n_ranges, req, totals, sites, site_capacity, n_sites, reads, read_capacity, n_reads); });
+}
+const char *uvcgpu_clip_site_section_name(int32_t id) { return uvc_clipsites_name(id); }
 
 // ---- callable-region intervals of ranges (uvc_callable.hip): [table] [block counts] [mask bytes] [runs, one per position at worst] ----
 // Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit

@@ -1642,6 +1642,120 @@ extern "C" int uvcio_sitereads_write(const uvcio_sitereads_t *f, const char *pat
 }
 extern "C" void uvcio_sitereads_close(uvcio_sitereads_t *f) { delete f; }
 
+// ---------------------------------------------------------------- clipped-read breakpoint sites ----
+// the rows are those of uvcgpu_region_clip_sites (UVC_CLIPSITE_* of uvcgpu.h, include/uvc_clipsites.def; UvcClipRead).  The family and fragment
+// ids of an event are local to its call, and a site comes from one call: the store compares them inside a site alone and writes none.
+namespace {
+enum {
+#define UVC_CLIPSITE(name, first, words) CSW_##name = first,
+#include "uvc_clipsites.def"
+#undef UVC_CLIPSITE
+};
+static_assert(CSW_VOTE == UVC_CLIPSITE_VOTE_BINS && CSW_VOTE + UVC_CLIPSITE_NCONS * UVC_CLIPSITE_NCODE == UVC_CLIPSITE_ROW && CSW_spanning == CSW_reads + 8,
+              "the words of an S line are reads .. spanning of include/uvc_clipsites.def, the votes fill the row behind the counters");
+}
+struct uvcio_clipsites {
+    UvcClipSitesRequest req;
+    struct Event { std::string qname; int32_t flag, mapq, soft, hard, fam, strand, frag; };
+    struct Site { std::string contig; int64_t row[UVC_CLIPSITE_ROW]; std::vector<Event> events; };
+    std::map<std::tuple<int32_t, int64_t, int64_t>, Site> sites;   // by (tid, zero-based position, side)
+    std::mutex mu;
+};
+extern "C" int uvcio_clipsites_open(uvcio_clipsites_t **out, int32_t min_mapq, int32_t min_clip, int32_t min_reads, int32_t with_reads) {
+    if (!out) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
+    uvcio_clipsites *f = new uvcio_clipsites;
+    f->req = UvcClipSitesRequest{ min_mapq, min_clip, min_reads, with_reads };
+    *out = f;
+    return 0;
+}
+extern "C" int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns,
+                                   const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
+    if (!f || !contig || n_sites < 0 || (n_sites > 0 && !sites) || n_reads < 0) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
+    if (n_reads > 0 && (!reads || !qnames || !flag || !mapq || !fam_id || !fam_strand || !frag_id)) return fail(UVCGPU_EINVAL, "clip sites: event rows without the columns of their alignments");
+    // what the sites keep is made outside the lock
+    std::vector<uvcio_clipsites::Site> made((size_t)n_sites);
+    for (int64_t s = 0; s < n_sites; s++) {
+        made[(size_t)s].contig = contig;
+        memcpy(made[(size_t)s].row, sites + s * UVC_CLIPSITE_ROW, sizeof(int64_t) * UVC_CLIPSITE_ROW);
+        const int64_t side = made[(size_t)s].row[CSW_side];
+        if (side != UVC_CLIPSITE_LEFT && side != UVC_CLIPSITE_RIGHT) return fail(UVCGPU_EINVAL, "clip sites: site " + std::to_string(s) + " has side " + std::to_string(side));
+    }
+    for (int64_t k = 0; k < n_reads; k++) {
+        const UvcClipRead &r = reads[k];
+        if (r.site < 0 || r.site >= n_sites || r.read < 0 || r.read >= n_alns || !qnames[r.read]) return fail(UVCGPU_EINVAL, "clip sites: event row " + std::to_string(k) + " names site " + std::to_string(r.site) + " and alignment " + std::to_string(r.read) + ", which the call does not hold");
+        const int a = r.read;
+        made[(size_t)r.site].events.push_back(uvcio_clipsites::Event{ qnames[a], flag[a], mapq[a], r.soft_len, r.hard_len, fam_id[a], fam_strand[a], frag_id[a] });
+    }
+    std::lock_guard<std::mutex> g(f->mu);
+    for (auto &m : made) {
+        const auto key = std::make_tuple(tid, m.row[CSW_pos], m.row[CSW_side]);
+        auto it = f->sites.find(key);
+        // a position inside two overlapping targets has two owners, which see the same alignments: the site is kept once -- the report with
+        // the larger row where the two differ, the first where they are equal -- so that the text does not depend on who came first
+        if (it == f->sites.end()) f->sites[key] = std::move(m);
+        else if (std::lexicographical_compare(it->second.row + CSW_reads, it->second.row + UVC_CLIPSITE_ROW, m.row + CSW_reads, m.row + UVC_CLIPSITE_ROW)) it->second = std::move(m);
+    }
+    return 0;
+}
+extern "C" int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *path) {
+    if (!f || !path || !*path) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
+    typedef uvcio_clipsites::Event Event;
+    std::string text = "##clip_sites_min_mapq=" + std::to_string(f->req.min_mapq) + "\n##clip_sites_min_clip=" + std::to_string(f->req.min_clip) + "\n##clip_sites_min_reads=" + std::to_string(f->req.min_reads)
+                       + "\n##clip_sites_reads=" + std::to_string(f->req.want_reads)
+                       + "\n#S\tcontig\tpos\tside\treads\tfwd\tsupp\tsecondary\thard\tlen_sum\tlen_max\tmapq_sum\tspanning\tfragments\tfamilies\tfamilies_both_strands\tcons_len\tcons\n"
+                         "#R\tcontig\tpos\tside\tqname\tflag\tmapq\tsoft_len\thard_len\tfamily_rank\tstrand\n";
+    for (const auto &kv : f->sites) {   // (the map is ordered by (tid, pos, side))
+        const uvcio_clipsites::Site &site = kv.second;
+        const bool left = (site.row[CSW_side] == UVC_CLIPSITE_LEFT);
+        const std::string at = "\t" + site.contig + "\t" + std::to_string(site.row[CSW_pos] + 1) + "\t" + (left ? "L" : "R");
+        text += "S" + at;
+        for (int w = CSW_reads; w <= CSW_spanning; w++) text += "\t" + std::to_string(site.row[w]);
+        std::set<std::tuple<int32_t, int32_t, int32_t>> frags;
+        std::map<int32_t, int> strands;   // family -> bit 0 / 1: an event of fam_strand 0 / 1
+        for (const Event &e : site.events) { frags.insert(std::make_tuple(e.fam, e.strand, e.frag)); strands[e.fam] |= 1 << (e.strand & 1); }
+        int64_t both = 0;
+        for (const auto &s : strands) both += (s.second == 3);
+        // the consensus of the votes: one letter per k with a vote, outward from the junction; a LEFT site reads in reference direction
+        std::string cons;
+        for (int k = 0; k < UVC_CLIPSITE_NCONS; k++) {
+            const int64_t *v = site.row + CSW_VOTE + k * UVC_CLIPSITE_NCODE;
+            int64_t total = 0; int win = 0;
+            for (int c = 0; c < UVC_CLIPSITE_NCODE; c++) { total += v[c]; if (v[c] > v[win]) win = c; }
+            if (total <= 0) continue;
+            const char ch = "ACGTN"[win];
+            cons += (v[win] * 3 < total * 2) ? (char)tolower((unsigned char)ch) : ch;
+        }
+        const size_t cons_len = cons.size();
+        if (left) std::reverse(cons.begin(), cons.end());
+        text += "\t" + std::to_string(frags.size()) + "\t" + std::to_string(strands.size()) + "\t" + std::to_string(both) + "\t" + std::to_string(cons_len) + "\t" + (cons.empty() ? std::string(".") : cons) + "\n";
+        if (!f->req.want_reads || site.events.empty()) continue;
+        // a family's rank: by the smallest (qname, flag) of its events at this site
+        std::map<int32_t, std::pair<std::string, int32_t>> least;
+        for (const Event &e : site.events) {
+            const auto key = std::make_pair(e.qname, e.flag);
+            auto it = least.find(e.fam);
+            if (it == least.end()) least[e.fam] = key; else if (key < it->second) it->second = key;
+        }
+        std::vector<std::pair<std::string, int32_t>> keys;
+        for (const auto &l : least) keys.push_back(l.second);
+        std::sort(keys.begin(), keys.end());
+        keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        std::map<int32_t, int64_t> rank;
+        for (const auto &l : least) rank[l.first] = (std::lower_bound(keys.begin(), keys.end(), l.second) - keys.begin()) + 1;
+        std::vector<const Event *> order;
+        for (const Event &e : site.events) order.push_back(&e);
+        std::stable_sort(order.begin(), order.end(), [&](const Event *a, const Event *b) {
+            const int64_t ra = rank[a->fam], rb = rank[b->fam];
+            return std::tie(ra, a->qname, a->flag) < std::tie(rb, b->qname, b->flag);
+        });
+        for (const Event *e : order)
+            text += "R" + at + "\t" + e->qname + "\t" + std::to_string(e->flag) + "\t" + std::to_string(e->mapq) + "\t" + std::to_string(e->soft) + "\t" + std::to_string(e->hard) + "\t" + std::to_string(rank[e->fam]) + "\t"
+                    + std::to_string(e->strand) + "\n";
+    }
+    return write_text(path, text);
+}
+extern "C" void uvcio_clipsites_close(uvcio_clipsites_t *f) { delete f; }
+
 // ---------------------------------------------------------------- the callable-region BED ----
 struct uvcio_callable {
     std::vector<std::string> measures, bits; std::vector<int32_t> min_depth; int32_t max_aDP = 0;

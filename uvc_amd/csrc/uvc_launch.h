@@ -155,6 +155,20 @@ void uvc_launch_sitereads_write(const RegionDev *R, const RawReads *W, const int
 int64_t uvc_sitereads_scratch_ints(int64_t n_alns, int64_t n_sites);
 int64_t uvc_sitereads_rows_at(int64_t n_alns, int64_t n_sites);
 const char *uvc_sitereads_kind_name(int k);
+// ---- uvc_clipsites.hip: two stages, each one entry of uvcgpu_region_kernel_times.  d_tab = n_ranges + 1 rows; d_totals: UVC_CLIPSITE_NTOTAL
+// words and d_pos: uvc_clipsites_pos_ints(npos) ints, both zero at the start; d_keys: key_room ints (no call has more sites than
+// min(2 positions of the ranges, 2 alignments)); d_scratch: uvc_clipsites_scratch_ints(n_alns, npos) ints: behind the find, entry
+// uvc_clipsites_sites_at holds the number of sites and entry uvc_clipsites_reads_at the number of event rows.  The fill follows a find with
+// the same arguments; d_rows: n_sites rows of UVC_CLIPSITE_ROW words, zero at the start; d_reads: room for the event rows, or NULL ----
+void uvc_launch_clipsites_find(const RegionDev *R, const RawReads *W, const UvcRangeRow *d_tab, int n_ranges, const UvcClipSitesRequest *req, long long *d_totals, int32_t *d_pos,
+                               int32_t *d_keys, int64_t key_room, int32_t *d_scratch, hipStream_t s);
+void uvc_launch_clipsites_fill(const RegionDev *R, const RawReads *W, const UvcRangeRow *d_tab, int n_ranges, const UvcClipSitesRequest *req, const int32_t *d_pos, const int32_t *d_keys,
+                               int n_sites, const int32_t *d_scratch, long long *d_rows, UvcClipRead *d_reads, hipStream_t s);
+int64_t uvc_clipsites_pos_ints(int64_t npos);
+int64_t uvc_clipsites_scratch_ints(int64_t n_alns, int64_t npos);
+int64_t uvc_clipsites_sites_at(int64_t n_alns, int64_t npos);
+int64_t uvc_clipsites_reads_at(int64_t n_alns, int64_t npos);
+const char *uvc_clipsites_name(int id);
 // ---- uvc_callable.hip: d_tab = n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one the
 // number of runs once the count has run; d_runs: room for that many runs.  The emit follows a count with the same arguments ----
 void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s);

@@ -328,6 +328,42 @@ class SiteReads(_Store):
                                          names, fl.ctypes.data, mq.ctypes.data, lq.ctypes.data, fam.ctypes.data, st.ctypes.data, fr.ctypes.data, ba.ctypes.data, so.ctypes.data))
 
 
+class ClipSites(_Store):
+    """uvcio_clipsites_*: the store behind uvc1-mi355x --clip-sites-out.  add() takes the site rows and event rows of one
+    Region.clip_sites(want_reads=True) with the columns of that call's alignments (any thread, any order; a site comes from one call).
+    write() sorts by (contig id, position, side) and makes the S lines, with_reads the R lines behind them."""
+    add_target = None   # the sites are found, not given
+
+    def __init__(self, min_mapq=0, min_clip=10, min_reads=3, with_reads=False):
+        d = self._bind("clipsites")
+        d.uvcio_clipsites_open.restype, d.uvcio_clipsites_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        d.uvcio_clipsites_add.restype, d.uvcio_clipsites_add.argtypes = C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                                                  C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _check(d.uvcio_clipsites_open(C.byref(self.h), int(min_mapq), int(min_clip), int(min_reads), int(with_reads)))
+
+    def add(self, tid, contig, rows, events=None, reads=None, qnames=None):
+        """rows, events: the second and third result of Region.clip_sites; reads: the reads the region was given (flag, mapq, fam_id,
+        fam_strand, frag_id); qnames: one name per alignment."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.ndim != 2 or rows.shape[1] != 176:
+            raise ValueError("rows is the second result of Region.clip_sites ([n_sites, 176])")
+        n_ev = 0 if events is None else len(events)
+        if n_ev == 0:
+            _check(dll().uvcio_clipsites_add(self.h, int(tid), contig.encode(), rows.ctypes.data, len(rows), None, 0, 0, None, None, None, None, None, None))
+            return
+        events = np.ascontiguousarray(events)
+        if events.dtype.itemsize != 16 or reads is None or qnames is None:
+            raise ValueError("event rows come with the reads of their call and their names")
+        n = len(qnames)
+        col = lambda k, t: np.ascontiguousarray(reads[k], dtype=t)                      # noqa: E731
+        fl, mq, fam, st, fr = col("flag", np.uint16), col("mapq", np.uint8), col("fam_id", np.int32), col("fam_strand", np.uint8), col("frag_id", np.int32)
+        if min(len(fl), len(mq), len(fam), len(st), len(fr)) < n:
+            raise ValueError("every alignment has a name")
+        names = (C.c_char_p * n)(*[q.encode() if isinstance(q, str) else q for q in qnames])
+        _check(dll().uvcio_clipsites_add(self.h, int(tid), contig.encode(), rows.ctypes.data, len(rows), events.ctypes.data, n_ev, n, names, fl.ctypes.data, mq.ctypes.data, fam.ctypes.data, st.ctypes.data, fr.ctypes.data))
+
+
 class Callable(_Store):
     """uvcio_callable_*: the store behind uvc1-mi355x --callable-out.  Targets are added in report order with their positions inside the
     contig; add_runs takes the runs of one Region.callable and the target of each of its ranges (any thread, any order); write() sorts,

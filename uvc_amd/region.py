@@ -30,6 +30,7 @@ FRAGMENT_PROFILE = _ffi.FRAGMENT_PROFILE     # the sections of the profile row o
 READ_CLASSES = ["R1_fwd", "R1_rev", "R2_fwd", "R2_rev"]   # the read classes of Region.read_profile, in row order (uvcgpu_read_class_name)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
 SITE_READ_KINDS = _ffi.SITE_READ_KINDS       # the observation kinds of Region.site_reads, in id order: A C G T N DEL
+CLIP_READ = np.dtype([(n, np.int32) for n, _ in _ffi.UvcClipRead._fields_])   # UvcClipRead: site read soft_len hard_len
 SITE_READ = np.dtype([(n, np.int32) for n, _ in _ffi.UvcSiteRead._fields_])   # UvcSiteRead: site read q obs ins_q ins_len del_len reserved
 CALLABLE_RUN = np.dtype([("range", np.int32), ("pos_beg", np.int32), ("pos_end", np.int32), ("mask", np.int32)])   # UvcCallableRun
 
@@ -598,6 +599,30 @@ class Region:
         if n.value:
             self._check(fn(self.h, arr.ctypes.data, len(arr), C.byref(req), counts.ctypes.data, out.ctypes.data, n.value, C.byref(n)))
         return out[:n.value].copy(), counts
+
+    def clip_sites(self, ranges, min_mapq=0, min_clip=10, min_reads=3, want_reads=False):
+        """uvcgpu_region_clip_sites: the (position, side) sites inside `ranges` -- (pos_beg, pos_end) pairs as for coverage() -- at which the
+        soft and hard clips of the region's reads pile up: at least min_reads alignments with mapq >= min_mapq whose clip of at least
+        min_clip bases (S + H) ends there.  -> (totals, rows, reads): totals int64 [8] (_ffi.CLIPSITE_TOTALS names the first five); rows
+        int64 [n_sites, UVC_CLIPSITE_ROW], sorted by (pos, side): range, pos, side (0 left, 1 right), reads, reads_fwd, reads_supp,
+        reads_secondary, reads_hard, len_sum, len_max, mapq_sum, spanning and VOTE[32][5], the base votes over the clipped sequence
+        counted outward from the junction (_ffi.CLIPSITE_SECTIONS names the sections, uvcgpu.h has the rules); reads: with want_reads a
+        structured array of CLIP_READ (site: index into rows; read: the alignment's index in the reads as given; soft_len, hard_len), one
+        per event behind a site, ascending by (read, side), else None.  Found and filled on the device; asks for the sizes first, then
+        for the rows.  Legal where read_profile() is."""
+        fn = self._ranges_fn("region_clip_sites", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        arr, rows = _coverage_ranges(ranges)
+        req = _ffi.UvcClipSitesRequest(int(min_mapq), int(min_clip), int(min_reads), int(want_reads))
+        totals = np.zeros(_ffi.ENUMS["UVC_CLIPSITE_NTOTAL"], dtype=np.int64)
+        ns, nr = C.c_int64(0), C.c_int64(0)
+        rc = fn(self.h, arr, len(rows), C.byref(req), totals.ctypes.data, None, 0, C.byref(ns), None, 0, C.byref(nr))
+        if rc != _ffi.ENUMS["UVCGPU_ENOMEM"]:
+            self._check(rc)
+        out = np.zeros((max(ns.value, 1), _ffi.ENUMS["UVC_CLIPSITE_ROW"]), dtype=np.int64)
+        ev = np.zeros(max(nr.value, 1), dtype=CLIP_READ)
+        if rc:
+            self._check(fn(self.h, arr, len(rows), C.byref(req), totals.ctypes.data, out.ctypes.data, ns.value, C.byref(ns), ev.ctypes.data if want_reads else None, nr.value if want_reads else 0, C.byref(nr)))
+        return totals, out[:ns.value].copy(), (ev[:nr.value].copy() if want_reads else None)
 
     def msi(self, ranges, min_tracklen=10, min_units=5, max_unitlen=6):
         """uvcgpu_region_msi: the microsatellite loci whose head lies in `ranges` -- (pos_beg, pos_end) pairs as for coverage() -- as the STR
