@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU-box helper: kernel trace of a short bench run, reduced to a per-step timeline (kernel busy time vs idle gaps) and the hand-off of the
-# P2 phase of the accumulate: how long after the end of the LINK pass k_p2_items and k_frag16 start, and when the side streams' kernels end.
+# P2 phase of the accumulate: how long after the end of the last k_p2_fast pass in front of the join k_p2_items and k_frag16 start, and when
+# the side streams' kernels end.
 #   TRACE_ARGS="--serial --tiles 2" bash scripts/gpu_trace.sh     (one tile alone: the chains show in full)
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out/trace
@@ -32,17 +33,24 @@ for s, e, n in seg:
 print("last step: span %.3f ms, busy %.3f ms, %d launches" % ((prev_end - t0) / 1e6, busy / 1e6, len(seg)))
 # the hand-off behind the P2 phase: the LINK pass is k_p2_fast<true, ...> (or k_p2_fast_split<true, ...>)
 link = [e for e in seg if base(e[2]) in ("k_p2_fast", "k_p2_fast_split") and "<true" in e[2]]
+basep = [e for e in seg if base(e[2]) in ("k_p2_fast", "k_p2_fast_split") and "<false" in e[2]]
+items = [e for e in seg if base(e[2]) == "k_p2_items"]
 thres = [e for e in seg if base(e[2]) == "k_thres"]
-if link:
-    l_end = link[-1][1]
-    print("LINK pass ends at %.1f us" % ((l_end - t0) / 1e3))
+# the last pass of k_p2_fast in front of the join: the LINK pass with UVCGPU_LINK=eager and before DESIGN 6-r8, the base pass since (the
+# completion pass of LINK_M then runs behind k_p5b and is listed with the rest)
+last, what = (link[-1], "LINK pass") if link else (None, "")
+if basep and (not link or (items and link[-1][0] > items[0][0])): last, what = basep[-1], "base pass"
+if last:
+    l_end = last[1]
+    print("%s ends at %.1f us" % (what, (l_end - t0) / 1e3))
     for want in ("k_p2_items", "k_frag_generic", "k_frag16", "k_frag16_split", "k_frag"):
-        hit = [e for e in seg if base(e[2]) == want and e[0] >= link[-1][0]]
-        if hit: print("stall: %s starts %.1f us behind the end of the LINK pass (runs %.1f us)" % (want, (hit[0][0] - l_end) / 1e3, (hit[0][1] - hit[0][0]) / 1e3))
+        hit = [e for e in seg if base(e[2]) == want and e[0] >= last[0]]
+        if hit: print("stall: %s starts %.1f us behind the end of the %s (runs %.1f us)" % (want, (hit[0][0] - l_end) / 1e3, what, (hit[0][1] - hit[0][0]) / 1e3))
     p2_side = ("k_p2_slow", "k_fragstat_fast", "k_win_index", "k_fragstat_sweep", "k_frag_sums", "k_p2_mism")
-    t_fork = thres[-1][1] if thres else link[-1][0]
-    side = [e for e in seg if base(e[2]) in p2_side and e[0] >= t_fork and e[0] < l_end]
-    for s, e, n in side: print("P2-phase side kernel %-28s ends %8.1f us behind the end of the LINK pass" % (n, (e - l_end) / 1e3))
+    t_fork = thres[-1][1] if thres else last[0]
+    t_items = items[0][0] if items else l_end
+    side = [e for e in seg if base(e[2]) in p2_side and e[0] >= t_fork and e[0] < max(l_end, t_items)]
+    for s, e, n in side: print("P2-phase side kernel %-28s ends %8.1f us behind the end of the %s" % (n, (e - l_end) / 1e3, what))
 for g, n in sorted(gaps, reverse=True)[:12]: print("gap %.1f us before %s" % (g / 1e3, n))
 for s, e, n in seg: print("%9.1f %9.1f %s" % ((s - t0) / 1e3, (e - s) / 1e3, n))
 PY

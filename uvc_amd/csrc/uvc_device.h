@@ -201,6 +201,8 @@ struct RegionDev {
                                     // anyway -- family 0: a rare symbol (BASE_NN, every LINK symbol but LINK_M) in the SEG / VQ / BQSUM / FRAG / FAM planes, 1: any symbol in
                                     // FAMINFO32 / 64, 2: any symbol in DUPLEX.  The fill in front of the next accumulate skips what is not marked (uvc_launch_zero_state)
     uint32_t *occ;                  // [npos] bit s: somebody wrote a cell of (s, position) outside the dense-symbol paths (occ_mark); zeroed with the planes, read by the scoring gate
+    uint8_t *link_need, *link_done; // [nwin, padded to a multiple of 4] per 64-position window: somebody reads the bias counters of LINK_M there / the completion pass
+                                    // (k_p2_fast<true, false>) has added them.  Zeroed with the marks above; see link_complete of uvc_host.cpp
     uint32_t *fam_digest;           // [n_generic_work][8]: what P4 leaves per (unit, position) for P5 and the duplex pass (k_fam_p4d / k_fam_p5d / k_duplex_d);
                                     // set_reads allocates it on deep data, and then the family passes take the digest form; NULL: the generic form
     Contrib *table;

@@ -102,6 +102,7 @@ struct uvcgpu_region {
     RegionDev R;
     int32_t *d_dup_units = nullptr; int64_t *d_dup_off = nullptr; int n_dup = 0; int64_t n_dup_work = 0;
     bool has_reads = false, accumulated = false;
+    UvcLinkState link; int link_split = 0;   // the completion pass of LINK_M has been to every window (link_complete); the form the accumulate took (UVCGPU_SPLIT)
     bool reads_given = false;    // set_reads went through for the present region, with or without reads (uvcgpu_region_family_stats)
     // zero fill without what the last accumulate left untouched (RegionDev::dirty, uvc_launch_zero_state)
     Buf<uint8_t> d_dirty{this}; Buf<ZeroPlane> d_zero_planes{this}; int64_t zero_planes_npos = 0;
@@ -137,6 +138,29 @@ static void quiesce(const uvcgpu_region *r) { for (hipStream_t s : { r->stream, 
 static int planes_guard(const uvcgpu_region *r, const char *call) {
     if (!r->accumulated) return fail(UVCGPU_ESTATE, std::string(call) + " before accumulate");
     if (r->state_released) return fail(UVCGPU_ESTATE, "the planes were released by the last score (UvcScoreRequest::release_state)");
+    return 0;
+}
+
+// UVCGPU_TIMING (diagnosis; the one read-back of this path): how many windows the completion pass has been to since the accumulate.  It waits for
+// the handle's stream and copies nwin bytes back, behind every accumulate and every link_complete: a UVCGPU_TIMING run is no timing of the step
+// (the forms lines it prints are for tests and diagnosis; time with the profiler or uvcgpu_region_set_profiling)
+static void link_report(const uvcgpu_region *r, const char *scope) {
+    std::vector<uint8_t> done((size_t)r->R.nwin);
+    if (hipStreamSynchronize(r->stream) != hipSuccess || hipMemcpy(done.data(), r->R.link_done, done.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return; }
+    long long n = 0;
+    for (uint8_t b : done) n += (b != 0);
+    fprintf(stderr, "[uvcgpu link_complete] scope=%s done=%lld of %d windows\n", scope, n, (int)r->R.nwin);
+}
+// The bias counters of LINK_M (its SEG32 / SEG64 cells beyond aDP**, its VQ a1BQ* / a2BQ* cells) are made where somebody reads them: an
+// accumulate leaves them complete in the 64-position windows with an InDel mark, which is all the default gate reads.  Every other reader
+// of those cells calls this first, behind planes_guard: it enqueues the completion pass for the windows of `scope` on the handle's stream,
+// once per window and accumulate.  d_xs: n_xs plane indices on the device (UVC_LINK_POSITIONS).  Nothing is read back.
+static int link_complete(uvcgpu_region *r, int scope, const int32_t *d_xs = nullptr, int64_t n_xs = 0) {
+    if (!r->link.wants(r->accumulated, r->state_released, scope)) return 0;
+    uvc_launch_link_complete(&r->R, &r->P, r->link_split, scope, d_xs, n_xs, nullptr, r->stream);
+    if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "completion pass of LINK_M: launch failed");
+    r->link.enqueued(scope);
+    if (getenv("UVCGPU_TIMING")) link_report(r, scope == UVC_LINK_ALL ? "all" : "positions");
     return 0;
 }
 
@@ -223,6 +247,8 @@ int uvcgpu_params_apply_platform_ex(UvcParams *p, int32_t sequencing_platform, i
     return 0;
 }
 
+// RegionDev::link_need / link_done in the buffer of the dirty marks: 8-byte aligned, a multiple of 4 windows each (k_p2_fast reads a block's four as one word)
+static size_t dirty_bytes(const RegionDev &R) { return (size_t)3 * NSYM * (size_t)R.ndblk; }
 // (Re)binds a handle to a region: side arrays of the reference (C10) and the plane layout.  Device buffers are kept when they are large
 // enough, so that a caller that streams tiles of one size through a handle pays hipMalloc / hipFree once (uvcgpu_region_reset).
 static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t end, const char *refseq) {
@@ -242,7 +268,7 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
         const size_t work_bytes = uvc_rtr_work_bytes(r->npos, vmax, smax, bqm, &scan_tmp);
         if (r->d_refsym.fit(n + 1) != hipSuccess || r->d_rtr.fit(n_rtr) != hipSuccess || r->d_rtr0.fit(n_rtr) != hipSuccess || r->d_fsum.fit(2 * UVC_FSUM_N * n) != hipSuccess
             || r->d_win.fit(16 * (size_t)((r->npos + 63) / 64)) != hipSuccess || r->d_baq.fit(2 * n) != hipSuccess || r->d_state.fit(r->L.total) != hipSuccess || r->d_rtrwork.fit(work_bytes) != hipSuccess
-            || r->d_dirty.fit((size_t)3 * NSYM * (size_t)((r->npos >> UVC_DIRTY_SHIFT) + 2)) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(region planes) failed");
+            || r->d_dirty.fit(uvc_link_marks_bytes((size_t)3 * NSYM * (size_t)((r->npos >> UVC_DIRTY_SHIFT) + 2), (r->npos + 63) / 64)) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(region planes) failed");
         uvc_rtr_bind(&r->rw, r->d_rtrwork, r->npos, vmax, smax, bqm, scan_tmp);
         r->npos_cap = r->npos;
     }
@@ -270,6 +296,8 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
 #undef X
     R.bucket = (int32_t *)(b + r->L.bucket_off); R.p5flag = (uint8_t *)(b + r->L.p5flag_off); R.occ = (uint32_t *)(b + r->L.occ_off);
     R.dirty = r->d_dirty; R.ndblk = (int32_t)((r->npos + ((int64_t)1 << UVC_DIRTY_SHIFT) - 1) >> UVC_DIRTY_SHIFT);
+    R.link_need = r->d_dirty + uvc_link_marks_off(dirty_bytes(R)); R.link_done = R.link_need + uvc_link_marks_stride(R.nwin);   // behind the dirty marks: one fill zeroes both
+    r->link.planes_zeroed();
     R.err = r->d_err;
     HIP_OK(hipMemsetAsync(R.err, 0, 4, r->stream));
     return 0;   // nothing to wait for: the staging memory belongs to the handle and a handle is rebound only when its streams are idle
@@ -574,7 +602,6 @@ int uvcgpu_region_read_quals(uvcgpu_region_t *r, uint8_t *dst, int64_t n) {
 // stream `s`.  When the slab's contents were written under the present layout, only what every accumulate writes and what the last one marked
 // (RegionDev::dirty) is filled; otherwise (first use, the handle was rebound to a region of another length) the whole slab.
 static int zero_state(uvcgpu_region *r, hipStream_t s) {
-    const size_t n_dirty = (size_t)3 * NSYM * (size_t)r->R.ndblk;
     const bool selective = (r->dirty_npos == r->npos && !getenv("UVCGPU_FILL_ALL"));
     r->dirty_npos = 0;   // from here on the slab and the marks describe no layout until the caller's launch went through and restores it
     if (selective) {
@@ -593,7 +620,8 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
     } else {
         HIP_OK(hipMemsetAsync(r->d_state, 0, r->buckets_clean ? r->L.bucket_off : r->L.total, s));
     }
-    HIP_OK(hipMemsetAsync(r->d_dirty, 0, n_dirty, s));
+    HIP_OK(hipMemsetAsync(r->d_dirty, 0, uvc_link_marks_bytes(dirty_bytes(r->R), r->R.nwin), s));   // the marks and link_need / link_done behind them
+    r->link.planes_zeroed();
     return 0;
 }
 
@@ -615,8 +643,14 @@ static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
     }
     const int half = (int)std::round((10.0 / std::log(10.0)) * std::log(r->P.indel_del_to_ins_err_ratio)) / 2;   // main.hpp:1244
     const UvcAccStreams st = { r->stream, r->side, r->side3, r->e_fork, r->e_join, r->e_fork2, r->e_join3, r->e_stat, r->e_alleles };
-    uvc_launch_accumulate(&r->R, &r->P, half, r->d_dup_units, r->n_dup, r->d_dup_off, r->n_dup_work, &st, &r->prof);
+    // UVCGPU_LINK=eager (read on every accumulate, like UVCGPU_SPLIT): every window of LINK_M completed inside the accumulate, for comparison
+    const char *lk_env = getenv("UVCGPU_LINK");
+    const bool link_eager = (lk_env && !strcmp(lk_env, "eager")) || !uvc_acc_p2_plain(&r->R, &r->P);   // (the generic P2 forms make all of LINK_M in their LINK pass, as before 6-r8)
+    r->link_split = uvc_acc_split_windows(&r->R);
+    uvc_launch_accumulate(&r->R, &r->P, half, r->d_dup_units, r->n_dup, r->d_dup_off, r->n_dup_work, &st, link_eager ? 1 : 0, &r->prof);
     HIP_OK(hipGetLastError());
+    r->link.accumulated(link_eager);
+    if (getenv("UVCGPU_TIMING")) link_report(r, link_eager ? "all" : "indel");
     r->buckets_clean = (r->P.inferred_is_vcf_generated != 0);   // k_frag (P3b) and k_p5b cleared every bucket they consumed
     r->dirty_npos = r->npos;   // the slab and the marks now describe this layout
     r->accumulated = true; r->gap_ready = false; r->hap_ready = false;
@@ -680,6 +714,7 @@ static int uvcgpu_region_fetch_impl(uvcgpu_region_t *r, int32_t g, void *dst, in
     if (!r || !dst || g < 0 || g >= UVC_NUM_FIELD_GROUPS) return fail(UVCGPU_EINVAL, "bad argument");
     if (uvc_group_in_slab(g)) { const int rcg = planes_guard(r, "fetch"); if (rcg) return rcg; }
     if ((int64_t)uvc_group_bytes(g, r->npos) != dst_bytes) return fail(UVCGPU_EINVAL, "bad destination size");
+    { const int rcl = link_complete(r, uvc_link_fetch_scope(g)); if (rcl) return rcl; }   // the groups with bias counters of LINK_M
     int rc = uvcgpu_region_sync(r);
     if (rc) return rc;
     const void *src = (g == UVC_F_RTR) ? (const void *)(r->accumulated ? r->d_rtr : r->d_rtr0) /* P1b's edit of indelphred exists after accumulate only */ : (g == UVC_F_BAQ) ? (const void *)r->d_baq : (const void *)(r->d_state + r->L.off[g]);
@@ -707,6 +742,7 @@ static int uvcgpu_region_fetch_columns_impl(uvcgpu_region_t *r, const int32_t *r
     if (!tmp.get(&d_xs, (size_t)n)) return fail(UVCGPU_ENOMEM, "hipMalloc(column positions) failed");
     if (!tmp.get(&d_out, (size_t)n * ncol)) return fail(UVCGPU_ENOMEM, "hipMalloc(columns) failed");
     hipError_t e = hipMemcpyAsync(d_xs, xs.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) { const int rcl = link_complete(r, uvc_link_columns_scope(), d_xs, n); if (rcl) return rcl; }   // a row holds the bias counters of LINK_M at its position
     if (e == hipSuccess) { uvc_launch_gather_columns(base, first, elem, r->npos, d_xs, n, d_out, r->stream); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(dst, d_out, sizeof(long long) * (size_t)n * ncol, hipMemcpyDeviceToHost, r->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
@@ -1045,6 +1081,9 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
         if (rq.pos_beg < r->beg + (rq.base_at_pos_beg ? 1 : 0) || rq.pos_end > r->end - 1 || rq.pos_end < rq.pos_beg) return fail(UVCGPU_EINVAL, "score range outside the region");
         npos_scored = (int64_t)rq.pos_end - rq.pos_beg;
     }
+    // The default gate opens a LINK group only at a position with an InDel mark (gate_count: one symbol in the mask and min_altdp_thres > 0
+    // give no record), and the accumulate has completed LINK_M in those windows.  Every other gate can open one anywhere.
+    { const int rcl = link_complete(r, uvc_link_score_scope(rq.all_out, r->P.should_output_all, r->P.tumor_vcf_is_provided, rq.n_force_sites, r->P.min_altdp_thres)); if (rcl) return rcl; }
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
     UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; UvcScoreRangeDev *d_rg = nullptr;

@@ -122,6 +122,22 @@ DEV void seg_store(const RegionDev &R, const SegAcc &A, int sym, int64_t x) {
     if (A.bq) BQS(R, sym, x) = A.bq;
 }
 
+// The completion pass of LINK_M (k_p2_fast<true, false>): everything of A but the five cells the base pass has stored (aDP**, BQSUM), added
+// to what k_p2_items put there since.  The lane owns its cells while the pass runs and no other writer does: load, add, store.
+DEV constexpr bool seg_is_adp(int f) { return f == UVC_S_aDPff || f == UVC_S_aDPfr || f == UVC_S_aDPrf || f == UVC_S_aDPrr; }
+template <bool WITH5>   // WITH5 (the generic forms): the five cells too, nobody has stored them
+DEV void seg_add_link(const RegionDev &R, const SegAcc &A, int64_t x) {
+    if (WITH5 && A.bq) BQS(R, UVC_LINK_M, x) += A.bq;
+#pragma unroll
+    for (int f = 0; f < UVC_NSEG32; f++) if (A.s[f] && (WITH5 || !seg_is_adp(f))) S32(R, f, UVC_LINK_M, x) += A.s[f];
+#pragma unroll
+    for (int f = 0; f < UVC_NSEG64; f++) if (A.l[f]) S64(R, f, UVC_LINK_M, x) += A.l[f];
+    if (A.a1BQf) VQP(R, UVC_VQ_a1BQf, UVC_LINK_M, x) += A.a1BQf;
+    if (A.a1BQr) VQP(R, UVC_VQ_a1BQr, UVC_LINK_M, x) += A.a1BQr;
+    if (A.a2BQf) VQP(R, UVC_VQ_a2BQf, UVC_LINK_M, x) += A.a2BQf;
+    if (A.a2BQr) VQP(R, UVC_VQ_a2BQr, UVC_LINK_M, x) += A.a2BQr;
+}
+
 struct PosThres { int t[UVC_NTHRES]; };
 
 // per-read quantities that dealwith_segbias needs; all wave-uniform in the fast kernels
@@ -1192,12 +1208,17 @@ DEV void mis_apply(const RegionDev &R, const UvcParams &P, const MisItem &it) {
 // which halves the accumulator footprint and doubles the waves per SIMD.
 // SPLIT (see k_prep_fast): a block per window, its four waves take every fourth chunk of the window's entries; their counters are added up
 // in LDS (red: one slot per counter and lane) and stored by the four waves together.
-#define P2_RED_SLOTS (UVC_NSEG32 + 2 * UVC_NSEG64 + 5)
+#define P2_RED_LINK5 (UVC_NSEG32 + 2 * UVC_NSEG64 + 5)   // base pass: the four aDP** rows and the BQSUM row of LINK_M, behind the rows of its own symbol
+#define P2_RED_SLOTS (P2_RED_LINK5 + 5)
 // the 64-bit counter f of the LDS reduction area: two int rows of 64 = one row of 64 unsigned long long
 DEV unsigned long long *red64(int (*red)[64], int f) { return (unsigned long long *)&red[UVC_NSEG32 + 2 * f][0]; }
 template <bool DO_L, bool DO_B, bool PLAIN, bool SPLIT = false>
 DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *amp2, MisItem (*misq)[DO_B ? MISQ_CAP : 1], int (*red)[64] = nullptr) {
     COARSE_T(ct0)
+    if (DO_L) {   // the completion pass runs a window only where a reader asked for it and no earlier pass has been (block-uniform; the waves look again below)
+        if (SPLIT) { const int w = xcd_block(); if (!uvc_link_window_runs(R.link_need[w], R.link_done[w])) return; }
+        else { const int b = xcd_block(); if (!(((const uint32_t *)R.link_need)[b] & ~((const uint32_t *)R.link_done)[b] & 0x01010101u)) return; }
+    }
     {
         for (int v = (int)threadIdx.x - AMP_LO; v < 256; v += 256) {   // (a threshold of 0 would divide by zero for a value below it, as the reference does: uvcgpu_params_check refuses a negative addend beside such a threshold, so that entry is never read)
             const int d1 = P.bias_thres_PFBQ1 * P.bias_thres_PFBQ1, d2 = P.bias_thres_PFBQ2 * P.bias_thres_PFBQ2;
@@ -1210,6 +1231,7 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     const int wave = SPLIT ? wave_uniform((int)xcd_block()) : wave_uniform((int)((xcd_block() * blockDim.x + threadIdx.x) >> 6));
     const int64_t x0 = (int64_t)wave * 64;
     if (x0 >= R.npos) return;   // (block-uniform in the split form)
+    if (DO_L && !SPLIT && !uvc_link_window_runs(R.link_need[wave], R.link_done[wave])) return;
     if (SPLIT) { for (int i2 = threadIdx.x; i2 < P2_RED_SLOTS * 64; i2 += 256) (&red[0][0])[i2] = 0; __syncthreads(); }
     const int w0 = R.beg + (int)x0;
     const int p = w0 + lane;
@@ -1225,10 +1247,14 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     SegAcc Aref, Alink;   // only the one selected by the template arguments stays live
     Aref.zero(); Alink.zero();
     // LINK_M value of a simple read at this position is a per-position constant up to the read's penalty (main.hpp:1919-1923)
+    // The plain base pass carries the five cells of LINK_M that P3 reads; the generic forms (IonTorrent, amplicon, primer, short reads) keep the
+    // parent's split of the work -- there the LINK pass makes all 39 cells, over every window, inside the accumulate (the host forces eager)
+    constexpr bool L5_BASE = DO_B && PLAIN, L5_LINK = DO_L && !PLAIN;
     int noindel80 = 80;
-    if (DO_L && valid && x > 0) noindel80 = imin(80, imin(RTRP(R, UVC_RTR_indelphred, x - 1), RTRP(R, UVC_RTR_indelphred, x)));
+    if ((DO_L || L5_BASE) && valid && x > 0) noindel80 = imin(80, imin(RTRP(R, UVC_RTR_indelphred, x - 1), RTRP(R, UVC_RTR_indelphred, x)));
     MisItem *myq = misq[DO_B ? (threadIdx.x >> 6) : 0];
     int nq = 0;   // wave-uniform: only updated in uniform control flow
+    int l5_bq = 0;   // base pass: BQSUM of LINK_M (see l5_dp)
     auto flush_queue = [&]() {
         int base = 0;
         if (lane == 0) base = atomicAdd(R.mis_cnt, nq);
@@ -1244,6 +1270,9 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     auto run_list = [&](auto IS, auto ST, int cls) {
     constexpr bool ISRC = decltype(IS)::value, STRAND = decltype(ST)::value;
     const int lo = wave_uniform(win_lo(R, 1 + cls, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 1 + cls, (int)(x0 >> 6)));
+    // The base pass also counts the five cells of LINK_M that the fragment kernels read at every position (maxq_at): the aDP** counter of this
+    // list's class and BQSUM, from the cover / hasL / incL expressions of the LINK pass.  The other 34 cells of LINK_M wait for a reader.
+    int l5_dp = 0;
     for (int k0 = lo + (SPLIT ? 64 * (int)(threadIdx.x >> 6) : 0); k0 < hi; k0 += (SPLIT ? 256 : 64)) {
         int c[16];
         if (DO_B) load_words(R.frec2 + (k0 + lane), k0 + lane < hi, c);   // (the LINK-only pass reads its records through the scalar cache, below)
@@ -1292,6 +1321,7 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
                 if (cover && !hasB) { MisItem it; it.rank = K(FR_W(aln)); it.epos = p; it.symval = sym | (inc << 8); myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = it; }
                 nq += (int)__builtin_popcountll(mm);
             }
+            if (L5_BASE) { const wmask ml = BAL(cover & (p > apos)); addm(l5_dp, ml); l5_bq += selm(ml, incL); }
             // a pass with one side acts on a lane iff that side has something there (one exec-mask level instead of cover, then hasL / hasB inside)
             constexpr bool ONE_SIDE = (DO_B != DO_L);
             if (!ONE_SIDE ? cover : (DO_B ? (cover & hasB) : (cover & hasL))) {
@@ -1354,6 +1384,11 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
         if (DO_B) Aref.fold();
         if (DO_L) Alink.fold();
     }
+    if (L5_BASE && l5_dp) {
+        constexpr int f = (STRAND ? (ISRC ? UVC_S_aDPrr : UVC_S_aDPrf) : (ISRC ? UVC_S_aDPfr : UVC_S_aDPff));
+        if (SPLIT) atomicAdd(&red[P2_RED_LINK5 + cls][lane], l5_dp);
+        else if (valid) S32(R, f, UVC_LINK_M, x) = l5_dp;
+    }
     };
     COARSE_T(ct1)
     run_list(std::false_type{}, std::false_type{}, 0);
@@ -1365,34 +1400,46 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     if (SPLIT) {   // the four partial sets -> LDS -> one set (the two passes own different symbols: one symbol per kernel)
         const SegAcc &A = (DO_B ? Aref : Alink);
 #pragma unroll
-        for (int f = 0; f < UVC_NSEG32; f++) if (A.s[f]) atomicAdd(&red[f][lane], A.s[f]);
+        for (int f = 0; f < UVC_NSEG32; f++) if (A.s[f] && !(DO_L && !L5_LINK && seg_is_adp(f))) atomicAdd(&red[f][lane], A.s[f]);
 #pragma unroll
         for (int f = 0; f < UVC_NSEG64; f++) if (A.l[f]) atomicAdd(&red64(red, f)[lane], (unsigned long long)A.l[f]);
         if (A.a1BQf) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 0][lane], A.a1BQf);
         if (A.a1BQr) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 1][lane], A.a1BQr);
         if (A.a2BQf) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 2][lane], A.a2BQf);
         if (A.a2BQr) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 3][lane], A.a2BQr);
-        if (A.bq) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 4][lane], A.bq);
+        if ((DO_B || L5_LINK) && A.bq) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 4][lane], A.bq);
+        if (L5_BASE && l5_bq) atomicAdd(&red[P2_RED_LINK5 + 4][lane], l5_bq);
         __syncthreads();
+        if (DO_L && threadIdx.x == 0) R.link_done[xcd_block()] = 1;
         if (!valid) return;
         const int sym = (DO_B ? my_ref : UVC_LINK_M), wv = (int)(threadIdx.x >> 6);
-        for (int f = wv; f < UVC_NSEG32; f += 4) { const int v = red[f][lane]; if (v) S32(R, f, sym, x) = v; }
-        for (int f = wv; f < UVC_NSEG64; f += 4) { const long long v = (long long)red64(red, f)[lane]; if (v) S64(R, f, sym, x) = v; }
+        // the base pass is the first writer of its cells: plain stores.  The completion pass adds to what k_p2_items has put there (seg_add_link)
+        auto put = [](auto &cell, auto v) { if (DO_L) cell += v; else cell = v; };
+        for (int f = wv; f < UVC_NSEG32; f += 4) { const int v = red[f][lane]; if (v) put(S32(R, f, sym, x), v); }
+        for (int f = wv; f < UVC_NSEG64; f += 4) { const long long v = (long long)red64(red, f)[lane]; if (v) put(S64(R, f, sym, x), v); }
         if (wv == 0) {
             const int b0 = UVC_NSEG32 + 2 * UVC_NSEG64;
-            if (red[b0][lane]) VQP(R, UVC_VQ_a1BQf, sym, x) = red[b0][lane];
-            if (red[b0 + 1][lane]) VQP(R, UVC_VQ_a1BQr, sym, x) = red[b0 + 1][lane];
-            if (red[b0 + 2][lane]) VQP(R, UVC_VQ_a2BQf, sym, x) = red[b0 + 2][lane];
-            if (red[b0 + 3][lane]) VQP(R, UVC_VQ_a2BQr, sym, x) = red[b0 + 3][lane];
-            if (red[b0 + 4][lane]) BQS(R, sym, x) = red[b0 + 4][lane];
+            if (red[b0][lane]) put(VQP(R, UVC_VQ_a1BQf, sym, x), red[b0][lane]);
+            if (red[b0 + 1][lane]) put(VQP(R, UVC_VQ_a1BQr, sym, x), red[b0 + 1][lane]);
+            if (red[b0 + 2][lane]) put(VQP(R, UVC_VQ_a2BQf, sym, x), red[b0 + 2][lane]);
+            if (red[b0 + 3][lane]) put(VQP(R, UVC_VQ_a2BQr, sym, x), red[b0 + 3][lane]);
+            if ((DO_B || L5_LINK) && red[b0 + 4][lane]) put(BQS(R, sym, x), red[b0 + 4][lane]);
+        }
+        if (L5_BASE && wv == 1) {   // the five cells of LINK_M
+            const int l0 = P2_RED_LINK5;
+            if (red[l0][lane]) S32(R, UVC_S_aDPff, UVC_LINK_M, x) = red[l0][lane];
+            if (red[l0 + 1][lane]) S32(R, UVC_S_aDPfr, UVC_LINK_M, x) = red[l0 + 1][lane];
+            if (red[l0 + 2][lane]) S32(R, UVC_S_aDPrf, UVC_LINK_M, x) = red[l0 + 2][lane];
+            if (red[l0 + 3][lane]) S32(R, UVC_S_aDPrr, UVC_LINK_M, x) = red[l0 + 3][lane];
+            if (red[l0 + 4][lane]) BQS(R, UVC_LINK_M, x) = red[l0 + 4][lane];
         }
         return;
     }
+    if (DO_L && lane == 0) R.link_done[wave] = 1;
     if (!valid) return;
-    // k_p2_fast runs before every other writer of these planes (k_p2_mism, k_p2_items), and the two instantiations own
-    // different symbols: plain stores
-    if (DO_B) seg_store(R, Aref, my_ref, x);
-    if (DO_L) seg_store(R, Alink, UVC_LINK_M, x);
+    // the base pass runs before every other writer of its planes (k_p2_mism, k_p2_items): plain stores, also for its five cells of LINK_M
+    if (DO_B) { seg_store(R, Aref, my_ref, x); if (L5_BASE && l5_bq) BQS(R, UVC_LINK_M, x) = l5_bq; }
+    if (DO_L) seg_add_link<L5_LINK>(R, Alink, x);
 #ifdef UVC_FRAG_COARSE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     COARSE_T(ct3)
@@ -3801,6 +3848,19 @@ extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d
 // The form each pass of the accumulate takes: decided once from the tile's shape, the parameters and the families' flags, then printed
 // (UVCGPU_TIMING) and launched from the same flags.
 struct AccForms { bool vcf, proton, split_windows, p2_plain, frag_plain, h16, fam, digest, duplex; int n_gen; };
+// UVCGPU_SPLIT is read on every accumulate; the handle remembers the answer for the completion passes that follow that accumulate
+extern "C" int uvc_acc_split_windows(const RegionDev *R) {
+    const char *sp_env = getenv("UVCGPU_SPLIT");
+    const long long per_window = (long long)R->n_fast2 * (R->max_p2_span + 64) / (R->npos > 0 ? R->npos : 1);
+    return (sp_env ? (atoi(sp_env) != 0) : (R->nwin < 4 * 1024 && per_window >= 1024)) ? 1 : 0;
+}
+// P2: no IonTorrent values, no amplicon-flagged family, no primer length, median read length at or above
+// microadjust_median_readlen_thres: the specialisation without those arms
+static bool p2_plain_form(const RegionDev *R, const UvcParams *P) {
+    return UVC_PLATFORM_IONTORRENT != P->inferred_sequencing_platform && !R->any_amplicon && !(P->primerlen > 0 && !(0x2 & P->primer_flag)) && (P->central_readlen >= P->microadjust_median_readlen_thres);
+}
+// (the host forces UVCGPU_LINK=eager on the generic forms: their base pass does not carry the five cells of LINK_M)
+extern "C" int uvc_acc_p2_plain(const RegionDev *R, const UvcParams *P) { return p2_plain_form(R, P) ? 1 : 0; }
 static AccForms acc_forms(const RegionDev *R, const UvcParams *P, int n_dup) {
     AccForms F;
     F.vcf = (P->inferred_is_vcf_generated != 0);
@@ -3808,12 +3868,8 @@ static AccForms acc_forms(const RegionDev *R, const UvcParams *P, int n_dup) {
     // fewer windows than four per SIMD, and many reads on each (at least sixteen chunks of 64: at 300x a wave of the split form would get fewer
     // than two and pay its prologue for them -- twice as slow on the 1 Mb tile): a block per window in the kernels that can share a window's
     // reads among its waves (UVCGPU_SPLIT=0 / 1 forces)
-    const char *sp_env = getenv("UVCGPU_SPLIT");
-    const long long per_window = (long long)R->n_fast2 * (R->max_p2_span + 64) / (R->npos > 0 ? R->npos : 1);
-    F.split_windows = sp_env ? (atoi(sp_env) != 0) : (R->nwin < 4 * 1024 && per_window >= 1024);
-    // P2: no IonTorrent values, no amplicon-flagged family, no primer length, median read length at or above
-    // microadjust_median_readlen_thres: the specialisation without those arms
-    F.p2_plain = !F.proton && !R->any_amplicon && !(P->primerlen > 0 && !(0x2 & P->primer_flag)) && (P->central_readlen >= P->microadjust_median_readlen_thres);
+    F.split_windows = (uvc_acc_split_windows(R) != 0);
+    F.p2_plain = p2_plain_form(R, P);
     // P3: no IonTorrent values, no SSCS table cap, no padded deletions
     F.frag_plain = F.vcf && !F.proton && !(0x1 & P->fam_flag) && !(P->microadjust_padded_deletion_flag & 0x1);
     F.h16 = (R->max_frag_depth < 65536) && !R->frag32;   // two 16-bit bucket counters per LDS word
@@ -3851,13 +3907,33 @@ static bool prep_scan_exact(const RegionDev *R, const UvcParams *P) {
     const long long m = (m_str > m_non ? m_str : m_non);
     return ((long long)R->max_p2_span + PSCAN_TILE) * m / 10 + 2 < (1LL << 30);
 }
-// one pass of k_p2_fast over the P2 work list: LINK_M (DO_L) or the base symbols (DO_B), in the form F names
+// one pass of k_p2_fast over the P2 work list: the base symbols with the five cells of LINK_M that P3 reads (DO_B), or the completion pass of
+// LINK_M (DO_L), a block per window (split) or a wave per window
 template <bool DO_L, bool DO_B>
-static void launch_p2_fast(const char *kname, const AccForms &F, const RegionDev *R, const UvcParams *P, unsigned nwin, UvcProf *prof, hipStream_t s) {
-    if (F.split_windows && F.p2_plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
-    else if (F.split_windows) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
-    else if (F.p2_plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
+static void launch_p2_fast(const char *kname, bool split, bool plain, const RegionDev *R, const UvcParams *P, UvcProf *prof, hipStream_t s) {
+    const unsigned nwin = nblk(R->npos, 256);   // 4 waves x 64 positions per block
+    if (split && plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
+    else if (split) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
+    else if (plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
     else TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, false>), dim3(nwin), dim3(256), 0, s, *R, *P));
+}
+// The bias counters of LINK_M beyond the five cells of the base pass are made where somebody reads them.  RegionDev::link_need
+// says which 64-position windows a reader wants, link_done which ones the completion pass has been to; both are zeroed with the planes.
+//   UVC_LINK_INDEL      windows with an InDel (or LINK_NN) mark in RegionDev::occ: the only LINK groups the default gate opens (gate_count)
+//   UVC_LINK_POSITIONS  windows of the n_xs plane indices d_xs (out-of-range entries are skipped)
+//   UVC_LINK_ALL        every window
+// The pass adds to cells that k_p2_items may have added to, in either order; a window is run once.
+__global__ void __launch_bounds__(256) k_link_mark(RegionDev R, const int32_t *xs, int64_t n_xs) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (xs) { if (t < n_xs) { const int x = xs[t]; if (x >= 0 && x < R.npos) R.link_need[x >> 6] = 1; } }
+    else if (t < R.npos && uvc_link_occ_marks(R.occ[t])) R.link_need[t >> 6] = 1;
+}
+extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split, int scope, const int32_t *d_xs, int64_t n_xs, UvcProf *prof, hipStream_t s) {
+    if (!P->inferred_is_vcf_generated) { hipMemsetAsync(R->link_done, 1, (size_t)R->nwin, s); return; }   // no P2 on a FASTQ-only run: the planes are complete as they are
+    if (scope == UVC_LINK_ALL) hipMemsetAsync(R->link_need, 1, (size_t)R->nwin, s);
+    else if (scope == UVC_LINK_POSITIONS) { if (n_xs <= 0) return; hipLaunchKernelGGL(k_link_mark, dim3(nblk(n_xs, 256)), dim3(256), 0, s, *R, d_xs, n_xs); }
+    else hipLaunchKernelGGL(k_link_mark, dim3(nblk(R->npos, 256)), dim3(256), 0, s, *R, (const int32_t *)nullptr, (int64_t)0);
+    launch_p2_fast<true, false>("k_p2_fast_link", split != 0, p2_plain_form(R, P), R, P, prof, s);
 }
 
 // The launches of one accumulate and what orders them (the same table: DESIGN 6-r7).  "reads": what another kernel of the accumulate writes;
@@ -3879,28 +3955,32 @@ static void launch_p2_fast(const char *kname, const AccForms &F, const RegionDev
 // 10  k_fragstat_sweep, sweep list    S3  table (7); behind the record stores of 8                  n_cov / n_near of frags and ffast
 // 11  k_fragstat_sweep, overflow      S3  overflow list and count (8), table (7)                    n_cov / n_near of frags and ffast
 // 12  k_frag_sums                     S3  ffast with n_cov / n_near (8, 10, 11), index 5-6 (9)      fsum
-// 13  k_p2_fast, base symbols         M   THRES (5), index 1-4 (1)                                  SEG32 / SEG64 / BQSUM / VQ a*BQ* of the reference symbol: plain stores; mismatch queue
+// 13  k_p2_fast, base symbols         M   THRES, RTR.indelphred (5), index 1-4 (1)                  SEG32 / SEG64 / BQSUM / VQ a*BQ* of the reference symbol and the five cells of LINK_M
+//                                                                                                   that rows 19 and 20 read (SEG32 aDP**, BQSUM): plain stores; mismatch queue
 // 14  k_p2_mism                       S2  mismatch queue (13 [e_fork2]); atomics behind the stores of 13   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
-// 15  k_p2_fast, LINK_M               M   THRES, RTR.indelphred (5)                                 the same planes of LINK_M: plain stores (no other writer of LINK_M cells before 18)
+// 15  (UVCGPU_LINK=eager only: row 23 with every window, here)
 //     -- join: M behind 14 [e_join] and 12 [e_join3]; S2 behind 12 [e_join3] --
 // 16  k_gap_keys .. k_gap_rows_fin    S2  gap events (7 [e_join3])                                  InDel allele tables; fam2_ins_len complete at [e_alleles]
 // 17  k_fam_stat                      S3  table (7), ffast_u (8)                                    unit records (fss) -> [e_stat]
-// 18  k_p2_items                      M   items (6 [e_join]), THRES (5); atomics behind the stores of 13 and 15   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
-// 19  k_frag_generic                  M   SEG32 aDP*, BQSUM (13, 14 [e_join], 15, 18), table (7 [e_join3]), ffast, n_cov / n_near (8, 10, 11 [e_join3])
+// 18  k_p2_items                      M   items (6 [e_join]), THRES (5); atomics behind the stores of 13   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
+// 19  k_frag_generic                  M   SEG32 aDP*, BQSUM (13, 14 [e_join], 18), table (7 [e_join3]), ffast, n_cov / n_near (8, 10, 11 [e_join3])
 //                                                                                                   FRAG, FAM, VQ bMQ (atomics), global buckets
 // 20  k_frag16 / k_frag               M   SEG32 aDP*, BQSUM (as 19), fsum (12 [e_join3]), ffast, index 5-6, global buckets (19)   FRAG, FAM, VQ b*, buckets
 // 21  k_fam_p4* / k_fam_p5* / k_duplex*  M  unit records (17 [e_stat]), fam2_ins_len (16 [e_alleles]), table, ffast_u, index 7 (1)   FAM, family info planes, buckets
 // 22  k_p5b                           M   buckets, p5flag (20, 21)                                  VQ, buckets cleared
 //     -- M behind 16 [e_fork2, recorded again on S2: gap_tables, the MSI call and set_reads wait for this last record] --
+// 23  k_link_mark, k_p2_fast LINK_M   M   occ (6, 18-21), THRES, RTR.indelphred (5), index 1-4 (1)  link_need; the other 34 cells of LINK_M in the marked windows, added to what 18 left
+//                                                                                                   there (load, add, store: no other writer of these cells runs); link_done
 // Rows 19 and 20 read, per position, the aDP* and BQSUM sums that row 18 adds to: k_p2_items cannot run beside the fragment kernels.
 // Row 3 cannot be forked in front of rows 1 and 2: a store of row 2 would overwrite what row 3 has added.
+// Row 23 runs again, for more windows, in front of any later call that reads the bias counters of LINK_M elsewhere (link_complete, uvc_host.cpp).
 extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
-                                      const UvcAccStreams *st, UvcProf *prof) {
+                                      const UvcAccStreams *st, int link_eager, UvcProf *prof) {
     const hipStream_t s = st->s, side = st->side, side3 = st->side3;
     const hipEvent_t e_fork = st->e_fork, e_join = st->e_join, e_fork2 = st->e_fork2, e_join3 = st->e_join3, e_stat = st->e_stat, e_alleles = st->e_alleles;
     const unsigned nwin = nblk(R->npos, 256);   // 4 waves x 64 positions per block
     const AccForms F = acc_forms(R, P, n_dup);
-    if (getenv("UVCGPU_TIMING")) print_forms(F);
+    if (getenv("UVCGPU_TIMING")) { print_forms(F); fprintf(stderr, "[uvcgpu accumulate] link %s\n", link_eager ? "eager" : "lazy"); }
     if (prof) prof->n = 0;
     hipStream_t s2 = (side ? side : s);
     hipStream_t s3 = ((side && side3) ? side3 : s2);   // the two CIGAR walks of the InDel reads are independent, one wave per 64 reads and long: a stream each
@@ -3943,11 +4023,11 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     // main stream: the base symbols first, so that the queued mismatches (rare symbols, atomics: disjoint from the planes the
     // LINK_M pass stores to) are applied on a side stream while the LINK_M pass runs
     if (P->inferred_is_vcf_generated) {
-        launch_p2_fast<false, true>("k_p2_fast_base", F, R, P, nwin, prof, s);
+        launch_p2_fast<false, true>("k_p2_fast_base", F.split_windows, F.p2_plain, R, P, prof, s);
         if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s2, e_fork2, 0); }
         TIMED2(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
-        launch_p2_fast<true, false>("k_p2_fast_link", F, R, P, nwin, prof, s);
     }
+    if (link_eager) uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_ALL, nullptr, 0, prof, s);   // UVCGPU_LINK=eager and the generic forms: where the LINK pass ran before 6-r8
     if (side) {
         hipEventRecord(e_join, s2); hipStreamWaitEvent(s, e_join, 0);
         if (s3 != s2) { hipEventRecord(e_join3, s3); hipStreamWaitEvent(s, e_join3, 0); hipStreamWaitEvent(s2, e_join3, 0); }   // (the allele tables below read the gap events of the table walk)
@@ -4004,6 +4084,8 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     }
     if (P->inferred_is_vcf_generated) TIMED(prof, "k_p5b", hipLaunchKernelGGL(k_p5b, dim3(nblk(R->npos * 2, 256)), dim3(256), 0, s, *R, *P));
     if (side) hipStreamWaitEvent(s, e_fork2, 0);   // the allele tables
+    // every InDel mark of the accumulate exists here (rows 6, 18-21): the windows the default gate can open a LINK group in
+    if (!link_eager) uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_INDEL, nullptr, 0, prof, s);
 }
 
 // ------------------------------------------------------------------------------------------------

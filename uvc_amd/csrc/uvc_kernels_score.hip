@@ -434,6 +434,9 @@ __global__ void __launch_bounds__(128) k_enum(RegionDev R, UvcParams P, ScoreCtx
     const int64_t x = refpos - R.beg;
     const int refidx = zpos - R.beg, refsize = (int)R.npos - 1;
     const int refsymbol = group_refsymbol(R, zpos, st), nsym = st_count(st);
+    // The records of a LINK group read the bias counters of LINK_M at x, which exist only where the completion pass has been (RegionDev::link_done;
+    // the host sends it wherever the request's gate can open a LINK group): a call that got this wrong fails, it never returns empty counters
+    if (st != UVC_BASE_SYMBOL && !R.link_done[x >> 6]) atomicExch(R.err, UVCGPU_EDEVICE);
     unsigned mask = type_mask(R, st, x, refsymbol);
     int bd[8], cd[8];
     const int totBDP = masked_bdepths(R, st, x, mask, bd);

@@ -4,6 +4,7 @@
 #ifndef UVC_LAUNCH_H
 #define UVC_LAUNCH_H
 #include "uvc_device.h"
+#include "uvc_link.h"
 
 // the caller's columns as they are (uvcgpu_region_set_reads) + what uvc_prep.hip derives per read; by value into k_aln_bm / k_aln_prelude.
 // fast_rank: the slot of a simple alignment's entry in RegionDev::frec2, -1 for every other alignment (k_gather4)
@@ -81,8 +82,13 @@ void uvc_launch_build_p2list(const RegionDev *R, const int32_t *fast_rank, const
 void uvc_launch_prelude(const RegionDev *R, const RawReads *W, const UvcParams *P, hipStream_t s);
 void uvc_launch_zero_state(char *slab, const ZeroPlane *planes, int n_planes, uint8_t *dirty, int ndblk, int64_t npos, hipStream_t s);
 void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hipStream_t s);
+// link_eager: the completion pass of LINK_M over every window inside the accumulate (UVCGPU_LINK=eager), else over the windows with an InDel mark at its end
 void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
-                           const UvcAccStreams *st, UvcProf *prof);
+                           const UvcAccStreams *st, int link_eager, UvcProf *prof);
+// the completion pass of LINK_M for a scope of windows (uvc_link.h); split: what uvc_acc_split_windows said at the accumulate
+int uvc_acc_split_windows(const RegionDev *R);
+int uvc_acc_p2_plain(const RegionDev *R, const UvcParams *P);   // the plain P2 forms: only their base pass carries the five cells of LINK_M, so only they can be lazy
+void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split, int scope, const int32_t *d_xs, int64_t n_xs, UvcProf *prof, hipStream_t s);
 void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
 void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
 // ---- uvc_kernels_score.hip ----
