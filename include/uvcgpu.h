@@ -729,6 +729,57 @@ int uvcgpu_region_clip_sites(uvcgpu_region_t *r, const UvcCoverageRange *ranges,
                              int64_t *sites /* [site_capacity][UVC_CLIPSITE_ROW] */, int64_t site_capacity, int64_t *n_sites,
                              UvcClipRead *reads, int64_t read_capacity, int64_t *n_reads);
 const char *uvcgpu_clip_site_section_name(int32_t id);   /* "range" .. "VOTE"; NULL for an id outside 0..UVC_NCLIPSITE - 1 */
+/* ---- clip-site junctions: where the clipped consensus of a site lies on the region's reference (uvc1-mi355x --clip-sites-junctions 1,
+ * DESIGN.md 4r) ----
+ * Per row of uvcgpu_region_clip_sites the call searches the consensus of the site's votes in the reference of the region, on both strands,
+ * and names the other end of the event.  All integers; of a site row only the words pos, side and VOTE are read.
+ *   Reference: the n = npos - 1 positions x in [0, n) with the code refsym[x] of the region's reference character; plane index npos - 1 has
+ *   no reference base and is never part of a placement.  A position is a base iff its code is <= UVC_BASE_T; any other code (N, a gap
+ *   character, ..) mismatches everything.
+ *   Query of a site: for k in 0 .. UVC_CLIPSITE_NCONS - 1, total_k = the sum of the five vote cells of k and winner_k = the code with the
+ *   most votes, ties to the smaller code.  query_len = 1 + the largest k with total_k >= 1, 0 when there is none.  Index k is compared iff
+ *   total_k >= min_votes, winner_k is 0..3 and winner_k's votes * 3 >= total_k * 2 (the upper-case rule of the S line's consensus);
+ *   cmp_len = the number of compared k.  The site is searched iff cmp_len >= min_len.
+ *   Placements: d = +1 for a RIGHT site, -1 for a LEFT site.  The forward placement at t has q[k] facing ref[t + d k]; the reverse placement
+ *   at t has q[k] facing the complement of ref[t - d k].  A placement exists iff all query_len faced positions lie in [0, n); its
+ *   mismatches are the compared k whose faced position is not a base or differs from winner_k.
+ *   Partner junction of a placement, in the convention of a site's pos (plane index; reported absolute, + beg), and the side of the mate:
+ *       RIGHT forward: t, LEFT       LEFT forward: t + 1, RIGHT       RIGHT reverse: t + 1, RIGHT       LEFT reverse: t, LEFT
+ *   A placement counts iff its mismatches are <= max_mismatch and, with max_dist > 0, |partner - pos| <= max_dist.
+ *   hist[m] = the counted placements with exactly m mismatches, m in 0..7 (0 above max_mismatch).  The best placement is the smallest by
+ *   (mismatches, strand with forward first, t); n_best = hist[best_mm]; second_mm = best_mm when n_best >= 2, else the next non-empty bin,
+ *   else -1.
+ *   klass: UVC_CLIPCLASS_INV for a reverse best placement; forward: ADJACENT when partner == pos; RIGHT site: DEL when partner > pos, DUP when
+ *   partner < pos; LEFT site: DEL when partner < pos, DUP when partner > pos.  len = |partner - pos|.
+ *   mate: among the given rows (the site itself included) the one of the expected side whose pos is nearest to partner, at most mate_slop
+ *   away; of two at the same distance the one with the smaller pos; its index in `sites`, -1 when there is none.  The slop absorbs
+ *   microhomology, which moves the two ends of one event apart.
+ *   status: UVC_CLIPJUNC_NOT_SEARCHED (0), UVC_CLIPJUNC_NOT_PLACED (1: searched, no placement counted), UVC_CLIPJUNC_PLACED (2).
+ * junctions: one row of UVC_CLIPJUNC_ROW int64 per site (sections: include/uvc_clipjunc.def): site (the row's index), query_len, cmp_len,
+ *   status, best_mm, n_best, second_mm, partner, strand (0 forward, 1 reverse), klass, len, mate, hist[8], reserved zeros.  Without a
+ *   placement best_mm, second_mm, partner, strand, len and mate are -1, n_best is 0 and klass is UVC_CLIPCLASS_NONE.
+ * totals[UVC_CLIPJUNC_NTOTAL]: sites; sites searched; sites placed; sites placed uniquely (n_best == 1); sites with a mate; three zeros. */
+enum UvcClipJuncSection { UVC_CLIPJUNC_site = 0, UVC_CLIPJUNC_query_len, UVC_CLIPJUNC_cmp_len, UVC_CLIPJUNC_status, UVC_CLIPJUNC_best_mm, UVC_CLIPJUNC_n_best,
+                          UVC_CLIPJUNC_second_mm, UVC_CLIPJUNC_partner, UVC_CLIPJUNC_strand, UVC_CLIPJUNC_klass, UVC_CLIPJUNC_len, UVC_CLIPJUNC_mate,
+                          UVC_CLIPJUNC_hist, UVC_CLIPJUNC_reserved, UVC_NCLIPJUNC };
+enum { UVC_CLIPJUNC_ROW = 24, UVC_CLIPJUNC_NTOTAL = 8, UVC_CLIPJUNC_NHIST = 8, UVC_CLIPJUNC_NOT_SEARCHED = 0, UVC_CLIPJUNC_NOT_PLACED = 1, UVC_CLIPJUNC_PLACED = 2 };
+enum UvcClipJuncTotal { UVC_CLIPJTOTAL_sites = 0, UVC_CLIPJTOTAL_searched, UVC_CLIPJTOTAL_placed, UVC_CLIPJTOTAL_unique, UVC_CLIPJTOTAL_mated };
+enum UvcClipClass { UVC_CLIPCLASS_NONE = 0, UVC_CLIPCLASS_DEL, UVC_CLIPCLASS_DUP, UVC_CLIPCLASS_INV, UVC_CLIPCLASS_ADJACENT, UVC_NCLIPCLASS };
+typedef struct UvcClipJunctionsRequest { int32_t min_votes, min_len, max_mismatch, max_dist, mate_slop; } UvcClipJunctionsRequest;
+/* Searched on the device: the reference packed once per call into 2-bit codes, a 64-bit query word and compare mask per site and strand,
+ * one XOR / popcount per (window, site, strand); the best placement is a 64-bit atomicMin over the packed (mismatches, strand, t), hist is
+ * integer adds: no atomic decides an order, two calls return the same bytes.
+ *   `sites` are n_sites rows as uvcgpu_region_clip_sites returns them, re-uploaded; `junctions` has room for n_sites rows (no sizes-first
+ *   step).  n_sites == 0 gives zero totals and success (sites and junctions may then be NULL).
+ *   Legal from uvcgpu_region_create / _reset on, in every later state of that region: it reads the reference and the caller's rows, no reads
+ *   and no planes; a score stream may be open.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason: a NULL argument; n_sites < 0; min_votes < 1; min_len outside
+ *   1..32; max_mismatch outside 0..7; max_dist < 0; mate_slop < 0; a row whose pos - beg is outside [0, npos) or whose side is not 0 or 1;
+ *   rows not strictly ascending by (pos, side).  A refused call writes nothing. */
+int uvcgpu_region_clip_junctions(uvcgpu_region_t *r, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, int64_t n_sites, const UvcClipJunctionsRequest *req,
+                                 int64_t *junctions /* [n_sites][UVC_CLIPJUNC_ROW] */, int64_t *totals /* [UVC_CLIPJUNC_NTOTAL] */);
+const char *uvcgpu_clip_junction_section_name(int32_t id);   /* "site" .. "reserved"; NULL for an id outside 0..UVC_NCLIPJUNC - 1 */
+const char *uvcgpu_clip_class_name(int32_t klass);           /* "NONE" "DEL" "DUP" "INV" "ADJACENT"; NULL for a class outside 0..4 */
 /* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
  * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
  * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when

@@ -269,11 +269,22 @@ void uvcio_sitereads_close(uvcio_sitereads_t *f);
  *   R contig pos side qname flag mapq soft_len hard_len family_rank strand   with reads = 1 one per event behind the site, ordered by
  *     (family_rank, qname, flag): the 1-based rank of the event's family among the families of the site, ordered by the smallest (qname,
  *     flag) of their events there.
+ * Junctions (uvcgpu_region_clip_junctions, uvc1-mi355x --clip-sites-junctions 1): set_junctions() turns them on and keeps the five request
+ * values; add_junctions() is add() with the call's junction rows ([n_sites][UVC_CLIPJUNC_ROW], one per site row; NULL: add()).  write()
+ * then adds "##clip_sites_junction_min_votes=", "_min_len=", "_max_mismatch=", "_max_dist=" and "_slop=" behind "##clip_sites_reads=", the
+ * "#J" column line behind "#R", and directly behind the S line of every site that came with a junction row
+ *   J contig pos side query_len cmp_len status best_mm n_best second_mm partner_pos(1-based) strand(+|-) class(NONE|DEL|DUP|INV|ADJACENT) len
+ *     mate_pos(1-based) mate_side(L|R)      "." where a field has no value; the mate is written as the position and side of its row.
+ * Of a site that two calls report, the J line is that of the call whose site row is kept.  Without set_junctions the file is the one above.
  * Integers and names only, tab-separated.  A path that ends in .gz is written block-gzipped. */
 typedef struct uvcio_clipsites uvcio_clipsites_t;
 int uvcio_clipsites_open(uvcio_clipsites_t **out, int32_t min_mapq, int32_t min_clip, int32_t min_reads, int32_t with_reads);
 int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads,
                         int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id);
+int uvcio_clipsites_set_junctions(uvcio_clipsites_t *f, int32_t min_votes, int32_t min_len, int32_t max_mismatch, int32_t max_dist, int32_t mate_slop);
+int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, const int64_t *junctions /* [n_sites][UVC_CLIPJUNC_ROW] or NULL */,
+                                  int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id,
+                                  const uint8_t *fam_strand, const int32_t *frag_id);
 int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *path);
 void uvcio_clipsites_close(uvcio_clipsites_t *f);
 /* ---- the read profile (uvc1-mi355x --read-profile-out) ----

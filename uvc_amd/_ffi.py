@@ -115,6 +115,10 @@ class UvcClipRead(C.Structure):
     _fields_ = [("site", C.c_int32), ("read", C.c_int32), ("soft_len", C.c_int32), ("hard_len", C.c_int32)]
 
 
+class UvcClipJunctionsRequest(C.Structure):
+    _fields_ = [("min_votes", C.c_int32), ("min_len", C.c_int32), ("max_mismatch", C.c_int32), ("max_dist", C.c_int32), ("mate_slop", C.c_int32)]
+
+
 class UvcCallableRun(C.Structure):
     _fields_ = [("range", C.c_int32), ("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("mask", C.c_int32)]
 
@@ -221,6 +225,15 @@ assert [ENUMS["UVC_CLIPSITE_" + n] for n, _, _ in CLIPSITE_SECTIONS] == list(ran
 assert sum(w for _, _, w in CLIPSITE_SECTIONS) == ENUMS["UVC_CLIPSITE_ROW"] and all(f == sum(w for _, _, w in CLIPSITE_SECTIONS[:k]) for k, (_, f, _) in enumerate(CLIPSITE_SECTIONS))
 assert CLIPSITE_SECTIONS[-1] == ("VOTE", ENUMS["UVC_CLIPSITE_VOTE_BINS"], ENUMS["UVC_CLIPSITE_NCONS"] * ENUMS["UVC_CLIPSITE_NCODE"]) and C.sizeof(UvcClipRead) == 16 and C.sizeof(UvcClipSitesRequest) == 16
 CLIPSITE_TOTALS = [k[len("UVC_CLIPTOTAL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPTOTAL_")), key=lambda kv: kv[1])]
+
+# the sections of a clip-junction row in id order (UvcClipJuncSection): the table of include/uvc_clipjunc.def, checked against the header's enums
+CLIPJUNC_SECTIONS = _read_def("uvc_clipjunc.def", "UVC_CLIPJUNC")
+assert [ENUMS["UVC_CLIPJUNC_" + n] for n, _, _ in CLIPJUNC_SECTIONS] == list(range(ENUMS["UVC_NCLIPJUNC"]))
+assert sum(w for _, _, w in CLIPJUNC_SECTIONS) == ENUMS["UVC_CLIPJUNC_ROW"] and all(f == sum(w for _, _, w in CLIPJUNC_SECTIONS[:k]) for k, (_, f, _) in enumerate(CLIPJUNC_SECTIONS))
+assert dict((n, w) for n, _, w in CLIPJUNC_SECTIONS)["hist"] == ENUMS["UVC_CLIPJUNC_NHIST"] and C.sizeof(UvcClipJunctionsRequest) == 20
+CLIPJUNC_TOTALS = [k[len("UVC_CLIPJTOTAL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPJTOTAL_")), key=lambda kv: kv[1])]
+CLIP_CLASSES = [k[len("UVC_CLIPCLASS_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPCLASS_")), key=lambda kv: kv[1])]
+assert len(CLIP_CLASSES) == ENUMS["UVC_NCLIPCLASS"]
 
 # the sections of a microsatellite row in id order (UvcMsiSection): the table of include/uvc_msi.def, checked against the header's enums
 MSI_SECTIONS = _read_def("uvc_msi.def", "UVC_MSI")

@@ -39,7 +39,7 @@
 namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
-// The reports beside the VCF, in the order their options are checked: of several faults the first in
+// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o, 4p, 4q with 4r), in the order their options are checked: of several faults the first in
 // this order is the one reported.
 // A row holds what the command line says of a report in more than one place: parse (the path, "a sub-option was given", the checks behind
 // the loop), split_pair (pair mode writes none) and main (the probe of the path).  A new report is a row here, an Opts store, a
@@ -47,7 +47,7 @@ const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-
 enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, R_CLIPSITES, N_REPORTS };
 struct ReportRow {
     const char *out;                 // --X-out PATH
-    const char *subs[6];             // the options that only shape this report: each needs --X-out (the list ends with a null)
+    const char *subs[12];            // the options that only shape this report: each needs --X-out (the list ends with a null)
     const char *window;              // the one of them that cuts the targets into windows (refuse_report_windows), or none
     const char *why_no_shard, *why_no_repeat;   // refuse_report_runs
     const char *pair_writes_no;      // split_pair: "pair mode ... writes no <this>"
@@ -67,7 +67,8 @@ const ReportRow REPORTS[N_REPORTS] = {
     { "--fragment-profile-out", { "--fragment-profile-window", "--fragment-profile-min-mapq", "--fragment-profile-short", "--fragment-profile-long" }, "--fragment-profile-window", "a target can straddle shards",
       "every tile would be counted that many times", "fragment profile", nullptr },
     { "--site-reads-out", { "--site-reads-sites", "--site-reads-min-mapq", "--site-reads-alt-only" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its rows that many times", "site reads report", nullptr },
-    { "--clip-sites-out", { "--clip-sites-min-clip", "--clip-sites-min-reads", "--clip-sites-min-mapq", "--clip-sites-reads" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its sites that many times",
+    { "--clip-sites-out", { "--clip-sites-min-clip", "--clip-sites-min-reads", "--clip-sites-min-mapq", "--clip-sites-reads", "--clip-sites-junctions", "--clip-sites-junction-min-len", "--clip-sites-junction-max-mismatch",
+                            "--clip-sites-junction-min-votes", "--clip-sites-junction-max-dist", "--clip-sites-junction-slop" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its sites that many times",
       "clip sites report", nullptr },
 };
 // the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
@@ -111,6 +112,7 @@ struct Opts {
     uvcio_sitereads_t *sitereads = nullptr; uvcio_sites_t *sitereads_list = nullptr;   // --site-reads-out: the report's store, filled by the workers, and the listed sites (main)
     UvcClipSitesRequest clipsites_req{ 0, 10, 3, 1 }; int32_t clipsites_reads = 0;   // --clip-sites-min-mapq, --clip-sites-min-clip, --clip-sites-min-reads (the call always asks for the event rows); --clip-sites-reads
     uvcio_clipsites_t *clipsites = nullptr;   // --clip-sites-out: the report's store, filled by the workers (main)
+    int32_t clipsites_junctions = 0; UvcClipJunctionsRequest clipjunc_req{ 2, 16, 1, 0, 10 };   // --clip-sites-junctions; --clip-sites-junction-min-votes, -min-len, -max-mismatch, -max-dist, -slop
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
     UvcGroupParams G;
@@ -190,6 +192,12 @@ const OptRow OPTS[] = {
     { "--clip-sites-min-reads", O_CLI, false, "3", "with --clip-sites-out: a site is written when the clips of at least this many alignments end there (1 or more)" },
     { "--clip-sites-min-mapq", O_CLI, false, "0", "with --clip-sites-out: only alignments of at least this mapping quality are counted (0..255)" },
     { "--clip-sites-reads", O_CLI, false, "0", "with --clip-sites-out: 1 (or true) writes an R line per clipped read behind each S line -- name, flag, mapping quality, soft and hard clip length, family rank and strand; 0 (or false) the S lines alone" },
+    { "--clip-sites-junctions", O_CLI, false, "0", "with --clip-sites-out: 1 (or true) searches the consensus of every site's clipped bases in the reference of the site's region, on both strands, and writes a J line behind the S line: where it lies (partner_pos, strand, mismatches, how many equally good places), what that makes of the site (DEL, DUP, INV, ADJACENT), the length and the site that is the other end of the event.  A partner is found only inside the region the site was searched in (the tile with its halo, or the merged BED batch), so J lines depend on how the run is cut; S and R lines do not" },
+    { "--clip-sites-junction-min-len", O_CLI, false, "16", "with --clip-sites-junctions 1: a site is searched when at least this many of its 32 consensus bases are compared (1..32)" },
+    { "--clip-sites-junction-max-mismatch", O_CLI, false, "1", "with --clip-sites-junctions 1: a place counts with at most this many mismatches among the compared bases (0..7)" },
+    { "--clip-sites-junction-min-votes", O_CLI, false, "2", "with --clip-sites-junctions 1: a consensus base is compared when at least this many reads vote there and two thirds of them agree on A, C, G or T (1 or more)" },
+    { "--clip-sites-junction-max-dist", O_CLI, false, "0", "with --clip-sites-junctions 1: only places whose partner junction lies at most this far from the site count; 0 is the whole region" },
+    { "--clip-sites-junction-slop", O_CLI, false, "10", "with --clip-sites-junctions 1: the mate of a site is the nearest site of the expected side at most this far from the partner junction (microhomology moves the two ends apart)" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -440,6 +448,12 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--clip-sites-min-reads") o.clipsites_req.min_reads = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
         else if (n0 == "--clip-sites-min-mapq") o.clipsites_req.min_mapq = (int32_t)whole_number(n0, val(), 0, 255, "a mapping quality from 0 to 255");
         else if (n0 == "--clip-sites-reads") o.clipsites_reads = (int32_t)whole_number(n0, val(), 0, 1, "0 or 1 (false or true)", N_STRTOD_BOOL);
+        else if (n0 == "--clip-sites-junctions") o.clipsites_junctions = (int32_t)whole_number(n0, val(), 0, 1, "0 or 1 (false or true)", N_STRTOD_BOOL);
+        else if (n0 == "--clip-sites-junction-min-len") o.clipjunc_req.min_len = (int32_t)whole_number(n0, val(), 1, UVC_CLIPSITE_NCONS, "a whole number from 1 to 32");
+        else if (n0 == "--clip-sites-junction-max-mismatch") o.clipjunc_req.max_mismatch = (int32_t)whole_number(n0, val(), 0, UVC_CLIPJUNC_NHIST - 1, "a whole number from 0 to 7");
+        else if (n0 == "--clip-sites-junction-min-votes") o.clipjunc_req.min_votes = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
+        else if (n0 == "--clip-sites-junction-max-dist") o.clipjunc_req.max_dist = (int32_t)whole_number(n0, val(), 0, 2e9, "a distance in bp (0 = the whole region)");
+        else if (n0 == "--clip-sites-junction-slop") o.clipjunc_req.mate_slop = (int32_t)whole_number(n0, val(), 0, 2e9, "a distance in bp");
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -490,6 +504,8 @@ Opts parse(int argc, char **argv) {
         }
         refuse_report_runs(o, R.out, R.why_no_shard, R.why_no_repeat);
         if (R.window) refuse_report_windows(o, R.out, R.window, o.report[r].window);
+        if (r == R_CLIPSITES && !o.clipsites_junctions)   // the junction sub-options shape the J lines alone
+            for (int s = 0; R.subs[s]; s++) if (((o.report[r].subs_given >> s) & 1) && !strncmp(R.subs[s], "--clip-sites-junction-", 22)) die(std::string(R.subs[s]) + " needs --clip-sites-junctions 1: it only shapes the J lines");
         if (r == R_SITEREADS && o.sitereads_sites.empty()) die("--site-reads-out needs --site-reads-sites FILE: the report is about the sites of that file");
     }
     if (o.merge > 0) {   // before any file or device
@@ -540,6 +556,7 @@ struct Worker {
     std::vector<int64_t> cov_rows, fam_rows, rp_row, frag_rows;   // --coverage-out, --family-stats-out, --read-profile-out, --fragment-profile-out: what the device call fills
     std::vector<UvcCallableRun> call_runs;   // --callable-out: the runs, as many as the last tiles had
     std::vector<int32_t> sr_sites, sr_counts; std::vector<UvcSiteRead> sr_rows; std::vector<const char *> sr_qnames;   // --site-reads-out: the sites a tile owns, their counts and rows, the names of the rows' alignments
+    std::vector<int64_t> cs_junc;   // --clip-sites-junctions 1: the junction rows of a tile's sites
     std::vector<int64_t> cs_rows; std::vector<UvcClipRead> cs_reads; std::vector<const char *> cs_qnames;   // --clip-sites-out: the site rows and event rows of a tile, as many as the last tiles had, the names of the events' alignments
     std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the loci, as many as the last tiles had
 };
@@ -702,7 +719,13 @@ void clip_sites_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
     if (n_sites == 0) return;
     w.cs_qnames.assign((size_t)k, nullptr);
     for (int64_t i = 0; i < n_reads; i++) { const int32_t a = w.cs_reads[(size_t)i].read; w.cs_qnames[(size_t)a] = b.qnames + b.qname_off[w.order[(size_t)a]]; }
-    if (uvcio_clipsites_add(o.clipsites, t.tid, t.chrom.c_str(), w.cs_rows.data(), n_sites, w.cs_reads.data(), n_reads, k, w.cs_qnames.data(), w.flag.data(), w.mapq.data(), w.fam.data(), w.fstrand.data(), w.frag.data())) die(uvcio_last_error());
+    if (o.clipsites_junctions) {   // right behind the tile's clip-site call, on that call's rows: the partner is looked for in this tile's region
+        int64_t jtotals[UVC_CLIPJUNC_NTOTAL];
+        w.cs_junc.resize((size_t)n_sites * UVC_CLIPJUNC_ROW);
+        if (uvcgpu_region_clip_junctions(w.reg, w.cs_rows.data(), n_sites, &o.clipjunc_req, w.cs_junc.data(), jtotals)) die(uvcgpu_last_error());
+    }
+    if (uvcio_clipsites_add_junctions(o.clipsites, t.tid, t.chrom.c_str(), w.cs_rows.data(), o.clipsites_junctions ? w.cs_junc.data() : nullptr, n_sites, w.cs_reads.data(), n_reads, k, w.cs_qnames.data(), w.flag.data(), w.mapq.data(),
+                                      w.fam.data(), w.fstrand.data(), w.frag.data())) die(uvcio_last_error());
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // The record text of one call behind `lines`: write(dst, room, &len) into a buffer as large as the last tiles needed (+ slack); a second
@@ -1458,6 +1481,7 @@ int main(int argc, char **argv) {
     std::vector<CovSpan> frag_spans((size_t)nref);
     if (wanted(R_FRAGPROF) && uvcio_fragprofile_open(&o.fragprof, o.fragprof_req.min_mapq, o.fragprof_req.short_lo, o.fragprof_req.short_hi, o.fragprof_req.long_lo, o.fragprof_req.long_hi)) die(uvcio_last_error());
     if (wanted(R_CLIPSITES) && uvcio_clipsites_open(&o.clipsites, o.clipsites_req.min_mapq, o.clipsites_req.min_clip, o.clipsites_req.min_reads, o.clipsites_reads)) die(uvcio_last_error());
+    if (o.clipsites && o.clipsites_junctions && uvcio_clipsites_set_junctions(o.clipsites, o.clipjunc_req.min_votes, o.clipjunc_req.min_len, o.clipjunc_req.max_mismatch, o.clipjunc_req.max_dist, o.clipjunc_req.mate_slop)) die(uvcio_last_error());
     if (wanted(R_SITEREADS)) {   // the listed sites, each with its reference base: a site that no tile owns keeps its S line of zeros
         uvcio_sites_t *list = nullptr; uvcio_fasta_t *fa = nullptr;
         if (uvcio_sites_open(&list, o.sitereads_sites.c_str(), G.cnames.data(), nref)) die("--site-reads-sites: " + std::string(uvcio_last_error()));

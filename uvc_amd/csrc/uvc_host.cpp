@@ -119,7 +119,7 @@ struct uvcgpu_region {
     Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
     Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
-    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1380,8 +1380,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads and _clip_sites ----
-// What the nine share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites and _clip_junctions ----
+// What the ten share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1754,6 +1754,104 @@ int uvcgpu_region_clip_sites(uvcgpu_region_t *r, const UvcCoverageRange *ranges,
     return guarded("uvcgpu_region_clip_sites", [&] { return uvcgpu_region_clip_sites_impl(r, ranges, n_ranges, req, totals, sites, site_capacity, n_sites, reads, read_capacity, n_reads); });
 }
 const char *uvcgpu_clip_site_section_name(int32_t id) { return uvc_clipsites_name(id); }
+
+// ---- clip-site junctions (uvc_clipjunc.hip): [the caller's site rows] [the mate lists] [packed reference] [its "not a base"
+// mask] [query rows] [best keys] [hist] [junction rows] ----
+// The call reads the reference of the region and the caller's rows: legal from create / reset on, whatever was done with reads, planes or
+// scores since.  The rows and the two mate lists (the plane indices of the LEFT sites ascending, then those of the RIGHT sites, and the row
+// each belongs to) go up through the staging buffer.  The totals are sums over the returned rows.
+namespace {
+enum {   // the first words of the sections the host reads: of a site row and of a junction row
+#define UVC_CLIPSITE(name, first, words) CS_AT_##name = first,
+#include "uvc_clipsites.def"
+#undef UVC_CLIPSITE
+#define UVC_CLIPJUNC(name, first, words) CJ_AT_##name = first,
+#include "uvc_clipjunc.def"
+#undef UVC_CLIPJUNC
+};
+}
+static int uvcgpu_region_clip_junctions_impl(uvcgpu_region_t *r, const int64_t *sites, int64_t n_sites, const UvcClipJunctionsRequest *req, int64_t *junctions, int64_t *totals) {
+    if (!r) return fail(UVCGPU_EINVAL, "clip_junctions: null region");
+    if (!req || !totals) return fail(UVCGPU_EINVAL, "clip_junctions: req and totals must not be NULL");
+    if (n_sites < 0) return fail(UVCGPU_EINVAL, "clip_junctions: n_sites " + std::to_string(n_sites) + " is negative");
+    if (n_sites > 0 && (!sites || !junctions)) return fail(UVCGPU_EINVAL, "clip_junctions: sites and junctions must not be NULL");
+    if (req->min_votes < 1) return fail(UVCGPU_EINVAL, "clip_junctions: min_votes " + std::to_string(req->min_votes) + " must be at least 1");
+    if (req->min_len < 1 || req->min_len > UVC_CLIPSITE_NCONS) return fail(UVCGPU_EINVAL, "clip_junctions: min_len " + std::to_string(req->min_len) + " is outside 1.." + std::to_string((int)UVC_CLIPSITE_NCONS));
+    if (req->max_mismatch < 0 || req->max_mismatch >= UVC_CLIPJUNC_NHIST) return fail(UVCGPU_EINVAL, "clip_junctions: max_mismatch " + std::to_string(req->max_mismatch) + " is outside 0.." + std::to_string(UVC_CLIPJUNC_NHIST - 1));
+    if (req->max_dist < 0) return fail(UVCGPU_EINVAL, "clip_junctions: max_dist " + std::to_string(req->max_dist) + " is negative");
+    if (req->mate_slop < 0) return fail(UVCGPU_EINVAL, "clip_junctions: mate_slop " + std::to_string(req->mate_slop) + " is negative");
+    if (n_sites > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "clip_junctions: n_sites " + std::to_string(n_sites) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
+    const size_t sites_bytes = sizeof(int64_t) * UVC_CLIPSITE_ROW * (size_t)n_sites, list_bytes = sizeof(int32_t) * (size_t)n_sites, rows_bytes = sizeof(int64_t) * UVC_CLIPJUNC_ROW * (size_t)n_sites;
+    int64_t n_left = 0;
+    for (int64_t k = 0; k < n_sites; k++) {
+        const int64_t *row = sites + k * UVC_CLIPSITE_ROW, pos = row[CS_AT_pos], side = row[CS_AT_side];
+        if (pos < r->beg || pos - r->beg >= r->npos) return fail(UVCGPU_EINVAL, "clip_junctions: row " + std::to_string(k) + " has pos " + std::to_string(pos) + ", outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+        if (side != UVC_CLIPSITE_LEFT && side != UVC_CLIPSITE_RIGHT) return fail(UVCGPU_EINVAL, "clip_junctions: row " + std::to_string(k) + " has side " + std::to_string(side) + ", neither 0 nor 1");
+        const int64_t *prev = row - UVC_CLIPSITE_ROW;
+        if (k > 0 && std::make_pair(prev[CS_AT_pos], prev[CS_AT_side]) >= std::make_pair(pos, side))
+            return fail(UVCGPU_EINVAL, "clip_junctions: row " + std::to_string(k) + " (" + std::to_string(pos) + ", " + std::to_string(side) + ") is not above row " + std::to_string(k - 1) + ": rows ascend strictly by (pos, side)");
+        n_left += (side == UVC_CLIPSITE_LEFT);
+    }
+    memset(totals, 0, sizeof(int64_t) * UVC_CLIPJUNC_NTOTAL);
+    if (n_sites == 0) return 0;
+    // the two mate lists: mpos, midx
+    std::vector<int32_t> lists(2 * (size_t)n_sites);
+    {
+        int32_t *mpos = lists.data(), *midx = mpos + n_sites;
+        int64_t at[2] = { 0, n_left };
+        for (int64_t k = 0; k < n_sites; k++) {
+            const int64_t *row = sites + k * UVC_CLIPSITE_ROW;
+            const int64_t j = at[row[CS_AT_side]]++;
+            mpos[j] = (int32_t)(row[CS_AT_pos] - r->beg); midx[j] = (int32_t)k;
+        }
+    }
+    const size_t ref_bytes = sizeof(uint64_t) * (size_t)uvc_clipjunc_ref_words(r->npos);
+    ReportLayout L;
+    const size_t o_sites = L.take(sites_bytes), o_lists = L.take(2 * list_bytes), o_ref2 = L.take(ref_bytes), o_inv = L.take(ref_bytes), o_query = L.take((size_t)uvc_clipjunc_query_bytes(n_sites));
+    const size_t o_best = L.take(sizeof(uint64_t) * (size_t)n_sites), o_hist = L.take(sizeof(uint32_t) * UVC_CLIPJUNC_NHIST * (size_t)n_sites), o_rows = L.take(rows_bytes);
+    { int rc1 = report_buffers(r, L.bytes, rows_bytes, "clip junctions"); if (rc1) return rc1; }
+    char *d = r->d_report;
+    {   // the rows and the lists through the staging buffer, one piece behind the other (stage_upload: never a copy from the caller's pages)
+        size_t at = 0;
+        const size_t total = o_ref2;   // (the two pieces lie at the head of the layout, each on a 64-byte boundary, as `at` counts them)
+        { int rc1 = stage_upload(r, d + o_sites, sites, sites_bytes, at, total); if (rc1) return rc1; }
+        { int rc1 = stage_upload(r, d + o_lists, lists.data(), 2 * list_bytes, at, total); if (rc1) return rc1; }
+    }
+    const long long *d_sites = (const long long *)(d + o_sites);
+    const int32_t *d_mpos = (const int32_t *)(d + o_lists), *d_midx = d_mpos + n_sites;
+    unsigned long long *d_ref2 = (unsigned long long *)(d + o_ref2), *d_inv = (unsigned long long *)(d + o_inv), *d_best = (unsigned long long *)(d + o_best);
+    unsigned *d_hist = (unsigned *)(d + o_hist);
+    void *d_query = d + o_query;
+    long long *d_rows = (long long *)(d + o_rows);
+    // with profiling on, four more entries of uvcgpu_region_kernel_times (accumulate starts the list anew)
+    int pi = uvc_prof_begin(&r->prof, "k_clipjunc_pack", r->stream);
+    uvc_launch_clipjunc_pack(&r->R, d_ref2, d_inv, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    pi = uvc_prof_begin(&r->prof, "k_clipjunc_queries", r->stream);
+    uvc_launch_clipjunc_queries(&r->R, d_sites, (int)n_sites, req, d_query, d_best, d_hist, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    pi = uvc_prof_begin(&r->prof, "k_clipjunc_search", r->stream);
+    uvc_launch_clipjunc_search(&r->R, d_ref2, d_inv, d_query, (int)n_sites, req, d_best, d_hist, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    pi = uvc_prof_begin(&r->prof, "k_clipjunc_finish", r->stream);
+    uvc_launch_clipjunc_finish(&r->R, d_query, (int)n_sites, req, d_best, d_hist, d_mpos, d_midx, (int)n_left, d_rows, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    { int rc1 = report_result(r, d_rows, junctions, rows_bytes, false); if (rc1) return rc1; }
+    totals[UVC_CLIPJTOTAL_sites] = n_sites;
+    for (int64_t k = 0; k < n_sites; k++) {
+        const int64_t *row = junctions + k * UVC_CLIPJUNC_ROW;
+        totals[UVC_CLIPJTOTAL_searched] += (row[CJ_AT_status] != UVC_CLIPJUNC_NOT_SEARCHED);
+        totals[UVC_CLIPJTOTAL_placed] += (row[CJ_AT_status] == UVC_CLIPJUNC_PLACED);
+        totals[UVC_CLIPJTOTAL_unique] += (row[CJ_AT_n_best] == 1);
+        totals[UVC_CLIPJTOTAL_mated] += (row[CJ_AT_mate] >= 0);
+    }
+    return 0;
+}
+int uvcgpu_region_clip_junctions(uvcgpu_region_t *r, const int64_t *sites, int64_t n_sites, const UvcClipJunctionsRequest *req, int64_t *junctions, int64_t *totals) {
+    return guarded("uvcgpu_region_clip_junctions", [&] { return uvcgpu_region_clip_junctions_impl(r, sites, n_sites, req, junctions, totals); });
+}
+const char *uvcgpu_clip_junction_section_name(int32_t id) { return uvc_clipjunc_name(id); }
+const char *uvcgpu_clip_class_name(int32_t klass) { return uvc_clipjunc_class_name(klass); }
 
 // ---- callable-region intervals of ranges (uvc_callable.hip): [table] [block counts] [mask bytes] [runs, one per position at worst] ----
 // Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit

@@ -1650,14 +1650,20 @@ enum {
 #define UVC_CLIPSITE(name, first, words) CSW_##name = first,
 #include "uvc_clipsites.def"
 #undef UVC_CLIPSITE
+#define UVC_CLIPJUNC(name, first, words) CJW_##name = first,
+#include "uvc_clipjunc.def"
+#undef UVC_CLIPJUNC
 };
+static_assert(CJW_hist + UVC_CLIPJUNC_NHIST <= UVC_CLIPJUNC_ROW && CJW_mate < CJW_hist, "the words of a J line are query_len .. mate of include/uvc_clipjunc.def");
 static_assert(CSW_VOTE == UVC_CLIPSITE_VOTE_BINS && CSW_VOTE + UVC_CLIPSITE_NCONS * UVC_CLIPSITE_NCODE == UVC_CLIPSITE_ROW && CSW_spanning == CSW_reads + 8,
               "the words of an S line are reads .. spanning of include/uvc_clipsites.def, the votes fill the row behind the counters");
 }
 struct uvcio_clipsites {
     UvcClipSitesRequest req;
     struct Event { std::string qname; int32_t flag, mapq, soft, hard, fam, strand, frag; };
-    struct Site { std::string contig; int64_t row[UVC_CLIPSITE_ROW]; std::vector<Event> events; };
+    // junc: the site's row of uvcgpu_region_clip_junctions, when its call came with them; its mate, an index into the call's rows, as (pos, side)
+    struct Site { std::string contig; int64_t row[UVC_CLIPSITE_ROW]; std::vector<Event> events; bool has_junc = false; int64_t junc[UVC_CLIPJUNC_ROW], mate_pos = -1, mate_side = -1; };
+    bool junctions = false; UvcClipJunctionsRequest jreq{ 0, 0, 0, 0, 0 };   // uvcio_clipsites_set_junctions
     std::map<std::tuple<int32_t, int64_t, int64_t>, Site> sites;   // by (tid, zero-based position, side)
     std::mutex mu;
 };
@@ -1668,8 +1674,14 @@ extern "C" int uvcio_clipsites_open(uvcio_clipsites_t **out, int32_t min_mapq, i
     *out = f;
     return 0;
 }
-extern "C" int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns,
-                                   const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
+extern "C" int uvcio_clipsites_set_junctions(uvcio_clipsites_t *f, int32_t min_votes, int32_t min_len, int32_t max_mismatch, int32_t max_dist, int32_t mate_slop) {
+    if (!f) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
+    f->junctions = true;
+    f->jreq = UvcClipJunctionsRequest{ min_votes, min_len, max_mismatch, max_dist, mate_slop };
+    return 0;
+}
+extern "C" int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, const int64_t *junctions, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads,
+                                             int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
     if (!f || !contig || n_sites < 0 || (n_sites > 0 && !sites) || n_reads < 0) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
     if (n_reads > 0 && (!reads || !qnames || !flag || !mapq || !fam_id || !fam_strand || !frag_id)) return fail(UVCGPU_EINVAL, "clip sites: event rows without the columns of their alignments");
     // what the sites keep is made outside the lock
@@ -1679,6 +1691,13 @@ extern "C" int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char
         memcpy(made[(size_t)s].row, sites + s * UVC_CLIPSITE_ROW, sizeof(int64_t) * UVC_CLIPSITE_ROW);
         const int64_t side = made[(size_t)s].row[CSW_side];
         if (side != UVC_CLIPSITE_LEFT && side != UVC_CLIPSITE_RIGHT) return fail(UVCGPU_EINVAL, "clip sites: site " + std::to_string(s) + " has side " + std::to_string(side));
+        if (!junctions) continue;
+        uvcio_clipsites::Site &m = made[(size_t)s];
+        m.has_junc = true;
+        memcpy(m.junc, junctions + s * UVC_CLIPJUNC_ROW, sizeof(int64_t) * UVC_CLIPJUNC_ROW);
+        const int64_t mate = m.junc[CJW_mate], klass = m.junc[CJW_klass];
+        if (mate >= n_sites || klass < 0 || klass >= UVC_NCLIPCLASS) return fail(UVCGPU_EINVAL, "clip sites: junction row " + std::to_string(s) + " has mate " + std::to_string(mate) + " and class " + std::to_string(klass) + ", which the call does not hold");
+        if (mate >= 0) { m.mate_pos = sites[mate * UVC_CLIPSITE_ROW + CSW_pos]; m.mate_side = sites[mate * UVC_CLIPSITE_ROW + CSW_side]; }
     }
     for (int64_t k = 0; k < n_reads; k++) {
         const UvcClipRead &r = reads[k];
@@ -1697,13 +1716,23 @@ extern "C" int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char
     }
     return 0;
 }
+extern "C" int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns,
+                                   const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
+    return uvcio_clipsites_add_junctions(f, tid, contig, sites, nullptr, n_sites, reads, n_reads, n_alns, qnames, flag, mapq, fam_id, fam_strand, frag_id);
+}
 extern "C" int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *path) {
     if (!f || !path || !*path) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
     typedef uvcio_clipsites::Event Event;
     std::string text = "##clip_sites_min_mapq=" + std::to_string(f->req.min_mapq) + "\n##clip_sites_min_clip=" + std::to_string(f->req.min_clip) + "\n##clip_sites_min_reads=" + std::to_string(f->req.min_reads)
                        + "\n##clip_sites_reads=" + std::to_string(f->req.want_reads)
+                       + (f->junctions ? "\n##clip_sites_junction_min_votes=" + std::to_string(f->jreq.min_votes) + "\n##clip_sites_junction_min_len=" + std::to_string(f->jreq.min_len) + "\n##clip_sites_junction_max_mismatch="
+                                             + std::to_string(f->jreq.max_mismatch) + "\n##clip_sites_junction_max_dist=" + std::to_string(f->jreq.max_dist) + "\n##clip_sites_junction_slop=" + std::to_string(f->jreq.mate_slop)
+                                       : std::string())
                        + "\n#S\tcontig\tpos\tside\treads\tfwd\tsupp\tsecondary\thard\tlen_sum\tlen_max\tmapq_sum\tspanning\tfragments\tfamilies\tfamilies_both_strands\tcons_len\tcons\n"
                          "#R\tcontig\tpos\tside\tqname\tflag\tmapq\tsoft_len\thard_len\tfamily_rank\tstrand\n";
+    if (f->junctions) text += "#J\tcontig\tpos\tside\tquery_len\tcmp_len\tstatus\tbest_mm\tn_best\tsecond_mm\tpartner_pos\tstrand\tclass\tlen\tmate_pos\tmate_side\n";
+    static const char *const classes[UVC_NCLIPCLASS] = { "NONE", "DEL", "DUP", "INV", "ADJACENT" };
+    auto dot = [](int64_t v, int64_t add) { return v < 0 ? std::string(".") : std::to_string(v + add); };
     for (const auto &kv : f->sites) {   // (the map is ordered by (tid, pos, side))
         const uvcio_clipsites::Site &site = kv.second;
         const bool left = (site.row[CSW_side] == UVC_CLIPSITE_LEFT);
@@ -1728,6 +1757,12 @@ extern "C" int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *pat
         const size_t cons_len = cons.size();
         if (left) std::reverse(cons.begin(), cons.end());
         text += "\t" + std::to_string(frags.size()) + "\t" + std::to_string(strands.size()) + "\t" + std::to_string(both) + "\t" + std::to_string(cons_len) + "\t" + (cons.empty() ? std::string(".") : cons) + "\n";
+        if (f->junctions && site.has_junc) {   // the J line directly behind the S line
+            const int64_t *j = site.junc;
+            text += "J" + at + "\t" + std::to_string(j[CJW_query_len]) + "\t" + std::to_string(j[CJW_cmp_len]) + "\t" + std::to_string(j[CJW_status]) + "\t" + dot(j[CJW_best_mm], 0) + "\t" + std::to_string(j[CJW_n_best])
+                    + "\t" + dot(j[CJW_second_mm], 0) + "\t" + dot(j[CJW_partner], 1) + "\t" + (j[CJW_strand] < 0 ? "." : j[CJW_strand] ? "-" : "+") + "\t" + classes[j[CJW_klass]] + "\t" + dot(j[CJW_len], 0)
+                    + "\t" + dot(site.mate_pos, 1) + "\t" + (site.mate_side < 0 ? "." : site.mate_side == UVC_CLIPSITE_LEFT ? "L" : "R") + "\n";
+        }
         if (!f->req.want_reads || site.events.empty()) continue;
         // a family's rank: by the smallest (qname, flag) of its events at this site
         std::map<int32_t, std::pair<std::string, int32_t>> least;

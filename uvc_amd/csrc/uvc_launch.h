@@ -175,6 +175,23 @@ int64_t uvc_clipsites_scratch_ints(int64_t n_alns, int64_t npos);
 int64_t uvc_clipsites_sites_at(int64_t n_alns, int64_t npos);
 int64_t uvc_clipsites_reads_at(int64_t n_alns, int64_t npos);
 const char *uvc_clipsites_name(int id);
+// ---- uvc_clipjunc.hip: four stages, each one entry of uvcgpu_region_kernel_times.  d_ref2 / d_inv: uvc_clipjunc_ref_words(npos) 64-bit words
+// each (the pack writes all of them); d_sites: the caller's n_sites rows of UVC_CLIPSITE_ROW words; d_query: uvc_clipjunc_query_bytes(n_sites)
+// bytes, d_best: n_sites words and d_hist: n_sites x UVC_CLIPJUNC_NHIST ints, all three written by the queries stage for every site;
+// d_mpos / d_midx: the plane indices and row indices of the n_left LEFT sites ascending, behind them those of the RIGHT sites; d_rows:
+// n_sites rows of UVC_CLIPJUNC_ROW words.  The stages follow each other with the same arguments.  uvc_clipjunc_naive: 1 in a build of the
+// file with -DUVC_CLIPJUNC_NAIVE (the byte-per-base search the packed one is tested and measured against; its pack launches nothing) ----
+void uvc_launch_clipjunc_pack(const RegionDev *R, unsigned long long *d_ref2, unsigned long long *d_inv, hipStream_t s);
+void uvc_launch_clipjunc_queries(const RegionDev *R, const long long *d_sites, int n_sites, const UvcClipJunctionsRequest *req, void *d_query, unsigned long long *d_best, unsigned *d_hist, hipStream_t s);
+void uvc_launch_clipjunc_search(const RegionDev *R, const unsigned long long *d_ref2, const unsigned long long *d_inv, const void *d_query, int n_sites, const UvcClipJunctionsRequest *req,
+                                unsigned long long *d_best, unsigned *d_hist, hipStream_t s);
+void uvc_launch_clipjunc_finish(const RegionDev *R, const void *d_query, int n_sites, const UvcClipJunctionsRequest *req, const unsigned long long *d_best, const unsigned *d_hist,
+                                const int32_t *d_mpos, const int32_t *d_midx, int n_left, long long *d_rows, hipStream_t s);
+int64_t uvc_clipjunc_ref_words(int64_t npos);
+int64_t uvc_clipjunc_query_bytes(int64_t n_sites);
+const char *uvc_clipjunc_name(int id);
+const char *uvc_clipjunc_class_name(int k);
+int uvc_clipjunc_naive(void);
 // ---- uvc_callable.hip: d_tab = n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one the
 // number of runs once the count has run; d_runs: room for that many runs.  The emit follows a count with the same arguments ----
 void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s);

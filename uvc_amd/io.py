@@ -339,18 +339,30 @@ class ClipSites(_Store):
         d.uvcio_clipsites_open.restype, d.uvcio_clipsites_open.argtypes = C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         d.uvcio_clipsites_add.restype, d.uvcio_clipsites_add.argtypes = C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                                                                   C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        d.uvcio_clipsites_set_junctions.restype, d.uvcio_clipsites_set_junctions.argtypes = C.c_int, [C.c_void_p] + [C.c_int32] * 5
+        d.uvcio_clipsites_add_junctions.restype, d.uvcio_clipsites_add_junctions.argtypes = C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                                                                      C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _check(d.uvcio_clipsites_open(C.byref(self.h), int(min_mapq), int(min_clip), int(min_reads), int(with_reads)))
 
-    def add(self, tid, contig, rows, events=None, reads=None, qnames=None):
+    def set_junctions(self, min_votes=2, min_len=16, max_mismatch=1, max_dist=0, mate_slop=10):
+        """Turns the J lines on: the request values of the Region.clip_junctions calls whose rows add(junctions=) hands over."""
+        _check(dll().uvcio_clipsites_set_junctions(self.h, int(min_votes), int(min_len), int(max_mismatch), int(max_dist), int(mate_slop)))
+
+    def add(self, tid, contig, rows, events=None, reads=None, qnames=None, junctions=None):
         """rows, events: the second and third result of Region.clip_sites; reads: the reads the region was given (flag, mapq, fam_id,
-        fam_strand, frag_id); qnames: one name per alignment."""
+        fam_strand, frag_id); qnames: one name per alignment; junctions: the second result of Region.clip_junctions(rows), or None."""
         import numpy as np
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         if rows.ndim != 2 or rows.shape[1] != 176:
             raise ValueError("rows is the second result of Region.clip_sites ([n_sites, 176])")
+        if junctions is not None:
+            junctions = np.ascontiguousarray(junctions, dtype=np.int64)
+            if junctions.shape != (len(rows), 24):
+                raise ValueError("junctions is the second result of Region.clip_junctions(rows) ([n_sites, 24])")
+        jp = junctions.ctypes.data if junctions is not None and len(rows) else None
         n_ev = 0 if events is None else len(events)
         if n_ev == 0:
-            _check(dll().uvcio_clipsites_add(self.h, int(tid), contig.encode(), rows.ctypes.data, len(rows), None, 0, 0, None, None, None, None, None, None))
+            _check(dll().uvcio_clipsites_add_junctions(self.h, int(tid), contig.encode(), rows.ctypes.data, jp, len(rows), None, 0, 0, None, None, None, None, None, None))
             return
         events = np.ascontiguousarray(events)
         if events.dtype.itemsize != 16 or reads is None or qnames is None:
@@ -361,7 +373,8 @@ class ClipSites(_Store):
         if min(len(fl), len(mq), len(fam), len(st), len(fr)) < n:
             raise ValueError("every alignment has a name")
         names = (C.c_char_p * n)(*[q.encode() if isinstance(q, str) else q for q in qnames])
-        _check(dll().uvcio_clipsites_add(self.h, int(tid), contig.encode(), rows.ctypes.data, len(rows), events.ctypes.data, n_ev, n, names, fl.ctypes.data, mq.ctypes.data, fam.ctypes.data, st.ctypes.data, fr.ctypes.data))
+        _check(dll().uvcio_clipsites_add_junctions(self.h, int(tid), contig.encode(), rows.ctypes.data, jp, len(rows), events.ctypes.data, n_ev, n, names, fl.ctypes.data, mq.ctypes.data, fam.ctypes.data, st.ctypes.data,
+                                                   fr.ctypes.data))
 
 
 class Callable(_Store):

@@ -624,6 +624,24 @@ class Region:
             self._check(fn(self.h, arr, len(rows), C.byref(req), totals.ctypes.data, out.ctypes.data, ns.value, C.byref(ns), ev.ctypes.data if want_reads else None, nr.value if want_reads else 0, C.byref(nr)))
         return totals, out[:ns.value].copy(), (ev[:nr.value].copy() if want_reads else None)
 
+    def clip_junctions(self, rows, min_votes=2, min_len=16, max_mismatch=1, max_dist=0, mate_slop=10):
+        """uvcgpu_region_clip_junctions: where the clipped consensus of each site row of clip_sites() lies on the reference of this region,
+        on which strand, how unique that is and which other row is the far end of the event.  A vote index is compared when it has at
+        least min_votes votes and a two-thirds A/C/G/T majority; a site is searched with at least min_len compared indices; a placement
+        counts with at most max_mismatch (0..7) mismatches and, with max_dist > 0, a partner at most max_dist from the site; the mate is
+        the nearest row of the expected side within mate_slop of the partner.  -> (totals, junction rows): totals int64 [8]
+        (_ffi.CLIPJUNC_TOTALS names the first five); rows int64 [n_sites, UVC_CLIPJUNC_ROW]: site, query_len, cmp_len, status (0 not
+        searched, 1 not placed, 2 placed), best_mm, n_best, second_mm, partner (absolute), strand (0 forward, 1 reverse), klass
+        (_ffi.CLIP_CLASSES), len, mate (a row index or -1), hist[8] (_ffi.CLIPJUNC_SECTIONS names the sections, uvcgpu.h has the rules).
+        A partner is found only inside this region.  Legal from the creation of the region on; reads no reads and no planes."""
+        fn = self._ranges_fn("region_clip_junctions", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p])
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, _ffi.ENUMS["UVC_CLIPSITE_ROW"])
+        req = _ffi.UvcClipJunctionsRequest(int(min_votes), int(min_len), int(max_mismatch), int(max_dist), int(mate_slop))
+        totals = np.zeros(_ffi.ENUMS["UVC_CLIPJUNC_NTOTAL"], dtype=np.int64)
+        out = np.zeros((max(len(rows), 1), _ffi.ENUMS["UVC_CLIPJUNC_ROW"]), dtype=np.int64)
+        self._check(fn(self.h, rows.ctypes.data if len(rows) else None, len(rows), C.byref(req), out.ctypes.data, totals.ctypes.data))
+        return totals, out[:len(rows)].copy()
+
     def msi(self, ranges, min_tracklen=10, min_units=5, max_unitlen=6):
         """uvcgpu_region_msi: the microsatellite loci whose head lies in `ranges` -- (pos_beg, pos_end) pairs as for coverage() -- as the STR
         planes of the region name them: tracts of at least min_tracklen bp and min_units whole units of at most max_unitlen bp.  int32
