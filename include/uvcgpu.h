@@ -780,6 +780,67 @@ int uvcgpu_region_clip_junctions(uvcgpu_region_t *r, const int64_t *sites /* [n_
                                  int64_t *junctions /* [n_sites][UVC_CLIPJUNC_ROW] */, int64_t *totals /* [UVC_CLIPJUNC_NTOTAL] */);
 const char *uvcgpu_clip_junction_section_name(int32_t id);   /* "site" .. "reserved"; NULL for an id outside 0..UVC_NCLIPJUNC - 1 */
 const char *uvcgpu_clip_class_name(int32_t klass);           /* "NONE" "DEL" "DUP" "INV" "ADJACENT"; NULL for a class outside 0..4 */
+/* ---- clip-site mates: where the mates of the discordant pairs that face a site cluster (uvc1-mi355x --clip-sites-mates 1) ----
+ * Per row of uvcgpu_region_clip_sites the call gathers the read pairs of the handle that face the breakpoint, classes each of them and
+ * clusters the mates of the discordant ones: the partner of a fusion or translocation lies on another contig or beyond the region, where
+ * uvcgpu_region_clip_junctions cannot place it.  All integers; of a site row only the words pos and side are read.  mt(i) = mtid ? mtid[i]
+ * : req->tid is the contig of alignment i's mate; mtid is a host column of its own, one entry per alignment of the handle in the order of
+ * the UvcReadSoA as given (UvcReadSoA has no such column), uploaded per call.
+ *   Pair read: alignment i is a pair read iff it is counted as in uvcgpu_region_clip_sites (mapq >= min_mapq, !(flag & 0x4), l_qseq > 0),
+ *   flag & 0x1, !(flag & 0x8), !(flag & 0x900) (a supplementary line repeats its primary's mate fields) and mt(i) >= 0.  rend = the handle's
+ *   end of the alignment (bam_endpos: pos + the reference length of the CIGAR, pos + 1 without one).
+ *   Facing: i faces a RIGHT site p iff !(flag & 0x10), pos < p and p - window < rend <= p + overhang; i faces a LEFT site p iff flag & 0x10,
+ *   rend > p and p - overhang <= pos < p + window.  One alignment may face several sites: the unit of work is the (alignment, site) item.
+ *   Class of an item, the first rule that applies: UVC_CLIPMATE_OTHER_CONTIG: mt != tid; UVC_CLIPMATE_SAME_STRAND: ((flag >> 5) & 1) ==
+ *   ((flag >> 4) & 1); UVC_CLIPMATE_FAR: |mpos - pos| >= min_dist; else UVC_CLIPMATE_CONCORDANT.  The three other classes are discordant;
+ *   their items are the witnesses.
+ *   Witness order: ascending by (site, mt, mate strand = (flag >> 5) & 1, mpos, read), mpos the mate's leftmost coordinate as the BAM gives
+ *   it (signed); total, since two items of one site never share a read.
+ *   Clusters: along that order a new cluster begins at the first witness of a site, at a change of mt or of mate strand, and where mpos -
+ *   the previous mpos > max_gap (single linkage in one dimension).  A cluster is kept iff its pairs >= min_pairs.
+ * site_rows: one row of UVC_CLIPMATE_SITE_ROW int64 per given site (include/uvc_clipmates.def): site (the row's index), facing (its items),
+ *   concordant, other_contig, same_strand, far (its items by class), clusters (all of them), clusters_kept.
+ * clusters: one row of UVC_CLIPMATE_ROW int64 per kept cluster, in witness order (so sorted by site): site, mtid, mate_strand, mpos_min,
+ *   mpos_max (the smallest and largest mpos, 0-based leftmost coordinates, not ends), pairs (its witnesses), other_contig, same_strand, far
+ *   (its witnesses by class), mapq_sum, first (the index of its first witness in the witness order, with or without want_reads), reserved 0.
+ * reads (written only with want_reads = 1): one UvcClipMate per witness in witness order; `site` indexes the given rows, `read` the
+ *   UvcReadSoA as given, `cluster` the returned cluster rows (-1: the witness's cluster is not kept), klass is the item's class.
+ * totals[UVC_CLIPMATE_NTOTAL]: pair reads (each alignment once); facing items; concordant items; discordant items; clusters; kept clusters;
+ *   sites with a kept cluster; 0. */
+enum UvcClipMateSiteWord { UVC_CLIPMSITE_site = 0, UVC_CLIPMSITE_facing, UVC_CLIPMSITE_concordant, UVC_CLIPMSITE_other_contig, UVC_CLIPMSITE_same_strand,
+                           UVC_CLIPMSITE_far, UVC_CLIPMSITE_clusters, UVC_CLIPMSITE_clusters_kept, UVC_NCLIPMSITE };
+enum UvcClipMateClusterWord { UVC_CLIPMCLUS_site = 0, UVC_CLIPMCLUS_mtid, UVC_CLIPMCLUS_mate_strand, UVC_CLIPMCLUS_mpos_min, UVC_CLIPMCLUS_mpos_max, UVC_CLIPMCLUS_pairs,
+                              UVC_CLIPMCLUS_other_contig, UVC_CLIPMCLUS_same_strand, UVC_CLIPMCLUS_far, UVC_CLIPMCLUS_mapq_sum, UVC_CLIPMCLUS_first,
+                              UVC_CLIPMCLUS_reserved, UVC_NCLIPMCLUS };
+enum { UVC_CLIPMATE_SITE_ROW = 8, UVC_CLIPMATE_ROW = 12, UVC_CLIPMATE_NTOTAL = 8 };
+enum UvcClipMateClass { UVC_CLIPMATE_CONCORDANT = 0, UVC_CLIPMATE_OTHER_CONTIG, UVC_CLIPMATE_SAME_STRAND, UVC_CLIPMATE_FAR, UVC_NCLIPMATECLASS };
+enum UvcClipMateTotal { UVC_CLIPMTOTAL_pair_reads = 0, UVC_CLIPMTOTAL_facing, UVC_CLIPMTOTAL_concordant, UVC_CLIPMTOTAL_discordant, UVC_CLIPMTOTAL_clusters,
+                        UVC_CLIPMTOTAL_clusters_kept, UVC_CLIPMTOTAL_sites_kept };
+typedef struct UvcClipMatesRequest { int32_t tid, min_mapq, window, overhang, min_dist, max_gap, min_pairs, want_reads; } UvcClipMatesRequest;
+typedef struct UvcClipMate { int32_t site, read, cluster, klass; } UvcClipMate;
+/* Gathered, ordered and clustered on the device from the read columns of the handle: a count pass and a scatter pass over the alignments
+ * (the sites an alignment faces are a stretch of the ascending LEFT or RIGHT list), the witnesses of a site ranked by their keys (the slot
+ * of a witness is the number of witnesses of its site with a smaller (mt, strand, mpos, read); no vendor sort, and no atomic decides an
+ * order), clusters numbered by a scan over "begins a cluster", their counters integer adds, the kept ones compacted by count / scan /
+ * write: two calls return the same bytes.
+ *   Sizes first: a call that is not refused always writes totals, site_rows, *n_clusters (the kept clusters) and *n_reads (the witnesses).
+ *   It returns UVCGPU_ENOMEM when cluster_capacity < *n_clusters, or when want_reads is set and read_capacity < *n_reads, and then writes
+ *   nothing to `clusters` or `reads`.  n_sites == 0 gives zero totals and success.
+ *   Legal where uvcgpu_region_clip_sites is.  Zero reads: zero counts in every row.
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason: called before set_reads or after a reset; NULL req, totals,
+ *   n_clusters or n_reads; NULL sites or site_rows with n_sites > 0; n_sites < 0; tid < 0; min_mapq outside 0..255; window < 1; overhang <
+ *   0; min_dist < 1; max_gap < 0; min_pairs < 1; want_reads outside 0..1; a negative capacity; a NULL array with a positive capacity; a
+ *   row whose pos - beg is outside [0, npos) or whose side is not 0 or 1; rows not strictly ascending by (pos, side).  A refused call
+ *   writes nothing.  UVCGPU_EUNSUPPORTED behind the count pass, the one refusal behind a launch: 2^31 or more facing items (pass the sites
+ *   in several calls); nothing is written then either. */
+int uvcgpu_region_clip_mates(uvcgpu_region_t *r, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, int64_t n_sites,
+                             const int32_t *mtid /* [alignments of the handle], host; NULL: every mate on req->tid */,
+                             const UvcClipMatesRequest *req, int64_t *totals /* [UVC_CLIPMATE_NTOTAL] */, int64_t *site_rows /* [n_sites][UVC_CLIPMATE_SITE_ROW] */,
+                             int64_t *clusters /* [cluster_capacity][UVC_CLIPMATE_ROW] */, int64_t cluster_capacity, int64_t *n_clusters,
+                             UvcClipMate *reads, int64_t read_capacity, int64_t *n_reads);
+const char *uvcgpu_clip_mate_site_name(int32_t id);      /* "site" .. "clusters_kept"; NULL for an id outside 0..UVC_NCLIPMSITE - 1 */
+const char *uvcgpu_clip_mate_cluster_name(int32_t id);   /* "site" .. "reserved"; NULL for an id outside 0..UVC_NCLIPMCLUS - 1 */
+const char *uvcgpu_clip_mate_class_name(int32_t klass);  /* "CONCORDANT" "OTHER_CONTIG" "SAME_STRAND" "FAR"; NULL for a class outside 0..3 */
 /* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
  * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
  * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when
@@ -925,7 +986,8 @@ int uvcgpu_region_last_score_counts(const uvcgpu_region_t *r, int64_t *scored, i
  * The test suite and the soak scripts run it behind every accumulate (UVCGPU_CHECK_PRESENCE=1 in uvc_amd/region.py). */
 int uvcgpu_region_check_presence(uvcgpu_region_t *r, int64_t *n_violations);
 /* Measurement hooks (bench.py): HIP-event timing of every kernel of the LAST accumulate, recorded on the handle's stream.
- * kernel_times returns the number of kernels; `names` receives their names separated by ';'. */
+ * kernel_times returns the number of kernels; `names` receives their names separated by ';'.  The report calls add their stages to
+ * the list (at most 32 entries in all); set_profiling starts it anew, as an accumulate does. */
 int uvcgpu_region_set_profiling(uvcgpu_region_t *r, int on);
 int uvcgpu_region_kernel_times(uvcgpu_region_t *r, char *names, int names_bytes, float *ms, int capacity);
 void uvcgpu_region_destroy(uvcgpu_region_t *r);

@@ -276,6 +276,20 @@ void uvcio_sitereads_close(uvcio_sitereads_t *f);
  *   J contig pos side query_len cmp_len status best_mm n_best second_mm partner_pos(1-based) strand(+|-) class(NONE|DEL|DUP|INV|ADJACENT) len
  *     mate_pos(1-based) mate_side(L|R)      "." where a field has no value; the mate is written as the position and side of its row.
  * Of a site that two calls report, the J line is that of the call whose site row is kept.  Without set_junctions the file is the one above.
+ * Mates (uvcgpu_region_clip_mates, uvc1-mi355x --clip-sites-mates 1): set_mates() turns them on and keeps the five request values and the
+ * contig names of the BAM header (mate contig ids index them).  add_mates() is add_junctions() with the call's site_rows ([n_sites]
+ * [UVC_CLIPMATE_SITE_ROW]; NULL: add_junctions()), kept cluster rows ([n_clusters][UVC_CLIPMATE_ROW]) and witness rows (UvcClipMate, as
+ * want_reads = 1 returns them).  write() then adds "##clip_sites_mate_window=", "_overhang=", "_min_dist=", "_max_gap=" and "_min_pairs="
+ * behind the lines above, the "#P" and "#M" column lines behind "#R" (and "#J"), and behind the S line of every site that came with a
+ * site row, and behind its J line if there is one,
+ *   P contig pos side facing concordant other_contig same_strand far clusters clusters_kept
+ *   M contig pos side mate_contig mate_beg mate_end mate_strand(+|-) pairs other_contig same_strand far mapq_sum fragments families
+ *     families_both_strands      one per kept cluster of the site, in witness order.  mate_beg / mate_end are 1-based, mpos_min + 1 and
+ *     mpos_max + 1: the leftmost coordinates of the mates, not their ends; mate_contig is "." for an id the names do not hold.  fragments,
+ *     families and families_both_strands are counted over the cluster's witnesses as the S line counts them over its events.
+ * Of a site that two calls report, the P and M lines are those of the call whose site row is kept.  Witnesses are the reads of the call,
+ * so the P and M lines of a site closer than the window to a border of its call may depend on how the run is cut into calls.  Without
+ * set_mates the file is the one above.
  * Integers and names only, tab-separated.  A path that ends in .gz is written block-gzipped. */
 typedef struct uvcio_clipsites uvcio_clipsites_t;
 int uvcio_clipsites_open(uvcio_clipsites_t **out, int32_t min_mapq, int32_t min_clip, int32_t min_reads, int32_t with_reads);
@@ -285,6 +299,11 @@ int uvcio_clipsites_set_junctions(uvcio_clipsites_t *f, int32_t min_votes, int32
 int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, const int64_t *junctions /* [n_sites][UVC_CLIPJUNC_ROW] or NULL */,
                                   int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id,
                                   const uint8_t *fam_strand, const int32_t *frag_id);
+int uvcio_clipsites_set_mates(uvcio_clipsites_t *f, int32_t window, int32_t overhang, int32_t min_dist, int32_t max_gap, int32_t min_pairs, const char *const *contig_names, int32_t n_contigs);
+int uvcio_clipsites_add_mates(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites /* [n_sites][UVC_CLIPSITE_ROW] */, const int64_t *junctions /* [n_sites][UVC_CLIPJUNC_ROW] or NULL */,
+                              int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id,
+                              const uint8_t *fam_strand, const int32_t *frag_id, const int64_t *site_rows /* [n_sites][UVC_CLIPMATE_SITE_ROW] or NULL */,
+                              const int64_t *clusters /* [n_clusters][UVC_CLIPMATE_ROW] */, int64_t n_clusters, const UvcClipMate *mates, int64_t n_mates);
 int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *path);
 void uvcio_clipsites_close(uvcio_clipsites_t *f);
 /* ---- the read profile (uvc1-mi355x --read-profile-out) ----

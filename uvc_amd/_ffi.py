@@ -119,6 +119,15 @@ class UvcClipJunctionsRequest(C.Structure):
     _fields_ = [("min_votes", C.c_int32), ("min_len", C.c_int32), ("max_mismatch", C.c_int32), ("max_dist", C.c_int32), ("mate_slop", C.c_int32)]
 
 
+class UvcClipMatesRequest(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("min_mapq", C.c_int32), ("window", C.c_int32), ("overhang", C.c_int32), ("min_dist", C.c_int32), ("max_gap", C.c_int32), ("min_pairs", C.c_int32),
+                ("want_reads", C.c_int32)]
+
+
+class UvcClipMate(C.Structure):
+    _fields_ = [("site", C.c_int32), ("read", C.c_int32), ("cluster", C.c_int32), ("klass", C.c_int32)]
+
+
 class UvcCallableRun(C.Structure):
     _fields_ = [("range", C.c_int32), ("pos_beg", C.c_int32), ("pos_end", C.c_int32), ("mask", C.c_int32)]
 
@@ -234,6 +243,17 @@ assert dict((n, w) for n, _, w in CLIPJUNC_SECTIONS)["hist"] == ENUMS["UVC_CLIPJ
 CLIPJUNC_TOTALS = [k[len("UVC_CLIPJTOTAL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPJTOTAL_")), key=lambda kv: kv[1])]
 CLIP_CLASSES = [k[len("UVC_CLIPCLASS_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPCLASS_")), key=lambda kv: kv[1])]
 assert len(CLIP_CLASSES) == ENUMS["UVC_NCLIPCLASS"]
+
+# the words of the two rows of uvcgpu_region_clip_mates in id order (UvcClipMateSiteWord, UvcClipMateClusterWord): the two tables of
+# include/uvc_clipmates.def, checked against the header's enums
+CLIPMATE_SITE_WORDS = _read_def("uvc_clipmates.def", "UVC_CLIPMATE_SITE")
+CLIPMATE_CLUSTER_WORDS = _read_def("uvc_clipmates.def", "UVC_CLIPMATE_CLUSTER")
+assert [ENUMS["UVC_CLIPMSITE_" + n] for n, _, _ in CLIPMATE_SITE_WORDS] == list(range(ENUMS["UVC_NCLIPMSITE"])) and [ENUMS["UVC_CLIPMCLUS_" + n] for n, _, _ in CLIPMATE_CLUSTER_WORDS] == list(range(ENUMS["UVC_NCLIPMCLUS"]))
+assert [(f, w) for _, f, w in CLIPMATE_SITE_WORDS] == [(k, 1) for k in range(ENUMS["UVC_CLIPMATE_SITE_ROW"])] and [(f, w) for _, f, w in CLIPMATE_CLUSTER_WORDS] == [(k, 1) for k in range(ENUMS["UVC_CLIPMATE_ROW"])]
+assert C.sizeof(UvcClipMatesRequest) == 32 and C.sizeof(UvcClipMate) == 16
+CLIPMATE_TOTALS = [k[len("UVC_CLIPMTOTAL_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_CLIPMTOTAL_")), key=lambda kv: kv[1])]
+CLIPMATE_CLASSES = ["CONCORDANT", "OTHER_CONTIG", "SAME_STRAND", "FAR"]
+assert [ENUMS["UVC_CLIPMATE_" + n] for n in CLIPMATE_CLASSES] == list(range(ENUMS["UVC_NCLIPMATECLASS"]))
 
 # the sections of a microsatellite row in id order (UvcMsiSection): the table of include/uvc_msi.def, checked against the header's enums
 MSI_SECTIONS = _read_def("uvc_msi.def", "UVC_MSI")

@@ -47,7 +47,7 @@ const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-
 enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, R_CLIPSITES, N_REPORTS };
 struct ReportRow {
     const char *out;                 // --X-out PATH
-    const char *subs[12];            // the options that only shape this report: each needs --X-out (the list ends with a null)
+    const char *subs[18];            // the options that only shape this report: each needs --X-out (the list ends with a null)
     const char *window;              // the one of them that cuts the targets into windows (refuse_report_windows), or none
     const char *why_no_shard, *why_no_repeat;   // refuse_report_runs
     const char *pair_writes_no;      // split_pair: "pair mode ... writes no <this>"
@@ -68,7 +68,8 @@ const ReportRow REPORTS[N_REPORTS] = {
       "every tile would be counted that many times", "fragment profile", nullptr },
     { "--site-reads-out", { "--site-reads-sites", "--site-reads-min-mapq", "--site-reads-alt-only" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its rows that many times", "site reads report", nullptr },
     { "--clip-sites-out", { "--clip-sites-min-clip", "--clip-sites-min-reads", "--clip-sites-min-mapq", "--clip-sites-reads", "--clip-sites-junctions", "--clip-sites-junction-min-len", "--clip-sites-junction-max-mismatch",
-                            "--clip-sites-junction-min-votes", "--clip-sites-junction-max-dist", "--clip-sites-junction-slop" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its sites that many times",
+                            "--clip-sites-junction-min-votes", "--clip-sites-junction-max-dist", "--clip-sites-junction-slop", "--clip-sites-mates", "--clip-sites-mate-window", "--clip-sites-mate-overhang",
+                            "--clip-sites-mate-min-dist", "--clip-sites-mate-max-gap", "--clip-sites-mate-min-pairs" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its sites that many times",
       "clip sites report", nullptr },
 };
 // the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
@@ -112,6 +113,7 @@ struct Opts {
     uvcio_sitereads_t *sitereads = nullptr; uvcio_sites_t *sitereads_list = nullptr;   // --site-reads-out: the report's store, filled by the workers, and the listed sites (main)
     UvcClipSitesRequest clipsites_req{ 0, 10, 3, 1 }; int32_t clipsites_reads = 0;   // --clip-sites-min-mapq, --clip-sites-min-clip, --clip-sites-min-reads (the call always asks for the event rows); --clip-sites-reads
     uvcio_clipsites_t *clipsites = nullptr;   // --clip-sites-out: the report's store, filled by the workers (main)
+    int32_t clipsites_mates = 0; UvcClipMatesRequest clipmates_req{ 0, 0, 500, 5, 1000, 500, 2, 1 };   // --clip-sites-mates; --clip-sites-mate-window, -overhang, -min-dist, -max-gap, -min-pairs (tid per tile, min_mapq = --clip-sites-min-mapq, always with the witness rows)
     int32_t clipsites_junctions = 0; UvcClipJunctionsRequest clipjunc_req{ 2, 16, 1, 0, 10 };   // --clip-sites-junctions; --clip-sites-junction-min-votes, -min-len, -max-mismatch, -max-dist, -slop
     bool timing = false, no_header = false, device_inflate = false, print_params = false;
     UvcParams P;                 // the reference's defaults and the user's values; the platform step comes on top (main)
@@ -198,6 +200,12 @@ const OptRow OPTS[] = {
     { "--clip-sites-junction-min-votes", O_CLI, false, "2", "with --clip-sites-junctions 1: a consensus base is compared when at least this many reads vote there and two thirds of them agree on A, C, G or T (1 or more)" },
     { "--clip-sites-junction-max-dist", O_CLI, false, "0", "with --clip-sites-junctions 1: only places whose partner junction lies at most this far from the site count; 0 is the whole region" },
     { "--clip-sites-junction-slop", O_CLI, false, "10", "with --clip-sites-junctions 1: the mate of a site is the nearest site of the expected side at most this far from the partner junction (microhomology moves the two ends apart)" },
+    { "--clip-sites-mates", O_CLI, false, "0", "with --clip-sites-out: 1 (or true) gathers the read pairs that face each site and clusters the mates of the discordant ones -- a P line per site (facing, concordant, other contig, same strand, far, clusters) and an M line per kept cluster (mate contig, span, strand, pairs, families): the partner of a fusion or translocation, on another contig or beyond the tile. A site closer than the window to a tile border sees the reads of its tile alone" },
+    { "--clip-sites-mate-window", O_CLI, false, "500", "with --clip-sites-mates 1: a read faces a site when it ends (forward read, RIGHT site) or begins (reverse read, LEFT site) less than this many bp in front of it (1 or more)" },
+    { "--clip-sites-mate-overhang", O_CLI, false, "5", "with --clip-sites-mates 1: a facing read may reach this many bp across the site (0 or more)" },
+    { "--clip-sites-mate-min-dist", O_CLI, false, "1000", "with --clip-sites-mates 1: a pair on one contig and opposite strands is discordant (far) when the mate begins at least this many bp from the read (1 or more)" },
+    { "--clip-sites-mate-max-gap", O_CLI, false, "500", "with --clip-sites-mates 1: mates of one contig and strand whose start positions lie at most this far apart join one cluster (0 or more)" },
+    { "--clip-sites-mate-min-pairs", O_CLI, false, "2", "with --clip-sites-mates 1: a cluster gets an M line from this many pairs on (1 or more)" },
     { "--timing", O_CLI, true, "", "per-stage thread-seconds on stderr; with --score-mem-mb also the chunks per tile" },
     { "--device-inflate", O_CLI, true, "", "inflate the BGZF blocks on the GPU" },
     { "--repeat", O_CLI, false, "1", "benchmark aid: the tile list n times" },
@@ -454,6 +462,12 @@ Opts parse(int argc, char **argv) {
         else if (n0 == "--clip-sites-junction-min-votes") o.clipjunc_req.min_votes = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
         else if (n0 == "--clip-sites-junction-max-dist") o.clipjunc_req.max_dist = (int32_t)whole_number(n0, val(), 0, 2e9, "a distance in bp (0 = the whole region)");
         else if (n0 == "--clip-sites-junction-slop") o.clipjunc_req.mate_slop = (int32_t)whole_number(n0, val(), 0, 2e9, "a distance in bp");
+        else if (n0 == "--clip-sites-mates") o.clipsites_mates = (int32_t)whole_number(n0, val(), 0, 1, "0 or 1 (false or true)", N_STRTOD_BOOL);
+        else if (n0 == "--clip-sites-mate-window") o.clipmates_req.window = (int32_t)whole_number(n0, val(), 1, 2e9, "a distance in bp of at least 1");
+        else if (n0 == "--clip-sites-mate-overhang") o.clipmates_req.overhang = (int32_t)whole_number(n0, val(), 0, 2e9, "a distance in bp");
+        else if (n0 == "--clip-sites-mate-min-dist") o.clipmates_req.min_dist = (int32_t)whole_number(n0, val(), 1, 2e9, "a distance in bp of at least 1");
+        else if (n0 == "--clip-sites-mate-max-gap") o.clipmates_req.max_gap = (int32_t)whole_number(n0, val(), 0, 2e9, "a distance in bp");
+        else if (n0 == "--clip-sites-mate-min-pairs") o.clipmates_req.min_pairs = (int32_t)whole_number(n0, val(), 1, 2e9, "a whole number of at least 1");
         else if (n0 == "--mem-per-thread") o.mem_per_thread = std::max<int64_t>(1, atoll(val().c_str()));
         else if (n0 == "--devices") {   // comma-separated HIP device ids; an id may repeat (two workers sets on one GPU)
             o.devices.clear();
@@ -506,6 +520,8 @@ Opts parse(int argc, char **argv) {
         if (R.window) refuse_report_windows(o, R.out, R.window, o.report[r].window);
         if (r == R_CLIPSITES && !o.clipsites_junctions)   // the junction sub-options shape the J lines alone
             for (int s = 0; R.subs[s]; s++) if (((o.report[r].subs_given >> s) & 1) && !strncmp(R.subs[s], "--clip-sites-junction-", 22)) die(std::string(R.subs[s]) + " needs --clip-sites-junctions 1: it only shapes the J lines");
+        if (r == R_CLIPSITES && !o.clipsites_mates)   // the mate sub-options shape the P and M lines alone
+            for (int s = 0; R.subs[s]; s++) if (((o.report[r].subs_given >> s) & 1) && !strncmp(R.subs[s], "--clip-sites-mate-", 18)) die(std::string(R.subs[s]) + " needs --clip-sites-mates 1: it only shapes the P and M lines");
         if (r == R_SITEREADS && o.sitereads_sites.empty()) die("--site-reads-out needs --site-reads-sites FILE: the report is about the sites of that file");
     }
     if (o.merge > 0) {   // before any file or device
@@ -557,6 +573,7 @@ struct Worker {
     std::vector<UvcCallableRun> call_runs;   // --callable-out: the runs, as many as the last tiles had
     std::vector<int32_t> sr_sites, sr_counts; std::vector<UvcSiteRead> sr_rows; std::vector<const char *> sr_qnames;   // --site-reads-out: the sites a tile owns, their counts and rows, the names of the rows' alignments
     std::vector<int64_t> cs_junc;   // --clip-sites-junctions 1: the junction rows of a tile's sites
+    std::vector<int32_t> cm_mtid; std::vector<int64_t> cm_sites, cm_clusters; std::vector<UvcClipMate> cm_reads;   // --clip-sites-mates 1: the mate contigs of the kept alignments; the site rows, kept clusters and witness rows of a tile
     std::vector<int64_t> cs_rows; std::vector<UvcClipRead> cs_reads; std::vector<const char *> cs_qnames;   // --clip-sites-out: the site rows and event rows of a tile, as many as the last tiles had, the names of the events' alignments
     std::vector<int32_t> msi_rows; std::vector<std::string> msi_units; std::vector<const char *> msi_unit_ptrs;   // --msi-out: the loci, as many as the last tiles had
 };
@@ -724,8 +741,23 @@ void clip_sites_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
         w.cs_junc.resize((size_t)n_sites * UVC_CLIPJUNC_ROW);
         if (uvcgpu_region_clip_junctions(w.reg, w.cs_rows.data(), n_sites, &o.clipjunc_req, w.cs_junc.data(), jtotals)) die(uvcgpu_last_error());
     }
-    if (uvcio_clipsites_add_junctions(o.clipsites, t.tid, t.chrom.c_str(), w.cs_rows.data(), o.clipsites_junctions ? w.cs_junc.data() : nullptr, n_sites, w.cs_reads.data(), n_reads, k, w.cs_qnames.data(), w.flag.data(), w.mapq.data(),
-                                      w.fam.data(), w.fstrand.data(), w.frag.data())) die(uvcio_last_error());
+    int64_t n_clusters = 0, n_mates = 0;
+    if (o.clipsites_mates) {   // behind the tile's clip-site call, on that call's rows: the mate contigs of the kept alignments in their order, always with the witness rows
+        int64_t mtotals[UVC_CLIPMATE_NTOTAL];
+        UvcClipMatesRequest req = o.clipmates_req;
+        req.tid = t.tid; req.min_mapq = o.clipsites_req.min_mapq;
+        w.cm_mtid.resize((size_t)k);
+        for (int64_t i = 0; i < k; i++) w.cm_mtid[(size_t)i] = b.mtid[w.order[(size_t)i]];
+        w.cm_sites.resize((size_t)n_sites * UVC_CLIPMATE_SITE_ROW);
+        n_clusters = sizes_first(w.cm_clusters, UVC_CLIPMATE_ROW, [&](int64_t *rows, int64_t cap, int64_t *n) {
+            int rc = uvcgpu_region_clip_mates(w.reg, w.cs_rows.data(), n_sites, w.cm_mtid.data(), &req, mtotals, w.cm_sites.data(), rows, cap, n, w.cm_reads.data(), (int64_t)w.cm_reads.size(), &n_mates);
+            if (rc == UVCGPU_ENOMEM && n_mates > (int64_t)w.cm_reads.size()) w.cm_reads.resize((size_t)n_mates);   // (sizes_first calls once more: with room for both)
+            if (rc == UVCGPU_ENOMEM && *n <= cap) rc = uvcgpu_region_clip_mates(w.reg, w.cs_rows.data(), n_sites, w.cm_mtid.data(), &req, mtotals, w.cm_sites.data(), rows, cap, n, w.cm_reads.data(), (int64_t)w.cm_reads.size(), &n_mates);
+            return rc;
+        });
+    }
+    if (uvcio_clipsites_add_mates(o.clipsites, t.tid, t.chrom.c_str(), w.cs_rows.data(), o.clipsites_junctions ? w.cs_junc.data() : nullptr, n_sites, w.cs_reads.data(), n_reads, k, w.cs_qnames.data(), w.flag.data(), w.mapq.data(),
+                                  w.fam.data(), w.fstrand.data(), w.frag.data(), o.clipsites_mates ? w.cm_sites.data() : nullptr, w.cm_clusters.data(), n_clusters, w.cm_reads.data(), n_mates)) die(uvcio_last_error());
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // The record text of one call behind `lines`: write(dst, room, &len) into a buffer as large as the last tiles needed (+ slack); a second
@@ -1482,6 +1514,8 @@ int main(int argc, char **argv) {
     if (wanted(R_FRAGPROF) && uvcio_fragprofile_open(&o.fragprof, o.fragprof_req.min_mapq, o.fragprof_req.short_lo, o.fragprof_req.short_hi, o.fragprof_req.long_lo, o.fragprof_req.long_hi)) die(uvcio_last_error());
     if (wanted(R_CLIPSITES) && uvcio_clipsites_open(&o.clipsites, o.clipsites_req.min_mapq, o.clipsites_req.min_clip, o.clipsites_req.min_reads, o.clipsites_reads)) die(uvcio_last_error());
     if (o.clipsites && o.clipsites_junctions && uvcio_clipsites_set_junctions(o.clipsites, o.clipjunc_req.min_votes, o.clipjunc_req.min_len, o.clipjunc_req.max_mismatch, o.clipjunc_req.max_dist, o.clipjunc_req.mate_slop)) die(uvcio_last_error());
+    if (o.clipsites && o.clipsites_mates && uvcio_clipsites_set_mates(o.clipsites, o.clipmates_req.window, o.clipmates_req.overhang, o.clipmates_req.min_dist, o.clipmates_req.max_gap, o.clipmates_req.min_pairs, G.cnames.data(), nref))
+        die(uvcio_last_error());
     if (wanted(R_SITEREADS)) {   // the listed sites, each with its reference base: a site that no tile owns keeps its S line of zeros
         uvcio_sites_t *list = nullptr; uvcio_fasta_t *fa = nullptr;
         if (uvcio_sites_open(&list, o.sitereads_sites.c_str(), G.cnames.data(), nref)) die("--site-reads-sites: " + std::string(uvcio_last_error()));

@@ -119,7 +119,7 @@ struct uvcgpu_region {
     Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
     Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
-    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions, _clip_mates): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -671,7 +671,8 @@ int uvcgpu_region_check_presence(uvcgpu_region_t *r, int64_t *n_violations) {
 }
 
 // Per-kernel timing of the LAST accumulate, measured with HIP events on the handle's own stream.
-int uvcgpu_region_set_profiling(uvcgpu_region_t *r, int on) { if (!r) return fail(UVCGPU_EINVAL, "null region"); r->prof.on = on ? 1 : 0; return 0; }
+// (the list of timed entries starts anew, as at an accumulate: a caller that times report calls alone need not accumulate between them)
+int uvcgpu_region_set_profiling(uvcgpu_region_t *r, int on) { if (!r) return fail(UVCGPU_EINVAL, "null region"); r->prof.on = on ? 1 : 0; r->prof.n = 0; return 0; }
 int uvcgpu_region_kernel_times(uvcgpu_region_t *r, char *names, int names_bytes, float *ms, int capacity) {
     if (!r || !names || !ms) return fail(UVCGPU_EINVAL, "bad argument");
     HIP_OK(hipStreamSynchronize(r->stream));
@@ -1380,8 +1381,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites and _clip_junctions ----
-// What the ten share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions and _clip_mates ----
+// What the eleven share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1852,6 +1853,153 @@ int uvcgpu_region_clip_junctions(uvcgpu_region_t *r, const int64_t *sites, int64
 }
 const char *uvcgpu_clip_junction_section_name(int32_t id) { return uvc_clipjunc_name(id); }
 const char *uvcgpu_clip_class_name(int32_t klass) { return uvc_clipjunc_class_name(klass); }
+
+// ---- clip-site mates (uvc_clipmates.hip): in the report buffer [the site lists] [the mtid column] [site rows] [totals] [per-site ints];
+// what depends on the number of witnesses and of clusters comes from a pool of this call ----
+// The read columns belong to the reads of the handle: the legality is that of uvcgpu_region_clip_sites.  The lists (the absolute positions
+// of the LEFT sites ascending, then those of the RIGHT sites, and the row each belongs to) and the caller's mtid go up through the staging
+// buffer.  Sizes first: the host waits behind the count (the four totals, the witnesses, the rank blocks), behind the cut (the clusters)
+// and behind the reduce (the site rows, the kept clusters); only a call with enough room copies cluster and witness rows.
+static int uvcgpu_region_clip_mates_impl(uvcgpu_region_t *r, const int64_t *sites, int64_t n_sites, const int32_t *mtid, const UvcClipMatesRequest *req, int64_t *totals, int64_t *site_rows,
+                                         int64_t *clusters, int64_t cluster_capacity, int64_t *n_clusters, UvcClipMate *reads, int64_t read_capacity, int64_t *n_reads) {
+    { int rc1 = report_guard(r, "clip_mates", nullptr, "reads"); if (rc1) return rc1; }
+    if (!req || !totals || !n_clusters || !n_reads) return fail(UVCGPU_EINVAL, "clip_mates: req, totals, n_clusters and n_reads must not be NULL");
+    if (n_sites < 0) return fail(UVCGPU_EINVAL, "clip_mates: n_sites " + std::to_string(n_sites) + " is negative");
+    if (n_sites > 0 && (!sites || !site_rows)) return fail(UVCGPU_EINVAL, "clip_mates: sites and site_rows must not be NULL");
+    if (req->tid < 0) return fail(UVCGPU_EINVAL, "clip_mates: tid " + std::to_string(req->tid) + " is negative");
+    if (req->min_mapq < 0 || req->min_mapq > 255) return fail(UVCGPU_EINVAL, "clip_mates: min_mapq " + std::to_string(req->min_mapq) + " is outside 0..255");
+    if (req->window < 1) return fail(UVCGPU_EINVAL, "clip_mates: window " + std::to_string(req->window) + " must be at least 1");
+    if (req->overhang < 0) return fail(UVCGPU_EINVAL, "clip_mates: overhang " + std::to_string(req->overhang) + " is negative");
+    if (req->min_dist < 1) return fail(UVCGPU_EINVAL, "clip_mates: min_dist " + std::to_string(req->min_dist) + " must be at least 1");
+    if (req->max_gap < 0) return fail(UVCGPU_EINVAL, "clip_mates: max_gap " + std::to_string(req->max_gap) + " is negative");
+    if (req->min_pairs < 1) return fail(UVCGPU_EINVAL, "clip_mates: min_pairs " + std::to_string(req->min_pairs) + " must be at least 1");
+    if (req->want_reads < 0 || req->want_reads > 1) return fail(UVCGPU_EINVAL, "clip_mates: want_reads " + std::to_string(req->want_reads) + " is outside 0..1");
+    if (cluster_capacity < 0) return fail(UVCGPU_EINVAL, "clip_mates: cluster_capacity " + std::to_string(cluster_capacity) + " is negative");
+    if (read_capacity < 0) return fail(UVCGPU_EINVAL, "clip_mates: read_capacity " + std::to_string(read_capacity) + " is negative");
+    if (!clusters && cluster_capacity > 0) return fail(UVCGPU_EINVAL, "clip_mates: clusters is NULL with cluster_capacity " + std::to_string(cluster_capacity));
+    if (!reads && read_capacity > 0) return fail(UVCGPU_EINVAL, "clip_mates: reads is NULL with read_capacity " + std::to_string(read_capacity));
+    if (n_sites > (INT32_MAX >> 1)) return fail(UVCGPU_EINVAL, "clip_mates: n_sites " + std::to_string(n_sites) + " is more than one call takes (" + std::to_string(INT32_MAX >> 1) + ")");
+    int64_t n_left = 0;
+    for (int64_t k = 0; k < n_sites; k++) {
+        const int64_t *row = sites + k * UVC_CLIPSITE_ROW, pos = row[CS_AT_pos], side = row[CS_AT_side];
+        if (pos < r->beg || pos - r->beg >= r->npos) return fail(UVCGPU_EINVAL, "clip_mates: row " + std::to_string(k) + " has pos " + std::to_string(pos) + ", outside the region [" + std::to_string(r->beg) + ", " + std::to_string(r->end) + ")");
+        if (side != UVC_CLIPSITE_LEFT && side != UVC_CLIPSITE_RIGHT) return fail(UVCGPU_EINVAL, "clip_mates: row " + std::to_string(k) + " has side " + std::to_string(side) + ", neither 0 nor 1");
+        const int64_t *prev = row - UVC_CLIPSITE_ROW;
+        if (k > 0 && std::make_pair(prev[CS_AT_pos], prev[CS_AT_side]) >= std::make_pair(pos, side))
+            return fail(UVCGPU_EINVAL, "clip_mates: row " + std::to_string(k) + " (" + std::to_string(pos) + ", " + std::to_string(side) + ") is not above row " + std::to_string(k - 1) + ": rows ascend strictly by (pos, side)");
+        n_left += (side == UVC_CLIPSITE_LEFT);
+    }
+    const size_t totals_bytes = sizeof(int64_t) * UVC_CLIPMATE_NTOTAL, rows_bytes = sizeof(int64_t) * UVC_CLIPMATE_SITE_ROW * (size_t)n_sites;
+    if (n_sites == 0 || !r->has_reads) {   // no site, or set_reads with zero reads: nothing to launch
+        memset(totals, 0, totals_bytes);
+        if (n_sites) memset(site_rows, 0, rows_bytes);
+        for (int64_t k = 0; k < n_sites; k++) site_rows[k * UVC_CLIPMATE_SITE_ROW + UVC_CLIPMSITE_site] = k;
+        *n_clusters = 0; *n_reads = 0;
+        return 0;
+    }
+    std::vector<int32_t> lists(2 * (size_t)n_sites);
+    {
+        int32_t *spos = lists.data(), *sidx = spos + n_sites;
+        int64_t at[2] = { 0, n_left };
+        for (int64_t k = 0; k < n_sites; k++) {
+            const int64_t *row = sites + k * UVC_CLIPSITE_ROW;
+            const int64_t j = at[row[CS_AT_side]]++;
+            spos[j] = (int32_t)row[CS_AT_pos]; sidx[j] = (int32_t)k;
+        }
+    }
+    const int64_t n_alns = r->R.n_alns, site_ints = uvc_clipmates_site_ints(n_sites);
+    const size_t list_bytes = sizeof(int32_t) * 2 * (size_t)n_sites, mtid_bytes = mtid ? sizeof(int32_t) * (size_t)n_alns : 0;
+    ReportLayout L;
+    const size_t o_lists = L.take(list_bytes), o_mtid = L.take(mtid_bytes), o_rows = L.take(rows_bytes), o_totals = L.take(totals_bytes), o_ints = L.take(sizeof(int32_t) * (size_t)site_ints);
+    const size_t head_bytes = 128;   // the page-locked head: the totals and the numbers the host waits for
+    { int rc1 = report_buffers(r, L.bytes, head_bytes + rows_bytes, "clip mates"); if (rc1) return rc1; }
+    char *d = r->d_report, *h = r->h_report;
+    {
+        size_t at = 0;
+        const size_t total = o_rows;   // (the two pieces lie at the head of the layout, each on a 64-byte boundary, as `at` counts them)
+        { int rc1 = stage_upload(r, d + o_lists, lists.data(), list_bytes, at, total); if (rc1) return rc1; }
+        if (mtid) { int rc1 = stage_upload(r, d + o_mtid, mtid, mtid_bytes, at, total); if (rc1) return rc1; }
+    }
+    const UvcClipMateLists lists_dev{ (const int32_t *)(d + o_lists), (const int32_t *)(d + o_lists) + n_sites, mtid ? (const int32_t *)(d + o_mtid) : nullptr, (int)n_sites, (int)n_left };
+    long long *d_rows = (long long *)(d + o_rows), *d_totals = (long long *)(d + o_totals);
+    int32_t *d_ints = (int32_t *)(d + o_ints);
+    HIP_OK(hipMemsetAsync(d_rows, 0, L.bytes - o_rows, r->stream));   // the site rows, the totals and the per-site ints
+    // with profiling on, up to five more entries of uvcgpu_region_kernel_times (accumulate starts the list anew)
+    int pi = uvc_prof_begin(&r->prof, "k_clipmates_count", r->stream);
+    uvc_launch_clipmates_count(&r->W, n_alns, &lists_dev, req, d_rows, d_totals, d_ints, r->stream);
+    uvc_prof_end(&r->prof, pi, r->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h, d_totals, totals_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipMemcpyAsync(h + totals_bytes, uvc_clipmates_n_witnesses_at(d_ints, n_sites), sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipMemcpyAsync(h + totals_bytes + 4, uvc_clipmates_n_rank_blocks_at(d_ints, n_sites), sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipMemcpyAsync(h + head_bytes, d_rows, rows_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipStreamSynchronize(r->stream));
+    int64_t tot[UVC_CLIPMATE_NTOTAL];
+    int32_t n_wit = 0, n_blocks = 0, n_clus = 0, n_kept = 0;
+    memcpy(tot, h, totals_bytes); memcpy(&n_wit, h + totals_bytes, sizeof n_wit); memcpy(&n_blocks, h + totals_bytes + 4, sizeof n_blocks);
+    if (tot[UVC_CLIPMTOTAL_facing] > INT32_MAX) return fail(UVCGPU_EUNSUPPORTED, "clip_mates: " + std::to_string(tot[UVC_CLIPMTOTAL_facing]) + " facing (alignment, site) items, more than one call takes (2^31 - 1): pass the sites in several calls");
+    Pool tmp(r);
+    unsigned long long *d_key = nullptr, *d_okey = nullptr; int32_t *d_wit = nullptr, *d_clus = nullptr; long long *d_crow = nullptr, *d_out = nullptr; UvcClipMate *d_reads = nullptr;
+    if (n_wit > 0) {
+        const int64_t wit_ints = uvc_clipmates_witness_ints(n_wit);
+        if (!tmp.get(&d_key, (size_t)n_wit) || !tmp.get(&d_okey, (size_t)n_wit) || !tmp.get(&d_wit, (size_t)wit_ints)) return fail(UVCGPU_ENOMEM, "clip_mates: hipMalloc(" + std::to_string(n_wit) + " witnesses) failed");
+        pi = uvc_prof_begin(&r->prof, "k_clipmates_scatter", r->stream);
+        uvc_launch_clipmates_scatter(&r->W, n_alns, &lists_dev, req, d_ints, n_wit, d_key, d_wit, r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
+        pi = uvc_prof_begin(&r->prof, "k_clipmates_rank", r->stream);
+        uvc_launch_clipmates_rank(&lists_dev, d_ints, n_wit, n_blocks, d_key, d_okey, d_wit, r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
+        pi = uvc_prof_begin(&r->prof, "k_clipmates_cut", r->stream);
+        uvc_launch_clipmates_cut(&lists_dev, req, d_ints, n_wit, d_okey, d_wit, r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(h, uvc_clipmates_n_clusters_at(d_wit, n_wit), sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipStreamSynchronize(r->stream));
+        memcpy(&n_clus, h, sizeof n_clus);   // (at least 1: the first witness begins a cluster)
+        const int64_t clus_ints = uvc_clipmates_cluster_ints(n_clus);
+        const size_t crow_bytes = sizeof(int64_t) * UVC_CLIPMATE_ROW * (size_t)n_clus;
+        if (!tmp.get(&d_crow, (size_t)UVC_CLIPMATE_ROW * n_clus) || !tmp.get(&d_out, (size_t)UVC_CLIPMATE_ROW * n_clus) || !tmp.get(&d_clus, (size_t)clus_ints) || (req->want_reads && !tmp.get(&d_reads, (size_t)n_wit)))
+            return fail(UVCGPU_ENOMEM, "clip_mates: hipMalloc(" + std::to_string(n_clus) + " clusters) failed");
+        HIP_OK(hipMemsetAsync(d_crow, 0, crow_bytes, r->stream));
+        pi = uvc_prof_begin(&r->prof, "k_clipmates_reduce", r->stream);
+        uvc_launch_clipmates_reduce(&r->W, &lists_dev, req, n_wit, n_clus, d_okey, d_wit, d_crow, d_rows, d_out, d_reads, d_clus, r->stream);
+        uvc_prof_end(&r->prof, pi, r->stream);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(h, uvc_clipmates_n_kept_at(d_clus, n_clus), sizeof(int32_t), hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipMemcpyAsync(h + head_bytes, d_rows, rows_bytes, hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipStreamSynchronize(r->stream));
+        memcpy(&n_kept, h, sizeof n_kept);
+    }
+    memcpy(site_rows, h + head_bytes, rows_bytes);
+    tot[UVC_CLIPMTOTAL_clusters] = n_clus; tot[UVC_CLIPMTOTAL_clusters_kept] = n_kept; tot[UVC_CLIPMTOTAL_sites_kept] = 0;
+    for (int64_t k = 0; k < n_sites; k++) {
+        int64_t *row = site_rows + k * UVC_CLIPMATE_SITE_ROW;
+        row[UVC_CLIPMSITE_site] = k;
+        row[UVC_CLIPMSITE_facing] = row[UVC_CLIPMSITE_concordant] + row[UVC_CLIPMSITE_other_contig] + row[UVC_CLIPMSITE_same_strand] + row[UVC_CLIPMSITE_far];   // (the device adds the class counters alone)
+        tot[UVC_CLIPMTOTAL_sites_kept] += (site_rows[k * UVC_CLIPMATE_SITE_ROW + UVC_CLIPMSITE_clusters_kept] > 0);
+    }
+    memcpy(totals, tot, totals_bytes);
+    *n_clusters = n_kept; *n_reads = n_wit;
+    if (n_kept > cluster_capacity) return fail(UVCGPU_ENOMEM, "clip_mates: " + std::to_string(n_kept) + " kept clusters, room for " + std::to_string(cluster_capacity));
+    if (req->want_reads && n_wit > read_capacity) return fail(UVCGPU_ENOMEM, "clip_mates: " + std::to_string(n_wit) + " witness rows, room for " + std::to_string(read_capacity));
+    const size_t out_bytes = sizeof(int64_t) * UVC_CLIPMATE_ROW * (size_t)n_kept, reads_bytes = req->want_reads ? sizeof(UvcClipMate) * (size_t)n_wit : 0;
+    if (out_bytes + reads_bytes == 0) return 0;
+    { int rc1 = report_buffers(r, 0, out_bytes + reads_bytes, "clip mates"); if (rc1) return rc1; }
+    h = r->h_report;
+    if (out_bytes) HIP_OK(hipMemcpyAsync(h, d_out, out_bytes, hipMemcpyDeviceToHost, r->stream));
+    if (reads_bytes) HIP_OK(hipMemcpyAsync(h + out_bytes, d_reads, reads_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_OK(hipStreamSynchronize(r->stream));
+    if (out_bytes) memcpy(clusters, h, out_bytes);
+    if (reads_bytes) memcpy(reads, h + out_bytes, reads_bytes);
+    return 0;
+}
+int uvcgpu_region_clip_mates(uvcgpu_region_t *r, const int64_t *sites, int64_t n_sites, const int32_t *mtid, const UvcClipMatesRequest *req, int64_t *totals, int64_t *site_rows,
+                             int64_t *clusters, int64_t cluster_capacity, int64_t *n_clusters, UvcClipMate *reads, int64_t read_capacity, int64_t *n_reads) {
+    return guarded("uvcgpu_region_clip_mates", [&] { return uvcgpu_region_clip_mates_impl(r, sites, n_sites, mtid, req, totals, site_rows, clusters, cluster_capacity, n_clusters, reads, read_capacity, n_reads); });
+}
+const char *uvcgpu_clip_mate_site_name(int32_t id) { return uvc_clipmates_site_name(id); }
+const char *uvcgpu_clip_mate_cluster_name(int32_t id) { return uvc_clipmates_cluster_name(id); }
+const char *uvcgpu_clip_mate_class_name(int32_t klass) { return uvc_clipmates_class_name(klass); }
 
 // ---- callable-region intervals of ranges (uvc_callable.hip): [table] [block counts] [mask bytes] [runs, one per position at worst] ----
 // Sizes first: the count and the scan run, the host reads the number of runs (4 bytes), and only a call with enough room launches the emit

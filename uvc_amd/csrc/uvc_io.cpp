@@ -1653,7 +1653,14 @@ enum {
 #define UVC_CLIPJUNC(name, first, words) CJW_##name = first,
 #include "uvc_clipjunc.def"
 #undef UVC_CLIPJUNC
+#define UVC_CLIPMATE_SITE(name, first, words) CMSW_##name = first,
+#define UVC_CLIPMATE_CLUSTER(name, first, words) CMCW_##name = first,
+#include "uvc_clipmates.def"
+#undef UVC_CLIPMATE_SITE
+#undef UVC_CLIPMATE_CLUSTER
 };
+static_assert(CMSW_facing == 1 && CMSW_clusters_kept == UVC_CLIPMATE_SITE_ROW - 1 && CMCW_mapq_sum == CMCW_pairs + 4 && (int)CMCW_first < (int)UVC_CLIPMATE_ROW,
+              "the words of a P line are facing .. clusters_kept, those of an M line pairs .. mapq_sum of include/uvc_clipmates.def");
 static_assert(CJW_hist + UVC_CLIPJUNC_NHIST <= UVC_CLIPJUNC_ROW && CJW_mate < CJW_hist, "the words of a J line are query_len .. mate of include/uvc_clipjunc.def");
 static_assert(CSW_VOTE == UVC_CLIPSITE_VOTE_BINS && CSW_VOTE + UVC_CLIPSITE_NCONS * UVC_CLIPSITE_NCODE == UVC_CLIPSITE_ROW && CSW_spanning == CSW_reads + 8,
               "the words of an S line are reads .. spanning of include/uvc_clipsites.def, the votes fill the row behind the counters");
@@ -1662,8 +1669,12 @@ struct uvcio_clipsites {
     UvcClipSitesRequest req;
     struct Event { std::string qname; int32_t flag, mapq, soft, hard, fam, strand, frag; };
     // junc: the site's row of uvcgpu_region_clip_junctions, when its call came with them; its mate, an index into the call's rows, as (pos, side)
-    struct Site { std::string contig; int64_t row[UVC_CLIPSITE_ROW]; std::vector<Event> events; bool has_junc = false; int64_t junc[UVC_CLIPJUNC_ROW], mate_pos = -1, mate_side = -1; };
+    // a kept cluster of uvcgpu_region_clip_mates with what the host counts over its witnesses: fragments, families, families on both strands
+    struct Mate { int64_t row[UVC_CLIPMATE_ROW], frags, fams, both; };
+    struct Site { std::string contig; int64_t row[UVC_CLIPSITE_ROW]; std::vector<Event> events; bool has_junc = false; int64_t junc[UVC_CLIPJUNC_ROW], mate_pos = -1, mate_side = -1;
+                  bool has_mates = false; int64_t mrow[UVC_CLIPMATE_SITE_ROW]; std::vector<Mate> mates; };
     bool junctions = false; UvcClipJunctionsRequest jreq{ 0, 0, 0, 0, 0 };   // uvcio_clipsites_set_junctions
+    bool mates = false; UvcClipMatesRequest mreq{ 0, 0, 0, 0, 0, 0, 0, 0 }; std::vector<std::string> contigs;   // uvcio_clipsites_set_mates
     std::map<std::tuple<int32_t, int64_t, int64_t>, Site> sites;   // by (tid, zero-based position, side)
     std::mutex mu;
 };
@@ -1680,8 +1691,17 @@ extern "C" int uvcio_clipsites_set_junctions(uvcio_clipsites_t *f, int32_t min_v
     f->jreq = UvcClipJunctionsRequest{ min_votes, min_len, max_mismatch, max_dist, mate_slop };
     return 0;
 }
-extern "C" int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, const int64_t *junctions, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads,
-                                             int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
+extern "C" int uvcio_clipsites_set_mates(uvcio_clipsites_t *f, int32_t window, int32_t overhang, int32_t min_dist, int32_t max_gap, int32_t min_pairs, const char *const *contig_names, int32_t n_contigs) {
+    if (!f || n_contigs < 0 || (n_contigs > 0 && !contig_names)) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
+    f->mates = true;
+    f->mreq = UvcClipMatesRequest{ 0, f->req.min_mapq, window, overhang, min_dist, max_gap, min_pairs, 1 };
+    f->contigs.clear();
+    for (int32_t k = 0; k < n_contigs; k++) f->contigs.push_back(contig_names[k] ? contig_names[k] : ".");
+    return 0;
+}
+extern "C" int uvcio_clipsites_add_mates(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, const int64_t *junctions, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads,
+                                         int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id,
+                                         const int64_t *site_rows, const int64_t *clusters, int64_t n_clusters, const UvcClipMate *mates, int64_t n_mates) {
     if (!f || !contig || n_sites < 0 || (n_sites > 0 && !sites) || n_reads < 0) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
     if (n_reads > 0 && (!reads || !qnames || !flag || !mapq || !fam_id || !fam_strand || !frag_id)) return fail(UVCGPU_EINVAL, "clip sites: event rows without the columns of their alignments");
     // what the sites keep is made outside the lock
@@ -1698,6 +1718,30 @@ extern "C" int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, 
         const int64_t mate = m.junc[CJW_mate], klass = m.junc[CJW_klass];
         if (mate >= n_sites || klass < 0 || klass >= UVC_NCLIPCLASS) return fail(UVCGPU_EINVAL, "clip sites: junction row " + std::to_string(s) + " has mate " + std::to_string(mate) + " and class " + std::to_string(klass) + ", which the call does not hold");
         if (mate >= 0) { m.mate_pos = sites[mate * UVC_CLIPSITE_ROW + CSW_pos]; m.mate_side = sites[mate * UVC_CLIPSITE_ROW + CSW_side]; }
+    }
+    if (site_rows) {   // the call's rows of uvcgpu_region_clip_mates: a P line per site, an M line per kept cluster
+        if (n_clusters < 0 || n_mates < 0 || (n_clusters > 0 && !clusters)) return fail(UVCGPU_EINVAL, "clip sites: bad argument");
+        if (n_mates > 0 && (!mates || !fam_id || !fam_strand || !frag_id)) return fail(UVCGPU_EINVAL, "clip sites: witness rows without the columns of their alignments");
+        for (int64_t s = 0; s < n_sites; s++) { made[(size_t)s].has_mates = true; memcpy(made[(size_t)s].mrow, site_rows + s * UVC_CLIPMATE_SITE_ROW, sizeof(int64_t) * UVC_CLIPMATE_SITE_ROW); }
+        std::vector<std::set<std::tuple<int32_t, int32_t, int32_t>>> frags((size_t)n_clusters);
+        std::vector<std::map<int32_t, int>> strands((size_t)n_clusters);   // family -> bit 0 / 1: a witness of fam_strand 0 / 1
+        for (int64_t k = 0; k < n_mates; k++) {
+            const UvcClipMate &w = mates[k];
+            if (w.cluster >= n_clusters || w.read < 0 || w.read >= n_alns) return fail(UVCGPU_EINVAL, "clip sites: witness row " + std::to_string(k) + " names cluster " + std::to_string(w.cluster) + " and alignment " + std::to_string(w.read) + ", which the call does not hold");
+            if (w.cluster < 0) continue;
+            const int a = w.read;
+            frags[(size_t)w.cluster].insert(std::make_tuple(fam_id[a], (int32_t)fam_strand[a], frag_id[a]));
+            strands[(size_t)w.cluster][fam_id[a]] |= 1 << (fam_strand[a] & 1);
+        }
+        for (int64_t c = 0; c < n_clusters; c++) {   // (in witness order: the M lines of a site keep it)
+            uvcio_clipsites::Mate m;
+            memcpy(m.row, clusters + c * UVC_CLIPMATE_ROW, sizeof m.row);
+            const int64_t s = m.row[CMCW_site], strand = m.row[CMCW_mate_strand];
+            if (s < 0 || s >= n_sites || strand < 0 || strand > 1) return fail(UVCGPU_EINVAL, "clip sites: cluster row " + std::to_string(c) + " has site " + std::to_string(s) + " and mate strand " + std::to_string(strand) + ", which the call does not hold");
+            m.frags = (int64_t)frags[(size_t)c].size(); m.fams = (int64_t)strands[(size_t)c].size(); m.both = 0;
+            for (const auto &kv : strands[(size_t)c]) m.both += (kv.second == 3);
+            made[(size_t)s].mates.push_back(m);
+        }
     }
     for (int64_t k = 0; k < n_reads; k++) {
         const UvcClipRead &r = reads[k];
@@ -1716,6 +1760,10 @@ extern "C" int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, 
     }
     return 0;
 }
+extern "C" int uvcio_clipsites_add_junctions(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, const int64_t *junctions, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads,
+                                             int64_t n_alns, const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
+    return uvcio_clipsites_add_mates(f, tid, contig, sites, junctions, n_sites, reads, n_reads, n_alns, qnames, flag, mapq, fam_id, fam_strand, frag_id, nullptr, nullptr, 0, nullptr, 0);
+}
 extern "C" int uvcio_clipsites_add(uvcio_clipsites_t *f, int32_t tid, const char *contig, const int64_t *sites, int64_t n_sites, const UvcClipRead *reads, int64_t n_reads, int64_t n_alns,
                                    const char *const *qnames, const uint16_t *flag, const uint8_t *mapq, const int32_t *fam_id, const uint8_t *fam_strand, const int32_t *frag_id) {
     return uvcio_clipsites_add_junctions(f, tid, contig, sites, nullptr, n_sites, reads, n_reads, n_alns, qnames, flag, mapq, fam_id, fam_strand, frag_id);
@@ -1728,9 +1776,14 @@ extern "C" int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *pat
                        + (f->junctions ? "\n##clip_sites_junction_min_votes=" + std::to_string(f->jreq.min_votes) + "\n##clip_sites_junction_min_len=" + std::to_string(f->jreq.min_len) + "\n##clip_sites_junction_max_mismatch="
                                              + std::to_string(f->jreq.max_mismatch) + "\n##clip_sites_junction_max_dist=" + std::to_string(f->jreq.max_dist) + "\n##clip_sites_junction_slop=" + std::to_string(f->jreq.mate_slop)
                                        : std::string())
+                       + (f->mates ? "\n##clip_sites_mate_window=" + std::to_string(f->mreq.window) + "\n##clip_sites_mate_overhang=" + std::to_string(f->mreq.overhang) + "\n##clip_sites_mate_min_dist="
+                                         + std::to_string(f->mreq.min_dist) + "\n##clip_sites_mate_max_gap=" + std::to_string(f->mreq.max_gap) + "\n##clip_sites_mate_min_pairs=" + std::to_string(f->mreq.min_pairs)
+                                   : std::string())
                        + "\n#S\tcontig\tpos\tside\treads\tfwd\tsupp\tsecondary\thard\tlen_sum\tlen_max\tmapq_sum\tspanning\tfragments\tfamilies\tfamilies_both_strands\tcons_len\tcons\n"
                          "#R\tcontig\tpos\tside\tqname\tflag\tmapq\tsoft_len\thard_len\tfamily_rank\tstrand\n";
     if (f->junctions) text += "#J\tcontig\tpos\tside\tquery_len\tcmp_len\tstatus\tbest_mm\tn_best\tsecond_mm\tpartner_pos\tstrand\tclass\tlen\tmate_pos\tmate_side\n";
+    if (f->mates) text += "#P\tcontig\tpos\tside\tfacing\tconcordant\tother_contig\tsame_strand\tfar\tclusters\tclusters_kept\n"
+                          "#M\tcontig\tpos\tside\tmate_contig\tmate_beg\tmate_end\tmate_strand\tpairs\tother_contig\tsame_strand\tfar\tmapq_sum\tfragments\tfamilies\tfamilies_both_strands\n";
     static const char *const classes[UVC_NCLIPCLASS] = { "NONE", "DEL", "DUP", "INV", "ADJACENT" };
     auto dot = [](int64_t v, int64_t add) { return v < 0 ? std::string(".") : std::to_string(v + add); };
     for (const auto &kv : f->sites) {   // (the map is ordered by (tid, pos, side))
@@ -1762,6 +1815,18 @@ extern "C" int uvcio_clipsites_write(const uvcio_clipsites_t *f, const char *pat
             text += "J" + at + "\t" + std::to_string(j[CJW_query_len]) + "\t" + std::to_string(j[CJW_cmp_len]) + "\t" + std::to_string(j[CJW_status]) + "\t" + dot(j[CJW_best_mm], 0) + "\t" + std::to_string(j[CJW_n_best])
                     + "\t" + dot(j[CJW_second_mm], 0) + "\t" + dot(j[CJW_partner], 1) + "\t" + (j[CJW_strand] < 0 ? "." : j[CJW_strand] ? "-" : "+") + "\t" + classes[j[CJW_klass]] + "\t" + dot(j[CJW_len], 0)
                     + "\t" + dot(site.mate_pos, 1) + "\t" + (site.mate_side < 0 ? "." : site.mate_side == UVC_CLIPSITE_LEFT ? "L" : "R") + "\n";
+        }
+        if (f->mates && site.has_mates) {   // the P line and the M lines of the kept clusters behind the S (and J) line
+            text += "P" + at;
+            for (int w = CMSW_facing; w <= CMSW_clusters_kept; w++) text += "\t" + std::to_string(site.mrow[w]);
+            text += "\n";
+            for (const uvcio_clipsites::Mate &m : site.mates) {
+                const int64_t mt = m.row[CMCW_mtid];
+                text += "M" + at + "\t" + (mt >= 0 && mt < (int64_t)f->contigs.size() ? f->contigs[(size_t)mt] : std::string(".")) + "\t" + std::to_string(m.row[CMCW_mpos_min] + 1) + "\t"
+                        + std::to_string(m.row[CMCW_mpos_max] + 1) + "\t" + (m.row[CMCW_mate_strand] ? "-" : "+");
+                for (int w = CMCW_pairs; w <= CMCW_mapq_sum; w++) text += "\t" + std::to_string(m.row[w]);
+                text += "\t" + std::to_string(m.frags) + "\t" + std::to_string(m.fams) + "\t" + std::to_string(m.both) + "\n";
+            }
         }
         if (!f->req.want_reads || site.events.empty()) continue;
         // a family's rank: by the smallest (qname, flag) of its events at this site

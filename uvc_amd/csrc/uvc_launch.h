@@ -192,6 +192,33 @@ int64_t uvc_clipjunc_query_bytes(int64_t n_sites);
 const char *uvc_clipjunc_name(int id);
 const char *uvc_clipjunc_class_name(int k);
 int uvc_clipjunc_naive(void);
+// ---- uvc_clipmates.hip: five stages (count, scatter, rank, cut, reduce), each one entry of uvcgpu_region_kernel_times; the host waits behind
+// the count, the cut and the reduce.
+// L: the site lists and the mtid column on the device.  d_rows: n_sites rows of UVC_CLIPMATE_SITE_ROW words, d_totals: UVC_CLIPMATE_NTOTAL
+// words and d_site_ints: uvc_clipmates_site_ints(n_sites) ints, all three zero at the start.  Behind the count the ints at
+// uvc_clipmates_n_witnesses_at / _n_rank_blocks_at hold the two numbers the scatter and the rank need (n_wit >= 1); d_key / d_okey: n_wit words each;
+// d_wit_ints: uvc_clipmates_witness_ints(n_wit) ints.  Behind the cut the int at uvc_clipmates_n_clusters_at holds n_clus; d_crow: n_clus
+// rows of UVC_CLIPMATE_ROW words, zero at the start; d_out: room for n_clus rows; d_reads: n_wit rows or NULL; d_clus_ints:
+// uvc_clipmates_cluster_ints(n_clus) ints.  Behind the reduce the int at uvc_clipmates_n_kept_at holds the number of rows in d_out ----
+struct UvcClipMateLists { const int32_t *spos, *sidx, *mtid; int n_sites, n_left; };
+void uvc_launch_clipmates_count(const RawReads *W, int64_t n_alns, const UvcClipMateLists *L, const UvcClipMatesRequest *req, long long *d_rows, long long *d_totals, int32_t *d_site_ints, hipStream_t s);
+void uvc_launch_clipmates_scatter(const RawReads *W, int64_t n_alns, const UvcClipMateLists *L, const UvcClipMatesRequest *req, int32_t *d_site_ints, int n_wit,
+                                  unsigned long long *d_key, int32_t *d_wit_ints, hipStream_t s);
+void uvc_launch_clipmates_rank(const UvcClipMateLists *L, const int32_t *d_site_ints, int n_wit, int n_rank_blocks, const unsigned long long *d_key, unsigned long long *d_okey,
+                               int32_t *d_wit_ints, hipStream_t s);
+void uvc_launch_clipmates_cut(const UvcClipMateLists *L, const UvcClipMatesRequest *req, const int32_t *d_site_ints, int n_wit, const unsigned long long *d_okey, int32_t *d_wit_ints, hipStream_t s);
+void uvc_launch_clipmates_reduce(const RawReads *W, const UvcClipMateLists *L, const UvcClipMatesRequest *req, int n_wit, int n_clus, const unsigned long long *d_okey, int32_t *d_wit_ints,
+                                 long long *d_crow, long long *d_rows, long long *d_out, UvcClipMate *d_reads, int32_t *d_clus_ints, hipStream_t s);
+int64_t uvc_clipmates_site_ints(int64_t n_sites);
+int64_t uvc_clipmates_witness_ints(int64_t n_wit);
+int64_t uvc_clipmates_cluster_ints(int64_t n_clus);
+const int32_t *uvc_clipmates_n_witnesses_at(const int32_t *d_site_ints, int64_t n_sites);
+const int32_t *uvc_clipmates_n_rank_blocks_at(const int32_t *d_site_ints, int64_t n_sites);
+const int32_t *uvc_clipmates_n_clusters_at(const int32_t *d_wit_ints, int64_t n_wit);
+const int32_t *uvc_clipmates_n_kept_at(const int32_t *d_clus_ints, int64_t n_clus);
+const char *uvc_clipmates_site_name(int id);
+const char *uvc_clipmates_cluster_name(int id);
+const char *uvc_clipmates_class_name(int k);
 // ---- uvc_callable.hip: d_tab = n_ranges + 1 rows; d_mask: n_total bytes; d_blocks: uvc_callable_blocks(n_total) + 1 ints, the last one the
 // number of runs once the count has run; d_runs: room for that many runs.  The emit follows a count with the same arguments ----
 void uvc_launch_callable_count(const RegionDev *R, const UvcRangeRow *d_tab, int n_ranges, int64_t n_total, const UvcCallableRequest *req, unsigned char *d_mask, int *d_blocks, hipStream_t s);

@@ -1,4 +1,4 @@
-// uvc_report_dev.h -- what the kernels of the ten report calls share on the device: the wave-merged LDS counters, the
+// uvc_report_dev.h -- what the kernels of the eleven report calls share on the device: the wave-merged LDS counters, the
 // three searches, the segmented fold, a block's LDS window of per-range rows, the rank of a head among the block's heads and the section
 // table of a row.  Device code only, force-inlined, with each function's wave or
 // block contract beside it; blocks are one-dimensional, 256 threads where a function says "block".  The kernels that several reports

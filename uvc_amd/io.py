@@ -342,15 +342,24 @@ class ClipSites(_Store):
         d.uvcio_clipsites_set_junctions.restype, d.uvcio_clipsites_set_junctions.argtypes = C.c_int, [C.c_void_p] + [C.c_int32] * 5
         d.uvcio_clipsites_add_junctions.restype, d.uvcio_clipsites_add_junctions.argtypes = C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                                                                                       C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        d.uvcio_clipsites_set_mates.restype, d.uvcio_clipsites_set_mates.argtypes = C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_char_p), C.c_int32]
+        d.uvcio_clipsites_add_mates.restype, d.uvcio_clipsites_add_mates.argtypes = C.c_int, d.uvcio_clipsites_add_junctions.argtypes + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         _check(d.uvcio_clipsites_open(C.byref(self.h), int(min_mapq), int(min_clip), int(min_reads), int(with_reads)))
 
     def set_junctions(self, min_votes=2, min_len=16, max_mismatch=1, max_dist=0, mate_slop=10):
         """Turns the J lines on: the request values of the Region.clip_junctions calls whose rows add(junctions=) hands over."""
         _check(dll().uvcio_clipsites_set_junctions(self.h, int(min_votes), int(min_len), int(max_mismatch), int(max_dist), int(mate_slop)))
 
-    def add(self, tid, contig, rows, events=None, reads=None, qnames=None, junctions=None):
+    def set_mates(self, window=500, overhang=5, min_dist=1000, max_gap=500, min_pairs=2, contig_names=()):
+        """Turns the P and M lines on: the request values of the Region.clip_mates calls whose results add(mates=) hands over, and the
+        contig names of the BAM header, which the mate contig ids index."""
+        names = (C.c_char_p * max(len(contig_names), 1))(*[c.encode() if isinstance(c, str) else c for c in contig_names])
+        _check(dll().uvcio_clipsites_set_mates(self.h, int(window), int(overhang), int(min_dist), int(max_gap), int(min_pairs), names, len(contig_names)))
+
+    def add(self, tid, contig, rows, events=None, reads=None, qnames=None, junctions=None, mates=None):
         """rows, events: the second and third result of Region.clip_sites; reads: the reads the region was given (flag, mapq, fam_id,
-        fam_strand, frag_id); qnames: one name per alignment; junctions: the second result of Region.clip_junctions(rows), or None."""
+        fam_strand, frag_id); qnames: one name per alignment; junctions: the second result of Region.clip_junctions(rows), or None; mates:
+        the second, third and fourth result of Region.clip_mates(rows, ..., want_reads=True) -- (site rows, cluster rows, reads) -- or None."""
         import numpy as np
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         if rows.ndim != 2 or rows.shape[1] != 176:
@@ -360,21 +369,35 @@ class ClipSites(_Store):
             if junctions.shape != (len(rows), 24):
                 raise ValueError("junctions is the second result of Region.clip_junctions(rows) ([n_sites, 24])")
         jp = junctions.ctypes.data if junctions is not None and len(rows) else None
+        mate_args = (None, None, 0, None, 0)
+        n_wit = 0
+        if mates is not None:
+            msites, mclus, mwit = (np.ascontiguousarray(mates[0], dtype=np.int64), np.ascontiguousarray(mates[1], dtype=np.int64), np.ascontiguousarray(mates[2]))
+            if msites.shape != (len(rows), 8) or mclus.ndim != 2 or mclus.shape[1] != 12 or mwit.dtype.itemsize != 16:
+                raise ValueError("mates is (site rows [n_sites, 8], cluster rows [n, 12], reads) of Region.clip_mates(rows, ..., want_reads=True)")
+            n_wit = len(mwit)
+            if len(rows):
+                mate_args = (msites.ctypes.data, mclus.ctypes.data if len(mclus) else None, len(mclus), mwit.ctypes.data if n_wit else None, n_wit)
         n_ev = 0 if events is None else len(events)
-        if n_ev == 0:
-            _check(dll().uvcio_clipsites_add_junctions(self.h, int(tid), contig.encode(), rows.ctypes.data, jp, len(rows), None, 0, 0, None, None, None, None, None, None))
+        if n_ev == 0 and n_wit == 0:
+            _check(dll().uvcio_clipsites_add_mates(self.h, int(tid), contig.encode(), rows.ctypes.data, jp, len(rows), None, 0, 0, None, None, None, None, None, None, *mate_args))
             return
-        events = np.ascontiguousarray(events)
-        if events.dtype.itemsize != 16 or reads is None or qnames is None:
-            raise ValueError("event rows come with the reads of their call and their names")
-        n = len(qnames)
+        if reads is None or (n_ev and qnames is None):
+            raise ValueError("event rows come with the reads of their call and their names, witness rows with the reads of their call")
+        ep = None
+        if n_ev:
+            events = np.ascontiguousarray(events)
+            if events.dtype.itemsize != 16:
+                raise ValueError("event rows come with the reads of their call and their names")
+            ep = events.ctypes.data
         col = lambda k, t: np.ascontiguousarray(reads[k], dtype=t)                      # noqa: E731
         fl, mq, fam, st, fr = col("flag", np.uint16), col("mapq", np.uint8), col("fam_id", np.int32), col("fam_strand", np.uint8), col("frag_id", np.int32)
+        n = len(qnames) if qnames is not None else min(len(fl), len(mq), len(fam), len(st), len(fr))
         if min(len(fl), len(mq), len(fam), len(st), len(fr)) < n:
             raise ValueError("every alignment has a name")
-        names = (C.c_char_p * n)(*[q.encode() if isinstance(q, str) else q for q in qnames])
-        _check(dll().uvcio_clipsites_add_junctions(self.h, int(tid), contig.encode(), rows.ctypes.data, jp, len(rows), events.ctypes.data, n_ev, n, names, fl.ctypes.data, mq.ctypes.data, fam.ctypes.data, st.ctypes.data,
-                                                   fr.ctypes.data))
+        names = (C.c_char_p * n)(*[q.encode() if isinstance(q, str) else q for q in qnames]) if qnames is not None else None
+        _check(dll().uvcio_clipsites_add_mates(self.h, int(tid), contig.encode(), rows.ctypes.data, jp, len(rows), ep, n_ev, n, names, fl.ctypes.data, mq.ctypes.data, fam.ctypes.data, st.ctypes.data,
+                                               fr.ctypes.data, *mate_args))
 
 
 class Callable(_Store):

@@ -153,6 +153,7 @@ def call_region(lib, bam, fasta, chrom, beg, end, params=None, group_params=None
         out["vcf"] = R.vcf_records(chrom, rec, tumor_keys=tk, tumor_sample_columns=tcols, tumor_ref_alt=tras, **skw)          # the record lines of append_vcf_record (uvcgpu_region_vcf_records), before the handle moves on
     if keep_handle:                                                                    # with the reads the handle was given; alignment i of them is alignment order[i] of the fetch, whose name is qnames[order[i]] (decoded on demand)
         out["region"], out["reads"], out["qnames"], out["order"] = R, reads, cols["qnames"], o
+        out["mtid"] = cols["mtid"][o]                                                    # the mate contigs of those reads (Region.clip_mates; UvcReadSoA has no such column)
     elif reuse is None:
         R.close()
     lap("alleles+close")

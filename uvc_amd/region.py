@@ -31,6 +31,7 @@ READ_CLASSES = ["R1_fwd", "R1_rev", "R2_fwd", "R2_rev"]   # the read classes of 
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
 SITE_READ_KINDS = _ffi.SITE_READ_KINDS       # the observation kinds of Region.site_reads, in id order: A C G T N DEL
 CLIP_READ = np.dtype([(n, np.int32) for n, _ in _ffi.UvcClipRead._fields_])   # UvcClipRead: site read soft_len hard_len
+CLIP_MATE = np.dtype([(n, np.int32) for n, _ in _ffi.UvcClipMate._fields_])   # UvcClipMate: site read cluster klass
 SITE_READ = np.dtype([(n, np.int32) for n, _ in _ffi.UvcSiteRead._fields_])   # UvcSiteRead: site read q obs ins_q ins_len del_len reserved
 CALLABLE_RUN = np.dtype([("range", np.int32), ("pos_beg", np.int32), ("pos_end", np.int32), ("mask", np.int32)])   # UvcCallableRun
 
@@ -641,6 +642,36 @@ class Region:
         out = np.zeros((max(len(rows), 1), _ffi.ENUMS["UVC_CLIPJUNC_ROW"]), dtype=np.int64)
         self._check(fn(self.h, rows.ctypes.data if len(rows) else None, len(rows), C.byref(req), out.ctypes.data, totals.ctypes.data))
         return totals, out[:len(rows)].copy()
+
+    def clip_mates(self, rows, mtid, tid, min_mapq=0, window=500, overhang=5, min_dist=1000, max_gap=500, min_pairs=2, want_reads=True):
+        """uvcgpu_region_clip_mates: the read pairs of the region's reads that face each site row of clip_sites() and where the mates of the
+        discordant ones cluster.  mtid: the contig of every alignment's mate, one int32 per alignment in the order of the reads as given,
+        or None (every mate on `tid`, the region's contig).  A forward pair read faces a RIGHT site p when pos < p and p - window < end <=
+        p + overhang, a reverse one a LEFT site p when end > p and p - overhang <= pos < p + window; an item is OTHER_CONTIG, SAME_STRAND,
+        FAR (|mpos - pos| >= min_dist) or CONCORDANT; the discordant ones, ordered by (site, mate contig, mate strand, mpos, read), are cut
+        into clusters where the contig or strand changes or mpos grows by more than max_gap; a cluster of at least min_pairs is kept.
+        -> (totals, site rows, cluster rows, reads): totals int64 [8] (_ffi.CLIPMATE_TOTALS names the first seven); site rows int64
+        [n_sites, UVC_CLIPMATE_SITE_ROW] (_ffi.CLIPMATE_SITE_WORDS); cluster rows int64 [n_kept, UVC_CLIPMATE_ROW]
+        (_ffi.CLIPMATE_CLUSTER_WORDS); reads: with want_reads a structured array of CLIP_MATE (site, read, cluster: index into the cluster
+        rows or -1, klass: _ffi.CLIPMATE_CLASSES), one per witness in witness order, else None.  uvcgpu.h has the rules.  Gathered, ranked
+        and clustered on the device; asks for the sizes first, then for the rows.  Legal where clip_sites() is."""
+        fn = self._ranges_fn("region_clip_mates", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                            C.c_void_p])
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, _ffi.ENUMS["UVC_CLIPSITE_ROW"])
+        mt = None if mtid is None else np.ascontiguousarray(mtid, dtype=np.int32)
+        req = _ffi.UvcClipMatesRequest(int(tid), int(min_mapq), int(window), int(overhang), int(min_dist), int(max_gap), int(min_pairs), int(want_reads))
+        totals = np.zeros(_ffi.ENUMS["UVC_CLIPMATE_NTOTAL"], dtype=np.int64)
+        site_rows = np.zeros((max(len(rows), 1), _ffi.ENUMS["UVC_CLIPMATE_SITE_ROW"]), dtype=np.int64)
+        nc, nr = C.c_int64(0), C.c_int64(0)
+        args = (self.h, rows.ctypes.data if len(rows) else None, len(rows), None if mt is None else mt.ctypes.data, C.byref(req), totals.ctypes.data, site_rows.ctypes.data)
+        rc = fn(*args, None, 0, C.byref(nc), None, 0, C.byref(nr))
+        if rc != _ffi.ENUMS["UVCGPU_ENOMEM"]:
+            self._check(rc)
+        out = np.zeros((max(nc.value, 1), _ffi.ENUMS["UVC_CLIPMATE_ROW"]), dtype=np.int64)
+        ev = np.zeros(max(nr.value, 1), dtype=CLIP_MATE)
+        if rc:
+            self._check(fn(*args, out.ctypes.data, nc.value, C.byref(nc), ev.ctypes.data if want_reads else None, nr.value if want_reads else 0, C.byref(nr)))
+        return totals, site_rows[:len(rows)].copy(), out[:nc.value].copy(), (ev[:nr.value].copy() if want_reads else None)
 
     def msi(self, ranges, min_tracklen=10, min_units=5, max_unitlen=6):
         """uvcgpu_region_msi: the microsatellite loci whose head lies in `ranges` -- (pos_beg, pos_end) pairs as for coverage() -- as the STR
