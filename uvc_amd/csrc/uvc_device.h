@@ -59,12 +59,14 @@ struct FastRec {
                                             // (index of the base at position p) - p; aln: index into alns[]
     int32_t fmd, isize, mpos, xm1500;       // fmd = flag | mapq << 16 | dflag << 24
     int32_t bmv, xbv, bm4c, clips;          // bmv: a2BM2 increment (<= 100) of base symbols 0..3, one byte each; xbv: that of symbol 4 | a2XM2 increment << 8 | FREC_M_RUN;
-                                            // bm4c: clip_cnt << 16 | (nogap_penal & 0xFFFF); clips = lclip_oplen | rclip_oplen << 16
+                                            // bm4c: clip_cnt << 16 | (nogap_penal & 0xFFFF); clips = lclip_oplen | rclip_oplen << 16, each saturated at FREC_CLIP_MAX
     int32_t baq_pos, baq_last, baq2_last, ext;   // ext: (pos - read start) | (read end - rend) << 16, zero for a whole read
 };
 // in FastRec::xbv: the entry is an M run of an InDel read, not a whole simple alignment.  (ext == 0 does not say so: the one M run of 2I58M
 // spans its whole alignment.)  P1 walks the same list as P2 and skips these entries: k_prep_slow has the read.
 #define FREC_M_RUN (1 << 16)
+// a half of FastRec::clips with this value says "this long or longer": the length itself is AlnRec::lclip_oplen / rclip_oplen
+#define FREC_CLIP_MAX 0xFFFF
 static_assert(sizeof(FastRec) == 64, "the position-centric kernels fetch a work-list record as four 16-byte words per lane");
 #define FR_W(field) ((int)(offsetof(FastRec, field) / 4))   // the dword of a field in a record fetched as words (load_words, the scalar-cache copies of k_p2_fast)
 

@@ -397,7 +397,7 @@ DEV void fill_fastrec(FastRec &f, const AlnRec &a, int id, int cbeg, int cend, i
     const int xv = (a.xm1500 > 20 ? (100 * (20 * 20) / (a.xm1500 * a.xm1500)) : 100);
     f.bmv = bv[0] | (bv[1] << 8) | (bv[2] << 16) | (bv[3] << 24); f.xbv = bv[4] | (xv << 8) | (m_run ? FREC_M_RUN : 0);
     f.bm4c = ((a.clip_cnt & 0xF) << 16) | (a.nogap_penal & 0xFFFF);   // nogap_penal is negative when NM < the InDel lengths
-    f.clips = (a.lclip_oplen & 0xFFFF) | (a.rclip_oplen << 16);
+    f.clips = imin(a.lclip_oplen, FREC_CLIP_MAX) | (imin(a.rclip_oplen, FREC_CLIP_MAX) << 16);   // saturated: frec_clip_len reads a full half from alns[]
     f.baq_pos = (int32_t)a.baq_pos; f.baq_last = (int32_t)a.baq_last; f.baq2_last = (int32_t)a.baq2_last;
     f.ext = ((cbeg - a.pos) & 0xFFFF) | ((a.rend - cend) << 16);
 }
@@ -577,6 +577,14 @@ DEV void clip_event(const RegionDev &R, const UvcParams &P, int rpos, int i, int
     }
 }
 
+// The clip op length of a simple alignment from one 16-bit half of FastRec::clips.  A half below FREC_CLIP_MAX is the length itself; a full
+// half stands for "65 535 or more" (a BAM op length has 28 bits: the hard clip of a supplementary alignment of an ultra-long read) and the
+// length comes from the alignment's own record, so that every microadjust_alignment_clip_min_len compares with the CIGAR's value.
+DEV int frec_clip_len(const RegionDev &R, int half, int aln, bool right) {
+    if (half < FREC_CLIP_MAX) return half;
+    return right ? R.alns[aln].rclip_oplen : R.alns[aln].lclip_oplen;
+}
+
 DEV int simple_base_value(const UvcParams &P, const AlnRec &a, int p, const uint8_t *quals_qbase, bool proton);
 
 // A mismatching base of a simple alignment: decide with the reference's fragment consensus (main.hpp:2658-2726) whether
@@ -752,7 +760,8 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
                 }
                 const int clips = bcast(c[FR_W(clips)], j);
                 if (clips != 0) {
-                    const int lclip = clips & 0xFFFF, rclip = (clips >> 16) & 0xFFFF;
+                    const int aln = bcast(c[FR_W(aln)], j);
+                    const int lclip = frec_clip_len(R, clips & 0xFFFF, aln, false), rclip = frec_clip_len(R, (clips >> 16) & 0xFFFF, aln, true);
                     const int pcr_inc = (((bcast(c[FR_W(fmd)], j) >> 24) & UVC_DFLAG_AMPLICON) ? 1 : 0);
                     if (p == apos && lclip > 0) clip_event(R, P, apos, 0, lclip, pcr_inc);
                     if (p == rend - 1 && rclip > 0) clip_event(R, P, rend, 1, rclip, pcr_inc);   // any index > 0 gives rpos_delta = -1
@@ -922,7 +931,7 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
                 const unsigned long long v = (unsigned long long)(long long)(sub == PN_N32 + PN_CL ? cL : cR);
                 diff_put_at(d64[sub - PN_N32], s - t0, e - t0, v);
             } else if (sub == 7 && h2.w != 0) {
-                const int lclip = h2.w & 0xFFFF, rclip = (h2.w >> 16) & 0xFFFF;
+                const int lclip = frec_clip_len(R, h2.w & 0xFFFF, h0.w, false), rclip = frec_clip_len(R, (h2.w >> 16) & 0xFFFF, h0.w, true);
                 const int pcr_inc = (((q4[1].x >> 24) & 0x4) ? 1 : 0);
                 if (lclip > 0 && apos >= t0) clip_event(R, P, apos, 0, lclip, pcr_inc);
                 if (rclip > 0 && rend <= t1) clip_event(R, P, rend, 1, rclip, pcr_inc);   // any index > 0 gives rpos_delta = -1
@@ -1799,43 +1808,8 @@ DEV void frag_counts(const RegionDev &R, const UvcParams &P, const FragRec &f, i
 // ------------------------------------------------------------------------------------------------
 // per fragment: counts of covered and near-mutation positions (b10xSeqTlen / b10xSeqTNevents, main.hpp:2738-2756)
 // ------------------------------------------------------------------------------------------------
-// sequential sweep over the fragment span (fragments with InDel reads, > 2 reads, primer gating, or > UVC_MAXEV events)
-DEV void fragstat_sweep(const RegionDev &R, const UvcParams &P, int fi) {
-    const FragRec f = R.frags[fi];
-    const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
-    const int nb = P.syserr_mut_region_n_bases;
-    int n_cov = 0, n_near = 0;
-    int last_mut = INT32_MIN / 2;
-    int tail[32]; int th = 0, tn = 0;   // covered positions within the last nb that are not (yet) near a mutation
-    int cnt[NSYM];
-    for (int p = f.beg; p < f.end; p++) {
-        frag_counts(R, P, f, p, proton, cnt);
-        bool covered = false, mut = false;
-        const int refsymbol = R.refsym[p - R.beg];
-        for (int vi = 0; vi < 2; vi++) {
-            const int st = (vi == 0 ? UVC_LINK_SYMBOL : UVC_BASE_SYMBOL);
-            int cs, cc, ct;
-            fill_consensus(cnt, cs, cc, ct, st, st == UVC_LINK_SYMBOL, false);
-            if (0 == ct) continue;
-            covered = true;
-            const int con_qual = cc * 2 - ct;
-            const bool highBQ = (proton ? (UVC_BASE_SYMBOL == st || con_qual + 3 >= P.bias_thres_highBQ) : (UVC_LINK_SYMBOL == st || con_qual >= P.bias_thres_highBQ));
-            if (symbols_mutated(refsymbol, cs) && highBQ) mut = true;
-        }
-        while (tn > 0 && tail[th] < p - nb) { th = (th + 1) & 31; tn--; }   // can no longer be reached by a later mutation
-        if (mut) { n_near += tn; tn = 0; last_mut = p; }
-        if (covered) {
-            n_cov++;
-            if (p - last_mut <= nb) n_near++;
-            else { tail[(th + tn) & 31] = p; tn++; }
-        }
-    }
-    R.frags[fi].n_cov = n_cov; R.frags[fi].n_near = n_near;
-    FragFast &ff = R.ffast[R.frag_rank[fi]]; ff.n_cov = n_cov; ff.n_near = n_near;   // k_frag reads the digest
-}
-
 // one wave per fragment: lanes classify positions (covered / mutated) into LDS, then count covered positions and those within
-// +-syserr_mut_region_n_bases of a mutation.  Spans beyond the LDS window fall back to the sequential sweep.
+// +-syserr_mut_region_n_bases of a mutation (fragments with InDel reads, > 2 reads, primer gating, or > UVC_MAXEV events).
 #define SWEEP_MAXSPAN 4096
 __global__ void __launch_bounds__(64) k_fragstat_sweep(RegionDev R, UvcParams P, const int32_t *list, const int32_t *n_dev, int n_host) {
     __shared__ uint8_t flag[SWEEP_MAXSPAN];
