@@ -75,10 +75,12 @@ def infer_max_qual(max_qual, dec_qual, distr, totDP):
     return maxv, argAD, argBQ
 
 
-def fragment_pass(reads, P, rtr, indelphred, baq, codes, prep, thres, seg, bqsum, proton, alleles=None):
+def fragment_pass(reads, P, rtr, indelphred, baq, codes, prep, thres, seg, bqsum, proton, alleles=None, haps=None):
     """-> (frag int64 [2][3][NSYM][npos] (bDP, bTA, bTB), vq {bMQ, bIAQb, bIADb, bIDQb: int64 [NSYM][npos]}).
     alleles (optional dict): gains "bq" = per strand {(symbol, position): {inserted text | deleted length: fragments}}, the allele-keyed maps of
-    symbol_to_frag_format_depth_sets (posToIndelToCount_updateByConsensus, main.hpp:2710-2717)."""
+    symbol_to_frag_format_depth_sets (posToIndelToCount_updateByConsensus, main.hpp:2710-2717).
+    haps (optional list): gains per fragment (strand, [(epos, con_symbol, con_qual, is_var_of_highBQ)]) of the mutated consensus symbols in the
+    order of the walk; those with is_var_of_highBQ (main.hpp:2720-2723) make pos_symbol_string (tests/hap_restatement.py::fragment_lists)."""
     beg = int(reads["beg"])
     npos = int(reads["end"]) - beg + 1
     frag = np.zeros((2, 3, NSYM, npos), dtype=np.int64)
@@ -116,6 +118,7 @@ def fragment_pass(reads, P, rtr, indelphred, baq, codes, prep, thres, seg, bqsum
                 cnt[p - beg2][s] = max(cnt[p - beg2][s], v)       # incSymbolCount<BASE_QUALITY_MAX>
         cov = [0] * tlen
         base_sym = [END] * tlen; link_sym = [END] * tlen
+        pos_symbol = []
         for e in range(tlen):
             epos = beg2 + e; x = epos - beg
             for st in (1, 0):                                    # SYMBOL_TYPES_IN_VCF_ORDER: LINK, BASE
@@ -142,10 +145,14 @@ def fragment_pass(reads, P, rtr, indelphred, baq, codes, prep, thres, seg, bqsum
                     dst[key] = dst.get(key, 0) + 1
                 cov[e] |= 1
                 high = ((st == 0 or con_qual + 3 >= highBQ) if proton else (st == 1 or con_qual >= highBQ))
-                if symbols_mutated(refsymbol, con) and high:
-                    cov[e] |= 2
+                if symbols_mutated(refsymbol, con):
+                    pos_symbol.append((epos, int(con), int(con_qual), bool(high)))
+                    if high:
+                        cov[e] |= 2
                 if st == 1: link_sym[e] = con
                 else: base_sym[e] = con
+        if haps is not None:
+            haps.append((strand, pos_symbol))
         for e in range(tlen):
             if cov[e] & 2:
                 for q in range(e - nb, e + nb + 1):

@@ -15,7 +15,7 @@ import numpy as np
 
 from p2_restatement import read_events
 from p3_restatement import (BASE_A, BASE_N, BASE_NN, BASE_T, LINK_M, LINK_NN, NSYM, NUM_BUCKETS, fill_consensus, infer_max_qual, is_del, is_ins,
-                            sscs_phred)
+                            sscs_phred, symbols_mutated)
 from segbias_restatement import non_neg_minus, update_bidirectional_bias
 
 MAX_STR_N_BASES = 100
@@ -110,8 +110,11 @@ def families(reads):
     return out
 
 
-def family_passes(reads, P, rtr, ip, baq, baq2, codes, prep, thres, proton, alleles=None):
-    """-> (fam int64 [2][8][NSYM][npos], fi32 {name: [NSYM][npos]}, fi64 {...}, duplex [2][NSYM][npos], vq {cIAQf cIADf cIDQf cIAQr cIADr cIDQr})."""
+def family_passes(reads, P, rtr, ip, baq, baq2, codes, prep, thres, proton, alleles=None, haps=None):
+    """-> (fam int64 [2][8][NSYM][npos], fi32 {name: [NSYM][npos]}, fi64 {...}, duplex [2][NSYM][npos], vq {cIAQf cIADf cIDQf cIAQr cIADr cIDQr}).
+    haps (optional list): gains per family-strand unit (strand, [(epos, con_symbol, confam_qual, avgBQ, is_var_of_highBQ, in_f2q)]) of the mutated
+    consensus symbols in the order of the walk; is_var_of_highBQ is main.hpp:3492-3494 and makes pos_symbol_string, in_f2q adds the condition of
+    main.hpp:3497-3502 for pos_symbol_string_confam (tests/hap_restatement.py::family_lists)."""
     beg = int(reads["beg"]); npos = int(reads["end"]) - beg + 1
     famp = np.zeros((2, len(FAM), NSYM, npos), dtype=np.int64)
     fi = {k: np.zeros((NSYM, npos), dtype=np.int64) for k in FI32 + FI64}
@@ -278,6 +281,7 @@ def family_passes(reads, P, rtr, ip, baq, baq2, codes, prep, thres, proton, alle
                     update_by_mmm(mmm, fc)
                 if dscs:
                     update_by_filtering(duplex, con, (1, 1), padded_ignored, False)
+                unit_symbols = []
                 for epos in range(beg2, end2):
                     x = epos - beg
                     for st in (1, 0):
@@ -302,11 +306,19 @@ def family_passes(reads, P, rtr, ip, baq, baq2, codes, prep, thres, proton, alle
                         else:
                             confam = max(1, min(indep, int(con_sum) * 2 - int(tot_sum)))
                         ref_symbol = int(codes_p[x])
+                        if haps is not None:                   # main.hpp:3491-3505
+                            high = ((st == 0 or max(confam + 3, avgBQ) >= int(P.bias_thres_highBQ)) if proton else (st == 1 or confam >= int(P.bias_thres_highBQ)))
+                            if symbols_mutated(ref_symbol, cs):
+                                cs1, cc1, ct1 = fill_consensus(crow, LINK_M, LINK_NN, False) if st == 1 else fill_consensus(crow, BASE_A, BASE_NN, False)
+                                in_f2q = high and cs == cs1 and int(P.fam_thres_dup1add) <= ct1 and cc1 * 100 >= ct1 * int(P.fam_thres_dup1perc)
+                                unit_symbols.append((epos, int(cs), int(confam), int(avgBQ), bool(high), bool(in_f2q)))
                         max_qual = sscs_phred(P, ref_symbol, cs, is_rescued) + (4 if provided else 0)
                         confam2 = min(confam, max_qual)
                         if tot_nfrags >= int(P.fam_thres_dup1add):
                             pb = cdiv_(max_qual - confam2 + 2, 4)
                             bucket[strand][x][cs][pb] += 1
+                if haps is not None:
+                    haps.append((strand, unit_symbols))
             if dscs:
                 for epos in range(duplex.beg, duplex.end):
                     x = epos - beg

@@ -61,7 +61,7 @@ void uvc_hap_build(const int32_t *events, int64_t n_ints, int32_t beg, int64_t n
     for (int w = 0; w < 3; w++) {
         out[w].clear();
         std::vector<Slot> &v = rows[w];
-        const size_t num_dst = std::min((size_t)std::max(max_detail_cnt, 0), v.size());
+        const size_t num_dst = std::min((size_t)max_detail_cnt, v.size());   // the reference's cast (main.hpp:3613): a negative value makes every link detailed
         std::partial_sort(v.begin(), v.begin() + (std::ptrdiff_t)num_dst, v.end(), before);   // the detailed links are the first num_dst rows of the full order
         std::vector<int32_t> inc_fw(num_dst, 0), inc_rv(num_dst, 0);
         for (size_t i = 0; i < num_dst; i++) {   // support from the lists behind it that contain all of its mutations
