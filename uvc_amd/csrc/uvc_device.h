@@ -205,6 +205,8 @@ struct RegionDev {
     uint32_t *occ;                  // [npos] bit s: somebody wrote a cell of (s, position) outside the dense-symbol paths (occ_mark); zeroed with the planes, read by the scoring gate
     uint8_t *link_need, *link_done; // [nwin, padded to a multiple of 4] per 64-position window: somebody reads the bias counters of LINK_M there / the completion pass
                                     // (k_p2_fast<true, false>) has added them.  Zeroed with the marks above; see link_complete of uvc_host.cpp
+    int32_t *link_cnt, *link_list;  // the windows k_link_mark was the first to ask for since that fill, and their count: what the sparse form of the pass
+                                    // (k_p2_link_sparse) walks.  Behind link_done, zeroed with it (uvc_link.h)
     uint32_t *fam_digest;           // [n_generic_work][8]: what P4 leaves per (unit, position) for P5 and the duplex pass (k_fam_p4d / k_fam_p5d / k_duplex_d);
                                     // set_reads allocates it on deep data, and then the family passes take the digest form; NULL: the generic form
     Contrib *table;

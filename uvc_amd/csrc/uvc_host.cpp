@@ -90,8 +90,8 @@ struct uvcgpu_region {
     hipStream_t stream = nullptr;
     // the streams (the main one first) and the events of a handle: created and destroyed in one loop over these lists
     std::array<hipStream_t *, 3> streams() { return { { &stream, &side, &side3 } }; }
-    std::array<hipEvent_t *, 6> events() { return { { &e_fork, &e_join, &e_fork2, &e_join3, &e_stat, &e_alleles } }; }
-    hipStream_t side = nullptr, side3 = nullptr; hipEvent_t e_fork = nullptr, e_join = nullptr, e_fork2 = nullptr, e_join3 = nullptr, e_stat = nullptr, e_alleles = nullptr;   // fork/join inside accumulate (see uvc_launch_accumulate)
+    std::array<hipEvent_t *, 8> events() { return { { &e_fork, &e_join, &e_fork2, &e_join3, &e_stat, &e_alleles, &e_link_fork, &e_link_join } }; }
+    hipStream_t side = nullptr, side3 = nullptr; hipEvent_t e_fork = nullptr, e_join = nullptr, e_fork2 = nullptr, e_join3 = nullptr, e_stat = nullptr, e_alleles = nullptr, e_link_fork = nullptr, e_link_join = nullptr;   // fork/join inside accumulate (see uvc_launch_accumulate)
     // device buffers
     Buf<uint8_t> d_refsym{this}; Buf<int32_t> d_rtr{this}, d_rtr0{this}, d_fsum{this}, d_win{this}; Buf<int64_t> d_baq{this};
     Buf<char> d_state{this}; SlabLayout L = {};   // the plane slab and its layout for npos (uvc_planes.h)
@@ -154,10 +154,11 @@ static void link_report(const uvcgpu_region *r, const char *scope) {
 // The bias counters of LINK_M (its SEG32 / SEG64 cells beyond aDP**, its VQ a1BQ* / a2BQ* cells) are made where somebody reads them: an
 // accumulate leaves them complete in the 64-position windows with an InDel mark, which is all the default gate reads.  Every other reader
 // of those cells calls this first, behind planes_guard: it enqueues the completion pass for the windows of `scope` on the handle's stream,
-// once per window and accumulate.  d_xs: n_xs plane indices on the device (UVC_LINK_POSITIONS).  Nothing is read back.
-static int link_complete(uvcgpu_region *r, int scope, const int32_t *d_xs = nullptr, int64_t n_xs = 0) {
+// once per window and accumulate.  d_xs: n_xs positions on the device (UVC_LINK_POSITIONS), read in place: xs_stride int32 words apart, xs_off
+// above their plane index.  Nothing is read back.
+static int link_complete(uvcgpu_region *r, int scope, const int32_t *d_xs = nullptr, int64_t n_xs = 0, int xs_stride = 1, int xs_off = 0) {
     if (!r->link.wants(r->accumulated, r->state_released, scope)) return 0;
-    uvc_launch_link_complete(&r->R, &r->P, r->link_split, scope, d_xs, n_xs, nullptr, r->stream);
+    uvc_launch_link_complete(&r->R, &r->P, r->link_split, scope, d_xs, n_xs, xs_stride, xs_off, "k_p2_fast_link", nullptr, r->stream);
     if (hipGetLastError() != hipSuccess) return fail(UVCGPU_EDEVICE, "completion pass of LINK_M: launch failed");
     r->link.enqueued(scope);
     if (getenv("UVCGPU_TIMING")) link_report(r, scope == UVC_LINK_ALL ? "all" : "positions");
@@ -268,7 +269,7 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
         const size_t work_bytes = uvc_rtr_work_bytes(r->npos, vmax, smax, bqm, &scan_tmp);
         if (r->d_refsym.fit(n + 1) != hipSuccess || r->d_rtr.fit(n_rtr) != hipSuccess || r->d_rtr0.fit(n_rtr) != hipSuccess || r->d_fsum.fit(2 * UVC_FSUM_N * n) != hipSuccess
             || r->d_win.fit(16 * (size_t)((r->npos + 63) / 64)) != hipSuccess || r->d_baq.fit(2 * n) != hipSuccess || r->d_state.fit(r->L.total) != hipSuccess || r->d_rtrwork.fit(work_bytes) != hipSuccess
-            || r->d_dirty.fit(uvc_link_marks_bytes((size_t)3 * NSYM * (size_t)((r->npos >> UVC_DIRTY_SHIFT) + 2), (r->npos + 63) / 64)) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(region planes) failed");
+            || r->d_dirty.fit(uvc_link_buffer_bytes((size_t)3 * NSYM * (size_t)((r->npos >> UVC_DIRTY_SHIFT) + 2), (r->npos + 63) / 64)) != hipSuccess) return fail(UVCGPU_ENOMEM, "hipMalloc(region planes) failed");
         uvc_rtr_bind(&r->rw, r->d_rtrwork, r->npos, vmax, smax, bqm, scan_tmp);
         r->npos_cap = r->npos;
     }
@@ -297,6 +298,7 @@ static int configure_region(uvcgpu_region *r, int32_t tid, int32_t beg, int32_t 
     R.bucket = (int32_t *)(b + r->L.bucket_off); R.p5flag = (uint8_t *)(b + r->L.p5flag_off); R.occ = (uint32_t *)(b + r->L.occ_off);
     R.dirty = r->d_dirty; R.ndblk = (int32_t)((r->npos + ((int64_t)1 << UVC_DIRTY_SHIFT) - 1) >> UVC_DIRTY_SHIFT);
     R.link_need = r->d_dirty + uvc_link_marks_off(dirty_bytes(R)); R.link_done = R.link_need + uvc_link_marks_stride(R.nwin);   // behind the dirty marks: one fill zeroes both
+    R.link_cnt = (int32_t *)(r->d_dirty + uvc_link_list_cnt_off(dirty_bytes(R), R.nwin)); R.link_list = (int32_t *)(r->d_dirty + uvc_link_list_off(dirty_bytes(R), R.nwin));   // (the same fill)
     r->link.planes_zeroed();
     R.err = r->d_err;
     HIP_OK(hipMemsetAsync(R.err, 0, 4, r->stream));
@@ -620,7 +622,7 @@ static int zero_state(uvcgpu_region *r, hipStream_t s) {
     } else {
         HIP_OK(hipMemsetAsync(r->d_state, 0, r->buckets_clean ? r->L.bucket_off : r->L.total, s));
     }
-    HIP_OK(hipMemsetAsync(r->d_dirty, 0, uvc_link_marks_bytes(dirty_bytes(r->R), r->R.nwin), s));   // the marks and link_need / link_done behind them
+    HIP_OK(hipMemsetAsync(r->d_dirty, 0, uvc_link_buffer_bytes(dirty_bytes(r->R), r->R.nwin), s));   // the marks and link_need / link_done / link_cnt / link_list behind them
     r->link.planes_zeroed();
     return 0;
 }
@@ -642,7 +644,7 @@ static int uvcgpu_region_accumulate_impl(uvcgpu_region_t *r) {
         // rows were set to 0xFF in set_reads and k_p2_slow<false> is idempotent under MAX, so no reset is needed
     }
     const int half = (int)std::round((10.0 / std::log(10.0)) * std::log(r->P.indel_del_to_ins_err_ratio)) / 2;   // main.hpp:1244
-    const UvcAccStreams st = { r->stream, r->side, r->side3, r->e_fork, r->e_join, r->e_fork2, r->e_join3, r->e_stat, r->e_alleles };
+    const UvcAccStreams st = { r->stream, r->side, r->side3, r->e_fork, r->e_join, r->e_fork2, r->e_join3, r->e_stat, r->e_alleles, r->e_link_fork, r->e_link_join };
     // UVCGPU_LINK=eager (read on every accumulate, like UVCGPU_SPLIT): every window of LINK_M completed inside the accumulate, for comparison
     const char *lk_env = getenv("UVCGPU_LINK");
     const bool link_eager = (lk_env && !strcmp(lk_env, "eager")) || !uvc_acc_p2_plain(&r->R, &r->P);   // (the generic P2 forms make all of LINK_M in their LINK pass, as before 6-r8)
@@ -1082,9 +1084,6 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
         if (rq.pos_beg < r->beg + (rq.base_at_pos_beg ? 1 : 0) || rq.pos_end > r->end - 1 || rq.pos_end < rq.pos_beg) return fail(UVCGPU_EINVAL, "score range outside the region");
         npos_scored = (int64_t)rq.pos_end - rq.pos_beg;
     }
-    // The default gate opens a LINK group only at a position with an InDel mark (gate_count: one symbol in the mask and min_altdp_thres > 0
-    // give no record), and the accumulate has completed LINK_M in those windows.  Every other gate can open one anywhere.
-    { const int rcl = link_complete(r, uvc_link_score_scope(rq.all_out, r->P.should_output_all, r->P.tumor_vcf_is_provided, rq.n_force_sites, r->P.min_altdp_thres)); if (rcl) return rcl; }
     // InDel alleles: the region's own tables (fill_by_indel_info / indel_get_majority); a (refpos, symbol) the caller lists is overridden
     { int rc0 = gap_tables(r); if (rc0) return rc0; }
     UvcIndelAllele *d_al = nullptr; int32_t *d_al_row = nullptr; UvcTumorKey *d_tk = nullptr; int32_t *d_fs = nullptr; UvcScoreRangeDev *d_rg = nullptr;
@@ -1130,6 +1129,17 @@ static int score_prepare(uvcgpu_region_t *r, const UvcScoreRequest *req, const U
     if (!rtab.empty()) {   // the ranges, through the staging buffer like the keys and the sites (k_range_map makes the position table)
         if (!p.tmp->get(&d_rg, rtab.size())) return no_room();
         { int rc1 = stage_upload(r, d_rg, rtab.data(), sizeof(UvcScoreRangeDev) * rtab.size(), stage_at, stage_total); if (rc1) return rc1; }
+    }
+    // The default gate opens a LINK group only at a position with an InDel mark (gate_count: one symbol in the mask and min_altdp_thres > 0
+    // give no record), and the accumulate has completed LINK_M in those windows.  A normal sample's gate opens one only at a keyed refpos, forced
+    // sites only at the sites: the mark kernel reads the uploaded keys and sites in place.  Every other gate can open one anywhere.
+    {
+        static_assert(sizeof(UvcTumorKey) % sizeof(int32_t) == 0 && offsetof(UvcTumorKey, refpos) == 0, "k_link_mark strides over UvcTumorKey::refpos");
+        const int scope = uvc_link_score_scope_at(rq.all_out, r->P.should_output_all, r->P.tumor_vcf_is_provided, d_tk ? rq.n_tumor_keys : 0, rq.n_force_sites, r->P.min_altdp_thres);
+        const int rcl = (scope != UVC_LINK_POSITIONS) ? link_complete(r, scope)
+                      : d_tk ? link_complete(r, scope, &d_tk->refpos, rq.n_tumor_keys, (int)(sizeof(UvcTumorKey) / sizeof(int32_t)), r->beg)
+                             : link_complete(r, scope, d_fs, rq.n_force_sites, 1, r->beg);
+        if (rcl) return rcl;
     }
     p.in = UvcScoreIn{ &r->R, &r->P, &rq, use_al, use_row, n_al, r->d_gap_rows, r->d_gap_seq, d_tk, nullptr, d_fs, d_rg, (int64_t)rtab.size(), npos_scored };
     return 0;

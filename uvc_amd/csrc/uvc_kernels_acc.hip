@@ -1221,14 +1221,18 @@ DEV void mis_apply(const RegionDev &R, const UvcParams &P, const MisItem &it) {
 #define P2_RED_SLOTS (P2_RED_LINK5 + 5)
 // the 64-bit counter f of the LDS reduction area: two int rows of 64 = one row of 64 unsigned long long
 DEV unsigned long long *red64(int (*red)[64], int f) { return (unsigned long long *)&red[UVC_NSEG32 + 2 * f][0]; }
-template <bool DO_L, bool DO_B, bool PLAIN, bool SPLIT = false>
-DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *amp2, MisItem (*misq)[DO_B ? MISQ_CAP : 1], int (*red)[64] = nullptr) {
+// NSL > 0 (with SPLIT, for the plain completion pass only): the sparse form, k_p2_link_sparse.  The block serves window `win` with 4 * NSL
+// waves; wave w walks slice w >> 2 (uvc_link_slice) of class list w & 3, and the LDS reduction of the split form adds the 4 * NSL partial sets up.
+template <bool DO_L, bool DO_B, bool PLAIN, bool SPLIT = false, int NSL = 0>
+DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *amp2, MisItem (*misq)[DO_B ? MISQ_CAP : 1], int (*red)[64] = nullptr, int win = 0) {
+    static_assert(NSL == 0 || (SPLIT && DO_L && !DO_B && PLAIN), "the sparse form exists for the plain completion pass");
+    constexpr int NWV = (NSL ? 4 * NSL : 4);   // waves of a block
     COARSE_T(ct0)
-    if (DO_L) {   // the completion pass runs a window only where a reader asked for it and no earlier pass has been (block-uniform; the waves look again below)
+    if (DO_L && !NSL) {   // the completion pass runs a window only where a reader asked for it and no earlier pass has been (block-uniform; the waves look again below)
         if (SPLIT) { const int w = xcd_block(); if (!uvc_link_window_runs(R.link_need[w], R.link_done[w])) return; }
         else { const int b = xcd_block(); if (!(((const uint32_t *)R.link_need)[b] & ~((const uint32_t *)R.link_done)[b] & 0x01010101u)) return; }
     }
-    {
+    if (!NSL) {   // (the sparse form's kernel fills the tables once for all its windows)
         for (int v = (int)threadIdx.x - AMP_LO; v < 256; v += 256) {   // (a threshold of 0 would divide by zero for a value below it, as the reference does: uvcgpu_params_check refuses a negative addend beside such a threshold, so that entry is never read)
             const int d1 = P.bias_thres_PFBQ1 * P.bias_thres_PFBQ1, d2 = P.bias_thres_PFBQ2 * P.bias_thres_PFBQ2;
             amp1[v + AMP_LO] = ((v < P.bias_thres_PFBQ1 && d1) ? 100 * (v * v) / d1 : 100);
@@ -1237,11 +1241,11 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     }
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int wave = SPLIT ? wave_uniform((int)xcd_block()) : wave_uniform((int)((xcd_block() * blockDim.x + threadIdx.x) >> 6));
+    const int wave = NSL ? wave_uniform(win) : SPLIT ? wave_uniform((int)xcd_block()) : wave_uniform((int)((xcd_block() * blockDim.x + threadIdx.x) >> 6));
     const int64_t x0 = (int64_t)wave * 64;
     if (x0 >= R.npos) return;   // (block-uniform in the split form)
     if (DO_L && !SPLIT && !uvc_link_window_runs(R.link_need[wave], R.link_done[wave])) return;
-    if (SPLIT) { for (int i2 = threadIdx.x; i2 < P2_RED_SLOTS * 64; i2 += 256) (&red[0][0])[i2] = 0; __syncthreads(); }
+    if (SPLIT) { for (int i2 = threadIdx.x; i2 < P2_RED_SLOTS * 64; i2 += 64 * NWV) (&red[0][0])[i2] = 0; __syncthreads(); }
     const int w0 = R.beg + (int)x0;
     const int p = w0 + lane;
     const int64_t x = x0 + lane;
@@ -1278,11 +1282,13 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     // the work list is stored as four pos-sorted sub-lists, one per (is-reverse, bam_get_strand) class
     auto run_list = [&](auto IS, auto ST, int cls) {
     constexpr bool ISRC = decltype(IS)::value, STRAND = decltype(ST)::value;
-    const int lo = wave_uniform(win_lo(R, 1 + cls, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 1 + cls, (int)(x0 >> 6)));
+    int lo = wave_uniform(win_lo(R, 1 + cls, (int)(x0 >> 6))), hi = wave_uniform(win_hi(R, 1 + cls, (int)(x0 >> 6)));
+    if (NSL) { int slo, shi; uvc_link_slice(lo, hi, (int)(threadIdx.x >> 8), NSL, &slo, &shi); lo = wave_uniform(slo); hi = wave_uniform(shi); }   // this wave's part of the class
     // The base pass also counts the five cells of LINK_M that the fragment kernels read at every position (maxq_at): the aDP** counter of this
     // list's class and BQSUM, from the cover / hasL / incL expressions of the LINK pass.  The other 34 cells of LINK_M wait for a reader.
     int l5_dp = 0;
-    for (int k0 = lo + (SPLIT ? 64 * (int)(threadIdx.x >> 6) : 0); k0 < hi; k0 += (SPLIT ? 256 : 64)) {
+    constexpr bool DEAL = SPLIT && !NSL;   // the split form deals a window's chunks of 64 records to its four waves
+    for (int k0 = lo + (DEAL ? 64 * (int)(threadIdx.x >> 6) : 0); k0 < hi; k0 += (DEAL ? 256 : 64)) {
         int c[16];
         if (DO_B) load_words(R.frec2 + (k0 + lane), k0 + lane < hi, c);   // (the LINK-only pass reads its records through the scalar cache, below)
         const int n = imin(64, hi - k0);
@@ -1400,10 +1406,19 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     }
     };
     COARSE_T(ct1)
+    if (NSL) {   // one class per wave: ISRC and STRAND stay compile-time behind a wave-uniform switch
+        switch (wave_uniform((int)(threadIdx.x >> 6) & 3)) {
+        case 0: run_list(std::false_type{}, std::false_type{}, 0); break;
+        case 1: run_list(std::true_type{}, std::false_type{}, 1); break;
+        case 2: run_list(std::false_type{}, std::true_type{}, 2); break;
+        default: run_list(std::true_type{}, std::true_type{}, 3); break;
+        }
+    } else {
     run_list(std::false_type{}, std::false_type{}, 0);
     run_list(std::true_type{}, std::false_type{}, 1);
     run_list(std::false_type{}, std::true_type{}, 2);
     run_list(std::true_type{}, std::true_type{}, 3);
+    }
     if (DO_B && nq > 0) flush_queue();
     COARSE_T(ct2)
     if (SPLIT) {   // the four partial sets -> LDS -> one set (the two passes own different symbols: one symbol per kernel)
@@ -1419,13 +1434,13 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
         if ((DO_B || L5_LINK) && A.bq) atomicAdd(&red[UVC_NSEG32 + 2 * UVC_NSEG64 + 4][lane], A.bq);
         if (L5_BASE && l5_bq) atomicAdd(&red[P2_RED_LINK5 + 4][lane], l5_bq);
         __syncthreads();
-        if (DO_L && threadIdx.x == 0) R.link_done[xcd_block()] = 1;
+        if (DO_L && threadIdx.x == 0) R.link_done[wave] = 1;   // once per window, behind the block's barrier
         if (!valid) return;
         const int sym = (DO_B ? my_ref : UVC_LINK_M), wv = (int)(threadIdx.x >> 6);
         // the base pass is the first writer of its cells: plain stores.  The completion pass adds to what k_p2_items has put there (seg_add_link)
         auto put = [](auto &cell, auto v) { if (DO_L) cell += v; else cell = v; };
-        for (int f = wv; f < UVC_NSEG32; f += 4) { const int v = red[f][lane]; if (v) put(S32(R, f, sym, x), v); }
-        for (int f = wv; f < UVC_NSEG64; f += 4) { const long long v = (long long)red64(red, f)[lane]; if (v) put(S64(R, f, sym, x), v); }
+        for (int f = wv; f < UVC_NSEG32; f += NWV) { const int v = red[f][lane]; if (v) put(S32(R, f, sym, x), v); }
+        for (int f = wv; f < UVC_NSEG64; f += NWV) { const long long v = (long long)red64(red, f)[lane]; if (v) put(S64(R, f, sym, x), v); }
         if (wv == 0) {
             const int b0 = UVC_NSEG32 + 2 * UVC_NSEG64;
             if (red[b0][lane]) put(VQP(R, UVC_VQ_a1BQf, sym, x), red[b0][lane]);
@@ -1467,6 +1482,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     __shared__ MisItem misq[DO_B ? 4 : 1][DO_B ? MISQ_CAP : 1];
     __shared__ __attribute__((aligned(8))) int red[P2_RED_SLOTS][64];
     p2_fast_body<DO_L, DO_B, PLAIN, true>(R, P, amp1, amp2, misq, red);
+}
+// The sparse form of the plain completion pass: where few windows are needed the wave-per-window form is bound by the length of
+// one wave's walk over a window's four class lists, not by the number of windows.  Here a block of 4 * NSL waves shares one window, and the
+// blocks stride over the list that k_link_mark made (RegionDev::link_list, link_cnt); a listed window that an earlier launch has run is
+// skipped on its link_done byte.  A window is in the list once, so no two blocks meet; no block waits for another.
+template <int NSL>
+__global__ void __launch_bounds__(256 * NSL) k_p2_link_sparse(RegionDev R, UvcParams P) {
+    __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
+    __shared__ MisItem misq[1][1];
+    __shared__ __attribute__((aligned(8))) int red[P2_RED_SLOTS][64];
+    const int n = imin(*R.link_cnt, R.nwin);
+    if ((int)blockIdx.x >= n) return;
+    for (int v = (int)threadIdx.x - AMP_LO; v < 256; v += (int)blockDim.x) {   // as in p2_fast_body
+        const int d1 = P.bias_thres_PFBQ1 * P.bias_thres_PFBQ1, d2 = P.bias_thres_PFBQ2 * P.bias_thres_PFBQ2;
+        amp1[v + AMP_LO] = ((v < P.bias_thres_PFBQ1 && d1) ? 100 * (v * v) / d1 : 100);
+        amp2[v + AMP_LO] = ((v < P.bias_thres_PFBQ2 && d2) ? 100 * (v * v) / d2 : 100);
+    }
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const int w = wave_uniform(R.link_list[i]);
+        if ((unsigned)w < (unsigned)R.nwin && uvc_link_window_runs(R.link_need[w], R.link_done[w])) p2_fast_body<true, false, true, true, NSL>(R, P, amp1, amp2, misq, red, w);
+        __syncthreads();   // the next window zeroes the reduction area
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3897,17 +3934,45 @@ static void launch_p2_fast(const char *kname, bool split, bool plain, const Regi
 //   UVC_LINK_POSITIONS  windows of the n_xs plane indices d_xs (out-of-range entries are skipped)
 //   UVC_LINK_ALL        every window
 // The pass adds to cells that k_p2_items may have added to, in either order; a window is run once.
-__global__ void __launch_bounds__(256) k_link_mark(RegionDev R, const int32_t *xs, int64_t n_xs) {
+// The position list is read in place: entry t is xs[t * xs_stride] - xs_off (the int32 sites of a request, or UvcTumorKey::refpos, a row apart).
+// Whoever is the first to set a window's need byte (an atomic OR on its word) also lists the window for the sparse form of the pass, unless
+// the pass has been there: a window is listed at most once between two fills of the marks, so link_list holds at most nwin entries.
+__global__ void __launch_bounds__(256) k_link_mark(RegionDev R, const int32_t *xs, int64_t n_xs, int xs_stride, int xs_off) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (xs) { if (t < n_xs) { const int x = xs[t]; if (x >= 0 && x < R.npos) R.link_need[x >> 6] = 1; } }
-    else if (t < R.npos && uvc_link_occ_marks(R.occ[t])) R.link_need[t >> 6] = 1;
+    int w = -1;
+    if (xs) { if (t < n_xs) { const int64_t x = (int64_t)xs[t * xs_stride] - xs_off; if (x >= 0 && x < R.npos) w = (int)(x >> 6); } }
+    else {   // the 64 positions of a wave are one window: one lane speaks for it
+        const bool m = (t < R.npos && uvc_link_occ_marks(R.occ[t]));
+        if (BAL(m) && (threadIdx.x & 63) == 0) w = (int)(t >> 6);
+    }
+    if (w < 0 || R.link_need[w]) return;
+    const unsigned byte = 0xFFu << (8 * (w & 3));
+    const unsigned old = atomicOr((unsigned *)R.link_need + (w >> 2), 0x01010101u & byte);
+    if (!(old & byte) && !R.link_done[w]) { const int i = atomicAdd(R.link_cnt, 1); if (i < R.nwin) R.link_list[i] = w; }
 }
-extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split, int scope, const int32_t *d_xs, int64_t n_xs, UvcProf *prof, hipStream_t s) {
+// UVCGPU_LINK_FORM=wave|sparse (read on every call, like UVCGPU_SPLIT) forces the form of an INDEL or POSITIONS pass of the plain forms; tests
+// and A/B runs compare the two.  UVC_LINK_ALL, UVCGPU_LINK=eager and the generic forms are throughput-bound and keep the wave / split forms.
+static bool link_form_sparse(const RegionDev *R, const UvcParams *P, int scope, int64_t n_xs) {
+    if (scope == UVC_LINK_ALL || !p2_plain_form(R, P)) return false;
+    const char *e = getenv("UVCGPU_LINK_FORM");
+    if (e && !strcmp(e, "wave")) return false;
+    if (e && !strcmp(e, "sparse")) return true;
+    return !(scope == UVC_LINK_POSITIONS && uvc_link_positions_dense(n_xs, R->nwin));
+}
+#ifndef UVC_LINK_SPARSE_NSL
+#define UVC_LINK_SPARSE_NSL 4   // slices per class list: 4 * 4 = 16 waves per window
+#endif
+extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split, int scope, const int32_t *d_xs, int64_t n_xs, int xs_stride, int xs_off,
+                                         const char *kname, UvcProf *prof, hipStream_t s) {
     if (!P->inferred_is_vcf_generated) { hipMemsetAsync(R->link_done, 1, (size_t)R->nwin, s); return; }   // no P2 on a FASTQ-only run: the planes are complete as they are
     if (scope == UVC_LINK_ALL) hipMemsetAsync(R->link_need, 1, (size_t)R->nwin, s);
-    else if (scope == UVC_LINK_POSITIONS) { if (n_xs <= 0) return; hipLaunchKernelGGL(k_link_mark, dim3(nblk(n_xs, 256)), dim3(256), 0, s, *R, d_xs, n_xs); }
-    else hipLaunchKernelGGL(k_link_mark, dim3(nblk(R->npos, 256)), dim3(256), 0, s, *R, (const int32_t *)nullptr, (int64_t)0);
-    launch_p2_fast<true, false>("k_p2_fast_link", split != 0, p2_plain_form(R, P), R, P, prof, s);
+    else if (scope == UVC_LINK_POSITIONS) { if (n_xs <= 0) return; hipLaunchKernelGGL(k_link_mark, dim3(nblk(n_xs, 256)), dim3(256), 0, s, *R, d_xs, n_xs, xs_stride, xs_off); }
+    else hipLaunchKernelGGL(k_link_mark, dim3(nblk(R->npos, 256)), dim3(256), 0, s, *R, (const int32_t *)nullptr, (int64_t)0, 1, 0);
+    const bool sparse = link_form_sparse(R, P, scope, n_xs);
+    if (getenv("UVCGPU_TIMING")) fprintf(stderr, "[uvcgpu link_form] scope=%s form=%s\n", scope == UVC_LINK_ALL ? "all" : scope == UVC_LINK_POSITIONS ? "positions" : "indel", sparse ? "sparse" : split ? "split" : "wave");
+    // the sparse form: a fixed grid that strides over the list; the blocks beyond the device-side count leave at once
+    if (sparse) TIMED(prof, kname, hipLaunchKernelGGL(k_p2_link_sparse<UVC_LINK_SPARSE_NSL>, dim3(imin_h(R->nwin, 1024)), dim3(256 * UVC_LINK_SPARSE_NSL), 0, s, *R, *P));
+    else launch_p2_fast<true, false>(kname, split != 0, p2_plain_form(R, P), R, P, prof, s);
 }
 
 // The launches of one accumulate and what orders them (the same table: DESIGN 6-r7).  "reads": what another kernel of the accumulate writes;
@@ -3937,21 +4002,31 @@ extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P,
 // 16  k_gap_keys .. k_gap_rows_fin    S2  gap events (7 [e_join3])                                  InDel allele tables; fam2_ins_len complete at [e_alleles]
 // 17  k_fam_stat                      S3  table (7), ffast_u (8)                                    unit records (fss) -> [e_stat]
 // 18  k_p2_items                      M   items (6 [e_join]), THRES (5); atomics behind the stores of 13   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
+//     -- fork [e_link_fork]: S3, behind 17 and its e_stat record, waits for M behind 18 (behind the join when there are no InDel reads) --
+// 18a k_link_mark, LINK_M early       S3  occ (6 [e_join, e_link_fork]; marks of 19-21 as far as they exist)   link_need, link_list / link_cnt
+// 18b k_p2_link_sparse, LINK_M early  S3  link_list (18a), THRES, RTR.indelphred (5), index 1-4 (1)  the other 34 cells of LINK_M in the listed windows, added to what 18 left there;
+//                                                                                                   link_done -> [e_link_join]
 // 19  k_frag_generic                  M   SEG32 aDP*, BQSUM (13, 14 [e_join], 18), table (7 [e_join3]), ffast, n_cov / n_near (8, 10, 11 [e_join3])
 //                                                                                                   FRAG, FAM, VQ bMQ (atomics), global buckets
 // 20  k_frag16 / k_frag               M   SEG32 aDP*, BQSUM (as 19), fsum (12 [e_join3]), ffast, index 5-6, global buckets (19)   FRAG, FAM, VQ b*, buckets
 // 21  k_fam_p4* / k_fam_p5* / k_duplex*  M  unit records (17 [e_stat]), fam2_ins_len (16 [e_alleles]), table, ffast_u, index 7 (1)   FAM, family info planes, buckets
 // 22  k_p5b                           M   buckets, p5flag (20, 21)                                  VQ, buckets cleared
-//     -- M behind 16 [e_fork2, recorded again on S2: gap_tables, the MSI call and set_reads wait for this last record] --
-// 23  k_link_mark, k_p2_fast LINK_M   M   occ (6, 18-21), THRES, RTR.indelphred (5), index 1-4 (1)  link_need; the other 34 cells of LINK_M in the marked windows, added to what 18 left
+//     -- M behind 16 [e_fork2, recorded again on S2: gap_tables, the MSI call and set_reads wait for this last record] and behind 18b [e_link_join] --
+// 23  k_link_mark, LINK_M final       M   occ (6, 18-21), link_need / link_done (18a, 18b)          link_need, link_list of the windows whose mark appeared after 18a
+//     k_p2_link_sparse / k_p2_fast    M   link_list (18a, 23), THRES, RTR.indelphred (5), index 1-4 (1)   the other 34 cells of LINK_M in those windows, added to what 18 left
 //                                                                                                   there (load, add, store: no other writer of these cells runs); link_done
 // Rows 19 and 20 read, per position, the aDP* and BQSUM sums that row 18 adds to: k_p2_items cannot run beside the fragment kernels.
 // Row 3 cannot be forked in front of rows 1 and 2: a store of row 2 would overwrite what row 3 has added.
+// Rows 18a / 18b may run beside rows 19 to 22: they write the 34 cells of LINK_M beyond aDP** / BQSUM, link_need, link_done and the list, none of
+// which 19 to 22 read (19 and 20 read the five cells of row 13), and 19 to 22 write none of the 34 cells.  occ is read while 19 to 21 may still add
+// marks to it: a mark 18a misses is found by row 23, a window either of them lists is run once (link_done).  Without side streams 18a / 18b run
+// in launch order behind 18.
 // Row 23 runs again, for more windows, in front of any later call that reads the bias counters of LINK_M elsewhere (link_complete, uvc_host.cpp).
 extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
                                       const UvcAccStreams *st, int link_eager, UvcProf *prof) {
     const hipStream_t s = st->s, side = st->side, side3 = st->side3;
     const hipEvent_t e_fork = st->e_fork, e_join = st->e_join, e_fork2 = st->e_fork2, e_join3 = st->e_join3, e_stat = st->e_stat, e_alleles = st->e_alleles;
+    const hipEvent_t e_link_fork = st->e_link_fork, e_link_join = st->e_link_join;
     const unsigned nwin = nblk(R->npos, 256);   // 4 waves x 64 positions per block
     const AccForms F = acc_forms(R, P, n_dup);
     if (getenv("UVCGPU_TIMING")) { print_forms(F); fprintf(stderr, "[uvcgpu accumulate] link %s\n", link_eager ? "eager" : "lazy"); }
@@ -4001,7 +4076,7 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
         if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s2, e_fork2, 0); }
         TIMED2(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
     }
-    if (link_eager) uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_ALL, nullptr, 0, prof, s);   // UVCGPU_LINK=eager and the generic forms: where the LINK pass ran before 6-r8
+    if (link_eager) uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_ALL, nullptr, 0, 1, 0, "k_p2_fast_link", prof, s);   // UVCGPU_LINK=eager and the generic forms: where the LINK pass ran before 6-r8
     if (side) {
         hipEventRecord(e_join, s2); hipStreamWaitEvent(s, e_join, 0);
         if (s3 != s2) { hipEventRecord(e_join3, s3); hipStreamWaitEvent(s, e_join3, 0); hipStreamWaitEvent(s2, e_join3, 0); }   // (the allele tables below read the gap events of the table walk)
@@ -4029,6 +4104,18 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     if (R->n_generic_fs) TIMED3(prof, "k_fam_stat", hipLaunchKernelGGL(k_fam_stat, dim3(nblk(R->n_generic_fs, 64)), dim3(64), 0, s, *R, *P));
     if (side) { hipEventRecord(e_stat, s3); hipEventRecord(e_fork2, s2); }
     if (P->inferred_is_vcf_generated && R->n_complex) TIMED(prof, "k_p2_items", hipLaunchKernelGGL(k_p2_items, dim3(R->n_complex), dim3(64), 0, s, *R, *P));
+    // The completion pass of LINK_M, early phase (row 18a): the InDel marks of the CIGAR walk exist, and no kernel below writes the 34 cells or
+    // reads them, so the pass runs on s3 underneath the fragment kernels.  Marks that appear later (rows 19-21) are left to the final phase.
+    if (!link_eager) {
+        if (side) { hipEventRecord(e_link_fork, s); hipStreamWaitEvent(s3, e_link_fork, 0); }
+        uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_INDEL, nullptr, 0, 1, 0, "k_p2_link_early", prof, s3);
+        if (side) hipEventRecord(e_link_join, s3);
+        if (getenv("UVCGPU_TIMING")) {   // (diagnosis, like link_report of uvc_host.cpp: it waits, so a UVCGPU_TIMING run is no timing of the step)
+            int n_early = 0;
+            if (hipStreamSynchronize(s3) == hipSuccess && hipMemcpy(&n_early, R->link_cnt, sizeof(n_early), hipMemcpyDeviceToHost) == hipSuccess)
+                fprintf(stderr, "[uvcgpu link_early] %d windows listed for the early phase, the rest of the total below for the final one\n", n_early);
+        }
+    }
     {
         if (F.n_gen) TIMED(prof, "k_frag_generic", hipLaunchKernelGGL(k_frag_generic, dim3(imin_h(F.n_gen, 1 << 20), imin_h((R->max_frag_span + 63) / 64, 16)), dim3(64), 0, s, *R, *P, F.proton ? (const int32_t *)nullptr : R->sweep_frags, F.n_gen));
     }
@@ -4059,7 +4146,11 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     if (P->inferred_is_vcf_generated) TIMED(prof, "k_p5b", hipLaunchKernelGGL(k_p5b, dim3(nblk(R->npos * 2, 256)), dim3(256), 0, s, *R, *P));
     if (side) hipStreamWaitEvent(s, e_fork2, 0);   // the allele tables
     // every InDel mark of the accumulate exists here (rows 6, 18-21): the windows the default gate can open a LINK group in
-    if (!link_eager) uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_INDEL, nullptr, 0, prof, s);
+    // (final phase, row 23: behind the early one, for the windows whose mark appeared after the fork)
+    if (!link_eager) {
+        if (side) hipStreamWaitEvent(s, e_link_join, 0);
+        uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_INDEL, nullptr, 0, 1, 0, "k_p2_fast_link", prof, s);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -69,7 +69,7 @@ struct UvcScoreIn {
 };
 // The streams and events of one accumulate (host-side aggregate): the handle's stream, the two side streams (NULL: everything on `s`) and
 // the events of the forks and joins between them (see uvc_launch_accumulate).
-struct UvcAccStreams { hipStream_t s, side, side3; hipEvent_t e_fork, e_join, e_fork2, e_join3, e_stat, e_alleles; };
+struct UvcAccStreams { hipStream_t s, side, side3; hipEvent_t e_fork, e_join, e_fork2, e_join3, e_stat, e_alleles, e_link_fork, e_link_join; };
 // elements of one tile of the reports' tile scan = threads of a block (uvc_launch_tile_sums)
 #define UVC_SCAN_TILE 256
 static inline int64_t uvc_scan_tiles(int64_t n) { return (n + UVC_SCAN_TILE - 1) / UVC_SCAN_TILE; }
@@ -85,10 +85,13 @@ void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d_n_bad, hip
 // link_eager: the completion pass of LINK_M over every window inside the accumulate (UVCGPU_LINK=eager), else over the windows with an InDel mark at its end
 void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, int half_ratio_phred, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
                            const UvcAccStreams *st, int link_eager, UvcProf *prof);
-// the completion pass of LINK_M for a scope of windows (uvc_link.h); split: what uvc_acc_split_windows said at the accumulate
+// the completion pass of LINK_M for a scope of windows (uvc_link.h); split: what uvc_acc_split_windows said at the accumulate.  d_xs (POSITIONS):
+// entry t is d_xs[t * xs_stride] - xs_off.  An INDEL or POSITIONS pass of the plain forms takes the sparse form (UVCGPU_LINK_FORM forces);
+// kname: its name in the profile
 int uvc_acc_split_windows(const RegionDev *R);
 int uvc_acc_p2_plain(const RegionDev *R, const UvcParams *P);   // the plain P2 forms: only their base pass carries the five cells of LINK_M, so only they can be lazy
-void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split, int scope, const int32_t *d_xs, int64_t n_xs, UvcProf *prof, hipStream_t s);
+void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split, int scope, const int32_t *d_xs, int64_t n_xs, int xs_stride, int xs_off,
+                              const char *kname, UvcProf *prof, hipStream_t s);
 void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
 void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
 // ---- uvc_kernels_score.hip ----
