@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from uvc_amd import synth
-from util import amplicon_stack, diff_groups, presence_violations, run_region
+from util import amplicon_stack, diff_groups, exact_stack, presence_violations, run_region
 
 pytestmark = pytest.mark.gpu
 
@@ -261,6 +261,26 @@ def test_more_than_65535_fragments_on_one_position(oracle_lib, gpu_lib):
     bad = diff_groups(Ro, Rg)
     assert not bad, "\n".join("%s: %d cells differ, e.g. %s" % (g, v[0], v[1]) for g, v in bad.items())
     assert Rg.fetch("FRAG")[:, 0].sum(axis=(0, 1)).max() >= 65536
+    compare_records(Ro.score(), Rg.score())
+
+
+@pytest.mark.parametrize("n, frag_form", [(65535, "h16"), (65536, "b32")])
+def test_exactly_65535_and_65536_fragments_on_one_position(n, frag_form, oracle_lib, gpu_lib, monkeypatch, capfd):
+    """The two sides of the bound itself: 65 535 equal fragments on one position fill a 16-bit bucket counter of k_frag to 0xFFFF and still
+    take the packed form; with one more the preparation reports a fragment depth of 65 536 and the 32-bit form runs (the forms line says which)."""
+    from kernel_forms import parse_forms
+    reads = exact_stack(n)
+    Ro = run_region(oracle_lib, reads)
+    monkeypatch.setenv("UVCGPU_TIMING", "1")
+    capfd.readouterr()
+    Rg = run_region(gpu_lib, reads)
+    forms = parse_forms(capfd.readouterr().err)
+    monkeypatch.delenv("UVCGPU_TIMING")
+    assert forms and forms[-1]["frag"].split(",")[0] == frag_form, forms
+    bad = diff_groups(Ro, Rg)
+    assert not bad, "\n".join("%s: %d cells differ, e.g. %s" % (g, v[0], v[1]) for g, v in bad.items())
+    assert presence_violations(Rg) == 0
+    assert Rg.fetch("FRAG")[:, 0].sum(axis=(0, 1)).max() >= n
     compare_records(Ro.score(), Rg.score())
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from uvc_amd import region, synth
+import prep_unit_cases
 from test_bq_correction import corrected
 from test_gpu_parity import compare_records
 from util import INT_GROUPS, diff_groups, presence_violations, run_region
@@ -171,3 +172,16 @@ def test_correct_bq_rebuilds_the_work_list(oracle_lib, gpu_lib):
     Rg, qg = corrected(gpu_lib, reads, 37, 2, accumulate=True)
     assert np.array_equal(qo, qg)
     check(Ro, Ro.score(), Rg)
+
+
+@pytest.mark.parametrize("arm", ["default", "iontorrent"])
+def test_preparation_edges_through_the_handle(arm, oracle_lib, gpu_lib):
+    """The `nesting` reads of tests/test_gpu_prep_units.py (every CIGAR shape, fragment and unit heads on the thread, wave and tile edges of the
+    preparation's scans, a read without a reference-consuming op, one without bases) through set_reads and accumulate: the direct test pins
+    the preparation's outputs, this one what the accumulate kernels make of them.  IonTorrent: no InDel read on the work list."""
+    case = prep_unit_cases.nesting(arm)
+    reads = prep_unit_cases.handle_reads(case)
+    Ro = run_region(oracle_lib, reads, platform=case["platform"])
+    Rg = run_region(gpu_lib, reads, platform=case["platform"])
+    check(Ro, Ro.score(), Rg, arm + ": ")
+    Rg.close()

@@ -31,6 +31,19 @@ def amplicon_stack():
                 tid=1, beg=beg, end=beg + ref_len, refseq="".join("ACGT"[b] for b in ref))
 
 
+def exact_stack(n):
+    """n single-read fragments, all the same 60 bases (the reference's) with one quality on one strand, over positions 150..209 of a 400 bp
+    region: with n = 65 535 one 16-bit bucket counter of k_frag reaches 0xFFFF, with 65 536 the fragment depth is the first that needs 32 bits."""
+    rng = np.random.default_rng(9)
+    L, ref_len, beg = 60, 400, 7_000_000
+    ref = rng.integers(0, 4, ref_len)
+    return dict(n_reads=n, pos=np.full(n, beg + 150, np.int32), mpos=np.full(n, -1, np.int32), isize=np.zeros(n, np.int32), flag=np.zeros(n, np.uint16),
+                mapq=np.full(n, 60, np.uint8), nm=np.full(n, -1, np.int32), l_qseq=np.full(n, L, np.int32), seq_off=(np.arange(n, dtype=np.int64) * L), cigar_off=np.arange(n, dtype=np.int64),
+                n_cigar=np.ones(n, np.int32), frag_id=np.arange(n, dtype=np.int32), fam_id=np.arange(n, dtype=np.int32), fam_strand=np.zeros(n, np.uint8), n_fams=n,
+                fam_dflag=np.zeros(n, np.uint8), bases=np.tile(ref[150:150 + L], n).astype(np.uint8), quals=np.full(n * L, 30, np.uint8), cigars=np.full(n, (L << 4) | 0, np.uint32),
+                tid=1, beg=beg, end=beg + ref_len, refseq="".join("ACGT"[b] for b in ref))
+
+
 def diff_groups(Ra, Rb, groups=INT_GROUPS):
     """Returns {group: (n_mismatching_cells, first few mismatches)} for groups that differ."""
     bad = {}
