@@ -990,6 +990,11 @@ int uvcgpu_region_check_presence(uvcgpu_region_t *r, int64_t *n_violations);
  * the list (at most 32 entries in all); set_profiling starts it anew, as an accumulate does. */
 int uvcgpu_region_set_profiling(uvcgpu_region_t *r, int on);
 int uvcgpu_region_kernel_times(uvcgpu_region_t *r, char *names, int names_bytes, float *ms, int capacity);
+/* For tests only: the queue of mismatching bases of the LAST accumulate (one item per base of a work-list entry that differs from the
+ * reference: the alignment's rank, the position, symbol | value << 8), in the order the device happened to write it.  Waits for the
+ * handle's streams; copies min(*n, cap) items to `out`; *n is the device's count, *total (may be NULL) the count set_reads made. */
+typedef struct UvcMisItem { int32_t rank, epos, symval; } UvcMisItem;
+int uvcgpu_region_debug_mis_queue(uvcgpu_region_t *r, UvcMisItem *out, int64_t cap, int64_t *n, int64_t *total);
 void uvcgpu_region_destroy(uvcgpu_region_t *r);
 
 /* ---------------------------------------------------------------- BGZF inflate on the device -- */

@@ -97,8 +97,8 @@ static_assert(sizeof(FsRec) == 64, "k_fam_p4d fetches a unit record as four 16-b
 struct Item { int32_t epos; uint8_t sym, flags /* bit0 isGap, bits 1..4 cigar op */; uint16_t pad1_; uint16_t dist, indel_len; int32_t val /* signed: a negative bq_phred_added_* gives values below 0 */; };
 static_assert(sizeof(Item) == 16, "Item");
 
-// A base of a simple alignment that differs from the reference: its P2 update goes to a non-dense symbol, so k_p2_fast
-// queues it here and k_p2_mism applies it (one lane per item).  symval = sym | value << 8.
+// A base of a work-list entry that differs from the reference: its P2 update goes to a non-dense symbol, so it is queued here and k_p2_mism
+// applies it (one lane per item).  symval = sym | value << 8.  P1 makes the queue for the plain P2 form, the base pass of k_p2_fast otherwise.
 struct MisItem { int32_t rank, epos, symval; };
 
 // compact per-fragment record for k_frag, stored in beg-sorted order (written by k_fragstat_fast).  A fragment of <= 2
@@ -212,8 +212,9 @@ struct RegionDev {
     Contrib *table;
     int32_t *ir_list;               // per InDel read: the positions of its low-quality InDels (k_p2_slow's cursor, main.hpp:1817-1859), [gap_off + 2 * rank .. ) with sentinels
     Item *items; int32_t *item_cnt;     // per complex alignment (indexed like complex_ids)
-    MisItem *mis; int32_t *mis_cnt; int32_t mis_cap;   // mismatch queue of k_p2_fast, sized from the exact count below
-    unsigned long long *mis_total;  // number of read bases of simple alignments that differ from the reference (k_aln_prelude)
+    MisItem *mis; int32_t *mis_cnt; int32_t mis_cap;   // mismatch queue of k_p2_mism (made by P1, or by the base pass of k_p2_fast: DESIGN 6-r11), sized from the count below
+    unsigned long long *mis_total;  // number of read bases that differ from the reference in the alignments that can be on the work list (k_aln_prelude: the simple ones and
+                                    // the InDel reads of kind 2 before the low-quality-InDel test, which uvcgpu_region_correct_bq can turn either way): the items never exceed it
     int32_t max_frag_span;
     int32_t any_amplicon;           // some family carries the amplicon flag (fam_dflag & 0x4)
     int32_t frag32;                 // UVCGPU_FRAG32=1: k_frag with 32-bit buckets although the depth would allow the packed form (tests compare the two)

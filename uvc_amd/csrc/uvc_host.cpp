@@ -690,6 +690,23 @@ int uvcgpu_region_kernel_times(uvcgpu_region_t *r, char *names, int names_bytes,
     return n;
 }
 
+// For tests only: the mismatch queue of the last accumulate as the device left it (the order of the items is the order of the atomics)
+static_assert(sizeof(UvcMisItem) == sizeof(MisItem), "UvcMisItem is MisItem");
+int uvcgpu_region_debug_mis_queue(uvcgpu_region_t *r, UvcMisItem *out, int64_t cap, int64_t *n, int64_t *total) {
+    if (!r || !n || cap < 0 || (cap > 0 && !out)) return fail(UVCGPU_EINVAL, "bad argument");
+    if (!r->has_reads || !r->accumulated) return fail(UVCGPU_ESTATE, "debug_mis_queue needs an accumulate");
+    HIP_OK(hipStreamSynchronize(r->stream));
+    if (r->side) HIP_OK(hipStreamSynchronize(r->side));
+    if (r->side3) HIP_OK(hipStreamSynchronize(r->side3));
+    int32_t cnt = 0; unsigned long long tot = 0;
+    HIP_OK(hipMemcpy(&cnt, r->R.mis_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(&tot, r->R.mis_total, sizeof(tot), hipMemcpyDeviceToHost));
+    *n = cnt; if (total) *total = (int64_t)tot;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>(cnt, r->R.mis_cap), cap);
+    if (k > 0) HIP_OK(hipMemcpy(out, r->R.mis, sizeof(MisItem) * (size_t)k, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // how many records the last uvcgpu_region_score scored, and how many it returned (fewer with UvcScoreRequest::kept_only)
 int uvcgpu_region_last_score_counts(const uvcgpu_region_t *r, int64_t *scored, int64_t *returned) {
     if (!r) return fail(UVCGPU_EINVAL, "null region");

@@ -614,7 +614,19 @@ DEV void mut_event(const RegionDev &R, const UvcParams &P, const AlnRec &a, int 
     }
 }
 
-#define PREPQ_CAP 192   // per-wave LDS queue of (alignment, position) pairs whose base differs from the reference
+#define PREPQ_CAP 192   // per-wave LDS queue of the bases that differ from the reference, see prepq_entry
+// An entry of the LDS queues of P1: x = FastRec::aln, with PREPQ_MRUN when the base belongs to an M run of an InDel read (k_prep_slow has that
+// read: only the base's item is made); y = position - `origin` (the window's or the tile's first position) | symbol << 16 | quality << 24.
+#define PREPQ_MRUN ((int)0x80000000u)
+DEV int2 prepq_entry(int aln, bool mrun, int p, int origin, int sym, int q) { return make_int2(aln | (mrun ? PREPQ_MRUN : 0), (int)((unsigned)(p - origin) | ((unsigned)sym << 16) | ((unsigned)q << 24))); }
+DEV int prepq_aln(int2 e) { return e.x & ~PREPQ_MRUN; }
+DEV int prepq_pos(int2 e, int origin) { return origin + (e.y & 0xFFFF); }
+// P1 makes the mismatch queue of k_p2_mism where the accumulate says misq=p1: entry e goes to slot `slot` of RegionDev::mis
+// (the caller's atomicAdd on mis_cnt gave the slots of its batch) as the item the plain base pass would have queued
+DEV void mis_emit(const RegionDev &R, const UvcParams &P, int2 e, int origin, int slot) {
+    if (slot < R.mis_cap) { MisItem it; it.rank = prepq_aln(e); it.epos = prepq_pos(e, origin); it.symval = (int)(((unsigned)e.y >> 16) & 0xFFu) | (base_value((int)((unsigned)e.y >> 24), P) << 8); R.mis[slot] = it; }
+    else atomicExch(R.err, UVCGPU_EDEVICE);   // cannot happen: the queue holds every mismatching base of the work list (RegionDev::mis_total)
+}
 // ------------------------------------------------------------------------------------------------
 // k_prep_sums: the P1 counters of the simple alignments that do not depend on the bases, as interval sums (the scheme of k_frag_sums).
 // a_dp, a_pcr_dp, a_umi_dp, a_qlen, a_XM1500, a_LIDP, a_RIDP are sums of per-read constants over the reads that cover a position;
@@ -697,8 +709,9 @@ __global__ void __launch_bounds__(256) k_prep_sums(RegionDev R, UvcParams P) {
 // SPLIT: a region with fewer windows than the chip has wave slots (a deep, short panel region: 200 kb are three waves per SIMD, each walking
 // thousands of reads) gives every window to a BLOCK: its four waves take every fourth chunk of the window's reads.  The kernel ends in
 // atomics anyway, so the partial sums need no reduction.
+// emit (misq=p1): every mismatching base also becomes an item of RegionDev::mis, and the M runs of the InDel reads are visited for that alone.
 template <bool SPLIT>
-__global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
+__global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P, int emit) {
     __shared__ int2 prepq[4][PREPQ_CAP];
     const int lane = threadIdx.x & 63;
     const int wave = SPLIT ? wave_uniform((int)xcd_block()) : wave_uniform((int)((xcd_block() * blockDim.x + threadIdx.x) >> 6));
@@ -720,11 +733,17 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
     int2 *myq = prepq[threadIdx.x >> 6];
     int nq = 0;   // wave-uniform: only updated in uniform control flow
     auto drain = [&]() {
+        int gbase = 0;
+        if (emit && lane == 0) gbase = atomicAdd(R.mis_cnt, nq);   // one atomic for the batch, then contiguous stores
+        gbase = wave_uniform(gbase);
         for (int i = lane; i < nq; i += 64) {
             const int2 e = myq[i];
+            if (emit) mis_emit(R, P, e, w0, gbase + i);
+            if (e.x & PREPQ_MRUN) continue;
             const AlnRec &a = R.alns[e.x];
-            snv_dnv_scatter(R, R.bases + a.seq_off, (int)(a.qbase + e.y - a.seq_off), a.l_qseq, a.pos, a.rend, e.y);
-            mut_event(R, P, a, e.y, R.refsym[e.y - R.beg]);
+            const int ep = prepq_pos(e, w0);
+            snv_dnv_scatter(R, R.bases + a.seq_off, (int)(a.qbase + ep - a.seq_off), a.l_qseq, a.pos, a.rend, ep);
+            mut_event(R, P, a, ep, R.refsym[ep - R.beg]);
         }
         nq = 0;
     };
@@ -743,15 +762,16 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
         auto one = [&](int j, int bqn) {
             const int b = bq_sym(bqn), q = bq_qual(bqn);
             const int apos = bcast(c[FR_W(pos)], j), rend = bcast(c[FR_W(rend)], j);
-            if (rend <= w0 || (bcast(c[FR_W(xbv)], j) & FREC_M_RUN)) return;   // behind the window, or an M run of an InDel read (k_prep_slow has the read)
+            const bool mrun = (bcast(c[FR_W(xbv)], j) & FREC_M_RUN) != 0;   // an M run of an InDel read: k_prep_slow has the read, only the items are made here
+            if (rend <= w0 || (mrun && !emit)) return;   // behind the window
             const bool cover = (valid && p >= apos && p < rend);
             const wmask mm = BAL(cover && b != my_ref);
             if (mm) {
                 if (nq > PREPQ_CAP - 64) drain();
-                if (cover && b != my_ref) myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = make_int2(bcast(c[FR_W(aln)], j), p);   // (FastRec::aln, position)
+                if (cover && b != my_ref) myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = prepq_entry(bcast(c[FR_W(aln)], j), mrun, p, w0, b, q);
                 nq += (int)__builtin_popcountll(mm);
             }
-            if (cover) {   // (the counters that do not look at the base: k_prep_sums)
+            if (cover && !mrun) {   // (the counters that do not look at the base: k_prep_sums)
                 if (q >= P.bias_thres_highBQ) {
                     ldist += p - apos + 1; rdist += rend - p;
                     lbaq += (my_baq - bcast(c[FR_W(baq_pos)], j) + 1);
@@ -812,26 +832,29 @@ __global__ void __launch_bounds__(256) k_prep_fast(RegionDev R, UvcParams P) {
 // adds +v / -v at the ends of its piece of the tile and -v / +v at p and p + 1 of each of its low-quality bases.  After a block prefix
 // sum every plane gets one coalesced global atomic per position (k_prep_slow adds to the same planes meanwhile).  Mismatching bases wait
 // in an LDS queue and go through snv_dnv_scatter / mut_event a block at a time; the clip events fire in the tile that owns their position.
+// emit (misq=p1): a drain also moves the queue to RegionDev::mis, behind one atomicAdd for the batch, and the scan visits the M runs of the
+// InDel reads for their items alone (no sums, no SNV / DNV runs, no mutation or clip events: k_prep_slow has those reads).
 // The scan waits on memory (a read's bases and qualities are two or three cache lines each, scattered over the columns): the next
 // entry's record and all words of this one are requested before anything is used (tile sizes and variants: DESIGN.md section 6-r6).
 // ------------------------------------------------------------------------------------------------
 #ifndef PSCAN_TILE
 #define PSCAN_TILE 1024
 #endif
-#define PSCAN_QCAP 512     // LDS queue of (alignment, position) pairs whose base differs from the reference
+#define PSCAN_QCAP 512     // LDS queue of the bases that differ from the reference (prepq_entry)
 #define PSCAN_ROUND 512    // entries between two looks at the queue
 #define PSCAN_WORDS 3      // 8-byte words per lane and trip: 192 bases of an entry (at most 8: a word's flags are every eighth bit of a mask)
 enum { PN_A = 0, PN_APOS, PN_REND, PN_N32 };
 enum { PN_CL = 0, PN_CR, PN_N64 };
-__global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
+__global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P, int emit) {
     static_assert(PSCAN_TILE % 256 == 0 && PSCAN_TILE % 64 == 0, "a thread owns PSCAN_TILE / 256 consecutive positions in the prefix sums");
     static_assert(PSCAN_WORDS <= 8, "a word's flags are every eighth bit of a mask");
+    static_assert(PSCAN_TILE <= 65536, "prepq_entry holds the offset in the tile in 16 bits");
     constexpr int PER = PSCAN_TILE / 256;
     // difference arrays: +v / -v at the ends of a read's piece of the tile, -v / +v around each of its low-quality bases; afterwards the finished counters
     __shared__ unsigned d32[PN_N32][PSCAN_TILE + 1];
     __shared__ unsigned long long d64[PN_N64][PSCAN_TILE + 1];
     __shared__ int2 queue[PSCAN_QCAP];
-    __shared__ int qn;
+    __shared__ int qn, qbase;
     __shared__ unsigned wtot[PN_N32][4];
     __shared__ unsigned long long wtot64[PN_N64][4];
     const unsigned long long K7F = 0x7F7F7F7F7F7F7F7FULL, K80 = 0x8080808080808080ULL, K01 = 0x0101010101010101ULL;
@@ -876,7 +899,8 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
             if (i + 32 < stop) fetch(i + 32);
             const int apos = h0.x, rend = h0.y;
             if (rend <= t0 || apos >= t1 || apos >= rend) continue;   // (the eight lanes of the entry leave together)
-            if (h2.y & FREC_M_RUN) continue;   // an M run of an InDel read (k_prep_slow has the read)
+            const bool mrun = (h2.y & FREC_M_RUN) != 0;   // an M run of an InDel read (k_prep_slow has the read): its items only
+            if (mrun && !emit) continue;
             const int s = imax(apos, t0), e = imin(rend, t1);
             const int cL = (int)(B0 - (unsigned)h3.x + 1u), cR = (int)((unsigned)h3.y - B0 + 1u);
             // up to PSCAN_WORDS words per lane are requested together, ahead of the LDS atomics
@@ -907,6 +931,7 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
                     mism |= (((((x & K7F) + K7F) | x) & vm) >> 7) << w;
                     low |= (((thr_hi ? ~(qq[w] & t) : ~(qq[w] | t)) & vm) >> 7) << w;
                 }
+                if (mrun) low = 0;
                 while (low) {   // the read's terms leave the sums at this one position: -v at p, +v at p + 1
                     const int bit = __builtin_ctzll(low), xp = pb + 64 * (bit & 7) + (bit >> 3) - t0;
                     low &= low - 1;
@@ -919,10 +944,20 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
                 while (mism) {
                     const int bit = __builtin_ctzll(mism), p = pb + 64 * (bit & 7) + (bit >> 3);
                     mism &= mism - 1;
+                    unsigned long long bw = 0, qw = 0;   // the word of the bit (selects: bb and qq stay in registers)
+#pragma unroll
+                    for (int w = 0; w < PSCAN_WORDS; w++) if ((bit & 7) == w) { bw = bb[w]; qw = qq[w]; }
+                    const int sym = (int)((bw >> (8 * (bit >> 3))) & 0xFF), q = (int)((qw >> (8 * (bit >> 3))) & 0xFF);
+                    const int2 it = prepq_entry(h0.w, mrun, p, t0, sym, q);
                     const int slot = atomicAdd(&qn, 1);
-                    if (slot < PSCAN_QCAP) queue[slot] = make_int2(h0.w, p); else mismatch(h0.w, p);   // (a full queue: at once, by this lane)
+                    if (slot < PSCAN_QCAP) queue[slot] = it;
+                    else {   // (a full queue: at once, by this lane, and one slot of the global queue)
+                        if (emit) mis_emit(R, P, it, t0, atomicAdd(R.mis_cnt, 1));
+                        if (!mrun) mismatch(h0.w, p);
+                    }
                 }
             }
+            if (mrun) continue;   // (the eight lanes of the entry)
             // the interval sums, a lane per sum; the clip events
             if (sub < PN_N32) {
                 const unsigned v = (sub == PN_A ? 1u : sub == PN_APOS ? (unsigned)apos : (unsigned)rend);
@@ -940,7 +975,15 @@ __global__ void __launch_bounds__(256) k_prep_scan(RegionDev R, UvcParams P) {
         __syncthreads();
         const int n_queued = imin(qn, PSCAN_QCAP);
         const bool drain = (n_queued >= 256 || stop == total);   // a base per thread, or the last look
-        if (drain) for (int i = tid; i < n_queued; i += 256) mismatch(queue[i].x, queue[i].y);
+        if (drain && emit && n_queued) {   // (block-uniform) the batch's place in the global queue: one atomic
+            if (tid == 0) qbase = atomicAdd(R.mis_cnt, n_queued);
+            __syncthreads();
+        }
+        if (drain) for (int i = tid; i < n_queued; i += 256) {
+            const int2 e = queue[i];
+            if (emit) mis_emit(R, P, e, t0, qbase + i);
+            if (!(e.x & PREPQ_MRUN)) mismatch(e.x, prepq_pos(e, t0));
+        }
         __syncthreads();
         if (drain && tid == 0) qn = 0;
         __syncthreads();
@@ -1223,9 +1266,13 @@ DEV void mis_apply(const RegionDev &R, const UvcParams &P, const MisItem &it) {
 DEV unsigned long long *red64(int (*red)[64], int f) { return (unsigned long long *)&red[UVC_NSEG32 + 2 * f][0]; }
 // NSL > 0 (with SPLIT, for the plain completion pass only): the sparse form, k_p2_link_sparse.  The block serves window `win` with 4 * NSL
 // waves; wave w walks slice w >> 2 (uvc_link_slice) of class list w & 3, and the LDS reduction of the split form adds the 4 * NSL partial sets up.
-template <bool DO_L, bool DO_B, bool PLAIN, bool SPLIT = false, int NSL = 0>
-DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *amp2, MisItem (*misq)[DO_B ? MISQ_CAP : 1], int (*red)[64] = nullptr, int win = 0) {
+// MQ: the base pass makes the mismatch queue itself (the generic forms, and the plain ones where the accumulate says misq=p2); without it P1
+// has made the queue (misq=p1) and no ballot, no LDS queue and no flush are compiled.
+template <bool DO_L, bool DO_B, bool PLAIN, bool SPLIT = false, int NSL = 0, bool MQ = DO_B>
+DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *amp2, MisItem (*misq)[MQ ? MISQ_CAP : 1], int (*red)[64] = nullptr, int win = 0) {
     static_assert(NSL == 0 || (SPLIT && DO_L && !DO_B && PLAIN), "the sparse form exists for the plain completion pass");
+    static_assert(!MQ || DO_B, "the queue holds read bases");
+    static_assert(MQ || !DO_B || PLAIN, "P1 makes the queue of the plain form only: the generic values need neighbouring qualities and the primer gate");
     constexpr int NWV = (NSL ? 4 * NSL : 4);   // waves of a block
     COARSE_T(ct0)
     if (DO_L && !NSL) {   // the completion pass runs a window only where a reader asked for it and no earlier pass has been (block-uniform; the waves look again below)
@@ -1265,7 +1312,7 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     constexpr bool L5_BASE = DO_B && PLAIN, L5_LINK = DO_L && !PLAIN;
     int noindel80 = 80;
     if ((DO_L || L5_BASE) && valid && x > 0) noindel80 = imin(80, imin(RTRP(R, UVC_RTR_indelphred, x - 1), RTRP(R, UVC_RTR_indelphred, x)));
-    MisItem *myq = misq[DO_B ? (threadIdx.x >> 6) : 0];
+    MisItem *myq = misq[MQ ? (threadIdx.x >> 6) : 0];
     int nq = 0;   // wave-uniform: only updated in uniform control flow
     int l5_bq = 0;   // base pass: BQSUM of LINK_M (see l5_dp)
     auto flush_queue = [&]() {
@@ -1330,8 +1377,8 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
                     if (DO_L) incL = (p > apos ? simple_link_value(R, P, a, p, R.quals + a.qbase, true) : 0);
                 }
             } else { inc = base_value(q, P); incL = (int)nnminus(noindel80, nogap) + 1; }
-            const wmask mm = DO_B ? BAL(cover && !hasB) : 0ull;
-            if (DO_B && mm) {   // bases that differ from the reference go to the wave's queue; k_p2_mism applies them
+            const wmask mm = MQ ? BAL(cover && !hasB) : 0ull;
+            if (MQ && mm) {   // bases that differ from the reference go to the wave's queue; k_p2_mism applies them
                 if (nq > MISQ_CAP - 64) flush_queue();
                 if (cover && !hasB) { MisItem it; it.rank = K(FR_W(aln)); it.epos = p; it.symval = sym | (inc << 8); myq[nq + (int)__builtin_popcountll(mm & ((1ull << lane) - 1ull))] = it; }
                 nq += (int)__builtin_popcountll(mm);
@@ -1419,7 +1466,7 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     run_list(std::false_type{}, std::true_type{}, 2);
     run_list(std::true_type{}, std::true_type{}, 3);
     }
-    if (DO_B && nq > 0) flush_queue();
+    if (MQ && nq > 0) flush_queue();
     COARSE_T(ct2)
     if (SPLIT) {   // the four partial sets -> LDS -> one set (the two passes own different symbols: one symbol per kernel)
         const SegAcc &A = (DO_B ? Aref : Alink);
@@ -1461,7 +1508,7 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     }
     if (DO_L && lane == 0) R.link_done[wave] = 1;
     if (!valid) return;
-    // the base pass runs before every other writer of its planes (k_p2_mism, k_p2_items): plain stores, also for its five cells of LINK_M
+    // the base pass is the only writer of the reference symbol's cells in front of k_p2_items (k_p2_mism writes the other symbols'): plain stores, also for its five cells of LINK_M
     if (DO_B) { seg_store(R, Aref, my_ref, x); if (L5_BASE && l5_bq) BQS(R, UVC_LINK_M, x) = l5_bq; }
     if (DO_L) seg_add_link<L5_LINK>(R, Alink, x);
 #ifdef UVC_FRAG_COARSE
@@ -1470,18 +1517,33 @@ DEV void p2_fast_body(const RegionDev &R, const UvcParams &P, int *amp1, int *am
     if (lane == 0 && (wave % 2999) == 7) printf("coarse p2<%d,%d> wave %d prologue %llu lists %llu epilogue %llu\n", (int)DO_L, (int)DO_B, wave, ct1 - ct0, ct2 - ct1, ct3 - ct2);
 #endif
 }
+// The plain base pass under these names reads a queue that P1 made; the generic base pass makes its own.  k_p2_fast_q / k_p2_fast_split_q
+// are the plain base pass that still makes the queue (misq=p2: UVCGPU_MISQ=p2, for comparison item by item).
 template <bool DO_L, bool DO_B, bool PLAIN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_p2_fast(RegionDev R, UvcParams P) {
+    constexpr bool MQ = DO_B && !PLAIN;
     __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
-    __shared__ MisItem misq[DO_B ? 4 : 1][DO_B ? MISQ_CAP : 1];
-    p2_fast_body<DO_L, DO_B, PLAIN>(R, P, amp1, amp2, misq);
+    __shared__ MisItem misq[MQ ? 4 : 1][MQ ? MISQ_CAP : 1];
+    p2_fast_body<DO_L, DO_B, PLAIN, false, 0, MQ>(R, P, amp1, amp2, misq);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) k_p2_fast_q(RegionDev R, UvcParams P) {
+    __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
+    __shared__ MisItem misq[4][MISQ_CAP];
+    p2_fast_body<false, true, true, false, 0, true>(R, P, amp1, amp2, misq);
 }
 template <bool DO_L, bool DO_B, bool PLAIN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_p2_fast_split(RegionDev R, UvcParams P) {
+    constexpr bool MQ = DO_B && !PLAIN;
     __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
-    __shared__ MisItem misq[DO_B ? 4 : 1][DO_B ? MISQ_CAP : 1];
+    __shared__ MisItem misq[MQ ? 4 : 1][MQ ? MISQ_CAP : 1];
     __shared__ __attribute__((aligned(8))) int red[P2_RED_SLOTS][64];
-    p2_fast_body<DO_L, DO_B, PLAIN, true>(R, P, amp1, amp2, misq, red);
+    p2_fast_body<DO_L, DO_B, PLAIN, true, 0, MQ>(R, P, amp1, amp2, misq, red);
+}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_p2_fast_split_q(RegionDev R, UvcParams P) {
+    __shared__ int amp1[256 + AMP_LO], amp2[256 + AMP_LO];
+    __shared__ MisItem misq[4][MISQ_CAP];
+    __shared__ __attribute__((aligned(8))) int red[P2_RED_SLOTS][64];
+    p2_fast_body<false, true, true, true, 0, true>(R, P, amp1, amp2, misq, red);
 }
 // The sparse form of the plain completion pass: where few windows are needed the wave-per-window form is bound by the length of
 // one wave's walk over a window's four class lists, not by the number of windows.  Here a block of 4 * NSL waves shares one window, and the
@@ -1501,7 +1563,7 @@ __global__ void __launch_bounds__(256 * NSL) k_p2_link_sparse(RegionDev R, UvcPa
     }
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const int w = wave_uniform(R.link_list[i]);
-        if ((unsigned)w < (unsigned)R.nwin && uvc_link_window_runs(R.link_need[w], R.link_done[w])) p2_fast_body<true, false, true, true, NSL>(R, P, amp1, amp2, misq, red, w);
+        if ((unsigned)w < (unsigned)R.nwin && uvc_link_window_runs(R.link_need[w], R.link_done[w])) p2_fast_body<true, false, true, true, NSL, false>(R, P, amp1, amp2, misq, red, w);
         __syncthreads();   // the next window zeroes the reduction area
     }
 }
@@ -3858,7 +3920,7 @@ extern "C" void uvc_launch_check_dirty(const RegionDev *R, unsigned long long *d
 
 // The form each pass of the accumulate takes: decided once from the tile's shape, the parameters and the families' flags, then printed
 // (UVCGPU_TIMING) and launched from the same flags.
-struct AccForms { bool vcf, proton, split_windows, p2_plain, frag_plain, h16, fam, digest, duplex; int n_gen; };
+struct AccForms { bool vcf, proton, split_windows, p2_plain, misq_p1, frag_plain, h16, fam, digest, duplex; int n_gen; };
 // UVCGPU_SPLIT is read on every accumulate; the handle remembers the answer for the completion passes that follow that accumulate
 extern "C" int uvc_acc_split_windows(const RegionDev *R) {
     const char *sp_env = getenv("UVCGPU_SPLIT");
@@ -3881,6 +3943,11 @@ static AccForms acc_forms(const RegionDev *R, const UvcParams *P, int n_dup) {
     // reads among its waves (UVCGPU_SPLIT=0 / 1 forces)
     F.split_windows = (uvc_acc_split_windows(R) != 0);
     F.p2_plain = p2_plain_form(R, P);
+    // The mismatch queue of k_p2_mism: P1 makes it for the plain P2 form, whose items are (read, position, base, quality + addend) -- all of it
+    // in P1's registers; the generic forms need neighbouring qualities and the primer gate and keep the queue of their base pass.
+    // UVCGPU_MISQ=p2 (read on every accumulate, like UVCGPU_SPLIT) keeps it in the plain base pass too; tests compare the two item by item.
+    const char *mq_env = getenv("UVCGPU_MISQ");
+    F.misq_p1 = F.vcf && F.p2_plain && !(mq_env && !strcmp(mq_env, "p2"));
     // P3: no IonTorrent values, no SSCS table cap, no padded deletions
     F.frag_plain = F.vcf && !F.proton && !(0x1 & P->fam_flag) && !(P->microadjust_padded_deletion_flag & 0x1);
     F.h16 = (R->max_frag_depth < 65536) && !R->frag32;   // two 16-bit bucket counters per LDS word
@@ -3899,6 +3966,8 @@ static void print_forms(const AccForms &F) {
             !F.fam ? "none" : F.digest ? "digest" : "generic",
             !F.duplex ? "none" : F.digest ? "digest" : "generic",
             !F.n_gen ? "none" : F.proton ? "all" : "sweep");
+    // who makes the mismatch queue (a line of its own: the keys of the forms line above are a closed set to its readers)
+    fprintf(stderr, "[uvcgpu accumulate] misq=%s\n", !F.vcf ? "none" : F.misq_p1 ? "p1" : "p2");
 }
 // The P1 pass of the forms that are not split: k_prep_scan, or k_prep_fast<false> with UVCGPU_PREP=window (read on every accumulate, like
 // UVCGPU_SPLIT; tests compare the two).
@@ -3920,10 +3989,13 @@ static bool prep_scan_exact(const RegionDev *R, const UvcParams *P) {
 }
 // one pass of k_p2_fast over the P2 work list: the base symbols with the five cells of LINK_M that P3 reads (DO_B), or the completion pass of
 // LINK_M (DO_L), a block per window (split) or a wave per window
+// (queue: the plain base pass that makes the mismatch queue itself, misq=p2; the generic base pass always does)
 template <bool DO_L, bool DO_B>
-static void launch_p2_fast(const char *kname, bool split, bool plain, const RegionDev *R, const UvcParams *P, UvcProf *prof, hipStream_t s) {
+static void launch_p2_fast(const char *kname, bool split, bool plain, const RegionDev *R, const UvcParams *P, UvcProf *prof, hipStream_t s, bool queue = false) {
     const unsigned nwin = nblk(R->npos, 256);   // 4 waves x 64 positions per block
-    if (split && plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
+    if (queue && plain && split) TIMED(prof, kname, hipLaunchKernelGGL(k_p2_fast_split_q, dim3(R->nwin), dim3(256), 0, s, *R, *P));
+    else if (queue && plain) TIMED(prof, kname, hipLaunchKernelGGL(k_p2_fast_q, dim3(nwin), dim3(256), 0, s, *R, *P));
+    else if (split && plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, true>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
     else if (split) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast_split<DO_L, DO_B, false>), dim3(R->nwin), dim3(256), 0, s, *R, *P));
     else if (plain) TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, true>), dim3(nwin), dim3(256), 0, s, *R, *P));
     else TIMED(prof, kname, hipLaunchKernelGGL((k_p2_fast<DO_L, DO_B, false>), dim3(nwin), dim3(256), 0, s, *R, *P));
@@ -3984,7 +4056,8 @@ extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P,
 //  2  k_prep_sums                     M   index 1-4 (1)                                             PREP: plain stores into zeroed planes
 //  3  k_prep_slow                     S2  -- ; its atomics must follow the plain stores of 2        PREP (atomics), fragment event lists, clip events
 //                                         [e_fork recorded behind 2]
-//  4  k_prep_scan / k_prep_fast       M   index 1-4 (1); atomics behind the stores of 2             PREP (atomics), fragment event lists, clip events
+//  4  k_prep_scan / k_prep_fast       M   index 1-4 (1); atomics behind the stores of 2             PREP (atomics), fragment event lists, clip events; misq=p1: the mismatch queue
+//                                                                                                   (mis_cnt was zeroed on M in front of the accumulate: uvcgpu_region_accumulate)
 //  5  k_thres                         M   PREP (2, 3 [e_join], 4)                                   THRES, RTR.indelphred
 //     -- fork [e_fork]: S2 and S3 behind 5 --
 //  6  k_p2_slow<true>  (walk)         S2  RTR.indelphred, THRES (5)                                 P2 items of the InDel reads
@@ -3995,10 +4068,11 @@ extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P,
 // 11  k_fragstat_sweep, overflow      S3  overflow list and count (8), table (7)                    n_cov / n_near of frags and ffast
 // 12  k_frag_sums                     S3  ffast with n_cov / n_near (8, 10, 11), index 5-6 (9)      fsum
 // 13  k_p2_fast, base symbols         M   THRES, RTR.indelphred (5), index 1-4 (1)                  SEG32 / SEG64 / BQSUM / VQ a*BQ* of the reference symbol and the five cells of LINK_M
-//                                                                                                   that rows 19 and 20 read (SEG32 aDP**, BQSUM): plain stores; mismatch queue
-// 14  k_p2_mism                       S2  mismatch queue (13 [e_fork2]); atomics behind the stores of 13   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
+//                                                                                                   that rows 19 and 20 read (SEG32 aDP**, BQSUM): plain stores; misq=p2: the mismatch queue
+// 14  k_p2_mism                       S2  THRES (5), misq=p1: the mismatch queue (4 [e_fork]), in front of 6;   SEG32 / SEG64 / BQSUM / VQ a*BQ* of the symbols that differ from the
+//                                         misq=p2: the queue (13 [e_fork2]), behind 6 and 13                   reference (atomics), occ marks
 // 15  (UVCGPU_LINK=eager only: row 23 with every window, here)
-//     -- join: M behind 14 [e_join] and 12 [e_join3]; S2 behind 12 [e_join3] --
+//     -- join: M behind 6 and 14 [e_join] and 12 [e_join3]; S2 behind 12 [e_join3] --
 // 16  k_gap_keys .. k_gap_rows_fin    S2  gap events (7 [e_join3])                                  InDel allele tables; fam2_ins_len complete at [e_alleles]
 // 17  k_fam_stat                      S3  table (7), ffast_u (8)                                    unit records (fss) -> [e_stat]
 // 18  k_p2_items                      M   items (6 [e_join]), THRES (5); atomics behind the stores of 13   SEG32 / SEG64 / BQSUM / VQ a*BQ* (atomics)
@@ -4016,6 +4090,10 @@ extern "C" void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P,
 //     k_p2_link_sparse / k_p2_fast    M   link_list (18a, 23), THRES, RTR.indelphred (5), index 1-4 (1)   the other 34 cells of LINK_M in those windows, added to what 18 left
 //                                                                                                   there (load, add, store: no other writer of these cells runs); link_done
 // Rows 19 and 20 read, per position, the aDP* and BQSUM sums that row 18 adds to: k_p2_items cannot run beside the fragment kernels.
+// Row 14 need not follow row 13 (misq=p1 runs them beside each other): an item has sym != the reference symbol of its position, mis_apply adds to
+// the cells of that symbol alone (seg_flush) and ORs its occ bit, and seg_store of row 13 stores into the cells of the reference symbol and
+// into five cells of LINK_M, which is no base symbol: no cell has both writers.  Rows 18, 18a, 19 and 20 read or add to cells of row 14 and
+// stay behind the join; 18a sees the occ marks of mis_apply.
 // Row 3 cannot be forked in front of rows 1 and 2: a store of row 2 would overwrite what row 3 has added.
 // Rows 18a / 18b may run beside rows 19 to 22: they write the 34 cells of LINK_M beyond aDP** / BQSUM, link_need, link_done and the list, none of
 // which 19 to 22 read (19 and 20 read the five cells of row 13), and 19 to 22 write none of the 34 cells.  occ is read while 19 to 21 may still add
@@ -4047,9 +4125,10 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
         if (side && R->n_complex) hipEventRecord(e_join, s2);
         const bool scan = !F.split_windows && prep_scan_wanted() && prep_scan_exact(R, P);
         if (getenv("UVCGPU_TIMING")) fprintf(stderr, "[uvcgpu accumulate] prep kernel %s\n", F.split_windows ? "k_prep_fast<true>" : scan ? "k_prep_scan" : "k_prep_fast<false>");
-        if (F.split_windows) TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P));
-        else if (scan) TIMED(prof, "k_prep_scan", hipLaunchKernelGGL(k_prep_scan, dim3(nblk(R->npos, PSCAN_TILE)), dim3(256), 0, s, *R, *P));
-        else TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<false>, dim3(nwin), dim3(256), 0, s, *R, *P));
+        const int emit = F.misq_p1 ? 1 : 0;   // (RegionDev::mis_cnt was zeroed on this stream in front of the accumulate)
+        if (F.split_windows) TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<true>, dim3(R->nwin), dim3(256), 0, s, *R, *P, emit));
+        else if (scan) TIMED(prof, "k_prep_scan", hipLaunchKernelGGL(k_prep_scan, dim3(nblk(R->npos, PSCAN_TILE)), dim3(256), 0, s, *R, *P, emit));
+        else TIMED(prof, "k_prep_fast", hipLaunchKernelGGL(k_prep_fast<false>, dim3(nwin), dim3(256), 0, s, *R, *P, emit));
         if (side && R->n_complex) hipStreamWaitEvent(s, e_join, 0);
     }
     // P1b is part of updateByAlns3UsingBQ too (main.hpp:3691-3702): on a FASTQ-only run the thresholds stay zero and rtr.indelphred unedited
@@ -4057,8 +4136,12 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     if (side) { hipEventRecord(e_fork, s); hipStreamWaitEvent(s2, e_fork, 0); if (s3 != s2) hipStreamWaitEvent(s3, e_fork, 0); }
     // ---- the P2 phase (rows 6-15 of the table).  Neither side chain may be longer than the two passes of k_p2_fast on the main stream, and
     // no more should run beside them than that takes: a side kernel costs the pass it runs beside part of its own time.
-    // s2: the walk that produces the P2 items, then, behind the base pass, its queued mismatches.  s3: the walk that fills the contribution
-    // table, then the per-fragment statistics, the fragment window index and the interval sums (they need P1 / P1b only).
+    // s2: the queued mismatches, then the walk that produces the P2 items (misq=p2: the walk, then, behind the base pass, the mismatches the
+    // pass has queued).  s3: the walk that fills the contribution table, then the per-fragment statistics, the fragment window index and the
+    // interval sums (they need P1 / P1b only).
+    // misq=p1: the queue is complete behind row 4, so k_p2_mism needs THRES only and runs beside the base pass, not behind it: on s2 in front
+    // of the walk, where it ends long before the join (behind the walk and on the main stream were measured and are no shorter: DESIGN 6-r11)
+    if (F.misq_p1) TIMED2(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
     if (P->inferred_is_vcf_generated && R->n_complex) TIMED2(prof, "k_p2_slow_walk", hipLaunchKernelGGL(k_p2_slow<true>, dim3(nblk(R->n_complex, 64)), dim3(64), 0, s, *R, *P));
     if (R->n_complex) TIMED3(prof, "k_p2_slow_table", hipLaunchKernelGGL(k_p2_slow<false>, dim3(nblk(R->n_complex, 64)), dim3(64), 0, s, *R, *P));
     TIMED3(prof, "k_fragstat_fast", hipLaunchKernelGGL(k_fragstat_fast, dim3(nblk(R->n_frags, 256)), dim3(256), 0, s, *R, *P));
@@ -4069,12 +4152,14 @@ extern "C" void uvc_launch_accumulate(const RegionDev *R, const UvcParams *P, in
     TIMED3(prof, "k_fragstat_overflow", hipLaunchKernelGGL(k_fragstat_sweep, dim3(imin_h(R->n_frags, 65535)), dim3(64), 0, s, *R, *P, (const int32_t *)R->overflow_frags, (const int32_t *)R->n_overflow, 0));
     if (UVC_PLATFORM_IONTORRENT != P->inferred_sequencing_platform)   // (there every fragment takes k_frag_generic)
         TIMED3(prof, "k_frag_sums", hipLaunchKernelGGL(k_frag_sums, dim3(nblk(R->npos, FSUM_TILE), 2), dim3(256), 0, s, *R, *P));
-    // main stream: the base symbols first, so that the queued mismatches (rare symbols, atomics: disjoint from the planes the
-    // LINK_M pass stores to) are applied on a side stream while the LINK_M pass runs
+    // main stream: the base symbols.  misq=p2: the mismatches the pass queues (other symbols, atomics: disjoint from the cells the pass
+    // stores to) are applied on a side stream behind it
     if (P->inferred_is_vcf_generated) {
-        launch_p2_fast<false, true>("k_p2_fast_base", F.split_windows, F.p2_plain, R, P, prof, s);
-        if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s2, e_fork2, 0); }
-        TIMED2(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
+        launch_p2_fast<false, true>("k_p2_fast_base", F.split_windows, F.p2_plain, R, P, prof, s, !F.misq_p1);
+        if (!F.misq_p1) {   // misq=p2: the base pass has made the queue
+            if (side) { hipEventRecord(e_fork2, s); hipStreamWaitEvent(s2, e_fork2, 0); }
+            TIMED2(prof, "k_p2_mism", hipLaunchKernelGGL(k_p2_mism, dim3(2048), dim3(256), 0, s, *R, *P));
+        }
     }
     if (link_eager) uvc_launch_link_complete(R, P, F.split_windows, UVC_LINK_ALL, nullptr, 0, 1, 0, "k_p2_fast_link", prof, s);   // UVCGPU_LINK=eager and the generic forms: where the LINK pass ran before 6-r8
     if (side) {

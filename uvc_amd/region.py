@@ -303,6 +303,17 @@ class Region:
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
         self._check(fn(self.h))
 
+    def debug_mis_queue(self):
+        """For tests: the mismatch queue of the last accumulate (uvcgpu_region_debug_mis_queue) -> (rows [n][rank, epos, symval] in the
+        device's order, the device's count n, the count set_reads made)."""
+        fn = getattr(self.lib.dll, self.lib.prefix + "region_debug_mis_queue")
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        n, total = C.c_int64(-1), C.c_int64(-1)
+        self._check(fn(self.h, None, 0, C.byref(n), C.byref(total)))
+        rows = np.empty((max(int(n.value), 0), 3), dtype=np.int32)
+        self._check(fn(self.h, rows.ctypes.data, rows.shape[0], C.byref(n), C.byref(total)))
+        return rows[:max(min(int(n.value), rows.shape[0]), 0)], int(n.value), int(total.value)
+
     def read_quals(self, n_bases):
         fn = getattr(self.lib.dll, self.lib.prefix + "region_read_quals")
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]
