@@ -841,6 +841,57 @@ int uvcgpu_region_clip_mates(uvcgpu_region_t *r, const int64_t *sites /* [n_site
 const char *uvcgpu_clip_mate_site_name(int32_t id);      /* "site" .. "clusters_kept"; NULL for an id outside 0..UVC_NCLIPMSITE - 1 */
 const char *uvcgpu_clip_mate_cluster_name(int32_t id);   /* "site" .. "reserved"; NULL for an id outside 0..UVC_NCLIPMCLUS - 1 */
 const char *uvcgpu_clip_mate_class_name(int32_t klass);  /* "CONCORDANT" "OTHER_CONTIG" "SAME_STRAND" "FAR"; NULL for a class outside 0..3 */
+/* ---- family concordance of ranges: what the family consensus out-voted, and where the two strands of a duplex family disagree
+ * (uvc1-mi355x --family-concordance-out) ----
+ * Units and votes.  A unit u is one family-strand unit of the reads the handle holds (one fam_id and one strand: what the family passes of
+ *   accumulate walk), with the span [u.beg, u.end) those passes give it: u.beg the smallest pos of its alignments, u.end grown over its
+ *   alignments in read order as max(u.end, reference end of the alignment) + 1 (one more per alignment, as the reference's
+ *   fillTidBegEndFromAlns2 has it) and clamped to the region's end + 1.  con_u(p)[s] is the number of fragments of u that vote symbol s at
+ *   position p, as the family pass counts them: every fragment's own consensus of its alignments (BASE_QUALITY_MAX merge) votes once per
+ *   symbol type when 2 cc - ct of that consensus (cc: the value of its symbol, ct: of the whole type) is at least 1 and, for BASE, at least
+ *   fam_thres_highBQ_snv (updateByFiltering with thresholds (fam_thres_highBQ_snv, 0); the fragment's LINK consensus counts the reference
+ *   symbol once, its BASE consensus leaves N and the padded deletion out where microadjust_padded_deletion_flag says so for the platform).
+ *   The IonTorrent rules apply where the inferred platform is IonTorrent.
+ * Per unit and position p of [u.beg, u.end) inside a range: unit_positions += 1, and units_seen += 1 where p == u.beg.  Then per symbol
+ *   type (BASE: A..NN, 6 symbols; LINK: LINK_M..LINK_NN, 8 symbols) (cs, cc, ct) = the consensus of con_u(p) over the type: cs the first
+ *   symbol with the most votes, cc its votes, ct all votes of the type (fill_consensus without the reference-once and the padded rule: the
+ *   call in front of cDP12).  ct == 0 adds 1 to base_no_vote / link_no_vote and nothing else.  Otherwise k is the bin of ct among
+ *   1, 2, 3, 4, 5-7, 8-15, 16-31, 32+ (UVC_FAMCONC_NBIN = 8) and
+ *     BASE: the reference symbol of p is that of the handle; a position without one (the region's last position, `end`) or with one that
+ *       is not A/C/G/T adds 1 to base_no_ref and nothing else.  Otherwise refclass = 0 when cs is the reference symbol, else 1, and
+ *       base[refclass][k][cs][s] += con_u(p)[s] for the six symbols s (the diagonal: the agreeing votes), base_pos[refclass][k][0] += 1 and
+ *       base_pos[refclass][k][1] += 1 when cc == ct (unanimous).
+ *     LINK: link[k][cs][s] += con_u(p)[s] for the eight symbols and link_pos[k][0..1] the same way; no reference gate.
+ * Duplex families: those the duplex pass of accumulate walks -- fam_dflag bit 1 set and both strand units present.  Per family and position
+ *   p of [min(beg0, beg1), max(end0, end1)) inside a range, and per symbol type, v_j is the vote unit j (j = its strand) casts in the
+ *   duplex pass: the cs of the consensus of con_j(p) over the type (BASE: over A..T only where the padded-deletion rule applies) when
+ *   max(2 cc, ct) - ct >= 1, else "none"; a unit that does not cover p: "none".  (none, none) adds 1 to duplex_no_vote (once per type) and
+ *   nothing else.  Otherwise LINK: dup_link[v0][v1] += 1 (9 x 9, vote 8 = none); BASE: a position without an A/C/G/T reference symbol adds
+ *   1 to duplex_base_no_ref, every other one dup_base[ref][v0][v1] += 1 (4 x 7 x 7, vote 6 = none).  The cells off the diagonal with two
+ *   votes are the strand conflicts the duplex pass settles silently (the smaller symbol wins).
+ * One row of UVC_FAMCONC_ROW int64 per call (sections: include/uvc_famconcord.def), every word a sum over the (unit, position) pairs whose
+ * position lies in a range: rows of disjoint position sets add.  Integers only, the same bits from call to call.
+ * A family is seen as the region it was grouped in sees it: next to a tile cut it may lack fragments that the fetch of the neighbouring
+ * tile holds, so its votes -- and sums over tiles -- depend on the cuts. */
+enum UvcFamConc { UVC_FAMCONC_base = 0, UVC_FAMCONC_base_pos, UVC_FAMCONC_link, UVC_FAMCONC_link_pos, UVC_FAMCONC_dup_base, UVC_FAMCONC_dup_link,
+                  UVC_FAMCONC_counters, UVC_NFAMCONC };
+enum { UVC_FAMCONC_NBIN = 8, UVC_FAMCONC_NBASE = 6, UVC_FAMCONC_NLINK = 8, UVC_FAMCONC_BASE = 0, UVC_FAMCONC_BASE_POS = 576 /* 2 * 8 * 6 * 6 */,
+       UVC_FAMCONC_LINK = 608 /* + 2 * 8 * 2 */, UVC_FAMCONC_LINK_POS = 1120 /* + 8 * 8 * 8 */, UVC_FAMCONC_DUP_BASE = 1136 /* + 8 * 2 */,
+       UVC_FAMCONC_DUP_LINK = 1332 /* + 4 * 7 * 7 */, UVC_FAMCONC_COUNTERS = 1413 /* + 9 * 9 */, UVC_FAMCONC_ROW = 1429 /* + 16 */ };
+enum UvcFamConcCounter { UVC_FAMCONCC_units_seen = 0, UVC_FAMCONCC_unit_positions, UVC_FAMCONCC_base_no_vote, UVC_FAMCONCC_link_no_vote,
+                         UVC_FAMCONCC_base_no_ref, UVC_FAMCONCC_duplex_no_vote, UVC_FAMCONCC_duplex_base_no_ref,
+                         UVC_FAMCONCC_reserved /* 7..15: 0 */, UVC_NFAMCONCC = 16 };
+/* The votes are evaluated again on the device, once per (unit, position) of the ranges, from what accumulate leaves beside the planes: the
+ * fragment records in position order, the contribution table of the InDel reads and the InDel-phred track as P1 edited it.  So the call
+ * is legal after uvcgpu_region_accumulate of the current reads, until uvcgpu_region_set_reads / _set_reads_device, _reset or
+ * _correct_bq end that accumulate -- after any score, a releasing one too (it gives up the planes, which the call does not read), and
+ * while a score stream is open.  A handle whose set_reads brought zero reads has nothing to accumulate: there the call gives a row of zeros.
+ *   Ranges: the rules and refusals of uvcgpu_region_coverage (zero-based, half open, sorted, disjoint, inside [beg, end + 1)).
+ *   UVCGPU_EINVAL before any launch, with a message that names the reason (a range by its index): a NULL handle; called before set_reads,
+ *   after a reset, or before the accumulate of the current reads; NULL ranges or out; n_ranges < 1; a range that is empty or reversed,
+ *   outside the region, or begins in front of its predecessor's end.  `out` is written only by a call that returns 0. */
+int uvcgpu_region_family_concordance(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, int64_t *out /* [UVC_FAMCONC_ROW] */);
+const char *uvcgpu_family_concordance_section_name(int32_t id);   /* "base" .. "counters"; NULL for an id outside 0..UVC_NFAMCONC - 1 */
 /* ---- callable-region intervals of ranges of the accumulated region (uvc1-mi355x --callable-out) ----
  * m_k(p) is measure k of uvcgpu_region_coverage at position p (UvcCoverageMeasure).  The mask of p has bit k = UVC_CALL_LOW_<measure k> set
  * when min_depth[k] > 0 and m_k(p) < min_depth[k], UVC_CALL_EXCESS_aDP when max_aDP > 0 and m_0(p) > max_aDP, UVC_CALL_NO_COVERAGE when

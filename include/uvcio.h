@@ -193,6 +193,23 @@ int uvcio_errprofile_open(uvcio_errprofile_t **out, const char *const *level_nam
 int uvcio_errprofile_add(uvcio_errprofile_t *e, const int64_t *profile /* [n_levels][712] */);
 int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *path);
 void uvcio_errprofile_close(uvcio_errprofile_t *e);
+/* ---- the family concordance report (uvc1-mi355x --family-concordance-out) ----
+ * The sum of the rows that tiles report (uvcgpu_region_family_concordance: 1429 int64; include/uvc_famconcord.def).  Rows of disjoint
+ * position sets add; add locks, so pieces come in any order and from any thread.
+ * write: "##family_concordance_sections=" with name:first:words of every section, "##family_concordance_bins=1,2,3,4,5-7,8-15,16-31,32+",
+ * "#counter\tcount" and one line per counter (units_seen unit_positions base_no_vote link_no_vote base_no_ref duplex_no_vote
+ * duplex_base_no_ref); "#summary\tkind\tbin\tminority_votes\tvotes" and one line per bin and kind (BASE: both reference classes; LINK): the
+ * votes off the diagonal and all votes of the bin, two integers and no ratio; then one "#<KIND>\t<columns>" line per kind and one line per cell that is not 0:
+ *   BASE <TAB> refclass (REF, ALT) <TAB> bin <TAB> consensus <TAB> vote <TAB> count        LINK <TAB> bin <TAB> consensus <TAB> vote <TAB> count
+ *   BASE_POS <TAB> refclass <TAB> bin <TAB> positions <TAB> unanimous                      LINK_POS <TAB> bin <TAB> positions <TAB> unanimous
+ *   DUPLEX_BASE <TAB> ref <TAB> strand0 <TAB> strand1 <TAB> count                          DUPLEX_LINK <TAB> strand0 <TAB> strand1 <TAB> count
+ * with the symbols A C G T N NN and M D3P D2 D1 I3P I2 I1 NN, and NONE for a strand without a vote.  Integers only; a path that ends in
+ * .gz is written block-gzipped (uvcio_bgzf_write_*). */
+typedef struct uvcio_famconcord uvcio_famconcord_t;
+int uvcio_famconcord_open(uvcio_famconcord_t **out);
+int uvcio_famconcord_add(uvcio_famconcord_t *f, const int64_t *row /* [1429] */);
+int uvcio_famconcord_write(const uvcio_famconcord_t *f, const char *path);
+void uvcio_famconcord_close(uvcio_famconcord_t *f);
 /* ---- the UMI family report (uvc1-mi355x --family-stats-out) ----
  * What tiles report with uvcgpu_region_family_stats (rows of 365 int64: the TARGET block of 4 counters, the FIRST block of 8 counters,
  * size[64] and strands[17][17]), kept per target and per run.  Targets are added in report order before the pieces; add_piece adds the

@@ -205,6 +205,14 @@ FAMILY_STATS = [n for n, _, _ in FAMSTAT_SECTIONS]
 assert [ENUMS["UVC_FAMSTAT_" + n] for n in FAMILY_STATS] == list(range(ENUMS["UVC_NFAMSTAT"]))
 assert sum(w for _, _, w in FAMSTAT_SECTIONS) == ENUMS["UVC_FAMSTAT_ROW"] and all(f == sum(w for _, _, w in FAMSTAT_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMSTAT_SECTIONS))
 
+# the sections of the family-concordance row in id order (UvcFamConc): the table of include/uvc_famconcord.def, checked against the header's enums
+FAMCONC_SECTIONS = _read_def("uvc_famconcord.def", "UVC_FAMCONC")
+FAMILY_CONCORDANCE = [n for n, _, _ in FAMCONC_SECTIONS]
+assert [ENUMS["UVC_FAMCONC_" + n] for n in FAMILY_CONCORDANCE] == list(range(ENUMS["UVC_NFAMCONC"]))
+assert sum(w for _, _, w in FAMCONC_SECTIONS) == ENUMS["UVC_FAMCONC_ROW"] and all(f == sum(w for _, _, w in FAMCONC_SECTIONS[:k]) for k, (_, f, _) in enumerate(FAMCONC_SECTIONS))
+assert [f for _, f, _ in FAMCONC_SECTIONS] == [ENUMS["UVC_FAMCONC_" + n.upper()] for n in FAMILY_CONCORDANCE] and FAMCONC_SECTIONS[-1][2] == ENUMS["UVC_NFAMCONCC"]
+FAMCONC_COUNTERS = [k[len("UVC_FAMCONCC_"):] for k, v in sorted(((k, v) for k, v in ENUMS.items() if k.startswith("UVC_FAMCONCC_")), key=lambda kv: kv[1])]
+
 # the sections of a fragment-profile row in id order (UvcFragProfSection): the table of include/uvc_fragprofile.def, checked against the header's enums
 FRAGPROF_SECTIONS = _read_def("uvc_fragprofile.def", "UVC_FRAGPROF")
 FRAGMENT_PROFILE = [n for n, _, _ in FRAGPROF_SECTIONS]

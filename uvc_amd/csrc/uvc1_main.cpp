@@ -39,12 +39,12 @@
 namespace {
 const int32_t MAX_INSERT_SIZE = 2000, MAX_STR_N_BASES = 100;   // common.hpp:63-64
 
-// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o, 4p, 4q with 4r), in the order their options are checked: of several faults the first in
+// The reports beside the VCF (DESIGN.md 4i, 4j, 4k, 4l, 4n, 4m, 4o, 4p, 4q with 4r, 4t), in the order their options are checked: of several faults the first in
 // this order is the one reported.
 // A row holds what the command line says of a report in more than one place: parse (the path, "a sub-option was given", the checks behind
 // the loop), split_pair (pair mode writes none) and main (the probe of the path).  A new report is a row here, an Opts store, a
 // *_of_tile and its open / write lines in main.
-enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, R_CLIPSITES, N_REPORTS };
+enum ReportId { R_COVERAGE, R_ERRPROF, R_FAMSTATS, R_CALLABLE, R_MSI, R_READPROF, R_FRAGPROF, R_SITEREADS, R_CLIPSITES, R_FAMCONC, N_REPORTS };
 struct ReportRow {
     const char *out;                 // --X-out PATH
     const char *subs[18];            // the options that only shape this report: each needs --X-out (the list ends with a null)
@@ -71,6 +71,7 @@ const ReportRow REPORTS[N_REPORTS] = {
                             "--clip-sites-junction-min-votes", "--clip-sites-junction-max-dist", "--clip-sites-junction-slop", "--clip-sites-mates", "--clip-sites-mate-window", "--clip-sites-mate-overhang",
                             "--clip-sites-mate-min-dist", "--clip-sites-mate-max-gap", "--clip-sites-mate-min-pairs" }, nullptr, "every shard would write the sites of its tiles", "every tile would report its sites that many times",
       "clip sites report", nullptr },
+    { "--family-concordance-out", { nullptr }, nullptr, "every shard would write a part of the row", "every tile would be counted that many times", "family concordance report", nullptr },
 };
 // the row that `name` is an option of, or -1; *sub: which of the row's sub-options, -1 for --X-out itself
 int report_of(const std::string &name, int *sub) {
@@ -99,6 +100,7 @@ struct Opts {
     UvcErrorProfileRequest errprof_req{ 20, 50 };   // --error-profile-min-depth, --error-profile-max-alt-permille
     uvcio_errprofile_t *errprof = nullptr;   // --error-profile-out: the run's table, summed over the tiles by the workers (main)
     uvcio_famstats_t *fam = nullptr;   // --family-stats-out: the report's store, filled by the workers (main)
+    uvcio_famconcord_t *famconc = nullptr;   // --family-concordance-out: the run's row, summed over the tiles by the workers (main)
     UvcCallableRequest call_req = [] { UvcCallableRequest q{}; q.min_depth[UVC_COV_cDP12] = 20; return q; }();   // --callable-min-depth, --callable-max-aDP
     uvcio_callable_t *callable = nullptr;   // --callable-out: the BED's store, filled by the workers (main)
     std::vector<int64_t> call_contig_target;   // without a BED file: per contig the store's target of its called span (-1: not called)
@@ -166,6 +168,7 @@ const OptRow OPTS[] = {
     { "--error-profile-min-depth", O_CLI, false, "20", "with --error-profile-out: a position enters a level's bins only where the level's depth is at least this (1 or more)" },
     { "--error-profile-max-alt-permille", O_CLI, false, "50", "with --error-profile-out: a position whose largest non-reference count is above this many thousandths of the level's depth counts as variant and stays out of the bins (0..1000)" },
     { "--family-stats-out", O_CLI, false, "", "write the UMI family report here (tab-separated; block-gzipped when the name ends in .gz): over all targets the number of read families, fragments and alignments, the families seen on both strands, with a UMI, a duplex tag or the amplicon flag, the duplication rate, the family-size histogram (1 .. 64+) and the strand0 x strand1 size histogram (0 .. 16+), then per BED line, or per --family-stats-window, the families that overlap it -- the families exactly as this caller groups and consumes them, reduced on the device from each tile's family units.  The VCF does not depend on it" },
+    { "--family-concordance-out", O_CLI, false, "", "write the family concordance report here (tab-separated; block-gzipped when the name ends in .gz): what the consensus of every read family out-voted -- the votes of a family's fragments by consensus symbol, voted symbol and family depth (1, 2, 3, 4, 5-7, 8-15, 16-31, 32+), apart for positions whose consensus is the reference base and the others -- and where the two strands of a duplex family cast different votes, by reference base: the substitution spectrum of the errors the families corrected and the signature of single-strand damage.  The votes are evaluated again on the device behind each tile's accumulate, over the positions the tile owns.  The VCF does not depend on it" },
     { "--family-stats-window", O_CLI, false, "0", "with --family-stats-out and no BED file: the targets are windows of this many bp, aligned to multiples of it on each contig and clipped to the called span" },
     { "--callable-out", O_CLI, false, "", "write the callable regions here as BED lines contig, beg, end, class, target (tab-separated; block-gzipped when the name ends in .gz): every target -- BED line, or called contig span without a BED file -- cut into stretches of equal class, CALLABLE or the criteria the stretch fails (LOW_<depth>, EXCESS_aDP, NO_COVERAGE), classified on the device from the planes of each tile over the six depths of --coverage-out; #summary lines count the positions per class.  The VCF does not depend on it" },
     { "--callable-min-depth", O_CLI, false, "cDP12=20", "with --callable-out: NAME=N[,NAME=N...], the smallest depth a callable position has of each named depth (aDP bDP cDP1 cDP12 cDP2 dDP1; 0 or unnamed: not tested)" },
@@ -632,6 +635,14 @@ void errprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<in
     if (uvcgpu_region_error_profile(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), &o.errprof_req, prof)) die(uvcgpu_last_error());
     if (uvcio_errprofile_add(o.errprof, prof)) die(uvcio_last_error());
 }
+// --family-concordance-out: the row of the stretches one accumulated tile owns -- the list coverage_of_tile reports on, so every position
+// counts once across the tiles -- by one uvcgpu_region_family_concordance, added to the run's row.
+void family_concordance_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own) {
+    if (!owned_ranges(w, own)) return;
+    int64_t row[UVC_FAMCONC_ROW];
+    if (uvcgpu_region_family_concordance(w.reg, w.ranges.data(), (int64_t)w.ranges.size(), row)) die(uvcgpu_last_error());
+    if (uvcio_famconcord_add(o.famconc, row)) die(uvcio_last_error());
+}
 // --read-profile-out: the profile of the reads over the stretches one tile owns -- the list coverage_of_tile reports on -- by one
 // uvcgpu_region_read_profile after set_reads, added to the run's row.
 void readprofile_of_tile(Worker &w, const Opts &o, const std::vector<std::pair<int64_t, int64_t>> &own) {
@@ -851,11 +862,11 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     w.t_reads += now() - t0; t0 = now();
     if (o.fam && fam_pieces) family_stats_of_tile(w, o, fam_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --family-stats-out: the units of set_reads, before anything else
     if (o.fragprof && frag_pieces) fragment_profile_of_tile(w, o, frag_pieces, std::max<size_t>(n_merged, 1), ext_end);   // --fragment-profile-out: the fragments and units of set_reads
-    // --coverage-out, --error-profile-out, --callable-out, --read-profile-out, --site-reads-out: the positions this tile owns -- the [first, last_excl) that scoring and
+    // --coverage-out, --error-profile-out, --callable-out, --read-profile-out, --site-reads-out, --family-concordance-out: the positions this tile owns -- the [first, last_excl) that scoring and
     // uvcio_sites_fetch go by, without the end point t.end itself, which lies outside every target the tile was cut from (and which two regions of
     // the reference's cuts share).  The list depends on scored() alone: made here, in front of accumulate, for the report of the reads as well.
     std::vector<std::pair<int64_t, int64_t>> own; std::vector<int64_t> target_of, call_target_of;
-    if (o.cov || o.errprof || o.callable || o.readprof || o.msi || o.sitereads || o.clipsites) {
+    if (o.cov || o.errprof || o.callable || o.readprof || o.msi || o.sitereads || o.clipsites || o.famconc) {
         auto call_target = [&](const Tile &l) { return l.call_target >= 0 || !(o.callable || o.msi) ? l.call_target : o.call_contig_target[(size_t)l.tid]; };
         for (size_t q = 0; q < std::max<size_t>(n_merged, 1); q++) {   // (n_merged = 0: t0_ alone)
             const Tile &l = (&t0_)[q];
@@ -867,6 +878,7 @@ bool call_tile(Worker &w, const Opts &o, const UvcParams &P, const Tile &t0_, in
     if (uvcgpu_region_correct_bq(w.reg) || uvcgpu_region_accumulate(w.reg)) die(uvcgpu_last_error());
     if (o.cov) coverage_of_tile(w, o, own, target_of, cov_span);
     if (o.errprof) errprofile_of_tile(w, o, own);
+    if (o.famconc) family_concordance_of_tile(w, o, own);
     if (o.callable) callable_of_tile(w, o, own, call_target_of);
     if (o.msi) msi_of_tile(w, o, own, call_target_of, w.ref, ext_beg);
     if (o.sitereads) site_reads_of_tile(w, o, own, t, b, k);   // the corrected qualities: behind correct_bq
@@ -1510,6 +1522,7 @@ int main(int argc, char **argv) {
     if (wanted(R_READPROF) && uvcio_readprofile_open(&o.readprof, names_of(uvcgpu_read_class_name, UVC_READPROF_NCLASS).data(), o.readprof_req.min_mapq, o.readprof_req.min_depth, o.readprof_req.max_alt_permille)) die(uvcio_last_error());
     std::vector<CovSpan> fam_spans((size_t)nref);
     if (wanted(R_FAMSTATS) && uvcio_famstats_open(&o.fam)) die(uvcio_last_error());
+    if (wanted(R_FAMCONC) && uvcio_famconcord_open(&o.famconc)) die(uvcio_last_error());
     std::vector<CovSpan> frag_spans((size_t)nref);
     if (wanted(R_FRAGPROF) && uvcio_fragprofile_open(&o.fragprof, o.fragprof_req.min_mapq, o.fragprof_req.short_lo, o.fragprof_req.short_hi, o.fragprof_req.long_lo, o.fragprof_req.long_hi)) die(uvcio_last_error());
     if (wanted(R_CLIPSITES) && uvcio_clipsites_open(&o.clipsites, o.clipsites_req.min_mapq, o.clipsites_req.min_clip, o.clipsites_req.min_reads, o.clipsites_reads)) die(uvcio_last_error());
@@ -1575,6 +1588,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "uvc1-mi355x: %lld force-output sites from %s\n", (long long)uvcio_sites_count(sites), o.force_sites.c_str());
         o.sites = sites;
     }
+    // a report path that cannot be written fails here -- before a device is opened -- not behind the last tile
+    for (int r = 0; r < N_REPORTS; r++) if (!o.report[r].path.empty()) probe_create(REPORTS[r].out, o.report[r].path);
     if (uvcgpu_init(o.devices[0])) die(uvcgpu_last_error());
     reader_switches(o);
     // T/N: the tumor pass's records (rescue_variants_from_vcf, main.cpp:183-398)
@@ -1587,8 +1602,6 @@ int main(int argc, char **argv) {
     // output: header, then the lines of every tile in tile order
     uvcio_bgzf_writer_t *zw = nullptr;
     if (uvcio_bgzf_write_open(&zw, o.out.c_str(), 6)) die(uvcio_last_error());
-    // a report path that cannot be written fails here, not behind the last tile
-    for (int r = 0; r < N_REPORTS; r++) if (!o.report[r].path.empty()) probe_create(REPORTS[r].out, o.report[r].path);
     if (!o.no_header) {
         const std::string h = vcf_header(o, cmd, (tvcf && o.tumor_format) ? uvcio_tumor_vcf_sample_name(tvcf) : nullptr, G.cnames.data(), G.lens.data(), nref);
         if (uvcio_bgzf_write(zw, h.data(), (int64_t)h.size())) die(uvcio_last_error());
@@ -1648,6 +1661,7 @@ int main(int argc, char **argv) {
         finish(R_MSI, uvcio_msi_write(o.msi, path(R_MSI))); uvcio_msi_close(o.msi);
     }
     if (o.errprof) { finish(R_ERRPROF, uvcio_errprofile_write(o.errprof, path(R_ERRPROF))); uvcio_errprofile_close(o.errprof); }
+    if (o.famconc) { finish(R_FAMCONC, uvcio_famconcord_write(o.famconc, path(R_FAMCONC))); uvcio_famconcord_close(o.famconc); }
     if (o.readprof) { finish(R_READPROF, uvcio_readprofile_write(o.readprof, path(R_READPROF))); uvcio_readprofile_close(o.readprof); }
     if (o.fragprof) { finish(R_FRAGPROF, uvcio_fragprofile_write(o.fragprof, path(R_FRAGPROF))); uvcio_fragprofile_close(o.fragprof); }
     if (o.sitereads) { finish(R_SITEREADS, uvcio_sitereads_write(o.sitereads, path(R_SITEREADS))); uvcio_sitereads_close(o.sitereads); uvcio_sites_close(o.sitereads_list); }

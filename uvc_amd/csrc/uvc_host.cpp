@@ -119,7 +119,7 @@ struct uvcgpu_region {
     Buf<int32_t> d_score_fields{this}; int64_t *d_score_count = nullptr;   // (cap: records)
     Buf<uint8_t, true> h_stage{this};   // page-locked staging for the small per-call uploads of score (tumor keys, caller's alleles): never the caller's own pages
     Buf<int32_t> d_score_kept{this};   // UvcScoreRequest::kept_only: the compacted copy, same pitch as d_score_fields (cap: records)
-    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions, _clip_mates): range list + pieces on the device, page-locked result (grown on demand)
+    Buf<char> d_report{this}; Buf<char, true> h_report{this};   // the report calls (uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions, _clip_mates, _family_concordance): range list + pieces on the device, page-locked result (grown on demand)
     uvcgpu_score_stream *ss = nullptr;   // the streamed score of this handle: its two row sets and page-locked buffers outlive a stream (reused by the next one)
     // InDel allele tables of the last accumulate (built on first use by gap_tables)
     bool gap_ready = false;
@@ -1408,8 +1408,8 @@ int64_t uvcgpu_score_stream_footprint(const uvcgpu_region_t *r) {
     return b;
 }
 
-// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions and _clip_mates ----
-// What the eleven share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
+// ---- the report calls: uvcgpu_region_coverage, _error_profile, _family_stats, _callable, _read_profile, _msi, _fragment_profile, _site_reads, _clip_sites, _clip_junctions, _clip_mates and _family_concordance ----
+// What the twelve share.  Each is synchronous: a checked list of sorted, disjoint ranges (the site call: of ascending sites) goes up through the staging buffer into the head of
 // the handle's report buffer, the kernels write behind it, and the result comes home through the page-locked report buffer.
 
 // The state a call needs.  planes_to ("reduce", "classify"): a reader of the accumulated planes; NULL: a reader of the family units, which
@@ -1420,6 +1420,15 @@ static int report_guard(const uvcgpu_region_t *r, const std::string &call, const
     if (!r->accumulated) return fail(UVCGPU_EINVAL, call + " before accumulate: there are no planes to " + planes_to);
     if (r->state_released) return fail(UVCGPU_EINVAL, call + " after the planes were released by the last score (UvcScoreRequest::release_state): call it before that score");
     if (stream_is_open(r)) return fail(UVCGPU_EINVAL, call + " while a score stream is open on this handle (the stream may release the planes): call it before uvcgpu_region_score_stream_begin");
+    return 0;
+}
+// The state of the one call that evaluates the units' votes again (uvcgpu_region_family_concordance).  It reads what accumulate leaves beside
+// the planes -- RegionDev::ffast / frag_rank, the contribution table, the InDel-phred track as P1b edited it -- and none of the planes: only
+// set_reads, reset and correct_bq end its window (each clears `accumulated`), a releasing score and an open score stream do not.
+static int report_guard_votes(const uvcgpu_region_t *r, const std::string &call) {
+    if (!r) return fail(UVCGPU_EINVAL, call + ": null region");
+    if (!r->reads_given) return fail(UVCGPU_EINVAL, call + " before set_reads: the region has no family units yet (uvcgpu_region_set_reads or _set_reads_device of this region comes first)");
+    if (r->has_reads && !r->accumulated) return fail(UVCGPU_EINVAL, call + " before accumulate: there are no fragment records and no contribution table to take the votes from (uvcgpu_region_accumulate of the current reads comes first)");
     return 0;
 }
 static int range_count(const std::string &call, int64_t n_ranges, int64_t most) {
@@ -1568,6 +1577,28 @@ int uvcgpu_region_family_stats(uvcgpu_region_t *r, const UvcFamilyRange *ranges,
     return guarded("uvcgpu_region_family_stats", [&] { return uvcgpu_region_family_stats_impl(r, ranges, n_ranges, out); });
 }
 const char *uvcgpu_family_stat_name(int32_t id) { return uvc_famstats_name(id); }
+
+// ---- family concordance of ranges (the end of uvc_kernels_acc.hip): [table] [row] [shard copies] ----
+static int uvcgpu_region_family_concordance_impl(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, int64_t *out) {
+    { int rc1 = report_guard_votes(r, "family_concordance"); if (rc1) return rc1; }
+    if (!ranges || !out) return fail(UVCGPU_EINVAL, "family_concordance: ranges and out must not be NULL");
+    { int rc1 = range_count("family_concordance", n_ranges, INT32_MAX >> 1); if (rc1) return rc1; }
+    std::vector<UvcRangeRow> tab; int64_t n_total;
+    { int rc1 = range_table(r, "family_concordance", ranges, n_ranges, tab, n_total); if (rc1) return rc1; }
+    const size_t out_bytes = sizeof(int64_t) * UVC_FAMCONC_ROW;
+    if (!r->has_reads) { memset(out, 0, out_bytes); return 0; }   // set_reads with zero reads: no unit, nothing to launch
+    ReportLayout L;
+    const size_t o_tab = L.take(sizeof(UvcRangeRow) * tab.size()), o_row = L.take(out_bytes), o_scratch = L.take(sizeof(int64_t) * (size_t)uvc_famconcord_scratch_cells());
+    { int rc1 = report_begin(r, L, out_bytes, "family concordance", tab.data(), sizeof(UvcRangeRow) * tab.size()); if (rc1) return rc1; }
+    long long *d_row = (long long *)(r->d_report + o_row);
+    uvc_launch_famconcord(&r->R, &r->P, (const UvcRangeRow *)(r->d_report + o_tab), (int)n_ranges, r->d_dup_units, r->n_dup, r->d_dup_off, r->n_dup_work, d_row,
+                          (long long *)(r->d_report + o_scratch), &r->prof, r->stream);
+    return report_result(r, d_row, out, out_bytes, true);
+}
+int uvcgpu_region_family_concordance(uvcgpu_region_t *r, const UvcCoverageRange *ranges, int64_t n_ranges, int64_t *out) {
+    return guarded("uvcgpu_region_family_concordance", [&] { return uvcgpu_region_family_concordance_impl(r, ranges, n_ranges, out); });
+}
+const char *uvcgpu_family_concordance_section_name(int32_t id) { return uvc_famconcord_section_name(id); }
 
 // ---- fragment length and end-motif profile of ranges (uvc_fragprofile.hip): [ranges] [TARGET rows, the profile row] [profile copies]
 // [fragment spans] [unit template spans] ----

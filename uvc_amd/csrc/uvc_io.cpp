@@ -1349,6 +1349,89 @@ extern "C" int uvcio_errprofile_write(const uvcio_errprofile_t *e, const char *p
 }
 extern "C" void uvcio_errprofile_close(uvcio_errprofile_t *e) { delete e; }
 
+// ---------------------------------------------------------------- the family concordance report ----
+// the row layout is that of uvcgpu_region_family_concordance (UVC_FAMCONC_* of uvcgpu.h, include/uvc_famconcord.def); the reserved counters are not written
+struct uvcio_famconcord {
+    std::vector<int64_t> sum;   // [UVC_FAMCONC_ROW]
+    std::mutex mu;
+};
+extern "C" int uvcio_famconcord_open(uvcio_famconcord_t **out) {
+    if (!out) return fail(UVCGPU_EINVAL, "family concordance report: bad argument");
+    uvcio_famconcord *f = new uvcio_famconcord;
+    f->sum.assign((size_t)UVC_FAMCONC_ROW, 0);
+    *out = f;
+    return 0;
+}
+extern "C" int uvcio_famconcord_add(uvcio_famconcord_t *f, const int64_t *row) {
+    if (!f || !row) return fail(UVCGPU_EINVAL, "family concordance report: bad argument");
+    std::lock_guard<std::mutex> g(f->mu);
+    for (size_t i = 0; i < f->sum.size(); i++) f->sum[i] += row[i];
+    return 0;
+}
+extern "C" int uvcio_famconcord_write(const uvcio_famconcord_t *f, const char *path) {
+    if (!f || !path || !*path) return fail(UVCGPU_EINVAL, "family concordance report: bad argument");
+    static const struct { const char *name; int first, words; } SECTIONS[] = {
+#define UVC_FAMCONC(name, first, words) { #name, first, words },
+#include "uvc_famconcord.def"
+#undef UVC_FAMCONC
+    };
+    static const char *const COUNTERS[UVC_FAMCONCC_reserved] = { "units_seen", "unit_positions", "base_no_vote", "link_no_vote", "base_no_ref", "duplex_no_vote", "duplex_base_no_ref" };
+    static const char *const BINS[UVC_FAMCONC_NBIN] = { "1", "2", "3", "4", "5-7", "8-15", "16-31", "32+" };
+    static const char *const BASE_SYM[UVC_FAMCONC_NBASE + 1] = { "A", "C", "G", "T", "N", "NN", "NONE" };
+    static const char *const LINK_SYM[UVC_FAMCONC_NLINK + 1] = { "M", "D3P", "D2", "D1", "I3P", "I2", "I1", "NN", "NONE" };
+    static const char *const REFCLASS[2] = { "REF", "ALT" };
+    const int64_t *v = f->sum.data();
+    const int NB = UVC_FAMCONC_NBASE, NL = UVC_FAMCONC_NLINK, NK = UVC_FAMCONC_NBIN;
+    std::string text = "##family_concordance_sections=";
+    for (size_t k = 0; k < sizeof(SECTIONS) / sizeof(SECTIONS[0]); k++) text += std::string(k ? "," : "") + SECTIONS[k].name + ":" + std::to_string(SECTIONS[k].first) + ":" + std::to_string(SECTIONS[k].words);
+    text += "\n##family_concordance_bins=";
+    for (int k = 0; k < NK; k++) text += std::string(k ? "," : "") + BINS[k];
+    text += "\n#counter\tcount\n";
+    for (int k = 0; k < UVC_FAMCONCC_reserved; k++) text += std::string(COUNTERS[k]) + "\t" + std::to_string(v[UVC_FAMCONC_COUNTERS + k]) + "\n";
+    text += "#summary\tkind\tbin\tminority_votes\tvotes\n";
+    for (int k = 0; k < NK; k++) {   // the minority share of a bin as two integers
+        int64_t all = 0, diag = 0;
+        for (int rc = 0; rc < 2; rc++) for (int cs = 0; cs < NB; cs++) for (int s = 0; s < NB; s++) {
+            const int64_t c = v[UVC_FAMCONC_BASE + ((rc * NK + k) * NB + cs) * NB + s];
+            all += c; if (cs == s) diag += c;
+        }
+        text += std::string("#summary\tBASE\t") + BINS[k] + "\t" + std::to_string(all - diag) + "\t" + std::to_string(all) + "\n";
+    }
+    for (int k = 0; k < NK; k++) {
+        int64_t all = 0, diag = 0;
+        for (int cs = 0; cs < NL; cs++) for (int s = 0; s < NL; s++) { const int64_t c = v[UVC_FAMCONC_LINK + (k * NL + cs) * NL + s]; all += c; if (cs == s) diag += c; }
+        text += std::string("#summary\tLINK\t") + BINS[k] + "\t" + std::to_string(all - diag) + "\t" + std::to_string(all) + "\n";
+    }
+    text += "#BASE\trefclass\tbin\tconsensus\tvote\tcount\n#BASE_POS\trefclass\tbin\tpositions\tunanimous\n#LINK\tbin\tconsensus\tvote\tcount\n#LINK_POS\tbin\tpositions\tunanimous\n"
+            "#DUPLEX_BASE\tref\tstrand0\tstrand1\tcount\n#DUPLEX_LINK\tstrand0\tstrand1\tcount\n";
+    for (int rc = 0; rc < 2; rc++) for (int k = 0; k < NK; k++) for (int cs = 0; cs < NB; cs++) for (int s = 0; s < NB; s++) {
+        const int64_t c = v[UVC_FAMCONC_BASE + ((rc * NK + k) * NB + cs) * NB + s];
+        if (c) text += std::string("BASE\t") + REFCLASS[rc] + "\t" + BINS[k] + "\t" + BASE_SYM[cs] + "\t" + BASE_SYM[s] + "\t" + std::to_string(c) + "\n";
+    }
+    for (int rc = 0; rc < 2; rc++) for (int k = 0; k < NK; k++) {
+        const int64_t *c = v + UVC_FAMCONC_BASE_POS + (rc * NK + k) * 2;
+        if (c[0] || c[1]) text += std::string("BASE_POS\t") + REFCLASS[rc] + "\t" + BINS[k] + "\t" + std::to_string(c[0]) + "\t" + std::to_string(c[1]) + "\n";
+    }
+    for (int k = 0; k < NK; k++) for (int cs = 0; cs < NL; cs++) for (int s = 0; s < NL; s++) {
+        const int64_t c = v[UVC_FAMCONC_LINK + (k * NL + cs) * NL + s];
+        if (c) text += std::string("LINK\t") + BINS[k] + "\t" + LINK_SYM[cs] + "\t" + LINK_SYM[s] + "\t" + std::to_string(c) + "\n";
+    }
+    for (int k = 0; k < NK; k++) {
+        const int64_t *c = v + UVC_FAMCONC_LINK_POS + k * 2;
+        if (c[0] || c[1]) text += std::string("LINK_POS\t") + BINS[k] + "\t" + std::to_string(c[0]) + "\t" + std::to_string(c[1]) + "\n";
+    }
+    for (int r = 0; r < 4; r++) for (int a = 0; a <= NB; a++) for (int b = 0; b <= NB; b++) {
+        const int64_t c = v[UVC_FAMCONC_DUP_BASE + (r * (NB + 1) + a) * (NB + 1) + b];
+        if (c) text += std::string("DUPLEX_BASE\t") + BASE_SYM[r] + "\t" + BASE_SYM[a] +"\t" + BASE_SYM[b] + "\t" + std::to_string(c) + "\n";
+    }
+    for (int a = 0; a <= NL; a++) for (int b = 0; b <= NL; b++) {
+        const int64_t c = v[UVC_FAMCONC_DUP_LINK + a * (NL + 1) + b];
+        if (c) text += std::string("DUPLEX_LINK\t") + LINK_SYM[a] + "\t" + LINK_SYM[b] + "\t" + std::to_string(c) + "\n";
+    }
+    return write_text(path, text);
+}
+extern "C" void uvcio_famconcord_close(uvcio_famconcord_t *f) { delete f; }
+
 // ---------------------------------------------------------------- the read profile ----
 // the row layout is that of uvcgpu_region_read_profile (UVC_READPROF_* of uvcgpu.h, include/uvc_readprofile.def); the reserved words are not written
 struct uvcio_readprofile {

@@ -38,6 +38,8 @@
 // The reference rules that several of them share (pair consensus, assay predicates, ...) stand once in uvc_rules.h; record words and flag bits go by the names of uvc_device.h.
 #include "uvc_launch.h"
 #include "uvc_collectives.h"
+#include "uvc_report_dev.h"   // the family-concordance kernels at the end tally like the report kernels
+#include <algorithm>
 #include <stdlib.h>
 #include <string.h>
 
@@ -3759,6 +3761,219 @@ extern "C" void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, co
     if (n_cand <= 0) return;
     if (units) hipLaunchKernelGGL(k_hap_units, dim3((unsigned)n_cand), dim3(64), 0, s, *R, *P, *H, n_cand);
     else hipLaunchKernelGGL(k_hap_frags, dim3((unsigned)n_cand), dim3(64), 0, s, *R, *P, *H, n_cand);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Family concordance (uvcgpu_region_family_concordance; the definitions are in uvcgpu.h).  The votes of a unit at a position
+// are stored nowhere once P4 has taken their consensus, so the report evaluates them again with the generic per-position form
+// (unit_counts), as the haplotype links above do: off the accumulate path, only for the positions inside the caller's ranges.
+//   k_famconc_units: one wave per unit, a lane per position of a 64-position window of its span, the waves of the grid striding over ALL
+//     units in unit order (neighbouring waves read neighbouring fragments).  Lone single-fragment units take the same grid: they too need
+//     the fragment's consensus symbol at every position, so a kernel of their own would save no evaluation.
+//   k_famconc_duplex: one lane per (duplex family, position) of the work list of k_duplex (dup_units, dup_off, the same binary search).
+// Both tally into a block's LDS copy of the row (11 432 B beside 14 336 B of vote counters): +1 words through merge_add / count_lanes, the
+// vote sums through famconc_add, which sums the lanes of equal cell first.  A block flushes its non-zero words into one of `shards` global
+// copies, uvc_launch_sum_fold adds the copies: 64-bit integer adds only, the same bits from call to call.
+// ------------------------------------------------------------------------------------------------
+namespace {
+enum {
+#define UVC_FAMCONC(name, first, words) FCROW_##name,
+#include "uvc_famconcord.def"
+#undef UVC_FAMCONC
+    FCROW_N
+};
+static_assert(FCROW_N == UVC_NFAMCONC, "include/uvc_famconcord.def and UvcFamConc of uvcgpu.h list the same sections");
+#define UVC_FAMCONC(name, first, words) static_assert((int)FCROW_##name == (int)UVC_FAMCONC_##name, "uvc_famconcord.def order = UvcFamConc order");
+#include "uvc_famconcord.def"
+#undef UVC_FAMCONC
+constexpr UvcSection FC_SECTIONS[UVC_NFAMCONC] = {
+#define UVC_FAMCONC(name, first, words) { #name, first, words },
+#include "uvc_famconcord.def"
+#undef UVC_FAMCONC
+};
+static_assert(uvc_sections_tile(FC_SECTIONS, UVC_FAMCONC_ROW), "the sections of uvc_famconcord.def tile the row");
+#define FC_BASE_VOTES (UVC_FAMCONC_NBASE + 1)   // a strand's BASE vote in the duplex pass: A..NN or none
+#define FC_LINK_VOTES (UVC_FAMCONC_NLINK + 1)
+static_assert(FC_SECTIONS[UVC_FAMCONC_base].first == UVC_FAMCONC_BASE && FC_SECTIONS[UVC_FAMCONC_base].words == 2 * UVC_FAMCONC_NBIN * UVC_FAMCONC_NBASE * UVC_FAMCONC_NBASE
+              && FC_SECTIONS[UVC_FAMCONC_base_pos].first == UVC_FAMCONC_BASE_POS && FC_SECTIONS[UVC_FAMCONC_base_pos].words == 2 * UVC_FAMCONC_NBIN * 2
+              && FC_SECTIONS[UVC_FAMCONC_link].first == UVC_FAMCONC_LINK && FC_SECTIONS[UVC_FAMCONC_link].words == UVC_FAMCONC_NBIN * UVC_FAMCONC_NLINK * UVC_FAMCONC_NLINK
+              && FC_SECTIONS[UVC_FAMCONC_link_pos].first == UVC_FAMCONC_LINK_POS && FC_SECTIONS[UVC_FAMCONC_link_pos].words == UVC_FAMCONC_NBIN * 2
+              && FC_SECTIONS[UVC_FAMCONC_dup_base].first == UVC_FAMCONC_DUP_BASE && FC_SECTIONS[UVC_FAMCONC_dup_base].words == 4 * FC_BASE_VOTES * FC_BASE_VOTES
+              && FC_SECTIONS[UVC_FAMCONC_dup_link].first == UVC_FAMCONC_DUP_LINK && FC_SECTIONS[UVC_FAMCONC_dup_link].words == FC_LINK_VOTES * FC_LINK_VOTES
+              && FC_SECTIONS[UVC_FAMCONC_counters].first == UVC_FAMCONC_COUNTERS && FC_SECTIONS[UVC_FAMCONC_counters].words == UVC_NFAMCONCC,
+              "the offsets and sizes of uvcgpu.h are those of uvc_famconcord.def");
+static_assert(UVC_BASE_NN - UVC_BASE_A + 1 == UVC_FAMCONC_NBASE && UVC_LINK_NN - UVC_LINK_M + 1 == UVC_FAMCONC_NLINK && UVC_BASE_A == 0, "the symbols of the two types are A..NN and LINK_M..LINK_NN");
+
+#define FC_MAX_SHARDS 16
+#define FC_MAX_BLOCKS 2048   // k_famconc_units: resident blocks of four waves that stride over the units (each flushes its row once)
+#define FC_MAX_STEPS 16      // k_famconc_duplex: groups of 256 cells a block tallies before it flushes
+
+// Is plane index x inside one of the caller's ranges?  g keeps the range of the last hit (its first plane index x0, its length next -
+// first): a lane walks up its unit, so most questions end at the first line.  Any lane alone.
+DEV bool famconc_in_range(UvcRangeCursor &g, const UvcRangeRow *tab, int n_ranges, int x) {
+    if (g.rid >= 0 && x >= g.x0 && x < g.x0 + (g.next - g.first)) return true;
+    int lo = 0, hi = n_ranges;   // the last range that begins at or in front of x (the ranges ascend)
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tab[mid].x0 <= x) lo = mid; else hi = mid; }
+    const int x0 = tab[lo].x0, first = tab[lo].first, next = tab[lo + 1].first;
+    if (x < x0 || x >= x0 + (next - first)) return false;
+    g.rid = lo; g.x0 = x0; g.first = first; g.next = next;
+    return true;
+}
+DEV int famconc_bin(int ct) { return ct <= 4 ? ct - 1 : (ct < 8 ? 4 : (ct < 16 ? 5 : (ct < 32 ? 6 : 7))); }   // 1, 2, 3, 4, 5-7, 8-15, 16-31, 32+
+// tab[key] += v for every lane with `on`, the lanes of equal key summed first (merge_add with a value): one round per distinct key among
+// the lanes, its first lane adds the sum.  Called by the whole wave, tab wave-uniform.
+DEV void famconc_add(unsigned long long *tab, int key, int v, bool on, int lane) {
+    unsigned long long left = __ballot(on);
+    while (left) {
+        const int lead = __ffsll((long long)left) - 1;
+        const int k = __shfl(key, lead);
+        const bool mine = (on && key == k);
+        const unsigned long long same = __ballot(mine);
+        const int sum = wave_sum(mine ? v : 0);
+        if (lane == lead) lds_add(tab + k, (unsigned long long)sum);
+        left &= ~same;
+    }
+}
+DEV void famconc_flush(const unsigned long long *row, int tid, int shards, unsigned long long *out) {
+    unsigned long long *dst = out + (size_t)(blockIdx.x % (unsigned)shards) * UVC_FAMCONC_ROW;
+    for (int j = tid; j < UVC_FAMCONC_ROW; j += 256) { const unsigned long long v = row[j]; if (v) atomicAdd(dst + j, v); }
+}
+
+__global__ void __launch_bounds__(256) k_famconc_units(RegionDev R, UvcParams P, const UvcRangeRow *tab, int n_ranges, int shards, unsigned long long *out) {
+    __shared__ unsigned long long row[UVC_FAMCONC_ROW];
+    __shared__ int con_s[NSYM][256];
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    for (int j = tid; j < UVC_FAMCONC_ROW; j += 256) row[j] = 0;
+    __syncthreads();
+    const LdsCounts<256> con = { &con_s[0][tid] };
+    const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
+    const int x_lo = tab[0].x0, x_hi = tab[n_ranges - 1].x0 + (tab[n_ranges].first - tab[n_ranges - 1].first);   // no range reaches outside [x_lo, x_hi)
+    unsigned long long *ctr = row + UVC_FAMCONC_COUNTERS;
+    UvcRangeCursor g;
+    for (int ui = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(tid >> 6); ui < R.n_fs; ui += (int)gridDim.x * 4) {   // wave-uniform: the unit record is a scalar load
+        const FsRec u = R.fss[ui];
+        if (u.end <= u.beg || u.end - R.beg <= x_lo || u.beg - R.beg >= x_hi) continue;
+        for (int i0 = 0; i0 < u.end - u.beg; i0 += 64) {
+            const int p = u.beg + i0 + lane, x = p - R.beg;
+            const bool act = (p < u.end && x >= 0 && (int64_t)x < R.npos && famconc_in_range(g, tab, n_ranges, x));
+            if (__ballot(act) == 0) continue;
+            if (act) unit_counts<false>(R, P, u, p, proton, con, con);
+            count_lanes(ctr + UVC_FAMCONCC_unit_positions, act, lane);
+            count_lanes(ctr + UVC_FAMCONCC_units_seen, act && p == u.beg, lane);
+            // reference symbols exist for plane indices 0 .. npos - 2 (the region's last position, `end`, has no reference base)
+            const int ref = ((act && (int64_t)x < R.npos - 1) ? (int)R.refsym[x] : UVC_BASE_N);
+            {   // BASE
+                int cs = 0, cc = 0, ct = 0;
+                if (act) fill_consensus(con, cs, cc, ct, UVC_BASE_SYMBOL, false, false);
+                count_lanes(ctr + UVC_FAMCONCC_base_no_vote, act && ct == 0, lane);
+                const bool voted = (act && ct > 0), on = (voted && ref <= UVC_BASE_T);
+                count_lanes(ctr + UVC_FAMCONCC_base_no_ref, voted && !on, lane);
+                const int cell = (on ? ((cs == ref ? 0 : 1) * UVC_FAMCONC_NBIN + famconc_bin(ct)) : 0);
+                for (int s = 0; s < UVC_FAMCONC_NBASE; s++) {
+                    const int v = (on ? con[UVC_BASE_A + s] : 0);
+                    famconc_add(row + UVC_FAMCONC_BASE, (cell * UVC_FAMCONC_NBASE + (on ? cs : 0)) * UVC_FAMCONC_NBASE + s, v, v != 0, lane);
+                }
+                merge_add(row + UVC_FAMCONC_BASE_POS, cell * 2, on, lane);
+                merge_add(row + UVC_FAMCONC_BASE_POS, cell * 2 + 1, on && cc == ct, lane);
+            }
+            {   // LINK
+                int cs = UVC_LINK_M, cc = 0, ct = 0;
+                if (act) fill_consensus(con, cs, cc, ct, UVC_LINK_SYMBOL, false, false);
+                count_lanes(ctr + UVC_FAMCONCC_link_no_vote, act && ct == 0, lane);
+                const bool on = (act && ct > 0);
+                const int cell = (on ? famconc_bin(ct) : 0);
+                for (int s = 0; s < UVC_FAMCONC_NLINK; s++) {
+                    const int v = (on ? con[UVC_LINK_M + s] : 0);
+                    famconc_add(row + UVC_FAMCONC_LINK, (cell * UVC_FAMCONC_NLINK + (on ? cs - UVC_LINK_M : 0)) * UVC_FAMCONC_NLINK + s, v, v != 0, lane);
+                }
+                merge_add(row + UVC_FAMCONC_LINK_POS, cell * 2, on, lane);
+                merge_add(row + UVC_FAMCONC_LINK_POS, cell * 2 + 1, on && cc == ct, lane);
+            }
+        }
+    }
+    __syncthreads();
+    famconc_flush(row, tid, shards, out);
+}
+
+__global__ void __launch_bounds__(256) k_famconc_duplex(RegionDev R, UvcParams P, const UvcRangeRow *tab, int n_ranges, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_work,
+                                                        int steps, int shards, unsigned long long *out) {
+    __shared__ unsigned long long row[UVC_FAMCONC_ROW];
+    __shared__ int con_s[NSYM][256];
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    for (int j = tid; j < UVC_FAMCONC_ROW; j += 256) row[j] = 0;
+    __syncthreads();
+    const LdsCounts<256> con = { &con_s[0][tid] };
+    const bool proton = (UVC_PLATFORM_IONTORRENT == P.inferred_sequencing_platform);
+    const bool padded_ignored = (P.microadjust_padded_deletion_flag & (proton ? 0x2 : 0x1)) != 0;
+    unsigned long long *ctr = row + UVC_FAMCONC_COUNTERS;
+    UvcRangeCursor g;
+    for (int c = 0; c < steps; c++) {
+        const int64_t w0 = ((int64_t)blockIdx.x * steps + c) * 256 + (tid & ~63);   // the wave's first cell of this step: wave-uniform
+        if (w0 >= n_work) break;
+        const int64_t w = w0 + lane;
+        bool act = (w < n_work);
+        int vb[2] = { UVC_FAMCONC_NBASE, UVC_FAMCONC_NBASE }, vl[2] = { UVC_FAMCONC_NLINK, UVC_FAMCONC_NLINK };   // the two strands' votes: none
+        int ref = 0;
+        if (act) {
+            int lo = 0, hi = n_dup;   // k_duplex's search: the last family whose first cell is <= w
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (dup_off[mid] <= w) lo = mid; else hi = mid; }
+            const FsRec u0 = R.fss[dup_units[lo]];   // the strand-0 unit of the family
+            const FsRec u1 = R.fss[u0.other_fs];
+            const int p = imin(u0.beg, u1.beg) + (int)(w - dup_off[lo]), x = p - R.beg;
+            act = (x >= 0 && (int64_t)x < R.npos && famconc_in_range(g, tab, n_ranges, x));
+            if (act) {
+                ref = ((int64_t)x < R.npos - 1 ? (int)R.refsym[x] : UVC_BASE_N);
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const FsRec &u = (k == 0 ? u0 : u1);
+                    if (p < u.beg || p >= u.end) continue;
+                    unit_counts<false>(R, P, u, p, proton, con, con);
+                    int cs, cc, ct;
+                    fill_consensus(con, cs, cc, ct, UVC_BASE_SYMBOL, false, padded_ignored);
+                    if (imax(cc * 2, ct) - ct >= 1) vb[k] = cs - UVC_BASE_A;
+                    fill_consensus(con, cs, cc, ct, UVC_LINK_SYMBOL, false, false);
+                    if (imax(cc * 2, ct) - ct >= 1) vl[k] = cs - UVC_LINK_M;
+                }
+            }
+        }
+        const bool none_b = (vb[0] == UVC_FAMCONC_NBASE && vb[1] == UVC_FAMCONC_NBASE), none_l = (vl[0] == UVC_FAMCONC_NLINK && vl[1] == UVC_FAMCONC_NLINK);
+        count_lanes(ctr + UVC_FAMCONCC_duplex_no_vote, act && none_b, lane);
+        count_lanes(ctr + UVC_FAMCONCC_duplex_no_vote, act && none_l, lane);
+        const bool on_b = (act && !none_b && ref <= UVC_BASE_T);
+        count_lanes(ctr + UVC_FAMCONCC_duplex_base_no_ref, act && !none_b && !on_b, lane);
+        merge_add(row + UVC_FAMCONC_DUP_BASE, on_b ? ((ref * FC_BASE_VOTES + vb[0]) * FC_BASE_VOTES + vb[1]) : 0, on_b, lane);
+        merge_add(row + UVC_FAMCONC_DUP_LINK, vl[0] * FC_LINK_VOTES + vl[1], act && !none_l, lane);
+    }
+    __syncthreads();
+    famconc_flush(row, tid, shards, out);
+}
+}   // namespace
+
+extern "C" const char *uvc_famconcord_section_name(int id) { return (id >= 0 && id < UVC_NFAMCONC) ? FC_SECTIONS[id].name : nullptr; }
+extern "C" int64_t uvc_famconcord_scratch_cells(void) { return (int64_t)FC_MAX_SHARDS * UVC_FAMCONC_ROW; }
+extern "C" void uvc_launch_famconcord(const RegionDev *R, const UvcParams *P, const UvcRangeRow *d_tab, int n_ranges, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
+                                      long long *d_out, long long *d_scratch, UvcProf *prof, hipStream_t s) {
+    if (n_ranges <= 0) return;
+    const long long blocks_u = (R->n_fs > 0 ? std::min<long long>(FC_MAX_BLOCKS, ((long long)R->n_fs + 3) / 4) : 0);
+    // a block of the duplex kernel keeps its row over `steps` groups of 256 cells: fewer flushes, as long as 1 024 blocks stay to fill the machine
+    const bool duplex = (n_dup > 0 && n_dup_work > 0);
+    const int steps = (int)std::max<int64_t>(1, std::min<int64_t>(FC_MAX_STEPS, n_dup_work / (256 * 1024)));
+    const long long blocks_d = (duplex ? (n_dup_work + 256LL * steps - 1) / (256LL * steps) : 0);
+    // from 128 blocks on the row is sharded (the flushes meet on the same 1 429 words), at most 16 copies
+    const int shards = (int)std::max<long long>(1, std::min<long long>(FC_MAX_SHARDS, std::max(blocks_u, blocks_d) / 64));
+    unsigned long long *d_parts = (unsigned long long *)(shards > 1 ? d_scratch : d_out);
+    hipMemsetAsync(d_parts, 0, sizeof(unsigned long long) * (size_t)shards * UVC_FAMCONC_ROW, s);
+    {
+        const int pi = uvc_prof_begin(prof, "k_famconc_units", s);
+        if (blocks_u > 0) hipLaunchKernelGGL(k_famconc_units, dim3((unsigned)blocks_u), dim3(256), 0, s, *R, *P, d_tab, n_ranges, shards, d_parts);
+        uvc_prof_end(prof, pi, s);
+    }
+    {
+        const int pi = uvc_prof_begin(prof, "k_famconc_duplex", s);   // with the fold of the copies
+        if (blocks_d > 0) hipLaunchKernelGGL(k_famconc_duplex, dim3((unsigned)blocks_d), dim3(256), 0, s, *R, *P, d_tab, n_ranges, dup_units, n_dup, dup_off, n_dup_work, steps, shards, d_parts);
+        if (shards > 1) uvc_launch_sum_fold(d_scratch, shards, UVC_FAMCONC_ROW, d_out, s);
+        uvc_prof_end(prof, pi, s);
+    }
 }
 
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }

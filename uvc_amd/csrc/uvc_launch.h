@@ -94,6 +94,13 @@ void uvc_launch_link_complete(const RegionDev *R, const UvcParams *P, int split,
                               const char *kname, UvcProf *prof, hipStream_t s);
 void uvc_launch_hap_cand(const RegionDev *R, const HapWork *H, int units, hipStream_t s);
 void uvc_launch_hap_events(const RegionDev *R, const UvcParams *P, const HapWork *H, int units, int n_cand, hipStream_t s);
+// uvcgpu_region_family_concordance: two stages (the units, the duplex families with the fold of the copies), each one entry of
+// uvcgpu_region_kernel_times.  d_tab = the n_ranges + 1 rows of UvcRangeRow; dup_units / dup_off: the duplex work list of
+// uvc_launch_accumulate; d_out: one row of UVC_FAMCONC_ROW words; d_scratch: uvc_famconcord_scratch_cells() words
+void uvc_launch_famconcord(const RegionDev *R, const UvcParams *P, const UvcRangeRow *d_tab, int n_ranges, const int32_t *dup_units, int n_dup, const int64_t *dup_off, int64_t n_dup_work,
+                           long long *d_out, long long *d_scratch, UvcProf *prof, hipStream_t s);
+const char *uvc_famconcord_section_name(int id);
+int64_t uvc_famconcord_scratch_cells(void);
 // ---- uvc_kernels_score.hip ----
 // The staged rows, their layouts and the sizes below come from one table (uvc_score_rows.h).  The caller zeroes the first
 // uvc_score_scratch_zero_bytes of in->scratch on the stream in front of uvc_launch_score / uvc_launch_score_gate; the record counts (all

@@ -234,6 +234,24 @@ class FamilyStats(_Store):
 
 
 
+class FamilyConcordance(_Store):
+    """uvcio_famconcord_*: the store behind uvc1-mi355x --family-concordance-out.  add() sums one row of Region.family_concordance (any
+    thread, any order: rows of disjoint position sets add); write() makes the text."""
+
+    def __init__(self):
+        d = self._bind("famconcord")
+        d.uvcio_famconcord_open.restype, d.uvcio_famconcord_open.argtypes = C.c_int, [C.POINTER(C.c_void_p)]
+        d.uvcio_famconcord_add.restype, d.uvcio_famconcord_add.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+        _check(d.uvcio_famconcord_open(C.byref(self.h)))
+
+    def add(self, row):
+        import numpy as np
+        row = np.ascontiguousarray(row, dtype=np.int64)
+        if row.shape != (1429,):
+            raise ValueError("a piece is one row of Region.family_concordance (1429 values)")
+        _check(dll().uvcio_famconcord_add(self.h, row.ctypes.data))
+
+
 class FragmentProfile(_Store):
     """uvcio_fragprofile_*: the store behind uvc1-mi355x --fragment-profile-out.  Targets are added in report order; add_piece takes one
     TARGET row of Region.fragment_profile for a target, add_profile sums the profile row of a call (any thread, any order); write() makes

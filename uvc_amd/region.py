@@ -26,6 +26,7 @@ class UvcError(RuntimeError):
 COVERAGE_MEASURES = _ffi.COVERAGE_MEASURES   # the measures of Region.coverage, in row order: aDP bDP cDP1 cDP12 cDP2 dDP1
 CALLABLE_BITS = _ffi.CALLABLE_BITS           # the bits of a mask of Region.callable, in bit order (include/uvc_callable.def)
 FAMILY_STATS = _ffi.FAMILY_STATS             # the sections of a row of Region.family_stats, in row order (include/uvc_famstats.def)
+FAMILY_CONCORDANCE = _ffi.FAMILY_CONCORDANCE   # the sections of the row of Region.family_concordance, in row order (include/uvc_famconcord.def)
 FRAGMENT_PROFILE = _ffi.FRAGMENT_PROFILE     # the sections of the profile row of Region.fragment_profile, in row order (include/uvc_fragprofile.def)
 READ_CLASSES = ["R1_fwd", "R1_rev", "R2_fwd", "R2_rev"]   # the read classes of Region.read_profile, in row order (uvcgpu_read_class_name)
 ERROR_LEVELS = _ffi.ERROR_LEVELS             # the evidence levels of Region.error_profile, in row order: bDP cDP1 cDP12 cDP2 dDP1
@@ -533,6 +534,20 @@ class Region:
         rows = [(int(q[0]), int(q[1]), int(q[2]) if len(q) > 2 else int(q[0]), int(q[3]) if len(q) > 3 else 0) for q in ranges]
         arr = (_ffi.UvcFamilyRange * max(len(rows), 1))(*[_ffi.UvcFamilyRange(*q) for q in rows])
         out = np.zeros((len(rows), _ffi.ENUMS["UVC_FAMSTAT_ROW"]), dtype=np.int64)
+        self._check(fn(self.h, arr, len(rows), out.ctypes.data))
+        return out
+
+    def family_concordance(self, ranges):
+        """uvcgpu_region_family_concordance: what the family consensus out-voted and where the strands of a duplex family disagree, over
+        `ranges` (as Region.coverage takes them).  int64 [UVC_FAMCONC_ROW], every word a sum over the (unit, position) pairs of the ranges:
+        base[refclass][bin][consensus][vote] and link[bin][consensus][vote] (the votes of a unit's fragments by the unit's consensus symbol
+        and the bin 1, 2, 3, 4, 5-7, 8-15, 16-31, 32+ of its vote total), base_pos / link_pos (positions, unanimous positions),
+        dup_base[ref][strand-0 vote][strand-1 vote] and dup_link (the two votes of the duplex pass, the last index: none) and 16 counters;
+        FAMILY_CONCORDANCE names the sections, uvcgpu.h has the rules.  The votes are evaluated again on the device: after accumulate() of
+        the current reads, whatever was scored since."""
+        fn = self._ranges_fn("region_family_concordance", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p])
+        arr, rows = _coverage_ranges(ranges)
+        out = np.zeros(_ffi.ENUMS["UVC_FAMCONC_ROW"], dtype=np.int64)
         self._check(fn(self.h, arr, len(rows), out.ctypes.data))
         return out
 
